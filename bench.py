@@ -21,10 +21,8 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # before the HIP runtime is loaded (manuscript_ocr_amd/__init__.py explains)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -64,6 +62,9 @@ def parse():
                     help="skip the three rocprofv3 --pmc child runs that measure roofline.traffic (FETCH_SIZE, WRITE_SIZE) and the MFMA-pipe utilisation for this line")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary lines (host pages / hipGraph replay / JPEG ingest, a few steps each after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (every rank's words: page, box, "
+                         "confidences, text) as DIR/<name>.npy, float64, at most 64 MB (a seeded sample of the words beyond that)")
     ap.add_argument("--serialize-streams", action="store_true",
                     help="run the sub-batch pipeline on ONE stream (no cross-stream kernel overlap): per-kernel profiling mode")
     return ap.parse_args()
@@ -206,6 +207,38 @@ def timed_region(run_steps, steps, warmup, sync, dist, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return out, dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records, with_text, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the words of the last timed step (dist.page_records form, all ranks) as float64 arrays, one row per word
+    in page / word order: page, word, polygon [4, 2], detection_confidence and, with_text, recognition_confidence (NaN when the
+    word was not recognised), text_length (-1 when not recognised) and text_codepoints (Unicode code points, 0-padded).  Past
+    limit_bytes, a fixed seeded sample of the rows (kept in order).  Returns {name: shape}."""
+    n = len(records)
+    arrs = {"page": np.array([r["page"] for r in records], dtype=np.float64),
+            "word": np.array([r["word"] for r in records], dtype=np.float64),
+            "polygon": np.array([r["polygon"] for r in records], dtype=np.float64).reshape(n, 4, 2),
+            "detection_confidence": np.array([r["det"] for r in records], dtype=np.float64)}
+    if with_text:
+        texts = [r["text"] for r in records]
+        width = max([len(t) for t in texts if t is not None], default=0)
+        codes = np.zeros((n, width), dtype=np.float64)
+        for i, t in enumerate(texts):
+            codes[i, :len(t or "")] = [ord(c) for c in t or ""]
+        arrs["recognition_confidence"] = np.array([np.nan if r["rec"] is None else r["rec"] for r in records], dtype=np.float64)
+        arrs["text_length"] = np.array([-1 if t is None else len(t) for t in texts], dtype=np.float64)
+        arrs["text_codepoints"] = codes
+    row_bytes = sum(a.nbytes // n for a in arrs.values()) if n else 0
+    if n and n * row_bytes > limit_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=limit_bytes // row_bytes, replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def emit(rank, res, fd):
@@ -383,6 +416,9 @@ def main():
     out, dt = timed_region(run_steps, a.steps, a.warmup, torch.cuda.synchronize, dist, "cuda")
     # the path's one real exchange: decoded strings/boxes of every rank gathered (RCCL when world > 1)
     records = gather_records([r for i, p in enumerate(out) for r in page_records(rank * NP + i, p)], torch.device("cuda", local))
+    if a.dump_outputs and rank == 0:
+        shapes = dump_outputs(a.dump_outputs, records, with_text=pipe is not None)
+        print(f"[bench] outputs of the last timed step written to {a.dump_outputs}: {shapes}", file=sys.stderr)
 
     total_pages = NP * a.steps * world
     words = [w for p in out for b in p.blocks for w in b.words]

@@ -124,7 +124,8 @@ local = [{"page": p, "word": 0, "text": "стр%d — ok" % p, "rec": 0.5 + p / 
 allr = gather_records(local, torch.device("cpu"))
 if rank == 0:
     print("RESULT" + json.dumps(allr, ensure_ascii=False))
-dist.barrier()
+# barrier as a CPU all_reduce: dist.barrier() asks torch for the accelerator, which starts the GPU runtime in every rank
+dist.all_reduce(torch.zeros(1))
 dist.destroy_process_group()
 '''
 
@@ -160,7 +161,8 @@ local = [{"page": p, "word": k, "text": "p%d/w%d é" % (p, k)} for p in range(lo
 allr = gather_records(local, torch.device("cpu"))
 if rank == 0:
     print("RESULT" + json.dumps({"recs": allr, "spans": [shard_range(n_pages, r, world) for r in range(world)]}, ensure_ascii=False))
-dist.barrier()
+# barrier as a CPU all_reduce: dist.barrier() asks torch for the accelerator, which starts the GPU runtime in every rank
+dist.all_reduce(torch.zeros(1))
 dist.destroy_process_group()
 '''
 
@@ -644,6 +646,37 @@ def test_bench_timed_region_world2_gloo(tmp_path):
     assert [x["page"] for x in res[0]["recs"]] == [0, 1, 2, 3] and res[0]["recs"][3]["text"] == "rank1-page1"
     assert json.loads(res[0]["line"])["n_gpus"] == 2 and res[1]["line"] == ""
     assert res[0]["shard"] == [0, 4] and res[1]["shard"] == [4, 7]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the records of the last timed step as float64 .npy files, one row per word in record order,
+    unrecognised words as NaN confidence / -1 length; over the byte limit, the same seeded sample of rows in every array."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    recs = [{"page": 0, "word": 0, "polygon": [[1.5, 2.0], [9.0, 2.0], [9.0, 7.25], [1.5, 7.25]], "det": 0.875, "text": "рукопись", "rec": 0.5},
+            {"page": 0, "word": 1, "polygon": [[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], "det": 0.25, "text": None, "rec": None},
+            {"page": 3, "word": 0, "polygon": [[4.0, 4.0], [5.0, 4.0], [5.0, 5.0], [4.0, 5.0]], "det": 1.0, "text": "ab", "rec": 1.0}]
+    shapes = bench.dump_outputs(str(tmp_path / "d"), recs, with_text=True)
+    got = {k: np.load(tmp_path / "d" / (k + ".npy")) for k in shapes}
+    assert all(a.dtype == np.float64 and list(a.shape) == shapes[k] for k, a in got.items())
+    assert got["page"].tolist() == [0, 0, 3] and got["word"].tolist() == [0, 1, 0]
+    assert got["polygon"].shape == (3, 4, 2) and got["polygon"][0, 2].tolist() == [9.0, 7.25]
+    assert got["detection_confidence"].tolist() == [0.875, 0.25, 1.0]
+    assert got["recognition_confidence"][0] == 0.5 and np.isnan(got["recognition_confidence"][1])
+    assert got["text_length"].tolist() == [8, -1, 2] and got["text_codepoints"].shape == (3, 8)
+    assert "".join(map(chr, got["text_codepoints"][0].astype(int))) == "рукопись" and got["text_codepoints"][2, 2:].sum() == 0
+    assert sorted(bench.dump_outputs(str(tmp_path / "e"), recs, with_text=False)) == ["detection_confidence", "page", "polygon", "word"]
+    many = [dict(recs[i % 3], page=i) for i in range(1000)]
+    row = 8 * (1 + 1 + 8 + 1 + 1 + 1 + 8)
+    a = bench.dump_outputs(str(tmp_path / "s1"), many, with_text=True, limit_bytes=100 * row)
+    b = bench.dump_outputs(str(tmp_path / "s2"), many, with_text=True, limit_bytes=100 * row)
+    assert a == b and a["page"] == [100] and a["text_codepoints"] == [100, 8]
+    p1, p2 = np.load(tmp_path / "s1" / "page.npy"), np.load(tmp_path / "s2" / "page.npy")
+    assert np.array_equal(p1, p2) and np.all(np.diff(p1) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "text_length.npy"), np.array([[8, -1, 2][int(p) % 3] for p in p1], dtype=np.float64))
+    assert sum(os.path.getsize(tmp_path / "s1" / (k + ".npy")) for k in a) <= 100 * row + 8 * 128  # + the .npy headers
 
 
 def test_attn_pack_split_host_layout_and_exactness():

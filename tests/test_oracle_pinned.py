@@ -190,7 +190,11 @@ def test_trba_post_oracle_vs_reference(golden_dir, tag, B, h, w):
             r = _oracle_predict(net, crops, itos, bs, mode, **kw)
             k = f"{tag}_{key}_bs{bs}"
             assert [x["text"] for x in r] == g[k + "_text"].tolist(), k
-            assert np.array_equal(np.array([x["confidence"] for x in r], dtype=np.float64), g[k + "_conf"]), k
+            # bit-exact on a host whose CPU kernels sum like the generating host's; elsewhere the network's logits differ by
+            # the summation order of its convolutions / GEMMs (tests/test_oracle_trba.py::test_trba_golden), which moved the
+            # confidences by <= 9.4e-5 between AVX-512 and AVX2 kernels and thread counts: bound at ~10x that
+            err = float(np.abs(np.array([x["confidence"] for x in r], dtype=np.float64) - g[k + "_conf"]).max())
+            assert err <= 1e-3, (k, err)
         moved += not np.array_equal(g[f"{tag}_{key}_bs32_conf"], g[f"{tag}_{key}_bs2_conf"])
     assert moved >= 1  # the fixtures do show the chunk-composition dependence of the confidence (run length)
 

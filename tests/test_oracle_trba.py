@@ -15,6 +15,14 @@ def _net(seed):
     return net.eval()
 
 
+def _assert_close(got, exp, rtol, what):
+    """max |got - exp| <= rtol * max |exp| (0 when the host reproduces the generating host's arithmetic)."""
+    assert got.shape == exp.shape, (what, got.shape, exp.shape)
+    err = float(np.abs(got.astype(np.float64) - exp).max()) / max(float(np.abs(exp).max()), 1e-30)
+    print(f"{what}: {err:.2e} of max|.|")
+    assert err <= rtol, (what, err)
+
+
 @pytest.mark.parametrize("tag,B,h,w", [("b4_32x100", 4, 32, 100), ("b2_64x256", 2, 64, 256)])
 def test_trba_golden(golden_dir, tag, B, h, w):
     g = np.load(os.path.join(golden_dir, "trba.npz"))
@@ -28,12 +36,15 @@ def test_trba_golden(golden_dir, tag, B, h, w):
         gl, gi = net(x, max_len=25, mode="greedy")
         bl, bi = net(x, max_len=25, mode="beam", beam_size=8, alpha=0.9, temperature=1.7)
         bl5, bi5 = net(x, max_len=25, mode="beam", beam_size=5, alpha=0.0, temperature=1.0)
-    # same torch ops in the same order as the reference -> bit-exact
-    assert np.array_equal(f.numpy(), g[f"{tag}_cnn"])
-    assert np.array_equal(enc.numpy(), g[f"{tag}_enc"])
+    # Same torch ops in the same order as the reference: bit-exact on a host whose CPU kernels sum like those of the host that
+    # generated the vectors.  CPU convolution / GEMM kernels order their sums by instruction set and thread count, so elsewhere
+    # the values differ by that reordering alone: measured <= 2.9e-6 / 2.9e-5 / 2.5e-4 of max|.| for features / encoder /
+    # logits between AVX-512 and AVX2 kernels and 1 / 3 / 8 / 64 threads.  Bounds at ~10x that; the token ids stay exact.
+    _assert_close(f.numpy(), g[f"{tag}_cnn"], 3e-5, "cnn")
+    _assert_close(enc.numpy(), g[f"{tag}_enc"], 3e-4, "enc")
     for got_l, got_i, key in ((gl, gi, "greedy"), (bl, bi, "beam"), (bl5, bi5, "beam5")):
         assert np.array_equal(got_i.numpy(), g[f"{tag}_{key}_ids"]), key
-        assert np.array_equal(got_l.numpy(), g[f"{tag}_{key}_logits"]), key
+        _assert_close(got_l.numpy(), g[f"{tag}_{key}_logits"], 3e-3, key)
 
 
 def test_charset_and_decode_tokens():

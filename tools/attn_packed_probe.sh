@@ -5,7 +5,7 @@
 # (-DMSOCR_ATTN_SUM_BARRIER), against the exact-f32 kernel of the product library: rows of every beam's step-1 logits off by more
 # than 1e-4.  The instruction-level reproducer is tools/microbench/pk_fma_beside_mfma.hip.   gpurun -- bash tools/attn_packed_probe.sh
 set -e
-R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/manuscript_ocr_amd/csrc
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -shared attn_beam_mfma.hip trba_kernels.hip attn_general.hip"
 /opt/rocm/bin/hipcc $F -Xclang -target-feature -Xclang -packed-fp32-ops -o /tmp/libattn_v0.so 2> >(grep -v "not a recognized feature" >&2) &

@@ -3,7 +3,7 @@
 #   gpurun -- bash tools/attn_phase_times.sh [B]
 # builds a private copy of the two recogniser translation units with -DMSOCR_ATTN_TIMING and runs one beam decode through it.
 set -e
-R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
 B=${1:-1024}
 cd $R/manuscript_ocr_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -DMSOCR_ATTN_TIMING -shared \

@@ -1,6 +1,6 @@
 """Dev: the reference-side BiLSTM binding of INTEGRATION.md section 2, run as written against torch.nn.LSTM (needs the MI355X)."""
 import ctypes, torch, os, sys
-_lib = ctypes.CDLL(os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "manuscript_ocr_amd", "libmsocr.so"))
+_lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "manuscript_ocr_amd", "libmsocr.so"))
 _lib.msocr_attn_pack_split_elems.restype = ctypes.c_int64
 def _pack_whh(lstm):
     H = lstm.hidden_size

@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC counter groups of conv_split_kernel on one GEMM shape (dev tool; gpurun: tools/pmc_split.sh M N K)
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+export MSOCR_REPO_ROOT=$R  # read by the digest below
 M=${1:-161280}; N=${2:-512}; K=${3:-512}
 cd /tmp; export TMPDIR=/tmp
 i=0
@@ -10,7 +11,7 @@ for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_I
 done
 python3 - <<'PY'
 import csv, glob, os, collections
-R=os.environ["GRAFT_REPO_ROOT"]
+R=os.environ["MSOCR_REPO_ROOT"]
 for i in range(1,6):
     agg=collections.defaultdict(float); n=collections.defaultdict(int); dur=[]
     for f in glob.glob(f"{R}/gpurun_out/pmcs_{i}/**/*_counter_collection.csv", recursive=True):

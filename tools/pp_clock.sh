@@ -1,6 +1,7 @@
 #!/bin/bash
 # dev: matrix-pipe busy fraction and effective clock of the split GEMM per MSOCR_PP_DBG ablation (gpurun: bash tools/pp_clock.sh M N K "0 1 2 8 10")
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+export MSOCR_REPO_ROOT=$R  # read by the digest below
 M=${1:-161280}; N=${2:-512}; K=${3:-4096}; DBGS=${4:-"0 1 2 8 10"}
 cd /tmp; export TMPDIR=/tmp
 for d in $DBGS; do
@@ -9,7 +10,7 @@ for d in $DBGS; do
 done
 python3 - "$DBGS" <<'PY'
 import csv, glob, os, collections, sys
-R=os.environ["GRAFT_REPO_ROOT"]
+R=os.environ["MSOCR_REPO_ROOT"]
 for d in sys.argv[1].split():
     agg=collections.defaultdict(float); n=collections.defaultdict(int); dur=[]
     for f in glob.glob(f"{R}/gpurun_out/pmcc_{d}/**/*_counter_collection.csv", recursive=True):

@@ -1,7 +1,8 @@
 #!/bin/bash
 # dev: arbitrary PMC counter sets on one split GEMM per MSOCR_PP_DBG ablation.
 #   gpurun: bash tools/pp_pmc.sh M N K "0 32" "CNT_A CNT_B;CNT_C CNT_D"
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+export MSOCR_REPO_ROOT=$R  # read by the digest below
 M=$1; N=$2; K=$3; DBGS=$4; SETS=$5
 cd /tmp; export TMPDIR=/tmp
 IFS=';' read -ra SETARR <<< "$SETS"
@@ -14,7 +15,7 @@ for d in $DBGS; do
 done
 python3 - "$DBGS" ${#SETARR[@]} <<'PY'
 import csv, glob, os, collections, sys
-R=os.environ["GRAFT_REPO_ROOT"]
+R=os.environ["MSOCR_REPO_ROOT"]
 for d in sys.argv[1].split():
     out=[]
     for i in range(1, int(sys.argv[2])+1):

@@ -7,7 +7,7 @@
 # fit one pass; gpurun refuses --pmc together with the system traces).
 set -e
 T=${1:-r02}
-R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
 export TMPDIR=/tmp
 rm -rf $R/gpurun_out/${T}_conc $R/gpurun_out/${T}_ser $R/gpurun_out/${T}_fetch $R/gpurun_out/${T}_write $R/gpurun_out/${T}_mfma  # one <pid>_*.csv set per directory

@@ -34,7 +34,7 @@ extern "C" {
 /* flags for msocr_conv2d */
 #define MSOCR_CONV_RELU 1u
 #define MSOCR_CONV_RESIDUAL 2u /* out = act(conv + bias + residual) */
-#define MSOCR_CONV_POOL2 4u    /* msocr_conv3x3_winograd42_fused only: out = maxpool2x2/2(act(conv + bias)), out is [N][H/2][W/2] */
+#define MSOCR_CONV_POOL2 4u    /* msocr_*winograd_fused64* only: out = maxpool2x2/2(act(conv + bias)), out is [N][H/2][W/2] */
 
 typedef struct msocr_conv_desc {
   int32_t dtype;                 /* MSOCR_F32 | MSOCR_BF16 (input, weight, residual, output) */
@@ -55,39 +55,36 @@ typedef struct msocr_conv_desc {
 int msocr_conv2d(const msocr_conv_desc* d, const void* in, const void* weight, const float* bias,
                  const void* residual, void* out, void* stream);
 
-/* The same convolution for KH=KW=3, stride 1, pad 1, MSOCR_F32, as Winograd F(2x2,3x3): input transform (HBM-bound) ->
- * 16 GEMMs [tiles x Cin] x [Cin x Cout] in one MFMA launch -> output transform + bias/residual/ReLU (HBM-bound).
- * 2.25x fewer matrix FLOPs than the direct form; all arithmetic f32 (differs from msocr_conv2d by rounding order only).
- * u_weight = [16][Cout][Cin] f32 on the DEVICE, produced by msocr_winograd_weights_host (a HOST function: both of
- * its pointers are host memory; evaluates G g G^T in f64, rounds once) from the BatchNorm-folded [Cout][3][3][Cin]
- * weight.  workspace: msocr_conv3x3_winograd_workspace_bytes(d) bytes, 16-B aligned (-1 = shape not supported:
- * Cin % 16, Cout % 32).  Same reference code as msocr_conv2d (every 3x3/1/1 conv of SE-ResNet31, ResNet-50 and the
- * EAST decoder). */
-int64_t msocr_conv3x3_winograd_workspace_bytes(const msocr_conv_desc* d);
-int msocr_conv3x3_winograd(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
+/* The same convolution for KH=KW=3, stride 1, pad 1, MSOCR_F32, as Winograd in one of three tile forms (`form`):
+ *   MSOCR_WINO_2X2  F(2x2,3x3): 16 transform points per 2x2 output tile, 4 multiplies per output (direct: 9);
+ *   MSOCR_WINO_4X2  the TALL form F(4,3) x F(2,3): 24 points per 4x2 tile, 3 multiplies per output, V / Mw 3x the layer's arrays;
+ *   MSOCR_WINO_4X4  the square form F(4,3) x F(4,3): 36 points per 4x4 tile, 2.25 multiplies and workspace words per output.
+ * The 6-point axes run on the interpolation points {0, +-3/2, +-2/3, inf} (round 4): the tall form at half the rounding error of the
+ * textbook points {0, +-1, +-2}, the square form at the tall form's error on those (the textbook points would cost 4.7x; DESIGN.md
+ * section 4.4).  Input transform (HBM-bound) -> P GEMMs [tiles x Cin] x [Cin x Cout] in one MFMA launch -> output transform +
+ * bias/residual/ReLU (HBM-bound); all arithmetic f32 (differs from msocr_conv2d by rounding order only).
+ * u = the transform-domain weight U = G g G^T on the DEVICE, from msocr_winograd_weights_host (a HOST function: both of its pointers
+ * are host memory; evaluates G g G^T in f64, rounds once) of the BatchNorm-folded [Cout][3][3][Cin] weight, [P][Cout][Cin] f32.
+ *   split = 0: u as that f32 array, the GEMMs on exact-f32 MFMA;
+ *   split = 1: u = K-tile-major bf16 planes [3][P][Cin/32][Cout][32] (msocr_split_bf16x3_ktile_host of it), the GEMMs with split
+ *              operands on the bf16 matrix pipes (see msocr_conv1x1_split; Cin % 32 == 0, Cout % 64 == 0).
+ * GEMMs exist for 2X2 exact, 4X2 exact and split, and 4X4 split; any other (form, split) is MSOCR_E_ARG.
+ * workspace: msocr_winograd_workspace_bytes(d, form) bytes, 16-B aligned = V [P][tiles][Cin] f32 + Mw [P][tiles][Cout] f32
+ * (-1 = shape not supported: Cin % 16, Cout % 32, not 3x3/1/1).  The three stages are also callable one by one (identical kernels,
+ * identical results when called in this order on one stream with the same workspace): V = B^T d B into the workspace;
+ * Mw[p] = V[p] U[p]^T; out = act(A^T Mw A + bias (+ residual)) — for tests and for the per-kernel rooflines of bench.py.
+ * Same reference code as msocr_conv2d (every 3x3/1/1 conv of SE-ResNet31, ResNet-50 and the EAST decoder). */
+#define MSOCR_WINO_2X2 0
+#define MSOCR_WINO_4X2 1
+#define MSOCR_WINO_4X4 2
+int64_t msocr_winograd_workspace_bytes(const msocr_conv_desc* d, int form);
+int msocr_winograd_weights_host(int form, const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
+int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int split, const void* in, const void* u, const float* bias,
                            const void* residual, void* out, void* workspace, void* stream);
-int msocr_winograd_weights_host(const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
-/* The three stages of msocr_conv3x3_winograd one by one (identical kernels, identical results when called in this order on one
- * stream with the same workspace): V = B^T d B into the workspace; Mw[p] = V[p] U[p]^T (16 GEMMs, one MFMA launch);
- * out = act(A^T Mw A + bias (+ residual)).  For tests and for the per-kernel rooflines of bench.py. */
-int msocr_winograd_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream);
-int msocr_winograd_gemm(const msocr_conv_desc* d, const float* u_weight, void* workspace, void* stream);
-int msocr_winograd_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
+int msocr_winograd_input_transform(const msocr_conv_desc* d, int form, const void* in, void* workspace, void* stream);
+int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const void* u, void* workspace, void* stream);
+int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* residual,
                                     void* out, void* stream);
-
-/* The same convolution in the TALL Winograd form F(4,3) x F(2,3) (6x4 input tile -> 4x2 output tile, 24 transform points:
- * 3 multiplies per output where F(2x2,3x3) spends 4 and the direct form 9; V / Mw are 3x the layer's arrays instead of 4x).
- * Only the H axis takes the 6-point transform, whose constants grow the layer's f32 rounding error ~2.5x rms over F(2x2)
- * (DESIGN.md section 4).  u_weight = [24][Cout][Cin] f32 on the DEVICE from msocr_winograd42_weights_host (HOST function, f64,
- * rounded once).  Same shape rules, workspace convention and stage entry points as msocr_conv3x3_winograd. */
-int64_t msocr_conv3x3_winograd42_workspace_bytes(const msocr_conv_desc* d);
-int msocr_conv3x3_winograd42(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
-                             const void* residual, void* out, void* workspace, void* stream);
-int msocr_winograd42_weights_host(const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
-int msocr_winograd42_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream);
-int msocr_winograd42_gemm(const msocr_conv_desc* d, const float* u_weight, void* workspace, void* stream);
-int msocr_winograd42_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
-                                      void* out, void* stream);
 
 /* ---- split-operand f32 ("bf16x3"): the default arithmetic of the f32 1x1 convolutions and Winograd-domain GEMMs --------------
  * gfx950 runs exact-f32 MFMA at 1/16 of the bf16 rate.  An f32 value is the exact sum of three bf16 values (round-to-nearest
@@ -99,17 +96,16 @@ int msocr_winograd42_output_transform(const msocr_conv_desc* d, const void* work
  *     K-TILE-MAJOR, planes [3][nb][k/32][rows][32]: the 32-element pieces of all rows for one K-tile are contiguous (64 bytes per row),
  *     so a workgroup's weight tile of one K-tile is ONE dense block — whole 128-byte lines, every byte used.  (Row-major planes
  *     gave 64-byte pieces at a stride of 2 k bytes: half of every fetched line belonged to the NEXT K-tile and was fetched again —
- *     TCP -> L2 read requests 2x the algorithmic count, profiles/r04_pp_ablations.txt.)  This is the layout the three GEMM entry
- *     points below take ("weight_planes" / "u_planes"; k = KH * KW * Cin in the weight's own [KH][KW][Cin] order).
+ *     TCP -> L2 read requests 2x the algorithmic count, profiles/r04_pp_ablations.txt.)  This is the layout the two GEMM entry
+ *     points below and msocr_winograd_gemm with split = 1 take ("weight_planes" / "u"; k = KH * KW * Cin in the weight's own
+ *     [KH][KW][Cin] order).
  * msocr_conv1x1_split: msocr_conv2d for KH = KW = 1 / stride 1 / no padding / MSOCR_F32 over a dense pixel sequence
  *   (in_sH == W * in_sW, in_sN == H * in_sH), Cin % 32 == 0, Cout % 64 == 0; weight_planes = K-tile-major planes of [1][Cout][Cin] on the device.
  *   Same flags, epilogue and reference layers as msocr_conv2d (torchvision Bottleneck conv1 / conv3 / downsample, DecoderBlock
  *   conv1x1, SEBasicBlock downsample, the BiLSTM input projections and linears).
  * msocr_conv2d_split: msocr_conv2d for MSOCR_F32 with any kernel size / stride / padding (the strided 3x3 and 1x1 convolutions of
  *   the two ResNet trunks, which have no Winograd form), weight_planes = K-tile-major planes of [1][Cout][KH*KW*Cin]; Cin % 32 == 0, Cout % 64 == 0.
- * msocr_winograd42_gemm_split / msocr_conv3x3_winograd42_split: stage 2 of / the whole msocr_conv3x3_winograd42 with
- *   u_planes = K-tile-major planes ([3][24][Cin/32][Cout][32] bf16) of msocr_winograd42_weights_host's [24][Cout][Cin] output
- *   (Cin % 32, Cout % 64).
+ * msocr_conv3x3_winograd with split = 1: the Winograd-domain GEMMs in this arithmetic.
  * Results differ from the exact-f32 entry points by rounding only (tests/test_gpu_ops.py bounds both against an f64 reference). */
 int msocr_split_bf16x3_host(const float* w_host, int64_t n, uint16_t* planes_out_host);
 int msocr_split_bf16x3_ktile_host(const float* w_host, int64_t nbatch, int64_t rows, int64_t k, uint16_t* planes_out_host);
@@ -117,44 +113,21 @@ int msocr_conv1x1_split(const msocr_conv_desc* d, const void* in, const void* we
                         const void* residual, void* out, void* stream);
 int msocr_conv2d_split(const msocr_conv_desc* d, const void* in, const void* weight_planes, const float* bias,
                        const void* residual, void* out, void* stream);
-int msocr_winograd42_gemm_split(const msocr_conv_desc* d, const void* u_planes, void* workspace, void* stream);
-int msocr_conv3x3_winograd42_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
-                                   const void* residual, void* out, void* workspace, void* stream);
 
-/* F(4,3) x F(4,3) on the interpolation points {0, +-3/2, +-2/3, inf} (round 4): 36 transform points per 4 x 4 outputs — 2.25
- * multiplies and workspace words per output instead of the tall form's 3 — at the tall form's rounding error (the textbook points
- * {0, +-1, +-2} would cost 4.7x).  Same contract as the msocr_*winograd42* entry points: workspace =
- * msocr_conv3x3_winograd44_workspace_bytes (V [36][tiles][Cin] f32 + Mw [36][tiles][Cout] f32, tiles = N ceil(H/4) ceil(W/4));
- * u_planes = K-tile-major bf16 planes ([3][36][Cin/32][Cout][32], msocr_split_bf16x3_ktile_host) of msocr_winograd44_weights_host's
- * [36][Cout][Cin] f32 output (HOST function, f64, rounded once); Cin % 32 == 0, Cout % 64 == 0; the 36 GEMMs run with split
- * operands on the bf16 matrix pipes.  The three stages are also callable one by one (same workspace). */
-int64_t msocr_conv3x3_winograd44_workspace_bytes(const msocr_conv_desc* d);
-int msocr_winograd44_weights_host(const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
-int msocr_winograd44_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream);
-int msocr_winograd44_gemm_split(const msocr_conv_desc* d, const void* u_planes, void* workspace, void* stream);
-int msocr_winograd44_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
-                                      void* out, void* stream);
-int msocr_conv3x3_winograd44_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
+/* Cin == 64: the tall form (MSOCR_WINO_4X2) with the 24 transform-domain GEMMs (K = 64) and the output transform fused in one
+ * kernel, so Mw never reaches HBM (unfused, a 64-channel layer is HBM-bound on Mw).  workspace holds V only
+ * (msocr_winograd_fused64_workspace_bytes; -1 = unsupported: Cin != 64, Cout % 32, or POOL2 with odd H / W or a residual).
+ * split = 0: u = [24][Cout][64] f32 from msocr_winograd_weights_host(MSOCR_WINO_4X2, ...); split = 1: u = its three bf16 planes
+ * [3][24][Cout][64] (msocr_split_bf16x3_host), the GEMMs in the split-operand arithmetic (see msocr_conv1x1_split).
+ * With MSOCR_CONV_POOL2 in d->flags the kernel also applies the 2x2 / stride-2 max-pool that closes conv0 of SE-ResNet31
+ * (recognizers/_trba/model/seresnet31.py:81-89: conv3x3 64->128, BN, ReLU, MaxPool2d(2, 2)) and writes the pooled
+ * [N][H/2][W/2][Cout] map (d->out_ld = its channel stride).  msocr_winograd_fused64_gemm_output is stage 2 alone (stage 1 =
+ * msocr_winograd_input_transform(d, MSOCR_WINO_4X2, ...) into the same workspace). */
+int64_t msocr_winograd_fused64_workspace_bytes(const msocr_conv_desc* d);
+int msocr_conv3x3_winograd_fused64(const msocr_conv_desc* d, int split, const void* in, const void* u, const float* bias,
                                    const void* residual, void* out, void* workspace, void* stream);
-
-/* Cin == 64: the tall Winograd form with the 24 transform-domain GEMMs (K = 64) and the output transform fused in one kernel, so
- * Mw never reaches HBM (unfused, a 64-channel layer is HBM-bound on Mw).  workspace holds V only
- * (msocr_conv3x3_winograd42_fused_workspace_bytes; -1 = unsupported: Cin != 64, Cout % 32, or POOL2 with odd H / W or a residual).
- * u_weight as for msocr_conv3x3_winograd42.  With MSOCR_CONV_POOL2 in d->flags the kernel also applies the 2x2 / stride-2 max-pool
- * that closes conv0 of SE-ResNet31 (recognizers/_trba/model/seresnet31.py:81-89: conv3x3 64->128, BN, ReLU, MaxPool2d(2, 2)) and writes the pooled
- * [N][H/2][W/2][Cout] map (d->out_ld = its channel stride).  msocr_winograd42_fused_gemm_output is stage 2 alone (stage 1 =
- * msocr_winograd42_input_transform into the same workspace). */
-int64_t msocr_conv3x3_winograd42_fused_workspace_bytes(const msocr_conv_desc* d);
-int msocr_conv3x3_winograd42_fused(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
-                                   const void* residual, void* out, void* workspace, void* stream);
-int msocr_winograd42_fused_gemm_output(const msocr_conv_desc* d, const float* u_weight, const void* workspace, const float* bias,
+int msocr_winograd_fused64_gemm_output(const msocr_conv_desc* d, int split, const void* u, const void* workspace, const float* bias,
                                        const void* residual, void* out, void* stream);
-/* The same two entry points with the 24 K = 64 GEMMs on the bf16 matrix pipes (split-operand arithmetic, see msocr_conv1x1_split):
- * u_planes = [3][24][Cout][64] bf16 = msocr_split_bf16x3_host of msocr_winograd42_weights_host's output. */
-int msocr_conv3x3_winograd42_fused_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
-                                         const void* residual, void* out, void* workspace, void* stream);
-int msocr_winograd42_fused_gemm_output_split(const msocr_conv_desc* d, const void* u_planes, const void* workspace, const float* bias,
-                                             const void* residual, void* out, void* stream);
 
 /* u8 RGB images (N x H x W x 3) -> normalised NHWC with C padded 3->cpad (4 or 8) inside a zero canvas
  * out[N][Hp][Wp][cpad], image origin at (pad_t, pad_l); the zero border is the stem convolution's padding.

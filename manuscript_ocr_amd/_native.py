@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmsocr.so")
 
 F32, BF16 = 0, 1
 CONV_RELU, CONV_RESIDUAL, CONV_POOL2 = 1, 2, 4
+WINO_2X2, WINO_4X2, WINO_4X4 = 0, 1, 2  # Winograd tile forms (msocr.h MSOCR_WINO_*)
 
 c_i32, c_i64, c_u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32
 c_f32, c_f64, c_vp = ctypes.c_float, ctypes.c_double, ctypes.c_void_p
@@ -46,35 +47,19 @@ class AttnSplitWeights(ctypes.Structure):
 
 _SIGS = {
     "msocr_conv2d": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
-    "msocr_conv3x3_winograd": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd_weights_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
-    "msocr_winograd_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd42_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
-    "msocr_conv3x3_winograd42": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd42_weights_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
-    "msocr_winograd42_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd42_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd42_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc), c_i32]),
+    "msocr_winograd_weights_host": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "msocr_conv3x3_winograd": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp]),
+    "msocr_winograd_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "msocr_winograd_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_fused64_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
+    "msocr_conv3x3_winograd_fused64": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_fused64_gemm_output": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_split_bf16x3_host": (c_i32, [c_vp, c_i64, c_vp]),
     "msocr_split_bf16x3_ktile_host": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp]),
     "msocr_conv1x1_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_conv2d_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd42_gemm_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd42_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd44_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
-    "msocr_winograd44_weights_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
-    "msocr_winograd44_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd44_gemm_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd44_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd44_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd42_fused_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
-    "msocr_conv3x3_winograd42_fused": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd42_fused_gemm_output": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_conv3x3_winograd42_fused_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd42_fused_gemm_output_split": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_normalize_u8": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_resize_linear_u8": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "msocr_maxpool2d": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i64, c_vp]),

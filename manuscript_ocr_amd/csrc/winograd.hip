@@ -1,14 +1,27 @@
-// winograd.hip — 3x3 / stride 1 / pad 1 convolution as Winograd F(2x2,3x3) in f32 for gfx950 (MI355X).
+// winograd.hip — 3x3 / stride 1 / pad 1 convolution as Winograd in f32 for gfx950 (MI355X), in three tile forms.
 //
 // Why here: exact-f32 MFMA (v_mfma_f32_32x32x2_f32) peaks at 157 TFLOP/s, 1/16 of the bf16 rate, while HBM3E
-// delivers 8 TB/s — so on this chip an f32 3x3 convolution is worth trading 2.25x fewer matrix FLOPs for two
-// streaming transform passes.  out = A^T [ sum_c (G g G^T) (.) (B^T d B) ] A  per 2x2 output tile:
-//   1. wino_input_kernel : V[xi*4+nu][tile][c]  = (B^T d B)[xi][nu]      (HBM-bound, 16-B coalesced)
-//   2. 16 GEMMs in ONE launch of conv_igemm_kernel: Mw[p][tile][co] = sum_c V[p][tile][c] * U[p][co][c]  (MFMA)
-//   3. wino_output_kernel: out[2x2 tile][co] = act(A^T Mw A + bias (+ residual))  (HBM-bound)
+// delivers 8 TB/s — so on this chip an f32 3x3 convolution is worth trading fewer matrix FLOPs for two
+// streaming transform passes.  out = A^T [ sum_c (G g G^T) (.) (B^T d B) ] A  per output tile:
+//   1. wino*_input_kernel : V[xi*PW+nu][tile][c] = (B^T d B)[xi][nu]      (HBM-bound, 16-B coalesced)
+//   2. PH*PW GEMMs in ONE launch (conv_igemm / conv_split): Mw[p][tile][co] = sum_c V[p][tile][c] * U[p][co][c]  (MFMA)
+//   3. wino*_output_kernel: out[tile][co] = act(A^T Mw A + bias (+ residual))  (HBM-bound)
 // U = G g G^T is computed once at weight-load time in f64 (msocr_winograd_weights_host).
-// The transforms only add/subtract and scale by 1/2 (exact), so the result differs from the direct f32
-// convolution by rounding order only (Lavin & Gray 2016 measure F(2x2,3x3) at or below direct-conv error).
+//
+// The forms (msocr.h MSOCR_WINO_*), output tile MH x MW, PH x PW = (MH + 2) x (MW + 2) transform points:
+//   2X2  F(2x2,3x3)       16 points, 4 multiplies per output (direct: 9).  The transforms only add/subtract and scale by 1/2
+//                         (exact), so the result differs from the direct f32 convolution by rounding order only (Lavin & Gray 2016).
+//   4X2  F(4,3) x F(2,3)  24 points per 4x2 outputs: 3 multiplies per output, V / Mw 3x the layer's arrays instead of 4x.  Only the
+//                         H axis takes the 6-point transform: on the textbook points {0, +-1, +-2, inf} its constants grew the layer's f32
+//                         rounding error ~2.5x rms over F(2x2), where the 6x6 form would grow it 6x; since round 4
+//                         it runs on the points {0, +-3/2, +-2/3, inf} (wino44_bt / wino44_at): half that error.
+//   4X4  F(4,3) x F(4,3)  36 points per 4x4 outputs: 2.25 multiplies and workspace words per output.  On the textbook points its error
+//                         is 4.7x the tall form's and cannot pass the f64 arbitration of the tolerances (tests/test_gpu_f64.py); on
+//                         {0, +-3/2, +-2/3, inf} — reciprocal pairs keep the Vandermonde entries within [8/27, 27/8] — an f32 simulation of
+//                         the whole pipeline of transforms measures 1.05x the tall form's error (and 0.5x for the tall form itself on these
+//                         points; tools/winograd_points.py, profiles/r04_winograd_points.txt).
+// ops.conv2d() picks the tall form for the Cin = 64 layers (fused kernels, below) and where the square form does not pay; the 2x2
+// form when 24 * ceil(H/4) >= 16 * ceil(H/2).
 //
 // Replaces nn.Conv2d(3x3, stride 1, padding 1)+BatchNorm2d(+ReLU)(+add) of
 //   recognizers/_trba/model/seresnet31.py:37-45,81-89 ; detectors/_east/east.py:13-30 (conv3x3 of DecoderBlock)
@@ -23,8 +36,30 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// 1-D transforms of F(4,3) on the interpolation points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4; the matrices and why these points:
-// the comment block in front of wino44_input_kernel).  Used on both axes of the square form and on the H axis of the tall form.
+// ---- 1-D transforms, four channels per lane: B^T (M + 2 inputs -> M + 2 points) and A^T (M + 2 points -> M outputs) ----------
+template <int M> __device__ void wino_bt1(const f32x4 d[M + 2], f32x4 r[M + 2]);
+template <int M> __device__ void wino_at1(const f32x4 m[M + 2], f32x4 y[M]);
+
+// F(2,3) on {0, 1, -1, inf}: B^T rows (d0-d2, d1+d2, d2-d1, d1-d3), A^T rows (m0+m1+m2, m1-m2-m3)
+template <> __device__ __forceinline__ void wino_bt1<2>(const f32x4 d[4], f32x4 r[4]) {
+  r[0] = d[0] - d[2];
+  r[1] = d[1] + d[2];
+  r[2] = d[2] - d[1];
+  r[3] = d[1] - d[3];
+}
+template <> __device__ __forceinline__ void wino_at1<2>(const f32x4 m[4], f32x4 y[2]) {
+  y[0] = (m[0] + m[1]) + m[2];
+  y[1] = (m[1] - m[2]) - m[3];
+}
+
+// F(4,3) on the interpolation points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4).  Matrices (Cook-Toom, wincnn scaling: G carries
+// 1 / prod(a_j - a_l)):
+//   B^T d:  r0 = d0 - 97/36 d2 + d4          r5 = d1 - 97/36 d3 + d5
+//           e1 = d4 - 4/9 d2,  o1 = 3/2 d3 - 2/3 d1:   r1 = e1 + o1,  r2 = e1 - o1        (points +-3/2)
+//           e2 = d4 - 9/4 d2,  o2 = 2/3 d3 - 3/2 d1:   r3 = e2 + o2,  r4 = e2 - o2        (points +-2/3)
+//   A^T m:  y0 = m0 + (m1 + m2) + (m3 + m4)             y1 = 3/2 (m1 - m2) + 2/3 (m3 - m4)
+//           y2 = 9/4 (m1 + m2) + 4/9 (m3 + m4)          y3 = 27/8 (m1 - m2) + 8/27 (m3 - m4) + m5
+//   G (host, f64): rows [1,0,0], [8,+-12,18]/65, [-81/2,-+27,-18]/65, [0,0,1].
 __device__ __forceinline__ void wino44_bt(const f32x4 d[6], f32x4 r[6]) {
   constexpr float k97_36 = 97.0f / 36.0f, k4_9 = 4.0f / 9.0f, k9_4 = 2.25f, k3_2 = 1.5f, k2_3 = 2.0f / 3.0f;
 #pragma unroll
@@ -48,17 +83,23 @@ __device__ __forceinline__ void wino44_at(const f32x4 m[6], f32x4 y[4]) {
     y[3][e] = fmaf(k27_8, d12, k8_27 * d34) + m[5][e];
   }
 }
+template <> __device__ __forceinline__ void wino_bt1<4>(const f32x4 d[6], f32x4 r[6]) { wino44_bt(d, r); }
+template <> __device__ __forceinline__ void wino_at1<4>(const f32x4 m[6], f32x4 y[4]) { wino44_at(m, y); }
 
 
 struct WinoGeom {
   int N, H, W;      // image extent (output extent is the same: stride 1, pad 1)
-  int TH, TW;       // 2x2-output tiles per image
+  int TH, TW;       // output tiles per image
   long Mt;          // N * TH * TW
 };
 
 // ---- 1. input transform: one thread = one tile x 4 channels ------------------------------------------------
-__global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ in, long sN, long sH, long sW, int C,
-                                                          WinoGeom g, float* __restrict__ V) {
+// The axis order sets the f32 rounding and is part of each form's result: the forms with a 6-point H axis transform W first (B^T
+// per row as the row is loaded), then H per column; F(2x2) loads the whole tile and transforms H first, then W.
+template <int MH, int MW>
+__device__ __forceinline__ void wino_input_body(const float* in, long sN, long sH, long sW, int C, WinoGeom g, float* V) {
+  constexpr int PH = MH + 2, PW = MW + 2;
+  constexpr bool w_first = MH == 4;
   const int cch = C >> 2;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long t = gid / cch;
@@ -68,47 +109,66 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
   const long r = t / g.TW;
   const int th = (int)(r % g.TH);
   const int n = (int)(r / g.TH);
-  const int h0 = 2 * th - 1, w0 = 2 * tw - 1;
+  const int h0 = MH * th - 1, w0 = MW * tw - 1;
   const float* base = in + (long)n * sN + c;
-  f32x4 d[4][4];
+  f32x4 q[PH][PW];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < PH; ++i) {
     const int hi = h0 + i;
     const bool okh = (unsigned)hi < (unsigned)g.H;
+    f32x4 d[PW];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < PW; ++j) {
       const int wi = w0 + j;
       const bool ok = okh && (unsigned)wi < (unsigned)g.W;
       // branch-free: padded taps read the (always valid) first vector of the image row block and are masked to zero
       const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? base + (long)hi * sH + (long)wi * sW : base);
-      d[i][j] = ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+      d[j] = ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if constexpr (w_first) {
+      wino_bt1<MW>(d, q[i]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < PW; ++j) q[i][j] = d[j];
     }
   }
-  // B^T d : rows (d0-d2, d1+d2, d2-d1, d1-d3)
-  f32x4 q[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    q[0][j] = d[0][j] - d[2][j];
-    q[1][j] = d[1][j] + d[2][j];
-    q[2][j] = d[2][j] - d[1][j];
-    q[3][j] = d[1][j] - d[3][j];
-  }
-  // (B^T d) B : columns likewise
   const long plane = g.Mt * (long)C;
   float* o = V + t * (long)C + c;
+  if constexpr (w_first) {  // then H per column, stored as it is transformed
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    *reinterpret_cast<f32x4*>(o + (i * 4 + 0) * plane) = q[i][0] - q[i][2];
-    *reinterpret_cast<f32x4*>(o + (i * 4 + 1) * plane) = q[i][1] + q[i][2];
-    *reinterpret_cast<f32x4*>(o + (i * 4 + 2) * plane) = q[i][2] - q[i][1];
-    *reinterpret_cast<f32x4*>(o + (i * 4 + 3) * plane) = q[i][1] - q[i][3];
+    for (int j = 0; j < PW; ++j) {
+      f32x4 col[PH], v[PH];
+#pragma unroll
+      for (int i = 0; i < PH; ++i) col[i] = q[i][j];
+      wino_bt1<MH>(col, v);
+#pragma unroll
+      for (int i = 0; i < PH; ++i) *reinterpret_cast<f32x4*>(o + (i * PW + j) * plane) = v[i];
+    }
+  } else {  // then W per row i, on row i of the H-transformed columns (the compiler keeps one H transform per column; written
+            // row by row, each store follows its own arithmetic: 76 VGPRs where transforming all columns first took 82)
+#pragma unroll
+    for (int i = 0; i < PH; ++i) {
+      f32x4 row[PW], v[PW];
+#pragma unroll
+      for (int j = 0; j < PW; ++j) {
+        f32x4 col[PH], hv[PH];
+#pragma unroll
+        for (int k = 0; k < PH; ++k) col[k] = q[k][j];
+        wino_bt1<MH>(col, hv);
+        row[j] = hv[i];
+      }
+      wino_bt1<MW>(row, v);
+#pragma unroll
+      for (int j = 0; j < PW; ++j) *reinterpret_cast<f32x4*>(o + (i * PW + j) * plane) = v[j];
+    }
   }
 }
 
-// ---- 3. output transform: one thread = one tile x 4 output channels ---------------------------------------
-__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,
-                                                           const float* __restrict__ bias, const float* __restrict__ res, long res_ld,
-                                                           int relu, float* __restrict__ out, long out_ld) {
+// ---- 3. output transform: one thread = one tile x 4 output channels; H axis first (A^T per column), then W -----------------
+template <int MH, int MW>
+__device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, WinoGeom g, const float* bias, const float* res, long res_ld,
+                                                 int relu, float* out, long out_ld) {
+  constexpr int PH = MH + 2, PW = MW + 2;
   const int cch = Cout >> 2;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long t = gid / cch;
@@ -120,30 +180,35 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
   const int n = (int)(r / g.TH);
   const long plane = g.Mt * (long)Cout;
   const float* mp = Mw + t * (long)Cout + c;
-  f32x4 m[4][4];
+  // load order only (register allocation, not arithmetic): F(2x2) loads the whole tile first, the 6-point forms column by column
+  f32x4 mt[PH][PW];
+  if constexpr (MH == 2) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < PH; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) m[i][j] = *reinterpret_cast<const f32x4*>(mp + (i * 4 + j) * plane);
-  // A^T m : rows (m0+m1+m2, m1-m2-m3)
-  f32x4 s[2][4];
+      for (int j = 0; j < PW; ++j) mt[i][j] = *reinterpret_cast<const f32x4*>(mp + (i * PW + j) * plane);
+  }
+  f32x4 s[MH][PW];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    s[0][j] = (m[0][j] + m[1][j]) + m[2][j];
-    s[1][j] = (m[1][j] - m[2][j]) - m[3][j];
+  for (int j = 0; j < PW; ++j) {
+    f32x4 m[PH], y[MH];
+#pragma unroll
+    for (int i = 0; i < PH; ++i) m[i] = MH == 2 ? mt[i][j] : *reinterpret_cast<const f32x4*>(mp + (i * PW + j) * plane);
+    wino_at1<MH>(m, y);
+#pragma unroll
+    for (int a = 0; a < MH; ++a) s[a][j] = y[a];
   }
   f32x4 b = {0.f, 0.f, 0.f, 0.f};
   if (bias) b = *reinterpret_cast<const f32x4*>(bias + c);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ho = 2 * th + i;
+  for (int a = 0; a < MH; ++a) {
+    const int ho = MH * th + a;
     if (ho >= g.H) continue;
-    f32x4 y[2];
-    y[0] = (s[i][0] + s[i][1]) + s[i][2];
-    y[1] = (s[i][1] - s[i][2]) - s[i][3];
+    f32x4 y[MW];
+    wino_at1<MW>(s[a], y);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int wo = 2 * tw + j;
+    for (int j = 0; j < MW; ++j) {
+      const int wo = MW * tw + j;
       if (wo >= g.W) continue;
       const long pix = ((long)n * g.H + ho) * g.W + wo;
       f32x4 v = y[j] + b;
@@ -156,459 +221,125 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
   }
 }
 
-static bool wino_geom(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!d || d->dtype != MSOCR_F32) return false;
+// One kernel symbol per form and direction: profilers, bench.py and tools/ sort kernels into the convolution stage by these names.
+#define WINO_TRANSFORM_KERNELS(PREFIX, MH, MW)                                                                                    \
+  __global__ __launch_bounds__(256) void PREFIX##_input_kernel(const float* __restrict__ in, long sN, long sH, long sW, int C,   \
+                                                               WinoGeom g, float* __restrict__ V) {                            \
+    wino_input_body<MH, MW>(in, sN, sH, sW, C, g, V);                                                                            \
+  }                                                                                                                              \
+  __global__ __launch_bounds__(256) void PREFIX##_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,              \
+                                                                const float* __restrict__ bias, const float* __restrict__ res,  \
+                                                                long res_ld, int relu, float* __restrict__ out, long out_ld) {  \
+    wino_output_body<MH, MW>(Mw, Cout, g, bias, res, res_ld, relu, out, out_ld);                                                 \
+  }
+WINO_TRANSFORM_KERNELS(wino, 2, 2)
+WINO_TRANSFORM_KERNELS(wino42, 4, 2)
+WINO_TRANSFORM_KERNELS(wino44, 4, 4)
+#undef WINO_TRANSFORM_KERNELS
+
+// ---- host side of the unfused forms --------------------------------------------------------------------------------------------
+static const int kWinoTile[3][2] = {{2, 2}, {4, 2}, {4, 4}};  // output tile (MH, MW) per MSOCR_WINO_* form
+
+static int wino_points(int form) { return (kWinoTile[form][0] + 2) * (kWinoTile[form][1] + 2); }
+
+static bool wino_geom(const msocr_conv_desc* d, int form, WinoGeom* g) {
+  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4 || !d || d->dtype != MSOCR_F32) return false;
   if (d->KH != 3 || d->KW != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ho != d->H || d->Wo != d->W) return false;
   if (d->Cin <= 0 || d->Cin % 16 || d->Cout <= 0 || d->Cout % 32) return false;
+  // every form: the F(2x2) tile count fits in 31 bits and the larger of V / Mw in 2^46 elements
+  if ((long)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2) > 0x7fffffffL) return false;
+  const int mh = kWinoTile[form][0], mw = kWinoTile[form][1];
   g->N = d->N; g->H = d->H; g->W = d->W;
-  g->TH = (d->H + 1) / 2; g->TW = (d->W + 1) / 2;
+  g->TH = (d->H + mh - 1) / mh; g->TW = (d->W + mw - 1) / mw;
   g->Mt = (long)d->N * g->TH * g->TW;
-  return g->Mt <= 0x7fffffffL;
+  return wino_points(form) * g->Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) <= 0x3fffffffffffL;
 }
 
-extern "C" int64_t msocr_conv3x3_winograd_workspace_bytes(const msocr_conv_desc* d) {
-  WinoGeom g;
-  if (!wino_geom(d, &g)) return -1;
-  return 16 * g.Mt * ((int64_t)d->Cin + d->Cout) * (int64_t)sizeof(float);
-}
+static bool wino_strides_ok(const msocr_conv_desc* d) { return !(d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4); }
 
-static int wino_check(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino_geom(d, g)) return MSOCR_E_ARG;
-  if (d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4 || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
+static int wino_check(const msocr_conv_desc* d, int form, WinoGeom* g) {
+  if (!wino_geom(d, form, g) || !wino_strides_ok(d) || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
   return MSOCR_OK;
+}
+
+// the (form, split) pairs that have GEMM kernels: 2X2 exact, 4X2 exact or split, 4X4 split
+static bool wino_gemm_ok(int form, int split) {
+  if (split != 0 && split != 1) return false;
+  return form == MSOCR_WINO_4X2 || (form == MSOCR_WINO_2X2 && !split) || (form == MSOCR_WINO_4X4 && split);
+}
+
+extern "C" int64_t msocr_winograd_workspace_bytes(const msocr_conv_desc* d, int form) {
+  WinoGeom g;
+  if (!wino_geom(d, form, &g)) return -1;
+  return wino_points(form) * g.Mt * ((int64_t)d->Cin + d->Cout) * (int64_t)sizeof(float);
+}
+
+static int wino_launch_input(const msocr_conv_desc* d, int form, const WinoGeom& g, const void* in, void* workspace, void* stream) {
+  if (!in || !workspace || (((uintptr_t)in | (uintptr_t)workspace) & 15)) return MSOCR_E_ARG;
+  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
+  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
+  const dim3 grid((unsigned)nb_in), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+  const float* x = (const float*)in;
+  float* V = (float*)workspace;
+  if (form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
+  else if (form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
+  else MSOCR_LAUNCH(wino44_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
+  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
 // The three stages of msocr_conv3x3_winograd as separate entry points (same kernels): tests and the per-kernel roofline of
-// bench.py time them one by one.  V = workspace, Mw = workspace + 16 * tiles * Cin floats.
-extern "C" int msocr_winograd_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream) {
+// bench.py time them one by one.  V = workspace, Mw = workspace + points * tiles * Cin floats.
+extern "C" int msocr_winograd_input_transform(const msocr_conv_desc* d, int form, const void* in, void* workspace, void* stream) {
   WinoGeom g;
-  if (wino_check(d, &g) != MSOCR_OK || !in || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(wino_input_kernel, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, g, (float*)workspace);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  if (wino_check(d, form, &g) != MSOCR_OK) return MSOCR_E_ARG;
+  return wino_launch_input(d, form, g, in, workspace, stream);
 }
 
-extern "C" int msocr_winograd_gemm(const msocr_conv_desc* d, const float* u_weight, void* workspace, void* stream) {
+// split = 0: u = [P][Cout][Cin] f32 (exact-f32 MFMA); split = 1: u = K-tile-major bf16 planes [3][P][Cin/32][Cout][32], the P GEMMs on
+// the bf16 matrix pipes with exactly split operands (conv_split.hip / conv_split_pp.hip; V is split in registers)
+extern "C" int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const void* u, void* workspace, void* stream) {
   WinoGeom g;
-  if (wino_check(d, &g) != MSOCR_OK || !u_weight || !workspace) return MSOCR_E_ARG;
+  if (!wino_gemm_ok(form, split) || wino_check(d, form, &g) != MSOCR_OK || !u || !workspace) return MSOCR_E_ARG;
+  if (split && (d->Cin % 32 || d->Cout % 64)) return MSOCR_E_ARG;
+  const int P = wino_points(form);
   float* V = (float*)workspace;
-  return msocr_internal_gemm_f32_batched(V, u_weight, V + 16 * g.Mt * (long)d->Cin, g.Mt, d->Cout, d->Cin, 16, (hipStream_t)stream);
+  float* Mw = V + P * g.Mt * (long)d->Cin;
+  if (split) return msocr_internal_gemm_split_batched(V, (const uint16_t*)u, Mw, g.Mt, d->Cout, d->Cin, P, (hipStream_t)stream);
+  return msocr_internal_gemm_f32_batched(V, (const float*)u, Mw, g.Mt, d->Cout, d->Cin, P, (hipStream_t)stream);
 }
 
-extern "C" int msocr_winograd_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
-                                               void* out, void* stream) {
+extern "C" int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias,
+                                               const void* residual, void* out, void* stream) {
   WinoGeom g;
-  if (wino_check(d, &g) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
+  if (wino_check(d, form, &g) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
   if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
   const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
   if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
   if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
   const long nb_out = (g.Mt * (d->Cout / 4) + 255) / 256;
   if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
-  const float* Mw = (const float*)workspace + 16 * g.Mt * (long)d->Cin;
-  MSOCR_LAUNCH(wino_output_kernel, dim3((unsigned)nb_out), dim3(256), 0, (hipStream_t)stream, Mw, d->Cout, g, bias,
-               has_res ? (const float*)residual : nullptr, (long)d->res_ld, (d->flags & MSOCR_CONV_RELU) ? 1 : 0, (float*)out,
-               (long)d->out_ld);
+  const float* Mw = (const float*)workspace + wino_points(form) * g.Mt * (long)d->Cin;
+  const float* rp = has_res ? (const float*)residual : nullptr;
+  const int relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
+  const dim3 grid((unsigned)nb_out), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+  float* o = (float*)out;
+  if (form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
+  else if (form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
+  else MSOCR_LAUNCH(wino44_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
-extern "C" int msocr_conv3x3_winograd(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
+extern "C" int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int split, const void* in, const void* u, const float* bias,
                                       const void* residual, void* out, void* workspace, void* stream) {
-  if (!u_weight) return MSOCR_E_ARG;
-  int rc = msocr_winograd_input_transform(d, in, workspace, stream);
+  if (!u || !wino_gemm_ok(form, split)) return MSOCR_E_ARG;
+  int rc = msocr_winograd_input_transform(d, form, in, workspace, stream);
   if (rc != MSOCR_OK) return rc;
-  rc = msocr_winograd_gemm(d, u_weight, workspace, stream);
+  rc = msocr_winograd_gemm(d, form, split, u, workspace, stream);
   if (rc != MSOCR_OK) return rc;
-  return msocr_winograd_output_transform(d, workspace, bias, residual, out, stream);
-}
-
-// =====================================================================================================================
-// The TALL form: F(4,3) along H x F(2,3) along W.  A 6x4 input tile gives a 4x2 output tile through 24 transform-domain
-// products: 3 multiplies per output instead of 4 (direct: 9), V / Mw expanded 3x instead of 4x.  Only the H axis takes the
-// 6-point transform: on the textbook points {0, +-1, +-2, inf} its constants (4, 5, 2, 8; 1/6, 1/24 in the weights) grew the f32
-// rounding error of the layer by ~2.5x rms over F(2x2) (measured against f64: DESIGN.md section 4), where the 6x6 form would grow
-// it 6x.  Since round 4 the H axis runs on the points {0, +-3/2, +-2/3, inf} (wino44_bt / wino44_at above): half that error, and
-// the 6x6 form on them (wino44_*, below) comes out where this form used to be.  ops.conv2d() picks the tall form for the Cin = 64
-// layers (fused kernels) and where the square form does not pay; the 2x2 form when 24 * ceil(H/4) >= 16 * ceil(H/2).
-//   V[(xi*4+nu)][tile][c], xi = 0..5 (H axis), nu = 0..3 (W axis); Mw likewise; U from msocr_winograd42_weights_host.
-// =====================================================================================================================
-__global__ __launch_bounds__(256) void wino42_input_kernel(const float* __restrict__ in, long sN, long sH, long sW, int C,
-                                                            WinoGeom g, float* __restrict__ V) {
-  const int cch = C >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
-  if (t >= g.Mt) return;
-  const int tw = (int)(t % g.TW);
-  const long r = t / g.TW;
-  const int th = (int)(r % g.TH);
-  const int n = (int)(r / g.TH);
-  const int h0 = 4 * th - 1, w0 = 2 * tw - 1;
-  const float* base = in + (long)n * sN + c;
-  // W axis first (B4^T per row as the row is loaded), then the 6-point H transform per column
-  f32x4 q[6][4];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int hi = h0 + i;
-    const bool okh = (unsigned)hi < (unsigned)g.H;
-    f32x4 d[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int wi = w0 + j;
-      const bool ok = okh && (unsigned)wi < (unsigned)g.W;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? base + (long)hi * sH + (long)wi * sW : base);
-      d[j] = ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    q[i][0] = d[0] - d[2];
-    q[i][1] = d[1] + d[2];
-    q[i][2] = d[2] - d[1];
-    q[i][3] = d[1] - d[3];
-  }
-  const long plane = g.Mt * (long)C;
-  float* o = V + t * (long)C + c;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x4 col[6] = {q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j]};
-    f32x4 v[6];
-    wino44_bt(col, v);   // H axis on the accuracy-chosen points (round 4: half the rounding error of {0, +-1, +-2})
-#pragma unroll
-    for (int i = 0; i < 6; ++i) *reinterpret_cast<f32x4*>(o + (i * 4 + j) * plane) = v[i];
-  }
-}
-
-__global__ __launch_bounds__(256) void wino42_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,
-                                                             const float* __restrict__ bias, const float* __restrict__ res,
-                                                             long res_ld, int relu, float* __restrict__ out, long out_ld) {
-  const int cch = Cout >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
-  if (t >= g.Mt) return;
-  const int tw = (int)(t % g.TW);
-  const long r = t / g.TW;
-  const int th = (int)(r % g.TH);
-  const int n = (int)(r / g.TH);
-  const long plane = g.Mt * (long)Cout;
-  const float* mp = Mw + t * (long)Cout + c;
-  // H axis first (A6^T per column as the column is loaded), then A4^T along W
-  f32x4 s[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f32x4 m[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const f32x4*>(mp + (i * 4 + j) * plane);
-    f32x4 y6[4];
-    wino44_at(m, y6);
-    s[0][j] = y6[0]; s[1][j] = y6[1]; s[2][j] = y6[2]; s[3][j] = y6[3];
-  }
-  f32x4 b = {0.f, 0.f, 0.f, 0.f};
-  if (bias) b = *reinterpret_cast<const f32x4*>(bias + c);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ho = 4 * th + i;
-    if (ho >= g.H) continue;
-    f32x4 y[2];
-    y[0] = (s[i][0] + s[i][1]) + s[i][2];
-    y[1] = (s[i][1] - s[i][2]) - s[i][3];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int wo = 2 * tw + j;
-      if (wo >= g.W) continue;
-      const long pix = ((long)n * g.H + ho) * g.W + wo;
-      f32x4 v = y[j] + b;
-      if (res) v += *reinterpret_cast<const f32x4*>(res + pix * res_ld + c);
-      if (relu) {
-        v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-      }
-      *reinterpret_cast<f32x4*>(out + pix * out_ld + c) = v;
-    }
-  }
-}
-
-static bool wino42_geom(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino_geom(d, g)) return false;
-  g->TH = (d->H + 3) / 4;
-  g->Mt = (long)d->N * g->TH * g->TW;
-  return 24 * g->Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) <= 0x3fffffffffffL;
-}
-
-extern "C" int64_t msocr_conv3x3_winograd42_workspace_bytes(const msocr_conv_desc* d) {
-  WinoGeom g;
-  if (!wino42_geom(d, &g)) return -1;
-  return 24 * g.Mt * ((int64_t)d->Cin + d->Cout) * (int64_t)sizeof(float);
-}
-
-static int wino42_check(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino42_geom(d, g)) return MSOCR_E_ARG;
-  if (d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4 || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
-  return MSOCR_OK;
-}
-
-extern "C" int msocr_winograd42_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino42_check(d, &g) != MSOCR_OK || !in || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(wino42_input_kernel, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, g, (float*)workspace);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-extern "C" int msocr_winograd42_gemm(const msocr_conv_desc* d, const float* u_weight, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino42_check(d, &g) != MSOCR_OK || !u_weight || !workspace) return MSOCR_E_ARG;
-  float* V = (float*)workspace;
-  return msocr_internal_gemm_f32_batched(V, u_weight, V + 24 * g.Mt * (long)d->Cin, g.Mt, d->Cout, d->Cin, 24, (hipStream_t)stream);
-}
-
-// The 24 transform-domain GEMMs on the bf16 matrix pipes with exactly split operands (conv_split.hip): V split in registers,
-// U given as three bf16 planes [3][24][Cout][Cin] (msocr_split_bf16x3_host of msocr_winograd42_weights_host's output).
-extern "C" int msocr_winograd42_gemm_split(const msocr_conv_desc* d, const void* u_planes, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino42_check(d, &g) != MSOCR_OK || !u_planes || !workspace || d->Cin % 32 || d->Cout % 64) return MSOCR_E_ARG;
-  float* V = (float*)workspace;
-  return msocr_internal_gemm_split_batched(V, (const uint16_t*)u_planes, V + 24 * g.Mt * (long)d->Cin, g.Mt, d->Cout, d->Cin, 24,
-                                           (hipStream_t)stream);
-}
-
-extern "C" int msocr_winograd42_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias,
-                                                 const void* residual, void* out, void* stream) {
-  WinoGeom g;
-  if (wino42_check(d, &g) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
-  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
-  if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
-  const long nb_out = (g.Mt * (d->Cout / 4) + 255) / 256;
-  if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
-  const float* Mw = (const float*)workspace + 24 * g.Mt * (long)d->Cin;
-  MSOCR_LAUNCH(wino42_output_kernel, dim3((unsigned)nb_out), dim3(256), 0, (hipStream_t)stream, Mw, d->Cout, g, bias,
-               has_res ? (const float*)residual : nullptr, (long)d->res_ld, (d->flags & MSOCR_CONV_RELU) ? 1 : 0, (float*)out,
-               (long)d->out_ld);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-extern "C" int msocr_conv3x3_winograd42(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
-                                        const void* residual, void* out, void* workspace, void* stream) {
-  if (!u_weight) return MSOCR_E_ARG;
-  int rc = msocr_winograd42_input_transform(d, in, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  rc = msocr_winograd42_gemm(d, u_weight, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  return msocr_winograd42_output_transform(d, workspace, bias, residual, out, stream);
-}
-
-extern "C" int msocr_conv3x3_winograd42_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
-                                              const void* residual, void* out, void* workspace, void* stream) {
-  if (!u_planes) return MSOCR_E_ARG;
-  int rc = msocr_winograd42_input_transform(d, in, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  rc = msocr_winograd42_gemm_split(d, u_planes, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  return msocr_winograd42_output_transform(d, workspace, bias, residual, out, stream);
-}
-
-// =====================================================================================================================
-// F(4,3) x F(4,3) on ACCURACY-CHOSEN interpolation points (round 4): 36 transform points per 4 x 4 outputs = 2.25 multiplies and
-// workspace words per output instead of the tall form's 3.  With the textbook points {0, +-1, +-2, inf} the square form's rounding
-// error is 4.7x the tall form's and cannot pass the f64 arbitration of the tolerances (tests/test_gpu_f64.py); with
-// {0, +-3/2, +-2/3, inf} — reciprocal pairs keep the Vandermonde entries within [8/27, 27/8] — an f32 simulation of the whole
-// pipeline of transforms measures 1.05x the tall form's error (and 0.5x for the tall form itself on these points;
-// tools/winograd_points.py, profiles/r04_winograd_points.txt).  Matrices (Cook-Toom, wincnn scaling: G carries 1 / prod(a_j - a_l)):
-//   B^T d:  r0 = d0 - 97/36 d2 + d4          r5 = d1 - 97/36 d3 + d5
-//           e1 = d4 - 4/9 d2,  o1 = 3/2 d3 - 2/3 d1:   r1 = e1 + o1,  r2 = e1 - o1        (points +-3/2)
-//           e2 = d4 - 9/4 d2,  o2 = 2/3 d3 - 3/2 d1:   r3 = e2 + o2,  r4 = e2 - o2        (points +-2/3)
-//   A^T m:  y0 = m0 + (m1 + m2) + (m3 + m4)             y1 = 3/2 (m1 - m2) + 2/3 (m3 - m4)
-//           y2 = 9/4 (m1 + m2) + 4/9 (m3 + m4)          y3 = 27/8 (m1 - m2) + 8/27 (m3 - m4) + m5
-//   G (host, f64): rows [1,0,0], [8,+-12,18]/65, [-81/2,-+27,-18]/65, [0,0,1].
-//   V[(xi*6+nu)][tile][c], xi = 0..5 (H axis), nu = 0..5 (W axis); Mw likewise; U from msocr_winograd44_weights_host.
-// Reference layers: the 3x3 / stride 1 / pad 1 convolutions of seresnet31.py:37-67 and of torchvision's Bottleneck (east.py:13-30).
-// =====================================================================================================================
-__global__ __launch_bounds__(256) void wino44_input_kernel(const float* __restrict__ in, long sN, long sH, long sW, int C,
-                                                            WinoGeom g, float* __restrict__ V) {
-  const int cch = C >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
-  if (t >= g.Mt) return;
-  const int tw = (int)(t % g.TW);
-  const long r = t / g.TW;
-  const int th = (int)(r % g.TH);
-  const int n = (int)(r / g.TH);
-  const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
-  const float* base = in + (long)n * sN + c;
-  // W axis first (B^T per row as the row is loaded), then the H transform per column
-  f32x4 q[6][6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int hi = h0 + i;
-    const bool okh = (unsigned)hi < (unsigned)g.H;
-    f32x4 d[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int wi = w0 + j;
-      const bool ok = okh && (unsigned)wi < (unsigned)g.W;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? base + (long)hi * sH + (long)wi * sW : base);
-      d[j] = ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    wino44_bt(d, q[i]);
-  }
-  const long plane = g.Mt * (long)C;
-  float* o = V + t * (long)C + c;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const f32x4 col[6] = {q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j]};
-    f32x4 v[6];
-    wino44_bt(col, v);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) *reinterpret_cast<f32x4*>(o + (i * 6 + j) * plane) = v[i];
-  }
-}
-
-__global__ __launch_bounds__(256) void wino44_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,
-                                                             const float* __restrict__ bias, const float* __restrict__ res,
-                                                             long res_ld, int relu, float* __restrict__ out, long out_ld) {
-  const int cch = Cout >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
-  if (t >= g.Mt) return;
-  const int tw = (int)(t % g.TW);
-  const long r = t / g.TW;
-  const int th = (int)(r % g.TH);
-  const int n = (int)(r / g.TH);
-  const long plane = g.Mt * (long)Cout;
-  const float* mp = Mw + t * (long)Cout + c;
-  // H axis first (A^T per column as the column is loaded), then A^T along W
-  f32x4 s[4][6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    f32x4 m[6], y[4];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const f32x4*>(mp + (i * 6 + j) * plane);
-    wino44_at(m, y);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) s[a][j] = y[a];
-  }
-  f32x4 b = {0.f, 0.f, 0.f, 0.f};
-  if (bias) b = *reinterpret_cast<const f32x4*>(bias + c);
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int ho = 4 * th + a;
-    if (ho >= g.H) continue;
-    f32x4 y[4];
-    wino44_at(s[a], y);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int wo = 4 * tw + j;
-      if (wo >= g.W) continue;
-      const long pix = ((long)n * g.H + ho) * g.W + wo;
-      f32x4 v = y[j] + b;
-      if (res) v += *reinterpret_cast<const f32x4*>(res + pix * res_ld + c);
-      if (relu) {
-        v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-      }
-      *reinterpret_cast<f32x4*>(out + pix * out_ld + c) = v;
-    }
-  }
-}
-
-static bool wino44_geom(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino_geom(d, g)) return false;
-  g->TH = (d->H + 3) / 4;
-  g->TW = (d->W + 3) / 4;
-  g->Mt = (long)d->N * g->TH * g->TW;
-  return 36 * g->Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) <= 0x3fffffffffffL;
-}
-
-extern "C" int64_t msocr_conv3x3_winograd44_workspace_bytes(const msocr_conv_desc* d) {
-  WinoGeom g;
-  if (!wino44_geom(d, &g)) return -1;
-  return 36 * g.Mt * ((int64_t)d->Cin + d->Cout) * (int64_t)sizeof(float);
-}
-
-static int wino44_check(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino44_geom(d, g)) return MSOCR_E_ARG;
-  if (d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4 || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
-  return MSOCR_OK;
-}
-
-extern "C" int msocr_winograd44_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino44_check(d, &g) != MSOCR_OK || !in || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(wino44_input_kernel, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, g, (float*)workspace);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-// The 36 transform-domain GEMMs on the bf16 matrix pipes with exactly split operands (conv_split_pp.hip): V split in registers,
-// U given as K-tile-major bf16 planes [3][36][Cin/32][Cout][32] of msocr_winograd44_weights_host's output.
-extern "C" int msocr_winograd44_gemm_split(const msocr_conv_desc* d, const void* u_planes, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino44_check(d, &g) != MSOCR_OK || !u_planes || !workspace || d->Cin % 32 || d->Cout % 64) return MSOCR_E_ARG;
-  float* V = (float*)workspace;
-  return msocr_internal_gemm_split_batched(V, (const uint16_t*)u_planes, V + 36 * g.Mt * (long)d->Cin, g.Mt, d->Cout, d->Cin, 36,
-                                           (hipStream_t)stream);
-}
-
-extern "C" int msocr_winograd44_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias,
-                                                 const void* residual, void* out, void* stream) {
-  WinoGeom g;
-  if (wino44_check(d, &g) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
-  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
-  if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
-  const long nb_out = (g.Mt * (d->Cout / 4) + 255) / 256;
-  if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
-  const float* Mw = (const float*)workspace + 36 * g.Mt * (long)d->Cin;
-  MSOCR_LAUNCH(wino44_output_kernel, dim3((unsigned)nb_out), dim3(256), 0, (hipStream_t)stream, Mw, d->Cout, g, bias,
-               has_res ? (const float*)residual : nullptr, (long)d->res_ld, (d->flags & MSOCR_CONV_RELU) ? 1 : 0, (float*)out,
-               (long)d->out_ld);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-extern "C" int msocr_conv3x3_winograd44_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
-                                              const void* residual, void* out, void* workspace, void* stream) {
-  if (!u_planes) return MSOCR_E_ARG;
-  int rc = msocr_winograd44_input_transform(d, in, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  rc = msocr_winograd44_gemm_split(d, u_planes, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  return msocr_winograd44_output_transform(d, workspace, bias, residual, out, stream);
-}
-
-// U[xi*6+nu][co][c] = sum_{kh,kw} G[xi][kh] G[nu][kw] w[co][kh][kw][c] for the points {0, 3/2, -3/2, 2/3, -2/3, inf}, f64, rounded once.
-// HOST function like msocr_winograd42_weights_host.
-extern "C" int msocr_winograd44_weights_host(const float* w_khwc, int Cout, int Cin, float* u_out) {
-  if (!w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
-  static const double G[6][3] = {{1.0, 0.0, 0.0},
-                                 {8.0 / 65, 12.0 / 65, 18.0 / 65},     {8.0 / 65, -12.0 / 65, 18.0 / 65},
-                                 {-81.0 / 130, -27.0 / 65, -18.0 / 65}, {-81.0 / 130, 27.0 / 65, -18.0 / 65},
-                                 {0.0, 0.0, 1.0}};
-  const long plane = (long)Cout * Cin;
-  for (int co = 0; co < Cout; ++co) {
-    const float* w = w_khwc + (long)co * 9 * Cin;
-    for (int c = 0; c < Cin; ++c) {
-      double gw[6][3];  // G g
-      for (int xi = 0; xi < 6; ++xi)
-        for (int kw = 0; kw < 3; ++kw)
-          gw[xi][kw] = G[xi][0] * w[(0 * 3 + kw) * Cin + c] + G[xi][1] * w[(1 * 3 + kw) * Cin + c] + G[xi][2] * w[(2 * 3 + kw) * Cin + c];
-      for (int xi = 0; xi < 6; ++xi)
-        for (int nu = 0; nu < 6; ++nu)
-          u_out[(xi * 6 + nu) * plane + (long)co * Cin + c] =
-              (float)(gw[xi][0] * G[nu][0] + gw[xi][1] * G[nu][1] + gw[xi][2] * G[nu][2]);
-    }
-  }
-  return MSOCR_OK;
+  return msocr_winograd_output_transform(d, form, workspace, bias, residual, out, stream);
 }
 
 // =====================================================================================================================
@@ -1038,42 +769,28 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
   }
 }
 
-static int wino42_fused_check(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino42_geom(d, g) || d->Cin != 64) return MSOCR_E_ARG;
-  if (d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
+static int wino_fused64_check(const msocr_conv_desc* d, WinoGeom* g) {
+  if (!wino_geom(d, MSOCR_WINO_4X2, g) || d->Cin != 64 || !wino_strides_ok(d) || d->out_ld < d->Cout) return MSOCR_E_ARG;
   if (d->flags & MSOCR_CONV_POOL2) {
     if ((d->H & 1) || (d->W & 1) || (d->flags & MSOCR_CONV_RESIDUAL)) return MSOCR_E_ARG;
   }
   return MSOCR_OK;
 }
 
-extern "C" int64_t msocr_conv3x3_winograd42_fused_workspace_bytes(const msocr_conv_desc* d) {
+extern "C" int64_t msocr_winograd_fused64_workspace_bytes(const msocr_conv_desc* d) {
   WinoGeom g;
-  if (wino42_fused_check(d, &g) != MSOCR_OK) return -1;
+  if (wino_fused64_check(d, &g) != MSOCR_OK) return -1;
   return 24 * g.Mt * (int64_t)d->Cin * (int64_t)sizeof(float);
 }
 
-// stage 2 of msocr_conv3x3_winograd42_fused (stage 1 is msocr_winograd42_input_transform): V in the workspace -> out
-static int wino42_fused_launch(const msocr_conv_desc* d, const void* u_weight, bool split, const void* workspace, const float* bias,
-                               const void* residual, void* out, void* stream);
-
-extern "C" int msocr_winograd42_fused_gemm_output(const msocr_conv_desc* d, const float* u_weight, const void* workspace,
+// stage 2 of msocr_conv3x3_winograd_fused64 (stage 1 is msocr_winograd_input_transform of the 4X2 form): V in the workspace -> out.
+// split = 0: u = [24][Cout][64] f32; split = 1: u = three bf16 planes [3][24][Cout][64] (msocr_split_bf16x3_host), the GEMMs on the
+// bf16 matrix pipes with exactly split operands
+extern "C" int msocr_winograd_fused64_gemm_output(const msocr_conv_desc* d, int split, const void* u, const void* workspace,
                                                   const float* bias, const void* residual, void* out, void* stream) {
-  return wino42_fused_launch(d, u_weight, false, workspace, bias, residual, out, stream);
-}
-
-// the same with U as three bf16 planes [3][24][Cout][64] (msocr_split_bf16x3_host of msocr_winograd42_weights_host's output): the
-// GEMMs run on the bf16 matrix pipes with exactly split operands
-extern "C" int msocr_winograd42_fused_gemm_output_split(const msocr_conv_desc* d, const void* u_planes, const void* workspace,
-                                                        const float* bias, const void* residual, void* out, void* stream) {
-  return wino42_fused_launch(d, u_planes, true, workspace, bias, residual, out, stream);
-}
-
-static int wino42_fused_launch(const msocr_conv_desc* d, const void* u_weight, bool split, const void* workspace, const float* bias,
-                               const void* residual, void* out, void* stream) {
   WinoGeom g;
-  if (wino42_fused_check(d, &g) != MSOCR_OK || !u_weight || !workspace || !out) return MSOCR_E_ARG;
-  if (((uintptr_t)workspace | (uintptr_t)u_weight) & 15) return MSOCR_E_ARG;
+  if ((split != 0 && split != 1) || wino_fused64_check(d, &g) != MSOCR_OK || !u || !workspace || !out) return MSOCR_E_ARG;
+  if (((uintptr_t)workspace | (uintptr_t)u) & 15) return MSOCR_E_ARG;
   const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
   if (has_res && (!residual || d->res_ld < d->Cout)) return MSOCR_E_ARG;
   const long nblk = ((g.Mt + 31) / 32) * (long)(d->Cout / 32);
@@ -1090,7 +807,7 @@ static int wino42_fused_launch(const msocr_conv_desc* d, const void* u_weight, b
     const long nblk2 = ((g.Mt + 63) / 64) * (long)(d->Cout / 64);
     if (nblk2 <= 0 || nblk2 > 0x7fffffffL) return MSOCR_E_ARG;
     const dim3 grid2((unsigned)nblk2);
-    const unsigned short* up = (const unsigned short*)u_weight;
+    const unsigned short* up = (const unsigned short*)u;
     if (d->flags & MSOCR_CONV_POOL2)
       MSOCR_LAUNCH((wino42_fused64_v2_kernel<true>), grid2, blk, 0, st, ws, up, d->Cout, g, bias, (const float*)nullptr, 0L, relu, (float*)out, (long)d->out_ld);
     else
@@ -1098,85 +815,48 @@ static int wino42_fused_launch(const msocr_conv_desc* d, const void* u_weight, b
     return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
   }
   if (d->flags & MSOCR_CONV_POOL2) {
-    if (split) MSOCR_LAUNCH((wino42_fused64_kernel<true, true>), grid, blk, 0, st, ws, u_weight, d->Cout, g, bias, (const float*)nullptr, 0L, relu, (float*)out, (long)d->out_ld);
-    else MSOCR_LAUNCH((wino42_fused64_kernel<true, false>), grid, blk, 0, st, ws, u_weight, d->Cout, g, bias, (const float*)nullptr, 0L, relu, (float*)out, (long)d->out_ld);
+    if (split) MSOCR_LAUNCH((wino42_fused64_kernel<true, true>), grid, blk, 0, st, ws, u, d->Cout, g, bias, (const float*)nullptr, 0L, relu, (float*)out, (long)d->out_ld);
+    else MSOCR_LAUNCH((wino42_fused64_kernel<true, false>), grid, blk, 0, st, ws, u, d->Cout, g, bias, (const float*)nullptr, 0L, relu, (float*)out, (long)d->out_ld);
   } else {
-    if (split) MSOCR_LAUNCH((wino42_fused64_kernel<false, true>), grid, blk, 0, st, ws, u_weight, d->Cout, g, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
-    else MSOCR_LAUNCH((wino42_fused64_kernel<false, false>), grid, blk, 0, st, ws, u_weight, d->Cout, g, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
+    if (split) MSOCR_LAUNCH((wino42_fused64_kernel<false, true>), grid, blk, 0, st, ws, u, d->Cout, g, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
+    else MSOCR_LAUNCH((wino42_fused64_kernel<false, false>), grid, blk, 0, st, ws, u, d->Cout, g, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
   }
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
-extern "C" int msocr_conv3x3_winograd42_fused(const msocr_conv_desc* d, const void* in, const float* u_weight, const float* bias,
+extern "C" int msocr_conv3x3_winograd_fused64(const msocr_conv_desc* d, int split, const void* in, const void* u, const float* bias,
                                               const void* residual, void* out, void* workspace, void* stream) {
   WinoGeom g;
-  if (wino42_fused_check(d, &g) != MSOCR_OK || !in || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(wino42_input_kernel, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, g, (float*)workspace);
-  if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
-  return msocr_winograd42_fused_gemm_output(d, u_weight, workspace, bias, residual, out, stream);
+  if ((split != 0 && split != 1) || wino_fused64_check(d, &g) != MSOCR_OK || !u) return MSOCR_E_ARG;
+  const int rc = wino_launch_input(d, MSOCR_WINO_4X2, g, in, workspace, stream);
+  if (rc != MSOCR_OK) return rc;
+  return msocr_winograd_fused64_gemm_output(d, split, u, workspace, bias, residual, out, stream);
 }
 
-extern "C" int msocr_conv3x3_winograd42_fused_split(const msocr_conv_desc* d, const void* in, const void* u_planes, const float* bias,
-                                                    const void* residual, void* out, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino42_fused_check(d, &g) != MSOCR_OK || !in || !workspace || !u_planes) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(wino42_input_kernel, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, g, (float*)workspace);
-  if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
-  return msocr_winograd42_fused_gemm_output_split(d, u_planes, workspace, bias, residual, out, stream);
-}
-
-// U[xi*4+nu][co][c] = sum_{kh,kw} G6[xi][kh] G4[nu][kw] w[co][kh][kw][c] (xi = 0..5 on the kernel's H axis), f64, rounded once.
-// HOST function like msocr_winograd_weights_host.
-extern "C" int msocr_winograd42_weights_host(const float* w_khwc, int Cout, int Cin, float* u_out) {
-  if (!w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
-  // H axis: the points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4), as msocr_winograd44_weights_host
-  static const double G6[6][3] = {{1.0, 0.0, 0.0},
+// U[xi*PW+nu][co][c] = sum_{kh,kw} Gh[xi][kh] Gw[nu][kw] w[co][kh][kw][c] (xi on the kernel's H axis), evaluated in f64 (G g over kh
+// first, then over kw) and rounded once to f32.  HOST function (runs at weight-load time): w_khwc and u_out are host pointers.
+extern "C" int msocr_winograd_weights_host(int form, const float* w_khwc, int Cout, int Cin, float* u_out) {
+  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4 || !w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
+  static const double G4[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};  // F(2,3) on {0, 1, -1, inf}
+  static const double G6[6][3] = {{1.0, 0.0, 0.0},                                                         // F(4,3): wino44_bt's points
                                   {8.0 / 65, 12.0 / 65, 18.0 / 65},     {8.0 / 65, -12.0 / 65, 18.0 / 65},
                                   {-81.0 / 130, -27.0 / 65, -18.0 / 65}, {-81.0 / 130, 27.0 / 65, -18.0 / 65},
                                   {0.0, 0.0, 1.0}};
-  static const double G4[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+  const int PH = kWinoTile[form][0] + 2, PW = kWinoTile[form][1] + 2;
+  const double(*Gh)[3] = PH == 6 ? G6 : G4;
+  const double(*Gw)[3] = PW == 6 ? G6 : G4;
   const long plane = (long)Cout * Cin;
   for (int co = 0; co < Cout; ++co) {
     const float* w = w_khwc + (long)co * 9 * Cin;
     for (int c = 0; c < Cin; ++c) {
-      double gw[6][3];  // G6 g
-      for (int xi = 0; xi < 6; ++xi)
+      double gw[6][3];  // Gh g
+      for (int xi = 0; xi < PH; ++xi)
         for (int kw = 0; kw < 3; ++kw)
-          gw[xi][kw] = G6[xi][0] * w[(0 * 3 + kw) * Cin + c] + G6[xi][1] * w[(1 * 3 + kw) * Cin + c] + G6[xi][2] * w[(2 * 3 + kw) * Cin + c];
-      for (int xi = 0; xi < 6; ++xi)
-        for (int nu = 0; nu < 4; ++nu)
-          u_out[(xi * 4 + nu) * plane + (long)co * Cin + c] =
-              (float)(gw[xi][0] * G4[nu][0] + gw[xi][1] * G4[nu][1] + gw[xi][2] * G4[nu][2]);
-    }
-  }
-  return MSOCR_OK;
-}
-
-// U[xi*4+nu][co][c] = sum_{kh,kw} G[xi][kh] G[nu][kw] w[co][kh][kw][c], evaluated in f64 and rounded once to f32.
-// HOST function (runs at weight-load time): w_khwc and u_out are host pointers.
-extern "C" int msocr_winograd_weights_host(const float* w_khwc, int Cout, int Cin, float* u_out) {
-  if (!w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
-  static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-  const long plane = (long)Cout * Cin;
-  for (int co = 0; co < Cout; ++co) {
-    const float* w = w_khwc + (long)co * 9 * Cin;
-    for (int c = 0; c < Cin; ++c) {
-      double gw[4][3];  // G g
-      for (int xi = 0; xi < 4; ++xi)
-        for (int kw = 0; kw < 3; ++kw)
-          gw[xi][kw] = G[xi][0] * w[(0 * 3 + kw) * Cin + c] + G[xi][1] * w[(1 * 3 + kw) * Cin + c] + G[xi][2] * w[(2 * 3 + kw) * Cin + c];
-      for (int xi = 0; xi < 4; ++xi)
-        for (int nu = 0; nu < 4; ++nu)
-          u_out[(xi * 4 + nu) * plane + (long)co * Cin + c] =
-              (float)(gw[xi][0] * G[nu][0] + gw[xi][1] * G[nu][1] + gw[xi][2] * G[nu][2]);
+          gw[xi][kw] = Gh[xi][0] * w[(0 * 3 + kw) * Cin + c] + Gh[xi][1] * w[(1 * 3 + kw) * Cin + c] + Gh[xi][2] * w[(2 * 3 + kw) * Cin + c];
+      for (int xi = 0; xi < PH; ++xi)
+        for (int nu = 0; nu < PW; ++nu)
+          u_out[(xi * PW + nu) * plane + (long)co * Cin + c] =
+              (float)(gw[xi][0] * Gw[nu][0] + gw[xi][1] * Gw[nu][1] + gw[xi][2] * Gw[nu][2]);
     }
   }
   return MSOCR_OK;

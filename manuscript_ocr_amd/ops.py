@@ -118,6 +118,18 @@ def _square_pays(W):
     return 36 * (-(-W // 4)) < 24 * (-(-W // 2))
 
 
+# The Winograd tile forms (csrc/winograd.hip, include/msocr.h MSOCR_WINO_*): form id -> (PROFILE tag stem, transform points, output tile)
+WINO_FORMS = {nat.WINO_2X2: ("winograd", 16, (2, 2)), nat.WINO_4X2: ("winograd42", 24, (4, 2)), nat.WINO_4X4: ("winograd44", 36, (4, 4))}
+
+
+def _wino_weights(wh, form):
+    """Host [Cout,3,3,Cin] f32 weight -> U [points, Cout, Cin] f32 (msocr_winograd_weights_host: f64, rounded once)."""
+    Cout, _, _, Cin = wh.shape
+    u = torch.empty((WINO_FORMS[form][1], Cout, Cin), dtype=torch.float32)
+    nat.check(nat.lib().msocr_winograd_weights_host(form, wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_weights_host")
+    return u
+
+
 # Cin == 64 layers (TRBA conv0b, the 3x3s of ResNet-50 layer1): tall Winograd with the 24 GEMMs (K = 64) and the output transform
 # fused in one kernel (csrc/winograd.hip, wino42_fused64_kernel) — unfused, such a layer is HBM-bound on Mw.  conv2d(pool2=True)
 # folds the following 2x2/2 max-pool into the same kernel.  MSOCR_WINO_FUSED64=0 keeps these layers on the direct kernel.
@@ -183,14 +195,12 @@ def attach_split(w, split=None):
 
 def attach_winograd(w, split=None, square=True):
     """Load-time: give a [Cout,3,3,Cin] f32 device weight its transform-domain twins U = G g G^T ([16,Cout,Cin] f32 for F(2x2,3x3),
-    [24,Cout,Cin] for the tall form F(4,3) x F(2,3); computed on the host in f64 by msocr_winograd[42]_weights_host).  conv2d() then
-    takes the Winograd path for 3x3/1/1 calls."""
+    [24,Cout,Cin] for the tall form F(4,3) x F(2,3), planes of [36,Cout,Cin] for the square form; computed on the host in f64 by
+    msocr_winograd_weights_host).  conv2d() then takes the Winograd path for 3x3/1/1 calls."""
     Cout, KH, KW, Cin = w.shape
     if (WINOGRAD_MIN_CIN and WINOGRAD_FUSED64 and WINOGRAD_TALL and w.dtype == torch.float32 and KH == 3 and KW == 3 and Cin == 64
             and Cin < WINOGRAD_MIN_CIN and Cout % 32 == 0):
-        wh = w.detach().cpu().contiguous()
-        u42 = torch.empty((24, Cout, Cin), dtype=torch.float32)
-        nat.check(nat.lib().msocr_winograd42_weights_host(wh.data_ptr(), Cout, Cin, u42.data_ptr()), "winograd42_weights_host")
+        u42 = _wino_weights(w.detach().cpu().contiguous(), nat.WINO_4X2)
         w._msocr_wino42_fused = u42.to(w.device)
         # the K = 64 GEMMs on the bf16 pipes pay only for the wide layer (TRBA conv0b, 64 -> 128 + pool: 2.43 -> 2.21 ms per 960 crops);
         # with 64 output channels the kernel is bound by staging and barriers either way (0.84 -> 0.86 ms) and stays exact
@@ -202,73 +212,64 @@ def attach_winograd(w, split=None, square=True):
             and Cout % 32 == 0):
         return w
     wh = w.detach().cpu().contiguous()
-    u = torch.empty((16, Cout, Cin), dtype=torch.float32)
-    nat.check(nat.lib().msocr_winograd_weights_host(wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_weights_host")
-    w._msocr_wino = u.to(w.device)
-    u42 = torch.empty((24, Cout, Cin), dtype=torch.float32)
-    nat.check(nat.lib().msocr_winograd42_weights_host(wh.data_ptr(), Cout, Cin, u42.data_ptr()), "winograd42_weights_host")
+    w._msocr_wino = _wino_weights(wh, nat.WINO_2X2).to(w.device)
+    u42 = _wino_weights(wh, nat.WINO_4X2)
     w._msocr_wino42 = u42.to(w.device)
     if (SPLIT_BF16X3 if split is None else split) and Cin % 32 == 0 and Cout % 64 == 0:
         w._msocr_wino42_split = split_planes_ktile(u42, 24, Cout).to(w.device)  # [3][24][Cin/32][Cout][32] bf16
         if WINOGRAD_SQUARE and square and Cin >= WINOGRAD_SQUARE_MIN_CIN:  # square=False: the caller keeps this layer on the tall form (half the rounding error)
-            u44 = torch.empty((36, Cout, Cin), dtype=torch.float32)
-            nat.check(nat.lib().msocr_winograd44_weights_host(wh.data_ptr(), Cout, Cin, u44.data_ptr()), "winograd44_weights_host")
-            w._msocr_wino44_split = split_planes_ktile(u44, 36, Cout).to(w.device)  # [3][36][Cin/32][Cout][32] bf16
+            w._msocr_wino44_split = split_planes_ktile(_wino_weights(wh, nat.WINO_4X4), 36, Cout).to(w.device)  # [3][36][Cin/32][Cout][32] bf16
     return w
 
 
-def _conv3x3_fused64(x, w, u42, bias, relu, residual, pool2, out):
-    """Cin == 64, 3x3/1/1, f32: tall Winograd, GEMMs + output transform (+ 2x2 max-pool) in one kernel."""
+def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False):
+    """One Winograd convolution described by d (3x3/1/1, f32) in the given form: the workspace from the per-stream arena, the batch cut
+    so that it stays under WINO_WS_LIMIT, and per part either the one-call entry point or — with PROFILE on — the stages one by one,
+    one event pair each.  fused: the Cin = 64 tall form with the GEMMs and the output transform (+ the 2x2 max-pool) in one kernel."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
-    oh, ow = (H // 2, W // 2) if pool2 else (H, W)
-    if out is None:
-        out = torch.empty((N, oh, ow, Cout), dtype=x.dtype, device=x.device)
-    assert out.shape == (N, oh, ow, Cout) and out.dtype == x.dtype
-    d = nat.ConvDesc()
-    d.dtype = _dt(x)
-    d.N, d.H, d.W, d.Cin = N, H, W, Cin
-    d.in_sN, d.in_sH, d.in_sW = x.stride(0), x.stride(1), x.stride(2)
-    d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, 1, 1, 1, 1
-    d.Ho, d.Wo, d.Cout = H, W, Cout
-    d.out_ld = _pixel_dense_ld(out)
-    flags = (nat.CONV_RELU if relu else 0) | (nat.CONV_POOL2 if pool2 else 0)
-    if residual is not None:
-        assert residual.shape == out.shape and residual.dtype == x.dtype and not pool2
-        d.res_ld = _pixel_dense_ld(residual)
-        flags |= nat.CONV_RESIDUAL
-    d.flags = flags
+    stem, npts, (mh, mw) = WINO_FORMS[form]
+    name = stem + ("_fused" if fused else "") + ("_split" if split else "")
     L = nat.lib()
-    nbytes = L.msocr_conv3x3_winograd42_fused_workspace_bytes(ctypes.byref(d))
+    nbytes = L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) if fused else L.msocr_winograd_workspace_bytes(ctypes.byref(d), form)
     if nbytes < 0:
-        raise nat.NativeError(f"winograd42_fused: unsupported shape {tuple(x.shape)} * {tuple(w.shape)} pool2={pool2}")
-    parts = min(N, -(-nbytes // WINO_WS_LIMIT))
+        raise nat.NativeError(f"{name}: unsupported shape {tuple(x.shape)} * {tuple(w.shape)} pool2={pool2}")
+    parts = min(N, -(-nbytes // WINO_WS_LIMIT))  # images per call such that the workspace stays under the limit
     per = -(-N // parts)
     ws = _wino_workspace(nbytes if parts == 1 else (nbytes // N) * per, x.device)
     bp = bias.data_ptr() if bias is not None else None
-    up = getattr(w, "_msocr_wino42_fused_split", None) if SPLIT_BF16X3 else None
-    f_whole, f_gemm, name = L.msocr_conv3x3_winograd42_fused, L.msocr_winograd42_fused_gemm_output, "winograd42_fused"
-    if up is not None:  # the 24 K = 64 GEMMs on the bf16 pipes with exactly split operands
-        u42, f_whole, f_gemm, name = up, L.msocr_conv3x3_winograd42_fused_split, L.msocr_winograd42_fused_gemm_output_split, "winograd42_fused_split"
     what = f"msocr_conv3x3_{name} {tuple(x.shape)} * {tuple(w.shape)}"
-    TH, TW = (H + 3) // 4, (W + 1) // 2
-    alg = 2.0 * N * H * W * Cout * 9 * Cin
+    TH, TW = -(-H // mh), -(-W // mw)
+    out_px = H * W // (4 if pool2 else 1)
+    res_io = 2 if residual is not None else 1
     for n0 in range(0, N, per):
         n1 = min(N, n0 + per)
         d.N = n1 - n0
-        xp, rp_, op = x[n0:n1].data_ptr(), (residual[n0:n1].data_ptr() if residual is not None else None), out[n0:n1].data_ptr()
+        xp, rp, op = x[n0:n1].data_ptr(), (residual[n0:n1].data_ptr() if residual is not None else None), out[n0:n1].data_ptr()
         if PROFILE is None:
-            nat.check(f_whole(ctypes.byref(d), xp, u42.data_ptr(), bp, rp_, op, ws.data_ptr(), _stream()), what)
+            if fused:
+                rc = L.msocr_conv3x3_winograd_fused64(ctypes.byref(d), int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
+            else:
+                rc = L.msocr_conv3x3_winograd(ctypes.byref(d), form, int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
+            nat.check(rc, what)
+            continue
+        nn, mt = n1 - n0, (n1 - n0) * TH * TW
+        e = _prof_begin()
+        nat.check(L.msocr_winograd_input_transform(ctypes.byref(d), form, xp, ws.data_ptr(), _stream()), what)
+        _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + npts * mt * Cin), (mt, Cin))
+        e = _prof_begin()
+        if fused:
+            rc = L.msocr_winograd_fused64_gemm_output(ctypes.byref(d), int(split), u.data_ptr(), ws.data_ptr(), bp, rp, op, _stream())
         else:
-            nn, mt = n1 - n0, (n1 - n0) * TH * TW
+            rc = L.msocr_winograd_gemm(ctypes.byref(d), form, int(split), u.data_ptr(), ws.data_ptr(), _stream())
+        nat.check(rc, what)
+        io = x.element_size() * (nn * H * W * Cin + nn * out_px * Cout * res_io + Cout * 9 * Cin)
+        _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * npts * mt * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
+        if not fused:
             e = _prof_begin()
-            nat.check(L.msocr_winograd42_input_transform(ctypes.byref(d), xp, ws.data_ptr(), _stream()), what)
-            _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + 24 * mt * Cin), (mt, Cin))
-            e = _prof_begin()
-            nat.check(f_gemm(ctypes.byref(d), u42.data_ptr(), ws.data_ptr(), bp, rp_, op, _stream()), what)
-            io = x.element_size() * (nn * H * W * Cin + nn * (H * W // (4 if pool2 else 1)) * Cout * (2 if residual is not None else 1) + Cout * 9 * Cin)
-            _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * 24 * mt * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
-    return out
+            nat.check(L.msocr_winograd_output_transform(ctypes.byref(d), form, ws.data_ptr(), bp, rp, op, _stream()), what)
+            _prof_end(e, "wino_out", 4.0 * (npts * mt * Cout + nn * H * W * Cout * res_io), (mt, Cout))
+    d.N = N
 
 
 def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out=None, out_hw=None, alg_k=None, pool2=False):
@@ -283,17 +284,17 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
     sh, sw = stride
     ph, pw = pad
     Ho, Wo = out_hw if out_hw else ((H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1)
-    u42f = getattr(w, "_msocr_wino42_fused", None)
-    if (u42f is not None and WINOGRAD_FUSED64 and WINOGRAD_TALL and (sh, sw, ph, pw) == (1, 1, 1, 1) and (Ho, Wo) == (H, W)
-            and _tall_pays(H) and (not pool2 or (H % 2 == 0 and W % 2 == 0 and residual is None))):
-        return _conv3x3_fused64(x, w, u42f, bias, relu, residual, pool2, out)
-    if pool2:
+    wino = (sh, sw, ph, pw) == (1, 1, 1, 1) and (Ho, Wo) == (H, W)
+    fused = (getattr(w, "_msocr_wino42_fused", None) is not None and WINOGRAD_FUSED64 and WINOGRAD_TALL and wino and _tall_pays(H)
+             and (not pool2 or (H % 2 == 0 and W % 2 == 0 and residual is None)))
+    if pool2 and not fused:
         return maxpool2d(conv2d(x, w, bias, stride, pad, relu, residual, None, out_hw, alg_k), 2, 2, 0, out=out)
     u = getattr(w, "_msocr_wino", None)
-    use_wino = u is not None and (sh, sw, ph, pw) == (1, 1, 1, 1) and (Ho, Wo) == (H, W)
+    use_wino = u is not None and wino
+    oh, ow = (Ho // 2, Wo // 2) if pool2 else (Ho, Wo)
     if out is None:
-        out = torch.empty((N, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
-    assert out.shape == (N, Ho, Wo, Cout) and out.dtype == x.dtype
+        out = torch.empty((N, oh, ow, Cout), dtype=x.dtype, device=x.device)
+    assert out.shape == (N, oh, ow, Cout) and out.dtype == x.dtype
     d = nat.ConvDesc()
     d.dtype = _dt(x)
     d.N, d.H, d.W, d.Cin = N, H, W, Cin
@@ -301,7 +302,7 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
     d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = KH, KW, sh, sw, ph, pw
     d.Ho, d.Wo, d.Cout = Ho, Wo, Cout
     d.out_ld = _pixel_dense_ld(out)
-    flags = nat.CONV_RELU if relu else 0
+    flags = (nat.CONV_RELU if relu else 0) | (nat.CONV_POOL2 if pool2 else 0)
     rp = None
     if residual is not None:
         assert residual.shape == out.shape and residual.dtype == x.dtype
@@ -311,57 +312,23 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
     d.flags = flags
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == Cout and bias.is_contiguous()
-    prof = PROFILE
     bp = bias.data_ptr() if bias is not None else None
     alg = 2.0 * N * Ho * Wo * Cout * (alg_k if alg_k else KH * KW * Cin)  # ALGORITHMIC direct-convolution FLOP (2 * MACs)
-    if use_wino:
-        L = nat.lib()
-        tall = bool(WINOGRAD_TALL) and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None
-        if tall:
-            u = w._msocr_wino42
-            name, f_ws, whole = "winograd42", L.msocr_conv3x3_winograd42_workspace_bytes, L.msocr_conv3x3_winograd42
-            st_in, st_gemm, st_out = L.msocr_winograd42_input_transform, L.msocr_winograd42_gemm, L.msocr_winograd42_output_transform
+    if fused:  # Cin == 64: the 24 GEMMs (on the bf16 pipes with exactly split operands where the planes exist) + output transform
+        up = getattr(w, "_msocr_wino42_fused_split", None) if SPLIT_BF16X3 else None
+        u = w._msocr_wino42_fused if up is None else up
+        _winograd(d, x, w, u, nat.WINO_4X2, up is not None, bias, residual, out, alg, fused=True, pool2=pool2)
+    elif use_wino:
+        form, split = nat.WINO_2X2, False
+        if WINOGRAD_TALL and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None:
+            form, u = nat.WINO_4X2, w._msocr_wino42
             up = getattr(w, "_msocr_wino42_split", None)
             if up is not None and SPLIT_BF16X3:  # the 24 GEMMs on the bf16 pipes with exactly split operands
-                u, name, whole, st_gemm = up, "winograd42_split", L.msocr_conv3x3_winograd42_split, L.msocr_winograd42_gemm_split
-            TH, TW, npts = (Ho + 3) // 4, (Wo + 1) // 2, 24
+                u, split = up, True
             up44 = getattr(w, "_msocr_wino44_split", None)
             if up44 is not None and SPLIT_BF16X3 and WINOGRAD_SQUARE and _square_pays(W):
-                u, name, f_ws, whole = up44, "winograd44_split", L.msocr_conv3x3_winograd44_workspace_bytes, L.msocr_conv3x3_winograd44_split
-                st_in, st_gemm, st_out = L.msocr_winograd44_input_transform, L.msocr_winograd44_gemm_split, L.msocr_winograd44_output_transform
-                TH, TW, npts = (Ho + 3) // 4, (Wo + 3) // 4, 36
-        else:
-            name, f_ws, whole = "winograd", L.msocr_conv3x3_winograd_workspace_bytes, L.msocr_conv3x3_winograd
-            st_in, st_gemm, st_out = L.msocr_winograd_input_transform, L.msocr_winograd_gemm, L.msocr_winograd_output_transform
-            TH, TW, npts = (Ho + 1) // 2, (Wo + 1) // 2, 16
-        nbytes = f_ws(ctypes.byref(d))
-        if nbytes < 0:
-            raise nat.NativeError(f"{name}: unsupported shape {tuple(x.shape)} * {tuple(w.shape)}")
-        parts = min(N, -(-nbytes // WINO_WS_LIMIT))  # images per call such that the workspace stays under the limit
-        per = -(-N // parts)
-        ws = _wino_workspace(nbytes if parts == 1 else (nbytes // N) * per, x.device)
-        what = f"msocr_conv3x3_{name} {tuple(x.shape)} * {tuple(w.shape)}"
-        for n0 in range(0, N, per):
-            n1 = min(N, n0 + per)
-            d.N = n1 - n0
-            xp, rp_, op = x[n0:n1].data_ptr(), (residual[n0:n1].data_ptr() if residual is not None else None), out[n0:n1].data_ptr()
-            if prof is None:
-                nat.check(whole(ctypes.byref(d), xp, u.data_ptr(), bp, rp_, op, ws.data_ptr(), _stream()), what)
-            else:  # the same three kernels through the per-stage entry points, one event pair each
-                nn, mt = n1 - n0, (n1 - n0) * TH * TW
-                v_el = npts * mt * Cin   # transformed input array V, elements
-                m_el = npts * mt * Cout  # transformed output array Mw
-                e = _prof_begin()
-                nat.check(st_in(ctypes.byref(d), xp, ws.data_ptr(), _stream()), what)
-                _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + v_el), (mt, Cin))
-                e = _prof_begin()
-                nat.check(st_gemm(ctypes.byref(d), u.data_ptr(), ws.data_ptr(), _stream()), what)
-                io = x.element_size() * (nn * H * W * Cin + nn * Ho * Wo * Cout * (2 if residual is not None else 1) + Cout * KH * KW * Cin)
-                _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * npts * mt * Cin * Cout, io), (nn * Ho * Wo, Cout, KH * KW * Cin, name))
-                e = _prof_begin()
-                nat.check(st_out(ctypes.byref(d), ws.data_ptr(), bp, rp_, op, _stream()), what)
-                _prof_end(e, "wino_out", 4.0 * (m_el + nn * Ho * Wo * Cout * (2 if residual is not None else 1)), (mt, Cout))
-        d.N = N
+                form, u, split = nat.WINO_4X4, up44, True
+        _winograd(d, x, w, u, form, split, bias, residual, out, alg)
     else:
         wp = getattr(w, "_msocr_split", None)
         if (wp is None and SPLIT_BF16X3 and not getattr(w, "_msocr_nosplit", False) and _split_eligible(w)

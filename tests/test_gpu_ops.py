@@ -358,8 +358,8 @@ def test_conv_pool2_unfused_paths(ops):
         assert a.shape == (2, H // 2, W // 2, 64) and torch.equal(a, c)
 
 
-def test_winograd_weight_transform_matches_definition(ops, monkeypatch):
-    """U = G g G^T evaluated in f64 (msocr_winograd_weights_host) for every (xi, nu)."""
+def test_winograd_weight_transforms_by_form_match_definition(ops, monkeypatch):
+    """U = G g G^T evaluated in f64 (msocr_winograd_weights_host, all three forms) for every (xi, nu)."""
     monkeypatch.setattr(ops, "WINOGRAD_SQUARE_MIN_CIN", 128)
     g = torch.Generator().manual_seed(9)
     w = torch.randn(64, 128, 3, 3, generator=g)
@@ -382,7 +382,7 @@ def test_winograd_weight_transform_matches_definition(ops, monkeypatch):
     u44 = torch.empty((36, 64, 128), dtype=torch.float32)
     wh = _w_khwc(w, torch.float32).cpu().contiguous()
     from manuscript_ocr_amd import _native as nat
-    nat.check(nat.lib().msocr_winograd44_weights_host(wh.data_ptr(), 64, 128, u44.data_ptr()), "winograd44_weights_host")
+    nat.check(nat.lib().msocr_winograd_weights_host(nat.WINO_4X4, wh.data_ptr(), 64, 128, u44.data_ptr()), "winograd_weights_host")
     exp44 = torch.einsum("xk,ockl,nl->xnoc", G6, w.double(), G6).reshape(36, 64, 128)
     assert (u44.double() - exp44).abs().max().item() <= 1.2e-7 * exp44.abs().max().item()
     assert torch.equal(ops.unsplit_planes_ktile(wk._msocr_wino44_split.cpu()), u44)   # the planes the kernels read: the exact three-term split

@@ -436,7 +436,7 @@ def test_vectorised_crop_descriptors_equal_the_loop():
     assert d.shape == (0, 8) and k.shape == (0,)
 
 
-def test_winograd_weight_transforms_host():
+def test_winograd_weight_transform_host_by_form():
     """The load-time weight transforms are HOST functions of the C ABI (f64, rounded once): U = G g G^T for F(2x2,3x3), U = G6 g G4^T
     for the tall form F(4,3) x F(2,3) and U = G6 g G6^T for the square form, G6 = the Cook-Toom matrix of F(4,3) on the interpolation
     points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4), checked against their definitions without a GPU."""
@@ -451,13 +451,55 @@ def test_winograd_weight_transforms_host():
     for j, a in enumerate(pts):   # G[j] = [1, a, a^2] / prod_{l != j}(a_j - a_l); the point at infinity: [0, 0, 1]
         G6[j] = np.array([1.0, a, a * a]) / np.prod([a - b for l, b in enumerate(pts) if l != j])
     G6[5, 2] = 1.0
-    for fn, Gh, Gw, npts in ((L.msocr_winograd_weights_host, G4, G4, 16), (L.msocr_winograd42_weights_host, G6, G4, 24),
-                             (L.msocr_winograd44_weights_host, G6, G6, 36)):
+    for form, Gh, Gw, npts in ((nat.WINO_2X2, G4, G4, 16), (nat.WINO_4X2, G6, G4, 24), (nat.WINO_4X4, G6, G6, 36)):
         u = np.empty((npts, Cout, Cin), np.float32)
-        assert fn(w.ctypes.data, Cout, Cin, u.ctypes.data) == 0
+        assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, u.ctypes.data) == 0
         exp = np.einsum("xk,oklc,nl->xnoc", Gh, w.astype(np.float64), Gw).reshape(npts, Cout, Cin)
         assert np.abs(u.astype(np.float64) - exp).max() <= 1.2e-7 * np.abs(exp).max()
-    assert L.msocr_winograd42_weights_host(None, Cout, Cin, None) != 0
+        assert L.msocr_winograd_weights_host(form, None, Cout, Cin, u.ctypes.data) == -1
+        assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, None) == -1
+        assert L.msocr_winograd_weights_host(form, None, Cout, Cin, None) != 0
+    u = np.empty((36, Cout, Cin), np.float32)
+    for form in (-1, 3, 99):  # unknown form ids
+        assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, u.ctypes.data) == -1
+
+
+def test_winograd_workspace_bytes_and_form_arguments():
+    """msocr_winograd_workspace_bytes = points * N ceil(H/mh) ceil(W/mw) * (Cin + Cout) * 4 per form, -1 for shapes without a Winograd
+    form; unknown form ids and (form, split) pairs without a GEMM kernel are MSOCR_E_ARG before anything is launched (no GPU needed)."""
+    from manuscript_ocr_amd import _native as nat
+    L = nat.lib()
+
+    def desc(N, H, W, Cin, Cout, stride=1):
+        d = nat.ConvDesc()
+        d.dtype, d.N, d.H, d.W, d.Cin = nat.F32, N, H, W, Cin
+        d.in_sN, d.in_sH, d.in_sW = H * W * Cin, W * Cin, Cin
+        d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, stride, stride, 1, 1
+        d.Ho, d.Wo, d.Cout = (H - 1) // stride + 1, (W - 1) // stride + 1, Cout
+        d.out_ld = d.res_ld = Cout
+        return d
+
+    for form, npts, (mh, mw) in ((nat.WINO_2X2, 16, (2, 2)), (nat.WINO_4X2, 24, (4, 2)), (nat.WINO_4X4, 36, (4, 4))):
+        for N, H, W, Cin, Cout in ((2, 8, 25, 256, 256), (3, 4, 13, 512, 512), (1, 17, 23, 128, 64), (5, 7, 9, 16, 32), (960, 32, 100, 64, 128)):
+            exp = npts * N * -(-H // mh) * -(-W // mw) * (Cin + Cout) * 4
+            assert L.msocr_winograd_workspace_bytes(ctypes.byref(desc(N, H, W, Cin, Cout)), form) == exp, (form, N, H, W, Cin, Cout)
+        for d in (desc(1, 8, 8, 24, 64), desc(1, 8, 8, 128, 48), desc(1, 8, 8, 128, 64, stride=2)):  # Cin % 16, Cout % 32, stride 2
+            assert L.msocr_winograd_workspace_bytes(ctypes.byref(d), form) == -1
+    d = desc(2, 8, 8, 128, 128)
+    for form in (-1, 3):
+        assert L.msocr_winograd_workspace_bytes(ctypes.byref(d), form) == -1
+    fake = ctypes.c_void_p(1 << 20)  # never dereferenced: every call below fails its argument checks first
+    for form, split in ((nat.WINO_2X2, 1), (nat.WINO_4X4, 0), (nat.WINO_4X2, 2), (3, 0), (-1, 1)):
+        assert L.msocr_winograd_gemm(ctypes.byref(d), form, split, fake, fake, None) == -1
+        assert L.msocr_conv3x3_winograd(ctypes.byref(d), form, split, fake, fake, None, None, fake, fake, None) == -1
+    for form in (-1, 3):
+        assert L.msocr_winograd_input_transform(ctypes.byref(d), form, fake, fake, None) == -1
+        assert L.msocr_winograd_output_transform(ctypes.byref(d), form, fake, None, None, fake, None) == -1
+    d64 = desc(2, 8, 8, 64, 128)
+    assert L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d64)) == 24 * 2 * 2 * 4 * 64 * 4
+    assert L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) == -1  # Cin != 64
+    assert L.msocr_winograd_fused64_gemm_output(ctypes.byref(d64), 2, fake, fake, None, None, fake, None) == -1
+    assert L.msocr_conv3x3_winograd_fused64(ctypes.byref(d64), 2, fake, fake, None, None, fake, fake, None) == -1
 
 
 def test_bench_live_pmc_digest_with_a_stub_profiler(tmp_path, monkeypatch):

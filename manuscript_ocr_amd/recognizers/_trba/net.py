@@ -51,13 +51,7 @@ LAYER_SPEC = (("layer1", 1, 2), ("layer2", 2, 1), ("layer3", 5, 2), ("layer4", 3
 
 class TrbaNet:
     def __init__(self, state_dict, num_classes, hidden=256, dtype=torch.float32, device="cuda", split=None):
-        # hidden_size comes from the checkpoint's config.json (reference __init__.py:142-151, default 256).  256 / <= 256 tokens /
-        # beam <= 8 run on the fast decoder kernels; other multiples of 64 up to 512, charsets up to 512 tokens and beams up to 16
-        # (beam x hidden <= 4096) on the general one (csrc/attn_general.hip)
-        if hidden % 64 or not 64 <= hidden <= 512:
-            raise ValueError(f"hidden_size must be a multiple of 64 between 64 and 512 for the HIP recurrent / attention kernels, got {hidden}")
-        if num_classes > 512:
-            raise ValueError(f"charsets above 512 tokens are not supported by the decoder kernels, got {num_classes}")
+        check_decoder_shape(hidden, num_classes)
         self.dtype, self.device = dtype, torch.device(device)
         self.V, self.Hd = num_classes, hidden
         dev, sd = self.device, state_dict
@@ -109,40 +103,10 @@ class TrbaNet:
                 "lin_w": sd[p + "linear.weight"].float().view(H, 1, 1, 2 * H).contiguous().to(dev),
                 "lin_b": sd[p + "linear.bias"].float().contiguous().to(dev),
             })
-        # ---- attention decoder (f32, transposed for coalesced column reads) ----
-        a = "attn.attention_cell."
-        w_ih = sd[a + "rnn.weight_ih"].float()  # [4H, H + V]
-        self.att = {
-            "i2h_w": sd[a + "i2h.weight"].float().view(H, 1, 1, H).contiguous().to(dev),
-            "h2h_wt": sd[a + "h2h.weight"].float().t().contiguous().to(dev),
-            "h2h_b": sd[a + "h2h.bias"].float().contiguous().to(dev),
-            "score_w": sd[a + "score.weight"].float().view(H).contiguous().to(dev),
-            "wih_ctx_t": _gate_interleave(w_ih[:, :H].t(), H).to(dev),
-            "wih_tok": _gate_interleave(w_ih[:, H:].t(), H).to(dev),
-            "whh_t": _gate_interleave(sd[a + "rnn.weight_hh"].float().t(), H).to(dev),
-            "b_gates": _gate_interleave((sd[a + "rnn.bias_ih"] + sd[a + "rnn.bias_hh"]).float().view(1, 4 * H), H).view(H, 4).contiguous().to(dev),
-            "gen_wt": sd["attn.generator.weight"].float().t().contiguous().to(dev),
-            "gen_b": sd["attn.generator.bias"].float().contiguous().to(dev),
-        }
-        # rows of rnn.weight_ih[:, :H] reordered unit-major (row j*4+g): the hoisted context product of the beam kernel
-        # (msocr_attn_beam_hoisted) is one GEMM batch_H x this^T -> [B*T, H*4]
-        self.att["wih_ctx_rows"] = ops.attach_split(w_ih[:, :H].reshape(4, H, H).permute(1, 0, 2).reshape(4 * H, 1, 1, H).contiguous().to(dev),
-                                                    split)
-        aw = nat.AttnWeights()
-        for k in ("h2h_wt", "h2h_b", "score_w", "wih_ctx_t", "wih_tok", "whh_t", "b_gates", "gen_wt", "gen_b"):
-            setattr(aw, k, self.att[k].data_ptr())
-        self._aw = aw
-        # split form of the three per-step matrices for the matrix-core beam kernel (precision "fp32"; "fp32-exact" keeps the f32 MFMA)
-        self._asw = None
-        if (ops.SPLIT_BF16X3 if split is None else split) and dtype == torch.float32 and H == 256 and self.V <= 256:
-            asw = nat.AttnSplitWeights()
-            for src, dst, n, gi in (("h2h_wt", "h2h_p", H, 0), ("whh_t", "whh_p", 4 * H, 1), ("gen_wt", "gen_p", self.V, 0)):
-                wt = self.att[src].cpu().contiguous()
-                packed = torch.empty((nat.lib().msocr_attn_pack_split_elems(n),), dtype=torch.int16)
-                nat.check(nat.lib().msocr_attn_pack_split_host(wt.data_ptr(), n, gi, packed.data_ptr()), "attn_pack_split_host")
-                self.att[dst] = packed.to(dev)
-                setattr(asw, dst, self.att[dst].data_ptr())
-            self._asw = asw
+        # ---- attention decoder ----
+        self.dec = AttnDecoder(state_dict, num_classes, hidden, split, device,
+                               step_split=bool((ops.SPLIT_BF16X3 if split is None else split) and dtype == torch.float32))
+        self.att, self._aw, self._asw = self.dec.att, self.dec._aw, self.dec._asw
 
     # ------------------------------------------------------------------------------------- CNN
     def _se_block(self, x, lname, i, stride):
@@ -171,9 +135,7 @@ class TrbaNet:
 
     # ------------------------------------------------------------------------------------- encoder
     def _gemm(self, x2d, w, b):
-        """x2d [M,K] f32 -> [M,N] via the exact-f32 MFMA implicit-GEMM (1x1 conv)."""
-        M, K = x2d.shape
-        return ops.conv2d(x2d.view(1, M, 1, K), w, b).view(M, w.shape[0])
+        return _gemm(x2d, w, b)
 
     def encode(self, canvases_u8):
         """-> (batch_H [B,T,256] f32, proj_H [B,T,256] f32)."""
@@ -191,6 +153,85 @@ class TrbaNet:
 
     # ------------------------------------------------------------------------------------- decoder
     def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id):
+        return self.dec.greedy(batch_H, proj_H, max_len, sos_id, eos_id, blank_id)
+
+    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None):
+        return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks)
+
+    def beam_finalize(self, ws, B, steps, beam_size, trun_dev):
+        return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev)
+
+
+def check_decoder_shape(hidden, num_classes):
+    # hidden_size comes from the checkpoint's config.json (reference __init__.py:142-151, default 256).  256 / <= 256 tokens /
+    # beam <= 8 run on the fast decoder kernels; other multiples of 64 up to 512, charsets up to 512 tokens and beams up to 16
+    # (beam x hidden <= 4096) on the general one (csrc/attn_general.hip)
+    if hidden % 64 or not 64 <= hidden <= 512:
+        raise ValueError(f"hidden_size must be a multiple of 64 between 64 and 512 for the HIP recurrent / attention kernels, got {hidden}")
+    if num_classes > 512:
+        raise ValueError(f"charsets above 512 tokens are not supported by the decoder kernels, got {num_classes}")
+
+
+def _gemm(x2d, w, b):
+    """x2d [M,K] f32 -> [M,N] via the MFMA implicit-GEMM (1x1 conv)."""
+    M, K = x2d.shape
+    return ops.conv2d(x2d.view(1, M, 1, K), w, b).view(M, w.shape[0])
+
+
+class AttnDecoder:
+    """The attention decoder's device weights (f32, transposed for coalesced column reads) and its launches: greedy, beam,
+    beam_finalize.  Built from the `attn.*` keys of a TRBA state dict; needs no CNN.  split: the hoisted context GEMM's weight
+    (ops.attach_split); step_split: pack the split form of the three per-step matrices for the matrix-core kernels (precision
+    "fp32" with an f32 CNN — TrbaNet decides)."""
+
+    def __init__(self, state_dict, num_classes, hidden=256, split=None, device="cuda", step_split=None):
+        check_decoder_shape(hidden, num_classes)
+        if step_split is None:
+            step_split = bool(ops.SPLIT_BF16X3 if split is None else split)
+        self.device = torch.device(device)
+        self.V, self.Hd = num_classes, hidden
+        dev, sd, H = self.device, state_dict, hidden
+        a = "attn.attention_cell."
+        w_ih = sd[a + "rnn.weight_ih"].float()  # [4H, H + V]
+        self.att = {
+            "i2h_w": sd[a + "i2h.weight"].float().view(H, 1, 1, H).contiguous().to(dev),
+            "h2h_wt": sd[a + "h2h.weight"].float().t().contiguous().to(dev),
+            "h2h_b": sd[a + "h2h.bias"].float().contiguous().to(dev),
+            "score_w": sd[a + "score.weight"].float().view(H).contiguous().to(dev),
+            "wih_ctx_t": _gate_interleave(w_ih[:, :H].t(), H).to(dev),
+            "wih_tok": _gate_interleave(w_ih[:, H:].t(), H).to(dev),
+            "whh_t": _gate_interleave(sd[a + "rnn.weight_hh"].float().t(), H).to(dev),
+            "b_gates": _gate_interleave((sd[a + "rnn.bias_ih"] + sd[a + "rnn.bias_hh"]).float().view(1, 4 * H), H).view(H, 4).contiguous().to(dev),
+            "gen_wt": sd["attn.generator.weight"].float().t().contiguous().to(dev),
+            "gen_b": sd["attn.generator.bias"].float().contiguous().to(dev),
+        }
+        # rows of rnn.weight_ih[:, :H] reordered unit-major (row j*4+g): the hoisted context product of the beam kernel
+        # (msocr_attn_beam_hoisted) is one GEMM batch_H x this^T -> [B*T, H*4]
+        self.att["wih_ctx_rows"] = ops.attach_split(w_ih[:, :H].reshape(4, H, H).permute(1, 0, 2).reshape(4 * H, 1, 1, H).contiguous().to(dev),
+                                                    split)
+        aw = nat.AttnWeights()
+        for k in ("h2h_wt", "h2h_b", "score_w", "wih_ctx_t", "wih_tok", "whh_t", "b_gates", "gen_wt", "gen_b"):
+            setattr(aw, k, self.att[k].data_ptr())
+        self._aw = aw
+        # split form of the three per-step matrices for the matrix-core beam kernel (precision "fp32"; "fp32-exact" keeps the f32 MFMA)
+        self._asw = None
+        if step_split and H == 256 and self.V <= 256:
+            asw = nat.AttnSplitWeights()
+            for src, dst, n, gi in (("h2h_wt", "h2h_p", H, 0), ("whh_t", "whh_p", 4 * H, 1), ("gen_wt", "gen_p", self.V, 0)):
+                wt = self.att[src].cpu().contiguous()
+                packed = torch.empty((nat.lib().msocr_attn_pack_split_elems(n),), dtype=torch.int16)
+                nat.check(nat.lib().msocr_attn_pack_split_host(wt.data_ptr(), n, gi, packed.data_ptr()), "attn_pack_split_host")
+                self.att[dst] = packed.to(dev)
+                setattr(asw, dst, self.att[dst].data_ptr())
+            self._asw = asw
+
+    def ctx_gates(self, batch_H):
+        """W_ih[:, :H] batch_H_t for every frame: [B*T, H*4] (unit-major, gates adjacent), the hoisted context product."""
+        B, T, H = batch_H.shape
+        return _gemm(batch_H.reshape(B * T, H), self.att["wih_ctx_rows"], None)
+
+    def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, ctx_gates=None):
+        """ctx_gates: this call's rows of a ctx_gates() result computed beforehand (used only where the kernel takes them)."""
         B, T, H = batch_H.shape
         steps = max_len + 1
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
@@ -198,9 +239,9 @@ class TrbaNet:
         blank = -1 if blank_id is None else blank_id
         # default: the matrix-core row-block kernel (32 crops per workgroup, split-operand products, hoisted context gates), like
         # the beam path; MSOCR_GREEDY_MFMA=0, precision="fp32-exact" and shapes outside the fast kernels: the VALU / general kernel
-        fast = H == 256 and self.V <= 256 and T <= 48 and getattr(self, "_asw", None) is not None
+        fast = H == 256 and self.V <= 256 and T <= 48 and self._asw is not None
         if fast and HOIST_CTX and os.environ.get("MSOCR_GREEDY_MFMA", "1") != "0":
-            ctxg = self._gemm(batch_H.reshape(B * T, H), self.att["wih_ctx_rows"], None)
+            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
             nat.check(nat.lib().msocr_attn_greedy_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
                                                           ctypes.byref(self._asw), B, T, H, self.V, steps, sos_id, eos_id, blank,
                                                           logits.data_ptr(), ids.data_ptr(), ops._stream()), "attn_greedy_hoisted")
@@ -209,8 +250,8 @@ class TrbaNet:
                                                   sos_id, eos_id, blank, logits.data_ptr(), ids.data_ptr(), ops._stream()), "attn_greedy")
         return logits, ids
 
-    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None):
-        """Returns (workspace, fin_step [B] i32, lp) for `beam_finalize`.  Runs all `max_len` steps, or — given
+    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None):
+        """Returns (workspace, fin_step [B] i32, lp) for `beam_finalize`.  ctx_gates as for `greedy`.  Runs all `max_len` steps, or — given
         chunks = (chunk_id [B] i32, chunk_size [nchunks] i32, chunk_state [2*nchunks] i32 zeros), all on the device — only
         as many as the reference's own loop would (it breaks once every beam of the chunk is finished, model.py:215)."""
         B, T, H = batch_H.shape
@@ -234,7 +275,7 @@ class TrbaNet:
         fast = H == 256 and self.V <= 256 and T <= 48 and beam_size <= 8  # the matrix-core kernel's shapes
         hoist = HOIST_CTX and fast and os.environ.get("MSOCR_BEAM_MFMA", "1") != "0"
         if hoist:  # W_ih[:, :H] batch_H_t for every frame, once per call instead of W_ih[:, :H] ctx in every step
-            ctxg = self._gemm(batch_H.reshape(B * T, H), self.att["wih_ctx_rows"], None)
+            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
         e = ops._prof_begin()
         tail = (B, T, H, self.V, steps, beam_size, lp.data_ptr() if lp is not None else None, float(temperature), sos_id, eos_id,
                 -1 if blank_id is None else blank_id, fin.data_ptr(), ws.data_ptr(),

@@ -130,8 +130,8 @@ class Attention(nn.Module):
         self.sos_id, self.eos_id, self.pad_id, self.blank_id = sos_id, eos_id, pad_id, blank_id
         self.generator = nn.Linear(hidden_size, num_classes)
 
-    def _onehot(self, tok):
-        oh = torch.zeros(tok.size(0), self.num_classes)
+    def _onehot(self, tok, dtype):
+        oh = torch.zeros(tok.size(0), self.num_classes, dtype=dtype, device=tok.device)
         oh.scatter_(1, tok.unsqueeze(1), 1.0)
         return oh
 
@@ -145,12 +145,12 @@ class Attention(nn.Module):
         """model.py:227-259. Returns (logits B x T_run x V, ids B x T_run).
         diag (checker only, no effect on the arithmetic): dict that receives "top2_margin" [B, T_run] = gap between the
         largest and second largest logit of every step, i.e. the margin of every arg-max decision of this decode."""
-        B = batch_H.size(0)
-        hid = (torch.zeros(B, self.hidden_size), torch.zeros(B, self.hidden_size))
-        tok = torch.full((B,), self.sos_id, dtype=torch.long)
+        B, fd, dev = batch_H.size(0), batch_H.dtype, batch_H.device
+        hid = (torch.zeros(B, self.hidden_size, dtype=fd, device=dev), torch.zeros(B, self.hidden_size, dtype=fd, device=dev))
+        tok = torch.full((B,), self.sos_id, dtype=torch.long, device=dev)
         logits_all, ids_all = [], []
         for _ in range(max_len + 1):
-            hid = self.attention_cell(hid, batch_H, self._onehot(tok))
+            hid = self.attention_cell(hid, batch_H, self._onehot(tok, fd))
             logits = self._mask(self.generator(hid[0]))
             tok = logits.argmax(1)
             logits_all.append(logits)
@@ -159,7 +159,7 @@ class Attention(nn.Module):
                 break
         if diag is not None:
             t2 = torch.stack(logits_all, 1).topk(2, dim=-1).values
-            diag["top2_margin"] = (t2[..., 0] - t2[..., 1]).numpy()
+            diag["top2_margin"] = (t2[..., 0] - t2[..., 1]).cpu().numpy()
         return torch.stack(logits_all, 1), torch.stack(ids_all, 1)
 
     @torch.no_grad()
@@ -170,16 +170,17 @@ class Attention(nn.Module):
         takes — "boundary_gap" [B, T_run]: K-th minus (K+1)-th candidate of each step's top-k (what decides which
         hypotheses survive), "beam_scores" [B, K] / "beam_tokens" [B, K, T_run]: the final hypotheses the arg-max picks from."""
         B, K, H, V = batch_H.size(0), beam_size, self.hidden_size, self.num_classes
-        toks = torch.full((B, K, 1), self.sos_id, dtype=torch.long)
-        score = torch.full((B, K), float("-inf"))
+        fd, dev = batch_H.dtype, batch_H.device
+        toks = torch.full((B, K, 1), self.sos_id, dtype=torch.long, device=dev)
+        score = torch.full((B, K), float("-inf"), dtype=fd, device=dev)
         score[:, 0] = 0.0
-        bh, bc = torch.zeros(B, K, H), torch.zeros(B, K, H)
-        done = torch.zeros(B, K, dtype=torch.bool)
+        bh, bc = torch.zeros(B, K, H, dtype=fd, device=dev), torch.zeros(B, K, H, dtype=fd, device=dev)
+        done = torch.zeros(B, K, dtype=torch.bool, device=dev)
         trace = None
         rep_H = batch_H.repeat_interleave(K, dim=0)
         for t in range(max_len):
             h1, c1 = self.attention_cell((bh.reshape(B * K, H), bc.reshape(B * K, H)), rep_H,
-                                         self._onehot(toks[:, :, -1].reshape(B * K)))
+                                         self._onehot(toks[:, :, -1].reshape(B * K), fd))
             logits = self._mask(self.generator(h1))
             if temperature != 1.0:
                 logits = logits / max(temperature, 1e-6)
@@ -198,7 +199,7 @@ class Attention(nn.Module):
             top, idx = torch.topk(cand.view(B, -1), k=K, dim=-1)
             if diag is not None:
                 tk1 = torch.topk(cand.view(B, -1), k=K + 1, dim=-1).values
-                diag.setdefault("boundary_gap", []).append((tk1[:, K - 1] - tk1[:, K]).numpy())
+                diag.setdefault("boundary_gap", []).append((tk1[:, K - 1] - tk1[:, K]).cpu().numpy())
             src = idx // V
             nxt = (idx % V).clamp(0, V - 1)
             gat = lambda x: x.gather(1, src.unsqueeze(-1).expand(-1, -1, x.size(-1)))
@@ -215,11 +216,11 @@ class Attention(nn.Module):
             if bool(done.all()):
                 break
         best = score.argmax(-1)
-        ar = torch.arange(B)
+        ar = torch.arange(B, device=dev)
         if diag is not None:
             import numpy as np
             diag["boundary_gap"] = np.stack(diag["boundary_gap"], 1)
-            diag["beam_scores"], diag["beam_tokens"] = score.numpy().copy(), toks[:, :, 1:].numpy().copy()
+            diag["beam_scores"], diag["beam_tokens"] = score.cpu().numpy().copy(), toks[:, :, 1:].cpu().numpy().copy()
         return trace[ar, best], toks[ar, best][:, 1:]
 
 

@@ -221,10 +221,11 @@ typedef struct msocr_attn_weights {
   const float* gen_b;    /* [V] */
 } msocr_attn_weights;
 
-/* Attention decode (model/model.py:34-46 cell, :227-259 greedy, :92-225 beam): one workgroup per batch row,
- * the whole step loop in ONE launch (rows are independent).  batch_H, proj_H: [B][T][H] f32 with
- * proj_H = i2h(batch_H) hoisted out of the loop (the reference recomputes it every step); H == 256, T <= 48,
- * V <= 256, steps <= 64.
+/* Attention decode (model/model.py:34-46 cell, :227-259 greedy, :92-225 beam): the whole step loop in ONE launch
+ * (rows are independent).  batch_H, proj_H: [B][T][H] f32 with proj_H = i2h(batch_H) hoisted out of the loop (the
+ * reference recomputes it every step); H a multiple of 64 in 64..512, V <= 512, T <= 64, steps <= 64, beam <= 16
+ * with beam * H <= 4096.  These two entry points run the general kernel (csrc/attn_general.hip, one workgroup per
+ * batch row, exact f32) for every such shape; the _hoisted entry points below run the matrix-core kernels.
  * greedy: steps = max_len+1; logits_out [B][steps][V] f32, ids_out [B][steps] i32 for ALL steps.
  * beam  : steps = max_len; per step the kernel stores every beam's temperature-scaled logits, back-pointers,
  *         tokens and the arg-max beam into `workspace`, and fin_step_out[b] = number of steps after which every
@@ -232,10 +233,9 @@ typedef struct msocr_attn_weights {
  *         ((5+t+1)^alpha / 6^alpha, computed by the host exactly as model.py:160) or NULL when alpha <= 0.
  *         Optional early exit (all three pointers non-NULL): chunk_id_dev[B] = index of the reference chunk (the slice of
  *         batch_size crops one model call sees) of every row, chunk_size_dev[nchunks] = rows per chunk, all of them inside
- *         this call; chunk_state_dev[2*nchunks] int32 zeroed by the caller.  A workgroup then leaves the step loop once every
- *         chunk its rows belong to is completely finished (model.py:215), so steps >= the chunk's run length are skipped.
- *         The default kernel runs the three matrix products of a step on the f32 matrix cores, 4 rows x 8 beams per
- *         workgroup (csrc/attn_beam_mfma.hip); MSOCR_BEAM_MFMA=0 selects the VALU kernel (one row per workgroup).
+ *         this call; chunk_state_dev[2*nchunks] int32 zeroed by the caller.  The matrix-core kernel (msocr_attn_beam_hoisted)
+ *         then leaves the step loop once every chunk its rows belong to is completely finished (model.py:215), so steps >=
+ *         the chunk's run length are skipped; the general kernel runs every step (same outputs for t < the run length).
  * The reference stops the loop for the whole batch chunk (model.py:215,254); the host derives each row's run length
  * t_run from ids/fin_step and msocr_attn_beam_finalize walks the back-pointers from (t_run-1, best beam at t_run-1):
  * logits_out [B][steps][V] (rows t < t_run valid), ids_out [B][steps] (-1 beyond t_run). */
@@ -257,9 +257,11 @@ typedef struct msocr_attn_split_weights {
   const uint16_t* gen_p;  /* from gen_wt, N = V */
 } msocr_attn_split_weights;
 
-/* msocr_attn_beam with the context half of the LSTMCell input product hoisted out of the step loop (matrix-core kernel only):
- * ctx_gates [B][T][H][4] f32 = batch_H x rnn.weight_ih[:, :H]^T with the four gates of a unit adjacent (row j*4+g of the
- * product), computed once per call by a GEMM (msocr_conv1x1_split).  W_ih[:, :H] (sum_t alpha_t batch_H_t) == sum_t alpha_t
+/* msocr_attn_beam on the matrix cores, 4 rows x 8 beams per workgroup (csrc/attn_beam_mfma.hip), with the context half of the
+ * LSTMCell input product hoisted out of the step loop; H == 256, V <= 256, T <= 48, beam <= 8 (other shapes: MSOCR_E_ARG — call
+ * msocr_attn_beam).  ws given: the split-operand products; ws == NULL: exact-f32 MFMA.  ctx_gates [B][T][H][4] f32 = batch_H x
+ * rnn.weight_ih[:, :H]^T with the four gates of a unit adjacent (row j*4+g of the product), computed once per call by a GEMM
+ * (msocr_conv1x1_split).  W_ih[:, :H] (sum_t alpha_t batch_H_t) == sum_t alpha_t
  * (W_ih[:, :H] batch_H_t): same result up to f32 summation order, half the matrix work per step. */
 int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                             const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev,

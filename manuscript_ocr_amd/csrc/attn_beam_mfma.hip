@@ -5,19 +5,17 @@
 //
 // One 512-thread workgroup owns NB = 4 crops x 8 beam slots = 32 state rows for the whole step loop (rows of different
 // crops are independent: no inter-workgroup hand-off).  32 rows are exactly one MFMA row block, so every weight element a
-// workgroup pulls from L2 now feeds 32 rows instead of the 8 of the VALU kernel (trba_kernels.hip): the L2 -> CU weight
-// stream that bounded that kernel (2.5 MB per step per workgroup) is shared by 4x more work, and the gate arithmetic
-// moves off the VALU.  Per step:
+// workgroup pulls from L2 feeds 32 rows instead of the 8 of a one-crop workgroup, and the gate arithmetic moves off the
+// VALU.  The context half of the gate product is hoisted out of the step loop (see attn_beam_mfma_kernel).  Per step:
 //   (a) ph    = h2h(h)                     [32x256] x [256x256]        MFMA  (wave w: columns 32w..32w+31)
-//   (b) e     = score . tanh(proj_H + ph)  32 x T dot products          VALU  (one wave per (row, t) pair)
+//   (b) e     = score . tanh(proj_H + ph)  32 x T dot products          VALU  (one wave per (crop, t) pair)
 //   (c) alpha = softmax_t(e)                                            VALU
-//   (d) ctx   = alpha . batch_H                                         VALU
-//   (e) gates = [ctx | h] x [W_ih_ctx ; W_hh]^T + W_ih_tok[token] + b   [32x512] x [512x1024]  MFMA
+//   (e) gates = sum_t alpha_t P_t + h x W_hh^T + W_ih_tok[token] + b    VALU + [32x256] x [256x1024]  MFMA
 //       (wave w owns hidden units 32w..32w+31; one 16-byte load per lane = the unit's 4 gates = B operands of 4 MFMAs,
 //        so the LSTM cell update is lane-local in the accumulator layout)
 //   (f) logits = generator(h')             [32x256] x [256xV]          MFMA
 //   (g-j) temperature, log-softmax, top-8 of 8*V candidates per crop, back-pointers, beam state permutation   VALU/LDS
-// Same outputs, workspace layout and tie rules as attn_beam_kernel (larger value first, then smaller flat index).
+// Same outputs, workspace layout and tie rules as attn_general_kernel<true> (larger value first, then smaller flat index).
 //
 // Replaces recognizers/_trba/model/model.py:34-46 (AttentionCell.forward) + :92-225 (Attention._beam_decode).
 #include <hip/hip_runtime.h>
@@ -216,18 +214,17 @@ __device__ __forceinline__ void mfma_gates(const float* __restrict__ sX, int k0,
   }
 }
 
-// HOIST: the context half of the LSTMCell input product is hoisted out of the step loop.  The reference computes
+// The context half of the LSTMCell input product is hoisted out of the step loop.  The reference computes
 // gates = W_ih [ctx ; onehot] + W_hh h with ctx = sum_t alpha_t batch_H_t (model.py:40-45); since W_ih[:, :H] ctx =
 // sum_t alpha_t (W_ih[:, :H] batch_H_t), the products P_t = W_ih[:, :H] batch_H_t are computed ONCE per crop by a GEMM before the
 // kernel (a.ctx_gates, [B][T][H][4]) and a step only forms sum_t alpha_t P_t on the VALU (13 x 1024 FMAs per row instead of
-// 256 x 1024 MACs): half of the step's matrix work, 1 of its 2.5 MB of weights and the ctx phase (d) disappear.  Same arithmetic
+// 256 x 1024 MACs): half of the step's matrix work, 1 of its 2.5 MB of weights and the context phase disappear.  Same arithmetic
 // up to the order of the f32 summation.
-// SPLITW (with HOIST): the three matrix products in the split-operand form above; h lives only as its three bf16 planes.
-template <bool HOIST, bool SPLITW>
+// SPLITW: the three matrix products in the split-operand form above, h only as its three bf16 planes; else exact-f32 MFMA.
+template <bool SPLITW>
 __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
-  static_assert(HOIST || !SPLITW, "the split form is built for the hoisted kernel");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* sX = lds;                 // [R][XS]   ctx (0..255) | h (256..511)        (exact form)
+  float* sX = lds;                 // [R][XS]   h in columns 256..511 (X = [ctx | h] of the un-hoisted product)   (exact form)
   unsigned char* sP = reinterpret_cast<unsigned char*>(lds);  // [3][R][PSB] bf16 planes of h  (split form)
   float* sbuf = SPLITW ? lds + 3 * PPL / 4 : sX + R * XS;     // [R][H]    ph, then logits, then scratch of the state permutation
   float* salpha = sbuf + R * H;    // [R][64]
@@ -328,34 +325,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     }
     __syncthreads();
     TSTAMP(3);
-    // ---- (d) ctx[r][j] = sum_t alpha[r][t] * batch_H[crop(r)][t][j] : thread = (j, half of the crops)
-    if constexpr (!HOIST) {
-      const int j = tid & 255, ch = tid >> 8;
-#pragma unroll
-      for (int n2 = 0; n2 < NB / 2; ++n2) {
-        const int nb = ch * (NB / 2) + n2;
-        const int b = min(b0 + nb, a.B - 1);
-        const float* pH = a.batch_H + (long)b * T * H + j;
-        float accd[KB8];
-#pragma unroll
-        for (int q = 0; q < KB8; ++q) accd[q] = 0.f;
-        for (int t0 = 0; t0 < T; t0 += 16) {  // 16 independent loads in flight, then the FMAs
-          float hv[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) hv[u] = (t0 + u < T) ? pH[(long)(t0 + u) * H] : 0.f;
-#pragma unroll
-          for (int u = 0; u < 16; ++u)
-            if (t0 + u < T) {
-#pragma unroll
-              for (int q = 0; q < KB8; ++q) accd[q] = fmaf(salpha[(nb * KB8 + q) * 64 + t0 + u], hv[u], accd[q]);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < KB8; ++q) sX[(nb * KB8 + q) * XS + j] = accd[q];
-      }
-    }
-    if constexpr (!HOIST) __syncthreads();
-    TSTAMP(4);
+    TSTAMP(4);  // (d) is empty, the context product being hoisted; the stamp keeps tools/attn_phase_times.sh's phase numbering
     // ---- (e) gates + LSTM cell for units ju, rows acc_row(e, half)
     {
       f32x16 acc[4];
@@ -394,7 +364,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
 #if defined(MSOCR_ATTN_SUM_BARRIER) || defined(MSOCR_ATTN_NO_STAGGER)
       constexpr bool STAGGER = false;
 #else
-      constexpr bool STAGGER = HOIST && SPLITW;
+      constexpr bool STAGGER = SPLITW;
 #endif
       if constexpr (STAGGER) {
         // The context sum is load-latency and VALU work, the recurrent product matrix-pipe work, and the two are independent: the two
@@ -405,14 +375,10 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
         mfma_gates_split(sP, a.whh_p, ju, r32, half, acc);
         if (mfma_first) ctx_sum();
       } else {
-        if constexpr (HOIST) {
-          ctx_sum();
+        ctx_sum();
 #ifdef MSOCR_ATTN_SUM_BARRIER  // dev builds: no wave enters the MFMA loop while another is still in the sum above
-          __syncthreads();
+        __syncthreads();
 #endif
-        } else {
-          mfma_gates(sX, 0, a.w.wih_ctx_t, ju, r32, half, acc);
-        }
         if constexpr (SPLITW) mfma_gates_split(sP, a.whh_p, ju, r32, half, acc);
         else mfma_gates(sX, H, a.w.whh_t, ju, r32, half, acc);
       }
@@ -682,10 +648,10 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
 // running after its own EOS and only stops a chunk when all rows emit EOS in the same step; the host derives those run lengths
 // from the ids, recognizers/_trba/__init__.py), so a step is the beam kernel's (a)-(f) without any beam bookkeeping — no
 // log-softmax, no top-k, no state permutation — followed by an arg-max per row (larger value, then smaller index; blank masked
-// to -1e4 as in attn_greedy_kernel).  Split-operand products and hoisted context gates (a.ctx_gates) as in
-// attn_beam_mfma_kernel<true, true>; gate and score nonlinearities libm-grade (see sigmoid_libm).  Each row reads ITS crop's proj_H / ctx_gates frames
+// to -1e4 as in attn_general_kernel).  Split-operand products and hoisted context gates (a.ctx_gates) as in
+// attn_beam_mfma_kernel<true>; gate and score nonlinearities libm-grade (see sigmoid_libm).  Each row reads ITS crop's proj_H / ctx_gates frames
 // (8x the beam kernel's traffic per row, from L2 / the Infinity Cache).
-// libm-grade nonlinearities for the greedy kernel: its logits are held to the VALU kernel's bound (2e-4 of max |logit| against the
+// libm-grade nonlinearities for the greedy kernel: its logits are held to the decoder-only bound (2e-4 of max |logit| against the
 // oracle's decoder over 41 chained steps of the all-random decoder, tests/test_gpu_trba.py DECODER_LOGIT_RTOL), which the hardware-
 // rate v_exp_f32 / v_rcp_f32 forms of the beam kernel miss by 5 % on one row of 96; greedy is not the pipeline's default mode.
 __device__ __forceinline__ float sigmoid_libm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -855,23 +821,21 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
 }  // namespace
 
 int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates) return MSOCR_E_ARG;
   const size_t ldsz = (size_t)(R * XS + R * H + R * 64) * sizeof(float);
   const size_t ldsz_split = (size_t)3 * PPL + (size_t)(R * H + R * 64) * sizeof(float);
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz_split) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz_split) != hipSuccess)
       return MSOCR_E_LAUNCH;
     attr = true;
   }
   const dim3 grid((a.B + NB - 1) / NB);
-  if (a.ctx_gates && a.h2h_p)
-    MSOCR_LAUNCH((attn_beam_mfma_kernel<true, true>), grid, dim3(NT), ldsz_split, s, a);
-  else if (a.ctx_gates)
-    MSOCR_LAUNCH((attn_beam_mfma_kernel<true, false>), grid, dim3(NT), ldsz, s, a);
+  if (a.h2h_p)
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<true>), grid, dim3(NT), ldsz_split, s, a);
   else
-    MSOCR_LAUNCH((attn_beam_mfma_kernel<false, false>), grid, dim3(NT), ldsz, s, a);
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<false>), grid, dim3(NT), ldsz, s, a);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 

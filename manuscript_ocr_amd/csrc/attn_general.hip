@@ -1,10 +1,12 @@
-// attn_general.hip — attention decode of the TRBA recogniser for the shapes the two fast kernels do not take:
-// hidden sizes other than 256 (the reference reads hidden_size from the checkpoint's config, recognizers/_trba/__init__.py:142-151),
-// charsets of up to 512 tokens, beam widths of up to 16 (TRBA.predict exposes beam_size, :295-299; the reference's own Optuna
-// script sweeps 2..12).  Same arithmetic, outputs, workspace layout and tie rules as attn_greedy_kernel / attn_beam_kernel
-// (trba_kernels.hip): one 256-thread workgroup per batch row runs the whole step loop, the K beam rows' state (h, c, context,
-// h2h projection, logits) lives in LDS, every phase is a strided loop over (row, unit) or (row, token) pairs, weights stream from
-// L2.  Written for generality, not speed: the default configuration (hidden 256, 194 tokens, beam 8) never comes here.
+// attn_general.hip — attention decode of the TRBA recogniser for every shape of the envelope: hidden sizes 64..512 (the reference
+// reads hidden_size from the checkpoint's config, recognizers/_trba/__init__.py:142-151), charsets of up to 512 tokens, beam widths
+// of up to 16 (TRBA.predict exposes beam_size, :295-299; the reference's own Optuna script sweeps 2..12).  The plain entry points
+// (msocr_attn_greedy / msocr_attn_beam) run it; the recogniser takes it for the shapes the matrix-core kernels (attn_beam_mfma.hip:
+// hidden 256, <= 256 tokens, <= 48 frames, beam <= 8) do not take, and for greedy decoding under precision "fp32-exact".  Exact f32
+// with libm-grade expf / tanhf; same outputs, workspace layout and tie rules as the matrix-core kernels: one 256-thread workgroup
+// per batch row runs the whole step loop, the K beam rows' state (h, c, context, h2h projection, logits) lives in LDS, every phase
+// is a strided loop over (row, unit) or (row, token) pairs, weights stream from L2.  Written for generality, not speed: the default
+// configuration (hidden 256, 194 tokens, beam 8, precision "fp32") never comes here.
 //
 // Replaces recognizers/_trba/model/model.py:34-46 (AttentionCell.forward), :227-259 (_greedy_decode), :92-225 (_beam_decode).
 #include <hip/hip_runtime.h>

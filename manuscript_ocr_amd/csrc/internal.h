@@ -13,14 +13,14 @@ __attribute__((visibility("hidden"))) int msocr_internal_gemm_f32_batched(const 
 __attribute__((visibility("hidden"))) int msocr_internal_gemm_split_batched(const float* A, const uint16_t* Bplanes, float* C, long M,
                                                                             int N, int K, int nbatch, hipStream_t s);
 
-// attention decoder arguments shared by trba_kernels.hip (VALU kernels) and attn_beam_mfma.hip (matrix-core beam kernel)
+// attention decoder arguments shared by trba_kernels.hip (entry points), attn_beam_mfma.hip (matrix-core kernels) and attn_general.hip
 #include "msocr.h"
 struct AttnArgs {
   const float* batch_H;
   const float* proj_H;
-  const float* ctx_gates;  // optional (matrix-core beam kernel): [B][T][H][4] = batch_H x rnn.weight_ih[:, :H]^T, hoisted out of the step loop
+  const float* ctx_gates;  // matrix-core kernels: [B][T][H][4] = batch_H x rnn.weight_ih[:, :H]^T, hoisted out of the step loop
   msocr_attn_weights w;
-  const uint16_t *h2h_p, *whh_p, *gen_p;  // optional (matrix-core beam kernel, with ctx_gates): msocr_attn_split_weights
+  const uint16_t *h2h_p, *whh_p, *gen_p;  // matrix-core kernels: msocr_attn_split_weights (greedy: required; beam: nullptr = exact f32)
   int B, T, V, steps, K;
   int sos_id, eos_id, blank_id;
   float temperature;
@@ -35,11 +35,12 @@ struct AttnArgs {
   const int32_t* chunk_size;  // [nchunks] crops per chunk
   int32_t* chunk_state;       // [2*nchunks] zeroed by the caller: {crops finished, max finish step}; enables the early exit
 };
-// attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the f32 matrix cores (H == 256, beam <= 8, T <= 64)
+// attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the matrix cores (H == 256, V <= 256, T <= 48, beam <= 8;
+// needs ctx_gates): split-operand products with the split weights, exact-f32 MFMA without them
 __attribute__((visibility("hidden"))) int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s);
-// attn_beam_mfma.hip: greedy decode with 32 crops per workgroup on the matrix cores (needs ctx_gates and the split weights)
+// attn_beam_mfma.hip: greedy decode with 32 crops per workgroup on the matrix cores (same shapes; needs ctx_gates and the split weights)
 __attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma(const AttnArgs& a, hipStream_t s);
-// attn_general.hip: greedy / beam decode for hidden sizes other than 256, charsets above 256 tokens, beams above 8 (see its header
-// for the shapes taken); same outputs and workspace layout as the fast kernels.
+// attn_general.hip: greedy / beam decode for every shape of the envelope (see its header), H == 256 included; the plain entry points
+// msocr_attn_greedy / msocr_attn_beam run it.  Same outputs and workspace layout as the matrix-core kernels.
 __attribute__((visibility("hidden"))) int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t s);
 #endif

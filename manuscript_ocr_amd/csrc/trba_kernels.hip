@@ -1,17 +1,18 @@
 // trba_kernels.hip — the non-convolutional part of the TRBA recogniser on gfx950:
-// squeeze-excite tail, mean over H, BiLSTM recurrence and the attention decoder
-// (greedy and beam).  These stages are bandwidth/latency bound: they run
-// on the VALU in exact f32 with coalesced weight streams (weights pre-transposed so lane j
-// reads column j), LDS-resident per-row state and wave-level reductions; no MFMA.
-// The sequential loops (T encoder steps, <= 26 decoder steps) live INSIDE one launch:
-// rows are independent, so one workgroup owns a row (or a few) for the whole loop and no
-// inter-workgroup hand-off exists.
+// squeeze-excite tail, mean over H, BiLSTM recurrence, the attention decoder's entry points
+// and the recognition confidence.  These stages are bandwidth/latency bound:
+// they run on the VALU in exact f32 with coalesced weight streams (weights pre-transposed so
+// lane j reads column j), LDS-resident per-row state and wave-level reductions; no MFMA.
+// The sequential loop (T encoder steps) lives INSIDE one launch: rows are independent, so
+// one workgroup owns a few rows for the whole loop and no inter-workgroup hand-off exists.
+// The decode kernels themselves are in attn_beam_mfma.hip and attn_general.hip.
 //
 //   msocr_se_residual       <- recognizers/_trba/model/seresnet31.py:5-20, 61-66
 //   msocr_mean_over_h       <- recognizers/_trba/model/model.py:388-390
 //   msocr_bilstm_recurrent  <- model.py:9-21 (nn.LSTM, gate order i,f,g,o)
-//   msocr_attn_greedy       <- model.py:34-46 + 227-259
-//   msocr_attn_beam(+_finalize) <- model.py:34-46 + 92-225
+//   msocr_attn_greedy(_hoisted)       <- model.py:34-46 + 227-259
+//   msocr_attn_beam(_hoisted, _finalize) <- model.py:34-46 + 92-225
+//   msocr_seq_confidence    <- recognizers/_trba/__init__.py:413-431
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -298,397 +299,8 @@ extern "C" int msocr_bilstm_recurrent(const float* xproj, const float* w_hh_t, i
 }
 
 // --------------------------------------------------------------------------------------------- attention decoder
-// One workgroup (256 threads, H == 256) owns NB batch rows for the whole step loop; KR = NB*RPB state rows
-// (RPB = 1 greedy, 8 beam).  Thread j owns hidden unit j (4 gates x KR rows in registers); weights are
-// pre-transposed so lane j streams column j (gate-interleaved: one 16-B load per k); every weight element a
-// workgroup fetches from L2 is used for KR rows, so NB = 2 halves the L2 traffic that bounds this kernel.
-// LDS: batch_H / proj_H of the NB rows [NB][T][H], h and ctx as [k][row], ph[row][j], alpha[row][t], logits[row][v].
-#define ATT_H 256
-#define ATT_KMAX 8
-
-
-template <int KR, int RPB, int PF = 4>
-__device__ __forceinline__ void attention_cell_step(const AttnArgs& a, int tid, const float* sH, const float* sP, float (*sh)[KR],
-                                                    float (*sctx)[KR], float (*sph)[ATT_H], float (*salpha)[64],
-                                                    float (*slog)[256], float (&c)[KR], const int* tok, int T, int V) {
-  constexpr int H = ATT_H;
-  const int j = tid;
-  // (a) ph[r][j] = h2h(h)[j]
-  {
-    float acc[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) acc[r] = a.w.h2h_b[j];
-#pragma unroll 1
-    for (int k0 = 0; k0 < H; k0 += 8) {
-      float wq[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) wq[u] = a.w.h2h_wt[(long)(k0 + u) * H + j];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int r = 0; r < KR; ++r) acc[r] = fmaf(wq[u], sh[k0 + u][r], acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < KR; ++r) sph[r][j] = acc[r];
-  }
-  __syncthreads();
-  // (b) e[r][t] = score . tanh(proj_H[t] + ph[r]) : one wave per (r,t) pair, lanes over j
-  {
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int p = wv; p < KR * T; p += 4) {
-      const int r = p / T, t = p - r * T;
-      const float* pP = sP + (r / RPB) * T * H;
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < H / 64; ++q) {
-        const int jj = lane + 64 * q;
-        s = fmaf(a.w.score_w[jj], tanhf(pP[t * H + jj] + sph[r][jj]), s);
-      }
-      s = wave_sum(s);
-      if (lane == 0) salpha[r][t] = s;
-    }
-  }
-  __syncthreads();
-  // (c) softmax over t (T <= 64): thread r
-  if (tid < KR) {
-    float m = -INFINITY;
-    for (int t = 0; t < T; ++t) m = fmaxf(m, salpha[tid][t]);
-    float sum = 0.f;
-    for (int t = 0; t < T; ++t) {
-      const float e = expf(salpha[tid][t] - m);
-      salpha[tid][t] = e;
-      sum += e;
-    }
-    for (int t = 0; t < T; ++t) salpha[tid][t] = salpha[tid][t] / sum;
-  }
-  __syncthreads();
-  // (d) ctx[r][j] = sum_t alpha[r][t] * batch_H[t][j]
-  {
-    float acc[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) acc[r] = 0.f;
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-      for (int nb = 0; nb < KR / RPB; ++nb) {
-        const float hv = sH[(nb * T + t) * H + j];
-#pragma unroll
-        for (int q = 0; q < RPB; ++q) acc[nb * RPB + q] = fmaf(salpha[nb * RPB + q][t], hv, acc[nb * RPB + q]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < KR; ++r) sctx[j][r] = acc[r];
-  }
-  __syncthreads();
-  // (e) LSTMCell gates: W_ih[:, :H] ctx + W_ih[:, H+tok] + W_hh h + (b_ih + b_hh); thread j owns unit j
-  float g4[4][KR];
-  {
-    const f32x4 b4 = *reinterpret_cast<const f32x4*>(&a.w.b_gates[j * 4]);
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-      const f32x4 t4 = *reinterpret_cast<const f32x4*>(&a.w.wih_tok[((long)tok[r] * H + j) * 4]);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) g4[g][r] = b4[g] + t4[g];
-    }
-  }
-  // weights stream from L2: keep PF 16-byte loads in flight per lane (the FMAs of a k-group run under the next group's loads)
-  auto gate_pass = [&](const float* __restrict__ wt, float (*x)[KR]) {
-    f32x4 wq[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) wq[u] = *reinterpret_cast<const f32x4*>(&wt[((long)u * H + j) * 4]);
-#pragma unroll 1
-    for (int k0 = 0; k0 < H; k0 += PF) {
-      f32x4 wn[PF];
-      if (k0 + PF < H) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) wn[u] = *reinterpret_cast<const f32x4*>(&wt[((long)(k0 + PF + u) * H + j) * 4]);
-      }
-#pragma unroll
-      for (int u = 0; u < PF; ++u)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-          for (int r = 0; r < KR; ++r) g4[g][r] = fmaf(wq[u][g], x[k0 + u][r], g4[g][r]);
-      if (k0 + PF < H) {
-#pragma unroll
-        for (int u = 0; u < PF; ++u) wq[u] = wn[u];
-      }
-    }
-  };
-  gate_pass(a.w.wih_ctx_t, sctx);
-  gate_pass(a.w.whh_t, sh);
-  __syncthreads();  // everyone finished reading the old h
-#pragma unroll
-  for (int r = 0; r < KR; ++r) {
-    const float ig = sigmoidf_(g4[0][r]), fg = sigmoidf_(g4[1][r]), gg = tanhf(g4[2][r]), og = sigmoidf_(g4[3][r]);
-    c[r] = fg * c[r] + ig * gg;
-    sh[j][r] = og * tanhf(c[r]);
-  }
-  __syncthreads();
-  // (f) generator logits[r][v]
-  if (tid < V) {
-    float acc[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) acc[r] = a.w.gen_b[tid];
-#pragma unroll 1
-    for (int k0 = 0; k0 < H; k0 += 8) {
-      float wq[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) wq[u] = a.w.gen_wt[(long)(k0 + u) * V + tid];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int r = 0; r < KR; ++r) acc[r] = fmaf(wq[u], sh[k0 + u][r], acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < KR; ++r) slog[r][tid] = (tid == a.blank_id) ? -1e4f : acc[r];
-  }
-  __syncthreads();
-}
-
-// block-wide arg-max over (value, index) pairs with "larger value, then smaller index" order
-__device__ __forceinline__ void block_argmax(float v, int idx, float* s_val, int* s_idx, int tid, float& out_v, int& out_i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(idx, o);
-    if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-  }
-  if ((tid & 63) == 0) { s_val[tid >> 6] = v; s_idx[tid >> 6] = idx; }
-  __syncthreads();
-  out_v = s_val[0];
-  out_i = s_idx[0];
-  for (int w = 1; w < 4; ++w)
-    if (s_val[w] > out_v || (s_val[w] == out_v && s_idx[w] < out_i)) { out_v = s_val[w]; out_i = s_idx[w]; }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void attn_greedy_kernel(AttnArgs a) {
-  constexpr int H = ATT_H, K = 1;
-  extern __shared__ __attribute__((aligned(16))) float dyn[];  // batch_H[T][H] | proj_H[T][H]
-  __shared__ __attribute__((aligned(16))) float sh[H][K], sctx[H][K];
-  __shared__ float sph[K][H], salpha[K][64], slog[K][256];
-  __shared__ float s_val[4];
-  __shared__ int s_idx[4];
-  const int b = blockIdx.x, tid = threadIdx.x, T = a.T, V = a.V;
-  float* sH = dyn;
-  float* sP = dyn + T * H;
-  for (int i = tid; i < T * H; i += 256) {
-    sH[i] = a.batch_H[(long)b * T * H + i];
-    sP[i] = a.proj_H[(long)b * T * H + i];
-  }
-  float c[K] = {0.f};
-  sh[tid][0] = 0.f;
-  int tok[K] = {a.sos_id};
-  __syncthreads();
-  for (int s = 0; s < a.steps; ++s) {
-    attention_cell_step<K, 1>(a, tid, sH, sP, sh, sctx, sph, salpha, slog, c, tok, T, V);
-    float v = -INFINITY;
-    int idx = 0x7fffffff;
-    if (tid < V) {
-      v = slog[0][tid];
-      idx = tid;
-      a.logits_out[((long)b * a.steps + s) * V + tid] = v;
-    }
-    float bv;
-    int bi;
-    block_argmax(v, idx, s_val, s_idx, tid, bv, bi);
-    tok[0] = bi;
-    if (tid == 0) a.ids_out[(long)b * a.steps + s] = bi;
-  }
-}
-
-// DIAGNOSTIC kernel (MSOCR_BEAM_MFMA=0), off the default path: the default beam decoder is attn_beam_mfma_kernel (attn_beam_mfma.hip);
-// this VALU form stays as its independent cross-check (tests/test_gpu_trba.py: MFMA vs VALU agreement, three-way parity test).
-// HB = number of 256-thread halves per workgroup.  With HB = 2 two batch rows share one workgroup: both halves run
-// the same instruction stream between the same barriers, so the second half's weight loads hit the lines the first
-// half just pulled into the CU's L1 — the L2 -> L1 weight stream that bounds this kernel is paid once for two rows,
-// at unchanged registers per thread and waves per CU.
-template <int NB, int HB, int PF = 4>
-__global__ __launch_bounds__(256 * HB, (NB == 1 && HB == 1) ? 2 : 1) void attn_beam_kernel(AttnArgs a) {
-  constexpr int H = ATT_H, K = ATT_KMAX, KR = NB * K;
-  extern __shared__ __attribute__((aligned(16))) float dyn[];  // per half: batch_H[NB][T][H] | proj_H[NB][T][H]
-  __shared__ __attribute__((aligned(16))) float sh_[HB][H][KR], sctx_[HB][H][KR];
-  __shared__ float sph_[HB][KR][H], salpha_[HB][KR][64], slog_[HB][KR][256];
-  __shared__ float s_val_[HB][4];
-  __shared__ int s_idx_[HB][4];
-  __shared__ float s_score_[HB][KR], s_lse_[HB][KR], s_top_[HB][KR];
-  __shared__ int s_tok_[HB][KR], s_done_[HB][KR], s_src_[HB][KR], s_nxt_[HB][KR];
-  const int half = threadIdx.x >> 8, tid = threadIdx.x & 255;
-  float (*sh)[KR] = sh_[half];
-  float (*sctx)[KR] = sctx_[half];
-  float (*sph)[H] = sph_[half];
-  float (*salpha)[64] = salpha_[half];
-  float (*slog)[256] = slog_[half];
-  float* s_val = s_val_[half];
-  int* s_idx = s_idx_[half];
-  float *s_score = s_score_[half], *s_lse = s_lse_[half], *s_top = s_top_[half];
-  int *s_tok = s_tok_[half], *s_done = s_done_[half], *s_src = s_src_[half], *s_nxt = s_nxt_[half];
-  const int b0 = (blockIdx.x * HB + half) * NB, T = a.T, V = a.V, KB = a.K;
-  float* sH = dyn + half * (2 * NB * T * H);
-  float* sP = sH + NB * T * H;
-  for (int nb = 0; nb < NB; ++nb) {
-    const int b = min(b0 + nb, a.B - 1);  // a ragged last workgroup recomputes row B-1 and does not store it
-    for (int i = tid; i < T * H; i += 256) {
-      sH[nb * T * H + i] = a.batch_H[(long)b * T * H + i];
-      sP[nb * T * H + i] = a.proj_H[(long)b * T * H + i];
-    }
-  }
-  float c[KR];
-#pragma unroll
-  for (int r = 0; r < KR; ++r) {
-    c[r] = 0.f;
-    sh[tid][r] = 0.f;
-  }
-  if (tid < KR) {
-    s_score[tid] = (tid % K) == 0 ? 0.f : -INFINITY;
-    s_tok[tid] = a.sos_id;
-    s_done[tid] = 0;
-  }
-  __syncthreads();
-  int fin[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) fin[nb] = a.steps;
-  const float temp = fmaxf(a.temperature, 1e-6f);
-  for (int s = 0; s < a.steps; ++s) {
-    int tok[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) tok[r] = s_tok[r];
-    attention_cell_step<KR, K, PF>(a, tid, sH, sP, sh, sctx, sph, salpha, slog, c, tok, T, V);
-    // temperature (true f32 division, model.py:135-137), keep the scaled logits for the trace
-    if (tid < V) {
-#pragma unroll
-      for (int r = 0; r < KR; ++r) {
-        float v = slog[r][tid];
-        if (a.temperature != 1.0f) v = v / temp;
-        slog[r][tid] = v;
-        const int b = b0 + r / K, rb = r % K;
-        if (rb < KB && b < a.B) a.logits_out[(((long)b * a.steps + s) * KB + rb) * V + tid] = v;
-      }
-    }
-    __syncthreads();
-    // log_softmax per state row: one wave per row
-    {
-      const int lane = tid & 63, wv = tid >> 6;
-      for (int r = wv; r < KR; r += 4) {
-        float m = -INFINITY;
-        for (int v = lane; v < V; v += 64) m = fmaxf(m, slog[r][v]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        float sum = 0.f;
-        for (int v = lane; v < V; v += 64) sum += expf(slog[r][v] - m);
-        sum = wave_sum(sum);
-        if (lane == 0) s_lse[r] = m + logf(sum);
-      }
-    }
-    __syncthreads();
-    // candidates: cand[r][v] = (score[r] + logp[r][v]) / lp ; finished beams: only EOS with logp 0
-    const float lp = a.lp ? a.lp[s] : 1.0f;
-    float cv[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-      cv[r] = -INFINITY;
-      if (tid < V && (r % K) < KB) {
-        float logp = slog[r][tid] - s_lse[r];  // log_softmax = x - (max + log(sum exp(x - max)))
-        if (s_done[r]) logp = (tid == a.eos_id) ? 0.f : -INFINITY;
-        float tot = s_score[r] + logp;
-        if (a.lp) tot = tot / lp;
-        cv[r] = tot;
-      }
-    }
-    // top-K per batch row by K rounds of block arg-max over its K*V candidates (flat index = beam*V + v)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      for (int kk = 0; kk < KB; ++kk) {
-        float bvv = -INFINITY;
-        int bii = 0x7fffffff;
-#pragma unroll
-        for (int rb = 0; rb < K; ++rb) {
-          const int fi = rb * V + tid;
-          const float x = cv[nb * K + rb];
-          if (tid < V && rb < KB && (x > bvv || (x == bvv && fi < bii))) { bvv = x; bii = fi; }
-        }
-        float wv_;
-        int wi_;
-        block_argmax(bvv, bii, s_val, s_idx, tid, wv_, wi_);
-        if (wi_ == 0x7fffffff) wi_ = 0;  // every candidate NaN: degenerate input
-        if (tid == 0) {
-          s_top[nb * K + kk] = wv_;
-          s_src[nb * K + kk] = wi_ / V;
-          s_nxt[nb * K + kk] = wi_ % V;
-        }
-        // remove the winner: NaN never wins a comparison again
-        if (tid < V) {
-          const int wr = wi_ / V, wc = wi_ - wr * V;
-#pragma unroll
-          for (int rb = 0; rb < K; ++rb)
-            if (rb == wr && tid == wc) cv[nb * K + rb] = __int_as_float(0x7fc00000);
-        }
-      }
-    }
-    __syncthreads();
-    // reorder beam state by src (within each batch row)
-    float cn[KR], hn[KR];
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-      const int nb = r / K, rb = r % K;
-      const int src = rb < KB ? s_src[r] : rb;
-      float cc = 0.f, hh = 0.f;
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        cc = (q == src) ? c[nb * K + q] : cc;
-        hh = (q == src) ? sh[tid][nb * K + q] : hh;
-      }
-      cn[r] = cc;
-      hn[r] = hh;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-      c[r] = cn[r];
-      sh[tid][r] = hn[r];
-    }
-    int nd[KR];
-    int alldone[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) alldone[nb] = 1;
-#pragma unroll
-    for (int r = 0; r < KR; ++r) {
-      const int nb = r / K, rb = r % K;
-      nd[r] = rb < KB ? (s_done[nb * K + s_src[r]] | (s_nxt[r] == a.eos_id)) : 1;
-      alldone[nb] &= nd[r];
-    }
-    __syncthreads();
-    if (tid < KR) {
-      const int nb = tid / K, rb = tid % K, b = b0 + nb;
-      if (rb < KB) {
-        if (b < a.B) {
-          const long o = ((long)b * a.steps + s) * KB + rb;
-          a.back[o] = s_src[tid];
-          a.tokv[o] = s_nxt[tid];
-        }
-        s_score[tid] = a.lp ? s_top[tid] * lp : s_top[tid];  // f32 round trip of the reference (model.py:188-192)
-        s_tok[tid] = s_nxt[tid];
-        s_done[tid] = nd[tid];
-      }
-    }
-    __syncthreads();
-    if (tid < NB && b0 + tid < a.B) {
-      // best beam if the loop stopped after this step: argmax of the un-normalised sums, first maximum
-      int best = 0;
-      float bs = s_score[tid * K];
-      for (int r = 1; r < KB; ++r)
-        if (s_score[tid * K + r] > bs) { bs = s_score[tid * K + r]; best = r; }
-      a.best_at[(long)(b0 + tid) * a.steps + s] = best;
-    }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-      if (alldone[nb] && fin[nb] == a.steps) fin[nb] = s + 1;
-    __syncthreads();
-  }
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-    if (tid == 0 && b0 + nb < a.B) a.fin_step[b0 + nb] = fin[nb];
-}
+// The decode kernels live in attn_beam_mfma.hip (matrix cores: the _hoisted entries) and attn_general.hip (every shape: the plain
+// entries); this file keeps the argument checks, the beam workspace layout and the finalize step.
 
 // finalize: walk the back-pointers from (t_run-1, best_at[t_run-1]) and gather the path's logits
 __global__ void attn_beam_finalize_kernel(const float* __restrict__ ws_logits, const int32_t* __restrict__ back,
@@ -714,8 +326,8 @@ __global__ void attn_beam_finalize_kernel(const float* __restrict__ ws_logits, c
       logits_out[((long)b * steps + t) * V + v] = ws_logits[(((long)b * steps + t) * K + path[t]) * V + v];
 }
 
-// shapes of the two fast kernels (one hidden unit per thread, logits of one row in 256 LDS floats)
-static bool attn_fast_shape(int T, int H, int V) { return H == ATT_H && V <= 256 && T <= 48; }
+// shapes of the matrix-core kernels (attn_beam_mfma.hip: hidden 256, the logits of a row in 256 LDS floats, T <= 48; beam <= 8)
+static bool attn_mfma_shape(int T, int H, int V) { return H == 256 && V <= 256 && T <= 48; }
 static int check_attn(const float* bh, const float* ph, const msocr_attn_weights* w, int B, int T, int H, int V, int steps) {
   if (!bh || !ph || !w || B <= 0 || T <= 0 || T > 64 || H < 64 || H > 512 || H % 64 || V <= 0 || V > 512 || steps <= 0 || steps > 64)
     return MSOCR_E_ARG;
@@ -724,6 +336,7 @@ static int check_attn(const float* bh, const float* ph, const msocr_attn_weights
   return MSOCR_OK;
 }
 
+// every shape of the envelope on the general kernel (attn_general.hip)
 extern "C" int msocr_attn_greedy(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
                                  int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
@@ -733,16 +346,7 @@ extern "C" int msocr_attn_greedy(const float* batch_H, const float* proj_H, cons
   a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
   a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = 1.0f;
   a.logits_out = logits_out; a.ids_out = ids_out;
-  if (!attn_fast_shape(T, H, V)) return msocr_internal_attn_general(a, H, false, (hipStream_t)stream);
-  const size_t lds = (size_t)2 * T * ATT_H * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)attn_greedy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 48 * ATT_H * 4) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
-  MSOCR_LAUNCH(attn_greedy_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, a);
-  return LAUNCH_OK();
+  return msocr_internal_attn_general(a, H, false, (hipStream_t)stream);
 }
 
 // mode="greedy" on the matrix cores (attn_greedy_mfma_kernel, csrc/attn_beam_mfma.hip): 32 crops per workgroup, the three per-step
@@ -752,7 +356,7 @@ extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj
                                          const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
                                          int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
-  if (sos_id < 0 || sos_id >= V || !attn_fast_shape(T, H, V)) return MSOCR_E_ARG;
+  if (sos_id < 0 || sos_id >= V || !attn_mfma_shape(T, H, V)) return MSOCR_E_ARG;
   if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
   if (!ws || !ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15))
     return MSOCR_E_ARG;
@@ -772,10 +376,30 @@ extern "C" int64_t msocr_attn_beam_workspace_bytes(int B, int steps, int beam, i
   return beam_ws_logits(B, steps, beam, V) + (int64_t)B * steps * beam * 8 + (int64_t)B * steps * 4 + 256;
 }
 
+// ctx_gates == nullptr (msocr_attn_beam): the general kernel, every shape of the envelope; otherwise (msocr_attn_beam_hoisted) the
+// matrix-core kernel, its products in the split-operand form with ws, on the exact-f32 MFMA without
 static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                           const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
                           int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                          int32_t* chunk_state_dev, void* stream);
+                          int32_t* chunk_state_dev, void* stream) {
+  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
+  if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
+  if (ctx_gates && (!attn_mfma_shape(T, H, V) || beam > 8)) return MSOCR_E_ARG;
+  AttnArgs a{};
+  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
+  if (ws) { a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p; }
+  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = beam;
+  a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = temperature; a.lp = lp_dev;
+  char* p = (char*)workspace;
+  a.logits_out = (float*)p; p += beam_ws_logits(B, steps, beam, V);
+  a.back = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
+  a.tokv = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
+  a.best_at = (int32_t*)p;
+  a.fin_step = fin_step_out;
+  if (chunk_id_dev && chunk_size_dev && chunk_state_dev) { a.chunk_id = chunk_id_dev; a.chunk_size = chunk_size_dev; a.chunk_state = chunk_state_dev; }
+  if (!ctx_gates) return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
+  return msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
+}
 
 extern "C" int msocr_attn_beam(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
                                int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
@@ -795,63 +419,6 @@ extern "C" int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H
     return MSOCR_E_ARG;
   return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
                         fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, stream);
-}
-
-static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                          const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                          int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                          int32_t* chunk_state_dev, void* stream) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
-  if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
-  AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
-  if (ws) { a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p; }
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = beam;
-  a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = temperature; a.lp = lp_dev;
-  char* p = (char*)workspace;
-  a.logits_out = (float*)p; p += beam_ws_logits(B, steps, beam, V);
-  a.back = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
-  a.tokv = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
-  a.best_at = (int32_t*)p;
-  a.fin_step = fin_step_out;
-  if (chunk_id_dev && chunk_size_dev && chunk_state_dev) { a.chunk_id = chunk_id_dev; a.chunk_size = chunk_size_dev; a.chunk_state = chunk_state_dev; }
-  if (!attn_fast_shape(T, H, V) || beam > ATT_KMAX) {  // other hidden sizes, charsets above 256, beams above 8: the general kernel
-    if (ctx_gates) return MSOCR_E_ARG;
-    return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
-  }
-  // NB = 2 batch rows per workgroup when their encoder rows fit in LDS beside the 68 KB of state (T <= 20), else 1
-  // two batch rows per workgroup (two 256-thread halves sharing the weight stream through L1) when both rows' encoder
-  // tiles fit in LDS beside 2 x 34 KB of state (T <= 20); MSOCR_BEAM_HB=1 forces one row per workgroup
-  int HB = 1;  // measured: two rows per workgroup (MSOCR_BEAM_HB=2) runs at the same speed (6.6 ms per 960 rows), so the
-  {            // kernel is bound by per-wave issue/latency, not by the L2 -> L1 weight stream; one row stays the default
-    const char* e = getenv("MSOCR_BEAM_HB");
-    if (e && e[0] == '2' && T <= 20 && B >= 2) HB = 2;
-  }
-  // default: the matrix-core kernel (4 crops x 8 beams per workgroup); MSOCR_BEAM_MFMA=0 selects the VALU kernel below
-  const char* em = getenv("MSOCR_BEAM_MFMA");  // read per call: tests switch kernels inside one process
-  const bool use_mfma = !(em && em[0] == '0');
-  if (use_mfma && HB == 1) return msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
-  a.ctx_gates = nullptr;  // the VALU kernels form the context vector themselves
-  const size_t lds = (size_t)2 * HB * T * ATT_H * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)attn_beam_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 48 * ATT_H * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_kernel<1, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 48 * ATT_H * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_kernel<1, 1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 48 * ATT_H * 4) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 20 * ATT_H * 4) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
-  static const int pf = getenv("MSOCR_BEAM_PF") ? atoi(getenv("MSOCR_BEAM_PF")) : 4;
-  if (HB == 2)
-    MSOCR_LAUNCH((attn_beam_kernel<1, 2>), dim3((B + 1) / 2), dim3(512), lds, (hipStream_t)stream, a);
-  else if (pf == 8)
-    MSOCR_LAUNCH((attn_beam_kernel<1, 1, 8>), dim3(B), dim3(256), lds, (hipStream_t)stream, a);
-  else if (pf == 16)
-    MSOCR_LAUNCH((attn_beam_kernel<1, 1, 16>), dim3(B), dim3(256), lds, (hipStream_t)stream, a);
-  else
-    MSOCR_LAUNCH((attn_beam_kernel<1, 1>), dim3(B), dim3(256), lds, (hipStream_t)stream, a);
-  return LAUNCH_OK();
 }
 
 extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,

@@ -12,13 +12,12 @@ model/seresnet31.py:180-187 with:
     the one-hot matmul replaced by a row gather of W_ih (model.py:36,44: identical arithmetic).
 The CNN may run in bf16 (`dtype`).  The recurrent and attention stages keep f32 state and f32 accumulation in every mode; under
 precision="fp32" (the default) their matrix products are the split-operand form on the bf16 pipes (f32 result up to summation
-order) and their gate nonlinearities use the hardware-rate v_exp_f32 / v_rcp_f32 (1-2 ulp); precision="fp32-exact" runs the
-exact-f32 MFMA / VALU kernels with libm-grade expf / tanhf throughout.
+order) and their gate nonlinearities use the hardware-rate v_exp_f32 / v_rcp_f32 (1-2 ulp); precision="fp32-exact" runs
+exact-f32 MFMA / VALU kernels (the decoder: beam on the matrix-core kernel's exact-f32 form, greedy on the general kernel).
 """
 import ctypes
 
 import numpy as np
-import os
 
 import torch
 
@@ -42,9 +41,10 @@ def _gate_interleave(w_t, H):
     return w_t.reshape(K, 4, H).permute(0, 2, 1).contiguous()
 
 
-# Beam decode: hoist the context half of the LSTMCell input product out of the step loop (csrc/attn_beam_mfma.hip, HOIST);
-# MSOCR_BEAM_HOIST=0 keeps the reference's per-step formulation.
-HOIST_CTX = os.environ.get("MSOCR_BEAM_HOIST", "1") != "0"
+# Decoder entry points: True = the `_hoisted` ones (context half of the LSTMCell input product hoisted out of the step loop) on the
+# matrix-core kernels wherever AttnDecoder._matrix_core allows; False = the plain ones, i.e. the general kernel for every shape
+# (csrc/attn_general.hip) — what the tests set to cross-check the matrix-core kernels on the device.
+HOIST_CTX = True
 
 LAYER_SPEC = (("layer1", 1, 2), ("layer2", 2, 1), ("layer3", 5, 2), ("layer4", 3, 1))
 
@@ -164,8 +164,8 @@ class TrbaNet:
 
 def check_decoder_shape(hidden, num_classes):
     # hidden_size comes from the checkpoint's config.json (reference __init__.py:142-151, default 256).  256 / <= 256 tokens /
-    # beam <= 8 run on the fast decoder kernels; other multiples of 64 up to 512, charsets up to 512 tokens and beams up to 16
-    # (beam x hidden <= 4096) on the general one (csrc/attn_general.hip)
+    # beam <= 8 run on the matrix-core decoder kernels (AttnDecoder._matrix_core); other multiples of 64 up to 512, charsets up to
+    # 512 tokens and beams up to 16 (beam x hidden <= 4096) on the general one (csrc/attn_general.hip)
     if hidden % 64 or not 64 <= hidden <= 512:
         raise ValueError(f"hidden_size must be a multiple of 64 between 64 and 512 for the HIP recurrent / attention kernels, got {hidden}")
     if num_classes > 512:
@@ -225,6 +225,14 @@ class AttnDecoder:
                 setattr(asw, dst, self.att[dst].data_ptr())
             self._asw = asw
 
+    def _matrix_core(self, T, beam_size=None):
+        """Whether a decode of T frames runs on the matrix-core kernels (csrc/attn_beam_mfma.hip, the `_hoisted` entries): hidden 256,
+        <= 256 tokens, <= 48 frames; greedy also needs the split weights (precision "fp32"), beam a width <= 8 (without the split
+        weights it runs on exact-f32 MFMA).  Everything else, and everything under HOIST_CTX = False, runs on the general kernel."""
+        if not HOIST_CTX or self.Hd != 256 or self.V > 256 or T > 48:
+            return False
+        return self._asw is not None if beam_size is None else beam_size <= 8
+
     def ctx_gates(self, batch_H):
         """W_ih[:, :H] batch_H_t for every frame: [B*T, H*4] (unit-major, gates adjacent), the hoisted context product."""
         B, T, H = batch_H.shape
@@ -237,10 +245,7 @@ class AttnDecoder:
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         ids = torch.empty((B, steps), dtype=torch.int32, device=self.device)
         blank = -1 if blank_id is None else blank_id
-        # default: the matrix-core row-block kernel (32 crops per workgroup, split-operand products, hoisted context gates), like
-        # the beam path; MSOCR_GREEDY_MFMA=0, precision="fp32-exact" and shapes outside the fast kernels: the VALU / general kernel
-        fast = H == 256 and self.V <= 256 and T <= 48 and self._asw is not None
-        if fast and HOIST_CTX and os.environ.get("MSOCR_GREEDY_MFMA", "1") != "0":
+        if self._matrix_core(T):  # 32 crops per workgroup, split-operand products, hoisted context gates
             ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
             nat.check(nat.lib().msocr_attn_greedy_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
                                                           ctypes.byref(self._asw), B, T, H, self.V, steps, sos_id, eos_id, blank,
@@ -270,10 +275,9 @@ class AttnDecoder:
                                                    dtype=torch.float32).to(self.device)
                 torch.cuda.synchronize()
             lp = self._lp_cache[key]
-        if not 1 <= beam_size <= 16 or (beam_size * H > 4096 and not (H == 256 and beam_size <= 8)):
+        if not 1 <= beam_size <= 16 or beam_size * H > 4096:
             raise ValueError(f"beam_size {beam_size} with hidden_size {H}: the decoder kernels take beam_size <= 16 and beam_size x hidden_size <= 4096")
-        fast = H == 256 and self.V <= 256 and T <= 48 and beam_size <= 8  # the matrix-core kernel's shapes
-        hoist = HOIST_CTX and fast and os.environ.get("MSOCR_BEAM_MFMA", "1") != "0"
+        hoist = self._matrix_core(T, beam_size)
         if hoist:  # W_ih[:, :H] batch_H_t for every frame, once per call instead of W_ih[:, :H] ctx in every step
             ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
         e = ops._prof_begin()
@@ -281,10 +285,10 @@ class AttnDecoder:
                 -1 if blank_id is None else blank_id, fin.data_ptr(), ws.data_ptr(),
                 chunks[0].data_ptr() if chunks else None, chunks[1].data_ptr() if chunks else None,
                 chunks[2].data_ptr() if chunks else None, ops._stream())
-        if hoist:
-            asw = self._asw if os.environ.get("MSOCR_BEAM_SPLIT", "1") != "0" else None
+        if hoist:  # split-operand products with the split weights, exact-f32 MFMA without them
+            asw = ctypes.byref(self._asw) if self._asw is not None else None
             nat.check(nat.lib().msocr_attn_beam_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
-                                                        ctypes.byref(asw) if asw is not None else None, *tail), "attn_beam_hoisted")
+                                                        asw, *tail), "attn_beam_hoisted")
         else:
             nat.check(nat.lib().msocr_attn_beam(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
         # SURVEY.md 8d, per decode step: proj_H + batch_H (shared by the beams) + LSTMCell W_ih (ctx part + one-hot rows), W_hh,

@@ -1,5 +1,5 @@
-"""The recogniser's sequence kernels against float64, without the CNN: the attention decoders (csrc/attn_beam_mfma.hip, the decode
-half of csrc/trba_kernels.hip, csrc/attn_general.hip), the BiLSTM recurrences (bilstm_kernel<H>, csrc/bilstm_mfma.hip),
+"""The recogniser's sequence kernels against float64, without the CNN: the attention decoders (csrc/attn_beam_mfma.hip,
+csrc/attn_general.hip, behind the entry points of csrc/trba_kernels.hip), the BiLSTM recurrences (bilstm_kernel<H>, csrc/bilstm_mfma.hip),
 se_residual, mean_over_h and seq_confidence, over the envelope DESIGN.md states (hidden 64..512, charsets <= 512 tokens, <= 64
 frames and steps, beam <= 16 with beam x hidden <= 4096).
 
@@ -39,9 +39,9 @@ BH_STD = 1.4  # standard deviation of the encoder output of synth.trba_state_dic
 RNN_SCALE = 4.0
 
 # Bounds of (a) and (b), set from the first MI355X run (every case prints its values with -s):
-#   e_dev <= E_F32_FACTOR * e_f32: measured e_dev / e_f32 0.16 .. 0.95 over the 37-row cases; 1.92 (VALU) and 2.09 (matrix cores) at
-#     B = 1, T = 48, where the maximum is over one row and both errors are a few ulp of max|logit| (6.0e-6 against 2.9e-6 at 13.95,
-#     whose ulp is 9.5e-7).
+#   e_dev <= E_F32_FACTOR * e_f32: measured e_dev / e_f32 0.16 .. 0.95 over the 37-row cases; 1.92 (a VALU kernel since retired) and
+#     2.09 (matrix cores) at B = 1, T = 48, where the maximum is over one row and both errors are a few ulp of max|logit| (6.0e-6
+#     against 2.9e-6 at 13.95, whose ulp is 9.5e-7).
 #   e_dev <= E_REL_MAX * max|logit|: measured 4.0e-7 .. 2.1e-6 (greedy, general kernel, H 320); the issue's ceiling was 1e-4.
 #   decisive rows: measured 89 % .. 100 % per case at DECISIVE_FACTOR = 20.
 E_F32_FACTOR = 4.0
@@ -72,11 +72,21 @@ def _sd(V, H, conf=False):
     return _SD[(V, H, conf)]
 
 
-def _decoder(V, H, conf=False):
+def _decoder(V, H, conf=False, exact=False):
+    """exact: without the split form of the per-step matrices (precision "fp32-exact"): the matrix-core beam kernel on exact-f32 MFMA."""
     from manuscript_ocr_amd.recognizers._trba.net import AttnDecoder
-    if (V, H, conf) not in _DEC:
-        _DEC[(V, H, conf)] = AttnDecoder(_sd(V, H, conf), V, H)
-    return _DEC[(V, H, conf)]
+    if (V, H, conf, exact) not in _DEC:
+        _DEC[(V, H, conf, exact)] = AttnDecoder(_sd(V, H, conf), V, H, step_split=False if exact else None)
+    return _DEC[(V, H, conf, exact)]
+
+
+def _kernel(monkeypatch, V, H, kernel, conf=False):
+    """The decoder for a case's kernel choice: "auto" (what the routing picks for the shape), "exact" (the same without the split
+    weights) or "valu" (the general kernel, csrc/attn_general.hip — the VALU decoder — even where the matrix-core kernels would take
+    the shape: net.HOIST_CTX = False)."""
+    from manuscript_ocr_amd.recognizers._trba import net
+    monkeypatch.setattr(net, "HOIST_CTX", kernel != "valu")
+    return _decoder(V, H, conf, exact=kernel == "exact")
 
 
 def _oracle(V, H, blank, where, conf=False):
@@ -146,24 +156,22 @@ def _check_arith(what, e_dev, e_f32, scale):
 
 # ------------------------------------------------------------------------------------------------ (a) + (b) greedy
 GREEDY_CASES = [
-    # (id, H, V, B, T, steps, env); env: MSOCR_GREEDY_MFMA
-    ("mfma-H256-V194", 256, 194, B_DEF, T_DEF, STEPS_G, {}),
-    ("valu-H256-V194", 256, 194, B_DEF, T_DEF, STEPS_G, {"MSOCR_GREEDY_MFMA": "0"}),
-    ("mfma-V256-T48-B1", 256, 256, 1, 48, STEPS_G, {}),
-    ("valu-V256-T48-B1", 256, 256, 1, 48, STEPS_G, {"MSOCR_GREEDY_MFMA": "0"}),
-    ("mfma-V256-T48-B70", 256, 256, 70, 48, STEPS_G, {}),
-    ("valu-V256-T48-B70", 256, 256, 70, 48, STEPS_G, {"MSOCR_GREEDY_MFMA": "0"}),
-] + [(f"general-H{h}", h, 194, B_DEF, T_DEF, STEPS_G, {}) for h in (64, 128, 192, 320, 384, 448, 512)] + [
-    ("general-V257", 256, 257, B_DEF, T_DEF, STEPS_G, {}),
-    ("general-T49", 256, 194, B_DEF, 49, STEPS_G, {}),
-    ("general-H128-V512-T64-S64", 128, 512, B_DEF, 64, 64, {}),
+    # (id, H, V, B, T, steps, kernel): see _kernel
+    ("mfma-H256-V194", 256, 194, B_DEF, T_DEF, STEPS_G, "auto"),
+    ("valu-H256-V194", 256, 194, B_DEF, T_DEF, STEPS_G, "valu"),
+    ("mfma-V256-T48-B1", 256, 256, 1, 48, STEPS_G, "auto"),
+    ("valu-V256-T48-B1", 256, 256, 1, 48, STEPS_G, "valu"),
+    ("mfma-V256-T48-B70", 256, 256, 70, 48, STEPS_G, "auto"),
+    ("valu-V256-T48-B70", 256, 256, 70, 48, STEPS_G, "valu"),
+] + [(f"general-H{h}", h, 194, B_DEF, T_DEF, STEPS_G, "auto") for h in (64, 128, 192, 320, 384, 448, 512)] + [
+    ("general-V257", 256, 257, B_DEF, T_DEF, STEPS_G, "auto"),
+    ("general-T49", 256, 194, B_DEF, 49, STEPS_G, "auto"),
+    ("general-H128-V512-T64-S64", 128, 512, B_DEF, 64, 64, "auto"),
 ]
 
 
-def _greedy_case(monkeypatch, what, H, V, B, T, steps, env, blank):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    dec = _decoder(V, H)
+def _greedy_case(monkeypatch, what, H, V, B, T, steps, kernel, blank):
+    dec = _kernel(monkeypatch, V, H, kernel)
     bH, pH = _inputs(B, T, H, V)
     lg, ids = dec.greedy(bH, pH, steps - 1, SOS, EOS, blank)
     torch.cuda.synchronize()
@@ -189,36 +197,30 @@ def _greedy_case(monkeypatch, what, H, V, B, T, steps, env, blank):
     assert (gap <= 2 * e_dev).all(), (what, np.argwhere(gap > 2 * e_dev)[:8].tolist())
 
 
-@pytest.mark.parametrize("what,H,V,B,T,steps,env", GREEDY_CASES, ids=[c[0] for c in GREEDY_CASES])
-def test_greedy_decode_against_f64_replay(cuda, monkeypatch, what, H, V, B, T, steps, env):
-    _greedy_case(monkeypatch, what, H, V, B, T, steps, env, None)
+@pytest.mark.parametrize("what,H,V,B,T,steps,kernel", GREEDY_CASES, ids=[c[0] for c in GREEDY_CASES])
+def test_greedy_decode_against_f64_replay(cuda, monkeypatch, what, H, V, B, T, steps, kernel):
+    _greedy_case(monkeypatch, what, H, V, B, T, steps, kernel, None)
 
 
 # ------------------------------------------------------------------------------------------------ (a) + (b) beam
 BEAM_CASES = [
-    # (id, H, V, K, T, steps, env, hoist)
-    ("mfma-split-hoisted", 256, 194, 8, T_DEF, STEPS_B, {}, True),
-    ("mfma-exact-hoisted", 256, 194, 8, T_DEF, STEPS_B, {"MSOCR_BEAM_SPLIT": "0"}, True),
-    ("mfma-not-hoisted", 256, 194, 8, T_DEF, STEPS_B, {}, False),
-    ("valu", 256, 194, 8, T_DEF, STEPS_B, {"MSOCR_BEAM_MFMA": "0"}, True),
-    ("valu-hb2", 256, 194, 8, T_DEF, STEPS_B, {"MSOCR_BEAM_MFMA": "0", "MSOCR_BEAM_HB": "2"}, True),
-] + [(f"mfma-K{k}", 256, 194, k, T_DEF, STEPS_B, {}, True) for k in (1, 2, 3, 5)] + [
-    (f"general-K{k}", 256, 194, k, T_DEF, STEPS_B, {}, True) for k in (9, 12, 16)] + [
-    ("general-H64-K16", 64, 194, 16, T_DEF, STEPS_B, {}, True),
-    ("general-H320-K12", 320, 194, 12, T_DEF, STEPS_B, {}, True),
-    ("general-H448-K9", 448, 194, 9, T_DEF, STEPS_B, {}, True),
-    ("general-H512-K8", 512, 194, 8, T_DEF, STEPS_B, {}, True),
-    ("general-V512-K16-T64-S64-planted", 256, 512, 16, 64, 64, {}, True),  # random decoder: 0/37 decisive rows (16 of 8192 candidates)
+    # (id, H, V, K, T, steps, kernel): see _kernel
+    ("mfma-split-hoisted", 256, 194, 8, T_DEF, STEPS_B, "auto"),
+    ("mfma-exact-hoisted", 256, 194, 8, T_DEF, STEPS_B, "exact"),
+    ("valu", 256, 194, 8, T_DEF, STEPS_B, "valu"),
+] + [(f"mfma-K{k}", 256, 194, k, T_DEF, STEPS_B, "auto") for k in (1, 2, 3, 5)] + [
+    (f"general-K{k}", 256, 194, k, T_DEF, STEPS_B, "auto") for k in (9, 12, 16)] + [
+    ("general-H64-K16", 64, 194, 16, T_DEF, STEPS_B, "auto"),
+    ("general-H320-K12", 320, 194, 12, T_DEF, STEPS_B, "auto"),
+    ("general-H448-K9", 448, 194, 9, T_DEF, STEPS_B, "auto"),
+    ("general-H512-K8", 512, 194, 8, T_DEF, STEPS_B, "auto"),
+    ("general-V512-K16-T64-S64-planted", 256, 512, 16, 64, 64, "auto"),  # random decoder: 0/37 decisive rows (16 of 8192 candidates)
 ]
 
 
-def _beam_case(monkeypatch, what, H, V, K, T, steps, env, hoist, blank, alpha=ALPHA, tau=TAU):
-    from manuscript_ocr_amd.recognizers._trba import net
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    monkeypatch.setattr(net, "HOIST_CTX", hoist)
+def _beam_case(monkeypatch, what, H, V, K, T, steps, kernel, blank, alpha=ALPHA, tau=TAU):
     B, conf = B_DEF, what.endswith("planted")
-    dec = _decoder(V, H, conf)
+    dec = _kernel(monkeypatch, V, H, kernel, conf)
     bH, pH = _inputs(B, T, H, V, conf)
     ws, fin, _ = dec.beam(bH, pH, steps, K, alpha, tau, SOS, EOS, blank)
     lg, ids = dec.beam_finalize(ws, B, steps, K, fin)  # every row its own chunk: t_run = its finish step
@@ -264,57 +266,49 @@ def _beam_case(monkeypatch, what, H, V, K, T, steps, env, hoist, blank, alpha=AL
     assert frac >= DECISIVE_MIN_FRACTION, f"degenerate fixture: {decisive}/{B} decisive rows ({what})"
 
 
-@pytest.mark.parametrize("what,H,V,K,T,steps,env,hoist", BEAM_CASES, ids=[c[0] for c in BEAM_CASES])
-def test_beam_decode_against_f64_replay_and_oracle(cuda, monkeypatch, what, H, V, K, T, steps, env, hoist):
-    _beam_case(monkeypatch, what, H, V, K, T, steps, env, hoist, None)
-
-
-VALU_ENV = {"greedy": {"MSOCR_GREEDY_MFMA": "0"}, "beam": {"MSOCR_BEAM_MFMA": "0"}}
+@pytest.mark.parametrize("what,H,V,K,T,steps,kernel", BEAM_CASES, ids=[c[0] for c in BEAM_CASES])
+def test_beam_decode_against_f64_replay_and_oracle(cuda, monkeypatch, what, H, V, K, T, steps, kernel):
+    _beam_case(monkeypatch, what, H, V, K, T, steps, kernel, None)
 
 
 @pytest.mark.parametrize("mode,what", [("greedy", "mfma"), ("greedy", "valu"), ("greedy", "general-H128"), ("beam", "mfma-K8"),
                                        ("beam", "valu-K8"), ("beam", "general-K12")])
 def test_blank_id_is_masked(cuda, monkeypatch, mode, what):
     """blank_id = 3 (the reference sets one whenever the charset has <BLANK>): its logit is exactly -1e4 (/ tau), it is never emitted,
-    and every other column still meets the f64 bounds.  All three kernel families mask it (attn_general.hip, attn_beam_mfma.hip and
-    attention_cell_step in trba_kernels.hip)."""
+    and every other column still meets the f64 bounds.  Both kernel families mask it (attn_general.hip, attn_beam_mfma.hip)."""
     H = 128 if "H128" in what else 256
-    env = VALU_ENV[mode] if what.startswith("valu") else {}
+    kernel = "valu" if what.startswith("valu") else "auto"
     if mode == "greedy":
-        _greedy_case(monkeypatch, f"{what} blank 3", H, 194, B_DEF, T_DEF, STEPS_G, env, 3)
+        _greedy_case(monkeypatch, f"{what} blank 3", H, 194, B_DEF, T_DEF, STEPS_G, kernel, 3)
     else:
-        _beam_case(monkeypatch, f"{what} blank 3", 256, 194, 12 if "K12" in what else 8, T_DEF, STEPS_B, env, True, 3)
+        _beam_case(monkeypatch, f"{what} blank 3", 256, 194, 12 if "K12" in what else 8, T_DEF, STEPS_B, kernel, 3)
 
 
 @pytest.mark.parametrize("K", [8, 12])
 def test_beam_without_length_penalty_or_temperature(cuda, monkeypatch, K):
     """alpha = 0 (no length penalty: lp_dev = NULL) and temperature = 1 (no division) on the matrix-core (K 8) and general (K 12) kernels."""
-    _beam_case(monkeypatch, f"K{K} alpha 0 tau 1", 256, 194, K, T_DEF, STEPS_B, {}, True, None, alpha=0.0, tau=1.0)
+    _beam_case(monkeypatch, f"K{K} alpha 0 tau 1", 256, 194, K, T_DEF, STEPS_B, "auto", None, alpha=0.0, tau=1.0)
 
 
 # ------------------------------------------------------------------------------------------------ (c) batch composition
 COMPOSITION_CASES = [
-    ("greedy-mfma", "greedy", 256, 194, 8, {}),
-    ("greedy-valu", "greedy", 256, 194, 8, {"MSOCR_GREEDY_MFMA": "0"}),
-    ("greedy-general", "greedy", 128, 194, 8, {}),
-    ("beam-mfma", "beam", 256, 194, 8, {}),
-    ("beam-valu", "beam", 256, 194, 8, {"MSOCR_BEAM_MFMA": "0"}),
-    ("beam-valu-hb2", "beam", 256, 194, 8, {"MSOCR_BEAM_MFMA": "0", "MSOCR_BEAM_HB": "2"}),
-    ("beam-general", "beam", 256, 194, 12, {}),
+    ("greedy-mfma", "greedy", 256, 194, 8, "auto"),
+    ("greedy-valu", "greedy", 256, 194, 8, "valu"),
+    ("greedy-general", "greedy", 128, 194, 8, "auto"),
+    ("beam-mfma", "beam", 256, 194, 8, "auto"),
+    ("beam-valu", "beam", 256, 194, 8, "valu"),
+    ("beam-general", "beam", 256, 194, 12, "auto"),
 ]
 
 
-@pytest.mark.parametrize("what,mode,H,V,K,env", COMPOSITION_CASES, ids=[c[0] for c in COMPOSITION_CASES])
-def test_decode_does_not_depend_on_batch_composition(cuda, monkeypatch, what, mode, H, V, K, env):
+@pytest.mark.parametrize("what,mode,H,V,K,kernel", COMPOSITION_CASES, ids=[c[0] for c in COMPOSITION_CASES])
+def test_decode_does_not_depend_on_batch_composition(cuda, monkeypatch, what, mode, H, V, K, kernel):
     """70 rows decoded as one batch, each row alone, and in a permuted order: every row's ids, logits (and finish step) bit-identical.
     The context gates are computed once for the 70 rows and every run gets its rows' slice (the GEMM producing them may pick another
     kernel for another row count; only the decode kernels are held to bit-equality).  Catches cross-row interference in the 32-row
-    greedy and 4-row beam matrix-core workgroups and in the two-rows-per-workgroup VALU kernel (a row alone runs that case's one-row
-    kernel: MSOCR_BEAM_HB=2 needs two rows, and both kernels give the row the same arithmetic)."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    greedy and 4-row beam matrix-core workgroups."""
     B, T = 70, T_DEF
-    dec = _decoder(V, H)
+    dec = _kernel(monkeypatch, V, H, kernel)
     bH, pH = _inputs(B, T, H, V)
     cg = dec.ctx_gates(bH).view(B, -1) if H == 256 else None  # the general kernels take none
 

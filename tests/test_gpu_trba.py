@@ -31,6 +31,13 @@ def _oracle_net(otm, seed):
     return net.eval()
 
 
+def _force_general_decoder(monkeypatch):
+    """Every decode on the general kernel (csrc/attn_general.hip, the VALU decoder), also where the matrix-core kernels take the
+    shape: the device-side cross-check of the matrix-core kernels."""
+    from manuscript_ocr_amd.recognizers._trba import net
+    monkeypatch.setattr(net, "HOIST_CTX", False)
+
+
 def _x_from_canvases(c):
     return torch.from_numpy(((c.astype(np.float32) - 127.5) * np.float32(1 / 127.5)).transpose(0, 3, 1, 2).copy())
 
@@ -331,7 +338,7 @@ def test_trba_shipped_config_32x128_maxlen40(env, mode):
 def test_trba_random_weights_three_way(env, monkeypatch):
     """The same 96 all-random-weight crops (three reference chunks; 256 in rounds 1-3 — the driver's GPU tier allows the whole suite
     900 s and each variant re-runs the CPU oracle's calibration) through (a) the default path (Winograd 3x3 layers, matrix-core beam kernel),
-    (b) direct convolutions only (MSOCR_WINOGRAD_MIN_CIN=0), (c) the VALU beam kernel (MSOCR_BEAM_MFMA=0): each against the
+    (b) direct convolutions only (MSOCR_WINOGRAD_MIN_CIN=0), (c) the general beam kernel (csrc/attn_general.hip): each against the
     oracle under the near-tie rule, and pairwise: rows that are identical to the oracle in two variants are identical to
     each other, so the variants can only differ on the oracle's near-tie rows."""
     from conftest import compare_decodes
@@ -343,9 +350,9 @@ def test_trba_random_weights_three_way(env, monkeypatch):
     results = {}
     rec_w = TRBA(state_dict=sd, config=cfg, device="cuda")
     results["winograd+mfma-beam"] = _random_weight_case(otm, RANDOM_WEIGHT_SEED, N, "beam", rec_w)
-    monkeypatch.setenv("MSOCR_BEAM_MFMA", "0")
-    results["winograd+valu-beam"] = _random_weight_case(otm, RANDOM_WEIGHT_SEED, N, "beam", rec_w)
-    monkeypatch.delenv("MSOCR_BEAM_MFMA")
+    with monkeypatch.context() as m:
+        _force_general_decoder(m)
+        results["winograd+general-beam"] = _random_weight_case(otm, RANDOM_WEIGHT_SEED, N, "beam", rec_w)
     monkeypatch.setattr(ops, "WINOGRAD_MIN_CIN", 0)
     rec_d = TRBA(state_dict=sd, config=cfg, device="cuda")
     assert not any(hasattr(w, "_msocr_wino") for w, _ in rec_d.model.P.values())
@@ -388,7 +395,7 @@ def test_trba_bf16_cnn_close(env):
 
 def test_greedy_matrix_core_kernel_matches_the_valu_kernel_and_the_oracle(env, monkeypatch):
     """mode="greedy" on the matrix cores (attn_greedy_mfma_kernel, 32 crops per workgroup, the default since round 4) against the
-    round-1 VALU kernel (MSOCR_GREEDY_MFMA=0) and against the oracle's greedy decode of the DEVICE's encoder output: 70 crops (two
+    VALU general kernel (csrc/attn_general.hip) and against the oracle's greedy decode of the DEVICE's encoder output: 70 crops (two
     full row blocks + a partial one), planted decoder — ids identical at every one of the 26 steps (the rows run on after their EOS,
     as model.py:254 does), logits within 1e-3 of the largest logit."""
     from manuscript_ocr_amd import synth
@@ -400,9 +407,9 @@ def test_greedy_matrix_core_kernel_matches_the_valu_kernel_and_the_oracle(env, m
     cd = torch.from_numpy(synth.synth_crops(21, B, 32, 100)).cuda()
     batch_H, proj_H = net.encode(cd)
     lg_m, ids_m = net.greedy(batch_H, proj_H, max_len, 1, 2, None)
-    monkeypatch.setenv("MSOCR_GREEDY_MFMA", "0")
-    lg_v, ids_v = net.greedy(batch_H, proj_H, max_len, 1, 2, None)
-    monkeypatch.delenv("MSOCR_GREEDY_MFMA")
+    with monkeypatch.context() as m:
+        _force_general_decoder(m)
+        lg_v, ids_v = net.greedy(batch_H, proj_H, max_len, 1, 2, None)
     lg_m, ids_m, lg_v, ids_v = lg_m.cpu().numpy(), ids_m.cpu().numpy(), lg_v.cpu().numpy(), ids_v.cpu().numpy()
     assert ids_m.shape == (B, max_len + 1) and np.array_equal(ids_m, ids_v)
     assert np.abs(lg_m - lg_v).max() < 1e-3 * np.abs(lg_v).max()
@@ -417,7 +424,7 @@ def test_greedy_matrix_core_kernel_matches_the_valu_kernel_and_the_oracle(env, m
 
 
 def test_beam_kernels_agree_and_early_exit_changes_nothing(env, monkeypatch):
-    """Matrix-core beam kernel (default) vs the VALU kernel (MSOCR_BEAM_MFMA=0): same ids / finish steps, logits within 1e-3 of
+    """Matrix-core beam kernel (default) vs the general kernel (csrc/attn_general.hip): same ids / finish steps, logits within 1e-3 of
     the largest logit; and the chunk-level early exit (rows grouped like the reference's batch_size chunks) leaves every
     output the finalize step reads (t < chunk run length) bit-identical to the run over all steps."""
     from manuscript_ocr_amd import synth
@@ -443,10 +450,10 @@ def test_beam_kernels_agree_and_early_exit_changes_nothing(env, monkeypatch):
     ws_m, fin_m = run()
     trun, lg_m, ids_m = finalize(ws_m, fin_m, sizes)
     assert trun.max() < steps, "fixture must finish early for the early-exit check to mean anything"
-    # (1) VALU kernel
-    monkeypatch.setenv("MSOCR_BEAM_MFMA", "0")
-    ws_v, fin_v = run()
-    monkeypatch.delenv("MSOCR_BEAM_MFMA")
+    # (1) general kernel
+    with monkeypatch.context() as m:
+        _force_general_decoder(m)
+        ws_v, fin_v = run()
     _, lg_v, ids_v = finalize(ws_v, fin_v, sizes)
     assert np.array_equal(fin_m, fin_v) and np.array_equal(ids_m, ids_v)
     for b in range(B):
@@ -465,35 +472,37 @@ def test_beam_kernels_agree_and_early_exit_changes_nothing(env, monkeypatch):
         assert np.array_equal(lg_e[b, :trun[b]], lg_m[b, :trun[b]])
 
 
-def test_split_operand_beam_kernel_matches_the_exact_one_on_every_beam(env, monkeypatch):
+def test_split_operand_beam_kernel_matches_the_exact_one_on_every_beam(env):
     """Guard for the split-operand form of the matrix-core beam kernel (three bf16 terms per f32 operand, csrc/attn_beam_mfma.hip):
     EVERY beam's logits of the first two steps — not only the best path the finalize step returns — against the exact-f32 MFMA form
-    (MSOCR_BEAM_SPLIT=0) on 1920 crops, three launches.  Steps 0 and 1 come before any near-tie can reorder beams, so the bound is
-    tight: 2e-5 of the largest logit (measured 3e-6).  A packed-f32 code shape in the hoisted context sum once produced wrong gate
-    pre-activations in ~0.5 % of the rows of one crop slot (see the note at add_np / fmac_np); this comparison is what shows it."""
+    (a decoder built from the same weights without the split ones, as precision "fp32-exact" builds it) on 1920 crops, three
+    launches.  Steps 0 and 1 come before any near-tie can reorder beams, so the bound is tight: 2e-5 of the largest logit (measured
+    3e-6).  A packed-f32 code shape in the hoisted context sum once produced wrong gate pre-activations in ~0.5 % of the rows of one
+    crop slot (see the note at add_np / fmac_np); this comparison is what shows it."""
     from manuscript_ocr_amd import synth
-    from manuscript_ocr_amd.recognizers._trba.net import TrbaNet
+    from manuscript_ocr_amd.recognizers._trba.net import AttnDecoder, TrbaNet
     B, V, S, K = 1920, 194, 4, 8
-    net = TrbaNet(synth.trba_state_dict(V, 256, seed=1), V, 256, torch.float32)
+    sd = synth.trba_state_dict(V, 256, seed=1)
+    net = TrbaNet(sd, V, 256, torch.float32)
     assert net._asw is not None, "precision fp32 must carry the split decoder weights"
+    exact = AttnDecoder(sd, V, 256, step_split=False)
+    assert exact._asw is None
     g = torch.Generator(device="cpu").manual_seed(0)
     bH = torch.randn(B, 13, 256, generator=g).cuda()
     pH = torch.randn(B, 13, 256, generator=g).cuda()
 
-    def run():
-        ws, _, _ = net.beam(bH, pH, S, K, 0.9, 1.7, 1, 2, None)
+    def run(dec):
+        ws, _, _ = dec.beam(bH, pH, S, K, 0.9, 1.7, 1, 2, None)
         torch.cuda.synchronize()
         n = B * S * K * V
         lg = ws[: 4 * n].view(torch.float32).view(B, S, K, V).clone()
         bt = ws[4 * n: 4 * n + 8 * B * S * K].view(torch.int32).view(2, B, S, K).clone()
         return lg, bt
 
-    monkeypatch.setenv("MSOCR_BEAM_SPLIT", "0")
-    ref_lg, ref_bt = run()
-    monkeypatch.setenv("MSOCR_BEAM_SPLIT", "1")
+    ref_lg, ref_bt = run(exact)
     scale = float(ref_lg[:, :2].abs().max())
     for rep in range(3):
-        lg, bt = run()
+        lg, bt = run(net)
         assert torch.equal(bt[:, :, 0], ref_bt[:, :, 0]), "step-0 back-pointers / tokens differ"
         d = (lg[:, :2] - ref_lg[:, :2]).abs().amax(dim=-1)      # [B][2][K]
         bad = (d > 2e-5 * scale).nonzero().tolist()
@@ -519,7 +528,7 @@ def test_small_device_batches_give_the_same_results(env):
 
 def test_random_span_layouts_match_the_full_length_decode(env, monkeypatch):
     """Randomised page layouts (spans of 1..90 crops, so chunks of 1..32 rows, ragged workgroups, launches of <= 64 rows):
-    ids, run lengths and confidences with the chunk-level early exit == the VALU kernel running all steps."""
+    ids, run lengths and confidences with the chunk-level early exit == the general kernel running all steps."""
     from manuscript_ocr_amd import synth
     from manuscript_ocr_amd.recognizers import TRBA
     sd = synth.trba_state_dict_confident(194, 256, seed=13)
@@ -534,9 +543,9 @@ def test_random_span_layouts_match_the_full_length_decode(env, monkeypatch):
             o += c
         canv = torch.from_numpy(synth.synth_crops(1000 + trial, N, 32, 100)).cuda()
         ids_a, trun_a, conf_a = rec.recognize_canvases(canv, spans=spans)
-        monkeypatch.setenv("MSOCR_BEAM_MFMA", "0")
-        ids_b, trun_b, conf_b = rec.recognize_canvases(canv, spans=spans)
-        monkeypatch.delenv("MSOCR_BEAM_MFMA")
+        with monkeypatch.context() as m:
+            _force_general_decoder(m)
+            ids_b, trun_b, conf_b = rec.recognize_canvases(canv, spans=spans)
         assert np.array_equal(trun_a, trun_b), (counts, trun_a, trun_b)
         assert np.array_equal(ids_a, ids_b), counts
         np.testing.assert_allclose(conf_a, conf_b, rtol=0, atol=1e-5)

@@ -15,7 +15,7 @@ for B in (960, 2048):
         e0.record()
         for _ in range(3): fn()
         e1.record(); torch.cuda.synchronize()
-        print(f"B={B} {name}: {e0.elapsed_time(e1)/3:.3f} ms  NB={os.environ.get('MSOCR_BEAM_NB','auto')}")
+        print(f"B={B} {name}: {e0.elapsed_time(e1)/3:.3f} ms")
 
 # BiLSTM recurrence
 from manuscript_ocr_amd import ops

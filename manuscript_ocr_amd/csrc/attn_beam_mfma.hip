@@ -824,13 +824,9 @@ int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates) return MSOCR_E_ARG;
   const size_t ldsz = (size_t)(R * XS + R * H + R * 64) * sizeof(float);
   const size_t ldsz_split = (size_t)3 * PPL + (size_t)(R * H + R * 64) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_beam_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz_split) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
+  if (msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<false>, (int)ldsz) != MSOCR_OK ||
+      msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<true>, (int)ldsz_split) != MSOCR_OK)
+    return MSOCR_E_LAUNCH;
   const dim3 grid((a.B + NB - 1) / NB);
   if (a.h2h_p)
     MSOCR_LAUNCH((attn_beam_mfma_kernel<true>), grid, dim3(NT), ldsz_split, s, a);
@@ -842,12 +838,7 @@ int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
 int msocr_internal_attn_greedy_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p) return MSOCR_E_ARG;
   const size_t ldsz_split = (size_t)3 * PPL + (size_t)(R * H + R * 64) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)attn_greedy_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz_split) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
+  if (msocr_internal_lds_limit((const void*)attn_greedy_mfma_kernel, (int)ldsz_split) != MSOCR_OK) return MSOCR_E_LAUNCH;
   MSOCR_LAUNCH(attn_greedy_mfma_kernel, dim3((a.B + R - 1) / R), dim3(NT), ldsz_split, s, a);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }

@@ -266,13 +266,8 @@ int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t
   const size_t ldsz = (size_t)(4 * K * H + K * a.V + K * 64) * sizeof(float);
   auto kb = attn_general_kernel<true>;
   auto kg = attn_general_kernel<false>;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)kg, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
+  if (msocr_internal_lds_limit((const void*)kb, 112 * 1024) != MSOCR_OK || msocr_internal_lds_limit((const void*)kg, 112 * 1024) != MSOCR_OK)
+    return MSOCR_E_LAUNCH;
   if (ldsz > 112 * 1024) return MSOCR_E_ARG;
   if (beam)
     MSOCR_LAUNCH(kb, dim3(a.B), dim3(NTH), ldsz, s, a, H);

@@ -104,11 +104,7 @@ extern "C" int msocr_bilstm_recurrent_split(const float* xproj, const uint16_t* 
   if (!xproj || !whh_planes || !hcat_out || B <= 0 || T <= 0 || H_ != H || ((uintptr_t)whh_planes & 15)) return MSOCR_E_ARG;
   if ((long)B * T * 2 * G >= (1L << 32)) return MSOCR_E_ARG;  // 32-bit element offsets into xproj (the VALU kernel has no such limit)
   const size_t ldsz = (size_t)3 * PPL;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)bilstm_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess) return MSOCR_E_LAUNCH;
-    attr = true;
-  }
+  if (msocr_internal_lds_limit((const void*)bilstm_split_kernel, (int)ldsz) != MSOCR_OK) return MSOCR_E_LAUNCH;
   MSOCR_LAUNCH(bilstm_split_kernel, dim3((B + R - 1) / R, 2), dim3(NT), ldsz, (hipStream_t)stream, xproj, whh_planes, B, T, hcat_out);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }

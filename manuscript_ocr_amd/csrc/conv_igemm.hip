@@ -310,12 +310,7 @@ static int launch_cfg(ConvParams& p, hipStream_t s) {
   constexpr int EPI = (BM / WM) * 32 * BN * 4;
   constexpr int LDS = STAGES * STAGE > EPI ? STAGES * STAGE : EPI;
   auto kern = conv_igemm_kernel<T, BM, BN, BKB, WM, WN, STAGES, LEAN, MT, WPE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr_set = true;
-  }
+  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(kern), LDS) != MSOCR_OK) return MSOCR_E_LAUNCH;
   const long nblk = (long)p.tilesM * p.tilesN * p.nbatch;
   if (nblk <= 0 || nblk > 0x7fffffffL) return MSOCR_E_ARG;
   MSOCR_LAUNCH(kern, dim3((unsigned)nblk), dim3(256), LDS, s, p);

@@ -268,27 +268,17 @@ int launch_split(ConvParams& p, hipStream_t s) {
   constexpr int EPI = 64 * BN * 4;
   constexpr int LDS = STAGE > EPI ? STAGE : EPI;
   auto kern = conv_split_kernel<BN, WPE, GEN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr_set = true;
-  }
+  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(kern), LDS) != MSOCR_OK) return MSOCR_E_LAUNCH;
   const long nblk = (long)p.tilesM * p.tilesN * p.nbatch;
   if (nblk <= 0 || nblk > 0x7fffffffL) return MSOCR_E_ARG;
   MSOCR_LAUNCH(kern, dim3((unsigned)nblk), dim3(256), LDS, s, p);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
-// Kernel choice.  MSOCR_SPLIT_PP (default 1): shapes the producer / consumer kernel of conv_split_pp.hip has an instance for
-// (Cout % 128 == 0) go there; 0 keeps everything on conv_split_kernel (diagnostics, A/B timing).
+// Kernel choice: shapes the producer / consumer kernel of conv_split_pp.hip has an instance for go there, the others (a residual
+// operand, Cout % 128 != 0) to conv_split_kernel.
 int launch_split_one(ConvParams& p, hipStream_t s, bool general) {
-  static int use_pp = -1;
-  if (use_pp < 0) {
-    const char* e = getenv("MSOCR_SPLIT_PP");
-    use_pp = e ? atoi(e) : 1;
-  }
-  if (use_pp && msocr_internal_split_pp_takes(p)) return msocr_internal_split_pp_launch(p, s, general);
+  if (msocr_internal_split_pp_takes(p)) return msocr_internal_split_pp_launch(p, s, general);
   if (general) return p.Cout % 128 == 0 ? launch_split<128, 3, true>(p, s) : launch_split<64, 3, true>(p, s);
   return p.Cout % 128 == 0 ? launch_split<128, 3, false>(p, s) : launch_split<64, 3, false>(p, s);
 }

@@ -29,7 +29,6 @@
 // Bottleneck.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -74,7 +73,7 @@ __device__ __forceinline__ int swz16(int row) { return (4 - ((row >> 2) & 3)) & 
 // TM x TN = 32-row x 32-column units per consumer wave (2 x 4 or 4 x 2).  GEN as in conv_split_kernel: false = a K-tile is a pointer
 // increment (1x1 / stride 1 / no padding over a dense pixel sequence, batched GEMMs); true = taps / stride / padding.
 template <int TM, int TN, bool GEN>
-__global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p, int prio) {
+__global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
   constexpr int BM = 64 * TM, BN = 64 * TN, BK = 32, ROWB = 64;
   constexpr int A_PLANE = BM * ROWB, B_PLANE = BN * ROWB;
   constexpr int STAGE_B = 3 * (A_PLANE + B_PLANE);
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p, int
   }
 
   // =========================================== CONSUMERS ===========================================
-  if (prio == 1) __builtin_amdgcn_s_setprio(1);
+  __builtin_amdgcn_s_setprio(1);
   const int wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, kg = lane >> 4;
   // fragment address inside a stage: row * 64 + ((chunk ^ swz16(row)) << 4), chunk = lane / 16; rows are r16 + multiples of 16,
@@ -424,28 +423,15 @@ int launch_pp(ConvParams& p, hipStream_t s) {
   p.ktiles = (int)(p.Ktot / 32);
   constexpr int LDS = 2 * 3 * (BM + BN) * 64 + 4 * BN * 4;
   auto kern = conv_split_pp_kernel<TM, TN, GEN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr_set = true;
-  }
+  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(kern), LDS) != MSOCR_OK) return MSOCR_E_LAUNCH;
   const long nblk = (long)p.tilesM * p.tilesN * p.nbatch;
   if (nblk <= 0 || nblk > 0x7fffffffL) return MSOCR_E_ARG;
-  static int n_cu = 0, prio = -1;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MSOCR_E_LAUNCH;
-    n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount & ~7 : 8;
-  }
-  if (prio < 0) {
-    const char* e = getenv("MSOCR_PP_PRIO");
-    prio = e ? atoi(e) : 1;
-  }
+  int n_cu = 0;
+  if (msocr_internal_cu_count(&n_cu) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  n_cu = n_cu > 8 ? n_cu & ~7 : 8;
   long grid = (nblk + 7) & ~7L;
   if (grid > n_cu) grid = n_cu;
-  MSOCR_LAUNCH(kern, dim3((unsigned)grid), dim3(512), LDS, s, p, prio);
+  MSOCR_LAUNCH(kern, dim3((unsigned)grid), dim3(512), LDS, s, p);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 

@@ -8,8 +8,6 @@
 // One workgroup per page; every kernel has a bounded trip count (no spinning).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include "msocr.h"
 
@@ -199,7 +197,6 @@ __device__ __forceinline__ bool d_surely_disjoint(const double* p1, const double
   if (!(ext < 1e12)) return false;                  // inf / NaN coordinates: full path
   return (l1 > r2 + margin) || (l2 > r1 + margin) || (t1 > b2 + margin) || (t2 > b1 + margin);
 }
-__device__ int g_lanms_shortcut = 1;
 
 // ---- register-resident polygon_iou for the common case ------------------------------------------------------------------
 // d_polygon_iou keeps its two clip buffers (2 x 20 vertices, dynamically indexed) in scratch memory, i.e. every vertex of
@@ -311,11 +308,10 @@ __device__ __forceinline__ bool d_polygon_iou_fast(const double* poly1, const do
   *iou = union_area <= 0 ? 0.0 : inter_area / union_area;
   return true;
 }
-__device__ int g_lanms_fastclip = 1;
 __device__ __forceinline__ double d_polygon_iou_q(const double* poly1, const double* poly2) {
-  if (g_lanms_shortcut && d_surely_disjoint(poly1, poly2)) return 0.0;
+  if (d_surely_disjoint(poly1, poly2)) return 0.0;
   double r;
-  if (g_lanms_fastclip && d_polygon_iou_fast(poly1, poly2, &r)) return r;
+  if (d_polygon_iou_fast(poly1, poly2, &r)) return r;
   return d_polygon_iou(poly1, poly2);
 }
 
@@ -353,7 +349,7 @@ template <typename K>
 __device__ __forceinline__ bool key_less(K a, K b) { return a < b || (b != b && a == a); }
 
 // ------------------------------------------------------------------------------------------ LANMS
-// One workgroup (1024 threads) per page.
+// One workgroup (LANMS_PAGE_T = 768 threads) per page.
 //
 // Phase 1 of the reference (lanms.py:174-192) is a sequential scan: each x0-sorted candidate either merges
 // into the LAST merged polygon (weighted mean after vertex-order normalisation) or starts a new one.  It
@@ -377,6 +373,10 @@ __device__ __forceinline__ bool key_less(K a, K b) { return a < b || (b != b && 
 //   order  i32[max_cand], supp i32[max_cand], flag i32[max_cand], sbreak i32[max_cand]
 #define LANMS_T 1024
 #define CARRY_W 11
+// page-kernel threads: 3 waves per SIMD = 168 VGPRs per lane, enough for the register-resident polygon clip (at 1024 threads =
+// 128 VGPRs it spills and the carry fix-up rounds get slower).  Measured on a 13 k-candidate page, phase 1 + score sort: 1024
+// threads with the old scratch-buffer clip 2.6 ms; 1024 / 768 / 512 / 256 threads with the register clip 2.3 / 1.7 / 2.1 / 2.7 ms.
+#define LANMS_PAGE_T 768
 // phase 2 across the chip: pages with at most NMS_BITCAP merged polygons get their "IoU > thr" relation as a bit matrix
 // computed by many workgroups (lanms_iou_bits_kernel) and a single wave then replays the greedy pass on the bits
 #define NMS_BITCAP 8192
@@ -523,16 +523,13 @@ __device__ __forceinline__ bool merge_step(MergeState& st, const float* b, doubl
   return true;
 }
 
-// TT threads per page (workspace carries are laid out for LANMS_T >= TT); REGNMS: keep the in-kernel register NMS loop
-template <int TT, bool REGNMS>
-__global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict__ cand, const int32_t* __restrict__ counts,
-                                                              int max_cand, double thr, float* __restrict__ boxes_out,
-                                                              int32_t* __restrict__ nbox_out, char* __restrict__ ws, long ws_stride, long long* dbg,
-                                                              long bits_off, int bitcap) {
+// LANMS_PAGE_T threads per page (workspace carries are laid out for LANMS_T >= LANMS_PAGE_T)
+__global__ __launch_bounds__(LANMS_PAGE_T) void east_lanms_kernel(const float* __restrict__ cand, const int32_t* __restrict__ counts,
+                                                                  int max_cand, double thr, float* __restrict__ boxes_out,
+                                                                  int32_t* __restrict__ nbox_out, char* __restrict__ ws, long ws_stride,
+                                                                  long bits_off, int bitcap) {
   const int pg = blockIdx.x;
-  const int tid = threadIdx.x, nthr = TT;
-#define DBG_STAMP(k) do { if (dbg && tid == 0) dbg[pg * 8 + (k)] = wall_clock64(); } while (0)
-  DBG_STAMP(0);
+  const int tid = threadIdx.x, nthr = LANMS_PAGE_T;
   const float* cb = cand + (long)pg * max_cand * 9;
   const int n = counts[pg] & 0x7fffffff;
   char* w = ws + (long)pg * ws_stride;
@@ -549,8 +546,8 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
   int32_t* sbreak = flag + max_cand;
   float* ob = boxes_out + (long)pg * max_cand * 9;
   __shared__ int nm_s, nk_s, any_changed;
-  __shared__ int scan_s[TT / 64];
-  __shared__ unsigned char ch_s[TT];
+  __shared__ int scan_s[LANMS_PAGE_T / 64];
+  __shared__ unsigned char ch_s[LANMS_PAGE_T];
 
   int32_t* nm_hdr = reinterpret_cast<int32_t*>(w + bits_off);  // {merged polygons for the bit-matrix path, or -1}
   if (n == 0) {
@@ -566,7 +563,6 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
   }
   __threadfence();
   __syncthreads();
-  DBG_STAMP(1);
   // ---- phase 1: speculative segmented scan -------------------------------------------------------------
   int S = (n + 7) / 8;  // >= 8 candidates per segment
   if (S > nthr) S = nthr;
@@ -593,7 +589,6 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
   }
   if (tid == 0) any_changed = 0;
   __syncthreads();
-  DBG_STAMP(2);
   // B. fixed point of the carries (thread 0's carry is already true: its incoming state IS empty)
   int in_dirty = active && tid > 0;  // my incoming carry has not been consumed yet
   for (int round = 0; round < S; ++round) {
@@ -624,7 +619,6 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
     __syncthreads();
     if (!any) break;
   }
-  DBG_STAMP(3);
   // C. replay the true prefix of every segment, emitting closed polygons into their slots
   if (active) {
     MergeState st = {};
@@ -653,7 +647,6 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
     }
   }
   __syncthreads();
-  DBG_STAMP(4);
   // D. ordered compaction of the flagged slots
   {
     const int per = (n + nthr - 1) / nthr;
@@ -682,91 +675,36 @@ __global__ __launch_bounds__(TT) void east_lanms_kernel(const float* __restrict_
   }
   __syncthreads();
   const int nm = nm_s;
-  DBG_STAMP(5);
   // ---- phase 2: order = argsort(-score) (stable), greedy suppression (lanms.py:133-153)
   block_rank_sort_neg_f64(nm, mscore, order, rs_tile);
-  if (bitcap > 0 && nm <= bitcap) {  // greedy suppression continues in lanms_iou_bits_kernel + lanms_greedy_bits_kernel
+  if (nm <= bitcap) {  // greedy suppression continues in lanms_iou_bits_kernel + lanms_greedy_bits_kernel
     if (tid == 0) nm_hdr[0] = nm;
-    DBG_STAMP(6);
-    if (dbg && tid == 0) dbg[pg * 8 + 7] = ((long long)n << 32) | (unsigned)nm;
     return;
   }
   if (tid == 0) nm_hdr[0] = -1;
   for (int i = tid; i < nm; i += nthr) supp[i] = 0;
   __syncthreads();
-  int nk = 0;  // kept count (every thread tracks it; the owner of a kept polygon writes its row)
-  constexpr int NQ = 4;
-  if (REGNMS && nm <= NQ * TT) {
-    // fast path: sorted position j = tid + q*1024 lives in thread tid's registers (polygon + suppressed flag); per
-    // iteration the owner broadcasts polygon i through LDS (double-buffered: one barrier per iteration).
-    __shared__ double bc_poly[2][8];
-    __shared__ int bc_alive[2];
-    double mp[NQ][8];
-    int ms_idx[NQ];
-    bool sup[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int j = tid + q * TT;
-      sup[q] = true;
-      ms_idx[q] = 0;
-      if (j < nm) {
-        ms_idx[q] = order[j];
-        sup[q] = false;
-        for (int k = 0; k < 8; ++k) mp[q][k] = mpoly[(long)ms_idx[q] * 8 + k];
-      } else {
-        for (int k = 0; k < 8; ++k) mp[q][k] = 0.0;
-      }
+  int nk = 0;  // kept count (every thread tracks it; thread 0 writes the kept polygon's row)
+  for (int i = 0; i < nm; ++i) {
+    const int idx = order[i];
+    if (supp[idx]) continue;  // uniform: written before the barrier that ended an earlier iteration
+    double a[8];
+    for (int k = 0; k < 8; ++k) a[k] = mpoly[(long)idx * 8 + k];
+    if (tid == 0) {
+      float* o = ob + (long)nk * 9;
+      for (int k = 0; k < 8; ++k) o[k] = (float)a[k];
+      o[8] = (float)mscore[idx];
     }
-    for (int i = 0; i < nm; ++i) {
-      const int buf = i & 1, own = i % TT, oq = i / TT;
-      if (tid == own) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-          if (q == oq) {
-            bc_alive[buf] = sup[q] ? 0 : 1;
-            if (!sup[q]) {
-              for (int k = 0; k < 8; ++k) bc_poly[buf][k] = mp[q][k];
-              float* o = ob + (long)nk * 9;
-              for (int k = 0; k < 8; ++k) o[k] = (float)mp[q][k];
-              o[8] = (float)mscore[ms_idx[q]];
-            }
-          }
-      }
-      __syncthreads();
-      if (!bc_alive[buf]) continue;
-      ++nk;
-      double a[8];
-      for (int k = 0; k < 8; ++k) a[k] = bc_poly[buf][k];
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        const int j = tid + q * TT;
-        if (j > i && j < nm && !sup[q] && d_polygon_iou_q(a, mp[q]) > thr) sup[q] = true;
-      }
+    ++nk;
+    for (int j = i + 1 + tid; j < nm; j += nthr) {
+      const int idj = order[j];
+      if (supp[idj]) continue;
+      if (d_polygon_iou_q(a, mpoly + (long)idj * 8) > thr) supp[idj] = 1;
     }
-  } else {
-    for (int i = 0; i < nm; ++i) {
-      const int idx = order[i];
-      if (supp[idx]) continue;  // uniform: written before the barrier that ended an earlier iteration
-      double a[8];
-      for (int k = 0; k < 8; ++k) a[k] = mpoly[(long)idx * 8 + k];
-      if (tid == 0) {
-        float* o = ob + (long)nk * 9;
-        for (int k = 0; k < 8; ++k) o[k] = (float)a[k];
-        o[8] = (float)mscore[idx];
-      }
-      ++nk;
-      for (int j = i + 1 + tid; j < nm; j += nthr) {
-        const int idj = order[j];
-        if (supp[idj]) continue;
-        if (d_polygon_iou_q(a, mpoly + (long)idj * 8) > thr) supp[idj] = 1;
-      }
-      __syncthreads();
-    }
+    __syncthreads();
   }
   if (tid == 0) nk_s = nk;
   if (tid == 0) nbox_out[pg] = nk_s;
-  DBG_STAMP(6);
-  if (dbg && tid == 0) dbg[pg * 8 + 7] = ((long long)n << 32) | (unsigned)nm;
 }
 
 // bit j of bits[i][w] (j = 32w + b > i, sorted positions): polygon_iou(poly_i, poly_j) > thr, the test of lanms.py:147-150 with
@@ -842,22 +780,6 @@ extern "C" int msocr_east_lanms(const float* cand, const int32_t* counts, int N,
   if ((uintptr_t)workspace & 7) return MSOCR_E_ARG;
   const long stride = (lanms_ws_per_page(max_cand) + 63) / 64 * 64;
   {
-    const char* e = getenv("MSOCR_LANMS_SHORTCUT");
-    const int v = (e && e[0] == '0') ? 0 : 1;
-    static int cur = -1;
-    if (v != cur) {
-      if (hipMemcpyToSymbol(HIP_SYMBOL(g_lanms_shortcut), &v, sizeof(int)) != hipSuccess) return MSOCR_E_LAUNCH;
-      cur = v;
-    }
-    const char* f = getenv("MSOCR_LANMS_FASTCLIP");  // 0: always the general (scratch-buffer) polygon clip (diagnostic)
-    const int vf = (f && f[0] == '0') ? 0 : 1;
-    static int curf = -1;
-    if (vf != curf) {
-      if (hipMemcpyToSymbol(HIP_SYMBOL(g_lanms_fastclip), &vf, sizeof(int)) != hipSuccess) return MSOCR_E_LAUNCH;
-      curf = vf;
-    }
-  }
-  {
     // rank accumulator = the `supp` array of the page workspace (order | supp | flag | sbreak, 4 bytes each per candidate)
     const long acc_off = ((long)max_cand * (2 * (64 + 8)) + (long)3 * LANMS_T * CARRY_W * 8) + (long)max_cand * 4;
     const int ichunks = (max_cand + 256 * RS_Q - 1) / (256 * RS_Q), jchunks = (max_cand + RS_TILE - 1) / RS_TILE;
@@ -868,34 +790,12 @@ extern "C" int msocr_east_lanms(const float* cand, const int32_t* counts, int N,
                  stride, acc_off);
     if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
   }
-  long long* dbg = nullptr;
-  const bool want_dbg = getenv("MSOCR_LANMS_DEBUG") != nullptr;  // diagnostic only: synchronises and prints phase times
-  if (want_dbg && hipMalloc(&dbg, sizeof(long long) * 8 * N) != hipSuccess) dbg = nullptr;
-  const int bits_on = getenv("MSOCR_LANMS_BITS") ? atoi(getenv("MSOCR_LANMS_BITS")) : 1;  // 0: greedy pass inside the page kernel (diagnostic)
   const long bits_off = lanms_bits_off(max_cand);
-  const int bitcap = bits_on ? nms_bitcap(max_cand) : 0;
-  // page kernel geometry: 768 threads = 3 waves per SIMD = 168 VGPRs per lane, enough for the register-resident polygon clip
-  // (at 1024 threads = 128 VGPRs it spills and the carry fix-up rounds get slower).  Measured on a 13 k-candidate page, phase 1 +
-  // score sort: 1024 threads with the old scratch-buffer clip 2.6 ms; 1024 / 768 / 512 / 256 threads with the register clip
-  // 2.3 / 1.7 / 2.1 / 2.7 ms.  MSOCR_LANMS_T=1024|1025|768|512|256 selects the others (diagnostics).
-  const int lt = getenv("MSOCR_LANMS_T") ? atoi(getenv("MSOCR_LANMS_T")) : 768;
-  if (lt == 1024)
-    MSOCR_LAUNCH((east_lanms_kernel<1024, true>), dim3(N), dim3(1024), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out,
-                 nbox_out, (char*)workspace, stride, dbg, bits_off, bitcap);
-  else if (lt == 1025)
-    MSOCR_LAUNCH((east_lanms_kernel<1024, false>), dim3(N), dim3(1024), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out,
-                 nbox_out, (char*)workspace, stride, dbg, bits_off, bitcap);
-  else if (lt == 768)
-    MSOCR_LAUNCH((east_lanms_kernel<768, false>), dim3(N), dim3(768), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out,
-                 nbox_out, (char*)workspace, stride, dbg, bits_off, bitcap);
-  else if (lt == 256)
-    MSOCR_LAUNCH((east_lanms_kernel<256, false>), dim3(N), dim3(256), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out,
-                 nbox_out, (char*)workspace, stride, dbg, bits_off, bitcap);
-  else
-    MSOCR_LAUNCH((east_lanms_kernel<512, false>), dim3(N), dim3(512), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out,
-                 nbox_out, (char*)workspace, stride, dbg, bits_off, bitcap);
+  const int bitcap = nms_bitcap(max_cand);
+  MSOCR_LAUNCH(east_lanms_kernel, dim3(N), dim3(LANMS_PAGE_T), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out, nbox_out,
+               (char*)workspace, stride, bits_off, bitcap);
   int rc = LAUNCH_OK();
-  if (rc == MSOCR_OK && bitcap > 0) {
+  if (rc == MSOCR_OK) {
     MSOCR_LAUNCH(lanms_iou_bits_kernel, dim3(256, N), dim3(256), 0, (hipStream_t)stream, (char*)workspace, stride, max_cand, iou_thr, bits_off,
                  bitcap);
     rc = LAUNCH_OK();
@@ -904,19 +804,6 @@ extern "C" int msocr_east_lanms(const float* cand, const int32_t* counts, int N,
                    boxes_out, nbox_out);
       rc = LAUNCH_OK();
     }
-  }
-  if (dbg) {
-    long long* h = (long long*)malloc(sizeof(long long) * 8 * N);
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipMemcpy(h, dbg, sizeof(long long) * 8 * N, hipMemcpyDeviceToHost);
-    for (int p = 0; p < N && p < 2; ++p) {
-      const long long* t = h + p * 8;
-      fprintf(stderr, "[lanms dbg] page %d n=%lld nm=%lld  us: sort %.0f specA %.0f fixB %.0f replayC %.0f compactD %.0f nms %.0f\n", p,
-              t[7] >> 32, t[7] & 0xffffffff, (t[1] - t[0]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0, (t[4] - t[3]) / 100.0,
-              (t[5] - t[4]) / 100.0, (t[6] - t[5]) / 100.0);
-    }
-    free(h);
-    (void)hipFree(dbg);
   }
   return rc;
 }

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "internal.h"
 #include "msocr.h"
 
 #define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
@@ -353,12 +354,7 @@ extern "C" int msocr_east_box_tail(const float* boxes, const int32_t* nbox, int 
   if (!boxes || !nbox || !out || !n_out || !workspace || N <= 0 || max_cand <= 0) return MSOCR_E_ARG;
   const TailParams p = make_params(expand_w, expand_h, scale_x, scale_y, axis_aligned_output, remove_anomalies, sigma, min_count);
   const size_t ldsz = (size_t)TAIL_LDSM * (9 + 1 + 4 + 1 + 1) * 4;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)east_box_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz) != hipSuccess)
-      return MSOCR_E_LAUNCH;
-    attr = true;
-  }
+  if (msocr_internal_lds_limit((const void*)east_box_tail_kernel, (int)ldsz) != MSOCR_OK) return MSOCR_E_LAUNCH;
   MSOCR_LAUNCH(east_box_tail_kernel, dim3(N), dim3(256), ldsz, (hipStream_t)stream, boxes, nbox, max_cand, tail_cap(max_cand), p, out,
                n_out, (uint32_t*)workspace);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;

@@ -3,6 +3,13 @@
 #define MSOCR_INTERNAL_H
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <mutex>
+#include <set>
+#include <utility>
+
+#include "msocr.h"
+
 // conv_igemm.hip: nbatch independent f32 GEMMs of one shape in one launch,
 // C[b][m][n] = sum_k A[b][m][k] * B[b][n][k]  (A [nbatch][M][K], B [nbatch][N][K], C [nbatch][M][N], dense, 16-B aligned).
 __attribute__((visibility("hidden"))) int msocr_internal_gemm_f32_batched(const float* A, const float* B, float* C, long M, int N,
@@ -13,8 +20,40 @@ __attribute__((visibility("hidden"))) int msocr_internal_gemm_f32_batched(const 
 __attribute__((visibility("hidden"))) int msocr_internal_gemm_split_batched(const float* A, const uint16_t* Bplanes, float* C, long M,
                                                                             int N, int K, int nbatch, hipStream_t s);
 
+// Per-device launch state.  hipFuncSetAttribute applies to the current device's copy of a kernel, and grid sizes follow the current
+// device's CU count, so both are cached per device (the first by kernel pointer) behind a mutex: safe to call from several host
+// threads.  Inline, so that every translation unit stands alone and the library still holds one cache of each.  Both return
+// MSOCR_OK or MSOCR_E_LAUNCH.
+// msocr_internal_lds_limit: raise the dynamic-LDS limit of `kernel` to `bytes` on the current device, once per (kernel, device).
+__attribute__((visibility("hidden"))) inline int msocr_internal_lds_limit(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> raised;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return MSOCR_E_LAUNCH;
+  std::lock_guard<std::mutex> lock(mu);
+  if (raised.count({kernel, dev})) return MSOCR_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return MSOCR_E_LAUNCH;
+  raised.insert({kernel, dev});
+  return MSOCR_OK;
+}
+// msocr_internal_cu_count: the current device's CU count.
+__attribute__((visibility("hidden"))) inline int msocr_internal_cu_count(int* n) {
+  static std::mutex mu;
+  static std::map<int, int> cu_count;  // device -> CU count
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return MSOCR_E_LAUNCH;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cu_count.find(dev);
+  if (it == cu_count.end()) {
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return MSOCR_E_LAUNCH;
+    it = cu_count.emplace(dev, cu).first;
+  }
+  *n = it->second;
+  return MSOCR_OK;
+}
+
 // attention decoder arguments shared by trba_kernels.hip (entry points), attn_beam_mfma.hip (matrix-core kernels) and attn_general.hip
-#include "msocr.h"
 struct AttnArgs {
   const float* batch_H;
   const float* proj_H;

@@ -19,11 +19,11 @@
 // test-suite pins it bit for bit against PIL's decode of the same files.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
+#include "internal.h"
 #include "msocr.h"
 
 #define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
@@ -791,19 +791,11 @@ extern "C" int msocr_jpeg_entropy_decode_device(const uint8_t* bytes_dev, const 
   if (hipMemsetAsync(coef_dev, 0, (size_t)coef_total * sizeof(int16_t), s) != hipSuccess) return MSOCR_E_LAUNCH;
   if (hipMemsetAsync(status_dev, 0, (size_t)n_pages * sizeof(int32_t), s) != hipSuccess) return MSOCR_E_LAUNCH;
   // wave slots wanted: two per SIMD of the device; lanes per wave = the power of two that fills them
-  static int slots = 0;
-  static int lanes_env = -1;
-  if (!slots) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MSOCR_E_LAUNCH;
-    slots = prop.multiProcessorCount * 8;
-    const char* e = getenv("MSOCR_JPEG_LANES");
-    lanes_env = e ? atoi(e) : 0;
-  }
+  int n_cu = 0;
+  if (msocr_internal_cu_count(&n_cu) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  const int slots = n_cu * 8;
   int lanes = 1;
   while (lanes < 64 && (int64_t)n_pages * max_intervals > (int64_t)slots * lanes) lanes *= 2;
-  if (lanes_env >= 1 && lanes_env <= 64 && !(lanes_env & (lanes_env - 1))) lanes = lanes_env;
   MSOCR_LAUNCH(jpeg_huffman_kernel, dim3((unsigned)((max_intervals + lanes - 1) / lanes), (unsigned)n_pages), dim3(64), 0, s, bytes_dev,
                static_cast<const ScanDesc*>(descs_dev), bounds_dev, page_base_dev, coef_dev, status_dev, lanes);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;

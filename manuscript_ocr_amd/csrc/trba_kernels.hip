@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "internal.h"
 #include "msocr.h"
@@ -171,15 +170,10 @@ extern "C" int msocr_se_residual(const void* x, const void* identity, int N, int
   // all 1920 crops of a sub-batch are resident at once — 0.8 GB between the two reads of a crop, nothing of it left in L2 / MALL.
   // Measured per 1920 crops: 0.587 / 0.311 / 0.173 ms (16x50x128 / 8x25x256 / 4x13x512) -> 0.541 / 0.249 / 0.151.  The size is the
   // same for every batch size (the order of the mean's additions depends on it, and results must not depend on the batch
-  // composition); MSOCR_SE_NT=256 selects the small workgroups.
-  static const int nt_env = getenv("MSOCR_SE_NT") ? atoi(getenv("MSOCR_SE_NT")) : 0;
-  const int NT = nt_env == 256 ? 256 : 1024;
-  const size_t lds = (size_t)((NT / (C / 4)) * C + 2 * C + C / 16) * sizeof(float);
+  // composition).
   if (dtype == MSOCR_F32) {
-    if (NT == 1024)
-      MSOCR_LAUNCH((se_residual_kernel<float, 1024>), dim3(N), dim3(1024), lds, s, (const float*)x, (const float*)identity, HW, C, w1, w2, gate_ws, (float*)out);
-    else
-      MSOCR_LAUNCH((se_residual_kernel<float, 256>), dim3(N), dim3(256), lds, s, (const float*)x, (const float*)identity, HW, C, w1, w2, gate_ws, (float*)out);
+    MSOCR_LAUNCH((se_residual_kernel<float, 1024>), dim3(N), dim3(1024), (size_t)((1024 / (C / 4)) * C + 2 * C + C / 16) * sizeof(float), s,
+                 (const float*)x, (const float*)identity, HW, C, w1, w2, gate_ws, (float*)out);
   } else if (dtype == MSOCR_BF16) {
     MSOCR_LAUNCH((se_residual_kernel<uint16_t, 256>), dim3(N), dim3(256), (size_t)((1024 / C) * C + 2 * C + C / 16) * sizeof(float), s,
                  (const uint16_t*)x, (const uint16_t*)identity, HW, C, w1, w2, gate_ws, (uint16_t*)out);

@@ -800,10 +800,9 @@ extern "C" int msocr_winograd_fused64_gemm_output(const msocr_conv_desc* d, int 
   const dim3 grid((unsigned)nblk), blk(256);
   hipStream_t st = (hipStream_t)stream;
   const float* ws = (const float*)workspace;
-  // split operands and Cout % 64 == 0: the on-the-fly output transform with 64 x 64 workgroup tiles (MSOCR_WINO_FUSED_V2=0: the
-  // 24-accumulator kernel, kept for Cout % 64 != 0 and as the cross-check of the tests)
-  static const bool v2 = !(getenv("MSOCR_WINO_FUSED_V2") && getenv("MSOCR_WINO_FUSED_V2")[0] == '0');
-  if (split && v2 && d->Cout % 64 == 0) {
+  // split operands and Cout % 64 == 0: the on-the-fly output transform with 64 x 64 workgroup tiles; the 24-accumulator kernel
+  // takes exact operands and split ones with Cout % 64 != 0
+  if (split && d->Cout % 64 == 0) {
     const long nblk2 = ((g.Mt + 63) / 64) * (long)(d->Cout / 64);
     if (nblk2 <= 0 || nblk2 > 0x7fffffffL) return MSOCR_E_ARG;
     const dim3 grid2((unsigned)nblk2);

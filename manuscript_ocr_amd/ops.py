@@ -203,9 +203,9 @@ def attach_winograd(w, split=None, square=True):
         u42 = _wino_weights(w.detach().cpu().contiguous(), nat.WINO_4X2)
         w._msocr_wino42_fused = u42.to(w.device)
         # the K = 64 GEMMs on the bf16 pipes pay only for the wide layer (TRBA conv0b, 64 -> 128 + pool: 2.43 -> 2.21 ms per 960 crops);
-        # with 64 output channels the kernel is bound by staging and barriers either way (0.84 -> 0.86 ms) and stays exact
-        v2 = os.environ.get("MSOCR_WINO_FUSED_V2", "1") != "0"  # wino42_fused64_v2_kernel (Cout % 64 == 0)
-        if (SPLIT_BF16X3 if split is None else split) and ((v2 and Cout % 64 == 0) or Cout >= 128):
+        # with 64 output channels the kernel is bound by staging and barriers either way (0.84 -> 0.86 ms) and stays exact.
+        # Cout % 64 == 0 takes wino42_fused64_v2_kernel, which is split whatever Cout.
+        if (SPLIT_BF16X3 if split is None else split) and (Cout % 64 == 0 or Cout >= 128):
             w._msocr_wino42_fused_split = split_planes(u42).to(w.device)  # [3][24][Cout][64] bf16
         return w
     if not (WINOGRAD_MIN_CIN and w.dtype == torch.float32 and KH == 3 and KW == 3 and Cin >= WINOGRAD_MIN_CIN and Cin % 16 == 0
@@ -521,8 +521,7 @@ def bilstm_recurrent(xproj, whh_t, B, T, H, whh_planes=None):
     assert xproj.is_contiguous() and xproj.numel() == B * T * 8 * H and whh_t.shape == (2, H, H, 4) and whh_t.is_contiguous()
     out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=xproj.device)
     e = _prof_begin()
-    if (whh_planes is not None and H == 256 and SPLIT_BF16X3 and B * T * 8 * H < 2 ** 32
-            and os.environ.get("MSOCR_BILSTM_MFMA", "1") != "0"):
+    if whh_planes is not None and H == 256 and SPLIT_BF16X3 and B * T * 8 * H < 2 ** 32:
         nat.check(nat.lib().msocr_bilstm_recurrent_split(xproj.data_ptr(), whh_planes.data_ptr(), B, T, H, out.data_ptr(), _stream()),
                   "bilstm_recurrent_split")
     else:

@@ -605,8 +605,8 @@ def test_decode_lanms_many_pages_stress(ops):
 
 
 def test_lanms_many_unmerged_polygons_general_nms_path(ops):
-    """> 4096 merged polygons (nothing merges in phase 1): exercises the NMS path that keeps polygons in global
-    memory instead of registers; equals the oracle bit for bit."""
+    """> 4096 merged polygons (nothing merges in phase 1): the IoU bit matrix + single-wave replay with more than two
+    suppression words per lane (the path of every page up to 8192 merged polygons); equals the oracle bit for bit."""
     from oracle import lanms as L
     rng = np.random.default_rng(77)
     n = 4300
@@ -622,13 +622,12 @@ def test_lanms_many_unmerged_polygons_general_nms_path(ops):
     assert np.array_equal(boxes[0, :nb].cpu().numpy().view(np.uint32), exp.view(np.uint32))
 
 
-@pytest.mark.parametrize("n,bits", [(4300, "0"), (1500, "0"), (9000, "1")])
-def test_lanms_nms_path_variants(ops, monkeypatch, n, bits):
-    """The greedy pass of standard_nms has three implementations that must all equal the oracle bit for bit: the chip-wide IoU
-    bit matrix + single-wave replay (default, up to 8192 merged polygons), and — MSOCR_LANMS_BITS=0, or above 8192 — the two
-    in-kernel loops of the page kernel (polygons in registers up to 4096, in memory beyond)."""
+@pytest.mark.parametrize("n", [4300, 1500, 9000])
+def test_lanms_nms_path_variants(ops, n):
+    """The greedy pass of standard_nms has two implementations that must both equal the oracle bit for bit: the chip-wide IoU
+    bit matrix + single-wave replay for pages of up to 8192 merged polygons (n = 1500, 4300), and the page kernel's in-kernel
+    loop over polygons in memory above that (n = 9000)."""
     from oracle import lanms as L
-    monkeypatch.setenv("MSOCR_LANMS_BITS", bits)
     rng = np.random.default_rng(n)
     span = 9000 if n > 5000 else 6000
     cx, cy = rng.uniform(50, span, n), rng.uniform(50, span, n)

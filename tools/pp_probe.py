@@ -1,5 +1,5 @@
 """Split-operand GEMM shapes of the pipeline through ops.conv2d (1x1 lean form) and the batched Winograd form: time, f32-equivalent
-TFLOP/s, error against an f64 product on sampled rows.  Run once per kernel choice (MSOCR_SPLIT_PP=0 / 1); dev tool, GPU only."""
+TFLOP/s, error against an f64 product on sampled rows.  The shape picks the kernel (residual shapes: conv_split_kernel); dev tool, GPU only."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -46,7 +46,6 @@ def run_wino(N, H, W, C):
 
 
 if __name__ == "__main__":
-    print("MSOCR_SPLIT_PP =", os.environ.get("MSOCR_SPLIT_PP", "default"), "MSOCR_PP_PRIO =", os.environ.get("MSOCR_PP_PRIO", "default"))
     for K in (128, 256, 512, 1024, 4096):
         run(24 * 6720, 512, K)
     run(161280, 256, 256)

@@ -1,5 +1,5 @@
 """Does a power-of-two row stride of the activation operand cost the split GEMM? (L2 channel camping probe; dev tool, GPU only)
-A [M][K] f32 with row stride K + pad, both kernels."""
+A [M][K] f32 with row stride K + pad."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,4 +20,4 @@ def run(M, N, K, pad, iters=8):
 
 if __name__ == "__main__":
     for (M, N, K) in [(161280, 512, 512), (161280, 512, 4096), (161280, 256, 256)]:
-        print("PP", os.environ.get("MSOCR_SPLIT_PP", "1"), f"{M}x{N}x{K}:", " ".join(f"pad{pad}: {run(M, N, K, pad):.1f}" for pad in (0, 32, 64, 16, 8)), flush=True)
+        print(f"{M}x{N}x{K}:", " ".join(f"pad{pad}: {run(M, N, K, pad):.1f}" for pad in (0, 32, 64, 16, 8)), flush=True)

@@ -55,7 +55,6 @@ def run_wino(N, H, W, C):
 
 
 if __name__ == "__main__":
-    print("MSOCR_SPLIT_WPE =", os.environ.get("MSOCR_SPLIT_WPE", "3 (default)"))
     for K in (128, 256, 512, 1024, 4096):
         run(24 * 6720, 512, K)
     for K in (64, 128, 256, 512):

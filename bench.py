@@ -11,9 +11,13 @@ ResizeAndPadA -> TRBA SE-ResNet31 + BiLSTM + beam-8 attention decode -> text (wo
 "pipeline", BASELINE configs[3]); "--workload east" stops after the detector (configs[1]).
 Pages shard across ranks with no data-path collective (weak scaling: fixed per-GPU batch); the
 only exchange is the final gather of decoded records (all_gather of a padded u8 buffer over
-RCCL).  Rank 0 prints ONE JSON line: whole-job pages/s, the live HIP-event roofline of the
-dominant kernel (implicit-GEMM convolution on MFMA) and a bounded CPU baseline (the oracle =
-CPU restatement of the reference path, timed on the host cores).
+RCCL).  Rank 0 prints ONE JSON line with the whole-job pages/s.
+
+A plain run does only what that figure needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+`--full` adds everything else, each leg outside the timed region: the rocprofv3 PMC child passes (HBM traffic and MFMA-pipe
+utilisation, before this process touches the GPU), the secondary lines (host pages, hipGraph replay, JPEG ingest), the live
+HIP-event roofline of the dominant kernel (implicit-GEMM convolution on MFMA) with the decode rates, and a bounded CPU baseline
+(the oracle = CPU restatement of the reference path, timed on the host cores, with the text comparison against it).
 """
 import argparse
 import json
@@ -33,7 +37,7 @@ STEP_TIMES = [] if os.environ.get("MSOCR_STEP_TIMES") else None  # diagnostics: 
 TIE_TOL = 5e-3  # first-step logit gap (|logit| ~ 5) treated as a tie between two f32 implementations (tests/conftest.py)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -48,8 +52,12 @@ def parse():
     ap.add_argument("--target-size", type=int, default=0,
                     help="reference-faithful detector geometry: resize every page to T x T on the device (EAST.predict default T=1280, "
                          "infer.py:304) instead of feeding the page at its native size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure: PMC child passes, secondary lines, live roofline, "
+                         "CPU baseline (each can be dropped again with its --no-* option); a plain run makes none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the live roofline (and with it the PMC child passes and the secondary lines)")
     ap.add_argument("--no-overlap-steps", action="store_true", help="do not enqueue step i+1's detector work before collecting step i")
     ap.add_argument("--sub-batches", type=int, default=0, help="sub-batch groups pipelined on separate streams (0 = auto)")
     ap.add_argument("--graphs", action="store_true",
@@ -59,15 +67,32 @@ def parse():
                     help="hand the pages over as HOST arrays every step, as Pipeline.predict()'s callers do (PCIe-inclusive rate, "
                          "DESIGN.md 7); the default keeps the synthetic pages resident in HBM as the bench contract asks")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="skip the three rocprofv3 --pmc child runs that measure roofline.traffic (FETCH_SIZE, WRITE_SIZE) and the MFMA-pipe utilisation for this line")
+                    help="with --full: skip the three rocprofv3 --pmc child runs that measure roofline.traffic (FETCH_SIZE, WRITE_SIZE) and the MFMA-pipe utilisation for this line")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary lines (host pages / hipGraph replay / JPEG ingest, a few steps each after the timed region)")
+                    help="with --full: skip the secondary lines (host pages / hipGraph replay / JPEG ingest, a few steps each after the timed region)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (every rank's words: page, box, "
                          "confidences, text) as DIR/<name>.npy, float64, at most 64 MB (a seeded sample of the words beyond that)")
     ap.add_argument("--serialize-streams", action="store_true",
                     help="run the sub-batch pipeline on ONE stream (no cross-stream kernel overlap): per-kernel profiling mode")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def extra_legs(a, world, rank, under_profiler=False):
+    """The measurements this process makes beyond the headline figure, all outside the timed region: none without --full; with it,
+    what the --no-* options, the rank, the world size and the precision leave."""
+    if not a.full:
+        return set()
+    legs = set()
+    if world == 1 and not (a.no_live_traffic or a.no_roofline or a.serialize_streams or under_profiler) and a.precision != "bf16":
+        legs.add("live_traffic")  # no profiler inside a profiled run
+    if rank == 0 and world == 1 and a.workload == "pipeline" and not (a.no_secondary or a.no_roofline or a.serialize_streams):
+        legs.add("secondary")
+    if rank == 0 and not a.no_roofline:
+        legs.add("roofline")
+    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
 
 
 CONV_STAGE_KERNELS = ("conv_igemm_kernel", "conv_split_kernel", "conv_split_pp_kernel", "wino_input_kernel", "wino_output_kernel", "wino42_input_kernel", "wino42_output_kernel",
@@ -259,8 +284,8 @@ def main():
         # (collect_batch, Page assembly) would fight over the same cores
         torch.set_num_threads(max(1, (os.cpu_count() or world) // world))
     live_traffic, live_note = None, "not requested"
-    under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)  # no profiler inside a profiled run
-    if world == 1 and not (a.no_live_traffic or a.no_roofline or a.serialize_streams or under_profiler) and a.precision != "bf16":
+    legs = extra_legs(a, world, rank, under_profiler=any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ))
+    if "live_traffic" in legs:
         t_pmc = time.time()
         live_traffic, live_note = live_pmc_traffic(a)  # child processes; this process has not touched the GPU yet
         print(f"[bench] live PMC traffic passes: {live_note}, {time.time() - t_pmc:.0f} s", file=sys.stderr)
@@ -468,7 +493,7 @@ def main():
     }
 
     res["max_memory_reserved_gb"] = round(torch.cuda.max_memory_reserved() / 2 ** 30, 2)  # after the timed steps (allocator high-water)
-    if rank == 0 and world == 1 and pipe is not None and not (a.no_secondary or a.no_roofline or a.serialize_streams):
+    if "secondary" in legs:
         # Secondary lines, same process, AFTER the timed region (never part of `value`): the variants BASELINE configs[3] and
         # VERDICT r3 #6 ask about.  Each: 1 untimed + 3 timed steps of the same software-pipelined loop.
         def secondary_rate(k=3):
@@ -533,7 +558,7 @@ def main():
     if pipe is not None:
         res["host_stage_s_last_step"] = {k: round(v, 4) for k, v in pipe.last_profile.items()}
         res["east_stage_s_last_step"] = {k: round(v, 4) for k, v in det.last_profile.items()}
-    if rank == 0 and not a.no_roofline:
+    if "roofline" in legs:
         # Live HIP-event timing of every hot-path launch (events on the launch stream = torch's current stream); records are
         # (start, end, kind, work, tag), see manuscript_ocr_amd/ops.py::PROFILE.
         peak = PEAK_TFLOPS[a.precision]
@@ -735,7 +760,7 @@ def main():
                     fh.write(f"M={tag[0]} N={tag[1]} K={tag[2]} {tag[3]} calls_per_step={cnt / a.steps:g} ms_per_step={m / a.steps:.3f} "
                              f"alg_TF/s={f / (m * 1e-3) / 1e12:.1f} executed_TF/s={fe / (m * 1e-3) / 1e12:.1f}\n")
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         res["cpu_baseline"] = cpu_baseline(a.workload, esd, tsd, pages, scores, geos, H, W, out, target_wh=(TW, TH))
 
     if STEP_TIMES:

@@ -721,6 +721,30 @@ def test_bench_dump_outputs(tmp_path):
     assert sum(os.path.getsize(tmp_path / "s1" / (k + ".npy")) for k in a) <= 100 * row + 8 * 128  # + the .npy headers
 
 
+def test_bench_plain_run_makes_no_extra_measurements():
+    """bench.py without --full measures the headline figure only; --full adds the PMC child passes, the secondary lines, the
+    live roofline and the CPU baseline where they applied before --full existed (1 GPU, f32, pipeline workload), and the
+    --no-* options, N > 1, bf16, the detector-only workload and a profiled run still drop theirs."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    every = {"live_traffic", "secondary", "roofline", "cpu_baseline"}
+    for extra in ([], ["--dump-outputs", "d"], ["--workload", "east"], ["--graphs"], ["--precision", "bf16"]):
+        assert bench.extra_legs(bench.parse(plain + extra), 1, 0) == set(), extra
+    assert bench.extra_legs(bench.parse(plain + ["--full"]), 1, 0) == every
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--dump-outputs", "d"]), 1, 0) == every
+    assert bench.extra_legs(bench.parse(plain + ["--full"]), 1, 0, under_profiler=True) == every - {"live_traffic"}
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--no-roofline"]), 1, 0) == {"cpu_baseline"}
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--no-cpu-baseline", "--no-secondary"]), 1, 0) == {"live_traffic", "roofline"}
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--workload", "east"]), 1, 0) == every - {"secondary"}
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--precision", "bf16"]), 1, 0) == every - {"live_traffic"}
+    assert bench.extra_legs(bench.parse(plain + ["--full", "--serialize-streams"]), 1, 0) == {"roofline", "cpu_baseline"}
+    assert bench.extra_legs(bench.parse(["--gpus", "2", "--full"]), 2, 0) == {"roofline"}
+    assert bench.extra_legs(bench.parse(["--gpus", "2", "--full"]), 2, 1) == set()
+
+
 def test_attn_pack_split_host_layout_and_exactness():
     """msocr_attn_pack_split_host: planes sum to the f32 weight exactly; layout [plane][k/16][column][k%16], columns padded to 32,
     gate-interleaved input reordered gate-major."""

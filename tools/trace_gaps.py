@@ -1,10 +1,10 @@
 """Where the device is idle or runs no convolution kernel: digest of a rocprofv3 --kernel-trace CSV (dev tool, CPU).
 
-    python tools/trace_gaps.py gpurun_out/<run>/<host>/<pid>_kernel_trace.csv [first_step last_step total_steps]
+    python tools/trace_gaps.py profile_runs/<tag>_conc/<host>/<pid>_kernel_trace.csv [first_step last_step total_steps]
 
-Takes the dispatches of steps [first_step, last_step) out of total_steps equally long (in dispatch count) steps — the default
-bench runs 2 priming + 2 warm-up + 5 timed + 6 instrumented + 6 serialized steps = 21, so "4 9 21" is the timed region — merges
-the kernel intervals and prints:
+Takes the dispatches of steps [first_step, last_step) out of total_steps equally long (in dispatch count) steps —
+`bench.py --full --no-secondary` (the trace pass of tools/profile_round.sh) runs 2 priming + 2 warm-up + 5 timed + 6 instrumented
++ 6 serialized steps = 21, so "4 9 21" is the timed region — merges the kernel intervals and prints:
 busy fraction, time with no conv-stage kernel running, and the largest idle gaps with the kernels that end before / start after
 them."""
 import csv

@@ -140,7 +140,8 @@ int msocr_normalize_u8(const uint8_t* src, int N, int H, int W, int pad_t, int p
  * Replaces detectors/_east/infer.py:304 (restated from OpenCV, parity unpinned). */
 int msocr_resize_linear_u8(const uint8_t* src, int N, int sh, int sw, uint8_t* dst, int dh, int dw, void* stream);
 
-/* MaxPool2d(k, stride=s, padding=p) on NHWC.  (torchvision resnet maxpool 3/2/1; seresnet31.py:88 2/2/0) */
+/* MaxPool2d(k, stride=s, padding=p) on NHWC.  (torchvision resnet maxpool 3/2/1; seresnet31.py:88 2/2/0)
+ * As torch: 2p <= k, a NaN in a window gives NaN.  in_ld, out_ld >= C: pixel strides in elements. */
 int msocr_maxpool2d(const void* in, int N, int H, int W, int C, int64_t in_ld, int k, int s, int p, int dtype,
                     void* out, int Ho, int Wo, int64_t out_ld, void* stream);
 
@@ -150,7 +151,8 @@ int msocr_upsample2x_bilinear(const void* in, int N, int H, int W, int C, int64_
                               int64_t out_ld, void* stream);
 
 /* OutputHead (east.py:96-105): score = sigmoid(w_s . x + b_s), geo = W_g x + b_g from the 32-channel h1.
- * w9 = [9][32] f32 (row 0 score, rows 1..8 geo), b9 = [9] f32.  score_out [N][H][W] f32, geo_out [N][H][W][8] f32. */
+ * w9 = [9][32] f32 (row 0 score, rows 1..8 geo), b9 = [9] f32.  score_out [N][H][W] f32, geo_out [N][H][W][8] f32.
+ * h1 is read and geo_out written by 16-byte vectors: h1 and geo_out 16-byte aligned, in_ld a multiple of 4 (f32) / 8 (bf16). */
 int msocr_east_head(const void* h1, int64_t npix, int64_t in_ld, int dtype, const float* w9, const float* b9,
                     float* score_out, float* geo_out, void* stream);
 

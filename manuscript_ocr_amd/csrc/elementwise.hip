@@ -182,7 +182,12 @@ __global__ void maxpool_kernel(const T* __restrict__ in, int N, int H, int W, in
         if ((unsigned)wi >= (unsigned)W) continue;
         const T* q = in + (((long)n * H + hi) * W + wi) * in_ld + c4 * 4;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], ld<T>(q + e));
+        for (int e = 0; e < 4; ++e) {
+          // NaN propagates as in torch's max_pool2d: a NaN held in m stays and a NaN tap sets it (fmaxf alone returns the other
+          // operand); finite and infinite taps take fmaxf
+          const float v = ld<T>(q + e);
+          m[e] = (m[e] != m[e] || v != v) ? m[e] + v : fmaxf(m[e], v);
+        }
       }
     }
     T* o = out + (((long)n * Ho + ho) * Wo + wo) * out_ld + c4 * 4;
@@ -193,8 +198,10 @@ __global__ void maxpool_kernel(const T* __restrict__ in, int N, int H, int W, in
 
 extern "C" int msocr_maxpool2d(const void* in, int N, int H, int W, int C, int64_t in_ld, int k, int s, int p, int dtype,
                                void* out, int Ho, int Wo, int64_t out_ld, void* stream) {
-  if (!in || !out || N <= 0 || C <= 0 || C % 4 || k <= 0 || s <= 0 || Ho <= 0 || Wo <= 0) return MSOCR_E_ARG;
-  if ((Ho - 1) * s - p >= H || (Wo - 1) * s - p >= W) return MSOCR_E_ARG;
+  if (!in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || k <= 0 || s <= 0 || p < 0 || Ho <= 0 || Wo <= 0) return MSOCR_E_ARG;
+  if (in_ld < C || out_ld < C) return MSOCR_E_ARG;
+  // torch's rule 2p <= k: with it and the last window starting inside the map, every window holds at least one pixel (no -inf outputs)
+  if (2 * p > k || (Ho - 1) * s - p >= H || (Wo - 1) * s - p >= W) return MSOCR_E_ARG;
   const long total = (long)N * Ho * Wo * (C / 4);
   hipStream_t st_ = (hipStream_t)stream;
   if (dtype == MSOCR_F32)
@@ -300,6 +307,9 @@ __global__ void east_head_kernel(const T* __restrict__ h1, long npix, long in_ld
 extern "C" int msocr_east_head(const void* h1, int64_t npix, int64_t in_ld, int dtype, const float* w9, const float* b9,
                                float* score_out, float* geo_out, void* stream) {
   if (!h1 || !w9 || !b9 || !score_out || !geo_out || npix <= 0 || in_ld < 32) return MSOCR_E_ARG;
+  // the kernel reads h1 with 16-byte loads (4 f32 / 8 bf16 per load) and writes geo with 16-byte stores
+  const int64_t vec = dtype == MSOCR_BF16 ? 8 : 4;
+  if (in_ld % vec || (uintptr_t)h1 % 16 || (uintptr_t)geo_out % 16) return MSOCR_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == MSOCR_F32)
     MSOCR_LAUNCH(east_head_kernel<float>, dim3(grid_for(npix, 256)), dim3(256), 0, s, (const float*)h1, (long)npix, (long)in_ld, w9, b9,

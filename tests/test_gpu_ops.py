@@ -448,8 +448,12 @@ def test_maxpool_upsample_head(ops, dtype):
     ops.upsample2x_into(xd, cat)
     up = cat[..., :64].float().cpu().permute(0, 3, 1, 2)
     ref = F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
-    tol = 1e-6 if dtype == torch.float32 else 1e-2
-    assert (up - ref).abs().max().item() <= tol * ref.abs().max().item()
+    if dtype == torch.float32:
+        assert (up - ref).abs().max().item() <= 1e-6 * ref.abs().max().item()
+    else:  # one round-to-nearest bf16 store per element (tests/test_gpu_stream_f64.py states the bound; a truncating store reaches 2^-7)
+        ref64 = F.interpolate(x.double(), scale_factor=2, mode="bilinear", align_corners=False)
+        A = F.interpolate(x.double().abs(), scale_factor=2, mode="bilinear", align_corners=False)
+        assert torch.all((up.double() - ref64).abs() <= 2.0 ** -8 * ref64.abs() * (1 + 1e-3) + 2 * (4 * 2.0 ** -24 / (1 - 4 * 2.0 ** -24)) * A)
     assert torch.all(cat[..., 64:] == 0)
     h1 = torch.randn(2, 32, 10, 14, generator=g)
     if dtype == torch.bfloat16:

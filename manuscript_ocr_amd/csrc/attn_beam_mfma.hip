@@ -26,13 +26,10 @@
 #include "msocr.h"
 #include "split_rows32.h"
 
-using split_rows32::acc_row;
-using split_rows32::f32x16;
 using split_rows32::mfma_cols32_split;
 using split_rows32::mfma_gates_split;
 using split_rows32::PPL;
 using split_rows32::PSB;
-using split_rows32::split_pair;
 using split_rows32::u32x4;
 
 #define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
@@ -396,7 +393,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
           unsigned char* d = sP + acc_row(e, half) * PSB + ju * 2;
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) {
-            const uint32_t pk = split_pair(hv[e], hv[e + 1]);
+            const uint32_t pk = split_step(hv[e], hv[e + 1]);
             *reinterpret_cast<uint16_t*>(d + pl * PPL) = (uint16_t)pk;
             *reinterpret_cast<uint16_t*>(d + pl * PPL + PSB) = (uint16_t)(pk >> 16);
           }
@@ -773,7 +770,7 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
         unsigned char* d = sP + acc_row(e, half) * PSB + ju * 2;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-          const uint32_t pk = split_pair(hv[e], hv[e + 1]);
+          const uint32_t pk = split_step(hv[e], hv[e + 1]);
           *reinterpret_cast<uint16_t*>(d + pl * PPL) = (uint16_t)pk;
           *reinterpret_cast<uint16_t*>(d + pl * PPL + PSB) = (uint16_t)(pk >> 16);
         }

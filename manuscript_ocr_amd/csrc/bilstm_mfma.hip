@@ -87,7 +87,7 @@ __global__ __launch_bounds__(NT, 1) void bilstm_split_kernel(const float* __rest
       unsigned char* dst = sP + acc_row(e, half) * PSB + ju * 2;
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
-        const uint32_t pk = split_pair(hv[e], hv[e + 1]);
+        const uint32_t pk = split_step(hv[e], hv[e + 1]);
         *reinterpret_cast<uint16_t*>(dst + pl * PPL) = (uint16_t)pk;
         *reinterpret_cast<uint16_t*>(dst + pl * PPL + PSB) = (uint16_t)(pk >> 16);
       }

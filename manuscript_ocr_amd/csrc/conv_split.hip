@@ -11,7 +11,8 @@
 // v_cvt_pk_bf16_f32 + two subtractions per pair); B = weights (or the Winograd U), split ONCE at load time into three bf16
 // planes [3][Cout][K] (msocr_split_bf16x3_host / ops.py).  Same tile as conv_igemm.hip's lean kernel: 128 x 128 (or 128 x 64) per
 // workgroup, 4 waves of 64 x 64 (64 x 32), K-tiles of 32, one LDS stage of six [rows][64 B] planes (16-B chunks XOR-swizzled by
-// row), 3 workgroups per CU; the epilogue (bias, residual, ReLU, 16-byte stores) is the exact-f32 kernel's.
+// row), 3 workgroups per CU; tile map, loaders and the epilogue (bias, residual, ReLU, 16-byte stores) are the shared ones of
+// conv_common.h, the split arithmetic is split_mma.h's.
 //
 // Used for every launch the lean exact-f32 GEMM served (1x1 / stride 1 / no padding convolutions, the LSTM / linear GEMMs and
 // the batched Winograd-domain GEMMs) unless the caller asks for precision = "fp32-exact".  Reference layers:
@@ -22,31 +23,21 @@
 #include <string.h>
 
 #include "conv_common.h"
-#include "internal.h"
-#include "msocr.h"
 
 namespace {
 
-// 16 zero bytes: padded (out-of-image) taps of the general loader read from here
-__device__ __attribute__((aligned(16))) uint32_t msocr_split_zero16[4] = {0u, 0u, 0u, 0u};
-
 // BN in {128, 64}; wave tile 64 x WN (WN = BN / 2); K-tile = 32 elements (A rows 128 B of f32 in HBM, 64 B per bf16 plane in LDS).
 // GEN = false: 1x1 / stride 1 / no padding over a dense pixel sequence and the batched GEMMs — a K-tile is a plain pointer
-// increment.  GEN = true: any kernel size / stride / padding (the implicit-GEMM loader of conv_igemm.hip: a K-tile lies inside one
-// filter tap because Cin % 32 == 0; out-of-image taps read zeros).
+// increment.  GEN = true: any kernel size / stride / padding (the tap loader of conv_common.h: a K-tile lies inside one filter tap
+// because Cin % 32 == 0; out-of-image taps read zeros).
 template <int BN, int WPE, bool GEN>
 __global__ __launch_bounds__(256, WPE) void conv_split_kernel(ConvParams p) {
-  constexpr int BM = 128, WM = 64, WN = BN / 2, BK = 32;
+  using G = SplitTile<BN>;
+  constexpr int BM = G::BM, WM = G::WM, WN = G::WN, BK = G::BK;
   constexpr int TM = WM / 32, TN = WN / 32;
-  constexpr int ROWB = BK * 2;             // bytes per LDS plane row (BK bf16)
-  constexpr int A_PLANE = BM * ROWB, B_PLANE = BN * ROWB;
-  constexpr int STAGE_B = 3 * (A_PLANE + B_PLANE);
-  constexpr int ACH = BK / 4;              // A: 16-B chunks per f32 row
-  constexpr int ARP = 256 / ACH;           //    rows per pass of 256 threads
-  constexpr int A_IT = BM / ARP;
-  constexpr int BCH = BK / 8;              // B: 16-B chunks per bf16 row
-  constexpr int BRP = 256 / BCH;
-  constexpr int B_IT = (BN + BRP - 1) / BRP;
+  constexpr int ROWB = G::ROWB, A_PLANE = G::A_PLANE, B_PLANE = G::B_PLANE, STAGE_B = G::STAGE_B;
+  constexpr int ACH = G::ACH, ARP = G::ARP, A_IT = G::A_IT;  // A: 16-B chunks per f32 row, rows per pass of 256 threads
+  constexpr int BCH = G::BCH, B_IT = G::B_IT;                // B: 16-B chunks per bf16 row
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -55,18 +46,8 @@ __global__ __launch_bounds__(256, WPE) void conv_split_kernel(ConvParams p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // XCD-aware tile mapping (as conv_igemm_kernel): each XCD gets a contiguous range of logical tiles
-  const int nblk1 = p.tilesM * p.tilesN;
-  const int nblk = nblk1 * p.nbatch;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-  }
-  const int batch = bid / nblk1;
-  bid -= batch * nblk1;
-  const int tile_n = bid % p.tilesN;
-  const int tile_m = bid / p.tilesN;
+  int batch, tile_m, tile_n;
+  tile_coords(p, xcd_tile<int>(blockIdx.x, p.tilesM * p.tilesN * p.nbatch), batch, tile_m, tile_n);
   const char* const g_in = p.in + (long)batch * p.bsA * 4;
   const char* const g_w = p.w + (long)batch * p.bsW * 2;
   char* const g_out = p.out + (long)batch * p.bsO * 4;
@@ -76,92 +57,36 @@ __global__ __launch_bounds__(256, WPE) void conv_split_kernel(ConvParams p) {
   // load), so the loop holds 4 + B_IT address registers instead of ten 64-bit pointers — the 168-register budget of 3 workgroups per
   // CU then leaves no spill in the loop (a spilled, freshly loaded register made every K-tile wait for a memory round trip).
   const int a_chunk = tid % ACH, a_row0 = tid / ACH;
-  uint32_t a_off[A_IT];  // GEN: signed byte offset of the row's (ho*SH - PH, wo*SW - PW) pixel, < 2 GB in magnitude (host check)
-  int a_hi0[GEN ? A_IT : 1], a_wi0[GEN ? A_IT : 1];
+  uint32_t a_off[A_IT];
+  ATap<GEN> a_tap[A_IT];
 #pragma unroll
-  for (int i = 0; i < A_IT; ++i) {
-    long m = (long)tile_m * BM + a_row0 + i * ARP;
-    if (m >= p.M) m = p.M - 1;  // rows past the end: valid addresses, values never stored
-    if constexpr (GEN) {
-      const long hw = (long)p.Ho * p.Wo;
-      const int n = (int)(m / hw);
-      const int rem = (int)(m - (long)n * hw);
-      const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
-      a_hi0[i] = ho * p.SH - p.PH;
-      a_wi0[i] = wo * p.SW - p.PW;
-      a_off[i] = (uint32_t)(int32_t)(((long)n * p.sN + (long)a_hi0[i] * p.sH + (long)a_wi0[i] * p.sW + a_chunk * 4) * 4);
-    } else {
-      // 1x1 / stride 1 / no padding: row m of the GEMM is pixel m of the NHWC input (row stride sW elements); < 4 GB (host check)
-      a_off[i] = (uint32_t)((m * p.sW + a_chunk * 4) * 4);
-    }
-  }
-  int t_kh = 0, t_kw = 0, t_c0 = 0;  // GEN: tap and channel offset of the NEXT K-tile load_tile() will fetch
+  for (int i = 0; i < A_IT; ++i) a_off[i] = a_row_offset32<GEN>(p, (long)tile_m * BM + a_row0 + i * ARP, a_chunk, a_tap[i]);
+  TapCursor tap;
+  tap.reset();
   const int b_chunk = tid % BCH, b_row0 = tid / BCH;
   uint32_t b_off[B_IT];
 #pragma unroll
-  for (int j = 0; j < B_IT; ++j) {
-    int co = tile_n * BN + b_row0 + j * BRP;
-    if (co >= p.Cout) co = p.Cout - 1;
-    b_off[j] = (uint32_t)(co * 64 + b_chunk * 16);   // K-tile-major planes: [k/32][Cout][32]
-  }
+  for (int j = 0; j < B_IT; ++j) b_off[j] = b_plane_offset(tile_n * BN + b_row0 + j * G::BRP, p.Cout, b_chunk);
   const long wplane_b = p.wplane * 2;
 
   u32x4 ra[A_IT], rb[3][B_IT];
   auto load_tile = [&](int kt) {
-    if constexpr (GEN) {
-      const int32_t koff = (int32_t)(((long)t_kh * p.sH + (long)t_kw * p.sW + t_c0) * 4);  // uniform
-#pragma unroll
-      for (int i = 0; i < A_IT; ++i) {
-        const int hi = a_hi0[i] + t_kh, wi = a_wi0[i] + t_kw;
-        const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-        // 32-bit offsets kept in registers, the 64-bit address formed per load: four address registers less than four pointers, which
-        // is what keeps this loop free of spill reloads at 168 registers
-        const char* src = g_in + (long)(int32_t)(a_off[i] + (uint32_t)koff);
-        ra[i] = *reinterpret_cast<const u32x4*>(ok ? src : reinterpret_cast<const char*>(msocr_split_zero16));
-      }
-      t_c0 += BK;
-      if (t_c0 == p.Cin) {
-        t_c0 = 0;
-        if (++t_kw == p.KW) { t_kw = 0; ++t_kh; }
-      }
-    } else {
-      const char* const ga = g_in + (long)kt * (BK * 4);  // uniform
-#pragma unroll
-      for (int i = 0; i < A_IT; ++i) ra[i] = *reinterpret_cast<const u32x4*>(ga + a_off[i]);
-    }
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      const char* const gb = g_w + pl * wplane_b + (long)kt * p.w_kt_b;  // uniform
-#pragma unroll
-      for (int j = 0; j < B_IT; ++j)
-        if (BN % BRP == 0 || b_row0 + j * BRP < BN) rb[pl][j] = *reinterpret_cast<const u32x4*>(gb + b_off[j]);
-    }
+    // GEN, BN = 128: the compiler spills 4 registers here (20 bytes of scratch) at the 168-register budget of 3 workgroups per CU; the
+    // instance runs only with a residual operand or a single K-tile (conv_split_pp.hip takes the rest).  The other three do not spill.
+    if constexpr (GEN) load_a_taps32(p, g_in, a_off, a_tap, tap, BK, ra);
+    else load_a_rows32(g_in + (long)kt * (BK * 4), a_off, ra);
+    load_b_planes<G>(p, g_w, wplane_b, kt, b_row0, b_off, rb);
   };
   auto store_tile = [&](int stage) {
     unsigned char* const sA = smem + stage * STAGE_B;  // [3][BM][ROWB] (one stage: stage == 0)
+#pragma unroll
+    for (int i = 0; i < A_IT; ++i) split_store_row<G>(sA, a_row0 + i * ARP, a_chunk, ra[i]);
     unsigned char* const sB = sA + 3 * A_PLANE;        // [3][BN][ROWB]
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-      const int row = a_row0 + i * ARP;
-      float x0 = __uint_as_float(ra[i][0]), x1 = __uint_as_float(ra[i][1]), x2 = __uint_as_float(ra[i][2]), x3 = __uint_as_float(ra[i][3]);
-      // this thread's 4 elements are bf16 positions 4 * a_chunk .. + 3 of the row: half of 16-B chunk a_chunk / 2
-      unsigned char* dst = sA + row * ROWB + (((a_chunk >> 1) ^ swz<ROWB>(row)) << 4) + ((a_chunk & 1) << 3);
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        u32x2 v;
-        v[0] = split_step(x0, x1);
-        v[1] = split_step(x2, x3);
-        *reinterpret_cast<u32x2*>(dst + pl * A_PLANE) = v;
-      }
-    }
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-      for (int j = 0; j < B_IT; ++j) {
-        const int row = b_row0 + j * BRP;
-        if (BN % BRP == 0 || row < BN)
-          *reinterpret_cast<u32x4*>(sB + pl * B_PLANE + row * ROWB + ((b_chunk ^ swz<ROWB>(row)) << 4)) = rb[pl][j];
-      }
+      for (int j = 0; j < B_IT; ++j)
+        if (BN % G::BRP == 0 || b_row0 + j * G::BRP < BN) store_b_row<G>(sB, pl, b_row0 + j * G::BRP, b_chunk, rb[pl][j]);
   };
 
   f32x16 acc[TM][TN];
@@ -194,17 +119,14 @@ __global__ __launch_bounds__(256, WPE) void conv_split_kernel(ConvParams p) {
           fb[pl][j] = *reinterpret_cast<const bf16x8*>(sB + pl * B_PLANE + row * ROWB + ((c ^ swz<ROWB>(row)) << 4));
         }
       }
-      // smallest terms first; consecutive MFMAs of one product class hit different accumulators
+      // the six products (split_mma.h: smallest terms first); consecutive MFMAs of one product class hit different accumulators
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+      for (int t = 0; t < 6; ++t)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[t]][i], fb[PB[t]][j], acc[i][j], 0, 0, 0);
-      }
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[split_pa(t)][i], fb[split_pb(t)][j], acc[i][j], 0, 0, 0);
     }
   };
 
@@ -226,53 +148,12 @@ __global__ __launch_bounds__(256, WPE) void conv_split_kernel(ConvParams p) {
     __syncthreads();
   }
 
-  // ---- epilogue (conv_igemm_kernel's): TM passes of (acc row-block -> LDS [64][BN] f32 -> bias/residual/ReLU -> 16-B stores) ----
-  constexpr int PR = (BM / WM) * 32;
-  float* sc = reinterpret_cast<float*>(smem);
-  constexpr int VPR = BN / 4;
-  constexpr int ROWS_PP = 256 / VPR;
-  const int vcol = (tid % VPR) * 4;
-  const int vrow0 = tid / VPR;
-  const int co = tile_n * BN + vcol;
-  f32x4 bias = {0.f, 0.f, 0.f, 0.f};
-  if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + co);
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    if (i) __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int rit = (e & 3) + 8 * (e >> 2) + 4 * half;
-        sc[(wm * 32 + rit) * BN + wn * WN + j * 32 + r32] = acc[i][j][e];
-      }
-    __syncthreads();
-    for (int lr = vrow0; lr < PR; lr += ROWS_PP) {
-      const int trow = (lr >> 5) * WM + i * 32 + (lr & 31);
-      const long m = (long)tile_m * BM + trow;
-      if (m >= p.M) continue;
-      f32x4 v = *reinterpret_cast<const f32x4*>(&sc[lr * BN + vcol]) + bias;
-      if (p.has_res) v += *reinterpret_cast<const f32x4*>(p.res + (m * p.res_ld + co) * 4);
-      if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      *reinterpret_cast<f32x4*>(g_out + (m * p.out_ld + co) * 4) = v;
-    }
-  }
+  epilogue_lds<float, BM, BN, WM, WN, 32, true>(p, smem, acc, tile_m, tile_n, g_out, wm, wn, r32, half);
 }
 
 template <int BN, int WPE, bool GEN>
 int launch_split(ConvParams& p, hipStream_t s) {
-  p.tilesM = (int)((p.M + 127) / 128);
-  p.tilesN = p.Cout / BN;
-  p.ktiles = (int)(p.Ktot / 32);
-  constexpr int STAGE = 3 * (128 + BN) * 64;
-  constexpr int EPI = 64 * BN * 4;
-  constexpr int LDS = STAGE > EPI ? STAGE : EPI;
-  auto kern = conv_split_kernel<BN, WPE, GEN>;
-  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(kern), LDS) != MSOCR_OK) return MSOCR_E_LAUNCH;
-  const long nblk = (long)p.tilesM * p.tilesN * p.nbatch;
-  if (nblk <= 0 || nblk > 0x7fffffffL) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(kern, dim3((unsigned)nblk), dim3(256), LDS, s, p);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return conv_launch<SplitTile<BN>>(conv_split_kernel<BN, WPE, GEN>, p, s);
 }
 
 // Kernel choice: shapes the producer / consumer kernel of conv_split_pp.hip has an instance for go there, the others (a residual
@@ -356,29 +237,9 @@ extern "C" int msocr_split_bf16x3_ktile_host(const float* w_host, int64_t nbatch
 // K-tile-major [3][Cin/32][Cout][32] (plane stride Cout * Cin).  Same descriptor, epilogue flags and error behaviour as msocr_conv2d.
 extern "C" int msocr_conv1x1_split(const msocr_conv_desc* d, const void* in, const void* weight_planes, const float* bias,
                                    const void* residual, void* out, void* stream) {
-  if (!d || !in || !weight_planes || !out) return MSOCR_E_ARG;
-  if (d->dtype != MSOCR_F32 || d->KH != 1 || d->KW != 1 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h || d->pad_w) return MSOCR_E_ARG;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ho != d->H || d->Wo != d->W) return MSOCR_E_ARG;
-  if (d->Cin <= 0 || d->Cin % 32 || d->Cout <= 0 || d->Cout % 64) return MSOCR_E_ARG;
-  // the pixels must form ONE dense row sequence: pixel stride sW, rows and images contiguous in units of it
-  if (d->in_sW % 4 || d->in_sW < d->Cin || (d->H > 1 && d->in_sH != (int64_t)d->W * d->in_sW) ||
-      (d->N > 1 && d->in_sN != (int64_t)d->H * d->W * d->in_sW)) return MSOCR_E_ARG;
-  if (d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
-  if (((uintptr_t)in | (uintptr_t)weight_planes | (uintptr_t)out) & 15) return MSOCR_E_ARG;
-  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
-  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
-  ConvParams p = {};
-  p.in = (const char*)in; p.w = (const char*)weight_planes; p.bias = bias; p.res = (const char*)residual; p.out = (char*)out;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
-  p.sN = d->in_sN; p.sH = d->in_sH; p.sW = d->in_sW;
-  p.KH = p.KW = 1; p.SH = p.SW = 1; p.PH = p.PW = 0;
-  p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
-  p.M = (long)d->N * d->Ho * d->Wo;
-  p.Ktot = d->Cin;
-  p.out_ld = d->out_ld; p.res_ld = d->res_ld;
-  p.relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
-  p.has_res = has_res ? 1 : 0;
-  p.nbatch = 1; p.bsA = p.bsW = p.bsO = 0;
+  if (!d || d->dtype != MSOCR_F32) return MSOCR_E_ARG;
+  if (conv_desc_check(d, in, weight_planes, residual, out, 4, 32, 64, CONV_STRIDES_DENSE) != MSOCR_OK) return MSOCR_E_ARG;
+  ConvParams p = conv_params(d, in, weight_planes, bias, residual, out);
   p.wplane = (long)d->Cout * d->Cin;
   return launch_split_any(p, (hipStream_t)stream, false);
 }
@@ -388,29 +249,9 @@ extern "C" int msocr_conv1x1_split(const msocr_conv_desc* d, const void* in, con
 // Cin % 32 == 0 and Cout % 64 == 0.
 extern "C" int msocr_conv2d_split(const msocr_conv_desc* d, const void* in, const void* weight_planes, const float* bias,
                                   const void* residual, void* out, void* stream) {
-  if (!d || !in || !weight_planes || !out || d->dtype != MSOCR_F32) return MSOCR_E_ARG;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0) return MSOCR_E_ARG;
-  if (d->Cin <= 0 || d->Cin % 32 || d->Cout <= 0 || d->Cout % 64) return MSOCR_E_ARG;
-  if (d->KH <= 0 || d->KW <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0) return MSOCR_E_ARG;
-  if (d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4 || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;  // 16-byte vector accesses
-  if (((uintptr_t)in | (uintptr_t)weight_planes | (uintptr_t)out) & 15) return MSOCR_E_ARG;
-  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
-  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
-  // output extent must agree with the conv arithmetic (guards the kernel's indexing)
-  if ((d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1 < d->Ho || (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1 < d->Wo)
-    return MSOCR_E_ARG;
-  ConvParams p = {};
-  p.in = (const char*)in; p.w = (const char*)weight_planes; p.bias = bias; p.res = (const char*)residual; p.out = (char*)out;
-  p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
-  p.sN = d->in_sN; p.sH = d->in_sH; p.sW = d->in_sW;
-  p.KH = d->KH; p.KW = d->KW; p.SH = d->stride_h; p.SW = d->stride_w; p.PH = d->pad_h; p.PW = d->pad_w;
-  p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
-  p.M = (long)d->N * d->Ho * d->Wo;
-  p.Ktot = (long)d->KH * d->KW * d->Cin;
-  p.out_ld = d->out_ld; p.res_ld = d->res_ld;
-  p.relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
-  p.has_res = has_res ? 1 : 0;
-  p.nbatch = 1; p.bsA = p.bsW = p.bsO = 0;
+  if (!d || d->dtype != MSOCR_F32) return MSOCR_E_ARG;
+  if (conv_desc_check(d, in, weight_planes, residual, out, 4, 32, 64, CONV_STRIDES_ALIGNED) != MSOCR_OK) return MSOCR_E_ARG;
+  ConvParams p = conv_params(d, in, weight_planes, bias, residual, out);
   p.wplane = (long)d->Cout * p.Ktot;
   // the general loader keeps signed 32-bit byte offsets from the input pointer: a batch whose input extent reaches 2 GB is launched
   // image range by image range (outputs of different images are independent)
@@ -425,7 +266,7 @@ extern "C" int msocr_conv2d_split(const msocr_conv_desc* d, const void* in, cons
     q.M = (long)q.N * d->Ho * d->Wo;
     q.in = p.in + (long)n0 * img_bytes;
     q.out = p.out + (long)n0 * out_img;
-    if (has_res) q.res = p.res + (long)n0 * res_img;
+    if (p.has_res) q.res = p.res + (long)n0 * res_img;
     const int rc = launch_split_any(q, (hipStream_t)stream, true);
     if (rc != MSOCR_OK) return rc;
   }
@@ -435,19 +276,8 @@ extern "C" int msocr_conv2d_split(const msocr_conv_desc* d, const void* in, cons
 // nbatch independent GEMMs of one shape in ONE launch, C[b][m][n] = sum_k A[b][m][k] * B[b][n][k]: A f32 [nbatch][M][K],
 // B as three K-tile-major bf16 planes [3][nbatch][K/32][N][32], C f32 [nbatch][M][N].  The Winograd-domain GEMMs (winograd.hip).
 int msocr_internal_gemm_split_batched(const float* A, const uint16_t* Bplanes, float* C, long M, int N, int K, int nbatch, hipStream_t s) {
-  if (!A || !Bplanes || !C || M <= 0 || N <= 0 || N % 64 || K <= 0 || K % 32 || nbatch <= 0) return MSOCR_E_ARG;
-  if (((uintptr_t)A | (uintptr_t)Bplanes | (uintptr_t)C) & 15) return MSOCR_E_ARG;
-  if (M > 0x7fffffffL) return MSOCR_E_ARG;
-  ConvParams p = {};
-  p.in = (const char*)A; p.w = (const char*)Bplanes; p.bias = nullptr; p.res = nullptr; p.out = (char*)C;
-  p.N = 1; p.H = (int)M; p.W = 1; p.Cin = K;
-  p.sN = M * (long)K; p.sH = K; p.sW = K;
-  p.KH = p.KW = 1; p.SH = p.SW = 1; p.PH = p.PW = 0;
-  p.Ho = (int)M; p.Wo = 1; p.Cout = N;
-  p.M = M; p.Ktot = K;
-  p.out_ld = N; p.res_ld = 0;
-  p.relu = 0; p.has_res = 0;
-  p.nbatch = nbatch; p.bsA = M * (long)K; p.bsW = (long)N * K; p.bsO = M * (long)N;
+  ConvParams p;
+  if (gemm_params(A, Bplanes, C, M, N, K, nbatch, 64, 32, &p) != MSOCR_OK) return MSOCR_E_ARG;
   p.wplane = (long)nbatch * N * K;
   return launch_split_any(p, s, false);
 }

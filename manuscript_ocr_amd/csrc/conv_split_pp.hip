@@ -33,12 +33,8 @@
 #include <type_traits>
 
 #include "conv_common.h"
-#include "internal.h"
-#include "msocr.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) uint32_t msocr_pp_zero16[4] = {0u, 0u, 0u, 0u};
 
 template <int I>
 using ic = std::integral_constant<int, I>;
@@ -65,19 +61,14 @@ __device__ __forceinline__ void store_f32x4_saddr(const char* sbase, uint32_t vo
   asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" ::"v"(voff), "v"(v), "s"(sbase), "n"(OFF) : "memory");
 }
 
-// LDS rows are 64 bytes (one K-tile of 32 bf16); a 16x16x32 fragment read takes 16-byte chunk lane / 16 of row lane % 16.  This
-// XOR of the chunk index by row makes every ds_read_b128 lane group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...) hit 16
-// distinct 16-byte slots (tools/microbench/mfma_energy.hip uses the same map; checked with SQ_LDS_BANK_CONFLICT).
-__device__ __forceinline__ int swz16(int row) { return (4 - ((row >> 2) & 3)) & 3; }
-
 // TM x TN = 32-row x 32-column units per consumer wave (2 x 4 or 4 x 2).  GEN as in conv_split_kernel: false = a K-tile is a pointer
 // increment (1x1 / stride 1 / no padding over a dense pixel sequence, batched GEMMs); true = taps / stride / padding.
 template <int TM, int TN, bool GEN>
 __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
-  constexpr int BM = 64 * TM, BN = 64 * TN, BK = 32, ROWB = 64;
-  constexpr int A_PLANE = BM * ROWB, B_PLANE = BN * ROWB;
-  constexpr int STAGE_B = 3 * (A_PLANE + B_PLANE);
-  constexpr int BIAS_OFF = 2 * STAGE_B;        // 4 slots of BN floats behind the two stages
+  using Tile = SplitPPTile<TM, TN>;
+  constexpr int BM = Tile::BM, BN = Tile::BN, BK = Tile::BK, ROWB = Tile::ROWB;
+  constexpr int A_PLANE = Tile::A_PLANE, B_PLANE = Tile::B_PLANE, STAGE_B = Tile::STAGE_B;
+  constexpr int BIAS_OFF = Tile::BIAS_OFF;     // 4 slots of BN floats behind the two stages
   constexpr int RM = 2 * TM, RN = 2 * TN;      // 16 x 16 blocks per consumer wave
   constexpr bool STREAM_B = TN >= TM;          // the operand with more blocks streams through, the other is held for the K-tile
   constexpr int RH = STREAM_B ? RM : RN, RS = STREAM_B ? RN : RM;   // held / streamed blocks: 4 / 8
@@ -90,22 +81,16 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
 
   // ---- static tile list: XCD x owns a contiguous range of logical tiles (neighbours share A rows / all share B in its L2);
   //      the workgroups of an XCD (blockIdx.x % 8 == x under round-robin placement; speed only) take them round-robin ----
-  const int nblk1 = p.tilesM * p.tilesN;
-  const int nblk = nblk1 * p.nbatch;
+  const int nblk = p.tilesM * p.tilesN * p.nbatch;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_x = gridDim.x >> 3;
-  const int xq = nblk >> 3, xr = nblk & 7;
-  const int x_start = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
-  const int x_cnt = xq + (xcd < xr ? 1 : 0);
+  int x_start, x_cnt;
+  xcd_range<int>(xcd, nblk, x_start, x_cnt);
   const int my_tiles = slot < x_cnt ? (x_cnt - slot + per_x - 1) / per_x : 0;
   const int G = my_tiles * p.ktiles;           // K-tiles this workgroup stages and multiplies
   if (G == 0) return;                          // uniform over the workgroup, before any barrier
 
-  auto tile_coords = [&](int n, int& batch, int& tile_m, int& tile_n) __attribute__((always_inline)) {
-    int t = x_start + slot + n * per_x;
-    batch = t / nblk1;
-    t -= batch * nblk1;
-    tile_n = t % p.tilesN;
-    tile_m = t / p.tilesN;
+  auto tile_of = [&](int n, int& batch, int& tile_m, int& tile_n) __attribute__((always_inline)) {
+    tile_coords(p, x_start + slot + n * per_x, batch, tile_m, tile_n);
   };
 
   if (wave >= 4) {
@@ -114,8 +99,8 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
     // measured and changes nothing: the loads were never the stall, profiles/r04_pp_ablations.txt.)
     constexpr int D = 2;
     const int ltid = tid & 255;
-    constexpr int ACH = 8, ARP = 32, A_IT = BM / ARP;   // A: 8 x 16-B chunks per 128-B f32 row, 32 rows per pass
-    constexpr int BCH = 4, BRP = 64, B_IT = BN / BRP;   // B: 4 x 16-B chunks per 64-B bf16 row, 64 rows per pass
+    constexpr int ACH = Tile::ACH, ARP = Tile::ARP, A_IT = Tile::A_IT;   // A: 8 x 16-B chunks per 128-B f32 row, 32 rows per pass
+    constexpr int BCH = Tile::BCH, B_IT = Tile::B_IT;                    // B: 4 x 16-B chunks per 64-B bf16 row, 64 rows per pass
     const int a_chunk = ltid % ACH, a_row0 = ltid / ACH;
     const int b_chunk = ltid % BCH, b_row0 = ltid / BCH;
     const long wplane_b = p.wplane * 2;
@@ -123,48 +108,31 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
 
     // two positions in the workgroup's (tile, K-tile) sequence: the next A tile and the next B tile (+ bias) to fetch
     uint32_t a_off[A_IT], b_off[B_IT];
-    int a_hi0[GEN ? A_IT : 1], a_wi0[GEN ? A_IT : 1];
+    ATap<GEN> a_tap[A_IT];
     const char* ga_base = nullptr;
     const char* gb_base = nullptr;
     const float* gbias = nullptr;
     int an = 0, akt = 0, bn = 0, bkt = 0;
     int sn = 0, skt = 0;                       // tile / K-tile of the next store
-    int t_kh = 0, t_kw = 0, t_c0 = 0;          // GEN: tap and channel offset of the next A tile
+    TapCursor tap;                             // GEN: tap and channel offset of the next A tile
+    tap.reset();
 
     auto set_tile_a = [&](int n) __attribute__((always_inline)) {
       int batch, tile_m, tile_n;
-      tile_coords(n, batch, tile_m, tile_n);
+      tile_of(n, batch, tile_m, tile_n);
       ga_base = p.in + (long)batch * p.bsA * 4;
 #pragma unroll
-      for (int i = 0; i < A_IT; ++i) {
-        long m = (long)tile_m * BM + a_row0 + i * ARP;
-        if (m >= p.M) m = p.M - 1;             // rows past the end: valid addresses, values never stored
-        if constexpr (GEN) {
-          const long hw = (long)p.Ho * p.Wo;
-          const int n_img = (int)(m / hw);
-          const int rem = (int)(m - (long)n_img * hw);
-          const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
-          a_hi0[i] = ho * p.SH - p.PH;
-          a_wi0[i] = wo * p.SW - p.PW;
-          a_off[i] = (uint32_t)(int32_t)(((long)n_img * p.sN + (long)a_hi0[i] * p.sH + (long)a_wi0[i] * p.sW + a_chunk * 4) * 4);
-        } else {
-          a_off[i] = (uint32_t)((m * p.sW + a_chunk * 4) * 4);   // < 4 GB (host check)
-        }
-      }
-      t_kh = t_kw = t_c0 = 0;
+      for (int i = 0; i < A_IT; ++i) a_off[i] = a_row_offset32<GEN>(p, (long)tile_m * BM + a_row0 + i * ARP, a_chunk, a_tap[i]);
+      tap.reset();
     };
     auto set_tile_b = [&](int n) __attribute__((always_inline)) {
       int batch, tile_m, tile_n;
-      tile_coords(n, batch, tile_m, tile_n);
+      tile_of(n, batch, tile_m, tile_n);
       gb_base = p.w + (long)batch * p.bsW * 2;
       // no bias: every lane reads the same zero word (the load stays unconditional, see below)
-      gbias = p.bias ? p.bias + tile_n * BN + bias_i : reinterpret_cast<const float*>(msocr_pp_zero16);
+      gbias = p.bias ? p.bias + tile_n * BN + bias_i : reinterpret_cast<const float*>(msocr_zero16);
 #pragma unroll
-      for (int j = 0; j < B_IT; ++j) {
-        int co = tile_n * BN + b_row0 + j * BRP;
-        if (co >= p.Cout) co = p.Cout - 1;
-        b_off[j] = (uint32_t)(co * 64 + b_chunk * 16);   // K-tile-major planes [k/32][Cout][32]: the tile's rows are one dense block
-      }
+      for (int j = 0; j < B_IT; ++j) b_off[j] = b_plane_offset(tile_n * BN + b_row0 + j * Tile::BRP, p.Cout, b_chunk);
     };
 
     // Loads are issued UNCONDITIONALLY — past the last K-tile of the last tile the position wraps to that tile's first K-tile (valid
@@ -174,40 +142,18 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
     float rbias[D];
     auto load_a = [&](auto buf_c) __attribute__((always_inline)) {
       constexpr int BUF = decltype(buf_c)::value;
-      if constexpr (GEN) {
-        const int32_t koff = (int32_t)(((long)t_kh * p.sH + (long)t_kw * p.sW + t_c0) * 4);   // uniform
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i) {
-          const int hi = a_hi0[i] + t_kh, wi = a_wi0[i] + t_kw;
-          const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-          const char* src = ga_base + (long)(int32_t)(a_off[i] + (uint32_t)koff);
-          ra[BUF][i] = *reinterpret_cast<const u32x4*>(ok ? src : reinterpret_cast<const char*>(msocr_pp_zero16));
-        }
-        t_c0 += BK;
-        if (t_c0 == p.Cin) {
-          t_c0 = 0;
-          if (++t_kw == p.KW) { t_kw = 0; ++t_kh; }
-        }
-      } else {
-        const char* const ga = ga_base + (long)akt * (BK * 4);   // uniform
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i) ra[BUF][i] = *reinterpret_cast<const u32x4*>(ga + a_off[i]);
-      }
+      if constexpr (GEN) load_a_taps32(p, ga_base, a_off, a_tap, tap, BK, ra[BUF]);
+      else load_a_rows32(ga_base + (long)akt * (BK * 4), a_off, ra[BUF]);
       if (++akt == p.ktiles) {
         akt = 0;
         if (an + 1 < my_tiles) set_tile_a(++an);
-        else t_kh = t_kw = t_c0 = 0;
+        else tap.reset();
       }
     };
     auto load_b = [&](auto buf_c) __attribute__((always_inline)) {
       constexpr int BUF = decltype(buf_c)::value;
       rbias[BUF] = *gbias;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        const char* const gb = gb_base + pl * wplane_b + (long)bkt * p.w_kt_b;   // uniform
-#pragma unroll
-        for (int j = 0; j < B_IT; ++j) rb[BUF][pl][j] = *reinterpret_cast<const u32x4*>(gb + b_off[j]);
-      }
+      load_b_planes<Tile>(p, gb_base, wplane_b, bkt, b_row0, b_off, rb[BUF]);
       if (++bkt == p.ktiles) {
         bkt = 0;
         if (bn + 1 < my_tiles) set_tile_b(++bn);
@@ -216,29 +162,13 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
     auto store = [&](auto buf_c, int stage) __attribute__((always_inline)) {
       constexpr int BUF = decltype(buf_c)::value;
       unsigned char* const sA = smem + stage * STAGE_B;   // [3][BM][ROWB]
+#pragma unroll
+      for (int i = 0; i < A_IT; ++i) split_store_row<Tile>(sA, a_row0 + i * ARP, a_chunk, ra[BUF][i]);
       unsigned char* const sB = sA + 3 * A_PLANE;         // [3][BN][ROWB]
-#pragma unroll
-      for (int i = 0; i < A_IT; ++i) {
-        const int row = a_row0 + i * ARP;
-        float x0 = __uint_as_float(ra[BUF][i][0]), x1 = __uint_as_float(ra[BUF][i][1]);
-        float x2 = __uint_as_float(ra[BUF][i][2]), x3 = __uint_as_float(ra[BUF][i][3]);
-        // this thread's 4 elements are bf16 positions 4 * a_chunk .. + 3 of the row: half of 16-B chunk a_chunk / 2
-        unsigned char* dst = sA + row * ROWB + (((a_chunk >> 1) ^ swz16(row)) << 4) + ((a_chunk & 1) << 3);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          u32x2 v;
-          v[0] = split_step(x0, x1);
-          v[1] = split_step(x2, x3);
-          *reinterpret_cast<u32x2*>(dst + pl * A_PLANE) = v;
-        }
-      }
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-        for (int j = 0; j < B_IT; ++j) {
-          const int row = b_row0 + j * BRP;
-          *reinterpret_cast<u32x4*>(sB + pl * B_PLANE + row * ROWB + ((b_chunk ^ swz16(row)) << 4)) = rb[BUF][pl][j];
-        }
+        for (int j = 0; j < B_IT; ++j) store_b_row<Tile>(sB, pl, b_row0 + j * Tile::BRP, b_chunk, rb[BUF][pl][j]);
       // the bias slice of this K-tile's output tile, slot (tile number) % 4: rewritten with every K-tile of the tile (same values),
       // read by the consumers one tile later, overwritten four tiles later
       if (BN == 256 || ltid < BN) *reinterpret_cast<float*>(smem + BIAS_OFF + ((sn & 3) * BN + ltid) * 4) = rbias[BUF];
@@ -304,13 +234,11 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
   f32x4 part[2][RH];
   auto chain = [&](auto s_c, auto h_c) __attribute__((always_inline)) {
     constexpr int S = decltype(s_c)::value, H = decltype(h_c)::value;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      if constexpr (STREAM_B) t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fs[S & 1][PB[k]], fh[PA[k]][H], t, 0, 0, 0);
-      else t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[PB[k]][H], fs[S & 1][PA[k]], t, 0, 0, 0);
+      if constexpr (STREAM_B) t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fs[S & 1][split_pb(k)], fh[split_pa(k)][H], t, 0, 0, 0);
+      else t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[split_pb(k)][H], fs[S & 1][split_pa(k)], t, 0, 0, 0);
     }
     part[S & 1][H] = t;
   };
@@ -331,7 +259,7 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
   const uint32_t vo = (uint32_t)((r16 * p.out_ld + 4 * kg) * 4);
   auto set_epilogue = [&](int n) __attribute__((always_inline)) {
     int batch, tile_m, tile_n;
-    tile_coords(n, batch, tile_m, tile_n);
+    tile_of(n, batch, tile_m, tile_n);
     const long row0 = (long)tile_m * BM + wm * 32 * TM;
     const int col0 = tile_n * BN + wn * 32 * TN;
     e_ob = p.out + ((long)batch * p.bsO + row0 * p.out_ld + col0) * 4;
@@ -417,22 +345,7 @@ __global__ __launch_bounds__(512, 2) void conv_split_pp_kernel(ConvParams p) {
 
 template <int TM, int TN, bool GEN>
 int launch_pp(ConvParams& p, hipStream_t s) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  p.tilesM = (int)((p.M + BM - 1) / BM);
-  p.tilesN = p.Cout / BN;
-  p.ktiles = (int)(p.Ktot / 32);
-  constexpr int LDS = 2 * 3 * (BM + BN) * 64 + 4 * BN * 4;
-  auto kern = conv_split_pp_kernel<TM, TN, GEN>;
-  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(kern), LDS) != MSOCR_OK) return MSOCR_E_LAUNCH;
-  const long nblk = (long)p.tilesM * p.tilesN * p.nbatch;
-  if (nblk <= 0 || nblk > 0x7fffffffL) return MSOCR_E_ARG;
-  int n_cu = 0;
-  if (msocr_internal_cu_count(&n_cu) != MSOCR_OK) return MSOCR_E_LAUNCH;
-  n_cu = n_cu > 8 ? n_cu & ~7 : 8;
-  long grid = (nblk + 7) & ~7L;
-  if (grid > n_cu) grid = n_cu;
-  MSOCR_LAUNCH(kern, dim3((unsigned)grid), dim3(512), LDS, s, p);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return conv_launch<SplitPPTile<TM, TN>>(conv_split_pp_kernel<TM, TN, GEN>, p, s);
 }
 
 }  // namespace

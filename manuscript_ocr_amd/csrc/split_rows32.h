@@ -6,42 +6,27 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "split_mma.h"
+
 namespace split_rows32 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int H = 256;  // hidden units = reduction length
 constexpr int R = 32;   // state rows = one MFMA row block
 
-// row of accumulator register e in the 32x32 MFMA output layout (lane half = lane >> 5)
-__device__ __forceinline__ int acc_row(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
 
 // ---- split-operand form of the three matrix products : h is kept in LDS as three bf16 planes with h == p0 + p1 + p2
 // exactly (the residual chain of conv_split.hip), the weights come pre-split and packed [plane][k / 16][column][16] bf16
-// (msocr_attn_pack_split_host), and every f32 product a * b is the six bf16 products a2b0 + a0b2 + a1b1 + a1b0 + a0b1 + a0b0 on
+// (msocr_attn_pack_split_host), and every f32 product a * b is the six bf16 products of split_mma.h on
 // v_mfma_f32_32x32x16_bf16 with f32 accumulation (dropped terms <= 2^-25 |a b|): 6 MFMAs of 8 passes per 16 k instead of 8 MFMAs of
 // 16 passes on the exact-f32 pipe, i.e. 2.7x less matrix-pipe time for the same f32 result up to summation order.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int PSB = H * 2 + 16;       // bytes per plane row: 528 = 132 dwords, rows shift 4 banks -> ds_read_b128 of 32 rows is conflict-free
 constexpr int PPL = R * PSB;          // bytes per plane
 
-__device__ __forceinline__ uint32_t split_pair(float& x, float& y) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {x, y};
-  const uint32_t pk = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));  // v_cvt_pk_bf16_f32, RNE
-  x -= __uint_as_float(pk << 16);
-  y -= __uint_as_float(pk & 0xffff0000u);
-  return pk;
-}
+// the weight fragments arrive as raw 16-byte loads
 __device__ __forceinline__ void mma6(const bf16x8 (&fa)[3], const u32x4 (&wb)[3], f32x16& acc) {
-  const bf16x8 b0 = __builtin_bit_cast(bf16x8, wb[0]), b1 = __builtin_bit_cast(bf16x8, wb[1]), b2 = __builtin_bit_cast(bf16x8, wb[2]);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], b2, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], b1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], b1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], b0, acc, 0, 0, 0);
+  const bf16x8 fb[3] = {__builtin_bit_cast(bf16x8, wb[0]), __builtin_bit_cast(bf16x8, wb[1]), __builtin_bit_cast(bf16x8, wb[2])};
+  ::mma6(fa, fb, acc);
 }
 __device__ __forceinline__ void read_a3(const unsigned char* sP, int kb, int r32, int half, bf16x8 (&fa)[3]) {
 #pragma unroll

@@ -29,12 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "internal.h"
-#include "msocr.h"
-
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "conv_common.h"
 
 // ---- 1-D transforms, four channels per lane: B^T (M + 2 inputs -> M + 2 points) and A^T (M + 2 points -> M outputs) ----------
 template <int M> __device__ void wino_bt1(const f32x4 d[M + 2], f32x4 r[M + 2]);
@@ -363,17 +358,6 @@ typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
 // output transform below is shared.
 typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2w __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned int wino_split_step(float& x, float& y) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {x, y};
-  const bf16x2 h = __builtin_convertvector(v, bf16x2);
-  const unsigned int pk = __builtin_bit_cast(unsigned int, h);
-  x -= __uint_as_float(pk << 16);
-  y -= __uint_as_float(pk & 0xffff0000u);
-  return pk;
-}
-
 template <bool POOL, bool SPLIT = false>
 __global__ __launch_bounds__(256, 3) void wino42_fused64_kernel(const float* __restrict__ V, const void* __restrict__ Uv, int Cout,
                                                                  WinoGeom g, const float* __restrict__ bias,
@@ -389,12 +373,7 @@ __global__ __launch_bounds__(256, 3) void wino42_fused64_kernel(const float* __r
   // XCD-aware order: blocks b, b+8, ... share an XCD (its L2): give each XCD a contiguous range of logical blocks, cout blocks
   // fastest, so the Cout/32 workgroups that read one V tile run on the same L2
   const int nbn = Cout / BN;
-  const long nblk = (long)gridDim.x;
-  long bid = blockIdx.x;
-  {
-    const long q = nblk >> 3, r = nblk & 7, x = bid & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-  }
+  const long bid = xcd_tile<long>(blockIdx.x, gridDim.x);
   const int nb = (int)(bid % nbn);
   const long m0 = (bid / nbn) * BM;
   const int n0 = nb * BN;
@@ -433,8 +412,8 @@ __global__ __launch_bounds__(256, 3) void wino42_fused64_kernel(const float* __r
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
           u32x2w v;
-          v[0] = wino_split_step(x0, x1);
-          v[1] = wino_split_step(x2, x3);
+          v[0] = split_step(x0, x1);
+          v[1] = split_step(x2, x3);
           *reinterpret_cast<u32x2w*>(dst + pl * PLANE) = v;
         }
       }
@@ -461,13 +440,7 @@ __global__ __launch_bounds__(256, 3) void wino42_fused64_kernel(const float* __r
           fa[pl] = *reinterpret_cast<const bf16x8w*>(st + pl * PLANE + rowa * ROWS + ((c ^ (rowa & 7)) << 4));
           fb[pl] = *reinterpret_cast<const bf16x8w*>(st + (3 + pl) * PLANE + rowb * ROWS + ((c ^ (rowb & 7)) << 4));
         }
-        // smallest terms first
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[0], c4, 0, 0, 0);
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[2], c4, 0, 0, 0);
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[1], c4, 0, 0, 0);
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[0], c4, 0, 0, 0);
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[1], c4, 0, 0, 0);
-        c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], c4, 0, 0, 0);
+        mma6(fa, fb, c4);
       }
       acc[p] = c4;
       if (p + 1 < 24) sstore(p + 1);
@@ -618,12 +591,7 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
   const int wm = wave >> 1, wn = wave & 1;
   const int r32 = lane & 31, half = lane >> 5;
   const int nbn = Cout / BN;
-  const long nblk = (long)gridDim.x;
-  long bid = blockIdx.x;
-  {  // XCD-aware order, cout blocks fastest (the workgroups that read one V tile share an L2)
-    const long q = nblk >> 3, r = nblk & 7, x = bid & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-  }
+  const long bid = xcd_tile<long>(blockIdx.x, gridDim.x);  // XCD-aware order, cout blocks fastest (the workgroups that read one V tile share an L2)
   const int nb = (int)(bid % nbn);
   const long m0 = (bid / nbn) * BM;
   const int n0 = nb * BN;
@@ -658,8 +626,8 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
         u32x2w v;
-        v[0] = wino_split_step(x0, x1);
-        v[1] = wino_split_step(x2, x3);
+        v[0] = split_step(x0, x1);
+        v[1] = split_step(x2, x3);
         *reinterpret_cast<u32x2w*>(dst + pl * PLANE) = v;
       }
     }
@@ -710,12 +678,7 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
         fa[pl] = *reinterpret_cast<const bf16x8w*>(smem + pl * PLANE + rowa * ROWS + ((c ^ (rowa & 7)) << 4));
         fb[pl] = *reinterpret_cast<const bf16x8w*>(smem + (3 + pl) * PLANE + rowb * ROWS + ((c ^ (rowb & 7)) << 4));
       }
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], m, 0, 0, 0);  // smallest terms first
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], m, 0, 0, 0);
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], m, 0, 0, 0);
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], m, 0, 0, 0);
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], m, 0, 0, 0);
-      m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], m, 0, 0, 0);
+      mma6(fa, fb, m);
     }
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
@@ -728,12 +691,12 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
     __syncthreads();
   }
 
-  // ---- epilogue: element e of this lane = tile m0 + 32 wm + (e & 3) + 8 (e >> 2) + 4 half, cout n0 + 32 wn + r32 ----
+  // ---- epilogue: element e of this lane = tile m0 + 32 wm + acc_row(e, half), cout n0 + 32 wn + r32 ----
   const int co = n0 + wn * 32 + r32;
   const float bv = bias ? bias[co] : 0.f;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const long t = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+    const long t = m0 + wm * 32 + acc_row(e, half);
     if (t >= g.Mt) continue;
     const int tw = (int)(t % g.TW);
     const long r = t / g.TW;

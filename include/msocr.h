@@ -328,10 +328,12 @@ int msocr_reading_order_crops(const float* boxes, const int32_t* nbox, int N, in
 /* ---- image ingest: JPEG -> RGB on the device -------------------------------------------------------------------------
  * Replaces the file decode of read_image (detectors/_east/utils.py:477-497: cv2.imread / PIL = libjpeg-turbo defaults).
  * 8-bit baseline / extended-sequential Huffman JPEG, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart
- * markers.  The serial entropy decode of a stream without restart markers runs on the HOST (msocr_jpeg_parse_host fills `info`;
- * msocr_jpeg_entropy_decode_host writes the quantised coefficients, natural order, component after component:
- * [blocks_h][blocks_w][64] int16 at coef_off[c]); a stream WITH a restart interval is decoded on the DEVICE, one thread per
- * interval (msocr_jpeg_scan_prepare_host + msocr_jpeg_entropy_decode_device below);
+ * markers.  msocr_jpeg_parse_host fills `info`; the Huffman stage has three forms that give the same bits: on the HOST
+ * msocr_jpeg_entropy_decode_host (the serial decoder and the judge of every stream; writes the quantised coefficients, natural
+ * order, component after component: [blocks_h][blocks_w][64] int16 at coef_off[c]); on the DEVICE one thread per restart interval
+ * for streams WITH a restart interval (msocr_jpeg_scan_prepare_host + msocr_jpeg_entropy_decode_device below); and on the DEVICE the
+ * self-synchronising decode of a serial segment, parallel inside it, for streams WITHOUT restart markers and for long intervals
+ * (msocr_jpeg_sync_prepare_host + msocr_jpeg_entropy_decode_sync_device below);
  * dequantisation + inverse DCT (libjpeg "islow"), fancy chroma upsampling and YCbCr->RGB run on the DEVICE
  * (msocr_jpeg_reconstruct: coef_dev = the same array in device memory, workspace = msocr_jpeg_workspace_bytes(info) bytes,
  * rgb_out [height][width][3] u8).  msocr_jpeg_reconstruct_host is the HOST twin of the device stage (same code; all pointers
@@ -369,6 +371,37 @@ int msocr_jpeg_entropy_decode_device(const uint8_t* bytes_dev, const void* descs
 int msocr_jpeg_entropy_decode_intervals_host(const uint8_t* bytes_host, const void* descs_host, int32_t n_pages,
                                              const uint32_t* bounds_host, const int64_t* page_base_host, int16_t* coef_host,
                                              int64_t coef_total, int32_t* status_host);
+/* Self-synchronising device entropy decode of a BATCH of streams, with or without restart intervals: every interval (a stream
+ * without DRI = one interval of all its MCUs) is cut into subsequences of subseq_bytes bytes, one thread each; max_rounds rounds
+ * bring their entry states to the fixed point (entry of i == exit of i - 1; a page that stands costs nothing in later rounds), a
+ * prefix sum places them, a write pass scatters the coefficients with DC differences and a per-component prefix sum turns those
+ * into values.  Host, per page: msocr_jpeg_sync_prepare_host = msocr_jpeg_scan_prepare_host that also takes streams without DRI
+ * (one pair: first byte of the scan, first marker) and refuses files above 0x1ff00000 bytes (bit positions are 32-bit).  The caller
+ * lays the subsequences out: interval k of a page has max(1, ceil((end - begin) / subseq_bytes)) of them, sub_first [one uint32 per
+ * interval, the pages' one after the other like the pairs] = index inside the PAGE of the interval's first subsequence, and
+ * page_base [n_pages][4] int64 = {where the page's coefficient array starts in coef (int16 elements), index of the page's first
+ * pair / sub_first entry, index of the page's first subsequence in the batch, number of subsequences of the page}; max_subseq = the
+ * largest of those numbers, total_subseq their sum.  workspace_dev: msocr_jpeg_sync_workspace_bytes(total_subseq, n_pages,
+ * max_rounds) bytes, 8-byte aligned.  16 <= subseq_bytes <= 65536, 2 <= max_rounds <= 65536.
+ * coef_dev [coef_total] is zero-filled by the call.  status_dev [n_pages]: 0 = decoded, bit-identical to
+ * msocr_jpeg_entropy_decode_host; 1 = the stream is bad (exactly when msocr_jpeg_entropy_decode_host refuses it: the verdict comes
+ * from the decode along the true chain of states, never from a speculative one); 2 = not decoded here, stream not judged (no fixed
+ * point within max_rounds, or the data ends with more than 64 blocks of an interval outstanding, i.e. a truncated stream): decode
+ * it with msocr_jpeg_entropy_decode_host.  rounds_dev [n_pages] (may be NULL): rounds that decoded something.  One launch sequence
+ * per batch on `stream`, no host wait.  msocr_jpeg_entropy_decode_sync_host is the HOST twin (same functions, same rounds; all
+ * pointers host memory; no workspace). */
+int64_t msocr_jpeg_sync_prepare_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base,
+                                     void* desc_out, uint32_t* bounds_out, int64_t bounds_cap);
+int64_t msocr_jpeg_sync_workspace_bytes(int64_t total_subseq, int32_t n_pages, int32_t max_rounds);
+int msocr_jpeg_entropy_decode_sync_device(const uint8_t* bytes_dev, const void* descs_dev, int32_t n_pages,
+                                          const uint32_t* bounds_dev, const uint32_t* sub_first_dev, const int64_t* page_base_dev,
+                                          int32_t max_subseq, int64_t total_subseq, int32_t subseq_bytes, int32_t max_rounds,
+                                          int16_t* coef_dev, int64_t coef_total, int32_t* status_dev, int32_t* rounds_dev,
+                                          void* workspace_dev, void* stream);
+int msocr_jpeg_entropy_decode_sync_host(const uint8_t* bytes_host, const void* descs_host, int32_t n_pages,
+                                        const uint32_t* bounds_host, const uint32_t* sub_first_host, const int64_t* page_base_host,
+                                        int32_t subseq_bytes, int32_t max_rounds, int16_t* coef_host, int64_t coef_total,
+                                        int32_t* status_host, int32_t* rounds_host);
 int64_t msocr_jpeg_workspace_bytes(const msocr_jpeg_info* info);
 int msocr_jpeg_reconstruct(const msocr_jpeg_info* info, const int16_t* coef_dev, void* workspace_dev, uint8_t* rgb_out_dev,
                            void* stream);

@@ -99,6 +99,11 @@ _SIGS = {
     "msocr_jpeg_scan_prepare_host": (c_i64, [c_vp, c_i64, ctypes.POINTER(JpegInfo), c_i64, c_vp, c_vp, c_i64]),
     "msocr_jpeg_entropy_decode_device": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "msocr_jpeg_entropy_decode_intervals_host": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "msocr_jpeg_sync_prepare_host": (c_i64, [c_vp, c_i64, ctypes.POINTER(JpegInfo), c_i64, c_vp, c_vp, c_i64]),
+    "msocr_jpeg_sync_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "msocr_jpeg_entropy_decode_sync_device": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i64,
+                                                      c_vp, c_vp, c_vp, c_vp]),
+    "msocr_jpeg_entropy_decode_sync_host": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "msocr_jpeg_workspace_bytes": (c_i64, [ctypes.POINTER(JpegInfo)]),
     "msocr_jpeg_reconstruct": (c_i32, [ctypes.POINTER(JpegInfo), c_vp, c_vp, c_vp, c_vp]),
     "msocr_jpeg_reconstruct_host": (c_i32, [ctypes.POINTER(JpegInfo), c_vp, c_vp]),

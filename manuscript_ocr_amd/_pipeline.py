@@ -228,12 +228,13 @@ class Pipeline:
         import torch
 
         det = self.detector
-        # image ingest: a JPEG file is decoded ON THE DEVICE (host Huffman stage + HIP reconstruction, ingest.py) — the page's
+        # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
         arrays, decoded = [], []
         dec, ingest_pending = [None] * len(images), None
-        # Which Huffman stage for files with restart intervals: ingest's policy (the device kernel unless an interval is so long that
-        # its serial chain loses to a host core; `pipeline.device_entropy = True / False` or MSOCR_JPEG_DEVICE_ENTROPY force one).
+        # Which Huffman stage: ingest's policy (the per-interval kernel for short restart intervals, the self-synchronising stage
+        # for long ones and for files without restart markers; `pipeline.device_entropy = True / False` or MSOCR_JPEG_DEVICE_ENTROPY
+        # force the device stages / the host pool).
         # From files, same box: device stage 79.5-80.1, host pool 78.2-79.2 pages/s against 83.0 resident.
         if _device_entropy is None:
             _device_entropy = getattr(self, "device_entropy", None)
@@ -241,8 +242,8 @@ class Pipeline:
         with torch.cuda.stream(ing):
             if pages_dev is None and getattr(self, "device_ingest", True):
                 from . import ingest
-                # Huffman stage on the device for files with restart intervals, on a host thread pool otherwise; the device stage's
-                # verdict on corrupt streams is read in advance_batch (ingest.check_pending), not here
+                # the device stages' verdict on corrupt streams (and the pages the self-synchronising stage declined) is read in
+                # advance_batch (ingest.check_pending), not here
                 dec, ingest_pending = ingest.read_images_device(list(images), det.device, device_entropy=_device_entropy, defer_status=True)
             for im, t in zip(images, dec):
                 if t is not None:

@@ -6,12 +6,14 @@
 // one interleaved scan, restart markers.  Anything else (progressive, arithmetic, CMYK, 12-bit, multi-scan, h1v2) is reported
 // as unsupported and the caller falls back to the host decoder.
 //
-// Split: the entropy-coded segment of a stream WITHOUT restart markers is one serial bit stream, so parsing + Huffman decoding run
-// on the HOST (msocr_jpeg_parse_host / msocr_jpeg_entropy_decode_host -> quantised DCT coefficients, 2 bytes each).  A stream WITH
-// a restart interval (DRI) is a sequence of independent, byte-aligned bit streams (DC predictors reset at every RSTn): the host only
-// walks the markers (msocr_jpeg_scan_prepare_host: interval bounds + Huffman tables), the file bytes go to the device as they are
-// and ONE THREAD PER INTERVAL decodes them there (msocr_jpeg_entropy_decode_device, round 4) — 0.3-0.6 MB of file bytes cross PCIe
-// instead of 9.4 MB of coefficients per 2048 x 1536 page, and no host core decodes anything.  Everything per-pixel —
+// Split: parsing runs on the HOST (msocr_jpeg_parse_host), and so does the serial Huffman decoder that judges every stream
+// (msocr_jpeg_entropy_decode_host -> quantised DCT coefficients, 2 bytes each).  A stream WITH a restart interval (DRI) is a sequence
+// of independent, byte-aligned bit streams (DC predictors reset at every RSTn): the host only walks the markers
+// (msocr_jpeg_scan_prepare_host: interval bounds + Huffman tables), the file bytes go to the device as they are and ONE THREAD PER
+// INTERVAL decodes them there (msocr_jpeg_entropy_decode_device).  A stream WITHOUT one, or an interval too long for one thread, is
+// one serial bit stream: the self-synchronising stage (msocr_jpeg_entropy_decode_sync_device, below the per-interval kernel) cuts it
+// into subsequences that are decoded in parallel from guessed states and brought into step in rounds.  Either way 0.3-1.6 MB of file
+// bytes cross PCIe instead of 9.4 MB of coefficients per 2048 x 1536 page, and no host core decodes anything.  Everything per-pixel —
 // dequantisation + inverse DCT, chroma upsampling, colour conversion — runs on the DEVICE (msocr_jpeg_reconstruct), so the
 // page's pixels are produced in HBM and never cross PCIe.  The reconstruction arithmetic is libjpeg's, restated from its
 // published algorithms (jidctint.c "islow" 13-bit fixed point, jdsample.c triangle-filter upsampling, jdcolor.c 16-bit YCC
@@ -421,7 +423,8 @@ struct IntervalBits {
   HD void skip(int n) { nbits -= n; }
 };
 
-HD int interval_symbol(IntervalBits& br, const DevTable& t) {
+template <class Bits>
+HD int interval_symbol(Bits& br, const DevTable& t) {
   const uint32_t look = br.peek(9);
   const uint32_t e = t.look[look];
   if (e) { br.skip((int)(e >> 8)); return (int)(e & 0xff); }
@@ -533,6 +536,432 @@ __global__ __launch_bounds__(64) void jpeg_huffman_kernel(const uint8_t* __restr
   const int first = iv * d.restart_interval;
   const int n = total - first < d.restart_interval ? total - first : d.restart_interval;
   if (decode_interval(d.info, d.mcus_x, s_dc, s_ac, s_zz, bytes + d.bytes_base, begin, end, first, n, coef + coef_base)) status[blockIdx.y] = 1;
+}
+
+// ---------------------------------------------------------------------------------------------------- self-synchronising decode
+// ONE serial entropy-coded segment (a stream without DRI, or one long restart interval) decoded in parallel.  The interval's bytes
+// are cut into subsequences of S bytes, one thread each.  A decoder state at a symbol boundary is (bit position in the file, block
+// inside the MCU, zigzag index k); the DC predictors are not part of it: the write pass stores DC DIFFERENCES and a prefix sum per
+// component turns them into values afterwards.  The first subsequence of an interval starts in the true state, every other one
+// from a guess; a Huffman decoder in a wrong state falls into step with the true decode after a short distance, so
+//   rounds  : every subsequence is decoded (nothing written) from its entry state to the first symbol that starts behind its last
+//             byte and leaves that exit state and the number of blocks it completed; in the next round it takes its predecessor's
+//             exit state as entry state and decodes again if that differs from what it used.  Fixed point: entry[i] == exit[i-1]
+//             for all i; subsequence r is final after round r, self-synchronisation makes it a handful of rounds instead of N.
+//             Rounds are kernel launches (their order on the stream is the only ordering between workgroups); exit states are
+//             double-buffered so that a round reads only what the round before wrote, and a page where a round changed nothing
+//             returns at once from every later round.
+//   place   : exclusive prefix sum of the block counts -> the first block of every subsequence.
+//   write   : every subsequence is decoded once more from its final entry state and scatters its coefficients.  This pass IS the
+//             decode along the true chain of states, so it alone judges the stream (status 1); what a speculative decode meets
+//             (undecodable codes, DC sizes > 15, k > 63, all the time) only makes an exit state that is not valid yet.
+//   dc      : per component, segmented inclusive prefix sum of the differences in scan order, modulo 2^16 (= the serial decoder's
+//             (int16_t) of its modulo-2^32 predictor).
+// The same __host__ __device__ functions run in the kernels and in msocr_jpeg_entropy_decode_sync_host.
+constexpr uint32_t kSyncTailBlocks = 64;   // blocks one thread may decode from the zeros behind the data's end (<= 64 symbols each)
+
+struct SyncBits {          // IntervalBits that knows where in the FILE its next unread bit sits
+  const uint8_t* base;
+  uint32_t pos, end;       // next byte to load (runs on past `end`: virtual zero bytes, so that positions stay monotonic)
+  uint64_t acc;
+  int nbits;
+  uint32_t stuffed;        // bit j: the byte loaded j loads ago was a 0xFF, i.e. took two file bytes
+  HD void load_byte() {
+    uint32_t b = 0, ff = 0;
+    if (pos < end) { b = base[pos]; ff = b == 0xFF; }
+    pos += 1 + ff;         // [begin, end) of an interval holds no marker: a 0xFF in it is followed by its stuffed 0x00
+    acc = (acc << 8) | (uint64_t)b;
+    stuffed = (stuffed << 1) | ff;
+    nbits += 8;
+  }
+  // at least 33 valid bits afterwards
+  HD void refill() {
+    if (nbits > 32) return;
+    if (pos + 4 <= end) {
+      const uint32_t lo = (uint32_t)base[pos] | ((uint32_t)base[pos + 1] << 8) | ((uint32_t)base[pos + 2] << 16) | ((uint32_t)base[pos + 3] << 24);
+      if ((((~lo) - 0x01010101u) & lo & 0x80808080u) == 0) {  // no 0xFF among the four
+        const uint32_t be = (lo << 24) | ((lo & 0xff00u) << 8) | ((lo >> 8) & 0xff00u) | (lo >> 24);
+        acc = (acc << 32) | (uint64_t)be;
+        nbits += 32;
+        pos += 4;
+        stuffed <<= 4;
+        return;
+      }
+    }
+    while (nbits <= 32) load_byte();
+  }
+  HD void start(const uint8_t* b, uint32_t bit, uint32_t e) {
+    base = b; pos = bit >> 3; end = e; acc = 0; nbits = 0; stuffed = 0;
+    load_byte();
+    nbits -= (int)(bit & 7);
+  }
+  HD uint32_t peek(int n) const { return (uint32_t)(acc >> (nbits - n)) & ((1u << n) - 1u); }
+  HD void skip(int n) { nbits -= n; }
+  // File bit position of the next unread bit.  A stuffed 0x00 counts as read together with its 0xFF, so a position never points into
+  // one and the same place in the stream always gives the same number, however much was buffered.
+  HD uint32_t bitpos() const {
+    const int nb = (nbits + 7) >> 3;                                   // buffered bytes with an unread bit, <= 8
+    const uint32_t m = stuffed & ((1u << nb) - 1u);
+#ifdef __HIP_DEVICE_COMPILE__
+    const int ns = __popc(m);
+#else
+    const int ns = __builtin_popcount(m);
+#endif
+    return pos * 8u - (uint32_t)nbits - 8u * (uint32_t)ns;
+  }
+};
+
+HD uint64_t sync_pack(uint32_t bit, int b, int k) { return (uint64_t)bit | ((uint64_t)(uint32_t)b << 32) | ((uint64_t)(uint32_t)k << 40); }
+
+// Decodes symbols from `state` on.  Count mode: every symbol that starts before bit `stop`; *n_out = blocks completed.  Write mode:
+// the same symbols (and, with `tail`, on into the zeros behind the data) as long as the block they belong to — number `blk` of the
+// interval — is one of the interval's `need` blocks: that is what keeps every coefficient address inside the page's array.  The two
+// modes treat what a valid stream cannot hold in the same way (an undecodable code = 16 bits skipped, symbol 0; a DC size > 15 =
+// its low four bits; k > 63 = end of block), so their state sequences are the same; only write mode reports it (*bad).
+// Every iteration consumes at least one bit: bounded by the bytes of the subsequence, the tail by kSyncTailBlocks * 64 symbols.
+// Returns the state at the first symbol not decoded.
+template <bool WRITE>
+HD uint64_t sync_decode(const ScanDesc& d, const DevTable* dc, const DevTable* ac, const uint8_t* zigzag, const uint8_t* bytes,
+                        uint32_t end, uint64_t state, uint32_t stop, bool tail, uint32_t blk, uint32_t need, int first_mcu,
+                        int16_t* coef, uint32_t* n_out, int* bad) {
+  const msocr_jpeg_info& f = d.info;
+  SyncBits br;
+  br.start(bytes, (uint32_t)state, end);
+  int b = (int)((state >> 32) & 0xff), k = (int)((state >> 40) & 0xff);
+  const int nb0 = f.hs[0] * f.vs[0];
+  const int per_mcu = f.ncomp == 3 ? nb0 + 2 : 1;
+  uint32_t n = 0, at;
+  int mx = 0, my = 0, bb = 0;
+  int64_t addr = 0;
+  auto block_addr = [&]() {
+    const int c = f.ncomp == 1 ? 0 : (bb < nb0 ? 0 : bb - nb0 + 1);
+    const int by = c == 0 ? bb / f.hs[0] : 0, bx = c == 0 ? bb - by * f.hs[0] : 0;
+    return f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+  };
+  if (WRITE) {
+    const int mcu = first_mcu + (int)(blk / (uint32_t)per_mcu);
+    bb = (int)(blk % (uint32_t)per_mcu);
+    my = mcu / d.mcus_x;
+    mx = mcu - my * d.mcus_x;
+    addr = block_addr();
+  }
+  for (;;) {
+    br.refill();
+    at = br.bitpos();
+    if (WRITE ? (blk >= need || (at >= stop && !tail)) : at >= stop) break;
+    int c = f.ncomp == 1 ? 0 : (b < nb0 ? 0 : b - nb0 + 1);
+    c = c > 2 ? 2 : c;
+    const bool is_dc = k == 0;
+    int sym = interval_symbol(br, is_dc ? dc[c] : ac[c]);
+    bool err = false;
+    if (sym < 0) { br.skip(16); sym = 0; err = true; }
+    if (is_dc && sym > 15) err = true;
+    const int sz = sym & 15;
+    int v = 0;
+    if (sz) {
+      v = (int)br.peek(sz);
+      br.skip(sz);
+      v = v < (1 << (sz - 1)) ? v - (1 << sz) + 1 : v;   // HUFF_EXTEND
+    }
+    if (is_dc) {
+      if (WRITE) coef[addr] = (int16_t)v;                // the difference; jpeg_sync_dc_kernel sums
+      k = 1;
+    } else {
+      const int r = sym >> 4;
+      if (sz == 0) {
+        k = r == 15 ? k + 16 : 64;                       // ZRL / EOB
+      } else {
+        k += r;
+        if (k > 63) { err = true; k = 64; }
+        else { if (WRITE) coef[addr + zigzag[k]] = (int16_t)v; ++k; }
+      }
+    }
+    if (WRITE && err) *bad = 1;
+    if (k >= 64) {                                       // next block of the MCU / next MCU
+      k = 0;
+      ++n;
+      if (++b >= per_mcu) b = 0;
+      if (WRITE) {
+        ++blk;
+        if (++bb == per_mcu) {
+          bb = 0;
+          if (++mx == d.mcus_x) { mx = 0; ++my; }
+        }
+        if (blk < need) addr = block_addr();
+      }
+    }
+  }
+  if (n_out) *n_out = n;
+  return sync_pack(at, b, k);
+}
+
+struct SyncSub {                  // where subsequence i of a page sits
+  uint32_t begin, end;            // its interval's data (file offsets; `end` = the first marker)
+  uint32_t lo, stop;              // its first byte; symbols that start before bit `stop` are its own
+  uint32_t first_sub, next_sub;   // the interval's first subsequence, the next interval's first subsequence
+  uint32_t need;                  // blocks of the interval
+  int first_mcu;
+  bool first, last;
+};
+
+// bounds / sub_first: the PAGE's interval pairs and first-subsequence indices.  Every loop bounded by n_intervals.
+HD SyncSub sync_locate(const ScanDesc& d, const uint32_t* bounds, const uint32_t* sub_first, uint32_t nsub, uint32_t S, uint32_t i) {
+  int lo = 0, hi = d.n_intervals - 1;
+  while (lo < hi) {                                      // last interval whose first subsequence is <= i
+    const int mid = (lo + hi + 1) >> 1;
+    if (sub_first[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  SyncSub q;
+  q.first_sub = sub_first[lo];
+  q.next_sub = lo + 1 < d.n_intervals ? sub_first[lo + 1] : nsub;
+  q.begin = bounds[2 * lo];
+  q.end = bounds[2 * lo + 1];
+  q.first = i == q.first_sub;
+  q.last = i + 1 == q.next_sub;
+  const uint64_t from = (uint64_t)q.begin + (uint64_t)(i - q.first_sub) * S;
+  q.lo = from < q.end ? (uint32_t)from : q.end;
+  q.stop = (q.last || from + S > q.end ? q.end : (uint32_t)(from + S)) * 8u;
+  const int total = d.mcus_x * d.mcus_y, per_mcu = d.info.ncomp == 3 ? d.info.hs[0] * d.info.vs[0] + 2 : 1;
+  q.first_mcu = lo * d.restart_interval;
+  const int n_mcu = total - q.first_mcu < d.restart_interval ? total - q.first_mcu : d.restart_interval;
+  q.need = n_mcu > 0 ? (uint32_t)n_mcu * (uint32_t)per_mcu : 0u;
+  return q;
+}
+
+// One subsequence in one round.  entry / ex_in / ex_out / cnt: the page's arrays.  Returns 1 when it decoded again.
+HD int sync_round(const ScanDesc& d, const DevTable* dc, const DevTable* ac, const uint8_t* zigzag, const uint8_t* bytes,
+                  const uint32_t* bounds, const uint32_t* sub_first, uint32_t nsub, uint32_t S, uint32_t i, int round,
+                  uint64_t* entry, const uint64_t* ex_in, uint64_t* ex_out, uint32_t* cnt) {
+  const SyncSub q = sync_locate(d, bounds, sub_first, nsub, S, i);
+  uint64_t e;
+  if (round == 0) {
+    // the true state at the head of an interval; elsewhere the first whole bit of the subsequence, (block 0, k 0) — behind the
+    // stuffed 0x00 when the previous byte is a 0xFF
+    uint32_t p = q.lo;
+    if (!q.first && p > q.begin && p < q.end && bytes[p - 1] == 0xFF) ++p;
+    e = sync_pack(p * 8u, 0, 0);
+  } else {
+    if (q.first || i == 0) { ex_out[i] = ex_in[i]; return 0; }
+    e = ex_in[i - 1];
+    if (e == entry[i]) { ex_out[i] = ex_in[i]; return 0; }
+  }
+  entry[i] = e;
+  uint32_t n = 0;
+  ex_out[i] = sync_decode<false>(d, dc, ac, zigzag, bytes, q.end, e, q.stop, false, 0, 0, 0, nullptr, &n, nullptr);
+  cnt[i] = n;
+  return 1;
+}
+
+// One subsequence in the write pass; P = the page's exclusive prefix sums of cnt (nsub + 1 entries).  Returns the page status this
+// subsequence asks for: 0, 1 (the true chain met what a valid stream cannot hold) or 2 (the data ends with more than
+// kSyncTailBlocks blocks of the interval outstanding: a truncated stream, left to the serial decoder).
+HD int sync_write(const ScanDesc& d, const DevTable* dc, const DevTable* ac, const uint8_t* zigzag, const uint8_t* bytes,
+                  const uint32_t* bounds, const uint32_t* sub_first, uint32_t nsub, uint32_t S, uint32_t i, const uint64_t* entry,
+                  const uint32_t* P, int16_t* coef) {
+  const SyncSub q = sync_locate(d, bounds, sub_first, nsub, S, i);
+  if (q.first_sub > i || q.next_sub > nsub || q.next_sub <= i) return 1;   // not what the prepare step lays out
+  const uint32_t base = P[q.first_sub], blk0 = P[i] - base, done = P[q.next_sub] - base;
+  bool tail = false;
+  if (q.last && done < q.need) {
+    if (q.need - done > kSyncTailBlocks) return 2;
+    tail = true;
+  }
+  if (blk0 >= q.need) return 0;
+  int bad = 0;
+  sync_decode<true>(d, dc, ac, zigzag, bytes, q.end, entry[i], q.stop, tail, blk0, q.need, q.first_mcu, coef, nullptr, &bad);
+  return bad;
+}
+
+// rounds taken and the verdict "no fixed point" of one page: `changed` = the page's flag of every round
+HD int sync_rounds_taken(const int32_t* changed, int stride, int max_rounds, uint32_t nsub, int* declined) {
+  *declined = 0;
+  for (int r = 1; r < max_rounds; ++r)
+    if (changed[(int64_t)r * stride] == 0) return r;     // round r decoded nothing again: the fixed point stood after round r - 1
+  if ((uint32_t)max_rounds < nsub) *declined = 1;        // (subsequence r is final after round r: max_rounds >= nsub needs no proof)
+  return max_rounds;
+}
+
+HD int64_t sync_dc_addr(const ScanDesc& d, int c, uint32_t e) {   // element e of component c in scan order -> its DC coefficient
+  const msocr_jpeg_info& f = d.info;
+  const uint32_t bpm = (uint32_t)(f.hs[c] * f.vs[c]);
+  const uint32_t mcu = e / bpm, j = e - mcu * bpm;
+  const int by = (int)(j / (uint32_t)f.hs[c]), bx = (int)j - by * f.hs[c];
+  const int my = (int)(mcu / (uint32_t)d.mcus_x), mx = (int)mcu - my * d.mcus_x;
+  return f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+}
+
+struct SyncWorkspace {
+  uint64_t *entry, *ex[2];
+  uint32_t *P, *cnt;
+  int32_t* changed;
+};
+// byte offsets of the six arrays inside the workspace; returns its size
+int64_t sync_layout(int64_t total_subseq, int32_t n_pages, int32_t max_rounds, int64_t off[6]) {
+  int64_t o = 0;
+  off[0] = o; o += 8 * total_subseq;                       // entry
+  off[1] = o; o += 8 * total_subseq;                       // exit states, even rounds
+  off[2] = o; o += 8 * total_subseq;                       // exit states, odd rounds
+  off[3] = o; o += 4 * (total_subseq + n_pages);           // P: one more entry than subsequences per page
+  off[4] = o; o += 4 * total_subseq;                       // cnt
+  off[5] = o; o += 4 * (int64_t)max_rounds * n_pages;      // changed[round][page]
+  return (o + 15) / 16 * 16;
+}
+SyncWorkspace sync_workspace(void* base, int64_t total_subseq, int32_t n_pages, int32_t max_rounds) {
+  int64_t off[6];
+  sync_layout(total_subseq, n_pages, max_rounds, off);
+  uint8_t* p = static_cast<uint8_t*>(base);
+  SyncWorkspace w;
+  w.entry = reinterpret_cast<uint64_t*>(p + off[0]);
+  w.ex[0] = reinterpret_cast<uint64_t*>(p + off[1]);
+  w.ex[1] = reinterpret_cast<uint64_t*>(p + off[2]);
+  w.P = reinterpret_cast<uint32_t*>(p + off[3]);
+  w.cnt = reinterpret_cast<uint32_t*>(p + off[4]);
+  w.changed = reinterpret_cast<int32_t*>(p + off[5]);
+  return w;
+}
+
+struct SyncArgs {                 // what every kernel of the sequence takes
+  const uint8_t* bytes;
+  const ScanDesc* descs;
+  const uint32_t *bounds, *sub_first;
+  const int64_t* page_base;       // [n_pages][4]: coefficient base, first interval, first subsequence (batch-wide), subsequences
+  uint32_t S;
+  int32_t n_pages, max_rounds;
+  SyncWorkspace w;
+};
+
+__device__ __forceinline__ void sync_stage_tables(const ScanDesc& d, DevTable* s_dc, DevTable* s_ac, uint8_t* s_zz) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(d.dc);
+  uint32_t* d0 = reinterpret_cast<uint32_t*>(s_dc);
+  uint32_t* d1 = reinterpret_cast<uint32_t*>(s_ac);
+  constexpr int W = (int)(3 * sizeof(DevTable) / 4);
+  for (int i = threadIdx.x; i < W; i += 256) { d0[i] = src[i]; d1[i] = src[W + i]; }
+  if (threadIdx.x < 64) s_zz[threadIdx.x] = d.zigzag[threadIdx.x];
+  __syncthreads();
+}
+
+// grid (subsequences of the longest page / 256, pages)
+__global__ __launch_bounds__(256) void jpeg_sync_round_kernel(SyncArgs a, int round) {
+  __shared__ DevTable s_dc[3], s_ac[3];
+  __shared__ uint8_t s_zz[64];
+  const int pg = blockIdx.y;
+  const int64_t* pb = a.page_base + 4 * pg;
+  const uint32_t nsub = (uint32_t)pb[3];
+  if (blockIdx.x * 256u >= nsub) return;                                        // uniform
+  if (round >= 2 && a.w.changed[(int64_t)(round - 1) * a.n_pages + pg] == 0) return;   // uniform: the page stands
+  const ScanDesc& d = a.descs[pg];
+  sync_stage_tables(d, s_dc, s_ac, s_zz);
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= nsub) return;
+  const int64_t sb = pb[2];
+  const int ch = sync_round(d, s_dc, s_ac, s_zz, a.bytes + d.bytes_base, a.bounds + 2 * pb[1], a.sub_first + pb[1], nsub, a.S, i, round,
+                            a.w.entry + sb, a.w.ex[(round + 1) & 1] + sb, a.w.ex[round & 1] + sb, a.w.cnt + sb);
+  if (ch && round >= 1) a.w.changed[(int64_t)round * a.n_pages + pg] = 1;
+}
+
+// one workgroup per page: exclusive prefix sum of cnt -> P (nsub + 1 entries per page, page p's at first subsequence + p), the
+// rounds taken, and status 2 for a page whose rounds did not reach the fixed point
+__global__ __launch_bounds__(256) void jpeg_sync_place_kernel(SyncArgs a, int32_t* __restrict__ status, int32_t* __restrict__ rounds) {
+  __shared__ uint32_t s_sum[256];
+  const int pg = blockIdx.x, tid = threadIdx.x;
+  const int64_t* pb = a.page_base + 4 * pg;
+  const uint32_t nsub = (uint32_t)pb[3];
+  const uint32_t* cnt = a.w.cnt + pb[2];
+  uint32_t* P = a.w.P + pb[2] + pg;
+  if (tid == 0) {
+    int declined;
+    const int r = sync_rounds_taken(a.w.changed + pg, a.n_pages, a.max_rounds, nsub, &declined);
+    if (rounds) rounds[pg] = r;
+    if (declined) status[pg] = 2;
+  }
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < nsub; base += 2048) {
+    uint32_t v[8], sum = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t i = base + tid * 8 + j;
+      v[j] = i < nsub ? cnt[i] : 0;
+      sum += v[j];
+    }
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+      const uint32_t t = tid >= off ? s_sum[tid - off] : 0;
+      __syncthreads();
+      s_sum[tid] += t;
+      __syncthreads();
+    }
+    uint32_t run = carry + s_sum[tid] - sum;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t i = base + tid * 8 + j;
+      if (i < nsub) P[i] = run;
+      run += v[j];
+    }
+    carry += s_sum[255];
+    __syncthreads();
+  }
+  if (tid == 0) P[nsub] = carry;
+}
+
+__global__ __launch_bounds__(256) void jpeg_sync_write_kernel(SyncArgs a, int16_t* __restrict__ coef, int32_t* __restrict__ status) {
+  __shared__ DevTable s_dc[3], s_ac[3];
+  __shared__ uint8_t s_zz[64];
+  const int pg = blockIdx.y;
+  const int64_t* pb = a.page_base + 4 * pg;
+  const uint32_t nsub = (uint32_t)pb[3];
+  if (blockIdx.x * 256u >= nsub) return;            // uniform
+  if (status[pg] == 2) return;                      // no fixed point (set by the place kernel, a launch ago): nothing to write
+  const ScanDesc& d = a.descs[pg];
+  sync_stage_tables(d, s_dc, s_ac, s_zz);
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= nsub) return;
+  const int st = sync_write(d, s_dc, s_ac, s_zz, a.bytes + d.bytes_base, a.bounds + 2 * pb[1], a.sub_first + pb[1], nsub, a.S, i,
+                            a.w.entry + pb[2], a.w.P + pb[2] + pg, coef + pb[0]);
+  if (st) atomicMax(&status[pg], st);
+}
+
+// grid (3 components, pages): segmented inclusive scan of the DC differences in scan order, 2048 elements per step, carried on
+__global__ __launch_bounds__(256) void jpeg_sync_dc_kernel(SyncArgs a, int16_t* __restrict__ coef_all) {
+  __shared__ uint32_t s_v[256], s_f[256];
+  const int pg = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
+  const ScanDesc& d = a.descs[pg];
+  if (c >= d.info.ncomp) return;
+  int16_t* coef = coef_all + a.page_base[4 * pg];
+  const uint32_t bpm = (uint32_t)(d.info.hs[c] * d.info.vs[c]);
+  const uint32_t L = (uint32_t)(d.mcus_x * d.mcus_y) * bpm, seg = d.restart_interval > 0 ? (uint32_t)d.restart_interval * bpm : L;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < L; base += 2048) {
+    uint32_t loc[8], run = 0, flag = 0;
+    int first_reset = 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t e = base + tid * 8 + j;
+      if (e < L) {
+        if (e % seg == 0) { run = 0; if (!flag) { flag = 1; first_reset = j; } }
+        run += (uint32_t)(int32_t)coef[sync_dc_addr(d, c, e)];
+      }
+      loc[j] = run;
+    }
+    s_v[tid] = run; s_f[tid] = flag;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {       // inclusive scan of (flag, value): a flag cuts what comes from the left
+      uint32_t v = s_v[tid], fl = s_f[tid];
+      if (tid >= off) { if (!fl) v += s_v[tid - off]; fl |= s_f[tid - off]; }
+      __syncthreads();
+      s_v[tid] = v; s_f[tid] = fl;
+      __syncthreads();
+    }
+    const uint32_t left = tid ? (s_f[tid - 1] ? s_v[tid - 1] : s_v[tid - 1] + carry) : carry;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t e = base + tid * 8 + j;
+      if (e < L) coef[sync_dc_addr(d, c, e)] = (int16_t)(loc[j] + (j < first_reset ? left : 0u));
+    }
+    const uint32_t next = s_f[255] ? s_v[255] : s_v[255] + carry;
+    __syncthreads();
+    carry = next;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------- reconstruction
@@ -736,16 +1165,21 @@ extern "C" int64_t msocr_jpeg_scan_desc_bytes(void) { return (int64_t)sizeof(Sca
 
 // Walks the entropy-coded segment exactly as entropy_decode's restart handling does: interval k ends at the first marker (0xFF not
 // followed by 0x00) at or after its start, interval k + 1 starts behind the first RSTn at or after that marker.
-extern "C" int64_t msocr_jpeg_scan_prepare_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base,
-                                                void* desc_out, uint32_t* bounds_out, int64_t bounds_cap) {
+// `serial_too`: a stream without DRI is taken as ONE interval of all its MCUs (the self-synchronising stage's view of it)
+static int64_t scan_prepare(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base, void* desc_out,
+                            uint32_t* bounds_out, int64_t bounds_cap, bool serial_too) {
   if (!data_host || !info || !desc_out || !bounds_out || bytes_base < 0) return MSOCR_E_ARG;
   Parsed P;
   if (parse(data_host, len, &P) != MSOCR_OK) return MSOCR_E_ARG;
   if (P.info.width != info->width || P.info.height != info->height || P.info.ncomp != info->ncomp ||
       P.info.coef_total != info->coef_total) return MSOCR_E_ARG;
-  if (P.restart_interval <= 0) return MSOCR_E_ARG;                       // one serial bit stream: the host decodes it
-  if (len > 0xfffffff0LL) return MSOCR_E_ARG;                            // interval bounds are 32-bit offsets into the file
   const int64_t total = (int64_t)P.mcus_x * P.mcus_y;
+  if (P.restart_interval <= 0) {
+    if (!serial_too || total > 0x7fffffff) return MSOCR_E_ARG;           // one serial bit stream: not the per-interval kernel's
+    P.restart_interval = (int)total;
+  }
+  // interval bounds are 32-bit offsets into the file; the self-synchronising stage keeps BIT positions in 32 bits
+  if (len > (serial_too ? 0x1ff00000LL : 0xfffffff0LL)) return MSOCR_E_ARG;
   const int64_t n_iv = (total + P.restart_interval - 1) / P.restart_interval;
   if (n_iv > bounds_cap || n_iv > 0x7fffffff) return MSOCR_E_ARG;
   ScanDesc* d = static_cast<ScanDesc*>(desc_out);
@@ -779,6 +1213,16 @@ extern "C" int64_t msocr_jpeg_scan_prepare_host(const uint8_t* data_host, int64_
     }
   }
   return n_iv;
+}
+
+extern "C" int64_t msocr_jpeg_scan_prepare_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base,
+                                                void* desc_out, uint32_t* bounds_out, int64_t bounds_cap) {
+  return scan_prepare(data_host, len, info, bytes_base, desc_out, bounds_out, bounds_cap, false);
+}
+
+extern "C" int64_t msocr_jpeg_sync_prepare_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base,
+                                                void* desc_out, uint32_t* bounds_out, int64_t bounds_cap) {
+  return scan_prepare(data_host, len, info, bytes_base, desc_out, bounds_out, bounds_cap, true);
 }
 
 extern "C" int msocr_jpeg_entropy_decode_device(const uint8_t* bytes_dev, const void* descs_dev, int32_t n_pages, int32_t max_intervals,
@@ -821,6 +1265,104 @@ extern "C" int msocr_jpeg_entropy_decode_intervals_host(const uint8_t* bytes_hos
       if (decode_interval(d.info, d.mcus_x, d.dc, d.ac, d.zigzag, bytes_host + d.bytes_base, bounds_host[2 * (first_interval + iv)],
                           bounds_host[2 * (first_interval + iv) + 1], first, n, coef_host + coef_base))
         status_host[pg] = 1;
+    }
+  }
+  return MSOCR_OK;
+}
+
+extern "C" int64_t msocr_jpeg_sync_workspace_bytes(int64_t total_subseq, int32_t n_pages, int32_t max_rounds) {
+  if (total_subseq <= 0 || n_pages <= 0 || max_rounds < 2 || max_rounds > 65536) return -1;
+  int64_t off[6];
+  return sync_layout(total_subseq, n_pages, max_rounds, off);
+}
+
+static bool sync_args_ok(const void* bytes, const void* descs, int32_t n_pages, const void* bounds, const void* sub_first,
+                         const void* page_base, int64_t total_subseq, int32_t subseq_bytes, int32_t max_rounds, const void* coef,
+                         int64_t coef_total, const void* status, const void* workspace) {
+  return bytes && descs && bounds && sub_first && page_base && coef && status && workspace && n_pages > 0 && n_pages <= 65535 &&
+         total_subseq > 0 && subseq_bytes >= 16 && subseq_bytes <= 65536 && max_rounds >= 2 && max_rounds <= 65536 && coef_total > 0 &&
+         !(((uintptr_t)descs | (uintptr_t)page_base | (uintptr_t)workspace) & 7);
+}
+
+extern "C" int msocr_jpeg_entropy_decode_sync_device(const uint8_t* bytes_dev, const void* descs_dev, int32_t n_pages,
+                                                     const uint32_t* bounds_dev, const uint32_t* sub_first_dev,
+                                                     const int64_t* page_base_dev, int32_t max_subseq, int64_t total_subseq,
+                                                     int32_t subseq_bytes, int32_t max_rounds, int16_t* coef_dev, int64_t coef_total,
+                                                     int32_t* status_dev, int32_t* rounds_dev, void* workspace_dev, void* stream) {
+  if (!sync_args_ok(bytes_dev, descs_dev, n_pages, bounds_dev, sub_first_dev, page_base_dev, total_subseq, subseq_bytes, max_rounds,
+                    coef_dev, coef_total, status_dev, workspace_dev) || max_subseq <= 0 || max_subseq > total_subseq)
+    return MSOCR_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  SyncArgs a;
+  a.bytes = bytes_dev; a.descs = static_cast<const ScanDesc*>(descs_dev); a.bounds = bounds_dev; a.sub_first = sub_first_dev;
+  a.page_base = page_base_dev; a.S = (uint32_t)subseq_bytes; a.n_pages = n_pages; a.max_rounds = max_rounds;
+  a.w = sync_workspace(workspace_dev, total_subseq, n_pages, max_rounds);
+  if (hipMemsetAsync(coef_dev, 0, (size_t)coef_total * sizeof(int16_t), s) != hipSuccess) return MSOCR_E_LAUNCH;
+  if (hipMemsetAsync(status_dev, 0, (size_t)n_pages * sizeof(int32_t), s) != hipSuccess) return MSOCR_E_LAUNCH;
+  if (hipMemsetAsync(a.w.changed, 0, (size_t)max_rounds * n_pages * sizeof(int32_t), s) != hipSuccess) return MSOCR_E_LAUNCH;
+  const dim3 grid((unsigned)((max_subseq + 255) / 256), (unsigned)n_pages);
+  // a fixed number of rounds, nobody waits in between: the kernels of a page that stands return at once
+  for (int r = 0; r < max_rounds; ++r) MSOCR_LAUNCH(jpeg_sync_round_kernel, grid, dim3(256), 0, s, a, r);
+  MSOCR_LAUNCH(jpeg_sync_place_kernel, dim3((unsigned)n_pages), dim3(256), 0, s, a, status_dev, rounds_dev);
+  MSOCR_LAUNCH(jpeg_sync_write_kernel, grid, dim3(256), 0, s, a, coef_dev, status_dev);
+  MSOCR_LAUNCH(jpeg_sync_dc_kernel, dim3(3, (unsigned)n_pages), dim3(256), 0, s, a, coef_dev);
+  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+}
+
+// HOST twin of the kernel sequence: the same rounds (double-buffered exit states, a page stops when a round changed nothing), the
+// same prefix sums, write pass and DC sums, subsequence after subsequence (all pointers host memory; no workspace).
+extern "C" int msocr_jpeg_entropy_decode_sync_host(const uint8_t* bytes_host, const void* descs_host, int32_t n_pages,
+                                                   const uint32_t* bounds_host, const uint32_t* sub_first_host,
+                                                   const int64_t* page_base_host, int32_t subseq_bytes, int32_t max_rounds,
+                                                   int16_t* coef_host, int64_t coef_total, int32_t* status_host, int32_t* rounds_host) {
+  int64_t dummy[1];
+  if (!sync_args_ok(bytes_host, descs_host, n_pages, bounds_host, sub_first_host, page_base_host, 1, subseq_bytes, max_rounds, coef_host,
+                    coef_total, status_host, dummy))
+    return MSOCR_E_ARG;
+  memset(coef_host, 0, (size_t)coef_total * sizeof(int16_t));
+  const ScanDesc* descs = static_cast<const ScanDesc*>(descs_host);
+  const uint32_t S = (uint32_t)subseq_bytes;
+  for (int pg = 0; pg < n_pages; ++pg) {
+    const ScanDesc& d = descs[pg];
+    const int64_t* pb = page_base_host + 4 * pg;
+    status_host[pg] = 0;
+    if (pb[0] < 0 || pb[0] + d.info.coef_total > coef_total || pb[1] < 0 || pb[3] <= 0 || pb[3] > 0x7fffffff || d.n_intervals <= 0)
+      return MSOCR_E_ARG;
+    const uint32_t nsub = (uint32_t)pb[3];
+    const uint8_t* bytes = bytes_host + d.bytes_base;
+    const uint32_t *bounds = bounds_host + 2 * pb[1], *sub_first = sub_first_host + pb[1];
+    std::vector<uint64_t> entry(nsub), ex0(nsub), ex1(nsub);
+    std::vector<uint32_t> cnt(nsub), P((size_t)nsub + 1);
+    std::vector<int32_t> changed((size_t)max_rounds, 0);
+    uint64_t* ex[2] = {ex0.data(), ex1.data()};
+    for (int r = 0; r < max_rounds; ++r) {
+      if (r >= 2 && !changed[r - 1]) break;
+      for (uint32_t i = 0; i < nsub; ++i)
+        if (sync_round(d, d.dc, d.ac, d.zigzag, bytes, bounds, sub_first, nsub, S, i, r, entry.data(), ex[(r + 1) & 1], ex[r & 1], cnt.data()) &&
+            r >= 1)
+          changed[r] = 1;
+    }
+    int declined;
+    const int rounds = sync_rounds_taken(changed.data(), 1, max_rounds, nsub, &declined);
+    if (rounds_host) rounds_host[pg] = rounds;
+    if (declined) { status_host[pg] = 2; continue; }
+    P[0] = 0;
+    for (uint32_t i = 0; i < nsub; ++i) P[i + 1] = P[i] + cnt[i];
+    int16_t* coef = coef_host + pb[0];
+    for (uint32_t i = 0; i < nsub; ++i) {
+      const int st = sync_write(d, d.dc, d.ac, d.zigzag, bytes, bounds, sub_first, nsub, S, i, entry.data(), P.data(), coef);
+      if (st > status_host[pg]) status_host[pg] = st;
+    }
+    for (int c = 0; c < d.info.ncomp; ++c) {
+      const uint32_t bpm = (uint32_t)(d.info.hs[c] * d.info.vs[c]);
+      const uint32_t L = (uint32_t)(d.mcus_x * d.mcus_y) * bpm, seg = d.restart_interval > 0 ? (uint32_t)d.restart_interval * bpm : L;
+      uint32_t run = 0;
+      for (uint32_t e = 0; e < L; ++e) {
+        if (e % seg == 0) run = 0;
+        const int64_t at = sync_dc_addr(d, c, e);
+        run += (uint32_t)(int32_t)coef[at];
+        coef[at] = (int16_t)run;
+      }
     }
   }
   return MSOCR_OK;

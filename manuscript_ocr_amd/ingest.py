@@ -1,11 +1,13 @@
 """Image ingest on the device: JPEG file -> RGB u8 tensor in HBM (msocr_jpeg_* of libmsocr.so, csrc/jpeg.hip).
 
 Replaces the file branch of the reference's read_image (detectors/_east/utils.py:477-497: cv2.imread + BGR->RGB, PIL
-fallback — both libjpeg-turbo with default settings).  Files written with a restart interval (DRI) are decoded entirely on
-the MI355X — the file's bytes are uploaded as they are and one thread per interval runs the Huffman stage
-(`entropy_batch_device`); for the others the serial Huffman decode runs on the host.  Dequantisation, inverse DCT, chroma
-upsampling and colour conversion always run on the device, so the decoded page (9.4 MB at 2048x1536, 69 MB for the
-reference's 5390x4250 example page) is produced in HBM instead of crossing PCIe.
+fallback — both libjpeg-turbo with default settings).  The file's bytes are uploaded as they are and the Huffman stage runs on
+the MI355X: one thread per restart interval for files written with short restart intervals (`entropy_batch_device`), the
+self-synchronising decode of a serial segment for files without restart markers and for long intervals
+(`entropy_sync_batch_device`); the serial host decoder on a thread pool is the other route (`read_images_device` has the table of
+which file takes which by default).  Dequantisation, inverse DCT, chroma upsampling and colour conversion always run on the
+device, so the decoded page (9.4 MB at 2048x1536, 69 MB for the reference's 5390x4250 example page) is produced in HBM instead of
+crossing PCIe.
 Formats outside the kernel's scope (progressive, CMYK, 12-bit, PNG, ...) return None: callers fall back to read_image.
 """
 import ctypes
@@ -50,7 +52,8 @@ def decode_jpeg_host(data: bytes):
 
 def decode_jpeg_device(data: bytes, device="cuda", device_entropy=True):
     """JPEG bytes -> [H, W, 3] u8 tensor on the device (current stream), or None when the stream is not supported.  A stream with
-    a restart interval takes the device Huffman stage (`device_entropy=False`: the host decoder, as for all other streams)."""
+    a restart interval takes the per-interval Huffman kernel, one without the self-synchronising stage (a stream that stage
+    declines, status 2, goes on to the host decoder); `device_entropy=False`: the host decoder for every stream."""
     import torch
 
     from . import ops
@@ -63,6 +66,12 @@ def decode_jpeg_device(data: bytes, device="cuda", device_entropy=True):
             coef, status = entropy_batch_device(batch, device)
             img = _reconstruct(info, coef, device, torch, ops)
             return img if int(status.cpu()[0]) == 0 else None
+        batch = SyncBatch([(info, buf, len(data))])
+        if batch.n_pages:
+            coef, status, _ = entropy_sync_batch_device(batch, device)
+            st = int(status.cpu()[0])
+            if st != 2:
+                return _reconstruct(info, coef, device, torch, ops) if st == 0 else None
     coef = np.empty(int(info.coef_total), dtype=np.int16)
     if nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data) != 0:
         return None
@@ -151,6 +160,114 @@ def entropy_batch_device(batch: ScanBatch, device="cuda", bytes_dev=None):
     return coef, status
 
 
+SYNC_SUBSEQ_BYTES = 256    # a few times the distance page-like streams need to fall into step
+SYNC_MAX_ROUNDS = 16
+SYNC_MAX_FILE = 0x1ff00000  # the stage keeps bit positions in 32 bits
+# Default route (device_entropy=None) of streams without a restart interval and of intervals longer than
+# MSOCR_JPEG_DEVICE_MAX_INTERVAL: the self-synchronising stage when True, the host pool when False.  True by the measurement in
+# profiles/jpeg_sync_huffman.txt: 6.4-7.0 ms per batch of 16 pages against 14.9-18.1 ms for the host pool.
+SYNC_BY_DEFAULT = True
+
+
+def _prepare_sync(ptr, n, info, bytes_base):
+    """`_prepare` for the self-synchronising stage: a stream without a restart interval is one interval of all its MCUs."""
+    lib = nat.lib()
+    mcus = (int(info.blocks_w[0]) // int(info.hs[0])) * (int(info.blocks_h[0]) // int(info.vs[0]))
+    d = np.zeros(int(lib.msocr_jpeg_scan_desc_bytes()), dtype=np.uint8)
+    b = np.empty(2 * mcus, dtype=np.uint32)
+    niv = int(lib.msocr_jpeg_sync_prepare_host(ptr, n, ctypes.byref(info), bytes_base, d.ctypes.data, b.ctypes.data, mcus))
+    return None if niv <= 0 else (d, b[: 2 * niv])
+
+
+class SyncBatch:
+    """`ScanBatch` for the self-synchronising Huffman stage (msocr_jpeg_entropy_decode_sync_device): takes streams with and without
+    a restart interval and lays out, beside descriptors / interval bounds / bytes, the subsequences of `subseq_bytes` bytes every
+    interval is cut into (`sub_first`, `page_base` [n_pages][4], `max_subseq`, `total_subseq`).  `pages[i]` = index into `descs` of
+    stream i, or -1 (a marker sequence the host decoder must judge, a file too large for 32-bit bit positions)."""
+
+    def __init__(self, parsed, prepared=None, bytes_=None, subseq_bytes=SYNC_SUBSEQ_BYTES):
+        self.pages, self.infos = [], []
+        self.subseq_bytes = int(subseq_bytes)
+        descs, bounds, sub_first, chunks, base = [], [], [], [], []
+        pos = coef_base = first = sub_base = 0
+        self.max_subseq = 0
+        for i, pr in enumerate(parsed):
+            r = None
+            if pr is not None and pr[2] <= SYNC_MAX_FILE:
+                info, buf, n = pr
+                r = prepared[i] if prepared is not None else _prepare_sync(ctypes.addressof(buf), n, info, pos)
+            if r is None:
+                self.pages.append(-1)
+                continue
+            self.pages.append(len(descs))
+            self.infos.append((info, coef_base))
+            descs.append(r[0])
+            bounds.append(r[1])
+            length = r[1][1::2].astype(np.int64) - r[1][0::2].astype(np.int64)
+            nsub = np.maximum(1, -(-length // self.subseq_bytes))
+            sub_first.append((np.cumsum(nsub) - nsub).astype(np.uint32))
+            nsub = int(nsub.sum())
+            base.append((coef_base, first, sub_base, nsub))
+            if prepared is None:
+                chunks.append(np.frombuffer(buf, dtype=np.uint8, count=n))
+                pad = (-n) % 16
+                if pad:
+                    chunks.append(np.zeros(pad, dtype=np.uint8))
+                pos += n + pad
+            coef_base += int(info.coef_total)
+            first += len(r[1]) // 2
+            sub_base += nsub
+            self.max_subseq = max(self.max_subseq, nsub)
+        self.n_pages = len(descs)
+        self.coef_total = coef_base
+        self.total_subseq = sub_base
+        if self.n_pages:
+            self.descs = np.stack(descs)
+            self.bounds = np.concatenate(bounds)
+            self.sub_first = np.concatenate(sub_first)
+            self.page_base = np.array(base, dtype=np.int64)
+            self.bytes = bytes_ if prepared is not None else np.concatenate(chunks)
+
+
+def entropy_sync_batch_host_twin(batch: SyncBatch, max_rounds=SYNC_MAX_ROUNDS):
+    """The self-synchronising stage on the CPU, same rounds and passes as the kernels (tests; not a product path)
+    -> (int16 coefficients of the batch, status [n_pages] 0 / 1 / 2, rounds taken [n_pages])."""
+    coef = np.empty(batch.coef_total, dtype=np.int16)
+    status = np.empty(batch.n_pages, dtype=np.int32)
+    rounds = np.empty(batch.n_pages, dtype=np.int32)
+    nat.check(nat.lib().msocr_jpeg_entropy_decode_sync_host(batch.bytes.ctypes.data, batch.descs.ctypes.data, batch.n_pages,
+                                                             batch.bounds.ctypes.data, batch.sub_first.ctypes.data,
+                                                             batch.page_base.ctypes.data, batch.subseq_bytes, int(max_rounds),
+                                                             coef.ctypes.data, batch.coef_total, status.ctypes.data, rounds.ctypes.data),
+              "jpeg_entropy_decode_sync_host")
+    return coef, status, rounds
+
+
+def entropy_sync_batch_device(batch: SyncBatch, device="cuda", bytes_dev=None, max_rounds=SYNC_MAX_ROUNDS):
+    """`entropy_batch_device` for a SyncBatch: uploads and queues the kernel sequence of the self-synchronising stage on the current
+    stream -> (int16 coefficient tensor, int32 status tensor [n_pages]: 0 / 1 = bad stream / 2 = declined, take the host decoder,
+    int32 tensor of the rounds taken [n_pages]); nothing is waited for."""
+    import torch
+
+    from . import ops
+    up = lambda a: torch.from_numpy(a).to(device)
+    if bytes_dev is None:
+        bytes_dev = torch.from_numpy(batch.bytes).pin_memory().to(device, non_blocking=True)
+    descs_dev, bounds_dev, sub_dev, base_dev = up(batch.descs), up(batch.bounds), up(batch.sub_first), up(batch.page_base)
+    coef = torch.empty(batch.coef_total, dtype=torch.int16, device=device)
+    status = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
+    rounds = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
+    lib = nat.lib()
+    ws = torch.empty(int(lib.msocr_jpeg_sync_workspace_bytes(batch.total_subseq, batch.n_pages, int(max_rounds))), dtype=torch.uint8,
+                     device=device)
+    nat.check(lib.msocr_jpeg_entropy_decode_sync_device(bytes_dev.data_ptr(), descs_dev.data_ptr(), batch.n_pages, bounds_dev.data_ptr(),
+                                                        sub_dev.data_ptr(), base_dev.data_ptr(), batch.max_subseq, batch.total_subseq,
+                                                        batch.subseq_bytes, int(max_rounds), coef.data_ptr(), batch.coef_total,
+                                                        status.data_ptr(), rounds.data_ptr(), ws.data_ptr(), ops._stream()),
+              "jpeg_entropy_decode_sync_device")
+    return coef, status, rounds
+
+
 def _reconstruct(info, coef_dev, device, torch, ops):
     ws = torch.empty((nat.lib().msocr_jpeg_workspace_bytes(ctypes.byref(info)),), dtype=torch.uint8, device=device)
     img = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
@@ -185,7 +302,8 @@ def _slot_buffer(slot, n, torch, dtype=None):
 
 
 def _load(path, arr, off, n, want_device):
-    """Worker: file -> its slice of the pinned batch buffer, header parse, marker walk.  -> (info, prepared or None) or None."""
+    """Worker: file -> its slice of the pinned batch buffer, header parse, marker walk.
+    -> (info, `_prepare` result or None, `_prepare_sync` result of a stream without restart interval or None) or None."""
     try:
         with open(path, "rb") as f:
             if f.readinto(memoryview(arr[off: off + n])) != n:
@@ -198,13 +316,17 @@ def _load(path, arr, off, n, want_device):
     ptr = arr.ctypes.data + off
     if nat.lib().msocr_jpeg_parse_host(ptr, n, ctypes.byref(info)) != 0 or not info.supported:
         return None
-    return info, (_prepare(ptr, n, info, off) if want_device else None)
+    if not want_device:
+        return info, None, None
+    pr = _prepare(ptr, n, info, off)
+    # no restart interval (or a marker sequence both walks refuse): the self-synchronising stage's view of the stream
+    return info, pr, (_prepare_sync(ptr, n, info, off) if pr is None and n <= SYNC_MAX_FILE else None)
 
 
 def check_pending(pending):
-    """Deferred verdict of the device Huffman stage (`read_images_device(..., defer_status=True)`): waits for the status words of
+    """Deferred verdict of the device Huffman stages (`read_images_device(..., defer_status=True)`): waits for the status words of
     that batch (a copy that was queued right behind the kernels; by the time a caller asks, long done) -> indices of the pages whose
-    stream the kernel flagged as bad (they must be read again through the host path)."""
+    stream a kernel flagged as bad or declined (they must be read again through the host path)."""
     if pending is None:
         return []
     st_host, ev, idx = pending
@@ -215,17 +337,24 @@ def check_pending(pending):
 def read_images_device(paths, device="cuda", device_entropy=None, defer_status=False):
     """A batch of files -> list of device RGB tensors (None where read_image must take over).
     A thread pool reads every file into its slice of ONE pinned batch buffer (reused across batches), parses its headers and walks
-    its markers (the ctypes calls release the GIL).  Files with a restart interval: the buffer is uploaded as it is and the Huffman
-    stage of the whole batch is ONE kernel launch (`entropy_batch_device`, one thread per interval) — unless the intervals are so
-    long that the serial chain inside one of them would take longer than a host core needs for the file
-    (MSOCR_JPEG_DEVICE_MAX_INTERVAL bytes, default 8192: 1.8 ms per KB of interval on the device against ~15 ms per 1.6 MB file on a
-    host core; `device_entropy=True` / False or MSOCR_JPEG_DEVICE_ENTROPY=1 / 0 force one path).
-    Files without: the entropy decode is one serial bit stream per FILE, but files are independent: the pool decodes one page per
-    core into per-slot PINNED coefficient buffers that live across batches (fresh 9 MB arrays per page made the threads serialise
-    on page faults), this thread uploads and launches the reconstruction page by page as the decodes finish.
-    defer_status=True -> (list, pending): the device path's one host wait — the kernel's per-page verdict — is NOT taken here; the
+    its markers (the ctypes calls release the GIL).  The buffer is uploaded as it is and the Huffman stage of the batch is at most
+    two launch sequences.  Routes (`device_entropy=True` / False or MSOCR_JPEG_DEVICE_ENTROPY=1 / 0 force the device / the host):
+
+        file                                          False   True                  None (default)
+        no restart interval                           host    self-synchronising    self-synchronising if SYNC_BY_DEFAULT, else host
+        intervals <= MSOCR_JPEG_DEVICE_MAX_INTERVAL   host    per-interval kernel   per-interval kernel
+        longer intervals                              host    per-interval kernel   self-synchronising if SYNC_BY_DEFAULT, else host
+
+    Per-interval kernel (`entropy_batch_device`): one thread per restart interval; its serial chain loses to a host core when an
+    interval is long (MSOCR_JPEG_DEVICE_MAX_INTERVAL bytes, default 8192: 1.8 ms per KB of interval on the device against ~15 ms per
+    1.6 MB file on a host core).  Self-synchronising stage (`entropy_sync_batch_device`): one thread per SYNC_SUBSEQ_BYTES bytes of
+    a serial segment; a page it declines (status 2: no fixed point within SYNC_MAX_ROUNDS rounds, or a truncated stream) is decoded
+    by the host pool inside this call, as every page of the "host" column is: the pool decodes one page per core into per-slot
+    PINNED coefficient buffers that live across batches (fresh 9 MB arrays per page made the threads serialise on page faults),
+    this thread uploads and launches the reconstruction page by page as the decodes finish.  The pixels are the same on every route.
+    defer_status=True -> (list, pending): the device path's one host wait — the kernels' per-page verdict — is NOT taken here; the
     caller asks `check_pending(pending)` later (the pipeline does, when it waits for the detector anyway), so that submitting a
-    batch never waits for the device."""
+    batch never waits for the device; bad and declined pages are both reported there."""
     global _POOL
     import torch
     from concurrent.futures import ThreadPoolExecutor
@@ -254,28 +383,47 @@ def read_images_device(paths, device="cuda", device_entropy=None, defer_status=F
     loaded = [j.result() if j is not None else None for j in jobs]
     on_dev = {}
     if want:
-        prepared = [None if (r is None or r[1] is None) else r[1] for r in loaded]
+        per_iv = [None if r is None else r[1] for r in loaded]          # the per-interval kernel's pages ...
+        sync = [None if r is None else r[2] for r in loaded]            # ... and the self-synchronising stage's
         if device_entropy is None:   # the policy: no interval of the page longer than max_iv bytes
-            prepared = [None if (r is None or int((r[1][1::2] - r[1][0::2]).max()) > max_iv) else r for r in prepared]
+            long_iv = [p is not None and int((p[1][1::2] - p[1][0::2]).max()) > max_iv for p in per_iv]
+            if SYNC_BY_DEFAULT:
+                sync = [p if lg and n <= SYNC_MAX_FILE else q for p, q, lg, n in zip(per_iv, sync, long_iv, sizes)]
+            else:
+                sync = [None] * len(loaded)
+            per_iv = [None if lg else p for p, lg in zip(per_iv, long_iv)]
         parsed = [None if r is None else (r[0], None, n) for r, n in zip(loaded, sizes)]
-        batch = ScanBatch(parsed, prepared, arr)
-        if batch.n_pages:
-            bytes_dev = ent[0][:total].to(device, non_blocking=True)
-            ent[1] = torch.cuda.Event()
-            ent[1].record()
-            coef, status = entropy_batch_device(batch, device, bytes_dev)
-            imgs = [_reconstruct(info, coef[base:], device, torch, ops) for info, base in batch.infos]
-            idx = [i for i, k in enumerate(batch.pages) if k >= 0]
+        runs = []                    # (batch, coefficient tensor, status tensor)
+        bytes_dev = None
+        for cls, prepared, run in ((ScanBatch, per_iv, entropy_batch_device), (SyncBatch, sync, entropy_sync_batch_device)):
+            batch = cls(parsed, prepared, arr) if any(p is not None for p in prepared) else None
+            if batch is None or not batch.n_pages:
+                continue
+            if bytes_dev is None:
+                bytes_dev = ent[0][:total].to(device, non_blocking=True)
+                ent[1] = torch.cuda.Event()
+                ent[1].record()
+            runs.append((batch,) + tuple(run(batch, device, bytes_dev)[:2]))
+        if runs:
+            imgs, idx = {}, []
+            for batch, coef, _ in runs:
+                for i, k in enumerate(batch.pages):
+                    if k >= 0:
+                        info, base = batch.infos[k]
+                        imgs[i] = _reconstruct(info, coef[base:], device, torch, ops)
+                        idx.append(i)
+            status = runs[0][2] if len(runs) == 1 else torch.cat([r[2] for r in runs])
             if defer_status:
-                st_host = torch.empty(batch.n_pages, dtype=torch.int32).pin_memory()
+                st_host = torch.empty(len(idx), dtype=torch.int32).pin_memory()
                 st_host.copy_(status, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
                 pending = (st_host, ev, idx)
-                on_dev = {i: imgs[batch.pages[i]] for i in idx}
+                on_dev = imgs
             else:
-                bad = status.cpu().numpy()   # the one wait of this path: a bad stream must go to the host reader, as the host decoder's verdict would
-                on_dev = {i: (imgs[batch.pages[i]] if bad[batch.pages[i]] == 0 else None) for i in idx}
+                # the one wait of this path.  1: a bad stream goes to the host reader, as the host decoder's verdict would send it;
+                # 2: declined, not judged: the host pool below decodes it
+                on_dev = {i: (imgs[i] if st == 0 else None) for i, st in zip(idx, status.cpu().tolist()) if st != 2}
     lib = nat.lib()
     futs = []
     for i, r in enumerate(loaded):

@@ -337,7 +337,19 @@ int msocr_reading_order_crops(const float* boxes, const int32_t* nbox, int N, in
  * dequantisation + inverse DCT (libjpeg "islow"), fancy chroma upsampling and YCbCr->RGB run on the DEVICE
  * (msocr_jpeg_reconstruct: coef_dev = the same array in device memory, workspace = msocr_jpeg_workspace_bytes(info) bytes,
  * rgb_out [height][width][3] u8).  msocr_jpeg_reconstruct_host is the HOST twin of the device stage (same code; all pointers
- * host memory).  Unsupported or corrupt streams: MSOCR_E_ARG / info.supported = 0 -> use the host decoder. */
+ * host memory).  Unsupported or corrupt streams: MSOCR_E_ARG / info.supported = 0 -> use the host decoder.
+ * Exif orientation (tag 0x0112 of IFD0 in an APP1 "Exif" segment), which the reference's reader applies: msocr_jpeg_parse_host
+ * refuses a stream whose orientation is 2..8 (msocr_jpeg_reconstruct writes upright pages only).  msocr_jpeg_parse_oriented_host is
+ * the same marker walk that reports the orientation instead: *orientation_out = 1..8 (1 for an absent tag, a value outside 2..8 or
+ * an unreadable Exif block); `info` is the same either way (width / height as stored in the frame header).  It refuses a stream
+ * with more than one Exif APP1 segment (readers differ on which one wins: host reader).  The entropy entries below take the `info` of
+ * either parse entry.  msocr_jpeg_reconstruct_oriented = msocr_jpeg_reconstruct with the orientation applied in the last write of
+ * the colour stage (no extra pass over the page): source pixel (X, Y) of the W x H frame goes to
+ *     orientation   2       3       4       5    6       7       8
+ *     row           Y       H-1-Y   H-1-Y   X    X       W-1-X   W-1-X
+ *     column        W-1-X   W-1-X   X       Y    H-1-Y   H-1-Y   Y
+ * rgb_out is [height][width][3] for orientations 1..4 and [width][height][3] for 5..8; orientation 1 IS msocr_jpeg_reconstruct;
+ * anything outside 1..8: MSOCR_E_ARG.  Same workspace.  msocr_jpeg_reconstruct_oriented_host is its HOST twin. */
 typedef struct msocr_jpeg_info {
   int32_t width, height, ncomp;   /* ncomp 1 (grayscale) or 3 (YCbCr) */
   int32_t hs[3], vs[3];           /* sampling factors per component */
@@ -348,6 +360,7 @@ typedef struct msocr_jpeg_info {
   uint16_t quant[3][64];          /* natural order */
 } msocr_jpeg_info;
 int msocr_jpeg_parse_host(const uint8_t* data_host, int64_t len, msocr_jpeg_info* info_out);
+int msocr_jpeg_parse_oriented_host(const uint8_t* data_host, int64_t len, msocr_jpeg_info* info_out, int32_t* orientation_out);
 int msocr_jpeg_entropy_decode_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int16_t* coef_out_host);
 /* Device-side entropy decode of a BATCH of streams with restart intervals (DRI): the intervals between RSTn markers are independent
  * byte-aligned bit streams.  Host, per page (thread-safe; no state): msocr_jpeg_scan_prepare_host walks the markers of a stream
@@ -406,6 +419,10 @@ int64_t msocr_jpeg_workspace_bytes(const msocr_jpeg_info* info);
 int msocr_jpeg_reconstruct(const msocr_jpeg_info* info, const int16_t* coef_dev, void* workspace_dev, uint8_t* rgb_out_dev,
                            void* stream);
 int msocr_jpeg_reconstruct_host(const msocr_jpeg_info* info, const int16_t* coef_host, uint8_t* rgb_out_host);
+int msocr_jpeg_reconstruct_oriented(const msocr_jpeg_info* info, int32_t orientation, const int16_t* coef_dev, void* workspace_dev,
+                                    uint8_t* rgb_out_dev, void* stream);
+int msocr_jpeg_reconstruct_oriented_host(const msocr_jpeg_info* info, int32_t orientation, const int16_t* coef_host,
+                                         uint8_t* rgb_out_host);
 
 /* f32 <-> bf16 / layout helpers */
 int msocr_nchw_f32_to_nhwc(const float* in, int N, int C, int H, int W, int dtype, void* out, int64_t out_ld,

@@ -94,6 +94,7 @@ _SIGS = {
     "msocr_reading_order_crops": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_jpeg_parse_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo)]),
+    "msocr_jpeg_parse_oriented_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo), ctypes.POINTER(c_i32)]),
     "msocr_jpeg_entropy_decode_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo), c_vp]),
     "msocr_jpeg_scan_desc_bytes": (c_i64, []),
     "msocr_jpeg_scan_prepare_host": (c_i64, [c_vp, c_i64, ctypes.POINTER(JpegInfo), c_i64, c_vp, c_vp, c_i64]),
@@ -107,6 +108,8 @@ _SIGS = {
     "msocr_jpeg_workspace_bytes": (c_i64, [ctypes.POINTER(JpegInfo)]),
     "msocr_jpeg_reconstruct": (c_i32, [ctypes.POINTER(JpegInfo), c_vp, c_vp, c_vp, c_vp]),
     "msocr_jpeg_reconstruct_host": (c_i32, [ctypes.POINTER(JpegInfo), c_vp, c_vp]),
+    "msocr_jpeg_reconstruct_oriented": (c_i32, [ctypes.POINTER(JpegInfo), c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_jpeg_reconstruct_oriented_host": (c_i32, [ctypes.POINTER(JpegInfo), c_i32, c_vp, c_vp]),
     "msocr_nchw_f32_to_nhwc": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "msocr_nhwc_to_nchw_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "msocr_version": (ctypes.c_char_p, []),

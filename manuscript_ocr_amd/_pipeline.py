@@ -209,11 +209,14 @@ class Pipeline:
 
     @staticmethod
     def _shape_of(im):
-        """(height, width) of a page without decoding it twice: arrays know theirs, files are asked through PIL's header parse."""
+        """(height, width) of a page as read_image / the device ingest return it, without decoding it twice: arrays know theirs,
+        files are asked through PIL's header parse — the stored size, swapped when the Exif orientation (tag 0x0112) is 5..8."""
         if isinstance(im, np.ndarray):
             return tuple(im.shape[:2])
         try:
             with Image.open(im) as f:
+                if f.getexif().get(0x0112) in (5, 6, 7, 8):
+                    return (f.width, f.height)
                 return (f.height, f.width)
         except Exception:
             return tuple(read_image(im).shape[:2])

@@ -8,7 +8,12 @@ self-synchronising decode of a serial segment for files without restart markers 
 which file takes which by default).  Dequantisation, inverse DCT, chroma upsampling and colour conversion always run on the
 device, so the decoded page (9.4 MB at 2048x1536, 69 MB for the reference's 5390x4250 example page) is produced in HBM instead of
 crossing PCIe.
-Formats outside the kernel's scope (progressive, CMYK, 12-bit, PNG, ...) return None: callers fall back to read_image.
+A file with an Exif orientation (tag 0x0112 = 2..8: a page photographed in portrait) takes the same routes: the entropy stages do
+not care, `_parse_oriented` reports the orientation beside the frame geometry and the reconstruction applies it in its last write
+(msocr_jpeg_reconstruct_oriented), so the tensor that comes back is what read_image returns (ImageOps.exif_transpose): [W, H, 3]
+for orientations 5..8.
+Formats outside the kernel's scope (progressive, CMYK, 12-bit, two Exif segments, PNG, ...) return None: callers fall back to
+read_image.
 """
 import ctypes
 import os
@@ -25,6 +30,21 @@ def _parse(data: bytes):
     if rc != 0 or not info.supported:
         return None, buf
     return info, buf
+
+
+def _parse_oriented(data: bytes):
+    """`_parse` for the product paths: streams with an Exif orientation are taken too -> (info or None, buffer, orientation 1..8)."""
+    info = nat.JpegInfo()
+    orient = ctypes.c_int32(1)
+    buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
+    rc = nat.lib().msocr_jpeg_parse_oriented_host(ctypes.addressof(buf), len(data), ctypes.byref(info), ctypes.byref(orient))
+    if rc != 0 or not info.supported:
+        return None, buf, 1
+    return info, buf, int(orient.value)
+
+
+def _oriented_shape(info, orientation):
+    return (info.width, info.height, 3) if orientation >= 5 else (info.height, info.width, 3)
 
 
 def jpeg_coefficients(data: bytes):
@@ -50,32 +70,48 @@ def decode_jpeg_host(data: bytes):
     return out
 
 
+def decode_jpeg_oriented_host(data: bytes):
+    """`decode_jpeg_host` with the Exif orientation applied: oriented parse, host entropy decoder, host twin of the oriented
+    reconstruction (tests; not a product path) -> what read_image returns for the file, or None."""
+    info, buf, orient = _parse_oriented(data)
+    if info is None:
+        return None
+    coef = np.empty(int(info.coef_total), dtype=np.int16)
+    if nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data) != 0:
+        return None
+    out = np.empty(_oriented_shape(info, orient), dtype=np.uint8)
+    nat.check(nat.lib().msocr_jpeg_reconstruct_oriented_host(ctypes.byref(info), orient, coef.ctypes.data, out.ctypes.data),
+              "jpeg_reconstruct_oriented_host")
+    return out
+
+
 def decode_jpeg_device(data: bytes, device="cuda", device_entropy=True):
-    """JPEG bytes -> [H, W, 3] u8 tensor on the device (current stream), or None when the stream is not supported.  A stream with
+    """JPEG bytes -> u8 tensor on the device (current stream), [H, W, 3] or, for Exif orientations 5..8, [W, H, 3] — the page as
+    read_image returns it — or None when the stream is not supported.  A stream with
     a restart interval takes the per-interval Huffman kernel, one without the self-synchronising stage (a stream that stage
     declines, status 2, goes on to the host decoder); `device_entropy=False`: the host decoder for every stream."""
     import torch
 
     from . import ops
-    info, buf = _parse(data)
+    info, buf, orient = _parse_oriented(data)
     if info is None:
         return None
     if device_entropy:
         batch = ScanBatch([(info, buf, len(data))])
         if batch.n_pages:
             coef, status = entropy_batch_device(batch, device)
-            img = _reconstruct(info, coef, device, torch, ops)
+            img = _reconstruct(info, coef, device, torch, ops, orient)
             return img if int(status.cpu()[0]) == 0 else None
         batch = SyncBatch([(info, buf, len(data))])
         if batch.n_pages:
             coef, status, _ = entropy_sync_batch_device(batch, device)
             st = int(status.cpu()[0])
             if st != 2:
-                return _reconstruct(info, coef, device, torch, ops) if st == 0 else None
+                return _reconstruct(info, coef, device, torch, ops, orient) if st == 0 else None
     coef = np.empty(int(info.coef_total), dtype=np.int16)
     if nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data) != 0:
         return None
-    return _reconstruct(info, torch.from_numpy(coef).to(device, non_blocking=True), device, torch, ops)
+    return _reconstruct(info, torch.from_numpy(coef).to(device, non_blocking=True), device, torch, ops, orient)
 
 
 def _prepare(ptr, n, info, bytes_base):
@@ -268,23 +304,26 @@ def entropy_sync_batch_device(batch: SyncBatch, device="cuda", bytes_dev=None, m
     return coef, status, rounds
 
 
-def _reconstruct(info, coef_dev, device, torch, ops):
+def _reconstruct(info, coef_dev, device, torch, ops, orientation=1):
+    """IDCT + upsampling + colour conversion of one page, the Exif orientation applied in the last write (1 = upright, the same
+    kernels as msocr_jpeg_reconstruct) -> [H, W, 3] u8, [W, H, 3] for orientations 5..8."""
     ws = torch.empty((nat.lib().msocr_jpeg_workspace_bytes(ctypes.byref(info)),), dtype=torch.uint8, device=device)
-    img = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
-    nat.check(nat.lib().msocr_jpeg_reconstruct(ctypes.byref(info), coef_dev.data_ptr(), ws.data_ptr(), img.data_ptr(), ops._stream()),
-              "jpeg_reconstruct")
+    img = torch.empty(_oriented_shape(info, orientation), dtype=torch.uint8, device=device)
+    nat.check(nat.lib().msocr_jpeg_reconstruct_oriented(ctypes.byref(info), int(orientation), coef_dev.data_ptr(), ws.data_ptr(),
+                                                        img.data_ptr(), ops._stream()), "jpeg_reconstruct_oriented")
     return img
 
 
 def _read_and_parse(path):
-    """File -> (info, ctypes byte buffer, length), or None (not a file / not a supported JPEG)."""
+    """File -> (info, ctypes byte buffer, length), or None (not a file / not a supported JPEG).  Streams with an Exif orientation
+    are taken (the entropy stages are orientation-blind); a caller that reconstructs asks `_parse_oriented` for the orientation."""
     if not isinstance(path, (str, os.PathLike)) or not os.path.isfile(path):
         return None
     with open(path, "rb") as f:
         data = f.read()
     if data[:2] != b"\xff\xd8":
         return None
-    info, buf = _parse(data)
+    info, buf, _ = _parse_oriented(data)
     return None if info is None else (info, buf, len(data))
 
 
@@ -303,7 +342,8 @@ def _slot_buffer(slot, n, torch, dtype=None):
 
 def _load(path, arr, off, n, want_device):
     """Worker: file -> its slice of the pinned batch buffer, header parse, marker walk.
-    -> (info, `_prepare` result or None, `_prepare_sync` result of a stream without restart interval or None) or None."""
+    -> (info, `_prepare` result or None, `_prepare_sync` result of a stream without restart interval or None, Exif orientation)
+    or None."""
     try:
         with open(path, "rb") as f:
             if f.readinto(memoryview(arr[off: off + n])) != n:
@@ -313,14 +353,15 @@ def _load(path, arr, off, n, want_device):
     if n < 4 or arr[off] != 0xFF or arr[off + 1] != 0xD8:
         return None
     info = nat.JpegInfo()
+    orient = ctypes.c_int32(1)
     ptr = arr.ctypes.data + off
-    if nat.lib().msocr_jpeg_parse_host(ptr, n, ctypes.byref(info)) != 0 or not info.supported:
+    if nat.lib().msocr_jpeg_parse_oriented_host(ptr, n, ctypes.byref(info), ctypes.byref(orient)) != 0 or not info.supported:
         return None
     if not want_device:
-        return info, None, None
+        return info, None, None, int(orient.value)
     pr = _prepare(ptr, n, info, off)
     # no restart interval (or a marker sequence both walks refuse): the self-synchronising stage's view of the stream
-    return info, pr, (_prepare_sync(ptr, n, info, off) if pr is None and n <= SYNC_MAX_FILE else None)
+    return info, pr, (_prepare_sync(ptr, n, info, off) if pr is None and n <= SYNC_MAX_FILE else None), int(orient.value)
 
 
 def check_pending(pending):
@@ -352,6 +393,8 @@ def read_images_device(paths, device="cuda", device_entropy=None, defer_status=F
     by the host pool inside this call, as every page of the "host" column is: the pool decodes one page per core into per-slot
     PINNED coefficient buffers that live across batches (fresh 9 MB arrays per page made the threads serialise on page faults),
     this thread uploads and launches the reconstruction page by page as the decodes finish.  The pixels are the same on every route.
+    A file with an Exif orientation 2..8 takes the row of the table its restart intervals put it in, like an upright one: the
+    orientation only changes the last write of its reconstruction (and the shape of its tensor: [W, H, 3] for 5..8).
     defer_status=True -> (list, pending): the device path's one host wait — the kernels' per-page verdict — is NOT taken here; the
     caller asks `check_pending(pending)` later (the pipeline does, when it waits for the detector anyway), so that submitting a
     batch never waits for the device; bad and declined pages are both reported there."""
@@ -410,7 +453,7 @@ def read_images_device(paths, device="cuda", device_entropy=None, defer_status=F
                 for i, k in enumerate(batch.pages):
                     if k >= 0:
                         info, base = batch.infos[k]
-                        imgs[i] = _reconstruct(info, coef[base:], device, torch, ops)
+                        imgs[i] = _reconstruct(info, coef[base:], device, torch, ops, loaded[i][3])
                         idx.append(i)
             status = runs[0][2] if len(runs) == 1 else torch.cat([r[2] for r in runs])
             if defer_status:
@@ -444,7 +487,7 @@ def read_images_device(paths, device="cuda", device_entropy=None, defer_status=F
         coef_dev = slot[0][: int(info.coef_total)].to(device, non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
-        out.append(_reconstruct(info, coef_dev, device, torch, ops))
+        out.append(_reconstruct(info, coef_dev, device, torch, ops, r[3]))
     return (out, pending) if defer_status else out
 
 

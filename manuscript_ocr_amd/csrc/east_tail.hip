@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void east_box_tail_kernel(const float* __restr
   const int pg = blockIdx.x, tid = threadIdx.x;
   const int M = nbox[pg];
   float* ob = out + (long)pg * max_cand * 9;
-  if (M > cap || M < 0) {
+  if (M > cap || M > max_cand || M < 0) {  // cap rounds max_cand up to a multiple of 32: rows max_cand .. cap-1 belong to the next page
     if (tid == 0) n_out[pg] = -1;
     return;
   }

@@ -433,12 +433,14 @@ def east_lanms(cand, counts, iou_thr, workspace=None):
     return boxes, nbox
 
 
-def east_box_tail(boxes, nbox, expand_w, expand_h, scale_x, scale_y, axis_aligned, remove_anomalies, sigma, min_count):
+def east_box_tail(boxes, nbox, expand_w, expand_h, scale_x, scale_y, axis_aligned, remove_anomalies, sigma, min_count, workspace=None):
     """boxes [N,max_cand,9] f32 + nbox [N] i32 (device, from east_lanms) -> (final boxes [N,max_cand,9], counts [N] i32; -1 = page
     with more than min(max_cand, 16384) boxes, to be finished by the host path).  expand / scale / contained / anomalies / axis-aligned."""
     _need_cuda(boxes, nbox)
     N, max_cand, _ = boxes.shape
-    ws = torch.empty((nat.lib().msocr_east_box_tail_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=boxes.device)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((nat.lib().msocr_east_box_tail_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=boxes.device)
     out = torch.empty_like(boxes)
     n_out = torch.empty((N,), dtype=torch.int32, device=boxes.device)
     nat.check(nat.lib().msocr_east_box_tail(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, float(expand_w), float(expand_h),
@@ -448,14 +450,17 @@ def east_box_tail(boxes, nbox, expand_w, expand_h, scale_x, scale_y, axis_aligne
     return out, n_out
 
 
-def reading_order_crops(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf")):
+def reading_order_crops(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf"),
+                        workspace=None):
     """Final boxes [N,max_cand,9] f32 + counts [N] i32 (device, from east_box_tail) -> per page, on the device: reading order of
     the words, which positions yield a crop, and the crop descriptors for crop_resize_pad (msocr_reading_order_crops).
     Returns (order [N,max_cand] i32, keep [N,max_cand] i32, desc [N,max_cand,8] i32, ncrop [N] i32; ncrop -1 = host path)."""
     _need_cuda(boxes, nbox)
     N, max_cand, _ = boxes.shape
     dev = boxes.device
-    ws = torch.empty((nat.lib().msocr_reading_order_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=dev)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((nat.lib().msocr_reading_order_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=dev)
     order = torch.empty((N, max_cand), dtype=torch.int32, device=dev)
     keep = torch.empty((N, max_cand), dtype=torch.int32, device=dev)
     desc = torch.empty((N, max_cand, 8), dtype=torch.int32, device=dev)

@@ -415,6 +415,43 @@ def test_box_tail_host_twin_equals_numpy_tail():
         assert rc == 0 and n.value == len(e) and np.array_equal(out[: n.value], e), (trial, M)
 
 
+# The two tests below pin the host twins to the oracle on the page classes where tests/test_gpu_post_envelope.py takes a twin as
+# the reference (pages too large for the oracle's Python loops).  Measured: the tail test
+# takes 8.5 s (6 s of it the oracle on the 1000-box grid) and the reading-order test 0.3 s; the CPU suite ran 90 s (166 tests) before
+# them and 106 s (168 tests) with them.
+def test_box_tail_host_twin_equals_oracle_on_envelope_pages():
+    """msocr_east_box_tail_host == the oracle chain (oracle/east_post.py) on exact duplicates, equal areas, nesting chains, kept
+    counts at NumPy's pairwise-summation block sizes, and a 1000-box grid with nested inserts and duplicates in far-apart words."""
+    import test_gpu_post_envelope as env
+    from manuscript_ocr_amd import _native as nat
+    pages = env.tail_content_pages(np.random.default_rng([env.SEED, 31]))
+    for name, q in pages.items():
+        for prm in (env.IDENT, env.PROD):
+            assert env._same(env.tail_host(nat, q, prm), env.tail_ref(q, prm)), (name, prm)
+    for K in (7, 8, 9, 128, 129, 136):
+        q = env.tail_kept_page(np.random.default_rng([env.SEED, 32, K]), K)
+        e, n1 = env.tail_ref(q, env.SUMS, stages=True)
+        assert n1 == K and env._same(env.tail_host(nat, q, env.SUMS), e), K
+    q, kept = env.tail_grid_page(1000)
+    assert 0 < len(kept) < 1000 and env._same(env.tail_host(nat, q, env.IDENT), q[kept])
+    assert env._same(env.tail_host(nat, q, env.PROD), env.tail_ref(q, env.PROD))
+
+
+def test_reading_order_host_twin_equals_python_glue_on_envelope_pages():
+    """msocr_reading_order_host == the oracle's sort_boxes_reading_order_with_resolutions + first-equal-word re-match on the pages
+    that never stop shrinking (50 sweeps), have zero height (NaN gap), collapse to duplicate shrunk boxes, and on the pair-cap
+    clique; and row-major on a word grid, as constructed."""
+    import test_gpu_post_envelope as env
+    pages = env.ro_content_pages(np.random.default_rng([env.SEED, 44]))
+    for name in ("fifty_sweeps", "negative_fractions", "zero_height", "duplicate_shrunk", "page_edges"):
+        b = pages[name][0]
+        assert env.ro_host_order(b) == env.ro_python_order(b), name
+    b = env.clique_page(25)
+    assert env.pair_count(b) == 8 * 200 + 4096 and env.ro_host_order(b) == env.ro_python_order(b)
+    b, order = env.word_grid(60, 5, 298, np.random.default_rng(3))
+    assert env.ro_host_order(b) == order == env.ro_python_order(b)
+
+
 def test_vectorised_crop_descriptors_equal_the_loop():
     """ops.crop_descriptors (NumPy) == the literal per-box arithmetic (clamping incl. Python's negative-stop slices, min of the
     two scale factors, banker's rounding of the new size, vertical centring), on boxes inside, across and outside the page."""

@@ -236,8 +236,8 @@ class Pipeline:
         arrays, decoded = [], []
         dec, ingest_pending = [None] * len(images), None
         # Which Huffman stage: ingest's policy (the per-interval kernel for short restart intervals, the self-synchronising stage
-        # for long ones and for files without restart markers; `pipeline.device_entropy = True / False` or MSOCR_JPEG_DEVICE_ENTROPY
-        # force the device stages / the host pool).
+        # for long ones and for files without restart markers; `pipeline.device_entropy = True / False` forces the device stages /
+        # the host pool).
         # From files, same box: device stage 79.5-80.1, host pool 78.2-79.2 pages/s against 83.0 resident.
         if _device_entropy is None:
             _device_entropy = getattr(self, "device_entropy", None)

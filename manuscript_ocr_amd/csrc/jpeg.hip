@@ -7,7 +7,7 @@
 // as unsupported and the caller falls back to the host decoder.
 // Exif orientation (what cv2.imread / ImageOps.exif_transpose apply): msocr_jpeg_parse_host refuses a stream with orientation 2..8,
 // msocr_jpeg_parse_oriented_host — the same marker walk — reports it, and msocr_jpeg_reconstruct_oriented applies it in the last
-// write of the colour stage: mirrored destinations for 2..4 (jpeg_color_flip_kernel), a tiled transpose through LDS for 5..8
+// write of the colour stage: mirrored destinations for 2..4 (jpeg_color_kernel<true>), a tiled transpose through LDS for 5..8
 // (jpeg_color_transpose_kernel), so a portrait page photographed in landscape costs no extra pass over its pixels.
 //
 // Split: parsing runs on the HOST (msocr_jpeg_parse_host), and so does the serial Huffman decoder that judges every stream
@@ -23,6 +23,16 @@
 // published algorithms (jidctint.c "islow" 13-bit fixed point, jdsample.c triangle-filter upsampling, jdcolor.c 16-bit YCC
 // tables) in __host__ __device__ functions: msocr_jpeg_reconstruct_host runs the same code on the CPU, which is how the CPU
 // test-suite pins it bit for bit against PIL's decode of the same files.
+//
+// Layout.  What every decoder shares comes first and exists once: the table (DevTable; HuffTable adds what it is built from), the
+// symbol decoder (interval_symbol, templated on the bit reader), HUFF_EXTEND (extend), the coefficient address of a block
+// (block_offset, mcu_block), an interval's MCU count (interval_mcus).  Then the host side: parse, the marker walk of an interval
+// (interval_walk: the serial decoder's restart handling and scan_prepare's bounds), the serial decoder.  Then the per-interval
+// decoder and its kernel (stage_tables puts a page's tables into LDS for every Huffman kernel), the self-synchronising stage,
+// the reconstruction (reconstruct / reconstruct_host behind the upright and the oriented entries), and the C entries.
+// Separate on purpose: the three bit readers and the serial decoder's loop (reasons beside four_plain_bytes and entropy_decode),
+// the two hand-written block scans (a plain sum in jpeg_sync_place_kernel, a segmented one in jpeg_sync_dc_kernel), and the
+// transposing colour kernel (its workgroup owns a tile, not a run of pixels).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -41,14 +51,67 @@ const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18,
                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// ---------------------------------------------------------------------------------------------------- host: parse + Huffman
-struct HuffTable {
-  bool present = false;
-  uint8_t bits[17] = {0}, vals[256] = {0};
-  // fast path: 9-bit lookahead -> (length << 8) | symbol, 0 = longer code
-  uint16_t look[512];
+// ---------------------------------------------------------------------------------------------------- shared by every decoder
+// The lookup arrays of one Huffman table: what a decoder reads, on the host and (as part of a ScanDesc, staged into LDS) on the
+// device; 1420 bytes.
+struct DevTable {
+  uint16_t look[512];   // fast path: 9-bit lookahead -> (length << 8) | symbol, 0 = longer code
   int32_t maxcode[18];  // largest code of each length (-1 none), [17] = sentinel
   int32_t valoff[17];
+  uint8_t vals[256];
+};
+
+// One Huffman symbol from any of the three bit readers (peek(n) = the next n bits, filled by the caller or on demand; skip(n)).
+// -1: no code of up to 16 bits matches.
+template <class Bits>
+HD int interval_symbol(Bits& br, const DevTable& t) {
+  const uint32_t look = br.peek(9);
+  const uint32_t e = t.look[look];
+  if (e) { br.skip((int)(e >> 8)); return (int)(e & 0xff); }
+  int l = 9;
+  int32_t code;
+  for (;;) {  // codes longer than 9 bits
+    ++l;
+    if (l > 16) return -1;
+    code = (int32_t)br.peek(l);
+    if (t.maxcode[l] >= 0 && code <= t.maxcode[l]) break;
+  }
+  br.skip(l);
+  return t.vals[(code + t.valoff[l]) & 0xff];
+}
+HD int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }  // HUFF_EXTEND
+
+// Coefficient offset of block (by, bx) of MCU (my, mx) in component c's plane of blocks.
+HD int64_t block_offset(const msocr_jpeg_info& f, int c, int my, int mx, int by, int bx) {
+  return f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+}
+// Block b of an interleaved MCU (the nb0 = hs[0] * vs[0] luma blocks row by row, then Cb, then Cr; a grey MCU is one block)
+// -> its component, *by / *bx = where it sits in that component's part of the MCU.
+HD int mcu_block_comp(const msocr_jpeg_info& f, int nb0, int b) { return f.ncomp == 1 ? 0 : (b < nb0 ? 0 : b - nb0 + 1); }
+HD int mcu_block(const msocr_jpeg_info& f, int nb0, int b, int* by, int* bx) {
+  const int c = mcu_block_comp(f, nb0, b);
+  *by = c == 0 ? b / f.hs[0] : 0;
+  *bx = c == 0 ? b - *by * f.hs[0] : 0;
+  return c;
+}
+// MCUs of the restart interval that starts at MCU `first` of `total`.
+HD int interval_mcus(int total, int restart_interval, int first) {
+  return total - first < restart_interval ? total - first : restart_interval;
+}
+// The step the two device bit readers share: four stream bytes (little-endian load) hold no 0xFF, i.e. no stuffing and no marker
+// -> *be = the four in stream order.  The readers stay three (BitReader fills on demand and stops at a marker, IntervalBits
+// un-stuffs five bytes in registers, SyncBits tracks file bit positions): each sits in a hot loop shaped for it.
+HD bool four_plain_bytes(uint32_t lo, uint32_t* be) {
+  if ((((~lo) - 0x01010101u) & lo & 0x80808080u) != 0) return false;
+  *be = (lo << 24) | ((lo & 0xff00u) << 8) | ((lo >> 8) & 0xff00u) | (lo >> 24);
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- host: parse + Huffman
+struct HuffTable {      // a DevTable and what it is built from
+  DevTable lut = {};
+  bool present = false;
+  uint8_t bits[17] = {0};
   // false: the code lengths do not form a prefix code (libjpeg jdhuff.c jpeg_make_d_derived_tbl -> JERR_BAD_HUFF_TABLE)
   bool build() {
     int code = 0, k = 0;
@@ -68,22 +131,22 @@ struct HuffTable {
     int p = 0;
     for (int l = 1; l <= 16; ++l) {
       if (bits[l]) {
-        valoff[l] = p - huffcode[p];
+        lut.valoff[l] = p - huffcode[p];
         p += bits[l];
-        maxcode[l] = huffcode[p - 1];
+        lut.maxcode[l] = huffcode[p - 1];
       } else {
-        maxcode[l] = -1;
-        valoff[l] = 0;
+        lut.maxcode[l] = -1;
+        lut.valoff[l] = 0;
       }
     }
-    maxcode[17] = 0x7fffffff;
-    memset(look, 0, sizeof(look));
+    lut.maxcode[17] = 0x7fffffff;
+    memset(lut.look, 0, sizeof(lut.look));
     p = 0;
     for (int l = 1; l <= 9; ++l)
       for (int i = 0; i < bits[l]; ++i, ++p) {
         const int base = huffcode[p] << (9 - l);
         if (base + (1 << (9 - l)) > 512) return false;  // unreachable after the check above; keeps the table write in bounds
-        for (int c = 0; c < (1 << (9 - l)); ++c) look[base + c] = (uint16_t)((l << 8) | vals[p]);
+        for (int c = 0; c < (1 << (9 - l)); ++c) lut.look[base + c] = (uint16_t)((l << 8) | lut.vals[p]);
       }
     return true;
   }
@@ -116,22 +179,6 @@ struct BitReader {
   inline int get(int n) { if (n == 0) return 0; const int v = peek(n); skip(n); return v; }
   void restart() { acc = 0; nbits = 0; hit_marker = false; }
 };
-
-inline int huff_decode(BitReader& br, const HuffTable& t) {
-  const int look = br.peek(9);
-  const uint16_t e = t.look[look];
-  if (e) { br.skip(e >> 8); return e & 0xff; }
-  int code = look, l = 9;
-  for (;;) {  // codes longer than 9 bits
-    ++l;
-    if (l > 16) return -1;
-    code = br.peek(l);
-    if (code <= t.maxcode[l] && t.maxcode[l] >= 0) break;
-  }
-  br.skip(l);
-  return t.vals[(code + t.valoff[l]) & 0xff];
-}
-inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }  // HUFF_EXTEND
 
 struct Parsed {
   msocr_jpeg_info info;
@@ -230,7 +277,7 @@ int parse(const uint8_t* d, int64_t len, Parsed* P, ExifRule exif = kExifRefuse,
         for (int l = 1; l <= 16; ++l) { t.bits[l] = s[o + l]; cnt += t.bits[l]; }
         o += 17;
         if (cnt > 256 || o + cnt > n) return MSOCR_E_ARG;
-        memcpy(t.vals, s + o, cnt);
+        memcpy(t.lut.vals, s + o, cnt);
         o += cnt;
         t.present = true;
         if (!t.build()) return MSOCR_E_ARG;
@@ -319,6 +366,36 @@ int parse(const uint8_t* d, int64_t len, Parsed* P, ExifRule exif = kExifRefuse,
   return MSOCR_OK;
 }
 
+// `info` of an entropy entry must be what a parse entry returned for this stream: parses it again (the Exif segment was judged
+// then) and compares.
+int reparse(const uint8_t* d, int64_t len, const msocr_jpeg_info* info, Parsed* P) {
+  if (!info || parse(d, len, P, kExifIgnore) != MSOCR_OK) return MSOCR_E_ARG;
+  const msocr_jpeg_info& f = P->info;
+  return f.width == info->width && f.height == info->height && f.ncomp == info->ncomp && f.coef_total == info->coef_total ? MSOCR_OK
+                                                                                                                        : MSOCR_E_ARG;
+}
+
+// The marker walk of one restart interval whose data starts at (or, for a reader that has consumed some, holds) `p`: *data_end =
+// the first 0xFF that is not followed by a stuffed 0x00 (`end` when there is none) — where the interval's bits end; returns the
+// byte behind the first RSTn at or after it — where the next interval starts — or nullptr when no RSTn follows.
+const uint8_t* interval_walk(const uint8_t* p, const uint8_t* end, const uint8_t** data_end) {
+  const uint8_t* e = p;
+  for (;;) {
+    e = e < end ? static_cast<const uint8_t*>(memchr(e, 0xFF, (size_t)(end - e))) : nullptr;
+    if (!e) { e = end; break; }
+    if (e + 1 < end && e[1] == 0x00) { e += 2; continue; }
+    break;
+  }
+  *data_end = e;
+  const uint8_t* q = e;
+  while (q + 1 < end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
+  return q + 1 < end ? q + 2 : nullptr;
+}
+
+// The serial decoder: the host pool's product path and the judge of every stream.  It shares the table, the symbol decoder, the
+// block addressing and the marker walk with the device decoders but keeps its own loop: decode_interval's one-symbol-per-
+// iteration form (made for converged lanes) is slower on a host core (1.62 MB 4:2:0 page, one core: 17.6-18.5 ms against
+// 20.6-21.2 ms through the per-interval host twin; 3.2 MB 4:4:4: 36.5-37.2 against 42.3-42.8 ms).
 int entropy_decode(const Parsed& P, const uint8_t* end, int16_t* coef) {
   const msocr_jpeg_info& f = P.info;
   memset(coef, 0, sizeof(int16_t) * (size_t)f.coef_total);
@@ -330,27 +407,27 @@ int entropy_decode(const Parsed& P, const uint8_t* end, int16_t* coef) {
   for (int my = 0; my < P.mcus_y; ++my)
     for (int mx = 0; mx < P.mcus_x; ++mx) {
       if (P.restart_interval && until_restart == 0) {
-        // byte-align, expect RSTn
+        // byte-align, expect RSTn (br.p has not passed the interval's marker: the walk from it ends where the walk from the
+        // interval's first byte does)
         br.restart();
-        const uint8_t* q = br.p;
-        while (q + 1 < end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
-        if (q + 1 >= end) return MSOCR_E_ARG;
-        br.p = q + 2;
+        const uint8_t* data_end;
+        br.p = interval_walk(br.p, end, &data_end);
+        if (!br.p) return MSOCR_E_ARG;
         pred[0] = pred[1] = pred[2] = 0;
         until_restart = P.restart_interval;
       }
       for (int c = 0; c < f.ncomp; ++c) {
-        const HuffTable& dct = P.dc[P.dc_sel[c]];
-        const HuffTable& act = P.ac[P.ac_sel[c]];
+        const DevTable& dct = P.dc[P.dc_sel[c]].lut;
+        const DevTable& act = P.ac[P.ac_sel[c]].lut;
         for (int by = 0; by < f.vs[c]; ++by)
           for (int bx = 0; bx < f.hs[c]; ++bx) {
-            int16_t* blk = coef + f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
-            int s = huff_decode(br, dct);
+            int16_t* blk = coef + block_offset(f, c, my, mx, by, bx);
+            int s = interval_symbol(br, dct);
             if (s < 0 || s > 15) return MSOCR_E_ARG;
             if (s) pred[c] = (int)((uint32_t)pred[c] + (uint32_t)extend(br.get(s), s));  // modulo 2^32: a hostile stream wraps
             blk[0] = (int16_t)pred[c];
             for (int k = 1; k < 64;) {
-              const int rs = huff_decode(br, act);
+              const int rs = interval_symbol(br, act);
               if (rs < 0) return MSOCR_E_ARG;
               const int r = rs >> 4, sz = rs & 15;
               if (sz == 0) {
@@ -375,12 +452,6 @@ int entropy_decode(const Parsed& P, const uint8_t* end, int16_t* coef) {
 // msocr_jpeg_entropy_decode_intervals_host runs the same code interval after interval on the CPU (how the CPU suite pins it against
 // entropy_decode above and against PIL).  Same arithmetic and the same treatment of bad streams as entropy_decode: zeros are fed
 // past the end of the interval (= at its marker), an undecodable code / a coefficient index past 63 is an error for the whole page.
-struct DevTable {            // HuffTable without the construction state; 1420 bytes
-  uint16_t look[512];
-  int32_t maxcode[18];
-  int32_t valoff[17];
-  uint8_t vals[256];
-};
 struct ScanDesc {            // one page; msocr_jpeg_scan_desc_bytes() bytes, opaque to callers
   msocr_jpeg_info info;
   int64_t bytes_base;        // where the file's first byte sits in the batch byte buffer (the interval bounds are relative to the FILE)
@@ -402,9 +473,8 @@ struct IntervalBits {
       // wave whose lanes are at different places of different streams pays the same few ALU instructions either way
       const uint64_t w = (uint64_t)base[pos] | ((uint64_t)base[pos + 1] << 8) | ((uint64_t)base[pos + 2] << 16) |
                          ((uint64_t)base[pos + 3] << 24) | ((uint64_t)base[pos + 4] << 32);
-      const uint32_t lo = (uint32_t)w;
-      if ((((~lo) - 0x01010101u) & lo & 0x80808080u) == 0) {  // no 0xFF among the four: no stuffing, no marker
-        const uint32_t be = (lo << 24) | ((lo & 0xff00u) << 8) | ((lo >> 8) & 0xff00u) | (lo >> 24);
+      uint32_t be;
+      if (four_plain_bytes((uint32_t)w, &be)) {
         acc = (acc << 32) | (uint64_t)be;
         nbits += 32;
         pos += 4;
@@ -444,23 +514,6 @@ struct IntervalBits {
   HD void skip(int n) { nbits -= n; }
 };
 
-template <class Bits>
-HD int interval_symbol(Bits& br, const DevTable& t) {
-  const uint32_t look = br.peek(9);
-  const uint32_t e = t.look[look];
-  if (e) { br.skip((int)(e >> 8)); return (int)(e & 0xff); }
-  int l = 9;
-  int32_t code;
-  for (;;) {
-    ++l;
-    if (l > 16) return -1;
-    code = (int32_t)br.peek(l);
-    if (t.maxcode[l] >= 0 && code <= t.maxcode[l]) break;
-  }
-  br.skip(l);
-  return t.vals[(code + t.valoff[l]) & 0xff];
-}
-
 // One Huffman symbol per loop iteration, the same instruction sequence for a DC difference and an AC run/size: the 64 lanes of a
 // wave decode 64 different intervals and stay converged except in the rare slow paths (codes longer than 9 bits, 0xFF bytes).
 // `coef` = the page's zero-filled coefficient array.  Returns 0, or 1 for a bad stream.
@@ -473,7 +526,7 @@ HD int decode_interval(const msocr_jpeg_info& f, int mcus_x, const DevTable* dc,
   int pred0 = 0, pred1 = 0, pred2 = 0;
   int mcu = first_mcu, b = 0, k = 0, c = 0;
   int my = mcu / mcus_x, mx = mcu - my * mcus_x;
-  int64_t blk = f.coef_off[0] + ((int64_t)(my * f.vs[0]) * f.blocks_w[0] + mx * f.hs[0]) * 64;
+  int64_t blk = block_offset(f, 0, my, mx, 0, 0);
   const int last = first_mcu + n_mcu;
   while (mcu < last) {
     br.refill();
@@ -485,7 +538,7 @@ HD int decode_interval(const msocr_jpeg_info& f, int mcus_x, const DevTable* dc,
     if (sz) {
       v = (int)br.peek(sz);
       br.skip(sz);
-      v = v < (1 << (sz - 1)) ? v - (1 << sz) + 1 : v;   // HUFF_EXTEND
+      v = extend(v, sz);
     }
     if (k == 0) {
       int pr = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
@@ -511,21 +564,24 @@ HD int decode_interval(const msocr_jpeg_info& f, int mcus_x, const DevTable* dc,
         ++mcu;
         if (++mx == mcus_x) { mx = 0; ++my; }
       }
-      c = b < nb0 ? 0 : b - nb0 + 1;
-      if (f.ncomp == 1) c = 0;
-      const int bi = c == 0 ? b : 0;
-      const int by = c == 0 ? bi / f.hs[0] : 0, bx = c == 0 ? bi - by * f.hs[0] : 0;
-      blk = f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+      int by, bx;
+      c = mcu_block(f, nb0, b, &by, &bx);
+      blk = block_offset(f, c, my, mx, by, bx);
     }
   }
   return 0;
 }
 
-void to_dev_table(const HuffTable& t, DevTable* o) {
-  memcpy(o->look, t.look, sizeof(o->look));
-  memcpy(o->maxcode, t.maxcode, sizeof(o->maxcode));
-  memcpy(o->valoff, t.valoff, sizeof(o->valoff));
-  memcpy(o->vals, t.vals, sizeof(o->vals));
+// The page's six tables and the zigzag order -> LDS, by all THREADS threads of the workgroup (ends with the barrier).
+template <int THREADS>
+__device__ __forceinline__ void stage_tables(const ScanDesc& d, DevTable* s_dc, DevTable* s_ac, uint8_t* s_zz) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(d.dc);
+  uint32_t* d0 = reinterpret_cast<uint32_t*>(s_dc);
+  uint32_t* d1 = reinterpret_cast<uint32_t*>(s_ac);
+  constexpr int W = (int)(3 * sizeof(DevTable) / 4);
+  for (int i = threadIdx.x; i < W; i += THREADS) { d0[i] = src[i]; d1[i] = src[W + i]; }
+  if (THREADS == 64 || threadIdx.x < 64) s_zz[threadIdx.x] = d.zigzag[threadIdx.x];
+  __syncthreads();
 }
 
 // One wave = `lanes` consecutive intervals of ONE page (blockIdx.y); the page's six tables sit in LDS (all 64 threads load them).
@@ -540,23 +596,15 @@ __global__ __launch_bounds__(64) void jpeg_huffman_kernel(const uint8_t* __restr
   __shared__ uint8_t s_zz[64];
   const ScanDesc& d = descs[blockIdx.y];
   if ((int)blockIdx.x * lanes >= d.n_intervals) return;    // uniform
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(d.dc);
-    uint32_t* d0 = reinterpret_cast<uint32_t*>(s_dc);
-    uint32_t* d1 = reinterpret_cast<uint32_t*>(s_ac);
-    constexpr int W = (int)(3 * sizeof(DevTable) / 4);
-    for (int i = threadIdx.x; i < W; i += 64) { d0[i] = src[i]; d1[i] = src[W + i]; }
-    s_zz[threadIdx.x] = d.zigzag[threadIdx.x];
-  }
-  __syncthreads();
+  stage_tables<64>(d, s_dc, s_ac, s_zz);
   const int iv = blockIdx.x * lanes + threadIdx.x;
   if ((int)threadIdx.x >= lanes || iv >= d.n_intervals) return;
   const int64_t coef_base = page_base[2 * blockIdx.y], first_interval = page_base[2 * blockIdx.y + 1];
   const uint32_t begin = bounds[2 * (first_interval + iv)], end = bounds[2 * (first_interval + iv) + 1];
-  const int total = d.mcus_x * d.mcus_y;
   const int first = iv * d.restart_interval;
-  const int n = total - first < d.restart_interval ? total - first : d.restart_interval;
-  if (decode_interval(d.info, d.mcus_x, s_dc, s_ac, s_zz, bytes + d.bytes_base, begin, end, first, n, coef + coef_base)) status[blockIdx.y] = 1;
+  if (decode_interval(d.info, d.mcus_x, s_dc, s_ac, s_zz, bytes + d.bytes_base, begin, end, first,
+                      interval_mcus(d.mcus_x * d.mcus_y, d.restart_interval, first), coef + coef_base))
+    status[blockIdx.y] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------- self-synchronising decode
@@ -600,8 +648,8 @@ struct SyncBits {          // IntervalBits that knows where in the FILE its next
     if (nbits > 32) return;
     if (pos + 4 <= end) {
       const uint32_t lo = (uint32_t)base[pos] | ((uint32_t)base[pos + 1] << 8) | ((uint32_t)base[pos + 2] << 16) | ((uint32_t)base[pos + 3] << 24);
-      if ((((~lo) - 0x01010101u) & lo & 0x80808080u) == 0) {  // no 0xFF among the four
-        const uint32_t be = (lo << 24) | ((lo & 0xff00u) << 8) | ((lo >> 8) & 0xff00u) | (lo >> 24);
+      uint32_t be;
+      if (four_plain_bytes(lo, &be)) {
         acc = (acc << 32) | (uint64_t)be;
         nbits += 32;
         pos += 4;
@@ -655,9 +703,9 @@ HD uint64_t sync_decode(const ScanDesc& d, const DevTable* dc, const DevTable* a
   int mx = 0, my = 0, bb = 0;
   int64_t addr = 0;
   auto block_addr = [&]() {
-    const int c = f.ncomp == 1 ? 0 : (bb < nb0 ? 0 : bb - nb0 + 1);
-    const int by = c == 0 ? bb / f.hs[0] : 0, bx = c == 0 ? bb - by * f.hs[0] : 0;
-    return f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+    int by, bx;
+    const int c = mcu_block(f, nb0, bb, &by, &bx);
+    return block_offset(f, c, my, mx, by, bx);
   };
   if (WRITE) {
     const int mcu = first_mcu + (int)(blk / (uint32_t)per_mcu);
@@ -670,8 +718,8 @@ HD uint64_t sync_decode(const ScanDesc& d, const DevTable* dc, const DevTable* a
     br.refill();
     at = br.bitpos();
     if (WRITE ? (blk >= need || (at >= stop && !tail)) : at >= stop) break;
-    int c = f.ncomp == 1 ? 0 : (b < nb0 ? 0 : b - nb0 + 1);
-    c = c > 2 ? 2 : c;
+    int c = mcu_block_comp(f, nb0, b);
+    c = c > 2 ? 2 : c;                                   // a guessed state may name a block no MCU has
     const bool is_dc = k == 0;
     int sym = interval_symbol(br, is_dc ? dc[c] : ac[c]);
     bool err = false;
@@ -682,7 +730,7 @@ HD uint64_t sync_decode(const ScanDesc& d, const DevTable* dc, const DevTable* a
     if (sz) {
       v = (int)br.peek(sz);
       br.skip(sz);
-      v = v < (1 << (sz - 1)) ? v - (1 << sz) + 1 : v;   // HUFF_EXTEND
+      v = extend(v, sz);
     }
     if (is_dc) {
       if (WRITE) coef[addr] = (int16_t)v;                // the difference; jpeg_sync_dc_kernel sums
@@ -742,9 +790,9 @@ HD SyncSub sync_locate(const ScanDesc& d, const uint32_t* bounds, const uint32_t
   const uint64_t from = (uint64_t)q.begin + (uint64_t)(i - q.first_sub) * S;
   q.lo = from < q.end ? (uint32_t)from : q.end;
   q.stop = (q.last || from + S > q.end ? q.end : (uint32_t)(from + S)) * 8u;
-  const int total = d.mcus_x * d.mcus_y, per_mcu = d.info.ncomp == 3 ? d.info.hs[0] * d.info.vs[0] + 2 : 1;
+  const int per_mcu = d.info.ncomp == 3 ? d.info.hs[0] * d.info.vs[0] + 2 : 1;
   q.first_mcu = lo * d.restart_interval;
-  const int n_mcu = total - q.first_mcu < d.restart_interval ? total - q.first_mcu : d.restart_interval;
+  const int n_mcu = interval_mcus(d.mcus_x * d.mcus_y, d.restart_interval, q.first_mcu);
   q.need = n_mcu > 0 ? (uint32_t)n_mcu * (uint32_t)per_mcu : 0u;
   return q;
 }
@@ -802,13 +850,23 @@ HD int sync_rounds_taken(const int32_t* changed, int stride, int max_rounds, uin
   return max_rounds;
 }
 
+// The DC scan of component c: bpm = its blocks per MCU, L = its blocks in scan order, seg = those of one restart interval (the
+// predictor starts from 0 at every multiple of seg).
+struct DcScan { uint32_t bpm, L, seg; };
+HD DcScan sync_dc_scan(const ScanDesc& d, int c) {
+  DcScan s;
+  s.bpm = (uint32_t)(d.info.hs[c] * d.info.vs[c]);
+  s.L = (uint32_t)(d.mcus_x * d.mcus_y) * s.bpm;
+  s.seg = d.restart_interval > 0 ? (uint32_t)d.restart_interval * s.bpm : s.L;
+  return s;
+}
 HD int64_t sync_dc_addr(const ScanDesc& d, int c, uint32_t e) {   // element e of component c in scan order -> its DC coefficient
   const msocr_jpeg_info& f = d.info;
-  const uint32_t bpm = (uint32_t)(f.hs[c] * f.vs[c]);
+  const uint32_t bpm = sync_dc_scan(d, c).bpm;   // asked for here, not handed down: 52 instead of 71 VGPRs in jpeg_sync_dc_kernel
   const uint32_t mcu = e / bpm, j = e - mcu * bpm;
   const int by = (int)(j / (uint32_t)f.hs[c]), bx = (int)j - by * f.hs[c];
   const int my = (int)(mcu / (uint32_t)d.mcus_x), mx = (int)mcu - my * d.mcus_x;
-  return f.coef_off[c] + ((int64_t)(my * f.vs[c] + by) * f.blocks_w[c] + (mx * f.hs[c] + bx)) * 64;
+  return block_offset(f, c, my, mx, by, bx);
 }
 
 struct SyncWorkspace {
@@ -851,16 +909,6 @@ struct SyncArgs {                 // what every kernel of the sequence takes
   SyncWorkspace w;
 };
 
-__device__ __forceinline__ void sync_stage_tables(const ScanDesc& d, DevTable* s_dc, DevTable* s_ac, uint8_t* s_zz) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(d.dc);
-  uint32_t* d0 = reinterpret_cast<uint32_t*>(s_dc);
-  uint32_t* d1 = reinterpret_cast<uint32_t*>(s_ac);
-  constexpr int W = (int)(3 * sizeof(DevTable) / 4);
-  for (int i = threadIdx.x; i < W; i += 256) { d0[i] = src[i]; d1[i] = src[W + i]; }
-  if (threadIdx.x < 64) s_zz[threadIdx.x] = d.zigzag[threadIdx.x];
-  __syncthreads();
-}
-
 // grid (subsequences of the longest page / 256, pages)
 __global__ __launch_bounds__(256) void jpeg_sync_round_kernel(SyncArgs a, int round) {
   __shared__ DevTable s_dc[3], s_ac[3];
@@ -871,7 +919,7 @@ __global__ __launch_bounds__(256) void jpeg_sync_round_kernel(SyncArgs a, int ro
   if (blockIdx.x * 256u >= nsub) return;                                        // uniform
   if (round >= 2 && a.w.changed[(int64_t)(round - 1) * a.n_pages + pg] == 0) return;   // uniform: the page stands
   const ScanDesc& d = a.descs[pg];
-  sync_stage_tables(d, s_dc, s_ac, s_zz);
+  stage_tables<256>(d, s_dc, s_ac, s_zz);
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= nsub) return;
   const int64_t sb = pb[2];
@@ -934,7 +982,7 @@ __global__ __launch_bounds__(256) void jpeg_sync_write_kernel(SyncArgs a, int16_
   if (blockIdx.x * 256u >= nsub) return;            // uniform
   if (status[pg] == 2) return;                      // no fixed point (set by the place kernel, a launch ago): nothing to write
   const ScanDesc& d = a.descs[pg];
-  sync_stage_tables(d, s_dc, s_ac, s_zz);
+  stage_tables<256>(d, s_dc, s_ac, s_zz);
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= nsub) return;
   const int st = sync_write(d, s_dc, s_ac, s_zz, a.bytes + d.bytes_base, a.bounds + 2 * pb[1], a.sub_first + pb[1], nsub, a.S, i,
@@ -949,8 +997,8 @@ __global__ __launch_bounds__(256) void jpeg_sync_dc_kernel(SyncArgs a, int16_t* 
   const ScanDesc& d = a.descs[pg];
   if (c >= d.info.ncomp) return;
   int16_t* coef = coef_all + a.page_base[4 * pg];
-  const uint32_t bpm = (uint32_t)(d.info.hs[c] * d.info.vs[c]);
-  const uint32_t L = (uint32_t)(d.mcus_x * d.mcus_y) * bpm, seg = d.restart_interval > 0 ? (uint32_t)d.restart_interval * bpm : L;
+  const DcScan sc = sync_dc_scan(d, c);
+  const uint32_t L = sc.L, seg = sc.seg;
   uint32_t carry = 0;
   for (uint32_t base = 0; base < L; base += 2048) {
     uint32_t loc[8], run = 0, flag = 0;
@@ -1152,16 +1200,6 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(msocr_jpeg_info f, const
   }
 }
 
-__global__ __launch_bounds__(256) void jpeg_color_kernel(msocr_jpeg_info f, Planes pl, uint8_t* __restrict__ rgb) {
-  const long total = (long)f.width * f.height;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int Y = (int)(i / f.width), X = (int)(i - (long)Y * f.width);
-    uint8_t o[3];
-    pixel_rgb(f, pl, X, Y, o);
-    rgb[3 * i] = o[0]; rgb[3 * i + 1] = o[1]; rgb[3 * i + 2] = o[2];
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- Exif orientation
 // Where source pixel (X, Y) of a W x H frame goes under Exif orientation 2..8 (what ImageOps.exif_transpose / cv2.imread do);
 // the output is [H][W][3] for 2..4 and [W][H][3] for 5..8.  Kernels and host twin share it.
@@ -1173,15 +1211,17 @@ HD int64_t orient_dest(int o, int W, int H, int X, int Y) {
   return orient_transposes(o) ? (int64_t)x * H + y : (int64_t)y * W + x;
 }
 
-// Orientations 2..4: jpeg_color_kernel's loop with the destination remapped.  Rows stay rows: a wave's stores cover one
-// contiguous run of a destination row (descending where X is mirrored).
-__global__ __launch_bounds__(256) void jpeg_color_flip_kernel(msocr_jpeg_info f, Planes pl, int o, uint8_t* __restrict__ rgb) {
+// The colour stage in source-row order, orientations 1..4.  MIRRORED = false: upright, pixel i goes to place i and there is no
+// remap code; true (2..4): the destination is remapped.  Rows stay rows either way: a wave's stores cover one contiguous run of
+// a destination row (descending where X is mirrored).
+template <bool MIRRORED>
+__global__ __launch_bounds__(256) void jpeg_color_kernel(msocr_jpeg_info f, Planes pl, int o, uint8_t* __restrict__ rgb) {
   const long total = (long)f.width * f.height;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int Y = (int)(i / f.width), X = (int)(i - (long)Y * f.width);
     uint8_t px[3];
     pixel_rgb(f, pl, X, Y, px);
-    const int64_t d = 3 * orient_dest(o, f.width, f.height, X, Y);
+    const int64_t d = 3 * (MIRRORED ? orient_dest(o, f.width, f.height, X, Y) : (int64_t)i);
     rgb[d] = px[0]; rgb[d + 1] = px[1]; rgb[d + 2] = px[2];
   }
 }
@@ -1221,11 +1261,30 @@ __global__ __launch_bounds__(256) void jpeg_color_transpose_kernel(msocr_jpeg_in
   }
 }
 
-int launch_idct(const msocr_jpeg_info* info, const int16_t* coef_dev, const Planes& pl, hipStream_t s) {
-  const long nblk = (long)info->coef_total / 64;
-  long g1 = (nblk + 255) / 256;
-  if (g1 > 65535) g1 = 65535;
-  MSOCR_LAUNCH(jpeg_idct_kernel, dim3((unsigned)g1), dim3(256), 0, s, *info, coef_dev, pl);
+// blocks of 256 threads for a grid-stride loop over n elements
+unsigned stride_grid(long n) {
+  const long g = (n + 255) / 256;
+  return (unsigned)(g > 65535 ? 65535 : g);
+}
+
+// The device reconstruction behind both entries: IDCT into the planes of the workspace, then the colour stage whose last write
+// applies the orientation: 1 = upright, 2..4 = mirrored destinations, 5..8 = the tiled transposing kernel.
+int reconstruct(const msocr_jpeg_info* info, int orientation, const int16_t* coef_dev, void* workspace_dev, uint8_t* rgb_out_dev,
+                hipStream_t s) {
+  if (orientation < 1 || orientation > 8 || !info_ok(info) || !coef_dev || !workspace_dev || !rgb_out_dev || ((uintptr_t)workspace_dev & 15))
+    return MSOCR_E_ARG;
+  const Planes pl = make_planes(*info, (uint8_t*)workspace_dev);
+  MSOCR_LAUNCH(jpeg_idct_kernel, dim3(stride_grid((long)info->coef_total / 64)), dim3(256), 0, s, *info, coef_dev, pl);
+  if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
+  const dim3 rows(stride_grid((long)info->width * info->height));
+  if (orient_transposes(orientation)) {
+    const dim3 grid((unsigned)((info->width + kOrientTile - 1) / kOrientTile), (unsigned)((info->height + kOrientTile - 1) / kOrientTile));
+    MSOCR_LAUNCH(jpeg_color_transpose_kernel, grid, dim3(256), 0, s, *info, pl, orientation, rgb_out_dev);
+  } else if (orientation == 1) {
+    MSOCR_LAUNCH(jpeg_color_kernel<false>, rows, dim3(256), 0, s, *info, pl, orientation, rgb_out_dev);
+  } else {
+    MSOCR_LAUNCH(jpeg_color_kernel<true>, rows, dim3(256), 0, s, *info, pl, orientation, rgb_out_dev);
+  }
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
@@ -1235,6 +1294,18 @@ void idct_planes_host(const msocr_jpeg_info* info, const int16_t* coef_host, con
       for (int bx = 0; bx < info->blocks_w[c]; ++bx)
         idct_block(coef_host + info->coef_off[c] + ((int64_t)by * info->blocks_w[c] + bx) * 64, info->quant[c],
                    pl.p[c] + ((long)by * 8) * pl.ld[c] + bx * 8, pl.ld[c]);
+}
+
+// The host twin behind both entries: the same idct_block, pixel_rgb and orient_dest (orientation 1: no flips, no transpose).
+int reconstruct_host(const msocr_jpeg_info* info, int orientation, const int16_t* coef_host, uint8_t* rgb_out_host) {
+  if (orientation < 1 || orientation > 8 || !info_ok(info) || !coef_host || !rgb_out_host) return MSOCR_E_ARG;
+  std::vector<uint8_t> ws((size_t)planes_bytes(*info));
+  const Planes pl = make_planes(*info, ws.data());
+  idct_planes_host(info, coef_host, pl);
+  for (int Y = 0; Y < info->height; ++Y)
+    for (int X = 0; X < info->width; ++X)
+      pixel_rgb(*info, pl, X, Y, rgb_out_host + 3 * orient_dest(orientation, info->width, info->height, X, Y));
+  return MSOCR_OK;
 }
 
 }  // namespace
@@ -1258,26 +1329,20 @@ extern "C" int msocr_jpeg_parse_oriented_host(const uint8_t* data_host, int64_t 
 }
 
 extern "C" int msocr_jpeg_entropy_decode_host(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int16_t* coef_out_host) {
-  if (!coef_out_host || !info) return MSOCR_E_ARG;
   Parsed P;
-  if (parse(data_host, len, &P, kExifIgnore) != MSOCR_OK) return MSOCR_E_ARG;
-  if (P.info.width != info->width || P.info.height != info->height || P.info.ncomp != info->ncomp ||
-      P.info.coef_total != info->coef_total) return MSOCR_E_ARG;  // `info` must be what a parse entry returned for this stream
+  if (!coef_out_host || reparse(data_host, len, info, &P) != MSOCR_OK) return MSOCR_E_ARG;
   return entropy_decode(P, data_host + len, coef_out_host);
 }
 
 extern "C" int64_t msocr_jpeg_scan_desc_bytes(void) { return (int64_t)sizeof(ScanDesc); }
 
-// Walks the entropy-coded segment exactly as entropy_decode's restart handling does: interval k ends at the first marker (0xFF not
-// followed by 0x00) at or after its start, interval k + 1 starts behind the first RSTn at or after that marker.
+// Walks the entropy-coded segment with entropy_decode's own interval_walk: interval k ends at the first marker (0xFF not followed
+// by 0x00) at or after its start, interval k + 1 starts behind the first RSTn at or after that marker.
 // `serial_too`: a stream without DRI is taken as ONE interval of all its MCUs (the self-synchronising stage's view of it)
 static int64_t scan_prepare(const uint8_t* data_host, int64_t len, const msocr_jpeg_info* info, int64_t bytes_base, void* desc_out,
                             uint32_t* bounds_out, int64_t bounds_cap, bool serial_too) {
-  if (!data_host || !info || !desc_out || !bounds_out || bytes_base < 0) return MSOCR_E_ARG;
   Parsed P;
-  if (parse(data_host, len, &P, kExifIgnore) != MSOCR_OK) return MSOCR_E_ARG;
-  if (P.info.width != info->width || P.info.height != info->height || P.info.ncomp != info->ncomp ||
-      P.info.coef_total != info->coef_total) return MSOCR_E_ARG;
+  if (!data_host || !desc_out || !bounds_out || bytes_base < 0 || reparse(data_host, len, info, &P) != MSOCR_OK) return MSOCR_E_ARG;
   const int64_t total = (int64_t)P.mcus_x * P.mcus_y;
   if (P.restart_interval <= 0) {
     if (!serial_too || total > 0x7fffffff) return MSOCR_E_ARG;           // one serial bit stream: not the per-interval kernel's
@@ -1294,28 +1359,19 @@ static int64_t scan_prepare(const uint8_t* data_host, int64_t len, const msocr_j
   d->restart_interval = P.restart_interval;
   d->mcus_x = P.mcus_x; d->mcus_y = P.mcus_y; d->n_intervals = (int32_t)n_iv;
   for (int c = 0; c < P.info.ncomp; ++c) {
-    to_dev_table(P.dc[P.dc_sel[c]], &d->dc[c]);
-    to_dev_table(P.ac[P.ac_sel[c]], &d->ac[c]);
+    d->dc[c] = P.dc[P.dc_sel[c]].lut;
+    d->ac[c] = P.ac[P.ac_sel[c]].lut;
   }
   memcpy(d->zigzag, kZigzag, 64);
   const uint8_t* const end = data_host + len;
   const uint8_t* p = P.scan;
   for (int64_t k = 0; k < n_iv; ++k) {
-    const uint8_t* e = p;
-    for (;;) {                                                           // first 0xFF that is not a stuffed byte
-      e = e < end ? static_cast<const uint8_t*>(memchr(e, 0xFF, (size_t)(end - e))) : nullptr;
-      if (!e) { e = end; break; }
-      if (e + 1 < end && e[1] == 0x00) { e += 2; continue; }
-      break;
-    }
+    const uint8_t* e;
+    const uint8_t* const next = interval_walk(p, end, &e);
     bounds_out[2 * k] = (uint32_t)(p - data_host);
     bounds_out[2 * k + 1] = (uint32_t)(e - data_host);
-    if (k + 1 < n_iv) {
-      const uint8_t* q = e;
-      while (q + 1 < end && !(q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7)) ++q;
-      if (q + 1 >= end) return MSOCR_E_ARG;
-      p = q + 2;
-    }
+    if (k + 1 < n_iv && !next) return MSOCR_E_ARG;
+    p = next;
   }
   return n_iv;
 }
@@ -1363,12 +1419,11 @@ extern "C" int msocr_jpeg_entropy_decode_intervals_host(const uint8_t* bytes_hos
     status_host[pg] = 0;
     const int64_t coef_base = page_base_host[2 * pg], first_interval = page_base_host[2 * pg + 1];
     if (coef_base < 0 || coef_base + d.info.coef_total > coef_total || first_interval < 0) return MSOCR_E_ARG;
-    const int total = d.mcus_x * d.mcus_y;
     for (int iv = 0; iv < d.n_intervals; ++iv) {
       const int first = iv * d.restart_interval;
-      const int n = total - first < d.restart_interval ? total - first : d.restart_interval;
       if (decode_interval(d.info, d.mcus_x, d.dc, d.ac, d.zigzag, bytes_host + d.bytes_base, bounds_host[2 * (first_interval + iv)],
-                          bounds_host[2 * (first_interval + iv) + 1], first, n, coef_host + coef_base))
+                          bounds_host[2 * (first_interval + iv) + 1], first, interval_mcus(d.mcus_x * d.mcus_y, d.restart_interval, first),
+                          coef_host + coef_base))
         status_host[pg] = 1;
     }
   }
@@ -1459,11 +1514,10 @@ extern "C" int msocr_jpeg_entropy_decode_sync_host(const uint8_t* bytes_host, co
       if (st > status_host[pg]) status_host[pg] = st;
     }
     for (int c = 0; c < d.info.ncomp; ++c) {
-      const uint32_t bpm = (uint32_t)(d.info.hs[c] * d.info.vs[c]);
-      const uint32_t L = (uint32_t)(d.mcus_x * d.mcus_y) * bpm, seg = d.restart_interval > 0 ? (uint32_t)d.restart_interval * bpm : L;
+      const DcScan sc = sync_dc_scan(d, c);
       uint32_t run = 0;
-      for (uint32_t e = 0; e < L; ++e) {
-        if (e % seg == 0) run = 0;
+      for (uint32_t e = 0; e < sc.L; ++e) {
+        if (e % sc.seg == 0) run = 0;
         const int64_t at = sync_dc_addr(d, c, e);
         run += (uint32_t)(int32_t)coef[at];
         coef[at] = (int16_t)run;
@@ -1477,55 +1531,21 @@ extern "C" int64_t msocr_jpeg_workspace_bytes(const msocr_jpeg_info* info) { ret
 
 extern "C" int msocr_jpeg_reconstruct(const msocr_jpeg_info* info, const int16_t* coef_dev, void* workspace_dev, uint8_t* rgb_out_dev,
                                       void* stream) {
-  if (!info_ok(info) || !coef_dev || !workspace_dev || !rgb_out_dev || ((uintptr_t)workspace_dev & 15)) return MSOCR_E_ARG;
-  const Planes pl = make_planes(*info, (uint8_t*)workspace_dev);
-  if (launch_idct(info, coef_dev, pl, (hipStream_t)stream) != MSOCR_OK) return MSOCR_E_LAUNCH;
-  long g2 = ((long)info->width * info->height + 255) / 256;
-  if (g2 > 65535) g2 = 65535;
-  MSOCR_LAUNCH(jpeg_color_kernel, dim3((unsigned)g2), dim3(256), 0, (hipStream_t)stream, *info, pl, rgb_out_dev);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return reconstruct(info, 1, coef_dev, workspace_dev, rgb_out_dev, (hipStream_t)stream);
 }
 
 extern "C" int msocr_jpeg_reconstruct_host(const msocr_jpeg_info* info, const int16_t* coef_host, uint8_t* rgb_out_host) {
-  if (!info_ok(info) || !coef_host || !rgb_out_host) return MSOCR_E_ARG;
-  std::vector<uint8_t> ws((size_t)planes_bytes(*info));
-  const Planes pl = make_planes(*info, ws.data());
-  idct_planes_host(info, coef_host, pl);
-  for (int Y = 0; Y < info->height; ++Y)
-    for (int X = 0; X < info->width; ++X) pixel_rgb(*info, pl, X, Y, rgb_out_host + 3 * ((int64_t)Y * info->width + X));
-  return MSOCR_OK;
+  return reconstruct_host(info, 1, coef_host, rgb_out_host);
 }
 
-// The reconstruction with the Exif orientation applied in its last write.  1 = msocr_jpeg_reconstruct itself; 2..4 = the colour
-// loop with mirrored destinations; 5..8 = the tiled transposing colour kernel.  The IDCT stage and the workspace are the same.
+// The reconstruction with the Exif orientation applied in its last write; 1 = msocr_jpeg_reconstruct.  The IDCT stage and the
+// workspace are the same for every orientation.
 extern "C" int msocr_jpeg_reconstruct_oriented(const msocr_jpeg_info* info, int32_t orientation, const int16_t* coef_dev,
                                                void* workspace_dev, uint8_t* rgb_out_dev, void* stream) {
-  if (orientation < 1 || orientation > 8) return MSOCR_E_ARG;
-  if (orientation == 1) return msocr_jpeg_reconstruct(info, coef_dev, workspace_dev, rgb_out_dev, stream);
-  if (!info_ok(info) || !coef_dev || !workspace_dev || !rgb_out_dev || ((uintptr_t)workspace_dev & 15)) return MSOCR_E_ARG;
-  const Planes pl = make_planes(*info, (uint8_t*)workspace_dev);
-  if (launch_idct(info, coef_dev, pl, (hipStream_t)stream) != MSOCR_OK) return MSOCR_E_LAUNCH;
-  if (orient_transposes(orientation)) {
-    const dim3 grid((unsigned)((info->width + kOrientTile - 1) / kOrientTile), (unsigned)((info->height + kOrientTile - 1) / kOrientTile));
-    MSOCR_LAUNCH(jpeg_color_transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, *info, pl, (int)orientation, rgb_out_dev);
-  } else {
-    long g2 = ((long)info->width * info->height + 255) / 256;
-    if (g2 > 65535) g2 = 65535;
-    MSOCR_LAUNCH(jpeg_color_flip_kernel, dim3((unsigned)g2), dim3(256), 0, (hipStream_t)stream, *info, pl, (int)orientation, rgb_out_dev);
-  }
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return reconstruct(info, orientation, coef_dev, workspace_dev, rgb_out_dev, (hipStream_t)stream);
 }
 
 extern "C" int msocr_jpeg_reconstruct_oriented_host(const msocr_jpeg_info* info, int32_t orientation, const int16_t* coef_host,
                                                     uint8_t* rgb_out_host) {
-  if (orientation < 1 || orientation > 8) return MSOCR_E_ARG;
-  if (orientation == 1) return msocr_jpeg_reconstruct_host(info, coef_host, rgb_out_host);
-  if (!info_ok(info) || !coef_host || !rgb_out_host) return MSOCR_E_ARG;
-  std::vector<uint8_t> ws((size_t)planes_bytes(*info));
-  const Planes pl = make_planes(*info, ws.data());
-  idct_planes_host(info, coef_host, pl);
-  for (int Y = 0; Y < info->height; ++Y)
-    for (int X = 0; X < info->width; ++X)
-      pixel_rgb(*info, pl, X, Y, rgb_out_host + 3 * orient_dest(orientation, info->width, info->height, X, Y));
-  return MSOCR_OK;
+  return reconstruct_host(info, orientation, coef_host, rgb_out_host);
 }

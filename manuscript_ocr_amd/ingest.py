@@ -23,61 +23,59 @@ import numpy as np
 from . import _native as nat
 
 
-def _parse(data: bytes):
+def _parse_at(ptr, n, strict):
+    """Header parse of the n bytes at `ptr` -> (info or None, Exif orientation 1..8).  strict: msocr_jpeg_parse_host, which refuses a
+    stream with orientation 2..8 (the upright reconstruction is not its); else msocr_jpeg_parse_oriented_host, which reports it."""
     info = nat.JpegInfo()
-    buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
-    rc = nat.lib().msocr_jpeg_parse_host(ctypes.addressof(buf), len(data), ctypes.byref(info))
+    orient = ctypes.c_int32(1)
+    if strict:
+        rc = nat.lib().msocr_jpeg_parse_host(ptr, n, ctypes.byref(info))
+    else:
+        rc = nat.lib().msocr_jpeg_parse_oriented_host(ptr, n, ctypes.byref(info), ctypes.byref(orient))
     if rc != 0 or not info.supported:
-        return None, buf
-    return info, buf
+        return None, 1
+    return info, int(orient.value)
+
+
+def _parse(data: bytes):
+    buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
+    return _parse_at(ctypes.addressof(buf), len(data), True)[0], buf
 
 
 def _parse_oriented(data: bytes):
     """`_parse` for the product paths: streams with an Exif orientation are taken too -> (info or None, buffer, orientation 1..8)."""
-    info = nat.JpegInfo()
-    orient = ctypes.c_int32(1)
     buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
-    rc = nat.lib().msocr_jpeg_parse_oriented_host(ctypes.addressof(buf), len(data), ctypes.byref(info), ctypes.byref(orient))
-    if rc != 0 or not info.supported:
-        return None, buf, 1
-    return info, buf, int(orient.value)
+    info, orient = _parse_at(ctypes.addressof(buf), len(data), False)
+    return info, buf, orient
 
 
 def _oriented_shape(info, orientation):
     return (info.width, info.height, 3) if orientation >= 5 else (info.height, info.width, 3)
 
 
+def _serial_decode(ptr, n, info, coef=None):
+    """The serial host decoder — the judge of every stream — on the n bytes at `ptr`, into `coef` (a fresh array when None)
+    -> the int16 coefficient array, or None for a bad stream."""
+    if coef is None:
+        coef = np.empty(int(info.coef_total), dtype=np.int16)
+    rc = nat.lib().msocr_jpeg_entropy_decode_host(ptr, n, ctypes.byref(info), coef.ctypes.data)
+    return coef if rc == 0 else None
+
+
 def jpeg_coefficients(data: bytes):
     """Host stage: (info, int16 coefficient array) of a supported JPEG, or None."""
     info, buf = _parse(data)
-    if info is None:
-        return None
-    coef = np.empty(int(info.coef_total), dtype=np.int16)
-    rc = nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data)
-    if rc != 0:
-        return None
-    return info, coef
+    coef = None if info is None else _serial_decode(ctypes.addressof(buf), len(data), info)
+    return None if coef is None else (info, coef)
 
 
-def decode_jpeg_host(data: bytes):
-    """The whole decode on the CPU through the host twin of the device stage (tests; not a product path)."""
-    r = jpeg_coefficients(data)
-    if r is None:
-        return None
-    info, coef = r
-    out = np.empty((info.height, info.width, 3), dtype=np.uint8)
-    nat.check(nat.lib().msocr_jpeg_reconstruct_host(ctypes.byref(info), coef.ctypes.data, out.ctypes.data), "jpeg_reconstruct_host")
-    return out
-
-
-def decode_jpeg_oriented_host(data: bytes):
-    """`decode_jpeg_host` with the Exif orientation applied: oriented parse, host entropy decoder, host twin of the oriented
-    reconstruction (tests; not a product path) -> what read_image returns for the file, or None."""
-    info, buf, orient = _parse_oriented(data)
-    if info is None:
-        return None
-    coef = np.empty(int(info.coef_total), dtype=np.int16)
-    if nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data) != 0:
+def _decode_host(data, strict):
+    """The whole decode on the CPU: parse (`strict`: see `_parse_at`), host entropy decoder, host twin of the oriented
+    reconstruction -> what read_image returns for the file, or None."""
+    buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
+    info, orient = _parse_at(ctypes.addressof(buf), len(data), strict)
+    coef = None if info is None else _serial_decode(ctypes.addressof(buf), len(data), info)
+    if coef is None:
         return None
     out = np.empty(_oriented_shape(info, orient), dtype=np.uint8)
     nat.check(nat.lib().msocr_jpeg_reconstruct_oriented_host(ctypes.byref(info), orient, coef.ctypes.data, out.ctypes.data),
@@ -85,62 +83,47 @@ def decode_jpeg_oriented_host(data: bytes):
     return out
 
 
-def decode_jpeg_device(data: bytes, device="cuda", device_entropy=True):
-    """JPEG bytes -> u8 tensor on the device (current stream), [H, W, 3] or, for Exif orientations 5..8, [W, H, 3] — the page as
-    read_image returns it — or None when the stream is not supported.  A stream with
-    a restart interval takes the per-interval Huffman kernel, one without the self-synchronising stage (a stream that stage
-    declines, status 2, goes on to the host decoder); `device_entropy=False`: the host decoder for every stream."""
-    import torch
-
-    from . import ops
-    info, buf, orient = _parse_oriented(data)
-    if info is None:
-        return None
-    if device_entropy:
-        batch = ScanBatch([(info, buf, len(data))])
-        if batch.n_pages:
-            coef, status = entropy_batch_device(batch, device)
-            img = _reconstruct(info, coef, device, torch, ops, orient)
-            return img if int(status.cpu()[0]) == 0 else None
-        batch = SyncBatch([(info, buf, len(data))])
-        if batch.n_pages:
-            coef, status, _ = entropy_sync_batch_device(batch, device)
-            st = int(status.cpu()[0])
-            if st != 2:
-                return _reconstruct(info, coef, device, torch, ops, orient) if st == 0 else None
-    coef = np.empty(int(info.coef_total), dtype=np.int16)
-    if nat.lib().msocr_jpeg_entropy_decode_host(ctypes.addressof(buf), len(data), ctypes.byref(info), coef.ctypes.data) != 0:
-        return None
-    return _reconstruct(info, torch.from_numpy(coef).to(device, non_blocking=True), device, torch, ops, orient)
+def decode_jpeg_oriented_host(data: bytes):
+    """The whole decode on the CPU through the host twin of the device stage, the Exif orientation applied (tests; not a product
+    path)."""
+    return _decode_host(data, strict=False)
 
 
-def _prepare(ptr, n, info, bytes_base):
-    """Marker walk of one parsed stream -> (descriptor bytes, interval bounds) or None (no restart interval / host decoder's case)."""
+def decode_jpeg_host(data: bytes):
+    """`decode_jpeg_oriented_host` with the strict parse: a stream with an Exif orientation 2..8 gives None."""
+    return _decode_host(data, strict=True)
+
+
+def _prepare(ptr, n, info, bytes_base, sync):
+    """Marker walk of one parsed stream -> (descriptor bytes, interval bounds) or None (the host decoder's case).  sync=False: the
+    per-interval kernel's walk, which also refuses a stream without a restart interval; True: the self-synchronising stage's,
+    which takes such a stream as one interval of all its MCUs."""
     lib = nat.lib()
+    walk = lib.msocr_jpeg_sync_prepare_host if sync else lib.msocr_jpeg_scan_prepare_host
     mcus = (int(info.blocks_w[0]) // int(info.hs[0])) * (int(info.blocks_h[0]) // int(info.vs[0]))
     d = np.zeros(int(lib.msocr_jpeg_scan_desc_bytes()), dtype=np.uint8)
     b = np.empty(2 * mcus, dtype=np.uint32)   # at most one interval per MCU
-    niv = int(lib.msocr_jpeg_scan_prepare_host(ptr, n, ctypes.byref(info), bytes_base, d.ctypes.data, b.ctypes.data, mcus))
+    niv = int(walk(ptr, n, ctypes.byref(info), bytes_base, d.ctypes.data, b.ctypes.data, mcus))
     return None if niv <= 0 else (d, b[: 2 * niv])
 
 
-class ScanBatch:
-    """Host side of the device entropy decode for a batch of parsed streams: descriptors, interval bounds, per-page bases and the
-    files' bytes laid out as msocr_jpeg_entropy_decode_device takes them.  `pages[i]` = index into `descs` of stream i, or -1 (no
-    restart interval, or a marker sequence the host decoder must judge).  `parsed[i]` = (info, ctypes buffer, length) or None;
-    `prepared[i]` (optional) = what `_prepare` returned for stream i with `bytes_base[i]` as its base inside `bytes`."""
+class _Batch:
+    """Host side of a device entropy stage for a batch of parsed streams: descriptors, interval bounds, per-page bases and the
+    files' bytes laid out as the stage's entry takes them.  `parsed[i]` = (info, ctypes buffer, length) or None; `prepared[i]`
+    (optional) = what `_prepare` returned for stream i with `bytes_base[i]` as its base inside `bytes_`.  `pages[i]` = index into
+    `descs` of stream i, or -1.  A subclass names its walk (`_sync`), its file-size cap (`_max_file`) and, in `_page`, the columns
+    it adds to a page's row of `page_base` behind (coefficient base, first interval)."""
+    _max_file = None
 
     def __init__(self, parsed, prepared=None, bytes_=None):
         self.pages, self.infos = [], []
-        descs, bounds, chunks, base = [], [], [], []
+        descs, bounds, chunks, rows = [], [], [], []
         pos = coef_base = first = 0
-        self.max_intervals = 0
         for i, pr in enumerate(parsed):
-            if pr is None:
-                self.pages.append(-1)
-                continue
-            info, buf, n = pr
-            r = prepared[i] if prepared is not None else _prepare(ctypes.addressof(buf), n, info, pos)
+            r = None
+            if pr is not None and (self._max_file is None or pr[2] <= self._max_file):
+                info, buf, n = pr
+                r = prepared[i] if prepared is not None else _prepare(ctypes.addressof(buf), n, info, pos, self._sync)
             if r is None:
                 self.pages.append(-1)
                 continue
@@ -148,7 +131,7 @@ class ScanBatch:
             self.infos.append((info, coef_base))
             descs.append(r[0])
             bounds.append(r[1])
-            base.append((coef_base, first))
+            rows.append((coef_base, first) + self._page(r[1]))
             if prepared is None:
                 chunks.append(np.frombuffer(buf, dtype=np.uint8, count=n))
                 pad = (-n) % 16
@@ -157,14 +140,40 @@ class ScanBatch:
                 pos += n + pad
             coef_base += int(info.coef_total)
             first += len(r[1]) // 2
-            self.max_intervals = max(self.max_intervals, len(r[1]) // 2)
         self.n_pages = len(descs)
         self.coef_total = coef_base
         if self.n_pages:
             self.descs = np.stack(descs)
             self.bounds = np.concatenate(bounds)
-            self.page_base = np.array(base, dtype=np.int64)
+            self.page_base = np.array(rows, dtype=np.int64)
             self.bytes = bytes_ if prepared is not None else np.concatenate(chunks)
+
+
+class ScanBatch(_Batch):
+    """The batch of the per-interval kernel (msocr_jpeg_entropy_decode_device).  `pages[i]` = -1: no restart interval, or a marker
+    sequence the host decoder must judge.  `page_base` is [n_pages][2]."""
+    _sync = False
+
+    def __init__(self, parsed, prepared=None, bytes_=None):
+        self.max_intervals = 0
+        super().__init__(parsed, prepared, bytes_)
+
+    def _page(self, bounds):
+        self.max_intervals = max(self.max_intervals, len(bounds) // 2)
+        return ()
+
+
+def _upload(batch, device, bytes_dev, *more):
+    """What the two device stages share: the batch's file bytes on the device (uploaded unless `bytes_dev` already holds them),
+    its descriptors, interval bounds, page bases and the arrays in `more`, and fresh coefficient and status tensors
+    -> (bytes, [descs, bounds, page_base, *more], coef, status)."""
+    import torch
+    if bytes_dev is None:
+        bytes_dev = torch.from_numpy(batch.bytes).pin_memory().to(device, non_blocking=True)
+    tables = [torch.from_numpy(a).to(device) for a in (batch.descs, batch.bounds, batch.page_base) + more]
+    coef = torch.empty(batch.coef_total, dtype=torch.int16, device=device)
+    status = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
+    return bytes_dev, tables, coef, status
 
 
 def entropy_batch_host_twin(batch: ScanBatch):
@@ -181,17 +190,10 @@ def entropy_batch_device(batch: ScanBatch, device="cuda", bytes_dev=None):
     """Uploads the batch's file bytes (unless `bytes_dev` already holds them), descriptors and interval bounds and runs the Huffman
     stage on the device (current stream) -> (int16 coefficient tensor of the batch, int32 status tensor [n_pages]); nothing is
     waited for."""
-    import torch
-
     from . import ops
-    up = lambda a: torch.from_numpy(a).to(device)
-    if bytes_dev is None:
-        bytes_dev = torch.from_numpy(batch.bytes).pin_memory().to(device, non_blocking=True)
-    descs_dev, bounds_dev, base_dev = up(batch.descs), up(batch.bounds), up(batch.page_base)
-    coef = torch.empty(batch.coef_total, dtype=torch.int16, device=device)
-    status = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
-    nat.check(nat.lib().msocr_jpeg_entropy_decode_device(bytes_dev.data_ptr(), descs_dev.data_ptr(), batch.n_pages, batch.max_intervals,
-                                                          bounds_dev.data_ptr(), base_dev.data_ptr(), coef.data_ptr(), batch.coef_total,
+    bytes_dev, (descs, bounds, base), coef, status = _upload(batch, device, bytes_dev)
+    nat.check(nat.lib().msocr_jpeg_entropy_decode_device(bytes_dev.data_ptr(), descs.data_ptr(), batch.n_pages, batch.max_intervals,
+                                                          bounds.data_ptr(), base.data_ptr(), coef.data_ptr(), batch.coef_total,
                                                           status.data_ptr(), ops._stream()), "jpeg_entropy_decode_device")
     return coef, status
 
@@ -199,70 +201,40 @@ def entropy_batch_device(batch: ScanBatch, device="cuda", bytes_dev=None):
 SYNC_SUBSEQ_BYTES = 256    # a few times the distance page-like streams need to fall into step
 SYNC_MAX_ROUNDS = 16
 SYNC_MAX_FILE = 0x1ff00000  # the stage keeps bit positions in 32 bits
-# Default route (device_entropy=None) of streams without a restart interval and of intervals longer than
-# MSOCR_JPEG_DEVICE_MAX_INTERVAL: the self-synchronising stage when True, the host pool when False.  True by the measurement in
-# profiles/jpeg_sync_huffman.txt: 6.4-7.0 ms per batch of 16 pages against 14.9-18.1 ms for the host pool.
-SYNC_BY_DEFAULT = True
+# The longest restart interval (bytes) the per-interval kernel takes by default: one thread decodes an interval, and its serial
+# chain loses to a host core when the interval is long (1.8 ms per KB of interval on the device against ~15 ms per 1.6 MB file on
+# a host core).  Longer intervals, like streams without a restart interval, take the self-synchronising stage by default:
+# profiles/jpeg_sync_huffman.txt measured it at 6.4-7.0 ms per batch of 16 pages against 14.9-18.1 ms for the
+# host pool.
+DEVICE_MAX_INTERVAL = 8192
 
 
-def _prepare_sync(ptr, n, info, bytes_base):
-    """`_prepare` for the self-synchronising stage: a stream without a restart interval is one interval of all its MCUs."""
-    lib = nat.lib()
-    mcus = (int(info.blocks_w[0]) // int(info.hs[0])) * (int(info.blocks_h[0]) // int(info.vs[0]))
-    d = np.zeros(int(lib.msocr_jpeg_scan_desc_bytes()), dtype=np.uint8)
-    b = np.empty(2 * mcus, dtype=np.uint32)
-    niv = int(lib.msocr_jpeg_sync_prepare_host(ptr, n, ctypes.byref(info), bytes_base, d.ctypes.data, b.ctypes.data, mcus))
-    return None if niv <= 0 else (d, b[: 2 * niv])
-
-
-class SyncBatch:
+class SyncBatch(_Batch):
     """`ScanBatch` for the self-synchronising Huffman stage (msocr_jpeg_entropy_decode_sync_device): takes streams with and without
     a restart interval and lays out, beside descriptors / interval bounds / bytes, the subsequences of `subseq_bytes` bytes every
-    interval is cut into (`sub_first`, `page_base` [n_pages][4], `max_subseq`, `total_subseq`).  `pages[i]` = index into `descs` of
-    stream i, or -1 (a marker sequence the host decoder must judge, a file too large for 32-bit bit positions)."""
+    interval is cut into (`sub_first`, `page_base` [n_pages][4], `max_subseq`, `total_subseq`).  `pages[i]` = -1: a marker sequence
+    the host decoder must judge, a file too large for 32-bit bit positions."""
+    _sync = True
+    _max_file = SYNC_MAX_FILE
 
     def __init__(self, parsed, prepared=None, bytes_=None, subseq_bytes=SYNC_SUBSEQ_BYTES):
-        self.pages, self.infos = [], []
         self.subseq_bytes = int(subseq_bytes)
-        descs, bounds, sub_first, chunks, base = [], [], [], [], []
-        pos = coef_base = first = sub_base = 0
-        self.max_subseq = 0
-        for i, pr in enumerate(parsed):
-            r = None
-            if pr is not None and pr[2] <= SYNC_MAX_FILE:
-                info, buf, n = pr
-                r = prepared[i] if prepared is not None else _prepare_sync(ctypes.addressof(buf), n, info, pos)
-            if r is None:
-                self.pages.append(-1)
-                continue
-            self.pages.append(len(descs))
-            self.infos.append((info, coef_base))
-            descs.append(r[0])
-            bounds.append(r[1])
-            length = r[1][1::2].astype(np.int64) - r[1][0::2].astype(np.int64)
-            nsub = np.maximum(1, -(-length // self.subseq_bytes))
-            sub_first.append((np.cumsum(nsub) - nsub).astype(np.uint32))
-            nsub = int(nsub.sum())
-            base.append((coef_base, first, sub_base, nsub))
-            if prepared is None:
-                chunks.append(np.frombuffer(buf, dtype=np.uint8, count=n))
-                pad = (-n) % 16
-                if pad:
-                    chunks.append(np.zeros(pad, dtype=np.uint8))
-                pos += n + pad
-            coef_base += int(info.coef_total)
-            first += len(r[1]) // 2
-            sub_base += nsub
-            self.max_subseq = max(self.max_subseq, nsub)
-        self.n_pages = len(descs)
-        self.coef_total = coef_base
-        self.total_subseq = sub_base
+        self.max_subseq = self.total_subseq = 0
+        self._sub_first = []
+        super().__init__(parsed, prepared, bytes_)
         if self.n_pages:
-            self.descs = np.stack(descs)
-            self.bounds = np.concatenate(bounds)
-            self.sub_first = np.concatenate(sub_first)
-            self.page_base = np.array(base, dtype=np.int64)
-            self.bytes = bytes_ if prepared is not None else np.concatenate(chunks)
+            self.sub_first = np.concatenate(self._sub_first)
+        del self._sub_first
+
+    def _page(self, bounds):
+        length = bounds[1::2].astype(np.int64) - bounds[0::2].astype(np.int64)
+        nsub = np.maximum(1, -(-length // self.subseq_bytes))
+        self._sub_first.append((np.cumsum(nsub) - nsub).astype(np.uint32))
+        nsub = int(nsub.sum())
+        row = (self.total_subseq, nsub)
+        self.total_subseq += nsub
+        self.max_subseq = max(self.max_subseq, nsub)
+        return row
 
 
 def entropy_sync_batch_host_twin(batch: SyncBatch, max_rounds=SYNC_MAX_ROUNDS):
@@ -286,18 +258,13 @@ def entropy_sync_batch_device(batch: SyncBatch, device="cuda", bytes_dev=None, m
     import torch
 
     from . import ops
-    up = lambda a: torch.from_numpy(a).to(device)
-    if bytes_dev is None:
-        bytes_dev = torch.from_numpy(batch.bytes).pin_memory().to(device, non_blocking=True)
-    descs_dev, bounds_dev, sub_dev, base_dev = up(batch.descs), up(batch.bounds), up(batch.sub_first), up(batch.page_base)
-    coef = torch.empty(batch.coef_total, dtype=torch.int16, device=device)
-    status = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
+    bytes_dev, (descs, bounds, base, sub), coef, status = _upload(batch, device, bytes_dev, batch.sub_first)
     rounds = torch.empty(batch.n_pages, dtype=torch.int32, device=device)
     lib = nat.lib()
     ws = torch.empty(int(lib.msocr_jpeg_sync_workspace_bytes(batch.total_subseq, batch.n_pages, int(max_rounds))), dtype=torch.uint8,
                      device=device)
-    nat.check(lib.msocr_jpeg_entropy_decode_sync_device(bytes_dev.data_ptr(), descs_dev.data_ptr(), batch.n_pages, bounds_dev.data_ptr(),
-                                                        sub_dev.data_ptr(), base_dev.data_ptr(), batch.max_subseq, batch.total_subseq,
+    nat.check(lib.msocr_jpeg_entropy_decode_sync_device(bytes_dev.data_ptr(), descs.data_ptr(), batch.n_pages, bounds.data_ptr(),
+                                                        sub.data_ptr(), base.data_ptr(), batch.max_subseq, batch.total_subseq,
                                                         batch.subseq_bytes, int(max_rounds), coef.data_ptr(), batch.coef_total,
                                                         status.data_ptr(), rounds.data_ptr(), ws.data_ptr(), ops._stream()),
               "jpeg_entropy_decode_sync_device")
@@ -327,11 +294,40 @@ def _read_and_parse(path):
     return None if info is None else (info, buf, len(data))
 
 
+def route(restart, longest_interval, size, interval_ok, sync_ok, device_entropy):
+    """Which Huffman decoder a file takes: "interval" (the per-interval kernel), "sync" (the self-synchronising stage) or "host"
+    (the serial decoder on the host pool).  The one place that knows the table in `read_images_device`'s docstring.
+    restart: the stream has a restart interval; longest_interval: its longest interval in bytes; size: the file's bytes;
+    interval_ok / sync_ok: the marker walk of that stage accepted the stream; device_entropy: False / True / None (default)."""
+    if device_entropy is False:
+        return "host"
+    sync = "sync" if sync_ok and size <= SYNC_MAX_FILE else "host"
+    if not (restart and interval_ok):
+        return sync
+    if device_entropy is None and longest_interval > DEVICE_MAX_INTERVAL:
+        return sync
+    return "interval"
+
+
 _POOL = None
 _SLOTS = {}   # slot -> [pinned tensor, event of the last upload from it]; reused across batches (one reader thread at a time)
 
 
+def _pool():
+    global _POOL
+    if _POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+
+        # one process per GPU: the ranks of a node share its cores (LOCAL_WORLD_SIZE is set by torch.distributed.run)
+        share = (os.cpu_count() or 2) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+        _POOL = ThreadPoolExecutor(max_workers=max(1, min(32, share - 1)), thread_name_prefix="msocr-jpeg")
+    return _POOL
+
+
 def _slot_buffer(slot, n, torch, dtype=None):
+    """The pinned buffer of `slot` with room for n elements; slot None: a fresh pageable one that nobody shares."""
+    if slot is None:
+        return [torch.empty(n, dtype=dtype or torch.int16), None]
     ent = _SLOTS.get(slot)
     if ent is None or ent[0].numel() < n:
         ent = _SLOTS[slot] = [torch.empty(n + n // 4, dtype=dtype or torch.int16).pin_memory(), None]
@@ -340,10 +336,24 @@ def _slot_buffer(slot, n, torch, dtype=None):
     return ent
 
 
-def _load(path, arr, off, n, want_device):
-    """Worker: file -> its slice of the pinned batch buffer, header parse, marker walk.
-    -> (info, `_prepare` result or None, `_prepare_sync` result of a stream without restart interval or None, Exif orientation)
-    or None."""
+def _stream(ptr, n, base, walks):
+    """Header parse and marker walks of the stream of n bytes at `ptr`, `base` bytes into its batch buffer
+    -> (info, per-interval `_prepare` result or None, self-synchronising one or None, Exif orientation) or None."""
+    info, orient = _parse_at(ptr, n, strict=False)
+    if info is None:
+        return None
+    if not walks:
+        return info, None, None, orient
+    iv = _prepare(ptr, n, info, base, sync=False)
+    if iv is not None or n > SYNC_MAX_FILE:
+        # with a restart interval the two walks are one walk and give one descriptor
+        return info, iv, (iv if n <= SYNC_MAX_FILE else None), orient
+    # no restart interval (or a marker sequence both walks refuse): the self-synchronising stage's view of the stream
+    return info, None, _prepare(ptr, n, info, base, sync=True), orient
+
+
+def _load(path, arr, off, n, walks):
+    """Worker: file -> its slice of the pinned batch buffer, then `_stream`; None for a file that cannot be read / is no JPEG."""
     try:
         with open(path, "rb") as f:
             if f.readinto(memoryview(arr[off: off + n])) != n:
@@ -352,16 +362,126 @@ def _load(path, arr, off, n, want_device):
         return None
     if n < 4 or arr[off] != 0xFF or arr[off + 1] != 0xD8:
         return None
-    info = nat.JpegInfo()
-    orient = ctypes.c_int32(1)
-    ptr = arr.ctypes.data + off
-    if nat.lib().msocr_jpeg_parse_oriented_host(ptr, n, ctypes.byref(info), ctypes.byref(orient)) != 0 or not info.supported:
+    return _stream(arr.ctypes.data + off, n, off, walks)
+
+
+def _load_batch(paths, walks, torch):
+    """Lays the files out in ONE pinned batch buffer (16-byte aligned slices, reused across batches) and reads + parses + walks
+    them on the pool -> (buffer entry, offsets, sizes, total bytes, `_stream` result per file) or None for a batch without files."""
+    sizes = [os.path.getsize(p) if isinstance(p, (str, os.PathLike)) and os.path.isfile(p) else -1 for p in paths]
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += (max(n, 0) + 15) // 16 * 16
+    if total == 0:
         return None
-    if not want_device:
-        return info, None, None, int(orient.value)
-    pr = _prepare(ptr, n, info, off)
-    # no restart interval (or a marker sequence both walks refuse): the self-synchronising stage's view of the stream
-    return info, pr, (_prepare_sync(ptr, n, info, off) if pr is None and n <= SYNC_MAX_FILE else None), int(orient.value)
+    ent = _slot_buffer("bytes", total, torch, torch.uint8)
+    arr = ent[0].numpy()
+    jobs = [(_pool().submit(_load, p, arr, o, n, walks) if n >= 0 else None) for p, o, n in zip(paths, offs, sizes)]
+    return ent, offs, sizes, total, [j.result() if j is not None else None for j in jobs]
+
+
+def _routes(streams, sizes, device_entropy):
+    out = []
+    for s, n in zip(streams, sizes):
+        if s is None:
+            out.append(None)
+            continue
+        iv = s[1]
+        longest = int((iv[1][1::2] - iv[1][0::2]).max()) if iv is not None else 0
+        # the per-interval walk refuses a stream without a restart interval: what it took has one
+        out.append(route(iv is not None, longest, n, iv is not None, s[2] is not None, device_entropy))
+    return out
+
+
+def _device_stages(streams, routes, sizes, arr, upload, device, torch, ops):
+    """Runs the Huffman stage of every file routed to the device — at most two launch sequences per batch — and its reconstruction
+    -> ({file index: image tensor}, those indices in status order, status tensor or None).  `upload()` puts `arr` on the device."""
+    parsed = [None if s is None else (s[0], None, n) for s, n in zip(streams, sizes)]
+    runs = []                    # (batch, coefficient tensor, status tensor): both Huffman stages are queued before any reconstruction
+    bytes_dev = None
+    for cls, name, col, run in ((ScanBatch, "interval", 1, entropy_batch_device), (SyncBatch, "sync", 2, entropy_sync_batch_device)):
+        prepared = [s[col] if r == name else None for s, r in zip(streams, routes)]
+        batch = cls(parsed, prepared, arr) if any(p is not None for p in prepared) else None
+        if batch is None or not batch.n_pages:
+            continue
+        if bytes_dev is None:
+            bytes_dev = upload()
+        runs.append((batch,) + tuple(run(batch, device, bytes_dev)[:2]))
+    imgs, idx = {}, []
+    for batch, coef, _ in runs:
+        for i, k in enumerate(batch.pages):
+            if k >= 0:
+                info, base = batch.infos[k]
+                imgs[i] = _reconstruct(info, coef[base:], device, torch, ops, streams[i][3])
+                idx.append(i)
+    return imgs, idx, (None if not runs else runs[0][2] if len(runs) == 1 else torch.cat([r[2] for r in runs]))
+
+
+def _verdict(imgs, idx, status, defer, torch):
+    """The kernels' per-page verdict, taken (the device path's one host wait) or deferred -> ({file index: tensor or None} of the
+    files that are done with, `check_pending`'s argument or None)."""
+    if status is None:
+        return {}, None
+    if defer:
+        st_host = torch.empty(len(idx), dtype=torch.int32).pin_memory()
+        st_host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return imgs, (st_host, ev, idx)
+    # 1: a bad stream goes to the host reader, as the host decoder's verdict would send it; 2: declined, not judged: the host
+    # stage decodes it
+    return {i: (imgs[i] if st == 0 else None) for i, st in zip(idx, status.cpu().tolist()) if st != 2}, None
+
+
+def _host_stage(streams, todo, offs, sizes, arr, pinned, device, torch, ops):
+    """The serial decoder on the pool for the files in `todo`, one page per core, then their reconstruction -> {file index: tensor
+    or None}.  pinned: decode into the per-slot PINNED coefficient buffers that live across batches (fresh 9 MB arrays per page made
+    the threads serialise on page faults); else into fresh arrays (a caller that may not be the one reader thread).  This thread
+    uploads and launches the reconstruction page by page as the decodes finish."""
+    jobs = []
+    for i in todo:
+        info = streams[i][0]
+        total = int(info.coef_total)
+        slot = _slot_buffer(i if pinned else None, total, torch)   # main thread: allocation / pinning is not done from the workers
+        jobs.append((i, info, total, slot, _pool().submit(_serial_decode, arr.ctypes.data + offs[i], sizes[i], info, slot[0].numpy()[:total])))
+    out = {}
+    for i, info, total, slot, job in jobs:
+        if job.result() is None:
+            out[i] = None
+            continue
+        coef_dev = slot[0][:total].to(device, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        out[i] = _reconstruct(info, coef_dev, device, torch, ops, streams[i][3])
+    return out
+
+
+def _decode_streams(streams, offs, sizes, arr, upload, pinned, device, device_entropy, defer_status):
+    """Route, device stages + reconstruction, verdict, host stage for the rest: `streams[i]` = `_stream`'s result for the sizes[i]
+    bytes at arr[offs[i]] -> (tensor or None per stream, pending verdict or None)."""
+    import torch
+
+    from . import ops
+    routes = _routes(streams, sizes, device_entropy)
+    imgs, idx, status = _device_stages(streams, routes, sizes, arr, upload, device, torch, ops)
+    done, pending = _verdict(imgs, idx, status, defer_status, torch)
+    todo = [i for i, s in enumerate(streams) if s is not None and i not in done]
+    done.update(_host_stage(streams, todo, offs, sizes, arr, pinned, device, torch, ops))
+    return [done.get(i) for i in range(len(streams))], pending
+
+
+def decode_jpeg_device(data: bytes, device="cuda", device_entropy=True):
+    """JPEG bytes -> u8 tensor on the device (current stream), [H, W, 3] or, for Exif orientations 5..8, [W, H, 3] — the page as
+    read_image returns it — or None when the stream is not supported.  The one-stream case of `read_images_device`, with the
+    "True" column of its table as the default: a stream with a restart interval takes the per-interval Huffman kernel, one
+    without the self-synchronising stage (a stream that stage declines, status 2, goes on to the host decoder);
+    `device_entropy=False`: the host decoder for every stream."""
+    import torch
+    arr = np.frombuffer(bytearray(data), dtype=np.uint8)
+    upload = lambda: torch.from_numpy(arr).pin_memory().to(device, non_blocking=True)
+    stream = _stream(arr.ctypes.data, len(data), 0, device_entropy is not False)
+    return _decode_streams([stream], [0], [len(data)], arr, upload, False, device, device_entropy, False)[0][0]
 
 
 def check_pending(pending):
@@ -379,115 +499,35 @@ def read_images_device(paths, device="cuda", device_entropy=None, defer_status=F
     """A batch of files -> list of device RGB tensors (None where read_image must take over).
     A thread pool reads every file into its slice of ONE pinned batch buffer (reused across batches), parses its headers and walks
     its markers (the ctypes calls release the GIL).  The buffer is uploaded as it is and the Huffman stage of the batch is at most
-    two launch sequences.  Routes (`device_entropy=True` / False or MSOCR_JPEG_DEVICE_ENTROPY=1 / 0 force the device / the host):
+    two launch sequences.  Routes (`route`; `device_entropy=True` / False force the device / the host):
 
-        file                                          False   True                  None (default)
-        no restart interval                           host    self-synchronising    self-synchronising if SYNC_BY_DEFAULT, else host
-        intervals <= MSOCR_JPEG_DEVICE_MAX_INTERVAL   host    per-interval kernel   per-interval kernel
-        longer intervals                              host    per-interval kernel   self-synchronising if SYNC_BY_DEFAULT, else host
+        file                               False   True                  None (default)
+        no restart interval                host    self-synchronising    self-synchronising
+        intervals <= DEVICE_MAX_INTERVAL   host    per-interval kernel   per-interval kernel
+        longer intervals                   host    per-interval kernel   self-synchronising
 
-    Per-interval kernel (`entropy_batch_device`): one thread per restart interval; its serial chain loses to a host core when an
-    interval is long (MSOCR_JPEG_DEVICE_MAX_INTERVAL bytes, default 8192: 1.8 ms per KB of interval on the device against ~15 ms per
-    1.6 MB file on a host core).  Self-synchronising stage (`entropy_sync_batch_device`): one thread per SYNC_SUBSEQ_BYTES bytes of
-    a serial segment; a page it declines (status 2: no fixed point within SYNC_MAX_ROUNDS rounds, or a truncated stream) is decoded
-    by the host pool inside this call, as every page of the "host" column is: the pool decodes one page per core into per-slot
-    PINNED coefficient buffers that live across batches (fresh 9 MB arrays per page made the threads serialise on page faults),
-    this thread uploads and launches the reconstruction page by page as the decodes finish.  The pixels are the same on every route.
+    Per-interval kernel (`entropy_batch_device`): one thread per restart interval.  Self-synchronising stage
+    (`entropy_sync_batch_device`): one thread per SYNC_SUBSEQ_BYTES bytes of a serial segment; a file it cannot take (a marker
+    sequence its walk refuses, more than SYNC_MAX_FILE bytes) goes to the host, and a page it declines (status 2: no fixed point
+    within SYNC_MAX_ROUNDS rounds, or a truncated stream) is decoded by the host pool inside this call, as every page of the "host"
+    column is (`_host_stage`).  The pixels are the same on every route.
     A file with an Exif orientation 2..8 takes the row of the table its restart intervals put it in, like an upright one: the
     orientation only changes the last write of its reconstruction (and the shape of its tensor: [W, H, 3] for 5..8).
     defer_status=True -> (list, pending): the device path's one host wait — the kernels' per-page verdict — is NOT taken here; the
     caller asks `check_pending(pending)` later (the pipeline does, when it waits for the detector anyway), so that submitting a
     batch never waits for the device; bad and declined pages are both reported there."""
-    global _POOL
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-
-    from . import ops
-    env = os.environ.get("MSOCR_JPEG_DEVICE_ENTROPY")
-    if device_entropy is None and env is not None:
-        device_entropy = env != "0"
-    max_iv = int(os.environ.get("MSOCR_JPEG_DEVICE_MAX_INTERVAL", "8192"))
-    if _POOL is None:
-        # one process per GPU: the ranks of a node share its cores (LOCAL_WORLD_SIZE is set by torch.distributed.run)
-        share = (os.cpu_count() or 2) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
-        _POOL = ThreadPoolExecutor(max_workers=max(1, min(32, share - 1)), thread_name_prefix="msocr-jpeg")
-    sizes = [os.path.getsize(p) if isinstance(p, (str, os.PathLike)) and os.path.isfile(p) else -1 for p in paths]
-    offs, total = [], 0
-    for n in sizes:
-        offs.append(total)
-        total += (max(n, 0) + 15) // 16 * 16
-    pending = None
-    if total == 0:
+    batch = _load_batch(paths, device_entropy is not False, torch)
+    if batch is None:
         return ([None] * len(paths), None) if defer_status else [None] * len(paths)
-    ent = _slot_buffer("bytes", total, torch, torch.uint8)
-    arr = ent[0].numpy()
-    want = device_entropy is not False
-    jobs = [(_POOL.submit(_load, p, arr, o, n, want) if n >= 0 else None) for p, o, n in zip(paths, offs, sizes)]
-    loaded = [j.result() if j is not None else None for j in jobs]
-    on_dev = {}
-    if want:
-        per_iv = [None if r is None else r[1] for r in loaded]          # the per-interval kernel's pages ...
-        sync = [None if r is None else r[2] for r in loaded]            # ... and the self-synchronising stage's
-        if device_entropy is None:   # the policy: no interval of the page longer than max_iv bytes
-            long_iv = [p is not None and int((p[1][1::2] - p[1][0::2]).max()) > max_iv for p in per_iv]
-            if SYNC_BY_DEFAULT:
-                sync = [p if lg and n <= SYNC_MAX_FILE else q for p, q, lg, n in zip(per_iv, sync, long_iv, sizes)]
-            else:
-                sync = [None] * len(loaded)
-            per_iv = [None if lg else p for p, lg in zip(per_iv, long_iv)]
-        parsed = [None if r is None else (r[0], None, n) for r, n in zip(loaded, sizes)]
-        runs = []                    # (batch, coefficient tensor, status tensor)
-        bytes_dev = None
-        for cls, prepared, run in ((ScanBatch, per_iv, entropy_batch_device), (SyncBatch, sync, entropy_sync_batch_device)):
-            batch = cls(parsed, prepared, arr) if any(p is not None for p in prepared) else None
-            if batch is None or not batch.n_pages:
-                continue
-            if bytes_dev is None:
-                bytes_dev = ent[0][:total].to(device, non_blocking=True)
-                ent[1] = torch.cuda.Event()
-                ent[1].record()
-            runs.append((batch,) + tuple(run(batch, device, bytes_dev)[:2]))
-        if runs:
-            imgs, idx = {}, []
-            for batch, coef, _ in runs:
-                for i, k in enumerate(batch.pages):
-                    if k >= 0:
-                        info, base = batch.infos[k]
-                        imgs[i] = _reconstruct(info, coef[base:], device, torch, ops, loaded[i][3])
-                        idx.append(i)
-            status = runs[0][2] if len(runs) == 1 else torch.cat([r[2] for r in runs])
-            if defer_status:
-                st_host = torch.empty(len(idx), dtype=torch.int32).pin_memory()
-                st_host.copy_(status, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending = (st_host, ev, idx)
-                on_dev = imgs
-            else:
-                # the one wait of this path.  1: a bad stream goes to the host reader, as the host decoder's verdict would send it;
-                # 2: declined, not judged: the host pool below decodes it
-                on_dev = {i: (imgs[i] if st == 0 else None) for i, st in zip(idx, status.cpu().tolist()) if st != 2}
-    lib = nat.lib()
-    futs = []
-    for i, r in enumerate(loaded):
-        if r is None or i in on_dev:
-            futs.append(None)
-            continue
-        slot = _slot_buffer(i, int(r[0].coef_total), torch)   # main thread: allocation / pinning is not done from the workers
-        futs.append((_POOL.submit(lib.msocr_jpeg_entropy_decode_host, arr.ctypes.data + offs[i], sizes[i], ctypes.byref(r[0]), slot[0].data_ptr()), slot))
-    out = []
-    for i, (r, f) in enumerate(zip(loaded, futs)):
-        if i in on_dev:
-            out.append(on_dev[i])
-            continue
-        if f is None or f[0].result() != 0:
-            out.append(None)
-            continue
-        info, slot = r[0], f[1]
-        coef_dev = slot[0][: int(info.coef_total)].to(device, non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record()
-        out.append(_reconstruct(info, coef_dev, device, torch, ops, r[3]))
+    ent, offs, sizes, total, streams = batch
+
+    def upload():
+        bytes_dev = ent[0][:total].to(device, non_blocking=True)
+        ent[1] = torch.cuda.Event()
+        ent[1].record()
+        return bytes_dev
+    out, pending = _decode_streams(streams, offs, sizes, ent[0].numpy(), upload, True, device, device_entropy, defer_status)
     return (out, pending) if defer_status else out
 
 

@@ -274,3 +274,45 @@ def test_jpeg_per_interval_decoder_bad_streams_get_the_host_decoders_verdict():
         else:
             refused += 1
     assert agree >= 10 and refused >= 1, (agree, refused)
+
+
+# The routing table of ingest.read_images_device's docstring, written out: (restart interval?, longest interval in bytes, file
+# bytes, per-interval walk accepted, self-synchronising walk accepted, device_entropy) -> decoder.  8192 = the longest interval
+# the per-interval kernel takes by default, 0x1ff00000 = the largest file the self-synchronising stage takes.
+_MB = 1 << 20
+_ROUTES = [
+    # the nine cells
+    ("plain/False", (False, 0, _MB, False, True, False), "host"),
+    ("plain/True", (False, 0, _MB, False, True, True), "sync"),
+    ("plain/None", (False, 0, _MB, False, True, None), "sync"),
+    ("short/False", (True, 4096, _MB, True, True, False), "host"),
+    ("short/True", (True, 4096, _MB, True, True, True), "interval"),
+    ("short/None", (True, 4096, _MB, True, True, None), "interval"),
+    ("long/False", (True, 100000, _MB, True, True, False), "host"),
+    ("long/True", (True, 100000, _MB, True, True, True), "interval"),
+    ("long/None", (True, 100000, _MB, True, True, None), "sync"),
+    # the threshold belongs to the per-interval kernel; forcing the device ignores it
+    ("at-threshold/None", (True, 8192, _MB, True, True, None), "interval"),
+    ("over-threshold/None", (True, 8193, _MB, True, True, None), "sync"),
+    ("over-threshold/True", (True, 8193, _MB, True, True, True), "interval"),
+    # one byte over the self-synchronising stage's file cap: "sync" is not offered, whatever its walk said
+    ("plain-at-cap/None", (False, 0, 0x1ff00000, False, True, None), "sync"),
+    ("plain-over-cap/None", (False, 0, 0x1ff00001, False, True, None), "host"),
+    ("plain-over-cap/True", (False, 0, 0x1ff00001, False, True, True), "host"),
+    ("long-over-cap/None", (True, 100000, 0x1ff00001, True, True, None), "host"),
+    ("long-over-cap/True", (True, 100000, 0x1ff00001, True, True, True), "interval"),
+    ("short-over-cap/None", (True, 4096, 0x1ff00001, True, False, None), "interval"),
+    # the per-interval walk refused the stream, the self-synchronising walk took it
+    ("interval-refused/None", (True, 4096, _MB, False, True, None), "sync"),
+    ("interval-refused/True", (True, 4096, _MB, False, True, True), "sync"),
+    ("interval-refused/False", (True, 4096, _MB, False, True, False), "host"),
+    # both walks refused it: the host decoder judges the stream
+    ("both-refused/None", (True, 4096, _MB, False, False, None), "host"),
+    ("both-refused/True", (False, 0, _MB, False, False, True), "host"),
+]
+
+
+@pytest.mark.parametrize("facts,expected", [r[1:] for r in _ROUTES], ids=[r[0] for r in _ROUTES])
+def test_route_is_the_documented_table(facts, expected):
+    assert (ingest.DEVICE_MAX_INTERVAL, ingest.SYNC_MAX_FILE) == (8192, 0x1ff00000)
+    assert ingest.route(*facts) == expected

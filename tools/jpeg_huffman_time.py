@@ -49,12 +49,7 @@ def sync_stage(label, paths, n):
     torch.cuda.synchronize()
     assert not status.cpu().numpy().any()
     rounds = rounds.cpu().numpy()
-    was = ingest.SYNC_BY_DEFAULT
-    ingest.SYNC_BY_DEFAULT = True            # the default route with the stage on: long intervals and plain files take it
-    try:
-        dev = end_to_end(paths, device_entropy=None)
-    finally:
-        ingest.SYNC_BY_DEFAULT = was
+    dev = end_to_end(paths, device_entropy=None)   # the default route: long intervals and plain files take the stage
     host = end_to_end(paths, device_entropy=False)
     print(f"{label}, self-synchronising stage: {batch.max_subseq} subsequences of {batch.subseq_bytes} B per page, rounds {rounds.min()}..{rounds.max()} "
           f"of {ingest.SYNC_MAX_ROUNDS}; marker walk + layout {1e3 * (t1 - t0):.1f} ms (serial, one thread), tables + bounds upload + memset + "
@@ -109,7 +104,7 @@ def main():
             Image.fromarray(pg).save(paths[-1], quality=90)
         sync_stage("no restart markers", paths, n)
         host = end_to_end(paths)
-        print(f"no restart markers, default route ({'self-synchronising stage' if ingest.SYNC_BY_DEFAULT else 'host thread pool'}): "
+        print(f"no restart markers, default route (self-synchronising stage): "
               f"read_images_device {host[0]:.1f} ms per batch of {n} (min {host[1]:.1f}, max {host[2]:.1f})", flush=True)
 
 

@@ -1,12 +1,12 @@
-// attn_beam_mfma.hip — beam-search attention decode of the TRBA recogniser with the step's three matrix products on
+// attn_beam_mfma.hip — attention decode of the TRBA recogniser (beam search and greedy) with the step's three matrix products on
 // the matrix cores: in the split-operand form (default, precision "fp32": every f32 operand as three bf16 terms, six
 // v_mfma_f32_32x32x16_bf16 partial products per 16 k, f32 accumulation) or on the exact-f32 pipe (v_mfma_f32_32x32x2_f32,
-// precision "fp32-exact" or no msocr_attn_split_weights).
+// precision "fp32-exact" or no msocr_attn_split_weights; beam only).
 //
-// One 512-thread workgroup owns NB = 4 crops x 8 beam slots = 32 state rows for the whole step loop (rows of different
-// crops are independent: no inter-workgroup hand-off).  32 rows are exactly one MFMA row block, so every weight element a
-// workgroup pulls from L2 feeds 32 rows instead of the 8 of a one-crop workgroup, and the gate arithmetic moves off the
-// VALU.  The context half of the gate product is hoisted out of the step loop (see attn_beam_mfma_kernel).  Per step:
+// One 512-thread workgroup owns 32 state rows = one MFMA row block for the whole step loop: NB = 4 crops x 8 beam slots in
+// attn_beam_mfma_kernel, 32 crops in attn_greedy_mfma_kernel (rows of different crops are independent: no inter-workgroup
+// hand-off).  Every weight element a workgroup pulls from L2 feeds 32 rows, and the gate arithmetic is off the VALU.  The context
+// half of the gate product is hoisted out of the step loop (see ctx_sum).  Per step:
 //   (a) ph    = h2h(h)                     [32x256] x [256x256]        MFMA  (wave w: columns 32w..32w+31)
 //   (b) e     = score . tanh(proj_H + ph)  32 x T dot products          VALU  (one wave per (crop, t) pair)
 //   (c) alpha = softmax_t(e)                                            VALU
@@ -14,10 +14,16 @@
 //       (wave w owns hidden units 32w..32w+31; one 16-byte load per lane = the unit's 4 gates = B operands of 4 MFMAs,
 //        so the LSTM cell update is lane-local in the accumulator layout)
 //   (f) logits = generator(h')             [32x256] x [256xV]          MFMA
-//   (g-j) temperature, log-softmax, top-8 of 8*V candidates per crop, back-pointers, beam state permutation   VALU/LDS
-// Same outputs, workspace layout and tie rules as attn_general_kernel<true> (larger value first, then smaller flat index).
+//   beam:   (g-j) temperature, log-softmax, top-8 of 8*V candidates per crop, back-pointers, beam state permutation   VALU/LDS
+//   greedy: (g) arg-max per row
+// Structure: (a)-(f) exist once, as the phase functions below, which both kernels call with three compile-time facts: the state
+// rows per crop (8 or 1), the grade of the nonlinearities (split_rows32.h: FastMath in beam, LibmMath in greedy) and the operand
+// form (HRows<SPLITW>: where h lives in LDS and which MFMA products read it).  The kernel bodies hold the step loop, the barriers
+// between the phases, the epilogue of (f) and the phases only they have.
+// Same outputs, workspace layout and tie rules as attn_general_kernel (larger value first, then smaller flat index).
 //
-// Replaces recognizers/_trba/model/model.py:34-46 (AttentionCell.forward) + :92-225 (Attention._beam_decode).
+// Replaces recognizers/_trba/model/model.py:34-46 (AttentionCell.forward), :92-225 (Attention._beam_decode) and :227-259
+// (Attention._greedy_decode).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -26,15 +32,7 @@
 #include "msocr.h"
 #include "split_rows32.h"
 
-using split_rows32::mfma_cols32_split;
-using split_rows32::mfma_gates_split;
-using split_rows32::PPL;
-using split_rows32::PSB;
-using split_rows32::u32x4;
-
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace split_rows32;
 
 // Per-phase timestamps of workgroup 0 (dev builds only: tools/attn_phase_times.sh compiles this file with -DMSOCR_ATTN_TIMING)
 #ifdef MSOCR_ATTN_TIMING
@@ -47,27 +45,14 @@ extern "C" int msocr_attn_timing_read(unsigned long long* out_host) {
 #define TSTAMP(ph) do { } while (0)
 #endif
 
-
 namespace {
 
-constexpr int H = split_rows32::H;  // hidden size (ATT_H)
 constexpr int KB8 = 8;        // beam slots per crop (ATT_KMAX)
-constexpr int NB = 4;         // crops per workgroup
-constexpr int R = NB * KB8;   // 32 state rows = one MFMA row block
-static_assert(R == split_rows32::R, "row block");
+constexpr int NB = 4;         // crops per workgroup (beam)
+static_assert(R == NB * KB8, "row block");
 constexpr int XS = 2 * H + 4; // row stride of X = [ctx | h] in floats: 516 -> ds_read_b128 of 32 rows is conflict-free
 constexpr int NT = 512;       // threads per workgroup
 
-// Hardware-rate transcendentals (v_exp_f32 / v_rcp_f32, ~1-2 ulp each): the decode step evaluates 32 x T x 256 tanh and
-// 5 x 32 x 256 gate activations on the VALU between the matrix phases; libm-grade expf/tanhf made that the longest phase.
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(fexp(2.0f * x) + 1.0f); }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 // Wave-wide reductions on the DPP data path (quad_perm / row_half_mirror / row_mirror / row_bcast15 / row_bcast31: a few cycles per
 // step) instead of ds_bpermute shuffles (an LDS round trip per step): the decode step runs ~400 of them per wave.  The result is
 // complete in lane 63 (every lane of the last row for sums of full rows); *_bcast return it to all lanes through an SGPR.
@@ -118,23 +103,11 @@ __device__ __forceinline__ void wave_argmax63(float& v, int& i) {
   argmax_step<DPP_BCAST31, 0xC>(v, i);
 }
 
-// Packed-f32 VALU beside bf16 MFMAs.  The VALU work between the softmax barrier and the gate MFMAs (token-row initialisation, the
-// hoisted context sum) runs while the other wave of the SIMD is inside its v_mfma_f32_32x32x16_bf16 loop.  Round 3 found that with
-// the packed form the compiler chose for that sum — v_pk_fma_f32 ... op_sel:[0,1,0], the LOW result taking the HIGH dword of a
-// source pair — about 0.5 % of the state rows came out with the low result of lanes 48..63 wrong (tools/attn_packed_probe.sh,
-// profiles/r03_attn_packed_probe.txt).  Round 4 settled the cause: the disassembly of that build has hundreds of cycles (a branch,
-// twelve buffer loads, an s_waitcnt vmcnt) between the last v_pk_fma_f32 that writes an accumulator and the first MFMA that reads it
-// as SrcC, so it is no missing VALU -> MFMA wait state; and the 90-line stand-alone tools/microbench/pk_fma_beside_mfma.hip
-// reproduces it with nothing else in the kernel — 22 880 wrong low results, all in lanes 48..63, out of 2.6e9 with the partner waves
-// running v_mfma_f32_32x32x16_bf16; 0 with idle partners; 0 for the same instruction without op_sel (profiles/r04_pk_fma_probe.txt).
-// It is a property of the instruction beside MFMAs, not of this kernel's code.  The remedy is at build level: this file, like every
-// translation unit whose kernels run beside bf16 MFMAs, is compiled without packed-f32 instructions (csrc/Makefile, NOPK_OBJS), the
-// sums below are plain C (the compiler's hazard recognizer sees them — round 3's inline asm hid them from it), and
-// tests/test_host_cpu.py::test_no_packed_f32_valu_beside_mfma disassembles the built objects.  tests/test_gpu_trba.py keeps the
-// split-against-exact comparison of every beam's logits as the run-time guard.
-__device__ __forceinline__ float add_np(float a, float b) { return a + b; }
-__device__ __forceinline__ float fmac_np(float a, float b, float c) { return fmaf(a, b, c); }
-
+// No packed-f32 VALU in this unit: a v_pk_fma_f32 whose low result takes the high dword of a source pair returns wrong low results
+// in lanes 48..63 while the other wave of the SIMD runs v_mfma_f32_32x32x16_bf16 (profiles/r04_pk_fma_probe.txt,
+// tools/microbench/pk_fma_beside_mfma.hip), and the sums of phase (e) run beside exactly those MFMAs.  So the file is compiled
+// without packed-f32 instructions (csrc/Makefile, NOPK_OBJS), and the sums stay plain C, not inline assembly, so that the
+// compiler's hazard recogniser sees them.
 
 // Weight streams use buffer loads: ONE per-lane byte offset in a VGPR (loop-invariant) + a scalar byte offset per load, so
 // the 12-16 loads in flight cost no address VGPRs (a global_load needs a 64-bit VGPR address each); out-of-range lanes
@@ -211,34 +184,276 @@ __device__ __forceinline__ void mfma_gates(const float* __restrict__ sX, int k0,
   }
 }
 
+// Dynamic LDS of both kernels: the h rows in their operand form, then sbuf [R][H] (ph, then logits, then scratch of the beam
+// permutation), then salpha [R][64] (scores, then attention weights).
+extern __shared__ __attribute__((aligned(16))) float lds[];
+
+// ---- operand form: the 32 state rows of h as the three products read them, named once per kernel.  HRows<true>: three bf16 planes
+// [3][R][PSB], split-operand products with the packed split weights.  HRows<false>: f32 in columns 256..511 of X = [ctx | h], [R][XS]
+// (the layout of the un-hoisted product), exact-f32 MFMA with the transposed f32 weights.  FLOATS = the LDS floats the form takes.
+template <bool SPLITW>
+struct HRows;
+template <class HS>
+__device__ __forceinline__ float* sbuf_of() { return lds + HS::FLOATS; }
+template <class HS>
+__device__ __forceinline__ float* salpha_of() { return lds + HS::FLOATS + R * H; }
+template <>
+struct HRows<true> {
+  static constexpr int FLOATS = 3 * PPL / 4;
+  typedef uint32_t Moved[3][KB8];
+  static __device__ __forceinline__ unsigned char* planes() { return reinterpret_cast<unsigned char*>(lds); }
+  static __device__ __forceinline__ void zero(int tid) {
+    for (int i = tid; i < FLOATS; i += NT) lds[i] = 0.f;
+  }
+  // acc[32 rows][column col] += h * W, W [256][n]: packed with the columns padded by zeros to a multiple of 32
+  static __device__ __forceinline__ void cols32(const uint16_t* Wp, const float*, int n, int col, int r32, int half, f32x16& acc) {
+    mfma_cols32_split(planes(), Wp, (n + 31) & ~31, col, true, r32, half, acc);
+  }
+  static __device__ __forceinline__ void gates(const AttnArgs& a, int j, int r32, int half, f32x16 (&acc)[4]) {
+    mfma_gates_split(planes(), a.whh_p, j, r32, half, acc);
+  }
+  static __device__ __forceinline__ void store_h(int ju, int half, float (&hv)[16]) { store_h_planes(planes(), ju, half, hv); }
+  // beam permutation: thread = (column pair, crop) takes the crop's 8 rows of the three planes, row rb from row src[rb]
+  static __device__ __forceinline__ void load_moved(int tid, int KB, const int* s_src, Moved& m) {
+    const int j2 = tid & 127, nb = tid >> 7;
+#pragma unroll
+    for (int rb = 0; rb < KB8; ++rb) {
+      const int src = rb < KB ? s_src[nb * KB8 + rb] : rb;
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl)
+        m[pl][rb] = *reinterpret_cast<const uint32_t*>(planes() + pl * PPL + (nb * KB8 + src) * PSB + j2 * 4);
+    }
+  }
+  static __device__ __forceinline__ void store_moved(int tid, const Moved& m) {
+    const int j2 = tid & 127, nb = tid >> 7;
+#pragma unroll
+    for (int rb = 0; rb < KB8; ++rb)
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl)
+        *reinterpret_cast<uint32_t*>(planes() + pl * PPL + (nb * KB8 + rb) * PSB + j2 * 4) = m[pl][rb];
+  }
+};
+template <>
+struct HRows<false> {
+  static constexpr int FLOATS = R * XS;
+  typedef float Moved[R / 2];
+  static __device__ __forceinline__ void zero(int tid) {
+    for (int i = tid; i < R * H; i += NT) lds[(i >> 8) * XS + H + (i & 255)] = 0.f;
+  }
+  static __device__ __forceinline__ void cols32(const uint16_t*, const float* W, int n, int col, int r32, int half, f32x16& acc) {
+    mfma_cols32(lds, H, W, n, col, col < n, r32, half, acc);
+  }
+  static __device__ __forceinline__ void gates(const AttnArgs& a, int j, int r32, int half, f32x16 (&acc)[4]) {
+    mfma_gates(lds, H, a.w.whh_t, j, r32, half, acc);
+  }
+  static __device__ __forceinline__ void store_h(int ju, int half, const float (&hv)[16]) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) lds[acc_row(e, half) * XS + H + ju] = hv[e];
+  }
+  // beam permutation: thread = (column, half of the rows)
+  static __device__ __forceinline__ void load_moved(int tid, int KB, const int* s_src, Moved& m) {
+    const int j = tid & 255, ch = tid >> 8;
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) {
+      const int r = ch * (R / 2) + q, nb = r / KB8, rb = r % KB8;
+      const int src = rb < KB ? s_src[r] : rb;
+      m[q] = lds[(nb * KB8 + src) * XS + H + j];
+    }
+  }
+  static __device__ __forceinline__ void store_moved(int tid, const Moved& m) {
+    const int j = tid & 255, ch = tid >> 8;
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) lds[(ch * (R / 2) + q) * XS + H + j] = m[q];
+  }
+};
+
+// a thread's place in the workgroup: wave wv owns hidden unit / output column ju and rows acc_row(e, half) in the MFMA phases
+struct Lane {
+  int tid, lane, wv, r32, half, ju;
+  __device__ __forceinline__ explicit Lane(int t)
+      : tid(t), lane(t & 63), wv(t >> 6), r32(lane & 31), half(lane >> 5), ju(32 * wv + r32) {}
+};
+
+// ---- the decode phases both kernels share.  RPC = state rows per crop (8: beam slots, 1: greedy), b0 = first crop of the
+// workgroup, so row r belongs to crop b0 + r / RPC; crops past B repeat the last one (computed, never stored).  NL = grade of the
+// nonlinearities (split_rows32.h), HS = operand form.
+
+// (a) ph[r][j] = h2h_b[j] + sum_k h[r][k] * h2h_wt[k][j]  -> sbuf
+template <class HS>
+__device__ __forceinline__ void phase_h2h(const AttnArgs& a, const Lane& l) {
+  float* const sbuf = sbuf_of<HS>();
+  f32x16 acc;
+  const float bj = a.w.h2h_b[l.ju];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = bj;
+  HS::cols32(a.h2h_p, a.w.h2h_wt, H, l.ju, l.r32, l.half, acc);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) sbuf[acc_row(e, l.half) * H + l.ju] = acc[e];
+}
+
+// (b) e[r][t] = sum_j score_w[j] * tanh(proj_H[crop][t][j] + ph[r][j]) -> salpha: one wave per (crop, t) group — the proj_H row is
+//     read once for the crop's RPC rows; the rows of up to GB groups are in flight together
+template <int RPC, class NL, class HS>
+__device__ __forceinline__ void phase_scores(const AttnArgs& a, const Lane& l, int b0) {
+  const float* const sbuf = sbuf_of<HS>();
+  float* const salpha = salpha_of<HS>();
+  constexpr int GB = 4;
+  const int T = a.T, lane = l.lane;
+  float sw[H / 64];
+#pragma unroll
+  for (int q = 0; q < H / 64; ++q) sw[q] = a.w.score_w[lane + 64 * q];
+  const int ngroups = (R / RPC) * T;
+  for (int g0 = l.wv; g0 < ngroups; g0 += GB * (NT / 64)) {
+    float pr[GB][H / 64];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      const int g = g0 + u * (NT / 64);
+      if (g < ngroups) {
+        const int nb = g / T, t = g - nb * T;
+        const float* pP = a.proj_H + ((long)min(b0 + nb, a.B - 1) * T + t) * H;
+#pragma unroll
+        for (int q = 0; q < H / 64; ++q) pr[u][q] = pP[lane + 64 * q];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      const int g = g0 + u * (NT / 64);
+      if (g < ngroups) {
+        const int nb = g / T, t = g - nb * T;
+        float sacc[RPC];
+#pragma unroll
+        for (int rb = 0; rb < RPC; ++rb) {
+          const int r = nb * RPC + rb;
+          sacc[rb] = 0.f;
+#pragma unroll
+          for (int q = 0; q < H / 64; ++q) sacc[rb] = fmaf(sw[q], NL::tanh(pr[u][q] + sbuf[r * H + lane + 64 * q]), sacc[rb]);
+        }
+        // RPC independent wave sums on the DPP path, totals in lane 63
+#pragma unroll
+        for (int rb = 0; rb < RPC; ++rb) sacc[rb] = wave_sum63(sacc[rb]);
+        if (lane == 63) {
+#pragma unroll
+          for (int rb = 0; rb < RPC; ++rb) salpha[(nb * RPC + rb) * 64 + t] = sacc[rb];
+        }
+      }
+    }
+  }
+}
+
+// (c) softmax over t in salpha: wave w handles rows 4w..4w+3, lane = t (T <= 64)
+template <class HS>
+__device__ __forceinline__ void phase_softmax_t(int T, const Lane& l) {
+  float* const salpha = salpha_of<HS>();
+  for (int r = 4 * l.wv; r < 4 * l.wv + 4; ++r) {
+    const float ev0 = l.lane < T ? salpha[r * 64 + l.lane] : -INFINITY;
+    const float m = bcast63(wave_max63(ev0));
+    const float ev = l.lane < T ? expf(ev0 - m) : 0.f;
+    const float sum = bcast63(wave_sum63(ev));
+    if (l.lane < T) salpha[r * 64 + l.lane] = ev / sum;
+  }
+}
+
 // The context half of the LSTMCell input product is hoisted out of the step loop.  The reference computes
 // gates = W_ih [ctx ; onehot] + W_hh h with ctx = sum_t alpha_t batch_H_t (model.py:40-45); since W_ih[:, :H] ctx =
 // sum_t alpha_t (W_ih[:, :H] batch_H_t), the products P_t = W_ih[:, :H] batch_H_t are computed ONCE per crop by a GEMM before the
 // kernel (a.ctx_gates, [B][T][H][4]) and a step only forms sum_t alpha_t P_t on the VALU (13 x 1024 FMAs per row instead of
 // 256 x 1024 MACs): half of the step's matrix work, 1 of its 2.5 MB of weights and the context phase disappear.  Same arithmetic
 // up to the order of the f32 summation.
-// SPLITW: the three matrix products in the split-operand form above, h only as its three bf16 planes; else exact-f32 MFMA.
+//
+// acc[gate][e] += sum_t alpha[row][t] * P[crop(row)][t][ju][gate].  A lane's 16 accumulator elements are E consecutive rows of
+// 16 / E crops (E = 4 of a beam crop's 8 slots, the other half-wave has the other 4; E = 1 in greedy): a crop's frames (T x 16 B
+// per lane, 8 in flight) are loaded once for its E rows, then the FMAs.
+template <int RPC, class HS>
+__device__ __forceinline__ void ctx_sum(const AttnArgs& a, const Lane& l, int b0, f32x16 (&acc)[4]) {
+  const float* const salpha = salpha_of<HS>();
+  constexpr int E = RPC == 1 ? 1 : 4;
+  static_assert(RPC == 1 || RPC == 8, "rows of a crop in one lane");
+  const int T = a.T;
+#pragma unroll
+  for (int e0 = 0; e0 < 16; e0 += E) {
+    const int row0 = acc_row(e0, l.half);
+    // the rows' crop, b0 + row0 / RPC: spelled without the half-wave term for a beam crop, whose 8 rows both half-waves share, so that
+    // it is a constant per e0 (with the term the exact-form beam kernel came out at 82 spilled VGPRs instead of 52)
+    const int crop = b0 + (RPC == 1 ? row0 : acc_row(e0, 0) / RPC);
+    const float* pP = a.ctx_gates + ((long)min(crop, a.B - 1) * T * H + l.ju) * 4;
+    const float* pa = salpha + row0 * 64;
+    for (int t0 = 0; t0 < T; t0 += 8) {
+      f32x4 pv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (t0 + u < T) pv[u] = *reinterpret_cast<const f32x4*>(pP + (long)(t0 + u) * H * 4);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (t0 + u < T) {
+#pragma unroll
+          for (int i = 0; i < E; ++i) {
+            const float al = pa[i * 64 + t0 + u];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[g][e0 + i] = fmaf(al, pv[u][g], acc[g][e0 + i]);
+          }
+        }
+    }
+    if constexpr (RPC == 1) __builtin_amdgcn_sched_barrier(0);  // keep the rows' loads from piling up across iterations (registers)
+  }
+}
+
+// (e) gates = b + W_ih_tok[token] + sum_t alpha_t P_t + h W_hh^T, LSTM cell for units ju and rows acc_row(e, half), h' -> the h rows.
+//     Holds the barrier between the last read of the old h and the store of the new one.
+template <int RPC, class NL, bool STAGGER, class HS>
+__device__ __forceinline__ void phase_gates_cell(const AttnArgs& a, const Lane& l, int b0, const int* s_tok, f32x16& c) {
+  f32x16 acc[4];
+  const f32x4 b4 = *reinterpret_cast<const f32x4*>(&a.w.b_gates[l.ju * 4]);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int tk = s_tok[acc_row(e, l.half)];
+    const f32x4 t4 = *reinterpret_cast<const f32x4*>(&a.w.wih_tok[((long)tk * H + l.ju) * 4]);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g][e] = b4[g] + t4[g];
+  }
+  if constexpr (STAGGER) {
+    // The context sum is load-latency and VALU work, the recurrent product matrix-pipe work, and the two are independent: the two
+    // waves of a SIMD (w and w + 4) take them in opposite orders, so one's loads and FMAs run under the other's MFMAs instead of
+    // both waiting for memory and then both queueing on the pipe.
+    const bool mfma_first = __builtin_amdgcn_readfirstlane(l.wv) >= 4;
+    if (!mfma_first) ctx_sum<RPC, HS>(a, l, b0, acc);
+    HS::gates(a, l.ju, l.r32, l.half, acc);
+    if (mfma_first) ctx_sum<RPC, HS>(a, l, b0, acc);
+  } else {
+    ctx_sum<RPC, HS>(a, l, b0, acc);
+    HS::gates(a, l.ju, l.r32, l.half, acc);
+  }
+  __syncthreads();  // every wave has read the old h
+  float hv[16];
+  lstm_cell<NL>(acc, c, hv);
+  HS::store_h(l.ju, l.half, hv);
+}
+
+// (f) logits[r][v] = gen_b[v] + sum_k h'[r][k] * gen_wt[k][v] for column v = ju, up to the accumulator (columns >= V: unspecified)
+template <class HS>
+__device__ __forceinline__ f32x16 phase_generator(const AttnArgs& a, const Lane& l) {
+  f32x16 acc;
+  const float bv = l.ju < a.V ? a.w.gen_b[l.ju] : 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = bv;
+  if (32 * l.wv < a.V) HS::cols32(a.gen_p, a.w.gen_wt, a.V, l.ju, l.r32, l.half, acc);
+  return acc;
+}
+
+// Beam decode: 4 crops x 8 beam slots per workgroup.  SPLITW: the operand form.  Nonlinearities at hardware rate; the context sum
+// staggered against the recurrent product in the split form (phase_gates_cell).
 template <bool SPLITW>
 __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* sX = lds;                 // [R][XS]   h in columns 256..511 (X = [ctx | h] of the un-hoisted product)   (exact form)
-  unsigned char* sP = reinterpret_cast<unsigned char*>(lds);  // [3][R][PSB] bf16 planes of h  (split form)
-  float* sbuf = SPLITW ? lds + 3 * PPL / 4 : sX + R * XS;     // [R][H]    ph, then logits, then scratch of the state permutation
-  float* salpha = sbuf + R * H;    // [R][64]
+  typedef HRows<SPLITW> HS;
+  float* const sbuf = sbuf_of<HS>();
   __shared__ float s_score[R], s_lse[R], s_top[R];
   __shared__ int s_tok[R], s_done[R], s_src[R], s_nxt[R], s_fin[NB], s_exit;
 
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r32 = lane & 31, half = lane >> 5;
-  const int T = a.T, V = a.V, KB = a.K;
+  const Lane l(threadIdx.x);
+  const int tid = l.tid, lane = l.lane, wv = l.wv, half = l.half, ju = l.ju;
+  const int V = a.V, KB = a.K;
   const int b0 = blockIdx.x * NB;
-  const int ju = 32 * wv + r32;    // hidden unit / output column owned in the MFMA phases
 
-  if constexpr (SPLITW) {
-    for (int i = tid; i < 3 * PPL / 4; i += NT) lds[i] = 0.f;  // h = 0
-  } else {
-    for (int i = tid; i < R * H; i += NT) sX[(i >> 8) * XS + H + (i & 255)] = 0.f;
-  }
+  HS::zero(tid);  // h = 0
   f32x16 c;
 #pragma unroll
   for (int e = 0; e < 16; ++e) c[e] = 0.f;
@@ -253,170 +468,23 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
 
   for (int s = 0; s < a.steps; ++s) {
     TSTAMP(0);
-    // ---- (a) ph[r][j] = h2h_b[j] + sum_k h[r][k] * h2h_wt[k][j]
-    {
-      f32x16 acc;
-      const float bj = a.w.h2h_b[ju];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = bj;
-      if constexpr (SPLITW) mfma_cols32_split(sP, a.h2h_p, H, ju, true, r32, half, acc);
-      else mfma_cols32(sX, H, a.w.h2h_wt, H, ju, true, r32, half, acc);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sbuf[acc_row(e, half) * H + ju] = acc[e];
-    }
+    phase_h2h<HS>(a, l);
     __syncthreads();
     TSTAMP(1);
-    // ---- (b) e[r][t] = sum_j score_w[j] * tanh(proj_H[crop][t][j] + ph[r][j]) : one wave per (crop, t) group — the
-    //      proj_H row is read once for the crop's 8 beams; the rows of up to GB groups are in flight together
-    {
-      constexpr int GB = 4;
-      float sw[H / 64];
-#pragma unroll
-      for (int q = 0; q < H / 64; ++q) sw[q] = a.w.score_w[lane + 64 * q];
-      const int ngroups = NB * T;
-      for (int g0 = wv; g0 < ngroups; g0 += GB * (NT / 64)) {
-        float pr[GB][H / 64];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int g = g0 + u * (NT / 64);
-          if (g < ngroups) {
-            const int nb = g / T, t = g - nb * T;
-            const float* pP = a.proj_H + ((long)min(b0 + nb, a.B - 1) * T + t) * H;
-#pragma unroll
-            for (int q = 0; q < H / 64; ++q) pr[u][q] = pP[lane + 64 * q];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int g = g0 + u * (NT / 64);
-          if (g < ngroups) {
-            const int nb = g / T, t = g - nb * T;
-            float sacc[KB8];
-#pragma unroll
-            for (int rb = 0; rb < KB8; ++rb) {
-              const int r = nb * KB8 + rb;
-              sacc[rb] = 0.f;
-#pragma unroll
-              for (int q = 0; q < H / 64; ++q) sacc[rb] = fmaf(sw[q], ftanh(pr[u][q] + sbuf[r * H + lane + 64 * q]), sacc[rb]);
-            }
-            // 8 independent wave sums on the DPP path, totals in lane 63
-#pragma unroll
-            for (int rb = 0; rb < KB8; ++rb) sacc[rb] = wave_sum63(sacc[rb]);
-            if (lane == 63) {
-#pragma unroll
-              for (int rb = 0; rb < KB8; ++rb) salpha[(nb * KB8 + rb) * 64 + t] = sacc[rb];
-            }
-          }
-        }
-      }
-    }
+    phase_scores<KB8, FastMath, HS>(a, l, b0);
     __syncthreads();
     TSTAMP(2);
-    // ---- (c) softmax over t: wave w handles rows 4w..4w+3, lane = t (T <= 64)
-    for (int r = 4 * wv; r < 4 * wv + 4; ++r) {
-      const float ev0 = lane < T ? salpha[r * 64 + lane] : -INFINITY;
-      const float m = bcast63(wave_max63(ev0));
-      const float ev = lane < T ? expf(ev0 - m) : 0.f;
-      const float sum = bcast63(wave_sum63(ev));
-      if (lane < T) salpha[r * 64 + lane] = ev / sum;
-    }
+    phase_softmax_t<HS>(a.T, l);
     __syncthreads();
     TSTAMP(3);
     TSTAMP(4);  // (d) is empty, the context product being hoisted; the stamp keeps tools/attn_phase_times.sh's phase numbering
-    // ---- (e) gates + LSTM cell for units ju, rows acc_row(e, half)
-    {
-      f32x16 acc[4];
-      const f32x4 b4 = *reinterpret_cast<const f32x4*>(&a.w.b_gates[ju * 4]);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int tk = s_tok[acc_row(e, half)];
-        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&a.w.wih_tok[((long)tk * H + ju) * 4]);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g][e] = add_np(b4[g], t4[g]);
-      }
-      // + sum_t alpha[row][t] * P[crop(row)][t][ju][gate]; this lane's rows of crop nb are beams 4 * half + 0..3 = acc elements 4 nb + i
-      auto ctx_sum = [&]() {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          const float* pP = a.ctx_gates + ((long)min(b0 + nb, a.B - 1) * T * H + ju) * 4;
-          const float* pa = salpha + (nb * KB8 + 4 * half) * 64;
-          for (int t0 = 0; t0 < T; t0 += 8) {  // 8 loads in flight, then the FMAs
-            f32x4 pv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-              if (t0 + u < T) pv[u] = *reinterpret_cast<const f32x4*>(pP + (long)(t0 + u) * H * 4);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-              if (t0 + u < T) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                  const float al = pa[i * 64 + t0 + u];
-#pragma unroll
-                  for (int g = 0; g < 4; ++g) acc[g][4 * nb + i] = fmac_np(al, pv[u][g], acc[g][4 * nb + i]);
-                }
-              }
-          }
-        }
-      };
-#if defined(MSOCR_ATTN_SUM_BARRIER) || defined(MSOCR_ATTN_NO_STAGGER)
-      constexpr bool STAGGER = false;
-#else
-      constexpr bool STAGGER = SPLITW;
-#endif
-      if constexpr (STAGGER) {
-        // The context sum is load-latency and VALU work, the recurrent product matrix-pipe work, and the two are independent: the two
-        // waves of a SIMD (w and w + 4) take them in opposite orders, so one's loads and FMAs run under the other's MFMAs instead of
-        // both waiting for memory and then both queueing on the pipe (one-register FMAs: see add_np / fmac_np above).
-        const bool mfma_first = __builtin_amdgcn_readfirstlane(wv) >= 4;
-        if (!mfma_first) ctx_sum();
-        mfma_gates_split(sP, a.whh_p, ju, r32, half, acc);
-        if (mfma_first) ctx_sum();
-      } else {
-        ctx_sum();
-#ifdef MSOCR_ATTN_SUM_BARRIER  // dev builds: no wave enters the MFMA loop while another is still in the sum above
-        __syncthreads();
-#endif
-        if constexpr (SPLITW) mfma_gates_split(sP, a.whh_p, ju, r32, half, acc);
-        else mfma_gates(sX, H, a.w.whh_t, ju, r32, half, acc);
-      }
-      __syncthreads();  // every wave has read the old h
-      float hv[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float ig = sigmoidf_(acc[0][e]), fg = sigmoidf_(acc[1][e]), gg = ftanh(acc[2][e]), og = sigmoidf_(acc[3][e]);
-        c[e] = fg * c[e] + ig * gg;
-        hv[e] = og * ftanh(c[e]);
-      }
-      if constexpr (SPLITW) {
-#pragma unroll
-        for (int e = 0; e < 16; e += 2) {  // acc_row(e + 1) == acc_row(e) + 1
-          unsigned char* d = sP + acc_row(e, half) * PSB + ju * 2;
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            const uint32_t pk = split_step(hv[e], hv[e + 1]);
-            *reinterpret_cast<uint16_t*>(d + pl * PPL) = (uint16_t)pk;
-            *reinterpret_cast<uint16_t*>(d + pl * PPL + PSB) = (uint16_t)(pk >> 16);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sX[acc_row(e, half) * XS + H + ju] = hv[e];
-      }
-    }
+    phase_gates_cell<KB8, FastMath, SPLITW, HS>(a, l, b0, s_tok, c);
     __syncthreads();
     TSTAMP(5);
-    // ---- (f) logits[r][v] = gen_b[v] + sum_k h'[r][k] * gen_wt[k][v]; temperature; trace store
+    // ---- (f) logits; temperature; trace store
     {
-      const bool vok = ju < V;
-      f32x16 acc;
-      const float bv = vok ? a.w.gen_b[ju] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = bv;
-      if (32 * wv < V) {
-        if constexpr (SPLITW) mfma_cols32_split(sP, a.gen_p, (V + 31) & ~31, ju, true, r32, half, acc);  // padded columns are zeros
-        else mfma_cols32(sX, H, a.w.gen_wt, V, ju, vok, r32, half, acc);
-      }
-      if (vok) {
+      const f32x16 acc = phase_generator<HS>(a, l);
+      if (ju < V) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int r = acc_row(e, half);
@@ -572,45 +640,16 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     {
 #pragma unroll
       for (int e = 0; e < 16; ++e) sbuf[acc_row(e, half) * H + ju] = c[e];
-      if constexpr (SPLITW) {
-        const int j2 = tid & 127, nb = tid >> 7;  // column pair, crop: the crop's 8 rows of the three planes
-        uint32_t hp[3][KB8];
+      typename HS::Moved hm;
+      HS::load_moved(tid, KB, s_src, hm);
+      __syncthreads();
 #pragma unroll
-        for (int rb = 0; rb < KB8; ++rb) {
-          const int src = rb < KB ? s_src[nb * KB8 + rb] : rb;
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) hp[pl][rb] = *reinterpret_cast<const uint32_t*>(sP + pl * PPL + (nb * KB8 + src) * PSB + j2 * 4);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int r = acc_row(e, half), cb = r / KB8, rb = r % KB8;
-          const int src = rb < KB ? s_src[r] : rb;
-          c[e] = sbuf[(cb * KB8 + src) * H + ju];
-        }
-#pragma unroll
-        for (int rb = 0; rb < KB8; ++rb)
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint32_t*>(sP + pl * PPL + (nb * KB8 + rb) * PSB + j2 * 4) = hp[pl][rb];
-      } else {
-        const int j = tid & 255, ch = tid >> 8;
-        float hn[R / 2];
-#pragma unroll
-        for (int q = 0; q < R / 2; ++q) {
-          const int r = ch * (R / 2) + q, nb = r / KB8, rb = r % KB8;
-          const int src = rb < KB ? s_src[r] : rb;
-          hn[q] = sX[(nb * KB8 + src) * XS + H + j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int r = acc_row(e, half), nb = r / KB8, rb = r % KB8;
-          const int src = rb < KB ? s_src[r] : rb;
-          c[e] = sbuf[(nb * KB8 + src) * H + ju];
-        }
-#pragma unroll
-        for (int q = 0; q < R / 2; ++q) sX[(ch * (R / 2) + q) * XS + H + j] = hn[q];
+      for (int e = 0; e < 16; ++e) {
+        const int r = acc_row(e, half), nb = r / KB8, rb = r % KB8;
+        const int src = rb < KB ? s_src[r] : rb;
+        c[e] = sbuf[(nb * KB8 + src) * H + ju];
       }
+      HS::store_moved(tid, hm);
     }
     __syncthreads();
     TSTAMP(10);
@@ -639,32 +678,24 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
   if (tid < NB && b0 + tid < a.B) a.fin_step[b0 + tid] = s_fin[tid];
 }
 
-// ------------------------------------------------------------------------------------------------- greedy (round 4)
-// mode="greedy" (Attention._greedy_decode, model.py:227-259) in the same row-block form: one 512-thread workgroup = 32 CROPS = 32
-// state rows = one MFMA row block, all `steps` steps in one launch.  The rows are independent (the reference keeps every row
-// running after its own EOS and only stops a chunk when all rows emit EOS in the same step; the host derives those run lengths
-// from the ids, recognizers/_trba/__init__.py), so a step is the beam kernel's (a)-(f) without any beam bookkeeping — no
-// log-softmax, no top-k, no state permutation — followed by an arg-max per row (larger value, then smaller index; blank masked
-// to -1e4 as in attn_general_kernel).  Split-operand products and hoisted context gates (a.ctx_gates) as in
-// attn_beam_mfma_kernel<true>; gate and score nonlinearities libm-grade (see sigmoid_libm).  Each row reads ITS crop's proj_H / ctx_gates frames
-// (8x the beam kernel's traffic per row, from L2 / the Infinity Cache).
-// libm-grade nonlinearities for the greedy kernel: its logits are held to the decoder-only bound (2e-4 of max |logit| against the
-// oracle's decoder over 41 chained steps of the all-random decoder, tests/test_gpu_trba.py DECODER_LOGIT_RTOL), which the hardware-
-// rate v_exp_f32 / v_rcp_f32 forms of the beam kernel miss by 5 % on one row of 96; greedy is not the pipeline's default mode.
-__device__ __forceinline__ float sigmoid_libm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
+// Greedy decode (Attention._greedy_decode, model.py:227-259): 32 CROPS per workgroup, one state row each, all `steps` steps in one
+// launch.  The rows are independent (the reference keeps every row running after its own EOS and only stops a chunk when all rows
+// emit EOS in the same step; the host derives those run lengths from the ids, recognizers/_trba/__init__.py), so a step is (a)-(f)
+// without any beam bookkeeping — no log-softmax, no top-k, no state permutation — followed by an arg-max per row (larger value,
+// then smaller index; blank masked to -1e4 as in attn_general_kernel).  Always the split form.  Each row reads ITS crop's proj_H /
+// ctx_gates frames (8x the beam kernel's traffic per row, from L2 / the Infinity Cache).
+// Nonlinearities libm-grade: the greedy logits are held to the decoder-only bound (2e-4 of max |logit| against the oracle's decoder
+// over 41 chained steps of the all-random decoder, tests/test_gpu_trba.py DECODER_LOGIT_RTOL), which the hardware-rate forms miss
+// by 5 % on one row of 96; greedy is not the pipeline's default mode.
 __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  unsigned char* sP = reinterpret_cast<unsigned char*>(lds);  // [3][R][PSB] bf16 planes of h
-  float* sbuf = lds + 3 * PPL / 4;                             // [R][H]    ph, then logits
-  float* salpha = sbuf + R * H;                                // [R][64]
+  typedef HRows<true> HS;
+  float* const sbuf = sbuf_of<HS>();
   __shared__ int s_tok[R];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r32 = lane & 31, half = lane >> 5;
-  const int T = a.T, V = a.V;
+  const Lane l(threadIdx.x);
+  const int tid = l.tid, lane = l.lane, wv = l.wv, half = l.half, ju = l.ju;
+  const int V = a.V;
   const int b0 = blockIdx.x * R;
-  const int ju = 32 * wv + r32;
-  for (int i = tid; i < 3 * PPL / 4; i += NT) lds[i] = 0.f;   // h = 0
+  HS::zero(tid);  // h = 0
   f32x16 c;
 #pragma unroll
   for (int e = 0; e < 16; ++e) c[e] = 0.f;
@@ -672,120 +703,18 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
   __syncthreads();
 
   for (int s = 0; s < a.steps; ++s) {
-    // ---- (a) ph[r][j] = h2h_b[j] + sum_k h[r][k] * h2h_wt[k][j]
-    {
-      f32x16 acc;
-      const float bj = a.w.h2h_b[ju];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = bj;
-      mfma_cols32_split(sP, a.h2h_p, H, ju, true, r32, half, acc);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sbuf[acc_row(e, half) * H + ju] = acc[e];
-    }
+    phase_h2h<HS>(a, l);
     __syncthreads();
-    // ---- (b) e[r][t] = sum_j score_w[j] * tanh(proj_H[crop r][t][j] + ph[r][j]): one wave per (row, t), GB rows of proj_H in flight
-    {
-      constexpr int GB = 4;
-      float sw[H / 64];
-#pragma unroll
-      for (int q = 0; q < H / 64; ++q) sw[q] = a.w.score_w[lane + 64 * q];
-      const int ngroups = R * T;
-      for (int g0 = wv; g0 < ngroups; g0 += GB * (NT / 64)) {
-        float pr[GB][H / 64];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int g = g0 + u * (NT / 64);
-          if (g < ngroups) {
-            const int r = g / T, t = g - r * T;
-            const float* pP = a.proj_H + ((long)min(b0 + r, a.B - 1) * T + t) * H;
-#pragma unroll
-            for (int q = 0; q < H / 64; ++q) pr[u][q] = pP[lane + 64 * q];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int g = g0 + u * (NT / 64);
-          if (g < ngroups) {
-            const int r = g / T, t = g - r * T;
-            float sacc = 0.f;
-#pragma unroll
-            for (int q = 0; q < H / 64; ++q) sacc = fmaf(sw[q], tanhf(pr[u][q] + sbuf[r * H + lane + 64 * q]), sacc);
-            sacc = wave_sum63(sacc);
-            if (lane == 63) salpha[r * 64 + t] = sacc;
-          }
-        }
-      }
-    }
+    phase_scores<1, LibmMath, HS>(a, l, b0);
     __syncthreads();
-    // ---- (c) softmax over t: wave w handles rows 4w..4w+3, lane = t (T <= 64)
-    for (int r = 4 * wv; r < 4 * wv + 4; ++r) {
-      const float ev0 = lane < T ? salpha[r * 64 + lane] : -INFINITY;
-      const float m = bcast63(wave_max63(ev0));
-      const float ev = lane < T ? expf(ev0 - m) : 0.f;
-      const float sum = bcast63(wave_sum63(ev));
-      if (lane < T) salpha[r * 64 + lane] = ev / sum;
-    }
+    phase_softmax_t<HS>(a.T, l);
     __syncthreads();
-    // ---- (e) gates = b + W_ih_tok[token] + sum_t alpha_t P[crop][t] + W_hh h ; LSTM cell for units ju, rows acc_row(e, half)
-    {
-      f32x16 acc[4];
-      const f32x4 b4 = *reinterpret_cast<const f32x4*>(&a.w.b_gates[ju * 4]);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = acc_row(e, half);
-        const f32x4 t4 = *reinterpret_cast<const f32x4*>(&a.w.wih_tok[((long)s_tok[row] * H + ju) * 4]);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g][e] = add_np(b4[g], t4[g]);
-      }
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {  // one row's frames (T x 16 B per lane, 8 in flight), then its FMAs; rows do not overlap
-        const float* pP = a.ctx_gates + ((long)min(b0 + acc_row(e, half), a.B - 1) * T * H + ju) * 4;
-        const float* pa = salpha + acc_row(e, half) * 64;
-        for (int t0 = 0; t0 < T; t0 += 8) {
-          f32x4 pv[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (t0 + u < T) pv[u] = *reinterpret_cast<const f32x4*>(pP + (long)(t0 + u) * H * 4);
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (t0 + u < T) {
-              const float al = pa[t0 + u];
-#pragma unroll
-              for (int g = 0; g < 4; ++g) acc[g][e] = fmac_np(al, pv[u][g], acc[g][e]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);  // keep the rows' loads from piling up across iterations (registers)
-      }
-      mfma_gates_split(sP, a.whh_p, ju, r32, half, acc);
-      __syncthreads();  // every wave has read the old h
-      float hv[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float ig = sigmoid_libm(acc[0][e]), fg = sigmoid_libm(acc[1][e]), gg = tanhf(acc[2][e]), og = sigmoid_libm(acc[3][e]);
-        c[e] = fg * c[e] + ig * gg;
-        hv[e] = og * tanhf(c[e]);
-      }
-#pragma unroll
-      for (int e = 0; e < 16; e += 2) {  // acc_row(e + 1) == acc_row(e) + 1
-        unsigned char* d = sP + acc_row(e, half) * PSB + ju * 2;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          const uint32_t pk = split_step(hv[e], hv[e + 1]);
-          *reinterpret_cast<uint16_t*>(d + pl * PPL) = (uint16_t)pk;
-          *reinterpret_cast<uint16_t*>(d + pl * PPL + PSB) = (uint16_t)(pk >> 16);
-        }
-      }
-    }
+    phase_gates_cell<1, LibmMath, false, HS>(a, l, b0, s_tok, c);
     __syncthreads();
-    // ---- (f) logits[r][v] = gen_b[v] + sum_k h'[r][k] * gen_wt[k][v]
+    // ---- (f) logits; trace store
     {
-      const bool vok = ju < V;
-      f32x16 acc;
-      const float bv = vok ? a.w.gen_b[ju] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = bv;
-      if (32 * wv < V) mfma_cols32_split(sP, a.gen_p, (V + 31) & ~31, ju, true, r32, half, acc);  // padded columns are zeros
-      if (vok) {
+      const f32x16 acc = phase_generator<HS>(a, l);
+      if (ju < V) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int r = acc_row(e, half);
@@ -815,12 +744,15 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
   }
 }
 
+// dynamic LDS of a decode kernel: the h rows in their form, sbuf, salpha
+template <bool SPLITW>
+constexpr size_t lds_bytes() { return (size_t)(HRows<SPLITW>::FLOATS + R * H + R * 64) * sizeof(float); }
+
 }  // namespace
 
 int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates) return MSOCR_E_ARG;
-  const size_t ldsz = (size_t)(R * XS + R * H + R * 64) * sizeof(float);
-  const size_t ldsz_split = (size_t)3 * PPL + (size_t)(R * H + R * 64) * sizeof(float);
+  const size_t ldsz = lds_bytes<false>(), ldsz_split = lds_bytes<true>();
   if (msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<false>, (int)ldsz) != MSOCR_OK ||
       msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<true>, (int)ldsz_split) != MSOCR_OK)
     return MSOCR_E_LAUNCH;
@@ -829,15 +761,15 @@ int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
     MSOCR_LAUNCH((attn_beam_mfma_kernel<true>), grid, dim3(NT), ldsz_split, s, a);
   else
     MSOCR_LAUNCH((attn_beam_mfma_kernel<false>), grid, dim3(NT), ldsz, s, a);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return LAUNCH_OK();
 }
 
 int msocr_internal_attn_greedy_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p) return MSOCR_E_ARG;
-  const size_t ldsz_split = (size_t)3 * PPL + (size_t)(R * H + R * 64) * sizeof(float);
+  const size_t ldsz_split = lds_bytes<true>();
   if (msocr_internal_lds_limit((const void*)attn_greedy_mfma_kernel, (int)ldsz_split) != MSOCR_OK) return MSOCR_E_LAUNCH;
   MSOCR_LAUNCH(attn_greedy_mfma_kernel, dim3((a.B + R - 1) / R), dim3(NT), ldsz_split, s, a);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return LAUNCH_OK();
 }
 
 // HOST helper: a transposed f32 weight matrix of the decoder ([256][N] row-major: h2h_wt, gen_wt; or gate-interleaved

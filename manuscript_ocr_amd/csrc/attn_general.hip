@@ -16,8 +16,6 @@
 #include "internal.h"
 #include "msocr.h"
 
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {

@@ -6,6 +6,8 @@
 // 32w..32w+31 with their four gates in its four accumulators, so the cell update is lane-local.  Against bilstm_kernel
 // (trba_kernels.hip: 4 crops per workgroup on the VALU, W_hh streamed once per 4 crops) every weight element pulled from L2 feeds
 // 32 rows instead of 4 and the multiply-adds leave the VALU.  xproj already holds x W_ih^T + b_ih + b_hh (a GEMM before this launch).
+// The recurrent product, the cell update and the store of h' to the planes are split_rows32.h's (shared with the attention decoders);
+// this file holds the step loop, the prefetch of the next step's input projections and the hcat store.
 //
 // Replaces recognizers/_trba/model/model.py:9-21 (BidirectionalLSTM.forward: nn.LSTM(bidirectional=True), the recurrent part).
 #include <hip/hip_runtime.h>
@@ -16,20 +18,12 @@
 #include "msocr.h"
 #include "split_rows32.h"
 
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
 namespace {
 
 using namespace split_rows32;
 
 constexpr int NT = 512;
 constexpr int G = 4 * H;
-
-// Hardware-rate transcendentals (v_exp_f32 / v_rcp_f32, 1-2 ulp each), as in the beam kernel: 80 activations per lane and step made
-// the libm forms the longest phase of the step (measured: 28 -> 23 us per step and workgroup with these and the prefetch below).
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(fexp(2.0f * x) + 1.0f); }
 
 __global__ __launch_bounds__(NT, 1) void bilstm_split_kernel(const float* __restrict__ xproj, const uint16_t* __restrict__ whh_p, int B, int T,
                                                             float* __restrict__ hcat) {
@@ -74,24 +68,13 @@ __global__ __launch_bounds__(NT, 1) void bilstm_split_kernel(const float* __rest
     if (s + 1 < T) load_x(s + 1);
     __syncthreads();  // every wave has read h_{t-1}
     float hv[16];
+    lstm_cell<FastMath>(acc, c, hv);  // hardware-rate nonlinearities: 28 -> 23 us per step and workgroup with these and the prefetch
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float ig = sigm(acc[0][e]), fg = sigm(acc[1][e]), gg = ftanh(acc[2][e]), og = sigm(acc[3][e]);
-      c[e] = fg * c[e] + ig * gg;
-      hv[e] = og * ftanh(c[e]);
       const int row = acc_row(e, half);
       if (b0 + row < B) hcat[((long)(b0 + row) * T + t) * (2 * H) + d * H + ju] = hv[e];
     }
-#pragma unroll
-    for (int e = 0; e < 16; e += 2) {  // acc_row(e + 1) == acc_row(e) + 1
-      unsigned char* dst = sP + acc_row(e, half) * PSB + ju * 2;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        const uint32_t pk = split_step(hv[e], hv[e + 1]);
-        *reinterpret_cast<uint16_t*>(dst + pl * PPL) = (uint16_t)pk;
-        *reinterpret_cast<uint16_t*>(dst + pl * PPL + PSB) = (uint16_t)(pk >> 16);
-      }
-    }
+    store_h_planes(sP, ju, half, hv);
     __syncthreads();
   }
 }

@@ -13,10 +13,6 @@
 #include "msocr.h"
 #include "split_mma.h"
 
-// Clear any stale (sticky) HIP error left by earlier runtime calls of the host process before a launch,
-// so that the status read back after it belongs to this launch.
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 

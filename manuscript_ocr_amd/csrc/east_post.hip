@@ -9,13 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "internal.h"
 #include "msocr.h"
-
-// Clear any stale (sticky) HIP error left by earlier runtime calls of the host process before a launch,
-// so that the status read back after it belongs to this launch.
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH)
 
 // ------------------------------------------------------------------------------------------ decode
 // Cells of q x q pixels in row-major order == np.unique(axis=0) order of the quantised (y, x)

@@ -4,11 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "internal.h"
 #include "msocr.h"
-
-// Clear any stale (sticky) HIP error left by earlier runtime calls of the host process before a launch,
-// so that the status read back after it belongs to this launch.
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -20,7 +17,6 @@ static inline int grid_for(long work, int block) {
   if (g < 1) g = 1;
   return (int)g;
 }
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH)
 
 __device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {

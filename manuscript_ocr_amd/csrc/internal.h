@@ -10,6 +10,11 @@
 
 #include "msocr.h"
 
+// Clear any stale (sticky) HIP error left by earlier runtime calls of the host process before a launch, so that the status read
+// back after it (LAUNCH_OK) belongs to this launch.
+#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH)
+
 // conv_igemm.hip: nbatch independent f32 GEMMs of one shape in one launch,
 // C[b][m][n] = sum_k A[b][m][k] * B[b][n][k]  (A [nbatch][M][K], B [nbatch][N][K], C [nbatch][M][N], dense, 16-B aligned).
 __attribute__((visibility("hidden"))) int msocr_internal_gemm_f32_batched(const float* A, const float* B, float* C, long M, int N,

@@ -42,7 +42,6 @@
 #include "internal.h"
 #include "msocr.h"
 
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 #define HD __host__ __device__ __forceinline__
 
 namespace {

@@ -22,9 +22,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "internal.h"
 #include "msocr.h"
-
-#define MSOCR_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 namespace {
 constexpr int RO_T = 1024;         // threads per page

@@ -1,6 +1,8 @@
 // split_rows32.h — device helpers shared by the recurrent kernels that keep a 32-row hidden state (one MFMA row block, 256 units) in
-// LDS and multiply it with a weight matrix streamed from L2 in the split-operand form: attn_beam_mfma.hip (beam decode) and
-// bilstm_mfma.hip (encoder BiLSTM).  Not part of the C ABI.
+// LDS and multiply it with a weight matrix streamed from L2 in the split-operand form: attn_beam_mfma.hip (beam and greedy decode)
+// and bilstm_mfma.hip (encoder BiLSTM).  Three parts: the split-operand products (mfma_cols32_split, mfma_gates_split), the two
+// grades of the LSTM nonlinearities (FastMath, LibmMath), and the row-block LSTM step on the gate accumulators (lstm_cell,
+// store_h_planes).  Not part of the C ABI.
 #ifndef MSOCR_SPLIT_ROWS32_H
 #define MSOCR_SPLIT_ROWS32_H
 #include <hip/hip_runtime.h>
@@ -87,6 +89,48 @@ __device__ __forceinline__ void mfma_gates_split(const unsigned char* __restrict
         for (int pl = 0; pl < 3; ++pl)
           wb[g][pl] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, pl * plstep + (kb + 1) * kbstep + g * gstep, 0);
       }
+    }
+  }
+}
+
+// ---- the LSTM step on the gate accumulators: wave w owns hidden units 32w..32w+31 with their four gates (i, f, g, o) in acc[0..3],
+// element e of every accumulator belonging to state row acc_row(e, half), so the cell update is lane-local.
+
+// The two grades of the nonlinearities, chosen by the kernel at compile time.  FastMath: hardware-rate v_exp_f32 / v_rcp_f32
+// (1-2 ulp each) — a recurrent step evaluates 5 x 32 x 256 gate activations (the beam decode another 32 x T x 256 tanh) on the VALU
+// between the matrix phases, and the libm forms made that the longest phase.  LibmMath: expf / tanhf, for the kernel whose logits
+// are held to a bound the hardware-rate forms miss (attn_greedy_mfma_kernel).
+__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+struct FastMath {
+  static __device__ __forceinline__ float sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + fexp(-x)); }
+  static __device__ __forceinline__ float tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(fexp(2.0f * x) + 1.0f); }
+};
+struct LibmMath {
+  static __device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+  static __device__ __forceinline__ float tanh(float x) { return tanhf(x); }
+};
+
+// c' = f c + i g,  h' = o tanh(c')  for this lane's 16 rows of its unit
+template <class NL>
+__device__ __forceinline__ void lstm_cell(const f32x16 (&acc)[4], f32x16& c, float (&hv)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const float ig = NL::sigmoid(acc[0][e]), fg = NL::sigmoid(acc[1][e]), gg = NL::tanh(acc[2][e]), og = NL::sigmoid(acc[3][e]);
+    c[e] = fg * c[e] + ig * gg;
+    hv[e] = og * NL::tanh(c[e]);
+  }
+}
+
+// h' of unit ju -> the three bf16 planes (hv is consumed: it ends as the residual of the split)
+__device__ __forceinline__ void store_h_planes(unsigned char* sP, int ju, int half, float (&hv)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; e += 2) {  // acc_row(e + 1) == acc_row(e) + 1
+    unsigned char* d = sP + acc_row(e, half) * PSB + ju * 2;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      const uint32_t pk = split_step(hv[e], hv[e + 1]);
+      *reinterpret_cast<uint16_t*>(d + pl * PPL) = (uint16_t)pk;
+      *reinterpret_cast<uint16_t*>(d + pl * PPL + PSB) = (uint16_t)(pk >> 16);
     }
   }
 }

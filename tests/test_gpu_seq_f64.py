@@ -208,6 +208,9 @@ BEAM_CASES = [
     ("mfma-split-hoisted", 256, 194, 8, T_DEF, STEPS_B, "auto"),
     ("mfma-exact-hoisted", 256, 194, 8, T_DEF, STEPS_B, "exact"),
     ("valu", 256, 194, 8, T_DEF, STEPS_B, "valu"),
+    # T 48: phase (b) loops over more (crop, t) groups than one pass holds; V 256: every generator column and top-k slot is in use
+    ("mfma-V256-T48", 256, 256, 8, 48, STEPS_B, "auto"),
+    ("mfma-exact-V256-T48", 256, 256, 8, 48, STEPS_B, "exact"),
 ] + [(f"mfma-K{k}", 256, 194, k, T_DEF, STEPS_B, "auto") for k in (1, 2, 3, 5)] + [
     (f"general-K{k}", 256, 194, k, T_DEF, STEPS_B, "auto") for k in (9, 12, 16)] + [
     ("general-H64-K16", 64, 194, 16, T_DEF, STEPS_B, "auto"),

@@ -478,7 +478,7 @@ def test_split_operand_beam_kernel_matches_the_exact_one_on_every_beam(env):
     (a decoder built from the same weights without the split ones, as precision "fp32-exact" builds it) on 1920 crops, three
     launches.  Steps 0 and 1 come before any near-tie can reorder beams, so the bound is tight: 2e-5 of the largest logit (measured
     3e-6).  A packed-f32 code shape in the hoisted context sum once produced wrong gate pre-activations in ~0.5 % of the rows of one
-    crop slot (see the note at add_np / fmac_np); this comparison is what shows it."""
+    crop slot (see the note on packed f32 in csrc/attn_beam_mfma.hip); this comparison is what shows it."""
     from manuscript_ocr_amd import synth
     from manuscript_ocr_amd.recognizers._trba.net import AttnDecoder, TrbaNet
     B, V, S, K = 1920, 194, 4, 8

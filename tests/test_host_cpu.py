@@ -810,7 +810,8 @@ def test_attn_pack_split_host_layout_and_exactness():
 def test_built_library_has_no_cross_dword_packed_f32_instruction(tmp_path):
     """The gfx950 code objects inside libmsocr.so hold no packed-f32 VALU instruction whose LOW result takes the HIGH dword of a
     source pair (`v_pk_*_f32 ... op_sel:[..]`): that form returned wrong lanes beside bf16 MFMAs on MI355X (csrc/Makefile,
-    DESIGN.md section 4, profiles/r03_attn_packed_probe.txt), so the kernels that had it are compiled without packed-f32 ops.
+    DESIGN.md section 4, profiles/r03_attn_packed_probe.txt and r04_pk_fma_probe.txt; tools/microbench/pk_fma_beside_mfma.hip is
+    the standing reproducer), so the kernels that had it are compiled without packed-f32 ops.
     This looks at the artifact the tests and the bench actually load."""
     import re
     import shutil

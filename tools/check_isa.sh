@@ -1,13 +1,15 @@
 #!/bin/bash
 # dev: counts the packed-f32 VALU instructions per translation unit as the Makefile compiles them, and the forms whose LOW result
 # takes the HIGH dword of a source (op_sel:[..1..]) — the form that misbehaved beside bf16 MFMAs (csrc/Makefile).
-# Expected: no such form anywhere.  Then the footprint of every kernel of the convolution / GEMM units (registers, spills, scratch,
-# static LDS, instruction counts per class): the table a refactor of conv_common.h / split_mma.h is compared on, before and after
-# (profiles/conv_kernel_footprint.txt).   bash tools/check_isa.sh [unit ...]   (CPU only, about a minute; units default to all)
+# Expected: no such form anywhere.  Then the footprint of every kernel of the convolution / GEMM units and of the recurrent
+# matrix-core units (registers, spills, scratch, static LDS, instruction counts per class): the table a refactor of conv_common.h /
+# split_mma.h / split_rows32.h is compared on, before and after (profiles/conv_kernel_footprint.txt, recorded before the buffer_load
+# column existed, and profiles/recurrent_kernel_footprint.txt).   bash tools/check_isa.sh [unit ...]   (CPU only, about a minute;
+# units default to all)
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/manuscript_ocr_amd/csrc
 NOPK=$(sed -n 's/^NOPK_OBJS = //p' $C/Makefile)
-FOOTPRINT="conv_igemm conv_split conv_split_pp winograd"
+FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma bilstm_mfma"
 T=$(mktemp -d)
 trap 'rm -rf $T' EXIT
 units="$*"
@@ -22,7 +24,7 @@ for f in $units; do
   bad=$((bad + m))
 done
 echo
-echo "kernel footprint: vgpr agpr sgpr spill(vgpr+sgpr) scratch_bytes static_lds | v_mfma ds_read ds_write global_load global_store scratch_* s_barrier v_cvt_pk_bf16_f32"
+echo "kernel footprint: vgpr agpr sgpr spill(vgpr+sgpr) scratch_bytes static_lds | v_mfma ds_read ds_write global_load global_store scratch_* s_barrier v_cvt_pk_bf16_f32 buffer_load"
 for f in $FOOTPRINT; do
   [ -f $T/$f.s ] || continue
   awk -v unit=$f '
@@ -36,13 +38,14 @@ for f in $FOOTPRINT; do
     infn && /^[ \t]+scratch_/ { c["scr"]++ }
     infn && /^[ \t]+s_barrier/ { c["bar"]++ }
     infn && /^[ \t]+v_cvt_pk_bf16_f32/ { c["cvt"]++ }
+    infn && /^[ \t]+buffer_load/ { c["bl"]++ }
     /^; TotalNumSgprs:/ { sg = $3 }
     /^; NumVgprs:/ { vg = $3 }
     /^; NumAgprs:/ { ag = $3 }
     /^; ScratchSize:/ { ss = $3 }
     /^; LDSByteSize:/ {
-      reg[fn] = sprintf("%3d %3d %3d", vg, ag, sg); rest[fn] = sprintf("%4d %6d | %4d %4d %4d %4d %4d %4d %3d %3d", ss, $3,
-        c["mfma"], c["dsr"], c["dsw"], c["gl"], c["gs"], c["scr"], c["bar"], c["cvt"])
+      reg[fn] = sprintf("%3d %3d %3d", vg, ag, sg); rest[fn] = sprintf("%4d %6d | %4d %4d %4d %4d %4d %4d %3d %3d %4d", ss, $3,
+        c["mfma"], c["dsr"], c["dsw"], c["gl"], c["gs"], c["scr"], c["bar"], c["cvt"], c["bl"])
     }
     /^[ \t]+\.name:[ \t]+_Z/ { mn = $2 }
     /^[ \t]+\.sgpr_spill_count:/ { sp = $2 }

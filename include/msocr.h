@@ -284,11 +284,47 @@ int msocr_attn_pack_split_host(const float* wt_host, int N, int gate_interleaved
 int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
                              float* logits_out, int32_t* ids_out, void* stream);
 
+/* The same decodes with the attention weights of every step kept (the softmax over the encoder frames that AttentionCell.forward
+ * returns, model.py:40-46, and its callers drop).  The plain entry points above are these with the output off: every other
+ * output is bit-identical either way, and the beam workspace layout is unchanged.
+ * greedy: alpha_out [B][steps][T] f32, every step written (NULL = off).
+ * beam  : a workspace of its own, alpha_ws [B][steps][beam][T] f32 (msocr_attn_beam_alpha_bytes; required, 16-byte aligned), slot-
+ *         indexed exactly like the logits trace: the weights of step s at slot k belong to the hypothesis that occupies slot k
+ *         WHEN step s is computed, the one whose logits are stored at [b][s][k].  Steps skipped by the chunk early exit are not
+ *         written.  The finalize step gathers the best path's weights, alpha_out[b][t][:] = alpha_ws[b][t][path[t]][:] for
+ *         t < t_run, and writes zeros for t >= t_run (alpha_ws, alpha_out required; T as in the decode call). */
+int msocr_attn_greedy_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
+                            int V, int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
+                            float* alpha_out, void* stream);
+int msocr_attn_greedy_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                    const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
+                                    int blank_id, float* logits_out, int32_t* ids_out, float* alpha_out, void* stream);
+int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T);
+int msocr_attn_beam_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
+                          int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id,
+                          int blank_id, int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
+                          const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, void* stream);
+int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                  const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                  const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
+                                  void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream);
+int msocr_attn_beam_finalize_alpha(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
+                                   float* logits_out, int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out,
+                                   void* stream);
+
 /* Recognition confidence (recognizers/_trba/__init__.py:413-431): mean over the t_run generated positions of
  * exp(log_softmax(logits)[id]).  logits [B][steps][V] f32, ids [B][steps] i32 (must be valid for t < trun[b]),
  * trun_dev [B] i32 -> conf_out [B] f32 (0 when t_run == 0). */
 int msocr_seq_confidence(const float* logits, const int32_t* ids, const int32_t* trun_dev, int B, int V, int steps,
                          float* conf_out, void* stream);
+
+/* Per-symbol details of a decoded batch, all [B][steps]: prob_out = exp(log_softmax(logits[b][t])[ids[b][t]]) (the quantity whose
+ * mean over t < t_run is the confidence above), centre_out = sum_j alpha[b][t][j] * (j + 0.5) in encoder frames, peak_out =
+ * the arg-max frame (int32, the smaller index on ties).  Entries t >= trun[b]: 0, 0 and -1.  alpha [B][steps][T] f32 from the
+ * _alpha decodes, T <= 64; everything stays on the device. */
+int msocr_seq_char_details(const float* logits, const int32_t* ids, const float* alpha, const int32_t* trun_dev, int B, int V,
+                           int steps, int T, float* prob_out, float* centre_out, int32_t* peak_out, void* stream);
 
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,

@@ -85,6 +85,18 @@ _SIGS = {
     "msocr_attn_beam_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "msocr_attn_beam_finalize": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_seq_confidence": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "msocr_attn_greedy_alpha": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                        c_vp, c_vp, c_vp, c_vp]),
+    "msocr_attn_greedy_hoisted_alpha": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32,
+                                                c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_attn_beam_alpha_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "msocr_attn_beam_alpha": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
+                                      c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_attn_beam_hoisted_alpha": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
+                                              c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp]),
+    "msocr_attn_beam_finalize_alpha": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "msocr_seq_char_details": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -4,6 +4,9 @@ recognise -> annotate, behind the same duck-typed plugin protocol
 (docs/PIPELINE_API.md: detector.predict(image, vis=False, profile=...) -> {"page"}|tuple|Page,
 recognizer.predict(List[np.ndarray]) -> [{"text","confidence"}|(text, conf)|other]).
 
+`pipeline.char_details = True` (this package's extension, native path only): recognised words come back as CharWords with
+per-symbol confidence and x position (detectors/_types.py).
+
 `process_batch` is broken upstream (it calls a non-existent `self.process`, _pipeline.py:187);
 here it is the per-image `predict`.  `predict_batch` is the MI355X fast path: when detector and
 recogniser are this package's EAST/TRBA it runs the detector once for all pages and the
@@ -347,6 +350,9 @@ class Pipeline:
         arrays, pages_dev, bounds, streams = h["arrays"], h["pages_dev"], h["bounds"], h["streams"]
         recognize_text, profile = h["recognize_text"], h["profile"]
         tm = {"detect_wait+tail": 0.0, "order": 0.0, "crop+enqueue": 0.0, "recognize_wait": 0.0, "assign": 0.0}
+        # `pipeline.char_details = True`: the recogniser also returns per-symbol confidence and position, and collect_batch hands the
+        # recognised words out as CharWords (detectors/_types.py).  Off by default; this package's recogniser only.
+        details = bool(getattr(self, "char_details", False))
         N = len(arrays)
         H, W = arrays[0].shape[:2]
         pages, groups = [None] * N, []
@@ -378,15 +384,17 @@ class Pipeline:
                             with torch.cuda.stream(st):
                                 ro[2].record_stream(st)
                                 desc_dev = torch.cat([ro[2][pi, :c] for pi, c in enumerate(nc_h.tolist()) if c])
-                                if use_graph:  # crop + encode + decode as one hipGraph replay
-                                    grp["handle"] = rec.recognize_start_graph(pages_dev, desc_dev, spans, upload_stream=dst)
+                                grp["desc"] = desc_dev if details else None
+                                if use_graph:  # crop + encode + decode as one hipGraph replay (declines when details are asked for)
+                                    grp["handle"] = rec.recognize_start_graph(pages_dev, desc_dev, spans, upload_stream=dst,
+                                                                              char_details=details)
                                 if grp["handle"] is None:
                                     if prepared is None:  # graph path declined (first call of a bucket, ...): plain launches
                                         with torch.cuda.stream(dst):
                                             prepared = rec.prepare_chunks(off, spans)
                                         st.wait_stream(dst)
                                     canv = ops.crop_resize_pad(pages_dev, None, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                                    grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared)
+                                    grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
                         tm["crop+enqueue"] += time.perf_counter() - t0
                         groups.append(grp)
                         continue
@@ -397,7 +405,7 @@ class Pipeline:
                 if st is not h["main"]:
                     st.wait_stream(h["main"])  # the page upload
                 with torch.cuda.stream(st):
-                    grp = {"words": [], "spans": [], "handle": None}
+                    grp = {"words": [], "spans": [], "handle": None, "lohi": (lo, hi)}
                     if recognize_text:
                         t0 = time.perf_counter()
                         boxes, page_ids = [], []
@@ -430,7 +438,8 @@ class Pipeline:
                                 if st is not up:
                                     st.wait_stream(up)
                                 canv = ops.crop_resize_pad(pages_dev, desc, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                                grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared)
+                                grp["desc"] = desc if details else None
+                                grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
                         tm["crop+enqueue"] += time.perf_counter() - t0
                     else:
                         for pi, r in enumerate(res):
@@ -481,13 +490,20 @@ class Pipeline:
                 if grp["handle"] is not None:
                     with torch.cuda.stream(st):
                         t0 = time.perf_counter()
-                        ids, trun, conf = rec.recognize_finish(grp["handle"], spans=[tuple(s) for s in grp["spans"] if s[1] > 0])
+                        details = bool(grp["handle"].get("char_details"))
+                        fin = rec.recognize_finish(grp["handle"], spans=[tuple(s) for s in grp["spans"] if s[1] > 0])
+                        ids, trun, conf = fin[:3]
+                        if details:
+                            desc = grp["desc"] if isinstance(grp["desc"], np.ndarray) else grp["desc"].cpu().numpy()
                         tm["recognize_wait"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
                     texts = rec.texts(ids, trun)
                     for word, text, c in zip(grp["words"], texts, conf.tolist()):
                         word.text = text
                         word.recognition_confidence = c
+                    if details:
+                        self._attach_chars(grp["words"], rec.chars(ids, trun, fin[3], fin[4], desc[:, 5], desc[:, 1], desc[:, 3]),
+                                           pages[grp["lohi"][0]:grp["lohi"][1]])
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
@@ -498,6 +514,22 @@ class Pipeline:
         if profile:
             print("Pipeline.predict_batch host stages (s):", {k: round(v, 4) for k, v in tm.items()})
         return pages
+
+    @staticmethod
+    def _attach_chars(words, chars, pages):
+        """Replace every recognised Word of `pages` by a CharWord carrying its symbols.  chars[k] belongs to words[k]; x is in page
+        pixels (the recogniser mapped the attention centroid into the word's clamped crop window)."""
+        from .detectors._types import Char, CharWord
+        new = {}
+        for word, ch in zip(words, chars):
+            # the [0, 1] clamp is a no-op guard for CharWord's validation: the confidence is a mean of exp(log-softmax) values, each
+            # <= 1 by the kernel's arithmetic (logp <= 0), so the value equals the plain Word's and a default dump does not change
+            c = word.recognition_confidence
+            new[id(word)] = CharWord(polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
+                                     recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), chars=[Char(**d) for d in ch])
+        for page in pages:
+            for block in page.blocks:
+                block.words = [new.get(id(w), w) for w in block.words]
 
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):

@@ -9,7 +9,7 @@
 // half of the gate product is hoisted out of the step loop (see ctx_sum).  Per step:
 //   (a) ph    = h2h(h)                     [32x256] x [256x256]        MFMA  (wave w: columns 32w..32w+31)
 //   (b) e     = score . tanh(proj_H + ph)  32 x T dot products          VALU  (one wave per (crop, t) pair)
-//   (c) alpha = softmax_t(e)                                            VALU
+//   (c) alpha = softmax_t(e)                                            VALU  (+ optional store of the weights, AttnArgs::alpha_out)
 //   (e) gates = sum_t alpha_t P_t + h x W_hh^T + W_ih_tok[token] + b    VALU + [32x256] x [256x1024]  MFMA
 //       (wave w owns hidden units 32w..32w+31; one 16-byte load per lane = the unit's 4 gates = B operands of 4 MFMAs,
 //        so the LSTM cell update is lane-local in the accumulator layout)
@@ -34,8 +34,23 @@
 
 using namespace split_rows32;
 
+// The optional output of the attention weights (AttnArgs::alpha_out) is a compile-time fact of the translation unit: this file is
+// compiled twice, as itself (ALPHA false: the kernels of the plain entry points) and through attn_beam_mfma_alpha.hip, which defines
+// MSOCR_ATTN_ALPHA and includes it (ALPHA true: the same kernels with the store in phase (c), behind msocr_internal_attn_*_mfma_alpha).
+// Not a test of the pointer in one kernel, and not a template parameter: the kernels sit at the register limit, and both a
+// run-time branch and further instantiations IN THIS UNIT changed the spills of the plain kernels (scratch of the beam kernels
+// 212 -> 276 / 332 B and 68 -> 132 / 216 B; profiles/attn_alpha.txt).  A unit of its own leaves their code object as it was.
+// Observed with one compiler (ROCm 7's hipcc): when the toolchain moves, try the template split again (tools/check_isa.sh).
+#ifdef MSOCR_ATTN_ALPHA
+constexpr bool ALPHA = true;
+#define ATTN_ENTRY(name) name##_alpha
+#else
+constexpr bool ALPHA = false;
+#define ATTN_ENTRY(name) name
+#endif
+
 // Per-phase timestamps of workgroup 0 (dev builds only: tools/attn_phase_times.sh compiles this file with -DMSOCR_ATTN_TIMING)
-#ifdef MSOCR_ATTN_TIMING
+#if defined(MSOCR_ATTN_TIMING) && !defined(MSOCR_ATTN_ALPHA)
 __device__ unsigned long long msocr_attn_timing[64 * 16];
 extern "C" int msocr_attn_timing_read(unsigned long long* out_host) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(msocr_attn_timing), sizeof(msocr_attn_timing)) == hipSuccess ? 0 : -2;
@@ -340,16 +355,26 @@ __device__ __forceinline__ void phase_scores(const AttnArgs& a, const Lane& l, i
   }
 }
 
-// (c) softmax over t in salpha: wave w handles rows 4w..4w+3, lane = t (T <= 64)
-template <class HS>
-__device__ __forceinline__ void phase_softmax_t(int T, const Lane& l) {
+// (c) softmax over t in salpha: wave w handles rows 4w..4w+3, lane = t (T <= 64).  ALPHA (a compile-time fact of the translation
+//     unit, see above; so uniform over the workgroup): the lanes that hold the weights of a live row (crop < B, beam slot < K) also
+//     store them to a.alpha_out, step s of [B][steps][RPC == 1 ? 1 : K][T]: the slot is the one the step's logits are stored at.
+template <int RPC, class HS>
+__device__ __forceinline__ void phase_softmax_t(const AttnArgs& a, const Lane& l, int b0, int s) {
   float* const salpha = salpha_of<HS>();
+  const int T = a.T;
   for (int r = 4 * l.wv; r < 4 * l.wv + 4; ++r) {
     const float ev0 = l.lane < T ? salpha[r * 64 + l.lane] : -INFINITY;
     const float m = bcast63(wave_max63(ev0));
     const float ev = l.lane < T ? expf(ev0 - m) : 0.f;
     const float sum = bcast63(wave_sum63(ev));
-    if (l.lane < T) salpha[r * 64 + l.lane] = ev / sum;
+    if (l.lane < T) {
+      const float al = ev / sum;
+      salpha[r * 64 + l.lane] = al;
+      if constexpr (ALPHA) {
+        const int b = b0 + r / RPC, rb = r % RPC, slots = RPC == 1 ? 1 : a.K;
+        if (b < a.B && rb < slots) a.alpha_out[(((long)b * a.steps + s) * slots + rb) * T + l.lane] = al;
+      }
+    }
   }
 }
 
@@ -474,7 +499,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     phase_scores<KB8, FastMath, HS>(a, l, b0);
     __syncthreads();
     TSTAMP(2);
-    phase_softmax_t<HS>(a.T, l);
+    phase_softmax_t<KB8, HS>(a, l, b0, s);
     __syncthreads();
     TSTAMP(3);
     TSTAMP(4);  // (d) is empty, the context product being hoisted; the stamp keeps tools/attn_phase_times.sh's phase numbering
@@ -707,7 +732,7 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
     __syncthreads();
     phase_scores<1, LibmMath, HS>(a, l, b0);
     __syncthreads();
-    phase_softmax_t<HS>(a.T, l);
+    phase_softmax_t<1, HS>(a, l, b0, s);
     __syncthreads();
     phase_gates_cell<1, LibmMath, false, HS>(a, l, b0, s_tok, c);
     __syncthreads();
@@ -750,8 +775,9 @@ constexpr size_t lds_bytes() { return (size_t)(HRows<SPLITW>::FLOATS + R * H + R
 
 }  // namespace
 
-int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
-  if (!a.ctx_gates) return MSOCR_E_ARG;
+// the kernels of this unit: with the attention-weight output in attn_beam_mfma_alpha.hip's copy (the _alpha names), without it here
+int ATTN_ENTRY(msocr_internal_attn_beam_mfma)(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates || ALPHA != (a.alpha_out != nullptr)) return MSOCR_E_ARG;
   const size_t ldsz = lds_bytes<false>(), ldsz_split = lds_bytes<true>();
   if (msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<false>, (int)ldsz) != MSOCR_OK ||
       msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<true>, (int)ldsz_split) != MSOCR_OK)
@@ -764,14 +790,15 @@ int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s) {
   return LAUNCH_OK();
 }
 
-int msocr_internal_attn_greedy_mfma(const AttnArgs& a, hipStream_t s) {
-  if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p) return MSOCR_E_ARG;
+int ATTN_ENTRY(msocr_internal_attn_greedy_mfma)(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p || ALPHA != (a.alpha_out != nullptr)) return MSOCR_E_ARG;
   const size_t ldsz_split = lds_bytes<true>();
   if (msocr_internal_lds_limit((const void*)attn_greedy_mfma_kernel, (int)ldsz_split) != MSOCR_OK) return MSOCR_E_LAUNCH;
   MSOCR_LAUNCH(attn_greedy_mfma_kernel, dim3((a.B + R - 1) / R), dim3(NT), ldsz_split, s, a);
   return LAUNCH_OK();
 }
 
+#ifndef MSOCR_ATTN_ALPHA
 // HOST helper: a transposed f32 weight matrix of the decoder ([256][N] row-major: h2h_wt, gen_wt; or gate-interleaved
 // [256][N / 4][4]: whh_t) -> the packed split form the matrix-core beam kernel reads: out[plane][k / 16][column][k % 16] bf16 with
 // w == p0 + p1 + p2 exactly; columns padded with zeros to a multiple of 32; gate-interleaved input: column = gate * (N / 4) + unit.
@@ -799,3 +826,4 @@ extern "C" int msocr_attn_pack_split_host(const float* wt_host, int N, int gate_
     }
   return MSOCR_OK;
 }
+#endif

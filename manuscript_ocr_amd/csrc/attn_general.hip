@@ -102,7 +102,14 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
         salpha[tid * 64 + t] = ev;
         sum += ev;
       }
-      for (int t = 0; t < T; ++t) salpha[tid * 64 + t] = salpha[tid * 64 + t] / sum;
+      // optional trace of the weights (AttnArgs::alpha_out, a kernel argument: uniform over the workgroup), [B][steps][K][T], from the
+      // thread that holds the row
+      float* const ao = a.alpha_out ? a.alpha_out + (((long)b * a.steps + s) * K + tid) * T : nullptr;
+      for (int t = 0; t < T; ++t) {
+        const float al = salpha[tid * 64 + t] / sum;
+        salpha[tid * 64 + t] = al;
+        if (ao) ao[t] = al;
+      }
     }
     __syncthreads();
     // (d) ctx[r][j] = sum_t alpha[r][t] * batch_H[t][j]

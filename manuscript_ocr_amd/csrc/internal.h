@@ -78,13 +78,19 @@ struct AttnArgs {
   const int32_t* chunk_id;    // beam, optional: [B] index of the reference chunk (one predict() slice of batch_size crops) of each crop
   const int32_t* chunk_size;  // [nchunks] crops per chunk
   int32_t* chunk_state;       // [2*nchunks] zeroed by the caller: {crops finished, max finish step}; enables the early exit
+  float* alpha_out;     // optional attention weights of every step (nullptr = off): greedy [B][steps][T]; beam [B][steps][K][T], slot-
+                        // indexed like the logits trace (the weights of step s at slot rb belong to the hypothesis whose logits are there)
 };
 // attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the matrix cores (H == 256, V <= 256, T <= 48, beam <= 8;
 // needs ctx_gates): split-operand products with the split weights, exact-f32 MFMA without them
 __attribute__((visibility("hidden"))) int msocr_internal_attn_beam_mfma(const AttnArgs& a, hipStream_t s);
 // attn_beam_mfma.hip: greedy decode with 32 crops per workgroup on the matrix cores (same shapes; needs ctx_gates and the split weights)
 __attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma(const AttnArgs& a, hipStream_t s);
+// attn_beam_mfma_alpha.hip: the same two with the attention weights of every step stored to a.alpha_out (required; the two above
+// require it to be nullptr)
+__attribute__((visibility("hidden"))) int msocr_internal_attn_beam_mfma_alpha(const AttnArgs& a, hipStream_t s);
+__attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma_alpha(const AttnArgs& a, hipStream_t s);
 // attn_general.hip: greedy / beam decode for every shape of the envelope (see its header), H == 256 included; the plain entry points
-// msocr_attn_greedy / msocr_attn_beam run it.  Same outputs and workspace layout as the matrix-core kernels.
+// msocr_attn_greedy / msocr_attn_beam run it.  Same outputs and workspace layout as the matrix-core kernels; a.alpha_out optional.
 __attribute__((visibility("hidden"))) int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t s);
 #endif

@@ -5,7 +5,7 @@
 // lane j reads column j), LDS-resident per-row state and wave-level reductions; no MFMA.
 // The sequential loop (T encoder steps) lives INSIDE one launch: rows are independent, so
 // one workgroup owns a few rows for the whole loop and no inter-workgroup hand-off exists.
-// The decode kernels themselves are in attn_beam_mfma.hip and attn_general.hip.
+// The decode kernels themselves are in attn_beam_mfma.hip (and its second compilation attn_beam_mfma_alpha.hip) and attn_general.hip.
 //
 //   msocr_se_residual       <- recognizers/_trba/model/seresnet31.py:5-20, 61-66
 //   msocr_mean_over_h       <- recognizers/_trba/model/model.py:388-390
@@ -13,6 +13,9 @@
 //   msocr_attn_greedy(_hoisted)       <- model.py:34-46 + 227-259
 //   msocr_attn_beam(_hoisted, _finalize) <- model.py:34-46 + 92-225
 //   msocr_seq_confidence    <- recognizers/_trba/__init__.py:413-431
+//   msocr_seq_char_details  per-symbol probability and attention position (no counterpart: the reference drops both)
+// The _alpha entry points are the same decodes with the attention weights of every step kept (model.py:40-46 returns them, its
+// callers drop them); the plain ones are those with the output off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -293,11 +296,13 @@ extern "C" int msocr_bilstm_recurrent(const float* xproj, const float* w_hh_t, i
 // The decode kernels live in attn_beam_mfma.hip (matrix cores: the _hoisted entries) and attn_general.hip (every shape: the plain
 // entries); this file keeps the argument checks, the beam workspace layout and the finalize step.
 
-// finalize: walk the back-pointers from (t_run-1, best_at[t_run-1]) and gather the path's logits
+// finalize: walk the back-pointers from (t_run-1, best_at[t_run-1]) and gather the path's logits; with alpha_ws [B][steps][K][T] also the
+// path's attention weights -> alpha_out [B][steps][T] (zeros for t >= t_run)
 __global__ void attn_beam_finalize_kernel(const float* __restrict__ ws_logits, const int32_t* __restrict__ back,
                                           const int32_t* __restrict__ tokv, const int32_t* __restrict__ best_at,
                                           const int32_t* __restrict__ trun, int V, int steps, int K, float* __restrict__ logits_out,
-                                          int32_t* __restrict__ ids_out) {
+                                          int32_t* __restrict__ ids_out, const float* __restrict__ alpha_ws, int T,
+                                          float* __restrict__ alpha_out) {
   const int b = blockIdx.x, tid = threadIdx.x;
   __shared__ int path[64];
   const int tr = trun[b];
@@ -315,6 +320,11 @@ __global__ void attn_beam_finalize_kernel(const float* __restrict__ ws_logits, c
   for (int t = 0; t < tr; ++t)
     for (int v = tid; v < V; v += blockDim.x)
       logits_out[((long)b * steps + t) * V + v] = ws_logits[(((long)b * steps + t) * K + path[t]) * V + v];
+  if (alpha_ws)
+    for (int i = tid; i < steps * T; i += blockDim.x) {
+      const int t = i / T, j = i - t * T;
+      alpha_out[((long)b * steps + t) * T + j] = t < tr ? alpha_ws[(((long)b * steps + t) * K + path[t]) * T + j] : 0.f;
+    }
 }
 
 // shapes of the matrix-core kernels (attn_beam_mfma.hip: hidden 256, the logits of a row in 256 LDS floats, T <= 48; beam <= 8)
@@ -328,24 +338,31 @@ static int check_attn(const float* bh, const float* ph, const msocr_attn_weights
 }
 
 // every shape of the envelope on the general kernel (attn_general.hip)
-extern "C" int msocr_attn_greedy(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                 int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
+// alpha_out: [B][steps][T] f32, the attention weights of every step, or NULL (off: the plain entry point)
+extern "C" int msocr_attn_greedy_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
+                                       int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
+                                       float* alpha_out, void* stream) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
   if (sos_id < 0 || sos_id >= V) return MSOCR_E_ARG;
   AttnArgs a{};
   a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w;
   a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
   a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.ids_out = ids_out;
+  a.logits_out = logits_out; a.ids_out = ids_out; a.alpha_out = alpha_out;
   return msocr_internal_attn_general(a, H, false, (hipStream_t)stream);
+}
+extern "C" int msocr_attn_greedy(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
+                                 int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
+  return msocr_attn_greedy_alpha(batch_H, proj_H, w, B, T, H, V, steps, sos_id, eos_id, blank_id, logits_out, ids_out, nullptr, stream);
 }
 
 // mode="greedy" on the matrix cores (attn_greedy_mfma_kernel, csrc/attn_beam_mfma.hip): 32 crops per workgroup, the three per-step
 // products in the split-operand form, the context half of the gate product hoisted (ctx_gates = batch_H x W_ih[:, :H]^T, [B][T][H][4],
 // computed once per call by a GEMM).  Same outputs as msocr_attn_greedy; hidden 256, V <= 256, T <= 48 only.
-extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                         const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
-                                         int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
+extern "C" int msocr_attn_greedy_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates,
+                                               const msocr_attn_weights* w, const msocr_attn_split_weights* ws, int B, int T, int H, int V,
+                                               int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
+                                               float* alpha_out, void* stream) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
   if (sos_id < 0 || sos_id >= V || !attn_mfma_shape(T, H, V)) return MSOCR_E_ARG;
   if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
@@ -356,8 +373,14 @@ extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj
   a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p;
   a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
   a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.ids_out = ids_out;
-  return msocr_internal_attn_greedy_mfma(a, (hipStream_t)stream);
+  a.logits_out = logits_out; a.ids_out = ids_out; a.alpha_out = alpha_out;
+  return alpha_out ? msocr_internal_attn_greedy_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_greedy_mfma(a, (hipStream_t)stream);
+}
+extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                         const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
+                                         int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
+  return msocr_attn_greedy_hoisted_alpha(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, sos_id, eos_id, blank_id, logits_out, ids_out,
+                                         nullptr, stream);
 }
 
 // workspace: logits [B][steps][K][V] f32 | back [B][steps][K] i32 | tokv [B][steps][K] i32 | best_at [B][steps] i32
@@ -366,13 +389,18 @@ extern "C" int64_t msocr_attn_beam_workspace_bytes(int B, int steps, int beam, i
   if (B <= 0 || steps <= 0 || beam <= 0 || V <= 0) return 0;
   return beam_ws_logits(B, steps, beam, V) + (int64_t)B * steps * beam * 8 + (int64_t)B * steps * 4 + 256;
 }
+// the separate attention-weight workspace of the _alpha entry points: [B][steps][K][T] f32, slot-indexed like the logits trace
+extern "C" int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T) {
+  if (B <= 0 || steps <= 0 || beam <= 0 || T <= 0) return 0;
+  return (int64_t)B * steps * beam * T * 4;
+}
 
 // ctx_gates == nullptr (msocr_attn_beam): the general kernel, every shape of the envelope; otherwise (msocr_attn_beam_hoisted) the
 // matrix-core kernel, its products in the split-operand form with ws, on the exact-f32 MFMA without
 static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                           const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
                           int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                          int32_t* chunk_state_dev, void* stream) {
+                          int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
   if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
   if (ctx_gates && (!attn_mfma_shape(T, H, V) || beam > 8)) return MSOCR_E_ARG;
@@ -387,9 +415,10 @@ static int attn_beam_impl(const float* batch_H, const float* proj_H, const float
   a.tokv = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
   a.best_at = (int32_t*)p;
   a.fin_step = fin_step_out;
+  a.alpha_out = (float*)alpha_ws;  // nullptr (the plain entry points): off
   if (chunk_id_dev && chunk_size_dev && chunk_state_dev) { a.chunk_id = chunk_id_dev; a.chunk_size = chunk_size_dev; a.chunk_state = chunk_state_dev; }
   if (!ctx_gates) return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
-  return msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
+  return alpha_ws ? msocr_internal_attn_beam_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
 }
 
 extern "C" int msocr_attn_beam(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
@@ -397,23 +426,49 @@ extern "C" int msocr_attn_beam(const float* batch_H, const float* proj_H, const 
                                int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
                                int32_t* chunk_state_dev, void* stream) {
   return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
-                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, stream);
+                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, nullptr, stream);
+}
+// the same with the attention weights of every computed step stored to alpha_ws (msocr_attn_beam_alpha_bytes, 16-byte aligned)
+extern "C" int msocr_attn_beam_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
+                                     int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                     int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                     int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
+  if (!alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
+                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
 }
 
+static int attn_beam_hoisted_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                  const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                  const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
+                                  void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
+  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
+  if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15)))
+    return MSOCR_E_ARG;
+  return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
+                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
+}
 extern "C" int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                                        const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
                                        const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
                                        void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
                                        int32_t* chunk_state_dev, void* stream) {
-  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
-  if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15)))
-    return MSOCR_E_ARG;
-  return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, stream);
+  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
+                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, nullptr, stream);
+}
+extern "C" int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                             const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                             const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                             int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
+                                             const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
+  if (!alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
+                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
 }
 
-extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
-                                        float* logits_out, int32_t* ids_out, void* stream) {
+static int attn_beam_finalize_impl(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev, float* logits_out,
+                                   int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out, void* stream) {
   if (!workspace || !trun_dev || !logits_out || !ids_out || B <= 0 || V <= 0 || steps <= 0 || steps > 64 || beam < 1 || beam > 16)
     return MSOCR_E_ARG;
   const char* p = (const char*)workspace;
@@ -422,32 +477,45 @@ extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int
   const int32_t* tokv = (const int32_t*)p; p += (int64_t)B * steps * beam * 4;
   const int32_t* best_at = (const int32_t*)p;
   MSOCR_LAUNCH(attn_beam_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, wl, back, tokv, best_at, trun_dev, V, steps, beam,
-               logits_out, ids_out);
+               logits_out, ids_out, (const float*)alpha_ws, T, alpha_out);
   return LAUNCH_OK();
+}
+extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
+                                        float* logits_out, int32_t* ids_out, void* stream) {
+  return attn_beam_finalize_impl(workspace, B, V, steps, beam, trun_dev, logits_out, ids_out, nullptr, 0, nullptr, stream);
+}
+// also gathers the path's attention weights from alpha_ws [B][steps][beam][T] (msocr_attn_beam_alpha) into alpha_out [B][steps][T]
+extern "C" int msocr_attn_beam_finalize_alpha(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
+                                              float* logits_out, int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out,
+                                              void* stream) {
+  if (!alpha_ws || ((uintptr_t)alpha_ws & 15) || !alpha_out || T <= 0 || T > 64) return MSOCR_E_ARG;
+  return attn_beam_finalize_impl(workspace, B, V, steps, beam, trun_dev, logits_out, ids_out, alpha_ws, T, alpha_out, stream);
 }
 
 // --------------------------------------------------------------------------------------------- confidence
 // TRBA.predict's confidence (recognizers/_trba/__init__.py:413-431): log_softmax over V of the returned logits,
 // exp of the chosen token's log-prob, mean over ALL t_run generated positions.  One wave per row.
+
+// exp(log_softmax(x[0 .. V))[id]) by one wave, in every lane: the probability of the chosen token of one decode step
+__device__ __forceinline__ float token_prob(const float* __restrict__ x, int V, int id, int lane) {
+  float m = -INFINITY;
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float s = 0.f;
+  for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
+  s = wave_sum(s);
+  const float logp = (x[id] - m) - logf(s);
+  return expf(logp);
+}
+
 __global__ __launch_bounds__(64) void seq_confidence_kernel(const float* __restrict__ logits, const int32_t* __restrict__ ids,
                                                              const int32_t* __restrict__ trun, int V, int steps,
                                                              float* __restrict__ conf) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int tr = trun[b];
   float acc = 0.f;
-  for (int t = 0; t < tr; ++t) {
-    const float* x = logits + ((long)b * steps + t) * V;
-    float m = -INFINITY;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float s = 0.f;
-    for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
-    s = wave_sum(s);
-    const int id = ids[(long)b * steps + t];
-    const float logp = (x[id] - m) - logf(s);
-    acc += expf(logp);
-  }
+  for (int t = 0; t < tr; ++t) acc += token_prob(logits + ((long)b * steps + t) * V, V, ids[(long)b * steps + t], lane);
   if (lane == 0) conf[b] = tr > 0 ? acc / (float)tr : 0.f;
 }
 
@@ -455,5 +523,48 @@ extern "C" int msocr_seq_confidence(const float* logits, const int32_t* ids, con
                                     float* conf_out, void* stream) {
   if (!logits || !ids || !trun_dev || !conf_out || B <= 0 || V <= 0 || steps <= 0) return MSOCR_E_ARG;
   MSOCR_LAUNCH(seq_confidence_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, ids, trun_dev, V, steps, conf_out);
+  return LAUNCH_OK();
+}
+
+// --------------------------------------------------------------------------------------------- per-symbol details
+// What the word confidence is the mean of, and where the decoder looked: one wave per (row, step), lane = encoder frame (T <= 64).
+//   prob   = token_prob of the step (the mean of prob[b][: t_run] is msocr_seq_confidence's value up to the order of the sum)
+//   centre = sum_j alpha[j] * (j + 0.5), in frames; summed in f64 (64 terms: the f32 result is the rounded exact sum)
+//   peak   = arg-max frame, the smaller index on ties
+// Steps t >= t_run: 0, 0, -1.
+constexpr int CD_WAVES = 4;
+__global__ __launch_bounds__(64 * CD_WAVES) void seq_char_details_kernel(const float* __restrict__ logits, const int32_t* __restrict__ ids,
+                                                                         const float* __restrict__ alpha, const int32_t* __restrict__ trun,
+                                                                         int B, int V, int steps, int T, float* __restrict__ prob,
+                                                                         float* __restrict__ centre, int32_t* __restrict__ peak) {
+  const int lane = threadIdx.x & 63;
+  const long p = (long)blockIdx.x * CD_WAVES + (threadIdx.x >> 6);  // (row, step) of this wave
+  if (p >= (long)B * steps) return;
+  const int b = (int)(p / steps), t = (int)(p - (long)b * steps);
+  if (t >= trun[b]) {
+    if (lane == 0) { prob[p] = 0.f; centre[p] = 0.f; peak[p] = -1; }
+    return;
+  }
+  const float pr = token_prob(logits + p * V, V, ids[p], lane);
+  float av = lane < T ? alpha[p * T + lane] : -INFINITY;
+  double c = lane < T ? (double)av * ((double)lane + 0.5) : 0.0;
+  int ai = lane;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_xor(c, o);
+    const float ov = __shfl_xor(av, o);
+    const int oi = __shfl_xor(ai, o);
+    if (ov > av || (ov == av && oi < ai)) { av = ov; ai = oi; }
+  }
+  if (lane == 0) { prob[p] = pr; centre[p] = (float)c; peak[p] = ai; }
+}
+
+extern "C" int msocr_seq_char_details(const float* logits, const int32_t* ids, const float* alpha, const int32_t* trun_dev, int B, int V,
+                                      int steps, int T, float* prob_out, float* centre_out, int32_t* peak_out, void* stream) {
+  if (!logits || !ids || !alpha || !trun_dev || !prob_out || !centre_out || !peak_out || B <= 0 || V <= 0 || steps <= 0 || T <= 0 || T > 64)
+    return MSOCR_E_ARG;
+  const long n = (long)B * steps;
+  MSOCR_LAUNCH(seq_char_details_kernel, dim3((unsigned)((n + CD_WAVES - 1) / CD_WAVES)), dim3(64 * CD_WAVES), 0, (hipStream_t)stream, logits,
+               ids, alpha, trun_dev, B, V, steps, T, prob_out, centre_out, peak_out);
   return LAUNCH_OK();
 }

@@ -20,6 +20,21 @@ class Word(BaseModel):
     recognition_confidence: Optional[float] = Field(None, description="mean per-step token probability from the recogniser", **_UNIT)
 
 
+class Char(BaseModel):
+    """One recognised symbol of a word (this package's extension; the reference has no symbol-level output)."""
+
+    char: str = Field(..., description="the symbol, one charset token")
+    confidence: float = Field(..., description="probability the recogniser gave the token at its decode step", **_UNIT)
+    x: float = Field(..., description="estimated horizontal centre in pixels of the image the word came from (attention centroid)")
+
+
+class CharWord(Word):
+    """A Word with its symbols, written by Pipeline when `char_details` is on.  Block.words is declared as List[Word], so a
+    default model_dump() of a Page serialises a CharWord as a Word: dumps do not change with the flag."""
+
+    chars: List[Char] = Field(default_factory=list, description="one entry per symbol of `text`, in order")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

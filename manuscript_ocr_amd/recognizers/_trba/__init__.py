@@ -7,7 +7,8 @@ decoder (greedy and beam) run on the MI355X through libmsocr.so; there is no CPU
 
 Extensions (keyword-only): precision="fp32"|"bf16" for the CNN (recurrent/attention stages are
 always exact f32), state_dict=... / config=... for in-memory weights (nothing can be downloaded
-offline), device_batch=2048 rows per launch sequence.  Confidences reproduce the reference's
+offline), device_batch=2048 rows per launch sequence, predict(..., return_chars=True) for per-symbol
+confidence and position (from the decoder's attention weights).  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -20,7 +21,7 @@ import torch
 from PIL import Image
 
 from .net import TrbaNet
-from .transforms import decode_tokens, load_charset, resize_and_pad
+from .transforms import decode_tokens, frame_to_pixel, load_charset, resize_and_pad, resized_size
 
 
 class _GraphLease:
@@ -202,11 +203,12 @@ class TRBA:
         return bounds, metas, meta_dev
 
     def recognize_start(self, canvases_dev: torch.Tensor, mode="beam", beam_size=8, temperature=1.7, alpha=0.9, spans=None,
-                        batch_size=32, prepared=None):
+                        batch_size=32, prepared=None, char_details=False):
         """Phase 1 — encode + decode of [N,img_h,img_w,3] u8 device canvases, enqueued on the CURRENT stream without any
         synchronisation.  Returns a handle for `recognize_finish`.  `spans`/`batch_size` (the same values `recognize_finish`
         will get) tell the beam kernel which rows share a reference chunk, so it can stop a chunk where the reference's
-        loop does; without them every row runs all max_length steps (same results)."""
+        loop does; without them every row runs all max_length steps (same results).  char_details: the decode also keeps its attention
+        weights (on the device) and `recognize_finish` returns per-symbol arrays; every other result is the same either way."""
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         N = canvases_dev.shape[0]
@@ -223,7 +225,8 @@ class TRBA:
             cv = canvases_dev[lo:hi]
             batch_H, proj_H = self.model.encode(cv)
             if mode == "greedy":
-                parts.append(self.model.greedy(batch_H, proj_H, self.max_length, self.sos_id, self.eos_id, self.blank_id))
+                parts.append(self.model.greedy(batch_H, proj_H, self.max_length, self.sos_id, self.eos_id, self.blank_id,
+                                               want_alpha=char_details))
             else:
                 chunks = None
                 if meta_dev is not None:
@@ -232,22 +235,23 @@ class TRBA:
                               torch.zeros((2 * nch,), dtype=torch.int32, device=self.device))
                     off += nrows + nch
                 parts.append(self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
-                                             self.blank_id, chunks))
-        return {"parts": parts, "N": N, "mode": mode, "beam": beam_size, "bounds": bounds}
+                                             self.blank_id, chunks, want_alpha=char_details))
+        return {"parts": parts, "N": N, "mode": mode, "beam": beam_size, "bounds": bounds, "char_details": bool(char_details)}
 
     def recognize_start_graph(self, pages_dev: torch.Tensor, desc_dev: torch.Tensor, spans, batch_size=32, beam_size=8,
-                              temperature=1.7, alpha=0.9, upload_stream=None):
+                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False):
         """`recognize_start` for crops that are still descriptors on the device (ops.reading_order_crops), as ONE hipGraph replay:
         crop + ResizeAndPadA, SE-ResNet31, BiLSTMs and the beam decode of up to `device_batch` rows are captured once per
         (page tensor, row bucket) and replayed (BASELINE configs[3]: "hipGraph-captured").  The row count is rounded up to a
         multiple of 32; the padding rows repeat crop 0 and form a reference chunk of their own, so they can neither change a real
         row's result nor delay a real chunk's early exit.  Falls back to the eager path (returns None) for empty or oversized
         batches, while kernels are being profiled, and for the first call of a bucket (lazy one-time kernel attributes must not
-        fall into a capture).  Results are bit-identical to the eager path (tests/test_gpu_pipeline.py)."""
+        fall into a capture), and whenever char_details is asked for (that path is not captured).  Results are bit-identical to the
+        eager path (tests/test_gpu_pipeline.py)."""
         from ... import ops
         M = int(desc_dev.shape[0])
         Mcap = (M + 31) // 32 * 32
-        if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None:
+        if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details:
             return None
         nch_cap = Mcap // batch_size + len(spans) + 2  # chunks of the real rows (<= rows/batch_size + one per page) + the padding chunk
         # one pool per launch stream: the groups of a batch are in flight together, each replays its own instances
@@ -321,7 +325,11 @@ class TRBA:
         `spans` = [(start, count), ...] groups of rows that the reference would have passed to ONE predict() call
         (one page each); inside a span rows are chunked by `batch_size` and every chunk stops at its own step
         (greedy: first step where every row emits EOS; beam: once every beam of every row is finished) — that run
-        length enters the confidences.  Only ids and one float per row cross PCIe (msocr_seq_confidence)."""
+        length enters the confidences.  Only ids and one float per row cross PCIe (msocr_seq_confidence).
+        A handle started with char_details=True: three more host arrays [N, steps] behind the others — prob (f32: the probability
+        of the token of every step, whose mean over t < t_run is the confidence), centre (f32: the attention centroid in encoder
+        frames) and peak (i32: the arg-max frame); steps t >= t_run hold 0, 0, -1 (msocr_seq_char_details; the weights stay on the
+        device)."""
         from ... import _native as nat
         from ... import ops
         try:
@@ -354,32 +362,49 @@ class TRBA:
         self.last_run_length_sum = getattr(self, "last_run_length_sum", 0) + int(trun[:M_real].sum())
         self.last_rows = getattr(self, "last_rows", 0) + M_real
         trun_dev = torch.from_numpy(trun).to(self.device)
-        ids_out, conf_out, logit_out = [], [], []
+        details = bool(handle.get("char_details"))
+        ids_out, conf_out, logit_out, det_out = [], [], [], []
         for k, (s, hi) in enumerate(handle["bounds"]):
             B = hi - s
             tr = trun_dev[s:s + B]
             if mode == "greedy":
-                lg, ids = parts[k]
+                lg, ids = parts[k][:2]
+                al = parts[k][2] if details else None
+            elif details:
+                lg, ids, al = self.model.beam_finalize(parts[k][0], B, steps, beam_size, tr, alpha_ws=parts[k][3])
             else:
                 lg, ids = self.model.beam_finalize(parts[k][0], B, steps, beam_size, tr)
             conf = torch.empty((B,), dtype=torch.float32, device=self.device)
             nat.check(nat.lib().msocr_seq_confidence(lg.data_ptr(), ids.data_ptr(), tr.data_ptr(), B, self.model.V, steps, conf.data_ptr(),
                                                      ops._stream()), "seq_confidence")
             ids_out.append(ids), conf_out.append(conf)
+            if details:
+                prob = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+                centre = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+                peak = torch.empty((B, steps), dtype=torch.int32, device=self.device)
+                nat.check(nat.lib().msocr_seq_char_details(lg.data_ptr(), ids.data_ptr(), al.data_ptr(), tr.data_ptr(), B, self.model.V, steps,
+                                                           al.shape[-1], prob.data_ptr(), centre.data_ptr(), peak.data_ptr(), ops._stream()),
+                          "seq_char_details")
+                det_out.append((prob, centre, peak))
             if return_logits:
                 logit_out.append(lg.cpu().numpy())
             parts[k] = None
         ids_h = torch.cat(ids_out).cpu().numpy()[:M_real]
         conf_h = torch.cat(conf_out).cpu().numpy()[:M_real]
+        out = (ids_h, trun[:M_real], conf_h)
         if return_logits:
-            return ids_h, trun[:M_real], conf_h, np.concatenate(logit_out)[:M_real]
-        return ids_h, trun[:M_real], conf_h
+            out += (np.concatenate(logit_out)[:M_real],)
+        if details:
+            out += tuple(torch.cat([d[i] for d in det_out]).cpu().numpy()[:M_real] for i in range(3))
+        return out
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
-                           spans=None, return_logits=False):
-        """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits]) on host."""
+                           spans=None, return_logits=False, char_details=False):
+        """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak])
+        on host."""
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
-                                                          spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size),
+                                                          spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
+                                                          char_details=char_details),
                                      batch_size, spans, return_logits)
 
     def texts(self, ids, trun) -> List[str]:
@@ -401,14 +426,46 @@ class TRBA:
         return [{"text": decode_tokens(ids[j, : int(trun[j])], self.itos, self.pad_id, self.eos_id, self.blank_id),
                  "confidence": float(conf[j])} for j in range(len(ids))]
 
+    def chars(self, ids, trun, prob, centre, new_w, x1, x2) -> List[List[Dict[str, Any]]]:
+        """Per row, one {"char", "confidence", "x"} per token that `texts` / decode_tokens keep (t < t_run, up to the first EOS, PAD
+        and BLANK skipped), so "".join(c["char"]) is the row's text.  x = frame_to_pixel(centre, new_w, x1, x2): new_w [N] the resized
+        widths ResizeAndPadA pasted at x = 0, [x1, x2) the rows' windows in the image the positions are wanted in."""
+        ids = np.asarray(ids)
+        n, T = (ids.shape[0], ids.shape[1]) if ids.ndim == 2 else (len(ids), 0)
+        if not n or T == 0:
+            return [[] for _ in range(n)]
+        pos = np.arange(T)[None, :]
+        stop = (ids == self.eos_id) | (pos >= np.asarray(trun)[:, None])
+        end = np.where(stop.any(axis=1), stop.argmax(axis=1), T)
+        new_w, x1, x2 = (np.asarray(v, dtype=np.float64).reshape(n, 1) for v in (new_w, x1, x2))
+        xs = frame_to_pixel(centre, new_w, x1, x2).tolist()
+        ps = np.clip(np.asarray(prob, dtype=np.float64), 0.0, 1.0).tolist()  # exp of a log-softmax: within [0, 1] up to rounding
+        itos, skip = self.itos, {self.pad_id, self.blank_id}
+        return [[{"char": itos[t], "confidence": p, "x": x} for t, p, x in zip(row[:e], pr, xr) if t not in skip]
+                for row, e, pr, xr in zip(ids.tolist(), end.tolist(), ps, xs)]
+
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
-                alpha: float = 0.9) -> List[Dict[str, Any]]:
-        """Same contract as the reference TRBA.predict (__init__.py:290-434)."""
+                alpha: float = 0.9, *, return_chars: bool = False) -> List[Dict[str, Any]]:
+        """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
+        result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
+        decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
+        through transforms.FRAME_STRIDE and the resize; an estimate, not a measured glyph position)."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         if not images_list:
             return []
-        canv = torch.from_numpy(self._canvases(images_list)).to(self.device, non_blocking=True)
-        return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
+        if not return_chars:
+            canv = torch.from_numpy(self._canvases(images_list)).to(self.device, non_blocking=True)
+            return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
+        arrays = [self._load_rgb(im) for im in images_list]
+        canv = torch.from_numpy(np.stack([resize_and_pad(a, self.img_h, self.img_w) for a in arrays])).to(self.device, non_blocking=True)
+        ids, trun, conf, prob, centre, _peak = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha,
+                                                                       char_details=True)
+        src_w = [a.shape[1] for a in arrays]
+        new_w = [resized_size(a.shape[0], a.shape[1], self.img_h, self.img_w)[0] for a in arrays]
+        results = self._results(ids, trun, conf)
+        for r, ch in zip(results, self.chars(ids, trun, prob, centre, new_w, np.zeros(len(arrays)), src_w)):
+            r["chars"] = ch
+        return results

@@ -152,14 +152,15 @@ class TrbaNet:
         return seq, proj
 
     # ------------------------------------------------------------------------------------- decoder
-    def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id):
-        return self.dec.greedy(batch_H, proj_H, max_len, sos_id, eos_id, blank_id)
+    def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, want_alpha=False):
+        return self.dec.greedy(batch_H, proj_H, max_len, sos_id, eos_id, blank_id, want_alpha=want_alpha)
 
-    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None):
-        return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks)
+    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, want_alpha=False):
+        return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks,
+                             want_alpha=want_alpha)
 
-    def beam_finalize(self, ws, B, steps, beam_size, trun_dev):
-        return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev)
+    def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None):
+        return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev, alpha_ws=alpha_ws)
 
 
 def check_decoder_shape(hidden, num_classes):
@@ -238,27 +239,43 @@ class AttnDecoder:
         B, T, H = batch_H.shape
         return _gemm(batch_H.reshape(B * T, H), self.att["wih_ctx_rows"], None)
 
-    def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, ctx_gates=None):
-        """ctx_gates: this call's rows of a ctx_gates() result computed beforehand (used only where the kernel takes them)."""
+    def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, ctx_gates=None, want_alpha=False, alpha_out=None):
+        """ctx_gates: this call's rows of a ctx_gates() result computed beforehand (used only where the kernel takes them).
+        want_alpha: also return the attention weights of every step, [B, steps, T] f32 (alpha_out: a buffer of that shape to write
+        them to); every other output is the same either way."""
         B, T, H = batch_H.shape
         steps = max_len + 1
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         ids = torch.empty((B, steps), dtype=torch.int32, device=self.device)
         blank = -1 if blank_id is None else blank_id
+        al = None
+        if want_alpha:
+            al = alpha_out if alpha_out is not None else torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
+            assert al.shape == (B, steps, T) and al.dtype == torch.float32 and al.is_contiguous() and al.is_cuda
         if self._matrix_core(T):  # 32 crops per workgroup, split-operand products, hoisted context gates
             ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
-            nat.check(nat.lib().msocr_attn_greedy_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
-                                                          ctypes.byref(self._asw), B, T, H, self.V, steps, sos_id, eos_id, blank,
-                                                          logits.data_ptr(), ids.data_ptr(), ops._stream()), "attn_greedy_hoisted")
+            head = (batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), ctypes.byref(self._asw), B, T, H, self.V,
+                    steps, sos_id, eos_id, blank, logits.data_ptr(), ids.data_ptr())
+            if al is None:
+                nat.check(nat.lib().msocr_attn_greedy_hoisted(*head, ops._stream()), "attn_greedy_hoisted")
+            else:
+                nat.check(nat.lib().msocr_attn_greedy_hoisted_alpha(*head, al.data_ptr(), ops._stream()), "attn_greedy_hoisted_alpha")
         else:
-            nat.check(nat.lib().msocr_attn_greedy(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), B, T, H, self.V, steps,
-                                                  sos_id, eos_id, blank, logits.data_ptr(), ids.data_ptr(), ops._stream()), "attn_greedy")
-        return logits, ids
+            head = (batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), B, T, H, self.V, steps, sos_id, eos_id, blank,
+                    logits.data_ptr(), ids.data_ptr())
+            if al is None:
+                nat.check(nat.lib().msocr_attn_greedy(*head, ops._stream()), "attn_greedy")
+            else:
+                nat.check(nat.lib().msocr_attn_greedy_alpha(*head, al.data_ptr(), ops._stream()), "attn_greedy_alpha")
+        return (logits, ids, al) if want_alpha else (logits, ids)
 
-    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None):
+    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None,
+             want_alpha=False, alpha_ws=None):
         """Returns (workspace, fin_step [B] i32, lp) for `beam_finalize`.  ctx_gates as for `greedy`.  Runs all `max_len` steps, or — given
         chunks = (chunk_id [B] i32, chunk_size [nchunks] i32, chunk_state [2*nchunks] i32 zeros), all on the device — only
-        as many as the reference's own loop would (it breaks once every beam of the chunk is finished, model.py:215)."""
+        as many as the reference's own loop would (it breaks once every beam of the chunk is finished, model.py:215).
+        want_alpha: a fourth result, the attention-weight trace [B, steps, beam, T] f32 for `beam_finalize(alpha_ws=...)` (slot-
+        indexed like the logits trace; steps the early exit skips stay unwritten); alpha_ws: a buffer of that shape to use."""
         B, T, H = batch_H.shape
         steps = max_len
         nbytes = nat.lib().msocr_attn_beam_workspace_bytes(B, steps, beam_size, self.V)
@@ -277,6 +294,11 @@ class AttnDecoder:
             lp = self._lp_cache[key]
         if not 1 <= beam_size <= 16 or beam_size * H > 4096:
             raise ValueError(f"beam_size {beam_size} with hidden_size {H}: the decoder kernels take beam_size <= 16 and beam_size x hidden_size <= 4096")
+        aws = None
+        if want_alpha:
+            aws = alpha_ws if alpha_ws is not None else torch.empty((B, steps, beam_size, T), dtype=torch.float32, device=self.device)
+            assert aws.shape == (B, steps, beam_size, T) and aws.dtype == torch.float32 and aws.is_contiguous() and aws.is_cuda
+            assert aws.numel() * 4 == nat.lib().msocr_attn_beam_alpha_bytes(B, steps, beam_size, T)
         hoist = self._matrix_core(T, beam_size)
         if hoist:  # W_ih[:, :H] batch_H_t for every frame, once per call instead of W_ih[:, :H] ctx in every step
             ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
@@ -284,26 +306,40 @@ class AttnDecoder:
         tail = (B, T, H, self.V, steps, beam_size, lp.data_ptr() if lp is not None else None, float(temperature), sos_id, eos_id,
                 -1 if blank_id is None else blank_id, fin.data_ptr(), ws.data_ptr(),
                 chunks[0].data_ptr() if chunks else None, chunks[1].data_ptr() if chunks else None,
-                chunks[2].data_ptr() if chunks else None, ops._stream())
+                chunks[2].data_ptr() if chunks else None)
+        tail += (ops._stream(),) if aws is None else (aws.data_ptr(), ops._stream())
+        L = nat.lib()
         if hoist:  # split-operand products with the split weights, exact-f32 MFMA without them
             asw = ctypes.byref(self._asw) if self._asw is not None else None
-            nat.check(nat.lib().msocr_attn_beam_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
-                                                        asw, *tail), "attn_beam_hoisted")
+            fn = L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha
+            nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), asw, *tail), "attn_beam_hoisted")
         else:
-            nat.check(nat.lib().msocr_attn_beam(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
+            fn = L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha
+            nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
         # SURVEY.md 8d, per decode step: proj_H + batch_H (shared by the beams) + LSTMCell W_ih (ctx part + one-hot rows), W_hh,
         # generator, h2h + per row (h, c state + logits); the launch runs up to `steps` of them (chunk-level early exit)
         V, R = self.V, B * beam_size
         per_step = 4.0 * (2 * B * T * H + 4 * H * (H + V) + 4 * H * H + H * V + H * H + R * (4 * H + V))
         ops._prof_end(e, "attn_beam", (per_step, steps), (B, T, beam_size))
-        return ws, fin, lp
+        return (ws, fin, lp, aws) if want_alpha else (ws, fin, lp)
 
-    def beam_finalize(self, ws, B, steps, beam_size, trun_dev):
+    def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None, alpha_out=None):
+        """alpha_ws (from `beam(want_alpha=True)`): a third result, the best path's attention weights [B, steps, T] f32, zeros for
+        t >= t_run (alpha_out: a buffer of that shape to write them to)."""
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         ids = torch.empty((B, steps), dtype=torch.int32, device=self.device)
-        nat.check(nat.lib().msocr_attn_beam_finalize(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(), logits.data_ptr(),
-                                                     ids.data_ptr(), ops._stream()), "attn_beam_finalize")
-        return logits, ids
+        if alpha_ws is None:
+            nat.check(nat.lib().msocr_attn_beam_finalize(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(), logits.data_ptr(),
+                                                         ids.data_ptr(), ops._stream()), "attn_beam_finalize")
+            return logits, ids
+        T = alpha_ws.shape[-1]
+        assert alpha_ws.shape == (B, steps, beam_size, T) and alpha_ws.dtype == torch.float32 and alpha_ws.is_contiguous()
+        al = alpha_out if alpha_out is not None else torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
+        assert al.shape == (B, steps, T) and al.dtype == torch.float32 and al.is_contiguous() and al.is_cuda
+        nat.check(nat.lib().msocr_attn_beam_finalize_alpha(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(),
+                                                           logits.data_ptr(), ids.data_ptr(), alpha_ws.data_ptr(), T, al.data_ptr(),
+                                                           ops._stream()), "attn_beam_finalize_alpha")
+        return logits, ids, al
 
 
 def trba_cnn_macs(h, w):

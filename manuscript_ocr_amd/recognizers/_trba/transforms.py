@@ -109,6 +109,26 @@ def resize_area(img, dw, dh):
     return np.clip(np.rint(out), 0, 255).astype(np.uint8)
 
 
+def resized_size(h, w, img_h, img_w):
+    """(new_w, new_h) of an h x w crop on an img_h x img_w canvas: ResizeAndPadA's size arithmetic (transforms.py:91-95)."""
+    scale = min(img_h / max(h, 1), img_w / max(w, 1))
+    return max(1, int(round(w * scale))), max(1, int(round(h * scale)))
+
+
+# One encoder frame per FRAME_STRIDE canvas columns: the product of the CNN's horizontal strides (max-pool 2, layer1 2, layer3 2).
+FRAME_STRIDE = 8
+
+
+def frame_to_pixel(centre, new_w, x1, x2):
+    """Attention position in encoder frames (msocr_seq_char_details' `centre`, 0 .. T) -> x in pixels of the image the crop was cut
+    from, for a crop window [x1, x2) whose resized copy of width new_w was pasted at x = 0 of the canvas:
+    x1 + clamp(FRAME_STRIDE * centre, 0, new_w) * (x2 - x1) / new_w.  The clamp keeps frames over the canvas padding (new_w <
+    img_w) inside the window.  Scalars or numpy arrays.  An estimate: the attention centroid is where the decoder looked, not a
+    measured glyph position."""
+    col = np.clip(FRAME_STRIDE * np.asarray(centre, dtype=np.float64), 0.0, np.asarray(new_w, dtype=np.float64))
+    return x1 + col * (np.asarray(x2, dtype=np.float64) - x1) / new_w
+
+
 def resize_and_pad(img, img_h, img_w):
     """Aspect-preserving resize (AREA if any axis shrinks else LINEAR), pasted left / vertically centred on white."""
     if img.ndim == 2:
@@ -116,8 +136,7 @@ def resize_and_pad(img, img_h, img_w):
     elif img.shape[2] == 4:
         img = img[:, :, :3]
     h, w = img.shape[:2]
-    scale = min(img_h / max(h, 1), img_w / max(w, 1))
-    new_w, new_h = max(1, int(round(w * scale))), max(1, int(round(h * scale)))
+    new_w, new_h = resized_size(h, w, img_h, img_w)
     small = resize_area(img, new_w, new_h) if (new_h < h or new_w < w) else resize_linear(img, new_w, new_h)
     canvas = np.full((img_h, img_w, 3), 255, dtype=img.dtype)
     x0 = max(0, min(0, img_w - new_w))

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Per-phase wall-clock of attn_beam_mfma_kernel's step loop (workgroup 0), dev tool for the GPU box:
 #   gpurun -- bash tools/attn_phase_times.sh [B]
-# builds a private copy of the two recogniser translation units with -DMSOCR_ATTN_TIMING and runs one beam decode through it.
+# builds a private copy of the recogniser's decoder translation units with -DMSOCR_ATTN_TIMING and runs one beam decode through it.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=${1:-1024}
 cd $R/manuscript_ocr_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -DMSOCR_ATTN_TIMING -shared \
-  attn_beam_mfma.hip trba_kernels.hip attn_general.hip -o /tmp/libattn_timing.so
+  attn_beam_mfma.hip attn_beam_mfma_alpha.hip trba_kernels.hip attn_general.hip -o /tmp/libattn_timing.so
 cd $R
 python3 - <<PY
 import ctypes, sys, numpy as np, torch

@@ -9,7 +9,7 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/manuscript_ocr_amd/csrc
 NOPK=$(sed -n 's/^NOPK_OBJS = //p' $C/Makefile)
-FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma bilstm_mfma"
+FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma attn_beam_mfma_alpha attn_general bilstm_mfma"
 T=$(mktemp -d)
 trap 'rm -rf $T' EXIT
 units="$*"

@@ -361,6 +361,50 @@ int msocr_reading_order_crops(const float* boxes, const int32_t* nbox, int N, in
                               int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, void* workspace,
                               void* stream);
 
+/* ---- rectified word crops (an extension beyond the reference, off by default: Pipeline.rectify_crops) -----------------------
+ * The canvas of a word is cut ALONG its detected quadrilateral instead of from the quad's axis-aligned window.  All arithmetic is
+ * IEEE f64 in the order written here, without contraction, so the device kernels and the HOST twins give the same bytes.
+ * Canonical corner order: the four cross products of consecutive edges of the polygon as stored ((P[i+1] - P[i]) x (P[i+2] - P[i+1]),
+ * f64) must be non-zero and of one sign, else the quad is unusable.  Negative (counter-clockwise on screen, y pointing down): the
+ * corners are walked backwards (3, 2, 1, 0).  Of the four cyclic rotations the one whose edge P0 -> P1 has the largest x1 - x0
+ * wins, on equality the one whose start corner has the smallest index in the stored order: (tl, tr, br, bl) for a tilt below 45
+ * degrees.  No transcendental is used.
+ * Size: w = max(|P1 - P0|, |P2 - P3|), h = max(|P3 - P0|, |P2 - P1|) (sqrt of the f64 sum of squares), then ResizeAndPadA's
+ * arithmetic: scale = min(img_h / h, img_w / w), new_w = max(1, rint(w * scale)), new_h likewise, both clipped to the canvas,
+ * y0 = max(0, min((img_h - new_h) / 2, img_h - new_h)).
+ * Fallback: an unusable quad, a non-finite corner, or w < 1 or h < 1 takes the corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) of
+ * the word's clamped AABB window instead, so every word that has an AABB crop has a rectified one.
+ * Descriptor = 12 x int32 {page, x0, y0, x1, y1, x2, y2, x3, y3 as f32 bit patterns in canonical order, new_w, new_h, y0}.
+ * Sampling: canvas pixel (cx, cy) with dx = cx < new_w and 0 <= dy = cy - y0 < new_h is the mean of Sx x Sy sub-samples,
+ * Sx = clamp(ceil(w / new_w), 1, 4), Sy likewise from h / new_h (w, h recomputed from the descriptor's corners), j outer, i inner:
+ * u = (dx + (i + 0.5) / Sx) / new_w, v = (dy + (j + 0.5) / Sy) / new_h,
+ * p = (1-u)(1-v) P0 + u(1-v) P1 + u v P2 + (1-u) v P3, the page read at p - 0.5 with 4 taps whose indices are clamped to the page:
+ * (1-fy) ((1-fx) a + fx b) + fy ((1-fx) c + fx d); value = rint(sum / (Sx Sy)) clamped to 0..255.  Every other pixel is 255.
+ * An axis-aligned quad with integer corners and new_w == w, new_h == h reproduces the page window byte for byte.
+ *
+ * msocr_quad_crop_descriptors (DEVICE, one workgroup per page): boxes / nbox as given to msocr_reading_order_crops and its
+ * order_out / keep_out / desc_out / ncrop_out -> qdesc_out [N][max_cand][12], the page's quad descriptors compacted in exactly the
+ * order of desc_out (page field copied from it).  A page with ncrop < 0 is skipped: its rows stay untouched.
+ * msocr_quad_crop_descriptors_host (HOST, all pointers host memory): the same arithmetic for quads_host [M][8] f32 (corners as
+ * stored) and their AABB descriptors desc_host [M][8].  natural != 0: the region at its own size (new_w = max(1, rint(w)), new_h
+ * likewise, y0 = 0; img_h / img_w unused) for a caller that resizes afterwards. */
+int msocr_quad_crop_descriptors(const float* boxes, const int32_t* nbox, int N, int max_cand, int img_h, int img_w,
+                                const int32_t* order, const int32_t* keep, const int32_t* desc, const int32_t* ncrop,
+                                int32_t* qdesc_out, void* stream);
+int msocr_quad_crop_descriptors_host(const float* quads_host, const int32_t* desc_host, int M, int img_h, int img_w, int natural,
+                                     int32_t* qdesc_out_host);
+
+/* pages [N][H][W][3] u8 + M quad descriptors -> canvases [M][img_h][img_w][3] u8, one workgroup per crop.  qdesc_host is the same
+ * array in host memory, used only to refuse invalid descriptors before the launch (MSOCR_E_ARG), or NULL when they were produced
+ * on the device: the kernel checks every descriptor itself and writes a white canvas for an invalid one.  Invalid: page outside
+ * [0, N), a non-finite corner, new_w / new_h outside [1, img_w] / [1, img_h], y0 < 0 or y0 + new_h > img_h.  Corners may lie
+ * anywhere (the taps are clamped to the page).  msocr_quad_crop_host is the HOST twin (all pointers host memory; an invalid
+ * descriptor gives a white canvas). */
+int msocr_quad_crop(const uint8_t* pages, int N, int H, int W, const int32_t* qdesc_dev, const int32_t* qdesc_host, int M,
+                    int img_h, int img_w, uint8_t* canvases, void* stream);
+int msocr_quad_crop_host(const uint8_t* pages_host, int N, int H, int W, const int32_t* qdesc_host, int M, int img_h, int img_w,
+                         uint8_t* canvases_host);
+
 /* ---- image ingest: JPEG -> RGB on the device -------------------------------------------------------------------------
  * Replaces the file decode of read_image (detectors/_east/utils.py:477-497: cv2.imread / PIL = libjpeg-turbo defaults).
  * 8-bit baseline / extended-sequential Huffman JPEG, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart

@@ -105,6 +105,10 @@ _SIGS = {
     "msocr_reading_order_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_reading_order_crops": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_quad_crop_descriptors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_quad_crop_descriptors_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "msocr_quad_crop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "msocr_quad_crop_host": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "msocr_jpeg_parse_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo)]),
     "msocr_jpeg_parse_oriented_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo), ctypes.POINTER(c_i32)]),
     "msocr_jpeg_entropy_decode_host": (c_i32, [c_vp, c_i64, ctypes.POINTER(JpegInfo), c_vp]),

@@ -7,6 +7,13 @@ recognizer.predict(List[np.ndarray]) -> [{"text","confidence"}|(text, conf)|othe
 `pipeline.char_details = True` (this package's extension, native path only): recognised words come back as CharWords with
 per-symbol confidence and x position (detectors/_types.py).
 
+`pipeline.rectify_crops = True` (this package's extension, absent by default): the recogniser's crops are cut ALONG the detected
+quadrilaterals instead of from their axis-aligned windows (useful with EAST(axis_aligned_output=False)).
+The recognised words and their order do not change, only the pixels the recogniser sees.  Native path: the device kernel
+msocr_quad_crop writes the recogniser's canvases directly.  Every other route (foreign plugins, profile=True, native_fast_path =
+False): `_extract_word_image` returns the rectified region at its natural size and the recogniser resizes it, so that route
+resamples twice and its canvases do not equal the device route's; identity holds within a route only.
+
 `process_batch` is broken upstream (it calls a non-existent `self.process`, _pipeline.py:187);
 here it is the per-image `predict`.  `predict_batch` is the MI355X fast path: when detector and
 recogniser are this package's EAST/TRBA it runs the detector once for all pages and the
@@ -86,7 +93,7 @@ class Pipeline:
             for word in block.words:
                 (x0, y0, x1, y1), poly = _word_aabb(word)
                 if (x1 - x0) >= self.min_text_size and (y1 - y0) >= self.min_text_size:
-                    region = self._extract_word_image(image_array, poly)
+                    region = self._extract_word_image(image_array, poly, quad=word.polygon)
                     if region is not None and region.size > 0:
                         words.append(word)
                         crops.append(region)
@@ -303,7 +310,7 @@ class Pipeline:
                 dpool.append(torch.cuda.Stream(priority=hi_prio))
             streams, det_streams = pool[:nsub], dpool[:nsub]
         from . import ops
-        det_handles, ro_handles, det_events = [], [], []
+        det_handles, ro_handles, det_events, qd_handles = [], [], [], {}
         H, W = arrays[0].shape[:2]
         for (lo, hi), st in zip(bounds, det_streams):
             if st is not main:
@@ -318,13 +325,15 @@ class Pipeline:
                 if recognize_text and dh[5] is not None and getattr(self, "device_order", True):
                     ro = ops.reading_order_crops(dh[5], dh[6], (H, W), self.min_text_size, self.recognizer.img_h, self.recognizer.img_w,
                                                  page_base=lo)
+                    if getattr(self, "rectify_crops", False):  # quad descriptors of the same words, right behind, same order
+                        qd_handles[len(ro_handles)] = ops.quad_crop_descriptors(dh[5], dh[6], ro, self.recognizer.img_h, self.recognizer.img_w)
                 ro_handles.append(ro)
                 ev = torch.cuda.Event()
                 ev.record(st)  # detector outputs of this group complete
                 det_events.append(ev)
         return {"arrays": arrays, "pages_dev": pages_dev, "bounds": bounds, "streams": streams, "det_streams": det_streams, "main": main,
                 "det_handles": det_handles, "ro_handles": ro_handles, "det_events": det_events, "recognize_text": recognize_text, "profile": profile,
-                "ingest_pending": ingest_pending,
+                "ingest_pending": ingest_pending, "qd_handles": qd_handles, "rectify": bool(getattr(self, "rectify_crops", False)),
                 "resubmit": (lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))}
 
     def advance_batch(self, h):
@@ -353,12 +362,16 @@ class Pipeline:
         # `pipeline.char_details = True`: the recogniser also returns per-symbol confidence and position, and collect_batch hands the
         # recognised words out as CharWords (detectors/_types.py).  Off by default; this package's recogniser only.
         details = bool(getattr(self, "char_details", False))
+        # `pipeline.rectify_crops = True`: canvases cut along the words' quadrilaterals (ops.quad_crop) instead of their AABB windows
+        rectify = bool(h.get("rectify"))
         N = len(arrays)
         H, W = arrays[0].shape[:2]
         pages, groups = [None] * N, []
         with _gc_paused():
-            for (lo, hi), st, dst, dh, ro, dev_ev in zip(bounds, streams, h["det_streams"], h["det_handles"], h["ro_handles"], h["det_events"]):
-                if ro is not None:
+            for gi, ((lo, hi), st, dst, dh, ro, dev_ev) in enumerate(zip(bounds, streams, h["det_streams"], h["det_handles"],
+                                                                         h["ro_handles"], h["det_events"])):
+                qd = h["qd_handles"].get(gi)
+                if ro is not None and (qd is not None or not rectify):
                     # device path: wait for the group's crop counts only (4 bytes per page), enqueue crops + recogniser
                     with torch.cuda.stream(dst):
                         t0 = time.perf_counter()
@@ -385,15 +398,22 @@ class Pipeline:
                                 ro[2].record_stream(st)
                                 desc_dev = torch.cat([ro[2][pi, :c] for pi, c in enumerate(nc_h.tolist()) if c])
                                 grp["desc"] = desc_dev if details else None
-                                if use_graph:  # crop + encode + decode as one hipGraph replay (declines when details are asked for)
+                                if rectify:
+                                    qd.record_stream(st)
+                                    qdesc_dev = torch.cat([qd[pi, :c] for pi, c in enumerate(nc_h.tolist()) if c])
+                                    grp["qdesc"] = qdesc_dev if details else None
+                                if use_graph:  # crop + encode + decode as one hipGraph replay (declines when details or rectified crops are asked for)
                                     grp["handle"] = rec.recognize_start_graph(pages_dev, desc_dev, spans, upload_stream=dst,
-                                                                              char_details=details)
+                                                                              char_details=details, rectified=rectify)
                                 if grp["handle"] is None:
                                     if prepared is None:  # graph path declined (first call of a bucket, ...): plain launches
                                         with torch.cuda.stream(dst):
                                             prepared = rec.prepare_chunks(off, spans)
                                         st.wait_stream(dst)
-                                    canv = ops.crop_resize_pad(pages_dev, None, rec.img_h, rec.img_w, desc_dev=desc_dev)
+                                    if rectify:
+                                        canv = ops.quad_crop(pages_dev, None, rec.img_h, rec.img_w, qdesc_dev=qdesc_dev)
+                                    else:
+                                        canv = ops.crop_resize_pad(pages_dev, None, rec.img_h, rec.img_w, desc_dev=desc_dev)
                                     grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
                         tm["crop+enqueue"] += time.perf_counter() - t0
                         groups.append(grp)
@@ -432,12 +452,18 @@ class Pipeline:
                             if len(desc):
                                 spans = [tuple(s) for s in grp["spans"] if s[1] > 0]
                                 up = dst if getattr(self, "upload_on_det_stream", True) else st
+                                # rectified: the host twin's descriptors from the kept words' polygons, in the order of desc
+                                qdesc = ops.quad_descriptors([w.polygon for w in grp["words"]], desc, rec.img_h, rec.img_w) if rectify else None
                                 with torch.cuda.stream(up):  # the two small blocking uploads ride the high-priority stream
-                                    desc_dev = torch.from_numpy(desc.astype("int32", copy=False)).to(det.device)
+                                    desc_dev = torch.from_numpy((qdesc if rectify else desc).astype("int32", copy=False)).to(det.device)
                                     prepared = rec.prepare_chunks(len(desc), spans)
                                 if st is not up:
                                     st.wait_stream(up)
-                                canv = ops.crop_resize_pad(pages_dev, desc, rec.img_h, rec.img_w, desc_dev=desc_dev)
+                                if rectify:
+                                    canv = ops.quad_crop(pages_dev, qdesc, rec.img_h, rec.img_w, qdesc_dev=desc_dev)
+                                    grp["qdesc"] = qdesc if details else None
+                                else:
+                                    canv = ops.crop_resize_pad(pages_dev, desc, rec.img_h, rec.img_w, desc_dev=desc_dev)
                                 grp["desc"] = desc if details else None
                                 grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
                         tm["crop+enqueue"] += time.perf_counter() - t0
@@ -493,15 +519,21 @@ class Pipeline:
                         details = bool(grp["handle"].get("char_details"))
                         fin = rec.recognize_finish(grp["handle"], spans=[tuple(s) for s in grp["spans"] if s[1] > 0])
                         ids, trun, conf = fin[:3]
+                        qdesc = None
                         if details:
                             desc = grp["desc"] if isinstance(grp["desc"], np.ndarray) else grp["desc"].cpu().numpy()
+                            if grp.get("qdesc") is not None:
+                                qdesc = grp["qdesc"] if isinstance(grp["qdesc"], np.ndarray) else grp["qdesc"].cpu().numpy()
                         tm["recognize_wait"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
                     texts = rec.texts(ids, trun)
                     for word, text, c in zip(grp["words"], texts, conf.tolist()):
                         word.text = text
                         word.recognition_confidence = c
-                    if details:
+                    if details and qdesc is not None:  # rectified: x through the quad's patch instead of the AABB window
+                        self._attach_chars(grp["words"], rec.chars(ids, trun, fin[3], fin[4], qdesc[:, 9], None, None, qdesc=qdesc),
+                                           pages[grp["lohi"][0]:grp["lohi"][1]])
+                    elif details:
                         self._attach_chars(grp["words"], rec.chars(ids, trun, fin[3], fin[4], desc[:, 5], desc[:, 1], desc[:, 3]),
                                            pages[grp["lohi"][0]:grp["lohi"][1]])
                     tm["assign"] += time.perf_counter() - t0
@@ -548,7 +580,11 @@ class Pipeline:
                 lines.append(" ".join(texts))
         return "\n".join(lines)
 
-    def _extract_word_image(self, image: np.ndarray, polygon: np.ndarray) -> Optional[np.ndarray]:
+    def _extract_word_image(self, image: np.ndarray, polygon: np.ndarray, quad=None) -> Optional[np.ndarray]:
+        """The word's clamped AABB window of the page (reference _pipeline.py:204-221).  With `rectify_crops` set and the word's
+        float corners given as `quad`: the region cut along the quadrilateral at its natural size, (rint(h), rint(w), 3), through
+        the host twin msocr_quad_crop_host (same sampling as the device kernel; the recogniser's own resize follows, so these
+        pixels are resampled twice and differ from the device route's canvases).  A word without a window has no region either way."""
         try:
             x_min, y_min = np.min(polygon, axis=0)
             x_max, y_max = np.max(polygon, axis=0)
@@ -556,6 +592,14 @@ class Pipeline:
             x1, y1 = max(0, int(x_min)), max(0, int(y_min))
             x2, y2 = min(w, int(x_max)), min(h, int(y_max))
             region = image[y1:y2, x1:x2]  # a view of the page, never mutated
-            return region if region.size > 0 else None
+            if region.size == 0:
+                return None
         except Exception:
             return None
+        if quad is not None and getattr(self, "rectify_crops", False) and image.ndim == 3 and image.shape[2] == 3:
+            from . import ops  # outside the try: a missing native library is an error, not a word without text
+            desc, _ = ops.crop_descriptors([(x_min, y_min, x_max, y_max)], [0], (h, w), 1, 1)
+            if len(desc):  # always: the window above is not empty
+                qd = ops.quad_descriptors([quad], desc, natural=True)
+                return ops.quad_crop_host(image[None], qd, int(qd[0, 10]), int(qd[0, 9]))[0]
+        return region

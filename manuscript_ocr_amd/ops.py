@@ -606,3 +606,73 @@ def crop_resize_pad(pages_u8, desc_host, img_h, img_w, desc_dev=None):
     nat.check(nat.lib().msocr_crop_resize_pad(pages_u8.data_ptr(), N, H, W, desc_dev.data_ptr(), hp, M, img_h, img_w,
                                               out.data_ptr(), _stream()), "crop_resize_pad")
     return out
+
+
+# ------------------------------------------------------------------------------------------- rectified crops
+def quad_crop_descriptors(boxes, nbox, ro, img_h, img_w, out=None):
+    """Device form of the quad descriptors (msocr_quad_crop_descriptors): boxes [N,max_cand,9] f32 + counts [N] as given to
+    `reading_order_crops` and its result `ro` = (order, keep, desc, ncrop) -> qdesc [N,max_cand,12] i32 on the device, per page the
+    quad descriptors of the kept words, compacted in exactly the order of `desc`.  Rows of a page with ncrop < 0 (host route) and
+    rows past a page's ncrop are not written (zeros, or what `out` held)."""
+    order, keep, desc, ncrop = ro
+    _need_cuda(boxes, nbox, order, keep, desc, ncrop)
+    N, max_cand, _ = boxes.shape
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and desc.shape == (N, max_cand, 8) and desc.is_contiguous()
+    qdesc = out if out is not None else torch.zeros((N, max_cand, 12), dtype=torch.int32, device=boxes.device)
+    assert qdesc.shape == (N, max_cand, 12) and qdesc.dtype == torch.int32 and qdesc.is_contiguous() and qdesc.is_cuda
+    nat.check(nat.lib().msocr_quad_crop_descriptors(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, int(img_h), int(img_w),
+                                                    order.data_ptr(), keep.data_ptr(), desc.data_ptr(), ncrop.data_ptr(),
+                                                    qdesc.data_ptr(), _stream()), "quad_crop_descriptors")
+    return qdesc
+
+
+def quad_descriptors(polygons, desc, img_h=0, img_w=0, natural=False):
+    """Host form through the host twin (msocr_quad_crop_descriptors_host): polygons [M,4,2] (corners as the detector stored them, taken
+    as f32) + the words' AABB descriptors `desc` int32 [M,8] (`crop_descriptors`) -> quad descriptors int32 [M,12] (numpy).
+    natural=True: the regions at their own size (new_w = rint(w), new_h = rint(h), y0 = 0) instead of the fit to img_h x img_w."""
+    import numpy as np
+    desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 8)
+    M = len(desc)
+    quads = np.ascontiguousarray(np.asarray(polygons, dtype=np.float32).reshape(M, 8))
+    out = np.zeros((M, 12), dtype=np.int32)
+    nat.check(nat.lib().msocr_quad_crop_descriptors_host(quads.ctypes.data, desc.ctypes.data, M, int(img_h), int(img_w), int(bool(natural)),
+                                                         out.ctypes.data), "quad_crop_descriptors_host")
+    return out
+
+
+def quad_crop_host(pages_u8, qdesc, img_h, img_w):
+    """The CPU twin of `quad_crop` (msocr_quad_crop_host): pages [N,H,W,3] u8 numpy + quad descriptors int32 [M,12] -> canvases
+    [M,img_h,img_w,3] u8 numpy, the same bytes as the kernel's."""
+    import numpy as np
+    pages_u8 = np.ascontiguousarray(pages_u8, dtype=np.uint8)
+    qdesc = np.ascontiguousarray(qdesc, dtype=np.int32).reshape(-1, 12)
+    N, H, W, C = pages_u8.shape
+    assert C == 3
+    out = np.empty((len(qdesc), img_h, img_w, 3), dtype=np.uint8)
+    nat.check(nat.lib().msocr_quad_crop_host(pages_u8.ctypes.data, N, H, W, qdesc.ctypes.data, len(qdesc), int(img_h), int(img_w),
+                                             out.ctypes.data), "quad_crop_host")
+    return out
+
+
+def quad_crop(pages_u8, qdesc_host, img_h, img_w, qdesc_dev=None):
+    """pages [N,H,W,3] u8 device, qdesc_host int32 [M,12] (numpy) -> canvases [M,img_h,img_w,3] u8 device, cut along the words'
+    quadrilaterals (msocr_quad_crop).  Mirrors `crop_resize_pad`: qdesc_dev = the same descriptors already on the device;
+    qdesc_host may be None when they were produced there (quad_crop_descriptors): the kernel then validates every descriptor itself."""
+    _need_cuda(pages_u8, qdesc_dev)
+    N, H, W, C = pages_u8.shape
+    assert C == 3 and pages_u8.dtype == torch.uint8 and pages_u8.is_contiguous()
+    hp = None
+    if qdesc_host is not None:
+        qdesc_host = qdesc_host.astype("int32", copy=False)
+        hp = qdesc_host.ctypes.data
+    M = len(qdesc_host) if qdesc_host is not None else int(qdesc_dev.shape[0])
+    if qdesc_dev is None:
+        qdesc_dev = torch.from_numpy(qdesc_host).to(pages_u8.device)
+    else:
+        assert qdesc_dev.dtype == torch.int32 and qdesc_dev.is_contiguous() and qdesc_dev.shape == (M, 12)
+        qdesc_dev.record_stream(torch.cuda.current_stream())
+    out = torch.empty((M, img_h, img_w, 3), dtype=torch.uint8, device=pages_u8.device)
+    nat.check(nat.lib().msocr_quad_crop(pages_u8.data_ptr(), N, H, W, qdesc_dev.data_ptr(), hp, M, img_h, img_w, out.data_ptr(), _stream()),
+              "quad_crop")
+    return out
+

@@ -21,7 +21,7 @@ import torch
 from PIL import Image
 
 from .net import TrbaNet
-from .transforms import decode_tokens, frame_to_pixel, load_charset, resize_and_pad, resized_size
+from .transforms import decode_tokens, frame_to_pixel, frame_to_quad_x, load_charset, resize_and_pad, resized_size
 
 
 class _GraphLease:
@@ -239,19 +239,20 @@ class TRBA:
         return {"parts": parts, "N": N, "mode": mode, "beam": beam_size, "bounds": bounds, "char_details": bool(char_details)}
 
     def recognize_start_graph(self, pages_dev: torch.Tensor, desc_dev: torch.Tensor, spans, batch_size=32, beam_size=8,
-                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False):
+                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False):
         """`recognize_start` for crops that are still descriptors on the device (ops.reading_order_crops), as ONE hipGraph replay:
         crop + ResizeAndPadA, SE-ResNet31, BiLSTMs and the beam decode of up to `device_batch` rows are captured once per
         (page tensor, row bucket) and replayed (BASELINE configs[3]: "hipGraph-captured").  The row count is rounded up to a
         multiple of 32; the padding rows repeat crop 0 and form a reference chunk of their own, so they can neither change a real
         row's result nor delay a real chunk's early exit.  Falls back to the eager path (returns None) for empty or oversized
         batches, while kernels are being profiled, and for the first call of a bucket (lazy one-time kernel attributes must not
-        fall into a capture), and whenever char_details is asked for (that path is not captured).  Results are bit-identical to the
-        eager path (tests/test_gpu_pipeline.py)."""
+        fall into a capture), and whenever char_details or rectified crops (Pipeline.rectify_crops: the captured graph holds the AABB
+        crop kernel, not msocr_quad_crop) are asked for (those paths are not captured).  Results are bit-identical to the eager path
+        (tests/test_gpu_pipeline.py)."""
         from ... import ops
         M = int(desc_dev.shape[0])
         Mcap = (M + 31) // 32 * 32
-        if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details:
+        if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details or rectified:
             return None
         nch_cap = Mcap // batch_size + len(spans) + 2  # chunks of the real rows (<= rows/batch_size + one per page) + the padding chunk
         # one pool per launch stream: the groups of a batch are in flight together, each replays its own instances
@@ -426,10 +427,11 @@ class TRBA:
         return [{"text": decode_tokens(ids[j, : int(trun[j])], self.itos, self.pad_id, self.eos_id, self.blank_id),
                  "confidence": float(conf[j])} for j in range(len(ids))]
 
-    def chars(self, ids, trun, prob, centre, new_w, x1, x2) -> List[List[Dict[str, Any]]]:
+    def chars(self, ids, trun, prob, centre, new_w, x1, x2, qdesc=None) -> List[List[Dict[str, Any]]]:
         """Per row, one {"char", "confidence", "x"} per token that `texts` / decode_tokens keep (t < t_run, up to the first EOS, PAD
         and BLANK skipped), so "".join(c["char"]) is the row's text.  x = frame_to_pixel(centre, new_w, x1, x2): new_w [N] the resized
-        widths ResizeAndPadA pasted at x = 0, [x1, x2) the rows' windows in the image the positions are wanted in."""
+        widths ResizeAndPadA pasted at x = 0, [x1, x2) the rows' windows in the image the positions are wanted in.  qdesc [N,12]
+        (rows cut along quadrilaterals, ops.quad_crop): x = frame_to_quad_x(centre, qdesc) instead, x1 / x2 unused."""
         ids = np.asarray(ids)
         n, T = (ids.shape[0], ids.shape[1]) if ids.ndim == 2 else (len(ids), 0)
         if not n or T == 0:
@@ -437,8 +439,11 @@ class TRBA:
         pos = np.arange(T)[None, :]
         stop = (ids == self.eos_id) | (pos >= np.asarray(trun)[:, None])
         end = np.where(stop.any(axis=1), stop.argmax(axis=1), T)
-        new_w, x1, x2 = (np.asarray(v, dtype=np.float64).reshape(n, 1) for v in (new_w, x1, x2))
-        xs = frame_to_pixel(centre, new_w, x1, x2).tolist()
+        if qdesc is not None:
+            xs = frame_to_quad_x(centre, qdesc).tolist()
+        else:
+            new_w, x1, x2 = (np.asarray(v, dtype=np.float64).reshape(n, 1) for v in (new_w, x1, x2))
+            xs = frame_to_pixel(centre, new_w, x1, x2).tolist()
         ps = np.clip(np.asarray(prob, dtype=np.float64), 0.0, 1.0).tolist()  # exp of a log-softmax: within [0, 1] up to rounding
         itos, skip = self.itos, {self.pad_id, self.blank_id}
         return [[{"char": itos[t], "confidence": p, "x": x} for t, p, x in zip(row[:e], pr, xr) if t not in skip]

@@ -129,6 +129,18 @@ def frame_to_pixel(centre, new_w, x1, x2):
     return x1 + col * (np.asarray(x2, dtype=np.float64) - x1) / new_w
 
 
+def frame_to_quad_x(centre, qdesc):
+    """The same for rows cut along quadrilaterals (msocr_quad_crop; qdesc int32 [N,12] = page, 8 corner coordinates as f32 bits in
+    (tl, tr, br, bl) order, new_w, new_h, y0): the x component of the quad's bilinear patch at u = clamp(FRAME_STRIDE * centre, 0,
+    new_w) / new_w, v = 0.5, i.e. on the word's centre line.  centre [N,steps]."""
+    q = np.ascontiguousarray(qdesc, dtype=np.int32)
+    c = np.ascontiguousarray(q[:, 1:9]).view(np.float32).astype(np.float64)
+    new_w = q[:, 9:10].astype(np.float64)
+    u = np.clip(FRAME_STRIDE * np.asarray(centre, dtype=np.float64), 0.0, new_w) / new_w
+    x0, x1, x2, x3 = (c[:, k:k + 1] for k in (0, 2, 4, 6))
+    return (1 - u) * 0.5 * x0 + u * 0.5 * x1 + u * 0.5 * x2 + (1 - u) * 0.5 * x3
+
+
 def resize_and_pad(img, img_h, img_w):
     """Aspect-preserving resize (AREA if any axis shrinks else LINEAR), pasted left / vertically centred on white."""
     if img.ndim == 2:

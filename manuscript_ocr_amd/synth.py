@@ -77,6 +77,55 @@ def synth_maps(rects, page_hw, map_hw, seed, noise=0.05):
     return score, geo
 
 
+def synth_tilted_quads(rects, seed, max_deg=10.0):
+    """Word rectangles (x0, y0, x1, y1) -> quads [n,4,2] (tl, tr, br, bl), each turned about its centre by U(-max_deg, max_deg)."""
+    rng = np.random.default_rng(seed + 15485863)
+    r = np.asarray(rects, dtype=np.float64).reshape(-1, 4)
+    q = np.stack([r[:, [0, 1]], r[:, [2, 1]], r[:, [2, 3]], r[:, [0, 3]]], axis=1)
+    t = np.deg2rad(rng.uniform(-max_deg, max_deg, size=len(r)))
+    c = q.mean(axis=1, keepdims=True)
+    rot = np.stack([np.stack([np.cos(t), -np.sin(t)], axis=1), np.stack([np.sin(t), np.cos(t)], axis=1)], axis=1)  # [n,2,2]
+    return np.einsum("nij,nkj->nki", rot, q - c) + c
+
+
+def synth_quad_maps(quads, page_hw, map_hw, seed, noise=0.05):
+    """`synth_maps` for tilted words: quads [n,4,2] in page pixels, (tl, tr, br, bl).  Score ~0.9 inside the quad shrunk by 0.3 of
+    its shorter side along both of its own axes, geometry = offsets from the pixel to that shrunk quad's four corners, valid on the
+    text region and a 2-px ring around it; background as in `synth_maps`."""
+    rng = np.random.default_rng(seed + 104729)
+    mh, mw = map_hw
+    sc = np.array([mw / page_hw[1], mh / page_hw[0]])
+    score = (0.2 * rng.random((mh, mw))).astype(np.float32)
+    geo = rng.normal(0, 1, size=(mh, mw, 8)).astype(np.float32)
+    yy, xx = np.mgrid[0:mh, 0:mw]
+
+    def inset(p, s):  # the quad moved in by s along its own two axes
+        ex, ey = p[1] - p[0], p[3] - p[0]
+        ex, ey = ex / np.linalg.norm(ex), ey / np.linalg.norm(ey)
+        return np.stack([p[0] + s * (ex + ey), p[1] + s * (ey - ex), p[2] - s * (ex + ey), p[3] + s * (ex - ey)])
+
+    def inside(p):  # map pixels inside the convex clockwise quad p
+        m = np.ones((mh, mw), dtype=bool)
+        for k in range(4):
+            a, b = p[k], p[(k + 1) % 4]
+            m &= (b[0] - a[0]) * (yy - a[1]) - (b[1] - a[1]) * (xx - a[0]) >= 0
+        return m
+
+    for q in np.asarray(quads, dtype=np.float64).reshape(-1, 4, 2):
+        p = q * sc
+        s = 0.3 * min(np.linalg.norm(p[1] - p[0]), np.linalg.norm(p[3] - p[0]))
+        shrunk = inset(p, s)
+        text = inside(shrunk)
+        if not text.any():
+            continue
+        gyy, gxx = np.nonzero(inside(inset(p, s - 2.0)))
+        for i, (vx, vy) in enumerate(shrunk):
+            geo[gyy, gxx, 2 * i] = (vx - gxx + rng.normal(0, noise, gyy.shape)).astype(np.float32)
+            geo[gyy, gxx, 2 * i + 1] = (vy - gyy + rng.normal(0, noise, gyy.shape)).astype(np.float32)
+        score[text] = (0.9 + 0.05 * rng.random(int(text.sum()))).astype(np.float32)
+    return score, geo
+
+
 def synth_crops(seed, n, h=32, w=100):
     """n u8 crops h x w x 3: parchment with 3-9 dark strokes."""
     rng = np.random.default_rng(seed)

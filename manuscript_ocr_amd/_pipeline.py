@@ -22,11 +22,15 @@ recogniser once for all crops of all pages (results identical to per-page predic
 import contextlib
 import gc
 import time
-from typing import List, Optional, Union
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, List, Optional, Union
 
 import numpy as np
+import torch
 from PIL import Image
 
+from . import _native as nat
+from . import ingest, ops
 from .detectors import EAST, read_image, sort_boxes_reading_order_with_resolutions, visualize_page
 from .recognizers import TRBA
 
@@ -48,7 +52,6 @@ def _gc_paused():
 def _reading_order(aabbs_i32):
     """Indices of the words in reading order: sort_boxes_reading_order_with_resolutions + the reference's "first word with an
     equal box" re-match (_pipeline.py:113-121), evaluated by the host helper msocr_reading_order_host (same arithmetic)."""
-    from . import _native as nat
     boxes = np.ascontiguousarray(aabbs_i32, dtype=np.int32)
     order = np.empty(len(boxes), dtype=np.int32)
     nat.check(nat.lib().msocr_reading_order_host(boxes.ctypes.data, len(boxes), 0.6, float("inf"), order.ctypes.data), "reading_order_host")
@@ -62,11 +65,66 @@ def _word_aabb(word):
     return (x_min, y_min, x_max, y_max), poly
 
 
+@dataclass(slots=True)
+class _Group:
+    """One group of consecutive pages of a batch, with the same fields on both routes; what a route does not produce stays None."""
+    lo: int
+    hi: int
+    stream: Any                      # crops + recogniser
+    det_stream: Any                  # detector, reading order, the small uploads
+    det: Any                         # the detector's Detection
+    det_event: Any                   # the detector outputs (and descriptors) of this group are complete
+    ro: Any = None                   # ops.ReadingOrder of the group's pages (device_order)
+    qd: Any = None                   # [pages,max_cand,12] device quad descriptors behind it (rectify_crops)
+    device_ordered: bool = False     # advance_batch took the device route: Page / Word assembly is collect_batch's
+    words: Optional[list] = None     # the Words that got a crop, in crop order
+    spans: List[List[int]] = field(default_factory=list)  # per page [first crop, crops]
+    handle: Any = None               # the recogniser's handle; None = no crops
+    desc_host: Any = None            # crop descriptors int32 [M,8]: numpy on the host route,
+    desc_dev: Any = None             # ... a device tensor on the device route (kept only for char_details)
+    qdesc_host: Any = None           # quad descriptors int32 [M,12] (rectify_crops), likewise
+    qdesc_dev: Any = None
+
+
+@dataclass(slots=True)
+class _Batch:
+    """Handle of submit_batch -> advance_batch -> collect_batch."""
+    arrays: list                     # per page: the host pixels, or a zero-stride placeholder of the right shape
+    pages_dev: Any                   # [N,H,W,3] u8 on the device
+    main: Any                        # the caller's stream
+    groups: List[_Group]
+    recognize_text: bool
+    profile: bool
+    rectify: bool                    # rectify_crops as it was at submit
+    ingest_pending: Any              # the device JPEG stages' deferred verdict, read in advance_batch
+    resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
+    pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
+    tm: Optional[Dict[str, float]] = None  # host seconds per stage -> Pipeline.last_profile
+
+    def replace_with(self, other):
+        """Become `other` (the corrupt-JPEG resubmission) while staying the object the caller holds."""
+        for name in self.__slots__:
+            setattr(self, name, getattr(other, name))
+
+
 class Pipeline:
     def __init__(self, detector: Optional[EAST] = None, recognizer: Optional[TRBA] = None, min_text_size: int = 5):
         self.detector = detector if detector is not None else EAST()
         self.recognizer = recognizer if recognizer is not None else TRBA()
         self.min_text_size = min_text_size
+        # Switches: plain attributes, set after construction (the constructor keeps the reference's signature).  DESIGN.md section 7c.
+        self.native_fast_path = True       # predict() of this package's plugins goes through predict_batch; False = generic route (test hook)
+        self.device_ingest = True          # JPEG files are decoded on the device (ingest.py); False = read_image on the host (test hook)
+        self.device_entropy = None         # Huffman stage: None = ingest's policy, True / False force the device stages / host pool (tests, bench.py)
+        self.device_order = True           # reading order + crop descriptors on the device; False = on the host (test hook)
+        self.rectify_crops = False         # crops cut along the detected quadrilaterals (user extension, see the module docstring)
+        self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
+        self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
+        self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
+        self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
+        self.upload_on_det_stream = True   # host route: the small blocking uploads ride the detector stream (bench.py A/B)
+        self._stream_sets, self._det_stream_sets, self._set_idx = [], [], 0  # submit_batch's streams, per set one per group
+        self._copy_stream = None           # collect_batch's read-back stream
 
     # ------------------------------------------------------------------------------------- helpers
     @staticmethod
@@ -115,7 +173,7 @@ class Pipeline:
     def predict(self, image: Union[str, np.ndarray, Image.Image], recognize_text: bool = True, vis: bool = False,
                 profile: bool = False):
         if (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA) and recognize_text and not profile
-                and getattr(self, "native_fast_path", True)):
+                and self.native_fast_path):
             # both plugins are this package's: same result through the device path (crops cut, resized and padded on the
             # device from the uploaded page, one recogniser pass) — tests/test_gpu_pipeline.py pins batch == per-page
             page = self.predict_batch([image])[0]  # a JPEG path is decoded on the device (ingest.py), arrays are uploaded
@@ -190,8 +248,7 @@ class Pipeline:
         filters, reading order, crop descriptors) overlap the device work of the others.
         `pages_dev`: optional [N,H,W,3] u8 device tensor already holding `images` (benchmarks: inputs resident in HBM).
         = collect_batch(submit_batch(...)); call the two halves yourself to overlap consecutive batches."""
-        native = isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)
-        if not native:
+        if not (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)):
             return [self.predict(im, recognize_text=recognize_text, profile=profile) for im in images]
         if pages_dev is None and len(images) > 1:
             shapes = [self._shape_of(im) for im in images]
@@ -203,7 +260,6 @@ class Pipeline:
                 def maps_of(idx):  # injected maps (tests / benchmarks) follow their pages
                     if _maps_override is None:
                         return None
-                    import torch
                     sel = torch.tensor(idx, device=_maps_override[0].device)
                     return (_maps_override[0].index_select(0, sel), _maps_override[1].index_select(0, sel))
                 handles = []
@@ -238,52 +294,42 @@ class Pipeline:
         batch i+1 can be enqueued before `collect_batch` of batch i and fills the device while batch i drains."""
         if not (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)):
             raise TypeError("submit_batch/collect_batch need this package's EAST and TRBA plugins")
-        import torch
-
         det = self.detector
         # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
-        arrays, decoded = [], []
         dec, ingest_pending = [None] * len(images), None
         # Which Huffman stage: ingest's policy (the per-interval kernel for short restart intervals, the self-synchronising stage
         # for long ones and for files without restart markers; `pipeline.device_entropy = True / False` forces the device stages /
         # the host pool).
         # From files, same box: device stage 79.5-80.1, host pool 78.2-79.2 pages/s against 83.0 resident (DESIGN.md section 7).
         if _device_entropy is None:
-            _device_entropy = getattr(self, "device_entropy", None)
+            _device_entropy = self.device_entropy
         ing = torch.cuda.current_stream()
         with torch.cuda.stream(ing):
-            if pages_dev is None and getattr(self, "device_ingest", True):
-                from . import ingest
+            if pages_dev is None and self.device_ingest:
                 # the device stages' verdict on corrupt streams (and the pages the self-synchronising stage declined) is read in
                 # advance_batch (ingest.check_pending), not here
                 dec, ingest_pending = ingest.read_images_device(list(images), det.device, device_entropy=_device_entropy, defer_status=True)
-            for im, t in zip(images, dec):
-                if t is not None:
-                    arrays.append(np.broadcast_to(np.uint8(0), tuple(t.shape)))
-                else:
-                    arrays.append(read_image(im))
-                decoded.append(t)
+            arrays = [np.broadcast_to(np.uint8(0), tuple(t.shape)) if t is not None else read_image(im) for im, t in zip(images, dec)]
             if len({a.shape for a in arrays}) != 1:
                 raise ValueError("predict_batch needs equally sized pages")
             N = len(arrays)
             if pages_dev is None:
-                if all(t is not None for t in decoded):
-                    pages_dev = torch.stack(decoded)
-                elif not any(t is not None for t in decoded):
+                if not any(t is not None for t in dec):
                     pages_dev = torch.from_numpy(np.ascontiguousarray(np.stack(arrays))).to(det.device)
                 else:
                     pages_dev = torch.stack([t if t is not None else torch.from_numpy(np.ascontiguousarray(a)).to(det.device)
-                                             for t, a in zip(decoded, arrays)])
+                                             for t, a in zip(dec, arrays)])
         # groups per batch.  Round 1 needed 8 groups of 2 pages to hide its host stages behind other groups' device work; with the
         # reading order on the device and Page assembly off the enqueue path, larger launch sequences win (bigger GEMM M, fewer
         # launches): 16 pages measured 44.0 / 45.4 / 45.7 pages/s at 8 / 4 / 2 groups with 4 hardware queues and 36.3 / 46.8 / 48.1
         # with 8 (DESIGN.md section 7); one group ties two at lower memory, two keeps a second detector sequence in flight
         nsub = sub_batches or (2 if N >= 8 else 1)
         nsub = max(1, min(nsub, N))
+        H, W = arrays[0].shape[:2]
         bounds = [(N * k // nsub, N * (k + 1) // nsub) for k in range(nsub)]
         main = torch.cuda.current_stream()
-        if getattr(self, "serialize_streams", False):  # profiling aid: same launches, no cross-stream kernel overlap
+        if self.serialize_streams:  # profiling aid: same launches, no cross-stream kernel overlap
             streams = det_streams = [main] * nsub
         else:
             # Two stream sets alternate between consecutive batches.  Per group: a HIGH-priority stream for the detector and a
@@ -291,216 +337,190 @@ class Pipeline:
             # before it can enqueue the long recogniser tail: with equal priorities the detector kernels of batch i+1 share the
             # chip fairly with the recogniser of batch i and finish together with it, so the next recogniser work is enqueued
             # only when the device has already drained (measured: 5 % idle); at high priority they overtake it.
-            nsets = max(1, int(getattr(self, "stream_sets", 2)))  # batches that may be in flight at once
+            nsets = max(1, int(self.stream_sets))  # batches that may be in flight at once
             # Every stream keeps its own allocator pool (stream-ordered reuse without waiting for the device), so reserved memory
             # grows with the number of streams in flight x the per-page activation footprint: measured 96 GB at 16 pages x
             # 1536 x 2048 with two stream sets = 1.9 KB per page pixel.  When two sets would not fit comfortably (configs[4]:
             # 16 pages x 3072 x 4096 -> 380 GB) consecutive batches share ONE set of streams: half the memory, still
             # stream-ordered, a little less overlap between batches — instead of an allocator that thrashes at the 288 GB limit.
-            H_, W_ = arrays[0].shape[:2]
-            if nsets > 1 and 1900.0 * N * H_ * W_ > 0.6 * torch.cuda.get_device_properties(pages_dev.device).total_memory:
+            if nsets > 1 and 1900.0 * N * H * W > 0.6 * torch.cuda.get_device_properties(pages_dev.device).total_memory:
                 nsets = 1
-            if not hasattr(self, "_stream_sets") or len(self._stream_sets) != nsets:
+            if len(self._stream_sets) != nsets:
                 self._stream_sets, self._det_stream_sets, self._set_idx = [[] for _ in range(nsets)], [[] for _ in range(nsets)], 0
             self._set_idx = (self._set_idx + 1) % nsets
             pool, dpool = self._stream_sets[self._set_idx], self._det_stream_sets[self._set_idx]
-            hi_prio = -1 if getattr(self, "det_stream_priority", True) else 0
+            hi_prio = -1 if self.det_stream_priority else 0
             while len(pool) < nsub:
                 pool.append(torch.cuda.Stream())
                 dpool.append(torch.cuda.Stream(priority=hi_prio))
             streams, det_streams = pool[:nsub], dpool[:nsub]
-        from . import ops
-        det_handles, ro_handles, det_events, qd_handles = [], [], [], {}
-        H, W = arrays[0].shape[:2]
-        for (lo, hi), st in zip(bounds, det_streams):
-            if st is not main:
-                st.wait_stream(main)
-            with torch.cuda.stream(st):
+        rec, rectify, groups = self.recognizer, bool(self.rectify_crops), []
+        for (lo, hi), st, dst in zip(bounds, streams, det_streams):
+            if dst is not main:
+                dst.wait_stream(main)
+            with torch.cuda.stream(dst):
                 mo = None if _maps_override is None else (_maps_override[0][lo:hi], _maps_override[1][lo:hi])
                 dh = det.detect_start(pages_dev[lo:hi], mo)
-                det_handles.append(dh)
                 # reading order + crop descriptors of the group's pages on the device, right behind the box filters: the host
                 # then needs only the crop COUNTS to enqueue the recogniser (Page / Word assembly moves to collect_batch)
-                ro = None
-                if recognize_text and dh[5] is not None and getattr(self, "device_order", True):
-                    ro = ops.reading_order_crops(dh[5], dh[6], (H, W), self.min_text_size, self.recognizer.img_h, self.recognizer.img_w,
-                                                 page_base=lo)
-                    if getattr(self, "rectify_crops", False):  # quad descriptors of the same words, right behind, same order
-                        qd_handles[len(ro_handles)] = ops.quad_crop_descriptors(dh[5], dh[6], ro, self.recognizer.img_h, self.recognizer.img_w)
-                ro_handles.append(ro)
+                ro = qd = None
+                if recognize_text and dh.final_boxes is not None and self.device_order:
+                    ro = ops.ReadingOrder(*ops.reading_order_crops(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h,
+                                                                   rec.img_w, page_base=lo))
+                    if rectify:  # quad descriptors of the same words, right behind, same order
+                        qd = ops.quad_crop_descriptors(dh.final_boxes, dh.final_counts, ro, rec.img_h, rec.img_w)
                 ev = torch.cuda.Event()
-                ev.record(st)  # detector outputs of this group complete
-                det_events.append(ev)
-        return {"arrays": arrays, "pages_dev": pages_dev, "bounds": bounds, "streams": streams, "det_streams": det_streams, "main": main,
-                "det_handles": det_handles, "ro_handles": ro_handles, "det_events": det_events, "recognize_text": recognize_text, "profile": profile,
-                "ingest_pending": ingest_pending, "qd_handles": qd_handles, "rectify": bool(getattr(self, "rectify_crops", False)),
-                "resubmit": (lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))}
+                ev.record(dst)  # detector outputs of this group complete
+                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, qd))
+        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, ingest_pending,
+                      lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
 
     def advance_batch(self, h):
         """Stage 2 of `predict_batch` for a handle from `submit_batch`: per group — wait for its boxes, run the host
-        tail + reading order, then enqueue device crops + the recogniser (asynchronous).  Idempotent.  Calling it for
-        batch i+1 BEFORE `collect_batch` of batch i keeps recogniser work queued on the device while the host
+        tail + reading order, then enqueue device crops + the recogniser (asynchronous).  Idempotent; returns `h`.  Calling it
+        for batch i+1 BEFORE `collect_batch` of batch i keeps recogniser work queued on the device while the host
         annotates batch i (bench.py does)."""
-        if h.get("groups") is not None:
+        if h.pages is not None:
             return h
-        import torch
-
-        from . import ingest, ops
-        if h.get("ingest_pending") is not None:
+        if h.ingest_pending is not None:
             # the device Huffman stage's verdict on this batch's files (queued right behind the kernels, long done by now): a corrupt
             # stream gets what the host decoder's verdict gives it — the whole batch is read again through the host path (rare)
-            bad = ingest.check_pending(h["ingest_pending"])
-            h["ingest_pending"] = None
-            if bad:
-                h2 = h["resubmit"]()
-                h.clear()
-                h.update(h2)
-        det, rec = self.detector, self.recognizer
-        arrays, pages_dev, bounds, streams = h["arrays"], h["pages_dev"], h["bounds"], h["streams"]
-        recognize_text, profile = h["recognize_text"], h["profile"]
-        tm = {"detect_wait+tail": 0.0, "order": 0.0, "crop+enqueue": 0.0, "recognize_wait": 0.0, "assign": 0.0}
-        # `pipeline.char_details = True`: the recogniser also returns per-symbol confidence and position, and collect_batch hands the
-        # recognised words out as CharWords (detectors/_types.py).  Off by default; this package's recogniser only.
-        details = bool(getattr(self, "char_details", False))
-        # `pipeline.rectify_crops = True`: canvases cut along the words' quadrilaterals (ops.quad_crop) instead of their AABB windows
-        rectify = bool(h.get("rectify"))
-        N = len(arrays)
-        H, W = arrays[0].shape[:2]
-        pages, groups = [None] * N, []
+            pending, h.ingest_pending = h.ingest_pending, None
+            if ingest.check_pending(pending):
+                h.replace_with(h.resubmit())
+        h.pages = [None] * len(h.arrays)
+        h.tm = {"detect_wait+tail": 0.0, "order": 0.0, "crop+enqueue": 0.0, "recognize_wait": 0.0, "assign": 0.0}
         with _gc_paused():
-            for gi, ((lo, hi), st, dst, dh, ro, dev_ev) in enumerate(zip(bounds, streams, h["det_streams"], h["det_handles"],
-                                                                         h["ro_handles"], h["det_events"])):
-                qd = h["qd_handles"].get(gi)
-                if ro is not None and (qd is not None or not rectify):
-                    # device path: wait for the group's crop counts only (4 bytes per page), enqueue crops + recogniser
-                    with torch.cuda.stream(dst):
-                        t0 = time.perf_counter()
-                        nc_h = ro[3].cpu().numpy()
-                        tm["detect_wait+tail"] += time.perf_counter() - t0
-                    if bool((nc_h >= 0).all()):
-                        t0 = time.perf_counter()
-                        grp = {"words": None, "spans": [], "handle": None, "ro": ro, "det": dh, "lohi": (lo, hi), "dst": dst, "det_event": dev_ev}
-                        off = 0
-                        for c in nc_h.tolist():
-                            grp["spans"].append([off, c])
-                            off += c
-                        if off:
-                            spans = [tuple(sp) for sp in grp["spans"] if sp[1] > 0]
-                            use_graph = getattr(rec, "use_graphs", False)
-                            prepared = None
-                            if not use_graph:
-                                with torch.cuda.stream(dst):  # the small blocking upload rides the high-priority stream
-                                    prepared = rec.prepare_chunks(off, spans)
-                            if st is not h["main"]:
-                                st.wait_stream(h["main"])  # the page upload
-                            st.wait_stream(dst)
-                            with torch.cuda.stream(st):
-                                ro[2].record_stream(st)
-                                desc_dev = torch.cat([ro[2][pi, :c] for pi, c in enumerate(nc_h.tolist()) if c])
-                                grp["desc"] = desc_dev if details else None
-                                if rectify:
-                                    qd.record_stream(st)
-                                    qdesc_dev = torch.cat([qd[pi, :c] for pi, c in enumerate(nc_h.tolist()) if c])
-                                    grp["qdesc"] = qdesc_dev if details else None
-                                if use_graph:  # crop + encode + decode as one hipGraph replay (declines when details or rectified crops are asked for)
-                                    grp["handle"] = rec.recognize_start_graph(pages_dev, desc_dev, spans, upload_stream=dst,
-                                                                              char_details=details, rectified=rectify)
-                                if grp["handle"] is None:
-                                    if prepared is None:  # graph path declined (first call of a bucket, ...): plain launches
-                                        with torch.cuda.stream(dst):
-                                            prepared = rec.prepare_chunks(off, spans)
-                                        st.wait_stream(dst)
-                                    if rectify:
-                                        canv = ops.quad_crop(pages_dev, None, rec.img_h, rec.img_w, qdesc_dev=qdesc_dev)
-                                    else:
-                                        canv = ops.crop_resize_pad(pages_dev, None, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                                    grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
-                        tm["crop+enqueue"] += time.perf_counter() - t0
-                        groups.append(grp)
-                        continue
-                with torch.cuda.stream(dst):
-                    t0 = time.perf_counter()
-                    res = det.detect_finish(dh, arrays[lo:hi], profile=profile)
-                    tm["detect_wait+tail"] += time.perf_counter() - t0
-                if st is not h["main"]:
-                    st.wait_stream(h["main"])  # the page upload
-                with torch.cuda.stream(st):
-                    grp = {"words": [], "spans": [], "handle": None, "lohi": (lo, hi)}
-                    if recognize_text:
-                        t0 = time.perf_counter()
-                        boxes, page_ids = [], []
-                        for pi, r in enumerate(res):
-                            page = self._page_of(r)
-                            pages[lo + pi] = page
-                            words, bxs = self._order_boxes(page)
-                            grp["spans"].append([len(grp["words"]), len(words)])
-                            grp["words"] += words
-                            boxes += bxs
-                            page_ids += [lo + pi] * len(bxs)
-                        tm["order"] += time.perf_counter() - t0
-                        t0 = time.perf_counter()
-                        if boxes:
-                            desc, keep = ops.crop_descriptors(boxes, page_ids, (H, W), rec.img_h, rec.img_w)
-                            if not keep.all():  # empty clamped crops are skipped by the reference (_pipeline.py:135)
-                                grp["words"] = [w for w, k in zip(grp["words"], keep) if k]
-                                kept_pages = np.asarray(page_ids)[keep]
-                                grp["spans"], n0 = [], 0
-                                for pi in range(lo, hi):
-                                    c = int((kept_pages == pi).sum())
-                                    grp["spans"].append([n0, c])
-                                    n0 += c
-                            if len(desc):
-                                spans = [tuple(s) for s in grp["spans"] if s[1] > 0]
-                                up = dst if getattr(self, "upload_on_det_stream", True) else st
-                                # rectified: the host twin's descriptors from the kept words' polygons, in the order of desc
-                                qdesc = ops.quad_descriptors([w.polygon for w in grp["words"]], desc, rec.img_h, rec.img_w) if rectify else None
-                                with torch.cuda.stream(up):  # the two small blocking uploads ride the high-priority stream
-                                    desc_dev = torch.from_numpy((qdesc if rectify else desc).astype("int32", copy=False)).to(det.device)
-                                    prepared = rec.prepare_chunks(len(desc), spans)
-                                if st is not up:
-                                    st.wait_stream(up)
-                                if rectify:
-                                    canv = ops.quad_crop(pages_dev, qdesc, rec.img_h, rec.img_w, qdesc_dev=desc_dev)
-                                    grp["qdesc"] = qdesc if details else None
-                                else:
-                                    canv = ops.crop_resize_pad(pages_dev, desc, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                                grp["desc"] = desc if details else None
-                                grp["handle"] = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
-                        tm["crop+enqueue"] += time.perf_counter() - t0
-                    else:
-                        for pi, r in enumerate(res):
-                            pages[lo + pi] = self._page_of(r)
-                    groups.append(grp)
-        h["pages"], h["groups"], h["tm"] = pages, groups, tm
+            for grp in h.groups:
+                if grp.ro is None or not self._advance_device_ordered(h, grp):
+                    self._advance_host_ordered(h, grp)
         return h
+
+    def _advance_device_ordered(self, h, grp):
+        """Device route: wait for the group's crop COUNTS only (4 bytes per page), enqueue crops + recogniser.  False: host route."""
+        with torch.cuda.stream(grp.det_stream):
+            t0 = time.perf_counter()
+            counts = grp.ro.ncrop.cpu().numpy()
+            h.tm["detect_wait+tail"] += time.perf_counter() - t0
+        if not bool((counts >= 0).all()):
+            return False
+        t0 = time.perf_counter()
+        grp.device_ordered, off = True, 0
+        for c in counts.tolist():
+            grp.spans.append([off, c])
+            off += c
+        if off:
+            self._enqueue_recognizer(h, grp, up=grp.det_stream, counts=counts.tolist())
+        h.tm["crop+enqueue"] += time.perf_counter() - t0
+        return True
+
+    def _advance_host_ordered(self, h, grp):
+        """Host route of a group: the detector's host tail, reading order and crop descriptors on the host, then crops + recogniser."""
+        rec, (lo, hi), st = self.recognizer, (grp.lo, grp.hi), grp.stream
+        H, W = h.arrays[0].shape[:2]
+        with torch.cuda.stream(grp.det_stream):
+            t0 = time.perf_counter()
+            res = self.detector.detect_finish(grp.det, h.arrays[lo:hi], profile=h.profile)
+            h.tm["detect_wait+tail"] += time.perf_counter() - t0
+        if st is not h.main:
+            st.wait_stream(h.main)  # the page upload
+        h.pages[lo:hi] = [self._page_of(r) for r in res]
+        if not h.recognize_text:
+            return
+        with torch.cuda.stream(st):
+            t0 = time.perf_counter()
+            grp.words, boxes, page_ids = [], [], []
+            for pi in range(lo, hi):
+                words, bxs = self._order_boxes(h.pages[pi])
+                grp.spans.append([len(grp.words), len(words)])
+                grp.words += words
+                boxes += bxs
+                page_ids += [pi] * len(bxs)
+            h.tm["order"] += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            if boxes:
+                desc, keep = ops.crop_descriptors(boxes, page_ids, (H, W), rec.img_h, rec.img_w)
+                if not keep.all():  # empty clamped crops are skipped by the reference (_pipeline.py:135)
+                    grp.words = [w for w, k in zip(grp.words, keep) if k]
+                    kept_pages = np.asarray(page_ids)[keep]
+                    grp.spans, n0 = [], 0
+                    for pi in range(lo, hi):
+                        c = int((kept_pages == pi).sum())
+                        grp.spans.append([n0, c])
+                        n0 += c
+                if len(desc):
+                    grp.desc_host = desc
+                    if h.rectify:  # the host twin's descriptors from the kept words' polygons, in the order of desc
+                        grp.qdesc_host = ops.quad_descriptors([w.polygon for w in grp.words], desc, rec.img_h, rec.img_w)
+                    self._enqueue_recognizer(h, grp, up=grp.det_stream if self.upload_on_det_stream else st)
+            h.tm["crop+enqueue"] += time.perf_counter() - t0
+
+    def _enqueue_recognizer(self, h, grp, up, counts=None):
+        """The tail both routes share, for a group with crops: the small blocking uploads on `up` (the high-priority detector stream,
+        so that they do not queue behind other groups' recogniser work), the waits of the group's recogniser stream, the crops — AABB
+        windows, or cut along the quadrilaterals with `rectify_crops` — and the recogniser, or all of it as one graph replay.
+        Device route (`counts` = the pages' crop counts): the descriptors are grp.ro / grp.qd, compacted here on the recogniser stream.
+        Host route: grp.desc_host / grp.qdesc_host, uploaded here; the kernel validates the device copy against them."""
+        rec, st, pages_dev, rectify, details = self.recognizer, grp.stream, h.pages_dev, h.rectify, bool(self.char_details)
+        on_device = counts is not None
+        spans = [(first, n) for first, n in grp.spans if n > 0]
+        rows = sum(n for _, n in spans)
+        use_graph = on_device and rec.use_graphs
+        desc_dev = qdesc_dev = prepared = None
+        with torch.cuda.stream(up):
+            if not on_device:
+                dev = torch.from_numpy((grp.qdesc_host if rectify else grp.desc_host).astype("int32", copy=False)).to(self.detector.device)
+                desc_dev, qdesc_dev = (None, dev) if rectify else (dev, None)
+            if not use_graph:
+                prepared = rec.prepare_chunks(rows, spans)
+        if on_device and st is not h.main:
+            st.wait_stream(h.main)  # the page upload (the host route waited for it before its host stage)
+        if on_device or st is not up:
+            st.wait_stream(up)
+        with torch.cuda.stream(st):
+            if on_device:
+                def compact(t):
+                    t.record_stream(st)
+                    return torch.cat([t[pi, :c] for pi, c in enumerate(counts) if c])
+                desc_dev, qdesc_dev = compact(grp.ro.desc), (compact(grp.qd) if rectify else None)
+                if details:
+                    grp.desc_dev, grp.qdesc_dev = desc_dev, qdesc_dev
+                if use_graph:  # crop + encode + decode as one hipGraph replay (declines when details or rectified crops are asked for)
+                    grp.handle = rec.recognize_start_graph(pages_dev, desc_dev, spans, upload_stream=up, char_details=details, rectified=rectify)
+            if grp.handle is None:
+                if prepared is None:  # graph path declined (first call of a bucket, ...): plain launches
+                    with torch.cuda.stream(up):
+                        prepared = rec.prepare_chunks(rows, spans)
+                    st.wait_stream(up)
+                if rectify:
+                    canv = ops.quad_crop(pages_dev, grp.qdesc_host, rec.img_h, rec.img_w, qdesc_dev=qdesc_dev)
+                else:
+                    canv = ops.crop_resize_pad(pages_dev, grp.desc_host, rec.img_h, rec.img_w, desc_dev=desc_dev)
+                grp.handle = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
 
     def collect_batch(self, h):
         """Stages 2-3 of `predict_batch` for a handle from `submit_batch` -> list of Pages (stage 2 = `advance_batch`,
         skipped when already done; stage 3 = per group: finish the recogniser (sync) and annotate the words)."""
-        import torch
-
         self.advance_batch(h)
-        rec = self.recognizer
-        streams, main, profile = h["streams"], h["main"], h["profile"]
-        pages, groups, tm = h["pages"], h["groups"], h["tm"]
+        rec, main, pages, tm = self.recognizer, h.main, h.pages, h.tm
         with _gc_paused():
-            for grp, st in zip(groups, streams):
-                if grp.get("ro") is not None:
-                    # device-ordered group: Page / Word assembly happens here, off the path that feeds the device
-                    lo, hi = grp["lohi"]
+            for grp in h.groups:
+                lo, hi, st = grp.lo, grp.hi, grp.stream
+                if grp.device_ordered:
+                    # device-ordered group: Page / Word assembly happens here, off the path that feeds the device.
                     # read the boxes back on a copy stream of their own that only waits for the group's detector outputs: on the
                     # detector stream these copies would queue behind the detector work of the batch after next (it shares that
                     # stream), on the recogniser stream behind this batch's whole recogniser
-                    if not hasattr(self, "_copy_stream"):
+                    if self._copy_stream is None:
                         self._copy_stream = torch.cuda.Stream(priority=-1)
-                    self._copy_stream.wait_event(grp["det_event"])
+                    self._copy_stream.wait_event(grp.det_event)
                     with torch.cuda.stream(self._copy_stream):
                         t0 = time.perf_counter()
-                        res = self.detector.detect_finish(grp["det"], h["arrays"][lo:hi], profile=profile)
-                        order_h, keep_h = grp["ro"][0].cpu().numpy(), grp["ro"][1].cpu().numpy()
+                        res = self.detector.detect_finish(grp.det, h.arrays[lo:hi], profile=h.profile)
+                        order_h, keep_h = grp.ro.order.cpu().numpy(), grp.ro.keep.cpu().numpy()
                         tm["detect_wait+tail"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
-                    grp["words"] = []
+                    grp.words = []
                     for pi, r in enumerate(res):
                         page = self._page_of(r)
                         pages[lo + pi] = page
@@ -510,40 +530,38 @@ class Pipeline:
                             if nw:
                                 old = block.words
                                 block.words = [old[k] for k in order_h[pi, k0:k0 + nw].tolist()]
-                                grp["words"] += [block.words[pos] for pos in np.flatnonzero(keep_h[pi, k0:k0 + nw]).tolist()]
+                                grp.words += [block.words[pos] for pos in np.flatnonzero(keep_h[pi, k0:k0 + nw]).tolist()]
                             k0 += nw
                     tm["order"] += time.perf_counter() - t0
-                if grp["handle"] is not None:
+                if grp.handle is not None:
+                    details = grp.handle.char_details
                     with torch.cuda.stream(st):
                         t0 = time.perf_counter()
-                        details = bool(grp["handle"].get("char_details"))
-                        fin = rec.recognize_finish(grp["handle"], spans=[tuple(s) for s in grp["spans"] if s[1] > 0])
-                        ids, trun, conf = fin[:3]
-                        qdesc = None
+                        fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0])
                         if details:
-                            desc = grp["desc"] if isinstance(grp["desc"], np.ndarray) else grp["desc"].cpu().numpy()
-                            if grp.get("qdesc") is not None:
-                                qdesc = grp["qdesc"] if isinstance(grp["qdesc"], np.ndarray) else grp["qdesc"].cpu().numpy()
+                            ids, trun, conf, prob, centre, _peak = fin
+                            desc = grp.desc_host if grp.desc_host is not None else grp.desc_dev.cpu().numpy()
+                            qdesc = grp.qdesc_host if grp.qdesc_dev is None else grp.qdesc_dev.cpu().numpy()
+                        else:
+                            ids, trun, conf = fin
                         tm["recognize_wait"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
                     texts = rec.texts(ids, trun)
-                    for word, text, c in zip(grp["words"], texts, conf.tolist()):
+                    for word, text, c in zip(grp.words, texts, conf.tolist()):
                         word.text = text
                         word.recognition_confidence = c
                     if details and qdesc is not None:  # rectified: x through the quad's patch instead of the AABB window
-                        self._attach_chars(grp["words"], rec.chars(ids, trun, fin[3], fin[4], qdesc[:, 9], None, None, qdesc=qdesc),
-                                           pages[grp["lohi"][0]:grp["lohi"][1]])
+                        self._attach_chars(grp.words, rec.chars(ids, trun, prob, centre, qdesc[:, 9], None, None, qdesc=qdesc), pages[lo:hi])
                     elif details:
-                        self._attach_chars(grp["words"], rec.chars(ids, trun, fin[3], fin[4], desc[:, 5], desc[:, 1], desc[:, 3]),
-                                           pages[grp["lohi"][0]:grp["lohi"][1]])
+                        self._attach_chars(grp.words, rec.chars(ids, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3]), pages[lo:hi])
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
-            for dst in h["det_streams"]:
-                if dst is not main:
-                    main.wait_stream(dst)
+            for grp in h.groups:
+                if grp.det_stream is not main:
+                    main.wait_stream(grp.det_stream)
         self.last_profile = tm
-        if profile:
+        if h.profile:
             print("Pipeline.predict_batch host stages (s):", {k: round(v, 4) for k, v in tm.items()})
         return pages
 
@@ -596,8 +614,7 @@ class Pipeline:
                 return None
         except Exception:
             return None
-        if quad is not None and getattr(self, "rectify_crops", False) and image.ndim == 3 and image.shape[2] == 3:
-            from . import ops  # outside the try: a missing native library is an error, not a word without text
+        if quad is not None and self.rectify_crops and image.ndim == 3 and image.shape[2] == 3:
             desc, _ = ops.crop_descriptors([(x_min, y_min, x_max, y_max)], [0], (h, w), 1, 1)
             if len(desc):  # always: the window above is not empty
                 qd = ops.quad_descriptors([quad], desc, natural=True)

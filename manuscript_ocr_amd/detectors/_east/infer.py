@@ -17,12 +17,13 @@ Extensions (keyword-only, all optional):
 """
 import time
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
-from ... import ops
+from ... import ingest, ops
+from ..._graphpool import GraphPool, Lease
 from .._types import Block, Page, Word
 from . import post
 from .net import EastNet
@@ -32,6 +33,18 @@ _DEFAULT_WEIGHT_LOCATIONS = (
     Path("weights") / "east_quad_23_05.pth",
     Path.home() / ".manuscript" / "east" / "east_quad_23_05.pth",
 )
+
+
+class Detection(NamedTuple):
+    """Device tensors: maps, LANMS output (boxes [N,max_cand,9], nbox [N]), decode's counts, box tail output (None without it)."""
+    score: torch.Tensor
+    geo: torch.Tensor
+    boxes: torch.Tensor
+    nbox: torch.Tensor
+    counts: torch.Tensor
+    final_boxes: Optional[torch.Tensor]
+    final_counts: Optional[torch.Tensor]
+    graph: Optional[Lease] = None  # the replayed instance these tensors live in; None = plain launches
 
 
 class EAST:
@@ -98,7 +111,9 @@ class EAST:
         # network input: one candidate per q x q cell of the 1/4-resolution map (utils.py:349-356), so decode cannot overflow
         self.max_candidates = max_candidates
         self.use_graphs = bool(use_graphs)  # hipGraph replay of the static detect sequence in detect_start (BASELINE configs[3])
-        self._graphs: Dict[Any, Dict[str, Any]] = {}
+        self._graphs = GraphPool()  # keyed by input shape (and the injected maps' addresses)
+        self.device_tail = True  # box filters behind LANMS on the device; False = the host tail an oversized page takes (test hook)
+        self.device_ingest = True  # predict_batch decodes JPEG files on the device; False = read_image on the host (test hook)
         if abs(1.0 / score_geo_scale - 4.0) > 1e-9:
             raise ValueError("the network emits maps at 1/4 resolution (east.py:126-127): score_geo_scale must be 0.25")
 
@@ -116,7 +131,7 @@ class EAST:
 
     def detect_device(self, pages_dev, maps_override=None):
         """pages_dev [N,h,w,3] u8 on the device (any size) -> device tensors
-        (score, geo, boxes [N,max_cand,9], nbox [N]).  Resize, network, decode and LANMS, all HIP.
+        (a Detection).  Resize, network, decode and LANMS, all HIP.
         A LIST of [h_i,w_i,3] tensors is a ragged batch: the reference resizes every page to the network input first
         (infer.py:304), so pages of any mix of sizes are resized on the device one by one, stacked and sent through the network
         together; only the box tail, which scales back to each page's own size, runs per size group."""
@@ -137,7 +152,7 @@ class EAST:
                                        self._max_candidates())
         boxes, nbox = ops.east_lanms(cand, counts, self.iou_threshold)
         fboxes = fn = None
-        if getattr(self, "device_tail", True):
+        if self.device_tail:
             # infer.py:340-356 on the device: expand, scale back to the page, contained boxes, area anomalies, axis-aligned
             def tail(b, n, hw):
                 return ops.east_box_tail(b, n, self.expand_ratio_w, self.expand_ratio_h, hw[1] / tw, hw[0] / th,
@@ -152,7 +167,7 @@ class EAST:
                     fb, fc = tail(boxes.index_select(0, idx).contiguous(), nbox.index_select(0, idx).contiguous(), hw)
                     fboxes.index_copy_(0, idx, fb)
                     fn.index_copy_(0, idx, fc)
-        return score, geo, boxes, nbox, counts, fboxes, fn
+        return Detection(score, geo, boxes, nbox, counts, fboxes, fn)
 
     def _host_tail(self, quads: np.ndarray, orig_hw) -> np.ndarray:
         """infer.py:340-356 on the (M,9) f32 NMS output."""
@@ -199,47 +214,42 @@ class EAST:
         hipGraph and replayed: the page bytes are copied into the instance's static input buffer, the outputs live in
         the graph's private pool until `detect_finish` has read them.  The first call of a shape runs eagerly (lazy
         one-time kernel attributes must not fall into a capture); an instance still in flight is never replayed — a
-        second one is captured (two batches in flight = two instances per group)."""
+        second one is captured (_graphpool.py has the policy); the result's `graph` lease holds the instance until
+        `detect_finish`, or until the result is dropped."""
         if not self.use_graphs or ops.PROFILE is not None or isinstance(pages_dev, (list, tuple)):
-            return self.detect_device(pages_dev, maps_override) + (None,)
+            return self.detect_device(pages_dev, maps_override)
         key = (tuple(pages_dev.shape), None if maps_override is None else (maps_override[0].data_ptr(), maps_override[1].data_ptr()))
-        pool = self._graphs.setdefault(key, {"warm": False, "inst": []})
-        if not pool["warm"]:
-            pool["warm"] = True
-            return self.detect_device(pages_dev, maps_override) + (None,)
-        inst = next((i for i in pool["inst"] if not i["busy"]), None)
-        if inst is None:
-            if len(pool["inst"]) >= 4:
-                return self.detect_device(pages_dev, maps_override) + (None,)
-            for _ in range(2 if not pool["inst"] else 1):  # the first capture of a shape makes TWO instances: consecutive
-                inp = torch.empty_like(pages_dev)          # batches overlap (submit i+1 before collect i), so both are needed
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self.detect_device(inp, maps_override)
-                pool["inst"].append({"graph": graph, "inp": inp, "out": out, "busy": False})
-            inst = pool["inst"][-1]
-        inst["busy"] = True
-        inst["inp"].copy_(pages_dev, non_blocking=True)
-        inst["graph"].replay()
-        return inst["out"] + (inst,)
+
+        def capture():
+            inp = torch.empty_like(pages_dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out = self.detect_device(inp, maps_override)
+            return graph, (inp, out)
+
+        inst = self._graphs.acquire(key, capture) if self._graphs.warm(key) else None
+        if inst is None:  # first call of a shape, or every instance in flight
+            return self.detect_device(pages_dev, maps_override)
+        inp, out = inst.state
+        inp.copy_(pages_dev, non_blocking=True)
+        inst.graph.replay()
+        return out._replace(graph=Lease(inst))
 
     def detect_finish(self, handle, imgs, vis=False, profile=False, return_maps=False, sort_reading_order=False):
         """Wait for `handle` (from detect_start), then the host tail (infer.py:340-390) -> list of result dicts."""
-        inst = handle[7]
         try:
             t0 = time.time()
-            score, geo, boxes, nbox, counts, fboxes, fn, _ = handle
-            nbox_h = nbox.cpu().numpy()
-            counts_h = counts.cpu().numpy()
+            nbox_h = handle.nbox.cpu().numpy()
+            counts_h = handle.counts.cpu().numpy()
             if np.any(counts_h < 0):
                 raise RuntimeError(f"more than max_candidates={self._max_candidates()} cells above threshold; raise max_candidates "
                                    "(None = the exact bound for the network input)")
-            fn_h = fn.cpu().numpy() if fn is not None else None
+            fn_h = handle.final_counts.cpu().numpy() if handle.final_counts is not None else None
             on_device = fn_h is not None and bool(np.all(fn_h >= 0))  # a page above the device tail capacity (16384 boxes) leaves the tail to the host
             if on_device:
-                final_h = fboxes[:, : max(int(fn_h.max()), 1)].cpu().numpy()
+                final_h = handle.final_boxes[:, : max(int(fn_h.max()), 1)].cpu().numpy()
             else:
-                boxes_h = boxes[:, : max(int(nbox_h.max()), 1)].cpu().numpy()
+                boxes_h = handle.boxes[:, : max(int(nbox_h.max()), 1)].cpu().numpy()
             if profile:
                 print(f"  Model inference + decode + NMS (device wait): {time.time() - t0:.3f}s")
                 print(f"    Boxes after NMS: {[int(v) for v in nbox_h]}")
@@ -254,22 +264,21 @@ class EAST:
                 results.append({
                     "page": page,
                     "vis_image": visualize_page(img, page, show_order=False) if vis else None,
-                    "score_map": score[n].cpu().numpy() if return_maps else None,
-                    "geo_map": geo[n].permute(2, 0, 1).contiguous().cpu().numpy() if return_maps else None,
+                    "score_map": handle.score[n].cpu().numpy() if return_maps else None,
+                    "geo_map": handle.geo[n].permute(2, 0, 1).contiguous().cpu().numpy() if return_maps else None,
                 })
             self.last_profile = {"device_wait": t_dev, "host_tail": time.time() - t0 - t_dev}
             return results
         finally:
-            if inst is not None:
-                inst["busy"] = False  # every output of the graph instance has been copied out (or the call failed)
+            if handle.graph is not None:
+                handle.graph.release()  # every output of the graph instance has been copied out (or the call failed)
 
     def predict_batch(self, images: Sequence[np.ndarray], vis=False, profile=False, return_maps=False,
                       sort_reading_order=False, _maps_override=None, _pages_dev=None) -> List[Dict[str, Any]]:
         imgs, decoded = [], []
         for im in images:
             t = None
-            if _pages_dev is None and not vis and getattr(self, "device_ingest", True):
-                from ... import ingest
+            if _pages_dev is None and not vis and self.device_ingest:
                 t = ingest.read_image_device(im, self.device)  # JPEG file: decoded on the device, the host keeps only the shape
             imgs.append(np.broadcast_to(np.uint8(0), tuple(t.shape)) if t is not None else read_image(im))
             decoded.append(t)

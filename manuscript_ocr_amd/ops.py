@@ -6,7 +6,9 @@ concat buffer: the kernels take explicit strides / leading dimensions).
 """
 import ctypes
 import os
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -450,11 +452,19 @@ def east_box_tail(boxes, nbox, expand_w, expand_h, scale_x, scale_y, axis_aligne
     return out, n_out
 
 
+class ReadingOrder(NamedTuple):
+    """Result of `reading_order_crops`, per page, on the device."""
+    order: torch.Tensor  # [N,max_cand] i32: the words in reading order
+    keep: torch.Tensor   # [N,max_cand] i32: which positions of that order yield a crop
+    desc: torch.Tensor   # [N,max_cand,8] i32: the kept words' crop descriptors, compacted
+    ncrop: torch.Tensor  # [N] i32: crops per page; -1 = the page takes the host path
+
+
 def reading_order_crops(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf"),
                         workspace=None):
     """Final boxes [N,max_cand,9] f32 + counts [N] i32 (device, from east_box_tail) -> per page, on the device: reading order of
     the words, which positions yield a crop, and the crop descriptors for crop_resize_pad (msocr_reading_order_crops).
-    Returns (order [N,max_cand] i32, keep [N,max_cand] i32, desc [N,max_cand,8] i32, ncrop [N] i32; ncrop -1 = host path)."""
+    Returns a ReadingOrder."""
     _need_cuda(boxes, nbox)
     N, max_cand, _ = boxes.shape
     dev = boxes.device
@@ -469,7 +479,7 @@ def reading_order_crops(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_
                                                   int(min_text_size), int(img_h), int(img_w), float(y_tol_ratio), float(x_gap_ratio),
                                                   int(page_base), order.data_ptr(), keep.data_ptr(), desc.data_ptr(), ncrop.data_ptr(),
                                                   ws.data_ptr(), _stream()), "reading_order_crops")
-    return order, keep, desc, ncrop
+    return ReadingOrder(order, keep, desc, ncrop)
 
 
 def nchw_to_nhwc(x_f32, dtype, out=None):
@@ -541,7 +551,6 @@ def crop_descriptors(boxes, page_ids, page_hw, img_h, img_w):
     arithmetic (transforms.py:91-95,114-117; Python round = banker's = np.rint on the same doubles).  boxes: iterable of
     (x_min,y_min,x_max,y_max) ints.  Returns (int32 [M,8] descriptors, keep mask) — empty crops are dropped like the
     reference does.  Vectorised; `_crop_descriptors_loop` is the literal per-box form it is tested against."""
-    import numpy as np
     H, W = page_hw
     b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
     pg = np.asarray(page_ids, dtype=np.int64).reshape(-1)
@@ -563,7 +572,6 @@ def crop_descriptors(boxes, page_ids, page_hw, img_h, img_w):
 def _crop_descriptors_loop(boxes, page_ids, page_hw, img_h, img_w):
     """DIAGNOSTIC, not on any product path: the literal per-box form of `crop_descriptors`, kept only as the second implementation
     of the differential CPU test (tests/test_host_cpu.py::test_vectorised_crop_descriptors_equal_the_loop)."""
-    import numpy as np
     H, W = page_hw
     desc, keep = [], []
     for (x0, y0, x1, y1), pg in zip(boxes, page_ids):
@@ -585,10 +593,8 @@ def _crop_descriptors_loop(boxes, page_ids, page_hw, img_h, img_w):
     return np.asarray(desc, dtype=np.int32).reshape(-1, 8), np.asarray(keep, dtype=bool)
 
 
-def crop_resize_pad(pages_u8, desc_host, img_h, img_w, desc_dev=None):
-    """pages [N,H,W,3] u8 device, desc_host int32 [M,8] (numpy) -> canvases [M,img_h,img_w,3] u8 device.
-    desc_dev: the same descriptors already on the device (uploaded by the caller on another stream); desc_host may be None
-    when they were produced on the device (reading_order_crops): the kernel then validates every descriptor itself."""
+def _crop(symbol, width, pages_u8, desc_host, img_h, img_w, desc_dev):
+    """The body of `crop_resize_pad` (msocr_crop_resize_pad, descriptors [M,8]) and `quad_crop` (msocr_quad_crop, [M,12])."""
     _need_cuda(pages_u8, desc_dev)
     N, H, W, C = pages_u8.shape
     assert C == 3 and pages_u8.dtype == torch.uint8 and pages_u8.is_contiguous()
@@ -600,12 +606,19 @@ def crop_resize_pad(pages_u8, desc_host, img_h, img_w, desc_dev=None):
     if desc_dev is None:
         desc_dev = torch.from_numpy(desc_host).to(pages_u8.device)
     else:
-        assert desc_dev.dtype == torch.int32 and desc_dev.is_contiguous() and desc_dev.shape == (M, 8)
+        assert desc_dev.dtype == torch.int32 and desc_dev.is_contiguous() and desc_dev.shape == (M, width)
         desc_dev.record_stream(torch.cuda.current_stream())
     out = torch.empty((M, img_h, img_w, 3), dtype=torch.uint8, device=pages_u8.device)
-    nat.check(nat.lib().msocr_crop_resize_pad(pages_u8.data_ptr(), N, H, W, desc_dev.data_ptr(), hp, M, img_h, img_w,
-                                              out.data_ptr(), _stream()), "crop_resize_pad")
+    nat.check(getattr(nat.lib(), symbol)(pages_u8.data_ptr(), N, H, W, desc_dev.data_ptr(), hp, M, img_h, img_w, out.data_ptr(), _stream()),
+              symbol[len("msocr_"):])
     return out
+
+
+def crop_resize_pad(pages_u8, desc_host, img_h, img_w, desc_dev=None):
+    """pages [N,H,W,3] u8 device, desc_host int32 [M,8] (numpy) -> canvases [M,img_h,img_w,3] u8 device.
+    desc_dev: the same descriptors already on the device (uploaded by the caller on another stream); desc_host may be None
+    when they were produced on the device (reading_order_crops): the kernel then validates every descriptor itself."""
+    return _crop("msocr_crop_resize_pad", 8, pages_u8, desc_host, img_h, img_w, desc_dev)
 
 
 # ------------------------------------------------------------------------------------------- rectified crops
@@ -614,14 +627,14 @@ def quad_crop_descriptors(boxes, nbox, ro, img_h, img_w, out=None):
     `reading_order_crops` and its result `ro` = (order, keep, desc, ncrop) -> qdesc [N,max_cand,12] i32 on the device, per page the
     quad descriptors of the kept words, compacted in exactly the order of `desc`.  Rows of a page with ncrop < 0 (host route) and
     rows past a page's ncrop are not written (zeros, or what `out` held)."""
-    order, keep, desc, ncrop = ro
-    _need_cuda(boxes, nbox, order, keep, desc, ncrop)
+    ro = ReadingOrder(*ro)  # any (order, keep, desc, ncrop) will do
+    _need_cuda(boxes, nbox, *ro)
     N, max_cand, _ = boxes.shape
-    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and desc.shape == (N, max_cand, 8) and desc.is_contiguous()
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and ro.desc.shape == (N, max_cand, 8) and ro.desc.is_contiguous()
     qdesc = out if out is not None else torch.zeros((N, max_cand, 12), dtype=torch.int32, device=boxes.device)
     assert qdesc.shape == (N, max_cand, 12) and qdesc.dtype == torch.int32 and qdesc.is_contiguous() and qdesc.is_cuda
     nat.check(nat.lib().msocr_quad_crop_descriptors(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, int(img_h), int(img_w),
-                                                    order.data_ptr(), keep.data_ptr(), desc.data_ptr(), ncrop.data_ptr(),
+                                                    ro.order.data_ptr(), ro.keep.data_ptr(), ro.desc.data_ptr(), ro.ncrop.data_ptr(),
                                                     qdesc.data_ptr(), _stream()), "quad_crop_descriptors")
     return qdesc
 
@@ -630,7 +643,6 @@ def quad_descriptors(polygons, desc, img_h=0, img_w=0, natural=False):
     """Host form through the host twin (msocr_quad_crop_descriptors_host): polygons [M,4,2] (corners as the detector stored them, taken
     as f32) + the words' AABB descriptors `desc` int32 [M,8] (`crop_descriptors`) -> quad descriptors int32 [M,12] (numpy).
     natural=True: the regions at their own size (new_w = rint(w), new_h = rint(h), y0 = 0) instead of the fit to img_h x img_w."""
-    import numpy as np
     desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 8)
     M = len(desc)
     quads = np.ascontiguousarray(np.asarray(polygons, dtype=np.float32).reshape(M, 8))
@@ -643,7 +655,6 @@ def quad_descriptors(polygons, desc, img_h=0, img_w=0, natural=False):
 def quad_crop_host(pages_u8, qdesc, img_h, img_w):
     """The CPU twin of `quad_crop` (msocr_quad_crop_host): pages [N,H,W,3] u8 numpy + quad descriptors int32 [M,12] -> canvases
     [M,img_h,img_w,3] u8 numpy, the same bytes as the kernel's."""
-    import numpy as np
     pages_u8 = np.ascontiguousarray(pages_u8, dtype=np.uint8)
     qdesc = np.ascontiguousarray(qdesc, dtype=np.int32).reshape(-1, 12)
     N, H, W, C = pages_u8.shape
@@ -658,21 +669,4 @@ def quad_crop(pages_u8, qdesc_host, img_h, img_w, qdesc_dev=None):
     """pages [N,H,W,3] u8 device, qdesc_host int32 [M,12] (numpy) -> canvases [M,img_h,img_w,3] u8 device, cut along the words'
     quadrilaterals (msocr_quad_crop).  Mirrors `crop_resize_pad`: qdesc_dev = the same descriptors already on the device;
     qdesc_host may be None when they were produced there (quad_crop_descriptors): the kernel then validates every descriptor itself."""
-    _need_cuda(pages_u8, qdesc_dev)
-    N, H, W, C = pages_u8.shape
-    assert C == 3 and pages_u8.dtype == torch.uint8 and pages_u8.is_contiguous()
-    hp = None
-    if qdesc_host is not None:
-        qdesc_host = qdesc_host.astype("int32", copy=False)
-        hp = qdesc_host.ctypes.data
-    M = len(qdesc_host) if qdesc_host is not None else int(qdesc_dev.shape[0])
-    if qdesc_dev is None:
-        qdesc_dev = torch.from_numpy(qdesc_host).to(pages_u8.device)
-    else:
-        assert qdesc_dev.dtype == torch.int32 and qdesc_dev.is_contiguous() and qdesc_dev.shape == (M, 12)
-        qdesc_dev.record_stream(torch.cuda.current_stream())
-    out = torch.empty((M, img_h, img_w, 3), dtype=torch.uint8, device=pages_u8.device)
-    nat.check(nat.lib().msocr_quad_crop(pages_u8.data_ptr(), N, H, W, qdesc_dev.data_ptr(), hp, M, img_h, img_w, out.data_ptr(), _stream()),
-              "quad_crop")
-    return out
-
+    return _crop("msocr_quad_crop", 12, pages_u8, qdesc_host, img_h, img_w, qdesc_dev)

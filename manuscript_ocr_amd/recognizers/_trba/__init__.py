@@ -13,45 +13,47 @@ dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215
 """
 import json
 import os
+from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
 from PIL import Image
 
+from ... import _native as nat
+from ... import ops
+from ..._graphpool import GraphPool, Lease
 from .net import TrbaNet
 from .transforms import decode_tokens, frame_to_pixel, frame_to_quad_x, load_charset, resize_and_pad, resized_size
 
 
-class _GraphLease:
-    """Holds one captured recogniser-graph instance for a handle; released by recognize_finish (also when it raises) or when the
-    handle is dropped without ever being finished.  An event recorded right behind the replay says when the instance's static
-    buffers may be rewritten: a dropped handle waits for THAT event only — never a device-wide synchronize from a finalizer (the
-    garbage collector may run it while another stream capture is in progress, and a synchronize would invalidate that capture)."""
+class _Launch(NamedTuple):
+    """What the decode of one launch left on the device (AttnDecoder.greedy / beam); the other mode's fields are None."""
+    logits: Optional[torch.Tensor] = None  # greedy: [B, steps, V] f32
+    ids: Optional[torch.Tensor] = None     # greedy: [B, steps] i32
+    ws: Optional[torch.Tensor] = None      # beam: the back-tracking workspace for beam_finalize
+    fin: Optional[torch.Tensor] = None     # beam: [B] i32, the step at which each row's beams were all finished
+    alpha: Optional[torch.Tensor] = None   # char_details: the attention weights (greedy) / their per-beam trace (beam)
 
-    def __init__(self, inst):
-        self.inst = inst
-        self.done = torch.cuda.Event()
-        self.done.record()  # on the replay's stream, behind the replay
 
-    def release(self):
-        if self.inst is not None:
-            self.inst["busy"] = False
-            self.inst = None
+@dataclass(slots=True)
+class _Recognition:
+    """Handle from recognize_start / recognize_start_graph for recognize_finish."""
+    parts: List[Optional[_Launch]]  # one per launch; recognize_finish clears each once it is reduced
+    bounds: List[Tuple[int, int]]   # the launches' row ranges
+    N: int                          # rows launched
+    rows: int                       # rows asked for: a graph replay carries N - rows padding rows behind them
+    mode: str
+    beam: int
+    char_details: bool = False
+    graph_inst: Optional[Lease] = None  # the replayed graph instance; None = plain launches
 
-    def __del__(self):
-        if self.inst is None:
-            return
-        try:
-            if torch.cuda.is_current_stream_capturing():
-                return  # leave the instance marked busy: it is simply never reused (a new one is captured on demand)
-            if not self.done.query():
-                self.done.synchronize()
-        except Exception:
-            return  # the wait failed: do not hand the instance out again
-        self.inst["busy"] = False
-        self.inst = None
+
+def _row_ends(ids, trun, eos_id):
+    """ids [N,T], t_run [N] -> per row, where its text ends: the first EOS, at most t_run (what decode_tokens reads)."""
+    stop = (ids == eos_id) | (np.arange(ids.shape[1])[None, :] >= np.asarray(trun)[:, None])
+    return np.where(stop.any(axis=1), stop.argmax(axis=1), ids.shape[1])
 
 
 class TRBA:
@@ -67,9 +69,11 @@ class TRBA:
         state_dict = kwargs.pop("state_dict", None)
         config = kwargs.pop("config", None)
         self.device_batch = int(kwargs.pop("device_batch", 2048))
-        self.use_graphs = bool(kwargs.pop("use_graphs", False))  # hipGraph replay of crop + encode + beam decode (recognize_start_graph)
+        # hipGraph replay of crop + encode + beam decode (recognize_start_graph), for Pipeline's device-ordered route; bench.py --graphs
+        self.use_graphs = bool(kwargs.pop("use_graphs", False))
         self.graph_cache_buckets = int(kwargs.pop("graph_cache_buckets", 8))  # captured (stream, pages, row bucket) keys kept
-        self._graphs: Dict[Any, Dict[str, Any]] = {}
+        self._graphs = GraphPool()
+        self.last_rows = self.last_run_length_sum = 0  # rows finished and the sum of their chunks' run lengths; bench.py reads and resets
         if kwargs:
             raise TypeError(f"Unexpected keyword argument(s): {', '.join(kwargs.keys())}")
         if weights_path is not None and model_path is not None:
@@ -225,8 +229,9 @@ class TRBA:
             cv = canvases_dev[lo:hi]
             batch_H, proj_H = self.model.encode(cv)
             if mode == "greedy":
-                parts.append(self.model.greedy(batch_H, proj_H, self.max_length, self.sos_id, self.eos_id, self.blank_id,
-                                               want_alpha=char_details))
+                res = self.model.greedy(batch_H, proj_H, self.max_length, self.sos_id, self.eos_id, self.blank_id, want_alpha=char_details)
+                logits, ids, al = res if char_details else (*res, None)
+                parts.append(_Launch(logits=logits, ids=ids, alpha=al))
             else:
                 chunks = None
                 if meta_dev is not None:
@@ -234,9 +239,11 @@ class TRBA:
                     chunks = (meta_dev[off:off + nrows], meta_dev[off + nrows:off + nrows + nch],
                               torch.zeros((2 * nch,), dtype=torch.int32, device=self.device))
                     off += nrows + nch
-                parts.append(self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
-                                             self.blank_id, chunks, want_alpha=char_details))
-        return {"parts": parts, "N": N, "mode": mode, "beam": beam_size, "bounds": bounds, "char_details": bool(char_details)}
+                res = self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
+                                      self.blank_id, chunks, want_alpha=char_details)
+                ws, fin, _lp, al = res if char_details else (*res, None)
+                parts.append(_Launch(ws=ws, fin=fin, alpha=al))
+        return _Recognition(parts, bounds, N, N, mode, beam_size, bool(char_details))
 
     def recognize_start_graph(self, pages_dev: torch.Tensor, desc_dev: torch.Tensor, spans, batch_size=32, beam_size=8,
                               temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False):
@@ -249,7 +256,6 @@ class TRBA:
         fall into a capture), and whenever char_details or rectified crops (Pipeline.rectify_crops: the captured graph holds the AABB
         crop kernel, not msocr_quad_crop) are asked for (those paths are not captured).  Results are bit-identical to the eager path
         (tests/test_gpu_pipeline.py)."""
-        from ... import ops
         M = int(desc_dev.shape[0])
         Mcap = (M + 31) // 32 * 32
         if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details or rectified:
@@ -258,18 +264,9 @@ class TRBA:
         # one pool per launch stream: the groups of a batch are in flight together, each replays its own instances
         key = (torch.cuda.current_stream().cuda_stream, pages_dev.data_ptr(), tuple(pages_dev.shape), Mcap, nch_cap, batch_size, beam_size,
                float(temperature), float(alpha))
-        pool = self._graphs.pop(key, None) or {"warm": False, "inst": []}
-        self._graphs[key] = pool  # most recently used last
         # bounded cache: the key holds the page tensor's address, so callers whose pages move would otherwise capture
-        # without end, each instance pinning a private pool of up to device_batch crops of activations.  Least recently used
-        # buckets whose instances are all idle are dropped.
-        while len(self._graphs) > self.graph_cache_buckets:
-            victim = next((k for k, v in self._graphs.items() if k != key and not any(i["busy"] for i in v["inst"])), None)
-            if victim is None:
-                break
-            del self._graphs[victim]
-        if not pool["warm"]:
-            pool["warm"] = True
+        # without end, each instance pinning a private pool of up to device_batch crops of activations.
+        if not self._graphs.warm(key, max_buckets=self.graph_cache_buckets):
             return None
         # chunk metadata of the real rows (as prepare_chunks) + one chunk for the padding rows, into the instance's static buffer
         bounds, metas = self._device_batches(M, spans, batch_size)
@@ -283,30 +280,30 @@ class TRBA:
         meta[M:Mcap] = len(sizes)
         meta[Mcap:Mcap + len(sizes)] = sizes
         meta[Mcap + len(sizes)] = max(Mcap - M, 1)
-        inst = next((i for i in pool["inst"] if not i["busy"]), None)
+
+        def capture():
+            dbuf = torch.zeros((Mcap, 8), dtype=torch.int32, device=self.device)
+            mbuf = torch.zeros((Mcap + nch_cap,), dtype=torch.int32, device=self.device)
+            dbuf[:M].copy_(desc_dev)
+            dbuf[M:] = desc_dev[0]
+            mbuf.copy_(torch.from_numpy(meta).to(self.device))
+            torch.cuda.current_stream().synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                canv = ops.crop_resize_pad(pages_dev, None, self.img_h, self.img_w, desc_dev=dbuf)
+                state = torch.zeros((2 * nch_cap,), dtype=torch.int32, device=self.device)
+                batch_H, proj_H = self.model.encode(canv)
+                ws, fin, _lp = self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
+                                               self.blank_id, (mbuf[:Mcap], mbuf[Mcap:], state))
+            return graph, (dbuf, mbuf, _Launch(ws=ws, fin=fin))
+
+        inst = self._graphs.acquire(key, capture)
         if inst is None:
-            if len(pool["inst"]) >= 4:
-                return None
-            for _ in range(2 if not pool["inst"] else 1):  # consecutive batches overlap: two instances per bucket
-                dbuf = torch.zeros((Mcap, 8), dtype=torch.int32, device=self.device)
-                mbuf = torch.zeros((Mcap + nch_cap,), dtype=torch.int32, device=self.device)
-                dbuf[:M].copy_(desc_dev)
-                dbuf[M:] = desc_dev[0]
-                mbuf.copy_(torch.from_numpy(meta).to(self.device))
-                torch.cuda.current_stream().synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    canv = ops.crop_resize_pad(pages_dev, None, self.img_h, self.img_w, desc_dev=dbuf)
-                    state = torch.zeros((2 * nch_cap,), dtype=torch.int32, device=self.device)
-                    batch_H, proj_H = self.model.encode(canv)
-                    part = self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
-                                           self.blank_id, (mbuf[:Mcap], mbuf[Mcap:], state))
-                pool["inst"].append({"graph": graph, "desc": dbuf, "meta": mbuf, "part": part, "busy": False})
-            inst = pool["inst"][-1]
-        inst["busy"] = True
-        inst["desc"][:M].copy_(desc_dev, non_blocking=True)
+            return None
+        dbuf, mbuf, part = inst.state
+        dbuf[:M].copy_(desc_dev, non_blocking=True)
         if Mcap > M:
-            inst["desc"][M:] = desc_dev[0]
+            dbuf[M:] = desc_dev[0]
         # the small blocking upload of the chunk metadata must not queue behind the recogniser work already on this stream
         cur = torch.cuda.current_stream()
         up = upload_stream if upload_stream is not None else cur
@@ -315,10 +312,9 @@ class TRBA:
         if up is not cur:
             cur.wait_stream(up)
             meta_dev.record_stream(cur)
-        inst["meta"].copy_(meta_dev, non_blocking=True)
-        inst["graph"].replay()
-        return {"parts": [inst["part"]], "N": Mcap, "M_real": M, "mode": "beam", "beam": beam_size, "bounds": [(0, Mcap)],
-                "graph_inst": _GraphLease(inst)}
+        mbuf.copy_(meta_dev, non_blocking=True)
+        inst.graph.replay()
+        return _Recognition([part], [(0, Mcap)], Mcap, M, "beam", beam_size, graph_inst=Lease(inst))
 
     def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False):
         """Phases 2-3 — derive the reference's per-chunk run lengths, back-track (beam) and reduce confidences.
@@ -331,50 +327,41 @@ class TRBA:
         of the token of every step, whose mean over t < t_run is the confidence), centre (f32: the attention centroid in encoder
         frames) and peak (i32: the arg-max frame); steps t >= t_run hold 0, 0, -1 (msocr_seq_char_details; the weights stay on the
         device)."""
-        from ... import _native as nat
-        from ... import ops
         try:
             return self._recognize_finish(handle, batch_size, spans, return_logits)
         finally:
-            if handle.get("graph_inst") is not None:  # also on an exception: the instance must not stay leased for ever
-                handle["graph_inst"].release()
+            if handle.graph_inst is not None:  # also on an exception: the instance must not stay leased for ever
+                handle.graph_inst.release()
 
     def _recognize_finish(self, handle, batch_size, spans, return_logits):
-        from ... import _native as nat
-        from ... import ops
-        parts, N, mode, beam_size = handle["parts"], handle["N"], handle["mode"], handle["beam"]
-        M_real = handle.get("M_real", N)  # a graph replay carries padding rows behind the real ones
+        parts, N, M_real, mode, beam_size = handle.parts, handle.N, handle.rows, handle.mode, handle.beam
         spans = spans if spans is not None else [(0, M_real)]
         steps = self.max_length + 1 if mode == "greedy" else self.max_length
         trun = np.ones(N, dtype=np.int32)
-        if mode == "greedy":
-            ids_h = np.concatenate([p[1].cpu().numpy() for p in parts])
-            for s0, cnt in spans:
-                for c0 in range(s0, s0 + cnt, batch_size):
-                    c1 = min(c0 + batch_size, s0 + cnt)
-                    hit = np.flatnonzero(np.all(ids_h[c0:c1] == self.eos_id, axis=0))
+        host = np.concatenate([(p.ids if mode == "greedy" else p.fin).cpu().numpy() for p in parts])
+        for s0, cnt in spans:
+            for c0 in range(s0, s0 + cnt, batch_size):
+                c1 = min(c0 + batch_size, s0 + cnt)
+                if mode == "greedy":
+                    hit = np.flatnonzero(np.all(host[c0:c1] == self.eos_id, axis=0))
                     trun[c0:c1] = (hit[0] + 1) if len(hit) else steps
-        else:
-            fin_h = np.concatenate([p[1].cpu().numpy() for p in parts])
-            for s0, cnt in spans:
-                for c0 in range(s0, s0 + cnt, batch_size):
-                    c1 = min(c0 + batch_size, s0 + cnt)
-                    trun[c0:c1] = fin_h[c0:c1].max()
-        self.last_run_length_sum = getattr(self, "last_run_length_sum", 0) + int(trun[:M_real].sum())
-        self.last_rows = getattr(self, "last_rows", 0) + M_real
+                else:
+                    trun[c0:c1] = host[c0:c1].max()
+        self.last_run_length_sum += int(trun[:M_real].sum())
+        self.last_rows += M_real
         trun_dev = torch.from_numpy(trun).to(self.device)
-        details = bool(handle.get("char_details"))
+        details = handle.char_details
         ids_out, conf_out, logit_out, det_out = [], [], [], []
-        for k, (s, hi) in enumerate(handle["bounds"]):
+        for k, (s, hi) in enumerate(handle.bounds):
             B = hi - s
             tr = trun_dev[s:s + B]
+            part = parts[k]
             if mode == "greedy":
-                lg, ids = parts[k][:2]
-                al = parts[k][2] if details else None
+                lg, ids, al = part.logits, part.ids, part.alpha
             elif details:
-                lg, ids, al = self.model.beam_finalize(parts[k][0], B, steps, beam_size, tr, alpha_ws=parts[k][3])
+                lg, ids, al = self.model.beam_finalize(part.ws, B, steps, beam_size, tr, alpha_ws=part.alpha)
             else:
-                lg, ids = self.model.beam_finalize(parts[k][0], B, steps, beam_size, tr)
+                lg, ids = self.model.beam_finalize(part.ws, B, steps, beam_size, tr)
             conf = torch.empty((B,), dtype=torch.float32, device=self.device)
             nat.check(nat.lib().msocr_seq_confidence(lg.data_ptr(), ids.data_ptr(), tr.data_ptr(), B, self.model.V, steps, conf.data_ptr(),
                                                      ops._stream()), "seq_confidence")
@@ -389,7 +376,7 @@ class TRBA:
                 det_out.append((prob, centre, peak))
             if return_logits:
                 logit_out.append(lg.cpu().numpy())
-            parts[k] = None
+            parts[k] = part = None
         ids_h = torch.cat(ids_out).cpu().numpy()[:M_real]
         conf_h = torch.cat(conf_out).cpu().numpy()[:M_real]
         out = (ids_h, trun[:M_real], conf_h)
@@ -415,9 +402,7 @@ class TRBA:
         T = ids.shape[1] if ids.ndim == 2 else 0
         if not len(ids) or T == 0:
             return ["" for _ in range(len(ids))]
-        pos = np.arange(T)[None, :]
-        stop = (ids == self.eos_id) | (pos >= np.asarray(trun)[:, None])
-        end = np.where(stop.any(axis=1), stop.argmax(axis=1), T)
+        end = _row_ends(ids, trun, self.eos_id)
         itos, skip = self.itos, {self.pad_id, self.blank_id}
         rows = ids.tolist()
         return ["".join([itos[t] for t in row[:e] if t not in skip]) for row, e in zip(rows, end.tolist())]
@@ -436,9 +421,7 @@ class TRBA:
         n, T = (ids.shape[0], ids.shape[1]) if ids.ndim == 2 else (len(ids), 0)
         if not n or T == 0:
             return [[] for _ in range(n)]
-        pos = np.arange(T)[None, :]
-        stop = (ids == self.eos_id) | (pos >= np.asarray(trun)[:, None])
-        end = np.where(stop.any(axis=1), stop.argmax(axis=1), T)
+        end = _row_ends(ids, trun, self.eos_id)
         if qdesc is not None:
             xs = frame_to_quad_x(centre, qdesc).tolist()
         else:
@@ -461,11 +444,10 @@ class TRBA:
             raise ValueError(f"Unknown mode: {mode}")
         if not images_list:
             return []
-        if not return_chars:
-            canv = torch.from_numpy(self._canvases(images_list)).to(self.device, non_blocking=True)
-            return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
         arrays = [self._load_rgb(im) for im in images_list]
-        canv = torch.from_numpy(np.stack([resize_and_pad(a, self.img_h, self.img_w) for a in arrays])).to(self.device, non_blocking=True)
+        canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
+        if not return_chars:
+            return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
         ids, trun, conf, prob, centre, _peak = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha,
                                                                        char_details=True)
         src_w = [a.shape[1] for a in arrays]

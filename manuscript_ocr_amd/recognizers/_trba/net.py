@@ -134,9 +134,6 @@ class TrbaNet:
         return ops.conv2d(x, *self.P["out1"], relu=True)
 
     # ------------------------------------------------------------------------------------- encoder
-    def _gemm(self, x2d, w, b):
-        return _gemm(x2d, w, b)
-
     def encode(self, canvases_u8):
         """-> (batch_H [B,T,256] f32, proj_H [B,T,256] f32)."""
         f = self.cnn(canvases_u8)
@@ -145,10 +142,10 @@ class TrbaNet:
         H = self.Hd
         for l in (0, 1):
             r = self.rnn[l]
-            xproj = self._gemm(seq.view(B * T, -1), r["w_ih"], r["b"])  # [B*T, 2*4H] = [B][T][2][4H]
+            xproj = _gemm(seq.view(B * T, -1), r["w_ih"], r["b"])  # [B*T, 2*4H] = [B][T][2][4H]
             hcat = ops.bilstm_recurrent(xproj, r["whh_t"], B, T, H, r["whh_p"])   # [B,T,2H]
-            seq = self._gemm(hcat.view(B * T, 2 * H), r["lin_w"], r["lin_b"]).view(B, T, H)
-        proj = self._gemm(seq.view(B * T, H), self.att["i2h_w"], None).view(B, T, H)
+            seq = _gemm(hcat.view(B * T, 2 * H), r["lin_w"], r["lin_b"]).view(B, T, H)
+        proj = _gemm(seq.view(B * T, H), self.att["i2h_w"], None).view(B, T, H)
         return seq, proj
 
     # ------------------------------------------------------------------------------------- decoder
@@ -216,6 +213,7 @@ class AttnDecoder:
         self._aw = aw
         # split form of the three per-step matrices for the matrix-core beam kernel (precision "fp32"; "fp32-exact" keeps the f32 MFMA)
         self._asw = None
+        self._lp_cache = {}  # (alpha, steps) -> the beam's length-penalty table on the device, filled by `beam`
         if step_split and H == 256 and self.V <= 256:
             asw = nat.AttnSplitWeights()
             for src, dst, n, gi in (("h2h_wt", "h2h_p", H, 0), ("whh_t", "whh_p", 4 * H, 1), ("gen_wt", "gen_p", self.V, 0)):
@@ -285,8 +283,6 @@ class AttnDecoder:
         if alpha > 0:  # model.py:160, evaluated in Python double then applied in f32; cached: an H2D copy here would make
             #            the host wait for every encoder kernel already queued on this stream
             key = (float(alpha), steps)
-            if not hasattr(self, "_lp_cache"):
-                self._lp_cache = {}
             if key not in self._lp_cache:
                 self._lp_cache[key] = torch.tensor([((5.0 + (t + 1)) ** alpha) / (6.0 ** alpha) for t in range(steps)],
                                                    dtype=torch.float32).to(self.device)

@@ -133,7 +133,7 @@ def test_pipeline_char_details(gpu, rec):
 
 
 def test_graph_path_is_kept_without_details_and_declined_with(gpu, monkeypatch):
-    """use_graphs=True: with the flag off the second call of a bucket replays a captured graph (handle["graph_inst"]); with it on
+    """use_graphs=True: with the flag off the second call of a bucket replays a captured graph (handle.graph_inst); with it on
     recognize_start_graph declines and the eager path returns the same words."""
     from manuscript_ocr_amd import Pipeline, synth
     from manuscript_ocr_amd.detectors import EAST
@@ -149,7 +149,7 @@ def test_graph_path_is_kept_without_details_and_declined_with(gpu, monkeypatch):
     finish = grec.recognize_finish
 
     def spy(handle, *a, **kw):
-        seen.append((handle.get("graph_inst") is not None, bool(handle.get("char_details"))))
+        seen.append((handle.graph_inst is not None, bool(handle.char_details)))
         return finish(handle, *a, **kw)
 
     monkeypatch.setattr(grec, "recognize_finish", spy)

@@ -82,12 +82,39 @@ def test_hipgraph_replay_equals_eager(setup):
         for ra, rb in zip(a, b):
             assert np.array_equal(ra["score_map"], rb["score_map"]) and np.array_equal(ra["geo_map"], rb["geo_map"])
             assert [w.polygon for w in ra["page"].blocks[0].words] == [w.polygon for w in rb["page"].blocks[0].words]
-    pool = next(iter(graph._graphs.values()))
-    assert pool["warm"] and len(pool["inst"]) == 2 and not any(i["busy"] for i in pool["inst"])
+    pool = next(iter(graph._graphs.buckets.values()))
+    assert pool.warm and len(pool.inst) == 2 and not any(i.busy for i in pool.inst)
     dev = torch.from_numpy(np.stack([_page(k, H, W) for k in range(2)])).cuda()
     h1, h2 = graph.detect_start(dev), graph.detect_start(dev)   # two batches in flight -> two instances
-    assert h1[-1] is not None and h2[-1] is not None and h1[-1] is not h2[-1] and len(pool["inst"]) == 2
+    assert h1.graph is not None and h2.graph is not None and h1.graph.inst is not h2.graph.inst and len(pool.inst) == 2
     r1 = graph.detect_finish(h1, [_page(0, H, W)] * 2)
     r2 = graph.detect_finish(h2, [_page(0, H, W)] * 2)
     assert [w.polygon for w in r1[0]["page"].blocks[0].words] == [w.polygon for w in r2[0]["page"].blocks[0].words]
-    assert not any(i["busy"] for i in pool["inst"])
+    assert not any(i.busy for i in pool.inst)
+
+
+def test_dropped_detector_handles_free_their_graph_instances(setup):
+    """A handle from detect_start that is dropped without detect_finish gives its graph instance back once the replay behind it has
+    run (the lease's event), so the next detect_start replays instead of capturing a third instance or launching eagerly."""
+    import gc
+
+    from manuscript_ocr_amd.detectors import EAST
+    sd, _ = setup
+    H, W = 128, 160
+    graph = EAST(state_dict=sd, target_size=(W, H), device="cuda", score_thresh=0.5, use_graphs=True)
+    pages = [_page(k, H, W) for k in range(2)]
+    for _ in range(2):  # 1st call warm-up (eager), 2nd captures two instances and replays one
+        graph.predict_batch(pages)
+    pool = next(iter(graph._graphs.buckets.values()))
+    assert pool.warm and len(pool.inst) == 2 and not any(i.busy for i in pool.inst)
+    dev = torch.from_numpy(np.stack(pages)).cuda()
+    h1, h2 = graph.detect_start(dev), graph.detect_start(dev)
+    assert h1.graph is not None and h2.graph is not None and all(i.busy for i in pool.inst)
+    del h1, h2
+    torch.cuda.current_stream().synchronize()
+    gc.collect()
+    assert not any(i.busy for i in pool.inst)
+    h3 = graph.detect_start(dev)
+    assert h3.graph is not None and len(pool.inst) == 2
+    graph.detect_finish(h3, pages)
+    assert not any(i.busy for i in pool.inst)

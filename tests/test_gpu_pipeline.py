@@ -663,8 +663,8 @@ def test_whole_pipeline_hipgraph_replay_equals_eager(gpu, H, W, n_pages, rounds)
             assert [key(p) for p in a] == [key(p) for p in b], rnd
             counts.append(sum(w.text is not None for p in a for w in p.blocks[0].words))
     assert len(set(counts)) >= 2 and min(counts) > (20 if H == 512 else 1200)
-    assert any(pool["inst"] for pool in graph.recognizer._graphs.values()), "the recogniser never replayed a graph"
-    assert any(pool["inst"] for pool in graph.detector._graphs.values())
+    assert any(b.inst for b in graph.recognizer._graphs.buckets.values()), "the recogniser never replayed a graph"
+    assert any(b.inst for b in graph.detector._graphs.buckets.values())
 
 
 def test_device_reading_order_fallback_flags_and_host_path(gpu, monkeypatch):

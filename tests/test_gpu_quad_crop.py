@@ -327,7 +327,7 @@ def test_graph_path_declines_rectified_crops(gpu, monkeypatch):
     finish = grec.recognize_finish
 
     def spy(handle, *a, **kw):
-        seen.append(handle.get("graph_inst") is not None)
+        seen.append(handle.graph_inst is not None)
         return finish(handle, *a, **kw)
 
     monkeypatch.setattr(grec, "recognize_finish", spy)

@@ -110,6 +110,17 @@ def test_reading_order_and_process_batch():
     assert p.min_text_size == 5 and p.detector is not None and p.recognizer is not None
 
 
+def test_switches_are_declared_with_their_defaults():
+    """Every switch of Pipeline is an instance attribute from construction on, at its default (they stay plain attributes: the
+    constructor's parameters are the reference's, see the next test), and so is the state the batch path creates on first use."""
+    p = Pipeline(detector=DummyDetector(), recognizer=DummyRecognizer())
+    switches = {"native_fast_path": True, "device_ingest": True, "device_entropy": None, "device_order": True, "rectify_crops": False,
+                "char_details": False, "serialize_streams": False, "stream_sets": 2, "det_stream_priority": True,
+                "upload_on_det_stream": True}
+    assert {k: vars(p)[k] for k in switches} == switches
+    assert vars(p)["_stream_sets"] == [] and vars(p)["_copy_stream"] is None
+
+
 def test_public_signatures_match_the_reference_kwargs():
     """Drop-in contract: constructor / predict keyword names, order and defaults of the reference's public API
     (detectors/_east/infer.py:28-43,235-241; recognizers/_trba/__init__.py:37-44,290-299; _pipeline.py:18-24,56-62), followed

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
 
@@ -30,42 +31,29 @@ __global__ __launch_bounds__(1024) void east_decode_kernel(const float* __restri
   const int Hq = H / q, Wq = W / q;
   const int ncell = Hq * Wq;
   __shared__ int wave_cnt[16];
-  __shared__ int base_s;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) base_s = 0;
-  __syncthreads();
+  const int tid = threadIdx.x;
+  int base = 0;  // candidates of the earlier chunks (the same in every thread)
   const float scale_f = (float)scale;
   for (int c0 = 0; c0 < ncell; c0 += 1024) {
     const int cell = c0 + tid;
     bool on = false;
-    int cy = 0, cx = 0;
+    const int cy = cell < ncell ? cell / Wq : 0, cx = cell < ncell ? cell - cy * Wq : 0;
+    const int y = q > 1 ? cy * q + q / 2 : cy, x = q > 1 ? cx * q + q / 2 : cx;  // the cell's centre
+    const float* g = gm + ((long)y * W + x) * 8;
     if (cell < ncell) {
-      cy = cell / Wq;
-      cx = cell - cy * Wq;
       for (int dy = 0; dy < q; ++dy)
         for (int dx = 0; dx < q; ++dx) on |= sm[(long)(cy * q + dy) * W + cx * q + dx] > thr;
       if (on) {
-        const int y = q > 1 ? cy * q + q / 2 : cy, x = q > 1 ? cx * q + q / 2 : cx;
-        const float* g = gm + ((long)y * W + x) * 8;
         bool sane = fabsf(sm[(long)y * W + x]) < 1.0e7f;   // false for NaN
 #pragma unroll
         for (int i = 0; i < 8; ++i) sane &= fabsf(g[i]) < 1.0e7f;
         on = sane;
       }
     }
-    const unsigned long long bal = __ballot(on);
-    const int wpre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_cnt[wv] = __popcll(bal);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wv; ++w) off += wave_cnt[w];
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += wave_cnt[w];
+    int tot;
+    const int idx = base + block_exclusive_scan<1024>(on ? 1 : 0, wave_cnt, &tot);
     if (on) {
-      const int idx = off + wpre;
       if (idx < max_cand) {
-        const int y = q > 1 ? cy * q + q / 2 : cy, x = q > 1 ? cx * q + q / 2 : cx;
-        const float* g = gm + ((long)y * W + x) * 8;
         float* o = out + (long)idx * 9;
         const double xs = (double)x * scale, ys = (double)y * scale;  // int64 * float -> f64
 #pragma unroll
@@ -77,14 +65,9 @@ __global__ __launch_bounds__(1024) void east_decode_kernel(const float* __restri
         o[8] = sm[(long)y * W + x];
       }
     }
-    __syncthreads();
-    if (tid == 0) base_s += tot;
-    __syncthreads();
+    base += tot;
   }
-  if (tid == 0) {
-    const int total = base_s;
-    count[n] = total > max_cand ? (max_cand | (int)0x80000000) : total;
-  }
+  if (tid == 0) count[n] = base > max_cand ? (max_cand | (int)0x80000000) : base;
 }
 
 extern "C" int msocr_east_decode(const float* score, const float* geo, int N, int H, int W, float thresh, float scale, int quant,
@@ -99,7 +82,7 @@ extern "C" int msocr_east_decode(const float* score, const float* geo, int N, in
 // ------------------------------------------------------------------------------------------ fp64 geometry
 #define MAXV 20  // lanms.py:34
 
-__device__ double d_polygon_area(const double* poly, int n) {  // lanms.py:7-14
+__device__ __forceinline__ double d_polygon_area(const double* poly, int n) {  // lanms.py:7-14
   double area = 0.0;
   for (int i = 0; i < n; i++) {
     const int j = (i + 1) % n;
@@ -107,6 +90,7 @@ __device__ double d_polygon_area(const double* poly, int n) {  // lanms.py:7-14
   }
   return fabs(area) / 2.0;
 }
+__device__ __forceinline__ double d_quad_area(const double* q) { return d_polygon_area(q, 4); }  // unrolls, indices static
 
 __device__ void d_compute_intersection(const double* p1, const double* p2, const double* A, const double* B, double* out) {  // :17-29
   const double BAx = p2[0] - p1[0], BAy = p2[1] - p1[1];
@@ -162,7 +146,7 @@ __device__ double d_polygon_iou(const double* poly1, const double* poly2) {  // 
   }
   double inter_area = 0.0;
   if (cnt > 2) inter_area = d_polygon_area(cur, cnt);
-  const double area1 = d_polygon_area(poly1, 4), area2 = d_polygon_area(poly2, 4);
+  const double area1 = d_quad_area(poly1), area2 = d_quad_area(poly2);
   const double union_area = area1 + area2 - inter_area;
   if (union_area <= 0) return 0.0;
   return inter_area / union_area;
@@ -291,14 +275,7 @@ __device__ __forceinline__ bool d_polygon_iou_fast(const double* poly1, const do
   if (over) return false;
   double inter_area = 0.0;
   if (cnt > 2) inter_area = in_a ? p8_area(a) : p8_area(b);
-  double s1 = 0.0, s2 = 0.0;  // polygon_area of the two quads (lanms.py:7-14)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int j = (i + 1) & 3;
-    s1 += poly1[2 * i] * poly1[2 * j + 1] - poly1[2 * j] * poly1[2 * i + 1];
-    s2 += poly2[2 * i] * poly2[2 * j + 1] - poly2[2 * j] * poly2[2 * i + 1];
-  }
-  const double area1 = fabs(s1) / 2.0, area2 = fabs(s2) / 2.0;
+  const double area1 = d_quad_area(poly1), area2 = d_quad_area(poly2);
   const double union_area = area1 + area2 - inter_area;
   *iou = union_area <= 0 ? 0.0 : inter_area / union_area;
   return true;
@@ -313,35 +290,22 @@ __device__ __forceinline__ double d_polygon_iou_q(const double* poly1, const dou
 __device__ void d_normalize_polygon(const double* ref, const double* poly, double* out) {  // :99-130
   int best_order = 0, best_start = 0;
   double min_d = 1e20;
-  for (int start = 0; start < 4; start++) {
-    double d = 0.0;
-    for (int i = 0; i < 4; i++) {
-      const int idx = (start + i) & 3;
-      const double dx = ref[2 * i] - poly[2 * idx], dy = ref[2 * i + 1] - poly[2 * idx + 1];
-      d += dx * dx + dy * dy;
+  for (int order = 0; order < 2; order++)  // the four rotations forwards, then the four backwards
+    for (int start = 0; start < 4; start++) {
+      double d = 0.0;
+      for (int i = 0; i < 4; i++) {
+        const int idx = order == 0 ? (start + i) & 3 : (start - i) & 3;
+        const double dx = ref[2 * i] - poly[2 * idx], dy = ref[2 * i + 1] - poly[2 * idx + 1];
+        d += dx * dx + dy * dy;
+      }
+      if (d < min_d) { min_d = d; best_start = start; best_order = order; }
     }
-    if (d < min_d) { min_d = d; best_start = start; best_order = 0; }
-  }
-  for (int start = 0; start < 4; start++) {
-    double d = 0.0;
-    for (int i = 0; i < 4; i++) {
-      const int idx = (start - i) & 3;
-      const double dx = ref[2 * i] - poly[2 * idx], dy = ref[2 * i + 1] - poly[2 * idx + 1];
-      d += dx * dx + dy * dy;
-    }
-    if (d < min_d) { min_d = d; best_start = start; best_order = 1; }
-  }
   for (int i = 0; i < 4; i++) {
     const int idx = best_order == 0 ? (best_start + i) & 3 : (best_start - i) & 3;
     out[2 * i] = poly[2 * idx];
     out[2 * i + 1] = poly[2 * idx + 1];
   }
 }
-
-// total order used for both sorts: ascending key, NaN last, ties by original index (stable).
-// (np.argsort's default sort is unstable: the reference leaves tie order implementation-defined.)
-template <typename K>
-__device__ __forceinline__ bool key_less(K a, K b) { return a < b || (b != b && a == a); }
 
 // ------------------------------------------------------------------------------------------ LANMS
 // One workgroup (LANMS_PAGE_T = 768 threads) per page.
@@ -360,33 +324,53 @@ __device__ __forceinline__ bool key_less(K a, K b) { return a < b || (b != b && 
 //      LAST candidate (unique), replacing the speculative emissions of that prefix;
 //   D. the flagged slots are compacted in order.
 // Every floating-point operation is the reference's, in the reference's order, so results are bit-identical.
-//
-// workspace layout per page (8-byte aligned blocks):
-//   mpoly  f64[max_cand*8], mscore f64[max_cand]   compacted merged polygons (phase 1 output)
-//   spoly  f64[max_cand*8], sscore f64[max_cand]   staged slots (by last candidate)
-//   carry  f64[3][1024][11]                        spec / current / next carry states (poly, weight, score, valid)
-//   order  i32[max_cand], supp i32[max_cand], flag i32[max_cand], sbreak i32[max_cand]
-#define LANMS_T 1024
 #define CARRY_W 11
+#define LANMS_CARRY_SLOTS 1024  // carry slots per carry array, one per page-kernel thread; part of the workspace layout
 // page-kernel threads: 3 waves per SIMD = 168 VGPRs per lane, enough for the register-resident polygon clip (at 1024 threads =
 // 128 VGPRs it spills and the carry fix-up rounds get slower).  Measured on a 13 k-candidate page, phase 1 + score sort: 1024
 // threads with the old scratch-buffer clip 2.6 ms; 1024 / 768 / 512 / 256 threads with the register clip 2.3 / 1.7 / 2.1 / 2.7 ms.
 #define LANMS_PAGE_T 768
+static_assert(LANMS_PAGE_T <= LANMS_CARRY_SLOTS, "one carry slot per thread");
 // phase 2 across the chip: pages with at most NMS_BITCAP merged polygons get their "IoU > thr" relation as a bit matrix
 // computed by many workgroups (lanms_iou_bits_kernel) and a single wave then replays the greedy pass on the bits
 #define NMS_BITCAP 8192
 #define NMS_BITW (NMS_BITCAP / 32)
-static inline int64_t lanms_bits_off(int max_cand) {
-  return ((int64_t)max_cand * (2 * (64 + 8) + 4 * 4) + (int64_t)3 * LANMS_T * CARRY_W * 8 + 64 + 63) / 64 * 64;
+__host__ __device__ inline int nms_bitcap(int max_cand) { return ((max_cand < NMS_BITCAP ? max_cand : NMS_BITCAP) + 31) / 32 * 32; }
+
+// The workspace of one page, in layout order (c = max_cand; every block starts 8-byte aligned, nm 64-byte aligned):
+struct LanmsWs {
+  double *mpoly, *mscore;                      // f64[c * 8], f64[c]   compacted merged polygons (phase 1 output)
+  double *spoly, *sscore;                      // f64[c * 8], f64[c]   staged slots (by last candidate)
+  double *carry_spec, *carry_cur, *carry_nxt;  // f64[LANMS_CARRY_SLOTS][CARRY_W] each: poly, weight, score, valid
+  int32_t* order;                              // i32[c]   x0 order, later the score order of the merged polygons
+  int32_t* supp;                               // i32[c]   suppressed flags of the in-kernel greedy pass ...
+  int32_t* rank_x0;                            // == supp: before that, the x0 rank accumulator of lanms_zero / lanms_rank_x0_kernel
+  int32_t *flag, *sbreak;                      // i32[c] each
+  int32_t* nm;                                 // 64-byte header {merged polygons for the bit-matrix path, or -1}
+  uint32_t* bits;                              // u32[bitcap][bitcap / 32]   bit matrix, bitcap = nms_bitcap(c)
+  int64_t page_bytes;                          // the distance between two pages' workspaces
+};
+// The one statement of the layout: blocks carved in order at integer byte offsets.  SIZE_ONLY forms no pointers (page_bytes alone).
+template <bool SIZE_ONLY = false>
+__host__ __device__ inline LanmsWs lanms_ws(char* page, int max_cand) {
+  const int64_t c = max_cand, cw = LANMS_CARRY_SLOTS * CARRY_W * 8, cap = nms_bitcap(max_cand);
+  int64_t off = 0;
+  auto f64 = [&](int64_t bytes) { char* p = SIZE_ONLY ? nullptr : page + off; off += bytes; return reinterpret_cast<double*>(p); };
+  auto i32 = [&](int64_t bytes) { return reinterpret_cast<int32_t*>(f64(bytes)); };
+  LanmsWs L;
+  L.mpoly = f64(c * 64); L.mscore = f64(c * 8); L.spoly = f64(c * 64); L.sscore = f64(c * 8);
+  L.carry_spec = f64(cw); L.carry_cur = f64(cw); L.carry_nxt = f64(cw);
+  L.order = i32(c * 4); L.supp = L.rank_x0 = i32(c * 4); L.flag = i32(c * 4); L.sbreak = i32(c * 4);
+  off = (off + 64 + 63) / 64 * 64;
+  L.nm = i32(64);
+  L.bits = reinterpret_cast<uint32_t*>(i32(cap * (cap / 32) * 4));
+  L.page_bytes = (off + 63) / 64 * 64;
+  return L;
 }
-static inline int nms_bitcap(int max_cand) { return ((max_cand < NMS_BITCAP ? max_cand : NMS_BITCAP) + 31) / 32 * 32; }
-static inline int64_t lanms_ws_per_page(int max_cand) {
-  const int64_t cap = nms_bitcap(max_cand);
-  return lanms_bits_off(max_cand) + cap * (cap / 32) * 4 + 64;  // ... + bit matrix [cap][cap/32] u32 + {nm} header
-}
+static inline int64_t lanms_ws_page_bytes(int max_cand) { return lanms_ws<true>(nullptr, max_cand).page_bytes; }
 extern "C" int64_t msocr_lanms_workspace_bytes(int N, int max_cand) {
   if (N <= 0 || max_cand <= 0) return 0;
-  return (lanms_ws_per_page(max_cand) + 63) / 64 * 64 * N;
+  return lanms_ws_page_bytes(max_cand) * N;
 }
 
 // Order-preserving integer images of the sort keys: ascending float order, -0 == +0, every NaN last; the original
@@ -409,23 +393,23 @@ __device__ __forceinline__ unsigned long long sortable_f64(double x) {
 #define RS_Q 8
 // x0 sort of every page's candidates, spread over the whole chip: grid (i chunks, j chunks, pages).  A workgroup counts, for its
 // 256*RS_Q candidates, how many of ITS RS_TILE candidates j sort before them (keys staged through LDS as 64-bit (key, index)
-// words) and adds that partial rank into rank_acc (zeroed by lanms_zero_kernel); the page kernel then scatters order[rank] = i.
+// words) and adds that partial rank into LanmsWs::rank_x0 (zeroed by lanms_zero_kernel); the page kernel then scatters order[rank] = i.
 // (Round 1 ran one workgroup per i chunk over ALL j: 5 workgroups per 10 k-candidate page, 0.59 ms; the 2-D split is ~n/2048
 // times more parallel.)
-__global__ __launch_bounds__(256) void lanms_zero_kernel(const int32_t* __restrict__ counts, char* __restrict__ ws, long ws_stride, long acc_off) {
+__global__ __launch_bounds__(256) void lanms_zero_kernel(const int32_t* __restrict__ counts, char* __restrict__ ws, long ws_stride, int max_cand) {
   const int pg = blockIdx.y;
   const int n = counts[pg] & 0x7fffffff;
-  int32_t* acc = reinterpret_cast<int32_t*>(ws + (long)pg * ws_stride + acc_off);
+  int32_t* acc = lanms_ws(ws + (long)pg * ws_stride, max_cand).rank_x0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) acc[i] = 0;
 }
 __global__ __launch_bounds__(256) void lanms_rank_x0_kernel(const float* __restrict__ cand, const int32_t* __restrict__ counts,
-                                                             int max_cand, char* __restrict__ ws, long ws_stride, long acc_off) {
+                                                             int max_cand, char* __restrict__ ws, long ws_stride) {
   const int pg = blockIdx.z, tid = threadIdx.x;
   const int n = counts[pg] & 0x7fffffff;
   const int i0 = blockIdx.x * 256 * RS_Q, j0 = blockIdx.y * RS_TILE;
   if (i0 >= n || j0 >= n) return;
   const float* cb = cand + (long)pg * max_cand * 9;
-  int32_t* acc = reinterpret_cast<int32_t*>(ws + (long)pg * ws_stride + acc_off);
+  int32_t* acc = lanms_ws(ws + (long)pg * ws_stride, max_cand).rank_x0;
   __shared__ unsigned long long tile[RS_TILE];
   unsigned long long ki[RS_Q];
   int rank[RS_Q];
@@ -518,253 +502,218 @@ __device__ __forceinline__ bool merge_step(MergeState& st, const float* b, doubl
   return true;
 }
 
-// LANMS_PAGE_T threads per page (workspace carries are laid out for LANMS_T >= LANMS_PAGE_T)
+// ---- the phases of east_lanms_kernel (described above the workspace layout); seg0 .. seg1 is the calling thread's segment ----
+// a closed polygon goes into the slot of its LAST candidate
+__device__ __forceinline__ void lanms_emit(const LanmsWs& L, int slot, const MergeState& closed) {
+  for (int k = 0; k < 8; ++k) L.spoly[(long)slot * 8 + k] = closed.p[k];
+  L.sscore[slot] = closed.sc;
+  L.flag[slot] = 1;
+}
+// A. speculative scan from EMPTY: records the breaks, emits the polygons it closes, leaves its open polygon as both carries
+__device__ __forceinline__ void lanms_scan_speculative(const LanmsWs& L, const float* cb, int seg0, int seg1, double thr) {
+  MergeState st = {};
+  for (int s = seg0; s < seg1; ++s) {
+    MergeState closed = {};
+    if (merge_step(st, cb + (long)L.order[s] * 9, thr, &closed)) {
+      L.sbreak[s] = 1;
+      if (closed.valid) lanms_emit(L, s - 1, closed);  // polygon that ended at candidate s-1
+    }
+  }
+  st_store(st, L.carry_spec + threadIdx.x * CARRY_W);
+  st_store(st, L.carry_cur + threadIdx.x * CARRY_W);
+}
+// Re-scan of a segment from its true incoming state `st` until it starts a polygon where the speculative scan also started one
+// (returns true: from there the speculative tail is the true tail) or the segment ends (false; st = the true outgoing state).
+// EMIT: the true scan's emissions replace the speculative ones of the prefix (seg0 >= 1: segment 0 never re-scans).
+template <bool EMIT>
+__device__ __forceinline__ bool lanms_rescan(const LanmsWs& L, const float* cb, int seg0, int seg1, double thr, MergeState& st) {
+  for (int s = seg0; s < seg1; ++s) {
+    MergeState closed = {};
+    const bool brk = merge_step(st, cb + (long)L.order[s] * 9, thr, EMIT ? &closed : nullptr);
+    if (EMIT) {
+      if (brk && closed.valid) lanms_emit(L, s - 1, closed);
+      else L.flag[s - 1] = 0;  // a speculative emission that the true scan does not make
+    }
+    if (brk && L.sbreak[s]) return true;
+  }
+  return false;
+}
+// B. fixed point of the carries (thread 0's carry is already true: its incoming state IS empty)
+__device__ __forceinline__ void lanms_settle_carries(const LanmsWs& L, const float* cb, int seg0, int seg1, double thr, int S,
+                                                     int* any_changed, unsigned char* ch_s) {
+  const int tid = threadIdx.x;
+  int in_dirty = tid > 0 && tid < S;  // my incoming carry has not been consumed yet
+  for (int round = 0; round < S; ++round) {
+    int changed = 0;
+    if (in_dirty) {
+      MergeState st = {};
+      st_load(st, L.carry_cur + (tid - 1) * CARRY_W);
+      if (lanms_rescan<false>(L, cb, seg0, seg1, thr, st)) st_load(st, L.carry_spec + tid * CARRY_W);
+      changed = !st_same(st, L.carry_cur + tid * CARRY_W);
+      if (changed) st_store(st, L.carry_nxt + tid * CARRY_W);
+    }
+    ch_s[tid] = (unsigned char)changed;
+    if (changed) atomicOr(any_changed, 1);
+    __syncthreads();  // every thread has read its predecessor's carry_cur and published `changed`
+    const int any = *any_changed;
+    if (changed)
+      for (int k = 0; k < CARRY_W; ++k) L.carry_cur[tid * CARRY_W + k] = L.carry_nxt[tid * CARRY_W + k];
+    in_dirty = tid > 0 && tid < S && ch_s[tid - 1];
+    __syncthreads();
+    if (tid == 0) *any_changed = 0;
+    __syncthreads();
+    if (!any) break;
+  }
+}
+// C. replay the true prefix of the segment, emitting closed polygons into their slots; the last segment closes the page
+__device__ __forceinline__ void lanms_replay_prefix(const LanmsWs& L, const float* cb, int seg0, int seg1, double thr, int S, int n) {
+  const int tid = threadIdx.x;
+  MergeState st = {};
+  bool resync = (tid == 0);  // segment 0's speculative scan is the true scan
+  if (!resync) {
+    st_load(st, L.carry_cur + (tid - 1) * CARRY_W);
+    resync = lanms_rescan<true>(L, cb, seg0, seg1, thr, st);
+  }
+  if (tid == S - 1) {  // the last open polygon of the page ends at candidate n-1
+    if (resync) st_load(st, L.carry_spec + tid * CARRY_W);
+    lanms_emit(L, n - 1, st);
+  }
+}
+// D. ordered compaction of the flagged slots into mpoly / mscore; returns the number of merged polygons
+__device__ __forceinline__ int lanms_compact(const LanmsWs& L, int n, int* scan_s) {
+  const int per = (n + LANMS_PAGE_T - 1) / LANMS_PAGE_T, a0 = threadIdx.x * per, a1 = min(n, a0 + per);
+  int cnt = 0;
+  for (int s = a0; s < a1; ++s) cnt += L.flag[s];
+  int nm, pos = block_exclusive_scan<LANMS_PAGE_T>(cnt, scan_s, &nm);
+  for (int s = a0; s < a1; ++s)
+    if (L.flag[s]) {
+      for (int k = 0; k < 8; ++k) L.mpoly[(long)pos * 8 + k] = L.spoly[(long)s * 8 + k];
+      L.mscore[pos] = L.sscore[s];
+      ++pos;
+    }
+  __syncthreads();
+  return nm;
+}
+// greedy suppression (lanms.py:141-152) inside the page kernel, for pages with more merged polygons than the bit matrix holds:
+// kept rows to ob in kept order; returns their number
+__device__ __forceinline__ int lanms_greedy_in_kernel(const LanmsWs& L, int nm, double thr, float* ob) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < nm; i += LANMS_PAGE_T) L.supp[i] = 0;
+  __syncthreads();
+  int nk = 0;  // kept count (every thread tracks it; thread 0 writes the kept polygon's row)
+  for (int i = 0; i < nm; ++i) {
+    const int idx = L.order[i];
+    if (L.supp[idx]) continue;  // uniform: written before the barrier that ended an earlier iteration
+    double a[8];
+    for (int k = 0; k < 8; ++k) a[k] = L.mpoly[(long)idx * 8 + k];
+    if (tid == 0) {
+      float* o = ob + (long)nk * 9;
+      for (int k = 0; k < 8; ++k) o[k] = (float)a[k];
+      o[8] = (float)L.mscore[idx];
+    }
+    ++nk;
+    for (int j = i + 1 + tid; j < nm; j += LANMS_PAGE_T) {
+      const int idj = L.order[j];
+      if (L.supp[idj]) continue;
+      if (d_polygon_iou_q(a, L.mpoly + (long)idj * 8) > thr) L.supp[idj] = 1;
+    }
+    __syncthreads();
+  }
+  return nk;
+}
+
 __global__ __launch_bounds__(LANMS_PAGE_T) void east_lanms_kernel(const float* __restrict__ cand, const int32_t* __restrict__ counts,
                                                                   int max_cand, double thr, float* __restrict__ boxes_out,
                                                                   int32_t* __restrict__ nbox_out, char* __restrict__ ws, long ws_stride,
-                                                                  long bits_off, int bitcap) {
-  const int pg = blockIdx.x;
-  const int tid = threadIdx.x, nthr = LANMS_PAGE_T;
+                                                                  int bitcap) {
+  const int pg = blockIdx.x, tid = threadIdx.x, nthr = LANMS_PAGE_T;
   const float* cb = cand + (long)pg * max_cand * 9;
   const int n = counts[pg] & 0x7fffffff;
-  char* w = ws + (long)pg * ws_stride;
-  double* mpoly = reinterpret_cast<double*>(w);
-  double* mscore = mpoly + (long)max_cand * 8;
-  double* spoly = mscore + max_cand;
-  double* sscore = spoly + (long)max_cand * 8;
-  double* carry_spec = sscore + max_cand;
-  double* carry_cur = carry_spec + LANMS_T * CARRY_W;
-  double* carry_nxt = carry_cur + LANMS_T * CARRY_W;
-  int32_t* order = reinterpret_cast<int32_t*>(carry_nxt + LANMS_T * CARRY_W);
-  int32_t* supp = order + max_cand;
-  int32_t* flag = supp + max_cand;
-  int32_t* sbreak = flag + max_cand;
-  float* ob = boxes_out + (long)pg * max_cand * 9;
-  __shared__ int nm_s, nk_s, any_changed;
+  const LanmsWs L = lanms_ws(ws + (long)pg * ws_stride, max_cand);
+  __shared__ int any_changed;
   __shared__ int scan_s[LANMS_PAGE_T / 64];
   __shared__ unsigned char ch_s[LANMS_PAGE_T];
-
-  int32_t* nm_hdr = reinterpret_cast<int32_t*>(w + bits_off);  // {merged polygons for the bit-matrix path, or -1}
+  __shared__ unsigned long long rs_tile[RS_TILE];
   if (n == 0) {
-    if (tid == 0) { nbox_out[pg] = 0; nm_hdr[0] = -1; }
+    if (tid == 0) { nbox_out[pg] = 0; L.nm[0] = -1; }
     return;
   }
-  // ---- `supp` holds every candidate's rank in the stable argsort by x0 (lanms.py:166-168), accumulated by lanms_rank_x0_kernel
-  __shared__ unsigned long long rs_tile[RS_TILE];
+  // ---- rank_x0 holds every candidate's rank in the stable argsort by x0 (lanms.py:166-168), accumulated by lanms_rank_x0_kernel
   for (int i = tid; i < n; i += nthr) {
-    order[supp[i]] = i;
-    flag[i] = 0;
-    sbreak[i] = 0;
+    L.order[L.rank_x0[i]] = i;
+    L.flag[i] = 0;
+    L.sbreak[i] = 0;
   }
   __threadfence();
   __syncthreads();
   // ---- phase 1: speculative segmented scan -------------------------------------------------------------
   int S = (n + 7) / 8;  // >= 8 candidates per segment
   if (S > nthr) S = nthr;
-  const int L = (n + S - 1) / S;
-  S = (n + L - 1) / L;
-  const int seg0 = tid * L, seg1 = min(n, seg0 + L);
+  const int seg_len = (n + S - 1) / S;
+  S = (n + seg_len - 1) / seg_len;
+  const int seg0 = tid * seg_len, seg1 = min(n, seg0 + seg_len);
   const bool active = tid < S;
-  // A. speculative scan from EMPTY
-  if (active) {
-    MergeState st = {};
-    for (int s = seg0; s < seg1; ++s) {
-      MergeState closed = {};
-      if (merge_step(st, cb + (long)order[s] * 9, thr, &closed)) {
-        sbreak[s] = 1;
-        if (closed.valid) {  // polygon that ended at candidate s-1
-          for (int k = 0; k < 8; ++k) spoly[(long)(s - 1) * 8 + k] = closed.p[k];
-          sscore[s - 1] = closed.sc;
-          flag[s - 1] = 1;
-        }
-      }
-    }
-    st_store(st, carry_spec + tid * CARRY_W);
-    st_store(st, carry_cur + tid * CARRY_W);
-  }
+  if (active) lanms_scan_speculative(L, cb, seg0, seg1, thr);
   if (tid == 0) any_changed = 0;
   __syncthreads();
-  // B. fixed point of the carries (thread 0's carry is already true: its incoming state IS empty)
-  int in_dirty = active && tid > 0;  // my incoming carry has not been consumed yet
-  for (int round = 0; round < S; ++round) {
-    int changed = 0;
-    if (in_dirty) {
-      MergeState st = {};
-      st_load(st, carry_cur + (tid - 1) * CARRY_W);
-      bool resync = false;
-      for (int s = seg0; s < seg1; ++s) {
-        if (merge_step(st, cb + (long)order[s] * 9, thr, nullptr) && sbreak[s]) {
-          resync = true;
-          break;
-        }
-      }
-      if (resync) st_load(st, carry_spec + tid * CARRY_W);
-      changed = !st_same(st, carry_cur + tid * CARRY_W);
-      if (changed) st_store(st, carry_nxt + tid * CARRY_W);
-    }
-    ch_s[tid] = (unsigned char)changed;
-    if (changed) atomicOr(&any_changed, 1);
-    __syncthreads();  // every thread has read its predecessor's carry_cur and published `changed`
-    const int any = any_changed;
-    if (changed)
-      for (int k = 0; k < CARRY_W; ++k) carry_cur[tid * CARRY_W + k] = carry_nxt[tid * CARRY_W + k];
-    in_dirty = active && tid > 0 && ch_s[tid - 1];
-    __syncthreads();
-    if (tid == 0) any_changed = 0;
-    __syncthreads();
-    if (!any) break;
-  }
-  // C. replay the true prefix of every segment, emitting closed polygons into their slots
-  if (active) {
-    MergeState st = {};
-    if (tid > 0) st_load(st, carry_cur + (tid - 1) * CARRY_W);
-    bool resync = (tid == 0);  // segment 0's speculative scan is the true scan
-    for (int s = seg0; s < seg1 && !resync; ++s) {
-      MergeState closed = {};
-      const bool brk = merge_step(st, cb + (long)order[s] * 9, thr, &closed);
-      if (s > 0) {
-        if (brk && closed.valid) {
-          for (int k = 0; k < 8; ++k) spoly[(long)(s - 1) * 8 + k] = closed.p[k];
-          sscore[s - 1] = closed.sc;
-          flag[s - 1] = 1;
-        } else {
-          flag[s - 1] = 0;  // a speculative emission that the true scan does not make
-        }
-      }
-      if (brk && sbreak[s]) resync = true;
-    }
-    if (tid == S - 1) {  // the last open polygon of the page ends at candidate n-1
-      MergeState fin = st;
-      if (resync) st_load(fin, carry_spec + tid * CARRY_W);
-      for (int k = 0; k < 8; ++k) spoly[(long)(n - 1) * 8 + k] = fin.p[k];
-      sscore[n - 1] = fin.sc;
-      flag[n - 1] = 1;
-    }
-  }
+  lanms_settle_carries(L, cb, seg0, seg1, thr, S, &any_changed, ch_s);
+  if (active) lanms_replay_prefix(L, cb, seg0, seg1, thr, S, n);
   __syncthreads();
-  // D. ordered compaction of the flagged slots
-  {
-    const int per = (n + nthr - 1) / nthr;
-    const int a0 = tid * per, a1 = min(n, a0 + per);
-    int cnt = 0;
-    for (int s = a0; s < a1; ++s) cnt += flag[s];
-    const int lane = tid & 63, wv = tid >> 6;
-    int inc = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o);
-      if (lane >= o) inc += v;
-    }
-    if (lane == 63) scan_s[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int q = 0; q < wv; ++q) base += scan_s[q];
-    int pos = base + inc - cnt;
-    for (int s = a0; s < a1; ++s)
-      if (flag[s]) {
-        for (int k = 0; k < 8; ++k) mpoly[(long)pos * 8 + k] = spoly[(long)s * 8 + k];
-        mscore[pos] = sscore[s];
-        ++pos;
-      }
-    if (tid == nthr - 1) nm_s = base + inc;
-  }
-  __syncthreads();
-  const int nm = nm_s;
+  const int nm = lanms_compact(L, n, scan_s);
   // ---- phase 2: order = argsort(-score) (stable), greedy suppression (lanms.py:133-153)
-  block_rank_sort_neg_f64(nm, mscore, order, rs_tile);
+  block_rank_sort_neg_f64(nm, L.mscore, L.order, rs_tile);
   if (nm <= bitcap) {  // greedy suppression continues in lanms_iou_bits_kernel + lanms_greedy_bits_kernel
-    if (tid == 0) nm_hdr[0] = nm;
+    if (tid == 0) L.nm[0] = nm;
     return;
   }
-  if (tid == 0) nm_hdr[0] = -1;
-  for (int i = tid; i < nm; i += nthr) supp[i] = 0;
-  __syncthreads();
-  int nk = 0;  // kept count (every thread tracks it; thread 0 writes the kept polygon's row)
-  for (int i = 0; i < nm; ++i) {
-    const int idx = order[i];
-    if (supp[idx]) continue;  // uniform: written before the barrier that ended an earlier iteration
-    double a[8];
-    for (int k = 0; k < 8; ++k) a[k] = mpoly[(long)idx * 8 + k];
-    if (tid == 0) {
-      float* o = ob + (long)nk * 9;
-      for (int k = 0; k < 8; ++k) o[k] = (float)a[k];
-      o[8] = (float)mscore[idx];
-    }
-    ++nk;
-    for (int j = i + 1 + tid; j < nm; j += nthr) {
-      const int idj = order[j];
-      if (supp[idj]) continue;
-      if (d_polygon_iou_q(a, mpoly + (long)idj * 8) > thr) supp[idj] = 1;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) nk_s = nk;
-  if (tid == 0) nbox_out[pg] = nk_s;
+  if (tid == 0) L.nm[0] = -1;
+  const int nk = lanms_greedy_in_kernel(L, nm, thr, boxes_out + (long)pg * max_cand * 9);
+  if (tid == 0) nbox_out[pg] = nk;
 }
 
 // bit j of bits[i][w] (j = 32w + b > i, sorted positions): polygon_iou(poly_i, poly_j) > thr, the test of lanms.py:147-150 with
 // the same argument order.  grid (row blocks of 8, pages), 256 threads: thread = (row, word) pairs in a strided loop.
-__global__ __launch_bounds__(256) void lanms_iou_bits_kernel(char* __restrict__ ws, long ws_stride, int max_cand, double thr, long bits_off,
-                                                              int bitcap) {
-  const int pg = blockIdx.y;
-  char* w = ws + (long)pg * ws_stride;
-  const int nm = reinterpret_cast<const int32_t*>(w + bits_off)[0];
+__global__ __launch_bounds__(256) void lanms_iou_bits_kernel(char* __restrict__ ws, long ws_stride, int max_cand, double thr, int bitcap) {
+  const LanmsWs L = lanms_ws(ws + (long)blockIdx.y * ws_stride, max_cand);
+  const int nm = L.nm[0];
   if (nm <= 0) return;
   const int W = (nm + 31) >> 5, capw = bitcap >> 5;
-  const double* mpoly = reinterpret_cast<const double*>(w);
-  const int32_t* order = reinterpret_cast<const int32_t*>(w + ((long)max_cand * (2 * (64 + 8)) + (long)3 * LANMS_T * CARRY_W * 8));
-  uint32_t* bits = reinterpret_cast<uint32_t*>(w + bits_off + 64);
   const long total = (long)nm * W;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const int i = (int)(idx / W), wd = (int)(idx - (long)i * W);
     uint32_t v = 0u;
     if (32 * wd + 31 > i) {
       double a[8];
-      const double* pa = mpoly + (long)order[i] * 8;
+      const double* pa = L.mpoly + (long)L.order[i] * 8;
       for (int k = 0; k < 8; ++k) a[k] = pa[k];
       for (int b = 0; b < 32; ++b) {
         const int j = 32 * wd + b;
-        if (j > i && j < nm && d_polygon_iou_q(a, mpoly + (long)order[j] * 8) > thr) v |= 1u << b;
+        if (j > i && j < nm && d_polygon_iou_q(a, L.mpoly + (long)L.order[j] * 8) > thr) v |= 1u << b;
       }
     }
-    bits[(long)i * capw + wd] = v;
+    L.bits[(long)i * capw + wd] = v;
   }
 }
 
 // the greedy pass of standard_nms (lanms.py:141-152) on the bit matrix: one wave per page, lane l owns the suppression words
 // l, l + 64, ...; a kept polygon ORs its row into them.  Output rows in kept order, like the reference's `keep` list.
-__global__ __launch_bounds__(64) void lanms_greedy_bits_kernel(char* __restrict__ ws, long ws_stride, int max_cand, long bits_off, int bitcap,
+__global__ __launch_bounds__(64) void lanms_greedy_bits_kernel(char* __restrict__ ws, long ws_stride, int max_cand, int bitcap,
                                                                 float* __restrict__ boxes_out, int32_t* __restrict__ nbox_out) {
   const int pg = blockIdx.x, lane = threadIdx.x;
-  char* w = ws + (long)pg * ws_stride;
-  const int nm = reinterpret_cast<const int32_t*>(w + bits_off)[0];
+  const LanmsWs L = lanms_ws(ws + (long)pg * ws_stride, max_cand);
+  const int nm = L.nm[0];
   if (nm <= 0) return;  // n == 0 or the in-kernel path: nbox_out is already written
   const int W = (nm + 31) >> 5, capw = bitcap >> 5;
-  const double* mpoly = reinterpret_cast<const double*>(w);
-  const double* mscore = mpoly + (long)max_cand * 8;
-  const int32_t* order = reinterpret_cast<const int32_t*>(w + ((long)max_cand * (2 * (64 + 8)) + (long)3 * LANMS_T * CARRY_W * 8));
-  const uint32_t* bits = reinterpret_cast<const uint32_t*>(w + bits_off + 64);
   float* ob = boxes_out + (long)pg * max_cand * 9;
-  constexpr int KW = NMS_BITW / 64;
-  uint32_t sup[KW];
-#pragma unroll
-  for (int k = 0; k < KW; ++k) sup[k] = 0u;
+  LaneBits<NMS_BITW / 64> sup;
+  sup.fill(0u);
   int nk = 0;
   for (int i = 0; i < nm; ++i) {
-    const int wi = i >> 5, owner = wi & 63, slot = wi >> 6;
-    uint32_t mine = 0u;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) mine = (k == slot) ? sup[k] : mine;
-    const uint32_t word = __shfl(mine, owner);
-    if ((word >> (i & 31)) & 1u) continue;  // suppressed (wave-uniform)
-    const int idx = order[i];
-    if (lane < 9) ob[(long)nk * 9 + lane] = lane < 8 ? (float)mpoly[(long)idx * 8 + lane] : (float)mscore[idx];
+    if (sup.test(i)) continue;  // suppressed (wave-uniform)
+    const int idx = L.order[i];
+    if (lane < 9) ob[(long)nk * 9 + lane] = lane < 8 ? (float)L.mpoly[(long)idx * 8 + lane] : (float)L.mscore[idx];
     ++nk;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) {
-      const int wd = lane + 64 * k;
-      if (wd < W) sup[k] |= bits[(long)i * capw + wd];
-    }
+    sup.or_row(L.bits + (long)i * capw, W);
   }
   if (lane == 0) nbox_out[pg] = nk;
 }
@@ -773,32 +722,20 @@ extern "C" int msocr_east_lanms(const float* cand, const int32_t* counts, int N,
                                 int32_t* nbox_out, void* workspace, void* stream) {
   if (!cand || !counts || !boxes_out || !nbox_out || !workspace || N <= 0 || max_cand <= 0) return MSOCR_E_ARG;
   if ((uintptr_t)workspace & 7) return MSOCR_E_ARG;
-  const long stride = (lanms_ws_per_page(max_cand) + 63) / 64 * 64;
-  {
-    // rank accumulator = the `supp` array of the page workspace (order | supp | flag | sbreak, 4 bytes each per candidate)
-    const long acc_off = ((long)max_cand * (2 * (64 + 8)) + (long)3 * LANMS_T * CARRY_W * 8) + (long)max_cand * 4;
-    const int ichunks = (max_cand + 256 * RS_Q - 1) / (256 * RS_Q), jchunks = (max_cand + RS_TILE - 1) / RS_TILE;
-    if (jchunks > 65535 || N > 65535) return MSOCR_E_ARG;
-    MSOCR_LAUNCH(lanms_zero_kernel, dim3(min(ichunks * RS_Q, 64), N), dim3(256), 0, (hipStream_t)stream, counts, (char*)workspace, stride, acc_off);
-    if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
-    MSOCR_LAUNCH(lanms_rank_x0_kernel, dim3(ichunks, jchunks, N), dim3(256), 0, (hipStream_t)stream, cand, counts, max_cand, (char*)workspace,
-                 stride, acc_off);
-    if (hipGetLastError() != hipSuccess) return MSOCR_E_LAUNCH;
-  }
-  const long bits_off = lanms_bits_off(max_cand);
+  const long stride = lanms_ws_page_bytes(max_cand);
+  char* ws = (char*)workspace;
+  const hipStream_t st = (hipStream_t)stream;
+  const int ichunks = (max_cand + 256 * RS_Q - 1) / (256 * RS_Q), jchunks = (max_cand + RS_TILE - 1) / RS_TILE;
+  if (jchunks > 65535 || N > 65535) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(lanms_zero_kernel, dim3(min(ichunks * RS_Q, 64), N), dim3(256), 0, st, counts, ws, stride, max_cand);
+  if (LAUNCH_OK() != MSOCR_OK) return MSOCR_E_LAUNCH;
+  MSOCR_LAUNCH(lanms_rank_x0_kernel, dim3(ichunks, jchunks, N), dim3(256), 0, st, cand, counts, max_cand, ws, stride);
+  if (LAUNCH_OK() != MSOCR_OK) return MSOCR_E_LAUNCH;
   const int bitcap = nms_bitcap(max_cand);
-  MSOCR_LAUNCH(east_lanms_kernel, dim3(N), dim3(LANMS_PAGE_T), 0, (hipStream_t)stream, cand, counts, max_cand, iou_thr, boxes_out, nbox_out,
-               (char*)workspace, stride, bits_off, bitcap);
-  int rc = LAUNCH_OK();
-  if (rc == MSOCR_OK) {
-    MSOCR_LAUNCH(lanms_iou_bits_kernel, dim3(256, N), dim3(256), 0, (hipStream_t)stream, (char*)workspace, stride, max_cand, iou_thr, bits_off,
-                 bitcap);
-    rc = LAUNCH_OK();
-    if (rc == MSOCR_OK) {
-      MSOCR_LAUNCH(lanms_greedy_bits_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, (char*)workspace, stride, max_cand, bits_off, bitcap,
-                   boxes_out, nbox_out);
-      rc = LAUNCH_OK();
-    }
-  }
-  return rc;
+  MSOCR_LAUNCH(east_lanms_kernel, dim3(N), dim3(LANMS_PAGE_T), 0, st, cand, counts, max_cand, iou_thr, boxes_out, nbox_out, ws, stride, bitcap);
+  if (LAUNCH_OK() != MSOCR_OK) return MSOCR_E_LAUNCH;
+  MSOCR_LAUNCH(lanms_iou_bits_kernel, dim3(256, N), dim3(256), 0, st, ws, stride, max_cand, iou_thr, bitcap);
+  if (LAUNCH_OK() != MSOCR_OK) return MSOCR_E_LAUNCH;
+  MSOCR_LAUNCH(lanms_greedy_bits_kernel, dim3(N), dim3(64), 0, st, ws, stride, max_cand, bitcap, boxes_out, nbox_out);
+  return LAUNCH_OK();
 }

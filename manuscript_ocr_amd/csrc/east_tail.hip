@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
 
@@ -291,23 +292,13 @@ __global__ __launch_bounds__(256) void east_box_tail_kernel(const float* __restr
     __syncthreads();
     // greedy pass in ascending-area order (infer.py:203-213): one wave, lane l owns words l, l+64, ... of the keep mask
     if (tid < 64) {
-      uint32_t mykeep[TAIL_KW];
-#pragma unroll
-      for (int k = 0; k < TAIL_KW; ++k) mykeep[k] = keepbits[tid + 64 * k];
+      LaneBits<TAIL_KW> mykeep;
+      mykeep.load(keepbits);
       for (int r = 0; r < M; ++r) {
         const int i = order[r];
-        uint32_t v = 0u;
-#pragma unroll
-        for (int k = 0; k < TAIL_KW; ++k)
-          if (tid + 64 * k < W) v |= inside[(long)i * capw + tid + 64 * k] & mykeep[k];
-        if (__any(v != 0u)) {
-#pragma unroll
-          for (int k = 0; k < TAIL_KW; ++k)
-            if (tid + 64 * k == (i >> 5)) mykeep[k] &= ~(1u << (i & 31));
-        }
+        if (mykeep.and_any(inside + (long)i * capw, W)) mykeep.clear(i);  // box i lies inside a box that is still kept
       }
-#pragma unroll
-      for (int k = 0; k < TAIL_KW; ++k) keepbits[tid + 64 * k] = mykeep[k];
+      mykeep.store(keepbits);
     }
     __syncthreads();
   }

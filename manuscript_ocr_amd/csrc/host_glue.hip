@@ -11,63 +11,59 @@
 
 #include <algorithm>
 #include <map>
+#include <tuple>
 #include <vector>
 
 #include "msocr.h"
+#include "word_boxes.h"
 
 namespace {
-struct Box {
-  long long x0, y0, x1, y1;
-  bool operator<(const Box& o) const {
-    if (x0 != o.x0) return x0 < o.x0;
-    if (y0 != o.y0) return y0 < o.y0;
-    if (x1 != o.x1) return x1 < o.x1;
-    return y1 < o.y1;
-  }
+struct BoxLess {  // the order of the std::map keys (any strict total order of the four coordinates serves)
+  bool operator()(const Box4& a, const Box4& b) const { return std::tie(a.x0, a.y0, a.x1, a.y1) < std::tie(b.x0, b.y0, b.x1, b.y1); }
 };
-inline long long shrink(long long lo, long long hi) { return (long long)((double)hi - (double)(hi - lo) * 0.1); }  // int() truncates
 }  // namespace
 
+// The sequential twin of reading_order_kernel's ordering: box test, shrink and equality are the kernel's (word_boxes.h); sums and
+// differences of coordinates are formed in 64 bits, so it is defined for any int32 boxes.
 extern "C" int msocr_reading_order_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio,
                                         int32_t* order_out_host) {
   if (n < 0 || (n > 0 && (!boxes_host || !order_out_host))) return MSOCR_E_ARG;
   if (n == 0) return MSOCR_OK;
-  std::vector<Box> orig(n), b(n);
-  for (int i = 0; i < n; ++i) orig[i] = b[i] = Box{boxes_host[4 * i], boxes_host[4 * i + 1], boxes_host[4 * i + 2], boxes_host[4 * i + 3]};
+  std::vector<Box4> orig(n), b(n);
+  for (int i = 0; i < n; ++i) orig[i] = b[i] = Box4{boxes_host[4 * i], boxes_host[4 * i + 1], boxes_host[4 * i + 2], boxes_host[4 * i + 3]};
   // resolve_intersections: both members of every intersecting pair shrink by 10 % towards their top-left corner
   for (int sweep = 0; sweep < 50; ++sweep) {
     bool dirty = false;
     for (int i = 0; i < n; ++i)
       for (int j = i + 1; j < n; ++j) {
-        const Box &p = b[i], &q = b[j];
-        if (p.x1 <= q.x0 || q.x1 <= p.x0 || p.y1 <= q.y0 || q.y1 <= p.y0) continue;
-        b[i].x1 = shrink(b[i].x0, b[i].x1); b[i].y1 = shrink(b[i].y0, b[i].y1);
-        b[j].x1 = shrink(b[j].x0, b[j].x1); b[j].y1 = shrink(b[j].y0, b[j].y1);
+        if (!box_hit(b[i], b[j])) continue;
+        box_shrink(b[i]);
+        box_shrink(b[j]);
         dirty = true;
       }
     if (!dirty) break;
   }
   // dict(zip(shrunk, boxes)): identical shrunk boxes collapse, the later original wins;  first word with an equal box
-  std::map<Box, int> back, first;
+  std::map<Box4, int, BoxLess> back, first;
   for (int i = 0; i < n; ++i) back[b[i]] = i;
   for (int i = n - 1; i >= 0; --i) first[orig[i]] = i;
   // sort_boxes_reading_order on the shrunk boxes
   double hsum = 0.0;
-  for (int i = 0; i < n; ++i) hsum += (double)(b[i].y1 - b[i].y0);
+  for (int i = 0; i < n; ++i) hsum += (double)((long long)b[i].y1 - b[i].y0);
   const double avg_h = hsum / n, tol = avg_h * y_tol_ratio, gap = avg_h * x_gap_ratio;
   std::vector<int> idx(n);
   for (int i = 0; i < n; ++i) idx[i] = i;
-  auto cy = [&](int i) { return (double)(b[i].y0 + b[i].y1) / 2.0; };
+  auto cy = [&](int i) { return (double)((long long)b[i].y0 + b[i].y1) / 2.0; };
   std::stable_sort(idx.begin(), idx.end(), [&](int u, int v) { return cy(u) < cy(v); });
   std::vector<std::vector<int>> lines;
   std::vector<double> sums;
-  std::vector<long long> maxx;
+  std::vector<int> maxx;
   for (int i : idx) {
     const double c = cy(i);
     int home = -1;
     for (size_t li = 0; li < lines.size(); ++li) {
       const double line_cy = sums[li] / (double)lines[li].size();
-      if (fabs(c - line_cy) <= tol && (double)(b[i].x0 - maxx[li]) <= gap) { home = (int)li; break; }
+      if (fabs(c - line_cy) <= tol && (double)((long long)b[i].x0 - maxx[li]) <= gap) { home = (int)li; break; }
     }
     if (home < 0) {
       lines.push_back({i}); sums.push_back(c); maxx.push_back(b[i].x1);

@@ -15,8 +15,10 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
+#include "word_boxes.h"
 
 namespace {
 #define HD __host__ __device__ __forceinline__
@@ -36,7 +38,6 @@ HD int32_t f32_bits(float f) {
   return v;
 }
 HD bool finite_f32(float f) { return (f32_bits(f) & 0x7f800000) != 0x7f800000; }
-HD double dmin(double a, double b) { return a < b ? a : b; }
 HD double dmax(double a, double b) { return a > b ? a : b; }
 
 // Canonical corner order of the quad q[8] (x, y pairs as stored) -> c[8]; false when the quad is not usable (a non-finite corner,
@@ -85,11 +86,6 @@ HD void quad_size(const float* c, double* w, double* h) {
   *h = dmax(lft, rgt);
 }
 
-HD int rint_clip(double v, int hi) {  // max(1, rint(v)) clipped to hi, without converting an out-of-range double
-  const double r = rint(v);
-  return r >= (double)hi ? hi : (r >= 1.0 ? (int)r : 1);
-}
-
 // One quad descriptor from the stored corners q[8] and the word's AABB descriptor aabb[8] (msocr_crop_resize_pad's format).
 // natural != 0: the region at its own size (new_w = rint(w), new_h = rint(h), y0 = 0) instead of ResizeAndPadA's fit.
 HD void quad_descriptor(const float* q, const int32_t* aabb, int img_h, int img_w, int natural, int32_t* out) {
@@ -112,12 +108,8 @@ HD void quad_descriptor(const float* q, const int32_t* aabb, int img_h, int img_
     nw = rint_clip(w, 1 << 30);
     nh = rint_clip(h, 1 << 30);
   } else {
-    const double scale = dmin((double)img_h / h, (double)img_w / w);
-    nw = rint_clip(w * scale, img_w);
-    nh = rint_clip(h * scale, img_h);
-    const int t = (img_h - nh) / 2;  // floor division: nh <= img_h
-    yy = t < img_h - nh ? t : img_h - nh;
-    yy = yy > 0 ? yy : 0;
+    const CanvasFit f = canvas_fit(w, h, img_h, img_w);
+    nw = f.new_w; nh = f.new_h; yy = f.y0;
   }
   out[0] = aabb[0];
   for (int k = 0; k < 8; ++k) out[1 + k] = f32_bits(c[k]);
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(QDESC_T) void quad_descriptors_kernel(const float* 
                                                                     const int32_t* __restrict__ order, const int32_t* __restrict__ keep,
                                                                     const int32_t* __restrict__ desc, const int32_t* __restrict__ ncrop,
                                                                     int32_t* __restrict__ qdesc) {
-  const int pg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int pg = blockIdx.x, tid = threadIdx.x;
   const int nc = ncrop[pg];
   int n = nbox[pg];
   if (nc <= 0 || n <= 0) return;  // uniform per workgroup
@@ -215,16 +207,7 @@ __global__ __launch_bounds__(QDESC_T) void quad_descriptors_kernel(const float* 
   const int a0 = min(n, tid * per), a1 = min(n, a0 + per);
   int sum = 0;
   for (int k = a0; k < a1; ++k) sum += ko[k] != 0 ? 1 : 0;
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o);
-    if (lane >= o) inc += v;
-  }
-  if (lane == 63) wave_tot[wv] = inc;
-  __syncthreads();
-  int rank = inc - sum;
-  for (int k = 0; k < wv; ++k) rank += wave_tot[k];
+  int total, rank = block_exclusive_scan<QDESC_T>(sum, wave_tot, &total);
   for (int pos = a0; pos < a1; ++pos) {
     if (ko[pos] == 0) continue;
     if (rank < nc && rank < max_cand) {  // always, for the outputs of msocr_reading_order_crops

@@ -22,48 +22,29 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
+#include "word_boxes.h"
 
 namespace {
 constexpr int RO_T = 1024;         // threads per page
 constexpr int RO_CAP = 16384;      // boxes per page
 constexpr int RO_MAXLINES = 4096;  // text lines per page (line state lives in LDS)
 
-struct Box4 { int x0, y0, x1, y1; };
-
 __host__ __device__ inline int ro_cap(int max_cand) { return max_cand < RO_CAP ? max_cand : RO_CAP; }
 __host__ __device__ inline long ro_pair_cap(int cap) { return 8L * cap + 4096; }
 // per-page workspace in 4-byte words: ob[4c] sb[4c] cnt[c+4] pairs[2P] sorted[c] lineof[c] seq[c] emitted[c] keepf[c]
 __host__ __device__ inline long ro_ws_words(int cap) { return (4L * cap + 4L * cap + (cap + 4) + 2 * ro_pair_cap(cap) + 5L * cap + 3) / 4 * 4; }
 
-__device__ __forceinline__ bool ro_hit(const Box4& a, const Box4& b) {  // utils.py:515-523
-  return !(a.x1 <= b.x0 || b.x1 <= a.x0 || a.y1 <= b.y0 || b.y1 <= a.y0);
-}
-__device__ __forceinline__ int ro_shrink(int lo, int hi) {  // int(hi - (hi - lo) * 0.1): f64, truncation toward zero
-  return (int)((double)hi - (double)(hi - lo) * 0.1);
-}
-__device__ __forceinline__ bool ro_same(const Box4& a, const Box4& b) { return a.x0 == b.x0 && a.y0 == b.y0 && a.x1 == b.x1 && a.y1 == b.y1; }
-
 // in-place exclusive prefix sum of arr[0..n) by the whole workgroup (contiguous chunk per thread); returns the total
-__device__ int ro_block_scan(int* arr, int n, int* wave_tot /* LDS [RO_T/64] */, int* total_s /* LDS */) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__device__ int ro_block_scan(int* arr, int n, int* wave_tot /* LDS [RO_T/64] */) {
+  const int tid = threadIdx.x;
   const int per = (n + RO_T - 1) / RO_T;
   const int a0 = min(n, tid * per), a1 = min(n, a0 + per);
   int sum = 0;
   for (int k = a0; k < a1; ++k) sum += arr[k];
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o);
-    if (lane >= o) inc += v;
-  }
-  if (lane == 63) wave_tot[wv] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int q = 0; q < wv; ++q) base += wave_tot[q];
-  if (tid == RO_T - 1) *total_s = base + inc;
-  int run = base + inc - sum;
+  int total, run = block_exclusive_scan<RO_T>(sum, wave_tot, &total);
   for (int k = a0; k < a1; ++k) {
     const int v = arr[k];
     arr[k] = run;
@@ -71,7 +52,7 @@ __device__ int ro_block_scan(int* arr, int n, int* wave_tot /* LDS [RO_T/64] */,
   }
   __threadfence();
   __syncthreads();
-  return *total_s;
+  return total;
 }
 
 __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ nbox,
@@ -108,18 +89,13 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __shared__ double lsum[RO_MAXLINES];
   __shared__ int lcnt[RO_MAXLINES], lmaxx[RO_MAXLINES], lstart[RO_MAXLINES];
   __shared__ int wave_tot[RO_T / 64];
-  __shared__ int total_s, nlines_s, fail_s;
+  __shared__ int nlines_s, fail_s;
   __shared__ long long hsum_s;
 
   // ---- word AABBs: np.array(polygon, dtype=np.int32) truncates toward zero, then min / max over the 4 points (_pipeline.py:106-109)
   const float* ib = boxes + (long)pg * max_cand * 9;
   for (int i = tid; i < n; i += RO_T) {
-    const float* q = ib + 9 * (long)i;
-    int xs[4], ys[4];
-    for (int k = 0; k < 4; ++k) { xs[k] = (int)q[2 * k]; ys[k] = (int)q[2 * k + 1]; }
-    Box4 b;
-    b.x0 = min(min(xs[0], xs[1]), min(xs[2], xs[3])); b.x1 = max(max(xs[0], xs[1]), max(xs[2], xs[3]));
-    b.y0 = min(min(ys[0], ys[1]), min(ys[2], ys[3])); b.y1 = max(max(ys[0], ys[1]), max(ys[2], ys[3]));
+    const Box4 b = box_from_quad(ib + 9 * (long)i);
     ob[i] = b;
     sb[i] = b;
   }
@@ -132,12 +108,12 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     for (int i = tid; i < n; i += RO_T) {
       const Box4 a = sb[i];
       int c = 0;
-      for (int j = i + 1; j < n; ++j) c += ro_hit(a, sb[j]) ? 1 : 0;
+      for (int j = i + 1; j < n; ++j) c += box_hit(a, sb[j]) ? 1 : 0;
       cnt[i] = c;
     }
     __threadfence();
     __syncthreads();
-    const int total = ro_block_scan(cnt, n, wave_tot, &total_s);
+    const int total = ro_block_scan(cnt, n, wave_tot);
     if (total == 0) break;
     if (total > P) {
       if (tid == 0) fail_s = 1;
@@ -147,7 +123,7 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
       const Box4 a = sb[i];
       int o = cnt[i];
       for (int j = i + 1; j < n; ++j)
-        if (ro_hit(a, sb[j])) { pairs[2 * (long)o] = i; pairs[2 * (long)o + 1] = j; ++o; }
+        if (box_hit(a, sb[j])) { pairs[2 * (long)o] = i; pairs[2 * (long)o + 1] = j; ++o; }
     }
     __threadfence();
     __syncthreads();
@@ -155,9 +131,9 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
       for (int p = 0; p < total; ++p) {
         const int i = pairs[2 * (long)p], j = pairs[2 * (long)p + 1];
         Box4 a = sb[i], b = sb[j];
-        if (!ro_hit(a, b)) continue;
-        a.x1 = ro_shrink(a.x0, a.x1); a.y1 = ro_shrink(a.y0, a.y1);
-        b.x1 = ro_shrink(b.x0, b.x1); b.y1 = ro_shrink(b.y0, b.y1);
+        if (!box_hit(a, b)) continue;
+        box_shrink(a);
+        box_shrink(b);
         sb[i] = a; sb[j] = b;
       }
     }
@@ -261,36 +237,25 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     const Box4 si = sb[i];
     int back = i;
     for (int j = n - 1; j > i; --j)
-      if (ro_same(sb[j], si)) { back = j; break; }
+      if (box_same(sb[j], si)) { back = j; break; }
     const Box4 o = ob[back];
     int wi = back;
     for (int j = 0; j < back; ++j)
-      if (ro_same(ob[j], o)) { wi = j; break; }
+      if (box_same(ob[j], o)) { wi = j; break; }
     oo[pos] = wi;
-    const Box4 bx = ob[wi];
-    int keep = 0;
-    int a = 0, b = 0, c = 0, d = 0;
-    if ((bx.x1 - bx.x0) >= min_text && (bx.y1 - bx.y0) >= min_text) {
-      a = max(0, bx.x0); b = max(0, bx.y0);
-      c = min(page_w, bx.x1); d = min(page_h, bx.y1);
-      if (c < 0) c = max(page_w + c, 0);  // Python slice semantics of image[y1:y2, x1:x2] with a negative stop
-      if (d < 0) d = max(page_h + d, 0);
-      keep = (c > a && d > b) ? 1 : 0;
-    }
+    int win[4];
+    const int keep = box_crop_window(ob[wi], page_h, page_w, min_text, win) ? 1 : 0;
     keepf[pos] = keep;
     ko[pos] = keep;
     if (keep) {  // staged at the word's position, compacted below
-      const int h = d - b, wd = c - a;
-      const double scale = fmin((double)img_h / (double)max(h, 1), (double)img_w / (double)max(wd, 1));
-      const int nw = max(1, (int)rint((double)wd * scale)), nh = max(1, (int)rint((double)h * scale));
-      const int yy = max(0, min((img_h - nh) / 2, img_h - nh));  // floor division of a non-negative numerator when nh <= img_h
+      const CanvasFit f = canvas_fit((double)(win[2] - win[0]), (double)(win[3] - win[1]), img_h, img_w);
       int32_t* t = dout + 8 * (long)pos;
-      t[0] = page_base + pg; t[1] = a; t[2] = b; t[3] = c; t[4] = d; t[5] = nw; t[6] = nh; t[7] = yy;
+      t[0] = page_base + pg; t[1] = win[0]; t[2] = win[1]; t[3] = win[2]; t[4] = win[3]; t[5] = f.new_w; t[6] = f.new_h; t[7] = f.y0;
     }
   }
   __threadfence();
   __syncthreads();
-  const int nk = ro_block_scan(keepf, n, wave_tot, &total_s);  // keepf[pos] = index of the crop among the page's crops
+  const int nk = ro_block_scan(keepf, n, wave_tot);  // keepf[pos] = index of the crop among the page's crops
   // compaction through a staging buffer (pairs[] holds >= 16 * cap words and is free again)
   for (int pos = tid; pos < n; pos += RO_T)
     if (ko[pos])

@@ -386,10 +386,11 @@ def _by_score(inp):
 
 
 @pytest.mark.parametrize("layout", ["runs", "disjoint"])
-@pytest.mark.parametrize("n", [1, 7, 8, 9, 2047, 2048, 2049])
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 767, 768, 769, 2047, 2048, 2049, 6144, 6145])
 def test_lanms_segment_and_rank_tile_edges(ops, nat, n, layout):
     """n < 8: one scan segment, 8 / 9: two; 2048 / 2049: one / two tiles of lanms_rank_x0_kernel (RS_TILE = 256 * RS_Q = 2048),
-    grid (1, 1) / (2, 2) per page."""
+    grid (1, 1) / (2, 2) per page.  768 / 769: the compaction's chunk per thread goes 1 -> 2 (LANMS_PAGE_T = 768 threads);
+    6144 / 6145: the segment count saturates at 768 and the segment length goes 8 -> 9."""
     rng = np.random.default_rng([SEED, 21, n, len(layout)])
     inp = merge_runs(rng, n, 4, 12) if layout == "runs" else disjoint_polys(rng, n)
     exp, nm = _lanms_ref(inp)

@@ -186,6 +186,46 @@ def test_descriptor_kernel_equals_host_form(gpu, page_base):
         assert (c[:, 1, 0] > c[:, 0, 0]).all() and (c[:, 2, 1] > c[:, 1, 1]).all()
 
 
+def test_descriptor_kernel_across_scan_boundaries(gpu):
+    """The kept words' ranks come from a workgroup scan: 63 / 64 / 65 words are the first prefix that crosses a wave, at 1023 /
+    1024 / 1025 the chunk per thread goes 1 -> 2 (QDESC_T = 1024).  The expected words, windows and count come from the host
+    side (msocr_reading_order_host + ops.crop_descriptors), not from the kernels' outputs.  The word ORDER comes from the host twin,
+    which shares box_hit / box_shrink with reading_order_kernel through word_boxes.h: tests/test_host_cpu.py pins that twin to the
+    reference's goldens; the windows, the filter and ncrop come from the NumPy restatement, which shares nothing."""
+    from manuscript_ocr_amd import ops
+    from manuscript_ocr_amd._pipeline import _reading_order
+    page_hw, img_h, img_w, max_cand, min_text = (7300, 640), 32, 128, 1030, 5
+    counts = [63, 64, 65, 1023, 1024, 1025, 0]  # the last page stays all sentinel
+    N = len(counts)
+    boxes = np.zeros((N, max_cand, 9), dtype=np.float32)
+    for pg, n in enumerate(counts):
+        if n:
+            boxes[pg, :n] = _tilted_boxes(n, 200 + pg, page_hw)
+    boxes_d, nbox_d = torch.from_numpy(boxes).cuda(), torch.from_numpy(np.array(counts, dtype=np.int32)).cuda()
+    ro = ops.reading_order_crops(boxes_d, nbox_d, page_hw, min_text, img_h, img_w)
+    SENT = 0x5A5A5A5A
+    out = torch.full((N, max_cand, 12), SENT, dtype=torch.int32, device="cuda")
+    qd = ops.quad_crop_descriptors(boxes_d, nbox_d, ro, img_h, img_w, out=out).cpu().numpy()
+    ncrop = ro[3].cpu().numpy()
+    for pg, n in enumerate(counts):
+        if n == 0:
+            assert ncrop[pg] == 0 and (qd[pg] == SENT).all()
+            continue
+        pts = boxes[pg, :n, :8].astype(np.int32).reshape(n, 4, 2)  # truncation toward zero
+        aabb = np.concatenate([pts.min(axis=1), pts.max(axis=1)], axis=1)
+        order = _reading_order(aabb)
+        sized = [pos for pos, w in enumerate(order) if min(aabb[w, 2] - aabb[w, 0], aabb[w, 3] - aabb[w, 1]) >= min_text]
+        desc, keep = ops.crop_descriptors(aabb[[order[pos] for pos in sized]], [pg] * len(sized), page_hw, img_h, img_w)
+        kept_pos = [pos for pos, k in zip(sized, keep) if k]
+        kept = [order[pos] for pos in kept_pos]
+        nc = len(kept)
+        assert 0 <= nc < n and kept_pos != list(range(nc)), "regime: some words filtered, so a kept word's rank != its position"
+        assert int(ncrop[pg]) == nc
+        exp = ops.quad_descriptors(boxes[pg, kept, :8].reshape(-1, 4, 2), desc, img_h, img_w)
+        assert np.array_equal(qd[pg, :nc], exp), pg
+        assert (qd[pg, nc:] == SENT).all(), pg
+
+
 # ------------------------------------------------------------------------------------------- Pipeline
 @pytest.fixture(scope="module")
 def rec(gpu):

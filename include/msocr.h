@@ -346,6 +346,15 @@ int msocr_crop_resize_pad(const uint8_t* pages, int N, int H, int W, const int32
 int msocr_reading_order_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio,
                              int32_t* order_out_host);
 
+/* HOST function: the same order together with the TEXT LINES it is built from (sort_boxes_reading_order groups the shrunk boxes
+ * into lines, sorts the lines by mean centre y and the words of a line by x, and returns only the flattened list).
+ * line_out_host [n]: 0-based index of the line of every position of order_out_host; lines are numbered in reading order, so the
+ * values start at 0, never decrease and step by 0 or 1.  lines_out_host [n][6]: one record {first, count, x0, y0, x1, y1} per line:
+ * first / count = the line's span of positions, x0..y1 = the union of the input boxes of the words written at those positions
+ * (boxes_host[order_out_host[pos]]).  *nlines_out_host: the number of lines, 0 for n = 0.  Rows past the line count stay untouched. */
+int msocr_reading_lines_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio, int32_t* order_out_host,
+                             int32_t* line_out_host, int32_t* lines_out_host, int32_t* nlines_out_host);
+
 /* The same glue ON THE DEVICE, one workgroup per page, fed by msocr_east_box_tail's output, plus what follows it on the way to the
  * recogniser: word AABBs with np.int32 truncation and the min_text_size filter (_pipeline.py:100-133), the clamped crop window
  * (_pipeline.py:204-221) and ResizeAndPadA's size arithmetic (recognizers/_trba/data/transforms.py:91-95,114-117) -> descriptors in
@@ -360,6 +369,20 @@ int msocr_reading_order_crops(const float* boxes, const int32_t* nbox, int N, in
                               int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio, int page_base,
                               int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, void* workspace,
                               void* stream);
+
+/* msocr_reading_order_crops with the page's text lines as three more outputs (an extension beyond the reference, off by default:
+ * Pipeline.group_lines).  Same arguments, same workspace, the same order_out / keep_out / desc_out / ncrop_out bit for bit.
+ * line_out [N][max_cand]: for every position pos < n of order_out the 0-based index of its line, lines numbered in reading order.
+ * lines_out [N][rows][6], rows = msocr_reading_order_line_rows(max_cand) = min(max_cand, 4096): one record
+ * {first, count, x0, y0, x1, y1} per line, first / count = its span of positions in order_out, x0..y1 = the union of the integer
+ * word boxes (np.int32 truncation of the quad, min / max) of the words written at those positions.  nlines_out [N]: lines of the
+ * page, 0 for a page without boxes, -1 exactly where ncrop_out is -1 (then nothing else of the three is defined; rows of such a
+ * page and rows past a page's counts stay untouched).  Bit-identical to msocr_reading_lines_host. */
+int msocr_reading_order_line_rows(int max_cand);
+int msocr_reading_order_lines(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                              int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio, int page_base,
+                              int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, int32_t* line_out,
+                              int32_t* lines_out, int32_t* nlines_out, void* workspace, void* stream);
 
 /* ---- rectified word crops (an extension beyond the reference, off by default: Pipeline.rectify_crops) -----------------------
  * The canvas of a word is cut ALONG its detected quadrilateral instead of from the quad's axis-aligned window.  All arithmetic is

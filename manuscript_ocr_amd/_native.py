@@ -102,9 +102,13 @@ _SIGS = {
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_east_box_tail_host": (c_i32, [c_vp, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp]),
     "msocr_reading_order_host": (c_i32, [c_vp, c_i32, c_f64, c_f64, c_vp]),
+    "msocr_reading_lines_host": (c_i32, [c_vp, c_i32, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "msocr_reading_order_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_reading_order_crops": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_reading_order_line_rows": (c_i32, [c_i32]),
+    "msocr_reading_order_lines": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "msocr_quad_crop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),

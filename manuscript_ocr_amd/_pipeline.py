@@ -11,8 +11,16 @@ per-symbol confidence and x position (detectors/_types.py; DESIGN.md section 4.8
 quadrilaterals instead of from their axis-aligned windows (useful with EAST(axis_aligned_output=False)).
 The recognised words and their order do not change, only the pixels the recogniser sees.  Native path: the device kernel
 msocr_quad_crop writes the recogniser's canvases directly.  Every other route (foreign plugins, profile=True, native_fast_path =
-False): `_extract_word_image` returns the rectified region at its natural size and the recogniser resizes it, so that route
-resamples twice and its canvases do not equal the device route's; identity holds within a route only.
+False) cuts on the host in `_extract_word_image`.  With this package's TRBA as the recogniser it hands over the word's finished
+img_h x img_w canvas from the host twin msocr_quad_crop_host, the device route's bytes, which the recogniser's ResizeAndPadA passes
+through unchanged: the pages equal the device route's.  A foreign recogniser, whose canvas is not known, gets the rectified region
+at its natural size and resizes it itself, so that route resamples twice.
+
+`pipeline.group_lines = True` (this package's extension, absent by default): every block the pipeline puts into reading order comes
+back as its text lines, one TextLine (detectors/_types.py) per line in reading order, holding exactly the words at the line's
+positions.  The lines are the ones the reading order is built from (y_tol_ratio = 0.6, x_gap_ratio = inf),
+nothing is estimated anew; `get_text` then returns one row per line.  Where the reference applies no reading order the switch has
+no effect: `recognize_text=False`, on the generic route and on the batch route, returns the detector's blocks in detector order.
 
 `process_batch` is broken upstream (it calls a non-existent `self.process`, _pipeline.py:187);
 here it is the per-image `predict`.  `predict_batch` is the MI355X fast path: when detector and
@@ -58,6 +66,9 @@ def _reading_order(aabbs_i32):
     return order.tolist()
 
 
+_NO_LINES = np.empty((0, 6), dtype=np.int32)  # the line records of a block without words
+
+
 def _word_aabb(word):
     poly = np.array(word.polygon, dtype=np.int32)  # float -> int32 truncation (reference :106)
     x_min, y_min = np.min(poly, axis=0)
@@ -75,6 +86,7 @@ class _Group:
     det: Any                         # the detector's Detection
     det_event: Any                   # the detector outputs (and descriptors) of this group are complete
     ro: Any = None                   # ops.ReadingOrder of the group's pages (device_order)
+    rl: Any = None                   # ops.ReadingLines behind it (group_lines)
     qd: Any = None                   # [pages,max_cand,12] device quad descriptors behind it (rectify_crops)
     device_ordered: bool = False     # advance_batch took the device route: Page / Word assembly is collect_batch's
     words: Optional[list] = None     # the Words that got a crop, in crop order
@@ -96,6 +108,7 @@ class _Batch:
     recognize_text: bool
     profile: bool
     rectify: bool                    # rectify_crops as it was at submit
+    line_recs: Optional[dict]        # group_lines as it was at submit: page index -> per block its [L,6] line records; None = off
     ingest_pending: Any              # the device JPEG stages' deferred verdict, read in advance_batch
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
@@ -119,6 +132,7 @@ class Pipeline:
         self.device_order = True           # reading order + crop descriptors on the device; False = on the host (test hook)
         self.rectify_crops = False         # crops cut along the detected quadrilaterals (user extension, see the module docstring)
         self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
+        self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -139,11 +153,15 @@ class Pipeline:
             raise RuntimeError("Detector did not return a Page result.")
         return page
 
-    def _order_and_crop(self, page, image_array):
-        """_pipeline.py:102-137: reorder every block in reading order, collect crops of words >= min_text_size."""
+    def _order_and_crop(self, page, image_array, line_recs=None):
+        """_pipeline.py:102-137: reorder every block in reading order, collect crops of words >= min_text_size.
+        `line_recs` (a list, group_lines): gets every block's line records from the host twin on the same AABBs; the order stays the
+        Python function's (tests/test_host_cpu.py pins the two orders to be equal)."""
         words, crops = [], []
         for block in page.blocks:
             boxes = [_word_aabb(w)[0] for w in block.words]
+            if line_recs is not None:
+                line_recs.append(ops.reading_lines_host(np.array(boxes, dtype=np.int32).reshape(-1, 4))[2])
             first = {}
             for k, bx in enumerate(boxes):  # first equal word wins, as the reference's tuple comparison (:113-121)
                 first.setdefault(tuple(int(v) for v in bx), k)
@@ -197,7 +215,8 @@ class Pipeline:
         if profile:
             print(f"Load image for crops: {time.time() - t0:.3f}s")
         t0 = time.time()
-        words, crops = self._order_and_crop(page, image_array)
+        line_recs = [] if self.group_lines else None
+        words, crops = self._order_and_crop(page, image_array, line_recs)
         if profile:
             print(f"Extract {len(crops)} crops: {time.time() - t0:.3f}s")
         if crops:
@@ -206,6 +225,8 @@ class Pipeline:
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
             self._assign(words, [results[i] for i in range(len(words))])
+        if line_recs is not None:
+            self._split_lines(page, line_recs)
         if profile:
             print(f"Pipeline total: {time.time() - start:.3f}s")
         if vis:
@@ -213,18 +234,26 @@ class Pipeline:
             return page, visualize_page(pil, page, show_order=True)
         return page
 
-    def _order_boxes(self, page):
+    def _order_boxes(self, page, line_recs=None):
         """Reading-order reorder of every block (in place) + AABBs of the words that pass min_text_size.
-        Same semantics as _pipeline.py:102-133 of the reference, vectorised."""
+        Same semantics as _pipeline.py:102-133 of the reference, vectorised.  `line_recs` (a list, group_lines): order and line
+        records of every block then come from msocr_reading_lines_host, and the records are appended to it."""
         words, boxes = [], []
         for block in page.blocks:
             if not block.words:
+                if line_recs is not None:
+                    line_recs.append(_NO_LINES)
                 continue
             # AABBs of all words at once: np.array(polygon, int32) truncates toward zero (_pipeline.py:106)
             polys = np.array([w.polygon for w in block.words], dtype=np.float64).astype(np.int32)
             mins, maxs = polys.min(axis=1), polys.max(axis=1)
             aabbs = [(a[0], a[1], b[0], b[1]) for a, b in zip(mins, maxs)]
-            order = _reading_order(np.concatenate([mins, maxs], axis=1))
+            if line_recs is None:
+                order = _reading_order(np.concatenate([mins, maxs], axis=1))
+            else:
+                order, _line, recs = ops.reading_lines_host(np.concatenate([mins, maxs], axis=1))
+                order = order.tolist()
+                line_recs.append(recs)
             old_words = block.words
             block.words = [old_words[k] for k in order]
             for k in order:
@@ -354,7 +383,7 @@ class Pipeline:
                 pool.append(torch.cuda.Stream())
                 dpool.append(torch.cuda.Stream(priority=hi_prio))
             streams, det_streams = pool[:nsub], dpool[:nsub]
-        rec, rectify, groups = self.recognizer, bool(self.rectify_crops), []
+        rec, rectify, group_lines, groups = self.recognizer, bool(self.rectify_crops), bool(self.group_lines), []
         for (lo, hi), st, dst in zip(bounds, streams, det_streams):
             if dst is not main:
                 dst.wait_stream(main)
@@ -363,16 +392,20 @@ class Pipeline:
                 dh = det.detect_start(pages_dev[lo:hi], mo)
                 # reading order + crop descriptors of the group's pages on the device, right behind the box filters: the host
                 # then needs only the crop COUNTS to enqueue the recogniser (Page / Word assembly moves to collect_batch)
-                ro = qd = None
+                ro = rl = qd = None
                 if recognize_text and dh.final_boxes is not None and self.device_order:
-                    ro = ops.ReadingOrder(*ops.reading_order_crops(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h,
-                                                                   rec.img_w, page_base=lo))
+                    if group_lines:  # the same kernel body with the line outputs compiled in
+                        ro, rl = ops.reading_order_lines(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h, rec.img_w,
+                                                         page_base=lo)
+                    else:
+                        ro = ops.ReadingOrder(*ops.reading_order_crops(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size,
+                                                                       rec.img_h, rec.img_w, page_base=lo))
                     if rectify:  # quad descriptors of the same words, right behind, same order
                         qd = ops.quad_crop_descriptors(dh.final_boxes, dh.final_counts, ro, rec.img_h, rec.img_w)
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
-                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, qd))
-        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, ingest_pending,
+                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
+        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
 
     def advance_batch(self, h):
@@ -431,7 +464,9 @@ class Pipeline:
             t0 = time.perf_counter()
             grp.words, boxes, page_ids = [], [], []
             for pi in range(lo, hi):
-                words, bxs = self._order_boxes(h.pages[pi])
+                if h.line_recs is not None:
+                    h.line_recs[pi] = []
+                words, bxs = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi])
                 grp.spans.append([len(grp.words), len(words)])
                 grp.words += words
                 boxes += bxs
@@ -518,6 +553,8 @@ class Pipeline:
                         t0 = time.perf_counter()
                         res = self.detector.detect_finish(grp.det, h.arrays[lo:hi], profile=h.profile)
                         order_h, keep_h = grp.ro.order.cpu().numpy(), grp.ro.keep.cpu().numpy()
+                        if grp.rl is not None:  # the records carry the spans; the per-position line index stays on the device
+                            lines_h, nlines_h = grp.rl.lines.cpu().numpy(), grp.rl.nlines.cpu().numpy()
                         tm["detect_wait+tail"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
                     grp.words = []
@@ -525,12 +562,16 @@ class Pipeline:
                         page = self._page_of(r)
                         pages[lo + pi] = page
                         k0 = 0
+                        if grp.rl is not None:
+                            h.line_recs[lo + pi] = []
                         for block in page.blocks:  # this package's EAST returns one block (infer.py:390)
                             nw = len(block.words)
                             if nw:
                                 old = block.words
                                 block.words = [old[k] for k in order_h[pi, k0:k0 + nw].tolist()]
                                 grp.words += [block.words[pos] for pos in np.flatnonzero(keep_h[pi, k0:k0 + nw]).tolist()]
+                            if grp.rl is not None:
+                                h.line_recs[lo + pi].append(lines_h[pi, :int(nlines_h[pi])] if nw else _NO_LINES)
                             k0 += nw
                     tm["order"] += time.perf_counter() - t0
                 if grp.handle is not None:
@@ -560,6 +601,9 @@ class Pipeline:
             for grp in h.groups:
                 if grp.det_stream is not main:
                     main.wait_stream(grp.det_stream)
+            if h.line_recs:  # after _attach_chars, so that the lines hold the CharWords
+                for pi, recs in h.line_recs.items():
+                    self._split_lines(pages[pi], recs)
         self.last_profile = tm
         if h.profile:
             print("Pipeline.predict_batch host stages (s):", {k: round(v, 4) for k, v in tm.items()})
@@ -580,6 +624,17 @@ class Pipeline:
         for page in pages:
             for block in page.blocks:
                 block.words = [new.get(id(w), w) for w in block.words]
+
+    @staticmethod
+    def _split_lines(page, line_recs):
+        """group_lines: replace every block of `page` by its text lines, block-major.  line_recs[b] = the [L,6] records
+        {first, count, x0, y0, x1, y1} of block b over the positions of its reading-ordered words; a block without words has none."""
+        from .detectors._types import TextLine
+        lines = []
+        for block, recs in zip(page.blocks, line_recs):
+            for first, count, x0, y0, x1, y1 in np.asarray(recs).tolist():
+                lines.append(TextLine(words=block.words[first:first + count], bbox=(x0, y0, x1, y1)))
+        page.blocks = lines
 
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):
@@ -602,7 +657,9 @@ class Pipeline:
         """The word's clamped AABB window of the page (reference _pipeline.py:204-221).  With `rectify_crops` set and the word's
         float corners given as `quad`: the region cut along the quadrilateral at its natural size, (rint(h), rint(w), 3), through
         the host twin msocr_quad_crop_host (same sampling as the device kernel; the recogniser's own resize follows, so these
-        pixels are resampled twice and differ from the device route's canvases).  A word without a window has no region either way."""
+        pixels are resampled twice) — or, when the recogniser is this package's TRBA and its canvas therefore known, the finished
+        (img_h, img_w, 3) canvas of the device route, which TRBA's ResizeAndPadA leaves as it is (a crop of the canvas size is pasted
+        unscaled at the origin).  A word without a window has no region either way."""
         try:
             x_min, y_min = np.min(polygon, axis=0)
             x_max, y_max = np.max(polygon, axis=0)
@@ -615,7 +672,11 @@ class Pipeline:
         except Exception:
             return None
         if quad is not None and self.rectify_crops and image.ndim == 3 and image.shape[2] == 3:
-            desc, _ = ops.crop_descriptors([(x_min, y_min, x_max, y_max)], [0], (h, w), 1, 1)
+            rec = self.recognizer
+            canvas = (rec.img_h, rec.img_w) if isinstance(rec, TRBA) else None
+            desc, _ = ops.crop_descriptors([(x_min, y_min, x_max, y_max)], [0], (h, w), *(canvas or (1, 1)))
+            if len(desc) and canvas:  # the device route's descriptor and canvas
+                return ops.quad_crop_host(image[None], ops.quad_descriptors([quad], desc, *canvas), *canvas)[0]
             if len(desc):  # always: the window above is not empty
                 qd = ops.quad_descriptors([quad], desc, natural=True)
                 return ops.quad_crop_host(image[None], qd, int(qd[0, 10]), int(qd[0, 9]))[0]

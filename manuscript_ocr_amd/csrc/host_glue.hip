@@ -21,13 +21,15 @@ namespace {
 struct BoxLess {  // the order of the std::map keys (any strict total order of the four coordinates serves)
   bool operator()(const Box4& a, const Box4& b) const { return std::tie(a.x0, a.y0, a.x1, a.y1) < std::tie(b.x0, b.y0, b.x1, b.y1); }
 };
-}  // namespace
 
 // The sequential twin of reading_order_kernel's ordering: box test, shrink and equality are the kernel's (word_boxes.h); sums and
-// differences of coordinates are formed in 64 bits, so it is defined for any int32 boxes.
-extern "C" int msocr_reading_order_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio,
-                                        int32_t* order_out_host) {
+// differences of coordinates are formed in 64 bits, so it is defined for any int32 boxes.  With line_out / lines_out / nlines_out
+// (all three or none) the text lines the order is built from leave as well: the line index of every position and one record
+// {first, count, x0, y0, x1, y1} per line, the box being the union of the original boxes of the words written at its positions.
+int reading_order_body(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio, int32_t* order_out_host,
+                       int32_t* line_out, int32_t* lines_out, int32_t* nlines_out) {
   if (n < 0 || (n > 0 && (!boxes_host || !order_out_host))) return MSOCR_E_ARG;
+  if (nlines_out) *nlines_out = 0;
   if (n == 0) return MSOCR_OK;
   std::vector<Box4> orig(n), b(n);
   for (int i = 0; i < n; ++i) orig[i] = b[i] = Box4{boxes_host[4 * i], boxes_host[4 * i + 1], boxes_host[4 * i + 2], boxes_host[4 * i + 3]};
@@ -75,11 +77,37 @@ extern "C" int msocr_reading_order_host(const int32_t* boxes_host, int n, double
   for (size_t li = 0; li < lines.size(); ++li) lorder[li] = (int)li;
   std::stable_sort(lorder.begin(), lorder.end(),
                    [&](int u, int v) { return sums[u] / (double)lines[u].size() < sums[v] / (double)lines[v].size(); });
-  int k = 0;
+  int k = 0, rank = 0;
   for (int li : lorder) {
     std::vector<int>& ln = lines[li];
     std::stable_sort(ln.begin(), ln.end(), [&](int u, int v) { return b[u].x0 < b[v].x0; });
+    const int start = k;
     for (int i : ln) order_out_host[k++] = first[orig[back[b[i]]]];
+    if (nlines_out) {
+      Box4 u = orig[order_out_host[start]];
+      for (int pos = start; pos < k; ++pos) {
+        const Box4& o = orig[order_out_host[pos]];
+        u.x0 = std::min(u.x0, o.x0); u.y0 = std::min(u.y0, o.y0); u.x1 = std::max(u.x1, o.x1); u.y1 = std::max(u.y1, o.y1);
+        line_out[pos] = rank;
+      }
+      const int32_t rec[6] = {start, k - start, u.x0, u.y0, u.x1, u.y1};
+      std::copy(rec, rec + 6, lines_out + 6 * (long)rank);
+    }
+    ++rank;
   }
+  if (nlines_out) *nlines_out = rank;
   return MSOCR_OK;
+}
+}  // namespace
+
+extern "C" int msocr_reading_order_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio,
+                                        int32_t* order_out_host) {
+  return reading_order_body(boxes_host, n, y_tol_ratio, x_gap_ratio, order_out_host, nullptr, nullptr, nullptr);
+}
+
+extern "C" int msocr_reading_lines_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio,
+                                        int32_t* order_out_host, int32_t* line_out_host, int32_t* lines_out_host,
+                                        int32_t* nlines_out_host) {
+  if (!nlines_out_host || (n > 0 && (!line_out_host || !lines_out_host))) return MSOCR_E_ARG;
+  return reading_order_body(boxes_host, n, y_tol_ratio, x_gap_ratio, order_out_host, line_out_host, lines_out_host, nlines_out_host);
 }

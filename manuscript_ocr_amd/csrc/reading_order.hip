@@ -12,6 +12,8 @@
 // Everything is integer or f64 arithmetic in the reference's order, so the result is bit-identical to the host helper
 // msocr_reading_order_host (host_glue.hip) + ops.crop_descriptors, which stay as the fallback for pages this kernel flags
 // (ncrop = -1: more boxes than the capacity, more than RO_MAXLINES text lines, or more intersecting pairs than the pair buffer).
+// msocr_reading_order_lines launches the same body with LINES = true: the text lines the order is built from leave as well (the
+// line of every position, one record per line, the line count), bit-identical to msocr_reading_lines_host.
 //
 // resolve_intersections is a SEQUENTIAL sweep over all pairs (i < j): an intersecting pair shrinks both boxes at once, which
 // changes what later pairs of the same sweep see.  It is parallelised exactly: boxes only ever shrink during a sweep, so the
@@ -55,20 +57,36 @@ __device__ int ro_block_scan(int* arr, int n, int* wave_tot /* LDS [RO_T/64] */)
   return total;
 }
 
+// the text lines of the reading order as a result (msocr_reading_order_lines); unused and compiled out with LINES = false
+struct RoLineOut {
+  int32_t* line;    // [N][max_cand]
+  int32_t* lines;   // [N][rows][6]
+  int32_t* nlines;  // [N]
+  int rows;
+};
+
+template <bool LINES>
 __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ nbox,
                                                               int max_cand, int cap, int page_h, int page_w, int min_text,
                                                               int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
                                                               int page_base, int32_t* __restrict__ order_out,
                                                               int32_t* __restrict__ keep_out, int32_t* __restrict__ desc_out,
-                                                              int32_t* __restrict__ ncrop_out, int32_t* __restrict__ ws) {
+                                                              int32_t* __restrict__ ncrop_out, int32_t* __restrict__ ws, RoLineOut lo) {
   const int pg = blockIdx.x, tid = threadIdx.x;
   const int n = nbox[pg];
+  // the page's verdict: crops (and lines) of the page, 0 for an empty page, -1 = the host path takes it
+  auto verdict = [&](int ncrop, int nlines) {
+    if (tid == 0) {
+      ncrop_out[pg] = ncrop;
+      if constexpr (LINES) lo.nlines[pg] = nlines;
+    }
+  };
   if (n < 0 || n > cap) {
-    if (tid == 0) ncrop_out[pg] = -1;
+    verdict(-1, -1);
     return;
   }
   if (n == 0) {
-    if (tid == 0) ncrop_out[pg] = 0;
+    verdict(0, 0);
     return;
   }
   int32_t* w = ws + (long)pg * ro_ws_words(cap);
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   }
   __syncthreads();
   if (fail_s) {
-    if (tid == 0) ncrop_out[pg] = -1;
+    verdict(-1, -1);
     return;
   }
 
@@ -202,19 +220,25 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __threadfence();
   __syncthreads();
   if (fail_s) {
-    if (tid == 0) ncrop_out[pg] = -1;
+    verdict(-1, -1);
     return;
   }
   const int L = nlines_s;
-  // lines sorted by their mean cy (stable: creation order breaks ties), then the first output position of every line
+  // lines sorted by their mean cy (stable: creation order breaks ties), then the first output position of every line;
+  // LINES: the same comparison counts the lines in front, which is the line's index in reading order (lmaxx[] is free again)
+  int* lrank = lmaxx;
   for (int l = tid; l < L; l += RO_T) {
     const double m = lsum[l] / (double)lcnt[l];
-    int start = 0;
+    int start = 0, rank = 0;
     for (int k = 0; k < L; ++k) {
       const double mk = lsum[k] / (double)lcnt[k];
-      if (mk < m || (mk == m && k < l)) start += lcnt[k];
+      if (mk < m || (mk == m && k < l)) {
+        start += lcnt[k];
+        if constexpr (LINES) ++rank;
+      }
     }
     lstart[l] = start;
+    if constexpr (LINES) lrank[l] = rank;
   }
   __syncthreads();
   // inside a line: stable sort by x0 (insertion order = cy-sorted order breaks ties)
@@ -255,6 +279,24 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   }
   __threadfence();
   __syncthreads();
+  if constexpr (LINES) {
+    // one thread per line walks the line's span of positions: the line index of every position and the union of the words'
+    // original AABBs (oo[] is complete: the barrier above)
+    int32_t* lno = lo.line + (long)pg * max_cand;
+    int32_t* rec = lo.lines + (long)pg * lo.rows * 6;  // L <= min(n, RO_MAXLINES) <= rows
+    for (int l = tid; l < L; l += RO_T) {
+      const int first = lstart[l], count = lcnt[l], rank = lrank[l];
+      Box4 u = ob[oo[first]];
+      lno[first] = rank;
+      for (int pos = first + 1; pos < first + count; ++pos) {
+        const Box4 b = ob[oo[pos]];
+        u.x0 = min(u.x0, b.x0); u.y0 = min(u.y0, b.y0); u.x1 = max(u.x1, b.x1); u.y1 = max(u.y1, b.y1);
+        lno[pos] = rank;
+      }
+      int32_t* t = rec + 6 * (long)rank;
+      t[0] = first; t[1] = count; t[2] = u.x0; t[3] = u.y0; t[4] = u.x1; t[5] = u.y1;
+    }
+  }
   const int nk = ro_block_scan(keepf, n, wave_tot);  // keepf[pos] = index of the crop among the page's crops
   // compaction through a staging buffer (pairs[] holds >= 16 * cap words and is free again)
   for (int pos = tid; pos < n; pos += RO_T)
@@ -263,7 +305,20 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __threadfence();
   __syncthreads();
   for (long k = tid; k < 8L * nk; k += RO_T) dout[k] = pairs[k];
-  if (tid == 0) ncrop_out[pg] = nk;
+  verdict(nk, L);
+}
+
+template <bool LINES>
+int ro_launch(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w, int min_text_size, int img_h,
+              int img_w, double y_tol_ratio, double x_gap_ratio, int page_base, int32_t* order_out, int32_t* keep_out,
+              int32_t* desc_out, int32_t* ncrop_out, void* workspace, RoLineOut lo, void* stream) {
+  if (!boxes || !nbox || !order_out || !keep_out || !desc_out || !ncrop_out || !workspace) return MSOCR_E_ARG;
+  if (N <= 0 || max_cand <= 0 || page_h <= 0 || page_w <= 0 || img_h <= 0 || img_w <= 0 || page_base < 0) return MSOCR_E_ARG;
+  if ((uintptr_t)workspace & 15) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(reading_order_kernel<LINES>, dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand),
+               page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base, order_out, keep_out, desc_out,
+               ncrop_out, (int32_t*)workspace, lo);
+  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 }  // namespace
 
@@ -275,11 +330,19 @@ extern "C" int msocr_reading_order_crops(const float* boxes, const int32_t* nbox
                                          int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
                                          int page_base, int32_t* order_out, int32_t* keep_out, int32_t* desc_out,
                                          int32_t* ncrop_out, void* workspace, void* stream) {
-  if (!boxes || !nbox || !order_out || !keep_out || !desc_out || !ncrop_out || !workspace) return MSOCR_E_ARG;
-  if (N <= 0 || max_cand <= 0 || page_h <= 0 || page_w <= 0 || img_h <= 0 || img_w <= 0 || page_base < 0) return MSOCR_E_ARG;
-  if ((uintptr_t)workspace & 15) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(reading_order_kernel, dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand), page_h,
-               page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base, order_out, keep_out, desc_out, ncrop_out,
-               (int32_t*)workspace);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+  return ro_launch<false>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base,
+                          order_out, keep_out, desc_out, ncrop_out, workspace, RoLineOut{nullptr, nullptr, nullptr, 0}, stream);
+}
+
+extern "C" int msocr_reading_order_line_rows(int max_cand) { return max_cand < RO_MAXLINES ? max_cand : RO_MAXLINES; }
+
+extern "C" int msocr_reading_order_lines(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                                         int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
+                                         int page_base, int32_t* order_out, int32_t* keep_out, int32_t* desc_out,
+                                         int32_t* ncrop_out, int32_t* line_out, int32_t* lines_out, int32_t* nlines_out,
+                                         void* workspace, void* stream) {
+  if (!line_out || !lines_out || !nlines_out) return MSOCR_E_ARG;
+  return ro_launch<true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base,
+                         order_out, keep_out, desc_out, ncrop_out, workspace,
+                         RoLineOut{line_out, lines_out, nlines_out, msocr_reading_order_line_rows(max_cand)}, stream);
 }

@@ -41,6 +41,14 @@ class Block(BaseModel):
     words: List[Word]
 
 
+class TextLine(Block):
+    """One text line of a page in reading order, written by Pipeline when `group_lines` is on (this package's extension).
+    Page.blocks is declared as List[Block], so a default model_dump() of a Page serialises a TextLine as a Block."""
+
+    bbox: Tuple[int, int, int, int] = Field(..., description="(x_min, y_min, x_max, y_max): union of the words' integer boxes "
+                                                             "as the reading order sees them (np.array(polygon, int32) truncation)")
+
+
 class Page(BaseModel):
     """All blocks of one page image."""
 

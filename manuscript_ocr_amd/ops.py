@@ -482,6 +482,45 @@ def reading_order_crops(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_
     return ReadingOrder(order, keep, desc, ncrop)
 
 
+class ReadingLines(NamedTuple):
+    """The text lines behind a ReadingOrder (`reading_order_lines`), per page, on the device."""
+    line: torch.Tensor    # [N,max_cand] i32: the line of every position of `order`, lines numbered in reading order
+    lines: torch.Tensor   # [N,rows,6] i32: per line {first, count, x0, y0, x1, y1}: its span of positions and the union of its words' boxes
+    nlines: torch.Tensor  # [N] i32: lines per page; -1 exactly where ncrop is -1
+
+
+def reading_order_lines(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf"),
+                        workspace=None):
+    """reading_order_crops that also returns the text lines the order is built from (msocr_reading_order_lines): the same
+    ReadingOrder bit for bit, and a ReadingLines.  Returns (ReadingOrder, ReadingLines)."""
+    _need_cuda(boxes, nbox)
+    N, max_cand, _ = boxes.shape
+    dev = boxes.device
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((nat.lib().msocr_reading_order_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    ro = ReadingOrder(i32(N, max_cand), i32(N, max_cand), i32(N, max_cand, 8), i32(N))
+    rl = ReadingLines(i32(N, max_cand), i32(N, nat.lib().msocr_reading_order_line_rows(max_cand), 6), i32(N))
+    nat.check(nat.lib().msocr_reading_order_lines(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, int(page_hw[0]), int(page_hw[1]),
+                                                  int(min_text_size), int(img_h), int(img_w), float(y_tol_ratio), float(x_gap_ratio),
+                                                  int(page_base), *[t.data_ptr() for t in ro + rl], ws.data_ptr(), _stream()),
+              "reading_order_lines")
+    return ro, rl
+
+
+def reading_lines_host(aabbs_i32, y_tol_ratio=0.6, x_gap_ratio=float("inf")):
+    """Integer word boxes [n,4] (x_min, y_min, x_max, y_max) -> (order [n], line [n], lines [L,6]) as numpy int32, through the host
+    twin msocr_reading_lines_host: the reading order, the line of every position and per line {first, count, x0, y0, x1, y1}."""
+    boxes = np.ascontiguousarray(aabbs_i32, dtype=np.int32).reshape(-1, 4)
+    n = len(boxes)
+    order, line, lines = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty((n, 6), dtype=np.int32)
+    nlines = np.zeros(1, dtype=np.int32)
+    nat.check(nat.lib().msocr_reading_lines_host(boxes.ctypes.data, n, float(y_tol_ratio), float(x_gap_ratio), order.ctypes.data,
+                                                 line.ctypes.data, lines.ctypes.data, nlines.ctypes.data), "reading_lines_host")
+    return order, line, lines[:int(nlines[0])].copy()
+
+
 def nchw_to_nhwc(x_f32, dtype, out=None):
     _need_cuda(x_f32)
     N, C, H, W = x_f32.shape

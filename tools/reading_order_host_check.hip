@@ -4,8 +4,9 @@
 //         tools/reading_order_host_check.hip -o /tmp/reading_order_host_check && /tmp/reading_order_host_check
 //
 // Random pages plus hostile ones: duplicates, zero and negative extents, nested cliques that never stop intersecting (all 50
-// sweeps), coordinates at +-(2^31 - 1).  Prints "ok" and returns 0 when every order is a list of valid word indices and the
-// helpers agree with their plain restatements; a sanitizer report aborts the run.
+// sweeps), coordinates at +-(2^31 - 1).  Prints "ok" and returns 0 when every order is a list of valid word indices, the text lines
+// of msocr_reading_lines_host tile that order with the right boxes, and the helpers agree with their plain restatements; a
+// sanitizer report aborts the run.
 #include <stdio.h>
 
 #include <random>
@@ -16,15 +17,46 @@
 static int fails = 0;
 #define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
 
+static const int32_t BIG_ = 2147483647;
+
 static void run_page(const std::vector<int32_t>& b, double tol, double gap) {
   const int n = (int)b.size() / 4;
   std::vector<int32_t> order(n, -1);
   EXPECT(msocr_reading_order_host(b.data(), n, tol, gap, order.data()) == MSOCR_OK);
   for (int v : order) EXPECT(v >= 0 && v < n);
+  // the same page through msocr_reading_lines_host: the same order, line indices that start at 0 and step by 0 or 1, records
+  // whose spans tile [0, n) and whose boxes are the unions of the words at their positions; one guard word behind every output
+  const int32_t G = -777;
+  std::vector<int32_t> order2(n + 1, G), line(n + 1, G), recs(6 * (size_t)n + 1, G);
+  int32_t nlines = G;
+  EXPECT(msocr_reading_lines_host(b.data(), n, tol, gap, order2.data(), line.data(), recs.data(), &nlines) == MSOCR_OK);
+  EXPECT(order2[n] == G && line[n] == G && recs[6 * (size_t)n] == G);
+  EXPECT(nlines >= (n > 0 ? 1 : 0) && nlines <= n);
+  int pos = 0;
+  for (int l = 0; l < nlines && l < n; ++l) {
+    const int32_t* r = &recs[6 * (size_t)l];
+    EXPECT(r[0] == pos && r[1] >= 1 && r[0] + (long long)r[1] <= n);
+    if (r[0] != pos || r[1] < 1 || r[0] + (long long)r[1] > n) break;
+    int32_t u[4] = {BIG_, BIG_, -BIG_, -BIG_};
+    for (int k = 0; k < r[1]; ++k, ++pos) {
+      EXPECT(order2[pos] == order[pos] && line[pos] == l);
+      const int32_t* w = &b[4 * (size_t)order[pos]];
+      u[0] = std::min(u[0], w[0]); u[1] = std::min(u[1], w[1]); u[2] = std::max(u[2], w[2]); u[3] = std::max(u[3], w[3]);
+    }
+    EXPECT(r[2] == u[0] && r[3] == u[1] && r[4] == u[2] && r[5] == u[3]);
+  }
+  EXPECT(pos == n);
+  for (size_t k = 6 * (size_t)std::max(nlines, 0); k < 6 * (size_t)n; ++k) EXPECT(recs[k] == G);  // rows past the line count
 }
 
 int main() {
-  const int32_t BIG = 2147483647;
+  const int32_t BIG = BIG_;
+  {  // no boxes: no lines, nothing else touched or needed
+    int32_t nlines = -5;
+    EXPECT(msocr_reading_lines_host(nullptr, 0, 0.6, INFINITY, nullptr, nullptr, nullptr, &nlines) == MSOCR_OK && nlines == 0);
+    EXPECT(msocr_reading_lines_host(nullptr, 0, 0.6, INFINITY, nullptr, nullptr, nullptr, nullptr) == MSOCR_E_ARG);
+    run_page({}, 0.6, INFINITY);
+  }
   std::mt19937 rng(20260101);
   auto uni = [&](int lo, int hi) { return (int32_t)std::uniform_int_distribution<int>(lo, hi)(rng); };
   for (int rep = 0; rep < 40; ++rep) {  // random pages, some words doubled

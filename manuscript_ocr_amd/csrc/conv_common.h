@@ -253,7 +253,15 @@ __device__ __forceinline__ void store_b_row(unsigned char* sB, int pl, int row, 
 // bias / residual / ReLU -> 16-byte coalesced stores).  acc[tile row][tile column] of MT x MT MFMA tiles, T the element type in HBM.
 // BIAS16: the thread's four f32 bias values come as one 16-byte load (conv_split_kernel) instead of one load each (conv_igemm_kernel)
 // — the same values; each kernel keeps the load count it was measured with.
-template <typename T, int BM, int BN, int WM, int WN, int MT, bool BIAS16, typename AccT, int TMA, int TN>
+// One memory round trip per pass, not one per row: stores count on vmcnt on this target, so a rolled row loop (load the residual
+// row, wait, add, store, next row) waits for the previous row's store and its own load on every one of its NR rows.  A tile that lies
+// wholly below M therefore runs straight-line code per pass: all residual rows loaded before the accumulator -> LDS write and the
+// barriers, all LDS rows read at once, every row in registers of its own, stores never waited for (only LDS reuse orders the passes).
+// The row guard has to stay out of that path: loads or stores under a per-row branch make the compiler's wait counts conservative
+// again (a skipped later load leaves fewer operations outstanding), so the last, partial M-tile of a launch takes the guarded
+// row-by-row loop instead.  NCH = 2 (conv_igemm_kernel at 128 registers): the pass by halves where a later pass's accumulators are
+// still alive.  Every path adds in the same order per element, so results do not depend on the path.
+template <typename T, int BM, int BN, int WM, int WN, int MT, bool BIAS16, int NCH = 1, typename AccT, int TMA, int TN>
 __device__ __forceinline__ void epilogue_lds(const ConvParams& p, unsigned char* smem, const AccT (&acc)[TMA][TN], int tile_m, int tile_n,
                                              char* g_out, int wm, int wn, int r32, int half) {
   constexpr int ES = sizeof(T), EPC = 16 / ES;
@@ -278,9 +286,15 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, unsigned char*
   }
 
   constexpr int TPP = 32 / MT;
-#pragma unroll
-  for (int i = 0; i < WM / 32; ++i) {
-    if (i) __syncthreads();
+  constexpr int NR = PR / ROWS_PP;  // rows of a pass per thread
+  static_assert(PR % ROWS_PP == 0 && NR % NCH == 0, "a pass is whole sweeps of 256 threads, a chunk whole rows");
+  // whole_tile's row_step needs tile_row(i, vrow0 + r * ROWS_PP) == tile_row(0, vrow0) + tile_row(i, r * ROWS_PP): true when a sweep
+  // never straddles a 32-row block (ROWS_PP divides 32) or covers whole blocks from the block's start (ROWS_PP == 64)
+  static_assert(32 % ROWS_PP == 0 || ROWS_PP == 64, "tile_row must be additive in the sweep index (see row_step)");
+  const long m0 = (long)tile_m * BM;
+  // tile row of row lr of pass i
+  auto tile_row = [&](int i, int lr) { return (lr >> 5) * WM + i * 32 + (lr & 31); };
+  auto lds_write = [&](int i) {
 #pragma unroll
     for (int ti = 0; ti < TPP; ++ti)
 #pragma unroll
@@ -290,42 +304,99 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, unsigned char*
           const int rit = MT == 32 ? acc_row(e, half) : 4 * half + e;
           sc[(wm * 32 + ti * MT + rit) * BN + wn * WN + j * MT + r32] = acc[i * TPP + ti][j][e];
         }
-    __syncthreads();
-    for (int lr = vrow0; lr < PR; lr += ROWS_PP) {
-      const int trow = (lr >> 5) * WM + i * 32 + (lr & 31);
-      const long m = (long)tile_m * BM + trow;
-      if (m >= p.M) continue;
-      float v[EPC];
+  };
+  auto lds_row = [&](int lr, float (&v)[EPC]) {
 #pragma unroll
-      for (int e4 = 0; e4 < EPC; e4 += 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(&sc[lr * BN + vcol + e4]);
-        v[e4] = t[0]; v[e4 + 1] = t[1]; v[e4 + 2] = t[2]; v[e4 + 3] = t[3];
-      }
+    for (int e4 = 0; e4 < EPC; e4 += 4) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(&sc[lr * BN + vcol + e4]);
+      v[e4] = t[0]; v[e4 + 1] = t[1]; v[e4 + 2] = t[2]; v[e4 + 3] = t[3];
+    }
+  };
+  // accumulator, + bias, + residual, ReLU, conversion, store: one order per element for every path below
+  auto finish_row = [&](float (&v)[EPC], bool res, const u32x4& rv, char* dst) {
 #pragma unroll
-      for (int e = 0; e < EPC; ++e) v[e] += bias[e];
-      if (p.has_res) {
-        const u32x4 rv = *reinterpret_cast<const u32x4*>(p.res + (m * p.res_ld + co) * ES);
-        if constexpr (ES == 4) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += __uint_as_float(rv[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)(rv[e >> 1] >> ((e & 1) * 16)));
-        }
-      }
-      if (p.relu) {
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      u32x4 o;
+    for (int e = 0; e < EPC; ++e) v[e] += bias[e];
+    if (res) {
       if constexpr (ES == 4) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = __float_as_uint(v[e]);
+        for (int e = 0; e < 4; ++e) v[e] += __uint_as_float(rv[e]);
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (uint32_t)f32_to_bf16(v[2 * e]) | ((uint32_t)f32_to_bf16(v[2 * e + 1]) << 16);
+        for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)(rv[e >> 1] >> ((e & 1) * 16)));
       }
-      *reinterpret_cast<u32x4*>(g_out + (m * p.out_ld + co) * ES) = o;
+    }
+    if (p.relu) {
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) v[e] = fmaxf(v[e], 0.f);
+    }
+    u32x4 o;
+    if constexpr (ES == 4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = __float_as_uint(v[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (uint32_t)f32_to_bf16(v[2 * e]) | ((uint32_t)f32_to_bf16(v[2 * e + 1]) << 16);
+    }
+    *reinterpret_cast<u32x4*>(dst) = o;
+  };
+  // a tile with all BM rows below M (see above).  NCH = 2 reads the LDS rows and stores by halves; its residual rows are all loaded
+  // early in the last pass, and by halves while the accumulators of a later pass are alive (128 registers did not hold more without
+  // a spill, and a reloaded spill waits for every load in flight).
+  auto whole_tile = [&](auto res_c) {
+    constexpr bool RES = decltype(res_c)::value;
+    constexpr int CR = NR / NCH;  // rows per chunk
+    // the thread's rows are its first row plus a compile-time number of tile rows: one 64-bit address per thread and operand, the
+    // row steps are wave-uniform
+    const long mt = m0 + tile_row(0, vrow0);
+    const char* const res_t = RES ? p.res + (mt * p.res_ld + co) * ES : nullptr;
+    char* const out_t = g_out + (mt * p.out_ld + co) * ES;
+    auto row_step = [&](int i, int r) { return tile_row(i, r * ROWS_PP); };  // vrow0 < ROWS_PP, and ROWS_PP divides 32 or is 64
+    auto load_res = [&](int i, int r0, int r1, u32x4 (&rv)[NR]) {
+      if constexpr (RES) {
+#pragma unroll
+        for (int r = r0; r < r1; ++r) rv[r] = *reinterpret_cast<const u32x4*>(res_t + row_step(i, r) * p.res_ld * ES);
+      }
+    };
+#pragma unroll
+    for (int i = 0; i < WM / 32; ++i) {
+      // rows whose residual is loaded before the barrier: all of them, or (NCH = 2) the first half while a later pass's accumulators
+      // are still alive; the second half is then loaded behind the first half's stores
+      const int early = (NCH == 1 || i == WM / 32 - 1) ? NR : CR;
+      u32x4 rv[NR];
+      load_res(i, 0, early, rv);
+      if (i) __syncthreads();
+      lds_write(i);
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        float v[CR][EPC];
+#pragma unroll
+        for (int r = 0; r < CR; ++r) lds_row(vrow0 + (c * CR + r) * ROWS_PP, v[r]);
+#pragma unroll
+        for (int r = 0; r < CR; ++r) finish_row(v[r], RES, rv[c * CR + r], out_t + row_step(i, c * CR + r) * p.out_ld * ES);
+        if (c == 0 && early < NR) load_res(i, early, NR, rv);
+      }
+    }
+  };
+  if (m0 + BM <= p.M) {
+    if (p.has_res) whole_tile(std::true_type{});
+    else whole_tile(std::false_type{});
+    return;
+  }
+  // the last, partial M-tile of a launch: row by row, a row with m >= M is neither loaded nor stored
+#pragma unroll
+  for (int i = 0; i < WM / 32; ++i) {
+    if (i) __syncthreads();
+    lds_write(i);
+    __syncthreads();
+    for (int lr = vrow0; lr < PR; lr += ROWS_PP) {
+      const long m = m0 + tile_row(i, lr);
+      if (m >= p.M) continue;
+      float v[EPC];
+      lds_row(lr, v);
+      u32x4 rv = {0u, 0u, 0u, 0u};
+      if (p.has_res) rv = *reinterpret_cast<const u32x4*>(p.res + (m * p.res_ld + co) * ES);
+      finish_row(v, p.has_res != 0, rv, g_out + (m * p.out_ld + co) * ES);
     }
   }
 }

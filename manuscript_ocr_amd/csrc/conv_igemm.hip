@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, WPE ? WPE : ((STAGES == 1 && BKB <= 128) ? 3 :
     __syncthreads();
   }
 
-  epilogue_lds<T, BM, BN, WM, WN, MT, false>(p, smem, acc, tile_m, tile_n, g_out, wm, wn, r32, half);
+  epilogue_lds<T, BM, BN, WM, WN, MT, false, WPE == 4 ? 2 : 1>(p, smem, acc, tile_m, tile_n, g_out, wm, wn, r32, half);
 }
 
 template <typename T, int BM, int BN, int BKB, int WM, int WN, int STAGES = 2, bool LEAN = false, int MT = 32, int WPE = 0>

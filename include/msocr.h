@@ -326,6 +326,28 @@ int msocr_seq_confidence(const float* logits, const int32_t* ids, const int32_t*
 int msocr_seq_char_details(const float* logits, const int32_t* ids, const float* alpha, const int32_t* trun_dev, int B, int V,
                            int steps, int T, float* prob_out, float* centre_out, int32_t* peak_out, void* stream);
 
+/* N-best readings: the final hypotheses of a row's beam search, read out of the workspace a beam decode left behind (any of the
+ * msocr_attn_beam entry points; the decode itself is untouched).  The workspace is logits [B][steps][beam][V] f32 | back
+ * [B][steps][beam] i32 | tokv [B][steps][beam] i32 | best_at [B][steps] i32, and the beam kernels fill the slots of every step in
+ * rank order (best score first), so the r-th best hypothesis of a row is the back-trace from slot r of step t_run-1.
+ * Rank rule: rank 0 is the slot best_at[b][t_run-1] — the walk of msocr_attn_beam_finalize, the same ids — and ranks 1 .. n_best-1
+ * are the remaining slots in slot order.  Outputs, for b < B and r < n_best <= beam:
+ *   ids_out  [B][n_best][steps] i32: the path's tokens, -1 for t >= t_run;
+ *   prob_out [B][n_best][steps] f32: exp(log_softmax(logits[b][t][parent slot])[token]) of every step, 0 for t >= t_run;
+ *   conf_out [B][n_best] f32: the mean of prob over t < t_run, summed in f32 in step order: for rank 0 bit-equal to
+ *            msocr_seq_confidence of the finalized path;
+ *   logp_out [B][n_best] f32: the hypothesis's summed log-probability, the score the search ranks by (before the length penalty):
+ *            log_softmax(...)[token] over the steps up to and including the path's first eos_id (later steps add 0, as the search
+ *            extends a finished hypothesis), accumulated in f64 in step order and rounded once.
+ * V <= 512, steps <= 64, beam <= 16, 1 <= n_best <= beam, otherwise MSOCR_E_ARG.  trun_dev [B] i32 as for the finalize step; a value
+ * outside [1, steps] is clamped into it.  The _host twin takes host copies of the workspace and of t_run and writes host arrays:
+ * the same walk and the same order of every sum; ids equal the device's, floats up to expf / logf of the host's libm. */
+int msocr_attn_beam_nbest(const void* workspace, int B, int V, int steps, int beam, int n_best, int eos_id, const int32_t* trun_dev,
+                          int32_t* ids_out, float* prob_out, float* conf_out, float* logp_out, void* stream);
+int msocr_attn_beam_nbest_host(const void* workspace_host, int B, int V, int steps, int beam, int n_best, int eos_id,
+                               const int32_t* trun_host, int32_t* ids_out_host, float* prob_out_host, float* conf_out_host,
+                               float* logp_out_host);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

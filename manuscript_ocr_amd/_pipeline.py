@@ -22,6 +22,13 @@ positions.  The lines are the ones the reading order is
 nothing is estimated anew; `get_text` then returns one row per line.  Where the reference applies no reading order the switch has
 no effect: `recognize_text=False`, on the generic route and on the batch route, returns the detector's blocks in detector order.
 
+`pipeline.n_best = n` (this package's extension, 0 = off by default; n <= 8, the beam width the pipeline decodes with): recognised
+words come back as AltWords (detectors/_types.py) whose `alternatives` are the n best final hypotheses of the recogniser's beam search
+in its own order, duplicates of an earlier text dropped, entry 0 the word's own text and confidence.  They are
+read out of the workspace the decode leaves behind: the decode itself, and with it every other field of the pages, does not change.
+Works on the native batch path with every other switch, and on the generic route when the recogniser is this package's TRBA; a
+foreign recogniser is not asked for alternatives.
+
 `process_batch` is broken upstream (it calls a non-existent `self.process`, _pipeline.py:187);
 here it is the per-image `predict`.  `predict_batch` is the MI355X fast path: when detector and
 recogniser are this package's EAST/TRBA it runs the detector once for all pages and the
@@ -109,6 +116,7 @@ class _Batch:
     profile: bool
     rectify: bool                    # rectify_crops as it was at submit
     line_recs: Optional[dict]        # group_lines as it was at submit: page index -> per block its [L,6] line records; None = off
+    n_best: int                      # n_best as it was at submit
     ingest_pending: Any              # the device JPEG stages' deferred verdict, read in advance_batch
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
@@ -133,6 +141,7 @@ class Pipeline:
         self.rectify_crops = False         # crops cut along the detected quadrilaterals (user extension, see the module docstring)
         self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
         self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
+        self.n_best = 0                    # > 0: recognised words come back as AltWords with the beam search's n best readings (user extension)
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -187,6 +196,15 @@ class Pipeline:
             word.text = text
             word.recognition_confidence = confidence
 
+    _BEAM_SIZE = 8  # the width the recogniser is called with: its default
+
+    def _n_best(self):
+        """The `n_best` switch for a call that recognises with this package's TRBA."""
+        n = int(self.n_best)
+        if not 0 <= n <= self._BEAM_SIZE:
+            raise ValueError(f"Pipeline.n_best must be between 0 and {self._BEAM_SIZE}, the recogniser's beam width, got {n}")
+        return n
+
     # ------------------------------------------------------------------------------------- API
     def predict(self, image: Union[str, np.ndarray, Image.Image], recognize_text: bool = True, vis: bool = False,
                 profile: bool = False):
@@ -221,10 +239,13 @@ class Pipeline:
             print(f"Extract {len(crops)} crops: {time.time() - t0:.3f}s")
         if crops:
             t0 = time.time()
-            results = self.recognizer.predict(crops)
+            n_best = self._n_best() if isinstance(self.recognizer, TRBA) else 0  # a foreign recogniser is not asked
+            results = self.recognizer.predict(crops, n_best=n_best) if n_best else self.recognizer.predict(crops)
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
             self._assign(words, [results[i] for i in range(len(words))])
+            if n_best:
+                self._attach_details(words, [page], alts=[results[i]["alternatives"] for i in range(len(words))])
         if line_recs is not None:
             self._split_lines(page, line_recs)
         if profile:
@@ -323,7 +344,7 @@ class Pipeline:
         batch i+1 can be enqueued before `collect_batch` of batch i and fills the device while batch i drains."""
         if not (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)):
             raise TypeError("submit_batch/collect_batch need this package's EAST and TRBA plugins")
-        det = self.detector
+        det, n_best = self.detector, self._n_best()
         # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
         dec, ingest_pending = [None] * len(images), None
@@ -405,7 +426,7 @@ class Pipeline:
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
                 groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
-        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, ingest_pending,
+        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
 
     def advance_batch(self, h):
@@ -578,7 +599,9 @@ class Pipeline:
                     details = grp.handle.char_details
                     with torch.cuda.stream(st):
                         t0 = time.perf_counter()
-                        fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0])
+                        fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0], n_best=h.n_best)
+                        if h.n_best:
+                            fin, (alt_ids, _alt_prob, alt_conf, alt_logp) = fin[:-4], fin[-4:]
                         if details:
                             ids, trun, conf, prob, centre, _peak = fin
                             desc = grp.desc_host if grp.desc_host is not None else grp.desc_dev.cpu().numpy()
@@ -591,17 +614,22 @@ class Pipeline:
                     for word, text, c in zip(grp.words, texts, conf.tolist()):
                         word.text = text
                         word.recognition_confidence = c
+                    chars = alts = None
                     if details and qdesc is not None:  # rectified: x through the quad's patch instead of the AABB window
-                        self._attach_chars(grp.words, rec.chars(ids, trun, prob, centre, qdesc[:, 9], None, None, qdesc=qdesc), pages[lo:hi])
+                        chars = rec.chars(ids, trun, prob, centre, qdesc[:, 9], None, None, qdesc=qdesc)
                     elif details:
-                        self._attach_chars(grp.words, rec.chars(ids, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3]), pages[lo:hi])
+                        chars = rec.chars(ids, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3])
+                    if h.n_best:
+                        alts = rec.alternatives(alt_ids, trun, alt_conf, alt_logp)
+                    if details or h.n_best:
+                        self._attach_details(grp.words, pages[lo:hi], chars, alts)
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
             for grp in h.groups:
                 if grp.det_stream is not main:
                     main.wait_stream(grp.det_stream)
-            if h.line_recs:  # after _attach_chars, so that the lines hold the CharWords
+            if h.line_recs:  # after _attach_details, so that the lines hold the CharWords / AltWords
                 for pi, recs in h.line_recs.items():
                     self._split_lines(pages[pi], recs)
         self.last_profile = tm
@@ -610,17 +638,22 @@ class Pipeline:
         return pages
 
     @staticmethod
-    def _attach_chars(words, chars, pages):
-        """Replace every recognised Word of `pages` by a CharWord carrying its symbols.  chars[k] belongs to words[k]; x is in page
-        pixels (the recogniser mapped the attention centroid into the word's clamped crop window)."""
-        from .detectors._types import Char, CharWord
+    def _attach_details(words, pages, chars=None, alts=None):
+        """Replace every recognised Word of `pages` by a CharWord carrying its symbols (`chars`, char_details), or by an AltWord that
+        also carries its readings (`alts`, n_best; its `chars` stay empty without char_details).  chars[k] / alts[k] belong to
+        words[k]; x is in page pixels (the recogniser mapped the attention centroid into the word's clamped crop window)."""
+        from .detectors._types import Alternative, AltWord, Char, CharWord
         new = {}
-        for word, ch in zip(words, chars):
+        for k, word in enumerate(words):
+            extra = {} if chars is None else {"chars": [Char(**d) for d in chars[k]]}
+            if alts is not None:
+                extra["alternatives"] = [Alternative(**d) for d in alts[k]]
             # the [0, 1] clamp is a no-op guard for CharWord's validation: the confidence is a mean of exp(log-softmax) values, each
             # <= 1 by the kernel's arithmetic (logp <= 0), so the value equals the plain Word's and a default dump does not change
             c = word.recognition_confidence
-            new[id(word)] = CharWord(polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
-                                     recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), chars=[Char(**d) for d in ch])
+            new[id(word)] = (CharWord if alts is None else AltWord)(
+                polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
+                recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), **extra)
         for page in pages:
             for block in page.blocks:
                 block.words = [new.get(id(w), w) for w in block.words]

@@ -467,17 +467,30 @@ extern "C" int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* 
                                 fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
 }
 
+// the four parts of a finished beam workspace (device memory, or a host copy of it), for the steps that read it back
+struct BeamTrace {
+  const float* logits;     // [B][steps][K][V]: row k of step t = the logits of the hypothesis in slot k when step t is computed
+  const int32_t* back;     // [B][steps][K]: the row of logits[t] that the survivor in slot k of step t was extended from
+  const int32_t* tokv;     // [B][steps][K]: the token it was extended by
+  const int32_t* best_at;  // [B][steps]: the slot with the largest score after step t
+};
+static inline BeamTrace beam_ws_trace(const void* workspace, int B, int steps, int K, int V) {
+  const char* p = (const char*)workspace;
+  BeamTrace w;
+  w.logits = (const float*)p; p += beam_ws_logits(B, steps, K, V);
+  w.back = (const int32_t*)p; p += (int64_t)B * steps * K * 4;
+  w.tokv = (const int32_t*)p; p += (int64_t)B * steps * K * 4;
+  w.best_at = (const int32_t*)p;
+  return w;
+}
+
 static int attn_beam_finalize_impl(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev, float* logits_out,
                                    int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out, void* stream) {
   if (!workspace || !trun_dev || !logits_out || !ids_out || B <= 0 || V <= 0 || steps <= 0 || steps > 64 || beam < 1 || beam > 16)
     return MSOCR_E_ARG;
-  const char* p = (const char*)workspace;
-  const float* wl = (const float*)p; p += beam_ws_logits(B, steps, beam, V);
-  const int32_t* back = (const int32_t*)p; p += (int64_t)B * steps * beam * 4;
-  const int32_t* tokv = (const int32_t*)p; p += (int64_t)B * steps * beam * 4;
-  const int32_t* best_at = (const int32_t*)p;
-  MSOCR_LAUNCH(attn_beam_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, wl, back, tokv, best_at, trun_dev, V, steps, beam,
-               logits_out, ids_out, (const float*)alpha_ws, T, alpha_out);
+  const BeamTrace w = beam_ws_trace(workspace, B, steps, beam, V);
+  MSOCR_LAUNCH(attn_beam_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, w.logits, w.back, w.tokv, w.best_at, trun_dev, V,
+               steps, beam, logits_out, ids_out, (const float*)alpha_ws, T, alpha_out);
   return LAUNCH_OK();
 }
 extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
@@ -496,8 +509,8 @@ extern "C" int msocr_attn_beam_finalize_alpha(const void* workspace, int B, int 
 // TRBA.predict's confidence (recognizers/_trba/__init__.py:413-431): log_softmax over V of the returned logits,
 // exp of the chosen token's log-prob, mean over ALL t_run generated positions.  One wave per row.
 
-// exp(log_softmax(x[0 .. V))[id]) by one wave, in every lane: the probability of the chosen token of one decode step
-__device__ __forceinline__ float token_prob(const float* __restrict__ x, int V, int id, int lane) {
+// log_softmax(x[0 .. V))[id] by one wave, in every lane: the log-probability of the chosen token of one decode step
+__device__ __forceinline__ float token_logp(const float* __restrict__ x, int V, int id, int lane) {
   float m = -INFINITY;
   for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
 #pragma unroll
@@ -505,9 +518,12 @@ __device__ __forceinline__ float token_prob(const float* __restrict__ x, int V, 
   float s = 0.f;
   for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
   s = wave_sum(s);
-  const float logp = (x[id] - m) - logf(s);
-  return expf(logp);
+  return (x[id] - m) - logf(s);
 }
+// its exponential: the probability of that token
+__device__ __forceinline__ float token_prob(const float* __restrict__ x, int V, int id, int lane) { return expf(token_logp(x, V, id, lane)); }
+// the confidence of a row from the f32 sum, in step order, of its t_run token probabilities
+__host__ __device__ __forceinline__ float mean_prob(float acc, int tr) { return tr > 0 ? acc / (float)tr : 0.f; }
 
 __global__ __launch_bounds__(64) void seq_confidence_kernel(const float* __restrict__ logits, const int32_t* __restrict__ ids,
                                                              const int32_t* __restrict__ trun, int V, int steps,
@@ -516,7 +532,7 @@ __global__ __launch_bounds__(64) void seq_confidence_kernel(const float* __restr
   const int tr = trun[b];
   float acc = 0.f;
   for (int t = 0; t < tr; ++t) acc += token_prob(logits + ((long)b * steps + t) * V, V, ids[(long)b * steps + t], lane);
-  if (lane == 0) conf[b] = tr > 0 ? acc / (float)tr : 0.f;
+  if (lane == 0) conf[b] = mean_prob(acc, tr);
 }
 
 extern "C" int msocr_seq_confidence(const float* logits, const int32_t* ids, const int32_t* trun_dev, int B, int V, int steps,
@@ -567,4 +583,137 @@ extern "C" int msocr_seq_char_details(const float* logits, const int32_t* ids, c
   MSOCR_LAUNCH(seq_char_details_kernel, dim3((unsigned)((n + CD_WAVES - 1) / CD_WAVES)), dim3(64 * CD_WAVES), 0, (hipStream_t)stream, logits,
                ids, alpha, trun_dev, B, V, steps, T, prob_out, centre_out, peak_out);
   return LAUNCH_OK();
+}
+
+// --------------------------------------------------------------------------------------------- n-best readings
+// A second read-out of the beam workspace: the K hypotheses a row's search ends with, not only the best.  Both beam kernels pick a
+// step's K survivors by K rounds of arg-max with winner removal (larger value first, then the smaller flat index), so the slots of
+// a step are in rank order and the r-th best final hypothesis is the back-trace from slot r of step t_run-1; nothing is re-ranked.
+//   rank 0  = the slot best_at[t_run-1], attn_beam_finalize_kernel's own start (the same walk, the same ids)
+//   rank 1..= the remaining slots in slot order
+// Per (row, rank): ids and token_prob of every step of the path, the confidence of the path (mean_prob of the f32 sum in step
+// order: seq_confidence_kernel's arithmetic) and its summed log-probability, the quantity the search ranks by: the token_logp terms
+// up to and including the path's first EOS (a finished hypothesis is extended by EOS at log-probability 0, model.py:145-156),
+// accumulated in f64 in step order and rounded once.  Steps t >= t_run: id -1, probability 0.
+// One workgroup per (row, rank): one thread walks the back-pointers into LDS, the waves take the steps round-robin (token_logp, one
+// wave per step), one thread does the two ordered sums.
+
+__host__ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the path of rank `rank` of row b: row[t] = its row of logits[t], tok[t] = its token, t < tr (1 <= tr <= steps).  Slots read from the
+// workspace are clamped to [0, K): a workspace that holds no finished search cannot send the walk out of bounds.
+__host__ __device__ inline void nbest_walk(const BeamTrace& w, int b, int steps, int K, int tr, int rank, int* row, int* tok) {
+  const int best = clampi(w.best_at[(long)b * steps + tr - 1], 0, K - 1);
+  int cur = rank == 0 ? best : (rank <= best ? rank - 1 : rank);
+  for (int t = tr - 1; t >= 0; --t) {
+    const long o = ((long)b * steps + t) * K + cur;
+    tok[t] = w.tokv[o];
+    cur = row[t] = clampi(w.back[o], 0, K - 1);
+  }
+}
+// the two ordered sums over a path's steps: p[t] = token_prob, lp[t] = token_logp of step t
+__host__ __device__ inline void nbest_sums(const float* p, const float* lp, const int* tok, int tr, int eos_id, float* conf, float* logp) {
+  float acc = 0.f;
+  double sum = 0.0;
+  bool open = true;  // no EOS yet
+  for (int t = 0; t < tr; ++t) {
+    acc += p[t];
+    if (open) {
+      sum += (double)lp[t];
+      open = tok[t] != eos_id;
+    }
+  }
+  *conf = mean_prob(acc, tr);
+  *logp = (float)sum;
+}
+
+constexpr int NB_WAVES = 4;
+__global__ __launch_bounds__(64 * NB_WAVES) void attn_beam_nbest_kernel(BeamTrace w, const int32_t* __restrict__ trun, int V, int steps, int K,
+                                                                        int n_best, int eos_id, int32_t* __restrict__ ids_out,
+                                                                        float* __restrict__ prob_out, float* __restrict__ conf_out,
+                                                                        float* __restrict__ logp_out) {
+  const int b = blockIdx.x / n_best, rank = blockIdx.x - b * n_best;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int s_row[64], s_tok[64];
+  __shared__ float s_p[64], s_lp[64];
+  const int tr = clampi(trun[b], 1, steps);
+  const long o = (long)blockIdx.x * steps;  // (b * n_best + rank) * steps
+  if (threadIdx.x == 0) nbest_walk(w, b, steps, K, tr, rank, s_row, s_tok);
+  __syncthreads();
+  for (int t = wave; t < steps; t += NB_WAVES) {
+    float lp = 0.f, p = 0.f;
+    int id = -1;
+    if (t < tr) {  // wave-uniform
+      id = s_tok[t];
+      lp = token_logp(w.logits + (((long)b * steps + t) * K + s_row[t]) * V, V, clampi(id, 0, V - 1), lane);
+      p = expf(lp);  // token_prob
+    }
+    if (lane == 0) {
+      s_lp[t] = lp;
+      s_p[t] = p;
+      ids_out[o + t] = id;
+      prob_out[o + t] = p;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) nbest_sums(s_p, s_lp, s_tok, tr, eos_id, conf_out + blockIdx.x, logp_out + blockIdx.x);
+}
+
+static bool nbest_args_ok(const void* workspace, int B, int V, int steps, int beam, int n_best, const int32_t* trun,
+                          const int32_t* ids_out, const float* prob_out, const float* conf_out, const float* logp_out) {
+  return workspace && trun && ids_out && prob_out && conf_out && logp_out && B > 0 && V > 0 && V <= 512 && steps > 0 && steps <= 64 &&
+         beam >= 1 && beam <= 16 && n_best >= 1 && n_best <= beam;
+}
+
+extern "C" int msocr_attn_beam_nbest(const void* workspace, int B, int V, int steps, int beam, int n_best, int eos_id,
+                                     const int32_t* trun_dev, int32_t* ids_out, float* prob_out, float* conf_out, float* logp_out,
+                                     void* stream) {
+  if (!nbest_args_ok(workspace, B, V, steps, beam, n_best, trun_dev, ids_out, prob_out, conf_out, logp_out)) return MSOCR_E_ARG;
+  if ((int64_t)B * n_best > 0x7fffffff) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(attn_beam_nbest_kernel, dim3((unsigned)(B * n_best)), dim3(64 * NB_WAVES), 0, (hipStream_t)stream,
+               beam_ws_trace(workspace, B, steps, beam, V), trun_dev, V, steps, beam, n_best, eos_id, ids_out, prob_out, conf_out, logp_out);
+  return LAUNCH_OK();
+}
+
+// token_logp as one wave evaluates it, on the host: 64 strided partial sums combined by the xor butterfly of wave_sum, so that the
+// twin differs from the kernel only by what expf / logf differ between the device and libm
+static float token_logp_host(const float* x, int V, int id) {
+  float m = -INFINITY;
+  for (int v = 0; v < V; ++v) m = fmaxf(m, x[v]);
+  float part[64], next[64];
+  for (int l = 0; l < 64; ++l) {
+    part[l] = 0.f;
+    for (int v = l; v < V; v += 64) part[l] += expf(x[v] - m);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int l = 0; l < 64; ++l) next[l] = part[l] + part[l ^ o];
+    for (int l = 0; l < 64; ++l) part[l] = next[l];
+  }
+  return (x[id] - m) - logf(part[0]);
+}
+
+// msocr_attn_beam_nbest over host copies of the workspace and of t_run: the same walk, the same order of sums
+extern "C" int msocr_attn_beam_nbest_host(const void* workspace_host, int B, int V, int steps, int beam, int n_best, int eos_id,
+                                          const int32_t* trun_host, int32_t* ids_out_host, float* prob_out_host, float* conf_out_host,
+                                          float* logp_out_host) {
+  if (!nbest_args_ok(workspace_host, B, V, steps, beam, n_best, trun_host, ids_out_host, prob_out_host, conf_out_host, logp_out_host))
+    return MSOCR_E_ARG;
+  const BeamTrace w = beam_ws_trace(workspace_host, B, steps, beam, V);
+  for (int b = 0; b < B; ++b)
+    for (int rank = 0; rank < n_best; ++rank) {
+      int row[64], tok[64];
+      float p[64], lp[64];
+      const int tr = clampi(trun_host[b], 1, steps);
+      const long q = (long)b * n_best + rank, o = q * steps;
+      nbest_walk(w, b, steps, beam, tr, rank, row, tok);
+      for (int t = 0; t < steps; ++t) {
+        const bool on = t < tr;
+        lp[t] = on ? token_logp_host(w.logits + (((long)b * steps + t) * beam + row[t]) * V, V, clampi(tok[t], 0, V - 1)) : 0.f;
+        p[t] = on ? expf(lp[t]) : 0.f;
+        ids_out_host[o + t] = on ? tok[t] : -1;
+        prob_out_host[o + t] = p[t];
+      }
+      nbest_sums(p, lp, tok, tr, eos_id, conf_out_host + q, logp_out_host + q);
+    }
+  return MSOCR_OK;
 }

@@ -35,6 +35,22 @@ class CharWord(Word):
     chars: List[Char] = Field(default_factory=list, description="one entry per symbol of `text`, in order")
 
 
+class Alternative(BaseModel):
+    """One reading of a word from the recogniser's beam search (this package's extension; the reference returns one per word)."""
+
+    text: str = Field(..., description="the hypothesis's transcription")
+    confidence: float = Field(..., description="mean per-step token probability along the hypothesis, as recognition_confidence", **_UNIT)
+    logp: float = Field(..., description="summed log-probability of the hypothesis's tokens up to its EOS: the score the search ranks by")
+
+
+class AltWord(CharWord):
+    """A Word with the beam search's best final readings, written by Pipeline when `n_best` is on: alternatives[0] is the word's own
+    text and confidence, the others follow in the search's order.  `chars` stays empty unless `char_details` is also on, and
+    describes the best reading only.  As for CharWord, a default model_dump() of a Page does not change with the switch."""
+
+    alternatives: List[Alternative] = Field(default_factory=list, description="distinct readings, best first")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

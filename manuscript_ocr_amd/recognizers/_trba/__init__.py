@@ -8,7 +8,8 @@ decoder (greedy and beam) run on the MI355X through libmsocr.so; there is no CPU
 Extensions (keyword-only): precision="fp32"|"bf16" for the CNN (recurrent/attention stages are
 always exact f32), state_dict=... / config=... for in-memory weights (nothing can be downloaded
 offline), device_batch=2048 rows per launch sequence, predict(..., return_chars=True) for per-symbol
-confidence and position (from the decoder's attention weights).  Confidences reproduce the reference's
+confidence and position (from the decoder's attention weights), predict(..., n_best=n) for the beam search's n
+best final readings with their scores.  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -255,7 +256,8 @@ class TRBA:
         batches, while kernels are being profiled, and for the first call of a bucket (lazy one-time kernel attributes must not
         fall into a capture), and whenever char_details or rectified crops (Pipeline.rectify_crops: the captured graph holds the AABB
         crop kernel, not msocr_quad_crop) are asked for (those paths are not captured).  Results are bit-identical to the eager path
-        (tests/test_gpu_pipeline.py)."""
+        (tests/test_gpu_pipeline.py).  `recognize_finish(n_best=...)` needs nothing from this route: the captured graph ends at the
+        decode, and the beam workspace the alternatives are read from is in the handle it returns."""
         M = int(desc_dev.shape[0])
         Mcap = (M + 31) // 32 * 32
         if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details or rectified:
@@ -316,7 +318,7 @@ class TRBA:
         inst.graph.replay()
         return _Recognition([part], [(0, Mcap)], Mcap, M, "beam", beam_size, graph_inst=Lease(inst))
 
-    def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False):
+    def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False, n_best=0):
         """Phases 2-3 — derive the reference's per-chunk run lengths, back-track (beam) and reduce confidences.
 
         `spans` = [(start, count), ...] groups of rows that the reference would have passed to ONE predict() call
@@ -326,14 +328,20 @@ class TRBA:
         A handle started with char_details=True: three more host arrays [N, steps] behind the others — prob (f32: the probability
         of the token of every step, whose mean over t < t_run is the confidence), centre (f32: the attention centroid in encoder
         frames) and peak (i32: the arg-max frame); steps t >= t_run hold 0, 0, -1 (msocr_seq_char_details; the weights stay on the
-        device)."""
+        device).
+        n_best >= 1 (beam handles, n_best <= the handle's beam width): four more host arrays behind everything else — alt_ids
+        [N, n_best, steps] i32, alt_prob [N, n_best, steps] f32, alt_conf [N, n_best] f32 and alt_logp [N, n_best] f32, the search's
+        n_best best final hypotheses per row in its own order (msocr_attn_beam_nbest; `alternatives` turns them into texts).  Rank 0
+        is the row's own ids and confidence."""
         try:
-            return self._recognize_finish(handle, batch_size, spans, return_logits)
+            if n_best < 0 or (n_best and (handle.mode != "beam" or n_best > handle.beam)):
+                raise ValueError(f"n_best = {n_best} needs a beam decode of at least that width (mode {handle.mode!r}, beam_size {handle.beam})")
+            return self._recognize_finish(handle, batch_size, spans, return_logits, int(n_best))
         finally:
             if handle.graph_inst is not None:  # also on an exception: the instance must not stay leased for ever
                 handle.graph_inst.release()
 
-    def _recognize_finish(self, handle, batch_size, spans, return_logits):
+    def _recognize_finish(self, handle, batch_size, spans, return_logits, n_best=0):
         parts, N, M_real, mode, beam_size = handle.parts, handle.N, handle.rows, handle.mode, handle.beam
         spans = spans if spans is not None else [(0, M_real)]
         steps = self.max_length + 1 if mode == "greedy" else self.max_length
@@ -351,7 +359,7 @@ class TRBA:
         self.last_rows += M_real
         trun_dev = torch.from_numpy(trun).to(self.device)
         details = handle.char_details
-        ids_out, conf_out, logit_out, det_out = [], [], [], []
+        ids_out, conf_out, logit_out, det_out, alt_out = [], [], [], [], []
         for k, (s, hi) in enumerate(handle.bounds):
             B = hi - s
             tr = trun_dev[s:s + B]
@@ -376,6 +384,8 @@ class TRBA:
                 det_out.append((prob, centre, peak))
             if return_logits:
                 logit_out.append(lg.cpu().numpy())
+            if n_best:
+                alt_out.append(self.model.beam_nbest(part.ws, B, steps, beam_size, tr, n_best, self.eos_id))
             parts[k] = part = None
         ids_h = torch.cat(ids_out).cpu().numpy()[:M_real]
         conf_h = torch.cat(conf_out).cpu().numpy()[:M_real]
@@ -384,16 +394,19 @@ class TRBA:
             out += (np.concatenate(logit_out)[:M_real],)
         if details:
             out += tuple(torch.cat([d[i] for d in det_out]).cpu().numpy()[:M_real] for i in range(3))
+        if n_best:
+            out += tuple(torch.cat([a[i] for a in alt_out]).cpu().numpy()[:M_real] for i in range(4))
         return out
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
-                           spans=None, return_logits=False, char_details=False):
-        """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak])
-        on host."""
+                           spans=None, return_logits=False, char_details=False, n_best=0):
+        """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak]
+        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host."""
+        self._check_n_best(n_best, mode, beam_size)
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
                                                           spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
                                                           char_details=char_details),
-                                     batch_size, spans, return_logits)
+                                     batch_size, spans, return_logits, n_best=n_best)
 
     def texts(self, ids, trun) -> List[str]:
         """decode_tokens (transforms.py:196-206) over the first t_run ids of every row, vectorised: the text ends at the
@@ -406,6 +419,38 @@ class TRBA:
         itos, skip = self.itos, {self.pad_id, self.blank_id}
         rows = ids.tolist()
         return ["".join([itos[t] for t in row[:e] if t not in skip]) for row, e in zip(rows, end.tolist())]
+
+    @staticmethod
+    def _check_n_best(n_best, mode, beam_size):
+        if n_best < 0:
+            raise ValueError(f"n_best must not be negative, got {n_best}")
+        if n_best and mode == "greedy":
+            raise ValueError("n_best needs mode='beam': the greedy decode has one hypothesis")
+        if n_best > beam_size:
+            raise ValueError(f"n_best = {n_best} exceeds beam_size = {beam_size}: the search keeps beam_size hypotheses")
+
+    def alternatives(self, alt_ids, trun, alt_conf, alt_logp) -> List[List[Dict[str, Any]]]:
+        """Per row, its readings as {"text", "confidence", "logp"} in rank order, from recognize_finish(n_best=...)'s arrays: text by
+        `texts` over the rank's ids, confidence as the word's own is computed, logp the hypothesis's summed log-probability.  Entry 0
+        is the word's own text and confidence and is always kept; a later rank whose text equals an earlier one of its row is
+        dropped (two hypotheses can differ only in PAD tokens, or behind their EOS)."""
+        alt_ids = np.asarray(alt_ids)
+        N, n = alt_ids.shape[:2]
+        if not N or not n:
+            return [[] for _ in range(N)]
+        texts = self.texts(alt_ids.reshape(N * n, -1), np.repeat(np.asarray(trun), n))
+        cs = np.clip(np.asarray(alt_conf, dtype=np.float64), 0.0, 1.0).tolist()  # means of exp(log-softmax): within [0, 1] up to rounding
+        ls = np.asarray(alt_logp, dtype=np.float64).tolist()
+        out = []
+        for b in range(N):
+            seen, row = set(), []
+            for r in range(n):
+                t = texts[b * n + r]
+                if t not in seen:
+                    seen.add(t)
+                    row.append({"text": t, "confidence": cs[b][r], "logp": ls[b][r]})
+            out.append(row)
+        return out
 
     def _results(self, ids, trun, conf) -> List[Dict[str, Any]]:
         """__init__.py:415-432: decode_tokens over the t_run generated ids; confidence computed on the device."""
@@ -434,25 +479,35 @@ class TRBA:
 
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
-                alpha: float = 0.9, *, return_chars: bool = False) -> List[Dict[str, Any]]:
+                alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0) -> List[Dict[str, Any]]:
         """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
         result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
         decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
-        through transforms.FRAME_STRIDE and the resize; an estimate, not a measured glyph position)."""
+        through transforms.FRAME_STRIDE and the resize; an estimate, not a measured glyph position).
+        n_best >= 1 (keyword-only extension, mode="beam", n_best <= beam_size): every result also has "alternatives", a list of
+        {"text", "confidence", "logp"}: the beam search's n_best best final hypotheses in its own order, duplicates of an earlier text
+        dropped (`alternatives`); entry 0 is the result's own text and confidence.  "chars" describes the best reading only."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
+        self._check_n_best(n_best, mode, beam_size)
         if not images_list:
             return []
         arrays = [self._load_rgb(im) for im in images_list]
         canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
-        if not return_chars:
+        if not return_chars and not n_best:
             return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
-        ids, trun, conf, prob, centre, _peak = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha,
-                                                                       char_details=True)
-        src_w = [a.shape[1] for a in arrays]
-        new_w = [resized_size(a.shape[0], a.shape[1], self.img_h, self.img_w)[0] for a in arrays]
+        fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best)
+        ids, trun, conf = fin[:3]
         results = self._results(ids, trun, conf)
-        for r, ch in zip(results, self.chars(ids, trun, prob, centre, new_w, np.zeros(len(arrays)), src_w)):
-            r["chars"] = ch
+        if return_chars:
+            prob, centre = fin[3:5]
+            src_w = [a.shape[1] for a in arrays]
+            new_w = [resized_size(a.shape[0], a.shape[1], self.img_h, self.img_w)[0] for a in arrays]
+            for r, ch in zip(results, self.chars(ids, trun, prob, centre, new_w, np.zeros(len(arrays)), src_w)):
+                r["chars"] = ch
+        if n_best:
+            alt_ids, _alt_prob, alt_conf, alt_logp = fin[-4:]
+            for r, al in zip(results, self.alternatives(alt_ids, trun, alt_conf, alt_logp)):
+                r["alternatives"] = al
         return results

@@ -159,6 +159,9 @@ class TrbaNet:
     def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None):
         return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev, alpha_ws=alpha_ws)
 
+    def beam_nbest(self, ws, B, steps, beam_size, trun_dev, n_best, eos_id):
+        return self.dec.beam_nbest(ws, B, steps, beam_size, trun_dev, n_best, eos_id)
+
 
 def check_decoder_shape(hidden, num_classes):
     # hidden_size comes from the checkpoint's config.json (reference __init__.py:142-151, default 256).  256 / <= 256 tokens /
@@ -178,7 +181,7 @@ def _gemm(x2d, w, b):
 
 class AttnDecoder:
     """The attention decoder's device weights (f32, transposed for coalesced column reads) and its launches: greedy, beam,
-    beam_finalize.  Built from the `attn.*` keys of a TRBA state dict; needs no CNN.  split: the hoisted context GEMM's weight
+    beam_finalize, beam_nbest.  Built from the `attn.*` keys of a TRBA state dict; needs no CNN.  split: the hoisted context GEMM's weight
     (ops.attach_split); step_split: pack the split form of the three per-step matrices for the matrix-core kernels (precision
     "fp32" with an f32 CNN — TrbaNet decides)."""
 
@@ -336,6 +339,22 @@ class AttnDecoder:
                                                            logits.data_ptr(), ids.data_ptr(), alpha_ws.data_ptr(), T, al.data_ptr(),
                                                            ops._stream()), "attn_beam_finalize_alpha")
         return logits, ids, al
+
+    def beam_nbest(self, ws, B, steps, beam_size, trun_dev, n_best, eos_id):
+        """The `n_best` best final hypotheses of every row, read out of the workspace of `beam` (msocr_attn_beam_nbest; the decode is
+        not run again): device tensors ids [B, n_best, steps] i32 (-1 for t >= t_run), prob [B, n_best, steps] f32 (0 there), conf
+        [B, n_best] f32 and logp [B, n_best] f32.  Rank 0 is `beam_finalize`'s path with msocr_seq_confidence's confidence, the others
+        follow in the search's own order; logp is the summed log-probability up to the hypothesis's first `eos_id`."""
+        if not 1 <= n_best <= beam_size:
+            raise ValueError(f"n_best must be between 1 and beam_size = {beam_size}, got {n_best}")
+        ids = torch.empty((B, n_best, steps), dtype=torch.int32, device=self.device)
+        prob = torch.empty((B, n_best, steps), dtype=torch.float32, device=self.device)
+        conf = torch.empty((B, n_best), dtype=torch.float32, device=self.device)
+        logp = torch.empty((B, n_best), dtype=torch.float32, device=self.device)
+        nat.check(nat.lib().msocr_attn_beam_nbest(ws.data_ptr(), B, self.V, steps, beam_size, n_best, eos_id, trun_dev.data_ptr(),
+                                                  ids.data_ptr(), prob.data_ptr(), conf.data_ptr(), logp.data_ptr(), ops._stream()),
+                  "attn_beam_nbest")
+        return ids, prob, conf, logp
 
 
 def trba_cnn_macs(h, w):

@@ -1,12 +1,16 @@
 """Times the beam-8 decode launch (all 25 steps, no early exit) for B crops, split-operand form against exact-f32 MFMA (dev tool).
-  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy]
+  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest]
 --alpha: with the attention-weight output on (the _alpha entry points, into one preallocated buffer).  --repeats N: N timed repeats
 of 5 calls each per form, one line each (default 1).  --general: the general kernel (csrc/attn_general.hip) at the same shape
 instead of the matrix-core kernels (net.HOIST_CTX = False; one form, no split / exact comparison).  --greedy: the greedy decode
-(26 steps) instead of the beam decode: the matrix-core greedy kernel, or the general one with --general; timings only."""
+(26 steps) instead of the beam decode: the matrix-core greedy kernel, or the general one with --general; timings only.
+--nbest: after the decode timing of the first form, the read-out of its workspace: msocr_attn_beam_finalize + msocr_seq_confidence
+(what every word pays today) and msocr_attn_beam_nbest for n_best 1, 3 and 8, each as the mean of 20 calls after 3 warm-up calls."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from manuscript_ocr_amd import _native as nat
+from manuscript_ocr_amd import ops
 from manuscript_ocr_amd.recognizers._trba import net
 from manuscript_ocr_amd.recognizers._trba.net import AttnDecoder
 from manuscript_ocr_amd import synth
@@ -16,6 +20,7 @@ ap.add_argument("--alpha", action="store_true")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--general", action="store_true")
 ap.add_argument("--greedy", action="store_true")
+ap.add_argument("--nbest", action="store_true")
 a = ap.parse_args()
 if a.repeats < 1:
     ap.error("--repeats must be at least 1")
@@ -45,6 +50,37 @@ if a.greedy:
         torch.cuda.synchronize()
         print(f"{name} greedy: {e0.elapsed_time(e1) / 5:.3f} ms per call (GEMM + greedy kernel{' + alpha output' if ALPHA else ''}), B={B}")
     sys.exit(0)
+def timed(fn, calls=20, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def time_nbest(dec, ws, B):
+    """All 25 steps of every row (t_run = 25, as the decode above ran them): the read-out's largest case at this shape."""
+    trun = torch.full((B,), 25, dtype=torch.int32, device="cuda")
+    conf = torch.empty((B,), dtype=torch.float32, device="cuda")
+
+    def today():
+        lg, ids = dec.beam_finalize(ws, B, 25, 8, trun)
+        nat.check(nat.lib().msocr_seq_confidence(lg.data_ptr(), ids.data_ptr(), trun.data_ptr(), B, dec.V, 25, conf.data_ptr(), ops._stream()),
+                  "seq_confidence")
+
+    base = timed(today)
+    print(f"read-out, B={B}, V={dec.V}, K=8, 25 steps (ms per call, mean of 20):")
+    print(f"  beam_finalize + seq_confidence: {base:.3f}")
+    for n in (1, 3, 8):
+        ms = timed(lambda: dec.beam_nbest(ws, B, 25, 8, trun, n, 2))
+        print(f"  beam_nbest n_best={n}: {ms:.3f}  = {ms / base:.2f} x the pair above")
+
+
 res = {}
 aws = torch.empty((B, 25, 8, 13), dtype=torch.float32, device="cuda") if ALPHA else None
 kw = {"want_alpha": True, "alpha_ws": aws} if ALPHA else {}
@@ -65,6 +101,9 @@ for mode, dec in decs.items():
     trun = torch.full((B,), 25, dtype=torch.int32, device="cuda")
     logits, ids = dec.beam_finalize(ws, B, 25, 8, trun)
     res[mode] = (ms, logits.cpu(), ids.cpu())
+    if a.nbest:
+        time_nbest(dec, ws, B)
+        sys.exit(0)
 if a.general:
     sys.exit(0)
 same = (res["split"][2] == res["exact"][2]).all(dim=1)

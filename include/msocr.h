@@ -462,7 +462,9 @@ int msocr_quad_crop_host(const uint8_t* pages_host, int N, int H, int W, const i
  * dequantisation + inverse DCT (libjpeg "islow"), fancy chroma upsampling and YCbCr->RGB run on the DEVICE
  * (msocr_jpeg_reconstruct: coef_dev = the same array in device memory, workspace = msocr_jpeg_workspace_bytes(info) bytes,
  * rgb_out [height][width][3] u8).  msocr_jpeg_reconstruct_host is the HOST twin of the device stage (same code; all pointers
- * host memory).  Unsupported or corrupt streams: MSOCR_E_ARG / info.supported = 0 -> use the host decoder.
+ * host memory).  Unsupported or corrupt streams: MSOCR_E_ARG / info.supported = 0 -> use the host decoder.  The reconstruction
+ * entries take the sampling forms a parse produces and no other (first component 1x1, 2x1 or 2x2, every other one 1x1): an
+ * `info` with anything else, h1v2 for one, is MSOCR_E_ARG and nothing is launched or written.
  * Exif orientation (tag 0x0112 of IFD0 in an APP1 "Exif" segment), which the reference's reader applies: msocr_jpeg_parse_host
  * refuses a stream whose orientation is 2..8 (msocr_jpeg_reconstruct writes upright pages only).  msocr_jpeg_parse_oriented_host is
  * the same marker walk that reports the orientation instead: *orientation_out = 1..8 (1 for an absent tag, a value outside 2..8 or

@@ -1176,9 +1176,13 @@ int64_t planes_bytes(const msocr_jpeg_info& f) {
 
 bool info_ok(const msocr_jpeg_info* f) {
   if (!f || f->supported != 1 || (f->ncomp != 1 && f->ncomp != 3) || f->width <= 0 || f->height <= 0) return false;
+  // the sampling forms a parse produces, the only ones chroma_at knows: 1x1 (grey, 4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) for the
+  // first component, 1x1 for the others
+  if (!((f->hs[0] == 1 && f->vs[0] == 1) || (f->hs[0] == 2 && f->vs[0] == 1) || (f->hs[0] == 2 && f->vs[0] == 2))) return false;
   int64_t off = 0;
   for (int c = 0; c < f->ncomp; ++c) {
-    if (f->hs[c] < 1 || f->hs[c] > 2 || f->vs[c] < 1 || f->vs[c] > 2 || f->blocks_w[c] <= 0 || f->blocks_h[c] <= 0) return false;
+    if (c > 0 && (f->hs[c] != 1 || f->vs[c] != 1)) return false;
+    if (f->blocks_w[c] <= 0 || f->blocks_h[c] <= 0) return false;
     if (f->coef_off[c] != off) return false;
     if ((int64_t)f->blocks_w[c] * 8 * f->hs[0] / f->hs[c] < f->width || (int64_t)f->blocks_h[c] * 8 * f->vs[0] / f->vs[c] < f->height) return false;
     off += (int64_t)f->blocks_w[c] * f->blocks_h[c] * 64;

@@ -86,6 +86,26 @@ int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const voi
 int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* residual,
                                     void* out, void* stream);
 
+/* Square tiles + tail column: the 4X4 form for maps with W % 4 == 1 (W >= 5) without its padded last tile.  Output columns
+ * 0 ... W-2 are W/4 square tiles per tile row, bit for bit what the 4X4 form stores there; column W-1 is one F(4,3) x F(1,3) tile per
+ * tile row (the 6-point transform along H, the three taps along W summed directly: 18 points).  36 * (W/4) + 18 point rows per tile row
+ * instead of 36 * (W/4 + 1).  Split-operand GEMMs only (Cin % 32 == 0, Cout % 64 == 0):
+ *   u44 = the 4X4 form's planes [3][36][Cin/32][Cout][32];
+ *   u41 = planes [3][18][Cin/32][Cout][32] of msocr_winograd_coltail_weights_host's [18][Cout][Cin] f32 (a HOST function, f64, rounded
+ *         once): U[xi*3+kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c].
+ * workspace: msocr_winograd_coltail_workspace_bytes(d) bytes, 16-B aligned, linear in N (-1 = no such form for the shape):
+ *   V44 [36][Mt44][Cin] | Mw44 [36][Mt44][Cout] | V41 [18][Mt41][Cin] | Mw41 [18][Mt41][Cout],  Mt44 = N ceil(H/4) (W/4), Mt41 = N ceil(H/4).
+ * One input-transform and one output-transform launch over the tiles of both parts, two batched GEMM launches (36 x Mt44 rows, 18 x Mt41
+ * rows).  Descriptor rules, epilogue flags and the stage-by-stage entry points as msocr_conv3x3_winograd. */
+int64_t msocr_winograd_coltail_workspace_bytes(const msocr_conv_desc* d);
+int msocr_winograd_coltail_weights_host(const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
+int msocr_conv3x3_winograd_coltail(const msocr_conv_desc* d, const void* in, const void* u44, const void* u41, const float* bias,
+                                   const void* residual, void* out, void* workspace, void* stream);
+int msocr_winograd_coltail_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream);
+int msocr_winograd_coltail_gemm(const msocr_conv_desc* d, const void* u44, const void* u41, void* workspace, void* stream);
+int msocr_winograd_coltail_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
+                                            void* out, void* stream);
+
 /* ---- split-operand f32 ("bf16x3"): the default arithmetic of the f32 1x1 convolutions and Winograd-domain GEMMs --------------
  * gfx950 runs exact-f32 MFMA at 1/16 of the bf16 rate.  An f32 value is the exact sum of three bf16 values (round-to-nearest
  * residual chain); of the nine cross products of two such sums the six largest are accumulated in f32 on the bf16 matrix pipes,

@@ -53,6 +53,12 @@ _SIGS = {
     "msocr_winograd_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_coltail_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
+    "msocr_winograd_coltail_weights_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    "msocr_conv3x3_winograd_coltail": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_coltail_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
+    "msocr_winograd_coltail_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_coltail_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "msocr_conv3x3_winograd_fused64": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_gemm_output": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -20,6 +20,11 @@
 //                         {0, +-3/2, +-2/3, inf} — reciprocal pairs keep the Vandermonde entries within [8/27, 27/8] — an f32 simulation of
 //                         the whole pipeline of transforms measures 1.05x the tall form's error (and 0.5x for the tall form itself on these
 //                         points; tools/winograd_points.py, profiles/r04_winograd_points.txt).
+//   4X4 + tail column     maps with W % 4 == 1 (the recogniser's 4 x 13): W/4 square tiles per tile row, then output column W - 1 as one
+//                         F(4,3) x F(1,3) tile — the 6-point transform along H, the three taps along W summed directly, 18 points —
+//                         instead of a fourth square tile that holds one real column: 36 * (W/4) + 18 point rows per tile row, not
+//                         36 * (W/4 + 1).  Not a fourth form id: its own entry points (msocr_winograd_coltail_*), one transform launch per
+//                         direction over the tiles of both parts (wino44_*_kernel_coltail), two batched GEMM launches.
 // ops.conv2d() picks the tall form for the Cin = 64 layers (fused kernels, below) and where the square form does not pay; the 2x2
 // form when 24 * ceil(H/4) >= 16 * ceil(H/2).
 //
@@ -81,10 +86,17 @@ __device__ __forceinline__ void wino44_at(const f32x4 m[6], f32x4 y[4]) {
 template <> __device__ __forceinline__ void wino_bt1<4>(const f32x4 d[6], f32x4 r[6]) { wino44_bt(d, r); }
 template <> __device__ __forceinline__ void wino_at1<4>(const f32x4 m[6], f32x4 y[4]) { wino44_at(m, y); }
 
+// F(1,3): the direct 3-tap sum as a "transform" (the W axis of the tail column, below): B^T and G are the 3 x 3 identity, A^T = [1 1 1]
+template <> __device__ __forceinline__ void wino_bt1<1>(const f32x4 d[3], f32x4 r[3]) {
+  r[0] = d[0]; r[1] = d[1]; r[2] = d[2];
+}
+template <> __device__ __forceinline__ void wino_at1<1>(const f32x4 m[3], f32x4 y[1]) { y[0] = (m[0] + m[1]) + m[2]; }
+
 
 struct WinoGeom {
-  int N, H, W;      // image extent (output extent is the same: stride 1, pad 1)
-  int TH, TW;       // output tiles per image
+  int N, H, W;      // image extent (output extent is the same: stride 1, pad 1): bounds the input taps and guards the output stores
+  int TH, TW;       // output tiles per image in this pass
+  int w0;           // first output column of the pass: its tile column tw covers output columns w0 + MW * tw ...
   long Mt;          // N * TH * TW
 };
 
@@ -92,19 +104,15 @@ struct WinoGeom {
 // The axis order sets the f32 rounding and is part of each form's result: the forms with a 6-point H axis transform W first (B^T
 // per row as the row is loaded), then H per column; F(2x2) loads the whole tile and transforms H first, then W.
 template <int MH, int MW>
-__device__ __forceinline__ void wino_input_body(const float* in, long sN, long sH, long sW, int C, WinoGeom g, float* V) {
+__device__ __forceinline__ void wino_input_body(const float* in, long sN, long sH, long sW, int C, const WinoGeom& g, float* V, long t, int c) {
   constexpr int PH = MH + 2, PW = MW + 2;
   constexpr bool w_first = MH == 4;
-  const int cch = C >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
   if (t >= g.Mt) return;
   const int tw = (int)(t % g.TW);
   const long r = t / g.TW;
   const int th = (int)(r % g.TH);
   const int n = (int)(r / g.TH);
-  const int h0 = MH * th - 1, w0 = MW * tw - 1;
+  const int h0 = MH * th - 1, w0 = g.w0 + MW * tw - 1;
   const float* base = in + (long)n * sN + c;
   f32x4 q[PH][PW];
 #pragma unroll
@@ -161,13 +169,9 @@ __device__ __forceinline__ void wino_input_body(const float* in, long sN, long s
 
 // ---- 3. output transform: one thread = one tile x 4 output channels; H axis first (A^T per column), then W -----------------
 template <int MH, int MW>
-__device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, WinoGeom g, const float* bias, const float* res, long res_ld,
-                                                 int relu, float* out, long out_ld) {
+__device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, const WinoGeom& g, const float* bias, const float* res, long res_ld,
+                                                 int relu, float* out, long out_ld, long t, int c) {
   constexpr int PH = MH + 2, PW = MW + 2;
-  const int cch = Cout >> 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long t = gid / cch;
-  const int c = (int)(gid - t * cch) << 2;
   if (t >= g.Mt) return;
   const int tw = (int)(t % g.TW);
   const long r = t / g.TW;
@@ -203,7 +207,7 @@ __device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, Wino
     wino_at1<MW>(s[a], y);
 #pragma unroll
     for (int j = 0; j < MW; ++j) {
-      const int wo = MW * tw + j;
+      const int wo = g.w0 + MW * tw + j;
       if (wo >= g.W) continue;
       const long pix = ((long)n * g.H + ho) * g.W + wo;
       f32x4 v = y[j] + b;
@@ -216,21 +220,55 @@ __device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, Wino
   }
 }
 
+// thread -> (tile, first of its 4 channels): gid = tile * (C / 4) + channel group
+__device__ __forceinline__ long wino_thread_tile(int C, int* c) {
+  const int cch = C >> 2;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long t = gid / cch;
+  *c = (int)(gid - t * cch) << 2;
+  return t;
+}
+
 // One kernel symbol per form and direction: profilers, bench.py and tools/ sort kernels into the convolution stage by these names.
 #define WINO_TRANSFORM_KERNELS(PREFIX, MH, MW)                                                                                    \
   __global__ __launch_bounds__(256) void PREFIX##_input_kernel(const float* __restrict__ in, long sN, long sH, long sW, int C,   \
                                                                WinoGeom g, float* __restrict__ V) {                            \
-    wino_input_body<MH, MW>(in, sN, sH, sW, C, g, V);                                                                            \
+    int c;                                                                                                                       \
+    const long t = wino_thread_tile(C, &c);                                                                                      \
+    wino_input_body<MH, MW>(in, sN, sH, sW, C, g, V, t, c);                                                                      \
   }                                                                                                                              \
   __global__ __launch_bounds__(256) void PREFIX##_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,              \
                                                                 const float* __restrict__ bias, const float* __restrict__ res,  \
                                                                 long res_ld, int relu, float* __restrict__ out, long out_ld) {  \
-    wino_output_body<MH, MW>(Mw, Cout, g, bias, res, res_ld, relu, out, out_ld);                                                 \
+    int c;                                                                                                                       \
+    const long t = wino_thread_tile(Cout, &c);                                                                                   \
+    wino_output_body<MH, MW>(Mw, Cout, g, bias, res, res_ld, relu, out, out_ld, t, c);                                           \
   }
 WINO_TRANSFORM_KERNELS(wino, 2, 2)
 WINO_TRANSFORM_KERNELS(wino42, 4, 2)
 WINO_TRANSFORM_KERNELS(wino44, 4, 4)
 #undef WINO_TRANSFORM_KERNELS
+
+// Square tiles + tail column (W % 4 == 1): ONE launch per direction over the tiles of both passes, the square pass's first.  The tile
+// index picks the body; with C / 4 >= 64 threads per tile the branch is uniform over a wave.  The names keep the wino44_ prefix:
+// they are the square form's kernels as far as profilers, bench.py and tools/ are concerned.
+__global__ __launch_bounds__(256) void wino44_input_kernel_coltail(const float* __restrict__ in, long sN, long sH, long sW, int C,
+                                                                   WinoGeom g44, WinoGeom g41, float* __restrict__ V44,
+                                                                   float* __restrict__ V41) {
+  int c;
+  const long t = wino_thread_tile(C, &c);
+  if (t < g44.Mt) wino_input_body<4, 4>(in, sN, sH, sW, C, g44, V44, t, c);
+  else wino_input_body<4, 1>(in, sN, sH, sW, C, g41, V41, t - g44.Mt, c);
+}
+__global__ __launch_bounds__(256) void wino44_output_kernel_coltail(const float* __restrict__ Mw44, const float* __restrict__ Mw41,
+                                                                    int Cout, WinoGeom g44, WinoGeom g41,
+                                                                    const float* __restrict__ bias, const float* __restrict__ res,
+                                                                    long res_ld, int relu, float* __restrict__ out, long out_ld) {
+  int c;
+  const long t = wino_thread_tile(Cout, &c);
+  if (t < g44.Mt) wino_output_body<4, 4>(Mw44, Cout, g44, bias, res, res_ld, relu, out, out_ld, t, c);
+  else wino_output_body<4, 1>(Mw41, Cout, g41, bias, res, res_ld, relu, out, out_ld, t - g44.Mt, c);
+}
 
 // ---- host side of the unfused forms --------------------------------------------------------------------------------------------
 static const int kWinoTile[3][2] = {{2, 2}, {4, 2}, {4, 4}};  // output tile (MH, MW) per MSOCR_WINO_* form
@@ -247,6 +285,7 @@ static bool wino_geom(const msocr_conv_desc* d, int form, WinoGeom* g) {
   const int mh = kWinoTile[form][0], mw = kWinoTile[form][1];
   g->N = d->N; g->H = d->H; g->W = d->W;
   g->TH = (d->H + mh - 1) / mh; g->TW = (d->W + mw - 1) / mw;
+  g->w0 = 0;
   g->Mt = (long)d->N * g->TH * g->TW;
   return wino_points(form) * g->Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) <= 0x3fffffffffffL;
 }
@@ -335,6 +374,94 @@ extern "C" int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int sp
   rc = msocr_winograd_gemm(d, form, split, u, workspace, stream);
   if (rc != MSOCR_OK) return rc;
   return msocr_winograd_output_transform(d, form, workspace, bias, residual, out, stream);
+}
+
+// ---- square tiles + tail column: the 4X4 form on maps with W % 4 == 1 without its padded last tile ----------------------------------
+// ceil(W/4) square tiles per tile row would end in a tile with one real output column and three discarded ones (TRBA's 4 x 13 maps:
+// 144 point rows per crop where 108 + the thirteenth column's are needed).  Here the square pass covers tile columns 0 ... W/4 - 1
+// (it reads input column W - 1 as the right halo of its last tile) and output column W - 1 is one F(4,3) x F(1,3) tile per tile row:
+// the 6-point transform along H, the three taps along W summed directly, 6 x 3 = 18 points.  36 * (W/4) + 18 point rows per tile row
+// instead of 36 * (W/4 + 1).  Columns 0 ... W - 2 are the 4X4 form's bit for bit (same tiles, same V rows, same GEMM rows).
+// Workspace: V44 [36][Mt44][Cin] | Mw44 [36][Mt44][Cout] | V41 [18][Mt41][Cin] | Mw41 [18][Mt41][Cout], Mt44 = N TH (W/4), Mt41 = N TH.
+// Split-operand GEMMs only, as the 4X4 form: u44 = the 4X4 form's planes, u41 = the planes of msocr_winograd_coltail_weights_host.
+struct WinoColtail {
+  WinoGeom g44, g41;
+  long v44, mw44, v41, mw41, total;  // workspace offsets, in floats
+};
+
+static bool wino_coltail_geom(const msocr_conv_desc* d, WinoColtail* ct) {
+  WinoGeom g;
+  if (!wino_geom(d, MSOCR_WINO_4X4, &g) || d->W < 5 || d->W % 4 != 1) return false;
+  if (d->Cin % 32 || d->Cout % 64) return false;  // the split GEMMs
+  ct->g44 = g; ct->g44.TW = d->W / 4; ct->g44.Mt = (long)d->N * g.TH * ct->g44.TW;
+  ct->g41 = g; ct->g41.TW = 1; ct->g41.w0 = d->W - 1; ct->g41.Mt = (long)d->N * g.TH;
+  ct->v44 = 0;
+  ct->mw44 = ct->v44 + 36 * ct->g44.Mt * d->Cin;
+  ct->v41 = ct->mw44 + 36 * ct->g44.Mt * d->Cout;
+  ct->mw41 = ct->v41 + 18 * ct->g41.Mt * d->Cin;
+  ct->total = ct->mw41 + 18 * ct->g41.Mt * d->Cout;
+  return true;
+}
+
+static int wino_coltail_check(const msocr_conv_desc* d, WinoColtail* ct) {
+  if (!wino_coltail_geom(d, ct) || !wino_strides_ok(d) || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
+  return MSOCR_OK;
+}
+
+extern "C" int64_t msocr_winograd_coltail_workspace_bytes(const msocr_conv_desc* d) {
+  WinoColtail ct;
+  if (!wino_coltail_geom(d, &ct)) return -1;
+  return ct.total * (int64_t)sizeof(float);
+}
+
+extern "C" int msocr_winograd_coltail_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream) {
+  WinoColtail ct;
+  if (wino_coltail_check(d, &ct) != MSOCR_OK) return MSOCR_E_ARG;
+  if (!in || !workspace || (((uintptr_t)in | (uintptr_t)workspace) & 15)) return MSOCR_E_ARG;
+  const long nb_in = ((ct.g44.Mt + ct.g41.Mt) * (d->Cin / 4) + 255) / 256;
+  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
+  float* ws = (float*)workspace;
+  MSOCR_LAUNCH(wino44_input_kernel_coltail, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
+               (long)d->in_sH, (long)d->in_sW, d->Cin, ct.g44, ct.g41, ws + ct.v44, ws + ct.v41);
+  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+}
+
+// two launches of the batched split GEMM: 36 of Mt44 x Cout x Cin, then 18 of Mt41 x Cout x Cin
+extern "C" int msocr_winograd_coltail_gemm(const msocr_conv_desc* d, const void* u44, const void* u41, void* workspace, void* stream) {
+  WinoColtail ct;
+  if (wino_coltail_check(d, &ct) != MSOCR_OK || !u44 || !u41 || !workspace) return MSOCR_E_ARG;
+  float* ws = (float*)workspace;
+  const int rc = msocr_internal_gemm_split_batched(ws + ct.v44, (const uint16_t*)u44, ws + ct.mw44, ct.g44.Mt, d->Cout, d->Cin, 36, (hipStream_t)stream);
+  if (rc != MSOCR_OK) return rc;
+  return msocr_internal_gemm_split_batched(ws + ct.v41, (const uint16_t*)u41, ws + ct.mw41, ct.g41.Mt, d->Cout, d->Cin, 18, (hipStream_t)stream);
+}
+
+extern "C" int msocr_winograd_coltail_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
+                                                       void* out, void* stream) {
+  WinoColtail ct;
+  if (wino_coltail_check(d, &ct) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
+  if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
+  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
+  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
+  if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
+  const long nb_out = ((ct.g44.Mt + ct.g41.Mt) * (d->Cout / 4) + 255) / 256;
+  if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
+  const float* ws = (const float*)workspace;
+  const float* rp = has_res ? (const float*)residual : nullptr;
+  const int relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
+  MSOCR_LAUNCH(wino44_output_kernel_coltail, dim3((unsigned)nb_out), dim3(256), 0, (hipStream_t)stream, ws + ct.mw44, ws + ct.mw41, d->Cout,
+               ct.g44, ct.g41, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
+  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+}
+
+extern "C" int msocr_conv3x3_winograd_coltail(const msocr_conv_desc* d, const void* in, const void* u44, const void* u41, const float* bias,
+                                              const void* residual, void* out, void* workspace, void* stream) {
+  if (!u44 || !u41) return MSOCR_E_ARG;
+  int rc = msocr_winograd_coltail_input_transform(d, in, workspace, stream);
+  if (rc != MSOCR_OK) return rc;
+  rc = msocr_winograd_coltail_gemm(d, u44, u41, workspace, stream);
+  if (rc != MSOCR_OK) return rc;
+  return msocr_winograd_coltail_output_transform(d, workspace, bias, residual, out, stream);
 }
 
 // =====================================================================================================================
@@ -795,15 +922,17 @@ extern "C" int msocr_conv3x3_winograd_fused64(const msocr_conv_desc* d, int spli
   return msocr_winograd_fused64_gemm_output(d, split, u, workspace, bias, residual, out, stream);
 }
 
+static const double kWinoG6[6][3] = {{1.0, 0.0, 0.0},                                                      // F(4,3): wino44_bt's points
+                                     {8.0 / 65, 12.0 / 65, 18.0 / 65},     {8.0 / 65, -12.0 / 65, 18.0 / 65},
+                                     {-81.0 / 130, -27.0 / 65, -18.0 / 65}, {-81.0 / 130, 27.0 / 65, -18.0 / 65},
+                                     {0.0, 0.0, 1.0}};
+
 // U[xi*PW+nu][co][c] = sum_{kh,kw} Gh[xi][kh] Gw[nu][kw] w[co][kh][kw][c] (xi on the kernel's H axis), evaluated in f64 (G g over kh
 // first, then over kw) and rounded once to f32.  HOST function (runs at weight-load time): w_khwc and u_out are host pointers.
 extern "C" int msocr_winograd_weights_host(int form, const float* w_khwc, int Cout, int Cin, float* u_out) {
   if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4 || !w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
   static const double G4[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};  // F(2,3) on {0, 1, -1, inf}
-  static const double G6[6][3] = {{1.0, 0.0, 0.0},                                                         // F(4,3): wino44_bt's points
-                                  {8.0 / 65, 12.0 / 65, 18.0 / 65},     {8.0 / 65, -12.0 / 65, 18.0 / 65},
-                                  {-81.0 / 130, -27.0 / 65, -18.0 / 65}, {-81.0 / 130, 27.0 / 65, -18.0 / 65},
-                                  {0.0, 0.0, 1.0}};
+  const double(*G6)[3] = kWinoG6;
   const int PH = kWinoTile[form][0] + 2, PW = kWinoTile[form][1] + 2;
   const double(*Gh)[3] = PH == 6 ? G6 : G4;
   const double(*Gw)[3] = PW == 6 ? G6 : G4;
@@ -820,6 +949,23 @@ extern "C" int msocr_winograd_weights_host(int form, const float* w_khwc, int Co
           u_out[(xi * PW + nu) * plane + (long)co * Cin + c] =
               (float)(gw[xi][0] * Gw[nu][0] + gw[xi][1] * Gw[nu][1] + gw[xi][2] * Gw[nu][2]);
     }
+  }
+  return MSOCR_OK;
+}
+
+// The tail column's weights, F(4,3) x F(1,3): U[xi*3+kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c] (Gw = the identity), [18][Cout][Cin],
+// in f64 and rounded once.  HOST function, as msocr_winograd_weights_host.
+extern "C" int msocr_winograd_coltail_weights_host(const float* w_khwc, int Cout, int Cin, float* u_out) {
+  if (!w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
+  const long plane = (long)Cout * Cin;
+  for (int co = 0; co < Cout; ++co) {
+    const float* w = w_khwc + (long)co * 9 * Cin;
+    for (int c = 0; c < Cin; ++c)
+      for (int xi = 0; xi < 6; ++xi)
+        for (int kw = 0; kw < 3; ++kw)
+          u_out[(xi * 3 + kw) * plane + (long)co * Cin + c] =
+              (float)(kWinoG6[xi][0] * w[(0 * 3 + kw) * Cin + c] + kWinoG6[xi][1] * w[(1 * 3 + kw) * Cin + c] +
+                      kWinoG6[xi][2] * w[(2 * 3 + kw) * Cin + c]);
   }
   return MSOCR_OK;
 }

@@ -106,7 +106,8 @@ def _tall_pays(H):
 
 # Square form F(4,3) x F(4,3) on the points {0, +-3/2, +-2/3, inf} (csrc/winograd.hip, wino44_*; round 4): 36 points per 4x4 outputs =
 # 2.25 multiplies and workspace words per output instead of 3.  Split-operand GEMMs only (precision="fp32" default); taken where it is
-# cheaper than the tall form for the map width: 36 * ceil(W/4) < 24 * ceil(W/2).  MSOCR_WINO_SQUARE=0 keeps the tall form.
+# cheaper than the tall form for the map width: 36 * ceil(W/4) < 24 * ceil(W/2) (_square_pays below; for W % 4 == 1 at the price of
+# square tiles + tail column).  MSOCR_WINO_SQUARE=0 keeps the tall form.
 # Which layers: per layer the square form's rounding error is 1.1-1.3x the tall form's on the textbook points and 2.2-2.5x the tall
 # form's on the new points; end to end (tests/test_gpu_f64.py, device error against f64 relative to the reference's own f32 error,
 # bound 2.0, three weight sets) the recogniser reads 1.47-1.60 all tall, 1.79-1.91 with the square form on its Cin = 512 layers
@@ -116,8 +117,20 @@ WINOGRAD_SQUARE = int(os.environ.get("MSOCR_WINO_SQUARE", "1"))
 WINOGRAD_SQUARE_MIN_CIN = int(os.environ.get("MSOCR_WINO_SQUARE_MIN_CIN", "512"))
 
 
+# Square tiles + tail column (csrc/winograd.hip, wino44_*_coltail): on a map with W % 4 == 1 the last of the ceil(W/4) square tiles holds
+# one real output column and three that are thrown away (TRBA's 4 x 13 maps pay for 16 columns).  There the square pass covers the
+# W // 4 full tiles and column W - 1 is one F(4,3) x F(1,3) tile per tile row, 18 points: 36 * (W // 4) + 18 point rows instead of
+# 36 * (W // 4 + 1), the other columns bit for bit the same.  MSOCR_WINO_COLTAIL=0 keeps the padded tile.
+WINOGRAD_COLTAIL = int(os.environ.get("MSOCR_WINO_COLTAIL", "1"))
+
+
+def _coltail(W):
+    return bool(WINOGRAD_COLTAIL) and W % 4 == 1 and W >= 5
+
+
 def _square_pays(W):
-    return 36 * (-(-W // 4)) < 24 * (-(-W // 2))
+    points = 36 * (W // 4) + 18 if _coltail(W) else 36 * (-(-W // 4))
+    return points < 24 * (-(-W // 2))
 
 
 # The Winograd tile forms (csrc/winograd.hip, include/msocr.h MSOCR_WINO_*): form id -> (PROFILE tag stem, transform points, output tile)
@@ -125,8 +138,13 @@ WINO_FORMS = {nat.WINO_2X2: ("winograd", 16, (2, 2)), nat.WINO_4X2: ("winograd42
 
 
 def _wino_weights(wh, form):
-    """Host [Cout,3,3,Cin] f32 weight -> U [points, Cout, Cin] f32 (msocr_winograd_weights_host: f64, rounded once)."""
+    """Host [Cout,3,3,Cin] f32 weight -> U [points, Cout, Cin] f32 (msocr_winograd_weights_host: f64, rounded once); form "coltail":
+    the tail column's [18, Cout, Cin] (msocr_winograd_coltail_weights_host)."""
     Cout, _, _, Cin = wh.shape
+    if form == "coltail":
+        u = torch.empty((18, Cout, Cin), dtype=torch.float32)
+        nat.check(nat.lib().msocr_winograd_coltail_weights_host(wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_coltail_weights_host")
+        return u
     u = torch.empty((WINO_FORMS[form][1], Cout, Cin), dtype=torch.float32)
     nat.check(nat.lib().msocr_winograd_weights_host(form, wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_weights_host")
     return u
@@ -221,19 +239,25 @@ def attach_winograd(w, split=None, square=True):
         w._msocr_wino42_split = split_planes_ktile(u42, 24, Cout).to(w.device)  # [3][24][Cin/32][Cout][32] bf16
         if WINOGRAD_SQUARE and square and Cin >= WINOGRAD_SQUARE_MIN_CIN:  # square=False: the caller keeps this layer on the tall form (half the rounding error)
             w._msocr_wino44_split = split_planes_ktile(_wino_weights(wh, nat.WINO_4X4), 36, Cout).to(w.device)  # [3][36][Cin/32][Cout][32] bf16
+            w._msocr_wino41_split = split_planes_ktile(_wino_weights(wh, "coltail"), 18, Cout).to(w.device)  # [3][18][Cin/32][Cout][32] bf16: the tail column
     return w
 
 
-def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False):
+def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False, u41=None):
     """One Winograd convolution described by d (3x3/1/1, f32) in the given form: the workspace from the per-stream arena, the batch cut
     so that it stays under WINO_WS_LIMIT, and per part either the one-call entry point or — with PROFILE on — the stages one by one,
-    one event pair each.  fused: the Cin = 64 tall form with the GEMMs and the output transform (+ the 2x2 max-pool) in one kernel."""
+    one event pair each.  fused: the Cin = 64 tall form with the GEMMs and the output transform (+ the 2x2 max-pool) in one kernel.
+    u41: the square form as square tiles + tail column (W % 4 == 1), u41 the tail column's planes; still ONE conv_gemm record, spanning
+    both GEMM launches."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
     stem, npts, (mh, mw) = WINO_FORMS[form]
     name = stem + ("_fused" if fused else "") + ("_split" if split else "")
     L = nat.lib()
-    nbytes = L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) if fused else L.msocr_winograd_workspace_bytes(ctypes.byref(d), form)
+    if u41 is not None:
+        nbytes = L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(d))
+    else:
+        nbytes = L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) if fused else L.msocr_winograd_workspace_bytes(ctypes.byref(d), form)
     if nbytes < 0:
         raise nat.NativeError(f"{name}: unsupported shape {tuple(x.shape)} * {tuple(w.shape)} pool2={pool2}")
     parts = min(N, -(-nbytes // WINO_WS_LIMIT))  # images per call such that the workspace stays under the limit
@@ -249,13 +273,29 @@ def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, po
         d.N = n1 - n0
         xp, rp, op = x[n0:n1].data_ptr(), (residual[n0:n1].data_ptr() if residual is not None else None), out[n0:n1].data_ptr()
         if PROFILE is None:
-            if fused:
+            if u41 is not None:
+                rc = L.msocr_conv3x3_winograd_coltail(ctypes.byref(d), xp, u.data_ptr(), u41.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
+            elif fused:
                 rc = L.msocr_conv3x3_winograd_fused64(ctypes.byref(d), int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
             else:
                 rc = L.msocr_conv3x3_winograd(ctypes.byref(d), form, int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
             nat.check(rc, what)
             continue
         nn, mt = n1 - n0, (n1 - n0) * TH * TW
+        if u41 is not None:  # point rows: 36 per square tile + 18 per tail tile; the records' tile count is that of both parts
+            mt44, mt41 = nn * TH * (W // 4), nn * TH
+            rows, mt = 36 * mt44 + 18 * mt41, mt44 + mt41
+            e = _prof_begin()
+            nat.check(L.msocr_winograd_coltail_input_transform(ctypes.byref(d), xp, ws.data_ptr(), _stream()), what)
+            _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + rows * Cin), (mt, Cin))
+            e = _prof_begin()
+            nat.check(L.msocr_winograd_coltail_gemm(ctypes.byref(d), u.data_ptr(), u41.data_ptr(), ws.data_ptr(), _stream()), what)
+            io = x.element_size() * (nn * H * W * Cin + nn * out_px * Cout * res_io + Cout * 9 * Cin)
+            _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * rows * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
+            e = _prof_begin()
+            nat.check(L.msocr_winograd_coltail_output_transform(ctypes.byref(d), ws.data_ptr(), bp, rp, op, _stream()), what)
+            _prof_end(e, "wino_out", 4.0 * (rows * Cout + nn * H * W * Cout * res_io), (mt, Cout))
+            continue
         e = _prof_begin()
         nat.check(L.msocr_winograd_input_transform(ctypes.byref(d), form, xp, ws.data_ptr(), _stream()), what)
         _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + npts * mt * Cin), (mt, Cin))
@@ -321,7 +361,7 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
         u = w._msocr_wino42_fused if up is None else up
         _winograd(d, x, w, u, nat.WINO_4X2, up is not None, bias, residual, out, alg, fused=True, pool2=pool2)
     elif use_wino:
-        form, split = nat.WINO_2X2, False
+        form, split, u41 = nat.WINO_2X2, False, None
         if WINOGRAD_TALL and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None:
             form, u = nat.WINO_4X2, w._msocr_wino42
             up = getattr(w, "_msocr_wino42_split", None)
@@ -330,7 +370,8 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
             up44 = getattr(w, "_msocr_wino44_split", None)
             if up44 is not None and SPLIT_BF16X3 and WINOGRAD_SQUARE and _square_pays(W):
                 form, u, split = nat.WINO_4X4, up44, True
-        _winograd(d, x, w, u, form, split, bias, residual, out, alg)
+                u41 = getattr(w, "_msocr_wino41_split", None) if _coltail(W) else None
+        _winograd(d, x, w, u, form, split, bias, residual, out, alg, u41=u41)
     else:
         wp = getattr(w, "_msocr_split", None)
         if (wp is None and SPLIT_BF16X3 and not getattr(w, "_msocr_nosplit", False) and _split_eligible(w)

@@ -1,0 +1,100 @@
+"""Square tiles + tail column (csrc/winograd.hip, msocr_winograd_coltail_*): the host side, without a GPU.
+
+The tail column of a map with W % 4 == 1 is F(4,3) along H and the three taps along W summed directly, so its weights are
+U[xi*3 + kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c] with G6 the Cook-Toom matrix of F(4,3) on {0, +-3/2, +-2/3, inf}.
+"""
+import ctypes
+
+import numpy as np
+
+
+def _g6():
+    pts = [0.0, 1.5, -1.5, 2 / 3, -2 / 3]
+    G6 = np.zeros((6, 3), np.float64)
+    for j, a in enumerate(pts):   # G[j] = [1, a, a^2] / prod_{l != j}(a_j - a_l); the point at infinity: [0, 0, 1]
+        G6[j] = np.array([1.0, a, a * a]) / np.prod([a - b for l, b in enumerate(pts) if l != j])
+    G6[5, 2] = 1.0
+    return G6
+
+
+def _desc(nat, N, H, W, Cin, Cout, stride=1):
+    d = nat.ConvDesc()
+    d.dtype, d.N, d.H, d.W, d.Cin = nat.F32, N, H, W, Cin
+    d.in_sN, d.in_sH, d.in_sW = H * W * Cin, W * Cin, Cin
+    d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, stride, stride, 1, 1
+    d.Ho, d.Wo, d.Cout = (H - 1) // stride + 1, (W - 1) // stride + 1, Cout
+    d.out_ld = d.res_ld = Cout
+    return d
+
+
+def test_coltail_weights_host_match_cook_toom_definition():
+    """f64, rounded once: within 1 ulp of the einsum (another summation order), the 1.2e-7 * max rule of the other forms."""
+    from manuscript_ocr_amd import _native as nat
+    L = nat.lib()
+    rng = np.random.default_rng(41)
+    for Cout, Cin in ((32, 16), (64, 96)):
+        w = rng.standard_normal((Cout, 3, 3, Cin)).astype(np.float32)  # [Cout][KH][KW][Cin]
+        u = np.empty((18, Cout, Cin), np.float32)
+        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, Cin, u.ctypes.data) == 0
+        exp = np.einsum("xk,oklc->xloc", _g6(), w.astype(np.float64)).reshape(18, Cout, Cin)
+        assert np.abs(u.astype(np.float64) - exp).max() <= 1.2e-7 * np.abs(exp).max()
+        # the rows of the points 0 and inf are the kernel's own first and last rows, exactly
+        assert np.array_equal(u[0:3], w[:, 0].transpose(1, 0, 2)) and np.array_equal(u[15:18], w[:, 2].transpose(1, 0, 2))
+        assert L.msocr_winograd_coltail_weights_host(None, Cout, Cin, u.ctypes.data) == -1
+        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, Cin, None) == -1
+        assert L.msocr_winograd_coltail_weights_host(None, Cout, Cin, None) == -1
+        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, 0, Cin, u.ctypes.data) == -1
+        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, 0, u.ctypes.data) == -1
+
+
+def test_coltail_workspace_bytes_and_shapes_without_the_form():
+    """V44 | Mw44 | V41 | Mw41 = (36 * N TH (W // 4) + 18 * N TH) * (Cin + Cout) f32, linear in N; -1 where there is no such form; the
+    entry points refuse those shapes before anything is launched."""
+    from manuscript_ocr_amd import _native as nat
+    L = nat.lib()
+    for N, H, W, Cin, Cout in ((3, 4, 13, 512, 512), (2, 8, 25, 256, 256), (2, 9, 5, 128, 128), (129, 4, 5, 128, 64), (1, 17, 9, 128, 192),
+                               (960, 4, 13, 512, 512)):
+        TH = -(-H // 4)
+        exp = (36 * N * TH * (W // 4) + 18 * N * TH) * (Cin + Cout) * 4
+        got = L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(_desc(nat, N, H, W, Cin, Cout)))
+        assert got == exp, (N, H, W, Cin, Cout)
+        assert got == N * L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(_desc(nat, 1, H, W, Cin, Cout)))
+        assert got < L.msocr_winograd_workspace_bytes(ctypes.byref(_desc(nat, N, H, W, Cin, Cout)), nat.WINO_4X4)
+    assert L.msocr_winograd_coltail_workspace_bytes(None) == -1
+    bad = [_desc(nat, 2, 8, 12, 128, 128), _desc(nat, 2, 8, 14, 128, 128), _desc(nat, 2, 8, 15, 128, 128),   # W % 4 != 1
+           _desc(nat, 2, 8, 1, 128, 128),                                                                   # no square tile
+           _desc(nat, 2, 8, 13, 144, 128), _desc(nat, 2, 8, 13, 128, 96),                                   # the split GEMMs: Cin % 32, Cout % 64
+           _desc(nat, 2, 8, 13, 128, 128, stride=2)]
+    bf16 = _desc(nat, 2, 8, 13, 128, 128)
+    bf16.dtype = nat.BF16
+    fake = ctypes.c_void_p(1 << 20)  # never dereferenced: every call below fails its argument checks first
+    for d in bad + [bf16]:
+        r = ctypes.byref(d)
+        assert L.msocr_winograd_coltail_workspace_bytes(r) == -1
+        assert L.msocr_winograd_coltail_input_transform(r, fake, fake, None) == -1
+        assert L.msocr_winograd_coltail_gemm(r, fake, fake, fake, None) == -1
+        assert L.msocr_winograd_coltail_output_transform(r, fake, None, None, fake, None) == -1
+        assert L.msocr_conv3x3_winograd_coltail(r, fake, fake, fake, None, None, fake, fake, None) == -1
+    ok = ctypes.byref(_desc(nat, 2, 8, 13, 128, 128))
+    assert L.msocr_winograd_coltail_input_transform(ok, None, fake, None) == -1
+    assert L.msocr_winograd_coltail_input_transform(ok, fake, None, None) == -1
+    assert L.msocr_winograd_coltail_gemm(ok, None, fake, fake, None) == -1
+    assert L.msocr_winograd_coltail_gemm(ok, fake, None, fake, None) == -1
+    assert L.msocr_winograd_coltail_gemm(ok, fake, fake, None, None) == -1
+    assert L.msocr_winograd_coltail_output_transform(ok, None, None, None, fake, None) == -1
+    assert L.msocr_winograd_coltail_output_transform(ok, fake, None, None, None, None) == -1
+    assert L.msocr_conv3x3_winograd_coltail(ok, fake, None, fake, None, None, fake, fake, None) == -1
+    assert L.msocr_conv3x3_winograd_coltail(ok, fake, fake, None, None, None, fake, fake, None) == -1
+
+
+def test_square_pays_prices_the_tail_column(monkeypatch):
+    """ops._square_pays: 36 * (W // 4) + 18 point rows per tile row where the composite runs, 36 * ceil(W / 4) elsewhere or with
+    the switch off, against the tall form's 24 * ceil(W / 2)."""
+    from manuscript_ocr_amd import ops
+    monkeypatch.setattr(ops, "WINOGRAD_COLTAIL", 1)
+    assert ops._square_pays(13) and ops._square_pays(25) and ops._square_pays(9)
+    assert ops._square_pays(5)            # 54 < 72
+    assert not ops._square_pays(1)        # no composite below W = 5: 36 > 24
+    assert not ops._square_pays(6) and ops._square_pays(12)   # unchanged: 72 = 72, 108 < 144
+    monkeypatch.setattr(ops, "WINOGRAD_COLTAIL", 0)
+    assert ops._square_pays(13) and not ops._square_pays(5)   # 144 < 168, 72 = 72

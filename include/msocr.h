@@ -55,28 +55,43 @@ typedef struct msocr_conv_desc {
 int msocr_conv2d(const msocr_conv_desc* d, const void* in, const void* weight, const float* bias,
                  const void* residual, void* out, void* stream);
 
-/* The same convolution for KH=KW=3, stride 1, pad 1, MSOCR_F32, as Winograd in one of three tile forms (`form`):
+/* The same convolution for KH=KW=3, stride 1, pad 1, MSOCR_F32, as Winograd in one of four tile forms (`form`):
  *   MSOCR_WINO_2X2  F(2x2,3x3): 16 transform points per 2x2 output tile, 4 multiplies per output (direct: 9);
  *   MSOCR_WINO_4X2  the TALL form F(4,3) x F(2,3): 24 points per 4x2 tile, 3 multiplies per output, V / Mw 3x the layer's arrays;
- *   MSOCR_WINO_4X4  the square form F(4,3) x F(4,3): 36 points per 4x4 tile, 2.25 multiplies and workspace words per output.
+ *   MSOCR_WINO_4X4  the square form F(4,3) x F(4,3): 36 points per 4x4 tile, 2.25 multiplies and workspace words per output;
+ *   MSOCR_WINO_4X4_COLTAIL  the square form + tail column, for maps with W % 4 == 1 (W >= 5), without the 4X4 form's padded last tile:
+ *                   output columns 0 ... W-2 are W/4 square tiles per tile row, bit for bit what the 4X4 form stores there; column W-1 is
+ *                   one F(4,3) x F(1,3) tile per tile row (the 6-point transform along H, the three taps along W summed directly: 18
+ *                   points).  36 * (W/4) + 18 point rows per tile row instead of 36 * (W/4 + 1).  The one form of two parts: one
+ *                   transform launch per direction over the tiles of both, one batched GEMM launch per part.
  * The 6-point axes run on the interpolation points {0, +-3/2, +-2/3, inf} (round 4): the tall form at half the rounding error of the
  * textbook points {0, +-1, +-2}, the square form at the tall form's error on those (the textbook points would cost 4.7x; DESIGN.md
  * section 4.4).  Input transform (HBM-bound) -> P GEMMs [tiles x Cin] x [Cin x Cout] in one MFMA launch -> output transform +
  * bias/residual/ReLU (HBM-bound); all arithmetic f32 (differs from msocr_conv2d by rounding order only).
  * u = the transform-domain weight U = G g G^T on the DEVICE, from msocr_winograd_weights_host (a HOST function: both of its pointers
- * are host memory; evaluates G g G^T in f64, rounds once) of the BatchNorm-folded [Cout][3][3][Cin] weight, [P][Cout][Cin] f32.
+ * are host memory; evaluates G g G^T in f64, rounds once) of the BatchNorm-folded [Cout][3][3][Cin] weight, [P][Cout][Cin] f32
+ * — one tile's planes per call.  4X4_COLTAIL: U is [54][Cout][Cin], the 4X4 form's 36 planes (that form's call), then the 18 of the
+ * tail tile, which the call with this form gives: [18][Cout][Cin], U[xi*3+kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c].  The
+ * output pointer carries no size; no call writes more than the 36 planes of the largest tile.
  *   split = 0: u as that f32 array, the GEMMs on exact-f32 MFMA;
  *   split = 1: u = K-tile-major bf16 planes [3][P][Cin/32][Cout][32] (msocr_split_bf16x3_ktile_host of it), the GEMMs with split
  *              operands on the bf16 matrix pipes (see msocr_conv1x1_split; Cin % 32 == 0, Cout % 64 == 0).
- * GEMMs exist for 2X2 exact, 4X2 exact and split, and 4X4 split; any other (form, split) is MSOCR_E_ARG.
- * workspace: msocr_winograd_workspace_bytes(d, form) bytes, 16-B aligned = V [P][tiles][Cin] f32 + Mw [P][tiles][Cout] f32
- * (-1 = shape not supported: Cin % 16, Cout % 32, not 3x3/1/1).  The three stages are also callable one by one (identical kernels,
- * identical results when called in this order on one stream with the same workspace): V = B^T d B into the workspace;
+ *              4X4_COLTAIL: ONE buffer, the 4X4 form's planes [3][36][Cin/32][Cout][32] immediately followed by the tail tile's planes
+ *              [3][18][Cin/32][Cout][32] (the second GEMM reads u + 3*36*Cout*Cin elements, 16-byte aligned as Cin % 32 == 0).  Each
+ *              group keeps its own plane stride: the concatenation of the splits of U[0:36] and U[36:54], NOT the split of the
+ *              [54][Cout][Cin] array as one.
+ * GEMMs exist for 2X2 exact, 4X2 exact and split, and 4X4 and 4X4_COLTAIL split; any other (form, split) is MSOCR_E_ARG.
+ * workspace: msocr_winograd_workspace_bytes(d, form) bytes, 16-B aligned, linear in N = V [P][tiles][Cin] f32 + Mw [P][tiles][Cout] f32;
+ * 4X4_COLTAIL: V44 [36][Mt44][Cin] | Mw44 [36][Mt44][Cout] | V41 [18][Mt41][Cin] | Mw41 [18][Mt41][Cout], Mt44 = N ceil(H/4) (W/4),
+ * Mt41 = N ceil(H/4)  (-1 = shape not supported: Cin % 16, Cout % 32, not 3x3/1/1; 4X4_COLTAIL also W % 4 != 1, W < 5, Cin % 32,
+ * Cout % 64).  The three stages are also callable one by one (identical kernels, identical results when called in this order on
+ * one stream with the same workspace): V = B^T d B into the workspace;
  * Mw[p] = V[p] U[p]^T; out = act(A^T Mw A + bias (+ residual)) — for tests and for the per-kernel rooflines of bench.py.
  * Same reference code as msocr_conv2d (every 3x3/1/1 conv of SE-ResNet31, ResNet-50 and the EAST decoder). */
 #define MSOCR_WINO_2X2 0
 #define MSOCR_WINO_4X2 1
 #define MSOCR_WINO_4X4 2
+#define MSOCR_WINO_4X4_COLTAIL 3
 int64_t msocr_winograd_workspace_bytes(const msocr_conv_desc* d, int form);
 int msocr_winograd_weights_host(int form, const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
 int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int split, const void* in, const void* u, const float* bias,
@@ -85,26 +100,6 @@ int msocr_winograd_input_transform(const msocr_conv_desc* d, int form, const voi
 int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const void* u, void* workspace, void* stream);
 int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* residual,
                                     void* out, void* stream);
-
-/* Square tiles + tail column: the 4X4 form for maps with W % 4 == 1 (W >= 5) without its padded last tile.  Output columns
- * 0 ... W-2 are W/4 square tiles per tile row, bit for bit what the 4X4 form stores there; column W-1 is one F(4,3) x F(1,3) tile per
- * tile row (the 6-point transform along H, the three taps along W summed directly: 18 points).  36 * (W/4) + 18 point rows per tile row
- * instead of 36 * (W/4 + 1).  Split-operand GEMMs only (Cin % 32 == 0, Cout % 64 == 0):
- *   u44 = the 4X4 form's planes [3][36][Cin/32][Cout][32];
- *   u41 = planes [3][18][Cin/32][Cout][32] of msocr_winograd_coltail_weights_host's [18][Cout][Cin] f32 (a HOST function, f64, rounded
- *         once): U[xi*3+kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c].
- * workspace: msocr_winograd_coltail_workspace_bytes(d) bytes, 16-B aligned, linear in N (-1 = no such form for the shape):
- *   V44 [36][Mt44][Cin] | Mw44 [36][Mt44][Cout] | V41 [18][Mt41][Cin] | Mw41 [18][Mt41][Cout],  Mt44 = N ceil(H/4) (W/4), Mt41 = N ceil(H/4).
- * One input-transform and one output-transform launch over the tiles of both parts, two batched GEMM launches (36 x Mt44 rows, 18 x Mt41
- * rows).  Descriptor rules, epilogue flags and the stage-by-stage entry points as msocr_conv3x3_winograd. */
-int64_t msocr_winograd_coltail_workspace_bytes(const msocr_conv_desc* d);
-int msocr_winograd_coltail_weights_host(const float* w_khwc_host, int Cout, int Cin, float* u_out_host);
-int msocr_conv3x3_winograd_coltail(const msocr_conv_desc* d, const void* in, const void* u44, const void* u41, const float* bias,
-                                   const void* residual, void* out, void* workspace, void* stream);
-int msocr_winograd_coltail_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream);
-int msocr_winograd_coltail_gemm(const msocr_conv_desc* d, const void* u44, const void* u41, void* workspace, void* stream);
-int msocr_winograd_coltail_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
-                                            void* out, void* stream);
 
 /* ---- split-operand f32 ("bf16x3"): the default arithmetic of the f32 1x1 convolutions and Winograd-domain GEMMs --------------
  * gfx950 runs exact-f32 MFMA at 1/16 of the bf16 rate.  An f32 value is the exact sum of three bf16 values (round-to-nearest

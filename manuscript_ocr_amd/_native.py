@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmsocr.so")
 
 F32, BF16 = 0, 1
 CONV_RELU, CONV_RESIDUAL, CONV_POOL2 = 1, 2, 4
-WINO_2X2, WINO_4X2, WINO_4X4 = 0, 1, 2  # Winograd tile forms (msocr.h MSOCR_WINO_*)
+WINO_2X2, WINO_4X2, WINO_4X4, WINO_4X4_COLTAIL = 0, 1, 2, 3  # Winograd tile forms (msocr.h MSOCR_WINO_*)
 
 c_i32, c_i64, c_u32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32
 c_f32, c_f64, c_vp = ctypes.c_float, ctypes.c_double, ctypes.c_void_p
@@ -53,12 +53,6 @@ _SIGS = {
     "msocr_winograd_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd_coltail_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
-    "msocr_winograd_coltail_weights_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
-    "msocr_conv3x3_winograd_coltail": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd_coltail_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp]),
-    "msocr_winograd_coltail_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp]),
-    "msocr_winograd_coltail_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "msocr_conv3x3_winograd_fused64": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_gemm_output": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -1,4 +1,4 @@
-// winograd.hip — 3x3 / stride 1 / pad 1 convolution as Winograd in f32 for gfx950 (MI355X), in three tile forms.
+// winograd.hip — 3x3 / stride 1 / pad 1 convolution as Winograd in f32 for gfx950 (MI355X), in four tile forms.
 //
 // Why here: exact-f32 MFMA (v_mfma_f32_32x32x2_f32) peaks at 157 TFLOP/s, 1/16 of the bf16 rate, while HBM3E
 // delivers 8 TB/s — so on this chip an f32 3x3 convolution is worth trading fewer matrix FLOPs for two
@@ -20,11 +20,11 @@
 //                         {0, +-3/2, +-2/3, inf} — reciprocal pairs keep the Vandermonde entries within [8/27, 27/8] — an f32 simulation of
 //                         the whole pipeline of transforms measures 1.05x the tall form's error (and 0.5x for the tall form itself on these
 //                         points; tools/winograd_points.py, profiles/r04_winograd_points.txt).
-//   4X4 + tail column     maps with W % 4 == 1 (the recogniser's 4 x 13): W/4 square tiles per tile row, then output column W - 1 as one
-//                         F(4,3) x F(1,3) tile — the 6-point transform along H, the three taps along W summed directly, 18 points —
-//                         instead of a fourth square tile that holds one real column: 36 * (W/4) + 18 point rows per tile row, not
-//                         36 * (W/4 + 1).  Not a fourth form id: its own entry points (msocr_winograd_coltail_*), one transform launch per
-//                         direction over the tiles of both parts (wino44_*_kernel_coltail), two batched GEMM launches.
+//   4X4_COLTAIL           the square form + tail column, for maps with W % 4 == 1 (the recogniser's 4 x 13): W/4 square tiles per
+//                         tile row, then output column W - 1 as one F(4,3) x F(1,3) tile — the 6-point transform along H, the three
+//                         taps along W summed directly, 18 points — instead of a fourth square tile that holds one real column:
+//                         36 * (W/4) + 18 point rows per tile row, not 36 * (W/4 + 1).  The one form of two parts (WinoPlan, below): one
+//                         transform launch per direction over the tiles of both (wino44_*_kernel_coltail), one batched GEMM launch each.
 // ops.conv2d() picks the tall form for the Cin = 64 layers (fused kernels, below) and where the square form does not pay; the 2x2
 // form when 24 * ceil(H/4) >= 16 * ceil(H/2).
 //
@@ -271,98 +271,157 @@ __global__ __launch_bounds__(256) void wino44_output_kernel_coltail(const float*
 }
 
 // ---- host side of the unfused forms --------------------------------------------------------------------------------------------
-static const int kWinoTile[3][2] = {{2, 2}, {4, 2}, {4, 4}};  // output tile (MH, MW) per MSOCR_WINO_* form
+// Every entry point derives ONE plan from (d, form): the form's parts, each with its tile geometry, its transform points and its V and
+// Mw blocks of the workspace.  2X2, 4X2 and 4X4 are one part, V | Mw.  4X4_COLTAIL is two, V44 | Mw44 | V41 | Mw41: the square pass
+// over tile columns 0 ... W/4 - 1 (it reads input column W - 1 as the right halo of its last tile; these are the 4X4 form's own tiles, V
+// rows and GEMM rows, so output columns 0 ... W - 2 are that form's bit for bit), then output column W - 1 as one F(4,3) x F(1,3) tile
+// per tile row (TRBA's 4 x 13 maps: 108 + 18 point rows per crop where the padded fourth tile made it 144).
+struct WinoPart {
+  WinoGeom g;
+  int P;       // transform points = batched GEMMs of this part
+  long v, mw;  // V [P][g.Mt][Cin] and Mw [P][g.Mt][Cout] in the workspace, in floats
+};
+struct WinoPlan {
+  int form, nparts;
+  WinoPart part[2];
+  long tiles, total;  // the tiles of all parts (the transform grids run over them); the workspace in floats
+};
 
-static int wino_points(int form) { return (kWinoTile[form][0] + 2) * (kWinoTile[form][1] + 2); }
+static const int kWinoTile[4][2] = {{2, 2}, {4, 2}, {4, 4}, {4, 4}};  // output tile (MH, MW) per MSOCR_WINO_* form (4X4_COLTAIL: of its square part)
 
-static bool wino_geom(const msocr_conv_desc* d, int form, WinoGeom* g) {
-  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4 || !d || d->dtype != MSOCR_F32) return false;
+static bool wino_plan(const msocr_conv_desc* d, int form, WinoPlan* pl) {
+  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4_COLTAIL || !d || d->dtype != MSOCR_F32) return false;
   if (d->KH != 3 || d->KW != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Ho != d->H || d->Wo != d->W) return false;
   if (d->Cin <= 0 || d->Cin % 16 || d->Cout <= 0 || d->Cout % 32) return false;
   // every form: the F(2x2) tile count fits in 31 bits and the larger of V / Mw in 2^46 elements
   if ((long)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2) > 0x7fffffffL) return false;
   const int mh = kWinoTile[form][0], mw = kWinoTile[form][1];
-  g->N = d->N; g->H = d->H; g->W = d->W;
-  g->TH = (d->H + mh - 1) / mh; g->TW = (d->W + mw - 1) / mw;
-  g->w0 = 0;
-  g->Mt = (long)d->N * g->TH * g->TW;
-  return wino_points(form) * g->Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) <= 0x3fffffffffffL;
+  WinoGeom g;
+  g.N = d->N; g.H = d->H; g.W = d->W;
+  g.TH = (d->H + mh - 1) / mh; g.TW = (d->W + mw - 1) / mw;
+  g.w0 = 0;
+  g.Mt = (long)d->N * g.TH * g.TW;
+  const int P = (mh + 2) * (mw + 2);
+  if (P * g.Mt * (long)(d->Cin > d->Cout ? d->Cin : d->Cout) > 0x3fffffffffffL) return false;
+  pl->form = form;
+  pl->nparts = 1;
+  pl->part[0].g = g; pl->part[0].P = P;
+  if (form == MSOCR_WINO_4X4_COLTAIL) {  // the checks above were the 4X4 form's, on its padded tile count
+    if (d->W < 5 || d->W % 4 != 1) return false;
+    if (d->Cin % 32 || d->Cout % 64) return false;  // the split GEMMs
+    pl->nparts = 2;
+    WinoGeom& g44 = pl->part[0].g;
+    g44.TW = d->W / 4; g44.Mt = (long)d->N * g.TH * g44.TW;
+    WinoGeom& g41 = pl->part[1].g;
+    g41 = g; g41.TW = 1; g41.w0 = d->W - 1; g41.Mt = (long)d->N * g.TH;
+    pl->part[1].P = 18;
+  }
+  pl->tiles = pl->total = 0;
+  for (int i = 0; i < pl->nparts; ++i) {
+    WinoPart& p = pl->part[i];
+    pl->tiles += p.g.Mt;
+    p.v = pl->total;
+    p.mw = p.v + p.P * p.g.Mt * d->Cin;
+    pl->total = p.mw + p.P * p.g.Mt * d->Cout;
+  }
+  return true;
 }
 
 static bool wino_strides_ok(const msocr_conv_desc* d) { return !(d->in_sN % 4 || d->in_sH % 4 || d->in_sW % 4); }
 
-static int wino_check(const msocr_conv_desc* d, int form, WinoGeom* g) {
-  if (!wino_geom(d, form, g) || !wino_strides_ok(d) || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
+static int wino_check(const msocr_conv_desc* d, int form, WinoPlan* pl) {
+  if (!wino_plan(d, form, pl) || !wino_strides_ok(d) || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
   return MSOCR_OK;
 }
 
-// the (form, split) pairs that have GEMM kernels: 2X2 exact, 4X2 exact or split, 4X4 split
+// the (form, split) pairs that have GEMM kernels: 2X2 exact, 4X2 exact or split, 4X4 with or without the tail column split
 static bool wino_gemm_ok(int form, int split) {
   if (split != 0 && split != 1) return false;
-  return form == MSOCR_WINO_4X2 || (form == MSOCR_WINO_2X2 && !split) || (form == MSOCR_WINO_4X4 && split);
+  return form == MSOCR_WINO_4X2 || (form == MSOCR_WINO_2X2 && !split) || ((form == MSOCR_WINO_4X4 || form == MSOCR_WINO_4X4_COLTAIL) && split);
 }
 
 extern "C" int64_t msocr_winograd_workspace_bytes(const msocr_conv_desc* d, int form) {
-  WinoGeom g;
-  if (!wino_geom(d, form, &g)) return -1;
-  return wino_points(form) * g.Mt * ((int64_t)d->Cin + d->Cout) * (int64_t)sizeof(float);
+  WinoPlan pl;
+  if (!wino_plan(d, form, &pl)) return -1;
+  return pl.total * (int64_t)sizeof(float);
 }
 
-static int wino_launch_input(const msocr_conv_desc* d, int form, const WinoGeom& g, const void* in, void* workspace, void* stream) {
+// the transform grids: one thread per tile and 4 channels, the tiles of all parts
+static bool wino_grid(const WinoPlan& pl, int C, dim3* grid) {
+  const long nb = (pl.tiles * (C / 4) + 255) / 256;
+  if (nb > 0x7fffffffL) return false;
+  *grid = dim3((unsigned)nb);
+  return true;
+}
+
+static int wino_launch_input(const msocr_conv_desc* d, const WinoPlan& pl, const void* in, void* workspace, void* stream) {
   if (!in || !workspace || (((uintptr_t)in | (uintptr_t)workspace) & 15)) return MSOCR_E_ARG;
-  const long nb_in = (g.Mt * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  const dim3 grid((unsigned)nb_in), blk(256);
+  dim3 grid;
+  if (!wino_grid(pl, d->Cin, &grid)) return MSOCR_E_ARG;
+  const dim3 blk(256);
   hipStream_t st = (hipStream_t)stream;
   const float* x = (const float*)in;
-  float* V = (float*)workspace;
-  if (form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
-  else if (form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
-  else MSOCR_LAUNCH(wino44_input_kernel, grid, blk, 0, st, x, (long)d->in_sN, (long)d->in_sH, (long)d->in_sW, d->Cin, g, V);
+  float* ws = (float*)workspace;
+  const long sN = d->in_sN, sH = d->in_sH, sW = d->in_sW;
+  const WinoPart& a = pl.part[0];
+  if (pl.nparts == 2) MSOCR_LAUNCH(wino44_input_kernel_coltail, grid, blk, 0, st, x, sN, sH, sW, d->Cin, a.g, pl.part[1].g, ws + a.v, ws + pl.part[1].v);
+  else if (pl.form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_input_kernel, grid, blk, 0, st, x, sN, sH, sW, d->Cin, a.g, ws + a.v);
+  else if (pl.form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_input_kernel, grid, blk, 0, st, x, sN, sH, sW, d->Cin, a.g, ws + a.v);
+  else MSOCR_LAUNCH(wino44_input_kernel, grid, blk, 0, st, x, sN, sH, sW, d->Cin, a.g, ws + a.v);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
 // The three stages of msocr_conv3x3_winograd as separate entry points (same kernels): tests and the per-kernel roofline of
-// bench.py time them one by one.  V = workspace, Mw = workspace + points * tiles * Cin floats.
+// bench.py time them one by one.
 extern "C" int msocr_winograd_input_transform(const msocr_conv_desc* d, int form, const void* in, void* workspace, void* stream) {
-  WinoGeom g;
-  if (wino_check(d, form, &g) != MSOCR_OK) return MSOCR_E_ARG;
-  return wino_launch_input(d, form, g, in, workspace, stream);
+  WinoPlan pl;
+  if (wino_check(d, form, &pl) != MSOCR_OK) return MSOCR_E_ARG;
+  return wino_launch_input(d, pl, in, workspace, stream);
 }
 
-// split = 0: u = [P][Cout][Cin] f32 (exact-f32 MFMA); split = 1: u = K-tile-major bf16 planes [3][P][Cin/32][Cout][32], the P GEMMs on
-// the bf16 matrix pipes with exactly split operands (conv_split.hip / conv_split_pp.hip; V is split in registers)
+// One batched GEMM launch per part, in part order.  split = 0: u = [P][Cout][Cin] f32 (exact-f32 MFMA); split = 1: u = K-tile-major bf16
+// planes [3][P][Cin/32][Cout][32], the P GEMMs on the bf16 matrix pipes with exactly split operands (conv_split.hip / conv_split_pp.hip;
+// V is split in registers).  Two parts: u = the first part's array, then the second's, each with its own plane stride (4X4_COLTAIL:
+// the split of the 4X4 form's [36][Cout][Cin], then the split of the tail tile's [18][Cout][Cin]).
 extern "C" int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const void* u, void* workspace, void* stream) {
-  WinoGeom g;
-  if (!wino_gemm_ok(form, split) || wino_check(d, form, &g) != MSOCR_OK || !u || !workspace) return MSOCR_E_ARG;
+  WinoPlan pl;
+  if (!wino_gemm_ok(form, split) || wino_check(d, form, &pl) != MSOCR_OK || !u || !workspace) return MSOCR_E_ARG;
   if (split && (d->Cin % 32 || d->Cout % 64)) return MSOCR_E_ARG;
-  const int P = wino_points(form);
-  float* V = (float*)workspace;
-  float* Mw = V + P * g.Mt * (long)d->Cin;
-  if (split) return msocr_internal_gemm_split_batched(V, (const uint16_t*)u, Mw, g.Mt, d->Cout, d->Cin, P, (hipStream_t)stream);
-  return msocr_internal_gemm_f32_batched(V, (const float*)u, Mw, g.Mt, d->Cout, d->Cin, P, (hipStream_t)stream);
+  float* ws = (float*)workspace;
+  long uoff = 0;  // in elements of u: a multiple of Cin, so 16-byte aligned in either format
+  for (int i = 0; i < pl.nparts; ++i) {
+    const WinoPart& p = pl.part[i];
+    const int rc = split ? msocr_internal_gemm_split_batched(ws + p.v, (const uint16_t*)u + uoff, ws + p.mw, p.g.Mt, d->Cout, d->Cin, p.P, (hipStream_t)stream)
+                         : msocr_internal_gemm_f32_batched(ws + p.v, (const float*)u + uoff, ws + p.mw, p.g.Mt, d->Cout, d->Cin, p.P, (hipStream_t)stream);
+    if (rc != MSOCR_OK) return rc;
+    uoff += (split ? 3L : 1L) * p.P * d->Cout * d->Cin;
+  }
+  return MSOCR_OK;
 }
 
 extern "C" int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias,
                                                const void* residual, void* out, void* stream) {
-  WinoGeom g;
-  if (wino_check(d, form, &g) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
+  WinoPlan pl;
+  if (wino_check(d, form, &pl) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
   if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
   const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
   if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
   if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
-  const long nb_out = (g.Mt * (d->Cout / 4) + 255) / 256;
-  if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
-  const float* Mw = (const float*)workspace + wino_points(form) * g.Mt * (long)d->Cin;
-  const float* rp = has_res ? (const float*)residual : nullptr;
-  const int relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
-  const dim3 grid((unsigned)nb_out), blk(256);
+  dim3 grid;
+  if (!wino_grid(pl, d->Cout, &grid)) return MSOCR_E_ARG;
+  const dim3 blk(256);
   hipStream_t st = (hipStream_t)stream;
+  const float* ws = (const float*)workspace;
+  const float* rp = has_res ? (const float*)residual : nullptr;
+  const long res_ld = d->res_ld, out_ld = d->out_ld;
+  const int relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
   float* o = (float*)out;
-  if (form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
-  else if (form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
-  else MSOCR_LAUNCH(wino44_output_kernel, grid, blk, 0, st, Mw, d->Cout, g, bias, rp, (long)d->res_ld, relu, o, (long)d->out_ld);
+  const WinoPart& a = pl.part[0];
+  if (pl.nparts == 2) MSOCR_LAUNCH(wino44_output_kernel_coltail, grid, blk, 0, st, ws + a.mw, ws + pl.part[1].mw, d->Cout, a.g, pl.part[1].g, bias, rp, res_ld, relu, o, out_ld);
+  else if (pl.form == MSOCR_WINO_2X2) MSOCR_LAUNCH(wino_output_kernel, grid, blk, 0, st, ws + a.mw, d->Cout, a.g, bias, rp, res_ld, relu, o, out_ld);
+  else if (pl.form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_output_kernel, grid, blk, 0, st, ws + a.mw, d->Cout, a.g, bias, rp, res_ld, relu, o, out_ld);
+  else MSOCR_LAUNCH(wino44_output_kernel, grid, blk, 0, st, ws + a.mw, d->Cout, a.g, bias, rp, res_ld, relu, o, out_ld);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 
@@ -374,94 +433,6 @@ extern "C" int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int sp
   rc = msocr_winograd_gemm(d, form, split, u, workspace, stream);
   if (rc != MSOCR_OK) return rc;
   return msocr_winograd_output_transform(d, form, workspace, bias, residual, out, stream);
-}
-
-// ---- square tiles + tail column: the 4X4 form on maps with W % 4 == 1 without its padded last tile ----------------------------------
-// ceil(W/4) square tiles per tile row would end in a tile with one real output column and three discarded ones (TRBA's 4 x 13 maps:
-// 144 point rows per crop where 108 + the thirteenth column's are needed).  Here the square pass covers tile columns 0 ... W/4 - 1
-// (it reads input column W - 1 as the right halo of its last tile) and output column W - 1 is one F(4,3) x F(1,3) tile per tile row:
-// the 6-point transform along H, the three taps along W summed directly, 6 x 3 = 18 points.  36 * (W/4) + 18 point rows per tile row
-// instead of 36 * (W/4 + 1).  Columns 0 ... W - 2 are the 4X4 form's bit for bit (same tiles, same V rows, same GEMM rows).
-// Workspace: V44 [36][Mt44][Cin] | Mw44 [36][Mt44][Cout] | V41 [18][Mt41][Cin] | Mw41 [18][Mt41][Cout], Mt44 = N TH (W/4), Mt41 = N TH.
-// Split-operand GEMMs only, as the 4X4 form: u44 = the 4X4 form's planes, u41 = the planes of msocr_winograd_coltail_weights_host.
-struct WinoColtail {
-  WinoGeom g44, g41;
-  long v44, mw44, v41, mw41, total;  // workspace offsets, in floats
-};
-
-static bool wino_coltail_geom(const msocr_conv_desc* d, WinoColtail* ct) {
-  WinoGeom g;
-  if (!wino_geom(d, MSOCR_WINO_4X4, &g) || d->W < 5 || d->W % 4 != 1) return false;
-  if (d->Cin % 32 || d->Cout % 64) return false;  // the split GEMMs
-  ct->g44 = g; ct->g44.TW = d->W / 4; ct->g44.Mt = (long)d->N * g.TH * ct->g44.TW;
-  ct->g41 = g; ct->g41.TW = 1; ct->g41.w0 = d->W - 1; ct->g41.Mt = (long)d->N * g.TH;
-  ct->v44 = 0;
-  ct->mw44 = ct->v44 + 36 * ct->g44.Mt * d->Cin;
-  ct->v41 = ct->mw44 + 36 * ct->g44.Mt * d->Cout;
-  ct->mw41 = ct->v41 + 18 * ct->g41.Mt * d->Cin;
-  ct->total = ct->mw41 + 18 * ct->g41.Mt * d->Cout;
-  return true;
-}
-
-static int wino_coltail_check(const msocr_conv_desc* d, WinoColtail* ct) {
-  if (!wino_coltail_geom(d, ct) || !wino_strides_ok(d) || d->out_ld % 4 || d->out_ld < d->Cout) return MSOCR_E_ARG;
-  return MSOCR_OK;
-}
-
-extern "C" int64_t msocr_winograd_coltail_workspace_bytes(const msocr_conv_desc* d) {
-  WinoColtail ct;
-  if (!wino_coltail_geom(d, &ct)) return -1;
-  return ct.total * (int64_t)sizeof(float);
-}
-
-extern "C" int msocr_winograd_coltail_input_transform(const msocr_conv_desc* d, const void* in, void* workspace, void* stream) {
-  WinoColtail ct;
-  if (wino_coltail_check(d, &ct) != MSOCR_OK) return MSOCR_E_ARG;
-  if (!in || !workspace || (((uintptr_t)in | (uintptr_t)workspace) & 15)) return MSOCR_E_ARG;
-  const long nb_in = ((ct.g44.Mt + ct.g41.Mt) * (d->Cin / 4) + 255) / 256;
-  if (nb_in > 0x7fffffffL) return MSOCR_E_ARG;
-  float* ws = (float*)workspace;
-  MSOCR_LAUNCH(wino44_input_kernel_coltail, dim3((unsigned)nb_in), dim3(256), 0, (hipStream_t)stream, (const float*)in, (long)d->in_sN,
-               (long)d->in_sH, (long)d->in_sW, d->Cin, ct.g44, ct.g41, ws + ct.v44, ws + ct.v41);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-// two launches of the batched split GEMM: 36 of Mt44 x Cout x Cin, then 18 of Mt41 x Cout x Cin
-extern "C" int msocr_winograd_coltail_gemm(const msocr_conv_desc* d, const void* u44, const void* u41, void* workspace, void* stream) {
-  WinoColtail ct;
-  if (wino_coltail_check(d, &ct) != MSOCR_OK || !u44 || !u41 || !workspace) return MSOCR_E_ARG;
-  float* ws = (float*)workspace;
-  const int rc = msocr_internal_gemm_split_batched(ws + ct.v44, (const uint16_t*)u44, ws + ct.mw44, ct.g44.Mt, d->Cout, d->Cin, 36, (hipStream_t)stream);
-  if (rc != MSOCR_OK) return rc;
-  return msocr_internal_gemm_split_batched(ws + ct.v41, (const uint16_t*)u41, ws + ct.mw41, ct.g41.Mt, d->Cout, d->Cin, 18, (hipStream_t)stream);
-}
-
-extern "C" int msocr_winograd_coltail_output_transform(const msocr_conv_desc* d, const void* workspace, const float* bias, const void* residual,
-                                                       void* out, void* stream) {
-  WinoColtail ct;
-  if (wino_coltail_check(d, &ct) != MSOCR_OK || !out || !workspace) return MSOCR_E_ARG;
-  if (((uintptr_t)out | (uintptr_t)workspace) & 15) return MSOCR_E_ARG;
-  const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
-  if (has_res && (!residual || d->res_ld % 4 || d->res_ld < d->Cout || ((uintptr_t)residual & 15))) return MSOCR_E_ARG;
-  if (bias && ((uintptr_t)bias & 15)) return MSOCR_E_ARG;
-  const long nb_out = ((ct.g44.Mt + ct.g41.Mt) * (d->Cout / 4) + 255) / 256;
-  if (nb_out > 0x7fffffffL) return MSOCR_E_ARG;
-  const float* ws = (const float*)workspace;
-  const float* rp = has_res ? (const float*)residual : nullptr;
-  const int relu = (d->flags & MSOCR_CONV_RELU) ? 1 : 0;
-  MSOCR_LAUNCH(wino44_output_kernel_coltail, dim3((unsigned)nb_out), dim3(256), 0, (hipStream_t)stream, ws + ct.mw44, ws + ct.mw41, d->Cout,
-               ct.g44, ct.g41, bias, rp, (long)d->res_ld, relu, (float*)out, (long)d->out_ld);
-  return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
-}
-
-extern "C" int msocr_conv3x3_winograd_coltail(const msocr_conv_desc* d, const void* in, const void* u44, const void* u41, const float* bias,
-                                              const void* residual, void* out, void* workspace, void* stream) {
-  if (!u44 || !u41) return MSOCR_E_ARG;
-  int rc = msocr_winograd_coltail_input_transform(d, in, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  rc = msocr_winograd_coltail_gemm(d, u44, u41, workspace, stream);
-  if (rc != MSOCR_OK) return rc;
-  return msocr_winograd_coltail_output_transform(d, workspace, bias, residual, out, stream);
 }
 
 // =====================================================================================================================
@@ -859,8 +830,8 @@ __global__ __launch_bounds__(256, 2) void wino42_fused64_v2_kernel(const float* 
   }
 }
 
-static int wino_fused64_check(const msocr_conv_desc* d, WinoGeom* g) {
-  if (!wino_geom(d, MSOCR_WINO_4X2, g) || d->Cin != 64 || !wino_strides_ok(d) || d->out_ld < d->Cout) return MSOCR_E_ARG;
+static int wino_fused64_check(const msocr_conv_desc* d, WinoPlan* pl) {
+  if (!wino_plan(d, MSOCR_WINO_4X2, pl) || d->Cin != 64 || !wino_strides_ok(d) || d->out_ld < d->Cout) return MSOCR_E_ARG;
   if (d->flags & MSOCR_CONV_POOL2) {
     if ((d->H & 1) || (d->W & 1) || (d->flags & MSOCR_CONV_RESIDUAL)) return MSOCR_E_ARG;
   }
@@ -868,9 +839,9 @@ static int wino_fused64_check(const msocr_conv_desc* d, WinoGeom* g) {
 }
 
 extern "C" int64_t msocr_winograd_fused64_workspace_bytes(const msocr_conv_desc* d) {
-  WinoGeom g;
-  if (wino_fused64_check(d, &g) != MSOCR_OK) return -1;
-  return 24 * g.Mt * (int64_t)d->Cin * (int64_t)sizeof(float);
+  WinoPlan pl;
+  if (wino_fused64_check(d, &pl) != MSOCR_OK) return -1;
+  return 24 * pl.part[0].g.Mt * (int64_t)d->Cin * (int64_t)sizeof(float);
 }
 
 // stage 2 of msocr_conv3x3_winograd_fused64 (stage 1 is msocr_winograd_input_transform of the 4X2 form): V in the workspace -> out.
@@ -878,8 +849,9 @@ extern "C" int64_t msocr_winograd_fused64_workspace_bytes(const msocr_conv_desc*
 // bf16 matrix pipes with exactly split operands
 extern "C" int msocr_winograd_fused64_gemm_output(const msocr_conv_desc* d, int split, const void* u, const void* workspace,
                                                   const float* bias, const void* residual, void* out, void* stream) {
-  WinoGeom g;
-  if ((split != 0 && split != 1) || wino_fused64_check(d, &g) != MSOCR_OK || !u || !workspace || !out) return MSOCR_E_ARG;
+  WinoPlan pl;
+  if ((split != 0 && split != 1) || wino_fused64_check(d, &pl) != MSOCR_OK || !u || !workspace || !out) return MSOCR_E_ARG;
+  const WinoGeom& g = pl.part[0].g;
   if (((uintptr_t)workspace | (uintptr_t)u) & 15) return MSOCR_E_ARG;
   const bool has_res = (d->flags & MSOCR_CONV_RESIDUAL) != 0;
   if (has_res && (!residual || d->res_ld < d->Cout)) return MSOCR_E_ARG;
@@ -915,27 +887,32 @@ extern "C" int msocr_winograd_fused64_gemm_output(const msocr_conv_desc* d, int 
 
 extern "C" int msocr_conv3x3_winograd_fused64(const msocr_conv_desc* d, int split, const void* in, const void* u, const float* bias,
                                               const void* residual, void* out, void* workspace, void* stream) {
-  WinoGeom g;
-  if ((split != 0 && split != 1) || wino_fused64_check(d, &g) != MSOCR_OK || !u) return MSOCR_E_ARG;
-  const int rc = wino_launch_input(d, MSOCR_WINO_4X2, g, in, workspace, stream);
+  WinoPlan pl;
+  if ((split != 0 && split != 1) || wino_fused64_check(d, &pl) != MSOCR_OK || !u) return MSOCR_E_ARG;
+  const int rc = wino_launch_input(d, pl, in, workspace, stream);
   if (rc != MSOCR_OK) return rc;
   return msocr_winograd_fused64_gemm_output(d, split, u, workspace, bias, residual, out, stream);
 }
 
+static const double kWinoG4[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};  // F(2,3) on {0, 1, -1, inf}
 static const double kWinoG6[6][3] = {{1.0, 0.0, 0.0},                                                      // F(4,3): wino44_bt's points
                                      {8.0 / 65, 12.0 / 65, 18.0 / 65},     {8.0 / 65, -12.0 / 65, 18.0 / 65},
                                      {-81.0 / 130, -27.0 / 65, -18.0 / 65}, {-81.0 / 130, 27.0 / 65, -18.0 / 65},
                                      {0.0, 0.0, 1.0}};
+static const double kWinoG3[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};                    // F(1,3): the taps themselves
+
+static const double (*wino_g(int points))[3] { return points == 6 ? kWinoG6 : points == 4 ? kWinoG4 : kWinoG3; }
 
 // U[xi*PW+nu][co][c] = sum_{kh,kw} Gh[xi][kh] Gw[nu][kw] w[co][kh][kw][c] (xi on the kernel's H axis), evaluated in f64 (G g over kh
-// first, then over kw) and rounded once to f32.  HOST function (runs at weight-load time): w_khwc and u_out are host pointers.
+// first, then over kw) and rounded once to f32, [PH*PW][Cout][Cin]: one tile's planes per call.  4X4_COLTAIL: its tail tile's,
+// F(4,3) x F(1,3) with Gw = the identity, [18][Cout][Cin]; its square tiles' planes are the 4X4 form's call.  u_out carries no size,
+// and no call writes more than the 36 planes of the largest tile.  HOST function (runs at weight-load time): w_khwc and u_out are
+// host pointers.
 extern "C" int msocr_winograd_weights_host(int form, const float* w_khwc, int Cout, int Cin, float* u_out) {
-  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4 || !w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
-  static const double G4[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};  // F(2,3) on {0, 1, -1, inf}
-  const double(*G6)[3] = kWinoG6;
-  const int PH = kWinoTile[form][0] + 2, PW = kWinoTile[form][1] + 2;
-  const double(*Gh)[3] = PH == 6 ? G6 : G4;
-  const double(*Gw)[3] = PW == 6 ? G6 : G4;
+  if (form < MSOCR_WINO_2X2 || form > MSOCR_WINO_4X4_COLTAIL || !w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
+  const int PH = kWinoTile[form][0] + 2, PW = form == MSOCR_WINO_4X4_COLTAIL ? 1 + 2 : kWinoTile[form][1] + 2;  // the tail tile is 4 x 1
+  const double(*Gh)[3] = wino_g(PH);
+  const double(*Gw)[3] = wino_g(PW);
   const long plane = (long)Cout * Cin;
   for (int co = 0; co < Cout; ++co) {
     const float* w = w_khwc + (long)co * 9 * Cin;
@@ -949,23 +926,6 @@ extern "C" int msocr_winograd_weights_host(int form, const float* w_khwc, int Co
           u_out[(xi * PW + nu) * plane + (long)co * Cin + c] =
               (float)(gw[xi][0] * Gw[nu][0] + gw[xi][1] * Gw[nu][1] + gw[xi][2] * Gw[nu][2]);
     }
-  }
-  return MSOCR_OK;
-}
-
-// The tail column's weights, F(4,3) x F(1,3): U[xi*3+kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c] (Gw = the identity), [18][Cout][Cin],
-// in f64 and rounded once.  HOST function, as msocr_winograd_weights_host.
-extern "C" int msocr_winograd_coltail_weights_host(const float* w_khwc, int Cout, int Cin, float* u_out) {
-  if (!w_khwc || !u_out || Cout <= 0 || Cin <= 0) return MSOCR_E_ARG;
-  const long plane = (long)Cout * Cin;
-  for (int co = 0; co < Cout; ++co) {
-    const float* w = w_khwc + (long)co * 9 * Cin;
-    for (int c = 0; c < Cin; ++c)
-      for (int xi = 0; xi < 6; ++xi)
-        for (int kw = 0; kw < 3; ++kw)
-          u_out[(xi * 3 + kw) * plane + (long)co * Cin + c] =
-              (float)(kWinoG6[xi][0] * w[(0 * 3 + kw) * Cin + c] + kWinoG6[xi][1] * w[(1 * 3 + kw) * Cin + c] +
-                      kWinoG6[xi][2] * w[(2 * 3 + kw) * Cin + c]);
   }
   return MSOCR_OK;
 }

@@ -133,20 +133,31 @@ def _square_pays(W):
     return points < 24 * (-(-W // 2))
 
 
-# The Winograd tile forms (csrc/winograd.hip, include/msocr.h MSOCR_WINO_*): form id -> (PROFILE tag stem, transform points, output tile)
-WINO_FORMS = {nat.WINO_2X2: ("winograd", 16, (2, 2)), nat.WINO_4X2: ("winograd42", 24, (4, 2)), nat.WINO_4X4: ("winograd44", 36, (4, 4))}
+# The Winograd tile forms (csrc/winograd.hip, include/msocr.h MSOCR_WINO_*): form id -> (PROFILE tag stem, transform points, output tile);
+# the square form + tail column is a square-form layer to the profile: 36 points of the square tiles, then 18 of the tail column's
+WINO_FORMS = {nat.WINO_2X2: ("winograd", 16, (2, 2)), nat.WINO_4X2: ("winograd42", 24, (4, 2)), nat.WINO_4X4: ("winograd44", 36, (4, 4)),
+              nat.WINO_4X4_COLTAIL: ("winograd44", 36 + 18, (4, 4))}
+
+
+def _wino_rows(form, nn, H, W):
+    """(point rows, tiles) of nn H x W images in a form: the rows of V and of Mw, and the tiles the transform kernels run over."""
+    _, npts, (mh, mw) = WINO_FORMS[form]
+    TH = -(-H // mh)
+    if form == nat.WINO_4X4_COLTAIL:  # 36 per square tile + 18 per tail tile
+        mt44, mt41 = nn * TH * (W // 4), nn * TH
+        return 36 * mt44 + 18 * mt41, mt44 + mt41
+    mt = nn * TH * -(-W // mw)
+    return npts * mt, mt
 
 
 def _wino_weights(wh, form):
-    """Host [Cout,3,3,Cin] f32 weight -> U [points, Cout, Cin] f32 (msocr_winograd_weights_host: f64, rounded once); form "coltail":
-    the tail column's [18, Cout, Cin] (msocr_winograd_coltail_weights_host)."""
+    """Host [Cout,3,3,Cin] f32 weight -> U [points, Cout, Cin] f32 (msocr_winograd_weights_host: f64, rounded once, one tile's planes
+    per call); WINO_4X4_COLTAIL: [54, Cout, Cin], the WINO_4X4 form's 36 planes, then the 18 of its tail tile."""
     Cout, _, _, Cin = wh.shape
-    if form == "coltail":
-        u = torch.empty((18, Cout, Cin), dtype=torch.float32)
-        nat.check(nat.lib().msocr_winograd_coltail_weights_host(wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_coltail_weights_host")
-        return u
     u = torch.empty((WINO_FORMS[form][1], Cout, Cin), dtype=torch.float32)
-    nat.check(nat.lib().msocr_winograd_weights_host(form, wh.data_ptr(), Cout, Cin, u.data_ptr()), "winograd_weights_host")
+    calls = [(nat.WINO_4X4, u[:36]), (form, u[36:])] if form == nat.WINO_4X4_COLTAIL else [(form, u)]
+    for f, planes in calls:
+        nat.check(nat.lib().msocr_winograd_weights_host(f, wh.data_ptr(), Cout, Cin, planes.data_ptr()), "winograd_weights_host")
     return u
 
 
@@ -238,26 +249,26 @@ def attach_winograd(w, split=None, square=True):
     if (SPLIT_BF16X3 if split is None else split) and Cin % 32 == 0 and Cout % 64 == 0:
         w._msocr_wino42_split = split_planes_ktile(u42, 24, Cout).to(w.device)  # [3][24][Cin/32][Cout][32] bf16
         if WINOGRAD_SQUARE and square and Cin >= WINOGRAD_SQUARE_MIN_CIN:  # square=False: the caller keeps this layer on the tall form (half the rounding error)
-            w._msocr_wino44_split = split_planes_ktile(_wino_weights(wh, nat.WINO_4X4), 36, Cout).to(w.device)  # [3][36][Cin/32][Cout][32] bf16
-            w._msocr_wino41_split = split_planes_ktile(_wino_weights(wh, "coltail"), 18, Cout).to(w.device)  # [3][18][Cin/32][Cout][32] bf16: the tail column
+            # ONE buffer, as the 4X4_COLTAIL form reads it: the split of the square form's 36 planes, then the split of the tail column's 18;
+            # the 4X4 form reads the first group alone
+            u54 = _wino_weights(wh, nat.WINO_4X4_COLTAIL)
+            p44, p41 = split_planes_ktile(u54[:36], 36, Cout), split_planes_ktile(u54[36:], 18, Cout)
+            w._msocr_wino44ct_split = torch.cat([p44.reshape(-1), p41.reshape(-1)]).to(w.device)
+            w._msocr_wino44_split = w._msocr_wino44ct_split[:p44.numel()].view(p44.shape)  # [3][36][Cin/32][Cout][32] bf16
+            w._msocr_wino41_split = w._msocr_wino44ct_split[p44.numel():].view(p41.shape)  # [3][18][Cin/32][Cout][32] bf16: the tail column
     return w
 
 
-def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False, u41=None):
+def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False):
     """One Winograd convolution described by d (3x3/1/1, f32) in the given form: the workspace from the per-stream arena, the batch cut
     so that it stays under WINO_WS_LIMIT, and per part either the one-call entry point or — with PROFILE on — the stages one by one,
     one event pair each.  fused: the Cin = 64 tall form with the GEMMs and the output transform (+ the 2x2 max-pool) in one kernel.
-    u41: the square form as square tiles + tail column (W % 4 == 1), u41 the tail column's planes; still ONE conv_gemm record, spanning
-    both GEMM launches."""
+    The square form + tail column is still ONE conv_gemm record, spanning both GEMM launches."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
-    stem, npts, (mh, mw) = WINO_FORMS[form]
-    name = stem + ("_fused" if fused else "") + ("_split" if split else "")
+    name = WINO_FORMS[form][0] + ("_fused" if fused else "") + ("_split" if split else "")
     L = nat.lib()
-    if u41 is not None:
-        nbytes = L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(d))
-    else:
-        nbytes = L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) if fused else L.msocr_winograd_workspace_bytes(ctypes.byref(d), form)
+    nbytes = L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) if fused else L.msocr_winograd_workspace_bytes(ctypes.byref(d), form)
     if nbytes < 0:
         raise nat.NativeError(f"{name}: unsupported shape {tuple(x.shape)} * {tuple(w.shape)} pool2={pool2}")
     parts = min(N, -(-nbytes // WINO_WS_LIMIT))  # images per call such that the workspace stays under the limit
@@ -265,7 +276,6 @@ def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, po
     ws = _wino_workspace(nbytes if parts == 1 else (nbytes // N) * per, x.device)
     bp = bias.data_ptr() if bias is not None else None
     what = f"msocr_conv3x3_{name} {tuple(x.shape)} * {tuple(w.shape)}"
-    TH, TW = -(-H // mh), -(-W // mw)
     out_px = H * W // (4 if pool2 else 1)
     res_io = 2 if residual is not None else 1
     for n0 in range(0, N, per):
@@ -273,32 +283,17 @@ def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, po
         d.N = n1 - n0
         xp, rp, op = x[n0:n1].data_ptr(), (residual[n0:n1].data_ptr() if residual is not None else None), out[n0:n1].data_ptr()
         if PROFILE is None:
-            if u41 is not None:
-                rc = L.msocr_conv3x3_winograd_coltail(ctypes.byref(d), xp, u.data_ptr(), u41.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
-            elif fused:
+            if fused:
                 rc = L.msocr_conv3x3_winograd_fused64(ctypes.byref(d), int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
             else:
                 rc = L.msocr_conv3x3_winograd(ctypes.byref(d), form, int(split), xp, u.data_ptr(), bp, rp, op, ws.data_ptr(), _stream())
             nat.check(rc, what)
             continue
-        nn, mt = n1 - n0, (n1 - n0) * TH * TW
-        if u41 is not None:  # point rows: 36 per square tile + 18 per tail tile; the records' tile count is that of both parts
-            mt44, mt41 = nn * TH * (W // 4), nn * TH
-            rows, mt = 36 * mt44 + 18 * mt41, mt44 + mt41
-            e = _prof_begin()
-            nat.check(L.msocr_winograd_coltail_input_transform(ctypes.byref(d), xp, ws.data_ptr(), _stream()), what)
-            _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + rows * Cin), (mt, Cin))
-            e = _prof_begin()
-            nat.check(L.msocr_winograd_coltail_gemm(ctypes.byref(d), u.data_ptr(), u41.data_ptr(), ws.data_ptr(), _stream()), what)
-            io = x.element_size() * (nn * H * W * Cin + nn * out_px * Cout * res_io + Cout * 9 * Cin)
-            _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * rows * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
-            e = _prof_begin()
-            nat.check(L.msocr_winograd_coltail_output_transform(ctypes.byref(d), ws.data_ptr(), bp, rp, op, _stream()), what)
-            _prof_end(e, "wino_out", 4.0 * (rows * Cout + nn * H * W * Cout * res_io), (mt, Cout))
-            continue
+        nn = n1 - n0
+        rows, mt = _wino_rows(form, nn, H, W)
         e = _prof_begin()
         nat.check(L.msocr_winograd_input_transform(ctypes.byref(d), form, xp, ws.data_ptr(), _stream()), what)
-        _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + npts * mt * Cin), (mt, Cin))
+        _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + rows * Cin), (mt, Cin))
         e = _prof_begin()
         if fused:
             rc = L.msocr_winograd_fused64_gemm_output(ctypes.byref(d), int(split), u.data_ptr(), ws.data_ptr(), bp, rp, op, _stream())
@@ -306,11 +301,11 @@ def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, po
             rc = L.msocr_winograd_gemm(ctypes.byref(d), form, int(split), u.data_ptr(), ws.data_ptr(), _stream())
         nat.check(rc, what)
         io = x.element_size() * (nn * H * W * Cin + nn * out_px * Cout * res_io + Cout * 9 * Cin)
-        _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * npts * mt * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
+        _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * rows * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
         if not fused:
             e = _prof_begin()
             nat.check(L.msocr_winograd_output_transform(ctypes.byref(d), form, ws.data_ptr(), bp, rp, op, _stream()), what)
-            _prof_end(e, "wino_out", 4.0 * (npts * mt * Cout + nn * H * W * Cout * res_io), (mt, Cout))
+            _prof_end(e, "wino_out", 4.0 * (rows * Cout + nn * H * W * Cout * res_io), (mt, Cout))
     d.N = N
 
 
@@ -361,17 +356,16 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
         u = w._msocr_wino42_fused if up is None else up
         _winograd(d, x, w, u, nat.WINO_4X2, up is not None, bias, residual, out, alg, fused=True, pool2=pool2)
     elif use_wino:
-        form, split, u41 = nat.WINO_2X2, False, None
+        form, split = nat.WINO_2X2, False
         if WINOGRAD_TALL and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None:
             form, u = nat.WINO_4X2, w._msocr_wino42
             up = getattr(w, "_msocr_wino42_split", None)
             if up is not None and SPLIT_BF16X3:  # the 24 GEMMs on the bf16 pipes with exactly split operands
                 u, split = up, True
-            up44 = getattr(w, "_msocr_wino44_split", None)
+            up44 = getattr(w, "_msocr_wino44ct_split", None)  # the 4X4 form reads the first 36 planes of the buffer, the composite all 54
             if up44 is not None and SPLIT_BF16X3 and WINOGRAD_SQUARE and _square_pays(W):
-                form, u, split = nat.WINO_4X4, up44, True
-                u41 = getattr(w, "_msocr_wino41_split", None) if _coltail(W) else None
-        _winograd(d, x, w, u, form, split, bias, residual, out, alg, u41=u41)
+                form, u, split = nat.WINO_4X4_COLTAIL if _coltail(W) else nat.WINO_4X4, up44, True
+        _winograd(d, x, w, u, form, split, bias, residual, out, alg)
     else:
         wp = getattr(w, "_msocr_split", None)
         if (wp is None and SPLIT_BF16X3 and not getattr(w, "_msocr_nosplit", False) and _split_eligible(w)

@@ -475,8 +475,9 @@ def test_vectorised_crop_descriptors_equal_the_loop():
 
 def test_winograd_weight_transform_host_by_form():
     """The load-time weight transforms are HOST functions of the C ABI (f64, rounded once): U = G g G^T for F(2x2,3x3), U = G6 g G4^T
-    for the tall form F(4,3) x F(2,3) and U = G6 g G6^T for the square form, G6 = the Cook-Toom matrix of F(4,3) on the interpolation
-    points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4), checked against their definitions without a GPU."""
+    for the tall form F(4,3) x F(2,3), U = G6 g G6^T for the square form and U = G6 g for the tail tile of the fourth form (18 planes
+    per call; 54 with the square tiles' before them), G6 = the Cook-Toom matrix of F(4,3) on the interpolation points {0, 3/2, -3/2, 2/3, -2/3, inf} (round 4),
+    checked against their definitions without a GPU."""
     from manuscript_ocr_amd import _native as nat
     L = nat.lib()
     rng = np.random.default_rng(11)
@@ -488,7 +489,8 @@ def test_winograd_weight_transform_host_by_form():
     for j, a in enumerate(pts):   # G[j] = [1, a, a^2] / prod_{l != j}(a_j - a_l); the point at infinity: [0, 0, 1]
         G6[j] = np.array([1.0, a, a * a]) / np.prod([a - b for l, b in enumerate(pts) if l != j])
     G6[5, 2] = 1.0
-    for form, Gh, Gw, npts in ((nat.WINO_2X2, G4, G4, 16), (nat.WINO_4X2, G6, G4, 24), (nat.WINO_4X4, G6, G6, 36)):
+    for form, Gh, Gw, npts in ((nat.WINO_2X2, G4, G4, 16), (nat.WINO_4X2, G6, G4, 24), (nat.WINO_4X4, G6, G6, 36),
+                               (nat.WINO_4X4_COLTAIL, G6, np.eye(3), 18)):
         u = np.empty((npts, Cout, Cin), np.float32)
         assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, u.ctypes.data) == 0
         exp = np.einsum("xk,oklc,nl->xnoc", Gh, w.astype(np.float64), Gw).reshape(npts, Cout, Cin)
@@ -496,40 +498,61 @@ def test_winograd_weight_transform_host_by_form():
         assert L.msocr_winograd_weights_host(form, None, Cout, Cin, u.ctypes.data) == -1
         assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, None) == -1
         assert L.msocr_winograd_weights_host(form, None, Cout, Cin, None) != 0
+    # the planes of a form as the GEMMs take them (ops._wino_weights): the table's, and for the fourth form the square form's 36
+    # followed by the tail tile's 18
+    import torch
+    from manuscript_ocr_amd import ops
+    for form, parts, npts in ((nat.WINO_2X2, [(G4, G4)], 16), (nat.WINO_4X2, [(G6, G4)], 24), (nat.WINO_4X4, [(G6, G6)], 36),
+                              (nat.WINO_4X4_COLTAIL, [(G6, G6), (G6, np.eye(3))], 54)):
+        u = ops._wino_weights(torch.from_numpy(w), form).numpy()
+        exp = np.concatenate([np.einsum("xk,oklc,nl->xnoc", Gh, w.astype(np.float64), Gw).reshape(-1, Cout, Cin) for Gh, Gw in parts])
+        assert u.shape == exp.shape == (npts, Cout, Cin)
+        assert np.abs(u.astype(np.float64) - exp).max() <= 1.2e-7 * np.abs(exp).max()
     u = np.empty((36, Cout, Cin), np.float32)
-    for form in (-1, 3, 99):  # unknown form ids
+    for form in (-1, 4, 99):  # unknown form ids
         assert L.msocr_winograd_weights_host(form, w.ctypes.data, Cout, Cin, u.ctypes.data) == -1
 
 
+def _wino_desc(N, H, W, Cin, Cout, stride=1):
+    from manuscript_ocr_amd import _native as nat
+    d = nat.ConvDesc()
+    d.dtype, d.N, d.H, d.W, d.Cin = nat.F32, N, H, W, Cin
+    d.in_sN, d.in_sH, d.in_sW = H * W * Cin, W * Cin, Cin
+    d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, stride, stride, 1, 1
+    d.Ho, d.Wo, d.Cout = (H - 1) // stride + 1, (W - 1) // stride + 1, Cout
+    d.out_ld = d.res_ld = Cout
+    return d
+
+
 def test_winograd_workspace_bytes_and_form_arguments():
-    """msocr_winograd_workspace_bytes = points * N ceil(H/mh) ceil(W/mw) * (Cin + Cout) * 4 per form, -1 for shapes without a Winograd
-    form; unknown form ids and (form, split) pairs without a GEMM kernel are MSOCR_E_ARG before anything is launched (no GPU needed)."""
+    """msocr_winograd_workspace_bytes = points * N ceil(H/mh) ceil(W/mw) * (Cin + Cout) * 4 per form (square tiles + tail column:
+    (36 * N ceil(H/4) (W // 4) + 18 * N ceil(H/4)) * (Cin + Cout) * 4 where W % 4 == 1), -1 for shapes without a Winograd form;
+    unknown form ids and (form, split) pairs without a GEMM kernel are MSOCR_E_ARG before anything is launched (no GPU needed)."""
     from manuscript_ocr_amd import _native as nat
     L = nat.lib()
-
-    def desc(N, H, W, Cin, Cout, stride=1):
-        d = nat.ConvDesc()
-        d.dtype, d.N, d.H, d.W, d.Cin = nat.F32, N, H, W, Cin
-        d.in_sN, d.in_sH, d.in_sW = H * W * Cin, W * Cin, Cin
-        d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, stride, stride, 1, 1
-        d.Ho, d.Wo, d.Cout = (H - 1) // stride + 1, (W - 1) // stride + 1, Cout
-        d.out_ld = d.res_ld = Cout
-        return d
-
+    desc = _wino_desc
+    SHAPES = ((2, 8, 25, 256, 256), (3, 4, 13, 512, 512), (1, 17, 23, 128, 64), (5, 7, 9, 16, 32), (960, 32, 100, 64, 128))
     for form, npts, (mh, mw) in ((nat.WINO_2X2, 16, (2, 2)), (nat.WINO_4X2, 24, (4, 2)), (nat.WINO_4X4, 36, (4, 4))):
-        for N, H, W, Cin, Cout in ((2, 8, 25, 256, 256), (3, 4, 13, 512, 512), (1, 17, 23, 128, 64), (5, 7, 9, 16, 32), (960, 32, 100, 64, 128)):
+        for N, H, W, Cin, Cout in SHAPES:
             exp = npts * N * -(-H // mh) * -(-W // mw) * (Cin + Cout) * 4
             assert L.msocr_winograd_workspace_bytes(ctypes.byref(desc(N, H, W, Cin, Cout)), form) == exp, (form, N, H, W, Cin, Cout)
         for d in (desc(1, 8, 8, 24, 64), desc(1, 8, 8, 128, 48), desc(1, 8, 8, 128, 64, stride=2)):  # Cin % 16, Cout % 32, stride 2
             assert L.msocr_winograd_workspace_bytes(ctypes.byref(d), form) == -1
+    for N, H, W, Cin, Cout in SHAPES:
+        TH = -(-H // 4)
+        # the form's shapes: W % 4 == 1 and the split GEMMs' channel counts ((5, 7, 9, 16, 32) has the width but not the channels)
+        exp = (36 * N * TH * (W // 4) + 18 * N * TH) * (Cin + Cout) * 4 if W % 4 == 1 and Cin % 32 == 0 and Cout % 64 == 0 else -1
+        assert L.msocr_winograd_workspace_bytes(ctypes.byref(desc(N, H, W, Cin, Cout)), nat.WINO_4X4_COLTAIL) == exp, (N, H, W, Cin, Cout)
+    for d in (desc(1, 8, 8, 24, 64), desc(1, 8, 8, 128, 48), desc(1, 8, 8, 128, 64, stride=2)):
+        assert L.msocr_winograd_workspace_bytes(ctypes.byref(d), nat.WINO_4X4_COLTAIL) == -1
     d = desc(2, 8, 8, 128, 128)
-    for form in (-1, 3):
+    for form in (-1, 4):
         assert L.msocr_winograd_workspace_bytes(ctypes.byref(d), form) == -1
     fake = ctypes.c_void_p(1 << 20)  # never dereferenced: every call below fails its argument checks first
-    for form, split in ((nat.WINO_2X2, 1), (nat.WINO_4X4, 0), (nat.WINO_4X2, 2), (3, 0), (-1, 1)):
+    for form, split in ((nat.WINO_2X2, 1), (nat.WINO_4X4, 0), (nat.WINO_4X2, 2), (nat.WINO_4X4_COLTAIL, 0), (4, 0), (-1, 1)):
         assert L.msocr_winograd_gemm(ctypes.byref(d), form, split, fake, fake, None) == -1
         assert L.msocr_conv3x3_winograd(ctypes.byref(d), form, split, fake, fake, None, None, fake, fake, None) == -1
-    for form in (-1, 3):
+    for form in (-1, 4):
         assert L.msocr_winograd_input_transform(ctypes.byref(d), form, fake, fake, None) == -1
         assert L.msocr_winograd_output_transform(ctypes.byref(d), form, fake, None, None, fake, None) == -1
     d64 = desc(2, 8, 8, 64, 128)
@@ -537,6 +560,59 @@ def test_winograd_workspace_bytes_and_form_arguments():
     assert L.msocr_winograd_fused64_workspace_bytes(ctypes.byref(d)) == -1  # Cin != 64
     assert L.msocr_winograd_fused64_gemm_output(ctypes.byref(d64), 2, fake, fake, None, None, fake, None) == -1
     assert L.msocr_conv3x3_winograd_fused64(ctypes.byref(d64), 2, fake, fake, None, None, fake, fake, None) == -1
+
+
+def test_winograd_stage_argument_checks_hold_for_every_form():
+    """The pointer, alignment, residual, bias and out_ld checks of the three stages are written once for the four forms: on a valid
+    descriptor of each form, every one of them is MSOCR_E_ARG before anything is launched (no GPU needed).  The one-call entry point
+    is asked only what it refuses before its first stage launches.  The GEMM stage's own checks in winograd.hip are the null
+    pointers; a misaligned workspace is refused by the batched GEMM it hands the workspace to (conv_common.h gemm_params), also before
+    any launch."""
+    from manuscript_ocr_amd import _native as nat
+    L = nat.lib()
+    fake = 1 << 20   # never dereferenced: every call below fails its argument checks first
+    odd = fake + 4   # 4-byte aligned only
+    for form, split, shape in ((nat.WINO_2X2, 0, (2, 8, 8, 128, 128)), (nat.WINO_4X2, 1, (2, 8, 8, 128, 128)),
+                               (nat.WINO_4X4, 1, (2, 8, 12, 128, 128)), (nat.WINO_4X4_COLTAIL, 1, (2, 8, 13, 128, 128))):
+        Cout = shape[4]
+
+        def D(**fields):
+            d = _wino_desc(*shape)
+            for k, v in fields.items():
+                setattr(d, k, v)
+            return ctypes.byref(d)
+
+        def inp(r, x=fake, ws=fake):
+            return L.msocr_winograd_input_transform(r, form, x, ws, None)
+
+        def gemm(r, u=fake, ws=fake):
+            return L.msocr_winograd_gemm(r, form, split, u, ws, None)
+
+        def outp(r, ws=fake, bias=None, res=None, out=fake):
+            return L.msocr_winograd_output_transform(r, form, ws, bias, res, out, None)
+
+        def conv(r, x=fake, u=fake, ws=fake):
+            return L.msocr_conv3x3_winograd(r, form, split, x, u, None, None, fake, ws, None)
+
+        assert L.msocr_winograd_workspace_bytes(D(), form) > 0, form
+        res = dict(flags=nat.CONV_RESIDUAL)
+        refused = {
+            "null input": [inp(D(), x=None), conv(D(), x=None)],
+            "misaligned input": [inp(D(), x=odd), conv(D(), x=odd)],
+            "null workspace": [inp(D(), ws=None), gemm(D(), ws=None), outp(D(), ws=None), conv(D(), ws=None)],
+            "misaligned workspace": [inp(D(), ws=odd), gemm(D(), ws=odd), outp(D(), ws=odd), conv(D(), ws=odd)],
+            "null u": [gemm(D(), u=None), conv(D(), u=None)],
+            "null output": [outp(D(), out=None)],
+            "misaligned output": [outp(D(), out=odd)],
+            "misaligned bias": [outp(D(), bias=odd)],
+            "residual flag, null residual": [outp(D(**res), res=None)],
+            "residual flag, misaligned residual": [outp(D(**res), res=odd)],
+            "res_ld < Cout": [outp(D(res_ld=Cout - 4, **res), res=fake)],
+            "res_ld % 4": [outp(D(res_ld=Cout + 2, **res), res=fake)],
+            "out_ld < Cout": [inp(D(out_ld=Cout - 4)), gemm(D(out_ld=Cout - 4)), outp(D(out_ld=Cout - 4)), conv(D(out_ld=Cout - 4))],
+        }
+        for what, rcs in refused.items():
+            assert rcs == [-1] * len(rcs), (form, what, rcs)
 
 
 def test_bench_live_pmc_digest_with_a_stub_profiler(tmp_path, monkeypatch):

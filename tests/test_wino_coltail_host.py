@@ -1,4 +1,4 @@
-"""Square tiles + tail column (csrc/winograd.hip, msocr_winograd_coltail_*): the host side, without a GPU.
+"""Square tiles + tail column (csrc/winograd.hip, form MSOCR_WINO_4X4_COLTAIL of the shared entry points): the host side, without a GPU.
 
 The tail column of a map with W % 4 == 1 is F(4,3) along H and the three taps along W summed directly, so its weights are
 U[xi*3 + kw][co][c] = sum_kh G6[xi][kh] w[co][kh][kw][c] with G6 the Cook-Toom matrix of F(4,3) on {0, +-3/2, +-2/3, inf}.
@@ -28,23 +28,35 @@ def _desc(nat, N, H, W, Cin, Cout, stride=1):
 
 
 def test_coltail_weights_host_match_cook_toom_definition():
-    """f64, rounded once: within 1 ulp of the einsum (another summation order), the 1.2e-7 * max rule of the other forms."""
+    """f64, rounded once: within 1 ulp of the einsum (another summation order), the 1.2e-7 * max rule of the other forms.  The form's
+    54 planes (ops._wino_weights) are the 4X4 form's 36, then the tail tile's 18; the C call with the form gives the tail tile's and
+    writes no more than those."""
+    import torch
     from manuscript_ocr_amd import _native as nat
+    from manuscript_ocr_amd import ops
     L = nat.lib()
+    CT = nat.WINO_4X4_COLTAIL
     rng = np.random.default_rng(41)
     for Cout, Cin in ((32, 16), (64, 96)):
         w = rng.standard_normal((Cout, 3, 3, Cin)).astype(np.float32)  # [Cout][KH][KW][Cin]
-        u = np.empty((18, Cout, Cin), np.float32)
-        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, Cin, u.ctypes.data) == 0
+        u54 = ops._wino_weights(torch.from_numpy(w), CT).numpy()
+        assert u54.shape == (54, Cout, Cin)
+        u44 = np.empty((36, Cout, Cin), np.float32)
+        assert L.msocr_winograd_weights_host(nat.WINO_4X4, w.ctypes.data, Cout, Cin, u44.ctypes.data) == 0
+        assert np.array_equal(u54[:36], u44)
+        u = u54[36:54]
+        buf = np.full((18 + 1, Cout, Cin), 7.0, np.float32)   # the tail tile's call alone, one sentinel plane behind
+        assert L.msocr_winograd_weights_host(CT, w.ctypes.data, Cout, Cin, buf.ctypes.data) == 0
+        assert np.array_equal(buf[:18], u) and np.all(buf[18] == 7.0)
         exp = np.einsum("xk,oklc->xloc", _g6(), w.astype(np.float64)).reshape(18, Cout, Cin)
         assert np.abs(u.astype(np.float64) - exp).max() <= 1.2e-7 * np.abs(exp).max()
         # the rows of the points 0 and inf are the kernel's own first and last rows, exactly
         assert np.array_equal(u[0:3], w[:, 0].transpose(1, 0, 2)) and np.array_equal(u[15:18], w[:, 2].transpose(1, 0, 2))
-        assert L.msocr_winograd_coltail_weights_host(None, Cout, Cin, u.ctypes.data) == -1
-        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, Cin, None) == -1
-        assert L.msocr_winograd_coltail_weights_host(None, Cout, Cin, None) == -1
-        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, 0, Cin, u.ctypes.data) == -1
-        assert L.msocr_winograd_coltail_weights_host(w.ctypes.data, Cout, 0, u.ctypes.data) == -1
+        assert L.msocr_winograd_weights_host(CT, None, Cout, Cin, u.ctypes.data) == -1
+        assert L.msocr_winograd_weights_host(CT, w.ctypes.data, Cout, Cin, None) == -1
+        assert L.msocr_winograd_weights_host(CT, None, Cout, Cin, None) == -1
+        assert L.msocr_winograd_weights_host(CT, w.ctypes.data, 0, Cin, u.ctypes.data) == -1
+        assert L.msocr_winograd_weights_host(CT, w.ctypes.data, Cout, 0, u.ctypes.data) == -1
 
 
 def test_coltail_workspace_bytes_and_shapes_without_the_form():
@@ -52,15 +64,16 @@ def test_coltail_workspace_bytes_and_shapes_without_the_form():
     entry points refuse those shapes before anything is launched."""
     from manuscript_ocr_amd import _native as nat
     L = nat.lib()
+    CT = nat.WINO_4X4_COLTAIL
     for N, H, W, Cin, Cout in ((3, 4, 13, 512, 512), (2, 8, 25, 256, 256), (2, 9, 5, 128, 128), (129, 4, 5, 128, 64), (1, 17, 9, 128, 192),
                                (960, 4, 13, 512, 512)):
         TH = -(-H // 4)
         exp = (36 * N * TH * (W // 4) + 18 * N * TH) * (Cin + Cout) * 4
-        got = L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(_desc(nat, N, H, W, Cin, Cout)))
+        got = L.msocr_winograd_workspace_bytes(ctypes.byref(_desc(nat, N, H, W, Cin, Cout)), CT)
         assert got == exp, (N, H, W, Cin, Cout)
-        assert got == N * L.msocr_winograd_coltail_workspace_bytes(ctypes.byref(_desc(nat, 1, H, W, Cin, Cout)))
+        assert got == N * L.msocr_winograd_workspace_bytes(ctypes.byref(_desc(nat, 1, H, W, Cin, Cout)), CT)
         assert got < L.msocr_winograd_workspace_bytes(ctypes.byref(_desc(nat, N, H, W, Cin, Cout)), nat.WINO_4X4)
-    assert L.msocr_winograd_coltail_workspace_bytes(None) == -1
+    assert L.msocr_winograd_workspace_bytes(None, CT) == -1
     bad = [_desc(nat, 2, 8, 12, 128, 128), _desc(nat, 2, 8, 14, 128, 128), _desc(nat, 2, 8, 15, 128, 128),   # W % 4 != 1
            _desc(nat, 2, 8, 1, 128, 128),                                                                   # no square tile
            _desc(nat, 2, 8, 13, 144, 128), _desc(nat, 2, 8, 13, 128, 96),                                   # the split GEMMs: Cin % 32, Cout % 64
@@ -70,21 +83,22 @@ def test_coltail_workspace_bytes_and_shapes_without_the_form():
     fake = ctypes.c_void_p(1 << 20)  # never dereferenced: every call below fails its argument checks first
     for d in bad + [bf16]:
         r = ctypes.byref(d)
-        assert L.msocr_winograd_coltail_workspace_bytes(r) == -1
-        assert L.msocr_winograd_coltail_input_transform(r, fake, fake, None) == -1
-        assert L.msocr_winograd_coltail_gemm(r, fake, fake, fake, None) == -1
-        assert L.msocr_winograd_coltail_output_transform(r, fake, None, None, fake, None) == -1
-        assert L.msocr_conv3x3_winograd_coltail(r, fake, fake, fake, None, None, fake, fake, None) == -1
+        assert L.msocr_winograd_workspace_bytes(r, CT) == -1
+        assert L.msocr_winograd_input_transform(r, CT, fake, fake, None) == -1
+        assert L.msocr_winograd_gemm(r, CT, 1, fake, fake, None) == -1
+        assert L.msocr_winograd_output_transform(r, CT, fake, None, None, fake, None) == -1
+        assert L.msocr_conv3x3_winograd(r, CT, 1, fake, fake, None, None, fake, fake, None) == -1
     ok = ctypes.byref(_desc(nat, 2, 8, 13, 128, 128))
-    assert L.msocr_winograd_coltail_input_transform(ok, None, fake, None) == -1
-    assert L.msocr_winograd_coltail_input_transform(ok, fake, None, None) == -1
-    assert L.msocr_winograd_coltail_gemm(ok, None, fake, fake, None) == -1
-    assert L.msocr_winograd_coltail_gemm(ok, fake, None, fake, None) == -1
-    assert L.msocr_winograd_coltail_gemm(ok, fake, fake, None, None) == -1
-    assert L.msocr_winograd_coltail_output_transform(ok, None, None, None, fake, None) == -1
-    assert L.msocr_winograd_coltail_output_transform(ok, fake, None, None, None, None) == -1
-    assert L.msocr_conv3x3_winograd_coltail(ok, fake, None, fake, None, None, fake, fake, None) == -1
-    assert L.msocr_conv3x3_winograd_coltail(ok, fake, fake, None, None, None, fake, fake, None) == -1
+    assert L.msocr_winograd_input_transform(ok, CT, None, fake, None) == -1
+    assert L.msocr_winograd_input_transform(ok, CT, fake, None, None) == -1
+    assert L.msocr_winograd_gemm(ok, CT, 1, None, fake, None) == -1      # a null u: one buffer now, the tail column's planes inside it
+    assert L.msocr_winograd_gemm(ok, CT, 1, fake, None, None) == -1
+    assert L.msocr_winograd_output_transform(ok, CT, None, None, None, fake, None) == -1
+    assert L.msocr_winograd_output_transform(ok, CT, fake, None, None, None, None) == -1
+    assert L.msocr_conv3x3_winograd(ok, CT, 1, fake, None, None, None, fake, fake, None) == -1
+    # split operands only: the form has no exact-f32 GEMM
+    assert L.msocr_winograd_gemm(ok, CT, 0, fake, fake, None) == -1
+    assert L.msocr_conv3x3_winograd(ok, CT, 0, fake, fake, None, None, fake, fake, None) == -1
 
 
 def test_square_pays_prices_the_tail_column(monkeypatch):

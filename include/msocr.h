@@ -363,6 +363,37 @@ int msocr_attn_beam_nbest_host(const void* workspace_host, int B, int V, int ste
                                const int32_t* trun_host, int32_t* ids_out_host, float* prob_out_host, float* conf_out_host,
                                float* logp_out_host);
 
+/* Forced (teacher-forced) decode: score and align a GIVEN transcription.  Attention.forward(is_train=True) of the reference
+ * (model.py:287-320) with sampling_prob 0 in eval(): step s is fed tok_in[b][s] (i32 [B][steps]: column 0 = sos_id, then the
+ * transcription's ids, the layout of the reference's pack_attention_targets, data/transforms.py:123-157) instead of the arg-max of
+ * step s-1, and the logits of every step are returned with the attention weights: logits_out [B][steps][V] f32 (blank_id masked to
+ * -1e4 as in the greedy decode; -1 = no blank), alpha_out [B][steps][T] f32 (required).  Every step of every row is written; no ids
+ * are. A row fed the ids of msocr_attn_greedy(_hoisted)_alpha reproduces that decode's logits and weights bit for bit.  An id outside
+ * [0, V) is replaced by sos_id inside the kernel before it is used as an index (callers who want an error check their ids first:
+ * msocr_seq_logp reports such an id as NaN).
+ *   msocr_attn_forced         every shape of the envelope (H 64..512 in steps of 64, V <= 512, T <= 64, steps <= 64), general kernel
+ *   msocr_attn_forced_hoisted H == 256, V <= 256, T <= 48 on the matrix cores, 32 rows per workgroup; ctx_gates and ws (required) as
+ *                             for msocr_attn_greedy_hoisted; other shapes: MSOCR_E_ARG
+ * Null pointers and shapes outside the envelope return MSOCR_E_ARG before any launch. */
+int msocr_attn_forced(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
+                      const int32_t* tok_in, int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream);
+int msocr_attn_forced_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                              const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, const int32_t* tok_in,
+                              int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream);
+
+/* Log-probability of given ids under a decode's logits: logp_steps_out [B][steps] f32 = log_softmax(logits[b][t] / temperature)[ids[b][t]]
+ * in f32 with max subtraction (a true f32 division, skipped when temperature == 1) for t < trun[b] and 0 behind; logp_out [B] f32 =
+ * their sum over t < trun[b], accumulated in f64 in step order and rounded once (the convention of msocr_attn_beam_nbest's logp_out).
+ * With ids = the targets of a forced decode (the transcription's ids, then EOS) and trun = length + 1 this is the summed
+ * log-probability of the transcription including its EOS.  An id outside [0, V) at a step t < trun[b] makes that step's value and
+ * the row's sum NaN; nothing is read through it.  trun is clamped into [0, steps].  V <= 512, steps <= 64, otherwise MSOCR_E_ARG.
+ * The _host twin takes host arrays: the same lane partials, the same order of every sum; it differs from the device by what
+ * expf / logf differ between the device and the host's libm. */
+int msocr_seq_logp(const float* logits, const int32_t* ids, const int32_t* trun_dev, int B, int V, int steps, float temperature,
+                   float* logp_steps_out, float* logp_out, void* stream);
+int msocr_seq_logp_host(const float* logits_host, const int32_t* ids_host, const int32_t* trun_host, int B, int V, int steps,
+                        float temperature, float* logp_steps_out_host, float* logp_out_host);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

@@ -99,6 +99,12 @@ _SIGS = {
     "msocr_seq_char_details": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_nbest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_nbest_host": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_attn_forced": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
+                                  c_vp, c_vp, c_vp]),
+    "msocr_attn_forced_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
+                                          c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "msocr_seq_logp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "msocr_seq_logp_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -29,6 +29,9 @@ read out of the workspace the decode leaves behind: the decode itself, and with 
 Works on the native batch path with every other switch, and on the generic route when the recogniser is this package's TRBA; a
 foreign recogniser is not asked for alternatives.
 
+`pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
+(an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
+
 `process_batch` is broken upstream (it calls a non-existent `self.process`, _pipeline.py:187);
 here it is the per-image `predict`.  `predict_batch` is the MI355X fast path: when detector and
 recogniser are this package's EAST/TRBA it runs the detector once for all pages and the
@@ -668,6 +671,68 @@ class Pipeline:
             for first, count, x0, y0, x1, y1 in np.asarray(recs).tolist():
                 lines.append(TextLine(words=block.words[first:first + count], bbox=(x0, y0, x1, y1)))
         page.blocks = lines
+
+    def score_page(self, image: Union[str, np.ndarray, Image.Image], page, strict: bool = True):
+        """Forced decode of a transcribed page (this package's extension; needs this package's TRBA): `page` is a Page whose words
+        carry a `text`.  -> (a deep copy of the page, logps).  Every word that has a text (not None) and whose box passes
+        min_text_size and has a window on the page comes back as a CharWord: recognition_confidence = the confidence of the GIVEN
+        text under the recogniser (TRBA.score's "confidence"), chars = its symbols with their probabilities and x positions in page
+        pixels, text = the text as packed (the word's own under strict=True).  Every other word is left as it was.  logps: one entry
+        per word in the page's word order (blocks in order, words in order), the summed log-probability of the text and its EOS,
+        None for a word that was not scored.  The caller's word order is kept: nothing is reordered and the detector is not run.
+        Crops are cut on the device from the words' boxes, along their quadrilaterals with `rectify_crops`, exactly as the
+        recognising routes cut them.  strict as for TRBA.score: a character outside the charset or a text longer than max_len
+        raises ValueError (False: dropped / truncated).  The positions are attention centroids: estimates, meaningful for trained
+        weights only."""
+        import copy
+        rec = self.recognizer
+        if not isinstance(rec, TRBA):
+            raise TypeError("score_page needs this package's TRBA as the recogniser")
+        from .recognizers._trba.transforms import pack_targets
+        page = copy.deepcopy(page)
+        all_words = [w for block in page.blocks for w in block.words]
+        logps: List[Optional[float]] = [None] * len(all_words)
+        arr = np.ascontiguousarray(read_image(image))
+        if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8:
+            raise ValueError(f"score_page needs an RGB uint8 image, got shape {arr.shape} {arr.dtype}")
+        H, W = arr.shape[:2]
+        cand, boxes = [], []
+        for k, word in enumerate(all_words):
+            if word.text is None:
+                continue
+            (x0, y0, x1, y1), _poly = _word_aabb(word)
+            if (x1 - x0) >= self.min_text_size and (y1 - y0) >= self.min_text_size:
+                cand.append(k)
+                boxes.append((x0, y0, x1, y1))
+        if not cand:
+            return page, logps
+        desc, keep = ops.crop_descriptors(boxes, [0] * len(boxes), (H, W), rec.img_h, rec.img_w)
+        rows = [k for k, kp in zip(cand, keep) if kp]  # a word without a window on the page is left as it was
+        if not rows:
+            return page, logps
+        words = [all_words[k] for k in rows]
+        try:
+            tok_in, target, trun, packed = pack_targets([w.text for w in words], rec.stoi, rec.max_length, strict=strict)
+        except ValueError as e:
+            raise ValueError(f"score_page, scored words in page order: {e}") from None
+        pages_dev = torch.from_numpy(arr[None]).to(rec.device)
+        qdesc = None
+        if self.rectify_crops:
+            qdesc = ops.quad_descriptors([w.polygon for w in words], desc, rec.img_h, rec.img_w)
+            canv = ops.quad_crop(pages_dev, qdesc, rec.img_h, rec.img_w)
+        else:
+            canv = ops.crop_resize_pad(pages_dev, desc, rec.img_h, rec.img_w)
+        logp, conf, _lps, prob, centre, _peak = rec.score_canvases(canv, np.arange(len(rows)), tok_in, target, trun)
+        if qdesc is not None:
+            chars = rec.chars(target, trun, prob, centre, qdesc[:, 9], None, None, qdesc=qdesc)
+        else:
+            chars = rec.chars(target, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3])
+        for k, word, text, c, lp in zip(rows, words, packed, conf.tolist(), logp.tolist()):
+            word.text = text
+            word.recognition_confidence = c
+            logps[k] = lp
+        self._attach_details(words, [page], chars)
+        return page, logps
 
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):

@@ -41,6 +41,8 @@ using namespace split_rows32;
 // run-time branch and further instantiations IN THIS UNIT changed the spills of the plain kernels (scratch of the beam kernels
 // 212 -> 276 / 332 B and 68 -> 132 / 216 B; profiles/attn_alpha.txt).  A unit of its own leaves their code object as it was.
 // Observed with one compiler (ROCm 7's hipcc): when the toolchain moves, try the template split again (tools/check_isa.sh).
+// A third compilation, through attn_forced_mfma.hip (MSOCR_ATTN_FORCED with MSOCR_ATTN_ALPHA), holds only the forced-decode kernel and
+// its launcher, for the same reason: neither the beam nor the greedy kernel is compiled there, nor the pack helpers.
 #ifdef MSOCR_ATTN_ALPHA
 constexpr bool ALPHA = true;
 #define ATTN_ENTRY(name) name##_alpha
@@ -464,6 +466,7 @@ __device__ __forceinline__ f32x16 phase_generator(const AttnArgs& a, const Lane&
   return acc;
 }
 
+#ifndef MSOCR_ATTN_FORCED
 // Beam decode: 4 crops x 8 beam slots per workgroup.  SPLITW: the operand form.  Nonlinearities at hardware rate; the context sum
 // staggered against the recurrent product in the split form (phase_gates_cell).
 template <bool SPLITW>
@@ -769,12 +772,73 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
   }
 }
 
+#else  // MSOCR_ATTN_FORCED
+// Forced (teacher-forced) decode, Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0: the greedy
+// kernel's step loop over 32 independent rows per workgroup, fed the GIVEN token of every step (a.tok_in [B][steps], column 0 = SOS)
+// instead of the arg-max of the step before.  Phases (a)-(f) are the greedy kernel's own instantiations (one state row per crop,
+// libm-grade nonlinearities, split form), so a row fed greedy's ids reproduces greedy's logits and attention weights bit for bit;
+// phase (g) is gone, and with it the copy of the logits to LDS and the barrier that ordered it: (f) of step s and (a) of step s + 1
+// both only read the h rows.  Writes logits_out [B][steps][V] and alpha_out [B][steps][T]; no ids.  Rows past B take sos_id (computed,
+// never stored); an id outside [0, V) is replaced by sos_id before it is used as the row index into wih_tok.
+__global__ __launch_bounds__(NT, 1) void attn_forced_mfma_kernel(AttnArgs a) {
+  typedef HRows<true> HS;
+  __shared__ int s_tok[R];
+  const Lane l(threadIdx.x);
+  const int tid = l.tid, half = l.half, ju = l.ju;
+  const int V = a.V;
+  const int b0 = blockIdx.x * R;
+  HS::zero(tid);  // h = 0
+  f32x16 c;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) c[e] = 0.f;
+  __syncthreads();
+
+  for (int s = 0; s < a.steps; ++s) {
+    // the step's input tokens; read by phase (e), three barriers on.  The last reader of the old ones, (e) of step s - 1, is a barrier back.
+    if (tid < R) {
+      int tk = b0 + tid < a.B ? a.tok_in[(long)(b0 + tid) * a.steps + s] : a.sos_id;
+      if (tk < 0 || tk >= V) tk = a.sos_id;
+      s_tok[tid] = tk;
+    }
+    phase_h2h<HS>(a, l);
+    __syncthreads();
+    phase_scores<1, LibmMath, HS>(a, l, b0);
+    __syncthreads();
+    phase_softmax_t<1, HS>(a, l, b0, s);
+    __syncthreads();
+    phase_gates_cell<1, LibmMath, false, HS>(a, l, b0, s_tok, c);
+    __syncthreads();
+    // ---- (f) logits; trace store
+    const f32x16 acc = phase_generator<HS>(a, l);
+    if (ju < V) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int r = acc_row(e, half);
+        const float v = (ju == a.blank_id) ? -1e4f : acc[e];
+        if (b0 + r < a.B) a.logits_out[((long)(b0 + r) * a.steps + s) * V + ju] = v;
+      }
+    }
+  }
+}
+#endif  // MSOCR_ATTN_FORCED
+
 // dynamic LDS of a decode kernel: the h rows in their form, sbuf, salpha
 template <bool SPLITW>
 constexpr size_t lds_bytes() { return (size_t)(HRows<SPLITW>::FLOATS + R * H + R * 64) * sizeof(float); }
 
 }  // namespace
 
+#ifdef MSOCR_ATTN_FORCED
+// the one kernel of attn_forced_mfma.hip
+int msocr_internal_attn_forced_mfma(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p || !a.alpha_out || !a.tok_in || !a.logits_out) return MSOCR_E_ARG;
+  if (a.sos_id < 0 || a.sos_id >= a.V) return MSOCR_E_ARG;
+  const size_t ldsz_split = lds_bytes<true>();
+  if (msocr_internal_lds_limit((const void*)attn_forced_mfma_kernel, (int)ldsz_split) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  MSOCR_LAUNCH(attn_forced_mfma_kernel, dim3((a.B + R - 1) / R), dim3(NT), ldsz_split, s, a);
+  return LAUNCH_OK();
+}
+#else
 // the kernels of this unit: with the attention-weight output in attn_beam_mfma_alpha.hip's copy (the _alpha names), without it here
 int ATTN_ENTRY(msocr_internal_attn_beam_mfma)(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates || ALPHA != (a.alpha_out != nullptr)) return MSOCR_E_ARG;
@@ -797,6 +861,8 @@ int ATTN_ENTRY(msocr_internal_attn_greedy_mfma)(const AttnArgs& a, hipStream_t s
   MSOCR_LAUNCH(attn_greedy_mfma_kernel, dim3((a.B + R - 1) / R), dim3(NT), ldsz_split, s, a);
   return LAUNCH_OK();
 }
+
+#endif  // MSOCR_ATTN_FORCED
 
 #ifndef MSOCR_ATTN_ALPHA
 // HOST helper: a transposed f32 weight matrix of the decoder ([256][N] row-major: h2h_wt, gen_wt; or gate-interleaved

@@ -18,6 +18,20 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// The forced decode is a compile-time fact of the translation unit, like the attention-weight output of attn_beam_mfma.hip: this file
+// is compiled twice, as itself (FORCED false: the greedy and beam kernels behind msocr_internal_attn_general) and through
+// attn_general_forced.hip, which defines MSOCR_ATTN_FORCED and includes it (FORCED true: the greedy instantiation alone, behind
+// msocr_internal_attn_general_forced).  A second kernel in THIS unit, through a shared body, moved the beam kernel from 77 to 78
+// VGPRs (profiles/attn_forced.txt); a unit of its own leaves both kernels' code as it was.
+// FORCED = Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0: the token fed to step s is
+// a.tok_in[b][s] instead of the arg-max of step s - 1 (an id outside [0, V) is replaced by sos_id before it indexes wih_tok); logits
+// and weights are stored as in greedy, the arg-max and the ids are not computed.
+#ifdef MSOCR_ATTN_FORCED
+constexpr bool FORCED = true;
+#else
+constexpr bool FORCED = false;
+#endif
+
 namespace {
 
 constexpr int NTH = 256;
@@ -75,6 +89,13 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
   int fin = a.steps;
   const float temp = fmaxf(a.temperature, 1e-6f);
   for (int s = 0; s < a.steps; ++s) {
+    if constexpr (FORCED) {  // read by (e), four barriers on; the last reader of the old one, (e) of step s - 1, is barriers back
+      if (tid == 0) {
+        int tk = a.tok_in[(long)b * a.steps + s];
+        if (tk < 0 || tk >= V) tk = a.sos_id;
+        s_tok[0] = tk;
+      }
+    }
     // (a) ph[r][j] = h2h_b[j] + sum_k h[r][k] * h2h_wt[k][j]
     for (int i = tid; i < K * H; i += NTH) {
       const int r = i / H, j = i - r * H;
@@ -152,7 +173,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
       slog[i] = (v == a.blank_id) ? -1e4f : acc;
     }
     __syncthreads();
-    if constexpr (!BEAM) {
+    if constexpr (FORCED) {
+      for (int v = tid; v < V; v += NTH) a.logits_out[((long)b * a.steps + s) * V + v] = slog[v];  // rewritten by (f), barriers on
+    } else if constexpr (!BEAM) {
       float bv = -INFINITY;
       int bi = 0x7fffffff;
       for (int v = tid; v < V; v += NTH) {
@@ -261,6 +284,18 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 
 }  // namespace
 
+#ifdef MSOCR_ATTN_FORCED
+// the one kernel of attn_general_forced.hip: the greedy loop along a.tok_in.  Same shapes as below with one row per crop.
+int msocr_internal_attn_general_forced(const AttnArgs& a, int H, hipStream_t s) {
+  if (!a.tok_in || !a.alpha_out || !a.logits_out || a.sos_id < 0 || a.sos_id >= a.V) return MSOCR_E_ARG;
+  if (H < 64 || H > 512 || H % 64 || a.V <= 0 || a.V > 512 || a.T <= 0 || a.T > 64 || a.steps <= 0 || a.steps > 64 || a.B <= 0) return MSOCR_E_ARG;
+  const size_t ldsz = (size_t)(4 * H + a.V + 64) * sizeof(float);
+  auto kg = attn_general_kernel<false>;
+  if (msocr_internal_lds_limit((const void*)kg, 112 * 1024) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  MSOCR_LAUNCH(kg, dim3(a.B), dim3(NTH), ldsz, s, a, H);
+  return LAUNCH_OK();
+}
+#else
 // Shapes taken: H % 64 == 0, 64 <= H <= 512, V <= 512, T <= 64, steps <= 64, beam <= 16, beam * H <= 4096 (the state of the beam
 // rows must fit in LDS).  beam = 0 selects the greedy loop.
 int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t s) {
@@ -280,3 +315,4 @@ int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t
     MSOCR_LAUNCH(kg, dim3(a.B), dim3(NTH), ldsz, s, a, H);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
+#endif  // MSOCR_ATTN_FORCED

@@ -80,6 +80,8 @@ struct AttnArgs {
   int32_t* chunk_state;       // [2*nchunks] zeroed by the caller: {crops finished, max finish step}; enables the early exit
   float* alpha_out;     // optional attention weights of every step (nullptr = off): greedy [B][steps][T]; beam [B][steps][K][T], slot-
                         // indexed like the logits trace (the weights of step s at slot rb belong to the hypothesis whose logits are there)
+  const int32_t* tok_in;  // forced decode: [B][steps] the token fed to step s of every row (nullptr everywhere else); the forced kernels
+                          // replace an id outside [0, V) by sos_id before it indexes wih_tok, and write no ids
 };
 // attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the matrix cores (H == 256, V <= 256, T <= 48, beam <= 8;
 // needs ctx_gates): split-operand products with the split weights, exact-f32 MFMA without them
@@ -90,7 +92,13 @@ __attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma(const 
 // require it to be nullptr)
 __attribute__((visibility("hidden"))) int msocr_internal_attn_beam_mfma_alpha(const AttnArgs& a, hipStream_t s);
 __attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma_alpha(const AttnArgs& a, hipStream_t s);
+// attn_forced_mfma.hip: forced decode (the greedy step loop along a.tok_in instead of its own arg-max) with 32 rows per workgroup on
+// the matrix cores; same shapes and weights as the greedy kernel, a.alpha_out and a.tok_in required
+__attribute__((visibility("hidden"))) int msocr_internal_attn_forced_mfma(const AttnArgs& a, hipStream_t s);
 // attn_general.hip: greedy / beam decode for every shape of the envelope (see its header), H == 256 included; the plain entry points
 // msocr_attn_greedy / msocr_attn_beam run it.  Same outputs and workspace layout as the matrix-core kernels; a.alpha_out optional.
 __attribute__((visibility("hidden"))) int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t s);
+// attn_general_forced.hip: the forced decode for the same shapes (one row per crop): a.tok_in and a.alpha_out required; logits and
+// weights as the greedy loop stores them, no ids
+__attribute__((visibility("hidden"))) int msocr_internal_attn_general_forced(const AttnArgs& a, int H, hipStream_t s);
 #endif

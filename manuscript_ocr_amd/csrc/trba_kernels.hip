@@ -5,14 +5,17 @@
 // lane j reads column j), LDS-resident per-row state and wave-level reductions; no MFMA.
 // The sequential loop (T encoder steps) lives INSIDE one launch: rows are independent, so
 // one workgroup owns a few rows for the whole loop and no inter-workgroup hand-off exists.
-// The decode kernels themselves are in attn_beam_mfma.hip (and its second compilation attn_beam_mfma_alpha.hip) and attn_general.hip.
+// The decode kernels themselves are in attn_beam_mfma.hip (and its further compilations attn_beam_mfma_alpha.hip and attn_forced_mfma.hip)
+// and attn_general.hip (and attn_general_forced.hip).
 //
 //   msocr_se_residual       <- recognizers/_trba/model/seresnet31.py:5-20, 61-66
 //   msocr_mean_over_h       <- recognizers/_trba/model/model.py:388-390
 //   msocr_bilstm_recurrent  <- model.py:9-21 (nn.LSTM, gate order i,f,g,o)
 //   msocr_attn_greedy(_hoisted)       <- model.py:34-46 + 227-259
 //   msocr_attn_beam(_hoisted, _finalize) <- model.py:34-46 + 92-225
+//   msocr_attn_forced(_hoisted)       <- model.py:34-46 + 287-320 (the teacher-forced pass, as an inference call)
 //   msocr_seq_confidence    <- recognizers/_trba/__init__.py:413-431
+//   msocr_seq_logp          summed log-probability of given ids (no counterpart: the reference has the training loss only)
 //   msocr_seq_char_details  per-symbol probability and attention position (no counterpart: the reference drops both)
 // The _alpha entry points are the same decodes with the attention weights of every step kept (model.py:40-46 returns them, its
 // callers drop them); the plain ones are those with the output off.
@@ -383,6 +386,41 @@ extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj
                                          nullptr, stream);
 }
 
+// Forced (teacher-forced) decode, Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0 in eval():
+// the decoder is run along the GIVEN tokens tok_in [B][steps] i32 (column 0 = SOS, then the transcription's ids: transforms.pack_targets)
+// instead of its own arg-max, and the logits it gives every step are returned with the attention weights.  The kernels replace an id
+// outside [0, V) by sos_id before they use it as an index; they write no ids.  msocr_attn_forced: every shape of the envelope on the
+// general kernel (attn_general_forced.hip); msocr_attn_forced_hoisted: the matrix-core kernel (attn_forced_mfma.hip), the greedy kernel's
+// shapes, ctx_gates and split weights.  A row fed the ids of msocr_attn_greedy(_hoisted)_alpha reproduces its logits and weights bit
+// for bit.
+extern "C" int msocr_attn_forced(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
+                                 const int32_t* tok_in, int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream) {
+  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !tok_in || !logits_out || !alpha_out) return MSOCR_E_ARG;
+  if (sos_id < 0 || sos_id >= V) return MSOCR_E_ARG;
+  AttnArgs a{};
+  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w;
+  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
+  a.sos_id = sos_id; a.eos_id = -1; a.blank_id = blank_id; a.temperature = 1.0f;
+  a.logits_out = logits_out; a.alpha_out = alpha_out; a.tok_in = tok_in;
+  return msocr_internal_attn_general_forced(a, H, (hipStream_t)stream);
+}
+extern "C" int msocr_attn_forced_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                         const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, const int32_t* tok_in,
+                                         int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream) {
+  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !tok_in || !logits_out || !alpha_out) return MSOCR_E_ARG;
+  if (sos_id < 0 || sos_id >= V || !attn_mfma_shape(T, H, V)) return MSOCR_E_ARG;
+  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
+  if (!ws || !ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15))
+    return MSOCR_E_ARG;
+  AttnArgs a{};
+  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
+  a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p;
+  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
+  a.sos_id = sos_id; a.eos_id = -1; a.blank_id = blank_id; a.temperature = 1.0f;
+  a.logits_out = logits_out; a.alpha_out = alpha_out; a.tok_in = tok_in;
+  return msocr_internal_attn_forced_mfma(a, (hipStream_t)stream);
+}
+
 // workspace: logits [B][steps][K][V] f32 | back [B][steps][K] i32 | tokv [B][steps][K] i32 | best_at [B][steps] i32
 static inline int64_t beam_ws_logits(int B, int steps, int K, int V) { return (int64_t)B * steps * K * V * 4; }
 extern "C" int64_t msocr_attn_beam_workspace_bytes(int B, int steps, int beam, int V) {
@@ -715,5 +753,104 @@ extern "C" int msocr_attn_beam_nbest_host(const void* workspace_host, int B, int
       }
       nbest_sums(p, lp, tok, tr, eos_id, conf_out_host + q, logp_out_host + q);
     }
+  return MSOCR_OK;
+}
+
+// --------------------------------------------------------------------------------------------- log-probability of given ids
+// How well a given token sequence fits the logits of a (forced) decode: per step log_softmax(logits / temperature)[id] in f32 with
+// max subtraction (the division is a true f32 division and is skipped at temperature 1, as in the beam kernels), and per row the sum
+// over t < t_run, accumulated in f64 in step order and rounded once (msocr_attn_beam_nbest's convention for logp_out).  Steps
+// t >= t_run hold 0.  An id outside [0, V) at a step t < t_run makes that step and the row's sum NaN; nothing is read through it.
+// The kernel and its host twin share the three pieces below; they differ in how the 64 lane partials are combined (cross-lane
+// exchange on the device, the same xor butterfly over an array on the host) and in what expf / logf differ between the two.
+
+struct SeqScale {  // logits / temperature as the beam kernels apply it
+  float temp;
+  bool div;
+  __host__ __device__ explicit SeqScale(float temperature) : temp(temperature > 1e-6f ? temperature : 1e-6f), div(temperature != 1.0f) {}
+  __host__ __device__ __forceinline__ float operator()(float x) const { return div ? x / temp : x; }
+};
+// lane `lane` of 64: its part of the maximum, and of the sum of exponentials under the maximum m
+__host__ __device__ __forceinline__ float seq_lane_max(const float* x, int V, int lane, const SeqScale& sc) {
+  float m = -INFINITY;
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, sc(x[v]));
+  return m;
+}
+__host__ __device__ __forceinline__ float seq_lane_sum(const float* x, int V, int lane, float m, const SeqScale& sc) {
+  float s = 0.f;
+  for (int v = lane; v < V; v += 64) s += expf(sc(x[v]) - m);
+  return s;
+}
+// the step's value from the maximum and the sum
+__host__ __device__ __forceinline__ float seq_step_logp(const float* x, int V, int id, float m, float sum, const SeqScale& sc) {
+  return id >= 0 && id < V ? (sc(x[id]) - m) - logf(sum) : __builtin_nanf("");
+}
+// a row: zeros behind t_run, the f64 sum in step order of what is before it
+__host__ __device__ inline void seq_row_sum(float* lp_steps, int steps, int tr, float* logp) {
+  double sum = 0.0;
+  for (int t = 0; t < steps; ++t) {
+    if (t < tr) sum += (double)lp_steps[t];
+    else lp_steps[t] = 0.f;
+  }
+  *logp = (float)sum;
+}
+
+constexpr int LP_WAVES = 4;
+// one workgroup per row, one wave per (row, step): the waves take the steps round-robin, thread 0 does the ordered sum
+__global__ __launch_bounds__(64 * LP_WAVES) void seq_logp_kernel(const float* __restrict__ logits, const int32_t* __restrict__ ids,
+                                                                  const int32_t* __restrict__ trun, int V, int steps, float temperature,
+                                                                  float* __restrict__ logp_steps, float* __restrict__ logp) {
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tr = clampi(trun[b], 0, steps);
+  const SeqScale sc(temperature);
+  __shared__ float s_lp[64];
+  for (int t = wave; t < tr; t += LP_WAVES) {
+    const float* x = logits + ((long)b * steps + t) * V;
+    float m = seq_lane_max(x, V, lane, sc);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    const float sum = wave_sum(seq_lane_sum(x, V, lane, m, sc));
+    if (lane == 0) s_lp[t] = seq_step_logp(x, V, ids[(long)b * steps + t], m, sum, sc);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) seq_row_sum(s_lp, steps, tr, logp + b);
+  __syncthreads();
+  if (threadIdx.x < steps) logp_steps[(long)b * steps + threadIdx.x] = s_lp[threadIdx.x];
+}
+
+static bool seq_logp_args_ok(const float* logits, const int32_t* ids, const int32_t* trun, int B, int V, int steps, const float* lps,
+                             const float* lp) {
+  return logits && ids && trun && lps && lp && B > 0 && V > 0 && V <= 512 && steps > 0 && steps <= 64;
+}
+
+extern "C" int msocr_seq_logp(const float* logits, const int32_t* ids, const int32_t* trun_dev, int B, int V, int steps, float temperature,
+                              float* logp_steps_out, float* logp_out, void* stream) {
+  if (!seq_logp_args_ok(logits, ids, trun_dev, B, V, steps, logp_steps_out, logp_out)) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(seq_logp_kernel, dim3(B), dim3(64 * LP_WAVES), 0, (hipStream_t)stream, logits, ids, trun_dev, V, steps, temperature,
+               logp_steps_out, logp_out);
+  return LAUNCH_OK();
+}
+
+// msocr_seq_logp over host arrays
+extern "C" int msocr_seq_logp_host(const float* logits_host, const int32_t* ids_host, const int32_t* trun_host, int B, int V, int steps,
+                                   float temperature, float* logp_steps_out_host, float* logp_out_host) {
+  if (!seq_logp_args_ok(logits_host, ids_host, trun_host, B, V, steps, logp_steps_out_host, logp_out_host)) return MSOCR_E_ARG;
+  const SeqScale sc(temperature);
+  for (int b = 0; b < B; ++b) {
+    const int tr = clampi(trun_host[b], 0, steps);
+    float* const out = logp_steps_out_host + (long)b * steps;
+    for (int t = 0; t < tr; ++t) {
+      const float* x = logits_host + ((long)b * steps + t) * V;
+      float m = -INFINITY, part[64], next[64];
+      for (int l = 0; l < 64; ++l) m = fmaxf(m, seq_lane_max(x, V, l, sc));
+      for (int l = 0; l < 64; ++l) part[l] = seq_lane_sum(x, V, l, m, sc);
+      for (int o = 32; o > 0; o >>= 1) {
+        for (int l = 0; l < 64; ++l) next[l] = part[l] + part[l ^ o];
+        for (int l = 0; l < 64; ++l) part[l] = next[l];
+      }
+      out[t] = seq_step_logp(x, V, ids_host[(long)b * steps + t], m, part[0], sc);
+    }
+    seq_row_sum(out, steps, tr, logp_out_host + b);
+  }
   return MSOCR_OK;
 }

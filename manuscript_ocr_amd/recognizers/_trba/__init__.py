@@ -9,7 +9,8 @@ Extensions (keyword-only): precision="fp32"|"bf16" for the CNN (recurrent/attent
 always exact f32), state_dict=... / config=... for in-memory weights (nothing can be downloaded
 offline), device_batch=2048 rows per launch sequence, predict(..., return_chars=True) for per-symbol
 confidence and position (from the decoder's attention weights), predict(..., n_best=n) for the beam search's n
-best final readings with their scores.  Confidences reproduce the reference's
+best final readings with their scores, score(images, texts) for the forced decode of given transcriptions: how
+well a text fits a word image and where its symbols sit.  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -26,7 +27,7 @@ from ... import _native as nat
 from ... import ops
 from ..._graphpool import GraphPool, Lease
 from .net import TrbaNet
-from .transforms import decode_tokens, frame_to_pixel, frame_to_quad_x, load_charset, resize_and_pad, resized_size
+from .transforms import decode_tokens, frame_to_pixel, frame_to_quad_x, load_charset, pack_targets, resize_and_pad, resized_size
 
 
 class _Launch(NamedTuple):
@@ -476,6 +477,105 @@ class TRBA:
         itos, skip = self.itos, {self.pad_id, self.blank_id}
         return [[{"char": itos[t], "confidence": p, "x": x} for t, p, x in zip(row[:e], pr, xr) if t not in skip]
                 for row, e, pr, xr in zip(ids.tolist(), end.tolist(), ps, xs)]
+
+    # ------------------------------------------------------------------------------------- forced decode
+    def score_canvases(self, canvases_dev: torch.Tensor, row_image, tok_in, target, trun, temperature=1.0):
+        """The forced decode of R candidate rows over N encoded canvases: canvases [N,img_h,img_w,3] u8 on the device, row_image [R]
+        the canvas each row reads, tok_in / target [R, max_length+1] int32 and trun [R] int32 from transforms.pack_targets (host
+        arrays).  The encoder runs once per canvas; a row gathers its canvas's encoder outputs, so candidates of one image share
+        them.  Not captured into a hipGraph.  -> host arrays (logp [R] f32, conf [R] f32, logp_steps [R, steps] f32, prob [R, steps]
+        f32, centre [R, steps] f32, peak [R, steps] i32): the summed log-probability of target over t < trun (msocr_seq_logp, at
+        `temperature`), the confidence as predict computes it (msocr_seq_confidence) and msocr_seq_char_details' per-step arrays."""
+        N, R = int(canvases_dev.shape[0]), len(row_image)
+        steps = self.max_length + 1
+        tok_in, target = (np.ascontiguousarray(v, dtype=np.int32) for v in (tok_in, target))
+        trun = np.ascontiguousarray(trun, dtype=np.int32)
+        row_image = np.ascontiguousarray(row_image, dtype=np.int64)
+        if tok_in.shape != (R, steps) or target.shape != (R, steps) or trun.shape != (R,):
+            raise ValueError(f"tok_in / target must be [{R}, {steps}] and trun [{R}]")
+        if R and (row_image.min() < 0 or row_image.max() >= N):
+            raise ValueError("row_image must index the canvases")
+        V = self.model.V
+        if R and (min(tok_in.min(), target.min()) < 0 or max(tok_in.max(), target.max()) >= V or trun.min() < 0 or trun.max() > steps):
+            raise ValueError("token ids must lie in [0, num_classes) and trun in [0, max_length + 1]")
+        if R == 0:
+            z = np.zeros((0, steps), dtype=np.float32)
+            return np.zeros(0, np.float32), np.zeros(0, np.float32), z, z.copy(), z.copy(), np.zeros((0, steps), np.int32)
+        enc = [self.model.encode(canvases_dev[s:s + self.device_batch]) for s in range(0, N, self.device_batch)]
+        batch_H, proj_H = (torch.cat([e[i] for e in enc]) for i in (0, 1))
+        T = batch_H.shape[1]
+        dec = self.model.dec
+        ctxg = dec.ctx_gates(batch_H).view(N, -1) if dec._matrix_core(T) else None  # the hoisted context product, once per image
+        dev = lambda a: torch.from_numpy(a).to(self.device)
+        row_dev, tok_dev, tgt_dev, trun_dev = dev(row_image), dev(tok_in), dev(target), dev(trun)
+        outs = []
+        for s in range(0, R, self.device_batch):
+            idx = row_dev[s:s + self.device_batch]
+            B = int(idx.shape[0])
+            tgt, tr = tgt_dev[s:s + B], trun_dev[s:s + B]
+            logits, al = self.model.forced(batch_H.index_select(0, idx), proj_H.index_select(0, idx), tok_dev[s:s + B], self.sos_id,
+                                           self.blank_id, ctx_gates=None if ctxg is None else ctxg.index_select(0, idx))
+            lps, lp = dec.seq_logp(logits, tgt, tr, temperature)
+            prob = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+            centre = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+            peak = torch.empty((B, steps), dtype=torch.int32, device=self.device)
+            nat.check(nat.lib().msocr_seq_char_details(logits.data_ptr(), tgt.data_ptr(), al.data_ptr(), tr.data_ptr(), B, V, steps, T,
+                                                       prob.data_ptr(), centre.data_ptr(), peak.data_ptr(), ops._stream()), "seq_char_details")
+            conf = torch.empty((B,), dtype=torch.float32, device=self.device)
+            nat.check(nat.lib().msocr_seq_confidence(logits.data_ptr(), tgt.data_ptr(), tr.data_ptr(), B, V, steps, conf.data_ptr(),
+                                                     ops._stream()), "seq_confidence")
+            outs.append((lp, conf, lps, prob, centre, peak))
+        return tuple(torch.cat([o[i] for o in outs]).cpu().numpy() for i in range(6))
+
+    def score(self, images, texts, batch_size: int = 32, temperature: float = 1.0, *, strict: bool = True):
+        """Forced decode (this package's extension; the reference has the pass only inside training, model.py:287-320): how well does a
+        given transcription fit a word image, and where does each of its symbols sit?  texts[i] is a str, or a list of str (candidate
+        readings of image i, e.g. from a lexicon).  The decoder is run along the given symbols instead of its own arg-max.  Per image
+        one dict for a str, a list of dicts in the given order for a list:
+          {"text": the text as packed, "logp": log P(text, EOS | image), the sum of log_softmax(logits / temperature) over the
+           text's symbols and its EOS, "confidence": the mean probability of those tokens, as predict computes a confidence (without
+           temperature), "chars": [{"char", "confidence", "x"}] as predict(return_chars=True) gives them}.
+        Candidates are comparable by logp; exp(logp / (len(text) + 1)) is a per-token geometric mean.  The encoder runs once per
+        image whatever the number of candidates.  strict=True: a character outside the charset or a text longer than the model's
+        max_len raises ValueError; strict=False drops such characters and truncates, as the reference's pack_attention_targets does
+        ("text" then shows what was scored).  batch_size is accepted for symmetry with predict and does not enter the numbers: a
+        forced row runs over its own length + 1 steps, there is no chunk-wide stopping step.  "x" is an attention centroid: an
+        estimate that means something for trained weights only."""
+        if isinstance(images, list) and isinstance(texts, str):
+            raise TypeError("texts must have one entry (a str or a list of str) per image")
+        images_list, texts_list = (images, list(texts)) if isinstance(images, list) else ([images], [texts])
+        if len(texts_list) != len(images_list):
+            raise ValueError(f"{len(images_list)} images but {len(texts_list)} entries of texts")
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if not (temperature > 0):
+            raise ValueError(f"temperature must be positive, got {temperature}")
+        if not images_list:
+            return []
+        single = [isinstance(t, str) for t in texts_list]
+        cands = [[t] if one else list(t) for t, one in zip(texts_list, single)]
+        row_image = np.repeat(np.arange(len(cands)), [len(c) for c in cands])
+        R = len(row_image)
+        packs = []
+        for i, c in enumerate(cands):
+            try:
+                packs.append(pack_targets(c, self.stoi, self.max_length, strict=strict))
+            except ValueError as e:
+                raise ValueError(f"image {i}: {e}") from None
+        tok_in, target, trun = (np.concatenate([p[k] for p in packs]) for k in range(3))
+        packed = [t for p in packs for t in p[3]]
+        arrays = [self._load_rgb(im) for im in images_list]
+        canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
+        logp, conf, _lps, prob, centre, _peak = self.score_canvases(canv, row_image, tok_in, target, trun, temperature)
+        src_w = np.array([a.shape[1] for a in arrays], dtype=np.float64)[row_image]
+        new_w = np.array([resized_size(a.shape[0], a.shape[1], self.img_h, self.img_w)[0] for a in arrays], dtype=np.float64)[row_image]
+        chars = self.chars(target, trun, prob, centre, new_w, np.zeros(R), src_w)
+        entries = [{"text": t, "logp": float(l), "confidence": float(c), "chars": ch} for t, l, c, ch in zip(packed, logp, conf, chars)]
+        out, k = [], 0
+        for c, one in zip(cands, single):
+            out.append(entries[k] if one else entries[k:k + len(c)])
+            k += len(c)
+        return out
 
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,

@@ -152,6 +152,9 @@ class TrbaNet:
     def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, want_alpha=False):
         return self.dec.greedy(batch_H, proj_H, max_len, sos_id, eos_id, blank_id, want_alpha=want_alpha)
 
+    def forced(self, batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=None):
+        return self.dec.forced(batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=ctx_gates)
+
     def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, want_alpha=False):
         return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks,
                              want_alpha=want_alpha)
@@ -269,6 +272,37 @@ class AttnDecoder:
             else:
                 nat.check(nat.lib().msocr_attn_greedy_alpha(*head, al.data_ptr(), ops._stream()), "attn_greedy_alpha")
         return (logits, ids, al) if want_alpha else (logits, ids)
+
+    def forced(self, batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=None):
+        """Forced (teacher-forced) decode along given tokens: tok_in [B, steps] int32 on the device, column 0 = SOS, then the ids the
+        decoder is to be fed (transforms.pack_targets) -> (logits [B, steps, V] f32, alpha [B, steps, T] f32), every step written.
+        Routed like `greedy`; a row fed greedy's own ids gets greedy's logits and weights bit for bit.  ctx_gates as for `greedy`."""
+        B, T, H = batch_H.shape
+        assert tok_in.dim() == 2 and tok_in.shape[0] == B and tok_in.dtype == torch.int32 and tok_in.is_contiguous() and tok_in.is_cuda
+        steps = tok_in.shape[1]
+        logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
+        al = torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
+        blank = -1 if blank_id is None else blank_id
+        if self._matrix_core(T):
+            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
+            nat.check(nat.lib().msocr_attn_forced_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
+                                                          ctypes.byref(self._asw), B, T, H, self.V, steps, tok_in.data_ptr(), sos_id, blank,
+                                                          logits.data_ptr(), al.data_ptr(), ops._stream()), "attn_forced_hoisted")
+        else:
+            nat.check(nat.lib().msocr_attn_forced(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), B, T, H, self.V, steps,
+                                                  tok_in.data_ptr(), sos_id, blank, logits.data_ptr(), al.data_ptr(), ops._stream()),
+                      "attn_forced")
+        return logits, al
+
+    def seq_logp(self, logits, ids, trun_dev, temperature=1.0):
+        """log_softmax(logits / temperature)[ids] per step and summed over t < t_run (msocr_seq_logp): (logp_steps [B, steps] f32,
+        logp [B] f32) on the device."""
+        B, steps, V = logits.shape
+        lps = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+        lp = torch.empty((B,), dtype=torch.float32, device=self.device)
+        nat.check(nat.lib().msocr_seq_logp(logits.data_ptr(), ids.data_ptr(), trun_dev.data_ptr(), B, V, steps, float(temperature),
+                                           lps.data_ptr(), lp.data_ptr(), ops._stream()), "seq_logp")
+        return lps, lp
 
     def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None,
              want_alpha=False, alpha_ws=None):

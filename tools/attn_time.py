@@ -1,9 +1,13 @@
 """Times the beam-8 decode launch (all 25 steps, no early exit) for B crops, split-operand form against exact-f32 MFMA (dev tool).
-  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest]
+  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest] [--forced]
 --alpha: with the attention-weight output on (the _alpha entry points, into one preallocated buffer).  --repeats N: N timed repeats
 of 5 calls each per form, one line each (default 1).  --general: the general kernel (csrc/attn_general.hip) at the same shape
 instead of the matrix-core kernels (net.HOIST_CTX = False; one form, no split / exact comparison).  --greedy: the greedy decode
 (26 steps) instead of the beam decode: the matrix-core greedy kernel, or the general one with --general; timings only.
+--forced: the forced decode (AttnDecoder.forced along the greedy decode's own ids, 26 steps, the context GEMM included as in greedy)
+against the greedy decode with the attention-weight output, alternating: per round 5 calls of one, then 5 of the other, --repeats
+rounds (default 1); one line per round and variant, then medians and spread (max - min) over the rounds.  With --general on the
+general kernels.
 --nbest: after the decode timing of the first form, the read-out of its workspace: msocr_attn_beam_finalize + msocr_seq_confidence
 (what every word pays today) and msocr_attn_beam_nbest for n_best 1, 3 and 8, each as the mean of 20 calls after 3 warm-up calls."""
 import argparse, os, sys
@@ -21,6 +25,7 @@ ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--general", action="store_true")
 ap.add_argument("--greedy", action="store_true")
 ap.add_argument("--nbest", action="store_true")
+ap.add_argument("--forced", action="store_true")
 a = ap.parse_args()
 if a.repeats < 1:
     ap.error("--repeats must be at least 1")
@@ -34,6 +39,32 @@ if a.general:
 torch.manual_seed(0)
 bH = torch.randn(B, 13, 256, device="cuda")
 pH = torch.randn(B, 13, 256, device="cuda")
+if a.forced:
+    import statistics
+    name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])
+    al = torch.empty((B, 26, 13), dtype=torch.float32, device="cuda")
+    _lg, ids, _ = dec.greedy(bH, pH, 25, 1, 2, None, want_alpha=True, alpha_out=al)
+    tok = torch.cat([torch.ones((B, 1), dtype=torch.int32, device="cuda"), ids[:, :-1]], 1).contiguous()
+    variants = {"greedy + alpha": lambda: dec.greedy(bH, pH, 25, 1, 2, None, want_alpha=True, alpha_out=al),
+                "forced": lambda: dec.forced(bH, pH, tok, 1, None)}
+    for fn in variants.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _rep in range(REPEATS):
+        for k, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 5)
+            print(f"{name} {k}: {ms[k][-1]:.3f} ms per call (GEMM + kernel), B={B}, 26 steps")
+    for k, v in ms.items():
+        print(f"{name} {k}: median {statistics.median(v):.3f} ms, spread {max(v) - min(v):.3f} ms over {len(v)} rounds")
+    sys.exit(0)
 if a.greedy:
     name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])
     al = torch.empty((B, 26, 13), dtype=torch.float32, device="cuda") if ALPHA else None

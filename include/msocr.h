@@ -394,6 +394,49 @@ int msocr_seq_logp(const float* logits, const int32_t* ids, const int32_t* trun_
 int msocr_seq_logp_host(const float* logits_host, const int32_t* ids_host, const int32_t* trun_host, int B, int V, int steps,
                         float temperature, float* logp_steps_out_host, float* logp_out_host);
 
+/* Lexicon-constrained beam decode: the search of msocr_attn_beam restricted to the words of a closed vocabulary, held as a prefix tree
+ * (trie) in device memory.  msocr_lexicon: CSR arrays, nodes in breadth-first order (root = node 0, child > parent): edge_begin
+ * [n_nodes + 1] i32, edge_tok [n_edges] i32 (strictly ascending inside a node), edge_child [n_edges] i32, terminal [n_nodes] u8 (1 where
+ * a word ends).  The decode is the beam loop with two additions:
+ *   state: every beam slot carries a trie node (i32; all slots start at the root; -1 = a dead slot);
+ *   mask : where the candidates are formed, token v of a slot that is not finished is allowed if v is a child token of the slot's
+ *          node, or v == eos_id and the node is terminal; every other candidate is -inf, and so is every candidate of a dead slot.
+ *          Finished slots keep the plain rule (EOS alone, log-probability 0).
+ * There is NO renormalisation: the log-sum-exp stays over the full row of V logits, so a path's score is the model's own joint
+ * log-probability of that text (the number msocr_seq_logp gives for a forced decode of it).  Temperature, length penalty, the blank
+ * column and the tie rule (larger value, then smaller flat index) are the plain decode's.  After the top-K a new slot's node is its
+ * source's node when the source was finished or the token is eos_id, else the child of the source's node along the token (-1 when
+ * there is none), and -1 whenever the winning candidate's value is not finite; a slot whose node is -1 counts as finished, so
+ * fin_step and the chunk early exit fire as before.  The workspace layout and fin_step are unchanged: msocr_attn_beam_finalize(_alpha),
+ * msocr_attn_beam_nbest and msocr_seq_confidence read a constrained decode's workspace as they read a plain one's.  One more output:
+ * node_out [B][steps][beam] i32 (msocr_attn_lexicon_nodes_bytes), the node of every slot after step s (steps the early exit skips stay
+ * unwritten).  alpha_ws is required (there is one constrained kernel per family, with the weight output on).
+ *   msocr_attn_beam_lexicon         the envelope of msocr_attn_beam, general kernel (csrc/attn_general_lexicon.hip)
+ *   msocr_attn_beam_lexicon_hoisted the shapes of msocr_attn_beam_hoisted on the matrix cores (csrc/attn_lexicon_mfma.hip)
+ * A null lex or member of it, n_nodes < 1, n_edges < 0, a null node_out or alpha_ws and shapes outside the kernel's envelope return
+ * MSOCR_E_ARG before any launch.  The entry points receive device pointers and cannot validate the trie; the kernels clamp every
+ * edge range into [0, n_edges], ignore an edge token outside [0, V) and treat a child outside [0, n_nodes) as none, so a malformed
+ * trie can yield a wrong word but no out-of-bounds read.  msocr_lexicon_check_host validates HOST copies of the arrays: begins
+ * monotone from 0 to n_edges, tokens strictly ascending per node and inside [0, V), parent < child < n_nodes, every node but the
+ * root with exactly one parent, every childless node terminal, depth <= max_depth; MSOCR_OK or MSOCR_E_ARG. */
+typedef struct {
+  const int32_t *edge_begin, *edge_tok, *edge_child;
+  const uint8_t* terminal;
+  int n_nodes, n_edges;
+} msocr_lexicon; /* device pointers */
+int64_t msocr_attn_lexicon_nodes_bytes(int B, int steps, int beam);
+int msocr_attn_beam_lexicon(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
+                            int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                            int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                            int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream);
+int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                    const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                    const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
+                                    void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                    int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream);
+int msocr_lexicon_check_host(const int32_t* edge_begin_host, const int32_t* edge_tok_host, const int32_t* edge_child_host,
+                             const uint8_t* terminal_host, int n_nodes, int n_edges, int V, int max_depth);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

@@ -45,6 +45,10 @@ class AttnSplitWeights(ctypes.Structure):
     _fields_ = [(n, c_vp) for n in ("h2h_p", "whh_p", "gen_p")]
 
 
+class LexiconArrays(ctypes.Structure):  # msocr_lexicon: device pointers
+    _fields_ = [("edge_begin", c_vp), ("edge_tok", c_vp), ("edge_child", c_vp), ("terminal", c_vp), ("n_nodes", c_i32), ("n_edges", c_i32)]
+
+
 _SIGS = {
     "msocr_conv2d": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc), c_i32]),
@@ -105,6 +109,13 @@ _SIGS = {
                                           c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "msocr_seq_logp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     "msocr_seq_logp_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    "msocr_attn_lexicon_nodes_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "msocr_attn_beam_lexicon": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
+                                        c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(LexiconArrays), c_vp, c_vp]),
+    "msocr_attn_beam_lexicon_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
+                                                c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                c_vp, ctypes.POINTER(LexiconArrays), c_vp, c_vp]),
+    "msocr_lexicon_check_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

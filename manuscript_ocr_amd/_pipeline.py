@@ -29,6 +29,13 @@ read out of the workspace the decode leaves behind: the decode itself, and with 
 Works on the native batch path with every other switch, and on the generic route when the recogniser is this package's TRBA; a
 foreign recogniser is not asked for alternatives.
 
+`pipeline.lexicon = Lexicon(words, recognizer.stoi, recognizer.max_length)` (this package's extension, None = off by default): the
+recogniser's beam search is constrained to the lexicon's words; recognised words come back as LexWords
+(detectors/_types.py) whose `text` is a lexicon word and whose `lexicon_index` is its index in `lexicon.words`.  Combines with
+char_details, rectify_crops, group_lines and n_best (the alternatives are then lexicon words too).  The detector's "words" carry their
+punctuation: a lexicon of bare word forms forbids "слово," — the caller supplies the forms to admit.  Captured graphs are not provided
+for this route: with a `use_graphs` recogniser a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
+
 `pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
 (an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
 
@@ -120,6 +127,7 @@ class _Batch:
     rectify: bool                    # rectify_crops as it was at submit
     line_recs: Optional[dict]        # group_lines as it was at submit: page index -> per block its [L,6] line records; None = off
     n_best: int                      # n_best as it was at submit
+    lexicon: Any                     # lexicon as it was at submit; None = the open search
     ingest_pending: Any              # the device JPEG stages' deferred verdict, read in advance_batch
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
@@ -145,6 +153,7 @@ class Pipeline:
         self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
         self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
         self.n_best = 0                    # > 0: recognised words come back as AltWords with the beam search's n best readings (user extension)
+        self.lexicon = None                # a recognizers.Lexicon: the beam search is constrained to its words, LexWords come back (user extension)
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -243,12 +252,15 @@ class Pipeline:
         if crops:
             t0 = time.time()
             n_best = self._n_best() if isinstance(self.recognizer, TRBA) else 0  # a foreign recogniser is not asked
-            results = self.recognizer.predict(crops, n_best=n_best) if n_best else self.recognizer.predict(crops)
+            lexicon = self.lexicon if isinstance(self.recognizer, TRBA) else None
+            extra = {**({"n_best": n_best} if n_best else {}), **({"lexicon": lexicon} if lexicon is not None else {})}
+            results = self.recognizer.predict(crops, **extra)
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
             self._assign(words, [results[i] for i in range(len(words))])
-            if n_best:
-                self._attach_details(words, [page], alts=[results[i]["alternatives"] for i in range(len(words))])
+            if n_best or lexicon is not None:
+                self._attach_details(words, [page], alts=[results[i]["alternatives"] for i in range(len(words))] if n_best else None,
+                                     lex_idx=None if lexicon is None else [results[i]["lexicon_index"] for i in range(len(words))])
         if line_recs is not None:
             self._split_lines(page, line_recs)
         if profile:
@@ -347,7 +359,12 @@ class Pipeline:
         batch i+1 can be enqueued before `collect_batch` of batch i and fills the device while batch i drains."""
         if not (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)):
             raise TypeError("submit_batch/collect_batch need this package's EAST and TRBA plugins")
-        det, n_best = self.detector, self._n_best()
+        det, n_best, lexicon = self.detector, self._n_best(), self.lexicon
+        if lexicon is not None:
+            self.recognizer._check_lexicon(lexicon, "beam")
+            if self.recognizer.use_graphs:
+                raise ValueError("Pipeline.lexicon with a use_graphs recogniser: captured graphs are not provided for the lexicon-constrained "
+                                 "decode; construct the recogniser without use_graphs")
         # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
         dec, ingest_pending = [None] * len(images), None
@@ -429,7 +446,8 @@ class Pipeline:
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
                 groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
-        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, ingest_pending,
+        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon,
+                      ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
 
     def advance_batch(self, h):
@@ -555,7 +573,7 @@ class Pipeline:
                     canv = ops.quad_crop(pages_dev, grp.qdesc_host, rec.img_h, rec.img_w, qdesc_dev=qdesc_dev)
                 else:
                     canv = ops.crop_resize_pad(pages_dev, grp.desc_host, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                grp.handle = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details)
+                grp.handle = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details, lexicon=h.lexicon)
 
     def collect_batch(self, h):
         """Stages 2-3 of `predict_batch` for a handle from `submit_batch` -> list of Pages (stage 2 = `advance_batch`,
@@ -623,9 +641,11 @@ class Pipeline:
                     elif details:
                         chars = rec.chars(ids, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3])
                     if h.n_best:
-                        alts = rec.alternatives(alt_ids, trun, alt_conf, alt_logp)
-                    if details or h.n_best:
-                        self._attach_details(grp.words, pages[lo:hi], chars, alts)
+                        alts = (rec.alternatives(alt_ids, trun, alt_conf, alt_logp) if h.lexicon is None else
+                                rec.lexicon_alternatives(alt_ids, trun, alt_conf, alt_logp, h.lexicon))
+                    if details or h.n_best or h.lexicon is not None:
+                        self._attach_details(grp.words, pages[lo:hi], chars, alts,
+                                             None if h.lexicon is None else rec.lexicon_indices(ids, h.lexicon))
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
@@ -641,20 +661,23 @@ class Pipeline:
         return pages
 
     @staticmethod
-    def _attach_details(words, pages, chars=None, alts=None):
+    def _attach_details(words, pages, chars=None, alts=None, lex_idx=None):
         """Replace every recognised Word of `pages` by a CharWord carrying its symbols (`chars`, char_details), or by an AltWord that
         also carries its readings (`alts`, n_best; its `chars` stay empty without char_details).  chars[k] / alts[k] belong to
-        words[k]; x is in page pixels (the recogniser mapped the attention centroid into the word's clamped crop window)."""
-        from .detectors._types import Alternative, AltWord, Char, CharWord
+        words[k]; x is in page pixels (the recogniser mapped the attention centroid into the word's clamped crop window).  lex_idx
+        (lexicon): a LexWord instead, carrying lex_idx[k]; its alternatives are LexAlternatives."""
+        from .detectors._types import Alternative, AltWord, Char, CharWord, LexAlternative, LexWord
         new = {}
         for k, word in enumerate(words):
             extra = {} if chars is None else {"chars": [Char(**d) for d in chars[k]]}
             if alts is not None:
-                extra["alternatives"] = [Alternative(**d) for d in alts[k]]
+                extra["alternatives"] = [(Alternative if lex_idx is None else LexAlternative)(**d) for d in alts[k]]
+            if lex_idx is not None:
+                extra["lexicon_index"] = lex_idx[k]
             # the [0, 1] clamp is a no-op guard for CharWord's validation: the confidence is a mean of exp(log-softmax) values, each
             # <= 1 by the kernel's arithmetic (logp <= 0), so the value equals the plain Word's and a default dump does not change
             c = word.recognition_confidence
-            new[id(word)] = (CharWord if alts is None else AltWord)(
+            new[id(word)] = (LexWord if lex_idx is not None else CharWord if alts is None else AltWord)(
                 polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
                 recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), **extra)
         for page in pages:

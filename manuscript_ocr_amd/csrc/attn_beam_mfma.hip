@@ -43,6 +43,13 @@ using namespace split_rows32;
 // Observed with one compiler (ROCm 7's hipcc): when the toolchain moves, try the template split again (tools/check_isa.sh).
 // A third compilation, through attn_forced_mfma.hip (MSOCR_ATTN_FORCED with MSOCR_ATTN_ALPHA), holds only the forced-decode kernel and
 // its launcher, for the same reason: neither the beam nor the greedy kernel is compiled there, nor the pack helpers.
+// A fourth, through attn_lexicon_mfma.hip (MSOCR_ATTN_LEXICON with MSOCR_ATTN_ALPHA), holds the beam kernel under the lexicon constraint
+// and its launcher, alone: a trie node per beam slot (a.lex_*, msocr_lexicon), a live slot's candidates are its node's child tokens and
+// EOS where a word ends at the node, every other candidate is -inf; the log-sum-exp of (g) stays over the full row.  The lines the
+// constraint adds are under #ifdef, so the other three compilations see the text they saw before.
+#ifdef MSOCR_ATTN_LEXICON
+#include "lexicon_walk.h"
+#endif
 #ifdef MSOCR_ATTN_ALPHA
 constexpr bool ALPHA = true;
 #define ATTN_ENTRY(name) name##_alpha
@@ -475,6 +482,10 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
   float* const sbuf = sbuf_of<HS>();
   __shared__ float s_score[R], s_lse[R], s_top[R];
   __shared__ int s_tok[R], s_done[R], s_src[R], s_nxt[R], s_fin[NB], s_exit;
+#ifdef MSOCR_ATTN_LEXICON
+  __shared__ int s_node[R];          // the slot's trie node; -1 = dead (it left the trie, or was filled from an all -inf round)
+  __shared__ unsigned s_mask[R * 8]; // allowed tokens of every slot in this step, one bit per token (V <= 256), rebuilt every step
+#endif
 
   const Lane l(threadIdx.x);
   const int tid = l.tid, lane = l.lane, wv = l.wv, half = l.half, ju = l.ju;
@@ -489,6 +500,9 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     s_score[tid] = (tid % KB8) == 0 ? 0.f : -INFINITY;
     s_tok[tid] = a.sos_id;
     s_done[tid] = 0;
+#ifdef MSOCR_ATTN_LEXICON
+    s_node[tid] = 0;  // the root
+#endif
   }
   if (tid < NB) s_fin[tid] = a.steps;
   __syncthreads();
@@ -510,6 +524,9 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     __syncthreads();
     TSTAMP(5);
     // ---- (f) logits; temperature; trace store
+#ifdef MSOCR_ATTN_LEXICON
+    if (tid < R * 8) s_mask[tid] = 0u;  // last read by (h) of the step before, barriers back; filled in (g), a barrier on
+#endif
     {
       const f32x16 acc = phase_generator<HS>(a, l);
       if (ju < V) {
@@ -535,6 +552,24 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
       for (int v = lane; v < V; v += 64) sum += expf(sbuf[r * H + v] - m);
       sum = wave_sum63(sum);
       if (lane == 63) s_lse[r] = m + logf(sum);  // libm-grade exp / log: the scores of a beam search are sums of these
+#ifdef MSOCR_ATTN_LEXICON
+      // the row's allowed tokens: a live slot's edge list strided over the wave (an edge token outside [0, V) is ignored), EOS where
+      // its node is terminal; a finished slot keeps the plain rule (EOS alone); a dead slot has none
+      const int node = s_node[r];
+      if ((r % KB8) < KB && node >= 0) {
+        const int dn = s_done[r];
+        if (!dn) {
+          int lo, hi;
+          lex_edge_range(a.lex_begin, a.lex_nodes, a.lex_edges, node, lo, hi);
+          for (int e = lo + lane; e < hi; e += 64) {
+            const int tk = a.lex_tok[e];
+            if (tk >= 0 && tk < V) atomicOr(&s_mask[r * 8 + (tk >> 5)], 1u << (tk & 31));
+          }
+        }
+        if (lane == 0 && a.eos_id >= 0 && a.eos_id < V && (dn || lex_terminal(a.lex_terminal, a.lex_nodes, node)))
+          atomicOr(&s_mask[r * 8 + (a.eos_id >> 5)], 1u << (a.eos_id & 31));
+      }
+#endif
     }
     __syncthreads();
     TSTAMP(7);
@@ -560,9 +595,15 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
         for (int rb = 0; rb < KB8; ++rb) {
           cv[i][rb] = -INFINITY;
           const int r = nb * KB8 + rb;
+#ifdef MSOCR_ATTN_LEXICON
+          const unsigned mw = s_mask[r * 8 + 2 * i + (lane >> 5)];  // the word that holds token v = lane + 64 i
+#endif
           if (v < V && rb < KB) {
             float logp = sbuf[r * H + v] - lse_r[rb];
             if (dn_r[rb]) logp = (v == a.eos_id) ? 0.f : -INFINITY;
+#ifdef MSOCR_ATTN_LEXICON
+            if (!((mw >> (lane & 31)) & 1u)) logp = -INFINITY;
+#endif
             float tot = sc_r[rb] + logp;
             if (a.lp) tot = tot / lp;
             cv[i][rb] = tot;
@@ -626,10 +667,23 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     TSTAMP(8);
     // ---- (i) bookkeeping per state row
     int nd = 1;
+#ifdef MSOCR_ATTN_LEXICON
+    int nn = -1;  // the new slot's node: its parent's where the hypothesis is finished, else the child along the token; -1 = dead
+    if (tid < R) {
+      const int nb = tid / KB8, rb = tid % KB8;
+      if (rb < KB) {
+        const int src = nb * KB8 + s_src[tid], nxt = s_nxt[tid], ended = s_done[src] | (nxt == a.eos_id);
+        nn = ended ? s_node[src] : lex_child(a.lex_begin, a.lex_tok, a.lex_child, a.lex_nodes, a.lex_edges, s_node[src], nxt);
+        if (!isfinite(s_top[tid])) nn = -1;
+        nd = ended | (nn < 0);  // no legal continuation counts as finished: fin_step and the chunk early exit still fire
+      }
+    }
+#else
     if (tid < R) {
       const int nb = tid / KB8, rb = tid % KB8;
       if (rb < KB) nd = s_done[nb * KB8 + s_src[tid]] | (s_nxt[tid] == a.eos_id);
     }
+#endif
     __syncthreads();
     if (tid < R) {
       const int nb = tid / KB8, rb = tid % KB8, b = b0 + nb;
@@ -638,9 +692,15 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
           const long o = ((long)b * a.steps + s) * KB + rb;
           a.back[o] = s_src[tid];
           a.tokv[o] = s_nxt[tid];
+#ifdef MSOCR_ATTN_LEXICON
+          a.node_out[o] = nn;
+#endif
         }
         s_score[tid] = a.lp ? s_top[tid] * lp : s_top[tid];  // f32 round trip of the reference (model.py:188-192)
         s_tok[tid] = s_nxt[tid];
+#ifdef MSOCR_ATTN_LEXICON
+        s_node[tid] = nn;
+#endif
       }
       s_done[tid] = nd;
     }
@@ -706,6 +766,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
   if (tid < NB && b0 + tid < a.B) a.fin_step[b0 + tid] = s_fin[tid];
 }
 
+#ifndef MSOCR_ATTN_LEXICON
 // Greedy decode (Attention._greedy_decode, model.py:227-259): 32 CROPS per workgroup, one state row each, all `steps` steps in one
 // launch.  The rows are independent (the reference keeps every row running after its own EOS and only stops a chunk when all rows
 // emit EOS in the same step; the host derives those run lengths from the ids, recognizers/_trba/__init__.py), so a step is (a)-(f)
@@ -771,6 +832,7 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
     __syncthreads();
   }
 }
+#endif  // MSOCR_ATTN_LEXICON
 
 #else  // MSOCR_ATTN_FORCED
 // Forced (teacher-forced) decode, Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0: the greedy
@@ -828,7 +890,23 @@ constexpr size_t lds_bytes() { return (size_t)(HRows<SPLITW>::FLOATS + R * H + R
 
 }  // namespace
 
-#ifdef MSOCR_ATTN_FORCED
+#if defined(MSOCR_ATTN_LEXICON)
+// the one kernel of attn_lexicon_mfma.hip (both operand forms)
+int msocr_internal_attn_lexicon_mfma(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates || !a.alpha_out || !a.node_out) return MSOCR_E_ARG;
+  if (!a.lex_begin || !a.lex_tok || !a.lex_child || !a.lex_terminal || a.lex_nodes < 1 || a.lex_edges < 0) return MSOCR_E_ARG;
+  const size_t ldsz = lds_bytes<false>(), ldsz_split = lds_bytes<true>();
+  if (msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<false>, (int)ldsz) != MSOCR_OK ||
+      msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<true>, (int)ldsz_split) != MSOCR_OK)
+    return MSOCR_E_LAUNCH;
+  const dim3 grid((a.B + NB - 1) / NB);
+  if (a.h2h_p)
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<true>), grid, dim3(NT), ldsz_split, s, a);
+  else
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<false>), grid, dim3(NT), ldsz, s, a);
+  return LAUNCH_OK();
+}
+#elif defined(MSOCR_ATTN_FORCED)
 // the one kernel of attn_forced_mfma.hip
 int msocr_internal_attn_forced_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates || !a.h2h_p || !a.whh_p || !a.gen_p || !a.alpha_out || !a.tok_in || !a.logits_out) return MSOCR_E_ARG;

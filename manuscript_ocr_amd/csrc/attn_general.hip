@@ -31,6 +31,14 @@ constexpr bool FORCED = true;
 #else
 constexpr bool FORCED = false;
 #endif
+// The lexicon constraint is the same kind of fact: attn_general_lexicon.hip defines MSOCR_ATTN_LEXICON and includes this file, which then
+// holds the beam instantiation alone, behind msocr_internal_attn_general_lexicon.  Every beam slot carries a node of the lexicon's prefix
+// tree (a.lex_*, msocr_lexicon); a live slot's candidates are its node's child tokens, and EOS where a word ends at the node; every other
+// candidate is -inf.  The log-sum-exp stays over the full row: a path's score is the model's own joint log-probability of that text.
+// The lines the constraint adds are under #ifdef, so this file compiled as itself is the text it was.
+#ifdef MSOCR_ATTN_LEXICON
+#include "lexicon_walk.h"
+#endif
 
 namespace {
 
@@ -76,6 +84,10 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
   __shared__ int s_idx[NTH / 64];
   __shared__ float s_score[KCAP], s_lse[KCAP], s_top[KCAP];
   __shared__ int s_tok[KCAP], s_done[KCAP], s_src[KCAP], s_nxt[KCAP];
+#ifdef MSOCR_ATTN_LEXICON
+  __shared__ int s_node[KCAP];             // the slot's trie node; -1 = dead (it left the trie, or was filled from an all -inf round)
+  __shared__ unsigned s_mask[KCAP * 16];   // allowed tokens of every slot in this step, one bit per token (V <= 512), rebuilt every step
+#endif
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* bH = a.batch_H + (long)b * T * H;
   const float* pH = a.proj_H + (long)b * T * H;
@@ -84,6 +96,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
     s_score[tid] = tid == 0 ? 0.f : -INFINITY;
     s_tok[tid] = a.sos_id;
     s_done[tid] = 0;
+#ifdef MSOCR_ATTN_LEXICON
+    s_node[tid] = 0;  // the root
+#endif
   }
   __syncthreads();
   int fin = a.steps;
@@ -202,6 +217,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
         const int r = i / V, v = i - r * V;
         a.logits_out[(((long)b * a.steps + s) * KB + r) * V + v] = x;
       }
+#ifdef MSOCR_ATTN_LEXICON
+      for (int i = tid; i < K * 16; i += NTH) s_mask[i] = 0u;
+#endif
       __syncthreads();
       for (int r = wv; r < K; r += NTH / 64) {  // log-sum-exp per row
         float m = -INFINITY;
@@ -213,6 +231,24 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
         sum = wsum(sum);
         if (lane == 0) s_lse[r] = m + logf(sum);
       }
+#ifdef MSOCR_ATTN_LEXICON
+      // allowed tokens: a live slot's edge list strided over the workgroup (an edge token outside [0, V) is ignored), EOS where its node
+      // is terminal; a finished slot keeps today's rule (EOS alone); a dead slot has none
+      for (int r = 0; r < K; ++r) {
+        const int node = s_node[r];
+        if (node < 0) continue;
+        if (!s_done[r]) {
+          int lo, hi;
+          lex_edge_range(a.lex_begin, a.lex_nodes, a.lex_edges, node, lo, hi);
+          for (int e = lo + tid; e < hi; e += NTH) {
+            const int tk = a.lex_tok[e];
+            if (tk >= 0 && tk < V) atomicOr(&s_mask[r * 16 + (tk >> 5)], 1u << (tk & 31));
+          }
+        }
+        if (tid == 0 && a.eos_id >= 0 && a.eos_id < V && (s_done[r] || lex_terminal(a.lex_terminal, a.lex_nodes, node)))
+          atomicOr(&s_mask[r * 16 + (a.eos_id >> 5)], 1u << (a.eos_id & 31));
+      }
+#endif
       __syncthreads();
       // candidates in place: (score[r] + logp[r][v]) / lp ; finished beams: only EOS with logp 0 (model.py:140-160)
       const float lp = a.lp ? a.lp[s] : 1.0f;
@@ -220,6 +256,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
         const int r = i / V, v = i - r * V;
         float logp = slog[i] - s_lse[r];
         if (s_done[r]) logp = (v == a.eos_id) ? 0.f : -INFINITY;
+#ifdef MSOCR_ATTN_LEXICON
+        if (!((s_mask[r * 16 + (v >> 5)] >> (v & 31)) & 1u)) logp = -INFINITY;
+#endif
         float tot = s_score[r] + logp;
         if (a.lp) tot = tot / lp;
         slog[i] = tot;
@@ -253,7 +292,17 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
       __syncthreads();
       for (int i = tid; i < K * H; i += NTH) { sh[i] = sctx[i]; sc[i] = sph[i]; }
       int nd = 1;
+#ifdef MSOCR_ATTN_LEXICON
+      int nn = -1;  // the new slot's node: its parent's where the hypothesis is finished, else the child along the token; -1 = dead
+      if (tid < K) {
+        const int src = s_src[tid], nxt = s_nxt[tid], ended = s_done[src] | (nxt == a.eos_id);
+        nn = ended ? s_node[src] : lex_child(a.lex_begin, a.lex_tok, a.lex_child, a.lex_nodes, a.lex_edges, s_node[src], nxt);
+        if (!isfinite(s_top[tid])) nn = -1;
+        nd = ended | (nn < 0);  // no legal continuation counts as finished: fin_step still fires
+      }
+#else
       if (tid < K) nd = s_done[s_src[tid]] | (s_nxt[tid] == a.eos_id);
+#endif
       __syncthreads();
       if (tid < K) {
         const long o = ((long)b * a.steps + s) * KB + tid;
@@ -262,6 +311,10 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
         s_score[tid] = a.lp ? s_top[tid] * lp : s_top[tid];  // f32 round trip of the reference (model.py:188-192)
         s_tok[tid] = s_nxt[tid];
         s_done[tid] = nd;
+#ifdef MSOCR_ATTN_LEXICON
+        s_node[tid] = nn;
+        a.node_out[o] = nn;
+#endif
       }
       __syncthreads();
       if (tid == 0) {
@@ -284,7 +337,22 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 
 }  // namespace
 
-#ifdef MSOCR_ATTN_FORCED
+#if defined(MSOCR_ATTN_LEXICON)
+// the one kernel of attn_general_lexicon.hip: the beam loop under the lexicon constraint.  Same shapes as msocr_internal_attn_general.
+int msocr_internal_attn_general_lexicon(const AttnArgs& a, int H, hipStream_t s) {
+  if (!a.lex_begin || !a.lex_tok || !a.lex_child || !a.lex_terminal || a.lex_nodes < 1 || a.lex_edges < 0 || !a.node_out) return MSOCR_E_ARG;
+  const int K = a.K;
+  if (H < 64 || H > 512 || H % 64 || a.V <= 0 || a.V > 512 || a.T <= 0 || a.T > 64 || a.steps <= 0 || a.steps > 64 || K < 1 || K > KCAP ||
+      K * H > 4096 || a.B <= 0)
+    return MSOCR_E_ARG;
+  const size_t ldsz = (size_t)(4 * K * H + K * a.V + K * 64) * sizeof(float);
+  auto kb = attn_general_kernel<true>;
+  if (msocr_internal_lds_limit((const void*)kb, 112 * 1024) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  if (ldsz > 112 * 1024) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(kb, dim3(a.B), dim3(NTH), ldsz, s, a, H);
+  return LAUNCH_OK();
+}
+#elif defined(MSOCR_ATTN_FORCED)
 // the one kernel of attn_general_forced.hip: the greedy loop along a.tok_in.  Same shapes as below with one row per crop.
 int msocr_internal_attn_general_forced(const AttnArgs& a, int H, hipStream_t s) {
   if (!a.tok_in || !a.alpha_out || !a.logits_out || a.sos_id < 0 || a.sos_id >= a.V) return MSOCR_E_ARG;

@@ -111,3 +111,31 @@ extern "C" int msocr_reading_lines_host(const int32_t* boxes_host, int n, double
   if (!nlines_out_host || (n > 0 && (!line_out_host || !lines_out_host))) return MSOCR_E_ARG;
   return reading_order_body(boxes_host, n, y_tol_ratio, x_gap_ratio, order_out_host, line_out_host, lines_out_host, nlines_out_host);
 }
+
+// --------------------------------------------------------------------------------------------- lexicon
+// Validator of a lexicon's prefix tree over HOST copies of its arrays (msocr.h, msocr_lexicon): what recognizers/_trba/lexicon.py calls
+// once per Lexicon, since the decode entry points receive device pointers and cannot look.  Breadth-first node order makes every check
+// one pass: a node's depth is known when its edges are read, because its parent (a smaller id) was read before it.
+extern "C" int msocr_lexicon_check_host(const int32_t* edge_begin, const int32_t* edge_tok, const int32_t* edge_child, const uint8_t* terminal,
+                                        int n_nodes, int n_edges, int V, int max_depth) {
+  if (!edge_begin || !terminal || n_nodes < 1 || n_edges < 0 || V <= 0 || max_depth < 0) return MSOCR_E_ARG;
+  if (n_edges > 0 && (!edge_tok || !edge_child)) return MSOCR_E_ARG;
+  if (edge_begin[0] != 0 || edge_begin[n_nodes] != n_edges) return MSOCR_E_ARG;
+  for (int n = 0; n < n_nodes; ++n)
+    if (edge_begin[n + 1] < edge_begin[n] || edge_begin[n + 1] > n_edges) return MSOCR_E_ARG;
+  std::vector<int32_t> depth((size_t)n_nodes, -1);  // -1 = no parent seen yet
+  depth[0] = 0;
+  for (int n = 0; n < n_nodes; ++n) {
+    if (depth[n] < 0) return MSOCR_E_ARG;  // n > 0 and no smaller node points at it
+    const int lo = edge_begin[n], hi = edge_begin[n + 1];
+    if (lo == hi && !terminal[n]) return MSOCR_E_ARG;  // a childless node ends a word
+    for (int e = lo; e < hi; ++e) {
+      const int tk = edge_tok[e], ch = edge_child[e];
+      if (tk < 0 || tk >= V || (e > lo && edge_tok[e - 1] >= tk)) return MSOCR_E_ARG;
+      if (ch <= n || ch >= n_nodes || depth[ch] >= 0) return MSOCR_E_ARG;  // parent < child < n_nodes, one parent
+      depth[ch] = depth[n] + 1;
+      if (depth[ch] > max_depth) return MSOCR_E_ARG;
+    }
+  }
+  return MSOCR_OK;
+}

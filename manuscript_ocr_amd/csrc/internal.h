@@ -82,6 +82,12 @@ struct AttnArgs {
                         // indexed like the logits trace (the weights of step s at slot rb belong to the hypothesis whose logits are there)
   const int32_t* tok_in;  // forced decode: [B][steps] the token fed to step s of every row (nullptr everywhere else); the forced kernels
                           // replace an id outside [0, V) by sos_id before it indexes wih_tok, and write no ids
+  // lexicon-constrained beam decode (attn_general_lexicon.hip, attn_lexicon_mfma.hip; null / zero everywhere else): the lexicon's prefix
+  // tree as CSR arrays on the device (msocr_lexicon) and the trie node of every slot after every step, [B][steps][K] i32 (-1 = dead)
+  const int32_t *lex_begin, *lex_tok, *lex_child;
+  const uint8_t* lex_terminal;
+  int lex_nodes, lex_edges;
+  int32_t* node_out;
 };
 // attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the matrix cores (H == 256, V <= 256, T <= 48, beam <= 8;
 // needs ctx_gates): split-operand products with the split weights, exact-f32 MFMA without them
@@ -101,4 +107,9 @@ __attribute__((visibility("hidden"))) int msocr_internal_attn_general(const Attn
 // attn_general_forced.hip: the forced decode for the same shapes (one row per crop): a.tok_in and a.alpha_out required; logits and
 // weights as the greedy loop stores them, no ids
 __attribute__((visibility("hidden"))) int msocr_internal_attn_general_forced(const AttnArgs& a, int H, hipStream_t s);
+// attn_general_lexicon.hip: the beam decode constrained to a lexicon's prefix tree, for the same shapes: a.lex_* and a.node_out required
+__attribute__((visibility("hidden"))) int msocr_internal_attn_general_lexicon(const AttnArgs& a, int H, hipStream_t s);
+// attn_lexicon_mfma.hip: the same on the matrix cores (the beam kernel's shapes; needs ctx_gates); a.alpha_out, a.lex_* and a.node_out
+// required
+__attribute__((visibility("hidden"))) int msocr_internal_attn_lexicon_mfma(const AttnArgs& a, hipStream_t s);
 #endif

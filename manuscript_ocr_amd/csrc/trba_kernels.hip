@@ -438,10 +438,14 @@ extern "C" int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T
 static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                           const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
                           int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                          int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
+                          int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
+                          int32_t* node_out = nullptr) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
   if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
   if (ctx_gates && (!attn_mfma_shape(T, H, V) || beam > 8)) return MSOCR_E_ARG;
+  if (lex && (!lex->edge_begin || !lex->edge_tok || !lex->edge_child || !lex->terminal || lex->n_nodes < 1 || lex->n_edges < 0 ||
+              !node_out || !alpha_ws || beam * H > 4096))
+    return MSOCR_E_ARG;
   AttnArgs a{};
   a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
   if (ws) { a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p; }
@@ -455,6 +459,11 @@ static int attn_beam_impl(const float* batch_H, const float* proj_H, const float
   a.fin_step = fin_step_out;
   a.alpha_out = (float*)alpha_ws;  // nullptr (the plain entry points): off
   if (chunk_id_dev && chunk_size_dev && chunk_state_dev) { a.chunk_id = chunk_id_dev; a.chunk_size = chunk_size_dev; a.chunk_state = chunk_state_dev; }
+  if (lex) {  // the constrained kernels, in translation units of their own
+    a.lex_begin = lex->edge_begin; a.lex_tok = lex->edge_tok; a.lex_child = lex->edge_child; a.lex_terminal = lex->terminal;
+    a.lex_nodes = lex->n_nodes; a.lex_edges = lex->n_edges; a.node_out = node_out;
+    return ctx_gates ? msocr_internal_attn_lexicon_mfma(a, (hipStream_t)stream) : msocr_internal_attn_general_lexicon(a, H, (hipStream_t)stream);
+  }
   if (!ctx_gates) return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
   return alpha_ws ? msocr_internal_attn_beam_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
 }
@@ -480,12 +489,13 @@ static int attn_beam_hoisted_impl(const float* batch_H, const float* proj_H, con
                                   const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
                                   const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
                                   void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
+                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
+                                  int32_t* node_out = nullptr) {
   if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
   if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15)))
     return MSOCR_E_ARG;
   return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
+                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
 }
 extern "C" int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                                        const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
@@ -503,6 +513,31 @@ extern "C" int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* 
   if (!alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
   return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
                                 fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
+}
+
+// Lexicon-constrained beam decode (msocr.h): the entries above with the lexicon's prefix tree (device arrays) and the node trace
+// node_out [B][steps][beam] i32; alpha_ws required.  Same workspace, same finalize / n-best / confidence steps.
+extern "C" int64_t msocr_attn_lexicon_nodes_bytes(int B, int steps, int beam) {
+  if (B <= 0 || steps <= 0 || beam <= 0) return 0;
+  return (int64_t)B * steps * beam * 4;
+}
+extern "C" int msocr_attn_beam_lexicon(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
+                                       int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                       int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                       int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream) {
+  if (!lex || !node_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
+                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
+}
+extern "C" int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                               const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                               const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                               int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
+                                               const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws,
+                                               const msocr_lexicon* lex, int32_t* node_out, void* stream) {
+  if (!lex || !node_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
+                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
 }
 
 // the four parts of a finished beam workspace (device memory, or a host copy of it), for the steps that read it back

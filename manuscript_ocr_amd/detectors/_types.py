@@ -51,6 +51,20 @@ class AltWord(CharWord):
     alternatives: List[Alternative] = Field(default_factory=list, description="distinct readings, best first")
 
 
+class LexAlternative(Alternative):
+    """An Alternative of a lexicon-constrained decode: a lexicon word, with its index."""
+
+    lexicon_index: int = Field(..., description="index of `text` in Lexicon.words")
+
+
+class LexWord(AltWord):
+    """A Word read under a lexicon, written by Pipeline when `lexicon` is set: `text` is a lexicon word and `lexicon_index` its index
+    in Lexicon.words (-1 only where the decoder's logits were not finite).  `alternatives` (LexAlternatives, lexicon words only) are
+    filled when `n_best` is also on, `chars` when `char_details` is.  As for CharWord, a default model_dump() of a Page does not change."""
+
+    lexicon_index: int = Field(..., description="index of `text` in Lexicon.words, -1 if it is none")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

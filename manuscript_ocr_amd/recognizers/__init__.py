@@ -1,3 +1,4 @@
 from ._trba import TRBA
+from ._trba.lexicon import Lexicon
 
-__all__ = ["TRBA"]
+__all__ = ["TRBA", "Lexicon"]

@@ -10,7 +10,8 @@ always exact f32), state_dict=... / config=... for in-memory weights (nothing ca
 offline), device_batch=2048 rows per launch sequence, predict(..., return_chars=True) for per-symbol
 confidence and position (from the decoder's attention weights), predict(..., n_best=n) for the beam search's n
 best final readings with their scores, score(images, texts) for the forced decode of given transcriptions: how
-well a text fits a word image and where its symbols sit.  Confidences reproduce the reference's
+well a text fits a word image and where its symbols sit, predict(..., lexicon=Lexicon(...)) for a beam search
+constrained to a closed vocabulary.  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -50,6 +51,7 @@ class _Recognition:
     beam: int
     char_details: bool = False
     graph_inst: Optional[Lease] = None  # the replayed graph instance; None = plain launches
+    lexicon: Any = None                 # the Lexicon the beam decode was constrained to; None = the open search
 
 
 def _row_ends(ids, trun, eos_id):
@@ -209,14 +211,18 @@ class TRBA:
         return bounds, metas, meta_dev
 
     def recognize_start(self, canvases_dev: torch.Tensor, mode="beam", beam_size=8, temperature=1.7, alpha=0.9, spans=None,
-                        batch_size=32, prepared=None, char_details=False):
+                        batch_size=32, prepared=None, char_details=False, lexicon=None):
         """Phase 1 — encode + decode of [N,img_h,img_w,3] u8 device canvases, enqueued on the CURRENT stream without any
         synchronisation.  Returns a handle for `recognize_finish`.  `spans`/`batch_size` (the same values `recognize_finish`
         will get) tell the beam kernel which rows share a reference chunk, so it can stop a chunk where the reference's
         loop does; without them every row runs all max_length steps (same results).  char_details: the decode also keeps its attention
-        weights (on the device) and `recognize_finish` returns per-symbol arrays; every other result is the same either way."""
+        weights (on the device) and `recognize_finish` returns per-symbol arrays; every other result is the same either way.
+        lexicon (a Lexicon built for this recogniser's charset and max_len; mode "beam"): the beam search is constrained to the
+        lexicon's words — every hypothesis carries a node of its prefix tree and may be extended only along it (DESIGN.md section
+        4.15).  Every array `recognize_finish` returns keeps its meaning; `Lexicon.find` of a row's ids gives the word's index."""
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
+        self._check_lexicon(lexicon, mode)
         N = canvases_dev.shape[0]
         if mode == "beam" and prepared is not None:
             bounds, metas, meta_dev = prepared
@@ -242,13 +248,17 @@ class TRBA:
                               torch.zeros((2 * nch,), dtype=torch.int32, device=self.device))
                     off += nrows + nch
                 res = self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
-                                      self.blank_id, chunks, want_alpha=char_details)
-                ws, fin, _lp, al = res if char_details else (*res, None)
+                                      self.blank_id, chunks, want_alpha=char_details, lexicon=lexicon)
+                if lexicon is not None:  # the constrained kernels always write the weight trace; it is kept only if asked for
+                    ws, fin, _lp, al, _nodes = res
+                    al = al if char_details else None
+                else:
+                    ws, fin, _lp, al = res if char_details else (*res, None)
                 parts.append(_Launch(ws=ws, fin=fin, alpha=al))
-        return _Recognition(parts, bounds, N, N, mode, beam_size, bool(char_details))
+        return _Recognition(parts, bounds, N, N, mode, beam_size, bool(char_details), lexicon=lexicon)
 
     def recognize_start_graph(self, pages_dev: torch.Tensor, desc_dev: torch.Tensor, spans, batch_size=32, beam_size=8,
-                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False):
+                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False, lexicon=None):
         """`recognize_start` for crops that are still descriptors on the device (ops.reading_order_crops), as ONE hipGraph replay:
         crop + ResizeAndPadA, SE-ResNet31, BiLSTMs and the beam decode of up to `device_batch` rows are captured once per
         (page tensor, row bucket) and replayed (BASELINE configs[3]: "hipGraph-captured").  The row count is rounded up to a
@@ -258,7 +268,11 @@ class TRBA:
         fall into a capture), and whenever char_details or rectified crops (Pipeline.rectify_crops: the captured graph holds the AABB
         crop kernel, not msocr_quad_crop) are asked for (those paths are not captured).  Results are bit-identical to the eager path
         (tests/test_gpu_pipeline.py).  `recognize_finish(n_best=...)` needs nothing from this route: the captured graph ends at the
-        decode, and the beam workspace the alternatives are read from is in the handle it returns."""
+        decode, and the beam workspace the alternatives are read from is in the handle it returns.  A lexicon is a ValueError here:
+        captured graphs are not provided for the lexicon-constrained decode."""
+        if lexicon is not None:
+            raise ValueError("captured graphs are not provided for the lexicon-constrained decode: use recognize_start, or a "
+                             "recogniser without use_graphs")
         M = int(desc_dev.shape[0])
         Mcap = (M + 31) // 32 * 32
         if M == 0 or Mcap > self.device_batch or ops.PROFILE is not None or char_details or rectified:
@@ -400,13 +414,13 @@ class TRBA:
         return out
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
-                           spans=None, return_logits=False, char_details=False, n_best=0):
+                           spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None):
         """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak]
-        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host."""
+        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host.  lexicon: as for `recognize_start`."""
         self._check_n_best(n_best, mode, beam_size)
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
                                                           spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
-                                                          char_details=char_details),
+                                                          char_details=char_details, lexicon=lexicon),
                                      batch_size, spans, return_logits, n_best=n_best)
 
     def texts(self, ids, trun) -> List[str]:
@@ -430,15 +444,39 @@ class TRBA:
         if n_best > beam_size:
             raise ValueError(f"n_best = {n_best} exceeds beam_size = {beam_size}: the search keeps beam_size hypotheses")
 
+    def _check_lexicon(self, lexicon, mode):
+        if lexicon is None:
+            return
+        if mode == "greedy":
+            raise ValueError("a lexicon needs mode='beam': a constrained arg-max walks into the trie's locally best branch and is not provided")
+        if lexicon.max_len != self.max_length:
+            raise ValueError(f"the lexicon was built for max_len {lexicon.max_len}, this recogniser's is {self.max_length}")
+        if lexicon.num_classes != len(self.itos):
+            raise ValueError(f"the lexicon was built for a charset of {lexicon.num_classes} tokens, this recogniser's has {len(self.itos)}")
+
+    def lexicon_indices(self, ids, lexicon) -> List[int]:
+        """Per row of ids [N, steps], `lexicon.find`: the index of the row's word in lexicon.words, -1 if it is none (a constrained
+        decode returns such a row only where its logits were not finite)."""
+        return [lexicon.find(row) for row in np.asarray(ids).tolist()]
+
     def alternatives(self, alt_ids, trun, alt_conf, alt_logp) -> List[List[Dict[str, Any]]]:
         """Per row, its readings as {"text", "confidence", "logp"} in rank order, from recognize_finish(n_best=...)'s arrays: text by
         `texts` over the rank's ids, confidence as the word's own is computed, logp the hypothesis's summed log-probability.  Entry 0
         is the word's own text and confidence and is always kept; a later rank whose text equals an earlier one of its row is
         dropped (two hypotheses can differ only in PAD tokens, or behind their EOS)."""
+        return self._alternatives(alt_ids, trun, alt_conf, alt_logp, None)
+
+    def lexicon_alternatives(self, alt_ids, trun, alt_conf, alt_logp, lexicon) -> List[List[Dict[str, Any]]]:
+        """`alternatives` for a decode constrained to `lexicon`: a later rank is kept only if its ids are a lexicon word (a slot that
+        died in the search, or never held a word, is none), and every entry also carries "lexicon_index"."""
+        return self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon)
+
+    def _alternatives(self, alt_ids, trun, alt_conf, alt_logp, lexicon):
         alt_ids = np.asarray(alt_ids)
         N, n = alt_ids.shape[:2]
         if not N or not n:
             return [[] for _ in range(N)]
+        lex_idx = self.lexicon_indices(alt_ids.reshape(N * n, -1), lexicon) if lexicon is not None else None
         texts = self.texts(alt_ids.reshape(N * n, -1), np.repeat(np.asarray(trun), n))
         cs = np.clip(np.asarray(alt_conf, dtype=np.float64), 0.0, 1.0).tolist()  # means of exp(log-softmax): within [0, 1] up to rounding
         ls = np.asarray(alt_logp, dtype=np.float64).tolist()
@@ -447,9 +485,13 @@ class TRBA:
             seen, row = set(), []
             for r in range(n):
                 t = texts[b * n + r]
+                if lex_idx is not None and r and lex_idx[b * n + r] < 0:
+                    continue
                 if t not in seen:
                     seen.add(t)
                     row.append({"text": t, "confidence": cs[b][r], "logp": ls[b][r]})
+                    if lex_idx is not None:
+                        row[-1]["lexicon_index"] = lex_idx[b * n + r]
             out.append(row)
         return out
 
@@ -579,27 +621,36 @@ class TRBA:
 
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
-                alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0) -> List[Dict[str, Any]]:
+                alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0, lexicon=None) -> List[Dict[str, Any]]:
         """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
         result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
         decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
         through transforms.FRAME_STRIDE and the resize; an estimate, not a measured glyph position).
         n_best >= 1 (keyword-only extension, mode="beam", n_best <= beam_size): every result also has "alternatives", a list of
         {"text", "confidence", "logp"}: the beam search's n_best best final hypotheses in its own order, duplicates of an earlier text
-        dropped (`alternatives`); entry 0 is the result's own text and confidence.  "chars" describes the best reading only."""
+        dropped (`alternatives`); entry 0 is the result's own text and confidence.  "chars" describes the best reading only.
+        lexicon=Lexicon(words, recognizer.stoi, recognizer.max_length) (keyword-only extension, mode="beam"): the beam search is
+        constrained to the lexicon's words.  Every result also has "lexicon_index", the index of its text in
+        lexicon.words (-1 only where the decoder's logits were not finite); "alternatives" then keeps only readings that are lexicon
+        words, each with its "lexicon_index".  A result's rank-0 "logp" is the number `score` gives that text at the same temperature."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         self._check_n_best(n_best, mode, beam_size)
+        self._check_lexicon(lexicon, mode)
         if not images_list:
             return []
         arrays = [self._load_rgb(im) for im in images_list]
         canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
-        if not return_chars and not n_best:
+        if not return_chars and not n_best and lexicon is None:
             return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
-        fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best)
+        fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best,
+                                      lexicon=lexicon)
         ids, trun, conf = fin[:3]
         results = self._results(ids, trun, conf)
+        if lexicon is not None:
+            for r, k in zip(results, self.lexicon_indices(ids, lexicon)):
+                r["lexicon_index"] = k
         if return_chars:
             prob, centre = fin[3:5]
             src_w = [a.shape[1] for a in arrays]
@@ -608,6 +659,6 @@ class TRBA:
                 r["chars"] = ch
         if n_best:
             alt_ids, _alt_prob, alt_conf, alt_logp = fin[-4:]
-            for r, al in zip(results, self.alternatives(alt_ids, trun, alt_conf, alt_logp)):
+            for r, al in zip(results, self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon)):
                 r["alternatives"] = al
         return results

@@ -155,9 +155,10 @@ class TrbaNet:
     def forced(self, batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=None):
         return self.dec.forced(batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=ctx_gates)
 
-    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, want_alpha=False):
+    def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, want_alpha=False,
+             lexicon=None):
         return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks,
-                             want_alpha=want_alpha)
+                             want_alpha=want_alpha, lexicon=lexicon)
 
     def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None):
         return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev, alpha_ws=alpha_ws)
@@ -305,14 +306,23 @@ class AttnDecoder:
         return lps, lp
 
     def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None,
-             want_alpha=False, alpha_ws=None):
+             want_alpha=False, alpha_ws=None, lexicon=None):
         """Returns (workspace, fin_step [B] i32, lp) for `beam_finalize`.  ctx_gates as for `greedy`.  Runs all `max_len` steps, or — given
         chunks = (chunk_id [B] i32, chunk_size [nchunks] i32, chunk_state [2*nchunks] i32 zeros), all on the device — only
         as many as the reference's own loop would (it breaks once every beam of the chunk is finished, model.py:215).
         want_alpha: a fourth result, the attention-weight trace [B, steps, beam, T] f32 for `beam_finalize(alpha_ws=...)` (slot-
-        indexed like the logits trace; steps the early exit skips stay unwritten); alpha_ws: a buffer of that shape to use."""
+        indexed like the logits trace; steps the early exit skips stay unwritten); alpha_ws: a buffer of that shape to use.
+        lexicon (a recognizers.Lexicon built for this charset and max_len): the search is constrained to the lexicon's words
+        (msocr_attn_beam_lexicon(_hoisted)) and the result is always (workspace, fin_step, lp, alpha trace,
+        nodes): nodes [B, steps, beam] i32, the trie node of every slot after every step (-1 = a dead slot; steps the early exit skips
+        stay unwritten).  The workspace is read by beam_finalize / beam_nbest as a plain one is.  None: nothing changes."""
         B, T, H = batch_H.shape
         steps = max_len
+        if lexicon is not None:
+            if lexicon.max_len != steps or lexicon.num_classes != self.V:
+                raise ValueError(f"the lexicon was built for max_len {lexicon.max_len} and {lexicon.num_classes} tokens, the decode has "
+                                 f"{steps} steps and {self.V} tokens")
+            want_alpha = True
         nbytes = nat.lib().msocr_attn_beam_workspace_bytes(B, steps, beam_size, self.V)
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
         fin = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -340,20 +350,28 @@ class AttnDecoder:
                 -1 if blank_id is None else blank_id, fin.data_ptr(), ws.data_ptr(),
                 chunks[0].data_ptr() if chunks else None, chunks[1].data_ptr() if chunks else None,
                 chunks[2].data_ptr() if chunks else None)
-        tail += (ops._stream(),) if aws is None else (aws.data_ptr(), ops._stream())
         L = nat.lib()
+        nodes = None
+        if lexicon is not None:  # the constrained kernels: same arguments, then the trie and the node trace
+            nodes = torch.empty((B, steps, beam_size), dtype=torch.int32, device=self.device)
+            assert nodes.numel() * 4 == L.msocr_attn_lexicon_nodes_bytes(B, steps, beam_size)
+            tail += (aws.data_ptr(), lexicon.struct(self.device), nodes.data_ptr(), ops._stream())
+        else:
+            tail += (ops._stream(),) if aws is None else (aws.data_ptr(), ops._stream())
         if hoist:  # split-operand products with the split weights, exact-f32 MFMA without them
             asw = ctypes.byref(self._asw) if self._asw is not None else None
-            fn = L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha
+            fn = L.msocr_attn_beam_lexicon_hoisted if lexicon is not None else L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha
             nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), asw, *tail), "attn_beam_hoisted")
         else:
-            fn = L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha
+            fn = L.msocr_attn_beam_lexicon if lexicon is not None else L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha
             nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
         # SURVEY.md 8d, per decode step: proj_H + batch_H (shared by the beams) + LSTMCell W_ih (ctx part + one-hot rows), W_hh,
         # generator, h2h + per row (h, c state + logits); the launch runs up to `steps` of them (chunk-level early exit)
         V, R = self.V, B * beam_size
         per_step = 4.0 * (2 * B * T * H + 4 * H * (H + V) + 4 * H * H + H * V + H * H + R * (4 * H + V))
         ops._prof_end(e, "attn_beam", (per_step, steps), (B, T, beam_size))
+        if lexicon is not None:
+            return ws, fin, lp, aws, nodes
         return (ws, fin, lp, aws) if want_alpha else (ws, fin, lp)
 
     def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None, alpha_out=None):

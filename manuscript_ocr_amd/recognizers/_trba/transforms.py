@@ -1,7 +1,7 @@
 """Host-side crop preprocessing and token decoding of the recogniser.
 
   load_charset / decode_tokens   <- reference recognizers/_trba/data/transforms.py:39-59,196-206
-  pack_targets                   <- pack_attention_targets, transforms.py:123-157 (the inputs of the forced decode)
+  pack_targets / encode_text     <- pack_attention_targets, transforms.py:123-157 (the inputs of the forced decode; the character rule)
   resize_and_pad                 <- ResizeAndPadA.apply, transforms.py:85-120 (align left / centre)
 cv2 is not a dependency: INTER_AREA / INTER_LINEAR for uint8 are implemented here from
 OpenCV's published algorithms (table-driven float area resize; 11-bit fixed-point bilinear).
@@ -36,6 +36,22 @@ def decode_tokens(ids, itos, pad_id, eos_id, blank_id=None):
     return "".join(chars)
 
 
+def encode_text(s, stoi):
+    """One transcription -> (ids, kept characters, rejected): the character rule of the reference's pack_attention_targets, shared by
+    pack_targets and Lexicon.  A character that is not in the charset, or that is <BLANK>'s, is left out of ids / kept and listed in
+    rejected as (character, reason)."""
+    BLANK = stoi.get("<BLANK>", None)
+    ids, kept, rejected = [], [], []
+    for ch in s:
+        idx = stoi.get(ch)
+        if idx is None or (BLANK is not None and idx == BLANK):
+            rejected.append((ch, "not in the charset" if idx is None else "the <BLANK> token"))
+            continue
+        ids.append(idx)
+        kept.append(ch)
+    return ids, kept, rejected
+
+
 def pack_targets(texts, stoi, max_len, strict=True):
     """Transcriptions -> the inputs of a forced decode (TRBA.score): (tok_in [N, max_len+1] int32, target [N, max_len+1] int32, trun
     [N] int32, packed_texts).  The layout is the reference's pack_attention_targets: tok_in = SOS, the ids, then PAD (what the decoder
@@ -45,7 +61,6 @@ def pack_targets(texts, stoi, max_len, strict=True):
     the ids are cut at max_len.  strict=True raises ValueError instead, naming the row and the character or the length: nothing is
     silently narrowed.  Needs no GPU."""
     PAD, SOS, EOS = stoi["<PAD>"], stoi["<SOS>"], stoi["<EOS>"]
-    BLANK = stoi.get("<BLANK>", None)
     N, T = len(texts), max_len + 1
     tok_in = np.full((N, T), PAD, dtype=np.int32)
     tok_in[:, 0] = SOS
@@ -55,15 +70,9 @@ def pack_targets(texts, stoi, max_len, strict=True):
     for i, s in enumerate(texts):
         if not isinstance(s, str):
             raise TypeError(f"texts[{i}] must be a str, got {type(s).__name__}")
-        ids, kept = [], []
-        for ch in s:
-            idx = stoi.get(ch)
-            if idx is None or (BLANK is not None and idx == BLANK):
-                if strict:
-                    raise ValueError(f"texts[{i}]: character {ch!r} is {'not in the charset' if idx is None else 'the <BLANK> token'}")
-                continue
-            ids.append(idx)
-            kept.append(ch)
+        ids, kept, rejected = encode_text(s, stoi)
+        if strict and rejected:
+            raise ValueError(f"texts[{i}]: character {rejected[0][0]!r} is {rejected[0][1]}")
         if strict and len(ids) > max_len:
             raise ValueError(f"texts[{i}]: {len(ids)} symbols, the model's max_len is {max_len}")
         L = min(len(ids), max_len)

@@ -1,5 +1,5 @@
 """Times the beam-8 decode launch (all 25 steps, no early exit) for B crops, split-operand form against exact-f32 MFMA (dev tool).
-  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest] [--forced]
+  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest] [--forced] [--lexicon N]
 --alpha: with the attention-weight output on (the _alpha entry points, into one preallocated buffer).  --repeats N: N timed repeats
 of 5 calls each per form, one line each (default 1).  --general: the general kernel (csrc/attn_general.hip) at the same shape
 instead of the matrix-core kernels (net.HOIST_CTX = False; one form, no split / exact comparison).  --greedy: the greedy decode
@@ -8,6 +8,9 @@ instead of the matrix-core kernels (net.HOIST_CTX = False; one form, no split / 
 against the greedy decode with the attention-weight output, alternating: per round 5 calls of one, then 5 of the other, --repeats
 rounds (default 1); one line per round and variant, then medians and spread (max - min) over the rounds.  With --general on the
 general kernels.
+--lexicon N: the beam decode constrained to a lexicon of N seeded random words (lengths 1..25, mean about 8, over the 191 symbols)
+against the unconstrained beam decode with the attention-weight output (msocr_attn_beam_hoisted_alpha), 26 steps, alternating as
+--forced does; medians and spread over --repeats rounds, and their ratio.  With --general on the general kernels.
 --nbest: after the decode timing of the first form, the read-out of its workspace: msocr_attn_beam_finalize + msocr_seq_confidence
 (what every word pays today) and msocr_attn_beam_nbest for n_best 1, 3 and 8, each as the mean of 20 calls after 3 warm-up calls."""
 import argparse, os, sys
@@ -26,6 +29,7 @@ ap.add_argument("--general", action="store_true")
 ap.add_argument("--greedy", action="store_true")
 ap.add_argument("--nbest", action="store_true")
 ap.add_argument("--forced", action="store_true")
+ap.add_argument("--lexicon", type=int, default=0, metavar="N")
 a = ap.parse_args()
 if a.repeats < 1:
     ap.error("--repeats must be at least 1")
@@ -64,6 +68,43 @@ if a.forced:
             print(f"{name} {k}: {ms[k][-1]:.3f} ms per call (GEMM + kernel), B={B}, 26 steps")
     for k, v in ms.items():
         print(f"{name} {k}: median {statistics.median(v):.3f} ms, spread {max(v) - min(v):.3f} ms over {len(v)} rounds")
+    sys.exit(0)
+if a.lexicon:
+    import statistics, time
+    import numpy as np
+    from manuscript_ocr_amd.recognizers import Lexicon
+    name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])
+    STEPS = 26
+    itos = ["<PAD>", "<SOS>", "<EOS>"] + [chr(0x400 + i) for i in range(191)]
+    rng = np.random.default_rng(a.lexicon)
+    lens = np.clip(rng.poisson(8, size=a.lexicon), 1, STEPS - 1)
+    t0 = time.perf_counter()
+    lex = Lexicon(["".join(itos[i] for i in rng.integers(3, 194, size=n)) for n in lens], itos, STEPS)
+    lex.to("cuda")
+    print(f"lexicon: {len(lex)} words, {lex.n_nodes} nodes, root fan-out {int(lex.edge_begin[1])}, built and uploaded in {time.perf_counter() - t0:.2f} s")
+    aws = torch.empty((B, STEPS, 8, 13), dtype=torch.float32, device="cuda")
+    variants = {"beam + alpha": lambda: dec.beam(bH, pH, STEPS, 8, 0.9, 1.7, 1, 2, None, want_alpha=True, alpha_ws=aws),
+                "lexicon": lambda: dec.beam(bH, pH, STEPS, 8, 0.9, 1.7, 1, 2, None, alpha_ws=aws, lexicon=lex)}
+    for fn in variants.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _rep in range(REPEATS):
+        for k, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 5)
+            print(f"{name} {k}: {ms[k][-1]:.3f} ms per call (GEMM + kernel), B={B}, {STEPS} steps")
+    for k, v in ms.items():
+        print(f"{name} {k}: median {statistics.median(v):.3f} ms, spread {max(v) - min(v):.3f} ms over {len(v)} rounds")
+    print(f"{name} lexicon / beam + alpha: {statistics.median(ms['lexicon']) / statistics.median(ms['beam + alpha']):.3f}")
+    fin = variants["lexicon"]()[1]
+    print(f"constrained finish steps: {int(fin.min())}..{int(fin.max())} (no chunk state: every launch runs all {STEPS} steps)")
     sys.exit(0)
 if a.greedy:
     name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])

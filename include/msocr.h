@@ -437,6 +437,48 @@ int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float* proj_H, c
 int msocr_lexicon_check_host(const int32_t* edge_begin_host, const int32_t* edge_tok_host, const int32_t* edge_child_host,
                              const uint8_t* terminal_host, int n_nodes, int n_edges, int V, int max_depth);
 
+/* Beam decode with a character n-gram language model fused in (shallow fusion), for open-vocabulary text: nothing is forbidden, every
+ * candidate of a live hypothesis gains lm_weight * log P_lm(token | its last order - 1 tokens).
+ * msocr_charlm: a dense table [n_ctx][V] f32 of natural-log probabilities in device memory, n_ctx = V^(order - 1), order 1..3.  Row ctx is
+ * the context made of a hypothesis' last order - 1 tokens, the most recent one least significant (order 3: ctx = t[-2] * V + t[-1]);
+ * positions before the start of the word count as sos_id, so every slot starts at ctx0 = sum_{i < order - 1} sos_id * V^i.  Order 1:
+ * n_ctx 1, ctx always 0.  n_ctx * V <= 2^26 elements (256 MiB; order 3 up to V 406), so every index fits 32 bits.
+ * The decode is the beam loop of msocr_attn_beam_alpha with one piece of state and one addend:
+ *   state : every beam slot carries ctx (i32).  After the top-K, with ended = done[src] | (token == eos_id):
+ *           ctx_new = ended ? ctx[src] : (ctx[src] * V + token) mod n_ctx.  ctx stays inside [0, n_ctx) and the token inside [0, V) by
+ *           construction, and no index is formed from a table value: arbitrary table contents cause no out-of-bounds read.
+ *   addend: where the candidates are formed, after the log-softmax (its log-sum-exp stays over the full temperature-scaled row), a slot
+ *           that is not finished gets logp = fma(lm_weight, table[ctx * V + v], logit - lse) for every v, eos_id included (the model's
+ *           end-of-word is fused with the LM's).  Finished slots keep the plain rule (EOS alone, log-probability 0, no LM term).
+ * Temperature, the length-penalty division, the blank column, the tie rule, done / fin_step, the chunk early exit and the workspace
+ * layout are unchanged.  The logits trace holds the MODEL's logits, not fused values: msocr_attn_beam_finalize(_alpha),
+ * msocr_attn_beam_nbest and msocr_seq_confidence read the workspace as they read a plain one's, and their log-probabilities and
+ * confidences are the model's own numbers; the slots are in fused-score order.  lm_weight is a finite f32 >= 0; with lm_weight == 0
+ * and a finite table the decode is bit-identical to msocr_attn_beam(_hoisted)_alpha (workspace, fin_step, weight trace).  A table
+ * with non-finite values is the caller's error (a NaN candidate is treated as in the plain decode).  One more output: ctx_out
+ * [B][steps][beam] i32 (msocr_attn_lm_ctx_bytes), the context of every slot after step s (steps the early exit skips stay unwritten).
+ *   msocr_attn_beam_lm         the envelope of msocr_attn_beam, general kernel (csrc/attn_general_lm.hip)
+ *   msocr_attn_beam_lm_hoisted the shapes of msocr_attn_beam_hoisted on the matrix cores (csrc/attn_lm_mfma.hip)
+ * A null lm, table, ctx_out or alpha_ws, order outside 1..3, lm->V != V, n_ctx != V^(order - 1), n_ctx * V > 2^26, lm_weight negative or
+ * not finite, sos_id outside [0, V) and shapes outside the kernel's envelope return MSOCR_E_ARG before any launch.  A language model
+ * and a lexicon in one decode are not provided. */
+typedef struct {
+  const float* table; /* device pointer */
+  int32_t order;
+  int32_t V;
+  int64_t n_ctx;
+} msocr_charlm;
+int64_t msocr_attn_lm_ctx_bytes(int B, int steps, int beam);
+int msocr_attn_beam_lm(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
+                       int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
+                       void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev,
+                       void* alpha_ws, const msocr_charlm* lm, float lm_weight, int32_t* ctx_out, void* stream);
+int msocr_attn_beam_lm_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                               const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev,
+                               float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out, void* workspace,
+                               const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws,
+                               const msocr_charlm* lm, float lm_weight, int32_t* ctx_out, void* stream);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

@@ -49,6 +49,10 @@ class LexiconArrays(ctypes.Structure):  # msocr_lexicon: device pointers
     _fields_ = [("edge_begin", c_vp), ("edge_tok", c_vp), ("edge_child", c_vp), ("terminal", c_vp), ("n_nodes", c_i32), ("n_edges", c_i32)]
 
 
+class CharLMTable(ctypes.Structure):  # msocr_charlm: table is a device pointer
+    _fields_ = [("table", c_vp), ("order", c_i32), ("V", c_i32), ("n_ctx", c_i64)]
+
+
 _SIGS = {
     "msocr_conv2d": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc), c_i32]),
@@ -115,6 +119,12 @@ _SIGS = {
     "msocr_attn_beam_lexicon_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
                                                 c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                 c_vp, ctypes.POINTER(LexiconArrays), c_vp, c_vp]),
+    "msocr_attn_lm_ctx_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "msocr_attn_beam_lm": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
+                                   c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(CharLMTable), c_f32, c_vp, c_vp]),
+    "msocr_attn_beam_lm_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
+                                           c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, ctypes.POINTER(CharLMTable), c_f32, c_vp, c_vp]),
     "msocr_lexicon_check_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),

@@ -36,6 +36,13 @@ char_details, rectify_crops, group_lines and n_best (the alternatives are then l
 punctuation: a lexicon of bare word forms forbids "слово," — the caller supplies the forms to admit.  Captured graphs are not provided
 for this route: with a `use_graphs` recogniser a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
 
+`pipeline.lm = CharLM.from_texts(texts, recognizer.stoi)` with `pipeline.lm_weight` (this package's extension, None = off by default;
+the weight's default 0.5 is a placeholder, not a tuned value): the recogniser's beam search is fused with a character n-gram language
+model, for open-vocabulary text; recognised words come back as LmWords (detectors/_types.py) whose `lm_logp`
+is the language model's unweighted log-probability of `text`; confidences stay the model's.  Combines with char_details,
+rectify_crops, group_lines and n_best (every alternative then carries its own lm_logp).  With a `use_graphs` recogniser, or with
+`lexicon` also set, a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
+
 `pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
 (an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
 
@@ -128,6 +135,8 @@ class _Batch:
     line_recs: Optional[dict]        # group_lines as it was at submit: page index -> per block its [L,6] line records; None = off
     n_best: int                      # n_best as it was at submit
     lexicon: Any                     # lexicon as it was at submit; None = the open search
+    lm: Any                          # lm as it was at submit; None = the model's own scores
+    lm_weight: float                 # lm_weight as it was at submit
     ingest_pending: Any              # the device JPEG stages' deferred verdict, read in advance_batch
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
@@ -154,6 +163,8 @@ class Pipeline:
         self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
         self.n_best = 0                    # > 0: recognised words come back as AltWords with the beam search's n best readings (user extension)
         self.lexicon = None                # a recognizers.Lexicon: the beam search is constrained to its words, LexWords come back (user extension)
+        self.lm = None                     # a recognizers.CharLM: the beam search is fused with it, LmWords come back (user extension)
+        self.lm_weight = 0.5               # weight of the language model's log-probabilities; a placeholder, not a tuned value
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -253,14 +264,17 @@ class Pipeline:
             t0 = time.time()
             n_best = self._n_best() if isinstance(self.recognizer, TRBA) else 0  # a foreign recogniser is not asked
             lexicon = self.lexicon if isinstance(self.recognizer, TRBA) else None
-            extra = {**({"n_best": n_best} if n_best else {}), **({"lexicon": lexicon} if lexicon is not None else {})}
+            lm = self.lm if isinstance(self.recognizer, TRBA) else None
+            extra = {**({"n_best": n_best} if n_best else {}), **({"lexicon": lexicon} if lexicon is not None else {}),
+                     **({"lm": lm, "lm_weight": self.lm_weight} if lm is not None else {})}
             results = self.recognizer.predict(crops, **extra)
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
             self._assign(words, [results[i] for i in range(len(words))])
-            if n_best or lexicon is not None:
+            if n_best or lexicon is not None or lm is not None:
                 self._attach_details(words, [page], alts=[results[i]["alternatives"] for i in range(len(words))] if n_best else None,
-                                     lex_idx=None if lexicon is None else [results[i]["lexicon_index"] for i in range(len(words))])
+                                     lex_idx=None if lexicon is None else [results[i]["lexicon_index"] for i in range(len(words))],
+                                     lm_logp=None if lm is None else [results[i]["lm_logp"] for i in range(len(words))])
         if line_recs is not None:
             self._split_lines(page, line_recs)
         if profile:
@@ -359,7 +373,12 @@ class Pipeline:
         batch i+1 can be enqueued before `collect_batch` of batch i and fills the device while batch i drains."""
         if not (isinstance(self.detector, EAST) and isinstance(self.recognizer, TRBA)):
             raise TypeError("submit_batch/collect_batch need this package's EAST and TRBA plugins")
-        det, n_best, lexicon = self.detector, self._n_best(), self.lexicon
+        det, n_best, lexicon, lm, lm_weight = self.detector, self._n_best(), self.lexicon, self.lm, self.lm_weight
+        if lm is not None:
+            self.recognizer._check_lm(lm, lm_weight, "beam", lexicon)
+            if self.recognizer.use_graphs:
+                raise ValueError("Pipeline.lm with a use_graphs recogniser: captured graphs are not provided for the decode fused with a "
+                                 "language model; construct the recogniser without use_graphs")
         if lexicon is not None:
             self.recognizer._check_lexicon(lexicon, "beam")
             if self.recognizer.use_graphs:
@@ -446,7 +465,7 @@ class Pipeline:
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
                 groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
-        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon,
+        return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon, lm, lm_weight,
                       ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
 
@@ -573,7 +592,8 @@ class Pipeline:
                     canv = ops.quad_crop(pages_dev, grp.qdesc_host, rec.img_h, rec.img_w, qdesc_dev=qdesc_dev)
                 else:
                     canv = ops.crop_resize_pad(pages_dev, grp.desc_host, rec.img_h, rec.img_w, desc_dev=desc_dev)
-                grp.handle = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details, lexicon=h.lexicon)
+                grp.handle = rec.recognize_start(canv, spans=spans, prepared=prepared, char_details=details, lexicon=h.lexicon,
+                                                 **({} if h.lm is None else {"lm": h.lm, "lm_weight": h.lm_weight}))
 
     def collect_batch(self, h):
         """Stages 2-3 of `predict_batch` for a handle from `submit_batch` -> list of Pages (stage 2 = `advance_batch`,
@@ -641,11 +661,13 @@ class Pipeline:
                     elif details:
                         chars = rec.chars(ids, trun, prob, centre, desc[:, 5], desc[:, 1], desc[:, 3])
                     if h.n_best:
-                        alts = (rec.alternatives(alt_ids, trun, alt_conf, alt_logp) if h.lexicon is None else
+                        alts = (rec.lm_alternatives(alt_ids, trun, alt_conf, alt_logp, h.lm) if h.lm is not None else
+                                rec.alternatives(alt_ids, trun, alt_conf, alt_logp) if h.lexicon is None else
                                 rec.lexicon_alternatives(alt_ids, trun, alt_conf, alt_logp, h.lexicon))
-                    if details or h.n_best or h.lexicon is not None:
+                    if details or h.n_best or h.lexicon is not None or h.lm is not None:
                         self._attach_details(grp.words, pages[lo:hi], chars, alts,
-                                             None if h.lexicon is None else rec.lexicon_indices(ids, h.lexicon))
+                                             None if h.lexicon is None else rec.lexicon_indices(ids, h.lexicon),
+                                             None if h.lm is None else rec.lm_logps(ids, trun, h.lm))
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
@@ -661,23 +683,27 @@ class Pipeline:
         return pages
 
     @staticmethod
-    def _attach_details(words, pages, chars=None, alts=None, lex_idx=None):
+    def _attach_details(words, pages, chars=None, alts=None, lex_idx=None, lm_logp=None):
         """Replace every recognised Word of `pages` by a CharWord carrying its symbols (`chars`, char_details), or by an AltWord that
         also carries its readings (`alts`, n_best; its `chars` stay empty without char_details).  chars[k] / alts[k] belong to
         words[k]; x is in page pixels (the recogniser mapped the attention centroid into the word's clamped crop window).  lex_idx
-        (lexicon): a LexWord instead, carrying lex_idx[k]; its alternatives are LexAlternatives."""
-        from .detectors._types import Alternative, AltWord, Char, CharWord, LexAlternative, LexWord
+        (lexicon): a LexWord instead, carrying lex_idx[k]; its alternatives are LexAlternatives.  lm_logp (lm): an LmWord instead,
+        carrying lm_logp[k]; its alternatives are LmAlternatives."""
+        from .detectors._types import Alternative, AltWord, Char, CharWord, LexAlternative, LexWord, LmAlternative, LmWord
         new = {}
         for k, word in enumerate(words):
             extra = {} if chars is None else {"chars": [Char(**d) for d in chars[k]]}
             if alts is not None:
-                extra["alternatives"] = [(Alternative if lex_idx is None else LexAlternative)(**d) for d in alts[k]]
+                alt_cls = LexAlternative if lex_idx is not None else LmAlternative if lm_logp is not None else Alternative
+                extra["alternatives"] = [alt_cls(**d) for d in alts[k]]
             if lex_idx is not None:
                 extra["lexicon_index"] = lex_idx[k]
+            if lm_logp is not None:
+                extra["lm_logp"] = lm_logp[k]
             # the [0, 1] clamp is a no-op guard for CharWord's validation: the confidence is a mean of exp(log-softmax) values, each
             # <= 1 by the kernel's arithmetic (logp <= 0), so the value equals the plain Word's and a default dump does not change
             c = word.recognition_confidence
-            new[id(word)] = (LexWord if lex_idx is not None else CharWord if alts is None else AltWord)(
+            new[id(word)] = (LexWord if lex_idx is not None else LmWord if lm_logp is not None else CharWord if alts is None else AltWord)(
                 polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
                 recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), **extra)
         for page in pages:

@@ -50,6 +50,12 @@ using namespace split_rows32;
 #ifdef MSOCR_ATTN_LEXICON
 #include "lexicon_walk.h"
 #endif
+// A fifth, through attn_lm_mfma.hip (MSOCR_ATTN_LM with MSOCR_ATTN_ALPHA), holds the beam kernel with a character n-gram language model
+// fused in (shallow fusion) and its launcher, alone: every slot carries its row of the model's dense table (a.lm_table [n_ctx][V],
+// msocr_charlm), and a live slot's candidates gain lm_weight * table[ctx][v] after the log-softmax.  The table values reach the
+// candidates through sbuf: (g), where all eight waves hold four rows each, loads its rows' table values before its two reductions, so
+// the loads' latency hides under them, and leaves the fused log-probabilities in place of the logits (which the trace already has and
+// nobody but (h) reads); (h) then reads one float per candidate, as it always did.  Lines under #ifdef, as above.
 #ifdef MSOCR_ATTN_ALPHA
 constexpr bool ALPHA = true;
 #define ATTN_ENTRY(name) name##_alpha
@@ -486,6 +492,9 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
   __shared__ int s_node[R];          // the slot's trie node; -1 = dead (it left the trie, or was filled from an all -inf round)
   __shared__ unsigned s_mask[R * 8]; // allowed tokens of every slot in this step, one bit per token (V <= 256), rebuilt every step
 #endif
+#ifdef MSOCR_ATTN_LM
+  __shared__ int s_ctx[R];  // the slot's row of the language model's table, in [0, lm_nctx)
+#endif
 
   const Lane l(threadIdx.x);
   const int tid = l.tid, lane = l.lane, wv = l.wv, half = l.half, ju = l.ju;
@@ -502,6 +511,9 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     s_done[tid] = 0;
 #ifdef MSOCR_ATTN_LEXICON
     s_node[tid] = 0;  // the root
+#endif
+#ifdef MSOCR_ATTN_LM
+    s_ctx[tid] = a.lm_ctx0;  // "all SOS"; the unused slots rb >= KB keep it, so every row's table reads stay inside the table
 #endif
   }
   if (tid < NB) s_fin[tid] = a.steps;
@@ -545,6 +557,17 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
     TSTAMP(6);
     // ---- (g) log-sum-exp per row: wave w handles rows 4w..4w+3
     for (int r = 4 * wv; r < 4 * wv + 4; ++r) {
+#ifdef MSOCR_ATTN_LM
+      // the table values of a live slot's row for this lane's tokens v = lane + 64 i (coalesced), issued before the reductions that
+      // hide their latency; 0 for a finished or unused slot, whose candidates (h) forms by the plain rule or not at all
+      float lmv[4];
+      {
+        const bool live = (r % KB8) < KB && !s_done[r];
+        const float* const trow = a.lm_table + s_ctx[r] * V;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lmv[i] = (live && lane + 64 * i < V) ? trow[lane + 64 * i] : 0.f;
+      }
+#endif
       float m = -INFINITY;
       for (int v = lane; v < V; v += 64) m = fmaxf(m, sbuf[r * H + v]);
       m = bcast63(wave_max63(m));
@@ -552,6 +575,18 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
       for (int v = lane; v < V; v += 64) sum += expf(sbuf[r * H + v] - m);
       sum = wave_sum63(sum);
       if (lane == 63) s_lse[r] = m + logf(sum);  // libm-grade exp / log: the scores of a beam search are sums of these
+#ifdef MSOCR_ATTN_LM
+      // fused log-probabilities in place of the row's logits, each lane its own tokens: (logit - lse) + lm_weight * table value, one
+      // rounding after the subtraction (weight 0 and a finite table: the subtraction's result, bit for bit)
+      {
+        const float lse = bcast63(m + logf(sum));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int v = lane + 64 * i;
+          if (v < V) sbuf[r * H + v] = fmaf(a.lm_weight, lmv[i], sbuf[r * H + v] - lse);
+        }
+      }
+#endif
 #ifdef MSOCR_ATTN_LEXICON
       // the row's allowed tokens: a live slot's edge list strided over the wave (an edge token outside [0, V) is ignored), EOS where
       // its node is terminal; a finished slot keeps the plain rule (EOS alone); a dead slot has none
@@ -599,7 +634,11 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
           const unsigned mw = s_mask[r * 8 + 2 * i + (lane >> 5)];  // the word that holds token v = lane + 64 i
 #endif
           if (v < V && rb < KB) {
+#ifdef MSOCR_ATTN_LM
+            float logp = sbuf[r * H + v];  // (g) left the fused log-probability there
+#else
             float logp = sbuf[r * H + v] - lse_r[rb];
+#endif
             if (dn_r[rb]) logp = (v == a.eos_id) ? 0.f : -INFINITY;
 #ifdef MSOCR_ATTN_LEXICON
             if (!((mw >> (lane & 31)) & 1u)) logp = -INFINITY;
@@ -684,6 +723,16 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
       if (rb < KB) nd = s_done[nb * KB8 + s_src[tid]] | (s_nxt[tid] == a.eos_id);
     }
 #endif
+#ifdef MSOCR_ATTN_LM
+    int nc = 0;  // the new slot's table row: its source's where the hypothesis is finished, else the source's shifted by the token
+    if (tid < R) {
+      const int nb = tid / KB8, rb = tid % KB8;
+      if (rb < KB) {
+        const int cs = s_ctx[nb * KB8 + s_src[tid]];  // s_src in [0, KB), s_nxt in [0, V): wi_ / V and wi_ - wr * V of wi_ < KB * V
+        nc = nd ? cs : (cs * V + s_nxt[tid]) % a.lm_nctx;  // cs * V + nxt < n_ctx * V <= 2^26
+      }
+    }
+#endif
     __syncthreads();
     if (tid < R) {
       const int nb = tid / KB8, rb = tid % KB8, b = b0 + nb;
@@ -695,11 +744,17 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
 #ifdef MSOCR_ATTN_LEXICON
           a.node_out[o] = nn;
 #endif
+#ifdef MSOCR_ATTN_LM
+          a.ctx_out[o] = nc;
+#endif
         }
         s_score[tid] = a.lp ? s_top[tid] * lp : s_top[tid];  // f32 round trip of the reference (model.py:188-192)
         s_tok[tid] = s_nxt[tid];
 #ifdef MSOCR_ATTN_LEXICON
         s_node[tid] = nn;
+#endif
+#ifdef MSOCR_ATTN_LM
+        s_ctx[tid] = nc;
 #endif
       }
       s_done[tid] = nd;
@@ -766,7 +821,7 @@ __global__ __launch_bounds__(NT, 1) void attn_beam_mfma_kernel(AttnArgs a) {
   if (tid < NB && b0 + tid < a.B) a.fin_step[b0 + tid] = s_fin[tid];
 }
 
-#ifndef MSOCR_ATTN_LEXICON
+#if !defined(MSOCR_ATTN_LEXICON) && !defined(MSOCR_ATTN_LM)
 // Greedy decode (Attention._greedy_decode, model.py:227-259): 32 CROPS per workgroup, one state row each, all `steps` steps in one
 // launch.  The rows are independent (the reference keeps every row running after its own EOS and only stops a chunk when all rows
 // emit EOS in the same step; the host derives those run lengths from the ids, recognizers/_trba/__init__.py), so a step is (a)-(f)
@@ -832,7 +887,7 @@ __global__ __launch_bounds__(NT, 1) void attn_greedy_mfma_kernel(AttnArgs a) {
     __syncthreads();
   }
 }
-#endif  // MSOCR_ATTN_LEXICON
+#endif  // MSOCR_ATTN_LEXICON, MSOCR_ATTN_LM
 
 #else  // MSOCR_ATTN_FORCED
 // Forced (teacher-forced) decode, Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0: the greedy
@@ -890,7 +945,23 @@ constexpr size_t lds_bytes() { return (size_t)(HRows<SPLITW>::FLOATS + R * H + R
 
 }  // namespace
 
-#if defined(MSOCR_ATTN_LEXICON)
+#if defined(MSOCR_ATTN_LM)
+// the one kernel of attn_lm_mfma.hip (both operand forms)
+int msocr_internal_attn_lm_mfma(const AttnArgs& a, hipStream_t s) {
+  if (!a.ctx_gates || !a.alpha_out || !a.ctx_out || !a.lm_table) return MSOCR_E_ARG;
+  if (a.lm_nctx < 1 || a.lm_ctx0 < 0 || a.lm_ctx0 >= a.lm_nctx || (long)a.lm_nctx * a.V > (1L << 26)) return MSOCR_E_ARG;
+  const size_t ldsz = lds_bytes<false>(), ldsz_split = lds_bytes<true>();
+  if (msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<false>, (int)ldsz) != MSOCR_OK ||
+      msocr_internal_lds_limit((const void*)attn_beam_mfma_kernel<true>, (int)ldsz_split) != MSOCR_OK)
+    return MSOCR_E_LAUNCH;
+  const dim3 grid((a.B + NB - 1) / NB);
+  if (a.h2h_p)
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<true>), grid, dim3(NT), ldsz_split, s, a);
+  else
+    MSOCR_LAUNCH((attn_beam_mfma_kernel<false>), grid, dim3(NT), ldsz, s, a);
+  return LAUNCH_OK();
+}
+#elif defined(MSOCR_ATTN_LEXICON)
 // the one kernel of attn_lexicon_mfma.hip (both operand forms)
 int msocr_internal_attn_lexicon_mfma(const AttnArgs& a, hipStream_t s) {
   if (!a.ctx_gates || !a.alpha_out || !a.node_out) return MSOCR_E_ARG;

@@ -39,6 +39,12 @@ constexpr bool FORCED = false;
 #ifdef MSOCR_ATTN_LEXICON
 #include "lexicon_walk.h"
 #endif
+// And so is the fusion of a character n-gram language model (shallow fusion): attn_general_lm.hip defines MSOCR_ATTN_LM and includes this
+// file, which then holds the beam instantiation alone, behind msocr_internal_attn_general_lm.  Every beam slot carries the row of the
+// model's dense table it stands at (a.lm_table [n_ctx][V], msocr_charlm; the slot's context = its last order - 1 tokens); a live slot's
+// candidates gain lm_weight * table[ctx][v] after the log-softmax, whose log-sum-exp stays over the full row; a finished slot keeps the
+// plain rule.  Nothing is forbidden.  The logits trace holds the model's logits, not fused values.  ctx stays inside [0, n_ctx) and the
+// token inside [0, V) by construction, and no index is formed from a table value.  Lines under #ifdef, as above.
 
 namespace {
 
@@ -88,6 +94,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
   __shared__ int s_node[KCAP];             // the slot's trie node; -1 = dead (it left the trie, or was filled from an all -inf round)
   __shared__ unsigned s_mask[KCAP * 16];   // allowed tokens of every slot in this step, one bit per token (V <= 512), rebuilt every step
 #endif
+#ifdef MSOCR_ATTN_LM
+  __shared__ int s_ctx[KCAP];  // the slot's row of the language model's table, in [0, lm_nctx)
+#endif
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* bH = a.batch_H + (long)b * T * H;
   const float* pH = a.proj_H + (long)b * T * H;
@@ -98,6 +107,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
     s_done[tid] = 0;
 #ifdef MSOCR_ATTN_LEXICON
     s_node[tid] = 0;  // the root
+#endif
+#ifdef MSOCR_ATTN_LM
+    s_ctx[tid] = a.lm_ctx0;  // "all SOS"
 #endif
   }
   __syncthreads();
@@ -259,6 +271,9 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 #ifdef MSOCR_ATTN_LEXICON
         if (!((s_mask[r * 16 + (v >> 5)] >> (v & 31)) & 1u)) logp = -INFINITY;
 #endif
+#ifdef MSOCR_ATTN_LM
+        if (!s_done[r]) logp = fmaf(a.lm_weight, a.lm_table[s_ctx[r] * V + v], logp);  // weight 0, finite table: logp as it was, bit for bit
+#endif
         float tot = s_score[r] + logp;
         if (a.lp) tot = tot / lp;
         slog[i] = tot;
@@ -303,6 +318,13 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 #else
       if (tid < K) nd = s_done[s_src[tid]] | (s_nxt[tid] == a.eos_id);
 #endif
+#ifdef MSOCR_ATTN_LM
+      int nc = 0;  // the new slot's table row: its source's where the hypothesis is finished, else the source's shifted by the token
+      if (tid < K) {
+        const int src = s_src[tid], nxt = s_nxt[tid];  // src in [0, K), nxt in [0, V): the top-K's wi_ / V and wi_ % V of wi_ < K * V
+        nc = nd ? s_ctx[src] : (int)(((long)s_ctx[src] * V + nxt) % a.lm_nctx);
+      }
+#endif
       __syncthreads();
       if (tid < K) {
         const long o = ((long)b * a.steps + s) * KB + tid;
@@ -314,6 +336,10 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 #ifdef MSOCR_ATTN_LEXICON
         s_node[tid] = nn;
         a.node_out[o] = nn;
+#endif
+#ifdef MSOCR_ATTN_LM
+        s_ctx[tid] = nc;
+        a.ctx_out[o] = nc;
 #endif
       }
       __syncthreads();
@@ -337,7 +363,22 @@ __global__ __launch_bounds__(NTH) void attn_general_kernel(AttnArgs a, int H) {
 
 }  // namespace
 
-#if defined(MSOCR_ATTN_LEXICON)
+#if defined(MSOCR_ATTN_LM)
+// the one kernel of attn_general_lm.hip: the beam loop with the language model's addend.  Same shapes as msocr_internal_attn_general.
+int msocr_internal_attn_general_lm(const AttnArgs& a, int H, hipStream_t s) {
+  if (!a.lm_table || !a.ctx_out || !a.alpha_out || a.lm_nctx < 1 || a.lm_ctx0 < 0 || a.lm_ctx0 >= a.lm_nctx) return MSOCR_E_ARG;
+  const int K = a.K;
+  if (H < 64 || H > 512 || H % 64 || a.V <= 0 || a.V > 512 || a.T <= 0 || a.T > 64 || a.steps <= 0 || a.steps > 64 || K < 1 || K > KCAP ||
+      K * H > 4096 || a.B <= 0 || (long)a.lm_nctx * a.V > (1L << 26))
+    return MSOCR_E_ARG;
+  const size_t ldsz = (size_t)(4 * K * H + K * a.V + K * 64) * sizeof(float);
+  auto kb = attn_general_kernel<true>;
+  if (msocr_internal_lds_limit((const void*)kb, 112 * 1024) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  if (ldsz > 112 * 1024) return MSOCR_E_ARG;
+  MSOCR_LAUNCH(kb, dim3(a.B), dim3(NTH), ldsz, s, a, H);
+  return LAUNCH_OK();
+}
+#elif defined(MSOCR_ATTN_LEXICON)
 // the one kernel of attn_general_lexicon.hip: the beam loop under the lexicon constraint.  Same shapes as msocr_internal_attn_general.
 int msocr_internal_attn_general_lexicon(const AttnArgs& a, int H, hipStream_t s) {
   if (!a.lex_begin || !a.lex_tok || !a.lex_child || !a.lex_terminal || a.lex_nodes < 1 || a.lex_edges < 0 || !a.node_out) return MSOCR_E_ARG;

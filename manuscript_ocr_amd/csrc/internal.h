@@ -88,6 +88,13 @@ struct AttnArgs {
   const uint8_t* lex_terminal;
   int lex_nodes, lex_edges;
   int32_t* node_out;
+  // beam decode with a character n-gram language model fused in (attn_general_lm.hip, attn_lm_mfma.hip; null / zero everywhere else):
+  // the dense table [lm_nctx][V] f32 of natural-log probabilities on the device (msocr_charlm), the "all SOS" row every slot starts at,
+  // the weight of the addend, and the table row of every slot after every step, [B][steps][K] i32
+  const float* lm_table;
+  int lm_nctx, lm_ctx0;
+  float lm_weight;
+  int32_t* ctx_out;
 };
 // attn_beam_mfma.hip: beam decode with 4 crops x 8 beams per workgroup on the matrix cores (H == 256, V <= 256, T <= 48, beam <= 8;
 // needs ctx_gates): split-operand products with the split weights, exact-f32 MFMA without them
@@ -112,4 +119,9 @@ __attribute__((visibility("hidden"))) int msocr_internal_attn_general_lexicon(co
 // attn_lexicon_mfma.hip: the same on the matrix cores (the beam kernel's shapes; needs ctx_gates); a.alpha_out, a.lex_* and a.node_out
 // required
 __attribute__((visibility("hidden"))) int msocr_internal_attn_lexicon_mfma(const AttnArgs& a, hipStream_t s);
+// attn_general_lm.hip: the beam decode with the language model's addend, for the shapes of attn_general.hip: a.lm_table, a.ctx_out and
+// a.alpha_out required, lm_ctx0 inside [0, lm_nctx), lm_nctx * V <= 2^26
+__attribute__((visibility("hidden"))) int msocr_internal_attn_general_lm(const AttnArgs& a, int H, hipStream_t s);
+// attn_lm_mfma.hip: the same on the matrix cores (the beam kernel's shapes; needs ctx_gates)
+__attribute__((visibility("hidden"))) int msocr_internal_attn_lm_mfma(const AttnArgs& a, hipStream_t s);
 #endif

@@ -433,18 +433,35 @@ extern "C" int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T
   return (int64_t)B * steps * beam * T * 4;
 }
 
+// what msocr_attn_beam_lm(_hoisted) add to a beam decode: the language model, the weight of its addend and the context trace
+struct LmFusion {
+  const msocr_charlm* lm;
+  float weight;
+  int32_t* ctx_out;
+};
+// whether the struct describes a table this decode can index: order 1..3, the decode's V, n_ctx = V^(order - 1), n_ctx * V <= 2^26
+static bool charlm_ok(const msocr_charlm* lm, int V) {
+  if (!lm || !lm->table || lm->order < 1 || lm->order > 3 || lm->V != V || V <= 0) return false;
+  int64_t n = 1;
+  for (int i = 1; i < lm->order; ++i) n *= V;
+  return lm->n_ctx == n && n * V <= ((int64_t)1 << 26);
+}
+
 // ctx_gates == nullptr (msocr_attn_beam): the general kernel, every shape of the envelope; otherwise (msocr_attn_beam_hoisted) the
 // matrix-core kernel, its products in the split-operand form with ws, on the exact-f32 MFMA without
 static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                           const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
                           int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
                           int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
-                          int32_t* node_out = nullptr) {
+                          int32_t* node_out = nullptr, const LmFusion* lmf = nullptr) {
   if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
   if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
   if (ctx_gates && (!attn_mfma_shape(T, H, V) || beam > 8)) return MSOCR_E_ARG;
   if (lex && (!lex->edge_begin || !lex->edge_tok || !lex->edge_child || !lex->terminal || lex->n_nodes < 1 || lex->n_edges < 0 ||
               !node_out || !alpha_ws || beam * H > 4096))
+    return MSOCR_E_ARG;
+  if (lmf && (lex || !charlm_ok(lmf->lm, V) || !lmf->ctx_out || !alpha_ws || !(lmf->weight >= 0.f) || !std::isfinite(lmf->weight) ||
+              beam * H > 4096))
     return MSOCR_E_ARG;
   AttnArgs a{};
   a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
@@ -463,6 +480,11 @@ static int attn_beam_impl(const float* batch_H, const float* proj_H, const float
     a.lex_begin = lex->edge_begin; a.lex_tok = lex->edge_tok; a.lex_child = lex->edge_child; a.lex_terminal = lex->terminal;
     a.lex_nodes = lex->n_nodes; a.lex_edges = lex->n_edges; a.node_out = node_out;
     return ctx_gates ? msocr_internal_attn_lexicon_mfma(a, (hipStream_t)stream) : msocr_internal_attn_general_lexicon(a, H, (hipStream_t)stream);
+  }
+  if (lmf) {  // the fused kernels, in translation units of their own; every slot starts at the "all SOS" row
+    a.lm_table = lmf->lm->table; a.lm_nctx = (int)lmf->lm->n_ctx; a.lm_weight = lmf->weight; a.ctx_out = lmf->ctx_out;
+    for (int i = 1; i < lmf->lm->order; ++i) a.lm_ctx0 = a.lm_ctx0 * V + sos_id;
+    return ctx_gates ? msocr_internal_attn_lm_mfma(a, (hipStream_t)stream) : msocr_internal_attn_general_lm(a, H, (hipStream_t)stream);
   }
   if (!ctx_gates) return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
   return alpha_ws ? msocr_internal_attn_beam_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
@@ -490,12 +512,12 @@ static int attn_beam_hoisted_impl(const float* batch_H, const float* proj_H, con
                                   const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
                                   void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
                                   int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
-                                  int32_t* node_out = nullptr) {
+                                  int32_t* node_out = nullptr, const LmFusion* lmf = nullptr) {
   if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
   if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15)))
     return MSOCR_E_ARG;
   return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
+                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out, lmf);
 }
 extern "C" int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
                                        const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
@@ -538,6 +560,36 @@ extern "C" int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float
   if (!lex || !node_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
   return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
                                 fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
+}
+
+// Beam decode with a character n-gram language model fused in (msocr.h): the _alpha entries above with the model's dense table (a device
+// array), the weight of its addend and the context trace ctx_out [B][steps][beam] i32; alpha_ws required.  Same workspace, same
+// finalize / n-best / confidence steps.
+extern "C" int64_t msocr_attn_lm_ctx_bytes(int B, int steps, int beam) {
+  if (B <= 0 || steps <= 0 || beam <= 0) return 0;
+  return (int64_t)B * steps * beam * 4;
+}
+extern "C" int msocr_attn_beam_lm(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
+                                  int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                  int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
+                                  int32_t* chunk_state_dev, void* alpha_ws, const msocr_charlm* lm, float lm_weight, int32_t* ctx_out,
+                                  void* stream) {
+  if (!lm || !ctx_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  const LmFusion lmf{lm, lm_weight, ctx_out};
+  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
+                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, nullptr, nullptr, &lmf);
+}
+extern "C" int msocr_attn_beam_lm_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
+                                          const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
+                                          const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
+                                          int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
+                                          const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, const msocr_charlm* lm,
+                                          float lm_weight, int32_t* ctx_out, void* stream) {
+  if (!lm || !ctx_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
+  const LmFusion lmf{lm, lm_weight, ctx_out};
+  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
+                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, nullptr, nullptr,
+                                &lmf);
 }
 
 // the four parts of a finished beam workspace (device memory, or a host copy of it), for the steps that read it back

@@ -65,6 +65,21 @@ class LexWord(AltWord):
     lexicon_index: int = Field(..., description="index of `text` in Lexicon.words, -1 if it is none")
 
 
+class LmAlternative(Alternative):
+    """An Alternative of a decode fused with a character language model, with the language model's own score of it."""
+
+    lm_logp: float = Field(..., description="unweighted language-model log-probability of `text`, its EOS included")
+
+
+class LmWord(AltWord):
+    """A Word read under a character language model, written by Pipeline when `lm` is set: `lm_logp` is the language model's
+    unweighted log-probability of `text`; `recognition_confidence` stays the recogniser's own.  `alternatives` (LmAlternatives, in
+    fused-score order) are filled when `n_best` is also on, `chars` when `char_details` is.  As for CharWord, a default model_dump()
+    of a Page does not change."""
+
+    lm_logp: float = Field(..., description="unweighted language-model log-probability of `text`, its EOS included")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

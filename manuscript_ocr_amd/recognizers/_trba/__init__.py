@@ -11,7 +11,8 @@ offline), device_batch=2048 rows per launch sequence, predict(..., return_chars=
 confidence and position (from the decoder's attention weights), predict(..., n_best=n) for the beam search's n
 best final readings with their scores, score(images, texts) for the forced decode of given transcriptions: how
 well a text fits a word image and where its symbols sit, predict(..., lexicon=Lexicon(...)) for a beam search
-constrained to a closed vocabulary.  Confidences reproduce the reference's
+constrained to a closed vocabulary, predict(..., lm=CharLM(...), lm_weight=w) for a beam search fused with a
+character n-gram language model, for open-vocabulary text.  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -52,6 +53,7 @@ class _Recognition:
     char_details: bool = False
     graph_inst: Optional[Lease] = None  # the replayed graph instance; None = plain launches
     lexicon: Any = None                 # the Lexicon the beam decode was constrained to; None = the open search
+    lm: Any = None                      # the CharLM the beam decode was fused with; None = the model's own scores
 
 
 def _row_ends(ids, trun, eos_id):
@@ -211,7 +213,7 @@ class TRBA:
         return bounds, metas, meta_dev
 
     def recognize_start(self, canvases_dev: torch.Tensor, mode="beam", beam_size=8, temperature=1.7, alpha=0.9, spans=None,
-                        batch_size=32, prepared=None, char_details=False, lexicon=None):
+                        batch_size=32, prepared=None, char_details=False, lexicon=None, lm=None, lm_weight=0.5):
         """Phase 1 — encode + decode of [N,img_h,img_w,3] u8 device canvases, enqueued on the CURRENT stream without any
         synchronisation.  Returns a handle for `recognize_finish`.  `spans`/`batch_size` (the same values `recognize_finish`
         will get) tell the beam kernel which rows share a reference chunk, so it can stop a chunk where the reference's
@@ -219,10 +221,15 @@ class TRBA:
         weights (on the device) and `recognize_finish` returns per-symbol arrays; every other result is the same either way.
         lexicon (a Lexicon built for this recogniser's charset and max_len; mode "beam"): the beam search is constrained to the
         lexicon's words — every hypothesis carries a node of its prefix tree and may be extended only along it (DESIGN.md section
-        4.15).  Every array `recognize_finish` returns keeps its meaning; `Lexicon.find` of a row's ids gives the word's index."""
+        4.15).  Every array `recognize_finish` returns keeps its meaning; `Lexicon.find` of a row's ids gives the word's index.
+        lm (a CharLM over this recogniser's charset; mode "beam"; not together with a lexicon) and lm_weight (finite, >= 0; the default
+        0.5 is a placeholder, not a tuned value): every candidate of a live hypothesis gains lm_weight * log P_lm(token | context)
+        (DESIGN.md section 4.16).  Every array `recognize_finish` returns keeps its meaning: log-probabilities and confidences are the
+        model's own numbers; `lm_logps` gives the language model's for the returned ids."""
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         self._check_lexicon(lexicon, mode)
+        self._check_lm(lm, lm_weight, mode, lexicon)
         N = canvases_dev.shape[0]
         if mode == "beam" and prepared is not None:
             bounds, metas, meta_dev = prepared
@@ -248,17 +255,18 @@ class TRBA:
                               torch.zeros((2 * nch,), dtype=torch.int32, device=self.device))
                     off += nrows + nch
                 res = self.model.beam(batch_H, proj_H, self.max_length, beam_size, alpha, temperature, self.sos_id, self.eos_id,
-                                      self.blank_id, chunks, want_alpha=char_details, lexicon=lexicon)
-                if lexicon is not None:  # the constrained kernels always write the weight trace; it is kept only if asked for
+                                      self.blank_id, chunks, want_alpha=char_details, lexicon=lexicon,
+                                      **({} if lm is None else {"lm": lm, "lm_weight": lm_weight}))
+                if lexicon is not None or lm is not None:  # these kernels always write the weight trace; it is kept only if asked for
                     ws, fin, _lp, al, _nodes = res
                     al = al if char_details else None
                 else:
                     ws, fin, _lp, al = res if char_details else (*res, None)
                 parts.append(_Launch(ws=ws, fin=fin, alpha=al))
-        return _Recognition(parts, bounds, N, N, mode, beam_size, bool(char_details), lexicon=lexicon)
+        return _Recognition(parts, bounds, N, N, mode, beam_size, bool(char_details), lexicon=lexicon, lm=lm)
 
     def recognize_start_graph(self, pages_dev: torch.Tensor, desc_dev: torch.Tensor, spans, batch_size=32, beam_size=8,
-                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False, lexicon=None):
+                              temperature=1.7, alpha=0.9, upload_stream=None, char_details=False, rectified=False, lexicon=None, lm=None):
         """`recognize_start` for crops that are still descriptors on the device (ops.reading_order_crops), as ONE hipGraph replay:
         crop + ResizeAndPadA, SE-ResNet31, BiLSTMs and the beam decode of up to `device_batch` rows are captured once per
         (page tensor, row bucket) and replayed (BASELINE configs[3]: "hipGraph-captured").  The row count is rounded up to a
@@ -269,7 +277,10 @@ class TRBA:
         crop kernel, not msocr_quad_crop) are asked for (those paths are not captured).  Results are bit-identical to the eager path
         (tests/test_gpu_pipeline.py).  `recognize_finish(n_best=...)` needs nothing from this route: the captured graph ends at the
         decode, and the beam workspace the alternatives are read from is in the handle it returns.  A lexicon is a ValueError here:
-        captured graphs are not provided for the lexicon-constrained decode."""
+        captured graphs are not provided for the lexicon-constrained decode.  So is a language model (lm)."""
+        if lm is not None:
+            raise ValueError("captured graphs are not provided for the decode fused with a language model: use recognize_start, or a "
+                             "recogniser without use_graphs")
         if lexicon is not None:
             raise ValueError("captured graphs are not provided for the lexicon-constrained decode: use recognize_start, or a "
                              "recogniser without use_graphs")
@@ -414,13 +425,13 @@ class TRBA:
         return out
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
-                           spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None):
+                           spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None, lm=None, lm_weight=0.5):
         """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak]
-        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host.  lexicon: as for `recognize_start`."""
+        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host.  lexicon, lm, lm_weight: as for `recognize_start`."""
         self._check_n_best(n_best, mode, beam_size)
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
                                                           spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
-                                                          char_details=char_details, lexicon=lexicon),
+                                                          char_details=char_details, lexicon=lexicon, lm=lm, lm_weight=lm_weight),
                                      batch_size, spans, return_logits, n_best=n_best)
 
     def texts(self, ids, trun) -> List[str]:
@@ -454,6 +465,39 @@ class TRBA:
         if lexicon.num_classes != len(self.itos):
             raise ValueError(f"the lexicon was built for a charset of {lexicon.num_classes} tokens, this recogniser's has {len(self.itos)}")
 
+    def _check_lm(self, lm, lm_weight, mode, lexicon=None):
+        if lm is None:
+            return
+        if mode == "greedy":
+            raise ValueError("a language model needs mode='beam': greedy decoding under a language model is not provided")
+        if lexicon is not None:
+            raise ValueError("a language model and a lexicon in one decode are not provided")
+        if lm.num_classes != len(self.itos) or lm.sos_id != self.sos_id:
+            raise ValueError(f"the language model was built for a charset of {lm.num_classes} tokens with sos_id {lm.sos_id}, this "
+                             f"recogniser's has {len(self.itos)} with sos_id {self.sos_id}")
+        if lm.eos_id is not None and lm.eos_id != self.eos_id:
+            raise ValueError(f"the language model's eos_id is {lm.eos_id}, this recogniser's {self.eos_id}")
+        if not (np.isfinite(lm_weight) and lm_weight >= 0):
+            raise ValueError(f"lm_weight must be finite and >= 0, got {lm_weight!r}")
+
+    def lm_logps(self, ids, trun, lm) -> List[float]:
+        """Per row of ids [N, steps], the unweighted language-model log-probability of its reading: the sum of table[ctx][id] over the
+        first t_run ids up to and including the first EOS, in float64 on the host (CharLM.logp; the table is on the host anyway and a
+        word has a few tokens, so no device gather)."""
+        V, ctx0, n_ctx, tab, eos = lm.num_classes, lm.ctx0, lm.n_ctx, lm.table, self.eos_id
+        out = []
+        for row, e in zip(np.asarray(ids).tolist(), np.asarray(trun).tolist()):
+            ctx, total = ctx0, 0.0
+            for t in row[:e]:
+                if t < 0:
+                    break
+                total += float(tab[ctx, t])
+                if t == eos:
+                    break
+                ctx = (ctx * V + t) % n_ctx
+            out.append(total)
+        return out
+
     def lexicon_indices(self, ids, lexicon) -> List[int]:
         """Per row of ids [N, steps], `lexicon.find`: the index of the row's word in lexicon.words, -1 if it is none (a constrained
         decode returns such a row only where its logits were not finite)."""
@@ -471,13 +515,19 @@ class TRBA:
         died in the search, or never held a word, is none), and every entry also carries "lexicon_index"."""
         return self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon)
 
-    def _alternatives(self, alt_ids, trun, alt_conf, alt_logp, lexicon):
+    def lm_alternatives(self, alt_ids, trun, alt_conf, alt_logp, lm) -> List[List[Dict[str, Any]]]:
+        """`alternatives` for a decode fused with `lm`: every entry also carries "lm_logp", the language model's unweighted
+        log-probability of its reading; "logp" and "confidence" stay the model's.  The ranks are in fused-score order."""
+        return self._alternatives(alt_ids, trun, alt_conf, alt_logp, None, lm)
+
+    def _alternatives(self, alt_ids, trun, alt_conf, alt_logp, lexicon, lm=None):
         alt_ids = np.asarray(alt_ids)
         N, n = alt_ids.shape[:2]
         if not N or not n:
             return [[] for _ in range(N)]
         lex_idx = self.lexicon_indices(alt_ids.reshape(N * n, -1), lexicon) if lexicon is not None else None
         texts = self.texts(alt_ids.reshape(N * n, -1), np.repeat(np.asarray(trun), n))
+        lm_lp = self.lm_logps(alt_ids.reshape(N * n, -1), np.repeat(np.asarray(trun), n), lm) if lm is not None else None
         cs = np.clip(np.asarray(alt_conf, dtype=np.float64), 0.0, 1.0).tolist()  # means of exp(log-softmax): within [0, 1] up to rounding
         ls = np.asarray(alt_logp, dtype=np.float64).tolist()
         out = []
@@ -492,6 +542,8 @@ class TRBA:
                     row.append({"text": t, "confidence": cs[b][r], "logp": ls[b][r]})
                     if lex_idx is not None:
                         row[-1]["lexicon_index"] = lex_idx[b * n + r]
+                    if lm_lp is not None:
+                        row[-1]["lm_logp"] = lm_lp[b * n + r]
             out.append(row)
         return out
 
@@ -621,7 +673,8 @@ class TRBA:
 
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
-                alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0, lexicon=None) -> List[Dict[str, Any]]:
+                alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0, lexicon=None, lm=None,
+                lm_weight: float = 0.5) -> List[Dict[str, Any]]:
         """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
         result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
         decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
@@ -632,22 +685,31 @@ class TRBA:
         lexicon=Lexicon(words, recognizer.stoi, recognizer.max_length) (keyword-only extension, mode="beam"): the beam search is
         constrained to the lexicon's words.  Every result also has "lexicon_index", the index of its text in
         lexicon.words (-1 only where the decoder's logits were not finite); "alternatives" then keeps only readings that are lexicon
-        words, each with its "lexicon_index".  A result's rank-0 "logp" is the number `score` gives that text at the same temperature."""
+        words, each with its "lexicon_index".  A result's rank-0 "logp" is the number `score` gives that text at the same temperature.
+        lm=CharLM.from_texts(texts, recognizer.stoi) with lm_weight (keyword-only extension, mode="beam", not together with a lexicon):
+        the beam search is fused with the character n-gram language model: every candidate gains lm_weight *
+        log P_lm(token | its last order - 1 tokens), nothing is forbidden.  Every result also has "lm_logp", the language model's
+        unweighted log-probability of its reading (CharLM.logp of its ids), and so has every entry of "alternatives"; "logp" and
+        "confidence" stay the model's own numbers.  The default lm_weight of 0.5 is a placeholder, not a tuned value."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         self._check_n_best(n_best, mode, beam_size)
         self._check_lexicon(lexicon, mode)
+        self._check_lm(lm, lm_weight, mode, lexicon)
         if not images_list:
             return []
         arrays = [self._load_rgb(im) for im in images_list]
         canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
-        if not return_chars and not n_best and lexicon is None:
+        if not return_chars and not n_best and lexicon is None and lm is None:
             return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
         fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best,
-                                      lexicon=lexicon)
+                                      lexicon=lexicon, lm=lm, lm_weight=lm_weight)
         ids, trun, conf = fin[:3]
         results = self._results(ids, trun, conf)
+        if lm is not None:
+            for r, v in zip(results, self.lm_logps(ids, trun, lm)):
+                r["lm_logp"] = v
         if lexicon is not None:
             for r, k in zip(results, self.lexicon_indices(ids, lexicon)):
                 r["lexicon_index"] = k
@@ -659,6 +721,6 @@ class TRBA:
                 r["chars"] = ch
         if n_best:
             alt_ids, _alt_prob, alt_conf, alt_logp = fin[-4:]
-            for r, al in zip(results, self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon)):
+            for r, al in zip(results, self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon, lm)):
                 r["alternatives"] = al
         return results

@@ -156,9 +156,9 @@ class TrbaNet:
         return self.dec.forced(batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=ctx_gates)
 
     def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, want_alpha=False,
-             lexicon=None):
+             lexicon=None, lm=None, lm_weight=0.0):
         return self.dec.beam(batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks,
-                             want_alpha=want_alpha, lexicon=lexicon)
+                             want_alpha=want_alpha, lexicon=lexicon, lm=lm, lm_weight=lm_weight)
 
     def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None):
         return self.dec.beam_finalize(ws, B, steps, beam_size, trun_dev, alpha_ws=alpha_ws)
@@ -306,7 +306,7 @@ class AttnDecoder:
         return lps, lp
 
     def beam(self, batch_H, proj_H, max_len, beam_size, alpha, temperature, sos_id, eos_id, blank_id, chunks=None, ctx_gates=None,
-             want_alpha=False, alpha_ws=None, lexicon=None):
+             want_alpha=False, alpha_ws=None, lexicon=None, lm=None, lm_weight=0.0):
         """Returns (workspace, fin_step [B] i32, lp) for `beam_finalize`.  ctx_gates as for `greedy`.  Runs all `max_len` steps, or — given
         chunks = (chunk_id [B] i32, chunk_size [nchunks] i32, chunk_state [2*nchunks] i32 zeros), all on the device — only
         as many as the reference's own loop would (it breaks once every beam of the chunk is finished, model.py:215).
@@ -315,9 +315,23 @@ class AttnDecoder:
         lexicon (a recognizers.Lexicon built for this charset and max_len): the search is constrained to the lexicon's words
         (msocr_attn_beam_lexicon(_hoisted)) and the result is always (workspace, fin_step, lp, alpha trace,
         nodes): nodes [B, steps, beam] i32, the trie node of every slot after every step (-1 = a dead slot; steps the early exit skips
-        stay unwritten).  The workspace is read by beam_finalize / beam_nbest as a plain one is.  None: nothing changes."""
+        stay unwritten).  The workspace is read by beam_finalize / beam_nbest as a plain one is.  None: nothing changes.
+        lm (a recognizers.CharLM for this charset and sos_id) with lm_weight (finite, >= 0): every candidate of a live hypothesis gains
+        lm_weight * log P_lm(token | context) (msocr_attn_beam_lm(_hoisted)) and the result is always
+        (workspace, fin_step, lp, alpha trace, ctx): ctx [B, steps, beam] i32, the language model's context of every slot after every
+        step (steps the early exit skips stay unwritten).  The workspace holds the model's own logits and is read as a plain one is.
+        Not together with a lexicon.  None: nothing changes."""
         B, T, H = batch_H.shape
         steps = max_len
+        if lm is not None:
+            if lexicon is not None:
+                raise ValueError("a language model and a lexicon in one decode are not provided")
+            if lm.num_classes != self.V or lm.sos_id != sos_id:
+                raise ValueError(f"the language model was built for {lm.num_classes} tokens with sos_id {lm.sos_id}, the decode has "
+                                 f"{self.V} tokens and sos_id {sos_id}")
+            if not (np.isfinite(lm_weight) and lm_weight >= 0):
+                raise ValueError(f"lm_weight must be finite and >= 0, got {lm_weight!r}")
+            want_alpha = True
         if lexicon is not None:
             if lexicon.max_len != steps or lexicon.num_classes != self.V:
                 raise ValueError(f"the lexicon was built for max_len {lexicon.max_len} and {lexicon.num_classes} tokens, the decode has "
@@ -356,14 +370,20 @@ class AttnDecoder:
             nodes = torch.empty((B, steps, beam_size), dtype=torch.int32, device=self.device)
             assert nodes.numel() * 4 == L.msocr_attn_lexicon_nodes_bytes(B, steps, beam_size)
             tail += (aws.data_ptr(), lexicon.struct(self.device), nodes.data_ptr(), ops._stream())
+        elif lm is not None:  # the fused kernels: same arguments, then the table, the weight and the context trace
+            ctx_trace = torch.empty((B, steps, beam_size), dtype=torch.int32, device=self.device)
+            assert ctx_trace.numel() * 4 == L.msocr_attn_lm_ctx_bytes(B, steps, beam_size)
+            tail += (aws.data_ptr(), lm.struct(self.device), float(lm_weight), ctx_trace.data_ptr(), ops._stream())
         else:
             tail += (ops._stream(),) if aws is None else (aws.data_ptr(), ops._stream())
         if hoist:  # split-operand products with the split weights, exact-f32 MFMA without them
             asw = ctypes.byref(self._asw) if self._asw is not None else None
-            fn = L.msocr_attn_beam_lexicon_hoisted if lexicon is not None else L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha
+            fn = (L.msocr_attn_beam_lexicon_hoisted if lexicon is not None else L.msocr_attn_beam_lm_hoisted if lm is not None else
+                  L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha)
             nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), asw, *tail), "attn_beam_hoisted")
         else:
-            fn = L.msocr_attn_beam_lexicon if lexicon is not None else L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha
+            fn = (L.msocr_attn_beam_lexicon if lexicon is not None else L.msocr_attn_beam_lm if lm is not None else
+                  L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha)
             nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
         # SURVEY.md 8d, per decode step: proj_H + batch_H (shared by the beams) + LSTMCell W_ih (ctx part + one-hot rows), W_hh,
         # generator, h2h + per row (h, c state + logits); the launch runs up to `steps` of them (chunk-level early exit)
@@ -372,6 +392,8 @@ class AttnDecoder:
         ops._prof_end(e, "attn_beam", (per_step, steps), (B, T, beam_size))
         if lexicon is not None:
             return ws, fin, lp, aws, nodes
+        if lm is not None:
+            return ws, fin, lp, aws, ctx_trace
         return (ws, fin, lp, aws) if want_alpha else (ws, fin, lp)
 
     def beam_finalize(self, ws, B, steps, beam_size, trun_dev, alpha_ws=None, alpha_out=None):

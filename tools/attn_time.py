@@ -1,5 +1,5 @@
 """Times the beam-8 decode launch (all 25 steps, no early exit) for B crops, split-operand form against exact-f32 MFMA (dev tool).
-  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest] [--forced] [--lexicon N]
+  python tools/attn_time.py [B] [--alpha] [--repeats N] [--general] [--greedy] [--nbest] [--forced] [--lexicon N] [--lm ORDER]
 --alpha: with the attention-weight output on (the _alpha entry points, into one preallocated buffer).  --repeats N: N timed repeats
 of 5 calls each per form, one line each (default 1).  --general: the general kernel (csrc/attn_general.hip) at the same shape
 instead of the matrix-core kernels (net.HOIST_CTX = False; one form, no split / exact comparison).  --greedy: the greedy decode
@@ -11,6 +11,9 @@ general kernels.
 --lexicon N: the beam decode constrained to a lexicon of N seeded random words (lengths 1..25, mean about 8, over the 191 symbols)
 against the unconstrained beam decode with the attention-weight output (msocr_attn_beam_hoisted_alpha), 26 steps, alternating as
 --forced does; medians and spread over --repeats rounds, and their ratio.  With --general on the general kernels.
+--lm ORDER: the beam decode fused with a character n-gram language model of that order (a seeded table: log_softmax(2 randn) per
+context over the 194 tokens, the non-emittable columns at -30; weight 0.5) against msocr_attn_beam_hoisted_alpha, 26 steps,
+alternating as --lexicon does; medians and spread over --repeats rounds, and their ratio.  With --general on the general kernels.
 --nbest: after the decode timing of the first form, the read-out of its workspace: msocr_attn_beam_finalize + msocr_seq_confidence
 (what every word pays today) and msocr_attn_beam_nbest for n_best 1, 3 and 8, each as the mean of 20 calls after 3 warm-up calls."""
 import argparse, os, sys
@@ -30,6 +33,7 @@ ap.add_argument("--greedy", action="store_true")
 ap.add_argument("--nbest", action="store_true")
 ap.add_argument("--forced", action="store_true")
 ap.add_argument("--lexicon", type=int, default=0, metavar="N")
+ap.add_argument("--lm", type=int, default=0, metavar="ORDER")
 a = ap.parse_args()
 if a.repeats < 1:
     ap.error("--repeats must be at least 1")
@@ -105,6 +109,41 @@ if a.lexicon:
     print(f"{name} lexicon / beam + alpha: {statistics.median(ms['lexicon']) / statistics.median(ms['beam + alpha']):.3f}")
     fin = variants["lexicon"]()[1]
     print(f"constrained finish steps: {int(fin.min())}..{int(fin.max())} (no chunk state: every launch runs all {STEPS} steps)")
+    sys.exit(0)
+if a.lm:
+    import statistics
+    from manuscript_ocr_amd.recognizers import CharLM
+    name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])
+    STEPS, V = 26, 194
+    g = torch.Generator().manual_seed(a.lm)
+    table = torch.log_softmax(2.0 * torch.randn(V ** (a.lm - 1), V, generator=g, dtype=torch.float64), -1)
+    table[:, [0, 1]] = -30.0
+    lm = CharLM(table.numpy(), V, a.lm, 1, 2)
+    lm.to("cuda")
+    print(f"language model: order {lm.order}, {lm.n_ctx} contexts x {V} tokens, {lm.table.nbytes / 1e6:.1f} MB on the device")
+    aws = torch.empty((B, STEPS, 8, 13), dtype=torch.float32, device="cuda")
+    variants = {"beam + alpha": lambda: dec.beam(bH, pH, STEPS, 8, 0.9, 1.7, 1, 2, None, want_alpha=True, alpha_ws=aws),
+                "lm": lambda: dec.beam(bH, pH, STEPS, 8, 0.9, 1.7, 1, 2, None, alpha_ws=aws, lm=lm, lm_weight=0.5)}
+    for fn in variants.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _rep in range(REPEATS):
+        for k, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 5)
+            print(f"{name} {k}: {ms[k][-1]:.3f} ms per call (GEMM + kernel), B={B}, {STEPS} steps")
+    for k, v in ms.items():
+        print(f"{name} {k}: median {statistics.median(v):.3f} ms, spread {max(v) - min(v):.3f} ms over {len(v)} rounds")
+    print(f"{name} lm / beam + alpha: {statistics.median(ms['lm']) / statistics.median(ms['beam + alpha']):.3f}")
+    fin = variants["lm"]()[1]
+    print(f"fused finish steps: {int(fin.min())}..{int(fin.max())} (no chunk state: every launch runs all {STEPS} steps)")
     sys.exit(0)
 if a.greedy:
     name, dec = ("general", decs["general"]) if a.general else ("split", decs["split"])

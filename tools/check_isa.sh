@@ -9,7 +9,7 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/manuscript_ocr_amd/csrc
 NOPK=$(sed -n 's/^NOPK_OBJS = //p' $C/Makefile)
-FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma attn_beam_mfma_alpha attn_forced_mfma attn_lexicon_mfma attn_general attn_general_forced attn_general_lexicon bilstm_mfma east_post east_tail reading_order quad_crop"
+FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma attn_beam_mfma_alpha attn_forced_mfma attn_lexicon_mfma attn_lm_mfma attn_general attn_general_forced attn_general_lexicon attn_general_lm bilstm_mfma east_post east_tail reading_order quad_crop"
 T=$(mktemp -d)
 trap 'rm -rf $T' EXIT
 units="$*"

@@ -479,6 +479,53 @@ int msocr_attn_beam_lm_hoisted(const float* batch_H, const float* proj_H, const 
                                const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws,
                                const msocr_charlm* lm, float lm_weight, int32_t* ctx_out, void* stream);
 
+/* Approximate dictionary lookup (csrc/lexicon_nearest.hip, csrc/edit_distance.h): for every recognised row the
+ * k words of a lexicon with the smallest Levenshtein distance (unit costs for insertion, deletion and substitution), and the same
+ * distance between pairs of rows.  Exact integers; the host twins run the same header.
+ * A row's text is what TRBA.texts decodes: the ids before the first eos_id among the first min(max(trun, 0), steps) steps (all of them
+ * if there is none), pad_id and blank_id removed; blank_id = -1 means none.  An id outside [0, V) in a row is a symbol that equals no
+ * token: it costs a substitution or deletion like any mismatch and is never an index; so is a word token outside [0, V).
+ * msocr_wordlist: the lexicon's encoded words as CSR arrays in device memory, word_begin [n_words + 1] i32 and word_tok [n_tok] i32; word
+ * i is entry i of the lexicon.  The device entry points cannot validate it: a begin is clamped into [0, n_tok] (lo <= hi) and a word
+ * longer than 63 tokens is read up to 63, so a corrupt list can give a wrong distance, not an out-of-bounds read.
+ * msocr_wordlist_check_host validates HOST copies: begins monotone from 0 to n_tok, every word 1..max_word_len (<= 63) tokens, every
+ * token in [0, V); MSOCR_OK or MSOCR_E_ARG.
+ * by_length is for a second, kernel-friendly copy of the same list: the words stored in ascending (length, index) order, position p of
+ * word_begin / word_tok holding the word whose index in the lexicon is by_length[p].  The lanes of a wave then hold words of one length
+ * in adjacent memory (no wave waits for its longest word, and a length the bound rules out is skipped by whole waves).  Results and the
+ * tie rule are in the ORIGINAL index and do not change with it: the key of a word is (distance, by_length[p]) whatever position it was
+ * met at; any order of storage is accepted.  An entry outside [0, n_words) is skipped; an array that is no permutation gives a wrong
+ * result (a word twice, or never), no out-of-bounds read.  The host twin reads it the same way.
+ *   msocr_lexicon_nearest: for row b the k words with the smallest key (distance, index), ascending; equal distances go to the smaller
+ *     index, a total order, so the result does not depend on how the lexicon is cut over workgroups.  max_distance >= 0 drops words
+ *     further away, -1 = no bound.  Unfilled ranks hold index = -1, dist = -1.  workspace: msocr_lexicon_nearest_ws_bytes(B, n_words,
+ *     k) bytes of device memory (0 when one workgroup per row covers the lexicon: then it may be NULL), 8-byte aligned, contents
+ *     irrelevant.  Two launches at most (per-slice top-k, merge), no allocation, no synchronisation, capturable.
+ *   msocr_edit_distance_pairs: row r of a against row r of b, both under the text rule: dist, and the two text lengths.
+ * Envelope: 1 <= k <= 16, 1 <= steps (steps_a, steps_b) <= 64, 1 <= V <= 512, B >= 0 (B == 0: MSOCR_OK, no launch).  Null pointers,
+ * n_words < 1, eos_id or pad_id outside [0, V), blank_id outside [-1, V), max_distance < -1 and shapes outside the envelope return
+ * MSOCR_E_ARG before any launch; msocr_lexicon_nearest_ws_bytes returns MSOCR_E_ARG for B < 0, n_words < 1 or k outside 1..16. */
+typedef struct {
+  const int32_t *word_begin, *word_tok;
+  int n_words, n_tok;
+  const int32_t* by_length; /* optional (NULL = none): [n_words] i32; the arrays then hold word by_length[p] at position p */
+} msocr_wordlist; /* device pointers (host pointers for the _host twin) */
+int64_t msocr_lexicon_nearest_ws_bytes(int B, int n_words, int k);
+int msocr_lexicon_nearest(const int32_t* ids, const int32_t* trun_dev, int B, int steps, int V, int eos_id, int pad_id, int blank_id,
+                          const msocr_wordlist* wl, int k, int max_distance, int32_t* index_out, int32_t* dist_out, void* workspace,
+                          void* stream);
+int msocr_lexicon_nearest_host(const int32_t* ids_host, const int32_t* trun_host, int B, int steps, int V, int eos_id, int pad_id,
+                               int blank_id, const msocr_wordlist* wl_host, int k, int max_distance, int32_t* index_out,
+                               int32_t* dist_out);
+int msocr_edit_distance_pairs(const int32_t* a_ids, const int32_t* a_trun, int steps_a, const int32_t* b_ids, const int32_t* b_trun,
+                              int steps_b, int B, int V, int eos_id, int pad_id, int blank_id, int32_t* dist_out, int32_t* len_a_out,
+                              int32_t* len_b_out, void* stream);
+int msocr_edit_distance_pairs_host(const int32_t* a_ids, const int32_t* a_trun, int steps_a, const int32_t* b_ids, const int32_t* b_trun,
+                                   int steps_b, int B, int V, int eos_id, int pad_id, int blank_id, int32_t* dist_out,
+                                   int32_t* len_a_out, int32_t* len_b_out);
+int msocr_wordlist_check_host(const int32_t* word_begin_host, const int32_t* word_tok_host, int n_words, int n_tok, int V,
+                              int max_word_len);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

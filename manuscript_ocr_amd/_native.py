@@ -49,6 +49,10 @@ class LexiconArrays(ctypes.Structure):  # msocr_lexicon: device pointers
     _fields_ = [("edge_begin", c_vp), ("edge_tok", c_vp), ("edge_child", c_vp), ("terminal", c_vp), ("n_nodes", c_i32), ("n_edges", c_i32)]
 
 
+class WordList(ctypes.Structure):  # msocr_wordlist: device pointers (host pointers for the host twin)
+    _fields_ = [("word_begin", c_vp), ("word_tok", c_vp), ("n_words", c_i32), ("n_tok", c_i32), ("by_length", c_vp)]
+
+
 class CharLMTable(ctypes.Structure):  # msocr_charlm: table is a device pointer
     _fields_ = [("table", c_vp), ("order", c_i32), ("V", c_i32), ("n_ctx", c_i64)]
 
@@ -126,6 +130,16 @@ _SIGS = {
                                            c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, ctypes.POINTER(CharLMTable), c_f32, c_vp, c_vp]),
     "msocr_lexicon_check_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
+    "msocr_lexicon_nearest_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "msocr_lexicon_nearest": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(WordList), c_i32, c_i32,
+                                      c_vp, c_vp, c_vp, c_vp]),
+    "msocr_lexicon_nearest_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(WordList), c_i32, c_i32,
+                                           c_vp, c_vp]),
+    "msocr_edit_distance_pairs": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                          c_vp]),
+    "msocr_edit_distance_pairs_host": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                               c_vp]),
+    "msocr_wordlist_check_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -43,6 +43,14 @@ is the language model's unweighted log-probability of `text`; confidences stay t
 rectify_crops, group_lines and n_best (every alternative then carries its own lm_logp).  With a `use_graphs` recogniser, or with
 `lexicon` also set, a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
 
+`pipeline.suggest = Lexicon(words, recognizer.stoi, recognizer.max_length)` with `pipeline.suggest_k` (1..16, default 3) and
+`pipeline.suggest_max_distance` (None = no bound) (this package's extension, None = off by default): approximate dictionary lookup
+behind the open decode (DESIGN.md section 4.17); recognised words come back as SuggestWords (SuggestLmWords when `lm` is also set;
+detectors/_types.py) whose `suggestions` are the suggest_k lexicon words nearest to `text` by Levenshtein distance, with their
+distances.  The decode is untouched: text and confidences are what the same batch gives without the switch.  Combines with
+char_details, n_best, rectify_crops, group_lines, lm and a `use_graphs` recogniser (the lookup runs behind the decode, on its device
+ids).  With `lexicon` also set a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
+
 `pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
 (an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
 
@@ -141,6 +149,7 @@ class _Batch:
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
     tm: Optional[Dict[str, float]] = None  # host seconds per stage -> Pipeline.last_profile
+    suggest: Optional[tuple] = None  # (suggest, suggest_k, suggest_max_distance) as they were at submit; None = off
 
     def replace_with(self, other):
         """Become `other` (the corrupt-JPEG resubmission) while staying the object the caller holds."""
@@ -165,6 +174,9 @@ class Pipeline:
         self.lexicon = None                # a recognizers.Lexicon: the beam search is constrained to its words, LexWords come back (user extension)
         self.lm = None                     # a recognizers.CharLM: the beam search is fused with it, LmWords come back (user extension)
         self.lm_weight = 0.5               # weight of the language model's log-probabilities; a placeholder, not a tuned value
+        self.suggest = None                # a recognizers.Lexicon: every word gets its nearest lexicon words, SuggestWords come back (user extension)
+        self.suggest_k = 3                 # suggestions per word, 1..16
+        self.suggest_max_distance = None   # drop suggestions further away than this many edits; None = no bound
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -265,16 +277,20 @@ class Pipeline:
             n_best = self._n_best() if isinstance(self.recognizer, TRBA) else 0  # a foreign recogniser is not asked
             lexicon = self.lexicon if isinstance(self.recognizer, TRBA) else None
             lm = self.lm if isinstance(self.recognizer, TRBA) else None
+            suggest = self.suggest if isinstance(self.recognizer, TRBA) else None
             extra = {**({"n_best": n_best} if n_best else {}), **({"lexicon": lexicon} if lexicon is not None else {}),
-                     **({"lm": lm, "lm_weight": self.lm_weight} if lm is not None else {})}
+                     **({"lm": lm, "lm_weight": self.lm_weight} if lm is not None else {}),
+                     **({"suggest": suggest, "suggest_k": self.suggest_k, "suggest_max_distance": self.suggest_max_distance}
+                        if suggest is not None else {})}
             results = self.recognizer.predict(crops, **extra)
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
             self._assign(words, [results[i] for i in range(len(words))])
-            if n_best or lexicon is not None or lm is not None:
+            if n_best or lexicon is not None or lm is not None or suggest is not None:
                 self._attach_details(words, [page], alts=[results[i]["alternatives"] for i in range(len(words))] if n_best else None,
                                      lex_idx=None if lexicon is None else [results[i]["lexicon_index"] for i in range(len(words))],
-                                     lm_logp=None if lm is None else [results[i]["lm_logp"] for i in range(len(words))])
+                                     lm_logp=None if lm is None else [results[i]["lm_logp"] for i in range(len(words))],
+                                     suggestions=None if suggest is None else [results[i]["suggestions"] for i in range(len(words))])
         if line_recs is not None:
             self._split_lines(page, line_recs)
         if profile:
@@ -384,6 +400,9 @@ class Pipeline:
             if self.recognizer.use_graphs:
                 raise ValueError("Pipeline.lexicon with a use_graphs recogniser: captured graphs are not provided for the lexicon-constrained "
                                  "decode; construct the recogniser without use_graphs")
+        suggest = None if self.suggest is None else (self.suggest, self.suggest_k, self.suggest_max_distance)
+        if suggest is not None:
+            self.recognizer._check_suggest(*suggest, lexicon, "beam")
         # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
         dec, ingest_pending = [None] * len(images), None
@@ -467,7 +486,8 @@ class Pipeline:
                 groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
         return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon, lm, lm_weight,
                       ingest_pending,
-                      lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False))
+                      lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False),
+                      suggest=suggest)
 
     def advance_batch(self, h):
         """Stage 2 of `predict_batch` for a handle from `submit_batch`: per group — wait for its boxes, run the host
@@ -640,7 +660,11 @@ class Pipeline:
                     details = grp.handle.char_details
                     with torch.cuda.stream(st):
                         t0 = time.perf_counter()
-                        fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0], n_best=h.n_best)
+                        fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0], n_best=h.n_best,
+                                                   **({} if h.suggest is None else {"suggest": h.suggest[0], "suggest_k": h.suggest[1],
+                                                                                    "suggest_max_distance": h.suggest[2]}))
+                        if h.suggest is not None:
+                            fin, (sug_index, sug_dist) = fin[:-2], fin[-2:]
                         if h.n_best:
                             fin, (alt_ids, _alt_prob, alt_conf, alt_logp) = fin[:-4], fin[-4:]
                         if details:
@@ -664,10 +688,11 @@ class Pipeline:
                         alts = (rec.lm_alternatives(alt_ids, trun, alt_conf, alt_logp, h.lm) if h.lm is not None else
                                 rec.alternatives(alt_ids, trun, alt_conf, alt_logp) if h.lexicon is None else
                                 rec.lexicon_alternatives(alt_ids, trun, alt_conf, alt_logp, h.lexicon))
-                    if details or h.n_best or h.lexicon is not None or h.lm is not None:
+                    if details or h.n_best or h.lexicon is not None or h.lm is not None or h.suggest is not None:
                         self._attach_details(grp.words, pages[lo:hi], chars, alts,
                                              None if h.lexicon is None else rec.lexicon_indices(ids, h.lexicon),
-                                             None if h.lm is None else rec.lm_logps(ids, trun, h.lm))
+                                             None if h.lm is None else rec.lm_logps(ids, trun, h.lm),
+                                             None if h.suggest is None else h.suggest[0].suggestions(sug_index, sug_dist))
                     tm["assign"] += time.perf_counter() - t0
                 if st is not main:
                     main.wait_stream(st)
@@ -683,13 +708,15 @@ class Pipeline:
         return pages
 
     @staticmethod
-    def _attach_details(words, pages, chars=None, alts=None, lex_idx=None, lm_logp=None):
+    def _attach_details(words, pages, chars=None, alts=None, lex_idx=None, lm_logp=None, suggestions=None):
         """Replace every recognised Word of `pages` by a CharWord carrying its symbols (`chars`, char_details), or by an AltWord that
         also carries its readings (`alts`, n_best; its `chars` stay empty without char_details).  chars[k] / alts[k] belong to
         words[k]; x is in page pixels (the recogniser mapped the attention centroid into the word's clamped crop window).  lex_idx
         (lexicon): a LexWord instead, carrying lex_idx[k]; its alternatives are LexAlternatives.  lm_logp (lm): an LmWord instead,
-        carrying lm_logp[k]; its alternatives are LmAlternatives."""
-        from .detectors._types import Alternative, AltWord, Char, CharWord, LexAlternative, LexWord, LmAlternative, LmWord
+        carrying lm_logp[k]; its alternatives are LmAlternatives.  suggestions (suggest): a SuggestWord (a SuggestLmWord with lm_logp)
+        instead, carrying suggestions[k] as Suggestions."""
+        from .detectors._types import (Alternative, AltWord, Char, CharWord, LexAlternative, LexWord, LmAlternative, LmWord, Suggestion,
+                                       SuggestLmWord, SuggestWord)
         new = {}
         for k, word in enumerate(words):
             extra = {} if chars is None else {"chars": [Char(**d) for d in chars[k]]}
@@ -700,10 +727,13 @@ class Pipeline:
                 extra["lexicon_index"] = lex_idx[k]
             if lm_logp is not None:
                 extra["lm_logp"] = lm_logp[k]
+            if suggestions is not None:
+                extra["suggestions"] = [Suggestion(**d) for d in suggestions[k]]
             # the [0, 1] clamp is a no-op guard for CharWord's validation: the confidence is a mean of exp(log-softmax) values, each
             # <= 1 by the kernel's arithmetic (logp <= 0), so the value equals the plain Word's and a default dump does not change
             c = word.recognition_confidence
-            new[id(word)] = (LexWord if lex_idx is not None else LmWord if lm_logp is not None else CharWord if alts is None else AltWord)(
+            new[id(word)] = ((SuggestLmWord if lm_logp is not None else SuggestWord) if suggestions is not None else
+                             LexWord if lex_idx is not None else LmWord if lm_logp is not None else CharWord if alts is None else AltWord)(
                 polygon=word.polygon, detection_confidence=word.detection_confidence, text=word.text,
                 recognition_confidence=None if c is None else min(max(c, 0.0), 1.0), **extra)
         for page in pages:

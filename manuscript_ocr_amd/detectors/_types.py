@@ -80,6 +80,29 @@ class LmWord(AltWord):
     lm_logp: float = Field(..., description="unweighted language-model log-probability of `text`, its EOS included")
 
 
+class Suggestion(BaseModel):
+    """One lexicon word near a recognised word (this package's extension): approximate dictionary lookup on the decoded text."""
+
+    text: str = Field(..., description="the lexicon word")
+    lexicon_index: int = Field(..., description="index of `text` in Lexicon.words")
+    distance: int = Field(..., description="Levenshtein distance (unit costs) between the recognised text and `text`", ge=0)
+
+
+class SuggestWord(AltWord):
+    """A Word with the lexicon words nearest to its text, written by Pipeline when `suggest` is set: nearest first, equal distances
+    by ascending lexicon index; distance 0 means `text` is a lexicon word, an empty list that nothing lies within the bound.  The
+    decode is the open one: `text` is the recogniser's own reading.  `alternatives` are filled when `n_best` is also on, `chars` when
+    `char_details` is.  As for CharWord, a default model_dump() of a Page does not change."""
+
+    suggestions: List[Suggestion] = Field(default_factory=list, description="nearest lexicon words, nearest first")
+
+
+class SuggestLmWord(LmWord):
+    """A SuggestWord of a decode fused with a character language model (`suggest` and `lm` both set): an LmWord with `suggestions`."""
+
+    suggestions: List[Suggestion] = Field(default_factory=list, description="nearest lexicon words, nearest first")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

@@ -1,5 +1,6 @@
 from ._trba import TRBA
 from ._trba.charlm import CharLM
 from ._trba.lexicon import Lexicon
+from ._trba.metrics import accuracy, character_error_rate, edit_distances
 
-__all__ = ["TRBA", "Lexicon", "CharLM"]
+__all__ = ["TRBA", "Lexicon", "CharLM", "edit_distances", "character_error_rate", "accuracy"]

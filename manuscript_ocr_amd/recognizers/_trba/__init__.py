@@ -12,7 +12,9 @@ confidence and position (from the decoder's attention weights; DESIGN.md section
 best final readings with their scores, score(images, texts) for the forced decode of given transcriptions: how
 well a text fits a word image and where its symbols sit, predict(..., lexicon=Lexicon(...)) for a beam search
 constrained to a closed vocabulary, predict(..., lm=CharLM(...), lm_weight=w) for a beam search fused with a
-character n-gram language model, for open-vocabulary text.  Confidences reproduce the reference's
+character n-gram language model, for open-vocabulary text, predict(..., suggest=Lexicon(...)) for the
+lexicon words nearest to every reading by edit distance, behind any decode, and evaluate(images, texts) for accuracy and CER over
+the same distance.  Confidences reproduce the reference's
 dependence on `batch_size` chunks (its decode loop stops per chunk, model.py:215,254).
 """
 import json
@@ -344,7 +346,8 @@ class TRBA:
         inst.graph.replay()
         return _Recognition([part], [(0, Mcap)], Mcap, M, "beam", beam_size, graph_inst=Lease(inst))
 
-    def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False, n_best=0):
+    def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False, n_best=0, suggest=None, suggest_k=3,
+                         suggest_max_distance=None, targets=None):
         """Phases 2-3 — derive the reference's per-chunk run lengths, back-track (beam) and reduce confidences.
 
         `spans` = [(start, count), ...] groups of rows that the reference would have passed to ONE predict() call
@@ -358,16 +361,26 @@ class TRBA:
         n_best >= 1 (beam handles, n_best <= the handle's beam width): four more host arrays behind everything else — alt_ids
         [N, n_best, steps] i32, alt_prob [N, n_best, steps] f32, alt_conf [N, n_best] f32 and alt_logp [N, n_best] f32, the search's
         n_best best final hypotheses per row in its own order (msocr_attn_beam_nbest; `alternatives` turns them into texts).  Rank 0
-        is the row's own ids and confidence."""
+        is the row's own ids and confidence.
+        suggest (a Lexicon over this recogniser's charset; not for a handle whose decode was constrained to a lexicon): two more host
+        arrays behind all others — sug_index [N, suggest_k] i32 and sug_dist [N, suggest_k] i32, per row the suggest_k lexicon words
+        nearest to its text by Levenshtein distance, nearest first, -1 / -1 where there are fewer or suggest_max_distance (None = no
+        bound) drops them (msocr_lexicon_nearest on the finalised device ids; `Lexicon.suggestions` turns
+        them into words).  With n_best they describe rank 0.  Nothing else changes with the switch.
+        targets = (target [N, steps_t] i32, t_run [N] i32), host arrays as transforms.pack_targets packs transcriptions: three more
+        host arrays behind all others — distance [N] i32, the Levenshtein distance between every row's text and its target's, and the
+        two text lengths hyp_len [N], ref_len [N] (msocr_edit_distance_pairs on the device ids; `evaluate`)."""
         try:
+            self._check_suggest(suggest, suggest_k, suggest_max_distance, handle.lexicon, handle.mode)
             if n_best < 0 or (n_best and (handle.mode != "beam" or n_best > handle.beam)):
                 raise ValueError(f"n_best = {n_best} needs a beam decode of at least that width (mode {handle.mode!r}, beam_size {handle.beam})")
-            return self._recognize_finish(handle, batch_size, spans, return_logits, int(n_best))
+            return self._recognize_finish(handle, batch_size, spans, return_logits, int(n_best),
+                                          None if suggest is None else (suggest, suggest_k, suggest_max_distance), targets)
         finally:
             if handle.graph_inst is not None:  # also on an exception: the instance must not stay leased for ever
                 handle.graph_inst.release()
 
-    def _recognize_finish(self, handle, batch_size, spans, return_logits, n_best=0):
+    def _recognize_finish(self, handle, batch_size, spans, return_logits, n_best=0, suggest=None, targets=None):
         parts, N, M_real, mode, beam_size = handle.parts, handle.N, handle.rows, handle.mode, handle.beam
         spans = spans if spans is not None else [(0, M_real)]
         steps = self.max_length + 1 if mode == "greedy" else self.max_length
@@ -385,7 +398,18 @@ class TRBA:
         self.last_rows += M_real
         trun_dev = torch.from_numpy(trun).to(self.device)
         details = handle.char_details
-        ids_out, conf_out, logit_out, det_out, alt_out = [], [], [], [], []
+        ids_out, conf_out, logit_out, det_out, alt_out, sug_out, pair_out = [], [], [], [], [], [], []
+        if targets is not None:
+            if steps > 64:
+                raise ValueError(f"the edit-distance kernel takes rows of at most 64 steps, this decode has {steps}")
+            tgt = np.ascontiguousarray(targets[0], dtype=np.int32)
+            if tgt.ndim != 2 or tgt.shape[0] != M_real or not 1 <= tgt.shape[1] <= 64 or np.shape(targets[1]) != (M_real,):
+                raise ValueError(f"targets must be ([{M_real}, 1..64], [{M_real}]) arrays")
+            tgt_full = np.full((N, tgt.shape[1]), self.eos_id, dtype=np.int32)  # a graph replay's padding rows compare against ""
+            tgt_full[:M_real] = tgt
+            ttr_full = np.zeros(N, dtype=np.int32)
+            ttr_full[:M_real] = targets[1]
+            tgt_dev, ttr_dev = torch.from_numpy(tgt_full).to(self.device), torch.from_numpy(ttr_full).to(self.device)
         for k, (s, hi) in enumerate(handle.bounds):
             B = hi - s
             tr = trun_dev[s:s + B]
@@ -400,6 +424,17 @@ class TRBA:
             nat.check(nat.lib().msocr_seq_confidence(lg.data_ptr(), ids.data_ptr(), tr.data_ptr(), B, self.model.V, steps, conf.data_ptr(),
                                                      ops._stream()), "seq_confidence")
             ids_out.append(ids), conf_out.append(conf)
+            if suggest is not None:  # on the device ids, before they cross PCIe
+                sug_out.append(suggest[0].nearest_device(ids, tr, suggest[1], suggest[2]))
+            if targets is not None:
+                po = torch.empty((3, B), dtype=torch.int32, device=self.device)
+                ids_c = ids.contiguous()
+                nat.check(nat.lib().msocr_edit_distance_pairs(ids_c.data_ptr(), tr.data_ptr(), steps, tgt_dev[s:s + B].data_ptr(),
+                                                              ttr_dev[s:s + B].data_ptr(), tgt_dev.shape[1], B, self.model.V, self.eos_id,
+                                                              self.pad_id, -1 if self.blank_id is None else self.blank_id,
+                                                              po[0].data_ptr(), po[1].data_ptr(), po[2].data_ptr(), ops._stream()),
+                          "edit_distance_pairs")
+                pair_out.append(po)
             if details:
                 prob = torch.empty((B, steps), dtype=torch.float32, device=self.device)
                 centre = torch.empty((B, steps), dtype=torch.float32, device=self.device)
@@ -422,17 +457,25 @@ class TRBA:
             out += tuple(torch.cat([d[i] for d in det_out]).cpu().numpy()[:M_real] for i in range(3))
         if n_best:
             out += tuple(torch.cat([a[i] for a in alt_out]).cpu().numpy()[:M_real] for i in range(4))
+        if suggest is not None:
+            out += tuple(torch.cat([g[i] for g in sug_out]).cpu().numpy()[:M_real] for i in range(2))
+        if targets is not None:
+            out += tuple(torch.cat([g[i] for g in pair_out]).cpu().numpy()[:M_real] for i in range(3))
         return out
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
-                           spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None, lm=None, lm_weight=0.5):
+                           spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None, lm=None, lm_weight=0.5,
+                           suggest=None, suggest_k=3, suggest_max_distance=None):
         """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak]
-        [, alt_ids, alt_prob, alt_conf, alt_logp]) on host.  lexicon, lm, lm_weight: as for `recognize_start`."""
+        [, alt_ids, alt_prob, alt_conf, alt_logp][, sug_index, sug_dist]) on host.  lexicon, lm, lm_weight: as for `recognize_start`;
+        suggest, suggest_k, suggest_max_distance: as for `recognize_finish`."""
         self._check_n_best(n_best, mode, beam_size)
+        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode)
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
                                                           spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
                                                           char_details=char_details, lexicon=lexicon, lm=lm, lm_weight=lm_weight),
-                                     batch_size, spans, return_logits, n_best=n_best)
+                                     batch_size, spans, return_logits, n_best=n_best, suggest=suggest, suggest_k=suggest_k,
+                                     suggest_max_distance=suggest_max_distance)
 
     def texts(self, ids, trun) -> List[str]:
         """decode_tokens (transforms.py:196-206) over the first t_run ids of every row, vectorised: the text ends at the
@@ -464,6 +507,19 @@ class TRBA:
             raise ValueError(f"the lexicon was built for max_len {lexicon.max_len}, this recogniser's is {self.max_length}")
         if lexicon.num_classes != len(self.itos):
             raise ValueError(f"the lexicon was built for a charset of {lexicon.num_classes} tokens, this recogniser's has {len(self.itos)}")
+
+    def _check_suggest(self, suggest, suggest_k, suggest_max_distance, lexicon=None, mode="beam"):
+        if suggest is None:
+            return
+        if lexicon is not None:
+            raise ValueError("suggest together with a lexicon is not provided: a constrained decode's word is in its lexicon, at distance 0")
+        if suggest.num_classes != len(self.itos):
+            raise ValueError(f"the suggest lexicon was built for a charset of {suggest.num_classes} tokens, this recogniser's has {len(self.itos)}")
+        suggest._check_k_bound(suggest_k, suggest_max_distance)
+        steps = self.max_length + 1 if mode == "greedy" else self.max_length
+        if steps > 64:
+            raise ValueError(f"the nearest-word lookup takes rows of at most 64 steps, this decode has {steps}")
+        suggest._check_wordlist()
 
     def _check_lm(self, lm, lm_weight, mode, lexicon=None):
         if lm is None:
@@ -671,10 +727,50 @@ class TRBA:
             k += len(c)
         return out
 
+    def evaluate(self, images, texts, batch_size: int = 32, *, strict: bool = True, **predict_kwargs) -> Dict[str, Any]:
+        """Recognise `images` and compare with their transcriptions `texts` (one str per image) by the reference's evaluation
+        measures (its trba_metrics.py: CER = Levenshtein / len(reference) per sample, accuracy = exact matches), with the distances
+        computed on the device from the decode's ids (msocr_edit_distance_pairs).  The texts are packed as
+        `score` packs them (strict=True: a character outside the charset or a text longer than max_len raises ValueError; False drops
+        and truncates).  predict_kwargs: mode, beam_size, temperature, alpha, lm, lm_weight, lexicon, as for `predict`.
+        -> {"n", "accuracy", "cer_mean" (the mean of the per-sample CERs; a sample with an empty reference counts inf if its text is
+        not empty, else 0), "cer_micro" (sum of distances / sum of reference lengths), "distances" [n] i32, "ref_lengths" [n] i32,
+        "texts" (the recognised strings)}.  Word error rate is not provided (single-word crops: 1 - accuracy)."""
+        images_list = images if isinstance(images, list) else [images]
+        texts_list = [texts] if isinstance(texts, str) else list(texts)
+        if len(texts_list) != len(images_list):
+            raise ValueError(f"{len(images_list)} images but {len(texts_list)} texts")
+        unknown = set(predict_kwargs) - {"mode", "beam_size", "temperature", "alpha", "lm", "lm_weight", "lexicon"}
+        if unknown:
+            raise TypeError(f"evaluate() got unexpected keyword arguments {sorted(unknown)}")
+        if not images_list:
+            return {"n": 0, "accuracy": 0.0, "cer_mean": 0.0, "cer_micro": 0.0, "distances": np.zeros(0, np.int32),
+                    "ref_lengths": np.zeros(0, np.int32), "texts": []}
+        _tok_in, target, ttrun, packed = pack_targets(texts_list, self.stoi, self.max_length, strict=strict)
+        mode = predict_kwargs.get("mode", "beam")
+        if mode not in ("greedy", "beam"):
+            raise ValueError(f"Unknown mode: {mode}")
+        arrays = [self._load_rgb(im) for im in images_list]
+        canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
+        kw = {k: predict_kwargs[k] for k in ("beam_size", "temperature", "alpha", "lexicon", "lm", "lm_weight") if k in predict_kwargs}
+        n = len(images_list)
+        handle = self.recognize_start(canv, mode, spans=[(0, n)], batch_size=batch_size, **kw)
+        fin = self.recognize_finish(handle, batch_size, None, targets=(target, ttrun))
+        ids, trun = fin[:2]
+        dist, _hyp_len, ref_len = fin[-3:]
+        hyp = self.texts(ids, trun)
+        d, L = dist.astype(np.float64), ref_len.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cer = np.where(L > 0, d / np.maximum(L, 1), np.where(d > 0, np.inf, 0.0))
+        total = float(L.sum())
+        micro = float(d.sum()) / total if total > 0 else (float("inf") if d.sum() > 0 else 0.0)
+        return {"n": n, "accuracy": float(np.mean(dist == 0)), "cer_mean": float(cer.mean()), "cer_micro": micro, "distances": dist,
+                "ref_lengths": ref_len, "texts": hyp}
+
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
                 alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0, lexicon=None, lm=None,
-                lm_weight: float = 0.5) -> List[Dict[str, Any]]:
+                lm_weight: float = 0.5, suggest=None, suggest_k: int = 3, suggest_max_distance=None) -> List[Dict[str, Any]]:
         """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
         result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
         decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
@@ -690,21 +786,30 @@ class TRBA:
         the beam search is fused with the character n-gram language model: every candidate gains lm_weight *
         log P_lm(token | its last order - 1 tokens), nothing is forbidden.  Every result also has "lm_logp", the language model's
         unweighted log-probability of its reading (CharLM.logp of its ids), and so has every entry of "alternatives"; "logp" and
-        "confidence" stay the model's own numbers.  The default lm_weight of 0.5 is a placeholder, not a tuned value."""
+        "confidence" stay the model's own numbers.  The default lm_weight of 0.5 is a placeholder, not a tuned value.
+        suggest=Lexicon(...) with suggest_k (1..16) and suggest_max_distance (None = no bound) (keyword-only extension, any mode, not
+        together with `lexicon`): every result also has "suggestions", a list of {"text", "lexicon_index", "distance"}: the
+        suggest_k words of the lexicon nearest to "text" by Levenshtein distance, nearest first, ties by ascending index (DESIGN.md
+        section 4.17).  Distance 0 means "text" is a lexicon word; an empty list means nothing lies within the bound.  The decode
+        itself is untouched: every other field is what the same call without `suggest` returns."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         self._check_n_best(n_best, mode, beam_size)
         self._check_lexicon(lexicon, mode)
         self._check_lm(lm, lm_weight, mode, lexicon)
+        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode)
         if not images_list:
             return []
         arrays = [self._load_rgb(im) for im in images_list]
         canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
-        if not return_chars and not n_best and lexicon is None and lm is None:
+        if not return_chars and not n_best and lexicon is None and lm is None and suggest is None:
             return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
         fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best,
-                                      lexicon=lexicon, lm=lm, lm_weight=lm_weight)
+                                      lexicon=lexicon, lm=lm, lm_weight=lm_weight, suggest=suggest, suggest_k=suggest_k,
+                                      suggest_max_distance=suggest_max_distance)
+        if suggest is not None:
+            fin, sug = fin[:-2], suggest.suggestions(*fin[-2:])
         ids, trun, conf = fin[:3]
         results = self._results(ids, trun, conf)
         if lm is not None:
@@ -723,4 +828,7 @@ class TRBA:
             alt_ids, _alt_prob, alt_conf, alt_logp = fin[-4:]
             for r, al in zip(results, self._alternatives(alt_ids, trun, alt_conf, alt_logp, lexicon, lm)):
                 r["alternatives"] = al
+        if suggest is not None:
+            for r, sg in zip(results, sug):
+                r["suggestions"] = sg
         return results

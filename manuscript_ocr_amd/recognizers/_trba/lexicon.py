@@ -5,6 +5,10 @@ target by), builds the trie as CSR arrays in breadth-first node order, has them 
 them per device.  The kernels (csrc/attn_general_lexicon.hip, csrc/attn_lexicon_mfma.hip) read edge_begin / edge_tok / edge_child /
 terminal; word_of_node stays on the host and turns a decoded word back into its index.  No minimisation to a DAWG: a node stands for
 one prefix, which is what word_of_node relies on.
+
+The encodings are also kept as a CSR word list (word_begin, word_tok) for the nearest-word lookup:
+`nearest` / `nearest_texts` give, for rows of ids or strings, the k words with the smallest Levenshtein distance and the distances,
+through msocr_lexicon_nearest on a device or its host twin without one; msocr_wordlist_check_host validates the list once.
 """
 import ctypes
 
@@ -65,12 +69,21 @@ class Lexicon:
         if not kept_words:
             raise ValueError("the lexicon is empty")
         self.words = kept_words
+        self._stoi = stoi
+        self.pad_id = stoi["<PAD>"]
+        self.blank_id = stoi.get("<BLANK>", -1)
+        # the encodings as a CSR word list beside the trie, for the nearest-word lookup: word i = words[i]
+        self.word_begin = np.zeros(len(encoded) + 1, dtype=np.int32)
+        np.cumsum([len(e) for e in encoded], out=self.word_begin[1:])
+        self.word_tok = np.fromiter((t for e in encoded for t in e), dtype=np.int32, count=int(self.word_begin[-1]))
         self._build(encoded)
         rc = nat.lib().msocr_lexicon_check_host(self.edge_begin.ctypes.data, self.edge_tok.ctypes.data, self.edge_child.ctypes.data,
                                                 self.terminal.ctypes.data, self.n_nodes, self.n_edges, self.num_classes, self.max_len - 1)
         if rc != 0:
             raise RuntimeError(f"msocr_lexicon_check_host refused the trie this class built (code {rc})")
         self._device = {}
+        self._wordlist = {}
+        self._wordlist_ok = False
 
     def _build(self, encoded):
         # insertion-order trie as a list of dicts, then a breadth-first renumbering with every node's edges sorted by token
@@ -145,3 +158,153 @@ class Lexicon:
 
     def struct(self, device):
         return ctypes.byref(self.to(device)[4])
+
+    # ------------------------------------------------------------------------------------- nearest words
+    def _check_wordlist(self):
+        """msocr_wordlist_check_host over the host arrays, once; the lookup's envelope (charset <= 512 tokens, words <= 63) on the way."""
+        if self._wordlist_ok:
+            return
+        if self.num_classes > 512 or self.max_len - 1 > 63:
+            raise ValueError(f"the nearest-word lookup takes charsets of at most 512 tokens and words of at most 63 symbols; this "
+                             f"lexicon has {self.num_classes} tokens and max_len {self.max_len}")
+        rc = nat.lib().msocr_wordlist_check_host(self.word_begin.ctypes.data, self.word_tok.ctypes.data, len(self.words),
+                                                 len(self.word_tok), self.num_classes, self.max_len - 1)
+        if rc != 0:
+            raise RuntimeError(f"msocr_wordlist_check_host refused the word list this class built (code {rc})")
+        self._wordlist_ok = True
+
+    def wordlist(self, device):
+        """The word list on `device` and the msocr_wordlist struct that points at it, cached per device: (word_begin, word_tok,
+        struct[, by_length]).  The device copy is stored in ascending (length, index) order with by_length, the word index of every
+        position, so that a wave's lanes hold words of one length in adjacent memory; results are in the original index either way.
+        device None: the host arrays themselves, in the original order (for the host twin)."""
+        if device is None:
+            key = None
+        else:
+            import torch
+            key = torch.device(device)
+            if key.type == "cuda" and key.index is None:
+                key = torch.device("cuda", torch.cuda.current_device())
+        if key not in self._wordlist:
+            self._check_wordlist()
+            wl = nat.WordList()
+            if key is None:
+                ts = (self.word_begin, self.word_tok)
+                wl.word_begin, wl.word_tok = self.word_begin.ctypes.data, self.word_tok.ctypes.data
+            else:
+                import torch
+                ts = tuple(torch.from_numpy(a).to(key) for a in self.sorted_wordlist())
+                wl.word_begin, wl.word_tok, wl.by_length = (t.data_ptr() for t in ts)
+            wl.n_words, wl.n_tok = len(self.words), len(self.word_tok)
+            self._wordlist[key] = (ts[0], ts[1], wl) + tuple(ts[2:])  # the struct third; by_length kept alive behind it
+        return self._wordlist[key]
+
+    def sorted_wordlist(self):
+        """(word_begin, word_tok, by_length) of the list stored in ascending (length, index) order: position p holds word by_length[p]."""
+        lens = np.diff(self.word_begin)
+        by_length = np.argsort(lens, kind="stable").astype(np.int32)
+        begin = np.zeros(len(lens) + 1, dtype=np.int32)
+        np.cumsum(lens[by_length], out=begin[1:])
+        src = np.repeat(self.word_begin[:-1][by_length] - begin[:-1], lens[by_length]) + np.arange(len(self.word_tok), dtype=np.int32)
+        return begin, np.ascontiguousarray(self.word_tok[src]), by_length
+
+    @staticmethod
+    def _check_k_bound(k, max_distance):
+        if not 1 <= int(k) <= 16:
+            raise ValueError(f"k must be between 1 and 16, got {k}")
+        if max_distance is not None and int(max_distance) < 0:
+            raise ValueError(f"max_distance must not be negative, got {max_distance}")
+        return int(k), -1 if max_distance is None else int(max_distance)
+
+    def nearest_device(self, ids_dev, trun_dev, k=3, max_distance=None):
+        """msocr_lexicon_nearest on the current stream over ids [N, steps] / t_run [N] int32 tensors on one device, without any
+        synchronisation -> (index [N, k], distance [N, k]) int32 tensors on that device."""
+        import torch
+        from ... import ops
+        k, bound = self._check_k_bound(k, max_distance)
+        N, steps = (int(v) for v in ids_dev.shape)
+        if not 1 <= steps <= 64:
+            raise ValueError(f"rows of 1 to 64 steps, got {steps}")
+        dev = ids_dev.device
+        wl = self.wordlist(dev)[2]
+        index = torch.empty((N, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((N, k), dtype=torch.int32, device=dev)
+        if N == 0:
+            return index, dist
+        ids_dev, trun_dev = ids_dev.contiguous(), trun_dev.contiguous()
+        ws = torch.empty((max(int(nat.lib().msocr_lexicon_nearest_ws_bytes(N, len(self.words), k)), 8),), dtype=torch.uint8, device=dev)
+        nat.check(nat.lib().msocr_lexicon_nearest(ids_dev.data_ptr(), trun_dev.data_ptr(), N, steps, self.num_classes, self.eos_id,
+                                                  self.pad_id, self.blank_id, ctypes.byref(wl), k, bound, index.data_ptr(),
+                                                  dist.data_ptr(), ws.data_ptr(), ops._stream()), "lexicon_nearest")
+        return index, dist
+
+    def nearest(self, ids, t_run=None, k=3, max_distance=None, device=None):
+        """For every row of ids [N, steps] (a host array or a device tensor of token ids, steps <= 64), the k lexicon words with the
+        smallest Levenshtein distance to the row's text (what TRBA.texts decodes: up to the first EOS among the first t_run ids, PAD
+        and BLANK removed; t_run None = all steps) -> host arrays (index [N, k] int32 into `words`, distance [N, k] int32), nearest
+        first, equal distances by ascending index.  max_distance: words further away are dropped (None = no bound); unfilled ranks
+        hold -1, -1.  device None: the host twin (no GPU needed); otherwise msocr_lexicon_nearest on that device."""
+        k, bound = self._check_k_bound(k, max_distance)
+        is_tensor = hasattr(ids, "data_ptr")
+        if device is None and not is_tensor:
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            if ids.ndim != 2 or not 1 <= ids.shape[1] <= 64:
+                raise ValueError(f"ids must be [N, steps] with 1 <= steps <= 64, got shape {ids.shape}")
+            N, steps = ids.shape
+            trun = np.full(N, steps, dtype=np.int32) if t_run is None else np.ascontiguousarray(t_run, dtype=np.int32)
+            if trun.shape != (N,):
+                raise ValueError(f"t_run must be [{N}]")
+            index, dist = np.empty((N, k), dtype=np.int32), np.empty((N, k), dtype=np.int32)
+            wl = self.wordlist(None)[2]
+            nat.check(nat.lib().msocr_lexicon_nearest_host(ids.ctypes.data, trun.ctypes.data, N, steps, self.num_classes, self.eos_id,
+                                                           self.pad_id, self.blank_id, ctypes.byref(wl), k, bound, index.ctypes.data,
+                                                           dist.ctypes.data), "lexicon_nearest_host")
+            return index, dist
+        import torch
+        dev = ids.device if device is None else torch.device(device)
+        ids_dev = ids.to(dev, torch.int32) if is_tensor else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
+        if ids_dev.ndim != 2:
+            raise ValueError(f"ids must be [N, steps], got shape {tuple(ids_dev.shape)}")
+        N, steps = ids_dev.shape
+        if t_run is None:
+            trun_dev = torch.full((N,), steps, dtype=torch.int32, device=dev)
+        elif hasattr(t_run, "data_ptr"):
+            trun_dev = t_run.to(dev, torch.int32)
+        else:
+            trun_dev = torch.from_numpy(np.ascontiguousarray(t_run, dtype=np.int32)).to(dev)
+        if tuple(trun_dev.shape) != (N,):
+            raise ValueError(f"t_run must be [{N}]")
+        with torch.cuda.device(dev):
+            index, dist = self.nearest_device(ids_dev, trun_dev, k, bound if bound >= 0 else None)
+            return index.cpu().numpy(), dist.cpu().numpy()
+
+    def encode_rows(self, texts):
+        """Strings -> (ids [N, steps] int32, t_run [N] int32) for `nearest`: encode_text's ids, except that a character outside the
+        charset (or <BLANK>'s) becomes -1, an id that matches no lexicon token — an error of the reading, not of the call.  A text
+        longer than 64 symbols is a ValueError."""
+        rows = []
+        for t in texts:
+            if not isinstance(t, str):
+                raise TypeError(f"texts must be str, got {type(t).__name__}")
+            row = [self._stoi.get(ch, -1) for ch in t]
+            row = [-1 if v in (self.blank_id, self.pad_id, self.eos_id) else v for v in row]
+            if len(row) > 64:
+                raise ValueError(f"text {t!r}: {len(row)} symbols, the lookup takes at most 64")
+            rows.append(row)
+        steps = max([len(r) for r in rows] + [1])
+        ids = np.full((len(rows), steps), self.eos_id, dtype=np.int32)
+        for i, r in enumerate(rows):
+            ids[i, :len(r)] = r
+        return ids, np.array([len(r) for r in rows], dtype=np.int32)
+
+    def nearest_texts(self, texts, k=3, max_distance=None, device=None):
+        """`nearest` for strings (encode_rows) -> (index [N, k], distance [N, k])."""
+        ids, trun = self.encode_rows(list(texts))
+        return self.nearest(ids, trun, k, max_distance, device)
+
+    def suggestions(self, index, distance):
+        """(index, distance) rows of `nearest` -> per row a list of {"text", "lexicon_index", "distance"}, nearest first; unfilled
+        ranks are left out."""
+        words = self.words
+        return [[{"text": words[i], "lexicon_index": i, "distance": d} for i, d in zip(ri, rd) if i >= 0]
+                for ri, rd in zip(np.asarray(index).tolist(), np.asarray(distance).tolist())]

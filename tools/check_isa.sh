@@ -4,12 +4,12 @@
 # Expected: no such form anywhere.  Then the footprint of every kernel of the convolution / GEMM units and of the recurrent
 # matrix-core units (registers, spills, scratch, static LDS, instruction counts per class): the table a refactor of conv_common.h /
 # split_mma.h / split_rows32.h is compared on, before and after (profiles/conv_kernel_footprint.txt, recorded before the buffer_load
-# column existed, profiles/recurrent_kernel_footprint.txt, and for the page post-processing units profiles/post_kernel_footprint.txt).   bash tools/check_isa.sh [unit ...]   (CPU only, about a minute;
+# column existed, profiles/recurrent_kernel_footprint.txt, and for the page post-processing units profiles/post_kernel_footprint.txt, and for the nearest-word lookup profiles/lexicon_nearest.txt).   bash tools/check_isa.sh [unit ...]   (CPU only, about a minute;
 # units default to all)
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/manuscript_ocr_amd/csrc
 NOPK=$(sed -n 's/^NOPK_OBJS = //p' $C/Makefile)
-FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma attn_beam_mfma_alpha attn_forced_mfma attn_lexicon_mfma attn_lm_mfma attn_general attn_general_forced attn_general_lexicon attn_general_lm bilstm_mfma east_post east_tail reading_order quad_crop"
+FOOTPRINT="conv_igemm conv_split conv_split_pp winograd attn_beam_mfma attn_beam_mfma_alpha attn_forced_mfma attn_lexicon_mfma attn_lm_mfma attn_general attn_general_forced attn_general_lexicon attn_general_lm bilstm_mfma east_post east_tail reading_order quad_crop lexicon_nearest"
 T=$(mktemp -d)
 trap 'rm -rf $T' EXIT
 units="$*"

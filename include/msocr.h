@@ -101,6 +101,21 @@ int msocr_winograd_gemm(const msocr_conv_desc* d, int form, int split, const voi
 int msocr_winograd_output_transform(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* residual,
                                     void* out, void* stream);
 
+/* Per-crop forms of the output transform for the SE blocks of SE-ResNet31 (seresnet31.py:37-66), forms 4X4 and 4X4_COLTAIL, where
+ * one image's map [H][W][Cout] f32 fits the LDS of a CU: one workgroup per image transforms its rows of Mw into LDS and goes on
+ * from there, so the map makes no round trip through HBM.  Same arithmetic in the same order as the calls they replace: bit-identical.
+ *   msocr_winograd_crop_lds_bytes: the dynamic LDS such a kernel takes for d's layer (se != 0: with the SE tail's scratch), or -1 where
+ *     it does not apply: another form, more than 160 KB, Cin != Cout (chain), Cout not a power of two in [64, 1024] or out_ld != Cout (se).
+ *   msocr_winograd_output_chain: conv1 -> conv2.  act(A^T Mw A + bias) of d's layer (flags: ReLU), then the INPUT transform of a
+ *     following 3x3/1/1 layer of the same shape (Cin == Cout), written over V of the same workspace (dead since d's GEMM):
+ *     msocr_winograd_gemm of that layer comes next.  Replaces msocr_winograd_output_transform + msocr_winograd_input_transform.
+ *   msocr_winograd_output_se: conv2 -> SE tail.  x = A^T Mw A + bias (no flags), then msocr_se_residual on it:
+ *     out = relu(x * sigmoid(W2 relu(W1 mean_hw(x))) + identity); identity and out [N][H][W][Cout] dense, gate_ws [N][Cout] f32. */
+int64_t msocr_winograd_crop_lds_bytes(const msocr_conv_desc* d, int form, int se);
+int msocr_winograd_output_chain(const msocr_conv_desc* d, int form, void* workspace, const float* bias, void* stream);
+int msocr_winograd_output_se(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* identity,
+                             const float* w1, const float* w2, float* gate_ws, void* out, void* stream);
+
 /* ---- split-operand f32 ("bf16x3"): the default arithmetic of the f32 1x1 convolutions and Winograd-domain GEMMs --------------
  * gfx950 runs exact-f32 MFMA at 1/16 of the bf16 rate.  An f32 value is the exact sum of three bf16 values (round-to-nearest
  * residual chain); of the nine cross products of two such sums the six largest are accumulated in f32 on the bf16 matrix pipes,

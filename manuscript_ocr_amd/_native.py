@@ -65,6 +65,9 @@ _SIGS = {
     "msocr_winograd_input_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_gemm": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_i32, c_vp, c_vp, c_vp]),
     "msocr_winograd_output_transform": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_winograd_crop_lds_bytes": (c_i64, [ctypes.POINTER(ConvDesc), c_i32, c_i32]),
+    "msocr_winograd_output_chain": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp]),
+    "msocr_winograd_output_se": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "msocr_conv3x3_winograd_fused64": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_fused64_gemm_output": (c_i32, [ctypes.POINTER(ConvDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

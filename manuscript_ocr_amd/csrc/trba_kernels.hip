@@ -25,8 +25,7 @@
 
 #include "internal.h"
 #include "msocr.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "se_tail.h"
 
 __device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {
@@ -39,14 +38,6 @@ template <> __device__ __forceinline__ float ldf<uint16_t>(const uint16_t* p) { 
 template <typename T> __device__ __forceinline__ void stf(T* p, float v);
 template <> __device__ __forceinline__ void stf<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void stf<uint16_t>(uint16_t* p, float v) { *p = f2bf(v); }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // --------------------------------------------------------------------------------------------- SE tail
 // One workgroup per sample: mean over HW (coalesced over channels), two tiny FCs, then
@@ -83,86 +74,15 @@ __global__ __launch_bounds__(NT) void se_residual_kernel(const T* __restrict__ x
                                                            float* __restrict__ gate_ws, T* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float sm[];  // part[PG][C] | mean[C] | hid[C/16] | gate[C]
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int C4 = C / 4, PG = NT / C4;  // host guarantees C in {64,128,256,512,1024}: C4 divides NT
-  float* part = sm;
-  float* mean = sm + PG * C;
-  float* hid = mean + C;
-  float* gate = hid + C / 16;
   const T* xs = x + (long)n * HW * C;
-  const int cg = tid % C4, pg = tid / C4;
-  {
-    // four loads in flight per thread, added in the order of the one-at-a-time loop (same sums): with one load per iteration the
-    // kernel sat at 0.45 of the HBM rate — too few bytes in flight per CU for a 2 us round trip
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    int p = pg;
-    for (; p + 3 * PG < HW; p += 4 * PG) {
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = ld4<T>(xs + (long)(p + u * PG) * C + cg * 4);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { s[0] += v[u][0]; s[1] += v[u][1]; s[2] += v[u][2]; s[3] += v[u][3]; }
-    }
-    for (; p < HW; p += PG) {
-      const f32x4 v = ld4<T>(xs + (long)p * C + cg * 4);
-      s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
-    }
-    *reinterpret_cast<f32x4*>(&part[pg * C + cg * 4]) = s;
-  }
-  __syncthreads();
-  const float inv = 1.0f / (float)HW;
-  for (int c = tid; c < C; c += NT) {
-    float s = 0.f;
-    for (int g = 0; g < PG; ++g) s += part[g * C + c];
-    mean[c] = s * inv;
-  }
-  __syncthreads();
-  const int Cr = C / 16;
-  {  // hid = relu(W1 mean): one wave per output, lanes over C
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int j = wv; j < Cr; j += NT / 64) {
-      float a = 0.f;
-      for (int c = lane; c < C; c += 64) a = fmaf(w1[(long)j * C + c], mean[c], a);
-      a = wave_sum(a);
-      if (lane == 0) hid[j] = fmaxf(a, 0.f);
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += NT) {
-    float a = 0.f;
-    for (int j = 0; j < Cr; ++j) a = fmaf(w2[(long)c * Cr + j], hid[j], a);
-    const float g = sigmoidf_(a);
-    gate[c] = g;
-    gate_ws[(long)n * C + c] = g;
-  }
-  __syncthreads();
   const T* is = idt + (long)n * HW * C;
   T* os = out + (long)n * HW * C;
-  const f32x4 g4 = *reinterpret_cast<const f32x4*>(&gate[cg * 4]);
-  int p = pg;
-  for (; p + 3 * PG < HW; p += 4 * PG) {
-    f32x4 v[4], r[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long o = (long)(p + u * PG) * C + cg * 4;
-      v[u] = ld4<T>(xs + o);
-      r[u] = ld4<T>(is + o);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      f32x4 y;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y[e] = fmaxf(v[u][e] * g4[e] + r[u][e], 0.f);
-      st4<T>(os + (long)(p + u * PG) * C + cg * 4, y);
-    }
-  }
-  for (; p < HW; p += PG) {
-    const long o = (long)p * C + cg * 4;
-    const f32x4 v = ld4<T>(xs + o), r = ld4<T>(is + o);
-    f32x4 y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = fmaxf(v[e] * g4[e] + r[e], 0.f);
-    st4<T>(os + o, y);
-  }
+  // the phases are se_tail.h's, with NT virtual threads = this workgroup's own
+  auto ldx = [&](int p, int c) { return ld4<T>(xs + (long)p * C + c); };
+  se_partial_sums<NT, NT>(ldx, HW, C, sm, tid);
+  const float* gate = se_gate<NT, NT>(sm, HW, C, w1, w2, gate_ws + (long)n * C, tid);
+  se_scale<NT, NT>(ldx, [&](int p, int c) { return ld4<T>(is + (long)p * C + c); },
+                   [&](int p, int c, f32x4 y) { st4<T>(os + (long)p * C + c, y); }, HW, C, gate, tid);
 }
 
 extern "C" int msocr_se_residual(const void* x, const void* identity, int N, int HW, int C, int dtype, const float* w1, const float* w2,
@@ -175,10 +95,10 @@ extern "C" int msocr_se_residual(const void* x, const void* identity, int N, int
   // same for every batch size (the order of the mean's additions depends on it, and results must not depend on the batch
   // composition).
   if (dtype == MSOCR_F32) {
-    MSOCR_LAUNCH((se_residual_kernel<float, 1024>), dim3(N), dim3(1024), (size_t)((1024 / (C / 4)) * C + 2 * C + C / 16) * sizeof(float), s,
+    MSOCR_LAUNCH((se_residual_kernel<float, 1024>), dim3(N), dim3(1024), (size_t)se_scratch_floats(1024, C) * sizeof(float), s,
                  (const float*)x, (const float*)identity, HW, C, w1, w2, gate_ws, (float*)out);
   } else if (dtype == MSOCR_BF16) {
-    MSOCR_LAUNCH((se_residual_kernel<uint16_t, 256>), dim3(N), dim3(256), (size_t)((1024 / C) * C + 2 * C + C / 16) * sizeof(float), s,
+    MSOCR_LAUNCH((se_residual_kernel<uint16_t, 256>), dim3(N), dim3(256), (size_t)se_scratch_floats(256, C) * sizeof(float), s,
                  (const uint16_t*)x, (const uint16_t*)identity, HW, C, w1, w2, gate_ws, (uint16_t*)out);
   } else {
     return MSOCR_E_ARG;

@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "conv_common.h"
+#include "se_tail.h"
 
 // ---- 1-D transforms, four channels per lane: B^T (M + 2 inputs -> M + 2 points) and A^T (M + 2 points -> M outputs) ----------
 template <int M> __device__ void wino_bt1(const f32x4 d[M + 2], f32x4 r[M + 2]);
@@ -104,7 +105,8 @@ struct WinoGeom {
 // The axis order sets the f32 rounding and is part of each form's result: the forms with a 6-point H axis transform W first (B^T
 // per row as the row is loaded), then H per column; F(2x2) loads the whole tile and transforms H first, then W.
 template <int MH, int MW>
-__device__ __forceinline__ void wino_input_body(const float* in, long sN, long sH, long sW, int C, const WinoGeom& g, float* V, long t, int c) {
+__device__ __forceinline__ void wino_input_body(const float* in, long sN, long sH, long sW, int C, const WinoGeom& g, long plane_mt, float* V,
+                                                long t, int c) {
   constexpr int PH = MH + 2, PW = MW + 2;
   constexpr bool w_first = MH == 4;
   if (t >= g.Mt) return;
@@ -135,7 +137,7 @@ __device__ __forceinline__ void wino_input_body(const float* in, long sN, long s
       for (int j = 0; j < PW; ++j) q[i][j] = d[j];
     }
   }
-  const long plane = g.Mt * (long)C;
+  const long plane = plane_mt * (long)C;
   float* o = V + t * (long)C + c;
   if constexpr (w_first) {  // then H per column, stored as it is transformed
 #pragma unroll
@@ -169,15 +171,15 @@ __device__ __forceinline__ void wino_input_body(const float* in, long sN, long s
 
 // ---- 3. output transform: one thread = one tile x 4 output channels; H axis first (A^T per column), then W -----------------
 template <int MH, int MW>
-__device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, const WinoGeom& g, const float* bias, const float* res, long res_ld,
-                                                 int relu, float* out, long out_ld, long t, int c) {
+__device__ __forceinline__ void wino_output_body(const float* Mw, int Cout, const WinoGeom& g, long plane_mt, const float* bias, const float* res,
+                                                 long res_ld, int relu, float* out, long out_ld, long t, int c) {
   constexpr int PH = MH + 2, PW = MW + 2;
   if (t >= g.Mt) return;
   const int tw = (int)(t % g.TW);
   const long r = t / g.TW;
   const int th = (int)(r % g.TH);
   const int n = (int)(r / g.TH);
-  const long plane = g.Mt * (long)Cout;
+  const long plane = plane_mt * (long)Cout;
   const float* mp = Mw + t * (long)Cout + c;
   // load order only (register allocation, not arithmetic): F(2x2) loads the whole tile first, the 6-point forms column by column
   f32x4 mt[PH][PW];
@@ -235,14 +237,14 @@ __device__ __forceinline__ long wino_thread_tile(int C, int* c) {
                                                                WinoGeom g, float* __restrict__ V) {                            \
     int c;                                                                                                                       \
     const long t = wino_thread_tile(C, &c);                                                                                      \
-    wino_input_body<MH, MW>(in, sN, sH, sW, C, g, V, t, c);                                                                      \
+    wino_input_body<MH, MW>(in, sN, sH, sW, C, g, g.Mt, V, t, c);                                                                \
   }                                                                                                                              \
   __global__ __launch_bounds__(256) void PREFIX##_output_kernel(const float* __restrict__ Mw, int Cout, WinoGeom g,              \
                                                                 const float* __restrict__ bias, const float* __restrict__ res,  \
                                                                 long res_ld, int relu, float* __restrict__ out, long out_ld) {  \
     int c;                                                                                                                       \
     const long t = wino_thread_tile(Cout, &c);                                                                                   \
-    wino_output_body<MH, MW>(Mw, Cout, g, bias, res, res_ld, relu, out, out_ld, t, c);                                           \
+    wino_output_body<MH, MW>(Mw, Cout, g, g.Mt, bias, res, res_ld, relu, out, out_ld, t, c);                                     \
   }
 WINO_TRANSFORM_KERNELS(wino, 2, 2)
 WINO_TRANSFORM_KERNELS(wino42, 4, 2)
@@ -257,8 +259,8 @@ __global__ __launch_bounds__(256) void wino44_input_kernel_coltail(const float* 
                                                                    float* __restrict__ V41) {
   int c;
   const long t = wino_thread_tile(C, &c);
-  if (t < g44.Mt) wino_input_body<4, 4>(in, sN, sH, sW, C, g44, V44, t, c);
-  else wino_input_body<4, 1>(in, sN, sH, sW, C, g41, V41, t - g44.Mt, c);
+  if (t < g44.Mt) wino_input_body<4, 4>(in, sN, sH, sW, C, g44, g44.Mt, V44, t, c);
+  else wino_input_body<4, 1>(in, sN, sH, sW, C, g41, g41.Mt, V41, t - g44.Mt, c);
 }
 __global__ __launch_bounds__(256) void wino44_output_kernel_coltail(const float* __restrict__ Mw44, const float* __restrict__ Mw41,
                                                                     int Cout, WinoGeom g44, WinoGeom g41,
@@ -266,8 +268,87 @@ __global__ __launch_bounds__(256) void wino44_output_kernel_coltail(const float*
                                                                     long res_ld, int relu, float* __restrict__ out, long out_ld) {
   int c;
   const long t = wino_thread_tile(Cout, &c);
-  if (t < g44.Mt) wino_output_body<4, 4>(Mw44, Cout, g44, bias, res, res_ld, relu, out, out_ld, t, c);
-  else wino_output_body<4, 1>(Mw41, Cout, g41, bias, res, res_ld, relu, out, out_ld, t - g44.Mt, c);
+  if (t < g44.Mt) wino_output_body<4, 4>(Mw44, Cout, g44, g44.Mt, bias, res, res_ld, relu, out, out_ld, t, c);
+  else wino_output_body<4, 1>(Mw41, Cout, g41, g41.Mt, bias, res, res_ld, relu, out, out_ld, t - g44.Mt, c);
+}
+
+// ---- per-crop kernels: the output transform of a square-form layer (with or without the tail column) into LDS ----------------------
+// Where one image's map [H][W][C] f32 fits the LDS of a CU (TRBA's 4 x 13 x 512: 106 496 B), what follows the output transform of an SE
+// block's convolution can read the map from there instead of from HBM.  One workgroup per image: phase 1 is the output bodies above on
+// this image's rows of Mw, storing into the LDS crop through a one-image geometry (tile t of the image, the batch's plane stride);
+// each thread takes (tile, 4 channels) pairs, looping where the image has more pairs than the workgroup has threads.  Then
+//   wino44_output_kernel_chain  conv1 -> conv2 of a block: the input bodies read the crop and write this image's rows of the next
+//                               convolution's V (Cin == Cout: the same plan, so V goes where this layer's V was, dead since its GEMM);
+//   wino44_output_kernel_se     conv2 -> SE tail: the phases of se_tail.h with x read from the crop, in the f32 order of
+//                               se_residual_kernel (1024 virtual threads).
+// The same device functions on the same values in the same order as the kernels they replace: bit-identical results.  The names keep
+// the wino44_output_kernel prefix (the convolution stage of profilers, bench.py and tools/).
+constexpr int kCropThreads = 512;  // 4 x 13 x 512: 4 tiles x 128 channel groups = one pair per thread; LDS allows one workgroup per CU
+constexpr int kCropLdsMax = 160 * 1024;  // the LDS of a CU: the kernels' dynamic-LDS limit is raised to it once, whatever the first crop's size
+
+struct WinoCrop {
+  WinoGeom a, b;                // one-image geometries of the square part and of the tail column (b.Mt == 0 without one)
+  long mt44, mt41, row0_44, row0_41;  // the batch's tiles per plane of each part; this image's first tile row of each part, in floats
+};
+__device__ __forceinline__ WinoCrop wino_crop(const WinoGeom& g44, const WinoGeom& g41, int C) {
+  WinoCrop k;
+  k.a = g44; k.b = g41;
+  k.a.N = k.b.N = 1;
+  k.a.Mt = (long)g44.TH * g44.TW;
+  k.b.Mt = g41.Mt ? (long)g41.TH * g41.TW : 0;
+  k.mt44 = g44.Mt; k.mt41 = g41.Mt;
+  k.row0_44 = blockIdx.x * k.a.Mt * C; k.row0_41 = blockIdx.x * k.b.Mt * C;
+  return k;
+}
+// f44(t, c) / f41(t, c) for this thread's (tile of the image, first of 4 channels) pairs, the square part's tiles first
+template <typename F44, typename F41>
+__device__ __forceinline__ void wino_crop_pairs(const WinoCrop& k, int C, F44 f44, F41 f41) {
+  const int cch = C >> 2, t44 = (int)k.a.Mt, pairs = (t44 + (int)k.b.Mt) * cch;
+  for (int i = threadIdx.x; i < pairs; i += kCropThreads) {
+    const int t = i / cch, c = (i - t * cch) << 2;
+    if (t < t44) f44(t, c);
+    else f41(t - t44, c);
+  }
+}
+__device__ __forceinline__ void wino_crop_output(const WinoCrop& k, const float* Mw44, const float* Mw41, int C, const float* bias, int relu,
+                                                 float* crop) {
+  wino_crop_pairs(k, C,
+                  [&](int t, int c) { wino_output_body<4, 4>(Mw44 + k.row0_44, C, k.a, k.mt44, bias, nullptr, 0, relu, crop, C, t, c); },
+                  [&](int t, int c) { wino_output_body<4, 1>(Mw41 + k.row0_41, C, k.b, k.mt41, bias, nullptr, 0, relu, crop, C, t, c); });
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kCropThreads) void wino44_output_kernel_chain(const float* __restrict__ Mw44, const float* __restrict__ Mw41,
+                                                                            int C, WinoGeom g44, WinoGeom g41,
+                                                                            const float* __restrict__ bias, int relu,
+                                                                            float* __restrict__ V44, float* __restrict__ V41) {
+  extern __shared__ __attribute__((aligned(16))) float crop[];  // [H][W][C]
+  const WinoCrop k = wino_crop(g44, g41, C);
+  wino_crop_output(k, Mw44, Mw41, C, bias, relu, crop);
+  const long sW = C, sH = (long)g44.W * C;
+  wino_crop_pairs(k, C,
+                  [&](int t, int c) { wino_input_body<4, 4>(crop, 0, sH, sW, C, k.a, k.mt44, V44 + k.row0_44, t, c); },
+                  [&](int t, int c) { wino_input_body<4, 1>(crop, 0, sH, sW, C, k.b, k.mt41, V41 + k.row0_41, t, c); });
+}
+
+__global__ __launch_bounds__(kCropThreads) void wino44_output_kernel_se(const float* __restrict__ Mw44, const float* __restrict__ Mw41,
+                                                                         int C, WinoGeom g44, WinoGeom g41,
+                                                                         const float* __restrict__ bias, const float* __restrict__ idt,
+                                                                         const float* __restrict__ w1, const float* __restrict__ w2,
+                                                                         float* __restrict__ gate_ws, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float crop[];  // [H][W][C] | the scratch of se_tail.h
+  const int tid = threadIdx.x, HW = g44.H * g44.W;
+  const long n = blockIdx.x;
+  float* sm = crop + (long)HW * C;
+  const WinoCrop k = wino_crop(g44, g41, C);
+  wino_crop_output(k, Mw44, Mw41, C, bias, 0, crop);
+  const float* is = idt + n * HW * C;
+  float* os = out + n * HW * C;
+  auto ldx = [&](int p, int c) { return *reinterpret_cast<const f32x4*>(crop + p * C + c); };
+  se_partial_sums<1024, kCropThreads>(ldx, HW, C, sm, tid);
+  const float* gate = se_gate<1024, kCropThreads>(sm, HW, C, w1, w2, gate_ws + n * C, tid);
+  se_scale<1024, kCropThreads>(ldx, [&](int p, int c) { return *reinterpret_cast<const f32x4*>(is + (long)p * C + c); },
+                               [&](int p, int c, f32x4 y) { *reinterpret_cast<f32x4*>(os + (long)p * C + c) = y; }, HW, C, gate, tid);
 }
 
 // ---- host side of the unfused forms --------------------------------------------------------------------------------------------
@@ -423,6 +504,65 @@ extern "C" int msocr_winograd_output_transform(const msocr_conv_desc* d, int for
   else if (pl.form == MSOCR_WINO_4X2) MSOCR_LAUNCH(wino42_output_kernel, grid, blk, 0, st, ws + a.mw, d->Cout, a.g, bias, rp, res_ld, relu, o, out_ld);
   else MSOCR_LAUNCH(wino44_output_kernel, grid, blk, 0, st, ws + a.mw, d->Cout, a.g, bias, rp, res_ld, relu, o, out_ld);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
+}
+
+// ---- host side of the per-crop kernels -------------------------------------------------------------------------------------------
+// Dynamic LDS of a per-crop kernel on d's layer: the crop, and with se the SE tail's scratch behind it; -1 where the kernels do not
+// apply: a form without square tiles, Cin != Cout for the chain, a channel count the SE tail does not take, out not dense, or more
+// than the 160 KB of a CU.
+static long wino_crop_lds(const msocr_conv_desc* d, const WinoPlan& pl, bool se) {
+  if (pl.form != MSOCR_WINO_4X4 && pl.form != MSOCR_WINO_4X4_COLTAIL) return -1;
+  const int C = d->Cout;
+  if (se ? (C < 64 || C > 1024 || (C & (C - 1)) || d->out_ld != C) : d->Cin != C) return -1;
+  const long bytes = ((long)d->H * d->W * C + (se ? se_scratch_floats(1024, C) : 0)) * (long)sizeof(float);
+  return bytes <= kCropLdsMax ? bytes : -1;
+}
+
+extern "C" int64_t msocr_winograd_crop_lds_bytes(const msocr_conv_desc* d, int form, int se) {
+  WinoPlan pl;
+  if (!wino_plan(d, form, &pl)) return -1;
+  return wino_crop_lds(d, pl, se != 0);
+}
+
+// the parts of a square-form plan as the per-crop kernels take them: without a tail column the second part is empty
+struct WinoCropParts {
+  WinoGeom g44, g41;
+  long v44, v41, mw44, mw41;
+};
+static WinoCropParts wino_crop_parts(const WinoPlan& pl) {
+  const WinoPart& a = pl.part[0];
+  const WinoPart& b = pl.part[pl.nparts - 1];
+  WinoCropParts k = {a.g, b.g, a.v, b.v, a.mw, b.mw};
+  if (pl.nparts == 1) k.g41.Mt = 0;
+  return k;
+}
+
+extern "C" int msocr_winograd_output_chain(const msocr_conv_desc* d, int form, void* workspace, const float* bias, void* stream) {
+  WinoPlan pl;
+  if (!wino_plan(d, form, &pl) || !workspace || ((uintptr_t)workspace & 15) || (bias && ((uintptr_t)bias & 15))) return MSOCR_E_ARG;
+  const long lds = wino_crop_lds(d, pl, false);
+  if (lds < 0 || (d->flags & MSOCR_CONV_RESIDUAL)) return MSOCR_E_ARG;
+  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(wino44_output_kernel_chain), kCropLdsMax) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  const WinoCropParts k = wino_crop_parts(pl);
+  float* ws = (float*)workspace;
+  MSOCR_LAUNCH(wino44_output_kernel_chain, dim3((unsigned)d->N), dim3(kCropThreads), (size_t)lds, (hipStream_t)stream, ws + k.mw44, ws + k.mw41,
+               d->Cout, k.g44, k.g41, bias, (d->flags & MSOCR_CONV_RELU) ? 1 : 0, ws + k.v44, ws + k.v41);
+  return LAUNCH_OK();
+}
+
+extern "C" int msocr_winograd_output_se(const msocr_conv_desc* d, int form, const void* workspace, const float* bias, const void* identity,
+                                        const float* w1, const float* w2, float* gate_ws, void* out, void* stream) {
+  WinoPlan pl;
+  if (!wino_plan(d, form, &pl) || !workspace || !identity || !w1 || !w2 || !gate_ws || !out) return MSOCR_E_ARG;
+  if (((uintptr_t)workspace | (uintptr_t)identity | (uintptr_t)out) & 15 || (bias && ((uintptr_t)bias & 15))) return MSOCR_E_ARG;
+  const long lds = wino_crop_lds(d, pl, true);
+  if (lds < 0 || (d->flags & (MSOCR_CONV_RESIDUAL | MSOCR_CONV_RELU))) return MSOCR_E_ARG;
+  if (msocr_internal_lds_limit(reinterpret_cast<const void*>(wino44_output_kernel_se), kCropLdsMax) != MSOCR_OK) return MSOCR_E_LAUNCH;
+  const WinoCropParts k = wino_crop_parts(pl);
+  const float* ws = (const float*)workspace;
+  MSOCR_LAUNCH(wino44_output_kernel_se, dim3((unsigned)d->N), dim3(kCropThreads), (size_t)lds, (hipStream_t)stream, ws + k.mw44, ws + k.mw41,
+               d->Cout, k.g44, k.g41, bias, (const float*)identity, w1, w2, gate_ws, (float*)out);
+  return LAUNCH_OK();
 }
 
 extern "C" int msocr_conv3x3_winograd(const msocr_conv_desc* d, int form, int split, const void* in, const void* u, const float* bias,

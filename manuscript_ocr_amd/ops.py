@@ -19,6 +19,7 @@ from . import _native as nat
 #   kind "conv_gemm": work = (algorithmic direct-convolution FLOP, FLOP the MFMAs execute, direct-form layer bytes: input + output
 #                     (+ residual) + weights at the tensor dtype), tag = (M, N, K, "direct"|"winograd")
 #   kind "wino_in" / "wino_out" / "se_residual" / "maxpool" / ...: work = algorithmic HBM bytes (bytes in + bytes out)
+#                     ("wino_out" of a per-crop kernel of se_block: tag = (tiles, C, "chain" | "se"))
 #   kind "bilstm" / "attn_beam": work = (algorithmic bytes per SURVEY.md 8d, recurrent steps of the launch)
 PROFILE = None
 
@@ -259,6 +260,28 @@ def attach_winograd(w, split=None, square=True):
     return w
 
 
+def _wino_stage_in(d, form, xp, ws, what):
+    """The input transform of d's images at xp into the workspace, as one "wino_in" record."""
+    rows, mt = _wino_rows(form, d.N, d.H, d.W)
+    e = _prof_begin()
+    nat.check(nat.lib().msocr_winograd_input_transform(ctypes.byref(d), form, xp, ws.data_ptr(), _stream()), what)
+    _prof_end(e, "wino_in", 4.0 * (d.N * d.H * d.W * d.Cin + rows * d.Cin), (mt, d.Cin))
+
+
+def _wino_stage_gemm(d, form, split, u, ws, what, alg, name, out_px, res_io, fused_tail=None):
+    """The transform-domain GEMMs of d's images as one "conv_gemm" record (alg: the algorithmic FLOP of these images); fused_tail =
+    (bias, residual, out) pointers: the Cin = 64 kernel, which holds the output transform too."""
+    rows, _ = _wino_rows(form, d.N, d.H, d.W)
+    e = _prof_begin()
+    if fused_tail is not None:
+        rc = nat.lib().msocr_winograd_fused64_gemm_output(ctypes.byref(d), int(split), u.data_ptr(), ws.data_ptr(), *fused_tail, _stream())
+    else:
+        rc = nat.lib().msocr_winograd_gemm(ctypes.byref(d), form, int(split), u.data_ptr(), ws.data_ptr(), _stream())
+    nat.check(rc, what)
+    io = 4 * (d.N * d.H * d.W * d.Cin + d.N * out_px * d.Cout * res_io + d.Cout * 9 * d.Cin)
+    _prof_end(e, "conv_gemm", (alg, 2.0 * rows * d.Cin * d.Cout, io), (d.N * d.H * d.W, d.Cout, 9 * d.Cin, name))
+
+
 def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, pool2=False):
     """One Winograd convolution described by d (3x3/1/1, f32) in the given form: the workspace from the per-stream arena, the batch cut
     so that it stays under WINO_WS_LIMIT, and per part either the one-call entry point or — with PROFILE on — the stages one by one,
@@ -291,22 +314,27 @@ def _winograd(d, x, w, u, form, split, bias, residual, out, alg, fused=False, po
             continue
         nn = n1 - n0
         rows, mt = _wino_rows(form, nn, H, W)
-        e = _prof_begin()
-        nat.check(L.msocr_winograd_input_transform(ctypes.byref(d), form, xp, ws.data_ptr(), _stream()), what)
-        _prof_end(e, "wino_in", 4.0 * (nn * H * W * Cin + rows * Cin), (mt, Cin))
-        e = _prof_begin()
-        if fused:
-            rc = L.msocr_winograd_fused64_gemm_output(ctypes.byref(d), int(split), u.data_ptr(), ws.data_ptr(), bp, rp, op, _stream())
-        else:
-            rc = L.msocr_winograd_gemm(ctypes.byref(d), form, int(split), u.data_ptr(), ws.data_ptr(), _stream())
-        nat.check(rc, what)
-        io = x.element_size() * (nn * H * W * Cin + nn * out_px * Cout * res_io + Cout * 9 * Cin)
-        _prof_end(e, "conv_gemm", (alg * nn / N, 2.0 * rows * Cin * Cout, io), (nn * H * W, Cout, 9 * Cin, name))
+        _wino_stage_in(d, form, xp, ws, what)
+        _wino_stage_gemm(d, form, split, u, ws, what, alg * nn / N, name, out_px, res_io, (bp, rp, op) if fused else None)
         if not fused:
             e = _prof_begin()
             nat.check(L.msocr_winograd_output_transform(ctypes.byref(d), form, ws.data_ptr(), bp, rp, op, _stream()), what)
             _prof_end(e, "wino_out", 4.0 * (rows * Cout + nn * H * W * Cout * res_io), (mt, Cout))
     d.N = N
+
+
+def _wino_form(w, H, W):
+    """(form, U, split) of the unfused Winograd path for a 3x3/1/1 call of weight w (attach_winograd) on H x W maps."""
+    form, u, split = nat.WINO_2X2, w._msocr_wino, False
+    if WINOGRAD_TALL and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None:
+        form, u = nat.WINO_4X2, w._msocr_wino42
+        up = getattr(w, "_msocr_wino42_split", None)
+        if up is not None and SPLIT_BF16X3:  # the 24 GEMMs on the bf16 pipes with exactly split operands
+            u, split = up, True
+        up44 = getattr(w, "_msocr_wino44ct_split", None)  # the 4X4 form reads the first 36 planes of the buffer, the composite all 54
+        if up44 is not None and SPLIT_BF16X3 and WINOGRAD_SQUARE and _square_pays(W):
+            form, u, split = nat.WINO_4X4_COLTAIL if _coltail(W) else nat.WINO_4X4, up44, True
+    return form, u, split
 
 
 def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out=None, out_hw=None, alg_k=None, pool2=False):
@@ -356,15 +384,7 @@ def conv2d(x, w, bias, stride=(1, 1), pad=(0, 0), relu=False, residual=None, out
         u = w._msocr_wino42_fused if up is None else up
         _winograd(d, x, w, u, nat.WINO_4X2, up is not None, bias, residual, out, alg, fused=True, pool2=pool2)
     elif use_wino:
-        form, split = nat.WINO_2X2, False
-        if WINOGRAD_TALL and _tall_pays(H) and getattr(w, "_msocr_wino42", None) is not None:
-            form, u = nat.WINO_4X2, w._msocr_wino42
-            up = getattr(w, "_msocr_wino42_split", None)
-            if up is not None and SPLIT_BF16X3:  # the 24 GEMMs on the bf16 pipes with exactly split operands
-                u, split = up, True
-            up44 = getattr(w, "_msocr_wino44ct_split", None)  # the 4X4 form reads the first 36 planes of the buffer, the composite all 54
-            if up44 is not None and SPLIT_BF16X3 and WINOGRAD_SQUARE and _square_pays(W):
-                form, u, split = nat.WINO_4X4_COLTAIL if _coltail(W) else nat.WINO_4X4, up44, True
+        form, u, split = _wino_form(w, H, W)
         _winograd(d, x, w, u, form, split, bias, residual, out, alg)
     else:
         wp = getattr(w, "_msocr_split", None)
@@ -577,19 +597,115 @@ def nhwc_to_nchw_f32(x):
 
 
 # ------------------------------------------------------------------------------------------- TRBA
-def se_residual(x, identity, w1, w2, out=None):
-    """relu(x * sigmoid(W2 relu(W1 mean_hw(x))) + identity); x, identity [N,H,W,C] contiguous."""
+def se_residual(x, identity, w1, w2, out=None, gate=None):
+    """relu(x * sigmoid(W2 relu(W1 mean_hw(x))) + identity); x, identity [N,H,W,C] contiguous.  gate: optional [N,C] f32 tensor that
+    receives the sigmoid gates (scratch otherwise)."""
     _need_cuda(x, identity, w1, w2)
     N, H, W, C = x.shape
     assert x.is_contiguous() and identity.is_contiguous() and identity.shape == x.shape and identity.dtype == x.dtype
     assert w1.shape == (C // 16, C) and w2.shape == (C, C // 16) and w1.dtype == torch.float32
     if out is None:
         out = torch.empty_like(x)
-    gate = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    if gate is None:
+        gate = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    assert gate.shape == (N, C) and gate.dtype == torch.float32 and gate.is_contiguous()
     e = _prof_begin()
     nat.check(nat.lib().msocr_se_residual(x.data_ptr(), identity.data_ptr(), N, H * W, C, _dt(x), w1.data_ptr(), w2.data_ptr(),
                                           gate.data_ptr(), out.data_ptr(), _stream()), "se_residual")
     _prof_end(e, "se_residual", 3.0 * x.element_size() * N * H * W * C, (N, H * W, C))  # x + identity in, out (x re-read from cache)
+    return out
+
+
+# SE blocks whose map fits the LDS of a CU (TRBA layer3 / layer4: 4 x 13 x 512 f32 = 106 496 B) on square-form Winograd convolutions:
+# the output transform of conv1 hands the map to the input transform of conv2 through LDS (wino44_output_kernel_chain), and the output
+# transform of conv2 hands it to the SE tail (wino44_output_kernel_se), instead of a round trip through HBM each.  The same device
+# functions in the same order: bit-identical.  MSOCR_SE_BLOCK_FUSED=0 keeps the three separate calls.
+SE_BLOCK_FUSED = int(os.environ.get("MSOCR_SE_BLOCK_FUSED", "1"))
+
+
+def _square_desc(dtype, N, H, W, w, stride, relu):
+    """(descriptor, form, U) where conv2d runs a dense [N,H,W,Cin] -> [N,H,W,Cout] 3x3 / pad 1 call of weight w as split-operand square-form
+    Winograd (with or without the tail column), else None."""
+    Cout, KH, KW, Cin = w.shape
+    if (dtype != torch.float32 or (KH, KW) != (3, 3) or tuple(stride) != (1, 1) or getattr(w, "_msocr_wino", None) is None
+            or getattr(w, "_msocr_wino42_fused", None) is not None):
+        return None
+    form, u, split = _wino_form(w, H, W)
+    if form not in (nat.WINO_4X4, nat.WINO_4X4_COLTAIL) or not split:
+        return None
+    d = nat.ConvDesc()
+    d.dtype = nat.F32
+    d.N, d.H, d.W, d.Cin = N, H, W, Cin
+    d.in_sN, d.in_sH, d.in_sW = H * W * Cin, W * Cin, Cin
+    d.KH, d.KW, d.stride_h, d.stride_w, d.pad_h, d.pad_w = 3, 3, 1, 1, 1, 1
+    d.Ho, d.Wo, d.Cout = H, W, Cout
+    d.out_ld = Cout
+    d.flags = nat.CONV_RELU if relu else 0
+    return d, form, u
+
+
+def se_block(x, conv1, conv2, identity, se, stride=(1, 1), gate=None):
+    """SEBasicBlock (seresnet31.py:37-66) in one call: relu(se(conv2(relu(conv1(x)))) + identity), conv1 / conv2 = (weight, bias) of the
+    BatchNorm-folded 3x3 / pad 1 convolutions (conv1 with the block's stride), se = (w1, w2) of the SE layer, identity [N,Ho,Wo,C]
+    contiguous (x itself or the downsample branch).  gate: as se_residual.
+    With SE_BLOCK_FUSED the per-crop kernels take what they can: conv2 -> SE tail where conv2 is a square-form Winograd layer whose
+    map and SE scratch fit LDS, and conv1 -> conv2 where conv1 is one too, of the same shape (Cin == Cout).  Everything else — larger
+    maps, bf16, exact f32, a strided conv1 — takes conv2d, conv2d, se_residual as before; the results are the same bit for bit."""
+    (w1, b1), (w2, b2), (s1, s2) = conv1, conv2, se
+    _need_cuda(x, w1, b1, w2, b2, identity, s1, s2, gate)
+    N, H, W, _ = x.shape
+    Ho, Wo = (H - 1) // stride[0] + 1, (W - 1) // stride[1] + 1
+    C = w2.shape[0]
+    L = nat.lib()
+    q2 = _square_desc(x.dtype, N, Ho, Wo, w2, (1, 1), False) if SE_BLOCK_FUSED and SPLIT_BF16X3 else None
+    if q2 is None or L.msocr_winograd_crop_lds_bytes(ctypes.byref(q2[0]), q2[1], 1) < 0:
+        o = conv2d(x, w1, b1, stride=stride, pad=(1, 1), relu=True)
+        o = conv2d(o, w2, b2, pad=(1, 1))
+        return se_residual(o, identity, s1, s2, gate=gate)
+    d2, form, u2 = q2
+    assert identity.shape == (N, Ho, Wo, C) and identity.dtype == x.dtype and identity.is_contiguous()
+    assert s1.shape == (C // 16, C) and s2.shape == (C, C // 16) and s1.dtype == torch.float32
+    assert b1.dtype == b2.dtype == torch.float32 and b1.is_contiguous() and b2.is_contiguous() and b2.numel() == C
+    assert w2.shape[3] == w1.shape[0] == b1.numel() and w1.shape[3] == x.shape[3]
+    q1 = _square_desc(x.dtype, N, H, W, w1, stride, True) if x.stride(3) == 1 else None
+    if q1 is not None and (q1[1] != form or L.msocr_winograd_crop_lds_bytes(ctypes.byref(q1[0]), form, 0) < 0):
+        q1 = None
+    if q1 is not None:  # conv1 -> conv2 through LDS: conv1's output is never written
+        d1, _, u1 = q1
+        d1.in_sN, d1.in_sH, d1.in_sW = x.stride(0), x.stride(1), x.stride(2)
+        o1 = None
+    else:
+        o1 = conv2d(x, w1, b1, stride=stride, pad=(1, 1), relu=True)
+    out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    if gate is None:
+        gate = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    assert gate.shape == (N, C) and gate.dtype == torch.float32 and gate.is_contiguous()
+    # one cut of the batch for the whole block: conv1 and conv2 have the same plan where they chain
+    nbytes = L.msocr_winograd_workspace_bytes(ctypes.byref(d2), form)
+    parts = min(N, -(-nbytes // WINO_WS_LIMIT))
+    per = -(-N // parts)
+    ws = _wino_workspace(nbytes if parts == 1 else (nbytes // N) * per, x.device)
+    name = WINO_FORMS[form][0] + "_split"
+    what = f"se_block {tuple(x.shape)} * {tuple(w1.shape)} * {tuple(w2.shape)}"
+    alg = 2.0 * Ho * Wo * C * 9  # algorithmic FLOP of a convolution per image and input channel
+    for n0 in range(0, N, per):
+        n1 = min(N, n0 + per)
+        nn = d2.N = n1 - n0
+        rows, mt = _wino_rows(form, nn, Ho, Wo)
+        if q1 is not None:
+            d1.N = nn
+            _wino_stage_in(d1, form, x[n0:n1].data_ptr(), ws, what)
+            _wino_stage_gemm(d1, form, True, u1, ws, what, alg * d1.Cin * nn, name, Ho * Wo, 1)
+            e = _prof_begin()
+            nat.check(L.msocr_winograd_output_chain(ctypes.byref(d1), form, ws.data_ptr(), b1.data_ptr(), _stream()), what)
+            _prof_end(e, "wino_out", 4.0 * 2 * rows * C, (mt, C, "chain"))  # Mw read, V written
+        else:
+            _wino_stage_in(d2, form, o1[n0:n1].data_ptr(), ws, what)
+        _wino_stage_gemm(d2, form, True, u2, ws, what, alg * d2.Cin * nn, name, Ho * Wo, 1)
+        e = _prof_begin()
+        nat.check(L.msocr_winograd_output_se(ctypes.byref(d2), form, ws.data_ptr(), b2.data_ptr(), identity[n0:n1].data_ptr(), s1.data_ptr(),
+                                             s2.data_ptr(), gate[n0:n1].data_ptr(), out[n0:n1].data_ptr(), _stream()), what)
+        _prof_end(e, "wino_out", 4.0 * (rows * C + 2 * nn * Ho * Wo * C), (mt, C, "se"))  # Mw + identity read, out written
     return out
 
 

@@ -113,12 +113,9 @@ class TrbaNet:
         P = self.P
         w1, b1 = P[f"{lname}.{i}.conv1"]
         w2, b2 = P[f"{lname}.{i}.conv2"]
-        o = ops.conv2d(x, w1, b1, stride=(stride, stride), pad=(1, 1), relu=True)
-        o = ops.conv2d(o, w2, b2, pad=(1, 1))
         key = f"{lname}.{i}.down"
         idt = ops.conv2d(x, *P[key], stride=(stride, stride)) if key in P else x
-        s1, s2 = P[f"{lname}.{i}.se"]
-        return ops.se_residual(o, idt, s1, s2)
+        return ops.se_block(x, (w1, b1), (w2, b2), idt, P[f"{lname}.{i}.se"], stride=(stride, stride))
 
     def cnn(self, canvases_u8):
         """canvases [B,h,w,3] u8 on device (already resized+padded) -> [B,Hf,T,512] NHWC (dtype)."""

@@ -101,6 +101,75 @@ def test_coltail_workspace_bytes_and_shapes_without_the_form():
     assert L.msocr_conv3x3_winograd(ok, CT, 0, fake, fake, None, None, fake, fake, None) == -1
 
 
+def test_crop_lds_bytes_envelope():
+    """msocr_winograd_crop_lds_bytes, the rule that decides which SE blocks take the per-crop kernels and how much dynamic LDS they ask
+    for: exactly 4 * (H W C + (se ? 4096 + 2C + C/16 : 0)) where the crop (and the SE tail's scratch behind it) fits the 163 840 B of a
+    CU, -1 one pixel past each largest fit and wherever the kernels do not apply."""
+    from manuscript_ocr_amd import _native as nat
+    L = nat.lib()
+    SQ, CT = nat.WINO_4X4, nat.WINO_4X4_COLTAIL
+    LDS = 160 * 1024
+
+    def lds(d, form, se):
+        return L.msocr_winograd_crop_lds_bytes(ctypes.byref(d), form, se)
+
+    def forms(W):  # the square form takes any width (padded last tile), the composite W % 4 == 1 from 5 on
+        return (SQ, CT) if W % 4 == 1 and W >= 5 else (SQ,)
+
+    scratch = lambda C: 4096 + 2 * C + C // 16
+    # largest H * W that fits with the SE scratch: floor((40960 - scratch) / C)
+    assert [(40960 - scratch(C)) // C for C in (64, 128, 256, 512, 1024)] == [573, 285, 141, 69, 33]
+    fits = [(3, 7, 64), (5, 6, 128), (6, 9, 128), (7, 3, 64), (4, 1, 64), (1, 33, 1024), (3, 11, 1024), (3, 23, 512), (3, 47, 256),
+            (15, 19, 128), (3, 191, 64), (4, 5, 64), (4, 13, 128), (5, 6, 64), (5, 7, 256),   # the shapes of test_gpu_se_block_f64.py
+            (4, 13, 512),                                                                      # the workload's
+            (8, 17, 256)]                                                                      # test_gpu_se_block_fused.py's largest
+    for H, W, C in fits:
+        for N in (1, 3):
+            d = _desc(nat, N, H, W, C, C)
+            for form in forms(W):
+                assert lds(d, form, 1) == 4 * (H * W * C + scratch(C)) <= LDS, (H, W, C, form)
+                assert lds(d, form, 0) == 4 * H * W * C, (H, W, C, form)
+    assert lds(_desc(nat, 2, 8, 17, 256, 256), CT, 1) == 157760
+    assert lds(_desc(nat, 2, 1, 33, 1024, 1024), CT, 1) == 160000 and lds(_desc(nat, 2, 3, 23, 512, 512), SQ, 1) == 161920
+    # Cin != Cout: the SE kernel only looks at Cout, the chain needs the same plan on both sides
+    for form in forms(7):
+        assert lds(_desc(nat, 2, 5, 7, 128, 256), form, 1) == 4 * (35 * 256 + scratch(256))
+        assert lds(_desc(nat, 2, 5, 7, 128, 256), form, 0) == -1
+    assert lds(_desc(nat, 2, 4, 13, 256, 512), CT, 0) == -1 and lds(_desc(nat, 2, 4, 13, 512, 256), SQ, 0) == -1
+    # one pixel past each largest fit: no SE kernel; the crop alone still fits, so the chain rule still says yes
+    for H, W, C in ((14, 41, 64), (13, 22, 128), (2, 71, 256), (5, 14, 512), (2, 17, 1024)):
+        assert H * W == (40960 - scratch(C)) // C + 1
+        d = _desc(nat, 2, H, W, C, C)
+        for form in forms(W):
+            assert 4 * (H * W * C + scratch(C)) > LDS and lds(d, form, 1) == -1, (H, W, C, form)
+            assert lds(d, form, 0) == 4 * H * W * C, (H, W, C, form)
+    # exactly the LDS of a CU: "fits", not "less than"
+    d = _desc(nat, 2, 4, 20, 512, 512)
+    assert lds(d, SQ, 0) == LDS == 4 * 4 * 20 * 512 and lds(d, SQ, 1) == -1
+    assert lds(_desc(nat, 2, 4, 21, 512, 512), SQ, 0) == -1 and lds(_desc(nat, 2, 4, 21, 512, 512), CT, 0) == -1
+    # forms without square tiles
+    ok = _desc(nat, 2, 4, 13, 128, 128)
+    for se in (0, 1):
+        assert lds(ok, nat.WINO_2X2, se) == -1 and lds(ok, nat.WINO_4X2, se) == -1
+        assert lds(ok, -1, se) == -1 and lds(ok, CT + 1, se) == -1
+        # the composite only where the map has a tail column
+        for W in (12, 14, 15, 1, 4):
+            assert lds(_desc(nat, 2, 4, W, 128, 128), CT, se) == -1, (W, se)
+            assert lds(_desc(nat, 2, 4, W, 128, 128), SQ, se) == 4 * (4 * W * 128 + se * scratch(128)), (W, se)
+        assert L.msocr_winograd_crop_lds_bytes(None, SQ, se) == -1 and L.msocr_winograd_crop_lds_bytes(None, CT, se) == -1
+        strided = _desc(nat, 2, 8, 13, 128, 128, stride=2)
+        assert lds(strided, SQ, se) == -1 and lds(strided, CT, se) == -1
+    # the SE tail takes powers of two from 64 to 1024 channels and a dense output
+    for C in (32, 96, 192, 2048):
+        assert lds(_desc(nat, 1, 1, 1, C, C), SQ, 1) == -1, C
+        assert lds(_desc(nat, 1, 1, 1, C, C), SQ, 0) == 4 * C, C      # the chain has no such rule
+    for C in (64, 128, 256, 512, 1024):
+        assert lds(_desc(nat, 1, 1, 1, C, C), SQ, 1) == 4 * (C + scratch(C)), C
+    wide = _desc(nat, 2, 4, 13, 128, 128)
+    wide.out_ld = 160
+    assert lds(wide, SQ, 1) == -1 and lds(wide, CT, 1) == -1
+
+
 def test_square_pays_prices_the_tail_column(monkeypatch):
     """ops._square_pays: 36 * (W // 4) + 18 point rows per tile row where the composite runs, 36 * ceil(W / 4) elsewhere or with
     the switch off, against the tall form's 24 * ceil(W / 2)."""

@@ -643,6 +643,40 @@ int msocr_quad_crop(const uint8_t* pages, int N, int H, int W, const int32_t* qd
 int msocr_quad_crop_host(const uint8_t* pages_host, int N, int H, int W, const int32_t* qdesc_host, int M, int img_h, int img_w,
                          uint8_t* canvases_host);
 
+/* ---- tiled detection of large pages (EAST(tile_size=...); an extension beyond the reference, off by default) ----------
+ * A page too large for one run of the network is cut into overlapping tiles at its own resolution; the network runs on the tiles
+ * as a batch and the tiles' maps are stitched into one page-sized map, behind which msocr_east_decode (scale 4), msocr_east_lanms
+ * and msocr_east_box_tail (scale_x = scale_y = 1) run unchanged.  The geometry map holds offsets relative to the map pixel
+ * itself, so stitching is pure data movement: both calls are bit-exact.
+ * Grid of one axis of `len` pixels (detectors/_east/tiles.py::tile_grid): L32 = round_up(len, 32); n tile origins, multiples of
+ * 32, ascending from 0 without gaps, the last tile ending at max(L32, tile): a page smaller than the tile has one tile, otherwise
+ * the last tile is pulled back to end at L32.  Tile index = ty * nx + tx.  Every origin list is given twice, on the device for the
+ * kernel and in host memory (_host) for the argument check; so are the owner tables.  The check is the one that keeps every read in
+ * bounds (multiples of 32, from 0, ascending, no gap, last tile ending at max(L32, tile)); it does not hold the overlap to
+ * tile / 2, which is tile_grid's own rule.
+ *
+ * msocr_east_tile_gather: pages [N][H][W][3] u8 -> tiles [N][ny*nx][tile_h][tile_w][3] u8 (16-byte aligned).  Tile pixel (y, x) of
+ * tile (ty, tx) is page pixel (min(oy[ty] + y, H - 1), min(ox[tx] + x, W - 1)): rows and columns past the page repeat its edge
+ * (at most 31 of them unless the tile is larger than the page), never a black frame.
+ * msocr_east_stitch_maps: tile maps score [N][ny*nx][tile_h/4][tile_w/4] f32 and geometry [...][8] f32 -> page maps
+ * score_out [N][Hm][Wm], geo_out [N][Hm][Wm][8] with Hm = round_up(H, 32) / 4, Wm likewise (all four 16-byte aligned).
+ * row_tile [Hm] / col_tile [Wm] int32 name the tile row / column that OWNS each map row / column (tiles.py::owner_table: tile i
+ * owns the page pixels between the middles of its overlaps with its neighbours; those cuts are multiples of 16 page pixels, so the
+ * tables are constant over every 4 map pixels and a 16-byte vector of scores has one owner).  Page-map pixel (y, x) is the owner's
+ * pixel (y - oy[row_tile[y]] / 4, x - ox[col_tile[x]] / 4); one whose page position (4 y, 4 x) lies outside the page (4 y >= H or
+ * 4 x >= W) is 0.0f in score and geometry, so the padding never yields a box.
+ * Both refuse with MSOCR_E_ARG, before any launch: a null pointer, N, H, W, ny, nx <= 0, tile_h / tile_w not a positive multiple
+ * of 32, origins that are not such a grid, a table entry outside [0, n), one that changes inside a group of 4 map pixels or whose
+ * map pixel lies outside its tile, a misaligned tensor (16 bytes; `pages` may start at any byte), 2^31 or more 16-byte vectors in the output, a
+ * page row of 2^30 or more bytes. */
+int msocr_east_tile_gather(const uint8_t* pages, int N, int H, int W, const int32_t* oy_dev, const int32_t* ox_dev,
+                           const int32_t* oy_host, const int32_t* ox_host, int ny, int nx, int tile_h, int tile_w, uint8_t* tiles,
+                           void* stream);
+int msocr_east_stitch_maps(const float* tile_score, const float* tile_geo, int N, int H, int W, int ny, int nx, int tile_h,
+                           int tile_w, const int32_t* oy_dev, const int32_t* ox_dev, const int32_t* row_tile_dev,
+                           const int32_t* col_tile_dev, const int32_t* oy_host, const int32_t* ox_host, const int32_t* row_tile_host,
+                           const int32_t* col_tile_host, float* score_out, float* geo_out, void* stream);
+
 /* ---- image ingest: JPEG -> RGB on the device -------------------------------------------------------------------------
  * Replaces the file decode of read_image (detectors/_east/utils.py:477-497: cv2.imread / PIL = libjpeg-turbo defaults).
  * 8-bit baseline / extended-sequential Huffman JPEG, grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart

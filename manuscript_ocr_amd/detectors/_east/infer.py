@@ -14,6 +14,11 @@ Extensions (keyword-only, all optional):
   target_size may also be a (W, H) tuple: native non-square network input (multiples of 32)
   predict_batch(pages)  list/array of same-sized RGB pages -> list of result dicts, one launch
                         sequence for the whole batch (the reference is strictly one page per call)
+  tile_size   None (default: the route above) | int or (W, H), multiples of 32: pages are NOT resized; each is cut into overlapping
+              tiles of this size at its own resolution, the network runs on the tiles in chunks of `tile_batch`, and the tiles' maps
+              are stitched into one page-sized map that decode, LANMS and the box filters see.
+              `target_size` is ignored on this route.  tile_overlap (default 256, a multiple of 32, at most half a tile) should exceed
+              the largest word extent expected: a longer word that straddles a cut is seen only in part by each tile.
 """
 import time
 from pathlib import Path
@@ -25,7 +30,7 @@ import torch
 from ... import ingest, ops
 from ..._graphpool import GraphPool, Lease
 from .._types import Block, Page, Word
-from . import post
+from . import post, tiles
 from .net import EastNet
 from .utils import read_image, sort_boxes_reading_order_with_resolutions, visualize_page
 
@@ -68,6 +73,9 @@ class EAST:
         state_dict: Optional[Dict[str, torch.Tensor]] = None,
         max_candidates: Optional[int] = None,
         use_graphs: bool = False,
+        tile_size: Optional[Union[int, Tuple[int, int]]] = None,
+        tile_overlap: int = 256,
+        tile_batch: int = 16,
     ):
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         if not str(self.device).startswith("cuda") or not torch.cuda.is_available():
@@ -75,6 +83,19 @@ class EAST:
                 f"manuscript_ocr_amd.EAST runs only on a HIP device (MI355X); device={self.device!r}, "
                 f"torch.cuda.is_available()={torch.cuda.is_available()}. There is no CPU fallback."
             )
+        # tiled detection (tile_size is not None): (W, H) of a tile; the arguments are checked before any weight is read
+        self.tile_size = None
+        if tile_size is not None:
+            tw, th = (int(tile_size), int(tile_size)) if np.isscalar(tile_size) else (int(tile_size[0]), int(tile_size[1]))
+            tiles.check_tiling(tw, int(tile_overlap))
+            tiles.check_tiling(th, int(tile_overlap))
+            if int(tile_batch) < 1:
+                raise ValueError(f"tile_batch must be at least 1, got {tile_batch}")
+            if use_graphs:
+                raise ValueError("tile_size with use_graphs=True: captured graphs are not provided on the tiled route")
+            self.tile_size = (tw, th)
+        self.tile_overlap, self.tile_batch = int(tile_overlap), int(tile_batch)
+        self._tile_tables = {}  # (H, W) -> ops.TileTables: the grid of a page size, with its tables on the device
         if state_dict is None:
             if weights_path is None:
                 # the reference downloads east_quad_23_05.pth with gdown (infer.py:96-107); no network here
@@ -129,12 +150,79 @@ class EAST:
         q = max(1, int(self.quantization))
         return max(1, (th // 4 // q) * (tw // 4 // q))
 
+    def _detect_tiled_group(self, pages_dev, maps_override):
+        """The tiled route for [N,H,W,3] u8 pages of one size -> Detection whose maps are the stitched page maps [N,Hm,Wm(,8)].
+        maps_override = TILE maps ([N,T,th/4,tw/4], [N,T,th/4,tw/4,8]), page first."""
+        N, H, W = int(pages_dev.shape[0]), int(pages_dev.shape[1]), int(pages_dev.shape[2])
+        tab = self._tile_tables.get((H, W))
+        if tab is None:
+            tab = self._tile_tables[(H, W)] = ops.east_tile_tables(tiles.page_grid(H, W, self.tile_size, self.tile_overlap), pages_dev.device)
+        g = tab.grid
+        Hm, Wm = g.map_hw
+        q = max(1, int(self.quantization))
+        if Hm % q or Wm % q:
+            raise ValueError(f"quantization {q} does not divide the stitched map {Hm} x {Wm} (1, 2, 4 and 8 always do)")
+        tile_px = ops.east_tile_gather(pages_dev.contiguous(), tab).view(N * g.ntiles, g.tile_h, g.tile_w, 3)
+        tscore = torch.empty((N * g.ntiles, g.tile_h // 4, g.tile_w // 4), dtype=torch.float32, device=pages_dev.device)
+        tgeo = torch.empty(tuple(tscore.shape) + (8,), dtype=torch.float32, device=pages_dev.device)
+        for lo in range(0, N * g.ntiles, self.tile_batch):
+            s, gm = self.model.forward(tile_px[lo:lo + self.tile_batch])
+            tscore[lo:lo + self.tile_batch].copy_(s, non_blocking=True)
+            tgeo[lo:lo + self.tile_batch].copy_(gm, non_blocking=True)
+        del tile_px
+        if maps_override is not None:  # benchmark / parity harness: injected tile maps
+            tscore.view(N, g.ntiles, *tscore.shape[1:]).copy_(maps_override[0], non_blocking=True)
+            tgeo.view(N, g.ntiles, *tgeo.shape[1:]).copy_(maps_override[1], non_blocking=True)
+        score, geo = ops.east_stitch_maps(tscore.view(N, g.ntiles, *tscore.shape[1:]), tgeo.view(N, g.ntiles, *tgeo.shape[1:]), tab)
+        max_cand = int(self.max_candidates) if self.max_candidates is not None else max(1, (Hm // q) * (Wm // q))
+        cand, counts = ops.east_decode(score, geo, self.score_thresh, 1.0 / self.score_geo_scale, self.quantization, max_cand)
+        boxes, nbox = ops.east_lanms(cand, counts, self.iou_threshold)
+        fboxes = fn = None
+        if self.device_tail:  # the map is at the page's own resolution: nothing to scale back
+            fboxes, fn = ops.east_box_tail(boxes, nbox, self.expand_ratio_w, self.expand_ratio_h, 1.0, 1.0, self.axis_aligned_output,
+                                           self.remove_area_anomalies, self.anomaly_sigma_threshold, self.anomaly_min_box_count)
+        return Detection(score, geo, boxes, nbox, counts, fboxes, fn)
+
+    def _detect_tiled(self, pages_dev, maps_override):
+        """Equally sized pages: one group.  A ragged list: one grid and one launch sequence per distinct size; the groups' results are
+        padded to the largest candidate capacity and returned in page order, the maps as a list (their sizes differ)."""
+        if not isinstance(pages_dev, (list, tuple)):
+            return self._detect_tiled_group(pages_dev, maps_override)
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in pages_dev]
+        if len(set(sizes)) == 1:
+            return self._detect_tiled_group(torch.stack(list(pages_dev)), maps_override)
+        if maps_override is not None:
+            raise ValueError("injected tile maps need equally sized pages (one tile grid)")
+        groups = {hw: [i for i, s_ in enumerate(sizes) if s_ == hw] for hw in sorted(set(sizes))}
+        dets = {hw: self._detect_tiled_group(torch.stack([pages_dev[i] for i in idx]), None) for hw, idx in groups.items()}
+        cap, n, dev = max(int(d.boxes.shape[1]) for d in dets.values()), len(sizes), pages_dev[0].device
+        score, geo = [None] * n, [None] * n
+        boxes = torch.zeros((n, cap, 9), dtype=torch.float32, device=dev)
+        fboxes = torch.zeros_like(boxes) if self.device_tail else None
+        nbox = torch.empty((n,), dtype=torch.int32, device=dev)
+        counts, fn = torch.empty_like(nbox), (torch.empty_like(nbox) if self.device_tail else None)
+        for hw, idx in groups.items():
+            d, sel = dets[hw], torch.tensor(idx, device=dev)
+            for k, i in enumerate(idx):
+                score[i], geo[i] = d.score[k], d.geo[k]
+            boxes[sel, : d.boxes.shape[1]] = d.boxes
+            nbox.index_copy_(0, sel, d.nbox)
+            counts.index_copy_(0, sel, d.counts)
+            if self.device_tail:
+                fboxes[sel, : d.final_boxes.shape[1]] = d.final_boxes
+                fn.index_copy_(0, sel, d.final_counts)
+        return Detection(score, geo, boxes, nbox, counts, fboxes, fn)
+
     def detect_device(self, pages_dev, maps_override=None):
         """pages_dev [N,h,w,3] u8 on the device (any size) -> device tensors
         (a Detection).  Resize, network, decode and LANMS, all HIP.
         A LIST of [h_i,w_i,3] tensors is a ragged batch: the reference resizes every page to the network input first
         (infer.py:304), so pages of any mix of sizes are resized on the device one by one, stacked and sent through the network
-        together; only the box tail, which scales back to each page's own size, runs per size group."""
+        together; only the box tail, which scales back to each page's own size, runs per size group.
+        With `tile_size` nothing is resized (`target_size` is ignored): gather the tiles, network on chunks of `tile_batch` tiles,
+        stitch the maps, then decode / LANMS / box filters on the page maps with scale 1; maps_override then means TILE maps."""
+        if self.tile_size is not None:
+            return self._detect_tiled(pages_dev, maps_override)
         tw, th = self._target_wh()
         if isinstance(pages_dev, (list, tuple)):
             sizes = [(int(t.shape[0]), int(t.shape[1])) for t in pages_dev]
@@ -172,7 +260,8 @@ class EAST:
     def _host_tail(self, quads: np.ndarray, orig_hw) -> np.ndarray:
         """infer.py:340-356 on the (M,9) f32 NMS output."""
         q = post.expand_boxes(quads, self.expand_ratio_w, self.expand_ratio_h)
-        q = post.scale_boxes(q, orig_hw, self._target_wh())
+        # the tiled route's map is at the page's own resolution: scale 1
+        q = post.scale_boxes(q, orig_hw, self._target_wh() if self.tile_size is None else (orig_hw[1], orig_hw[0]))
         q = post.remove_contained(q)
         q = post.remove_area_anomalies(q, self.remove_area_anomalies, self.anomaly_sigma_threshold, self.anomaly_min_box_count)
         return post.to_axis_aligned(q) if self.axis_aligned_output else q
@@ -216,7 +305,7 @@ class EAST:
         one-time kernel attributes must not fall into a capture); an instance still in flight is never replayed — a
         second one is captured (_graphpool.py has the policy); the result's `graph` lease holds the instance until
         `detect_finish`, or until the result is dropped."""
-        if not self.use_graphs or ops.PROFILE is not None or isinstance(pages_dev, (list, tuple)):
+        if not self.use_graphs or ops.PROFILE is not None or isinstance(pages_dev, (list, tuple)):  # use_graphs excludes tile_size
             return self.detect_device(pages_dev, maps_override)
         key = (tuple(pages_dev.shape), None if maps_override is None else (maps_override[0].data_ptr(), maps_override[1].data_ptr()))
 
@@ -242,6 +331,9 @@ class EAST:
             nbox_h = handle.nbox.cpu().numpy()
             counts_h = handle.counts.cpu().numpy()
             if np.any(counts_h < 0):
+                if self.tile_size is not None:
+                    raise RuntimeError(f"more than max_candidates={int(handle.boxes.shape[1])} cells above threshold; raise max_candidates "
+                                       "(None = the exact bound for the stitched page map)")
                 raise RuntimeError(f"more than max_candidates={self._max_candidates()} cells above threshold; raise max_candidates "
                                    "(None = the exact bound for the network input)")
             fn_h = handle.final_counts.cpu().numpy() if handle.final_counts is not None else None

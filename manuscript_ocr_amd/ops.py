@@ -507,6 +507,54 @@ def east_box_tail(boxes, nbox, expand_w, expand_h, scale_x, scale_y, axis_aligne
     return out, n_out
 
 
+# ------------------------------------------------------------------------------------------- tiled detection
+class TileTables(NamedTuple):
+    """A tile grid (detectors/_east/tiles.py::PageGrid) with its four int32 arrays also on the device."""
+    grid: tuple          # the PageGrid: host arrays, read by the argument checks of the C ABI
+    oy: torch.Tensor
+    ox: torch.Tensor
+    row_tile: torch.Tensor
+    col_tile: torch.Tensor
+
+
+def east_tile_tables(grid, device):
+    host = [np.ascontiguousarray(a, dtype=np.int32) for a in (grid.oy, grid.ox, grid.row_tile, grid.col_tile)]
+    grid = grid._replace(oy=host[0], ox=host[1], row_tile=host[2], col_tile=host[3])
+    return TileTables(grid, *[torch.from_numpy(a).to(device) for a in host])
+
+
+def east_tile_gather(pages_u8, tables):
+    """pages [N,H,W,3] u8 device + the tables of the grid of an H x W page -> tiles [N, ny*nx, tile_h, tile_w, 3] u8, clamped to
+    the page's edge (msocr_east_tile_gather)."""
+    _need_cuda(pages_u8)
+    g = tables.grid
+    N, H, W, C = pages_u8.shape
+    assert C == 3 and pages_u8.dtype == torch.uint8 and pages_u8.is_contiguous() and (H, W) == (g.H, g.W)
+    tiles = torch.empty((N, g.ntiles, g.tile_h, g.tile_w, 3), dtype=torch.uint8, device=pages_u8.device)
+    nat.check(nat.lib().msocr_east_tile_gather(pages_u8.data_ptr(), N, H, W, tables.oy.data_ptr(), tables.ox.data_ptr(),
+                                               g.oy.ctypes.data, g.ox.ctypes.data, g.ny, g.nx, g.tile_h, g.tile_w, tiles.data_ptr(),
+                                               _stream()), "east_tile_gather")
+    return tiles
+
+
+def east_stitch_maps(tile_score, tile_geo, tables):
+    """Tile maps score [N,T,th/4,tw/4] f32 + geo [N,T,th/4,tw/4,8] f32 -> page maps score [N,Hm,Wm], geo [N,Hm,Wm,8]: every pixel
+    from the tile that owns it, zeros outside the page (msocr_east_stitch_maps)."""
+    _need_cuda(tile_score, tile_geo)
+    g = tables.grid
+    N = int(tile_score.shape[0])
+    assert tile_score.dtype == torch.float32 and tile_geo.dtype == torch.float32 and tile_score.is_contiguous() and tile_geo.is_contiguous()
+    assert tuple(tile_score.shape) == (N, g.ntiles, g.tile_h // 4, g.tile_w // 4) and tuple(tile_geo.shape) == tuple(tile_score.shape) + (8,)
+    Hm, Wm = g.map_hw
+    score = torch.empty((N, Hm, Wm), dtype=torch.float32, device=tile_score.device)
+    geo = torch.empty((N, Hm, Wm, 8), dtype=torch.float32, device=tile_score.device)
+    nat.check(nat.lib().msocr_east_stitch_maps(tile_score.data_ptr(), tile_geo.data_ptr(), N, g.H, g.W, g.ny, g.nx, g.tile_h, g.tile_w,
+                                               tables.oy.data_ptr(), tables.ox.data_ptr(), tables.row_tile.data_ptr(),
+                                               tables.col_tile.data_ptr(), g.oy.ctypes.data, g.ox.ctypes.data, g.row_tile.ctypes.data,
+                                               g.col_tile.ctypes.data, score.data_ptr(), geo.data_ptr(), _stream()), "east_stitch_maps")
+    return score, geo
+
+
 class ReadingOrder(NamedTuple):
     """Result of `reading_order_crops`, per page, on the device."""
     order: torch.Tensor  # [N,max_cand] i32: the words in reading order

@@ -256,29 +256,44 @@ typedef struct msocr_attn_weights {
 /* Attention decode (model/model.py:34-46 cell, :227-259 greedy, :92-225 beam): the whole step loop in ONE launch
  * (rows are independent).  batch_H, proj_H: [B][T][H] f32 with proj_H = i2h(batch_H) hoisted out of the loop (the
  * reference recomputes it every step); H a multiple of 64 in 64..512, V <= 512, T <= 64, steps <= 64, beam <= 16
- * with beam * H <= 4096.  These two entry points run the general kernel (csrc/attn_general.hip, one workgroup per
- * batch row, exact f32) for every such shape; the _hoisted entry points below run the matrix-core kernels.
- * greedy: steps = max_len+1; logits_out [B][steps][V] f32, ids_out [B][steps] i32 for ALL steps.
+ * with beam * H <= 4096.  Every decode is one call, msocr_attn_decode, of a descriptor (msocr_attn_desc, below the two beam
+ * options); this comment and the ones that follow say what the modes and options compute.
+ * Kernel family: ctx_gates == NULL runs the general kernels (csrc/attn_general.hip, one workgroup per batch row, exact f32) for
+ * every shape of the envelope.  ctx_gates given runs the matrix-core kernels (csrc/attn_beam_mfma.hip: greedy and forced 32 crops
+ * per workgroup, beam 4 rows x 8 beams) with the context half of the LSTMCell input product hoisted out of the step loop:
+ * H == 256, V <= 256, T <= 48, beam <= 8, other shapes MSOCR_E_ARG.  ctx_gates [B][T][H][4] f32 = batch_H x
+ * rnn.weight_ih[:, :H]^T with the four gates of a unit adjacent (row j*4+g of the product), computed once per call by a GEMM
+ * (msocr_conv1x1_split), 16-byte aligned.  W_ih[:, :H] (sum_t alpha_t batch_H_t) == sum_t alpha_t (W_ih[:, :H] batch_H_t): same
+ * result up to f32 summation order, half the matrix work per step.  ws (msocr_attn_split_weights) given: the split-operand
+ * products; ws == NULL: exact-f32 MFMA in beam mode, MSOCR_E_ARG in greedy and forced mode.
+ * greedy (Attention._greedy_decode, model.py:227-259): steps = max_len+1; logits_out [B][steps][V] f32, ids_out [B][steps] i32 for
+ *         ALL steps.
  * beam  : steps = max_len; per step the kernel stores every beam's temperature-scaled logits, back-pointers,
  *         tokens and the arg-max beam into `workspace`, and fin_step_out[b] = number of steps after which every
- *         beam of row b is finished (or steps).  lp_dev[steps] = f32 length-penalty factors
+ *         beam of row b is finished (or steps).  lp[steps] = f32 length-penalty factors
  *         ((5+t+1)^alpha / 6^alpha, computed by the host exactly as model.py:160) or NULL when alpha <= 0.
- *         Optional early exit (all three pointers non-NULL): chunk_id_dev[B] = index of the reference chunk (the slice of
- *         batch_size crops one model call sees) of every row, chunk_size_dev[nchunks] = rows per chunk, all of them inside
- *         this call; chunk_state_dev[2*nchunks] int32 zeroed by the caller.  The matrix-core kernel (msocr_attn_beam_hoisted)
+ *         Optional early exit (all three pointers non-NULL): chunk_id[B] = index of the reference chunk (the slice of
+ *         batch_size crops one model call sees) of every row, chunk_size[nchunks] = rows per chunk, all of them inside
+ *         this call; chunk_state[2*nchunks] int32 zeroed by the caller.  The matrix-core kernel
  *         then leaves the step loop once every chunk its rows belong to is completely finished (model.py:215), so steps >=
  *         the chunk's run length are skipped; the general kernel runs every step (same outputs for t < the run length).
  * The reference stops the loop for the whole batch chunk (model.py:215,254); the host derives each row's run length
  * t_run from ids/fin_step and msocr_attn_beam_finalize walks the back-pointers from (t_run-1, best beam at t_run-1):
- * logits_out [B][steps][V] (rows t < t_run valid), ids_out [B][steps] (-1 beyond t_run). */
-int msocr_attn_greedy(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
-                      int V, int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
-                      void* stream);
+ * logits_out [B][steps][V] (rows t < t_run valid), ids_out [B][steps] (-1 beyond t_run).
+ * Attention weights (the softmax over the encoder frames that AttentionCell.forward returns, model.py:40-46, and its callers
+ * drop): alpha_out keeps them for every step; every other output is bit-identical with it on or off, and the beam workspace
+ * layout is unchanged.
+ * greedy: alpha_out [B][steps][T] f32, every step written.
+ * beam  : alpha_out is a workspace of its own, [B][steps][beam][T] f32 (msocr_attn_beam_alpha_bytes; 16-byte aligned), slot-
+ *         indexed exactly like the logits trace: the weights of step s at slot k belong to the hypothesis that occupies slot k
+ *         WHEN step s is computed, the one whose logits are stored at [b][s][k].  Steps skipped by the chunk early exit are not
+ *         written.  Given that trace as alpha_ws (with T as in the decode, and alpha_out [B][steps][T]) the finalize step also
+ *         gathers the best path's weights, alpha_out[b][t][:] = alpha_ws[b][t][path[t]][:] for t < t_run, and writes zeros for
+ *         t >= t_run; alpha_ws NULL, T 0, alpha_out NULL: off. */
 int64_t msocr_attn_beam_workspace_bytes(int B, int steps, int beam, int V);
-int msocr_attn_beam(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
-                    int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id,
-                    int blank_id, int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
-                    const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* stream);
+int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T);
+int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev, float* logits_out,
+                             int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out, void* stream);
 /* Optional split form of the three per-step weight matrices (device pointers, each packed by msocr_attn_pack_split_host and
  * copied to the device by the caller): with it the matrix-core kernel forms every f32 product from three bf16 terms per
  * operand on the bf16 matrix pipe (six partial products, f32 accumulation: f32 result up to 2^-25 relative per product and the
@@ -288,60 +303,11 @@ typedef struct msocr_attn_split_weights {
   const uint16_t* whh_p;  /* from whh_t,  N = 4 H, gate_interleaved */
   const uint16_t* gen_p;  /* from gen_wt, N = V */
 } msocr_attn_split_weights;
-
-/* msocr_attn_beam on the matrix cores, 4 rows x 8 beams per workgroup (csrc/attn_beam_mfma.hip), with the context half of the
- * LSTMCell input product hoisted out of the step loop; H == 256, V <= 256, T <= 48, beam <= 8 (other shapes: MSOCR_E_ARG — call
- * msocr_attn_beam).  ws given: the split-operand products; ws == NULL: exact-f32 MFMA.  ctx_gates [B][T][H][4] f32 = batch_H x
- * rnn.weight_ih[:, :H]^T with the four gates of a unit adjacent (row j*4+g of the product), computed once per call by a GEMM
- * (msocr_conv1x1_split).  W_ih[:, :H] (sum_t alpha_t batch_H_t) == sum_t alpha_t
- * (W_ih[:, :H] batch_H_t): same result up to f32 summation order, half the matrix work per step. */
-int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                            const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev,
-                            float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out, void* workspace,
-                            const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* stream);
-/* msocr_attn_greedy on the matrix cores (round 4; Attention._greedy_decode, model.py:227-259): 32 crops per workgroup = one MFMA
- * row block, the three per-step products in the split-operand form (ws must be given), the context half of the gate product
- * hoisted as in msocr_attn_beam_hoisted.  Same outputs and argument meaning as msocr_attn_greedy; H == 256, V <= 256, T <= 48
- * (other shapes: MSOCR_E_ARG — call msocr_attn_greedy). */
-int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                              const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
-                              int blank_id, float* logits_out, int32_t* ids_out, void* stream);
 /* Packing of a decoder weight for the fields of msocr_attn_split_weights; HOST memory in and out.  wt: [256][N] f32 row-major (h2h_wt,
  * gen_wt) or, with gate_interleaved != 0, [256][N/4][4] (whh_t).  out: msocr_attn_pack_split_elems(N) = 3 * 256 * ceil32(N)
  * uint16 (bf16 bit patterns), laid out [plane][k / 16][column][k % 16] with wt == plane0 + plane1 + plane2 exactly. */
 int64_t msocr_attn_pack_split_elems(int N);
 int msocr_attn_pack_split_host(const float* wt_host, int N, int gate_interleaved, uint16_t* out_host);
-int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
-                             float* logits_out, int32_t* ids_out, void* stream);
-
-/* The same decodes with the attention weights of every step kept (the softmax over the encoder frames that AttentionCell.forward
- * returns, model.py:40-46, and its callers drop).  The plain entry points above are these with the output off: every other
- * output is bit-identical either way, and the beam workspace layout is unchanged.
- * greedy: alpha_out [B][steps][T] f32, every step written (NULL = off).
- * beam  : a workspace of its own, alpha_ws [B][steps][beam][T] f32 (msocr_attn_beam_alpha_bytes; required, 16-byte aligned), slot-
- *         indexed exactly like the logits trace: the weights of step s at slot k belong to the hypothesis that occupies slot k
- *         WHEN step s is computed, the one whose logits are stored at [b][s][k].  Steps skipped by the chunk early exit are not
- *         written.  The finalize step gathers the best path's weights, alpha_out[b][t][:] = alpha_ws[b][t][path[t]][:] for
- *         t < t_run, and writes zeros for t >= t_run (alpha_ws, alpha_out required; T as in the decode call). */
-int msocr_attn_greedy_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
-                            int V, int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
-                            float* alpha_out, void* stream);
-int msocr_attn_greedy_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                    const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
-                                    int blank_id, float* logits_out, int32_t* ids_out, float* alpha_out, void* stream);
-int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T);
-int msocr_attn_beam_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H,
-                          int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id,
-                          int blank_id, int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
-                          const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, void* stream);
-int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                  const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                  const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
-                                  void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream);
-int msocr_attn_beam_finalize_alpha(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
-                                   float* logits_out, int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out,
-                                   void* stream);
 
 /* Recognition confidence (recognizers/_trba/__init__.py:413-431): mean over the t_run generated positions of
  * exp(log_softmax(logits)[id]).  logits [B][steps][V] f32, ids [B][steps] i32 (must be valid for t < trun[b]),
@@ -352,12 +318,12 @@ int msocr_seq_confidence(const float* logits, const int32_t* ids, const int32_t*
 /* Per-symbol details of a decoded batch, all [B][steps]: prob_out = exp(log_softmax(logits[b][t])[ids[b][t]]) (the quantity whose
  * mean over t < t_run is the confidence above), centre_out = sum_j alpha[b][t][j] * (j + 0.5) in encoder frames, peak_out =
  * the arg-max frame (int32, the smaller index on ties).  Entries t >= trun[b]: 0, 0 and -1.  alpha [B][steps][T] f32 from the
- * _alpha decodes, T <= 64; everything stays on the device. */
+ * decodes' alpha_out, T <= 64; everything stays on the device. */
 int msocr_seq_char_details(const float* logits, const int32_t* ids, const float* alpha, const int32_t* trun_dev, int B, int V,
                            int steps, int T, float* prob_out, float* centre_out, int32_t* peak_out, void* stream);
 
 /* N-best readings: the final hypotheses of a row's beam search, read out of the workspace a beam decode left behind (any of the
- * msocr_attn_beam entry points; the decode itself is untouched).  The workspace is logits [B][steps][beam][V] f32 | back
+ * beam decodes; the decode itself is untouched).  The workspace is logits [B][steps][beam][V] f32 | back
  * [B][steps][beam] i32 | tokv [B][steps][beam] i32 | best_at [B][steps] i32, and the beam kernels fill the slots of every step in
  * rank order (best score first), so the r-th best hypothesis of a row is the back-trace from slot r of step t_run-1.
  * Rank rule: rank 0 is the slot best_at[b][t_run-1] — the walk of msocr_attn_beam_finalize, the same ids — and ranks 1 .. n_best-1
@@ -383,18 +349,10 @@ int msocr_attn_beam_nbest_host(const void* workspace_host, int B, int V, int ste
  * transcription's ids, the layout of the reference's pack_attention_targets, data/transforms.py:123-157) instead of the arg-max of
  * step s-1, and the logits of every step are returned with the attention weights: logits_out [B][steps][V] f32 (blank_id masked to
  * -1e4 as in the greedy decode; -1 = no blank), alpha_out [B][steps][T] f32 (required).  Every step of every row is written; no ids
- * are. A row fed the ids of msocr_attn_greedy(_hoisted)_alpha reproduces that decode's logits and weights bit for bit.  An id outside
+ * are. A row fed the ids of a greedy decode with alpha_out reproduces that decode's logits and weights bit for bit.  An id outside
  * [0, V) is replaced by sos_id inside the kernel before it is used as an index (callers who want an error check their ids first:
- * msocr_seq_logp reports such an id as NaN).
- *   msocr_attn_forced         every shape of the envelope (H 64..512 in steps of 64, V <= 512, T <= 64, steps <= 64), general kernel
- *   msocr_attn_forced_hoisted H == 256, V <= 256, T <= 48 on the matrix cores, 32 rows per workgroup; ctx_gates and ws (required) as
- *                             for msocr_attn_greedy_hoisted; other shapes: MSOCR_E_ARG
- * Null pointers and shapes outside the envelope return MSOCR_E_ARG before any launch. */
-int msocr_attn_forced(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
-                      const int32_t* tok_in, int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream);
-int msocr_attn_forced_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                              const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, const int32_t* tok_in,
-                              int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream);
+ * msocr_seq_logp reports such an id as NaN).  Forced mode of msocr_attn_decode; the kernel families and their shapes are the greedy
+ * decode's (csrc/attn_general_forced.hip, csrc/attn_forced_mfma.hip). */
 
 /* Log-probability of given ids under a decode's logits: logp_steps_out [B][steps] f32 = log_softmax(logits[b][t] / temperature)[ids[b][t]]
  * in f32 with max subtraction (a true f32 division, skipped when temperature == 1) for t < trun[b] and 0 behind; logp_out [B] f32 =
@@ -409,7 +367,7 @@ int msocr_seq_logp(const float* logits, const int32_t* ids, const int32_t* trun_
 int msocr_seq_logp_host(const float* logits_host, const int32_t* ids_host, const int32_t* trun_host, int B, int V, int steps,
                         float temperature, float* logp_steps_out_host, float* logp_out_host);
 
-/* Lexicon-constrained beam decode: the search of msocr_attn_beam restricted to the words of a closed vocabulary, held as a prefix tree
+/* Lexicon-constrained beam decode (beam mode with lexicon set): the search restricted to the words of a closed vocabulary, held as a prefix tree
  * (trie) in device memory.  msocr_lexicon: CSR arrays, nodes in breadth-first order (root = node 0, child > parent): edge_begin
  * [n_nodes + 1] i32, edge_tok [n_edges] i32 (strictly ascending inside a node), edge_child [n_edges] i32, terminal [n_nodes] u8 (1 where
  * a word ends).  The decode is the beam loop with two additions:
@@ -422,14 +380,13 @@ int msocr_seq_logp_host(const float* logits_host, const int32_t* ids_host, const
  * column and the tie rule (larger value, then smaller flat index) are the plain decode's.  After the top-K a new slot's node is its
  * source's node when the source was finished or the token is eos_id, else the child of the source's node along the token (-1 when
  * there is none), and -1 whenever the winning candidate's value is not finite; a slot whose node is -1 counts as finished, so
- * fin_step and the chunk early exit fire as before.  The workspace layout and fin_step are unchanged: msocr_attn_beam_finalize(_alpha),
+ * fin_step and the chunk early exit fire as before.  The workspace layout and fin_step are unchanged: msocr_attn_beam_finalize,
  * msocr_attn_beam_nbest and msocr_seq_confidence read a constrained decode's workspace as they read a plain one's.  One more output:
- * node_out [B][steps][beam] i32 (msocr_attn_lexicon_nodes_bytes), the node of every slot after step s (steps the early exit skips stay
- * unwritten).  alpha_ws is required (there is one constrained kernel per family, with the weight output on).
- *   msocr_attn_beam_lexicon         the envelope of msocr_attn_beam, general kernel (csrc/attn_general_lexicon.hip)
- *   msocr_attn_beam_lexicon_hoisted the shapes of msocr_attn_beam_hoisted on the matrix cores (csrc/attn_lexicon_mfma.hip)
- * A null lex or member of it, n_nodes < 1, n_edges < 0, a null node_out or alpha_ws and shapes outside the kernel's envelope return
- * MSOCR_E_ARG before any launch.  The entry points receive device pointers and cannot validate the trie; the kernels clamp every
+ * node_out [B][steps][beam] i32 (msocr_attn_beam_slots_bytes), the node of every slot after step s (steps the early exit skips stay
+ * unwritten).  alpha_out is required (there is one constrained kernel per family, with the weight output on:
+ * csrc/attn_general_lexicon.hip, csrc/attn_lexicon_mfma.hip).
+ * A null member of the lexicon, n_nodes < 1, n_edges < 0, a null node_out or alpha_out and shapes outside the kernel's envelope return
+ * MSOCR_E_ARG before any launch.  The entry point receives device pointers and cannot validate the trie; the kernels clamp every
  * edge range into [0, n_edges], ignore an edge token outside [0, V) and treat a child outside [0, n_nodes) as none, so a malformed
  * trie can yield a wrong word but no out-of-bounds read.  msocr_lexicon_check_host validates HOST copies of the arrays: begins
  * monotone from 0 to n_edges, tokens strictly ascending per node and inside [0, V), parent < child < n_nodes, every node but the
@@ -439,16 +396,6 @@ typedef struct {
   const uint8_t* terminal;
   int n_nodes, n_edges;
 } msocr_lexicon; /* device pointers */
-int64_t msocr_attn_lexicon_nodes_bytes(int B, int steps, int beam);
-int msocr_attn_beam_lexicon(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
-                            int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                            int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                            int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream);
-int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                    const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                    const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
-                                    void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                    int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream);
 int msocr_lexicon_check_host(const int32_t* edge_begin_host, const int32_t* edge_tok_host, const int32_t* edge_child_host,
                              const uint8_t* terminal_host, int n_nodes, int n_edges, int V, int max_depth);
 
@@ -458,7 +405,7 @@ int msocr_lexicon_check_host(const int32_t* edge_begin_host, const int32_t* edge
  * the context made of a hypothesis' last order - 1 tokens, the most recent one least significant (order 3: ctx = t[-2] * V + t[-1]);
  * positions before the start of the word count as sos_id, so every slot starts at ctx0 = sum_{i < order - 1} sos_id * V^i.  Order 1:
  * n_ctx 1, ctx always 0.  n_ctx * V <= 2^26 elements (256 MiB; order 3 up to V 406), so every index fits 32 bits.
- * The decode is the beam loop of msocr_attn_beam_alpha with one piece of state and one addend:
+ * The decode (beam mode with lm set) is the beam loop with alpha_out on, with one piece of state and one addend:
  *   state : every beam slot carries ctx (i32).  After the top-K, with ended = done[src] | (token == eos_id):
  *           ctx_new = ended ? ctx[src] : (ctx[src] * V + token) mod n_ctx.  ctx stays inside [0, n_ctx) and the token inside [0, V) by
  *           construction, and no index is formed from a table value: arbitrary table contents cause no out-of-bounds read.
@@ -466,15 +413,14 @@ int msocr_lexicon_check_host(const int32_t* edge_begin_host, const int32_t* edge
  *           that is not finished gets logp = fma(lm_weight, table[ctx * V + v], logit - lse) for every v, eos_id included (the model's
  *           end-of-word is fused with the LM's).  Finished slots keep the plain rule (EOS alone, log-probability 0, no LM term).
  * Temperature, the length-penalty division, the blank column, the tie rule, done / fin_step, the chunk early exit and the workspace
- * layout are unchanged.  The logits trace holds the MODEL's logits, not fused values: msocr_attn_beam_finalize(_alpha),
+ * layout are unchanged.  The logits trace holds the MODEL's logits, not fused values: msocr_attn_beam_finalize,
  * msocr_attn_beam_nbest and msocr_seq_confidence read the workspace as they read a plain one's, and their log-probabilities and
  * confidences are the model's own numbers; the slots are in fused-score order.  lm_weight is a finite f32 >= 0; with lm_weight == 0
- * and a finite table the decode is bit-identical to msocr_attn_beam(_hoisted)_alpha (workspace, fin_step, weight trace).  A table
+ * and a finite table the decode is bit-identical to the plain beam decode with alpha_out (workspace, fin_step, weight trace).  A table
  * with non-finite values is the caller's error (a NaN candidate is treated as in the plain decode).  One more output: ctx_out
- * [B][steps][beam] i32 (msocr_attn_lm_ctx_bytes), the context of every slot after step s (steps the early exit skips stay unwritten).
- *   msocr_attn_beam_lm         the envelope of msocr_attn_beam, general kernel (csrc/attn_general_lm.hip)
- *   msocr_attn_beam_lm_hoisted the shapes of msocr_attn_beam_hoisted on the matrix cores (csrc/attn_lm_mfma.hip)
- * A null lm, table, ctx_out or alpha_ws, order outside 1..3, lm->V != V, n_ctx != V^(order - 1), n_ctx * V > 2^26, lm_weight negative or
+ * [B][steps][beam] i32 (msocr_attn_beam_slots_bytes), the context of every slot after step s (steps the early exit skips stay unwritten).
+ * The kernels: csrc/attn_general_lm.hip (general), csrc/attn_lm_mfma.hip (matrix cores).
+ * A null table, ctx_out or alpha_out, order outside 1..3, lm->V != V, n_ctx != V^(order - 1), n_ctx * V > 2^26, lm_weight negative or
  * not finite, sos_id outside [0, V) and shapes outside the kernel's envelope return MSOCR_E_ARG before any launch.  A language model
  * and a lexicon in one decode are not provided. */
 typedef struct {
@@ -483,16 +429,50 @@ typedef struct {
   int32_t V;
   int64_t n_ctx;
 } msocr_charlm;
-int64_t msocr_attn_lm_ctx_bytes(int B, int steps, int beam);
-int msocr_attn_beam_lm(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
-                       int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
-                       void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev,
-                       void* alpha_ws, const msocr_charlm* lm, float lm_weight, int32_t* ctx_out, void* stream);
-int msocr_attn_beam_lm_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                               const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev,
-                               float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out, void* workspace,
-                               const int32_t* chunk_id_dev, const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws,
-                               const msocr_charlm* lm, float lm_weight, int32_t* ctx_out, void* stream);
+/* the size of node_out and of ctx_out: [B][steps][beam] i32; 0 for a non-positive dimension */
+int64_t msocr_attn_beam_slots_bytes(int B, int steps, int beam);
+
+/* The one attention decode call.  The caller zeroes a descriptor, sets struct_bytes and mode, and fills the fields its mode reads
+ * (G greedy, B beam, F forced); a pointer field the mode does not read must stay NULL, so a descriptor that mixes modes is
+ * refused.  Null required pointers, shapes outside the envelope of the kernel family (above) and every other violation named in
+ * this header return MSOCR_E_ARG before any launch.  All pointers but w, ws, lexicon and lm are device memory.  (The constants
+ * carry _MODE_ because the kernel units use MSOCR_ATTN_FORCED and its like as their own compile-time switches.) */
+#define MSOCR_ATTN_MODE_GREEDY 0
+#define MSOCR_ATTN_MODE_BEAM 1
+#define MSOCR_ATTN_MODE_FORCED 2
+typedef struct msocr_attn_desc {
+  int32_t struct_bytes;  /* GBF  sizeof(msocr_attn_desc); any other value: MSOCR_E_ARG before anything else is read */
+  int32_t mode;          /* GBF  MSOCR_ATTN_MODE_GREEDY, MSOCR_ATTN_MODE_BEAM or MSOCR_ATTN_MODE_FORCED */
+  int32_t B, T, H, V;    /* GBF  rows, encoder frames, hidden size, tokens */
+  int32_t steps;         /* GBF  greedy max_len + 1, beam max_len, forced the columns of tok_in */
+  int32_t beam;          /* B    beam width, 1..16 (matrix cores: <= 8) */
+  int32_t sos_id;        /* GBF  inside [0, V) */
+  int32_t eos_id;        /* GB   forced mode ends no row: it runs with -1 */
+  int32_t blank_id;      /* GBF  column masked to -1e4; -1 = none */
+  float temperature;     /* B    greedy and forced run with 1 */
+  const float* batch_H;  /* GBF  [B][T][H] f32 */
+  const float* proj_H;   /* GBF  [B][T][H] f32 = i2h(batch_H) */
+  const float* ctx_gates;                /* GBF  [B][T][H][4] f32, 16-byte aligned: the matrix-core kernels; NULL: the general kernels */
+  const msocr_attn_weights* w;           /* GBF */
+  const msocr_attn_split_weights* ws;    /* GBF  with ctx_gates only (NULL without); G and F require it there, B: NULL = exact f32 */
+  const float* lp;       /* B    [steps] f32 length-penalty factors, or NULL */
+  const int32_t* tok_in; /* F    [B][steps] i32 */
+  float* logits_out;     /* GF   [B][steps][V] f32 */
+  int32_t* ids_out;      /* G    [B][steps] i32 */
+  void* workspace;       /* B    msocr_attn_beam_workspace_bytes, 16-byte aligned */
+  int32_t* fin_step_out; /* B    [B] i32 */
+  const int32_t* chunk_id;   /* B    [B] i32          the early exit: all three or none */
+  const int32_t* chunk_size; /* B    [nchunks] i32 */
+  int32_t* chunk_state;      /* B    [2*nchunks] i32, zeroed by the caller */
+  float* alpha_out;      /* GBF  attention weights: G, F [B][steps][T]; B [B][steps][beam][T], 16-byte aligned.  NULL = off (G, B);
+                          *      F requires it */
+  const msocr_lexicon* lexicon; /* B    non-NULL: the lexicon-constrained kernels; needs node_out and alpha_out; not with lm */
+  int32_t* node_out;            /* B    [B][steps][beam] i32, with lexicon only */
+  const msocr_charlm* lm;       /* B    non-NULL: the language-model kernels; needs ctx_out and alpha_out; not with lexicon */
+  float lm_weight;              /* B    with lm: finite, >= 0 */
+  int32_t* ctx_out;             /* B    [B][steps][beam] i32, with lm only */
+} msocr_attn_desc;
+int msocr_attn_decode(const msocr_attn_desc* d, void* stream);
 
 /* Approximate dictionary lookup (csrc/lexicon_nearest.hip, csrc/edit_distance.h): for every recognised row the
  * k words of a lexicon with the smallest Levenshtein distance (unit costs for insertion, deletion and substitution), and the same

@@ -57,6 +57,20 @@ class CharLMTable(ctypes.Structure):  # msocr_charlm: table is a device pointer
     _fields_ = [("table", c_vp), ("order", c_i32), ("V", c_i32), ("n_ctx", c_i64)]
 
 
+ATTN_GREEDY, ATTN_BEAM, ATTN_FORCED = 0, 1, 2  # msocr.h MSOCR_ATTN_MODE_*
+
+
+class AttnDesc(ctypes.Structure):  # msocr_attn_desc, field for field; msocr_attn_decode refuses a struct_bytes other than its own sizeof
+    _fields_ = (
+        [(n, c_i32) for n in ("struct_bytes", "mode", "B", "T", "H", "V", "steps", "beam", "sos_id", "eos_id", "blank_id")]
+        + [("temperature", c_f32), ("batch_H", c_vp), ("proj_H", c_vp), ("ctx_gates", c_vp),
+           ("w", ctypes.POINTER(AttnWeights)), ("ws", ctypes.POINTER(AttnSplitWeights))]
+        + [(n, c_vp) for n in ("lp", "tok_in", "logits_out", "ids_out", "workspace", "fin_step_out", "chunk_id", "chunk_size",
+                               "chunk_state", "alpha_out")]
+        + [("lexicon", ctypes.POINTER(LexiconArrays)), ("node_out", c_vp), ("lm", ctypes.POINTER(CharLMTable)), ("lm_weight", c_f32),
+           ("ctx_out", c_vp)])
+
+
 _SIGS = {
     "msocr_conv2d": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_winograd_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc), c_i32]),
@@ -87,51 +101,19 @@ _SIGS = {
     "msocr_mean_over_h": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_bilstm_recurrent": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_bilstm_recurrent_split": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
-    "msocr_attn_greedy": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
-                                  c_vp, c_vp, c_vp]),
-    "msocr_attn_greedy_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
-                                          c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
-    "msocr_attn_beam": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
-                                c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_pack_split_elems": (c_i64, [c_i32]),
     "msocr_attn_pack_split_host": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
-    "msocr_attn_beam_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
-                                        c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    "msocr_attn_beam_finalize": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_attn_beam_finalize": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "msocr_attn_beam_slots_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "msocr_attn_decode": (c_i32, [ctypes.POINTER(AttnDesc), c_vp]),
     "msocr_seq_confidence": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
-    "msocr_attn_greedy_alpha": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
-                                        c_vp, c_vp, c_vp, c_vp]),
-    "msocr_attn_greedy_hoisted_alpha": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32,
-                                                c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_alpha_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    "msocr_attn_beam_alpha": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
-                                      c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_attn_beam_hoisted_alpha": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
-                                              c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                              c_vp, c_vp]),
-    "msocr_attn_beam_finalize_alpha": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "msocr_seq_char_details": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_nbest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_attn_beam_nbest_host": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "msocr_attn_forced": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
-                                  c_vp, c_vp, c_vp]),
-    "msocr_attn_forced_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
-                                          c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "msocr_seq_logp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     "msocr_seq_logp_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
-    "msocr_attn_lexicon_nodes_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "msocr_attn_beam_lexicon": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
-                                        c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(LexiconArrays), c_vp, c_vp]),
-    "msocr_attn_beam_lexicon_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
-                                                c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                c_vp, ctypes.POINTER(LexiconArrays), c_vp, c_vp]),
-    "msocr_attn_lm_ctx_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "msocr_attn_beam_lm": (c_i32, [c_vp, c_vp, ctypes.POINTER(AttnWeights), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32,
-                                   c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(CharLMTable), c_f32, c_vp, c_vp]),
-    "msocr_attn_beam_lm_hoisted": (c_i32, [c_vp, c_vp, c_vp, ctypes.POINTER(AttnWeights), ctypes.POINTER(AttnSplitWeights), c_i32, c_i32,
-                                           c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                           c_vp, ctypes.POINTER(CharLMTable), c_f32, c_vp, c_vp]),
     "msocr_lexicon_check_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
     "msocr_lexicon_nearest_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "msocr_lexicon_nearest": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(WordList), c_i32, c_i32,

@@ -369,7 +369,7 @@ extern "C" int msocr_nhwc_to_nchw_f32(const void* in, int N, int C, int H, int W
   return LAUNCH_OK();
 }
 
-extern "C" const char* msocr_version(void) { return "msocr 0.1 (gfx950)"; }
+extern "C" const char* msocr_version(void) { return "msocr 0.2 (gfx950)"; }
 
 // ---------------------------------------------------------------------------------------------
 // Crop + ResizeAndPadA on the device (recognizers/_trba/data/transforms.py:85-120 applied to the clamped

@@ -108,8 +108,8 @@ __attribute__((visibility("hidden"))) int msocr_internal_attn_greedy_mfma_alpha(
 // attn_forced_mfma.hip: forced decode (the greedy step loop along a.tok_in instead of its own arg-max) with 32 rows per workgroup on
 // the matrix cores; same shapes and weights as the greedy kernel, a.alpha_out and a.tok_in required
 __attribute__((visibility("hidden"))) int msocr_internal_attn_forced_mfma(const AttnArgs& a, hipStream_t s);
-// attn_general.hip: greedy / beam decode for every shape of the envelope (see its header), H == 256 included; the plain entry points
-// msocr_attn_greedy / msocr_attn_beam run it.  Same outputs and workspace layout as the matrix-core kernels; a.alpha_out optional.
+// attn_general.hip: greedy / beam decode for every shape of the envelope (see its header), H == 256 included; msocr_attn_decode
+// runs it for a descriptor without ctx_gates.  Same outputs and workspace layout as the matrix-core kernels; a.alpha_out optional.
 __attribute__((visibility("hidden"))) int msocr_internal_attn_general(const AttnArgs& a, int H, bool beam, hipStream_t s);
 // attn_general_forced.hip: the forced decode for the same shapes (one row per crop): a.tok_in and a.alpha_out required; logits and
 // weights as the greedy loop stores them, no ids

@@ -11,14 +11,12 @@
 //   msocr_se_residual       <- recognizers/_trba/model/seresnet31.py:5-20, 61-66
 //   msocr_mean_over_h       <- recognizers/_trba/model/model.py:388-390
 //   msocr_bilstm_recurrent  <- model.py:9-21 (nn.LSTM, gate order i,f,g,o)
-//   msocr_attn_greedy(_hoisted)       <- model.py:34-46 + 227-259
-//   msocr_attn_beam(_hoisted, _finalize) <- model.py:34-46 + 92-225
-//   msocr_attn_forced(_hoisted)       <- model.py:34-46 + 287-320 (the teacher-forced pass, as an inference call)
+//   msocr_attn_decode       <- model.py:34-46 + 227-259 (greedy), 92-225 (beam, with msocr_attn_beam_finalize), 287-320 (forced: the
+//                              teacher-forced pass, as an inference call)
 //   msocr_seq_confidence    <- recognizers/_trba/__init__.py:413-431
 //   msocr_seq_logp          summed log-probability of given ids (no counterpart: the reference has the training loss only)
 //   msocr_seq_char_details  per-symbol probability and attention position (no counterpart: the reference drops both)
-// The _alpha entry points are the same decodes with the attention weights of every step kept (model.py:40-46 returns them, its
-// callers drop them); the plain ones are those with the output off.
+// A decode with alpha_out keeps the attention weights of every step (model.py:40-46 returns them, its callers drop them).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -216,8 +214,8 @@ extern "C" int msocr_bilstm_recurrent(const float* xproj, const float* w_hh_t, i
 }
 
 // --------------------------------------------------------------------------------------------- attention decoder
-// The decode kernels live in attn_beam_mfma.hip (matrix cores: the _hoisted entries) and attn_general.hip (every shape: the plain
-// entries); this file keeps the argument checks, the beam workspace layout and the finalize step.
+// The decode kernels live in attn_beam_mfma.hip (matrix cores: a descriptor with ctx_gates) and attn_general.hip (every shape: one
+// without); this file keeps the one entry point, its argument checks, the beam workspace layout and the finalize step.
 
 // finalize: walk the back-pointers from (t_run-1, best_at[t_run-1]) and gather the path's logits; with alpha_ws [B][steps][K][T] also the
 // path's attention weights -> alpha_out [B][steps][T] (zeros for t >= t_run)
@@ -260,105 +258,18 @@ static int check_attn(const float* bh, const float* ph, const msocr_attn_weights
   return MSOCR_OK;
 }
 
-// every shape of the envelope on the general kernel (attn_general.hip)
-// alpha_out: [B][steps][T] f32, the attention weights of every step, or NULL (off: the plain entry point)
-extern "C" int msocr_attn_greedy_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                       int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
-                                       float* alpha_out, void* stream) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
-  if (sos_id < 0 || sos_id >= V) return MSOCR_E_ARG;
-  AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w;
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
-  a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.ids_out = ids_out; a.alpha_out = alpha_out;
-  return msocr_internal_attn_general(a, H, false, (hipStream_t)stream);
-}
-extern "C" int msocr_attn_greedy(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                 int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
-  return msocr_attn_greedy_alpha(batch_H, proj_H, w, B, T, H, V, steps, sos_id, eos_id, blank_id, logits_out, ids_out, nullptr, stream);
-}
-
-// mode="greedy" on the matrix cores (attn_greedy_mfma_kernel, csrc/attn_beam_mfma.hip): 32 crops per workgroup, the three per-step
-// products in the split-operand form, the context half of the gate product hoisted (ctx_gates = batch_H x W_ih[:, :H]^T, [B][T][H][4],
-// computed once per call by a GEMM).  Same outputs as msocr_attn_greedy; hidden 256, V <= 256, T <= 48 only.
-extern "C" int msocr_attn_greedy_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates,
-                                               const msocr_attn_weights* w, const msocr_attn_split_weights* ws, int B, int T, int H, int V,
-                                               int steps, int sos_id, int eos_id, int blank_id, float* logits_out, int32_t* ids_out,
-                                               float* alpha_out, void* stream) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !logits_out || !ids_out) return MSOCR_E_ARG;
-  if (sos_id < 0 || sos_id >= V || !attn_mfma_shape(T, H, V)) return MSOCR_E_ARG;
-  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
-  if (!ws || !ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15))
-    return MSOCR_E_ARG;
-  AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
-  a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p;
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
-  a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.ids_out = ids_out; a.alpha_out = alpha_out;
-  return alpha_out ? msocr_internal_attn_greedy_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_greedy_mfma(a, (hipStream_t)stream);
-}
-extern "C" int msocr_attn_greedy_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                         const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int sos_id, int eos_id,
-                                         int blank_id, float* logits_out, int32_t* ids_out, void* stream) {
-  return msocr_attn_greedy_hoisted_alpha(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, sos_id, eos_id, blank_id, logits_out, ids_out,
-                                         nullptr, stream);
-}
-
-// Forced (teacher-forced) decode, Attention.forward(is_train=True) of the reference (model.py:287-320) with sampling_prob 0 in eval():
-// the decoder is run along the GIVEN tokens tok_in [B][steps] i32 (column 0 = SOS, then the transcription's ids: transforms.pack_targets)
-// instead of its own arg-max, and the logits it gives every step are returned with the attention weights.  The kernels replace an id
-// outside [0, V) by sos_id before they use it as an index; they write no ids.  msocr_attn_forced: every shape of the envelope on the
-// general kernel (attn_general_forced.hip); msocr_attn_forced_hoisted: the matrix-core kernel (attn_forced_mfma.hip), the greedy kernel's
-// shapes, ctx_gates and split weights.  A row fed the ids of msocr_attn_greedy(_hoisted)_alpha reproduces its logits and weights bit
-// for bit.
-extern "C" int msocr_attn_forced(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V, int steps,
-                                 const int32_t* tok_in, int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !tok_in || !logits_out || !alpha_out) return MSOCR_E_ARG;
-  if (sos_id < 0 || sos_id >= V) return MSOCR_E_ARG;
-  AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w;
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
-  a.sos_id = sos_id; a.eos_id = -1; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.alpha_out = alpha_out; a.tok_in = tok_in;
-  return msocr_internal_attn_general_forced(a, H, (hipStream_t)stream);
-}
-extern "C" int msocr_attn_forced_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                         const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, const int32_t* tok_in,
-                                         int sos_id, int blank_id, float* logits_out, float* alpha_out, void* stream) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !tok_in || !logits_out || !alpha_out) return MSOCR_E_ARG;
-  if (sos_id < 0 || sos_id >= V || !attn_mfma_shape(T, H, V)) return MSOCR_E_ARG;
-  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
-  if (!ws || !ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15))
-    return MSOCR_E_ARG;
-  AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
-  a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p;
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = 1;
-  a.sos_id = sos_id; a.eos_id = -1; a.blank_id = blank_id; a.temperature = 1.0f;
-  a.logits_out = logits_out; a.alpha_out = alpha_out; a.tok_in = tok_in;
-  return msocr_internal_attn_forced_mfma(a, (hipStream_t)stream);
-}
-
 // workspace: logits [B][steps][K][V] f32 | back [B][steps][K] i32 | tokv [B][steps][K] i32 | best_at [B][steps] i32
 static inline int64_t beam_ws_logits(int B, int steps, int K, int V) { return (int64_t)B * steps * K * V * 4; }
 extern "C" int64_t msocr_attn_beam_workspace_bytes(int B, int steps, int beam, int V) {
   if (B <= 0 || steps <= 0 || beam <= 0 || V <= 0) return 0;
   return beam_ws_logits(B, steps, beam, V) + (int64_t)B * steps * beam * 8 + (int64_t)B * steps * 4 + 256;
 }
-// the separate attention-weight workspace of the _alpha entry points: [B][steps][K][T] f32, slot-indexed like the logits trace
+// the separate attention-weight workspace of a beam decode with alpha_out: [B][steps][K][T] f32, slot-indexed like the logits trace
 extern "C" int64_t msocr_attn_beam_alpha_bytes(int B, int steps, int beam, int T) {
   if (B <= 0 || steps <= 0 || beam <= 0 || T <= 0) return 0;
   return (int64_t)B * steps * beam * T * 4;
 }
 
-// what msocr_attn_beam_lm(_hoisted) add to a beam decode: the language model, the weight of its addend and the context trace
-struct LmFusion {
-  const msocr_charlm* lm;
-  float weight;
-  int32_t* ctx_out;
-};
 // whether the struct describes a table this decode can index: order 1..3, the decode's V, n_ctx = V^(order - 1), n_ctx * V <= 2^26
 static bool charlm_ok(const msocr_charlm* lm, int V) {
   if (!lm || !lm->table || lm->order < 1 || lm->order > 3 || lm->V != V || V <= 0) return false;
@@ -367,149 +278,103 @@ static bool charlm_ok(const msocr_charlm* lm, int V) {
   return lm->n_ctx == n && n * V <= ((int64_t)1 << 26);
 }
 
-// ctx_gates == nullptr (msocr_attn_beam): the general kernel, every shape of the envelope; otherwise (msocr_attn_beam_hoisted) the
-// matrix-core kernel, its products in the split-operand form with ws, on the exact-f32 MFMA without
-static int attn_beam_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                          const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                          int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                          int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
-                          int32_t* node_out = nullptr, const LmFusion* lmf = nullptr) {
-  if (check_attn(batch_H, proj_H, w, B, T, H, V, steps) || !fin_step_out || !workspace) return MSOCR_E_ARG;
-  if (beam < 1 || beam > 16 || sos_id < 0 || sos_id >= V || ((uintptr_t)workspace & 15)) return MSOCR_E_ARG;
-  if (ctx_gates && (!attn_mfma_shape(T, H, V) || beam > 8)) return MSOCR_E_ARG;
-  if (lex && (!lex->edge_begin || !lex->edge_tok || !lex->edge_child || !lex->terminal || lex->n_nodes < 1 || lex->n_edges < 0 ||
-              !node_out || !alpha_ws || beam * H > 4096))
+// msocr_attn_decode (msocr.h) in three parts: what a descriptor must satisfy, AttnArgs from it, the launcher for it.
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+static int attn_desc_check(const msocr_attn_desc* d) {
+  if (!d || d->struct_bytes != (int32_t)sizeof(msocr_attn_desc)) return MSOCR_E_ARG;
+  const bool beam = d->mode == MSOCR_ATTN_MODE_BEAM, forced = d->mode == MSOCR_ATTN_MODE_FORCED;
+  if (!beam && !forced && d->mode != MSOCR_ATTN_MODE_GREEDY) return MSOCR_E_ARG;
+  // a pointer the mode does not read must be NULL: a call that mixes modes is refused, not half-ignored
+  if (beam ? d->logits_out || d->ids_out
+           : d->lp || d->workspace || d->fin_step_out || d->chunk_id || d->chunk_size || d->chunk_state || d->lexicon || d->lm)
     return MSOCR_E_ARG;
-  if (lmf && (lex || !charlm_ok(lmf->lm, V) || !lmf->ctx_out || !alpha_ws || !(lmf->weight >= 0.f) || !std::isfinite(lmf->weight) ||
-              beam * H > 4096))
+  if ((forced ? d->ids_out != nullptr : d->tok_in != nullptr) || (d->ws && !d->ctx_gates) || (d->node_out && !d->lexicon) ||
+      (d->ctx_out && !d->lm))
     return MSOCR_E_ARG;
+  // every mode: the envelope, the weights, the start token
+  if (check_attn(d->batch_H, d->proj_H, d->w, d->B, d->T, d->H, d->V, d->steps) || d->sos_id < 0 || d->sos_id >= d->V) return MSOCR_E_ARG;
+  // what the mode reads and writes
+  if (beam) {
+    if (!d->fin_step_out || !d->workspace || misaligned16(d->workspace) || misaligned16(d->alpha_out) || d->beam < 1 || d->beam > 16)
+      return MSOCR_E_ARG;
+  } else if (!d->logits_out || (forced ? !d->tok_in || !d->alpha_out : !d->ids_out)) {
+    return MSOCR_E_ARG;
+  }
+  // ctx_gates given: the matrix-core kernels, their shapes and alignments; greedy and forced need the split weights, beam runs on
+  // exact f32 without them
+  if (d->ctx_gates) {
+    const msocr_attn_split_weights* ws = d->ws;
+    if (misaligned16(d->ctx_gates) || !attn_mfma_shape(d->T, d->H, d->V) || (beam && d->beam > 8) || (!ws && !beam)) return MSOCR_E_ARG;
+    if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || misaligned16(ws->h2h_p) || misaligned16(ws->whh_p) || misaligned16(ws->gen_p)))
+      return MSOCR_E_ARG;
+  }
+  // the two beam options: one at a time, each with its trace and the weight trace (their kernels have the weight output on)
+  const msocr_lexicon* lex = d->lexicon;
+  if (lex && (d->lm || !lex->edge_begin || !lex->edge_tok || !lex->edge_child || !lex->terminal || lex->n_nodes < 1 || lex->n_edges < 0 ||
+              !d->node_out || !d->alpha_out || d->beam * d->H > 4096))
+    return MSOCR_E_ARG;
+  if (d->lm && (!charlm_ok(d->lm, d->V) || !d->ctx_out || !d->alpha_out || !(d->lm_weight >= 0.f) || !std::isfinite(d->lm_weight) ||
+                d->beam * d->H > 4096))
+    return MSOCR_E_ARG;
+  return MSOCR_OK;
+}
+
+static AttnArgs attn_args(const msocr_attn_desc* d) {
+  const bool beam = d->mode == MSOCR_ATTN_MODE_BEAM;
   AttnArgs a{};
-  a.batch_H = batch_H; a.proj_H = proj_H; a.w = *w; a.ctx_gates = ctx_gates;
-  if (ws) { a.h2h_p = ws->h2h_p; a.whh_p = ws->whh_p; a.gen_p = ws->gen_p; }
-  a.B = B; a.T = T; a.V = V; a.steps = steps; a.K = beam;
-  a.sos_id = sos_id; a.eos_id = eos_id; a.blank_id = blank_id; a.temperature = temperature; a.lp = lp_dev;
-  char* p = (char*)workspace;
-  a.logits_out = (float*)p; p += beam_ws_logits(B, steps, beam, V);
-  a.back = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
-  a.tokv = (int32_t*)p; p += (int64_t)B * steps * beam * 4;
+  a.batch_H = d->batch_H; a.proj_H = d->proj_H; a.w = *d->w; a.ctx_gates = d->ctx_gates;
+  if (d->ws) { a.h2h_p = d->ws->h2h_p; a.whh_p = d->ws->whh_p; a.gen_p = d->ws->gen_p; }
+  a.B = d->B; a.T = d->T; a.V = d->V; a.steps = d->steps; a.K = beam ? d->beam : 1;
+  a.sos_id = d->sos_id; a.blank_id = d->blank_id;
+  a.eos_id = d->mode == MSOCR_ATTN_MODE_FORCED ? -1 : d->eos_id;  // the forced decode ends no row
+  a.temperature = beam ? d->temperature : 1.0f;
+  a.alpha_out = d->alpha_out;  // nullptr: off
+  a.tok_in = d->tok_in;
+  if (!beam) {
+    a.logits_out = d->logits_out; a.ids_out = d->ids_out;
+    return a;
+  }
+  a.lp = d->lp;
+  char* p = (char*)d->workspace;
+  a.logits_out = (float*)p; p += beam_ws_logits(d->B, d->steps, d->beam, d->V);
+  a.back = (int32_t*)p; p += (int64_t)d->B * d->steps * d->beam * 4;
+  a.tokv = (int32_t*)p; p += (int64_t)d->B * d->steps * d->beam * 4;
   a.best_at = (int32_t*)p;
-  a.fin_step = fin_step_out;
-  a.alpha_out = (float*)alpha_ws;  // nullptr (the plain entry points): off
-  if (chunk_id_dev && chunk_size_dev && chunk_state_dev) { a.chunk_id = chunk_id_dev; a.chunk_size = chunk_size_dev; a.chunk_state = chunk_state_dev; }
-  if (lex) {  // the constrained kernels, in translation units of their own
+  a.fin_step = d->fin_step_out;
+  if (d->chunk_id && d->chunk_size && d->chunk_state) { a.chunk_id = d->chunk_id; a.chunk_size = d->chunk_size; a.chunk_state = d->chunk_state; }
+  if (const msocr_lexicon* lex = d->lexicon) {
     a.lex_begin = lex->edge_begin; a.lex_tok = lex->edge_tok; a.lex_child = lex->edge_child; a.lex_terminal = lex->terminal;
-    a.lex_nodes = lex->n_nodes; a.lex_edges = lex->n_edges; a.node_out = node_out;
-    return ctx_gates ? msocr_internal_attn_lexicon_mfma(a, (hipStream_t)stream) : msocr_internal_attn_general_lexicon(a, H, (hipStream_t)stream);
+    a.lex_nodes = lex->n_nodes; a.lex_edges = lex->n_edges; a.node_out = d->node_out;
   }
-  if (lmf) {  // the fused kernels, in translation units of their own; every slot starts at the "all SOS" row
-    a.lm_table = lmf->lm->table; a.lm_nctx = (int)lmf->lm->n_ctx; a.lm_weight = lmf->weight; a.ctx_out = lmf->ctx_out;
-    for (int i = 1; i < lmf->lm->order; ++i) a.lm_ctx0 = a.lm_ctx0 * V + sos_id;
-    return ctx_gates ? msocr_internal_attn_lm_mfma(a, (hipStream_t)stream) : msocr_internal_attn_general_lm(a, H, (hipStream_t)stream);
+  if (const msocr_charlm* lm = d->lm) {  // every slot starts at the "all SOS" row
+    a.lm_table = lm->table; a.lm_nctx = (int)lm->n_ctx; a.lm_weight = d->lm_weight; a.ctx_out = d->ctx_out;
+    for (int i = 1; i < lm->order; ++i) a.lm_ctx0 = a.lm_ctx0 * d->V + d->sos_id;
   }
-  if (!ctx_gates) return msocr_internal_attn_general(a, H, true, (hipStream_t)stream);
-  return alpha_ws ? msocr_internal_attn_beam_mfma_alpha(a, (hipStream_t)stream) : msocr_internal_attn_beam_mfma(a, (hipStream_t)stream);
+  return a;
 }
 
-extern "C" int msocr_attn_beam(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                               int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                               int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                               int32_t* chunk_state_dev, void* stream) {
-  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
-                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, nullptr, stream);
-}
-// the same with the attention weights of every computed step stored to alpha_ws (msocr_attn_beam_alpha_bytes, 16-byte aligned)
-extern "C" int msocr_attn_beam_alpha(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                     int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                     int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                     int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
-  if (!alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
-                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
+// ctx_gates == nullptr: the general kernels, every shape of the envelope; otherwise the matrix-core kernels.  The forced, lexicon and
+// language-model kernels are in translation units of their own; so are the matrix-core kernels with the weight output on.
+static int attn_launch(const msocr_attn_desc* d, const AttnArgs& a, hipStream_t s) {
+  const bool mfma = d->ctx_gates != nullptr, beam = d->mode == MSOCR_ATTN_MODE_BEAM;
+  if (d->mode == MSOCR_ATTN_MODE_FORCED) return mfma ? msocr_internal_attn_forced_mfma(a, s) : msocr_internal_attn_general_forced(a, d->H, s);
+  if (d->lexicon) return mfma ? msocr_internal_attn_lexicon_mfma(a, s) : msocr_internal_attn_general_lexicon(a, d->H, s);
+  if (d->lm) return mfma ? msocr_internal_attn_lm_mfma(a, s) : msocr_internal_attn_general_lm(a, d->H, s);
+  if (!mfma) return msocr_internal_attn_general(a, d->H, beam, s);
+  if (beam) return a.alpha_out ? msocr_internal_attn_beam_mfma_alpha(a, s) : msocr_internal_attn_beam_mfma(a, s);
+  return a.alpha_out ? msocr_internal_attn_greedy_mfma_alpha(a, s) : msocr_internal_attn_greedy_mfma(a, s);
 }
 
-static int attn_beam_hoisted_impl(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                  const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                  const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
-                                  void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                  int32_t* chunk_state_dev, void* alpha_ws, void* stream, const msocr_lexicon* lex = nullptr,
-                                  int32_t* node_out = nullptr, const LmFusion* lmf = nullptr) {
-  if (!ctx_gates || ((uintptr_t)ctx_gates & 15)) return MSOCR_E_ARG;
-  if (ws && (!ws->h2h_p || !ws->whh_p || !ws->gen_p || (((uintptr_t)ws->h2h_p | (uintptr_t)ws->whh_p | (uintptr_t)ws->gen_p) & 15)))
-    return MSOCR_E_ARG;
-  return attn_beam_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                        fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out, lmf);
-}
-extern "C" int msocr_attn_beam_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                       const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                       const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id, int32_t* fin_step_out,
-                                       void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                       int32_t* chunk_state_dev, void* stream) {
-  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, nullptr, stream);
-}
-extern "C" int msocr_attn_beam_hoisted_alpha(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                             const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                             const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                             int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
-                                             const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, void* stream) {
-  if (!alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream);
+extern "C" int msocr_attn_decode(const msocr_attn_desc* d, void* stream) {
+  if (attn_desc_check(d)) return MSOCR_E_ARG;
+  return attn_launch(d, attn_args(d), (hipStream_t)stream);
 }
 
-// Lexicon-constrained beam decode (msocr.h): the entries above with the lexicon's prefix tree (device arrays) and the node trace
-// node_out [B][steps][beam] i32; alpha_ws required.  Same workspace, same finalize / n-best / confidence steps.
-extern "C" int64_t msocr_attn_lexicon_nodes_bytes(int B, int steps, int beam) {
+// the size of node_out (lexicon) and of ctx_out (language model): [B][steps][beam] i32, one entry per slot and step
+extern "C" int64_t msocr_attn_beam_slots_bytes(int B, int steps, int beam) {
   if (B <= 0 || steps <= 0 || beam <= 0) return 0;
   return (int64_t)B * steps * beam * 4;
-}
-extern "C" int msocr_attn_beam_lexicon(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                       int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                       int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                       int32_t* chunk_state_dev, void* alpha_ws, const msocr_lexicon* lex, int32_t* node_out, void* stream) {
-  if (!lex || !node_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
-                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
-}
-extern "C" int msocr_attn_beam_lexicon_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                               const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                               const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                               int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
-                                               const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws,
-                                               const msocr_lexicon* lex, int32_t* node_out, void* stream) {
-  if (!lex || !node_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, lex, node_out);
-}
-
-// Beam decode with a character n-gram language model fused in (msocr.h): the _alpha entries above with the model's dense table (a device
-// array), the weight of its addend and the context trace ctx_out [B][steps][beam] i32; alpha_ws required.  Same workspace, same
-// finalize / n-best / confidence steps.
-extern "C" int64_t msocr_attn_lm_ctx_bytes(int B, int steps, int beam) {
-  if (B <= 0 || steps <= 0 || beam <= 0) return 0;
-  return (int64_t)B * steps * beam * 4;
-}
-extern "C" int msocr_attn_beam_lm(const float* batch_H, const float* proj_H, const msocr_attn_weights* w, int B, int T, int H, int V,
-                                  int steps, int beam, const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                  int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev, const int32_t* chunk_size_dev,
-                                  int32_t* chunk_state_dev, void* alpha_ws, const msocr_charlm* lm, float lm_weight, int32_t* ctx_out,
-                                  void* stream) {
-  if (!lm || !ctx_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  const LmFusion lmf{lm, lm_weight, ctx_out};
-  return attn_beam_impl(batch_H, proj_H, nullptr, w, nullptr, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id, fin_step_out,
-                        workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, nullptr, nullptr, &lmf);
-}
-extern "C" int msocr_attn_beam_lm_hoisted(const float* batch_H, const float* proj_H, const float* ctx_gates, const msocr_attn_weights* w,
-                                          const msocr_attn_split_weights* ws, int B, int T, int H, int V, int steps, int beam,
-                                          const float* lp_dev, float temperature, int sos_id, int eos_id, int blank_id,
-                                          int32_t* fin_step_out, void* workspace, const int32_t* chunk_id_dev,
-                                          const int32_t* chunk_size_dev, int32_t* chunk_state_dev, void* alpha_ws, const msocr_charlm* lm,
-                                          float lm_weight, int32_t* ctx_out, void* stream) {
-  if (!lm || !ctx_out || !alpha_ws || ((uintptr_t)alpha_ws & 15)) return MSOCR_E_ARG;
-  const LmFusion lmf{lm, lm_weight, ctx_out};
-  return attn_beam_hoisted_impl(batch_H, proj_H, ctx_gates, w, ws, B, T, H, V, steps, beam, lp_dev, temperature, sos_id, eos_id, blank_id,
-                                fin_step_out, workspace, chunk_id_dev, chunk_size_dev, chunk_state_dev, alpha_ws, stream, nullptr, nullptr,
-                                &lmf);
 }
 
 // the four parts of a finished beam workspace (device memory, or a host copy of it), for the steps that read it back
@@ -529,25 +394,18 @@ static inline BeamTrace beam_ws_trace(const void* workspace, int B, int steps, i
   return w;
 }
 
-static int attn_beam_finalize_impl(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev, float* logits_out,
-                                   int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out, void* stream) {
+// alpha_ws [B][steps][beam][T] (a beam decode's alpha_out), T and alpha_out [B][steps][T]: also gathers the path's attention weights;
+// NULL, 0, NULL: off (a T or an alpha_out without alpha_ws is refused)
+extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
+                                        float* logits_out, int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out,
+                                        void* stream) {
   if (!workspace || !trun_dev || !logits_out || !ids_out || B <= 0 || V <= 0 || steps <= 0 || steps > 64 || beam < 1 || beam > 16)
     return MSOCR_E_ARG;
+  if (alpha_ws ? misaligned16(alpha_ws) || !alpha_out || T <= 0 || T > 64 : alpha_out || T) return MSOCR_E_ARG;
   const BeamTrace w = beam_ws_trace(workspace, B, steps, beam, V);
   MSOCR_LAUNCH(attn_beam_finalize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, w.logits, w.back, w.tokv, w.best_at, trun_dev, V,
                steps, beam, logits_out, ids_out, (const float*)alpha_ws, T, alpha_out);
   return LAUNCH_OK();
-}
-extern "C" int msocr_attn_beam_finalize(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
-                                        float* logits_out, int32_t* ids_out, void* stream) {
-  return attn_beam_finalize_impl(workspace, B, V, steps, beam, trun_dev, logits_out, ids_out, nullptr, 0, nullptr, stream);
-}
-// also gathers the path's attention weights from alpha_ws [B][steps][beam][T] (msocr_attn_beam_alpha) into alpha_out [B][steps][T]
-extern "C" int msocr_attn_beam_finalize_alpha(const void* workspace, int B, int V, int steps, int beam, const int32_t* trun_dev,
-                                              float* logits_out, int32_t* ids_out, const void* alpha_ws, int T, float* alpha_out,
-                                              void* stream) {
-  if (!alpha_ws || ((uintptr_t)alpha_ws & 15) || !alpha_out || T <= 0 || T > 64) return MSOCR_E_ARG;
-  return attn_beam_finalize_impl(workspace, B, V, steps, beam, trun_dev, logits_out, ids_out, alpha_ws, T, alpha_out, stream);
 }
 
 // --------------------------------------------------------------------------------------------- confidence

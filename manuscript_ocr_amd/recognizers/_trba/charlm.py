@@ -165,4 +165,4 @@ class CharLM:
         return self._device[dev]
 
     def struct(self, device):
-        return ctypes.byref(self.to(device)[1])
+        return ctypes.pointer(self.to(device)[1])  # what the field AttnDesc.lm takes

@@ -157,7 +157,7 @@ class Lexicon:
         return self._device[dev]
 
     def struct(self, device):
-        return ctypes.byref(self.to(device)[4])
+        return ctypes.pointer(self.to(device)[4])  # what the field AttnDesc.lexicon takes
 
     # ------------------------------------------------------------------------------------- nearest words
     def _check_wordlist(self):

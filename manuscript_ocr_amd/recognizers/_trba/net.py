@@ -208,7 +208,7 @@ class AttnDecoder:
             "gen_b": sd["attn.generator.bias"].float().contiguous().to(dev),
         }
         # rows of rnn.weight_ih[:, :H] reordered unit-major (row j*4+g): the hoisted context product of the beam kernel
-        # (msocr_attn_beam_hoisted) is one GEMM batch_H x this^T -> [B*T, H*4]
+        # (msocr_attn_decode with ctx_gates) is one GEMM batch_H x this^T -> [B*T, H*4]
         self.att["wih_ctx_rows"] = ops.attach_split(w_ih[:, :H].reshape(4, H, H).permute(1, 0, 2).reshape(4 * H, 1, 1, H).contiguous().to(dev),
                                                     split)
         aw = nat.AttnWeights()
@@ -229,7 +229,7 @@ class AttnDecoder:
             self._asw = asw
 
     def _matrix_core(self, T, beam_size=None):
-        """Whether a decode of T frames runs on the matrix-core kernels (csrc/attn_beam_mfma.hip, the `_hoisted` entries): hidden 256,
+        """Whether a decode of T frames runs on the matrix-core kernels (csrc/attn_beam_mfma.hip: a descriptor with ctx_gates): hidden 256,
         <= 256 tokens, <= 48 frames; greedy also needs the split weights (precision "fp32"), beam a width <= 8 (without the split
         weights it runs on exact-f32 MFMA).  Everything else, and everything under HOIST_CTX = False, runs on the general kernel."""
         if not HOIST_CTX or self.Hd != 256 or self.V > 256 or T > 48:
@@ -241,6 +241,25 @@ class AttnDecoder:
         B, T, H = batch_H.shape
         return _gemm(batch_H.reshape(B * T, H), self.att["wih_ctx_rows"], None)
 
+    def _desc(self, mode, batch_H, proj_H, steps, sos_id, blank_id, ctx_gates, beam_size=None):
+        """A descriptor for msocr_attn_decode with the fields every mode sets.  Where the decode runs on the matrix-core kernels
+        (`_matrix_core`) that includes the hoisted context gates, W_ih[:, :H] batch_H_t for every frame once per call instead of
+        W_ih[:, :H] ctx in every step (ctx_gates, or computed here), and the split weights if there are any (exact-f32 MFMA without)."""
+        B, T, H = batch_H.shape
+        d = nat.AttnDesc(struct_bytes=ctypes.sizeof(nat.AttnDesc), mode=mode, B=B, T=T, H=H, V=self.V, steps=steps, sos_id=sos_id,
+                         blank_id=-1 if blank_id is None else blank_id, batch_H=batch_H.data_ptr(), proj_H=proj_H.data_ptr(),
+                         w=ctypes.pointer(self._aw))
+        if self._matrix_core(T, beam_size):
+            d.keep = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates  # alive as long as the descriptor
+            d.ctx_gates = d.keep.data_ptr()
+            if self._asw is not None:
+                d.ws = ctypes.pointer(self._asw)
+        return d
+
+    @staticmethod
+    def _decode(d, what):
+        nat.check(nat.lib().msocr_attn_decode(ctypes.byref(d), ops._stream()), what)
+
     def greedy(self, batch_H, proj_H, max_len, sos_id, eos_id, blank_id, ctx_gates=None, want_alpha=False, alpha_out=None):
         """ctx_gates: this call's rows of a ctx_gates() result computed beforehand (used only where the kernel takes them).
         want_alpha: also return the attention weights of every step, [B, steps, T] f32 (alpha_out: a buffer of that shape to write
@@ -249,26 +268,15 @@ class AttnDecoder:
         steps = max_len + 1
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         ids = torch.empty((B, steps), dtype=torch.int32, device=self.device)
-        blank = -1 if blank_id is None else blank_id
         al = None
         if want_alpha:
             al = alpha_out if alpha_out is not None else torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
             assert al.shape == (B, steps, T) and al.dtype == torch.float32 and al.is_contiguous() and al.is_cuda
-        if self._matrix_core(T):  # 32 crops per workgroup, split-operand products, hoisted context gates
-            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
-            head = (batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), ctypes.byref(self._asw), B, T, H, self.V,
-                    steps, sos_id, eos_id, blank, logits.data_ptr(), ids.data_ptr())
-            if al is None:
-                nat.check(nat.lib().msocr_attn_greedy_hoisted(*head, ops._stream()), "attn_greedy_hoisted")
-            else:
-                nat.check(nat.lib().msocr_attn_greedy_hoisted_alpha(*head, al.data_ptr(), ops._stream()), "attn_greedy_hoisted_alpha")
-        else:
-            head = (batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), B, T, H, self.V, steps, sos_id, eos_id, blank,
-                    logits.data_ptr(), ids.data_ptr())
-            if al is None:
-                nat.check(nat.lib().msocr_attn_greedy(*head, ops._stream()), "attn_greedy")
-            else:
-                nat.check(nat.lib().msocr_attn_greedy_alpha(*head, al.data_ptr(), ops._stream()), "attn_greedy_alpha")
+        d = self._desc(nat.ATTN_GREEDY, batch_H, proj_H, steps, sos_id, blank_id, ctx_gates)
+        d.eos_id, d.logits_out, d.ids_out = eos_id, logits.data_ptr(), ids.data_ptr()
+        if al is not None:
+            d.alpha_out = al.data_ptr()
+        self._decode(d, "attn_greedy")
         return (logits, ids, al) if want_alpha else (logits, ids)
 
     def forced(self, batch_H, proj_H, tok_in, sos_id, blank_id, ctx_gates=None):
@@ -280,16 +288,9 @@ class AttnDecoder:
         steps = tok_in.shape[1]
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         al = torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
-        blank = -1 if blank_id is None else blank_id
-        if self._matrix_core(T):
-            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
-            nat.check(nat.lib().msocr_attn_forced_hoisted(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw),
-                                                          ctypes.byref(self._asw), B, T, H, self.V, steps, tok_in.data_ptr(), sos_id, blank,
-                                                          logits.data_ptr(), al.data_ptr(), ops._stream()), "attn_forced_hoisted")
-        else:
-            nat.check(nat.lib().msocr_attn_forced(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), B, T, H, self.V, steps,
-                                                  tok_in.data_ptr(), sos_id, blank, logits.data_ptr(), al.data_ptr(), ops._stream()),
-                      "attn_forced")
+        d = self._desc(nat.ATTN_FORCED, batch_H, proj_H, steps, sos_id, blank_id, ctx_gates)
+        d.tok_in, d.logits_out, d.alpha_out = tok_in.data_ptr(), logits.data_ptr(), al.data_ptr()
+        self._decode(d, "attn_forced")
         return logits, al
 
     def seq_logp(self, logits, ids, trun_dev, temperature=1.0):
@@ -310,11 +311,11 @@ class AttnDecoder:
         want_alpha: a fourth result, the attention-weight trace [B, steps, beam, T] f32 for `beam_finalize(alpha_ws=...)` (slot-
         indexed like the logits trace; steps the early exit skips stay unwritten); alpha_ws: a buffer of that shape to use.
         lexicon (a recognizers.Lexicon built for this charset and max_len): the search is constrained to the lexicon's words
-        (msocr_attn_beam_lexicon(_hoisted)) and the result is always (workspace, fin_step, lp, alpha trace,
+        (the descriptor's lexicon field) and the result is always (workspace, fin_step, lp, alpha trace,
         nodes): nodes [B, steps, beam] i32, the trie node of every slot after every step (-1 = a dead slot; steps the early exit skips
         stay unwritten).  The workspace is read by beam_finalize / beam_nbest as a plain one is.  None: nothing changes.
         lm (a recognizers.CharLM for this charset and sos_id) with lm_weight (finite, >= 0): every candidate of a live hypothesis gains
-        lm_weight * log P_lm(token | context) (msocr_attn_beam_lm(_hoisted)) and the result is always
+        lm_weight * log P_lm(token | context) (the descriptor's lm field) and the result is always
         (workspace, fin_step, lp, alpha trace, ctx): ctx [B, steps, beam] i32, the language model's context of every slot after every
         step (steps the early exit skips stay unwritten).  The workspace holds the model's own logits and is read as a plain one is.
         Not together with a lexicon.  None: nothing changes."""
@@ -353,35 +354,25 @@ class AttnDecoder:
             aws = alpha_ws if alpha_ws is not None else torch.empty((B, steps, beam_size, T), dtype=torch.float32, device=self.device)
             assert aws.shape == (B, steps, beam_size, T) and aws.dtype == torch.float32 and aws.is_contiguous() and aws.is_cuda
             assert aws.numel() * 4 == nat.lib().msocr_attn_beam_alpha_bytes(B, steps, beam_size, T)
-        hoist = self._matrix_core(T, beam_size)
-        if hoist:  # W_ih[:, :H] batch_H_t for every frame, once per call instead of W_ih[:, :H] ctx in every step
-            ctxg = self.ctx_gates(batch_H) if ctx_gates is None else ctx_gates
+        d = self._desc(nat.ATTN_BEAM, batch_H, proj_H, steps, sos_id, blank_id, ctx_gates, beam_size)  # the context GEMM is not the decode's
         e = ops._prof_begin()
-        tail = (B, T, H, self.V, steps, beam_size, lp.data_ptr() if lp is not None else None, float(temperature), sos_id, eos_id,
-                -1 if blank_id is None else blank_id, fin.data_ptr(), ws.data_ptr(),
-                chunks[0].data_ptr() if chunks else None, chunks[1].data_ptr() if chunks else None,
-                chunks[2].data_ptr() if chunks else None)
-        L = nat.lib()
-        nodes = None
-        if lexicon is not None:  # the constrained kernels: same arguments, then the trie and the node trace
+        d.beam, d.eos_id, d.temperature = beam_size, eos_id, float(temperature)
+        d.workspace, d.fin_step_out = ws.data_ptr(), fin.data_ptr()
+        if lp is not None:
+            d.lp = lp.data_ptr()
+        if chunks:
+            d.chunk_id, d.chunk_size, d.chunk_state = (c.data_ptr() for c in chunks[:3])
+        if aws is not None:
+            d.alpha_out = aws.data_ptr()
+        if lexicon is not None:  # the constrained kernels: the trie and the node trace
             nodes = torch.empty((B, steps, beam_size), dtype=torch.int32, device=self.device)
-            assert nodes.numel() * 4 == L.msocr_attn_lexicon_nodes_bytes(B, steps, beam_size)
-            tail += (aws.data_ptr(), lexicon.struct(self.device), nodes.data_ptr(), ops._stream())
-        elif lm is not None:  # the fused kernels: same arguments, then the table, the weight and the context trace
+            assert nodes.numel() * 4 == nat.lib().msocr_attn_beam_slots_bytes(B, steps, beam_size)
+            d.lexicon, d.node_out = lexicon.struct(self.device), nodes.data_ptr()
+        elif lm is not None:  # the fused kernels: the table, the weight and the context trace
             ctx_trace = torch.empty((B, steps, beam_size), dtype=torch.int32, device=self.device)
-            assert ctx_trace.numel() * 4 == L.msocr_attn_lm_ctx_bytes(B, steps, beam_size)
-            tail += (aws.data_ptr(), lm.struct(self.device), float(lm_weight), ctx_trace.data_ptr(), ops._stream())
-        else:
-            tail += (ops._stream(),) if aws is None else (aws.data_ptr(), ops._stream())
-        if hoist:  # split-operand products with the split weights, exact-f32 MFMA without them
-            asw = ctypes.byref(self._asw) if self._asw is not None else None
-            fn = (L.msocr_attn_beam_lexicon_hoisted if lexicon is not None else L.msocr_attn_beam_lm_hoisted if lm is not None else
-                  L.msocr_attn_beam_hoisted if aws is None else L.msocr_attn_beam_hoisted_alpha)
-            nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctxg.data_ptr(), ctypes.byref(self._aw), asw, *tail), "attn_beam_hoisted")
-        else:
-            fn = (L.msocr_attn_beam_lexicon if lexicon is not None else L.msocr_attn_beam_lm if lm is not None else
-                  L.msocr_attn_beam if aws is None else L.msocr_attn_beam_alpha)
-            nat.check(fn(batch_H.data_ptr(), proj_H.data_ptr(), ctypes.byref(self._aw), *tail), "attn_beam")
+            assert ctx_trace.numel() * 4 == nat.lib().msocr_attn_beam_slots_bytes(B, steps, beam_size)
+            d.lm, d.lm_weight, d.ctx_out = lm.struct(self.device), float(lm_weight), ctx_trace.data_ptr()
+        self._decode(d, "attn_beam")
         # SURVEY.md 8d, per decode step: proj_H + batch_H (shared by the beams) + LSTMCell W_ih (ctx part + one-hot rows), W_hh,
         # generator, h2h + per row (h, c state + logits); the launch runs up to `steps` of them (chunk-level early exit)
         V, R = self.V, B * beam_size
@@ -398,17 +389,16 @@ class AttnDecoder:
         t >= t_run (alpha_out: a buffer of that shape to write them to)."""
         logits = torch.empty((B, steps, self.V), dtype=torch.float32, device=self.device)
         ids = torch.empty((B, steps), dtype=torch.int32, device=self.device)
-        if alpha_ws is None:
-            nat.check(nat.lib().msocr_attn_beam_finalize(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(), logits.data_ptr(),
-                                                         ids.data_ptr(), ops._stream()), "attn_beam_finalize")
-            return logits, ids
-        T = alpha_ws.shape[-1]
-        assert alpha_ws.shape == (B, steps, beam_size, T) and alpha_ws.dtype == torch.float32 and alpha_ws.is_contiguous()
-        al = alpha_out if alpha_out is not None else torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
-        assert al.shape == (B, steps, T) and al.dtype == torch.float32 and al.is_contiguous() and al.is_cuda
-        nat.check(nat.lib().msocr_attn_beam_finalize_alpha(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(),
-                                                           logits.data_ptr(), ids.data_ptr(), alpha_ws.data_ptr(), T, al.data_ptr(),
-                                                           ops._stream()), "attn_beam_finalize_alpha")
+        al, T = None, 0
+        if alpha_ws is not None:
+            T = alpha_ws.shape[-1]
+            assert alpha_ws.shape == (B, steps, beam_size, T) and alpha_ws.dtype == torch.float32 and alpha_ws.is_contiguous()
+            al = alpha_out if alpha_out is not None else torch.empty((B, steps, T), dtype=torch.float32, device=self.device)
+            assert al.shape == (B, steps, T) and al.dtype == torch.float32 and al.is_contiguous() and al.is_cuda
+        nat.check(nat.lib().msocr_attn_beam_finalize(ws.data_ptr(), B, self.V, steps, beam_size, trun_dev.data_ptr(), logits.data_ptr(),
+                                                     ids.data_ptr(), alpha_ws.data_ptr() if al is not None else None, T,
+                                                     al.data_ptr() if al is not None else None, ops._stream()), "attn_beam_finalize")
+        return (logits, ids) if al is None else (logits, ids, al)
         return logits, ids, al
 
     def beam_nbest(self, ws, B, steps, beam_size, trun_dev, n_best, eos_id):

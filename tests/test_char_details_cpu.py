@@ -8,8 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-NEW_SYMBOLS = {"msocr_attn_greedy_alpha", "msocr_attn_greedy_hoisted_alpha", "msocr_attn_beam_alpha_bytes", "msocr_attn_beam_alpha",
-               "msocr_attn_beam_hoisted_alpha", "msocr_attn_beam_finalize_alpha", "msocr_seq_char_details"}
+NEW_SYMBOLS = {"msocr_attn_decode", "msocr_attn_beam_alpha_bytes", "msocr_attn_beam_finalize", "msocr_seq_char_details"}
 
 
 def test_frame_to_pixel_mapping():

@@ -176,10 +176,10 @@ def test_constructor_refusals():
 
 def test_new_symbols_are_exported():
     L = nat.lib()
-    for name in ("msocr_attn_lm_ctx_bytes", "msocr_attn_beam_lm", "msocr_attn_beam_lm_hoisted"):
+    for name in ("msocr_attn_beam_slots_bytes", "msocr_attn_decode"):
         assert hasattr(L, name)
-    assert L.msocr_attn_lm_ctx_bytes(37, 9, 8) == 37 * 9 * 8 * 4
-    assert L.msocr_attn_lm_ctx_bytes(0, 9, 8) == 0
+    assert L.msocr_attn_beam_slots_bytes(37, 9, 8) == 37 * 9 * 8 * 4
+    assert L.msocr_attn_beam_slots_bytes(0, 9, 8) == 0
     st = nat.CharLMTable()
     st.table, st.order, st.V, st.n_ctx = 16, 3, 194, 194 * 194
     assert (st.order, st.V, st.n_ctx) == (3, 194, 37636)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_call import attn_decode
 from manuscript_ocr_amd import _native as nat
 from manuscript_ocr_amd.recognizers._trba.transforms import pack_targets
 from test_gpu_seq_f64 import _replay
@@ -140,7 +141,7 @@ def test_seq_logp_host_flags_an_id_outside_the_charset():
 
 
 # ------------------------------------------------------------------------------------------------ C ABI
-NEW_SYMBOLS = ("msocr_attn_forced", "msocr_attn_forced_hoisted", "msocr_seq_logp", "msocr_seq_logp_host")
+NEW_SYMBOLS = ("msocr_attn_decode", "msocr_seq_logp", "msocr_seq_logp_host")
 
 
 def test_library_exports_the_forced_decode():
@@ -169,12 +170,12 @@ def _host_args(B=2, T=13, H=256, V=194, steps=26):
 
 def _forced_rc(hoisted, B=2, T=13, H=256, V=194, steps=26, sos=1, null=None, no_ws=False):
     w, ws, b, _keep = _host_args()
-    p = {k: (None if k == null else v.ctypes.data) for k, v in b.items()}
-    wp = None if null == "w" else ctypes.byref(w)
-    if hoisted:
-        return nat.lib().msocr_attn_forced_hoisted(p["bh"], p["ph"], p["cg"], wp, None if no_ws else ctypes.byref(ws), B, T, H, V, steps,
-                                                   p["tok"], sos, -1, p["lg"], p["al"], None)
-    return nat.lib().msocr_attn_forced(p["bh"], p["ph"], wp, B, T, H, V, steps, p["tok"], sos, -1, p["lg"], p["al"], None)
+    p = {k: (None if k == null else v) for k, v in b.items()}
+    bufs = {"batch_H": p["bh"], "proj_H": p["ph"], "w": None if null == "w" else w, "tok_in": p["tok"], "logits_out": p["lg"],
+            "alpha_out": p["al"]}
+    if hoisted:  # the matrix-core route: ctx_gates and the split weights
+        bufs.update(ctx_gates=p["cg"], ws=None if no_ws else ws)
+    return attn_decode(nat.ATTN_FORCED, bufs, B=B, T=T, H=H, V=V, steps=steps, sos_id=sos, blank_id=-1)
 
 
 def test_forced_entry_points_refuse_bad_arguments_without_a_device():
@@ -187,6 +188,62 @@ def test_forced_entry_points_refuse_bad_arguments_without_a_device():
     # the matrix-core entry point takes its kernel's shapes only, and needs the split weights
     for bad in (dict(H=128), dict(H=320), dict(V=257), dict(T=49), dict(no_ws=True)):
         assert _forced_rc(True, **bad) == E_ARG, bad
+
+
+# The descriptor itself.  Every call here is refused, so no device is needed: the "good" descriptors are complete but for one later
+# argument (sos_id outside the charset), which shows that what comes before it was accepted.
+def _desc_rc(mode, extra=(), drop=(), **fields):
+    """A complete descriptor of `mode` over host stand-ins (B 2, T 13, H 256, V 194), plus the stand-in buffer `bufs[name]` for every
+    field named in `extra`, minus the fields in `drop`."""
+    w, _ws, b, _keep = _host_args()
+    i32 = np.zeros((2, 26, 8), dtype=np.int32)
+    spare = np.zeros(2 * 26 * 8 * 194 + 64, dtype=np.float32)  # 16-byte aligned like every numpy allocation of this size
+    assert spare.ctypes.data % 16 == 0
+    lex, lm = nat.LexiconArrays(), nat.CharLMTable()
+    lex.edge_begin = lex.edge_tok = lex.edge_child = lex.terminal = i32.ctypes.data
+    lex.n_nodes, lex.n_edges = 1, 0
+    lm.table, lm.order, lm.V, lm.n_ctx = spare.ctypes.data, 1, 194, 1
+    pool = {"batch_H": b["bh"], "proj_H": b["ph"], "w": w, "tok_in": b["tok"], "logits_out": b["lg"], "ids_out": i32, "alpha_out": spare,
+            "workspace": spare, "fin_step_out": i32, "lexicon": lex, "node_out": i32, "lm": lm, "ctx_out": i32}
+    own = {nat.ATTN_GREEDY: ("logits_out", "ids_out"), nat.ATTN_BEAM: ("workspace", "fin_step_out"),
+           nat.ATTN_FORCED: ("tok_in", "logits_out", "alpha_out")}.get(mode, ())
+    names = [n for n in ("batch_H", "proj_H", "w") + own + tuple(extra) if n not in drop]
+    fields = {**dict(B=2, T=13, H=256, V=194, steps=26, beam=8, temperature=1.0, sos_id=1, eos_id=2, blank_id=-1), **fields}
+    return attn_decode(mode, {n: pool[n] for n in names}, **fields)
+
+
+MODES = (nat.ATTN_GREEDY, nat.ATTN_BEAM, nat.ATTN_FORCED)
+
+
+def test_attn_desc_struct_bytes_and_mode():
+    size = ctypes.sizeof(nat.AttnDesc)
+    for mode in MODES:
+        # the right size is accepted: the call gets as far as the weights, which are missing
+        assert _desc_rc(mode, drop=("w",), struct_bytes=size) == E_ARG
+        # a wrong one is refused before anything else is read: nothing else in this descriptor is valid either
+        for bad in (0, size + 8):
+            assert attn_decode(mode, {}, struct_bytes=bad) == E_ARG, (mode, bad)
+    for mode in (3, -1):
+        assert _desc_rc(mode) == E_ARG, mode
+    assert nat.lib().msocr_attn_decode(None, None) == E_ARG
+
+
+def test_attn_desc_beam_options_need_beam_mode_their_trace_and_the_weight_trace():
+    both = ("alpha_out", "lexicon", "node_out", "lm", "ctx_out")
+    assert _desc_rc(nat.ATTN_BEAM, extra=both, lm_weight=0.5) == E_ARG                       # a lexicon and a language model together
+    for opt, trace in (("lexicon", "node_out"), ("lm", "ctx_out")):
+        for mode in (nat.ATTN_GREEDY, nat.ATTN_FORCED):
+            assert _desc_rc(mode, extra=(opt,)) == E_ARG, (opt, mode)                           # outside beam mode
+            assert _desc_rc(mode, extra=("alpha_out", opt, trace), lm_weight=0.5) == E_ARG, (opt, mode)
+        assert _desc_rc(nat.ATTN_BEAM, extra=(opt, trace), lm_weight=0.5) == E_ARG, opt         # without alpha_out
+        assert _desc_rc(nat.ATTN_BEAM, extra=("alpha_out", opt), lm_weight=0.5) == E_ARG, opt   # without its own trace
+        assert _desc_rc(nat.ATTN_BEAM, extra=("alpha_out", trace)) == E_ARG, opt                # the trace without the option
+
+
+def test_attn_desc_refuses_a_pointer_its_mode_does_not_read():
+    for mode, foreign in ((nat.ATTN_BEAM, "tok_in"), (nat.ATTN_GREEDY, "workspace"), (nat.ATTN_FORCED, "ids_out"),
+                          (nat.ATTN_GREEDY, "tok_in"), (nat.ATTN_BEAM, "logits_out"), (nat.ATTN_FORCED, "fin_step_out")):
+        assert _desc_rc(mode, extra=(foreign,)) == E_ARG, (mode, foreign)
 
 
 def test_seq_logp_entry_points_refuse_bad_arguments_without_a_device():

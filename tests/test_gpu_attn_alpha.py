@@ -1,4 +1,4 @@
-"""The attention-weight output of the decode kernels (the `_alpha` entry points of csrc/trba_kernels.hip: attn_beam_mfma_alpha.hip,
+"""The attention-weight output of the decode kernels (msocr_attn_decode with alpha_out, csrc/trba_kernels.hip: attn_beam_mfma_alpha.hip,
 attn_general.hip, attn_beam_finalize_kernel) and msocr_seq_char_details, against float64.
 
 Fixtures are those of test_gpu_seq_f64.py (copied, not imported): the decoder of synth.trba_state_dict(V, H, seed, rnn_scale=4.0),
@@ -16,7 +16,7 @@ the yardstick.
     are exactly zero after finalize; the beam cases run with two chunks and the chunked early exit, and hold rows with t_run < steps.
 (4) off means off: logits, ids and fin_step with the output on are bit-identical to the plain entry points.
 (5) msocr_seq_char_details against numpy f64 of the device's own inputs.
-(6) the new entry points reject what the plain ones reject, and a null or misaligned alpha workspace.
+(6) a descriptor with alpha_out is refused where the plain one is, and for a misaligned alpha workspace.
 
 Measured on MI355X (pytest -s prints them): e_dev, e_f32, e_dev / e_f32 per case
   a-mfma-greedy              4.2e-7  1.24e-6  0.34        d-general-greedy           1.9e-7  3.9e-7  0.49
@@ -26,12 +26,11 @@ Measured on MI355X (pytest -s prints them): e_dev, e_f32, e_dev / e_f32 per case
 so the first bound (1.4e-6 .. 6.0e-6 here) decides everywhere and the cap of 1e-5 nowhere; row sums within 3.2e-7 of 1 (bound
 3.8e-6); seq_char_details: prob within 2.6e-7, centre within 4.7e-7 (T 13) / 1.9e-6 (T 64, half an ulp of a centre near 32).
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from attn_call import attn_decode
 from manuscript_ocr_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -349,13 +348,10 @@ def _greedy_rc(B, T, H, V, steps, sos=SOS, hoisted=False):
     from manuscript_ocr_amd import _native as nat
     from manuscript_ocr_amd import ops
     b, aw, asw = _attn_buffers(B, T, H, V, steps, 1)
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "logits_out": b["logits"], "ids_out": b["ids"], "alpha_out": b["alpha"]}
     if hoisted:
-        rc = nat.lib().msocr_attn_greedy_hoisted_alpha(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw),
-                                                       ctypes.byref(asw), B, T, H, V, steps, sos, EOS, -1, b["logits"].data_ptr(),
-                                                       b["ids"].data_ptr(), b["alpha"].data_ptr(), ops._stream())
-    else:
-        rc = nat.lib().msocr_attn_greedy_alpha(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), B, T, H, V, steps, sos, EOS, -1,
-                                               b["logits"].data_ptr(), b["ids"].data_ptr(), b["alpha"].data_ptr(), ops._stream())
+        bufs.update(ctx_gates=b["ctx"], ws=asw)
+    rc = attn_decode(nat.ATTN_GREEDY, bufs, B=B, T=T, H=H, V=V, steps=steps, sos_id=sos, eos_id=EOS, blank_id=-1, stream=ops._stream())
     assert rc == 0 or _untouched(b)
     return rc
 
@@ -364,20 +360,19 @@ def _beam_rc(B, T, H, V, steps, K, sos=SOS, ctx=False, alpha_ws="ok"):
     from manuscript_ocr_amd import _native as nat
     from manuscript_ocr_amd import ops
     b, aw, asw = _attn_buffers(B, T, H, V, steps, K)
-    ap = {"ok": b["alpha_ws"].data_ptr(), "null": None, "misaligned": b["alpha_ws"].data_ptr() + 4}[alpha_ws]
-    tail = (B, T, H, V, steps, K, b["lp"].data_ptr(), 1.7, sos, EOS, -1, b["fin"].data_ptr(), b["ws"].data_ptr(), None, None, None, ap,
-            ops._stream())
+    ap = {"ok": b["alpha_ws"].data_ptr(), "misaligned": b["alpha_ws"].data_ptr() + 4}[alpha_ws]
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "lp": b["lp"], "fin_step_out": b["fin"], "workspace": b["ws"], "alpha_out": ap}
     if ctx:
-        rc = nat.lib().msocr_attn_beam_hoisted_alpha(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw), None, *tail)
-    else:
-        rc = nat.lib().msocr_attn_beam_alpha(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), *tail)
+        bufs["ctx_gates"] = b["ctx"]
+    rc = attn_decode(nat.ATTN_BEAM, bufs, B=B, T=T, H=H, V=V, steps=steps, beam=K, temperature=1.7, sos_id=sos, eos_id=EOS, blank_id=-1,
+                     stream=ops._stream())
     assert rc == 0 or _untouched(b)
     return rc
 
 
 def test_alpha_entry_points_reject_what_the_plain_ones_reject(cuda):
-    """The shapes of test_c_abi_rejects_shapes_outside_the_envelope through the `_alpha` entry points, plus a null and a misaligned
-    alpha workspace; buffers sized for the rejected shape, the alpha buffers' sentinels untouched after every rejection."""
+    """The shapes of test_c_abi_rejects_shapes_outside_the_envelope through descriptors with alpha_out, plus a misaligned alpha
+    workspace and the finalize step's alpha arguments; buffers sized for the rejected shape, the alpha buffers' sentinels untouched after every rejection."""
     from manuscript_ocr_amd import _native as nat
     from manuscript_ocr_amd import ops
     B, T_DEF, STEPS_G, STEPS_B = 2, 13, 26, 25
@@ -399,14 +394,14 @@ def test_alpha_entry_points_reject_what_the_plain_ones_reject(cuda):
     assert _greedy_rc(B, T_DEF, 256, 257, STEPS_G, hoisted=True) == E_ARG
     assert _beam_rc(B, T_DEF, 256, 194, STEPS_B, 12, ctx=True) == E_ARG    # context gates on a general shape
     assert _beam_rc(B, T_DEF, 128, 194, STEPS_B, 8, ctx=True) == E_ARG
-    # the alpha workspace itself: required, 16-byte aligned (accepted shapes otherwise)
+    # the alpha workspace itself: 16-byte aligned (accepted shapes otherwise).  A NULL one is the plain decode now, not an error:
+    # "the weight entry without its workspace" cannot be written as a descriptor.
     for ctx in (False, True):
-        assert _beam_rc(B, T_DEF, 256, 194, STEPS_B, 8, ctx=ctx, alpha_ws="null") == E_ARG
         assert _beam_rc(B, T_DEF, 256, 194, STEPS_B, 8, ctx=ctx, alpha_ws="misaligned") == E_ARG
     L = nat.lib()
     b, _, _ = _attn_buffers(B, T_DEF, 256, 194, 65, 8)
-    fz = lambda steps, ap, T, out: L.msocr_attn_beam_finalize_alpha(b["ws"].data_ptr(), B, 194, steps, 8, b["trun"].data_ptr(),
-                                                                    b["logits"].data_ptr(), b["ids"].data_ptr(), ap, T, out, ops._stream())
+    fz = lambda steps, ap, T, out: L.msocr_attn_beam_finalize(b["ws"].data_ptr(), B, 194, steps, 8, b["trun"].data_ptr(),
+                                                              b["logits"].data_ptr(), b["ids"].data_ptr(), ap, T, out, ops._stream())
     ws_p, out_p = b["alpha_ws"].data_ptr(), b["alpha"].data_ptr()
     assert fz(65, ws_p, T_DEF, out_p) == E_ARG
     assert fz(STEPS_B, None, T_DEF, out_p) == E_ARG
@@ -429,3 +424,50 @@ def test_alpha_entry_points_reject_what_the_plain_ones_reject(cuda):
     assert _beam_rc(B, T_DEF, 512, 194, STEPS_B, 8) == 0
     assert _beam_rc(B, 48, 256, 256, STEPS_B, 8, ctx=True) == 0
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------ (7) the one finalize entry
+def test_finalize_with_and_without_the_alpha_arguments(cuda):
+    """msocr_attn_beam_finalize on a hand-filled workspace (the random fill of test_nbest_cpu.py; B 5, steps 4, beam 3, V 7, T 6,
+    t_run 1 .. steps): with NULL, 0, NULL nothing writes to an attention-weight buffer; with the arguments set the logits and ids
+    are those of the NULL call bit for bit, and the gathered weights are a numpy walk of the back-pointers, zeros for t >= t_run."""
+    from manuscript_ocr_amd import _native as nat
+    from manuscript_ocr_amd import ops
+    from test_nbest_cpu import _pack, _workspace
+    L = nat.lib()
+    B, steps, K, V, T = 5, 4, 3, 7, 6
+    logits, back, tokv, best_at = _workspace(B, V, steps, K, seed=11)
+    ws = torch.from_numpy(_pack(logits, back, tokv, best_at)).cuda()
+    assert ws.numel() == L.msocr_attn_beam_workspace_bytes(B, steps, K, V)
+    aws_h = np.random.default_rng(12).random((B, steps, K, T), dtype=np.float32)
+    aws = torch.from_numpy(aws_h).cuda()
+    assert aws.numel() * 4 == L.msocr_attn_beam_alpha_bytes(B, steps, K, T)
+    trun_h = np.array([4, 1, 3, 2, 4], dtype=np.int32)
+    trun = torch.from_numpy(trun_h).cuda()
+    big, al = _guarded(B, steps, T)
+
+    def run(alpha_ws, T_, alpha_out):
+        lg = torch.full((B, steps, V), SENT, dtype=torch.float32, device="cuda")
+        ids = torch.full((B, steps), -7, dtype=torch.int32, device="cuda")
+        assert L.msocr_attn_beam_finalize(ws.data_ptr(), B, V, steps, K, trun.data_ptr(), lg.data_ptr(), ids.data_ptr(), alpha_ws, T_,
+                                          alpha_out, ops._stream()) == 0
+        torch.cuda.synchronize()
+        return lg.cpu().numpy(), ids.cpu().numpy()
+
+    lg0, ids0 = run(None, 0, None)
+    assert bool((big == SENT).all())  # off: the buffer the next call writes is still untouched
+    lg1, ids1 = run(aws.data_ptr(), T, al.data_ptr())
+    assert np.array_equal(lg0.view(np.int32), lg1.view(np.int32)) and np.array_equal(ids0, ids1)
+    exp_lg = np.full((B, steps, V), SENT, dtype=np.float32)  # rows t >= t_run are not written
+    exp_ids = np.full((B, steps), -1, dtype=np.int32)
+    exp_al = np.zeros((B, steps, T), dtype=np.float32)
+    for b in range(B):
+        cur = int(best_at[b, trun_h[b] - 1])
+        for t in range(trun_h[b] - 1, -1, -1):
+            exp_ids[b, t] = tokv[b, t, cur]
+            cur = int(back[b, t, cur])  # the slot whose logits and weights produced the token
+            exp_lg[b, t], exp_al[b, t] = logits[b, t, cur], aws_h[b, t, cur]
+    assert np.array_equal(ids1, exp_ids) and np.array_equal(lg1.view(np.int32), exp_lg.view(np.int32))
+    got = al.cpu().numpy()
+    assert np.array_equal(got.view(np.int32), exp_al.view(np.int32)) and (got[np.arange(steps)[None, :] >= trun_h[:, None]] == 0).all()
+    assert _guards_intact(big)

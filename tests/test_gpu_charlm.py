@@ -1,5 +1,5 @@
-"""The beam decode fused with a character n-gram language model, on the device: msocr_attn_beam_lm
-(csrc/attn_general_lm.hip) and msocr_attn_beam_lm_hoisted (csrc/attn_lm_mfma.hip) on the decoder fixtures of test_gpu_seq_f64.py (its
+"""The beam decode fused with a character n-gram language model, on the device: msocr_attn_decode with lm
+(csrc/attn_general_lm.hip on the general route, csrc/attn_lm_mfma.hip on the matrix cores) on the decoder fixtures of test_gpu_seq_f64.py (its
 inputs, decoders, oracle and bounds) and the kernel cases of test_gpu_lexicon.py, then the switch through TRBA and Pipeline on
 test_gpu_nbest.py's pipeline fixture.
 
@@ -18,12 +18,11 @@ Tables: log_softmax(2 * randn) per context, seeded, with three special columns a
 fixture charsets have no <BLANK>; the last token stands where the shipped charset has it).  Order 3 where V <= 256, order 2 above.
 The condition of (2) was checked on the CPU before this file was written, with E_REL_MAX * max|logit| standing in for e_dev: see the
 figures in DESIGN.md section 4.16."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from attn_call import attn_decode
 from test_gpu_lexicon import KERNEL_CASES
 from test_gpu_nbest import _pages_and_maps, _pipe
 from test_gpu_seq_f64 import (B_DEF, DECISIVE_FACTOR, DECISIVE_MIN_FRACTION, E_REL_MAX, EOS, PAD, SOS, T_DEF, TAU, _attn_buffers, _inputs,
@@ -447,13 +446,12 @@ def _lm_rc(B, T, H, V, steps, K, hoisted, order=2, null=None, sos=SOS, weight=0.
     elems = max(int(st.n_ctx), 1) * max(V, st.V) if table_elems is None else table_elems
     table = (torch.zeros if elems <= 1 << 24 else torch.empty)((elems,), dtype=torch.float32, device="cuda")
     st.table = None if null == "table" else table.data_ptr()
-    tail = (B, T, H, V, steps, K, b["lp"].data_ptr(), 1.7, sos, EOS, -1, b["fin"].data_ptr(), b["ws"].data_ptr(), None, None, None,
-            None if null == "alpha_ws" else aws.data_ptr(), None if null == "lm" else ctypes.byref(st), float(weight),
-            None if null == "ctx_out" else ctx.data_ptr(), ops._stream())
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "lp": b["lp"], "fin_step_out": b["fin"], "workspace": b["ws"],
+            "alpha_out": None if null == "alpha_ws" else aws, "lm": None if null == "lm" else st, "ctx_out": None if null == "ctx_out" else ctx}
     if hoisted:
-        rc = nat.lib().msocr_attn_beam_lm_hoisted(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw), None, *tail)
-    else:
-        rc = nat.lib().msocr_attn_beam_lm(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), *tail)
+        bufs["ctx_gates"] = b["ctx"]
+    rc = attn_decode(nat.ATTN_BEAM, bufs, B=B, T=T, H=H, V=V, steps=steps, beam=K, temperature=1.7, sos_id=sos, eos_id=EOS, blank_id=-1,
+                     lm_weight=float(weight), stream=ops._stream())
     torch.cuda.synchronize()
     return rc
 

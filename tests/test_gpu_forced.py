@@ -1,4 +1,4 @@
-"""Forced (teacher-forced) decode on the device: msocr_attn_forced(_hoisted) and msocr_seq_logp behind
+"""Forced (teacher-forced) decode on the device: msocr_attn_decode in forced mode and msocr_seq_logp behind
 AttnDecoder.forced / seq_logp, TRBA.score and Pipeline.score_page.  Fixtures, replays and bounds are those of test_gpu_seq_f64.py
 (decoder of synth.trba_state_dict at rnn_scale 4, batch_H ~ N(0, 1.4^2)); nothing here depends on a discrete decision of the code
 under test: the decoder is told which tokens to follow.

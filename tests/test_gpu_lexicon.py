@@ -1,5 +1,5 @@
-"""The lexicon-constrained beam decode on the device: msocr_attn_beam_lexicon (csrc/attn_general_lexicon.hip) and
-msocr_attn_beam_lexicon_hoisted (csrc/attn_lexicon_mfma.hip) on the decoder fixtures of test_gpu_seq_f64.py (its inputs, decoders, oracle
+"""The lexicon-constrained beam decode on the device: msocr_attn_decode with lexicon (csrc/attn_general_lexicon.hip
+on the general route, csrc/attn_lexicon_mfma.hip on the matrix cores) on the decoder fixtures of test_gpu_seq_f64.py (its inputs, decoders, oracle
 and bounds), then the switch through TRBA and Pipeline on test_gpu_nbest.py's pipeline fixture.
 
 (1) Structural invariants, no tolerance, every row: node_out is the host trie walk of every slot's back-traced token path (-1 exactly
@@ -15,12 +15,11 @@ and bounds), then the switch through TRBA and Pipeline on test_gpu_nbest.py's pi
 (5) MSOCR_E_ARG from the C ABI.  (6) TRBA.predict / Pipeline.lexicon.
 The fixtures of (2) and (3) were checked on the CPU beforehand: with E_REL_MAX * max|logit| standing in for e_dev the float64 search
 alone leaves 37/37 rows decisive in (2) and at least 34/37 in every case of (3)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from attn_call import attn_decode
 from test_gpu_nbest import _pages_and_maps, _pipe
 from test_gpu_seq_f64 import (B_DEF, DECISIVE_FACTOR, DECISIVE_MIN_FRACTION, E_REL_MAX, EOS, SOS, T_DEF, TAU, _attn_buffers, _inputs,
                               _kernel, _oracle, _replay)
@@ -419,7 +418,7 @@ def test_pruned_search_against_f64_constrained_beam_search(cuda, monkeypatch, wh
 
 # ------------------------------------------------------------------------------------------------ (4) identities
 def test_single_word_lexicon_equals_the_forced_decode(cuda, monkeypatch):
-    """{w}: the only path is w.  General kernel, temperature 1, no length penalty: slot 0's logits are msocr_attn_forced's for w bit for
+    """{w}: the only path is w.  General kernel, temperature 1, no length penalty: slot 0's logits are the forced decode's for w bit for
     bit, and the rank-0 logp is msocr_seq_logp of that forced pass."""
     from manuscript_ocr_amd.recognizers import Lexicon
     H, V, K, B, T, steps = 256, 194, 8, B_DEF, T_DEF, STEPS
@@ -504,13 +503,13 @@ def _lexicon_rc(lex, B, T, H, V, steps, K, hoisted, null=None, n_nodes=None, n_e
         setattr(la, f, None if null == f else getattr(src, f))
     la.n_nodes = lex.n_nodes if n_nodes is None else n_nodes
     la.n_edges = lex.n_edges if n_edges is None else n_edges
-    tail = (B, T, H, V, steps, K, b["lp"].data_ptr(), 1.7, SOS, EOS, -1, b["fin"].data_ptr(), b["ws"].data_ptr(), None, None, None,
-            None if null == "alpha_ws" else aws.data_ptr(), None if null == "lex" else ctypes.byref(la),
-            None if null == "node_out" else nodes.data_ptr(), ops._stream())
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "lp": b["lp"], "fin_step_out": b["fin"], "workspace": b["ws"],
+            "alpha_out": None if null == "alpha_ws" else aws, "lexicon": None if null == "lex" else la,
+            "node_out": None if null == "node_out" else nodes}
     if hoisted:
-        rc = nat.lib().msocr_attn_beam_lexicon_hoisted(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw), None, *tail)
-    else:
-        rc = nat.lib().msocr_attn_beam_lexicon(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), *tail)
+        bufs["ctx_gates"] = b["ctx"]
+    rc = attn_decode(nat.ATTN_BEAM, bufs, B=B, T=T, H=H, V=V, steps=steps, beam=K, temperature=1.7, sos_id=SOS, eos_id=EOS, blank_id=-1,
+                     stream=ops._stream())
     torch.cuda.synchronize()
     return rc
 

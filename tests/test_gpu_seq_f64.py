@@ -19,12 +19,11 @@ the GPU; its torch-CPU f32 evaluation measures what f32 arithmetic itself costs 
 (c) Batch-composition invariance: a row's outputs do not depend on which rows share its launch (bit-for-bit).
 (d) Shapes outside the envelope return MSOCR_E_ARG from the C ABI (device buffers sized for the rejected shape).
 (e) BiLSTM, (f) se_residual / mean_over_h / seq_confidence against f64."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from attn_call import attn_decode
 from manuscript_ocr_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -384,13 +383,10 @@ def _greedy_rc(B, T, H, V, steps, sos=SOS, hoisted=False):
     from manuscript_ocr_amd import _native as nat
     from manuscript_ocr_amd import ops
     b, aw, asw = _attn_buffers(B, T, H, V, steps, 1)
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "logits_out": b["logits"], "ids_out": b["ids"]}
     if hoisted:
-        rc = nat.lib().msocr_attn_greedy_hoisted(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw),
-                                                 ctypes.byref(asw), B, T, H, V, steps, sos, EOS, -1, b["logits"].data_ptr(),
-                                                 b["ids"].data_ptr(), ops._stream())
-    else:
-        rc = nat.lib().msocr_attn_greedy(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), B, T, H, V, steps, sos, EOS, -1,
-                                         b["logits"].data_ptr(), b["ids"].data_ptr(), ops._stream())
+        bufs.update(ctx_gates=b["ctx"], ws=asw)
+    rc = attn_decode(nat.ATTN_GREEDY, bufs, B=B, T=T, H=H, V=V, steps=steps, sos_id=sos, eos_id=EOS, blank_id=-1, stream=ops._stream())
     torch.cuda.synchronize()
     return rc
 
@@ -399,12 +395,11 @@ def _beam_rc(B, T, H, V, steps, K, sos=SOS, ctx=False):
     from manuscript_ocr_amd import _native as nat
     from manuscript_ocr_amd import ops
     b, aw, asw = _attn_buffers(B, T, H, V, steps, K)
-    tail = (B, T, H, V, steps, K, b["lp"].data_ptr(), 1.7, sos, EOS, -1, b["fin"].data_ptr(), b["ws"].data_ptr(), None, None, None,
-            ops._stream())
+    bufs = {"batch_H": b["bH"], "proj_H": b["pH"], "w": aw, "lp": b["lp"], "fin_step_out": b["fin"], "workspace": b["ws"]}
     if ctx:
-        rc = nat.lib().msocr_attn_beam_hoisted(b["bH"].data_ptr(), b["pH"].data_ptr(), b["ctx"].data_ptr(), ctypes.byref(aw), None, *tail)
-    else:
-        rc = nat.lib().msocr_attn_beam(b["bH"].data_ptr(), b["pH"].data_ptr(), ctypes.byref(aw), *tail)
+        bufs["ctx_gates"] = b["ctx"]
+    rc = attn_decode(nat.ATTN_BEAM, bufs, B=B, T=T, H=H, V=V, steps=steps, beam=K, temperature=1.7, sos_id=sos, eos_id=EOS, blank_id=-1,
+                     stream=ops._stream())
     torch.cuda.synchronize()
     return rc
 
@@ -433,7 +428,7 @@ def test_c_abi_rejects_shapes_outside_the_envelope(cuda):
     assert _beam_rc(B, T_DEF, 128, 194, STEPS_B, 8, ctx=True) == E_ARG
     b, _, _ = _attn_buffers(B, T_DEF, 256, 194, 65, 8)
     assert nat.lib().msocr_attn_beam_finalize(b["ws"].data_ptr(), B, 194, 65, 8, b["trun"].data_ptr(), b["logits"].data_ptr(),
-                                              b["ids"].data_ptr(), ops._stream()) == E_ARG
+                                              b["ids"].data_ptr(), None, 0, None, ops._stream()) == E_ARG
     # the shapes at the envelope's edge are accepted (same buffers, so a rejection above is the check, not the buffers)
     assert _greedy_rc(B, 64, 128, 512, 64) == 0
     assert _beam_rc(B, T_DEF, 512, 194, STEPS_B, 8) == 0

@@ -913,7 +913,7 @@ def test_built_library_has_no_cross_dword_packed_f32_instruction(tmp_path):
 
 
 def test_new_recurrent_entry_points_reject_bad_arguments_before_any_launch():
-    """msocr_bilstm_recurrent_split / msocr_attn_beam_hoisted validate their arguments first (no GPU is touched for these calls):
+    """msocr_bilstm_recurrent_split / msocr_attn_decode on the matrix-core route validate their arguments first (no GPU is touched for these calls):
     hidden sizes other than 256, null or misaligned packed planes, an xproj too large for 32-bit offsets, a split-weight struct with a
     missing plane."""
     import ctypes
@@ -931,6 +931,11 @@ def test_new_recurrent_entry_points_reject_bad_arguments_before_any_launch():
         setattr(aw, name, p)
     sw = nat.AttnSplitWeights()
     sw.h2h_p, sw.whh_p, sw.gen_p = p16, None, p16
-    args = (4, 13, 256, 194, 25, 8, None, 1.0, 1, 2, -1, p, p16, None, None, None, None)
-    assert L.msocr_attn_beam_hoisted(p, p, p16, ctypes.byref(aw), ctypes.byref(sw), *args) != 0   # a plane is missing
-    assert L.msocr_attn_beam_hoisted(p, p, None, ctypes.byref(aw), None, *args) != 0              # no hoisted product
+    from attn_call import attn_decode
+    bufs = {"batch_H": p, "proj_H": p, "w": aw, "ws": sw, "fin_step_out": p, "workspace": p16}
+    args = dict(B=4, T=13, H=256, V=194, steps=25, beam=8, temperature=1.0, sos_id=1, eos_id=2, blank_id=-1)
+    assert attn_decode(nat.ATTN_BEAM, {**bufs, "ctx_gates": p16}, **args) == -1   # a plane is missing
+    # no hoisted product: with the split weights given it is refused; without them it is the decode on the general kernels, which a
+    # descriptor cannot tell from "the matrix-core entry without its ctx_gates"
+    sw.whh_p = p16
+    assert attn_decode(nat.ATTN_BEAM, bufs, **args) == -1

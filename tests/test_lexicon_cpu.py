@@ -180,14 +180,13 @@ def test_check_host_accepts_the_trie_and_refuses_single_corruptions(lex):
 
 def test_new_symbols_are_bound():
     L = nat.lib()
-    for name in ("msocr_attn_lexicon_nodes_bytes", "msocr_attn_beam_lexicon", "msocr_attn_beam_lexicon_hoisted", "msocr_lexicon_check_host"):
+    for name in ("msocr_attn_beam_slots_bytes", "msocr_attn_decode", "msocr_lexicon_check_host"):
         assert name in nat.exported_symbols() and hasattr(L, name)
-    assert L.msocr_attn_lexicon_nodes_bytes(37, 9, 8) == 37 * 9 * 8 * 4
-    assert L.msocr_attn_lexicon_nodes_bytes(0, 9, 8) == 0 and L.msocr_attn_lexicon_nodes_bytes(3, 9, 0) == 0
+    assert L.msocr_attn_beam_slots_bytes(37, 9, 8) == 37 * 9 * 8 * 4
+    assert L.msocr_attn_beam_slots_bytes(0, 9, 8) == 0 and L.msocr_attn_beam_slots_bytes(3, 9, 0) == 0
     assert ctypes_sizeof_lexicon() == 4 * 8 + 2 * 4
     hdr = open(__file__.replace("tests/test_lexicon_cpu.py", "include/msocr.h"), encoding="utf-8").read()
-    for name in ("msocr_lexicon;", "msocr_attn_beam_lexicon(", "msocr_attn_beam_lexicon_hoisted(", "msocr_lexicon_check_host(",
-                 "msocr_attn_lexicon_nodes_bytes("):
+    for name in ("msocr_lexicon;", "msocr_attn_decode(", "msocr_lexicon_check_host(", "msocr_attn_beam_slots_bytes("):
         assert name in hdr, name
 
 

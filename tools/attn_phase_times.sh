@@ -7,7 +7,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 B=${1:-1024}
 cd $R/manuscript_ocr_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -DMSOCR_ATTN_TIMING -shared \
-  attn_beam_mfma.hip attn_beam_mfma_alpha.hip trba_kernels.hip attn_general.hip -o /tmp/libattn_timing.so
+  attn_beam_mfma.hip attn_beam_mfma_alpha.hip attn_forced_mfma.hip attn_lexicon_mfma.hip attn_lm_mfma.hip trba_kernels.hip \
+  attn_general.hip attn_general_forced.hip attn_general_lexicon.hip attn_general_lm.hip -o /tmp/libattn_timing.so
 cd $R
 python3 - <<PY
 import ctypes, sys, numpy as np, torch
@@ -17,8 +18,8 @@ from manuscript_ocr_amd.recognizers._trba.net import TrbaNet
 L = ctypes.CDLL("/tmp/libattn_timing.so")
 net = TrbaNet(synth.trba_state_dict(194, 256, seed=1), 194, 256, torch.float32)
 real = nat.lib()
-# route msocr_attn_beam of the product library object to the timing build for this process
-for name in ("msocr_attn_beam", "msocr_attn_beam_hoisted"):
+# route msocr_attn_decode of the product library object to the timing build for this process
+for name in ("msocr_attn_decode",):
     fn = getattr(L, name); fn.restype, fn.argtypes = nat._SIGS[name]
     setattr(real, name, fn)
 B = $B

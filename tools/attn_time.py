@@ -9,10 +9,10 @@ against the greedy decode with the attention-weight output, alternating: per rou
 rounds (default 1); one line per round and variant, then medians and spread (max - min) over the rounds.  With --general on the
 general kernels.
 --lexicon N: the beam decode constrained to a lexicon of N seeded random words (lengths 1..25, mean about 8, over the 191 symbols)
-against the unconstrained beam decode with the attention-weight output (msocr_attn_beam_hoisted_alpha), 26 steps, alternating as
+against the unconstrained beam decode with the attention-weight output (msocr_attn_decode, beam mode with alpha_out), 26 steps, alternating as
 --forced does; medians and spread over --repeats rounds, and their ratio.  With --general on the general kernels.
 --lm ORDER: the beam decode fused with a character n-gram language model of that order (a seeded table: log_softmax(2 randn) per
-context over the 194 tokens, the non-emittable columns at -30; weight 0.5) against msocr_attn_beam_hoisted_alpha, 26 steps,
+context over the 194 tokens, the non-emittable columns at -30; weight 0.5) against the same plain beam decode with alpha_out, 26 steps,
 alternating as --lexicon does; medians and spread over --repeats rounds, and their ratio.  With --general on the general kernels.
 --nbest: after the decode timing of the first form, the read-out of its workspace: msocr_attn_beam_finalize + msocr_seq_confidence
 (what every word pays today) and msocr_attn_beam_nbest for n_best 1, 3 and 8, each as the mean of 20 calls after 3 warm-up calls."""

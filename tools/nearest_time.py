@@ -2,7 +2,7 @@
   python tools/nearest_time.py [--repeats N] [--k K]
 For B = 1920 and 7680 rows and lexicons of 1 000 and 100 000 seeded random words (lengths 1..24, mean about 8, over the 191 symbols),
 k = 3, without a bound and with max_distance = 2: per round 5 calls of every variant in turn, the beam decode with the attention-weight
-output (msocr_attn_beam_hoisted_alpha, 26 steps, at B = 1920) among them for scale; one line per variant with the median and the spread
+output (msocr_attn_decode in beam mode with alpha_out, 26 steps, at B = 1920) among them for scale; one line per variant with the median and the spread
 (max - min) over --repeats rounds (default 7).  Half of the rows are lexicon words with 0..2 random edits, half are independent draws
 of the same length distribution (out-of-vocabulary readings).  The results are compared with the host twin on the first 8 rows."""
 import argparse, os, statistics, sys, time

@@ -14,6 +14,8 @@ from manuscript_ocr_amd import synth
 
 pytestmark = pytest.mark.gpu
 
+F64_FACTOR = 2.0  # the device may be at most this many times as far from f64 as the yardstick is
+
 
 def _need_gpu():
     if not torch.cuda.is_available():
@@ -52,8 +54,8 @@ def test_east_forward_device_vs_f64_no_worse_than_2x_the_oracle_f32(hw, pages, s
     s64, g64 = r64["score"][:, 0].numpy(), r64["geometry"].permute(0, 2, 3, 1).numpy()
     es_d, es_r = _report(f"EAST {hw} score", score.cpu().numpy(), s32, s64)
     eg_d, eg_r = _report(f"EAST {hw} geometry", geo.cpu().numpy(), g32, g64)
-    assert es_d <= 2.0 * es_r, (es_d, es_r)
-    assert eg_d <= 2.0 * eg_r, (eg_d, eg_r)
+    assert es_d <= F64_FACTOR * es_r, (es_d, es_r)
+    assert eg_d <= F64_FACTOR * eg_r, (eg_d, eg_r)
     # precision="fp32-exact" (exact-f32 MFMA everywhere, sequential accumulation, no chunking): BASELINE.md's ORIGINAL bound — 1e-4
     # absolute on both maps against the f32 reference path — is asserted for this mode so that the exact path cannot drift
     # (ADVICE r3); its distance from f64 is printed beside the default mode's
@@ -93,5 +95,5 @@ def test_trba_batch_H_device_vs_f64_no_worse_than_2x_the_oracle_f32(seed):
     h_dev = net.encode(cd)[0].float().cpu().numpy()
     ef_d, ef_r = _report(f"TRBA SE-ResNet31 features (32 crops, seed {seed})", f_dev.reshape(f64_.shape), f32_, f64_)
     eh_d, eh_r = _report(f"TRBA batch_H (32 crops, seed {seed})", h_dev, h32, h64)
-    assert ef_d <= 2.0 * ef_r, (ef_d, ef_r)
-    assert eh_d <= 2.0 * eh_r, (eh_d, eh_r)
+    assert ef_d <= F64_FACTOR * ef_r, (ef_d, ef_r)
+    assert eh_d <= F64_FACTOR * eh_r, (eh_d, eh_r)

@@ -525,6 +525,8 @@ def _se_ref(x, idt, w1, w2):
 # f32: measured 3.2e-7 .. 4.3e-7 absolute at max|ref| 4.8 .. 5.8 (the issue's ceiling was 1e-5 of max(1, max|ref|)).  bf16: the output's
 # own rounding (up to 2^-8 relative) plus 1e-5; measured within 1e-5 of the rounding term (the f32 arithmetic before it is exact enough).
 SE_F32_RTOL = 5e-7
+SE_BF16_U, SE_BF16_ABS = 2.0 ** -8, 1e-5  # bf16 se_residual: |dev - ref| <= 2^-8 |ref| + 1e-5 per element
+MEAN_H_RTOL = 1e-6                       # mean_over_h, f32 and bf16 input: 1e-6 of max(1, max|ref|)
 
 
 @pytest.mark.parametrize("N,Hh,W,C", [(37, 8, 25, 256), (37, 4, 13, 512), (3, 16, 64, 256), (2, 5, 7, 1024)])
@@ -539,7 +541,7 @@ def test_se_residual_against_f64(cuda, N, Hh, W, C):
     xb, ib = x.bfloat16(), idt.bfloat16()
     refb = _se_ref(xb.float(), ib.float(), w1, w2)
     gotb = ops.se_residual(xb.cuda(), ib.cuda(), w1.cuda(), w2.cuda()).float().cpu().numpy()
-    excess = np.abs(gotb - refb) - (2.0 ** -8 * np.abs(refb) + 1e-5)
+    excess = np.abs(gotb - refb) - (SE_BF16_U * np.abs(refb) + SE_BF16_ABS)
     print(f"[seq-f64] se_residual bf16 {(N, Hh, W, C)}: max err {np.abs(gotb - refb).max():.2e}, worst excess over the bound {excess.max():.2e}")
     assert (excess <= 0).all(), float(excess.max())
 
@@ -555,7 +557,7 @@ def test_mean_over_h_against_f64(cuda, Hh):
         got = ops.mean_over_h(xd.cuda()).cpu().numpy()
         err = float(np.abs(got - ref).max())
         print(f"[seq-f64] mean_over_h H {Hh} {xd.dtype}: max err {err:.2e} (scale {float(np.abs(ref).max()):.2f})")
-        assert err <= 1e-6 * max(1.0, float(np.abs(ref).max())), (xd.dtype, err)
+        assert err <= MEAN_H_RTOL * max(1.0, float(np.abs(ref).max())), (xd.dtype, err)
 
 
 @pytest.mark.parametrize("V", [194, 512])

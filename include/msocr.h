@@ -579,6 +579,37 @@ int msocr_reading_order_lines(const float* boxes, const int32_t* nbox, int N, in
                               int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, int32_t* line_out,
                               int32_t* lines_out, int32_t* nlines_out, void* workspace, void* stream);
 
+/* ---- skew-aware reading order (an extension beyond the reference, off by default: Pipeline.deskew) ----
+ * The page's skew is estimated from the detected quads, and the boxes that the reading order shrinks, groups and sorts are those of
+ * the corners rotated back about the page centre.  Integer arithmetic, or IEEE f64 in the order written here without contraction and
+ * without a transcendental, so the kernel and the HOST twins give the same bytes.
+ * A word votes when its corners are finite, its quad passes the convexity test of the canonical corner order (below, rectified
+ * crops), and with d = (P1 - P0) + (P2 - P3), r = (P3 - P0) + (P2 - P1) of the canonical corners (f64), qx = (int64)rint(8 d.x),
+ * qy, px, py likewise: 0 < qx < 2^23, |qy| <= qx, qx^2 + qy^2 >= px^2 + py^2 (wider than tall).  S1 = the int64 sum of (qx, qy)
+ * over the voting words; S2 and the count m over those of them with 4 |S1x qy - S1y qx| <= S1x qx + S1y qy (within atan(1/4) of
+ * S1).  The rotation is applied iff m >= 8, S2x > 0, |S2y| <= S2x and 256 |S2y| > S2x; then nrm = sqrt(S2x S2x + S2y S2y),
+ * c = S2x / nrm, s = S2y / nrm, else c = 1, s = 0.  Ordering box of a word, rotation applied and all corners finite: per corner
+ * u = x - 0.5 page_w, v = y - 0.5 page_h, x' = (c u + s v) + 0.5 page_w, y' = (c v - s u) + 0.5 page_h, box = floor of the min / max
+ * of x' and y'; otherwise the word's integer box as msocr_reading_order_crops forms it (truncation).
+ * msocr_page_skew_host (HOST): quads_host [n][8] f32, n <= 65536 -> skew_out_host [4] = {S2x, S2y, m, applied}, cs_out_host [2] = {c, s}.
+ * msocr_deskew_boxes_host (HOST): the ordering boxes [n][4] int32 for a skew / cs pair from it.
+ * msocr_reading_order_deskew (DEVICE): msocr_reading_order_lines with these boxes as the ones shrunk and ordered, and as the unshrunk
+ * copy of the duplicate dictionary and the re-match; crop windows, keep_out, desc_out and the line records' x0..y1 stay those of the
+ * original boxes of the words at the positions.  Order and lines are those of msocr_reading_lines_host on the ordering boxes.
+ * line_out / lines_out / nlines_out: all three or none (NULL).  skew_out [N][4] int64 and cs_out [N][2] f64 as above ({0, 0, 0, 0},
+ * {1, 0} for a page without boxes); the rows of a page with ncrop_out = -1 stay untouched.  A page whose rotation is not applied
+ * gives the outputs of msocr_reading_order_lines bit for bit.  workspace: msocr_reading_order_deskew_workspace_bytes(N, max_cand)
+ * bytes, 16-B aligned. */
+int msocr_page_skew_host(const float* quads_host, int n, int64_t* skew_out_host, double* cs_out_host);
+int msocr_deskew_boxes_host(const float* quads_host, int n, int page_h, int page_w, const int64_t* skew_host, const double* cs_host,
+                            int32_t* boxes_out_host);
+int64_t msocr_reading_order_deskew_workspace_bytes(int N, int max_cand);
+int msocr_reading_order_deskew(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                               int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio, int page_base,
+                               int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, int32_t* line_out,
+                               int32_t* lines_out, int32_t* nlines_out, int64_t* skew_out, double* cs_out, void* workspace,
+                               void* stream);
+
 /* ---- rectified word crops (an extension beyond the reference, off by default: Pipeline.rectify_crops) -----------------------
  * The canvas of a word is cut ALONG its detected quadrilateral instead of from the quad's axis-aligned window.  All arithmetic is
  * IEEE f64 in the order written here, without contraction, so the device kernels and the HOST twins give the same bytes.

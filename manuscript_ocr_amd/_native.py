@@ -137,6 +137,11 @@ _SIGS = {
     "msocr_reading_order_line_rows": (c_i32, [c_i32]),
     "msocr_reading_order_lines": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_page_skew_host": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "msocr_deskew_boxes_host": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "msocr_reading_order_deskew_workspace_bytes": (c_i64, [c_i32, c_i32]),
+    "msocr_reading_order_deskew": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "msocr_quad_crop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),

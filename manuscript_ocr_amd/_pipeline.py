@@ -51,6 +51,17 @@ distances.  The decode is untouched: text and confidences are what the same batc
 char_details, n_best, rectify_crops, group_lines, lm and a `use_graphs` recogniser (the lookup runs behind the decode, on its device
 ids).  With `lexicon` also set a batch is refused at submit (ValueError).  A foreign recogniser is not asked.
 
+`pipeline.deskew = True` (this package's extension, absent by default; needs EAST(axis_aligned_output=False)): the page's skew is
+estimated from the detected quadrilaterals, and the reading order and the text lines are computed in the deskewed frame (DESIGN.md
+section 4.19).  Only the permutation of the words and the line spans change: the word polygons, the crop windows, the recogniser's
+inputs and the TextLine boxes stay in page coordinates, computed from the original boxes.  The page comes back as a SkewPage
+(detectors/_types.py) whose `skew_deg` is the estimate, 0.0 where no rotation was applied (fewer than 8 words that vote, or a skew
+inside the dead zone of 0.22 degrees: an upright page keeps its order bit for bit).  With axis-aligned detector output every word
+is a rectangle, the estimate is zero by construction and the switch is a no-op.  The threshold of 8 words and the 14-degree gate of
+the second pass are placeholders, not tuned values.  Combines with group_lines, rectify_crops, char_details, n_best, lexicon, lm and
+suggest, which all sit behind the order; `score_page` takes the words as given.  Where the reference applies no reading order
+(`recognize_text=False`) the switch has no effect.
+
 `pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
 (an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
 
@@ -108,6 +119,46 @@ def _word_aabb(word):
     return (x_min, y_min, x_max, y_max), poly
 
 
+def _word_quads(words):
+    """[n,8] f32 corners of the words as stored; a polygon that is not four points gets NaN corners (it does not vote and keeps its box)."""
+    q = np.full((len(words), 8), np.nan, dtype=np.float32)
+    for k, w in enumerate(words):
+        if len(w.polygon) == 4:
+            q[k] = np.asarray(w.polygon, dtype=np.float32).reshape(8)
+    return q
+
+
+def _page_skew(page):
+    """deskew: the skew of a page from the quads of all its words -> (skew, cs, skew_deg) (ops.page_skew_host); skew_deg is for
+    reporting only, 0.0 where the rotation is not applied."""
+    skew, cs = ops.page_skew_host(_word_quads([w for block in page.blocks for w in block.words]))
+    return skew, cs, (float(np.degrees(np.arctan2(float(skew[1]), float(skew[0])))) if skew[3] else 0.0)
+
+
+def _ordering_boxes(words, aabbs_i32, page_hw, skew, cs):
+    """deskew: the boxes the reading order sees, [n,4] int32: the words' own boxes where the rotation is not applied, else the boxes
+    of the rotated corners (ops.deskew_boxes_host); a word without four finite corners keeps its own box."""
+    aabbs = np.ascontiguousarray(aabbs_i32, dtype=np.int32).reshape(-1, 4)
+    if not skew[3] or not len(aabbs):
+        return aabbs
+    quads = _word_quads(words)
+    boxes = ops.deskew_boxes_host(quads, page_hw, skew, cs)
+    plain = ~np.isfinite(quads).all(axis=1)
+    boxes[plain] = aabbs[plain]
+    return boxes
+
+
+def _page_frame_records(recs, order, aabbs_i32):
+    """deskew: line records of the ordering boxes -> the same spans with x0..y1 = the union of the ORIGINAL boxes of the words at
+    the line's positions."""
+    at_pos = np.ascontiguousarray(aabbs_i32, dtype=np.int32).reshape(-1, 4)[np.asarray(order, dtype=np.int64)]
+    out = np.array(recs, dtype=np.int32).reshape(-1, 6)
+    for r in out:
+        seg = at_pos[r[0]:r[0] + r[1]]
+        r[2:4], r[4:6] = seg[:, :2].min(axis=0), seg[:, 2:].max(axis=0)
+    return out
+
+
 @dataclass(slots=True)
 class _Group:
     """One group of consecutive pages of a batch, with the same fields on both routes; what a route does not produce stays None."""
@@ -120,6 +171,7 @@ class _Group:
     ro: Any = None                   # ops.ReadingOrder of the group's pages (device_order)
     rl: Any = None                   # ops.ReadingLines behind it (group_lines)
     qd: Any = None                   # [pages,max_cand,12] device quad descriptors behind it (rectify_crops)
+    sk: Any = None                   # ops.PageSkew behind it (deskew)
     device_ordered: bool = False     # advance_batch took the device route: Page / Word assembly is collect_batch's
     words: Optional[list] = None     # the Words that got a crop, in crop order
     spans: List[List[int]] = field(default_factory=list)  # per page [first crop, crops]
@@ -150,6 +202,7 @@ class _Batch:
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
     tm: Optional[Dict[str, float]] = None  # host seconds per stage -> Pipeline.last_profile
     suggest: Optional[tuple] = None  # (suggest, suggest_k, suggest_max_distance) as they were at submit; None = off
+    skews: Optional[dict] = None     # deskew as it was at submit: page index -> skew_deg; None = off
 
     def replace_with(self, other):
         """Become `other` (the corrupt-JPEG resubmission) while staying the object the caller holds."""
@@ -170,6 +223,7 @@ class Pipeline:
         self.rectify_crops = False         # crops cut along the detected quadrilaterals (user extension, see the module docstring)
         self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
         self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
+        self.deskew = False                # reading order and text lines in the deskewed frame, SkewPages come back (user extension)
         self.n_best = 0                    # > 0: recognised words come back as AltWords with the beam search's n best readings (user extension)
         self.lexicon = None                # a recognizers.Lexicon: the beam search is constrained to its words, LexWords come back (user extension)
         self.lm = None                     # a recognizers.CharLM: the beam search is fused with it, LmWords come back (user extension)
@@ -197,19 +251,27 @@ class Pipeline:
             raise RuntimeError("Detector did not return a Page result.")
         return page
 
-    def _order_and_crop(self, page, image_array, line_recs=None):
+    def _order_and_crop(self, page, image_array, line_recs=None, skew=None):
         """_pipeline.py:102-137: reorder every block in reading order, collect crops of words >= min_text_size.
         `line_recs` (a list, group_lines): gets every block's line records from the host twin on the same AABBs; the order stays the
-        Python function's (tests/test_host_cpu.py pins the two orders to be equal)."""
+        Python function's (tests/test_host_cpu.py pins the two orders to be equal).  `skew` (deskew): the page's (skew, cs) with the
+        rotation applied: order and lines come from the host twins on the ordering boxes, the records' boxes from the words' own."""
         words, crops = [], []
         for block in page.blocks:
             boxes = [_word_aabb(w)[0] for w in block.words]
-            if line_recs is not None:
+            if skew is not None and block.words:
+                order, _line, recs = ops.reading_lines_host(_ordering_boxes(block.words, boxes, image_array.shape[:2], *skew))
+                if line_recs is not None:
+                    line_recs.append(_page_frame_records(recs, order, boxes))
+                block.words = [block.words[k] for k in order.tolist()]
+                boxes = None
+            elif line_recs is not None:
                 line_recs.append(ops.reading_lines_host(np.array(boxes, dtype=np.int32).reshape(-1, 4))[2])
-            first = {}
-            for k, bx in enumerate(boxes):  # first equal word wins, as the reference's tuple comparison (:113-121)
-                first.setdefault(tuple(int(v) for v in bx), k)
-            block.words = [block.words[first[tuple(int(v) for v in bx)]] for bx in sort_boxes_reading_order_with_resolutions(boxes)]
+            if boxes is not None:
+                first = {}
+                for k, bx in enumerate(boxes):  # first equal word wins, as the reference's tuple comparison (:113-121)
+                    first.setdefault(tuple(int(v) for v in bx), k)
+                block.words = [block.words[first[tuple(int(v) for v in bx)]] for bx in sort_boxes_reading_order_with_resolutions(boxes)]
             for word in block.words:
                 (x0, y0, x1, y1), poly = _word_aabb(word)
                 if (x1 - x0) >= self.min_text_size and (y1 - y0) >= self.min_text_size:
@@ -269,7 +331,8 @@ class Pipeline:
             print(f"Load image for crops: {time.time() - t0:.3f}s")
         t0 = time.time()
         line_recs = [] if self.group_lines else None
-        words, crops = self._order_and_crop(page, image_array, line_recs)
+        skew = _page_skew(page) if self.deskew else None
+        words, crops = self._order_and_crop(page, image_array, line_recs, skew[:2] if skew is not None and skew[0][3] else None)
         if profile:
             print(f"Extract {len(crops)} crops: {time.time() - t0:.3f}s")
         if crops:
@@ -293,6 +356,8 @@ class Pipeline:
                                      suggestions=None if suggest is None else [results[i]["suggestions"] for i in range(len(words))])
         if line_recs is not None:
             self._split_lines(page, line_recs)
+        if skew is not None:
+            page = self._skew_page(page, skew[2])
         if profile:
             print(f"Pipeline total: {time.time() - start:.3f}s")
         if vis:
@@ -300,11 +365,14 @@ class Pipeline:
             return page, visualize_page(pil, page, show_order=True)
         return page
 
-    def _order_boxes(self, page, line_recs=None):
+    def _order_boxes(self, page, line_recs=None, deskew_hw=None):
         """Reading-order reorder of every block (in place) + AABBs of the words that pass min_text_size.
         Same semantics as _pipeline.py:102-133 of the reference, vectorised.  `line_recs` (a list, group_lines): order and line
-        records of every block then come from msocr_reading_lines_host, and the records are appended to it."""
+        records of every block then come from msocr_reading_lines_host, and the records are appended to it.  `deskew_hw` (the page's
+        (H, W), deskew): the order and the lines are those of the ordering boxes of the deskewed frame, everything else stays the
+        original boxes'; returns the page's skew_deg as a third value."""
         words, boxes = [], []
+        skew = _page_skew(page) if deskew_hw is not None else None
         for block in page.blocks:
             if not block.words:
                 if line_recs is not None:
@@ -314,12 +382,14 @@ class Pipeline:
             polys = np.array([w.polygon for w in block.words], dtype=np.float64).astype(np.int32)
             mins, maxs = polys.min(axis=1), polys.max(axis=1)
             aabbs = [(a[0], a[1], b[0], b[1]) for a, b in zip(mins, maxs)]
+            own = np.concatenate([mins, maxs], axis=1)
+            seen = _ordering_boxes(block.words, own, deskew_hw, skew[0], skew[1]) if skew is not None and skew[0][3] else own
             if line_recs is None:
-                order = _reading_order(np.concatenate([mins, maxs], axis=1))
+                order = _reading_order(seen)
             else:
-                order, _line, recs = ops.reading_lines_host(np.concatenate([mins, maxs], axis=1))
+                order, _line, recs = ops.reading_lines_host(seen)
                 order = order.tolist()
-                line_recs.append(recs)
+                line_recs.append(recs if seen is own else _page_frame_records(recs, order, own))
             old_words = block.words
             block.words = [old_words[k] for k in order]
             for k in order:
@@ -327,6 +397,8 @@ class Pipeline:
                 if (x1 - x0) >= self.min_text_size and (y1 - y0) >= self.min_text_size:
                     words.append(old_words[k])
                     boxes.append((x0, y0, x1, y1))
+        if skew is not None:
+            return words, boxes, skew[2]
         return words, boxes
 
     def predict_batch(self, images: List[Union[str, np.ndarray]], recognize_text: bool = True, profile: bool = False,
@@ -463,6 +535,7 @@ class Pipeline:
                 dpool.append(torch.cuda.Stream(priority=hi_prio))
             streams, det_streams = pool[:nsub], dpool[:nsub]
         rec, rectify, group_lines, groups = self.recognizer, bool(self.rectify_crops), bool(self.group_lines), []
+        deskew = bool(self.deskew)
         for (lo, hi), st, dst in zip(bounds, streams, det_streams):
             if dst is not main:
                 dst.wait_stream(main)
@@ -471,9 +544,12 @@ class Pipeline:
                 dh = det.detect_start(pages_dev[lo:hi], mo)
                 # reading order + crop descriptors of the group's pages on the device, right behind the box filters: the host
                 # then needs only the crop COUNTS to enqueue the recogniser (Page / Word assembly moves to collect_batch)
-                ro = rl = qd = None
+                ro = rl = qd = sk = None
                 if recognize_text and dh.final_boxes is not None and self.device_order:
-                    if group_lines:  # the same kernel body with the line outputs compiled in
+                    if deskew:  # the same kernel body with the skew estimate and the ordering boxes compiled in
+                        ro, rl, sk = ops.reading_order_deskew(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h, rec.img_w,
+                                                              page_base=lo, lines=group_lines)
+                    elif group_lines:  # the same kernel body with the line outputs compiled in
                         ro, rl = ops.reading_order_lines(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h, rec.img_w,
                                                          page_base=lo)
                     else:
@@ -483,11 +559,11 @@ class Pipeline:
                         qd = ops.quad_crop_descriptors(dh.final_boxes, dh.final_counts, ro, rec.img_h, rec.img_w)
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
-                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd))
+                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd, sk))
         return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon, lm, lm_weight,
                       ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False),
-                      suggest=suggest)
+                      suggest=suggest, skews={} if deskew else None)
 
     def advance_batch(self, h):
         """Stage 2 of `predict_batch` for a handle from `submit_batch`: per group — wait for its boxes, run the host
@@ -547,7 +623,10 @@ class Pipeline:
             for pi in range(lo, hi):
                 if h.line_recs is not None:
                     h.line_recs[pi] = []
-                words, bxs = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi])
+                if h.skews is None:
+                    words, bxs = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi])
+                else:
+                    words, bxs, h.skews[pi] = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi], (H, W))
                 grp.spans.append([len(grp.words), len(words)])
                 grp.words += words
                 boxes += bxs
@@ -637,6 +716,9 @@ class Pipeline:
                         order_h, keep_h = grp.ro.order.cpu().numpy(), grp.ro.keep.cpu().numpy()
                         if grp.rl is not None:  # the records carry the spans; the per-position line index stays on the device
                             lines_h, nlines_h = grp.rl.lines.cpu().numpy(), grp.rl.nlines.cpu().numpy()
+                        if grp.sk is not None:
+                            for pi, (sx, sy, _m, applied) in enumerate(grp.sk.skew.cpu().numpy().tolist()):
+                                h.skews[lo + pi] = float(np.degrees(np.arctan2(float(sy), float(sx)))) if applied else 0.0
                         tm["detect_wait+tail"] += time.perf_counter() - t0
                     t0 = time.perf_counter()
                     grp.words = []
@@ -702,6 +784,9 @@ class Pipeline:
             if h.line_recs:  # after _attach_details, so that the lines hold the CharWords / AltWords
                 for pi, recs in h.line_recs.items():
                     self._split_lines(pages[pi], recs)
+            if h.skews:
+                for pi, deg in h.skews.items():
+                    pages[pi] = self._skew_page(pages[pi], deg)
         self.last_profile = tm
         if h.profile:
             print("Pipeline.predict_batch host stages (s):", {k: round(v, 4) for k, v in tm.items()})
@@ -739,6 +824,12 @@ class Pipeline:
         for page in pages:
             for block in page.blocks:
                 block.words = [new.get(id(w), w) for w in block.words]
+
+    @staticmethod
+    def _skew_page(page, skew_deg):
+        """deskew: the page as a SkewPage over the same blocks (and so the same words)."""
+        from .detectors._types import SkewPage
+        return SkewPage.model_construct(blocks=page.blocks, skew_deg=skew_deg)
 
     @staticmethod
     def _split_lines(page, line_recs):

@@ -33,6 +33,22 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* wave_tot, int* t
   return base + inc - v;
 }
 
+// Sum of one int64 per thread over a workgroup of T threads, in every thread (every thread must call it).  Integer, so exact and
+// independent of the order.  wave_tot is the caller's LDS, long long[T / 64]; the two barriers serve as in block_exclusive_scan.
+template <int T>
+__device__ __forceinline__ long long block_sum_i64(long long v, long long* wave_tot) {
+  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "whole waves, one workgroup");
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  long long tot = 0;
+#pragma nounroll
+  for (int q = 0; q < T / 64; ++q) tot += wave_tot[q];
+  __syncthreads();
+  return tot;
+}
+
 // The bit words a greedy wave keeps in registers: a mask of 64 * KW * 32 bits, word l + 64 k owned by lane l in w[k].  w[] is
 // only ever indexed by the counter of a fully unrolled loop, so the words stay in registers; the one dynamic access, "the word
 // that holds bit i", is a select chain + __shfl.  All 64 lanes call every operation with the same (wave-uniform) arguments;

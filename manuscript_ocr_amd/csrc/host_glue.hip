@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "msocr.h"
+#include "page_skew.h"
 #include "word_boxes.h"
 
 namespace {
@@ -110,6 +111,33 @@ extern "C" int msocr_reading_lines_host(const int32_t* boxes_host, int n, double
                                         int32_t* nlines_out_host) {
   if (!nlines_out_host || (n > 0 && (!line_out_host || !lines_out_host))) return MSOCR_E_ARG;
   return reading_order_body(boxes_host, n, y_tol_ratio, x_gap_ratio, order_out_host, line_out_host, lines_out_host, nlines_out_host);
+}
+
+// --------------------------------------------------------------------------------------------- page skew
+// Host twins of reading_order_kernel's DESKEW part (Pipeline.deskew): the per-word arithmetic is page_skew.h's,
+// the sums are int64.  n <= 65536 keeps every product of a sum and a word inside int64 (the kernel takes at most 16384 words).
+extern "C" int msocr_page_skew_host(const float* quads_host, int n, int64_t* skew_out_host, double* cs_out_host) {
+  if (n < 0 || n > 65536 || !skew_out_host || !cs_out_host || (n > 0 && !quads_host)) return MSOCR_E_ARG;
+  long long s1x = 0, s1y = 0, s2x = 0, s2y = 0, m = 0, qx, qy;
+  for (int i = 0; i < n; ++i)
+    if (skew_word(quads_host + 8 * (size_t)i, &qx, &qy)) { s1x += qx; s1y += qy; }
+  for (int i = 0; i < n; ++i)
+    if (skew_word(quads_host + 8 * (size_t)i, &qx, &qy) && skew_near(s1x, s1y, qx, qy)) { s2x += qx; s2y += qy; ++m; }
+  const bool applied = skew_applied(s2x, s2y, m);
+  skew_out_host[0] = s2x; skew_out_host[1] = s2y; skew_out_host[2] = m; skew_out_host[3] = applied ? 1 : 0;
+  skew_cos_sin(s2x, s2y, applied, cs_out_host);
+  return MSOCR_OK;
+}
+
+extern "C" int msocr_deskew_boxes_host(const float* quads_host, int n, int page_h, int page_w, const int64_t* skew_host,
+                                       const double* cs_host, int32_t* boxes_out_host) {
+  if (n < 0 || page_h <= 0 || page_w <= 0 || !skew_host || !cs_host || (n > 0 && (!quads_host || !boxes_out_host))) return MSOCR_E_ARG;
+  for (int i = 0; i < n; ++i) {
+    const Box4 b = deskew_box(quads_host + 8 * (size_t)i, skew_host[3] != 0, cs_host[0], cs_host[1], page_h, page_w);
+    boxes_out_host[4 * (size_t)i] = b.x0; boxes_out_host[4 * (size_t)i + 1] = b.y0;
+    boxes_out_host[4 * (size_t)i + 2] = b.x1; boxes_out_host[4 * (size_t)i + 3] = b.y1;
+  }
+  return MSOCR_OK;
 }
 
 // --------------------------------------------------------------------------------------------- lexicon

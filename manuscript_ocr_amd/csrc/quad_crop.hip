@@ -27,53 +27,7 @@ constexpr int QD = 12;        // words per quad descriptor
 constexpr int QDESC_T = 1024; // threads per page of the descriptor kernel
 constexpr int QCROP_T = 256;  // threads per crop
 
-HD float bits_f32(int32_t v) {
-  float f;
-  memcpy(&f, &v, 4);
-  return f;
-}
-HD int32_t f32_bits(float f) {
-  int32_t v;
-  memcpy(&v, &f, 4);
-  return v;
-}
-HD bool finite_f32(float f) { return (f32_bits(f) & 0x7f800000) != 0x7f800000; }
 HD double dmax(double a, double b) { return a > b ? a : b; }
-
-// Canonical corner order of the quad q[8] (x, y pairs as stored) -> c[8]; false when the quad is not usable (a non-finite corner,
-// a zero edge cross product, or cross products of both signs).
-HD bool quad_canonical(const float* q, float* c) {
-  for (int k = 0; k < 8; ++k)
-    if (!finite_f32(q[k])) return false;
-  int pos = 0, neg = 0;
-  for (int i = 0; i < 4; ++i) {  // cross product of the edges P[i] -> P[i+1] and P[i+1] -> P[i+2]
-    const int j = (i + 1) & 3, k = (i + 2) & 3;
-    const double ax = (double)q[2 * j] - (double)q[2 * i], ay = (double)q[2 * j + 1] - (double)q[2 * i + 1];
-    const double bx = (double)q[2 * k] - (double)q[2 * j], by = (double)q[2 * k + 1] - (double)q[2 * j + 1];
-    const double cr = ax * by - ay * bx;
-    pos += cr > 0.0 ? 1 : 0;
-    neg += cr < 0.0 ? 1 : 0;
-  }
-  if (pos != 4 && neg != 4) return false;
-  // y points down: positive cross products = clockwise on screen; otherwise walk the stored corners backwards (3, 2, 1, 0)
-  int idx[4];
-  for (int k = 0; k < 4; ++k) idx[k] = pos == 4 ? k : 3 - k;
-  // the rotation whose first edge has the largest x1 - x0; on equality the start corner with the smallest stored index
-  int best = 0;
-  double best_dx = 0.0;
-  for (int r = 0; r < 4; ++r) {
-    const double dx = (double)q[2 * idx[(r + 1) & 3]] - (double)q[2 * idx[r]];
-    if (r == 0 || dx > best_dx || (dx == best_dx && idx[r] < idx[best])) {
-      best = r;
-      best_dx = dx;
-    }
-  }
-  for (int k = 0; k < 4; ++k) {
-    c[2 * k] = q[2 * idx[(best + k) & 3]];
-    c[2 * k + 1] = q[2 * idx[(best + k) & 3] + 1];
-  }
-  return true;
-}
 
 // Side lengths of canonical corners: w = max(|P1-P0|, |P2-P3|), h = max(|P3-P0|, |P2-P1|).
 HD void quad_size(const float* c, double* w, double* h) {

@@ -14,6 +14,10 @@
 // (ncrop = -1: more boxes than the capacity, more than RO_MAXLINES text lines, or more intersecting pairs than the pair buffer).
 // msocr_reading_order_lines launches the same body with LINES = true: the text lines the order is built from leave as well (the
 // line of every position, one record per line, the line count), bit-identical to msocr_reading_lines_host.
+// msocr_reading_order_deskew launches it with DESKEW = true (Pipeline.deskew): the page's skew is estimated
+// from the quads (page_skew.h, two exact int64 reductions over the workgroup) and the boxes that are shrunk, grouped and ordered are
+// those of the rotated corners; windows, descriptors and line unions stay those of the original boxes.  Bit-identical to
+// msocr_page_skew_host + msocr_deskew_boxes_host + msocr_reading_lines_host.
 //
 // resolve_intersections is a SEQUENTIAL sweep over all pairs (i < j): an intersecting pair shrinks both boxes at once, which
 // changes what later pairs of the same sweep see.  It is parallelised exactly: boxes only ever shrink during a sweep, so the
@@ -27,6 +31,7 @@
 #include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
+#include "page_skew.h"
 #include "word_boxes.h"
 
 namespace {
@@ -65,20 +70,35 @@ struct RoLineOut {
   int rows;
 };
 
-template <bool LINES>
+// the page's skew estimate as a result (msocr_reading_order_deskew); unused and compiled out with DESKEW = false
+struct RoSkewOut {
+  int64_t* skew;  // [N][4] {S2x, S2y, m, applied}
+  double* cs;     // [N][2] {c, s}
+};
+
+template <bool LINES, bool DESKEW>
 __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ nbox,
                                                               int max_cand, int cap, int page_h, int page_w, int min_text,
                                                               int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
                                                               int page_base, int32_t* __restrict__ order_out,
                                                               int32_t* __restrict__ keep_out, int32_t* __restrict__ desc_out,
-                                                              int32_t* __restrict__ ncrop_out, int32_t* __restrict__ ws, RoLineOut lo) {
+                                                              int32_t* __restrict__ ncrop_out, int32_t* __restrict__ ws, RoLineOut lo,
+                                                              RoSkewOut so) {
   const int pg = blockIdx.x, tid = threadIdx.x;
   const int n = nbox[pg];
+  __shared__ long long skew_s[4];  // DESKEW: {S2x, S2y, m, applied}, written out with the verdict of a page that is not flagged
+  __shared__ double cs_s[2];
   // the page's verdict: crops (and lines) of the page, 0 for an empty page, -1 = the host path takes it
   auto verdict = [&](int ncrop, int nlines) {
     if (tid == 0) {
       ncrop_out[pg] = ncrop;
       if constexpr (LINES) lo.nlines[pg] = nlines;
+      if constexpr (DESKEW)
+        if (ncrop >= 0) {
+          for (int k = 0; k < 4; ++k) so.skew[4 * (long)pg + k] = (n > 0 ? skew_s[k] : 0LL);
+          so.cs[2 * (long)pg] = n > 0 ? cs_s[0] : 1.0;
+          so.cs[2 * (long)pg + 1] = n > 0 ? cs_s[1] : 0.0;
+        }
     }
   };
   if (n < 0 || n > cap) {
@@ -89,8 +109,10 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     verdict(0, 0);
     return;
   }
-  int32_t* w = ws + (long)pg * ro_ws_words(cap);
+  int32_t* w = ws + (long)pg * (ro_ws_words(cap) + (DESKEW ? 4L * cap : 0L));
   Box4* ob = reinterpret_cast<Box4*>(w);
+  // DESKEW: the boxes of the rotated corners, unshrunk (the dictionary and the re-match compare them); else the original boxes
+  Box4* rb = DESKEW ? reinterpret_cast<Box4*>(w + ro_ws_words(cap)) : ob;
   Box4* sb = ob + cap;
   int* cnt = reinterpret_cast<int*>(sb + cap);
   const long P = ro_pair_cap(cap);
@@ -115,9 +137,35 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   for (int i = tid; i < n; i += RO_T) {
     const Box4 b = box_from_quad(ib + 9 * (long)i);
     ob[i] = b;
-    sb[i] = b;
+    if constexpr (!DESKEW) sb[i] = b;
   }
   if (tid == 0) { fail_s = 0; hsum_s = 0; }
+  if constexpr (DESKEW) {
+    // ---- page skew (page_skew.h): S1 over the words that vote, S2 and m over those near S1; then the ordering boxes
+    __shared__ long long wave_tot64[RO_T / 64];
+    long long ax = 0, ay = 0;
+    for (int i = tid; i < n; i += RO_T) {
+      long long qx, qy;
+      if (skew_word(ib + 9 * (long)i, &qx, &qy)) { ax += qx; ay += qy; }
+    }
+    const long long s1x = block_sum_i64<RO_T>(ax, wave_tot64), s1y = block_sum_i64<RO_T>(ay, wave_tot64);
+    long long bx = 0, by = 0, bm = 0;
+    for (int i = tid; i < n; i += RO_T) {
+      long long qx, qy;
+      if (skew_word(ib + 9 * (long)i, &qx, &qy) && skew_near(s1x, s1y, qx, qy)) { bx += qx; by += qy; ++bm; }
+    }
+    const long long s2x = block_sum_i64<RO_T>(bx, wave_tot64), s2y = block_sum_i64<RO_T>(by, wave_tot64);
+    const long long m = block_sum_i64<RO_T>(bm, wave_tot64);
+    const bool applied = skew_applied(s2x, s2y, m);
+    double cs[2];
+    skew_cos_sin(s2x, s2y, applied, cs);
+    if (tid == 0) { skew_s[0] = s2x; skew_s[1] = s2y; skew_s[2] = m; skew_s[3] = applied ? 1 : 0; cs_s[0] = cs[0]; cs_s[1] = cs[1]; }
+    for (int i = tid; i < n; i += RO_T) {
+      const Box4 b = deskew_box(ib + 9 * (long)i, applied, cs[0], cs[1], page_h, page_w);
+      rb[i] = b;
+      sb[i] = b;
+    }
+  }
   __threadfence();
   __syncthreads();
 
@@ -262,10 +310,10 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     int back = i;
     for (int j = n - 1; j > i; --j)
       if (box_same(sb[j], si)) { back = j; break; }
-    const Box4 o = ob[back];
+    const Box4 o = rb[back];
     int wi = back;
     for (int j = 0; j < back; ++j)
-      if (box_same(ob[j], o)) { wi = j; break; }
+      if (box_same(rb[j], o)) { wi = j; break; }
     oo[pos] = wi;
     int win[4];
     const int keep = box_crop_window(ob[wi], page_h, page_w, min_text, win) ? 1 : 0;
@@ -308,16 +356,17 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   verdict(nk, L);
 }
 
-template <bool LINES>
+template <bool LINES, bool DESKEW = false>
 int ro_launch(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w, int min_text_size, int img_h,
               int img_w, double y_tol_ratio, double x_gap_ratio, int page_base, int32_t* order_out, int32_t* keep_out,
-              int32_t* desc_out, int32_t* ncrop_out, void* workspace, RoLineOut lo, void* stream) {
+              int32_t* desc_out, int32_t* ncrop_out, void* workspace, RoLineOut lo, void* stream,
+              RoSkewOut so = RoSkewOut{nullptr, nullptr}) {
   if (!boxes || !nbox || !order_out || !keep_out || !desc_out || !ncrop_out || !workspace) return MSOCR_E_ARG;
   if (N <= 0 || max_cand <= 0 || page_h <= 0 || page_w <= 0 || img_h <= 0 || img_w <= 0 || page_base < 0) return MSOCR_E_ARG;
   if ((uintptr_t)workspace & 15) return MSOCR_E_ARG;
-  MSOCR_LAUNCH(reading_order_kernel<LINES>, dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand),
+  MSOCR_LAUNCH((reading_order_kernel<LINES, DESKEW>), dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand),
                page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base, order_out, keep_out, desc_out,
-               ncrop_out, (int32_t*)workspace, lo);
+               ncrop_out, (int32_t*)workspace, lo, so);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 }  // namespace
@@ -345,4 +394,26 @@ extern "C" int msocr_reading_order_lines(const float* boxes, const int32_t* nbox
   return ro_launch<true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base,
                          order_out, keep_out, desc_out, ncrop_out, workspace,
                          RoLineOut{line_out, lines_out, nlines_out, msocr_reading_order_line_rows(max_cand)}, stream);
+}
+
+extern "C" int64_t msocr_reading_order_deskew_workspace_bytes(int N, int max_cand) {
+  return (N > 0 && max_cand > 0) ? (int64_t)N * (ro_ws_words(ro_cap(max_cand)) + 4L * ro_cap(max_cand)) * 4 : 0;
+}
+
+extern "C" int msocr_reading_order_deskew(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                                          int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
+                                          int page_base, int32_t* order_out, int32_t* keep_out, int32_t* desc_out,
+                                          int32_t* ncrop_out, int32_t* line_out, int32_t* lines_out, int32_t* nlines_out,
+                                          int64_t* skew_out, double* cs_out, void* workspace, void* stream) {
+  if (!skew_out || !cs_out) return MSOCR_E_ARG;
+  const int given = (line_out ? 1 : 0) + (lines_out ? 1 : 0) + (nlines_out ? 1 : 0);
+  if (given != 0 && given != 3) return MSOCR_E_ARG;  // the line outputs: all three or none
+  const RoSkewOut so{skew_out, cs_out};
+  if (given == 0)
+    return ro_launch<false, true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio,
+                                  page_base, order_out, keep_out, desc_out, ncrop_out, workspace, RoLineOut{nullptr, nullptr, nullptr, 0},
+                                  stream, so);
+  return ro_launch<true, true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base,
+                               order_out, keep_out, desc_out, ncrop_out, workspace,
+                               RoLineOut{line_out, lines_out, nlines_out, msocr_reading_order_line_rows(max_cand)}, stream, so);
 }

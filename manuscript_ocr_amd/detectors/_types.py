@@ -121,3 +121,12 @@ class Page(BaseModel):
     """All blocks of one page image."""
 
     blocks: List[Block]
+
+
+class SkewPage(Page):
+    """A Page whose reading order and text lines were computed in the deskewed frame, written by Pipeline when `deskew` is on (this
+    package's extension).  The words, their polygons and the TextLine boxes stay in page coordinates.  Declared where a Page is
+    expected (List[Page], a field of type Page), a default model_dump() serialises it as a Page."""
+
+    skew_deg: float = Field(0.0, description="estimated skew of the page's text lines in degrees, positive = lines descend to the right "
+                                             "(y points down); 0.0 where no rotation was applied")

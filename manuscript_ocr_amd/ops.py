@@ -624,6 +624,56 @@ def reading_lines_host(aabbs_i32, y_tol_ratio=0.6, x_gap_ratio=float("inf")):
     return order, line, lines[:int(nlines[0])].copy()
 
 
+class PageSkew(NamedTuple):
+    """The skew estimate behind a deskewed ReadingOrder (`reading_order_deskew`), per page, on the device."""
+    skew: torch.Tensor  # [N,4] i64 {S2x, S2y, m, applied}: the summed word directions in 1/16 px, the words in the sum, 1 = rotated
+    cs: torch.Tensor    # [N,2] f64 {c, s}: the rotation the ordering boxes were formed with; {1, 0} where none was applied
+
+
+def reading_order_deskew(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf"),
+                         workspace=None, lines=True):
+    """reading_order_lines in the deskewed frame (msocr_reading_order_deskew): the page's skew is estimated
+    from the quads and the order and lines are those of the rotated corners' boxes; keep, desc and the line records' boxes stay those
+    of the original boxes.  The rows of `skew` / `cs` of a page with ncrop = -1 are undefined.  lines=False: without the three line
+    outputs.  Returns (ReadingOrder, ReadingLines or None, PageSkew)."""
+    _need_cuda(boxes, nbox)
+    N, max_cand, _ = boxes.shape
+    dev = boxes.device
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((nat.lib().msocr_reading_order_deskew_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    ro = ReadingOrder(i32(N, max_cand), i32(N, max_cand), i32(N, max_cand, 8), i32(N))
+    rl = ReadingLines(i32(N, max_cand), i32(N, nat.lib().msocr_reading_order_line_rows(max_cand), 6), i32(N)) if lines else None
+    sk = PageSkew(torch.empty((N, 4), dtype=torch.int64, device=dev), torch.empty((N, 2), dtype=torch.float64, device=dev))
+    nat.check(nat.lib().msocr_reading_order_deskew(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, int(page_hw[0]), int(page_hw[1]),
+                                                   int(min_text_size), int(img_h), int(img_w), float(y_tol_ratio), float(x_gap_ratio),
+                                                   int(page_base), *[t.data_ptr() for t in ro], *([t.data_ptr() for t in rl] if lines else [None] * 3),
+                                                   sk.skew.data_ptr(), sk.cs.data_ptr(), ws.data_ptr(), _stream()), "reading_order_deskew")
+    return ro, rl, sk
+
+
+def page_skew_host(quads):
+    """Word quads [n,4,2] or [n,8] (x, y per corner as stored) -> (skew int64 [4] = {S2x, S2y, m, applied}, cs f64 [2] = {c, s}) through
+    the host twin msocr_page_skew_host.  skew_deg = degrees(atan2(S2y, S2x)) is the caller's, for reporting."""
+    q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    skew, cs = np.zeros(4, dtype=np.int64), np.zeros(2, dtype=np.float64)
+    nat.check(nat.lib().msocr_page_skew_host(q.ctypes.data, len(q), skew.ctypes.data, cs.ctypes.data), "page_skew_host")
+    return skew, cs
+
+
+def deskew_boxes_host(quads, page_hw, skew, cs):
+    """Word quads [n,4,2] or [n,8] + a (skew, cs) of page_skew_host -> the ordering boxes int32 [n,4] of the deskewed frame through the
+    host twin msocr_deskew_boxes_host: the words' integer boxes themselves where the rotation is not applied (skew[3] = 0)."""
+    q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    skew, cs = np.ascontiguousarray(skew, dtype=np.int64), np.ascontiguousarray(cs, dtype=np.float64)
+    assert skew.shape == (4,) and cs.shape == (2,)
+    out = np.empty((len(q), 4), dtype=np.int32)
+    nat.check(nat.lib().msocr_deskew_boxes_host(q.ctypes.data, len(q), int(page_hw[0]), int(page_hw[1]), skew.ctypes.data, cs.ctypes.data,
+                                                out.ctypes.data), "deskew_boxes_host")
+    return out
+
+
 def nchw_to_nhwc(x_f32, dtype, out=None):
     _need_cuda(x_f32)
     N, C, H, W = x_f32.shape

@@ -610,6 +610,47 @@ int msocr_reading_order_deskew(const float* boxes, const int32_t* nbox, int N, i
                                int32_t* lines_out, int32_t* nlines_out, int64_t* skew_out, double* cs_out, void* workspace,
                                void* stream);
 
+/* ---- column-aware reading order (an extension beyond the reference, off by default: Pipeline.columns) ----
+ * An XY-cut ahead of the line rule: the page is cut at its wide empty vertical and horizontal bands into regions, the regions are
+ * read in order and sort_boxes_reading_order runs inside every region.  Integer arithmetic, or IEEE f64 in the order written here
+ * without contraction, so the kernel and the HOST twin give the same bytes.
+ * S[i] = the shrunk boxes after resolve_intersections over the whole page (with deskew: of the ordering boxes of the deskewed
+ * frame).  avg_h = (exact integer sum of y1 - y0 over all n shrunk boxes) / n, gx = col_gap_ratio * avg_h, gy = row_gap_ratio * avg_h,
+ * mh = col_min_height_ratio * avg_h.  Differences of coordinates are formed in int64 and converted to f64 for the comparison.
+ * A region is a set of words; the root holds all words at depth 0.  A region at depth 6 or with one word is a leaf.  Otherwise the
+ * vertical attempt, allowed only when (double)(max y1 - min y0 over the region) >= mh: walk the region's words in the order
+ * (x0, index) with the running maximum of x1 over the words before the current one; a word starts a new segment iff
+ * (double)(x0 - running maximum) >= gx; more than one segment: the segments, left to right, are the children at depth + 1.  Not
+ * allowed, or one segment: the horizontal attempt, the same walk with (y0, index), y1 and gy, children top to bottom.  No cut by
+ * either: a leaf.  The leaves in depth-first order are the regions in reading order.  Inside a leaf, order and lines are
+ * sort_boxes_reading_order's on the leaf's shrunk boxes in ascending word index, with the LEAF's mean height behind y_tol_ratio and
+ * x_gap_ratio.  Lines are numbered region-major; a line never spans two regions.  The dictionary from shrunk box to original box
+ * and the first-equal-word re-match stay page-wide.  A ratio may be +inf (never cuts); NaN or a negative ratio: MSOCR_E_ARG.
+ * msocr_reading_regions_host (HOST): msocr_reading_lines_host with the three ratios, and region_out_host [n]: the region of every
+ * position; regions_out_host [n][6]: one record {first, count, x0, y0, x1, y1} per region, its span of positions and the union of the
+ * input boxes of the words written there; *nregions_out_host (0 for n = 0).  No cap on the regions.  A page that ends as one leaf
+ * gives msocr_reading_lines_host's outputs.
+ * msocr_reading_order_regions (DEVICE): msocr_reading_order_deskew's arguments with the three ratios and `deskew` (1: the cut and
+ * the order run in the deskewed frame; 0: on the words' own boxes, and skew_out / cs_out may be NULL and stay untouched).
+ * line_out / lines_out / nlines_out: all three or none.  region_out [N][max_cand], regions_out [N][rows][6] with
+ * rows = msocr_reading_order_region_rows(max_cand) = min(max_cand, 256) (the box is the union of the words' own integer boxes, as
+ * in the line records), nregions_out [N]: -1 exactly where ncrop_out is -1, 0 for a page without boxes.  More than 256 regions flag
+ * the page (ncrop_out = -1) like the other capacities; rows of a flagged page and rows past a page's counts stay untouched.  A page
+ * that ends as one region gives the outputs of msocr_reading_order_lines (deskew = 1: of msocr_reading_order_deskew) bit for bit.
+ * workspace: msocr_reading_order_regions_workspace_bytes(N, max_cand) bytes, 16-B aligned. */
+int msocr_reading_regions_host(const int32_t* boxes_host, int n, double y_tol_ratio, double x_gap_ratio, double col_gap_ratio,
+                               double row_gap_ratio, double col_min_height_ratio, int32_t* order_out_host, int32_t* line_out_host,
+                               int32_t* lines_out_host, int32_t* nlines_out_host, int32_t* region_out_host, int32_t* regions_out_host,
+                               int32_t* nregions_out_host);
+int msocr_reading_order_region_rows(int max_cand);
+int64_t msocr_reading_order_regions_workspace_bytes(int N, int max_cand);
+int msocr_reading_order_regions(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                                int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio, int page_base,
+                                double col_gap_ratio, double row_gap_ratio, double col_min_height_ratio, int deskew,
+                                int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out, int32_t* line_out,
+                                int32_t* lines_out, int32_t* nlines_out, int64_t* skew_out, double* cs_out, int32_t* region_out,
+                                int32_t* regions_out, int32_t* nregions_out, void* workspace, void* stream);
+
 /* ---- rectified word crops (an extension beyond the reference, off by default: Pipeline.rectify_crops) -----------------------
  * The canvas of a word is cut ALONG its detected quadrilateral instead of from the quad's axis-aligned window.  All arithmetic is
  * IEEE f64 in the order written here, without contraction, so the device kernels and the HOST twins give the same bytes.

@@ -142,6 +142,12 @@ _SIGS = {
     "msocr_reading_order_deskew_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_reading_order_deskew": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_reading_regions_host": (c_i32, [c_vp, c_i32, c_f64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_reading_order_region_rows": (c_i32, [c_i32]),
+    "msocr_reading_order_regions_workspace_bytes": (c_i64, [c_i32, c_i32]),
+    "msocr_reading_order_regions": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32,
+                                            c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_crop_descriptors_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "msocr_quad_crop": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),

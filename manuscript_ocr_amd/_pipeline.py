@@ -62,6 +62,14 @@ the second pass are placeholders, not tuned values.  Combines with group_lines, 
 suggest, which all sit behind the order; `score_page` takes the words as given.  Where the reference applies no reading order
 (`recognize_text=False`) the switch has no effect.
 
+`pipeline.columns = True` (this package's extension, absent by default): the page is cut into regions at its wide empty vertical and
+horizontal bands (an XY-cut) ahead of the line rule, so an open book, a two-column register or a heading above
+two columns is read column by column instead of straight across the gutter.  `pipeline.column_params` holds the three ratios of the
+cut (col_gap_ratio, row_gap_ratio, col_min_height_ratio, in units of the page's mean word height): placeholders, not tuned values.
+Every reading-ordered block comes back as its Regions (detectors/_types.py), with `group_lines` as RegionLines; both dump as a
+Block.  With `deskew` the cut runs in the deskewed frame.  Combines with rectify_crops, char_details, n_best, lexicon, lm and suggest,
+which all sit behind the order.  A page without a wide empty band is one region and keeps its order bit for bit.
+
 `pipeline.score_page(image, page)` (this package's extension): the forced decode of a page whose words already carry a `text`
 (an edition, a keyed-in ground truth): how well every text fits its word image and where its symbols sit.
 
@@ -172,6 +180,7 @@ class _Group:
     rl: Any = None                   # ops.ReadingLines behind it (group_lines)
     qd: Any = None                   # [pages,max_cand,12] device quad descriptors behind it (rectify_crops)
     sk: Any = None                   # ops.PageSkew behind it (deskew)
+    rg: Any = None                   # ops.ReadingRegions behind it (columns)
     device_ordered: bool = False     # advance_batch took the device route: Page / Word assembly is collect_batch's
     words: Optional[list] = None     # the Words that got a crop, in crop order
     spans: List[List[int]] = field(default_factory=list)  # per page [first crop, crops]
@@ -203,6 +212,8 @@ class _Batch:
     tm: Optional[Dict[str, float]] = None  # host seconds per stage -> Pipeline.last_profile
     suggest: Optional[tuple] = None  # (suggest, suggest_k, suggest_max_distance) as they were at submit; None = off
     skews: Optional[dict] = None     # deskew as it was at submit: page index -> skew_deg; None = off
+    region_recs: Optional[dict] = None  # columns as it was at submit: page index -> per block its [R,6] region records; None = off
+    ratios: Optional[tuple] = None   # column_params as they were at submit: the three ratios of the cut; None = off
 
     def replace_with(self, other):
         """Become `other` (the corrupt-JPEG resubmission) while staying the object the caller holds."""
@@ -224,6 +235,8 @@ class Pipeline:
         self.char_details = False          # recognised words come back as CharWords with per-symbol details (user extension)
         self.group_lines = False           # every reading-ordered block comes back as its text lines, one TextLine each (user extension)
         self.deskew = False                # reading order and text lines in the deskewed frame, SkewPages come back (user extension)
+        self.columns = False               # the page is cut into regions ahead of the line rule, Regions / RegionLines come back (user extension)
+        self.column_params = dict(ops.COLUMN_PARAMS)  # the three ratios of that cut; placeholders, not tuned values
         self.n_best = 0                    # > 0: recognised words come back as AltWords with the beam search's n best readings (user extension)
         self.lexicon = None                # a recognizers.Lexicon: the beam search is constrained to its words, LexWords come back (user extension)
         self.lm = None                     # a recognizers.CharLM: the beam search is fused with it, LmWords come back (user extension)
@@ -251,15 +264,29 @@ class Pipeline:
             raise RuntimeError("Detector did not return a Page result.")
         return page
 
-    def _order_and_crop(self, page, image_array, line_recs=None, skew=None):
+    def _order_and_crop(self, page, image_array, line_recs=None, skew=None, region_recs=None, ratios=None):
         """_pipeline.py:102-137: reorder every block in reading order, collect crops of words >= min_text_size.
         `line_recs` (a list, group_lines): gets every block's line records from the host twin on the same AABBs; the order stays the
         Python function's (tests/test_host_cpu.py pins the two orders to be equal).  `skew` (deskew): the page's (skew, cs) with the
-        rotation applied: order and lines come from the host twins on the ordering boxes, the records' boxes from the words' own."""
+        rotation applied: order and lines come from the host twins on the ordering boxes, the records' boxes from the words' own.
+        `region_recs` (a list) and `ratios` (columns): order, lines and every block's region records come from
+        msocr_reading_regions_host, on the ordering boxes where `skew` is given."""
         words, crops = [], []
         for block in page.blocks:
             boxes = [_word_aabb(w)[0] for w in block.words]
-            if skew is not None and block.words:
+            if ratios is not None:
+                if block.words:
+                    seen = boxes if skew is None else _ordering_boxes(block.words, boxes, image_array.shape[:2], *skew)
+                    order, _line, recs, _region, rrecs = ops.reading_regions_host(seen, 0.6, float("inf"), *ratios)
+                    recs, rrecs = _page_frame_records(recs, order, boxes), _page_frame_records(rrecs, order, boxes)
+                    block.words = [block.words[k] for k in order.tolist()]
+                else:
+                    recs = rrecs = _NO_LINES
+                region_recs.append(rrecs)
+                if line_recs is not None:
+                    line_recs.append(recs)
+                boxes = None
+            elif skew is not None and block.words:
                 order, _line, recs = ops.reading_lines_host(_ordering_boxes(block.words, boxes, image_array.shape[:2], *skew))
                 if line_recs is not None:
                     line_recs.append(_page_frame_records(recs, order, boxes))
@@ -332,7 +359,10 @@ class Pipeline:
         t0 = time.time()
         line_recs = [] if self.group_lines else None
         skew = _page_skew(page) if self.deskew else None
-        words, crops = self._order_and_crop(page, image_array, line_recs, skew[:2] if skew is not None and skew[0][3] else None)
+        ratios = ops.column_ratios(self.column_params) if self.columns else None
+        region_recs = [] if ratios is not None else None
+        words, crops = self._order_and_crop(page, image_array, line_recs, skew[:2] if skew is not None and skew[0][3] else None,
+                                            region_recs, ratios)
         if profile:
             print(f"Extract {len(crops)} crops: {time.time() - t0:.3f}s")
         if crops:
@@ -354,7 +384,9 @@ class Pipeline:
                                      lex_idx=None if lexicon is None else [results[i]["lexicon_index"] for i in range(len(words))],
                                      lm_logp=None if lm is None else [results[i]["lm_logp"] for i in range(len(words))],
                                      suggestions=None if suggest is None else [results[i]["suggestions"] for i in range(len(words))])
-        if line_recs is not None:
+        if region_recs is not None:
+            self._split_regions(page, region_recs, line_recs)
+        elif line_recs is not None:
             self._split_lines(page, line_recs)
         if skew is not None:
             page = self._skew_page(page, skew[2])
@@ -365,18 +397,21 @@ class Pipeline:
             return page, visualize_page(pil, page, show_order=True)
         return page
 
-    def _order_boxes(self, page, line_recs=None, deskew_hw=None):
+    def _order_boxes(self, page, line_recs=None, deskew_hw=None, region_recs=None, ratios=None):
         """Reading-order reorder of every block (in place) + AABBs of the words that pass min_text_size.
         Same semantics as _pipeline.py:102-133 of the reference, vectorised.  `line_recs` (a list, group_lines): order and line
         records of every block then come from msocr_reading_lines_host, and the records are appended to it.  `deskew_hw` (the page's
         (H, W), deskew): the order and the lines are those of the ordering boxes of the deskewed frame, everything else stays the
-        original boxes'; returns the page's skew_deg as a third value."""
+        original boxes'; returns the page's skew_deg as a third value.  `region_recs` (a list) and `ratios` (columns): order, lines
+        and every block's region records come from msocr_reading_regions_host."""
         words, boxes = [], []
         skew = _page_skew(page) if deskew_hw is not None else None
         for block in page.blocks:
             if not block.words:
                 if line_recs is not None:
                     line_recs.append(_NO_LINES)
+                if region_recs is not None:
+                    region_recs.append(_NO_LINES)
                 continue
             # AABBs of all words at once: np.array(polygon, int32) truncates toward zero (_pipeline.py:106)
             polys = np.array([w.polygon for w in block.words], dtype=np.float64).astype(np.int32)
@@ -384,7 +419,13 @@ class Pipeline:
             aabbs = [(a[0], a[1], b[0], b[1]) for a, b in zip(mins, maxs)]
             own = np.concatenate([mins, maxs], axis=1)
             seen = _ordering_boxes(block.words, own, deskew_hw, skew[0], skew[1]) if skew is not None and skew[0][3] else own
-            if line_recs is None:
+            if ratios is not None:
+                order, _line, recs, _region, rrecs = ops.reading_regions_host(seen, 0.6, float("inf"), *ratios)
+                order = order.tolist()
+                region_recs.append(rrecs if seen is own else _page_frame_records(rrecs, order, own))
+                if line_recs is not None:
+                    line_recs.append(recs if seen is own else _page_frame_records(recs, order, own))
+            elif line_recs is None:
                 order = _reading_order(seen)
             else:
                 order, _line, recs = ops.reading_lines_host(seen)
@@ -536,6 +577,7 @@ class Pipeline:
             streams, det_streams = pool[:nsub], dpool[:nsub]
         rec, rectify, group_lines, groups = self.recognizer, bool(self.rectify_crops), bool(self.group_lines), []
         deskew = bool(self.deskew)
+        ratios = ops.column_ratios(self.column_params) if self.columns else None
         for (lo, hi), st, dst in zip(bounds, streams, det_streams):
             if dst is not main:
                 dst.wait_stream(main)
@@ -544,9 +586,12 @@ class Pipeline:
                 dh = det.detect_start(pages_dev[lo:hi], mo)
                 # reading order + crop descriptors of the group's pages on the device, right behind the box filters: the host
                 # then needs only the crop COUNTS to enqueue the recogniser (Page / Word assembly moves to collect_batch)
-                ro = rl = qd = sk = None
+                ro = rl = qd = sk = rg = None
                 if recognize_text and dh.final_boxes is not None and self.device_order:
-                    if deskew:  # the same kernel body with the skew estimate and the ordering boxes compiled in
+                    if ratios is not None:  # the same kernel body with the XY-cut ahead of the line walk
+                        ro, rl, sk, rg = ops.reading_order_regions(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h,
+                                                                   rec.img_w, lo, 0.6, float("inf"), *ratios, lines=group_lines, deskew=deskew)
+                    elif deskew:  # the same kernel body with the skew estimate and the ordering boxes compiled in
                         ro, rl, sk = ops.reading_order_deskew(dh.final_boxes, dh.final_counts, (H, W), self.min_text_size, rec.img_h, rec.img_w,
                                                               page_base=lo, lines=group_lines)
                     elif group_lines:  # the same kernel body with the line outputs compiled in
@@ -559,11 +604,11 @@ class Pipeline:
                         qd = ops.quad_crop_descriptors(dh.final_boxes, dh.final_counts, ro, rec.img_h, rec.img_w)
                 ev = torch.cuda.Event()
                 ev.record(dst)  # detector outputs of this group complete
-                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd, sk))
+                groups.append(_Group(lo, hi, st, dst, dh, ev, ro, rl, qd, sk, rg))
         return _Batch(arrays, pages_dev, main, groups, recognize_text, profile, rectify, {} if group_lines else None, n_best, lexicon, lm, lm_weight,
                       ingest_pending,
                       lambda: self.submit_batch(images, recognize_text, profile, None, sub_batches, _maps_override, _device_entropy=False),
-                      suggest=suggest, skews={} if deskew else None)
+                      suggest=suggest, skews={} if deskew else None, region_recs=None if ratios is None else {}, ratios=ratios)
 
     def advance_batch(self, h):
         """Stage 2 of `predict_batch` for a handle from `submit_batch`: per group — wait for its boxes, run the host
@@ -623,10 +668,13 @@ class Pipeline:
             for pi in range(lo, hi):
                 if h.line_recs is not None:
                     h.line_recs[pi] = []
+                if h.region_recs is not None:
+                    h.region_recs[pi] = []
+                cols = () if h.region_recs is None else (h.region_recs[pi], h.ratios)
                 if h.skews is None:
-                    words, bxs = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi])
+                    words, bxs = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi], None, *cols)
                 else:
-                    words, bxs, h.skews[pi] = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi], (H, W))
+                    words, bxs, h.skews[pi] = self._order_boxes(h.pages[pi], None if h.line_recs is None else h.line_recs[pi], (H, W), *cols)
                 grp.spans.append([len(grp.words), len(words)])
                 grp.words += words
                 boxes += bxs
@@ -716,6 +764,8 @@ class Pipeline:
                         order_h, keep_h = grp.ro.order.cpu().numpy(), grp.ro.keep.cpu().numpy()
                         if grp.rl is not None:  # the records carry the spans; the per-position line index stays on the device
                             lines_h, nlines_h = grp.rl.lines.cpu().numpy(), grp.rl.nlines.cpu().numpy()
+                        if grp.rg is not None:
+                            regions_h, nregions_h = grp.rg.regions.cpu().numpy(), grp.rg.nregions.cpu().numpy()
                         if grp.sk is not None:
                             for pi, (sx, sy, _m, applied) in enumerate(grp.sk.skew.cpu().numpy().tolist()):
                                 h.skews[lo + pi] = float(np.degrees(np.arctan2(float(sy), float(sx)))) if applied else 0.0
@@ -728,6 +778,8 @@ class Pipeline:
                         k0 = 0
                         if grp.rl is not None:
                             h.line_recs[lo + pi] = []
+                        if grp.rg is not None:
+                            h.region_recs[lo + pi] = []
                         for block in page.blocks:  # this package's EAST returns one block (infer.py:390)
                             nw = len(block.words)
                             if nw:
@@ -736,6 +788,8 @@ class Pipeline:
                                 grp.words += [block.words[pos] for pos in np.flatnonzero(keep_h[pi, k0:k0 + nw]).tolist()]
                             if grp.rl is not None:
                                 h.line_recs[lo + pi].append(lines_h[pi, :int(nlines_h[pi])] if nw else _NO_LINES)
+                            if grp.rg is not None:
+                                h.region_recs[lo + pi].append(regions_h[pi, :int(nregions_h[pi])] if nw else _NO_LINES)
                             k0 += nw
                     tm["order"] += time.perf_counter() - t0
                 if grp.handle is not None:
@@ -781,7 +835,10 @@ class Pipeline:
             for grp in h.groups:
                 if grp.det_stream is not main:
                     main.wait_stream(grp.det_stream)
-            if h.line_recs:  # after _attach_details, so that the lines hold the CharWords / AltWords
+            if h.region_recs:  # after _attach_details, so that the regions and lines hold the CharWords / AltWords
+                for pi, rrecs in h.region_recs.items():
+                    self._split_regions(pages[pi], rrecs, None if h.line_recs is None else h.line_recs[pi])
+            elif h.line_recs:
                 for pi, recs in h.line_recs.items():
                     self._split_lines(pages[pi], recs)
             if h.skews:
@@ -841,6 +898,27 @@ class Pipeline:
             for first, count, x0, y0, x1, y1 in np.asarray(recs).tolist():
                 lines.append(TextLine(words=block.words[first:first + count], bbox=(x0, y0, x1, y1)))
         page.blocks = lines
+
+    @staticmethod
+    def _split_regions(page, region_recs, line_recs=None):
+        """columns: replace every block of `page` by its Regions, block-major; with `line_recs` (group_lines) by its RegionLines.
+        region_recs[b] / line_recs[b] = the [R,6] / [L,6] records {first, count, x0, y0, x1, y1} of block b over the positions of its
+        reading-ordered words; the regions are numbered through the page."""
+        from .detectors._types import Region, RegionLine
+        out, base = [], 0
+        for b, block in enumerate(page.blocks):
+            rrecs = np.asarray(region_recs[b]).reshape(-1, 6).tolist()
+            if line_recs is None:
+                for r, (first, count, x0, y0, x1, y1) in enumerate(rrecs):
+                    out.append(Region(words=block.words[first:first + count], bbox=(x0, y0, x1, y1), index=base + r))
+            else:
+                r = 0
+                for first, count, x0, y0, x1, y1 in np.asarray(line_recs[b]).reshape(-1, 6).tolist():
+                    while first >= rrecs[r][0] + rrecs[r][1]:  # lines come region-major, and a line never spans two regions
+                        r += 1
+                    out.append(RegionLine(words=block.words[first:first + count], bbox=(x0, y0, x1, y1), region=base + r))
+            base += len(rrecs)
+        page.blocks = out
 
     def score_page(self, image: Union[str, np.ndarray, Image.Image], page, strict: bool = True):
         """Forced decode of a transcribed page (this package's extension; needs this package's TRBA): `page` is a Page whose words

@@ -18,6 +18,10 @@
 // from the quads (page_skew.h, two exact int64 reductions over the workgroup) and the boxes that are shrunk, grouped and ordered are
 // those of the rotated corners; windows, descriptors and line unions stay those of the original boxes.  Bit-identical to
 // msocr_page_skew_host + msocr_deskew_boxes_host + msocr_reading_lines_host.
+// msocr_reading_order_regions launches it with REGIONS = true (Pipeline.columns): between the shrink and the
+// line walk an XY-cut splits the page at its wide empty bands into regions, level by level over the whole workgroup; a line then
+// belongs to one region, takes its tolerances from that region's mean height, and the lines are ordered region-major.  Bit-identical
+// to msocr_reading_regions_host.
 //
 // resolve_intersections is a SEQUENTIAL sweep over all pairs (i < j): an intersecting pair shrinks both boxes at once, which
 // changes what later pairs of the same sweep see.  It is parallelised exactly: boxes only ever shrink during a sweep, so the
@@ -31,6 +35,7 @@
 #include "block_prims.h"
 #include "internal.h"
 #include "msocr.h"
+#include "page_regions.h"
 #include "page_skew.h"
 #include "word_boxes.h"
 
@@ -38,11 +43,14 @@ namespace {
 constexpr int RO_T = 1024;         // threads per page
 constexpr int RO_CAP = 16384;      // boxes per page
 constexpr int RO_MAXLINES = 4096;  // text lines per page (line state lives in LDS)
+constexpr int RO_MAXREGIONS = 256; // regions per page (REGIONS; the region tables live in LDS)
 
 __host__ __device__ inline int ro_cap(int max_cand) { return max_cand < RO_CAP ? max_cand : RO_CAP; }
 __host__ __device__ inline long ro_pair_cap(int cap) { return 8L * cap + 4096; }
 // per-page workspace in 4-byte words: ob[4c] sb[4c] cnt[c+4] pairs[2P] sorted[c] lineof[c] seq[c] emitted[c] keepf[c]
 __host__ __device__ inline long ro_ws_words(int cap) { return (4L * cap + 4L * cap + (cap + 4) + 2 * ro_pair_cap(cap) + 5L * cap + 3) / 4 * 4; }
+// REGIONS, behind the ordering boxes rb[4c] of DESKEW (reserved with or without it): reg[c] regn[c] startf[c]
+__host__ __device__ inline long ro_region_words(int cap) { return (3L * cap + 3) / 4 * 4; }
 
 // in-place exclusive prefix sum of arr[0..n) by the whole workgroup (contiguous chunk per thread); returns the total
 __device__ int ro_block_scan(int* arr, int n, int* wave_tot /* LDS [RO_T/64] */) {
@@ -76,23 +84,78 @@ struct RoSkewOut {
   double* cs;     // [N][2] {c, s}
 };
 
-template <bool LINES, bool DESKEW>
+// the page's regions as a result, and the thresholds of the cut (msocr_reading_order_regions); unused and compiled out with REGIONS = false
+struct RoRegionOut {
+  int32_t* region;    // [N][max_cand]
+  int32_t* regions;   // [N][rows][6]
+  int32_t* nregions;  // [N]
+  int rows;
+  double col_gap_ratio, row_gap_ratio, col_min_height_ratio;
+};
+
+// REGIONS: the region of every line and the tables of the regions, in LDS
+struct RoRegionLds {
+  int lreg[RO_MAXLINES];
+  int lo[RO_MAXREGIONS], hi[RO_MAXREGIONS];    // the cut: min y0 / max y1 of the region;  the records: min x0 / max x1
+  int lo2[RO_MAXREGIONS], hi2[RO_MAXREGIONS];  // the records: min y0 / max y1
+  int axis[RO_MAXREGIONS];                     // the attempt of this level: 0 = vertical (walk along x), 1 = horizontal (along y)
+  int nseg[RO_MAXREGIONS];                     // start words the attempt found: more than one = the region is cut
+  int base[RO_MAXREGIONS];                     // the cut: ordinal of the region's first child;  the records: its first position
+  int cnt[RO_MAXREGIONS];                      // words of the region
+  unsigned long long hsum[RO_MAXREGIONS];      // exact sum of their shrunk heights (two's complement)
+  double tol[RO_MAXREGIONS], gap[RO_MAXREGIONS];
+  int nreg, cut;
+};
+__device__ __forceinline__ RoRegionLds& ro_region_lds() {
+  __shared__ RoRegionLds s;
+  return s;
+}
+
+// REGIONS: one attempt of a level over the regions whose axis[] is `ax`.  Every word of such a region finds the running maximum of
+// the high edges of the words before it in (low edge, index) and whether it starts a segment (startf[]); nseg[] counts the starts.
+__device__ __forceinline__ void ro_region_attempt(RoRegionLds& g, int ax, double thr, const Box4* sb, const int* reg, int* startf, int n) {
+  for (int i = threadIdx.x; i < n; i += RO_T) {
+    const int r = reg[i];
+    if (g.axis[r] != ax) continue;
+    const Box4 a = sb[i];
+    const int li = ax ? a.y0 : a.x0;
+    bool has = false;
+    int run = 0;
+    for (int j = 0; j < n; ++j) {
+      if (reg[j] != r) continue;
+      const Box4 b = sb[j];
+      const int lj = ax ? b.y0 : b.x0, hj = ax ? b.y1 : b.x1;
+      if (region_before(lj, j, li, i)) {
+        run = has ? max(run, hj) : hj;
+        has = true;
+      }
+    }
+    const int st = (!has || region_gap(li, run, thr)) ? 1 : 0;
+    startf[i] = st;
+    if (st) atomicAdd(&g.nseg[r], 1);
+  }
+  __threadfence();
+  __syncthreads();
+}
+
+template <bool LINES, bool DESKEW, bool REGIONS>
 __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ nbox,
                                                               int max_cand, int cap, int page_h, int page_w, int min_text,
                                                               int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
                                                               int page_base, int32_t* __restrict__ order_out,
                                                               int32_t* __restrict__ keep_out, int32_t* __restrict__ desc_out,
                                                               int32_t* __restrict__ ncrop_out, int32_t* __restrict__ ws, RoLineOut lo,
-                                                              RoSkewOut so) {
+                                                              RoSkewOut so, RoRegionOut go) {
   const int pg = blockIdx.x, tid = threadIdx.x;
   const int n = nbox[pg];
   __shared__ long long skew_s[4];  // DESKEW: {S2x, S2y, m, applied}, written out with the verdict of a page that is not flagged
   __shared__ double cs_s[2];
   // the page's verdict: crops (and lines) of the page, 0 for an empty page, -1 = the host path takes it
-  auto verdict = [&](int ncrop, int nlines) {
+  auto verdict = [&](int ncrop, int nlines, int nregions) {
     if (tid == 0) {
       ncrop_out[pg] = ncrop;
       if constexpr (LINES) lo.nlines[pg] = nlines;
+      if constexpr (REGIONS) go.nregions[pg] = nregions;
       if constexpr (DESKEW)
         if (ncrop >= 0) {
           for (int k = 0; k < 4; ++k) so.skew[4 * (long)pg + k] = (n > 0 ? skew_s[k] : 0LL);
@@ -102,14 +165,14 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     }
   };
   if (n < 0 || n > cap) {
-    verdict(-1, -1);
+    verdict(-1, -1, -1);
     return;
   }
   if (n == 0) {
-    verdict(0, 0);
+    verdict(0, 0, 0);
     return;
   }
-  int32_t* w = ws + (long)pg * (ro_ws_words(cap) + (DESKEW ? 4L * cap : 0L));
+  int32_t* w = ws + (long)pg * (ro_ws_words(cap) + (DESKEW || REGIONS ? 4L * cap : 0L) + (REGIONS ? ro_region_words(cap) : 0L));
   Box4* ob = reinterpret_cast<Box4*>(w);
   // DESKEW: the boxes of the rotated corners, unshrunk (the dictionary and the re-match compare them); else the original boxes
   Box4* rb = DESKEW ? reinterpret_cast<Box4*>(w + ro_ws_words(cap)) : ob;
@@ -208,7 +271,7 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   }
   __syncthreads();
   if (fail_s) {
-    verdict(-1, -1);
+    verdict(-1, -1, -1);
     return;
   }
 
@@ -234,6 +297,96 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __syncthreads();
   const double avg_h = (double)hsum_s / (double)n;  // np.mean of ints: exact sum, one division
   const double tol = avg_h * y_tol_ratio, gap = avg_h * x_gap_ratio;
+  int* reg = nullptr;  // REGIONS: the region of every word
+  if constexpr (REGIONS) {
+    // ---- XY-cut (msocr.h, msocr_reading_order_regions): at most RG_MAXDEPTH levels; at every level each region tries the vertical
+    // cut where it is tall enough, else (or where that found one segment) the horizontal one.  A region that is not cut is tried
+    // again at the next level with the same outcome, so its depth never grows and no leaf flag is kept; the children take the
+    // parent's place in the numbering, so the ordinal is the depth-first leaf order.
+    RoRegionLds& g = ro_region_lds();
+    reg = w + ro_ws_words(cap) + 4L * cap;
+    int* regn = reg + cap;
+    int* startf = regn + cap;
+    const RegionParams rp = region_params(avg_h, go.col_gap_ratio, go.row_gap_ratio, go.col_min_height_ratio);
+    for (int i = tid; i < n; i += RO_T) reg[i] = 0;
+    if (tid == 0) g.nreg = 1;
+    __threadfence();
+    __syncthreads();
+    for (int level = 0; level < RG_MAXDEPTH; ++level) {
+      const int nreg = g.nreg;
+      for (int r = tid; r < nreg; r += RO_T) { g.lo[r] = INT32_MAX; g.hi[r] = INT32_MIN; g.nseg[r] = 0; }
+      __syncthreads();
+      for (int i = tid; i < n; i += RO_T) {
+        const int r = reg[i];
+        atomicMin(&g.lo[r], sb[i].y0);
+        atomicMax(&g.hi[r], sb[i].y1);
+      }
+      __syncthreads();
+      for (int r = tid; r < nreg; r += RO_T) g.axis[r] = region_tall(g.lo[r], g.hi[r], rp.col_min_h) ? 0 : 1;
+      __syncthreads();
+      ro_region_attempt(g, 0, rp.col_gap, sb, reg, startf, n);
+      for (int r = tid; r < nreg; r += RO_T)
+        if (g.axis[r] == 0 && g.nseg[r] <= 1) { g.axis[r] = 1; g.nseg[r] = 0; }
+      __syncthreads();
+      ro_region_attempt(g, 1, rp.row_gap, sb, reg, startf, n);
+      if (tid == 0) {
+        int run = 0, cut = 0;
+        for (int r = 0; r < nreg; ++r) {
+          g.base[r] = run;
+          const int kids = g.nseg[r] > 1 ? g.nseg[r] : 1;
+          cut |= kids > 1 ? 1 : 0;
+          run = run + kids > RO_MAXREGIONS ? RO_MAXREGIONS + 1 : run + kids;  // saturates: nseg may be n in every region
+        }
+        g.cut = cut;
+        g.nreg = run;
+        if (run > RO_MAXREGIONS) fail_s = 1;
+      }
+      __syncthreads();
+      if (fail_s || !g.cut) break;
+      // the segment of a word = the start words of its region at or before it, less one
+      for (int i = tid; i < n; i += RO_T) {
+        const int r = reg[i];
+        int seg = 0;
+        if (g.nseg[r] > 1) {
+          const int ax = g.axis[r];
+          const int li = ax ? sb[i].y0 : sb[i].x0;
+          for (int j = 0; j < n; ++j)
+            if (reg[j] == r && startf[j]) {
+              const int lj = ax ? sb[j].y0 : sb[j].x0;
+              seg += (j == i || region_before(lj, j, li, i)) ? 1 : 0;
+            }
+          seg -= 1;
+        }
+        regn[i] = g.base[r] + seg;
+      }
+      __threadfence();
+      __syncthreads();
+      for (int i = tid; i < n; i += RO_T) reg[i] = regn[i];
+      __threadfence();
+      __syncthreads();
+    }
+    __syncthreads();
+    if (fail_s) {
+      verdict(-1, -1, -1);
+      return;
+    }
+    // every region's own mean height: the tolerances of its lines
+    const int nreg = g.nreg;
+    for (int r = tid; r < nreg; r += RO_T) { g.hsum[r] = 0ULL; g.cnt[r] = 0; }
+    __syncthreads();
+    for (int i = tid; i < n; i += RO_T) {
+      const int r = reg[i];
+      atomicAdd(&g.hsum[r], (unsigned long long)(long long)(sb[i].y1 - sb[i].y0));
+      atomicAdd(&g.cnt[r], 1);
+    }
+    __syncthreads();
+    for (int r = tid; r < nreg; r += RO_T) {
+      const double ah = (double)(long long)g.hsum[r] / (double)g.cnt[r];
+      g.tol[r] = ah * y_tol_ratio;
+      g.gap[r] = ah * x_gap_ratio;
+    }
+    __syncthreads();
+  }
   if (tid < 64) {  // one wave walks the cy-sorted boxes; its lanes test 64 lines at a time, the FIRST matching line wins
     const int lane = tid;
     int L = 0;
@@ -242,20 +395,31 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
       const int i = sorted[s];
       const Box4 b = sb[i];
       const double c = (double)(b.y0 + b.y1) / 2.0;
+      int ri = 0;
+      double tol_i = tol, gap_i = gap;
+      if constexpr (REGIONS) {
+        ri = reg[i];
+        tol_i = ro_region_lds().tol[ri];
+        gap_i = ro_region_lds().gap[ri];
+      }
       int home = -1;
       for (int l0 = 0; l0 < L; l0 += 64) {
         const int l = l0 + lane;
         bool ok = false;
         if (l < L) {
           const double line_cy = lsum[l] / (double)lcnt[l];
-          ok = fabs(c - line_cy) <= tol && (double)(b.x0 - lmaxx[l]) <= gap;
+          ok = fabs(c - line_cy) <= tol_i && (double)(b.x0 - lmaxx[l]) <= gap_i;
+          if constexpr (REGIONS) ok = ok && ro_region_lds().lreg[l] == ri;
         }
         const unsigned long long bal = __ballot(ok);
         if (bal) { home = l0 + (int)__ffsll((long long)bal) - 1; break; }
       }
       if (home < 0) {
         if (L >= RO_MAXLINES) { over = true; break; }
-        if (lane == 0) { lsum[L] = c; lcnt[L] = 1; lmaxx[L] = b.x1; lineof[i] = L; }
+        if (lane == 0) {
+          lsum[L] = c; lcnt[L] = 1; lmaxx[L] = b.x1; lineof[i] = L;
+          if constexpr (REGIONS) ro_region_lds().lreg[L] = ri;
+        }
         ++L;
       } else if (lane == 0) {
         lsum[home] += c; lcnt[home] += 1; lmaxx[home] = max(lmaxx[home], b.x1); lineof[i] = home;
@@ -268,7 +432,7 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __threadfence();
   __syncthreads();
   if (fail_s) {
-    verdict(-1, -1);
+    verdict(-1, -1, -1);
     return;
   }
   const int L = nlines_s;
@@ -280,7 +444,12 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
     int start = 0, rank = 0;
     for (int k = 0; k < L; ++k) {
       const double mk = lsum[k] / (double)lcnt[k];
-      if (mk < m || (mk == m && k < l)) {
+      bool front = mk < m || (mk == m && k < l);
+      if constexpr (REGIONS) {  // region-major
+        const int rk = ro_region_lds().lreg[k], rl = ro_region_lds().lreg[l];
+        front = rk < rl || (rk == rl && front);
+      }
+      if (front) {
         start += lcnt[k];
         if constexpr (LINES) ++rank;
       }
@@ -345,6 +514,32 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
       t[0] = first; t[1] = count; t[2] = u.x0; t[3] = u.y0; t[4] = u.x1; t[5] = u.y1;
     }
   }
+  if constexpr (REGIONS) {
+    // the region of every position, and one record per region: its span of positions (the positions are region-major) and the
+    // union of the words' original AABBs (oo[] is complete: the barrier above)
+    RoRegionLds& g = ro_region_lds();
+    const int nreg = g.nreg;
+    int32_t* rno = go.region + (long)pg * max_cand;
+    int32_t* rec = go.regions + (long)pg * go.rows * 6;  // nreg <= min(n, RO_MAXREGIONS) <= rows
+    for (int r = tid; r < nreg; r += RO_T) {
+      g.lo[r] = INT32_MAX; g.hi[r] = INT32_MIN; g.lo2[r] = INT32_MAX; g.hi2[r] = INT32_MIN;
+      int first = 0;
+      for (int k = 0; k < r; ++k) first += g.cnt[k];
+      g.base[r] = first;
+    }
+    __syncthreads();
+    for (int pos = tid; pos < n; pos += RO_T) {
+      const int r = reg[emitted[pos]];
+      const Box4 b = ob[oo[pos]];
+      rno[pos] = r;
+      atomicMin(&g.lo[r], b.x0); atomicMax(&g.hi[r], b.x1); atomicMin(&g.lo2[r], b.y0); atomicMax(&g.hi2[r], b.y1);
+    }
+    __syncthreads();
+    for (int r = tid; r < nreg; r += RO_T) {
+      int32_t* t = rec + 6 * (long)r;
+      t[0] = g.base[r]; t[1] = g.cnt[r]; t[2] = g.lo[r]; t[3] = g.lo2[r]; t[4] = g.hi[r]; t[5] = g.hi2[r];
+    }
+  }
   const int nk = ro_block_scan(keepf, n, wave_tot);  // keepf[pos] = index of the crop among the page's crops
   // compaction through a staging buffer (pairs[] holds >= 16 * cap words and is free again)
   for (int pos = tid; pos < n; pos += RO_T)
@@ -353,20 +548,22 @@ __global__ __launch_bounds__(RO_T) void reading_order_kernel(const float* __rest
   __threadfence();
   __syncthreads();
   for (long k = tid; k < 8L * nk; k += RO_T) dout[k] = pairs[k];
-  verdict(nk, L);
+  int nregions = 0;
+  if constexpr (REGIONS) nregions = ro_region_lds().nreg;
+  verdict(nk, L, nregions);
 }
 
-template <bool LINES, bool DESKEW = false>
+template <bool LINES, bool DESKEW = false, bool REGIONS = false>
 int ro_launch(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w, int min_text_size, int img_h,
               int img_w, double y_tol_ratio, double x_gap_ratio, int page_base, int32_t* order_out, int32_t* keep_out,
               int32_t* desc_out, int32_t* ncrop_out, void* workspace, RoLineOut lo, void* stream,
-              RoSkewOut so = RoSkewOut{nullptr, nullptr}) {
+              RoSkewOut so = RoSkewOut{nullptr, nullptr}, RoRegionOut go = RoRegionOut{nullptr, nullptr, nullptr, 0, 0.0, 0.0, 0.0}) {
   if (!boxes || !nbox || !order_out || !keep_out || !desc_out || !ncrop_out || !workspace) return MSOCR_E_ARG;
   if (N <= 0 || max_cand <= 0 || page_h <= 0 || page_w <= 0 || img_h <= 0 || img_w <= 0 || page_base < 0) return MSOCR_E_ARG;
   if ((uintptr_t)workspace & 15) return MSOCR_E_ARG;
-  MSOCR_LAUNCH((reading_order_kernel<LINES, DESKEW>), dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand),
+  MSOCR_LAUNCH((reading_order_kernel<LINES, DESKEW, REGIONS>), dim3(N), dim3(RO_T), 0, (hipStream_t)stream, boxes, nbox, max_cand, ro_cap(max_cand),
                page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base, order_out, keep_out, desc_out,
-               ncrop_out, (int32_t*)workspace, lo, so);
+               ncrop_out, (int32_t*)workspace, lo, so, go);
   return hipGetLastError() == hipSuccess ? MSOCR_OK : MSOCR_E_LAUNCH;
 }
 }  // namespace
@@ -416,4 +613,37 @@ extern "C" int msocr_reading_order_deskew(const float* boxes, const int32_t* nbo
   return ro_launch<true, true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base,
                                order_out, keep_out, desc_out, ncrop_out, workspace,
                                RoLineOut{line_out, lines_out, nlines_out, msocr_reading_order_line_rows(max_cand)}, stream, so);
+}
+
+extern "C" int msocr_reading_order_region_rows(int max_cand) { return max_cand < RO_MAXREGIONS ? max_cand : RO_MAXREGIONS; }
+
+extern "C" int64_t msocr_reading_order_regions_workspace_bytes(int N, int max_cand) {
+  const int cap = ro_cap(max_cand);
+  return (N > 0 && max_cand > 0) ? (int64_t)N * (ro_ws_words(cap) + 4L * cap + ro_region_words(cap)) * 4 : 0;
+}
+
+extern "C" int msocr_reading_order_regions(const float* boxes, const int32_t* nbox, int N, int max_cand, int page_h, int page_w,
+                                           int min_text_size, int img_h, int img_w, double y_tol_ratio, double x_gap_ratio,
+                                           int page_base, double col_gap_ratio, double row_gap_ratio, double col_min_height_ratio,
+                                           int deskew, int32_t* order_out, int32_t* keep_out, int32_t* desc_out, int32_t* ncrop_out,
+                                           int32_t* line_out, int32_t* lines_out, int32_t* nlines_out, int64_t* skew_out,
+                                           double* cs_out, int32_t* region_out, int32_t* regions_out, int32_t* nregions_out,
+                                           void* workspace, void* stream) {
+  if (!region_out || !regions_out || !nregions_out) return MSOCR_E_ARG;
+  if (!region_ratio_ok(col_gap_ratio) || !region_ratio_ok(row_gap_ratio) || !region_ratio_ok(col_min_height_ratio)) return MSOCR_E_ARG;
+  if (deskew != 0 && deskew != 1) return MSOCR_E_ARG;
+  if (deskew && (!skew_out || !cs_out)) return MSOCR_E_ARG;
+  const int given = (line_out ? 1 : 0) + (lines_out ? 1 : 0) + (nlines_out ? 1 : 0);
+  if (given != 0 && given != 3) return MSOCR_E_ARG;  // the line outputs: all three or none
+  const RoSkewOut so{skew_out, cs_out};
+  const RoRegionOut go{region_out, regions_out, nregions_out, msocr_reading_order_region_rows(max_cand), col_gap_ratio, row_gap_ratio,
+                       col_min_height_ratio};
+  const RoLineOut lo = given ? RoLineOut{line_out, lines_out, nlines_out, msocr_reading_order_line_rows(max_cand)}
+                             : RoLineOut{nullptr, nullptr, nullptr, 0};
+#define RO_REGIONS(L, D)                                                                                                              \
+  ro_launch<L, D, true>(boxes, nbox, N, max_cand, page_h, page_w, min_text_size, img_h, img_w, y_tol_ratio, x_gap_ratio, page_base, \
+                        order_out, keep_out, desc_out, ncrop_out, workspace, lo, stream, so, go)
+  if (deskew) return given ? RO_REGIONS(true, true) : RO_REGIONS(false, true);
+  return given ? RO_REGIONS(true, false) : RO_REGIONS(false, false);
+#undef RO_REGIONS
 }

@@ -103,6 +103,59 @@ def sort_boxes_reading_order_with_resolutions(boxes, y_tol_ratio=0.6, x_gap_rati
     return [back[b] for b in sort_boxes_reading_order(shrunk, y_tol_ratio, x_gap_ratio)]
 
 
+def xy_cut_regions(boxes, col_gap_ratio=2.0, row_gap_ratio=1.5, col_min_height_ratio=3.0, max_depth=6):
+    """XY-cut of integer boxes (x_min, y_min, x_max, y_max) into regions (include/msocr.h,
+    msocr_reading_regions_host): -> the leaves in reading order, each a list of ascending box indices.  A region is cut at every
+    empty vertical band at least col_gap_ratio * avg_h wide when it is at least col_min_height_ratio * avg_h tall, else at every
+    empty horizontal band at least row_gap_ratio * avg_h high; avg_h is the mean height of ALL boxes.  The ratios are placeholders,
+    not tuned values."""
+    n = len(boxes)
+    if n == 0:
+        return []
+    b = [tuple(int(v) for v in bx) for bx in boxes]
+    avg_h = float(sum(bx[3] - bx[1] for bx in b)) / float(n)
+    gx, gy, mh = col_gap_ratio * avg_h, row_gap_ratio * avg_h, col_min_height_ratio * avg_h
+    leaves = []
+
+    def cut(words, depth):
+        if depth < max_depth and len(words) > 1:
+            tall = float(max(b[i][3] for i in words) - min(b[i][1] for i in words)) >= mh
+            for lo, hi, g in ((0, 2, gx), (1, 3, gy)):
+                if lo == 0 and not tall:
+                    continue
+                segs, run = [], None
+                for i in sorted(words, key=lambda i: (b[i][lo], i)):
+                    if run is None or float(b[i][lo] - run) >= g:
+                        segs.append([])
+                    run = b[i][hi] if run is None else max(run, b[i][hi])
+                    segs[-1].append(i)
+                if len(segs) > 1:
+                    for seg in segs:
+                        cut(sorted(seg), depth + 1)
+                    return
+        leaves.append(list(words))
+
+    cut(list(range(n)), 0)
+    return leaves
+
+
+def sort_boxes_reading_order_regions(boxes, y_tol_ratio=0.6, x_gap_ratio=np.inf, col_gap_ratio=2.0, row_gap_ratio=1.5,
+                                     col_min_height_ratio=3.0, return_regions=False):
+    """sort_boxes_reading_order_with_resolutions behind an XY-cut (this package's extension): the boxes are shrunk off each other
+    over the whole page, the shrunk boxes are cut into regions (xy_cut_regions), and sort_boxes_reading_order runs inside every
+    region with the region's own mean height.  -> the boxes in column-aware reading order; with return_regions also the region
+    index of every returned box.  Integer boxes, as the pipeline forms them."""
+    boxes = [tuple(bx) for bx in boxes]
+    shrunk = resolve_intersections(boxes)
+    back = dict(zip(shrunk, boxes))  # page-wide, as sort_boxes_reading_order_with_resolutions
+    out, region = [], []
+    for r, leaf in enumerate(xy_cut_regions(shrunk, col_gap_ratio, row_gap_ratio, col_min_height_ratio)):
+        ordered = sort_boxes_reading_order([shrunk[i] for i in leaf], y_tol_ratio, x_gap_ratio)
+        out += [back[s] for s in ordered]
+        region += [r] * len(ordered)
+    return (out, region) if return_regions else out
+
+
 def _gaussian_blur_f32(mask, k):
     """cv2.GaussianBlur(mask, (k, k), 0) restated: separable kernel exp(-(x - c)^2 / (2 sigma^2)) normalised to 1 with OpenCV's
     sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8 for a non-positive sigma argument, BORDER_REFLECT_101 (parity unpinned: cv2 absent;

@@ -117,6 +117,22 @@ class TextLine(Block):
                                                              "as the reading order sees them (np.array(polygon, int32) truncation)")
 
 
+class Region(Block):
+    """One region of a page in reading order (a column, a heading, a paragraph cut off by wide empty bands), written by Pipeline
+    when `columns` is on (this package's extension): its words in reading order.  As for TextLine, a default model_dump() of a Page
+    serialises a Region as a Block."""
+
+    bbox: Tuple[int, int, int, int] = Field(..., description="(x_min, y_min, x_max, y_max): union of the words' integer boxes")
+    index: int = Field(..., description="0-based index of the region in the page's reading order", ge=0)
+
+
+class RegionLine(TextLine):
+    """A TextLine with the region it lies in, written by Pipeline when `columns` and `group_lines` are both on.  A line never spans
+    two regions, and the lines come region by region."""
+
+    region: int = Field(..., description="0-based index of the line's region in the page's reading order", ge=0)
+
+
 class Page(BaseModel):
     """All blocks of one page image."""
 

@@ -674,6 +674,72 @@ def deskew_boxes_host(quads, page_hw, skew, cs):
     return out
 
 
+COLUMN_PARAMS = {"col_gap_ratio": 2.0, "row_gap_ratio": 1.5, "col_min_height_ratio": 3.0}  # placeholders, not tuned values
+
+
+def column_ratios(params=None):
+    """The three ratios of the column-aware reading order as floats, (col_gap_ratio, row_gap_ratio, col_min_height_ratio), from a
+    mapping that may leave any of them out (COLUMN_PARAMS then).  +inf is taken (never cuts); NaN or a negative ratio is refused."""
+    p = {**COLUMN_PARAMS, **(params or {})}
+    if set(p) != set(COLUMN_PARAMS):
+        raise ValueError(f"column_params takes {sorted(COLUMN_PARAMS)}, got {sorted(p)}")
+    r = tuple(float(p[k]) for k in COLUMN_PARAMS)
+    if not all(v >= 0.0 for v in r):
+        raise ValueError(f"column_params: a ratio must be >= 0 (+inf = never cut), got {p}")
+    return r
+
+
+class ReadingRegions(NamedTuple):
+    """The regions behind a column-aware ReadingOrder (`reading_order_regions`), per page, on the device."""
+    region: torch.Tensor    # [N,max_cand] i32: the region of every position of `order`, regions numbered in reading order
+    regions: torch.Tensor   # [N,rows,6] i32: per region {first, count, x0, y0, x1, y1}: its span of positions and the union of its words' boxes
+    nregions: torch.Tensor  # [N] i32: regions per page; -1 exactly where ncrop is -1
+
+
+def reading_order_regions(boxes, nbox, page_hw, min_text_size, img_h, img_w, page_base=0, y_tol_ratio=0.6, x_gap_ratio=float("inf"),
+                          col_gap_ratio=COLUMN_PARAMS["col_gap_ratio"], row_gap_ratio=COLUMN_PARAMS["row_gap_ratio"],
+                          col_min_height_ratio=COLUMN_PARAMS["col_min_height_ratio"], workspace=None, lines=True, deskew=False):
+    """The column-aware reading order (msocr_reading_order_regions): the page is cut into regions at its wide
+    empty bands, and reading_order_lines' rule runs inside every region.  deskew=True: in the deskewed frame, as reading_order_deskew.
+    lines=False: without the three line outputs.  Returns (ReadingOrder, ReadingLines or None, PageSkew or None, ReadingRegions)."""
+    _need_cuda(boxes, nbox)
+    N, max_cand, _ = boxes.shape
+    dev = boxes.device
+    ws = workspace
+    if ws is None:
+        ws = torch.empty((nat.lib().msocr_reading_order_regions_workspace_bytes(N, max_cand),), dtype=torch.uint8, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    ro = ReadingOrder(i32(N, max_cand), i32(N, max_cand), i32(N, max_cand, 8), i32(N))
+    rl = ReadingLines(i32(N, max_cand), i32(N, nat.lib().msocr_reading_order_line_rows(max_cand), 6), i32(N)) if lines else None
+    sk = PageSkew(torch.empty((N, 4), dtype=torch.int64, device=dev), torch.empty((N, 2), dtype=torch.float64, device=dev)) if deskew else None
+    rg = ReadingRegions(i32(N, max_cand), i32(N, nat.lib().msocr_reading_order_region_rows(max_cand), 6), i32(N))
+    nat.check(nat.lib().msocr_reading_order_regions(boxes.data_ptr(), nbox.data_ptr(), N, max_cand, int(page_hw[0]), int(page_hw[1]),
+                                                    int(min_text_size), int(img_h), int(img_w), float(y_tol_ratio), float(x_gap_ratio),
+                                                    int(page_base), float(col_gap_ratio), float(row_gap_ratio), float(col_min_height_ratio),
+                                                    1 if deskew else 0, *[t.data_ptr() for t in ro],
+                                                    *([t.data_ptr() for t in rl] if lines else [None] * 3),
+                                                    *([t.data_ptr() for t in sk] if deskew else [None] * 2),
+                                                    *[t.data_ptr() for t in rg], ws.data_ptr(), _stream()), "reading_order_regions")
+    return ro, rl, sk, rg
+
+
+def reading_regions_host(aabbs_i32, y_tol_ratio=0.6, x_gap_ratio=float("inf"), col_gap_ratio=COLUMN_PARAMS["col_gap_ratio"],
+                         row_gap_ratio=COLUMN_PARAMS["row_gap_ratio"], col_min_height_ratio=COLUMN_PARAMS["col_min_height_ratio"]):
+    """Integer word boxes [n,4] -> (order [n], line [n], lines [L,6], region [n], regions [R,6]) as numpy int32 through the host twin
+    msocr_reading_regions_host: reading_lines_host behind an XY-cut of the page, with the region of every position and per region
+    {first, count, x0, y0, x1, y1}."""
+    boxes = np.ascontiguousarray(aabbs_i32, dtype=np.int32).reshape(-1, 4)
+    n = len(boxes)
+    order, line, lines = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty((n, 6), dtype=np.int32)
+    region, regions = np.empty(n, dtype=np.int32), np.empty((n, 6), dtype=np.int32)
+    nlines, nregions = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    nat.check(nat.lib().msocr_reading_regions_host(boxes.ctypes.data, n, float(y_tol_ratio), float(x_gap_ratio), float(col_gap_ratio),
+                                                   float(row_gap_ratio), float(col_min_height_ratio), order.ctypes.data, line.ctypes.data,
+                                                   lines.ctypes.data, nlines.ctypes.data, region.ctypes.data, regions.ctypes.data,
+                                                   nregions.ctypes.data), "reading_regions_host")
+    return order, line, lines[:int(nlines[0])].copy(), region, regions[:int(nregions[0])].copy()
+
+
 def nchw_to_nhwc(x_f32, dtype, out=None):
     _need_cuda(x_f32)
     N, C, H, W = x_f32.shape

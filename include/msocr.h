@@ -521,6 +521,43 @@ int msocr_edit_distance_pairs_host(const int32_t* a_ids, const int32_t* a_trun, 
 int msocr_wordlist_check_host(const int32_t* word_begin_host, const int32_t* word_tok_host, int n_words, int n_tok, int V,
                               int max_word_len);
 
+/* ---- detection quality: predicted quads matched to ground truth (an extension beyond the reference's inference code:
+ * EAST.evaluate, Pipeline.evaluate, detectors.match_detections) ----
+ * The matching rule of the reference's compute_f1 (detectors/_east/utils.py:435-474) with one change: the IoU is the reference's own
+ * lanms.polygon_iou (lanms.py:60-91; csrc/quad_iou.h restates it bit for bit), not shapely's.
+ * Inputs: quads [n][4][2] f32; all arithmetic is f64 on the converted values.
+ * Validity: a quad is valid iff its eight coordinates are finite and the four turn cross products (v[i+1]-v[i]) x (v[i+2]-v[i+1])
+ *   are all > 0 or all < 0 (strictly convex).  This stands in for shapely's is_valid: self-intersecting and degenerate quads are
+ *   invalid under both rules; a concave simple quad is valid for shapely and INVALID here (stated deviation).
+ * Canonical winding: a valid quad whose cross products are negative is read as [v0, v3, v2, v1], predictions and ground truth alike.
+ *   polygon_iou takes the left of the clip polygon's edges as inside (polygon_iou(q, q reversed) is 0.0, polygon_iou(q, q) is 1.0);
+ *   shapely is winding-blind and annotations come in either winding.
+ * IoU: polygon_iou(prediction, ground truth), prediction as subject, ground truth as clip.  The function is not bitwise symmetric:
+ *   the argument order is part of the definition.
+ * Matching, per page and per threshold t independently:
+ *   predictions in the given order; an invalid prediction is a false positive (match -2, iou 0);
+ *   a valid prediction starts at best_iou = 0, bj = -1 and scans the ground truths j ascending that are valid and unused at this t,
+ *   taking j when iou > best_iou (strict: the smallest j wins a tie); best_iou >= t: true positive, match = bj, used[bj] set;
+ *   otherwise false positive, match = -1, nothing marked.  iou_out holds best_iou as it stood at the decision (0 when no unused
+ *   ground truth overlapped).  An invalid ground truth is never matched but counts: fn = n_gt - tp.  counts = {tp, fp, fn}.
+ * Thresholds: T f64 values in (0, 1], read from HOST memory by both entry points and handed to the kernel as an argument (a
+ *   threshold <= 0 would mark used[-1] in the reference).
+ * Envelope: 0 <= n_pred[p] <= max_pred <= 16384, 0 <= n_gt[p] <= max_gt <= 16384, 1 <= T <= 16, N >= 0 (N == 0: MSOCR_OK, no launch).
+ *   Null pointers (the workspace included), a threshold outside (0, 1] or not finite and shapes outside the envelope return MSOCR_E_ARG
+ *   before any launch; the ws_bytes query returns MSOCR_E_ARG for them.  The host twin also refuses a count outside [0, max]; the
+ *   device entry point cannot read its counts and the kernels clamp them into [0, max].
+ * Outputs: match_out [N][T][max_pred] i32, iou_out [N][T][max_pred] f64: entries i < n_pred[p] are written, the others are left as
+ *   they were; counts_out [N][T][3] i32.  workspace: msocr_quad_match_ws_bytes bytes of device memory, 8-byte aligned, contents
+ *   irrelevant (candidate lists of 8 slots per prediction; a prediction with more overlaps is recomputed against the whole page, the
+ *   result does not depend on the slot count).  Three launches, no allocation, no synchronisation, capturable. */
+int64_t msocr_quad_match_ws_bytes(int N, int max_pred, int max_gt);
+int msocr_quad_match(const float* pred, const int32_t* n_pred, int max_pred, const float* gt, const int32_t* n_gt, int max_gt, int N,
+                     const double* thresholds_host, int T, int32_t* match_out, double* iou_out, int32_t* counts_out, void* workspace,
+                     void* stream);
+int msocr_quad_match_host(const float* pred_host, const int32_t* n_pred_host, int max_pred, const float* gt_host,
+                          const int32_t* n_gt_host, int max_gt, int N, const double* thresholds_host, int T, int32_t* match_out,
+                          double* iou_out, int32_t* counts_out);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

@@ -982,6 +982,64 @@ class Pipeline:
         self._attach_details(words, [page], chars)
         return page, logps
 
+    def evaluate(self, images, gt_pages, iou: float = 0.5) -> Dict[str, Any]:
+        """Detection, recognition and end-to-end quality against an annotated set (this package's extension).
+
+        gt_pages[i]: the annotated words of images[i], a list of (quad [4,2], text).  Every image goes through `predict` as this
+        pipeline is configured; the words of all blocks, flattened in the order they come back, are the predictions.  They are
+        matched to the annotations at the one IoU threshold `iou` by detectors.match_detections (on the detector's device when it
+        is this package's EAST, else by the host twin), and for the matched pairs the Levenshtein distances come from
+        recognizers.edit_distances (on the recogniser's device when it is this package's TRBA).  A word the pipeline left without a
+        text reads as "".  Returns
+          "detection":   {precision, recall, f1, tp, fp, fn}
+          "recognition": {n, accuracy, cer_micro, cer_mean} over the matched pairs, with TRBA.evaluate's conventions (an empty
+                         reference counts inf in cer_mean if the reading is not empty, else 0; no pairs: all 0)
+          "end_to_end":  {precision, recall, f1}: a true positive is a matched word whose text is identical to the annotation's
+          "matches":     per page a list of (prediction index, ground-truth index, iou, reference text, recognised text)."""
+        from .detectors import detection_f1, match_detections
+        from .recognizers import edit_distances
+        images, gt_pages = list(images), [list(g) for g in gt_pages]
+        if len(images) != len(gt_pages):
+            raise ValueError(f"{len(images)} images but {len(gt_pages)} annotated pages")
+        pred_quads, pred_texts = [], []
+        for image in images:
+            page = self.predict(image)
+            words = [w for block in page.blocks for w in block.words]
+            pred_quads.append(np.array([w.polygon for w in words], dtype=np.float32).reshape(-1, 4, 2))
+            pred_texts.append([w.text if w.text is not None else "" for w in words])
+        gt_quads = [np.array([q for q, _t in g], dtype=np.float32).reshape(-1, 4, 2) for g in gt_pages]
+        m = match_detections(pred_quads, gt_quads, [float(iou)], device=self.detector.device if isinstance(self.detector, EAST) else None)
+        det = detection_f1(m.counts, m.thresholds)
+        matches, refs, hyps = [], [], []
+        for p, g in enumerate(gt_pages):
+            rows = []
+            for i, j in enumerate(m.match[p][0].tolist()):
+                if j >= 0:
+                    rows.append((i, j, float(m.iou[p][0, i]), g[j][1], pred_texts[p][i]))
+                    refs.append(g[j][1])
+                    hyps.append(pred_texts[p][i])
+            matches.append(rows)
+        is_trba = isinstance(self.recognizer, TRBA)
+        dist = edit_distances(refs, hyps, stoi=self.recognizer.stoi if is_trba else None,
+                              device=self.recognizer.device if is_trba else None).astype(np.float64)
+        n = len(refs)
+        L = np.array([len(r) for r in refs], dtype=np.float64)
+        cer = np.where(L > 0, dist / np.maximum(L, 1), np.where(dist > 0, np.inf, 0.0))
+        total = float(L.sum())
+        same = sum(1 for r, h in zip(refs, hyps) if r == h)
+        n_pred, n_gt = sum(len(q) for q in pred_quads), sum(len(g) for g in gt_pages)
+        prec = same / n_pred if n_pred > 0 else 0.0
+        rec = same / n_gt if n_gt > 0 else 0.0
+        return {
+            "detection": {"precision": float(det["precision"][0]), "recall": float(det["recall"][0]), "f1": float(det["f1"][0]),
+                          "tp": int(det["tp"][0]), "fp": int(det["fp"][0]), "fn": int(det["fn"][0])},
+            "recognition": {"n": n, "accuracy": same / n if n else 0.0,
+                            "cer_micro": (float(dist.sum()) / total if total > 0 else (float("inf") if dist.sum() > 0 else 0.0)),
+                            "cer_mean": float(cer.mean()) if n else 0.0},
+            "end_to_end": {"precision": prec, "recall": rec, "f1": 2 * prec * rec / (prec + rec) if (prec + rec) > 0 else 0.0},
+            "matches": matches,
+        }
+
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):
         results = []

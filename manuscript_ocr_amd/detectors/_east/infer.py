@@ -390,3 +390,62 @@ class EAST:
             raise TypeError(f"Unsupported type for image input: {type(img_or_path)}")  # read_image's contract (utils.py:494-495)
         return self.predict_batch([img_or_path], vis=vis, profile=profile, return_maps=return_maps,
                                   sort_reading_order=sort_reading_order)[0]
+
+    # ------------------------------------------------------------------------------------- evaluation (an extension)
+    def evaluate(self, images: Sequence[Any], gt_quads: Sequence[Any], thresholds=None, batch: int = 16) -> Dict[str, Any]:
+        """Detection quality against a ground truth (the reference has it in a script around compute_f1).
+
+        images: what `predict_batch` takes; gt_quads[i]: the [n,4,2] ground-truth quads of image i.  thresholds: IoU thresholds in
+        (0, 1], at most 16; None = metrics.DEFAULT_IOU_THRESHOLDS (0.50 ... 0.95).  The pages go through the batched route of
+        `predict_batch`, `batch` at a time, with this instance's settings, and the boxes the device tail leaves are matched where
+        they are (ops.quad_match); only match indices, IoUs and counts come back.  A chunk whose box tail fell to the host (a page above
+        its capacity, or device_tail off) is matched on the device all the same, from the boxes the host tail returns.
+        Returns metrics.detection_f1's dict plus n_images, n_pred, n_gt, "matches" and "ious": per page an int32 / f64 [T, n_pred]
+        array in the order of `predict_batch`'s words (ground-truth index, -1 false positive, -2 invalid quad)."""
+        from . import metrics
+        images, gt_quads = list(images), list(gt_quads)
+        if len(images) != len(gt_quads):
+            raise ValueError(f"{len(images)} images but {len(gt_quads)} pages of ground truth")
+        if int(batch) < 1:
+            raise ValueError(f"batch must be at least 1, got {batch}")
+        th = ops._thresholds(metrics.DEFAULT_IOU_THRESHOLDS if thresholds is None else thresholds)
+        counts, matches, ious = [], [], []
+        for s in range(0, len(images), int(batch)):
+            imgs, decoded = [], []
+            for im in images[s: s + int(batch)]:  # the ingest of predict_batch
+                t = ingest.read_image_device(im, self.device) if self.device_ingest else None
+                imgs.append(np.broadcast_to(np.uint8(0), tuple(t.shape)) if t is not None else read_image(im))
+                decoded.append(t)
+            pages = [t if t is not None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for t, a in zip(decoded, imgs)]
+            if len({im.shape for im in imgs}) == 1:
+                pages = torch.stack(pages)
+            gt, n_gt = metrics.pack_pages(gt_quads[s: s + int(batch)], "ground truth")
+            handle = self.detect_start(pages)
+            fn_h = handle.final_counts.cpu().numpy() if handle.final_counts is not None else None
+            if fn_h is not None and bool(np.all(handle.counts.cpu().numpy() >= 0)) and bool(np.all(fn_h >= 0)):
+                try:
+                    n_pred = fn_h.astype(np.int32)
+                    pred = handle.final_boxes[:, : int(fn_h.max()), :8].contiguous().view(len(imgs), int(fn_h.max()), 4, 2)
+                    out = ops.quad_match(pred, handle.final_counts.contiguous(), torch.from_numpy(gt).to(pred.device),
+                                         torch.from_numpy(n_gt).to(pred.device), th)
+                    m, i, c = (t.cpu().numpy() for t in out)
+                finally:
+                    if handle.graph is not None:
+                        handle.graph.release()
+            else:  # the host tail (or its error for a decode overflow); detect_finish releases the graph instance
+                res = self.detect_finish(handle, imgs)
+                quads = [np.array([w.polygon for w in r["page"].blocks[0].words], dtype=np.float32).reshape(-1, 4, 2) for r in res]
+                pred_h, n_pred = metrics.pack_pages(quads, "predictions")
+                dev = torch.device(self.device)
+                with torch.cuda.device(dev):
+                    out = ops.quad_match(*(torch.from_numpy(a).to(dev) for a in (pred_h, n_pred, gt, n_gt)), th)
+                m, i, c = (t.cpu().numpy() for t in out)
+            counts.append(c)
+            for p, n in enumerate(n_pred):
+                matches.append(m[p, :, :n].copy())
+                ious.append(i[p, :, :n].copy())
+        counts = np.concatenate(counts) if counts else np.zeros((0, len(th), 3), dtype=np.int32)
+        out = metrics.detection_f1(counts, th)
+        out.update(n_images=len(images), n_pred=int(sum(mm.shape[1] for mm in matches)),
+                   n_gt=int(sum(len(np.asarray(g).reshape(-1, 8)) for g in gt_quads)), matches=matches, ious=ious)
+        return out

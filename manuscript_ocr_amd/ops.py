@@ -1024,3 +1024,68 @@ def quad_crop(pages_u8, qdesc_host, img_h, img_w, qdesc_dev=None):
     quadrilaterals (msocr_quad_crop).  Mirrors `crop_resize_pad`: qdesc_dev = the same descriptors already on the device;
     qdesc_host may be None when they were produced there (quad_crop_descriptors): the kernel then validates every descriptor itself."""
     return _crop("msocr_quad_crop", 12, pages_u8, qdesc_host, img_h, img_w, qdesc_dev)
+
+
+# ------------------------------------------------------------------------------------------- detection quality
+def _thresholds(thresholds):
+    th = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+    if th.ndim != 1:
+        raise ValueError("thresholds must be a scalar or a one-dimensional sequence")
+    return th
+
+
+def quad_match_workspace_bytes(N, max_pred, max_gt):
+    n = nat.lib().msocr_quad_match_ws_bytes(int(N), int(max_pred), int(max_gt))
+    nat.check(min(n, 0), "quad_match_ws_bytes")
+    return int(n)
+
+
+def quad_match(pred, n_pred, gt, n_gt, thresholds, workspace=None, out=None):
+    """pred [N,max_pred,4,2] f32, n_pred [N] i32, gt [N,max_gt,4,2] f32, n_gt [N] i32 (device), thresholds: T f64 values in (0, 1]
+    (host) -> (match [N,T,max_pred] i32, iou [N,T,max_pred] f64, counts [N,T,3] i32 = tp, fp, fn), all on the device
+    (msocr_quad_match: the matching rule of include/msocr.h, "detection quality").  Entries behind a page's n_pred are not written.
+    out: the three tensors to write into."""
+    _need_cuda(pred, n_pred, gt, n_gt)
+    th = _thresholds(thresholds)
+    N, max_pred, max_gt, T = int(pred.shape[0]), int(pred.shape[1]), int(gt.shape[1]), len(th)
+    if tuple(pred.shape[2:]) != (4, 2) or tuple(gt.shape[2:]) != (4, 2) or gt.shape[0] != N or n_pred.numel() != N or n_gt.numel() != N:
+        raise ValueError("quads are [N,max,4,2] with one count per page")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32 or n_pred.dtype != torch.int32 or n_gt.dtype != torch.int32:
+        raise TypeError("quads are float32, counts int32")
+    if not (pred.is_contiguous() and gt.is_contiguous() and n_pred.is_contiguous() and n_gt.is_contiguous()):
+        raise ValueError("quad_match takes dense tensors")
+    dev = pred.device
+    if workspace is None:
+        workspace = torch.empty((quad_match_workspace_bytes(N, max_pred, max_gt),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((N, T, max_pred), dtype=torch.int32, device=dev), torch.empty((N, T, max_pred), dtype=torch.float64, device=dev),
+               torch.empty((N, T, 3), dtype=torch.int32, device=dev))
+    match, iou, counts = out
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    ptr = [t.data_ptr() or workspace.data_ptr() for t in (pred, n_pred, gt, n_gt, match, iou, counts)]
+    nat.check(nat.lib().msocr_quad_match(ptr[0], ptr[1], max_pred, ptr[2], ptr[3], max_gt, N, th.ctypes.data, T, ptr[4], ptr[5], ptr[6],
+                                         workspace.data_ptr(), _stream()), "quad_match")
+    return match, iou, counts
+
+
+def quad_match_host(pred, n_pred, gt, n_gt, thresholds):
+    """The CPU twin of `quad_match` (msocr_quad_match_host) on numpy arrays: the same three arrays, bit for bit.  Entries behind a
+    page's n_pred hold match -3 and iou NaN (the entry point leaves them unwritten)."""
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    gt = np.ascontiguousarray(gt, dtype=np.float32)
+    n_pred = np.ascontiguousarray(n_pred, dtype=np.int32).reshape(-1)
+    n_gt = np.ascontiguousarray(n_gt, dtype=np.int32).reshape(-1)
+    th = _thresholds(thresholds)
+    N, T = len(n_pred), len(th)
+    if pred.ndim != 4 or gt.ndim != 4 or pred.shape[0] != N or gt.shape[0] != N or pred.shape[2:] != (4, 2) or gt.shape[2:] != (4, 2) \
+            or len(n_gt) != N:
+        raise ValueError("quads are [N,max,4,2] with one count per page")
+    max_pred, max_gt = pred.shape[1], gt.shape[1]
+    match = np.full((N, T, max_pred), -3, dtype=np.int32)
+    iou = np.full((N, T, max_pred), np.nan, dtype=np.float64)
+    counts = np.zeros((N, T, 3), dtype=np.int32)
+    pad = np.zeros(8, dtype=np.float64)  # an address for arrays without elements
+    ptr = [a.ctypes.data if a.size else pad.ctypes.data for a in (pred, n_pred, gt, n_gt, match, iou, counts)]
+    nat.check(nat.lib().msocr_quad_match_host(ptr[0], ptr[1], max_pred, ptr[2], ptr[3], max_gt, N, th.ctypes.data, T, ptr[4], ptr[5],
+                                              ptr[6]), "quad_match_host")
+    return match, iou, counts

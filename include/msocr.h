@@ -558,6 +558,35 @@ int msocr_quad_match_host(const float* pred_host, const int32_t* n_pred_host, in
                           const int32_t* n_gt_host, int max_gt, int N, const double* thresholds_host, int T, int32_t* match_out,
                           double* iou_out, int32_t* counts_out);
 
+/* ---- page-level error rates: the edit distance of long sequences (an extension beyond the reference's inference code:
+ * recognizers.sequence_edit_distances / text_error_rates, Pipeline.evaluate_text; csrc/edit_distance_long.hip,
+ * csrc/edit_distance_long.h) ----
+ * The exact Levenshtein distance (unit costs for insertion, deletion and substitution) between N pairs of int32 token sequences of
+ * 0 .. 16384 tokens each (MSOCR_EDL_MAX_LEN): a page's running text against its transcription, as characters or as words.
+ * Integers; the host twin runs the same header block by block.
+ * Tokens: CSR arrays.  a_tok holds the patterns, b_tok the texts, pair p being a_tok[a_off[p] .. a_off[p + 1]) against
+ * b_tok[b_off[p] .. b_off[p + 1]); device memory for msocr_edit_distance_long, host memory for the twin.  The offset arrays
+ * a_off [N + 1], b_off [N + 1] and the alphabet sizes v [N] are HOST memory on both routes.  The token arrays hold at least
+ * a_off[N] / b_off[N] elements; a pointer to an array without elements must still be non-null.
+ * v[p]: tokens of pair p in [0, v[p]) compare by equality; a token outside it, on either side, equals nothing (the rule of
+ * msocr_edit_distance_pairs) and is never an index.  The distance is symmetric, so either side may be the pattern; the pattern's
+ * side decides the workspace.
+ * m == 0 gives n, n == 0 gives m; N == 0: MSOCR_OK, nothing launched.  dist_out [N] i32; nothing behind it is written.
+ * workspace (device route): device memory, 8-byte aligned, contents irrelevant, of at least msocr_edit_distance_long_ws_bytes =
+ *   32 N + sum over the pairs of v[p] * ceil(m_p / 64) * 8 bytes: the uploaded heads (one 32-byte record per pair) and the pairs'
+ *   match-mask tables [v][ceil(m / 64)] of 64-bit words, which a small kernel builds before the distance kernel runs.
+ * Refused with MSOCR_E_ARG before any launch: N < 0, a null pointer, an offset array that does not start at a value >= 0 or
+ *   decreases, a length above the cap, v[p] < 0, a workspace that is misaligned or smaller than required (workspace_bytes); the
+ *   ws_bytes query returns MSOCR_E_ARG for the same arrays.  The host twin also returns MSOCR_E_ARG when it cannot allocate a table.
+ * The entry point uploads the heads from a buffer of its own and waits for that copy on `stream`; three launches follow, which
+ *   the host does not wait for.  Not capturable: this is an evaluation call.  One wave per pair: a batch of a few long pairs is
+ *   bound by latency, not by the chip (measured: profiles/edit_distance_long.txt). */
+int64_t msocr_edit_distance_long_ws_bytes(const int32_t* a_off_host, const int32_t* b_off_host, const int32_t* v_host, int N);
+int msocr_edit_distance_long(const int32_t* a_tok, const int32_t* a_off_host, const int32_t* b_tok, const int32_t* b_off_host,
+                             const int32_t* v_host, int N, int32_t* dist_out, void* workspace, int64_t workspace_bytes, void* stream);
+int msocr_edit_distance_long_host(const int32_t* a_tok_host, const int32_t* a_off_host, const int32_t* b_tok_host,
+                                  const int32_t* b_off_host, const int32_t* v_host, int N, int32_t* dist_out);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

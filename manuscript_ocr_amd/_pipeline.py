@@ -1040,6 +1040,28 @@ class Pipeline:
             "matches": matches,
         }
 
+    def evaluate_text(self, images, gt_texts) -> Dict[str, Any]:
+        """Character and word error rate of the pages' running text, in this pipeline's reading order, against plain transcriptions
+        (this package's extension).  Unlike `evaluate` it needs no boxes and it sees the order: a page read
+        across its gutter scores worse than one read column by column.
+
+        gt_texts[i]: the transcription of images[i], one str.  Every image goes through `predict` as this pipeline is configured;
+        the hypothesis is the texts of all blocks' words, flattened in the order they come back (the order `evaluate` uses) and
+        joined by one space; a word without text is skipped.  Returns recognizers.text_error_rates' figures, per page and pooled
+        (distances on the recogniser's device when it is this package's TRBA, else by the host twin: foreign plugins need no GPU),
+        and "hypotheses": the pages' texts as they were compared."""
+        from .recognizers import text_error_rates
+        images, gt_texts = list(images), list(gt_texts)
+        if len(images) != len(gt_texts):
+            raise ValueError(f"{len(images)} images but {len(gt_texts)} transcriptions")
+        hyps = []
+        for image in images:
+            page = self.predict(image)
+            hyps.append(" ".join(w.text for block in page.blocks for w in block.words if w.text))
+        out = text_error_rates(gt_texts, hyps, device=self.recognizer.device if isinstance(self.recognizer, TRBA) else None)
+        out["hypotheses"] = hyps
+        return out
+
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):
         results = []

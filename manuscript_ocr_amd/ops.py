@@ -1089,3 +1089,66 @@ def quad_match_host(pred, n_pred, gt, n_gt, thresholds):
     nat.check(nat.lib().msocr_quad_match_host(ptr[0], ptr[1], max_pred, ptr[2], ptr[3], max_gt, N, th.ctypes.data, T, ptr[4], ptr[5],
                                               ptr[6]), "quad_match_host")
     return match, iou, counts
+
+
+# ------------------------------------------------------------------------------------------- page-level error rates
+EDL_MAX_LEN = 16384  # msocr.h MSOCR_EDL_MAX_LEN: tokens of either side of a pair
+
+
+def _edl_heads(a_off, b_off, v):
+    a_off = np.ascontiguousarray(a_off, dtype=np.int32).reshape(-1)
+    b_off = np.ascontiguousarray(b_off, dtype=np.int32).reshape(-1)
+    v = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+    N = len(v)
+    if len(a_off) != N + 1 or len(b_off) != N + 1:
+        raise ValueError("offsets are [N + 1] for v [N]")
+    return a_off, b_off, v, N
+
+
+def edit_distance_long_workspace_bytes(a_off, b_off, v):
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    n = nat.lib().msocr_edit_distance_long_ws_bytes(a_off.ctypes.data, b_off.ctypes.data, v.ctypes.data, N)
+    nat.check(min(n, 0), "edit_distance_long_ws_bytes")
+    return int(n)
+
+
+def edit_distance_long(a_tok, a_off, b_tok, b_off, v, workspace=None, out=None):
+    """Levenshtein distance of N pairs of token sequences of up to EDL_MAX_LEN tokens each (msocr_edit_distance_long; include/msocr.h,
+    "page-level error rates").  a_tok, b_tok: int32 device tensors, the patterns and the texts one after the other; a_off, b_off
+    [N + 1] and v [N]: host arrays (numpy), pair p = a_tok[a_off[p]:a_off[p + 1]] against b_tok[b_off[p]:b_off[p + 1]], tokens in
+    [0, v[p]) compare by equality and every other token equals nothing.  -> dist [N] i32 on the device (out: the tensor to write into)."""
+    _need_cuda(a_tok, b_tok)
+    if a_tok.dtype != torch.int32 or b_tok.dtype != torch.int32 or a_tok.dim() != 1 or b_tok.dim() != 1:
+        raise TypeError("tokens are one-dimensional int32 tensors")
+    if not (a_tok.is_contiguous() and b_tok.is_contiguous()):
+        raise ValueError("edit_distance_long takes dense tensors")
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    if N and (int(a_off[-1]) > a_tok.numel() or int(b_off[-1]) > b_tok.numel()):
+        raise ValueError("offsets reach past the token tensors")
+    dev = a_tok.device
+    need = edit_distance_long_workspace_bytes(a_off, b_off, v)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((N,), dtype=torch.int32, device=dev)
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    ptr = [t.data_ptr() or workspace.data_ptr() for t in (a_tok, b_tok, out)]
+    nat.check(nat.lib().msocr_edit_distance_long(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2],
+                                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+              "edit_distance_long")
+    return out
+
+
+def edit_distance_long_host(a_tok, a_off, b_tok, b_off, v):
+    """The CPU twin of `edit_distance_long` (msocr_edit_distance_long_host) on numpy arrays -> dist [N] int32."""
+    a_tok = np.ascontiguousarray(a_tok, dtype=np.int32).reshape(-1)
+    b_tok = np.ascontiguousarray(b_tok, dtype=np.int32).reshape(-1)
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    if N and (int(a_off[-1]) > a_tok.size or int(b_off[-1]) > b_tok.size):
+        raise ValueError("offsets reach past the token arrays")
+    out = np.empty(N, dtype=np.int32)
+    pad = np.zeros(2, dtype=np.int32)  # an address for arrays without elements
+    ptr = [x.ctypes.data if x.size else pad.ctypes.data for x in (a_tok, b_tok, out)]
+    nat.check(nat.lib().msocr_edit_distance_long_host(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2]),
+              "edit_distance_long_host")
+    return out

@@ -6,14 +6,26 @@
   accuracy(refs, hyps)                                 share of exact matches; 0 for no pairs
 
 The distances come from msocr_edit_distance_pairs (device given) or its host twin (device None, no GPU needed): unit costs, strings
-of at most 64 characters.  Word error rate is not provided: the reference takes it from jiwer, whose tokenisation rules cannot be pinned
-here; for single-word crops it equals 1 - accuracy.
+of at most 64 characters.
+
+Running text (a page in reading order against its transcription), over msocr_edit_distance_long and its host
+twin, sequences of at most 16384 tokens:
+
+  sequence_edit_distances(refs, hyps, device=None)   distance of every pair of strings (characters) or lists (items), int32 array
+  word_error_rate(ref, hyp)                           word distance / words of ref, words = str.split(); empty reference as for CER
+  text_error_rates(refs, hyps, device=None)           per pair and pooled: character and word distances, CER, WER, bag-of-words errors
+
+The word error rate here is this package's: words are str.split() of the strings as they are.  The reference takes WER from jiwer,
+whose transforms cannot be pinned here, so the two need not agree on punctuation or case; for single-word crops WER equals 1 - accuracy.
 """
+from collections import Counter
+
 import numpy as np
 
 from ... import _native as nat
 
 _MAX_LEN, _MAX_V = 64, 512
+MAX_SEQUENCE_LEN = 16384  # msocr.h MSOCR_EDL_MAX_LEN
 
 
 def _encode(refs, hyps, stoi):
@@ -89,3 +101,108 @@ def accuracy(references, hypotheses):
     if not references:
         return 0.0
     return sum(1 for r, h in zip(references, hypotheses) if r == h) / len(references)
+
+
+# ------------------------------------------------------------------------------------------------- running text
+def _tokens(x):
+    if isinstance(x, str):
+        return x
+    if isinstance(x, (list, tuple)):
+        return x
+    raise TypeError(f"a sequence is a str (its characters) or a list of hashable items, got {type(x).__name__}")
+
+
+def _encode_pair(ref, hyp):
+    """One pair as (pattern ids, text ids, v): the shorter side is the pattern (the distance is symmetric, and the pattern's side
+    sizes the match-mask table); its distinct tokens are numbered 0 .. v - 1 in order of first occurrence, the other side's remaining
+    tokens get ids >= v: equal tokens equal ids, none of which can match the pattern."""
+    a, b = (hyp, ref) if len(hyp) < len(ref) else (ref, hyp)
+    table = {}
+    pat = [table.setdefault(t, len(table)) for t in a]
+    v = len(table)
+    txt = [table.setdefault(t, len(table)) for t in b]
+    return pat, txt, v
+
+
+def sequence_edit_distances(refs, hyps, device=None):
+    """Levenshtein distance (unit costs) between refs[i] and hyps[i] -> int32 [N].  An item is a str (tokens = its characters) or a
+    list / tuple of hashables (tokens = its items, compared by equality); at most 16384 tokens a side (ValueError above).
+    device None: the host twin msocr_edit_distance_long_host (no GPU needed); a device: msocr_edit_distance_long there."""
+    refs, hyps = [_tokens(r) for r in refs], [_tokens(h) for h in hyps]
+    if len(refs) != len(hyps):
+        raise ValueError(f"{len(refs)} references but {len(hyps)} hypotheses")
+    N = len(refs)
+    if N == 0:
+        return np.zeros(0, dtype=np.int32)
+    for s in refs + hyps:
+        if len(s) > MAX_SEQUENCE_LEN:
+            raise ValueError(f"a sequence of {len(s)} tokens; at most {MAX_SEQUENCE_LEN} are provided")
+    from ... import ops
+    pats, txts, v = [], [], np.empty(N, dtype=np.int32)
+    for p, (r, h) in enumerate(zip(refs, hyps)):
+        pat, txt, v[p] = _encode_pair(r, h)
+        pats.append(pat)
+        txts.append(txt)
+    if max(sum(len(x) for x in pats), sum(len(x) for x in txts)) > np.iinfo(np.int32).max:
+        raise ValueError("more than 2^31 - 1 tokens in one call: split the batch")
+    a_off = np.concatenate([[0], np.cumsum([len(x) for x in pats])]).astype(np.int32)
+    b_off = np.concatenate([[0], np.cumsum([len(x) for x in txts])]).astype(np.int32)
+    a_tok = np.fromiter((t for x in pats for t in x), dtype=np.int32, count=int(a_off[-1]))
+    b_tok = np.fromiter((t for x in txts for t in x), dtype=np.int32, count=int(b_off[-1]))
+    if device is None:
+        return ops.edit_distance_long_host(a_tok, a_off, b_tok, b_off, v)
+    import torch
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        return ops.edit_distance_long(torch.from_numpy(a_tok).to(dev), a_off, torch.from_numpy(b_tok).to(dev), b_off, v).cpu().numpy()
+
+
+def _rate(dist, length):
+    """distance / length with the reference's empty-reference convention: inf for a non-empty hypothesis, else 0"""
+    if length == 0:
+        return float("inf") if dist > 0 else 0.0
+    return dist / length
+
+
+def word_error_rate(reference, hypothesis):
+    """WER = Levenshtein distance over words / words of the reference; an empty reference: inf if the hypothesis has a word, else 0.
+    Words are str.split() of the strings as they are: this package's tokenisation, not jiwer's (which the reference uses and whose
+    transforms cannot be pinned here)."""
+    r, h = reference.split(), hypothesis.split()
+    return _rate(int(sequence_edit_distances([r], [h])[0]), len(r))
+
+
+def text_error_rates(refs, hyps, device=None):
+    """Character and word error rates of running text: refs[i] a transcription, hyps[i] the text read, both str.  Both are
+    whitespace-normalised first (" ".join(s.split())); words are str.split() (this package's tokenisation, not jiwer's).  Returns
+      per pair (arrays [N]):  "char_dist", "ref_chars", "word_dist", "ref_words" (int), "cer", "wer" (float; an empty reference
+                              gives inf for a non-empty hypothesis, else 0), and
+                              "bag_errors" = max(|R|, |H|) - |R & H| over the word multisets: the word errors left when the order
+                              is ignored, computed on the host.  bag_errors <= word_dist; the gap is what the reading order costs.
+      pooled:                 "n", "cer_micro", "wer_micro" (summed distances / summed reference lengths, same convention),
+                              "cer_mean", "wer_mean" (means of the per-pair rates; 0 for no pairs), "bag_error_rate" (summed
+                              bag_errors / summed reference words).
+    The 2 N distances are one call of sequence_edit_distances (device None: the host twin)."""
+    refs, hyps = list(refs), list(hyps)
+    if len(refs) != len(hyps):
+        raise ValueError(f"{len(refs)} references but {len(hyps)} hypotheses")
+    for s in refs + hyps:
+        if not isinstance(s, str):
+            raise TypeError(f"texts must be str, got {type(s).__name__}")
+    N = len(refs)
+    rw, hw = [r.split() for r in refs], [h.split() for h in hyps]
+    rc, hc = [" ".join(w) for w in rw], [" ".join(w) for w in hw]
+    dist = sequence_edit_distances(rc + rw, hc + hw, device=device).astype(np.int64)
+    char_dist, word_dist = dist[:N], dist[N:]
+    ref_chars = np.array([len(s) for s in rc], dtype=np.int64)
+    ref_words = np.array([len(w) for w in rw], dtype=np.int64)
+    bag = np.array([max(len(r), len(h)) - sum((Counter(r) & Counter(h)).values()) for r, h in zip(rw, hw)], dtype=np.int64)
+    cer = np.array([_rate(int(d), int(n)) for d, n in zip(char_dist, ref_chars)], dtype=np.float64)
+    wer = np.array([_rate(int(d), int(n)) for d, n in zip(word_dist, ref_words)], dtype=np.float64)
+    return {
+        "char_dist": char_dist, "ref_chars": ref_chars, "word_dist": word_dist, "ref_words": ref_words, "cer": cer, "wer": wer,
+        "bag_errors": bag, "n": N,
+        "cer_micro": _rate(int(char_dist.sum()), int(ref_chars.sum())), "wer_micro": _rate(int(word_dist.sum()), int(ref_words.sum())),
+        "cer_mean": float(cer.mean()) if N else 0.0, "wer_mean": float(wer.mean()) if N else 0.0,
+        "bag_error_rate": _rate(int(bag.sum()), int(ref_words.sum())),
+    }

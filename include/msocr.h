@@ -587,6 +587,45 @@ int msocr_edit_distance_long(const int32_t* a_tok, const int32_t* a_off_host, co
 int msocr_edit_distance_long_host(const int32_t* a_tok_host, const int32_t* a_off_host, const int32_t* b_tok_host,
                                   const int32_t* b_off_host, const int32_t* v_host, int N, int32_t* dist_out);
 
+/* ---- alignment behind the error rates: one optimal edit script of long sequences (an extension beyond the reference's inference
+ * code: recognizers.sequence_alignments / error_breakdown / text_error_rates(breakdown=True), Pipeline.evaluate_text(breakdown=True),
+ * Pipeline.transfer_text; csrc/edit_alignment.hip, csrc/edit_alignment.h) ----
+ * Which pattern token pairs with which text token under the distance of msocr_edit_distance_long, and how many hits,
+ * substitutions, deletions and insertions that makes.  Of the optimal alignments the one this tie rule fixes: from
+ * (i, j) = (m, n), while i > 0 and j > 0, the first of
+ *   1. a[i-1] equals b[j-1]: hit, paired, to (i-1, j-1);      2. D[i-1][j-1] + 1 == D[i][j]: substitution, paired, to (i-1, j-1);
+ *   3. D[i-1][j] + 1 == D[i][j]: deletion, a[i-1] unpaired, to (i-1, j);      4. otherwise insertion, b[j-1] unpaired, to (i, j-1);
+ * then the rest of the pattern is deletions or the rest of the text insertions (D: the Levenshtein table).  Integers; the host
+ * twin applies the same header's rule to the same trace, so the two routes agree bit for bit.  The rule is NOT symmetric: the
+ * caller decides which side is the pattern (recognizers.sequence_alignments: always the reference).
+ * Tokens, offsets, v and the equality rule: as for msocr_edit_distance_long above.
+ * Outputs (device memory; host memory for the twin): dist_out [N] i32; a_map_out [a_off[N] - a_off[0]] i32, for the token at
+ * a_tok[a_off[p] + i] the element a_off[p] - a_off[0] + i = the index of its partner within pair p's text, or -1;
+ * b_map_out [b_off[N] - b_off[0]] i32 likewise, indices within the pair's pattern; counts_out [N][4] i32 = {hits, substitutions,
+ * deletions, insertions}: substitutions + deletions + insertions = dist, hits + substitutions + deletions = m,
+ * hits + substitutions + insertions = n.  Every element is written exactly once; nothing behind the stated extents is written.
+ * A map without elements must still be a non-null pointer.  m == 0: all insertions; n == 0: all deletions; N == 0: MSOCR_OK,
+ * nothing launched.
+ * workspace (device route): device memory, 16-byte aligned, contents irrelevant, of at least msocr_edit_alignment_ws_bytes =
+ *   40 N + sum v[p] * ceil(m_p / 64) * 8, rounded up to a multiple of 16, + sum 16 * ceil(m_p / 64) * n_p bytes: the heads, one
+ *   trace offset per pair, the match-mask tables, and the trace: per pattern block and text column the two 64-bit words of the
+ *   block recurrence that decide every cell of that block and column.  2.9 MB for a page of 3400 characters against itself, 64 MiB
+ *   for a pair at the cap on both sides (a linear-memory traceback is not provided).
+ * Refused with MSOCR_E_ARG before any launch: what msocr_edit_distance_long refuses (a workspace not 16-byte aligned included);
+ *   the ws_bytes query returns MSOCR_E_ARG for the same arrays.  The host twin also returns MSOCR_E_ARG when it cannot allocate a
+ *   table or a trace.
+ * The entry point uploads the heads from a buffer of its own and waits for that copy on `stream`; four launches follow (tables,
+ *   the distance kernel's sweep with the trace stores, and the traceback in a launch of its own: one wave per pair walks back
+ *   through windows of 64 x 64 cells held in registers), which the host does not wait for.  Not capturable: an evaluation call.
+ *   Measured: profiles/edit_alignment.txt. */
+int64_t msocr_edit_alignment_ws_bytes(const int32_t* a_off_host, const int32_t* b_off_host, const int32_t* v_host, int N);
+int msocr_edit_alignment(const int32_t* a_tok, const int32_t* a_off_host, const int32_t* b_tok, const int32_t* b_off_host,
+                         const int32_t* v_host, int N, int32_t* dist_out, int32_t* a_map_out, int32_t* b_map_out, int32_t* counts_out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int msocr_edit_alignment_host(const int32_t* a_tok_host, const int32_t* a_off_host, const int32_t* b_tok_host,
+                              const int32_t* b_off_host, const int32_t* v_host, int N, int32_t* dist_out, int32_t* a_map_out,
+                              int32_t* b_map_out, int32_t* counts_out);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

@@ -131,6 +131,9 @@ _SIGS = {
     "msocr_edit_distance_long_ws_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
     "msocr_edit_distance_long": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "msocr_edit_distance_long_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "msocr_edit_alignment_ws_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
+    "msocr_edit_alignment": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "msocr_edit_alignment_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

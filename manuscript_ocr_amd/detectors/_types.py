@@ -6,7 +6,7 @@ Field names, optionality and the [0, 1] range checks are those of the reference 
 """
 from typing import List, Optional, Tuple
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, ConfigDict, Field
 
 _UNIT = dict(ge=0.0, le=1.0)
 
@@ -101,6 +101,21 @@ class SuggestLmWord(LmWord):
     """A SuggestWord of a decode fused with a character language model (`suggest` and `lm` both set): an LmWord with `suggestions`."""
 
     suggestions: List[Suggestion] = Field(default_factory=list, description="nearest lexicon words, nearest first")
+
+
+class TransferWord(AltWord):
+    """A recognised Word with the transcription word that Pipeline.transfer_text aligned to it (this package's extension): the
+    page's words in reading order against the words of a plain transcription, by the alignment of msocr_edit_alignment.  A word
+    paired as a hit or a substitution carries the three fields; a word the alignment left without a partner (or un-paired by
+    `max_cer`) has None in all three.  The word keeps every field of the class it came as (`chars`, `alternatives`, and, as extra
+    fields, `lexicon_index`, `lm_logp` or `suggestions` where it had them).  As for CharWord, a default model_dump() of a Page does
+    not change."""
+
+    model_config = ConfigDict(extra="allow")
+
+    gt_text: Optional[str] = Field(None, description="the transcription word paired with this word, None if it has none")
+    gt_index: Optional[int] = Field(None, description="index of `gt_text` in the transcription's str.split()", ge=0)
+    char_distance: Optional[int] = Field(None, description="Levenshtein distance (unit costs) between `text` and `gt_text`", ge=0)
 
 
 class Block(BaseModel):

@@ -1152,3 +1152,59 @@ def edit_distance_long_host(a_tok, a_off, b_tok, b_off, v):
     nat.check(nat.lib().msocr_edit_distance_long_host(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2]),
               "edit_distance_long_host")
     return out
+
+
+# ------------------------------------------------------------------------------------------- alignment behind the error rates
+def edit_alignment_workspace_bytes(a_off, b_off, v):
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    n = nat.lib().msocr_edit_alignment_ws_bytes(a_off.ctypes.data, b_off.ctypes.data, v.ctypes.data, N)
+    nat.check(min(n, 0), "edit_alignment_ws_bytes")
+    return int(n)
+
+
+def edit_alignment(a_tok, a_off, b_tok, b_off, v, workspace=None, out=None):
+    """One optimal alignment of N pairs of token sequences of up to EDL_MAX_LEN tokens each (msocr_edit_alignment; include/msocr.h,
+    "alignment behind the error rates": the tie rule is stated there).  Arguments as for `edit_distance_long`; the pattern side a is
+    the side whose unpaired tokens count as deletions.  -> (dist [N], a_map [a_off[N] - a_off[0]], b_map [b_off[N] - b_off[0]],
+    counts [N, 4] = hits, substitutions, deletions, insertions), int32 on the device; a map holds, for each token, the index of its
+    partner within its pair's other side, or -1.  out: the four tensors to write into.  workspace: uint8, 16-byte aligned, at least
+    `edit_alignment_workspace_bytes` (16 bytes per pattern block and text column for the trace: 64 MiB for a pair at the cap)."""
+    _need_cuda(a_tok, b_tok)
+    if a_tok.dtype != torch.int32 or b_tok.dtype != torch.int32 or a_tok.dim() != 1 or b_tok.dim() != 1:
+        raise TypeError("tokens are one-dimensional int32 tensors")
+    if not (a_tok.is_contiguous() and b_tok.is_contiguous()):
+        raise ValueError("edit_alignment takes dense tensors")
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    if N and (int(a_off[-1]) > a_tok.numel() or int(b_off[-1]) > b_tok.numel()):
+        raise ValueError("offsets reach past the token tensors")
+    dev = a_tok.device
+    need = edit_alignment_workspace_bytes(a_off, b_off, v)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    if out is None:
+        na, nb = (int(a_off[-1]) - int(a_off[0]), int(b_off[-1]) - int(b_off[0])) if N else (0, 0)
+        out = (torch.empty((N,), dtype=torch.int32, device=dev), torch.empty((na,), dtype=torch.int32, device=dev),
+               torch.empty((nb,), dtype=torch.int32, device=dev), torch.empty((N, 4), dtype=torch.int32, device=dev))
+    dist, a_map, b_map, counts = out
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    ptr = [t.data_ptr() or workspace.data_ptr() for t in (a_tok, b_tok, dist, a_map, b_map, counts)]
+    nat.check(nat.lib().msocr_edit_alignment(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2], ptr[3],
+                                             ptr[4], ptr[5], workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                             _stream()), "edit_alignment")
+    return dist, a_map, b_map, counts
+
+
+def edit_alignment_host(a_tok, a_off, b_tok, b_off, v):
+    """The CPU twin of `edit_alignment` (msocr_edit_alignment_host) on numpy arrays -> (dist, a_map, b_map, counts) int32, bit for bit."""
+    a_tok = np.ascontiguousarray(a_tok, dtype=np.int32).reshape(-1)
+    b_tok = np.ascontiguousarray(b_tok, dtype=np.int32).reshape(-1)
+    a_off, b_off, v, N = _edl_heads(a_off, b_off, v)
+    if N and (int(a_off[-1]) > a_tok.size or int(b_off[-1]) > b_tok.size):
+        raise ValueError("offsets reach past the token arrays")
+    na, nb = (int(a_off[-1]) - int(a_off[0]), int(b_off[-1]) - int(b_off[0])) if N else (0, 0)
+    out = (np.empty(N, dtype=np.int32), np.empty(na, dtype=np.int32), np.empty(nb, dtype=np.int32), np.empty((N, 4), dtype=np.int32))
+    pad = np.zeros(4, dtype=np.int32)  # an address for arrays without elements
+    ptr = [x.ctypes.data if x.size else pad.ctypes.data for x in (a_tok, b_tok) + out]
+    nat.check(nat.lib().msocr_edit_alignment_host(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2], ptr[3],
+                                                  ptr[4], ptr[5]), "edit_alignment_host")
+    return out

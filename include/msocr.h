@@ -626,6 +626,58 @@ int msocr_edit_alignment_host(const int32_t* a_tok_host, const int32_t* a_off_ho
                               const int32_t* b_off_host, const int32_t* v_host, int N, int32_t* dist_out, int32_t* a_map_out,
                               int32_t* b_map_out, int32_t* counts_out);
 
+/* ---- approximate text search: where do Q short patterns occur in T texts, with up to k errors each (an extension beyond the
+ * reference's inference code: recognizers.TextCorpus / search_texts, PageCorpus, Pipeline.search; csrc/text_search.hip,
+ * csrc/text_search.h) ----
+ * Sellers' semi-global form of the Levenshtein table, unit costs, integers.
+ * Tokens: int32.  A call has one alphabet size v, 1 <= v <= MSOCR_SEARCH_MAX_ALPHABET.  Tokens in [0, v) compare by equality; any
+ *   other token, on either side, equals nothing and is never used as an index (the rule of msocr_edit_distance_long).
+ * Inputs: patterns q = 0 .. Q-1 as CSR (pat_tok, pat_off [Q + 1]), each of length 1 <= m_q <= MSOCR_SEARCH_MAX_PATTERN (64) with an
+ *   error bound k_q = max_dist[q], 0 <= k_q < m_q (with k >= m the empty substring would match everywhere); texts t = 0 .. T-1 as
+ *   CSR (txt_tok, txt_off [T + 1]), each of any length n_t >= 0, at most 2^31 - 1 tokens in all.  The token arrays are device memory
+ *   for the device entry point and host memory for the twin; pat_off, max_dist and txt_off are HOST memory on both routes.
+ * Scores: for a pattern a[0..m) and a text b[0..n), s_0 = m and s_j = min over 0 <= l <= j of ed(a, b[j-l .. j)) for 1 <= j <= n:
+ *   the bottom row of Sellers' table, which has D[0][j] = 0 and D[i][0] = i.
+ * Hits: every (q, t, j) with s_j <= k_q is a hit; all end positions are reported, not local minima.  Its record:
+ *   end = j, exclusive, counted inside its text; distance = s_j; start = j - l*, l* the SMALLEST l with ed(a, b[j-l .. j)) == s_j,
+ *   the shortest substring that attains the score (m - s_j <= l* <= min(j, m + s_j)).  It is computed by the global recurrence of
+ *   the reversed pattern over b[j-1], b[j-2], ..: the first l at which that distance equals s_j.
+ * Order and capacity: the canonical order is ascending (pattern, text, end); the key is unique.  The host twin writes the first
+ *   `capacity` hits in canonical order; the device route writes hits in no particular order.  On both routes count_out (int64) is
+ *   the EXACT number of hits, also when it exceeds `capacity`: then exactly `capacity` records are written, each a true, distinct
+ *   hit, and nothing is written behind hits_out[capacity].
+ * Selection (a host function on read-back hits, for both routes, which therefore agree bit for bit after it): sorts the n records
+ *   into canonical order; per (pattern, text) it walks the hits by (distance, end) ascending and keeps one iff [start, end)
+ *   intersects no kept hit of the same (pattern, text); the kept hits are compacted to the front in canonical order and their
+ *   number is returned.  MSOCR_E_ARG for n < 0 or a null pointer with n > 0.
+ * workspace (device route): device memory, 8-byte aligned, contents irrelevant, of at least the ws_bytes query's
+ *   16 Q v + 8 (T + 1) + 4 (T + 1) + 4 (Q + 1) + 4 Q bytes, rounded up to a multiple of 8: the match-mask tables [Q][2][v] of 64-bit
+ *   words (the patterns' masks and the reversed patterns'), which a small kernel builds, and the uploaded heads: per text the
+ *   number of segments before it and its offset, per pattern its offset and bound.  A text is cut into segments of
+ *   MSOCR_SEARCH_SEGMENT tokens; one lane scans one (pattern, segment), from m + k tokens before it.
+ * Refused with MSOCR_E_ARG before any launch: a null pointer (an array without elements is never read, its pointer must still be
+ *   non-null; Q == 0 / T == 0 do not read the pattern / text offsets), Q < 0 or T < 0, offsets that do not start at a value >= 0 or
+ *   decrease, m_q outside 1..64, k_q outside [0, m_q), v outside 1..2048, capacity < 0, a workspace that is misaligned or smaller
+ *   than required; the ws_bytes query returns MSOCR_E_ARG for the same arrays.  Q == 0 or T == 0: MSOCR_OK with count 0 (ws_bytes: 0;
+ *   the device route needs no workspace then and launches the one kernel that clears the count).
+ * The device entry point uploads the heads from a buffer of its own and waits for that copy on `stream`; four launches follow
+ *   (clear, masks, scan, starts), which the host does not wait for.  Not capturable.  Measured: profiles/text_search.txt. */
+#define MSOCR_SEARCH_MAX_ALPHABET 2048
+#define MSOCR_SEARCH_MAX_PATTERN 64
+#define MSOCR_SEARCH_SEGMENT 64
+typedef struct msocr_search_hit {
+  int32_t pattern, text, start, end, distance;
+} msocr_search_hit;
+int64_t msocr_text_search_ws_bytes(const int32_t* pat_off_host, const int32_t* max_dist_host, int Q, const int32_t* txt_off_host, int T,
+                                   int v);
+int msocr_text_search(const int32_t* pat_tok, const int32_t* pat_off_host, const int32_t* max_dist_host, int Q, const int32_t* txt_tok,
+                      const int32_t* txt_off_host, int T, int v, msocr_search_hit* hits_out, int64_t capacity, int64_t* count_out,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int msocr_text_search_host(const int32_t* pat_tok_host, const int32_t* pat_off_host, const int32_t* max_dist_host, int Q,
+                           const int32_t* txt_tok_host, const int32_t* txt_off_host, int T, int v, msocr_search_hit* hits_out,
+                           int64_t capacity, int64_t* count_out);
+int64_t msocr_text_search_select_host(msocr_search_hit* hits, int64_t n);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

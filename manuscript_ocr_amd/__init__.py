@@ -7,6 +7,7 @@ behind the reference's plugin API: `from manuscript_ocr_amd import Pipeline` rep
 # environment variable; the package does not set it: hardware queues are a resource of the machine, shared by every process on the
 # card, so the machine's environment decides.
 from ._pipeline import Pipeline
+from ._search import PageCorpus
 from .detectors import read_image, visualize_page
 
-__all__ = ["Pipeline", "visualize_page", "read_image"]
+__all__ = ["Pipeline", "PageCorpus", "visualize_page", "read_image"]

@@ -134,6 +134,10 @@ _SIGS = {
     "msocr_edit_alignment_ws_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
     "msocr_edit_alignment": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "msocr_edit_alignment_host": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_text_search_ws_bytes": (c_i64, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32]),
+    "msocr_text_search": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "msocr_text_search_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "msocr_text_search_select_host": (c_i64, [c_vp, c_i64]),
     "msocr_crop_resize_pad": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_east_box_tail_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "msocr_east_box_tail": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_i32, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -1105,6 +1105,25 @@ class Pipeline:
         taken = {e["gt_index"] for e in extra.values()}
         return page, [g for g in range(len(gt_words)) if g not in taken]
 
+    def search(self, pages_or_images, queries, max_distance=None, max_error_rate=None, overlapping: bool = False, device=None):
+        """Where do the queries occur in these pages, allowing for what the recogniser may have misread (this package's extension;
+        DESIGN.md section 4.24)?  -> a list of detectors._types.SearchHit in canonical order (query, page, end).
+
+        pages_or_images: Pages are taken as they are, so searching needs neither the networks nor a GPU; anything else goes
+        through `predict` first.  A page's text is the texts of its words that have one, flattened in the order `evaluate_text`
+        flattens them and joined by one space; a query is whitespace-normalised the same way and may span words and blocks.  Exactly
+        one of max_distance (edits allowed: an int, or one per query) and max_error_rate (k = min(floor(rate * len(query)),
+        len(query) - 1)) is given; a query has 1 to 64 characters.  A hit carries the words it touches as (block index, word index).
+        overlapping=True reports every end position within the bound instead of the occurrences.  device: None = the host twin; a
+        device: msocr_text_search there, the same hits bit for bit.  No automatic switch between the two (Pages must be searchable
+        without a GPU): 16 pages x 10 queries take 2.4 ms on one host core and 0.16 ms on the device with the corpus upload and the
+        read-back (profiles/text_search.txt), and for many searches of one collection a PageCorpus keeps it on the device."""
+        from ._search import PageCorpus
+        from .detectors._types import Page
+        pages = [p if isinstance(p, Page) else self.predict(p) for p in pages_or_images]
+        return PageCorpus(pages, device=device).search(queries, max_distance=max_distance, max_error_rate=max_error_rate,
+                                                       overlapping=overlapping)
+
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):
         results = []

@@ -118,6 +118,21 @@ class TransferWord(AltWord):
     char_distance: Optional[int] = Field(None, description="Levenshtein distance (unit costs) between `text` and `gt_text`", ge=0)
 
 
+class SearchHit(BaseModel):
+    """One occurrence of a query in the running text of a page (this package's extension: PageCorpus.search, Pipeline.search).  A
+    page's text is the texts of its words that have one, in reading order, joined by one space; `start` and `end` count its
+    characters, and `words` are the words whose characters the match touches (a separator alone counts for no word)."""
+
+    page: int = Field(..., description="index of the page in the corpus", ge=0)
+    query: int = Field(..., description="index of the query in the call", ge=0)
+    query_text: str = Field(..., description="the query as it was searched, whitespace-normalised")
+    matched_text: str = Field(..., description="the page's text from `start` to `end`")
+    distance: int = Field(..., description="Levenshtein distance (unit costs) between `query_text` and `matched_text`", ge=0)
+    start: int = Field(..., description="first character of the match in the page's text", ge=0)
+    end: int = Field(..., description="one past its last character", ge=0)
+    words: List[Tuple[int, int]] = Field(default_factory=list, description="(block index, word index) of the words the match touches, in order")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

@@ -1208,3 +1208,111 @@ def edit_alignment_host(a_tok, a_off, b_tok, b_off, v):
     nat.check(nat.lib().msocr_edit_alignment_host(ptr[0], a_off.ctypes.data, ptr[1], b_off.ctypes.data, v.ctypes.data, N, ptr[2], ptr[3],
                                                   ptr[4], ptr[5]), "edit_alignment_host")
     return out
+
+
+# ------------------------------------------------------------------------------------------- approximate text search
+SEARCH_MAX_ALPHABET = 2048  # msocr.h MSOCR_SEARCH_MAX_ALPHABET
+SEARCH_MAX_PATTERN = 64     # msocr.h MSOCR_SEARCH_MAX_PATTERN: tokens of a pattern
+SEARCH_SEGMENT = 64         # msocr.h MSOCR_SEARCH_SEGMENT: tokens of a text that one lane of the scan kernel reports
+SEARCH_CAPACITY = 65536     # records of the first pass of `text_search`
+
+
+def _ts_heads(pat_off, max_dist, txt_off):
+    pat_off = np.ascontiguousarray(pat_off, dtype=np.int32).reshape(-1)
+    max_dist = np.ascontiguousarray(max_dist, dtype=np.int32).reshape(-1)
+    txt_off = np.ascontiguousarray(txt_off, dtype=np.int32).reshape(-1)
+    Q, T = len(max_dist), len(txt_off) - 1
+    if len(pat_off) != Q + 1 or T < 0:
+        raise ValueError("offsets are [Q + 1] for max_dist [Q], and [T + 1]")
+    return pat_off, max_dist, txt_off, Q, T
+
+
+def text_search_workspace_bytes(pat_off, max_dist, txt_off, v):
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    n = nat.lib().msocr_text_search_ws_bytes(pat_off.ctypes.data, max_dist.ctypes.data, Q, txt_off.ctypes.data, T, int(v))
+    nat.check(min(n, 0), "text_search_ws_bytes")
+    return int(n)
+
+
+def text_search_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, hits, count, workspace=None):
+    """One call of msocr_text_search (include/msocr.h, "approximate text search"): every end position at which pattern q
+    = pat_tok[pat_off[q]:pat_off[q + 1]] matches a substring of text t = txt_tok[txt_off[t]:txt_off[t + 1]] with at most max_dist[q]
+    errors.  pat_tok, txt_tok: int32 device tensors; pat_off [Q + 1], max_dist [Q], txt_off [T + 1]: host arrays (numpy); tokens in
+    [0, v) compare by equality and every other token equals nothing.  hits: int32 device tensor [capacity, 5], rows (pattern, text,
+    start, end, distance), written in no particular order up to its capacity; count: int64 device tensor [1], the exact number of
+    hits.  Nothing is read back and nothing is waited for but the upload of the offsets."""
+    _need_cuda(pat_tok, txt_tok, hits, count)
+    if pat_tok.dtype != torch.int32 or txt_tok.dtype != torch.int32 or pat_tok.dim() != 1 or txt_tok.dim() != 1:
+        raise TypeError("tokens are one-dimensional int32 tensors")
+    if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 5 or count.dtype != torch.int64 or count.numel() != 1:
+        raise TypeError("hits is int32 [capacity, 5], count is int64 [1]")
+    if not (pat_tok.is_contiguous() and txt_tok.is_contiguous() and hits.is_contiguous()):
+        raise ValueError("text_search takes dense tensors")
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    if (Q and int(pat_off[-1]) > pat_tok.numel()) or (T and int(txt_off[-1]) > txt_tok.numel()):
+        raise ValueError("offsets reach past the token tensors")
+    need = text_search_workspace_bytes(pat_off, max_dist, txt_off, v)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=txt_tok.device)
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    ptr = [t.data_ptr() or workspace.data_ptr() for t in (pat_tok, txt_tok, hits)]
+    nat.check(nat.lib().msocr_text_search(ptr[0], pat_off.ctypes.data, max_dist.ctypes.data, Q, ptr[1], txt_off.ctypes.data, T, int(v),
+                                          ptr[2], hits.shape[0], count.data_ptr(), workspace.data_ptr(),
+                                          workspace.numel() * workspace.element_size(), _stream()), "text_search")
+
+
+def text_search(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, capacity=SEARCH_CAPACITY):
+    """All hits of `text_search_into`, read back: int32 numpy [count, 5], rows (pattern, text, start, end, distance) in no particular
+    order (`text_search_select` or a sort makes them canonical).  The overflow protocol lives here: the first pass has room for
+    `capacity` records; if there are more hits than that, the search runs once more with room for all of them, so the result is
+    complete whatever the capacity."""
+    capacity = int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity >= 0")
+    dev = txt_tok.device
+    with torch.cuda.device(dev):
+        count = torch.zeros((1,), dtype=torch.int64, device=dev)
+        hits = torch.empty((capacity, 5), dtype=torch.int32, device=dev)
+        text_search_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, hits, count)
+        n = int(count.item())
+        if n > capacity:
+            hits = torch.empty((n, 5), dtype=torch.int32, device=dev)
+            text_search_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, hits, count)
+            if int(count.item()) != n:
+                raise nat.NativeError("text_search: the second pass counted other hits than the first")
+        return hits[:n].cpu().numpy()
+
+
+def text_search_host(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, capacity=None):
+    """The CPU twin of `text_search` (msocr_text_search_host) on numpy arrays -> (hits int32 [min(count, capacity), 5] in canonical
+    order (pattern, text, end ascending), count).  capacity None: room for every hit (a first call counts them)."""
+    pat_tok = np.ascontiguousarray(pat_tok, dtype=np.int32).reshape(-1)
+    txt_tok = np.ascontiguousarray(txt_tok, dtype=np.int32).reshape(-1)
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    if (Q and int(pat_off[-1]) > pat_tok.size) or (T and int(txt_off[-1]) > txt_tok.size):
+        raise ValueError("offsets reach past the token arrays")
+    pad = np.zeros(8, dtype=np.int32)  # an address for arrays without elements
+    count = np.zeros(1, dtype=np.int64)
+
+    def run(cap):
+        hits = np.empty((cap, 5), dtype=np.int32)
+        ptr = [x.ctypes.data if x.size else pad.ctypes.data for x in (pat_tok, txt_tok, hits)]
+        nat.check(nat.lib().msocr_text_search_host(ptr[0], pat_off.ctypes.data, max_dist.ctypes.data, Q, ptr[1], txt_off.ctypes.data, T,
+                                                   int(v), ptr[2], cap, count.ctypes.data), "text_search_host")
+        return hits[:min(cap, int(count[0]))]
+
+    if capacity is None:
+        run(0)
+        capacity = int(count[0])
+    elif capacity < 0:
+        raise ValueError("capacity >= 0")
+    return run(int(capacity)), int(count[0])
+
+
+def text_search_select(hits):
+    """msocr_text_search_select_host on hits int32 [n, 5] (numpy): sorted into canonical order, then per (pattern, text) the hits are
+    walked by (distance, end) ascending and one is kept iff [start, end) intersects none kept before -> the kept rows, canonical."""
+    hits = np.array(hits, dtype=np.int32).reshape(-1, 5)  # a copy: the C function works in place
+    n = nat.lib().msocr_text_search_select_host(hits.ctypes.data if len(hits) else None, len(hits))
+    nat.check(min(n, 0), "text_search_select_host")
+    return hits[:int(n)]

@@ -678,6 +678,50 @@ int msocr_text_search_host(const int32_t* pat_tok_host, const int32_t* pat_off_h
                            int64_t capacity, int64_t* count_out);
 int64_t msocr_text_search_select_host(msocr_search_hit* hits, int64_t n);
 
+/* ---- word spotting: query-by-example search over encoder features, Q query words against N indexed words by a dynamic-time-warping
+ * distance between their frame sequences (an extension beyond the reference's inference code: TRBA.embed, WordIndex,
+ * Pipeline.index_words / spot; csrc/word_spotting.hip, csrc/word_spotting.h) ----
+ * Sequences: a sequence is x[0..L) of frames in R^H, stored as row n of a dense [N][T][H] f32 array with its length len[n],
+ *   1 <= len <= T.  Frames t >= len are never read by any function here.
+ * Unit frames (msocr_frame_normalize): u_t = x_t / ||x_t||, the squared norm accumulated in f32 in this order: 64 partial sums,
+ *   partial l takes the elements l, l + 64, l + 128, .. ascending, each by one fmaf; the partials are folded by a butterfly over the
+ *   masks 32, 16, 8, 4, 2, 1 (p[l] += p[l ^ mask]); the root and the quotient x / root are correctly rounded f32 operations.  If the
+ *   squared norm is not finite (an Inf or NaN element, or an overflow) or below FLT_MIN, u_t = 0: such a frame costs 1 against
+ *   everything, and no NaN leaves this step.  Frames t >= len are WRITTEN as zeros (and not read); a length outside [0, T] is
+ *   clamped into it.  unit_out may be feat itself.  | ||u|| - 1 | <= (H + 4) 2^-24.
+ * Local cost: c(i, j) = 1 - <u_i, v_j>.
+ * Distance (msocr_dtw_distances): symmetric steps, unit weights: D(0,0) = c(0,0); D(i,j) = c(i,j) + min(D(i-1,j-1), D(i-1,j),
+ *   D(i,j-1)), absent neighbours +inf; d = D(Lq-1, Ln-1) / (Lq + Ln).  dist [Q][N] f32.
+ * Length gate: query q carries integer bounds len_lo[q] <= len_hi[q]; a pair whose word length lies outside them gets d = +inf and
+ *   costs no arithmetic.  On the device route a query or word length outside [1, T] gates its pairs out the same way (the lengths
+ *   are device memory there and cannot be refused); the host twin refuses them, and len_lo > len_hi.
+ * Arithmetic: the device forms <u_i, v_j> with the exact f32 matrix instruction (one f32 rounding per product and per addition, K
+ *   order documented in the kernel), the table and the division in f32: | d - d_f64 | <= (H + 2 (Lq + Ln) + 16) 2^-24 for the
+ *   same unit frames (DESIGN.md section 4.25 has the derivation).
+ *   The host twin forms every product, sum and table entry in f64 and rounds to f32 once.
+ * Selection (msocr_topk_smallest): per row of dist the k smallest FINITE values in ascending order, equal values (as floats:
+ *   -0.0 == +0.0) by ascending index; +inf, -inf and NaN are never returned; unused slots hold index -1 and value +inf.  A value is
+ *   copied as stored.  The host twin returns the same bits as the device.
+ * Envelope: 1 <= T <= MSOCR_SPOT_MAX_T (64); H a multiple of 64 in 64 .. MSOCR_SPOT_MAX_H (512); Q, N >= 0; Q T H and N T H below
+ *   2^31; 1 <= k <= MSOCR_SPOT_MAX_K (256); q_unit and c_unit 16-byte aligned on the device route.  Anything else, and a null
+ *   pointer, is MSOCR_E_ARG before any launch.  Q == 0 or N == 0 launches nothing that reads features (the selection still fills its
+ *   Q rows with -1 / +inf).
+ * The device entry points take device pointers, allocate nothing, wait for nothing and launch one kernel each on `stream`; they
+ *   are not meant for graph capture.  A workgroup of msocr_dtw_distances owns MSOCR_SPOT_TILE words.  Measured:
+ *   profiles/word_spotting.txt. */
+#define MSOCR_SPOT_MAX_T 64
+#define MSOCR_SPOT_MAX_H 512
+#define MSOCR_SPOT_MAX_K 256
+#define MSOCR_SPOT_TILE 4
+int msocr_frame_normalize(const float* feat, const int32_t* len, int N, int T, int H, float* unit_out, void* stream);
+int msocr_frame_normalize_host(const float* feat, const int32_t* len, int N, int T, int H, float* unit_out);
+int msocr_dtw_distances(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                        const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, void* stream);
+int msocr_dtw_distances_host(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                             const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist);
+int msocr_topk_smallest(const float* dist, int Q, int N, int k, int32_t* idx, float* val, void* stream);
+int msocr_topk_smallest_host(const float* dist, int Q, int N, int k, int32_t* idx, float* val);
+
 /* Word crops -> recogniser canvases on the device: clamped AABB crop (Pipeline._extract_word_image,
  * _pipeline.py:204-221) + ResizeAndPadA (recognizers/_trba/data/transforms.py:85-120: aspect-preserving resize,
  * INTER_AREA if any axis shrinks else INTER_LINEAR, pasted at x=0 / vertically centred on a 255 canvas).

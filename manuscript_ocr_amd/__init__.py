@@ -8,6 +8,7 @@ behind the reference's plugin API: `from manuscript_ocr_amd import Pipeline` rep
 # card, so the machine's environment decides.
 from ._pipeline import Pipeline
 from ._search import PageCorpus
+from ._spotting import WordIndex
 from .detectors import read_image, visualize_page
 
-__all__ = ["Pipeline", "PageCorpus", "visualize_page", "read_image"]
+__all__ = ["Pipeline", "PageCorpus", "WordIndex", "visualize_page", "read_image"]

@@ -1124,6 +1124,35 @@ class Pipeline:
         return PageCorpus(pages, device=device).search(queries, max_distance=max_distance, max_error_rate=max_error_rate,
                                                        overlapping=overlapping)
 
+    def index_words(self, images, pages=None):
+        """A WordIndex of the words of these pages, for word spotting by example (this package's extension; DESIGN.md section 4.25;
+        needs this package's TRBA).  pages: the Pages of `images`, one each; None runs `predict` on every image first.  The words
+        are cut as `score_page` cuts them, with this pipeline's min_text_size and rectify_crops; the index lives on the
+        recogniser's device."""
+        from ._spotting import WordIndex
+        if not isinstance(self.recognizer, TRBA):
+            raise TypeError("index_words needs this package's TRBA as the recogniser")
+        images = list(images)
+        pages = [self.predict(im) for im in images] if pages is None else list(pages)
+        index = WordIndex(self.recognizer)
+        index.min_text_size, index.rectify_crops = self.min_text_size, bool(self.rectify_crops)
+        index.add_pages(images, pages)
+        return index
+
+    def spot(self, index, queries, k: int = 10, max_length_ratio: Optional[float] = 2.0):
+        """WordIndex.spot with one more kind of query: (image, polygon), a region of a page, which is cut as this pipeline cuts a
+        word (min_text_size, rectify_crops) and embedded.  Word images and (page, block, word) references pass through.  -> one list
+        of detectors._types.SpotHit per query."""
+        from ._spotting import WordIndex
+        resolved = []
+        for q in queries:
+            if isinstance(q, tuple) and len(q) == 2:
+                cutter = WordIndex(self.recognizer)
+                cutter.min_text_size, cutter.rectify_crops = self.min_text_size, bool(self.rectify_crops)
+                q = cutter.frames_of_polygon(q[0], q[1])
+            resolved.append(q)
+        return index.spot(resolved, k=k, max_length_ratio=max_length_ratio)
+
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):
         results = []

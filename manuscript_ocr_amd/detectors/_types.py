@@ -133,6 +133,19 @@ class SearchHit(BaseModel):
     words: List[Tuple[int, int]] = Field(default_factory=list, description="(block index, word index) of the words the match touches, in order")
 
 
+class SpotHit(BaseModel):
+    """One neighbour of a query word in a WordIndex (this package's extension: WordIndex.spot, Pipeline.spot).  The hits of one query
+    come in ascending `distance`, equal distances by the order the words entered the index; `rank` counts them from 0."""
+
+    query: int = Field(..., description="index of the query in the call", ge=0)
+    page: int = Field(..., description="index of the page the word was added with", ge=0)
+    block: int = Field(..., description="index of the word's block on its page", ge=0)
+    word: int = Field(..., description="index of the word in its block", ge=0)
+    distance: float = Field(..., description="DTW distance between the unit frames of query and word, divided by the sum of their lengths")
+    rank: int = Field(..., description="0 for the nearest word of this query", ge=0)
+    text: Optional[str] = Field(None, description="the indexed word's text, if it has one")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

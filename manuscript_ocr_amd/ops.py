@@ -1316,3 +1316,144 @@ def text_search_select(hits):
     n = nat.lib().msocr_text_search_select_host(hits.ctypes.data if len(hits) else None, len(hits))
     nat.check(min(n, 0), "text_search_select_host")
     return hits[:int(n)]
+
+
+# ------------------------------------------------------------------------------------------- word spotting
+SPOT_MAX_T = 64    # msocr.h MSOCR_SPOT_MAX_T: frames of a sequence
+SPOT_MAX_H = 512   # msocr.h MSOCR_SPOT_MAX_H: elements of a frame, a multiple of 64
+SPOT_MAX_K = 256   # msocr.h MSOCR_SPOT_MAX_K: neighbours of one selection
+SPOT_TILE = 4      # msocr.h MSOCR_SPOT_TILE: corpus words of one workgroup of the distance kernel
+
+
+def _ws_feat_dev(x, what):
+    _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise TypeError(f"{what} is a dense float32 device tensor [N, T, H]")
+    return x
+
+
+def _ws_i32_dev(x, n, like, what):
+    _need_cuda(x)
+    if x.dtype != torch.int32 or x.dim() != 1 or x.numel() != n or not x.is_contiguous() or x.device != like.device:
+        raise TypeError(f"{what} is a dense int32 tensor [{n}] on the features' device")
+    return x
+
+
+def _ws_ptr(t, pad):
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    return t.data_ptr() or pad.data_ptr()
+
+
+def frame_normalize(feat, lengths, out=None):
+    """msocr_frame_normalize (include/msocr.h, "word spotting"): feat f32 [N, T, H] and lengths int32 [N] on the device -> unit frames
+    f32 [N, T, H]; frames at or beyond a word's length are zeros, a frame without a finite norm of at least sqrt(FLT_MIN) too."""
+    _ws_feat_dev(feat, "feat")
+    N, T, H = feat.shape
+    _ws_i32_dev(lengths, N, feat, "lengths")
+    if out is None:
+        out = torch.empty_like(feat)
+    elif out.shape != feat.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feat.device:
+        raise TypeError("out is a dense float32 tensor of feat's shape and device")
+    with torch.cuda.device(feat.device):
+        pad = torch.empty(4, dtype=torch.float32, device=feat.device)
+        nat.check(nat.lib().msocr_frame_normalize(_ws_ptr(feat, pad), _ws_ptr(lengths, pad), N, T, H, _ws_ptr(out, pad), _stream()),
+                  "frame_normalize")
+    return out
+
+
+def dtw_distances(q_unit, q_len, len_lo, len_hi, c_unit, c_len, out=None):
+    """msocr_dtw_distances: the normalised DTW distance of every query (q_unit f32 [Q, T, H], q_len, len_lo, len_hi int32 [Q]) to every
+    indexed word (c_unit f32 [N, T, H], c_len int32 [N]), all on one device -> f32 [Q, N]; +inf where the word's length lies outside
+    [len_lo[q], len_hi[q]].  Nothing is read back or waited for."""
+    _ws_feat_dev(q_unit, "q_unit")
+    _ws_feat_dev(c_unit, "c_unit")
+    Q, T, H = q_unit.shape
+    N = c_unit.shape[0]
+    if tuple(c_unit.shape[1:]) != (T, H) or c_unit.device != q_unit.device:
+        raise ValueError("queries and corpus share T, H and the device")
+    for x, n, what in ((q_len, Q, "q_len"), (len_lo, Q, "len_lo"), (len_hi, Q, "len_hi"), (c_len, N, "c_len")):
+        _ws_i32_dev(x, n, q_unit, what)
+    if out is None:
+        out = torch.empty((Q, N), dtype=torch.float32, device=q_unit.device)
+    elif tuple(out.shape) != (Q, N) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q_unit.device:
+        raise TypeError("out is a dense float32 tensor [Q, N] on the features' device")
+    with torch.cuda.device(q_unit.device):
+        pad = torch.empty(4, dtype=torch.float32, device=q_unit.device)
+        p = [_ws_ptr(t, pad) for t in (q_unit, q_len, len_lo, len_hi, c_unit, c_len, out)]
+        nat.check(nat.lib().msocr_dtw_distances(p[0], p[1], p[2], p[3], Q, p[4], p[5], N, T, H, p[6], _stream()), "dtw_distances")
+    return out
+
+
+def topk_smallest(dist, k):
+    """msocr_topk_smallest: per row of dist (f32 [Q, N] on the device) the k smallest finite values ascending, ties by ascending index
+    -> (idx int32 [Q, k], val f32 [Q, k]) on the device; unused slots hold -1 / +inf."""
+    _need_cuda(dist)
+    if dist.dtype != torch.float32 or dist.dim() != 2 or not dist.is_contiguous():
+        raise TypeError("dist is a dense float32 device tensor [Q, N]")
+    Q, N = dist.shape
+    idx = torch.empty((Q, int(k)), dtype=torch.int32, device=dist.device)
+    val = torch.empty((Q, int(k)), dtype=torch.float32, device=dist.device)
+    with torch.cuda.device(dist.device):
+        pad = torch.empty(4, dtype=torch.float32, device=dist.device)
+        nat.check(nat.lib().msocr_topk_smallest(_ws_ptr(dist, pad), Q, N, int(k), _ws_ptr(idx, pad), _ws_ptr(val, pad), _stream()),
+                  "topk_smallest")
+    return idx, val
+
+
+def _ws_feat_host(x, what):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 3:
+        raise TypeError(f"{what} is float32 [N, T, H]")
+    return x
+
+
+def _ws_i32_host(x, n, what):
+    x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
+    if x.size != n:
+        raise TypeError(f"{what} is int32 [{n}]")
+    return x
+
+
+_WS_PAD = np.zeros(8, dtype=np.float32)  # an address for arrays without elements
+
+
+def _ws_hptr(x):
+    return x.ctypes.data if x.size else _WS_PAD.ctypes.data
+
+
+def frame_normalize_host(feat, lengths):
+    """The CPU twin of `frame_normalize` (msocr_frame_normalize_host) on numpy arrays, with the same order of the f32 sum."""
+    feat = _ws_feat_host(feat, "feat")
+    N, T, H = feat.shape
+    lengths = _ws_i32_host(lengths, N, "lengths")
+    out = np.empty_like(feat)
+    nat.check(nat.lib().msocr_frame_normalize_host(_ws_hptr(feat), _ws_hptr(lengths), N, T, H, _ws_hptr(out)), "frame_normalize_host")
+    return out
+
+
+def dtw_distances_host(q_unit, q_len, len_lo, len_hi, c_unit, c_len):
+    """The CPU twin of `dtw_distances` (msocr_dtw_distances_host): every product, sum and table entry in f64, one rounding to f32.
+    It refuses lengths outside [1, T] and len_lo > len_hi."""
+    q_unit, c_unit = _ws_feat_host(q_unit, "q_unit"), _ws_feat_host(c_unit, "c_unit")
+    Q, T, H = q_unit.shape
+    N = c_unit.shape[0]
+    if tuple(c_unit.shape[1:]) != (T, H):
+        raise ValueError("queries and corpus share T and H")
+    q_len, len_lo, len_hi = (_ws_i32_host(x, Q, w) for x, w in ((q_len, "q_len"), (len_lo, "len_lo"), (len_hi, "len_hi")))
+    c_len = _ws_i32_host(c_len, N, "c_len")
+    out = np.empty((Q, N), dtype=np.float32)
+    p = [_ws_hptr(x) for x in (q_unit, q_len, len_lo, len_hi, c_unit, c_len, out)]
+    nat.check(nat.lib().msocr_dtw_distances_host(p[0], p[1], p[2], p[3], Q, p[4], p[5], N, T, H, p[6]), "dtw_distances_host")
+    return out
+
+
+def topk_smallest_host(dist, k):
+    """The CPU twin of `topk_smallest` (msocr_topk_smallest_host): the same bits as the device on the same array."""
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    if dist.ndim != 2:
+        raise TypeError("dist is float32 [Q, N]")
+    Q, N = dist.shape
+    idx = np.empty((Q, int(k)), dtype=np.int32)
+    val = np.empty((Q, int(k)), dtype=np.float32)
+    nat.check(nat.lib().msocr_topk_smallest_host(_ws_hptr(dist), Q, N, int(k), _ws_hptr(idx), _ws_hptr(val)), "topk_smallest_host")
+    return idx, val

@@ -727,6 +727,40 @@ class TRBA:
             k += len(c)
         return out
 
+    # ------------------------------------------------------------------------------------- word spotting
+    def embed_canvases(self, canvases_dev: torch.Tensor, new_w):
+        """The encoder's frames of crops that are already canvases on the device (this package's extension):
+        canvases [N, img_h, img_w, 3] u8, new_w [N] the resized width of each crop on its canvas (desc[:, 5], qdesc[:, 9]).
+        -> (features [N, T, H] f32 on the device: batch_H of `model.encode`, run in `device_batch` chunks; lengths [N] int32, host:
+        min(T, new_w // FRAME_STRIDE + 1), the frames whose column 8 t lies on the crop and not on the canvas padding, which is
+        frame_to_pixel's own mapping).  The decoder is not run and `recognize_start` is not touched."""
+        from .transforms import FRAME_STRIDE
+        N = int(canvases_dev.shape[0])
+        new_w = np.asarray(new_w, dtype=np.int64).reshape(-1)
+        if new_w.shape != (N,):
+            raise ValueError(f"new_w must be [{N}]")
+        if N == 0:
+            T = self.img_w // FRAME_STRIDE + 1
+            return torch.empty((0, T, self.hidden_size), dtype=torch.float32, device=self.device), np.zeros(0, dtype=np.int32)
+        feats = torch.cat([self.model.encode(canvases_dev[s:s + self.device_batch])[0] for s in range(0, N, self.device_batch)])
+        T = int(feats.shape[1])
+        lengths = np.clip(new_w // FRAME_STRIDE + 1, 1, T).astype(np.int32)
+        return feats.contiguous(), lengths
+
+    def embed(self, images, batch_size: int = 32):
+        """Word images (arrays, paths or PIL images, or one of them) -> (features [N, T, H] f32 on the device, lengths [N] int32), as
+        `embed_canvases` gives them for the canvases `predict` would build.  batch_size is accepted for symmetry with predict and
+        does not enter the numbers: the encoder has no chunk-wide state."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        images_list = images if isinstance(images, list) else [images]
+        arrays = [self._load_rgb(im) for im in images_list]
+        if not arrays:
+            return self.embed_canvases(torch.empty((0, self.img_h, self.img_w, 3), dtype=torch.uint8, device=self.device), [])
+        canv = torch.from_numpy(self._canvases(arrays)).to(self.device, non_blocking=True)
+        new_w = [resized_size(a.shape[0], a.shape[1], self.img_h, self.img_w)[0] for a in arrays]
+        return self.embed_canvases(canv, new_w)
+
     def evaluate(self, images, texts, batch_size: int = 32, *, strict: bool = True, **predict_kwargs) -> Dict[str, Any]:
         """Recognise `images` and compare with their transcriptions `texts` (one str per image) by the reference's evaluation
         measures (its trba_metrics.py: CER = Levenshtein / len(reference) per sample, accuracy = exact matches), with the distances

@@ -521,6 +521,40 @@ int msocr_edit_distance_pairs_host(const int32_t* a_ids, const int32_t* a_trun, 
 int msocr_wordlist_check_host(const int32_t* word_begin_host, const int32_t* word_tok_host, int n_words, int n_tok, int V,
                               int max_word_len);
 
+/* The same lookup under confusion-weighted costs (csrc/lexicon_nearest.hip, csrc/edit_distance_weighted.h): the
+ * distance is what it costs to turn the recognised ROW into the lexicon WORD, the textbook dynamic programme in exact integers.
+ * msocr_edit_costs, device pointers (host pointers for the _host twin):
+ *   sub [V][V] u8: sub[a * V + b] = reading recognised symbol a as lexicon symbol b; diagonal 0; need not be symmetric.
+ *   del [V] u8: dropping recognised symbol a (the recogniser added it).  ins [V] u8: supplying lexicon symbol b (it dropped it).
+ *   unknown, 1..255: any edit that involves a symbol outside [0, V), in the row or in the word; such a symbol matches nothing, itself
+ *     included (the unit-cost rule above).
+ *   min_ins, min_del: the minima of the two vectors, computed by the host; read only for the length bound: a word of n tokens costs a
+ *     row of m symbols at least (n - m) * min_ins or (m - n) * min_del, and is skipped where that exceeds what could still be kept;
+ *     the entry point takes min(min_ins, unknown) and min(min_del, unknown) for it, since a symbol outside [0, V) costs `unknown`.
+ *     Minima larger than the true ones make the lookup miss words; they cause no out-of-bounds read.
+ *   Every off-diagonal sub and every ins and del is 1..255, so distance 0 still means "the row is in the lexicon"; the largest
+ *   distance is (64 + 63) * 255 = 32 385.  The device entry point cannot validate the tables: msocr_edit_costs_check_host does, for
+ *   HOST copies (zero diagonal, nothing else zero, the minima, unknown in 1..255, 1 <= V <= 512, no null pointer): MSOCR_OK or
+ *   MSOCR_E_ARG.  A table that breaks these rules gives other distances, no out-of-bounds read.
+ * msocr_lexicon_nearest_weighted(_host): the contract of msocr_lexicon_nearest(_host) in every other respect: index / dist [B][k]
+ *   ascending in (distance, index), -1 / -1 in unfilled ranks, max_distance in cost units (-1 = no bound), 1 <= k <= 16, the same
+ *   envelope and rejections, and MSOCR_E_ARG also for costs == NULL, a null table, costs->V != V, unknown outside 1..255 or a minimum
+ *   outside 1..255.  workspace: msocr_lexicon_nearest_weighted_ws_bytes(B, n_words, k), the number msocr_lexicon_nearest_ws_bytes
+ *   returns.  Two launches at most, no allocation, no synchronisation, capturable. */
+typedef struct {
+  const uint8_t *sub, *del, *ins;
+  int V, unknown, min_ins, min_del;
+} msocr_edit_costs;
+int msocr_edit_costs_check_host(const uint8_t* sub_host, const uint8_t* del_host, const uint8_t* ins_host, int V, int unknown, int min_ins,
+                                int min_del);
+int64_t msocr_lexicon_nearest_weighted_ws_bytes(int B, int n_words, int k);
+int msocr_lexicon_nearest_weighted(const int32_t* ids, const int32_t* trun_dev, int B, int steps, int V, int eos_id, int pad_id,
+                                   int blank_id, const msocr_wordlist* wl, const msocr_edit_costs* costs, int k, int max_distance,
+                                   int32_t* index_out, int32_t* dist_out, void* workspace, void* stream);
+int msocr_lexicon_nearest_weighted_host(const int32_t* ids_host, const int32_t* trun_host, int B, int steps, int V, int eos_id,
+                                        int pad_id, int blank_id, const msocr_wordlist* wl_host, const msocr_edit_costs* costs_host,
+                                        int k, int max_distance, int32_t* index_out, int32_t* dist_out);
+
 /* ---- detection quality: predicted quads matched to ground truth (an extension beyond the reference's inference code:
  * EAST.evaluate, Pipeline.evaluate, detectors.match_detections) ----
  * The matching rule of the reference's compute_f1 (detectors/_east/utils.py:435-474) with one change: the IoU is the reference's own

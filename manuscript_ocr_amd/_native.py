@@ -53,6 +53,10 @@ class WordList(ctypes.Structure):  # msocr_wordlist: device pointers (host point
     _fields_ = [("word_begin", c_vp), ("word_tok", c_vp), ("n_words", c_i32), ("n_tok", c_i32), ("by_length", c_vp)]
 
 
+class EditCostsTable(ctypes.Structure):  # msocr_edit_costs: device pointers (host pointers for the host twin)
+    _fields_ = [("sub", c_vp), ("del_", c_vp), ("ins", c_vp), ("V", c_i32), ("unknown", c_i32), ("min_ins", c_i32), ("min_del", c_i32)]
+
+
 class CharLMTable(ctypes.Structure):  # msocr_charlm: table is a device pointer
     _fields_ = [("table", c_vp), ("order", c_i32), ("V", c_i32), ("n_ctx", c_i64)]
 
@@ -125,6 +129,12 @@ _SIGS = {
     "msocr_edit_distance_pairs_host": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
                                                c_vp]),
     "msocr_wordlist_check_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
+    "msocr_edit_costs_check_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32]),
+    "msocr_lexicon_nearest_weighted_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "msocr_lexicon_nearest_weighted": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(WordList),
+                                               ctypes.POINTER(EditCostsTable), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "msocr_lexicon_nearest_weighted_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(WordList),
+                                                    ctypes.POINTER(EditCostsTable), c_i32, c_i32, c_vp, c_vp]),
     "msocr_quad_match_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "msocr_quad_match": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "msocr_quad_match_host": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),

@@ -45,6 +45,7 @@ rectify_crops, group_lines and n_best (every alternative then carries its own lm
 
 `pipeline.suggest = Lexicon(words, recognizer.stoi, recognizer.max_length)` with `pipeline.suggest_k` (1..16, default 3) and
 `pipeline.suggest_max_distance` (None = no bound) (this package's extension, None = off by default): approximate dictionary lookup
+(with `pipeline.suggest_costs = EditCosts(...)` under confusion-weighted costs, distances then in cost units)
 behind the open decode (DESIGN.md section 4.17); recognised words come back as SuggestWords (SuggestLmWords when `lm` is also set;
 detectors/_types.py) whose `suggestions` are the suggest_k lexicon words nearest to `text` by Levenshtein distance, with their
 distances.  The decode is untouched: text and confidences are what the same batch gives without the switch.  Combines with
@@ -210,7 +211,7 @@ class _Batch:
     resubmit: Callable[[], "_Batch"]  # the same batch again through the host JPEG decoder
     pages: Optional[list] = None     # set by advance_batch (which makes it idempotent), filled by both stages
     tm: Optional[Dict[str, float]] = None  # host seconds per stage -> Pipeline.last_profile
-    suggest: Optional[tuple] = None  # (suggest, suggest_k, suggest_max_distance) as they were at submit; None = off
+    suggest: Optional[tuple] = None  # (suggest, suggest_k, suggest_max_distance, suggest_costs) as they were at submit; None = off
     skews: Optional[dict] = None     # deskew as it was at submit: page index -> skew_deg; None = off
     region_recs: Optional[dict] = None  # columns as it was at submit: page index -> per block its [R,6] region records; None = off
     ratios: Optional[tuple] = None   # column_params as they were at submit: the three ratios of the cut; None = off
@@ -244,6 +245,7 @@ class Pipeline:
         self.suggest = None                # a recognizers.Lexicon: every word gets its nearest lexicon words, SuggestWords come back (user extension)
         self.suggest_k = 3                 # suggestions per word, 1..16
         self.suggest_max_distance = None   # drop suggestions further away than this many edits; None = no bound
+        self.suggest_costs = None          # a recognizers.EditCosts: rank the suggestions by the confusion-weighted distance (needs suggest)
         self.serialize_streams = False     # every group on the caller's stream: same launches, no overlap (profiling aid, bench.py)
         self.stream_sets = 2               # batches that may be in flight at once, each on its own set of streams (bench.py, tests)
         self.det_stream_priority = True    # detector streams are created at high priority; False = normal (profiling aid)
@@ -371,10 +373,12 @@ class Pipeline:
             lexicon = self.lexicon if isinstance(self.recognizer, TRBA) else None
             lm = self.lm if isinstance(self.recognizer, TRBA) else None
             suggest = self.suggest if isinstance(self.recognizer, TRBA) else None
+            suggest_costs = self.suggest_costs if isinstance(self.recognizer, TRBA) else None
             extra = {**({"n_best": n_best} if n_best else {}), **({"lexicon": lexicon} if lexicon is not None else {}),
                      **({"lm": lm, "lm_weight": self.lm_weight} if lm is not None else {}),
                      **({"suggest": suggest, "suggest_k": self.suggest_k, "suggest_max_distance": self.suggest_max_distance}
-                        if suggest is not None else {})}
+                        if suggest is not None else {}),
+                     **({"suggest_costs": suggest_costs} if suggest_costs is not None else {})}
             results = self.recognizer.predict(crops, **extra)
             if profile:
                 print(f"Recognition: {time.time() - t0:.3f}s")
@@ -513,9 +517,11 @@ class Pipeline:
             if self.recognizer.use_graphs:
                 raise ValueError("Pipeline.lexicon with a use_graphs recogniser: captured graphs are not provided for the lexicon-constrained "
                                  "decode; construct the recogniser without use_graphs")
-        suggest = None if self.suggest is None else (self.suggest, self.suggest_k, self.suggest_max_distance)
+        suggest = None if self.suggest is None else (self.suggest, self.suggest_k, self.suggest_max_distance, self.suggest_costs)
         if suggest is not None:
-            self.recognizer._check_suggest(*suggest, lexicon, "beam")
+            self.recognizer._check_suggest(*suggest[:3], lexicon, "beam", suggest[3])
+        elif self.suggest_costs is not None:
+            raise ValueError("Pipeline.suggest_costs needs Pipeline.suggest: the costs weight a lexicon lookup, they start none")
         # image ingest: a JPEG file is decoded ON THE DEVICE (Huffman stage + reconstruction, ingest.py) — the page's
         # pixels never exist on the host, `arrays` then only carries the shape; everything else goes through read_image
         dec, ingest_pending = [None] * len(images), None
@@ -798,7 +804,8 @@ class Pipeline:
                         t0 = time.perf_counter()
                         fin = rec.recognize_finish(grp.handle, spans=[(first, n) for first, n in grp.spans if n > 0], n_best=h.n_best,
                                                    **({} if h.suggest is None else {"suggest": h.suggest[0], "suggest_k": h.suggest[1],
-                                                                                    "suggest_max_distance": h.suggest[2]}))
+                                                                                    "suggest_max_distance": h.suggest[2]}),
+                                                   **({} if h.suggest is None or h.suggest[3] is None else {"suggest_costs": h.suggest[3]}))
                         if h.suggest is not None:
                             fin, (sug_index, sug_dist) = fin[:-2], fin[-2:]
                         if h.n_best:

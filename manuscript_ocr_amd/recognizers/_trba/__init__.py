@@ -347,7 +347,7 @@ class TRBA:
         return _Recognition([part], [(0, Mcap)], Mcap, M, "beam", beam_size, graph_inst=Lease(inst))
 
     def recognize_finish(self, handle, batch_size=32, spans=None, return_logits=False, n_best=0, suggest=None, suggest_k=3,
-                         suggest_max_distance=None, targets=None):
+                         suggest_max_distance=None, targets=None, suggest_costs=None):
         """Phases 2-3 — derive the reference's per-chunk run lengths, back-track (beam) and reduce confidences.
 
         `spans` = [(start, count), ...] groups of rows that the reference would have passed to ONE predict() call
@@ -367,15 +367,18 @@ class TRBA:
         nearest to its text by Levenshtein distance, nearest first, -1 / -1 where there are fewer or suggest_max_distance (None = no
         bound) drops them (msocr_lexicon_nearest on the finalised device ids; `Lexicon.suggestions` turns
         them into words).  With n_best they describe rank 0.  Nothing else changes with the switch.
+        suggest_costs (an EditCosts over the same charset, only with suggest): the lookup ranks by the confusion-weighted distance
+        instead (msocr_lexicon_nearest_weighted); sug_dist and suggest_max_distance are then in cost units.
         targets = (target [N, steps_t] i32, t_run [N] i32), host arrays as transforms.pack_targets packs transcriptions: three more
         host arrays behind all others — distance [N] i32, the Levenshtein distance between every row's text and its target's, and the
         two text lengths hyp_len [N], ref_len [N] (msocr_edit_distance_pairs on the device ids; `evaluate`)."""
         try:
-            self._check_suggest(suggest, suggest_k, suggest_max_distance, handle.lexicon, handle.mode)
+            self._check_suggest(suggest, suggest_k, suggest_max_distance, handle.lexicon, handle.mode, suggest_costs)
             if n_best < 0 or (n_best and (handle.mode != "beam" or n_best > handle.beam)):
                 raise ValueError(f"n_best = {n_best} needs a beam decode of at least that width (mode {handle.mode!r}, beam_size {handle.beam})")
             return self._recognize_finish(handle, batch_size, spans, return_logits, int(n_best),
-                                          None if suggest is None else (suggest, suggest_k, suggest_max_distance), targets)
+                                          None if suggest is None else (suggest, suggest_k, suggest_max_distance, suggest_costs),
+                                          targets)
         finally:
             if handle.graph_inst is not None:  # also on an exception: the instance must not stay leased for ever
                 handle.graph_inst.release()
@@ -425,7 +428,7 @@ class TRBA:
                                                      ops._stream()), "seq_confidence")
             ids_out.append(ids), conf_out.append(conf)
             if suggest is not None:  # on the device ids, before they cross PCIe
-                sug_out.append(suggest[0].nearest_device(ids, tr, suggest[1], suggest[2]))
+                sug_out.append(suggest[0].nearest_device(ids, tr, suggest[1], suggest[2], suggest[3]))
             if targets is not None:
                 po = torch.empty((3, B), dtype=torch.int32, device=self.device)
                 ids_c = ids.contiguous()
@@ -465,17 +468,17 @@ class TRBA:
 
     def recognize_canvases(self, canvases_dev: torch.Tensor, batch_size=32, mode="beam", beam_size=8, temperature=1.7, alpha=0.9,
                            spans=None, return_logits=False, char_details=False, n_best=0, lexicon=None, lm=None, lm_weight=0.5,
-                           suggest=None, suggest_k=3, suggest_max_distance=None):
+                           suggest=None, suggest_k=3, suggest_max_distance=None, suggest_costs=None):
         """canvases [N,img_h,img_w,3] u8 on device -> (ids [N,steps] i32, t_run [N] i32, conf [N] f32[, logits][, prob, centre, peak]
         [, alt_ids, alt_prob, alt_conf, alt_logp][, sug_index, sug_dist]) on host.  lexicon, lm, lm_weight: as for `recognize_start`;
-        suggest, suggest_k, suggest_max_distance: as for `recognize_finish`."""
+        suggest, suggest_k, suggest_max_distance, suggest_costs: as for `recognize_finish`."""
         self._check_n_best(n_best, mode, beam_size)
-        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode)
+        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode, suggest_costs)
         return self.recognize_finish(self.recognize_start(canvases_dev, mode, beam_size, temperature, alpha,
                                                           spans if spans is not None else [(0, canvases_dev.shape[0])], batch_size,
                                                           char_details=char_details, lexicon=lexicon, lm=lm, lm_weight=lm_weight),
                                      batch_size, spans, return_logits, n_best=n_best, suggest=suggest, suggest_k=suggest_k,
-                                     suggest_max_distance=suggest_max_distance)
+                                     suggest_max_distance=suggest_max_distance, suggest_costs=suggest_costs)
 
     def texts(self, ids, trun) -> List[str]:
         """decode_tokens (transforms.py:196-206) over the first t_run ids of every row, vectorised: the text ends at the
@@ -508,14 +511,17 @@ class TRBA:
         if lexicon.num_classes != len(self.itos):
             raise ValueError(f"the lexicon was built for a charset of {lexicon.num_classes} tokens, this recogniser's has {len(self.itos)}")
 
-    def _check_suggest(self, suggest, suggest_k, suggest_max_distance, lexicon=None, mode="beam"):
+    def _check_suggest(self, suggest, suggest_k, suggest_max_distance, lexicon=None, mode="beam", suggest_costs=None):
         if suggest is None:
+            if suggest_costs is not None:
+                raise ValueError("suggest_costs needs suggest: the costs weight a lexicon lookup, they start none")
             return
         if lexicon is not None:
             raise ValueError("suggest together with a lexicon is not provided: a constrained decode's word is in its lexicon, at distance 0")
         if suggest.num_classes != len(self.itos):
             raise ValueError(f"the suggest lexicon was built for a charset of {suggest.num_classes} tokens, this recogniser's has {len(self.itos)}")
         suggest._check_k_bound(suggest_k, suggest_max_distance)
+        suggest._check_costs(suggest_costs)
         steps = self.max_length + 1 if mode == "greedy" else self.max_length
         if steps > 64:
             raise ValueError(f"the nearest-word lookup takes rows of at most 64 steps, this decode has {steps}")
@@ -804,7 +810,8 @@ class TRBA:
     # ------------------------------------------------------------------------------------- API
     def predict(self, images, batch_size: int = 32, mode: str = "beam", beam_size: int = 8, temperature: float = 1.7,
                 alpha: float = 0.9, *, return_chars: bool = False, n_best: int = 0, lexicon=None, lm=None,
-                lm_weight: float = 0.5, suggest=None, suggest_k: int = 3, suggest_max_distance=None) -> List[Dict[str, Any]]:
+                lm_weight: float = 0.5, suggest=None, suggest_k: int = 3, suggest_max_distance=None,
+                suggest_costs=None) -> List[Dict[str, Any]]:
         """Same contract as the reference TRBA.predict (__init__.py:290-434).  return_chars=True (this package's keyword-only extension): every
         result also has "chars", a list of {"char", "confidence", "x"} with one entry per symbol of "text": the probability the
         decoder gave the symbol and the estimated x of its centre in pixels of the input image (the attention centroid mapped
@@ -825,14 +832,17 @@ class TRBA:
         together with `lexicon`): every result also has "suggestions", a list of {"text", "lexicon_index", "distance"}: the
         suggest_k words of the lexicon nearest to "text" by Levenshtein distance, nearest first, ties by ascending index (DESIGN.md
         section 4.17).  Distance 0 means "text" is a lexicon word; an empty list means nothing lies within the bound.  The decode
-        itself is untouched: every other field is what the same call without `suggest` returns."""
+        itself is untouched: every other field is what the same call without `suggest` returns.
+        suggest_costs=EditCosts(...) (only with `suggest`, over the same charset): the suggestions are ranked by the
+        confusion-weighted edit distance instead, what it costs to turn "text" into the word under the recogniser's own confusions
+        (DESIGN.md section 4.26); "distance" and suggest_max_distance are then in cost units."""
         images_list = images if isinstance(images, list) else [images]
         if mode not in ("greedy", "beam"):
             raise ValueError(f"Unknown mode: {mode}")
         self._check_n_best(n_best, mode, beam_size)
         self._check_lexicon(lexicon, mode)
         self._check_lm(lm, lm_weight, mode, lexicon)
-        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode)
+        self._check_suggest(suggest, suggest_k, suggest_max_distance, lexicon, mode, suggest_costs)
         if not images_list:
             return []
         arrays = [self._load_rgb(im) for im in images_list]
@@ -841,7 +851,7 @@ class TRBA:
             return self._results(*self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha))
         fin = self.recognize_canvases(canv, batch_size, mode, beam_size, temperature, alpha, char_details=return_chars, n_best=n_best,
                                       lexicon=lexicon, lm=lm, lm_weight=lm_weight, suggest=suggest, suggest_k=suggest_k,
-                                      suggest_max_distance=suggest_max_distance)
+                                      suggest_max_distance=suggest_max_distance, suggest_costs=suggest_costs)
         if suggest is not None:
             fin, sug = fin[:-2], suggest.suggestions(*fin[-2:])
         ids, trun, conf = fin[:3]

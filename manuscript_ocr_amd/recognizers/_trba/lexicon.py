@@ -9,6 +9,8 @@ one prefix, which is what word_of_node relies on.
 The encodings are also kept as a CSR word list (word_begin, word_tok) for the nearest-word lookup:
 `nearest` / `nearest_texts` give, for rows of ids or strings, the k words with the smallest Levenshtein distance and the distances,
 through msocr_lexicon_nearest on a device or its host twin without one; msocr_wordlist_check_host validates the list once.
+With `costs=EditCosts(...)` the same calls rank by the confusion-weighted distance (msocr_lexicon_nearest_weighted, DESIGN.md section
+4.26); distances and max_distance are then in cost units.
 """
 import ctypes
 
@@ -216,12 +218,21 @@ class Lexicon:
             raise ValueError(f"max_distance must not be negative, got {max_distance}")
         return int(k), -1 if max_distance is None else int(max_distance)
 
-    def nearest_device(self, ids_dev, trun_dev, k=3, max_distance=None):
-        """msocr_lexicon_nearest on the current stream over ids [N, steps] / t_run [N] int32 tensors on one device, without any
-        synchronisation -> (index [N, k], distance [N, k]) int32 tensors on that device."""
+    def _check_costs(self, costs):
+        if costs is None:
+            return
+        if not hasattr(costs, "struct") or not hasattr(costs, "num_classes"):
+            raise TypeError(f"costs must be an EditCosts, got {type(costs).__name__}")
+        if costs.num_classes != self.num_classes:
+            raise ValueError(f"the costs were built for a charset of {costs.num_classes} tokens, this lexicon's has {self.num_classes}")
+
+    def nearest_device(self, ids_dev, trun_dev, k=3, max_distance=None, costs=None):
+        """msocr_lexicon_nearest (with costs: msocr_lexicon_nearest_weighted) on the current stream over ids [N, steps] / t_run [N]
+        int32 tensors on one device, without any synchronisation -> (index [N, k], distance [N, k]) int32 tensors on that device."""
         import torch
         from ... import ops
         k, bound = self._check_k_bound(k, max_distance)
+        self._check_costs(costs)
         N, steps = (int(v) for v in ids_dev.shape)
         if not 1 <= steps <= 64:
             raise ValueError(f"rows of 1 to 64 steps, got {steps}")
@@ -233,18 +244,27 @@ class Lexicon:
             return index, dist
         ids_dev, trun_dev = ids_dev.contiguous(), trun_dev.contiguous()
         ws = torch.empty((max(int(nat.lib().msocr_lexicon_nearest_ws_bytes(N, len(self.words), k)), 8),), dtype=torch.uint8, device=dev)
+        if costs is not None:  # the same workspace: msocr_lexicon_nearest_weighted_ws_bytes is that number
+            nat.check(nat.lib().msocr_lexicon_nearest_weighted(ids_dev.data_ptr(), trun_dev.data_ptr(), N, steps, self.num_classes,
+                                                               self.eos_id, self.pad_id, self.blank_id, ctypes.byref(wl), costs.struct(dev),
+                                                               k, bound, index.data_ptr(), dist.data_ptr(), ws.data_ptr(), ops._stream()),
+                      "lexicon_nearest_weighted")
+            return index, dist
         nat.check(nat.lib().msocr_lexicon_nearest(ids_dev.data_ptr(), trun_dev.data_ptr(), N, steps, self.num_classes, self.eos_id,
                                                   self.pad_id, self.blank_id, ctypes.byref(wl), k, bound, index.data_ptr(),
                                                   dist.data_ptr(), ws.data_ptr(), ops._stream()), "lexicon_nearest")
         return index, dist
 
-    def nearest(self, ids, t_run=None, k=3, max_distance=None, device=None):
+    def nearest(self, ids, t_run=None, k=3, max_distance=None, device=None, costs=None):
         """For every row of ids [N, steps] (a host array or a device tensor of token ids, steps <= 64), the k lexicon words with the
         smallest Levenshtein distance to the row's text (what TRBA.texts decodes: up to the first EOS among the first t_run ids, PAD
         and BLANK removed; t_run None = all steps) -> host arrays (index [N, k] int32 into `words`, distance [N, k] int32), nearest
         first, equal distances by ascending index.  max_distance: words further away are dropped (None = no bound); unfilled ranks
-        hold -1, -1.  device None: the host twin (no GPU needed); otherwise msocr_lexicon_nearest on that device."""
+        hold -1, -1.  device None: the host twin (no GPU needed); otherwise msocr_lexicon_nearest on that device.
+        costs (an EditCosts over this lexicon's charset, else ValueError): the confusion-weighted distance of DESIGN.md section 4.26
+        instead, what it costs to turn the row into the word; distances and max_distance are then in cost units."""
         k, bound = self._check_k_bound(k, max_distance)
+        self._check_costs(costs)
         is_tensor = hasattr(ids, "data_ptr")
         if device is None and not is_tensor:
             ids = np.ascontiguousarray(ids, dtype=np.int32)
@@ -256,6 +276,12 @@ class Lexicon:
                 raise ValueError(f"t_run must be [{N}]")
             index, dist = np.empty((N, k), dtype=np.int32), np.empty((N, k), dtype=np.int32)
             wl = self.wordlist(None)[2]
+            if costs is not None:
+                nat.check(nat.lib().msocr_lexicon_nearest_weighted_host(ids.ctypes.data, trun.ctypes.data, N, steps, self.num_classes,
+                                                                        self.eos_id, self.pad_id, self.blank_id, ctypes.byref(wl),
+                                                                        costs.struct(None), k, bound, index.ctypes.data,
+                                                                        dist.ctypes.data), "lexicon_nearest_weighted_host")
+                return index, dist
             nat.check(nat.lib().msocr_lexicon_nearest_host(ids.ctypes.data, trun.ctypes.data, N, steps, self.num_classes, self.eos_id,
                                                            self.pad_id, self.blank_id, ctypes.byref(wl), k, bound, index.ctypes.data,
                                                            dist.ctypes.data), "lexicon_nearest_host")
@@ -275,7 +301,7 @@ class Lexicon:
         if tuple(trun_dev.shape) != (N,):
             raise ValueError(f"t_run must be [{N}]")
         with torch.cuda.device(dev):
-            index, dist = self.nearest_device(ids_dev, trun_dev, k, bound if bound >= 0 else None)
+            index, dist = self.nearest_device(ids_dev, trun_dev, k, bound if bound >= 0 else None, costs)
             return index.cpu().numpy(), dist.cpu().numpy()
 
     def encode_rows(self, texts):
@@ -297,10 +323,10 @@ class Lexicon:
             ids[i, :len(r)] = r
         return ids, np.array([len(r) for r in rows], dtype=np.int32)
 
-    def nearest_texts(self, texts, k=3, max_distance=None, device=None):
+    def nearest_texts(self, texts, k=3, max_distance=None, device=None, costs=None):
         """`nearest` for strings (encode_rows) -> (index [N, k], distance [N, k])."""
         ids, trun = self.encode_rows(list(texts))
-        return self.nearest(ids, trun, k, max_distance, device)
+        return self.nearest(ids, trun, k, max_distance, device, costs)
 
     def suggestions(self, index, distance):
         """(index, distance) rows of `nearest` -> per row a list of {"text", "lexicon_index", "distance"}, nearest first; unfilled

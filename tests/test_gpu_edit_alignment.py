@@ -126,6 +126,54 @@ def test_no_pairs_and_the_guards_behind_every_buffer():
     assert bool((ws[need:] == 0xA5).all())
 
 
+@pytest.mark.parametrize("shift", [0, 3])
+def test_first_offsets_above_zero_and_views(shift):
+    """The first test on the device with a_off[0] > 0 and b_off[0] > 0: a_base / b_base of eal_traceback_kernel are not 0, and
+    p.a0 / p.b0 of the mask and sweep kernels count from inside the token arrays, which carry junk before the first offset and
+    behind the last.  The maps hold a_off[N] - a_off[0] and b_off[N] - b_off[0] entries and begin at the first pair's tokens: a map
+    written at its array index instead lands in the guard.  shift = 3: the token arrays are the views buf[3:] of a fresh allocation
+    besides.  Guards of -7 on both sides of every output; the host twin gets the same arrays and offsets."""
+    import torch
+    from manuscript_ocr_amd import ops
+    rng = np.random.default_rng(52)
+    pairs = [random_pair(rng, m, n, 30) for m, n in ((0, 5), (70, 0), (200, 129), (4097, 300), (64, 64), (65, 63))]
+    a_tok, a_off = csr([p[0] for p in pairs])
+    b_tok, b_off = csr([p[1] for p in pairs])
+    v = [p[2] for p in pairs]
+    clean = ops.edit_alignment_host(a_tok, a_off, b_tok, b_off, v)
+    # the junk repeats the neighbouring tokens, so that a table or a sweep that starts early or ends late finds matches there
+    a_tok, a_off = np.concatenate([a_tok[:37], a_tok, a_tok[-21:]]), a_off + 37
+    b_tok, b_off = np.concatenate([b_tok[:5], b_tok, b_tok[-66:]]), b_off + 5
+    N, na, nb = len(pairs), int(a_off[-1] - a_off[0]), int(b_off[-1] - b_off[0])
+    assert a_off[0] == 37 and b_off[0] == 5 and na == len(a_tok) - 58 and nb == len(b_tok) - 71
+    want = ops.edit_alignment_host(a_tok, a_off, b_tok, b_off, v)
+    for w, c in zip(want, clean):
+        assert w.shape == c.shape and w.tolist() == c.tolist()    # the host twin reads nothing outside the offsets
+    views = []
+    for tok in (a_tok, b_tok):
+        buf = torch.full((shift + len(tok),), -3, dtype=torch.int32, device="cuda")
+        buf[shift:] = torch.from_numpy(tok).cuda()
+        views.append(buf[shift:])
+        assert views[-1].data_ptr() % 16 == 4 * shift
+    G = 64
+    sizes = (N, na, nb, 4 * N)
+    bufs = [torch.full((G + k + G,), -7, dtype=torch.int32, device="cuda") for k in sizes]
+    out = (bufs[0][G:G + N], bufs[1][G:G + na], bufs[2][G:G + nb], bufs[3][G:G + 4 * N].view(N, 4))
+    ops.edit_alignment(views[0], a_off, views[1], b_off, v, out=out)
+    torch.cuda.synchronize()
+    for name, got, w in zip(("dist", "a_map", "b_map", "counts"), out, want):
+        assert got.cpu().numpy().tolist() == w.tolist(), name
+    for buf, k in zip(bufs, sizes):
+        assert bool((buf[:G] == -7).all()) and bool((buf[G + k:] == -7).all())
+    # without `out` the maps have the length of the offsets' span, not of the token arrays
+    fresh = ops.edit_alignment(views[0], a_off, views[1], b_off, v)
+    assert [tuple(t.shape) for t in fresh] == [(N,), (na,), (nb,), (N, 4)]
+    for got, w in zip(fresh, want):
+        assert got.cpu().numpy().tolist() == w.tolist()
+    for pair, g in zip(pairs, split(pairs, [t.cpu().numpy() for t in fresh])):
+        check_invariants(pair, g)
+
+
 def same_alignments(a, b):
     assert len(a) == len(b)
     for x, y in zip(a, b):

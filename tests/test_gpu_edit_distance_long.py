@@ -105,6 +105,40 @@ def test_no_pairs_and_the_guard_behind_the_distances():
     assert bool((buf[N:] == -7).all()) and bool((ws[need:] == 0xA5).all())
 
 
+@pytest.mark.parametrize("shift", [0, 3])
+def test_first_offsets_above_zero_and_views(shift):
+    """The first test on the device with a_off[0] > 0 and b_off[0] > 0: p.a0 / p.b0 of the mask and sweep kernels count from inside
+    the token arrays, which carry junk before the first offset and behind the last (the neighbouring tokens again, so that a table
+    or a sweep that starts early or ends late finds matches there).  shift = 3: the token arrays are the views buf[3:] of a fresh
+    allocation besides.  A guard of -7 on both sides of the distances; the host twin gets the same arrays and offsets."""
+    import torch
+    from manuscript_ocr_amd import ops
+    rng = np.random.default_rng(52)
+    pairs = [random_pair(rng, m, n, 30) for m, n in ((0, 5), (70, 0), (200, 129), (4097, 300), (64, 64), (65, 63))]
+    a_tok, a_off = csr([p[0] for p in pairs])
+    b_tok, b_off = csr([p[1] for p in pairs])
+    v = [p[2] for p in pairs]
+    clean = ops.edit_distance_long_host(a_tok, a_off, b_tok, b_off, v)
+    a_tok, a_off = np.concatenate([a_tok[:37], a_tok, a_tok[-21:]]), a_off + 37
+    b_tok, b_off = np.concatenate([b_tok[:5], b_tok, b_tok[-66:]]), b_off + 5
+    assert a_off[0] == 37 and b_off[0] == 5 and a_off[-1] == len(a_tok) - 21 and b_off[-1] == len(b_tok) - 66
+    want = ops.edit_distance_long_host(a_tok, a_off, b_tok, b_off, v)
+    assert want.tolist() == clean.tolist()                        # the host twin reads nothing outside the offsets
+    views = []
+    for tok in (a_tok, b_tok):
+        buf = torch.full((shift + len(tok),), -3, dtype=torch.int32, device="cuda")
+        buf[shift:] = torch.from_numpy(tok).cuda()
+        views.append(buf[shift:])
+        assert views[-1].data_ptr() % 16 == 4 * shift
+    N, G = len(pairs), 64
+    buf = torch.full((G + N + G,), -7, dtype=torch.int32, device="cuda")
+    ops.edit_distance_long(views[0], a_off, views[1], b_off, v, out=buf[G:G + N])
+    torch.cuda.synchronize()
+    assert buf[G:G + N].cpu().numpy().tolist() == want.tolist()
+    assert bool((buf[:G] == -7).all()) and bool((buf[G + N:] == -7).all())
+    assert ops.edit_distance_long(views[0], a_off, views[1], b_off, v).cpu().numpy().tolist() == want.tolist()
+
+
 def test_sequence_edit_distances_on_the_device():
     from manuscript_ocr_amd.recognizers import sequence_edit_distances, text_error_rates
     rng = np.random.default_rng(61)

@@ -5,7 +5,8 @@ text_search_select or a canonical sort (the device writes its hits in no particu
 Sizes follow L = MSOCR_SEARCH_SEGMENT, the tokens one lane of the scan kernel reports: text lengths around one, two and three
 segments, patterns planted around the first cut and around the first token after the warm-up of m + k tokens, texts whose neighbours
 hold the rest of the pattern, more segments than a workgroup has lanes, every lane of every wave appending at once, and capacities
-below the count."""
+below the count.  A last group enters what those sizes leave out: token arrays off the 16-byte boundary, first offsets above 0,
+and tables, records and patterns beyond one trip of a capped grid."""
 import numpy as np
 import pytest
 
@@ -39,8 +40,23 @@ def same_as_host(patterns, ks, texts, v):
     return want
 
 
-@pytest.mark.parametrize("m", [5, 63, 64])
-def test_cuts_and_the_first_token_after_the_warm_up(m):
+def device_views(pat_tok, pat_off, ks, txt_tok, txt_off, v, shift=0):
+    """ops.text_search on token arrays that lie `shift` elements behind the start of a fresh allocation, as the views buf[shift:]:
+    the array's memory then begins 4 * shift bytes behind a 16-byte boundary, which the view's address must show"""
+    import torch
+    from manuscript_ocr_amd import ops
+    views = []
+    for tok in (pat_tok, txt_tok):
+        buf = torch.full((shift + len(tok),), -3, dtype=torch.int32, device="cuda")
+        buf[shift:] = torch.from_numpy(np.ascontiguousarray(tok, dtype=np.int32)).cuda()
+        views.append(buf[shift:])
+        assert views[-1].data_ptr() % 16 == 4 * shift and views[-1].is_contiguous()
+    return ops.text_search(views[0], pat_off, ks, views[1], txt_off, v)
+
+
+def cut_texts(m):
+    """one pattern of m tokens under three bounds, and texts with its copies planted around the segment cuts
+    -> (a, ks, v, texts, planted_at)"""
     L = seg()
     rng = np.random.default_rng(300 + m)
     v = 60
@@ -61,6 +77,12 @@ def test_cuts_and_the_first_token_after_the_warm_up(m):
             noisy = b.copy()                        # the same copy with one substitution and one token dropped in front of it
             noisy[end - 1 - m // 2] = v + 3
             texts.append(np.delete(noisy, max(end - m - 1, 0)))
+    return a, ks, v, texts, planted_at
+
+
+@pytest.mark.parametrize("m", [5, 63, 64])
+def test_cuts_and_the_first_token_after_the_warm_up(m):
+    a, ks, v, texts, planted_at = cut_texts(m)
     want = same_as_host([a, a, a], ks, texts, v)
     exact = {(h[1], h[3]) for h in want.tolist() if h[0] == 0}
     assert all(p in exact for p in planted_at)
@@ -173,6 +195,163 @@ def test_alphabets_of_one_and_of_the_cap_and_foreign_tokens():
     patterns = [wild[rng.integers(0, 7, m)] for m in (4, 33, 64)]
     texts = [wild[rng.integers(0, 7, n)] for n in (0, L + 6, 5 * L)]
     same_as_host(patterns, [2, 20, 50], texts, 6)
+
+
+# ------------------------------------------------------------------------------------------------ launch geometry and views
+# The tests above hand over fresh allocations with offsets from 0 and stay below every cap of a grid.  The ones below enter the
+# code that runs otherwise: each names the loop or branch it is the first to enter and asserts the geometry it is there for.
+ZERO_CAP = 4096 * 256      # workgroups x words of one trip of ts_zero_kernel, and workgroups x records of one of ts_start_kernel
+SCAN_ROWS = 65535          # gridDim.y of ts_scan_kernel at most
+
+
+@pytest.mark.parametrize("shift", [1, 2, 3])
+def test_token_arrays_off_the_16_byte_boundary(shift):
+    """The first test in which `align` of ts_scan_kernel is not 0: both token arrays are the views buf[shift:] of a fresh
+    allocation, so the 16-byte loads of ts_load4 start `shift` elements off the array's own index and both ends of the array go
+    through its element-wise arm.  The texts of the cut test for m = 5, between texts of L - 1, L and L + 1 tokens whose first and
+    whose last m tokens are the pattern: the first and the last token of the array end and begin a hit."""
+    L = seg()
+    a, ks, v, texts, planted_at = cut_texts(5)
+    rng = np.random.default_rng(310 + shift)
+    ends = []
+    for n in (L - 1, L, L + 1):
+        b = rng.integers(0, v, n).astype(np.int32)
+        b[:5], b[-5:] = a, a
+        ends.append(b)
+    texts = ends[:2] + texts + ends[2:]
+    patterns = [a, a, a]
+    want, count = host(patterns, ks, texts, v)
+    pat_tok, pat_off = csr(patterns)
+    txt_tok, txt_off = csr(texts)
+    plain = device_views(pat_tok, pat_off, ks, txt_tok, txt_off, v, 0)
+    got = device_views(pat_tok, pat_off, ks, txt_tok, txt_off, v, shift)
+    assert len(got) == count == len(plain)
+    assert np.array_equal(canonical(got), canonical(plain)) and np.array_equal(canonical(got), want)
+    exact = {(h[1], h[3]) for h in want.tolist() if h[0] == 0}
+    assert all((t + 2, end) in exact for t, end in planted_at)
+    last = len(texts) - 1
+    assert {(0, 5), (0, L - 1), (1, 5), (1, L), (last, 5), (last, L + 1)} <= exact
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_first_offsets_above_zero(shift):
+    """The first test on the device with txt_off[0] > 0 and pat_off[0] > 0 (glo > 0 in ts_scan_kernel, a0 > 0 for pattern 0 in
+    ts_masks_kernel): the token arrays carry junk before the first offset and behind the last.  The junk before txt_off[0] ends
+    with the first half of a pattern whose second half opens text 0, the junk behind txt_off[T] completes a pattern that the last
+    text begins, and the junk around the patterns would complete a third: a read across either edge makes a hit the host twin, given
+    the same arrays and offsets, does not have.  Once aligned, once with both arrays one element off the 16-byte boundary."""
+    from manuscript_ocr_amd import ops
+    L = seg()
+    rng = np.random.default_rng(320)
+    v = 30
+    a = rng.integers(0, v, 12).astype(np.int32)
+    c = rng.integers(0, v, 9).astype(np.int32)
+    rnd = lambda n: rng.integers(0, v, n).astype(np.int32)  # noqa: E731
+    texts = [np.concatenate([a[6:], rnd(L + 2), a, rnd(5)]), np.zeros(0, dtype=np.int32), rnd(2 * L - 1), np.concatenate([rnd(L - 3), a, a[:6]])]
+    patterns, ks = [a, a, c[3:6], a[:7]], [0, 2, 0, 1]
+    clean, count = host(patterns, ks, texts, v)
+    txt_tok, txt_off = csr(texts)
+    pat_tok, pat_off = csr(patterns)
+    before_t, after_t = np.concatenate([rnd(7), a[:6]]), np.concatenate([a[6:], rnd(6)])    # 13 tokens: text 0 starts off the boundary
+    before_p, after_p = c[:3], c[6:]                                                       # c[3:6] is a pattern: c would be one too
+    txt_tok, txt_off = np.concatenate([before_t, txt_tok, after_t]), txt_off + len(before_t)
+    pat_tok, pat_off = np.concatenate([before_p, pat_tok, after_p]), pat_off + len(before_p)
+    assert txt_off[0] == 13 and txt_off[-1] == len(txt_tok) - 12 and pat_off[0] == 3 and pat_off[-1] == len(pat_tok) - 3
+    want, n = ops.text_search_host(pat_tok, pat_off, ks, txt_tok, txt_off, v)
+    assert n == count and np.array_equal(want, clean)       # the host twin reads nothing outside the offsets
+    got = device_views(pat_tok, pat_off, ks, txt_tok, txt_off, v, shift)
+    assert len(got) == count
+    assert np.array_equal(canonical(got), want)
+    assert np.array_equal(ops.text_search_select(got), ops.text_search_select(want))
+    exact = [h for h in want.tolist() if h[0] == 0]
+    assert [(h[1], h[2], h[3]) for h in exact] == [(0, 6 + L + 2, 6 + L + 2 + 12), (3, L - 3, L + 9)]  # the two whole copies, no half
+
+
+def test_mask_tables_beyond_one_trip_of_the_zero_kernel():
+    """The first test in which ts_zero_kernel takes a second trip of its grid-stride loop: 257 patterns over v = 2048 are
+    257 * 2 * 2048 table words, above the 4096 workgroups x 256 words of one trip.  The workspace holds 0xA5 everywhere, so a word
+    that is not cleared matches at garbage positions; the words of the second trip are the rows of the last pattern, which has
+    known hits, and a text over all 2048 symbols reads every row's every word."""
+    import torch
+    from manuscript_ocr_amd import ops
+    Q, V = 257, ops.SEARCH_MAX_ALPHABET
+    words = Q * 2 * V
+    assert words == 1052672 and words > ZERO_CAP and (Q - 1) * 2 * V >= ZERO_CAP   # pattern 256's rows lie in the second trip
+    rng = np.random.default_rng(330)
+    text = rng.permutation(V).astype(np.int32)
+    at = rng.integers(0, V - 8, Q)
+    patterns = [text[int(s):int(s) + 4 + q % 5].copy() for q, s in enumerate(at)]
+    patterns[Q - 1] = text[V - 5:].copy()
+    ks = [q % 2 for q in range(Q)]
+    texts = [text, text[::-1].copy(), text[:100]]
+    want, count = host(patterns, ks, texts, V)
+    pat_tok, pat_off = csr(patterns)
+    txt_tok, txt_off = csr(texts)
+    need = ops.text_search_workspace_bytes(pat_off, ks, txt_off, V)
+    assert need >= 8 * words
+    ws = torch.full((need + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    buf = torch.full((count + 16, 5), -7, dtype=torch.int32, device="cuda")
+    cnt = torch.full((1,), -7, dtype=torch.int64, device="cuda")
+    ops.text_search_into(torch.from_numpy(pat_tok).cuda(), pat_off, ks, torch.from_numpy(txt_tok).cuda(), txt_off, V, buf[:count], cnt,
+                         workspace=ws[:need])
+    torch.cuda.synchronize()
+    assert int(cnt.item()) == count
+    assert np.array_equal(canonical(buf[:count].cpu().numpy()), want)
+    assert bool((buf[count:] == -7).all()) and bool((ws[need:] == 0xA5).all())
+    assert [Q - 1, 0, V - 5, V, 0] in want.tolist() and len(want[want[:, 0] == Q - 1]) >= 1
+
+
+def test_more_records_than_one_trip_of_the_start_kernel():
+    """The first test in which ts_start_kernel takes a second trip of its grid-stride loop: the one-symbol text of 2^20 + 300 tokens
+    holds the pattern [0] at every position, more records than 4096 workgroups x 256 lanes.  Every record must be a true hit with
+    its start, end = 1 .. n each exactly once, and the guard rows behind hits[capacity] stay as they were."""
+    import torch
+    from manuscript_ocr_amd import ops
+    n = (1 << 20) + 300
+    patterns, ks, texts = [np.zeros(1, dtype=np.int32)], [0], [np.zeros(n, dtype=np.int32)]
+    count = host(patterns, ks, texts, 1, capacity=0)[1]
+    assert count == n and count > ZERO_CAP
+    pat_tok, pat_off = csr(patterns)
+    txt_tok, txt_off = csr(texts)
+    buf = torch.full((count + 16, 5), -7, dtype=torch.int32, device="cuda")
+    cnt = torch.full((1,), -7, dtype=torch.int64, device="cuda")
+    ops.text_search_into(torch.from_numpy(pat_tok).cuda(), pat_off, ks, torch.from_numpy(txt_tok).cuda(), txt_off, 1, buf[:count], cnt)
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert int(cnt.item()) == count
+    rows = got[:count]
+    assert not rows[:, 0].any() and not rows[:, 1].any() and not rows[:, 4].any()        # pattern 0 in text 0 at distance 0
+    assert np.array_equal(rows[:, 2], rows[:, 3] - 1)                                      # start == end - 1 throughout
+    assert np.array_equal(np.sort(rows[:, 3]), np.arange(1, n + 1, dtype=np.int32))        # every end once: true hits, all distinct
+    assert (got[count:] == -7).all()
+
+
+def test_more_patterns_than_grid_rows():
+    """The first test in which a workgroup of ts_scan_kernel handles a second pattern (q += gridDim.y): 65 539 patterns against a
+    grid of at most 65 535 rows.  The workgroup then loads another mask row over the one in LDS, between the two barriers at the
+    loop's head.  The four patterns of the second trip are copies of text[10:12] and of the two tokens around the cut at L of
+    both texts."""
+    L = seg()
+    Q = 65539
+    assert Q > SCAN_ROWS
+    rng = np.random.default_rng(340)
+    v = 16
+    texts = [rng.integers(0, v, L + 6).astype(np.int32), rng.integers(0, v, L + 9).astype(np.int32)]
+    two = rng.integers(0, v, (Q, 2)).astype(np.int32)
+    patterns = list(two)
+    ks = [0] * Q
+    for q in (7, 30000, SCAN_ROWS - 1):                       # a few of three tokens within one error
+        patterns[q], ks[q] = rng.integers(0, v, 3).astype(np.int32), 1
+    known = []
+    for j, (t, s) in enumerate(((0, 10), (0, L - 1), (1, 10), (1, L - 1))):
+        patterns[SCAN_ROWS + j] = texts[t][s:s + 2].copy()
+        known.append([SCAN_ROWS + j, t, s, s + 2, 0])
+    assert SCAN_ROWS + 3 == Q - 1
+    want = same_as_host(patterns, ks, texts, v)
+    rows = want.tolist()
+    assert all(h in rows for h in known)
+    assert 10000 <= len(want) <= 60000
+    assert (want[:, 0] >= SCAN_ROWS).sum() >= 4 and len(np.unique(want[:, 0])) > 10000
 
 
 def test_no_patterns_no_texts_and_empty_texts_only():

@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_word_spotting_cpu import EPS, bound, full_gate, random_words, same_bits, yard_all, yard_topk, yard_unit
+from test_word_spotting_cpu import (EPS, bound, full_gate, random_words, same_bits, spot_in_blocks_and_in_one, words_for_blocks, yard_all,
+                                    yard_topk, yard_unit)
 
 pytestmark = pytest.mark.gpu
 
@@ -61,11 +62,19 @@ def nan_behind(feat, lengths):
     return feat
 
 
+def yard_sliced(qu, ql, lo, hi, cu, cl, dtype=np.float64, words=256):
+    """yard_all over the corpus in slices of `words` words, so that its [Q, n, T, T] table stays small; a pair's value does not
+    depend on the slice it is in"""
+    if len(cl) <= words:
+        return yard_all(qu, ql, lo, hi, cu, cl, dtype)
+    return np.concatenate([yard_all(qu, ql, lo, hi, cu[s:s + words], cl[s:s + words], dtype) for s in range(0, len(cl), words)], axis=1)
+
+
 def check_against_yardstick(fq, ql, lo, hi, fc, cl, what):
     H = fq.shape[2]
     got = device_from_raw(fq, ql, lo, hi, fc, cl)
-    want = yard_all(yard_unit(fq, ql), ql, lo, hi, yard_unit(fc, cl), cl)
-    f32 = yard_all(yard_unit(fq, ql, np.float32), ql, lo, hi, yard_unit(fc, cl, np.float32), cl, np.float32)
+    want = yard_sliced(yard_unit(fq, ql), ql, lo, hi, yard_unit(fc, cl), cl)
+    f32 = yard_sliced(yard_unit(fq, ql, np.float32), ql, lo, hi, yard_unit(fc, cl, np.float32), cl, np.float32)
     assert np.array_equal(np.isinf(got), np.isinf(want)), what
     assert not np.isnan(got).any(), what
     fin = np.isfinite(want)
@@ -197,6 +206,147 @@ def test_dtw_gate_and_identities(cuda):
     assert e.shape == (2, 0)
 
 
+# ------------------------------------------------------------------------------------------------ launch geometry
+# msocr_dtw_distances sizes its grid from the CU count: tiles of 4 words by `rows` query rows, about four workgroups per CU, and a
+# workgroup walks the queries q = blockIdx.y, blockIdx.y + rows, ..  At the sizes above rows = Q, one query per workgroup.  The tests
+# below read the CU count, restate the host's formula and assert the geometry they are there for, so on a part with another CU
+# count they either still enter their path or fail and say so.
+def cu_count():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
+def grid_rows(Q, N, cu):
+    """gridDim.y of ws_dtw_kernel as msocr_dtw_distances sets it"""
+    tiles = -(-N // tile())
+    return max(1, min(Q, 65535, -(-4 * cu // tiles)))
+
+
+def check_rows_alone(fq, ql, lo, hi, fc, cl, got, what):
+    """Row q of the batched result against a call that holds query q alone (its workgroups then handle it first, on a fresh LDS
+    tile and fresh wavefront registers): nothing in a pair's arithmetic depends on the query its workgroup handled before, so the
+    two agree bit for bit."""
+    from manuscript_ocr_amd import ops
+    qlen, clen, lo_d, hi_d = dev(ql, np.int32), dev(cl, np.int32), dev(lo, np.int32), dev(hi, np.int32)
+    uq, uc = ops.frame_normalize(dev(fq), qlen), ops.frame_normalize(dev(fc), clen)
+    alone = torch.cat([ops.dtw_distances(uq[q:q + 1], qlen[q:q + 1], lo_d[q:q + 1], hi_d[q:q + 1], uc, clen) for q in range(len(ql))])
+    torch.cuda.synchronize()
+    alone = alone.cpu().numpy()
+    bad = np.argwhere(alone.view(np.uint32) != got.view(np.uint32))
+    assert len(bad) == 0, (what, len(bad), bad[:8].tolist(), [(float(got[q, n]), float(alone[q, n])) for q, n in bad[:8]])
+
+
+def test_dtw_one_grid_row_walks_all_queries(cuda):
+    """rows = 1, the geometry of any index of real size: the first test in which a workgroup of ws_dtw_kernel takes a second trip of
+    `for (q = blockIdx.y; q < Q; q += gridDim.y)`, so the first to reuse a wave's LDS cost tile for the next query (the
+    ws_wave_lds_order() at the loop's head) and to reset d1 / up_prev between queries.  Query lengths T, 1, T - 1, 2, T: a short
+    query follows a long one on the same tile, whose cells outside Lq x Ln are the long one's.  The gates skip pairs between
+    computed ones (the `continue` arm leaves the tile as it was).  16 cu words of ragged lengths, NaN behind every length."""
+    cu = cu_count()
+    T, H, Q = 8, 64, 5
+    N = 16 * cu
+    assert grid_rows(Q, N, cu) == 1
+    rng = np.random.default_rng(61)
+    fq, ql = random_words(rng, Q, T, H, [T, 1, T - 1, 2, T])
+    fc, cl = random_words(rng, N, T, H, (list(range(1, T + 1)) + list(rng.integers(1, T + 1, N)))[:N])
+    nan_behind(fq, ql), nan_behind(fc, cl)
+    lo, hi = np.array([1, 1, 4, 1, 3], dtype=np.int32), np.array([T, 4, T, 2, T], dtype=np.int32)
+    got, _ = check_against_yardstick(fq, ql, lo, hi, fc, cl, f"rows 1: Q {Q} N {N} T {T} H {H}")
+    for n in (2, 5, N - 1):      # words of 3 and of 6 frames: skipped pairs between computed ones
+        L = int(cl[n])
+        assert np.isfinite(got[:, n]).tolist() == [lo[q] <= L <= hi[q] for q in range(Q)]
+    assert np.isfinite(got[:, 2]).tolist() == [True, True, False, False, True]
+    assert np.isfinite(got[:, 5]).tolist() == [True, False, True, False, True]
+    check_rows_alone(fq, ql, lo, hi, fc, cl, got, "rows 1")
+
+
+@pytest.mark.parametrize("T,H", [(33, 256), (64, 64)])
+def test_dtw_a_few_queries_per_workgroup(cuda, T, H):
+    """1 < rows < Q: a workgroup of ws_dtw_kernel handles the queries blockIdx.y, blockIdx.y + rows, ..: the stride of the query
+    loop is neither 1 nor Q.  At (33, 256) the tile's pitch is T + 1, at (64, 64) it is T and all 64 lanes are rows of the
+    wavefront; 4 cu + 3 words, so the last tile is partial.  The reuse of the tile and of the wavefront registers as in the test
+    above, at two blocks of the cost tile per side."""
+    cu = cu_count()
+    Q, N = 9, 4 * cu + 3
+    rows = grid_rows(Q, N, cu)
+    assert 1 < rows < Q, (rows, cu)
+    rng = np.random.default_rng(62 + T)
+    fq, ql = random_words(rng, Q, T, H, [T, 1, T - 1, 2, T, T // 2 + 1, 5, T // 2, 9])
+    fc, cl = random_words(rng, N, T, H)
+    cl[:4] = [T, 1, T - 1, 2]
+    cl[-1] = T
+    nan_behind(fq, ql), nan_behind(fc, cl)
+    lo, hi = np.maximum(ql // 2, 1).astype(np.int32), np.minimum(ql * 2, T).astype(np.int32)
+    lo[4], hi[4] = 1, T
+    got, _ = check_against_yardstick(fq, ql, lo, hi, fc, cl, f"rows {rows}: Q {Q} N {N} T {T} H {H}")
+    assert np.isinf(got).any() and np.isfinite(got[4]).all()
+    check_rows_alone(fq, ql, lo, hi, fc, cl, got, f"rows {rows} T {T}")
+
+
+def test_dtw_many_queries_one_partial_tile(cuda):
+    """rows < Q with a single tile of three words: the fourth wave of every workgroup returns before the query loop while the other
+    three take two trips of it (the kernel has no block-wide barrier for it to miss)."""
+    cu = cu_count()
+    T, H, N = 2, 64, 3
+    Q = 4 * cu + 5
+    rows = grid_rows(Q, N, cu)
+    assert rows < Q, (rows, cu)
+    rng = np.random.default_rng(63)
+    fq, ql = random_words(rng, Q, T, H)
+    fc, cl = random_words(rng, N, T, H, [2, 1, 2])
+    nan_behind(fq, ql), nan_behind(fc, cl)
+    lo = np.ones(Q, dtype=np.int32)
+    hi = np.where(np.arange(Q) % 7 == 3, 1, T).astype(np.int32)
+    got, _ = check_against_yardstick(fq, ql, lo, hi, fc, cl, f"rows {rows}: Q {Q} N {N} T {T} H {H}")
+    assert np.isfinite(got[:, 1]).all() and np.array_equal(np.isfinite(got[:, 0]), hi == T)
+
+
+def test_frame_normalize_beyond_one_trip_of_the_grid(cuda):
+    """The first test in which ws_normalize_kernel takes a second trip of its grid-stride loop (f += stride): the grid is capped at
+    32 cu workgroups of 4 frames, and N T frames lie above 128 cu.  Ragged lengths with 0 and T among them, NaN behind them, and a
+    zero frame, non-finite frames and overflowing frames among the words behind frame 128 cu: the second trip sees the zero rule
+    and the frames behind a length too.  The asserts are those of test_frame_normalize."""
+    from manuscript_ocr_amd import ops
+    cu = cu_count()
+    T, H = 7, 64
+    first = -(-128 * cu // T)            # the first word whose frames all lie in the second trip
+    N = first + 5
+    assert N * T > 128 * cu and first * T >= 128 * cu
+    rng = np.random.default_rng(64)
+    feat, lengths = random_words(rng, N, T, H, rng.integers(0, T + 1, N))
+    lengths[:3] = [T, 0, 3]
+    lengths[first:] = [T, T, 0, 4, T]
+    special = []
+    for w in (0, first):
+        feat[w, 1] = 0.0
+        feat[w, 2, 7] = np.nan
+        feat[w, 3, H - 1] = np.inf
+        feat[w, 4] = 1e30
+        feat[w, 5] = 1e-30
+        feat[w + (N - 1 - first if w else 2), 1] *= 1e18      # words of T and of 3 frames: finite, far from 1
+        special += [(w, t) for t in (1, 2, 3, 4, 5)]
+    feat[first + 1, 6] *= 1e-18
+    nan_behind(feat, lengths)
+    unit = ops.frame_normalize(dev(feat), dev(lengths)).cpu().numpy()
+    assert np.isfinite(unit).all()
+    for n, t in special:
+        assert not unit[n, t].any()
+    behind = np.arange(T)[None, :] >= lengths[:, None]
+    assert not unit[behind].any()
+    want = yard_unit(feat, lengths)
+    nz = np.abs(want).sum(axis=2) > 0
+    assert np.array_equal(nz, np.abs(unit).sum(axis=2) > 0)
+    assert nz[first:].sum() == 3 * T - 5 + 4 and nz[first + 4, 1] and nz[first + 1, 6]
+    norm = np.sqrt((unit.astype(np.float64) ** 2).sum(axis=2))
+    err = np.abs(unit - want).max()
+    print(f"second trip, N {N} T {T} H {H}: | ||u|| - 1 | max {np.abs(norm[nz] - 1.0).max():.3e}, |u - yardstick| max {err:.3e}, "
+          f"bound {(H + 4) * EPS:.3e}, worst err/bound {err / ((H + 4) * EPS):.3f}")
+    assert np.abs(norm[nz] - 1.0).max() <= (H + 4) * EPS
+    assert err <= (H + 4) * EPS
+    host = ops.frame_normalize_host(feat, lengths)
+    print(f"second trip: device against the host twin {np.abs(unit - host).max():.3e}, bound {2 * EPS:.3e}")
+    assert np.abs(unit - host).max() <= 2 * EPS
+
+
 # ------------------------------------------------------------------------------------------------ msocr_topk_smallest
 def same_as_host_topk(dist, k):
     from manuscript_ocr_amd import ops
@@ -271,6 +421,25 @@ def test_embed(cuda, rec):
     assert one.shape == (1, T, 256) and l1.tolist() == [lengths[1]]
     none, l0 = rec.embed([])
     assert none.shape[0] == 0 and len(l0) == 0
+
+
+def test_word_index_in_several_blocks_on_the_device(cuda, monkeypatch):
+    """The device route of an index and a query set beyond one native call: the first test to enter the `else` arm of
+    WordIndex.spot_features, which fills one [Q, N] array from a launch per (query piece, block), here 2 x 5, over blocks that
+    WordIndex._pack joined with torch.cat across the pieces' edges.  The same hits as the index in one block, distances bit for
+    bit (tests/test_word_spotting_cpu.py holds the host route to the same), and the distances within `bound` of the yardstick."""
+    everything = spot_in_blocks_and_in_one(monkeypatch, "cuda")
+    feat, lens, _ids, _texts, fq, ql = words_for_blocks()
+    T, H = feat.shape[1:]
+    want = yard_all(yard_unit(fq, ql), ql, *full_gate(len(ql), T), yard_unit(feat, lens), lens)
+    worst = 0.0
+    for q, hits in enumerate(everything):
+        assert [h.distance for h in hits] == sorted(h.distance for h in hits)
+        for h in hits:
+            lim = bound(H, ql[q], lens[h.word])
+            worst = max(worst, abs(h.distance - want[q, h.word]) / lim)
+            assert abs(h.distance - want[q, h.word]) <= lim
+    print(f"index in blocks of 5, 5, 5, 5, 3: worst err/bound {worst:.3f}")
 
 
 @pytest.mark.parametrize("rectify", [False, True])

@@ -435,6 +435,84 @@ def test_word_index_from_features_and_spot():
     assert index.spot([]) == []
 
 
+def words_for_blocks():
+    """23 words of T = 6, H = 64 and 7 queries.  Word 17 is word 3 again and query 2 is the same frames, so that its two nearest
+    words tie bit for bit; with five words to a block they lie in blocks 0 and 3."""
+    rng = np.random.default_rng(9)
+    T, H = 6, 64
+    feat, lens = random_words(rng, 23, T, H)
+    feat[17], lens[17] = feat[3], lens[3]
+    ids = [(n // 10, n % 2, n) for n in range(23)]
+    texts = [f"w{n}" if n % 3 else None for n in range(23)]
+    fq, ql = random_words(rng, 7, T, H, [6, 1, 3, 5, 2, 6, 4])
+    fq[2], ql[2] = feat[3], lens[3]
+    return feat, lens, ids, texts, fq, ql
+
+
+def hit_rows(per_query):
+    """what a caller sees of the hits, the distance as its f32 bits"""
+    return [[(h.query, h.page, h.block, h.word, h.rank, h.text, np.float32(h.distance).tobytes()) for h in hits] for hits in per_query]
+
+
+def spot_in_blocks_and_in_one(monkeypatch, device):
+    """The words of `words_for_blocks` enter an index in pieces of 3, 9 and 11, once under the default limit of a native call (one
+    block, one call) and once with room for five words per call: blocks of 5, 5, 5, 5, 3, joined from the pieces across their
+    edges, and the 7 queries cut into 5 + 2.  Both indexes answer the same questions, by frames and by reference (a word of the last
+    block, both tied words), and must give the same hits: ids, ranks, texts, and distances bit for bit.
+    -> the hits of the frame queries without a length gate, k = 23, from the index in blocks"""
+    from manuscript_ocr_amd import WordIndex, _spotting
+    feat, lens, ids, texts, fq, ql = words_for_blocks()
+    T, H = feat.shape[1:]
+
+    def build():
+        index, at = WordIndex(None, device=device), 0
+        for n in (3, 9, 11):
+            index.add_features(feat[at:at + n], lens[at:at + n], ids[at:at + n], texts[at:at + n])
+            at += n
+        return index
+
+    refs = [ids[21], ids[3], ids[17], ids[0], ids[22], ids[20]]
+
+    def ask(index):
+        return [index.spot_features(fq, ql, k=23, max_length_ratio=None), index.spot_features(fq, ql, k=4), index.spot(refs, k=6),
+                index.spot(refs + [ids[9]], k=256, max_length_ratio=1.5)]
+
+    one = build()
+    want = ask(one)
+    assert [int(u.shape[0]) for u, _ in one._blocks] == [23]
+    monkeypatch.setattr(_spotting, "_LIMIT", 5 * T * H)
+    cut = build()
+    got = ask(cut)
+    assert [int(u.shape[0]) for u, _ in cut._blocks] == [5, 5, 5, 5, 3] and len(cut) == 23
+    assert [int(l.shape[0]) for _, l in cut._blocks] == [5, 5, 5, 5, 3]
+    for g, w in zip(got, want):
+        assert hit_rows(g) == hit_rows(w)
+    everything = got[0]
+    assert all(len(hits) == 23 for hits in everything)                       # no gate: every word once, whichever block holds it
+    assert all(sorted(h.word for h in hits) == list(range(23)) for hits in everything)
+    # the tie across the block edge: the word that entered first wins, from the frames and from either reference
+    for hits in (everything[2], got[2][1], got[2][2]):
+        assert [(h.word, h.rank) for h in hits[:2]] == [(3, 0), (17, 1)] and hits[0].distance == hits[1].distance
+        assert abs(hits[0].distance) <= bound(H, lens[3], lens[3]) < 0.01 < hits[2].distance
+    # a reference into the last block (frames_of walks the blocks) finds itself
+    for q, n in ((0, 21), (4, 22), (5, 20)):
+        assert got[2][q][0].word == n and abs(got[2][q][0].distance) <= bound(H, lens[n], lens[n])
+    return everything
+
+
+def test_word_index_in_several_blocks(monkeypatch):
+    """The host route of an index and a query set beyond one native call: the first test in which
+    WordIndex._pack begins a second block and joins pieces across block edges, in which frames_of walks past the first block, and in
+    which spot_features joins the [Q', n] parts of several calls, here 2 x 5, into one [Q, N] array."""
+    everything = spot_in_blocks_and_in_one(monkeypatch, None)
+    feat, lens, _ids, _texts, fq, ql = words_for_blocks()
+    want = yard_all(yard_unit(fq, ql), ql, *full_gate(7, 6), yard_unit(feat, lens), lens)
+    for q, hits in enumerate(everything):
+        assert [h.distance for h in hits] == sorted(h.distance for h in hits)
+        for h in hits:
+            assert abs(h.distance - want[q, h.word]) <= bound(64, ql[q], lens[h.word])
+
+
 def test_empty_index_and_exports():
     import manuscript_ocr_amd
     from manuscript_ocr_amd import Pipeline, WordIndex

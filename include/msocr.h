@@ -712,6 +712,51 @@ int msocr_text_search_host(const int32_t* pat_tok_host, const int32_t* pat_off_h
                            int64_t capacity, int64_t* count_out);
 int64_t msocr_text_search_select_host(msocr_search_hit* hits, int64_t n);
 
+/* The same search under confusion-weighted costs (csrc/text_search_weighted.hip, csrc/text_search_weighted.h):
+ * the semi-global form of the weighted table of msocr_lexicon_nearest_weighted, in exact integers.  Everything not said here is the
+ * contract of msocr_text_search(_host): the CSR inputs, which arrays are host memory, the record, the canonical order, the capacity
+ * and count protocol, Q == 0 / T == 0, and msocr_text_search_select_host on the read-back records.
+ * Direction: the TEXT is the recognised side, the PATTERN the true word (msocr_edit_costs' own direction).
+ * Classes: tok_class [v] int32 (device memory; host memory for the twin) gives the cost class in [0, costs->V) of corpus token c, any
+ *   other value (-1 by convention) where c has none.  cls(t) = tok_class[t] for t in [0, v) if that lies in [0, V), else none.
+ *   w_sub(t, p), reading text token t as pattern token p: 0 if t == p and both lie in [0, v) (equal corpus characters match even
+ *     where the charset lacks them); else sub[cls(t) * V + cls(p)] if both have a class (two tokens of one class cost the diagonal);
+ *     else `unknown`.  A token outside [0, v), on either side, matches nothing, itself included.
+ *   w_del(t) = del[cls(t)] or `unknown`: dropping a text token.  w_ins(p) = ins[cls(p)] or `unknown`: supplying a pattern token.
+ * Table: D[0][j] = 0; D[i][0] = the sum of w_ins over a[0..i); D[i][j] = min(D[i-1][j-1] + w_sub(b[j-1], a[i-1]),
+ *   D[i][j-1] + w_del(b[j-1]), D[i-1][j] + w_ins(a[i-1])).
+ * Hits: every end j >= 1 with D[m][j] <= k' = min(k_q, D[m][0] - 1), so the empty substring never matches; k_q = max_dist[q] >= 0
+ *   is in cost units.  distance = D[m][j]; start = the LARGEST s whose weighted global distance between the pattern and b[s .. j)
+ *   equals it: the shortest substring that attains the score, the tie rule of the unit search.
+ * Window: W_q = m_q + k_q / dmin tokens, dmin = min(costs->min_del, costs->unknown), must not exceed MSOCR_SEARCH_W_MAX_WINDOW: an
+ *   alignment of cost <= k drops at most k / dmin text tokens, so it spans at most W_q of them, and the device scans a segment from
+ *   that far before it (from m_q + k' / dmin, which is no more).  The check takes k_q as given, since D[m][0] is device data.  A
+ *   min_del above the true minimum makes the device route miss hits; it causes no out-of-bounds read.
+ * With every cost 1 (and unknown 1) the records are those of msocr_text_search on the same arrays, whether the tokens have a class
+ *   or not, as long as no two tokens share one (those would match at the diagonal's 0).
+ * workspace (device route): 8-byte aligned, at least the ws_bytes query's 8 (T + 1) + 4 (T + 1) + 4 (Q + 1) + 4 Q bytes rounded up
+ *   to a multiple of 8 (the uploaded heads; there are no mask tables).
+ * MSOCR_E_ARG before any launch, beyond the cases of msocr_text_search: k_q < 0 (k_q >= m_q is allowed), W_q above the cap, v
+ *   outside 1..MSOCR_SEARCH_W_MAX_ALPHABET, tok_class or costs NULL, a null table, costs->V outside 1..512, unknown, min_ins or
+ *   min_del outside 1..255.  The device entry point cannot validate the tables or the classes (msocr_edit_costs_check_host does
+ *   the former): whatever they hold, no index leaves them.
+ * The device entry point uploads the heads and waits for that copy on `stream`; two launches follow (clear the count, scan), which
+ *   the host does not wait for.  A workgroup builds its pattern's cost profile, (v + 1) rows of 72 bytes, in dynamic LDS (at most
+ *   57 KB); a lane keeps its column in 64 registers, the start packed under the cost.  Not capturable.  Measured:
+ *   profiles/text_search_weighted.txt. */
+#define MSOCR_SEARCH_W_MAX_ALPHABET 768
+#define MSOCR_SEARCH_W_MAX_WINDOW 256
+int64_t msocr_text_search_weighted_ws_bytes(const int32_t* pat_off_host, const int32_t* max_dist_host, int Q, const int32_t* txt_off_host,
+                                            int T, int v, const msocr_edit_costs* costs);
+int msocr_text_search_weighted(const int32_t* pat_tok, const int32_t* pat_off_host, const int32_t* max_dist_host, int Q,
+                               const int32_t* txt_tok, const int32_t* txt_off_host, int T, int v, const int32_t* tok_class,
+                               const msocr_edit_costs* costs, msocr_search_hit* hits_out, int64_t capacity, int64_t* count_out,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int msocr_text_search_weighted_host(const int32_t* pat_tok_host, const int32_t* pat_off_host, const int32_t* max_dist_host, int Q,
+                                    const int32_t* txt_tok_host, const int32_t* txt_off_host, int T, int v,
+                                    const int32_t* tok_class_host, const msocr_edit_costs* costs_host, msocr_search_hit* hits_out,
+                                    int64_t capacity, int64_t* count_out);
+
 /* ---- word spotting: query-by-example search over encoder features, Q query words against N indexed words by a dynamic-time-warping
  * distance between their frame sequences (an extension beyond the reference's inference code: TRBA.embed, WordIndex,
  * Pipeline.index_words / spot; csrc/word_spotting.hip, csrc/word_spotting.h) ----

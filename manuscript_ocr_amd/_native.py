@@ -148,6 +148,11 @@ _SIGS = {
     "msocr_text_search": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "msocr_text_search_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "msocr_text_search_select_host": (c_i64, [c_vp, c_i64]),
+    "msocr_text_search_weighted_ws_bytes": (c_i64, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, ctypes.POINTER(EditCostsTable)]),
+    "msocr_text_search_weighted": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, ctypes.POINTER(EditCostsTable), c_vp,
+                                           c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "msocr_text_search_weighted_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, ctypes.POINTER(EditCostsTable),
+                                                c_vp, c_i64, c_vp]),
     "msocr_frame_normalize": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "msocr_frame_normalize_host": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "msocr_dtw_distances": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),

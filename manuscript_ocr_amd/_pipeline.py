@@ -1112,7 +1112,8 @@ class Pipeline:
         taken = {e["gt_index"] for e in extra.values()}
         return page, [g for g in range(len(gt_words)) if g not in taken]
 
-    def search(self, pages_or_images, queries, max_distance=None, max_error_rate=None, overlapping: bool = False, device=None):
+    def search(self, pages_or_images, queries, max_distance=None, max_error_rate=None, overlapping: bool = False, device=None,
+               costs=None):
         """Where do the queries occur in these pages, allowing for what the recogniser may have misread (this package's extension;
         DESIGN.md section 4.24)?  -> a list of detectors._types.SearchHit in canonical order (query, page, end).
 
@@ -1124,12 +1125,14 @@ class Pipeline:
         overlapping=True reports every end position within the bound instead of the occurrences.  device: None = the host twin; a
         device: msocr_text_search there, the same hits bit for bit.  No automatic switch between the two (Pages must be searchable
         without a GPU): 16 pages x 10 queries take 2.4 ms on one host core and 0.16 ms on the device with the corpus upload and the
-        read-back (profiles/text_search.txt), and for many searches of one collection a PageCorpus keeps it on the device."""
+        read-back (profiles/text_search.txt), and for many searches of one collection a PageCorpus keeps it on the device.
+        costs=EditCosts(...): the search under confusion-weighted costs (msocr_text_search_weighted): the
+        bounds and SearchHit.distance are then in cost units, as recognizers.TextCorpus.search says."""
         from ._search import PageCorpus
         from .detectors._types import Page
         pages = [p if isinstance(p, Page) else self.predict(p) for p in pages_or_images]
         return PageCorpus(pages, device=device).search(queries, max_distance=max_distance, max_error_rate=max_error_rate,
-                                                       overlapping=overlapping)
+                                                       overlapping=overlapping, costs=costs)
 
     def index_words(self, images, pages=None):
         """A WordIndex of the words of these pages, for word spotting by example (this package's extension; DESIGN.md section 4.25;

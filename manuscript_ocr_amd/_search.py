@@ -48,13 +48,15 @@ class PageCorpus:
         return out
 
     def search(self, queries: Sequence[str], max_distance: Union[None, int, Sequence[int]] = None,
-               max_error_rate: Optional[float] = None, overlapping: bool = False) -> List[SearchHit]:
+               max_error_rate: Optional[float] = None, overlapping: bool = False, costs=None) -> List[SearchHit]:
         """Occurrences of the queries in the pages, in canonical order (query, page, end).  A query is whitespace-normalised as the
-        pages' texts are (" ".join(q.split())), so it may span words, lines and blocks.  The bounds and `overlapping`: as for
-        recognizers.TextCorpus.search."""
+        pages' texts are (" ".join(q.split())), so it may span words, lines and blocks.  The bounds, `overlapping` and `costs` (an
+        EditCosts: bounds and distances in cost units; the space between words costs `unknown` to add or drop unless the charset
+        holds it): as for recognizers.TextCorpus.search."""
         queries = [" ".join(q.split()) for q in queries]
         out = []
-        for h in self.corpus.search(queries, max_distance=max_distance, max_error_rate=max_error_rate, overlapping=overlapping):
+        for h in self.corpus.search(queries, max_distance=max_distance, max_error_rate=max_error_rate, overlapping=overlapping,
+                                    costs=costs):
             out.append(SearchHit(page=h.text, query=h.pattern, query_text=queries[h.pattern], matched_text=self.texts[h.text][h.start:h.end],
                                  distance=h.distance, start=h.start, end=h.end, words=self.words_of(h.text, h.start, h.end)))
         return out

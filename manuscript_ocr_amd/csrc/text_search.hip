@@ -20,6 +20,7 @@
 
 #include "internal.h"
 #include "text_search.h"
+#include "text_search_kernels.h"
 
 namespace {
 
@@ -47,32 +48,11 @@ __global__ __launch_bounds__(64) void ts_masks_kernel(const int32_t* __restrict_
   atomicOr((unsigned long long*)(rows + v + c), 1ull << (m - 1 - i));
 }
 
-// the four tokens txt_tok[g .. g + 4): one 16-byte load where they lie inside [glo, ghi) (g is then 16-byte aligned: the caller
-// aligned it by the array's own address), else the elements that do, -1 for the others
-__device__ __forceinline__ int4 ts_load4(const int32_t* __restrict__ txt_tok, int64_t g, int64_t glo, int64_t ghi, bool want) {
-  int4 r = make_int4(-1, -1, -1, -1);
-  if (!want) return r;
-  if (g >= glo && g + 4 <= ghi) return *reinterpret_cast<const int4*>(txt_tok + g);
-  if (g + 0 >= glo && g + 0 < ghi) r.x = txt_tok[g + 0];
-  if (g + 1 >= glo && g + 1 < ghi) r.y = txt_tok[g + 1];
-  if (g + 2 >= glo && g + 2 < ghi) r.z = txt_tok[g + 2];
-  if (g + 3 >= glo && g + 3 < ghi) r.w = txt_tok[g + 3];
-  return r;
-}
-
-// every lane of the wave calls this; those with `hit` append one record each
+// every lane of the wave calls this; those with `hit` append one record each (the start is the start kernel's)
 __device__ __forceinline__ void ts_append(bool hit, int32_t q, int32_t t, int32_t end, int32_t dist, msocr_search_hit* __restrict__ hits,
                                           int64_t capacity, unsigned long long* __restrict__ count) {
-  const unsigned long long mask = __ballot(hit);
-  if (mask == 0ull) return;
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll((long long)mask) - 1;
-  unsigned long long base = 0ull;
-  if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(mask));
-  base = __shfl(base, leader, 64);
-  const unsigned long long slot = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-  if (hit && slot < (unsigned long long)capacity) {
-    msocr_search_hit* h = hits + slot;
+  msocr_search_hit* h = ts_append_slot(hit, hits, capacity, count);
+  if (h) {
     h->pattern = q;
     h->text = t;
     h->end = end;

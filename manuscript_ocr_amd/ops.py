@@ -1318,6 +1318,97 @@ def text_search_select(hits):
     return hits[:int(n)]
 
 
+# ------------------------------------------------------------------------------- text search under confusion-weighted costs
+SEARCH_W_MAX_ALPHABET = 768  # msocr.h MSOCR_SEARCH_W_MAX_ALPHABET
+SEARCH_W_MAX_WINDOW = 256    # msocr.h MSOCR_SEARCH_W_MAX_WINDOW: m + max_dist // min(min_del, unknown) of a pattern
+
+
+def text_search_weighted_workspace_bytes(pat_off, max_dist, txt_off, v, costs):
+    """costs: a recognizers.EditCosts; only its scalars are read"""
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    n = nat.lib().msocr_text_search_weighted_ws_bytes(pat_off.ctypes.data, max_dist.ctypes.data, Q, txt_off.ctypes.data, T, int(v),
+                                                      costs.struct(None))
+    nat.check(min(n, 0), "text_search_weighted_ws_bytes")
+    return int(n)
+
+
+def text_search_weighted_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, tok_class, costs, hits, count, workspace=None):
+    """One call of msocr_text_search_weighted (include/msocr.h, "The same search under confusion-weighted costs"): `text_search_into`
+    with max_dist in cost units under costs (a recognizers.EditCosts; the text is the recognised side, the pattern the true word).
+    tok_class: int32 device tensor [v], the cost class of corpus token c or -1.  hits, count and the workspace: as there."""
+    _need_cuda(pat_tok, txt_tok, tok_class, hits, count)
+    if pat_tok.dtype != torch.int32 or txt_tok.dtype != torch.int32 or pat_tok.dim() != 1 or txt_tok.dim() != 1:
+        raise TypeError("tokens are one-dimensional int32 tensors")
+    if tok_class.dtype != torch.int32 or tok_class.dim() != 1 or tok_class.numel() != int(v) or not tok_class.is_contiguous():
+        raise TypeError("tok_class is a dense int32 tensor [v]")
+    if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 5 or count.dtype != torch.int64 or count.numel() != 1:
+        raise TypeError("hits is int32 [capacity, 5], count is int64 [1]")
+    if not (pat_tok.is_contiguous() and txt_tok.is_contiguous() and hits.is_contiguous()):
+        raise ValueError("text_search_weighted takes dense tensors")
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    if (Q and int(pat_off[-1]) > pat_tok.numel()) or (T and int(txt_off[-1]) > txt_tok.numel()):
+        raise ValueError("offsets reach past the token tensors")
+    need = text_search_weighted_workspace_bytes(pat_off, max_dist, txt_off, v, costs)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=txt_tok.device)
+    # a tensor without elements has no address: the entry point wants one and then reads or writes nothing through it
+    ptr = [t.data_ptr() or workspace.data_ptr() for t in (pat_tok, txt_tok, hits)]
+    nat.check(nat.lib().msocr_text_search_weighted(ptr[0], pat_off.ctypes.data, max_dist.ctypes.data, Q, ptr[1], txt_off.ctypes.data, T,
+                                                   int(v), tok_class.data_ptr(), costs.struct(txt_tok.device), ptr[2], hits.shape[0],
+                                                   count.data_ptr(), workspace.data_ptr(),
+                                                   workspace.numel() * workspace.element_size(), _stream()), "text_search_weighted")
+
+
+def text_search_weighted(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, tok_class, costs, capacity=SEARCH_CAPACITY):
+    """All hits of `text_search_weighted_into`, read back: int32 numpy [count, 5] in no particular order; the two-pass overflow
+    protocol of `text_search`."""
+    capacity = int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity >= 0")
+    dev = txt_tok.device
+    with torch.cuda.device(dev):
+        count = torch.zeros((1,), dtype=torch.int64, device=dev)
+        hits = torch.empty((capacity, 5), dtype=torch.int32, device=dev)
+        text_search_weighted_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, tok_class, costs, hits, count)
+        n = int(count.item())
+        if n > capacity:
+            hits = torch.empty((n, 5), dtype=torch.int32, device=dev)
+            text_search_weighted_into(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, tok_class, costs, hits, count)
+            if int(count.item()) != n:
+                raise nat.NativeError("text_search_weighted: the second pass counted other hits than the first")
+        return hits[:n].cpu().numpy()
+
+
+def text_search_weighted_host(pat_tok, pat_off, max_dist, txt_tok, txt_off, v, tok_class, costs, capacity=None):
+    """The CPU twin of `text_search_weighted` (msocr_text_search_weighted_host) on numpy arrays -> (hits in canonical order, count).
+    capacity None: room for every hit (a first call counts them)."""
+    pat_tok = np.ascontiguousarray(pat_tok, dtype=np.int32).reshape(-1)
+    txt_tok = np.ascontiguousarray(txt_tok, dtype=np.int32).reshape(-1)
+    tok_class = np.ascontiguousarray(tok_class, dtype=np.int32).reshape(-1)
+    if tok_class.size != int(v):
+        raise ValueError("tok_class is [v]")
+    pat_off, max_dist, txt_off, Q, T = _ts_heads(pat_off, max_dist, txt_off)
+    if (Q and int(pat_off[-1]) > pat_tok.size) or (T and int(txt_off[-1]) > txt_tok.size):
+        raise ValueError("offsets reach past the token arrays")
+    pad = np.zeros(8, dtype=np.int32)  # an address for arrays without elements
+    count = np.zeros(1, dtype=np.int64)
+
+    def run(cap):
+        hits = np.empty((cap, 5), dtype=np.int32)
+        ptr = [x.ctypes.data if x.size else pad.ctypes.data for x in (pat_tok, txt_tok, hits, tok_class)]
+        nat.check(nat.lib().msocr_text_search_weighted_host(ptr[0], pat_off.ctypes.data, max_dist.ctypes.data, Q, ptr[1],
+                                                            txt_off.ctypes.data, T, int(v), ptr[3], costs.struct(None), ptr[2], cap,
+                                                            count.ctypes.data), "text_search_weighted_host")
+        return hits[:min(cap, int(count[0]))]
+
+    if capacity is None:
+        run(0)
+        capacity = int(count[0])
+    elif capacity < 0:
+        raise ValueError("capacity >= 0")
+    return run(int(capacity)), int(count[0])
+
+
 # ------------------------------------------------------------------------------------------- word spotting
 SPOT_MAX_T = 64    # msocr.h MSOCR_SPOT_MAX_T: frames of a sequence
 SPOT_MAX_H = 512   # msocr.h MSOCR_SPOT_MAX_H: elements of a frame, a multiple of 64

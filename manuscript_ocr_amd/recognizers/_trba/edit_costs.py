@@ -29,7 +29,8 @@ class EditCosts:
     msocr_edit_costs_check_host validates the tables once; a violation is a ValueError."""
 
     def __init__(self, sub, delete, insert, charset, unknown=None):
-        self.num_classes = max(_stoi(charset).values()) + 1
+        self.stoi = dict(_stoi(charset))  # symbol -> class: TextCorpus.search maps the corpus characters through it
+        self.num_classes = max(self.stoi.values()) + 1
         V = self.num_classes
         arrays = []
         for name, a, shape in (("sub", sub, (V, V)), ("delete", delete, (V,)), ("insert", insert, (V,))):

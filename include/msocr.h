@@ -778,6 +778,21 @@ int msocr_text_search_weighted_host(const int32_t* pat_tok_host, const int32_t* 
  *   order documented in the kernel), the table and the division in f32: | d - d_f64 | <= (H + 2 (Lq + Ln) + 16) 2^-24 for the
  *   same unit frames (DESIGN.md section 4.25 has the derivation).
  *   The host twin forms every product, sum and table entry in f64 and rounds to f32 once.
+ * Subsequence distance (msocr_dtw_subsequence): "which words CONTAIN this".  The same sequences, unit frames
+ *   and local cost; the query may start and end anywhere on the word's axis.  S(0, j) = c(0, j) for every j (a free start: row 0
+ *   takes no left step); S(i, j) = c(i, j) + min(S(i-1, j-1), S(i-1, j), S(i, j-1)) for i >= 1, absent neighbours +inf;
+ *   d = min_j S(Lq-1, j) / Lq.  Every cell carries the column at which its path left row 0: start(0, j) = j, otherwise the start of
+ *   the chosen predecessor; among equal predecessors the diagonal one wins, then the upper, then the left.  The end e is the
+ *   SMALLEST j that attains the minimum.  Per pair: dist [Q][N] f32 = d and span [Q][N][2] int32 = [start(Lq-1, e), e + 1), in word
+ *   frames.  Lq > Ln is legal (the path then takes vertical steps).  There is no slope constraint and no minimum span: a query may
+ *   collapse onto one word frame.  The length gate is msocr_dtw_distances' (same two arguments); a gated-out pair, and on the device
+ *   route a query or word length outside [1, T], gets d = +inf and span (-1, -1) and costs no arithmetic; the host twin refuses such
+ *   lengths, and len_lo > len_hi.  Arithmetic as for the distance: the device's table and division are f32,
+ *   | d - d_f64 | <= (3 H + 2 (Lq + Ln) + 16) 2^-24 (Lq + Ln) / Lq from the same raw frames (tests/test_gpu_word_spotting_partial.py
+ *   has the derivation); its span is a span whose best pinned path costs at most that much more than the f64 optimum (near-ties may
+ *   fall differently).  The host twin forms every product, sum and table entry in f64 and rounds d to f32 once.
+ *   The encoder's frames carry context (a BiLSTM), so a stem cut alone and the same stem inside a longer word need not embed alike:
+ *   what is defined and tested is the arithmetic, nothing about retrieval quality.
  * Selection (msocr_topk_smallest): per row of dist the k smallest FINITE values in ascending order, equal values (as floats:
  *   -0.0 == +0.0) by ascending index; +inf, -inf and NaN are never returned; unused slots hold index -1 and value +inf.  A value is
  *   copied as stored.  The host twin returns the same bits as the device.
@@ -786,8 +801,8 @@ int msocr_text_search_weighted_host(const int32_t* pat_tok_host, const int32_t* 
  *   pointer, is MSOCR_E_ARG before any launch.  Q == 0 or N == 0 launches nothing that reads features (the selection still fills its
  *   Q rows with -1 / +inf).
  * The device entry points take device pointers, allocate nothing, wait for nothing and launch one kernel each on `stream`; they
- *   are not meant for graph capture.  A workgroup of msocr_dtw_distances owns MSOCR_SPOT_TILE words.  Measured:
- *   profiles/word_spotting.txt. */
+ *   are not meant for graph capture.  A workgroup of msocr_dtw_distances or msocr_dtw_subsequence owns MSOCR_SPOT_TILE words.
+ *   Measured: profiles/word_spotting.txt, profiles/word_spotting_partial.txt. */
 #define MSOCR_SPOT_MAX_T 64
 #define MSOCR_SPOT_MAX_H 512
 #define MSOCR_SPOT_MAX_K 256
@@ -798,6 +813,10 @@ int msocr_dtw_distances(const float* q_unit, const int32_t* q_len, const int32_t
                         const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, void* stream);
 int msocr_dtw_distances_host(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
                              const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist);
+int msocr_dtw_subsequence(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                          const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, int32_t* span, void* stream);
+int msocr_dtw_subsequence_host(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                               const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, int32_t* span);
 int msocr_topk_smallest(const float* dist, int Q, int N, int k, int32_t* idx, float* val, void* stream);
 int msocr_topk_smallest_host(const float* dist, int Q, int N, int k, int32_t* idx, float* val);
 

@@ -1149,10 +1149,11 @@ class Pipeline:
         index.add_pages(images, pages)
         return index
 
-    def spot(self, index, queries, k: int = 10, max_length_ratio: Optional[float] = 2.0):
+    def spot(self, index, queries, k: int = 10, max_length_ratio: Optional[float] = 2.0, partial: bool = False):
         """WordIndex.spot with one more kind of query: (image, polygon), a region of a page, which is cut as this pipeline cuts a
         word (min_text_size, rectify_crops) and embedded.  Word images and (page, block, word) references pass through.  -> one list
-        of detectors._types.SpotHit per query."""
+        of detectors._types.SpotHit per query.  partial=True: "which words contain this", e.g. a boxed stem; the hits are
+        PartSpotHit with the matched stretch of frames (WordIndex.spot)."""
         from ._spotting import WordIndex
         resolved = []
         for q in queries:
@@ -1161,7 +1162,7 @@ class Pipeline:
                 cutter.min_text_size, cutter.rectify_crops = self.min_text_size, bool(self.rectify_crops)
                 q = cutter.frames_of_polygon(q[0], q[1])
             resolved.append(q)
-        return index.spot(resolved, k=k, max_length_ratio=max_length_ratio)
+        return index.spot(resolved, k=k, max_length_ratio=max_length_ratio, partial=partial)
 
     def process_batch(self, images: List[Union[str, np.ndarray, Image.Image]], recognize_text: bool = True, vis: bool = False,
                       profile: bool = False):

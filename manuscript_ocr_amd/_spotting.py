@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import ops
-from .detectors._types import SpotHit
+from .detectors._types import PartSpotHit, SpotHit
 
 _LIMIT = (1 << 31) - 1  # elements of one feature array of a native call (msocr.h: N T H < 2^31)
 
@@ -273,7 +273,7 @@ class WordIndex:
                 out[s] = _Frames(unit[k], int(lens[k]))
         return out
 
-    def spot(self, queries: Sequence, k: int = 10, max_length_ratio: Optional[float] = 2.0) -> List[List[SpotHit]]:
+    def spot(self, queries: Sequence, k: int = 10, max_length_ratio: Optional[float] = 2.0, partial: bool = False) -> List[List[SpotHit]]:
         """The k nearest indexed words of every query -> one list of SpotHit per query, nearest first.
 
         A query is a word image (an array, a path or a PIL image; it is embedded as TRBA.embed embeds it) or a reference
@@ -281,7 +281,14 @@ class WordIndex:
         word comes back at rank 0 with a distance of about 0 (inside the distance's own bound, (3 H + 4 L + 16) 2^-24 for L frames:
         the unit frames' rounding), unless an identical word entered the index before it.  k is 1 .. 256.  max_length_ratio r gates the pairs by length, before any
         arithmetic: a query of L frames is compared with words of ceil(L / r) .. floor(L r) frames only, None compares it with all.
-        The default 2.0 is a placeholder, not a tuned value.  Fewer than k hits come back where fewer words pass the gate."""
+        The default 2.0 is a placeholder, not a tuned value.  Fewer than k hits come back where fewer words pass the gate.
+
+        partial=True asks "which words CONTAIN this" (DESIGN.md section 4.28): the query may start and end anywhere inside a word
+        (msocr_dtw_subsequence), the distance is the path's cost divided by the query's length alone, and the hits are PartSpotHit:
+        a SpotHit with the stretch of the word's frames that was matched (`frame_start`, `frame_end`, `fraction`).  The gate is then
+        ceil(L / r) .. T: a word may be longer than the query by any amount, but not much shorter; r is the same placeholder.
+        Nothing constrains the stretch (a query may collapse onto one frame), and the encoder's frames carry context, so a stem cut
+        alone and the same stem inside a longer word need not embed alike: nothing about retrieval quality is claimed."""
         frames = self._resolve(list(queries))
         if not frames:
             return []
@@ -290,11 +297,13 @@ class WordIndex:
         else:
             import torch
             unit = torch.stack([f.unit for f in frames])
-        return self.spot_features(unit, [f.length for f in frames], k=k, max_length_ratio=max_length_ratio, normalized=True)
+        return self.spot_features(unit, [f.length for f in frames], k=k, max_length_ratio=max_length_ratio, normalized=True,
+                                  partial=partial)
 
-    def spot_features(self, features, lengths, k: int = 10, max_length_ratio: Optional[float] = 2.0, normalized: bool = False):
+    def spot_features(self, features, lengths, k: int = 10, max_length_ratio: Optional[float] = 2.0, normalized: bool = False,
+                      partial: bool = False):
         """`spot` for queries given as frames: features [Q, T, H] f32, lengths [Q] in [1, T]; they are normalised unless
-        `normalized` says they are unit frames already."""
+        `normalized` says they are unit frames already.  partial: as for `spot`."""
         k = int(k)
         if not 1 <= k <= ops.SPOT_MAX_K:
             raise ValueError(f"k must lie in 1 .. {ops.SPOT_MAX_K}, got {k}")
@@ -311,6 +320,8 @@ class WordIndex:
         lo, hi = length_bounds(lengths, max_length_ratio, self.T)
         self._pack()
         per_call = max(1, _LIMIT // (self.T * self.H))
+        if partial:
+            return self._spot_partial(features, lengths, lo, k, normalized, per_call)
         if self.device is None:
             unit = np.ascontiguousarray(features, dtype=np.float32)
             if not normalized:
@@ -350,5 +361,66 @@ class WordIndex:
                     break
                 page, block, word = self.ids[i]
                 hits.append(SpotHit(query=q, page=page, block=block, word=word, distance=d, rank=rank, text=self.texts[i]))
+            out.append(hits)
+        return out
+
+    def _spot_partial(self, features, lengths, lo, k, normalized, per_call):
+        """spot_features(partial=True) behind its checks: the subsequence distance under the gate [lo, T]; spans are joined over
+        blocks and query pieces exactly as the distances are, and the selection is the same one"""
+        Q = len(lengths)
+        hi = np.full(Q, self.T, dtype=np.int32)
+        if self.device is None:
+            unit = np.ascontiguousarray(features, dtype=np.float32)
+            if not normalized:
+                unit = ops.frame_normalize_host(unit, lengths)
+            parts = [ops.dtw_subsequence_host(unit[s:s + per_call], lengths[s:s + per_call], lo[s:s + per_call], hi[s:s + per_call], cu, cl)
+                     for s in range(0, Q, per_call) for cu, cl in self._blocks]
+            nb = len(self._blocks)
+            dist = np.concatenate([np.concatenate([d for d, _ in parts[r * nb:(r + 1) * nb]], axis=1) for r in range(len(parts) // nb)])
+            span = np.concatenate([np.concatenate([sp for _, sp in parts[r * nb:(r + 1) * nb]], axis=1) for r in range(len(parts) // nb)])
+            idx, val = ops.topk_smallest_host(dist, k)
+            word_len = np.concatenate([np.asarray(cl) for _, cl in self._blocks])
+        else:
+            import torch
+            with torch.cuda.device(self.device):
+                if not isinstance(features, torch.Tensor):
+                    features = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32))
+                unit = features.to(self.device, dtype=torch.float32).contiguous()
+                ql, lo_d, hi_d = (torch.from_numpy(a).to(self.device) for a in (lengths, lo, hi))
+                if not normalized:
+                    unit = ops.frame_normalize(unit, ql)
+                if len(self._blocks) == 1 and Q <= per_call:
+                    dist, span = ops.dtw_subsequence(unit, ql, lo_d, hi_d, *self._blocks[0])
+                else:
+                    dist = torch.empty((Q, len(self)), dtype=torch.float32, device=self.device)
+                    span = torch.empty((Q, len(self), 2), dtype=torch.int32, device=self.device)
+                    for s in range(0, Q, per_call):
+                        at = 0
+                        for cu, cl in self._blocks:
+                            n = int(cu.shape[0])
+                            d, sp = ops.dtw_subsequence(unit[s:s + per_call], ql[s:s + per_call], lo_d[s:s + per_call],
+                                                        hi_d[s:s + per_call], cu, cl)
+                            dist[s:s + per_call, at:at + n] = d
+                            span[s:s + per_call, at:at + n] = sp
+                            at += n
+                idx, val = ops.topk_smallest(dist, k)
+                # the spans and word lengths of the selected words only: [Q, k, 2] and [Q, k] leave the device
+                at = idx.clamp(min=0).long()
+                span = torch.gather(span, 1, at[:, :, None].expand(-1, -1, 2)).cpu().numpy()
+                word_len = torch.cat([cl for _, cl in self._blocks])[at].cpu().numpy()
+                idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        out = []
+        for q in range(Q):
+            hits = []
+            for rank, (i, d) in enumerate(zip(idx[q].tolist(), val[q].tolist())):
+                if i < 0:
+                    break
+                if self.device is None:
+                    (a, b), L = span[q, i].tolist(), int(word_len[i])
+                else:
+                    (a, b), L = span[q, rank].tolist(), int(word_len[q, rank])
+                page, block, word = self.ids[i]
+                hits.append(PartSpotHit(query=q, page=page, block=block, word=word, distance=d, rank=rank, text=self.texts[i],
+                                        frame_start=a, frame_end=b, fraction=(a / L, b / L)))
             out.append(hits)
         return out

@@ -1,10 +1,11 @@
 // word_spotting.h — word spotting by example: the dynamic-time-warping distance between sequences of unit frames, Q queries against
-// N indexed words, and the selection of the k nearest (include/msocr.h, "word spotting").  Host and device:
+// N indexed words, and the selection of the k nearest (include/msocr.h, "word spotting"; DESIGN.md sections 4.25, 4.28).  Host and device:
 // the kernels of word_spotting.hip share the argument checks, the frame rule and the ordering key below; the host twins
-// msocr_frame_normalize_host, msocr_dtw_distances_host and msocr_topk_smallest_host are ws_normalize_host, ws_dtw_host and
-// ws_topk_host; a plain C++ program feeds them garbage lengths, non-finite features and heap blocks of their exact size under the
-// address and undefined-behaviour sanitizers (tests/native/word_spotting_fuzz.cpp).  Whatever the length arrays hold, every index
-// formed here lies inside the arrays the caller described.
+// msocr_frame_normalize_host, msocr_dtw_distances_host, msocr_dtw_subsequence_host and msocr_topk_smallest_host are
+// ws_normalize_host, ws_dtw_host, ws_dtw_sub_host and ws_topk_host; plain C++ programs feed them garbage lengths, non-finite features
+// and heap blocks of their exact size under the address and undefined-behaviour sanitizers (tests/native/word_spotting_fuzz.cpp,
+// tests/native/word_spotting_partial_fuzz.cpp).  Whatever the length arrays hold, every index formed here lies inside the arrays the
+// caller described.
 #ifndef MSOCR_WORD_SPOTTING_H
 #define MSOCR_WORD_SPOTTING_H
 #include <float.h>
@@ -111,6 +112,68 @@ inline void ws_dtw_host(const float* q_unit, const int32_t* q_len, const int32_t
       if (Ln >= len_lo[q] && Ln <= len_hi[q])
         d = ws_dtw_pair_host(q_unit + (size_t)q * T * H, q_len[q], c_unit + (size_t)n * T * H, Ln, H, row.data());
       dist[(size_t)q * N + n] = d;
+    }
+}
+
+// ---- the subsequence form (msocr.h, "word spotting", "Subsequence distance"): the query may start and end
+// anywhere on the word's axis.
+// what msocr_dtw_subsequence and its host twin check alike before anything else (the device route adds the alignment of the frames)
+inline bool ws_sub_args_ok(const void* q_unit, const void* q_len, const void* len_lo, const void* len_hi, int Q, const void* c_unit,
+                           const void* c_len, int N, int T, int H, const void* dist, const void* span) {
+  if (!ws_shape_ok(Q, T, H) || !ws_shape_ok(N, T, H)) return false;
+  return q_unit && q_len && len_lo && len_hi && c_unit && c_len && dist && span;
+}
+
+// The definition in f64, as ws_dtw_pair_host forms it: S(0, j) = c(0, j) (a free start: row 0 takes no left step), S(i, j) = c(i, j) +
+// min(S(i-1, j-1), S(i-1, j), S(i, j-1)); every cell carries the column at which its path left row 0: among equal predecessors the
+// diagonal one wins, then the upper, then the left (strict < in that order).  The end is the smallest j that attains min_j
+// S(La-1, j).  a [La][H] is the query, b [Lb][H] the word; row and start are scratch of Lb entries each.
+// -> d = min / La rounded to f32 once; span[0..2) = [start, end + 1) in word frames.
+inline float ws_dtw_sub_pair_host(const float* a, int La, const float* b, int Lb, int H, double* row, int32_t* start, int32_t* span) {
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int i = 0; i < La; ++i) {
+    double diag = inf, left = inf;  // S(i-1, j-1) and S(i, j-1)
+    int32_t sdiag = -1, sleft = -1;
+    for (int j = 0; j < Lb; ++j) {
+      double dot = 0.0;
+      for (int k = 0; k < H; ++k) dot += (double)a[(size_t)i * H + k] * (double)b[(size_t)j * H + k];
+      const double up = i > 0 ? row[j] : inf;
+      const int32_t sup = i > 0 ? start[j] : -1;
+      double best = diag;
+      int32_t st = sdiag;
+      if (up < best) best = up, st = sup;
+      if (left < best) best = left, st = sleft;
+      if (i == 0) best = 0.0, st = j;
+      diag = up;
+      sdiag = sup;
+      left = (1.0 - dot) + best;
+      sleft = st;
+      row[j] = left;
+      start[j] = st;
+    }
+  }
+  int e = 0;
+  for (int j = 1; j < Lb; ++j)
+    if (row[j] < row[e]) e = j;
+  span[0] = start[e];
+  span[1] = e + 1;
+  return (float)(row[e] / (double)La);
+}
+
+// msocr_dtw_subsequence_host after its argument check: a gated-out pair is +inf and (-1, -1) without arithmetic
+inline void ws_dtw_sub_host(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                            const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, int32_t* span) {
+  std::vector<double> row((size_t)T);
+  std::vector<int32_t> start((size_t)T);
+  for (int q = 0; q < Q; ++q)
+    for (int n = 0; n < N; ++n) {
+      const int Ln = c_len[n];
+      const size_t at = (size_t)q * N + n;
+      dist[at] = std::numeric_limits<float>::infinity();
+      span[2 * at] = span[2 * at + 1] = -1;
+      if (Ln >= len_lo[q] && Ln <= len_hi[q])
+        dist[at] = ws_dtw_sub_pair_host(q_unit + (size_t)q * T * H, q_len[q], c_unit + (size_t)n * T * H, Ln, H, row.data(), start.data(),
+                                        span + 2 * at);
     }
 }
 

@@ -1,8 +1,8 @@
-// word_spotting.hip — msocr_frame_normalize, msocr_dtw_distances, msocr_topk_smallest and their host twins (include/msocr.h, "word
-// spotting").  The definition in f64, the frame rule, the ordering key and the argument checks are
-// csrc/word_spotting.h.
+// word_spotting.hip — msocr_frame_normalize, msocr_dtw_distances, msocr_dtw_subsequence, msocr_topk_smallest and their host twins
+// (include/msocr.h, "word spotting"; DESIGN.md sections 4.25 and 4.28).  The definitions in f64, the frame rule, the ordering key and
+// the argument checks are csrc/word_spotting.h.
 //
-// Three kernels:
+// Four kernels:
 //   normalize  one wave per frame: lane l sums the squares of elements l, l + 64, .. (fmaf), a butterfly folds the 64 partials, every
 //              lane divides its own elements by the root.  Frames at or beyond a word's length are written as zeros and not read.
 //   dtw        a workgroup of four waves owns MSOCR_SPOT_TILE = 4 corpus words, one per wave, and walks all queries (the queries of
@@ -20,6 +20,9 @@
 //              The word frames are NOT staged in LDS: one word of the envelope's largest shape is 128 KB, and at T = 33, H = 256
 //              four words (135 KB) beside the cost tiles leave one workgroup per CU.  Both operands come through L1 / L2 instead;
 //              the corpus leaves HBM once per grid row of queries.
+//   dtw_sub    the subsequence form on dtw's grid, cost tile (one copy of the product-and-store part, ws_cost_tile) and LDS
+//              discipline: row 0 starts afresh in every column, every lane carries the start column of its cell's path beside the
+//              value (a second DPP move per step), lane Lq - 1 keeps the first smallest cell of the last row with its end and start.
 //   topk       one workgroup per query: a radix select over the ordering key (four passes of 8 bits, LDS histogram) finds the key
 //              of rank k among the finite entries; one more pass gathers everything below it and, walking in index order, the first
 //              entries equal to it; a bitonic sort of the at most 256 (key, index) pairs in LDS orders them.  Comparisons only, so
@@ -91,7 +94,40 @@ __device__ __forceinline__ float ws_from_lane_below(float x, float first) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(x), 0x138, 0xf, 0xf, false));
 }
 
+// lane i's start column of lane i - 1 (lane 0: `first`): the same move on the integer the subsequence walk carries beside its value
+__device__ __forceinline__ int ws_int_from_lane_below(int x, int first) {
+  return __builtin_amdgcn_update_dpp(first, x, 0x138, 0xf, 0xf, false);
+}
+
 constexpr int WS_KGROUP = 32;  // elements of K per trip of the product loop: four 16-byte loads per operand row in flight at once
+
+// The cost tile of one pair, for both table walks: one 32 x 32 block at a time (one accumulator: the registers this saves are waves
+// per SIMD, and most pairs of words are one block); a lane's row of A / B beyond the length is fed as zeros and never read.  qbase /
+// wbase: the pair's frames + 4 (lane >> 5); r = lane & 31.  The caller orders the wave's LDS traffic around it.
+__device__ __forceinline__ void ws_cost_tile(float* __restrict__ tile, const float* __restrict__ qbase, const float* __restrict__ wbase,
+                                             int Lq, int Ln, int H, int P, int r) {
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  for (int mb = 0; mb < Lq; mb += 32)
+    for (int nb = 0; nb < Ln; nb += 32) {
+      const float* pa = mb + r < Lq ? qbase + (size_t)(mb + r) * H : nullptr;
+      const float* pb = nb + r < Ln ? wbase + (size_t)(nb + r) * H : nullptr;
+      f32x16 acc = {0};
+      for (int k = 0; k < H; k += WS_KGROUP) {  // H is a multiple of 64
+        f32x4 av[WS_KGROUP / 8], bv[WS_KGROUP / 8];
+#pragma unroll
+        for (int u = 0; u < WS_KGROUP / 8; ++u) {
+          av[u] = pa ? *reinterpret_cast<const f32x4*>(pa + k + 8 * u) : zero4;
+          bv[u] = pb ? *reinterpret_cast<const f32x4*>(pb + k + 8 * u) : zero4;
+        }
+#pragma unroll
+        for (int u = 0; u < WS_KGROUP / 8; ++u) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][e], bv[u][e], acc, 0, 0, 0);
+        }
+      }
+      ws_store_block(tile, acc, mb, nb + r, Lq, Ln, P);
+    }
+}
 
 // grid (tiles of MSOCR_SPOT_TILE words, query rows), 256 threads, dynamic LDS: WS_WAVES cost tiles of T rows at a pitch of P floats
 // (T rounded up to even: lane i reads word (P - 1) i + s at step s, and an odd stride puts 64 lanes on 64 banks)
@@ -110,7 +146,6 @@ __global__ __launch_bounds__(WS_THREADS) void ws_dtw_kernel(const float* __restr
   const bool word_ok = Ln >= 1 && Ln <= T;
   const float inf = __builtin_inff();
   const float* wbase = c_unit + (size_t)n * T * H + 4 * half;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   for (int q = blockIdx.y; q < Q; q += gridDim.y) {
     const int Lq = __builtin_amdgcn_readfirstlane(q_len[q]);
     float* out = dist + (size_t)q * N + n;
@@ -118,30 +153,8 @@ __global__ __launch_bounds__(WS_THREADS) void ws_dtw_kernel(const float* __restr
       if (lane == 0) *out = inf;
       continue;
     }
-    const float* qbase = q_unit + (size_t)q * T * H + 4 * half;
     ws_wave_lds_order();  // the table walk of the pair before this one has read the tile
-    // one 32 x 32 block of the cost tile at a time (one accumulator: the registers this saves are waves per SIMD, and most pairs of
-    // words are one block); a lane's row of A / B beyond the length is fed as zeros and never read
-    for (int mb = 0; mb < Lq; mb += 32)
-      for (int nb = 0; nb < Ln; nb += 32) {
-        const float* pa = mb + r < Lq ? qbase + (size_t)(mb + r) * H : nullptr;
-        const float* pb = nb + r < Ln ? wbase + (size_t)(nb + r) * H : nullptr;
-        f32x16 acc = {0};
-        for (int k = 0; k < H; k += WS_KGROUP) {  // H is a multiple of 64
-          f32x4 av[WS_KGROUP / 8], bv[WS_KGROUP / 8];
-#pragma unroll
-          for (int u = 0; u < WS_KGROUP / 8; ++u) {
-            av[u] = pa ? *reinterpret_cast<const f32x4*>(pa + k + 8 * u) : zero4;
-            bv[u] = pb ? *reinterpret_cast<const f32x4*>(pb + k + 8 * u) : zero4;
-          }
-#pragma unroll
-          for (int u = 0; u < WS_KGROUP / 8; ++u) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][e], bv[u][e], acc, 0, 0, 0);
-          }
-        }
-        ws_store_block(tile, acc, mb, nb + r, Lq, Ln, P);
-      }
+    ws_cost_tile(tile, q_unit + (size_t)q * T * H + 4 * half, wbase, Lq, Ln, H, P, r);
     ws_wave_lds_order();
     // the wavefront: lane i = row i; d1 = this row's cell of the step before (its left neighbour now)
     const int i = lane;
@@ -158,6 +171,70 @@ __global__ __launch_bounds__(WS_THREADS) void ws_dtw_kernel(const float* __restr
       d1 = cell ? c + best : inf;
     }
     if (i == Lq - 1) *out = d1 / (float)(Lq + Ln);
+  }
+}
+
+// The subsequence form on ws_dtw_kernel's grid, cost tile and LDS discipline: the walk alone differs.  Lane i carries, beside its
+// row's last value, the column at which that cell's path left row 0; both come from lane i - 1 by one DPP move each, the diagonal
+// pair is the upper pair of the step before.  Row 0 starts afresh in every column (best = 0, start = j).  Among equal predecessors
+// the diagonal wins, then the upper, then the left: strict < in that order, as the host twin compares.  Lane Lq - 1 sees its Ln
+// cells in ascending j and keeps the first smallest one with its end and start.  span [Q][N][2].
+__global__ __launch_bounds__(WS_THREADS) void ws_dtw_sub_kernel(const float* __restrict__ q_unit, const int32_t* __restrict__ q_len,
+                                                                const int32_t* __restrict__ len_lo, const int32_t* __restrict__ len_hi,
+                                                                int Q, const float* __restrict__ c_unit, const int32_t* __restrict__ c_len,
+                                                                int N, int T, int H, int P, float* __restrict__ dist,
+                                                                int32_t* __restrict__ span) {
+  extern __shared__ float tiles[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int r = lane & 31, half = lane >> 5;
+  float* tile = tiles + (size_t)wave * T * P;
+  const int64_t n64 = (int64_t)blockIdx.x * WS_WAVES + wave;
+  if (n64 >= N) return;  // no block-wide barrier below
+  const int n = (int)n64;
+  const int Ln = __builtin_amdgcn_readfirstlane(c_len[n]);
+  const bool word_ok = Ln >= 1 && Ln <= T;
+  const float inf = __builtin_inff();
+  const float* wbase = c_unit + (size_t)n * T * H + 4 * half;
+  for (int q = blockIdx.y; q < Q; q += gridDim.y) {
+    const int Lq = __builtin_amdgcn_readfirstlane(q_len[q]);
+    const size_t at = (size_t)q * N + n;
+    if (!word_ok || Lq < 1 || Lq > T || Ln < len_lo[q] || Ln > len_hi[q]) {  // the gate: no arithmetic
+      if (lane == 0) {
+        dist[at] = inf;
+        span[2 * at] = -1;
+        span[2 * at + 1] = -1;
+      }
+      continue;
+    }
+    ws_wave_lds_order();  // the table walk of the pair before this one has read the tile
+    ws_cost_tile(tile, q_unit + (size_t)q * T * H + 4 * half, wbase, Lq, Ln, H, P, r);
+    ws_wave_lds_order();
+    const int i = lane;
+    float d1 = inf, up_prev = inf, low = inf;  // low / low_end / low_start: the last row's running minimum (lane Lq - 1 alone)
+    int st1 = -1, ups_prev = -1, low_end = -1, low_start = -1;
+    const int steps = Lq + Ln - 1;
+    for (int s = 0; s < steps; ++s) {
+      const int j = s - i;
+      const float up = ws_from_lane_below(d1, inf);  // row 0 has no upper neighbour
+      const int ups = ws_int_from_lane_below(st1, -1);
+      const bool cell = i < Lq && j >= 0 && j < Ln;
+      const float c = cell ? tile[i * P + j] : 0.f;
+      float best = up_prev;
+      int st = ups_prev;
+      if (up < best) best = up, st = ups;
+      if (d1 < best) best = d1, st = st1;
+      if (i == 0) best = 0.f, st = j;  // the free start
+      up_prev = up;
+      ups_prev = ups;
+      d1 = cell ? c + best : inf;
+      st1 = st;
+      if (cell && d1 < low) low = d1, low_end = j, low_start = st;
+    }
+    if (i == Lq - 1) {
+      dist[at] = low / (float)Lq;
+      span[2 * at] = low_start;
+      span[2 * at + 1] = low_end < 0 ? -1 : low_end + 1;  // no cell below +inf: only frames that are not unit frames do that
+    }
   }
 }
 
@@ -276,6 +353,19 @@ __global__ __launch_bounds__(WS_THREADS) void ws_topk_kernel(const float* __rest
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// the grid of both pair kernels, and the pitch of their LDS tiles
+int ws_pair_grid(int Q, int N, int T, dim3* grid, int* P) {
+  int cu = 0, rc;
+  if ((rc = msocr_internal_cu_count(&cu)) != MSOCR_OK) return rc;
+  // grid rows share the queries when the corpus alone leaves CUs without work: about four workgroups per CU
+  const int64_t tiles = ((int64_t)N + WS_WAVES - 1) / WS_WAVES;
+  int64_t rows = ((int64_t)cu * 4 + tiles - 1) / tiles;
+  rows = rows < 1 ? 1 : rows > Q ? Q : rows > 65535 ? 65535 : rows;
+  *grid = dim3((unsigned)tiles, (unsigned)rows);
+  *P = (T + 1) & ~1;  // at most 64: WS_WAVES tiles are at most 64 KB of dynamic LDS, inside the default limit
+  return MSOCR_OK;
+}
+
 }  // namespace
 
 extern "C" int msocr_frame_normalize(const float* feat, const int32_t* len, int N, int T, int H, float* unit_out, void* stream) {
@@ -301,15 +391,11 @@ extern "C" int msocr_dtw_distances(const float* q_unit, const int32_t* q_len, co
   if (!ws_shape_ok(Q, T, H) || !ws_shape_ok(N, T, H)) return MSOCR_E_ARG;
   if (!q_unit || !q_len || !len_lo || !len_hi || !c_unit || !c_len || !dist || !aligned16(q_unit) || !aligned16(c_unit)) return MSOCR_E_ARG;
   if (Q == 0 || N == 0) return MSOCR_OK;
-  int cu = 0, rc;
-  if ((rc = msocr_internal_cu_count(&cu)) != MSOCR_OK) return rc;
-  // grid rows share the queries when the corpus alone leaves CUs without work: about four workgroups per CU
-  const int64_t tiles = ((int64_t)N + WS_WAVES - 1) / WS_WAVES;
-  int64_t rows = ((int64_t)cu * 4 + tiles - 1) / tiles;
-  rows = rows < 1 ? 1 : rows > Q ? Q : rows > 65535 ? 65535 : rows;
-  const int P = (T + 1) & ~1;  // at most 64: WS_WAVES tiles are at most 64 KB of dynamic LDS, inside the default limit
-  MSOCR_LAUNCH(ws_dtw_kernel, dim3((unsigned)tiles, (unsigned)rows), dim3(WS_THREADS), (size_t)WS_WAVES * T * P * sizeof(float),
-               (hipStream_t)stream, q_unit, q_len, len_lo, len_hi, Q, c_unit, c_len, N, T, H, P, dist);
+  dim3 grid;
+  int P, rc;
+  if ((rc = ws_pair_grid(Q, N, T, &grid, &P)) != MSOCR_OK) return rc;
+  MSOCR_LAUNCH(ws_dtw_kernel, grid, dim3(WS_THREADS), (size_t)WS_WAVES * T * P * sizeof(float), (hipStream_t)stream, q_unit, q_len, len_lo,
+               len_hi, Q, c_unit, c_len, N, T, H, P, dist);
   return LAUNCH_OK();
 }
 
@@ -322,6 +408,34 @@ extern "C" int msocr_dtw_distances_host(const float* q_unit, const int32_t* q_le
     if (len_lo[q] > len_hi[q]) return MSOCR_E_ARG;
   try {
     ws_dtw_host(q_unit, q_len, len_lo, len_hi, Q, c_unit, c_len, N, T, H, dist);
+  } catch (const std::bad_alloc&) {
+    return MSOCR_E_ARG;
+  }
+  return MSOCR_OK;
+}
+
+extern "C" int msocr_dtw_subsequence(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                                     const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, int32_t* span,
+                                     void* stream) {
+  if (!ws_sub_args_ok(q_unit, q_len, len_lo, len_hi, Q, c_unit, c_len, N, T, H, dist, span) || !aligned16(q_unit) || !aligned16(c_unit))
+    return MSOCR_E_ARG;
+  if (Q == 0 || N == 0) return MSOCR_OK;
+  dim3 grid;
+  int P, rc;
+  if ((rc = ws_pair_grid(Q, N, T, &grid, &P)) != MSOCR_OK) return rc;
+  MSOCR_LAUNCH(ws_dtw_sub_kernel, grid, dim3(WS_THREADS), (size_t)WS_WAVES * T * P * sizeof(float), (hipStream_t)stream, q_unit, q_len,
+               len_lo, len_hi, Q, c_unit, c_len, N, T, H, P, dist, span);
+  return LAUNCH_OK();
+}
+
+extern "C" int msocr_dtw_subsequence_host(const float* q_unit, const int32_t* q_len, const int32_t* len_lo, const int32_t* len_hi, int Q,
+                                          const float* c_unit, const int32_t* c_len, int N, int T, int H, float* dist, int32_t* span) {
+  if (!ws_sub_args_ok(q_unit, q_len, len_lo, len_hi, Q, c_unit, c_len, N, T, H, dist, span)) return MSOCR_E_ARG;
+  if (!ws_lens_ok(q_len, Q, T) || !ws_lens_ok(c_len, N, T)) return MSOCR_E_ARG;
+  for (int q = 0; q < Q; ++q)
+    if (len_lo[q] > len_hi[q]) return MSOCR_E_ARG;
+  try {
+    ws_dtw_sub_host(q_unit, q_len, len_lo, len_hi, Q, c_unit, c_len, N, T, H, dist, span);
   } catch (const std::bad_alloc&) {
     return MSOCR_E_ARG;
   }

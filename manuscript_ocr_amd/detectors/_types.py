@@ -146,6 +146,19 @@ class SpotHit(BaseModel):
     text: Optional[str] = Field(None, description="the indexed word's text, if it has one")
 
 
+class PartSpotHit(SpotHit):
+    """A SpotHit of a partial search (WordIndex.spot(..., partial=True)): the query was matched against a stretch of the word's
+    frames (msocr_dtw_subsequence), and the hit says which.  Nothing constrains the stretch's length: a query may collapse onto one
+    frame of the word."""
+
+    distance: float = Field(..., description="subsequence DTW distance: the cost of the best path from the query's first frame to its "
+                                             "last, starting and ending anywhere in the word, divided by the QUERY's length")
+    frame_start: int = Field(..., description="first frame of the word the query was matched to", ge=0)
+    frame_end: int = Field(..., description="one past the last such frame", ge=1)
+    fraction: Tuple[float, float] = Field(..., description="(frame_start / L, frame_end / L) for the word's L frames: where along "
+                                                           "the word the match lies")
+
+
 class Block(BaseModel):
     """A group of words; the detector emits exactly one block per page."""
 

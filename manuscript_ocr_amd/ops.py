@@ -1475,6 +1475,35 @@ def dtw_distances(q_unit, q_len, len_lo, len_hi, c_unit, c_len, out=None):
     return out
 
 
+def dtw_subsequence(q_unit, q_len, len_lo, len_hi, c_unit, c_len, out=None, span_out=None):
+    """msocr_dtw_subsequence: the subsequence DTW distance of every query to every indexed word (arguments as `dtw_distances`): the
+    query may start and end anywhere inside the word -> (d f32 [Q, N], the path's cost divided by the QUERY's length; span int32
+    [Q, N, 2], the word frames [start, end) it matched).  +inf and (-1, -1) where the word's length lies outside [len_lo[q],
+    len_hi[q]].  Nothing is read back or waited for."""
+    _ws_feat_dev(q_unit, "q_unit")
+    _ws_feat_dev(c_unit, "c_unit")
+    Q, T, H = q_unit.shape
+    N = c_unit.shape[0]
+    if tuple(c_unit.shape[1:]) != (T, H) or c_unit.device != q_unit.device:
+        raise ValueError("queries and corpus share T, H and the device")
+    for x, n, what in ((q_len, Q, "q_len"), (len_lo, Q, "len_lo"), (len_hi, Q, "len_hi"), (c_len, N, "c_len")):
+        _ws_i32_dev(x, n, q_unit, what)
+    if out is None:
+        out = torch.empty((Q, N), dtype=torch.float32, device=q_unit.device)
+    elif tuple(out.shape) != (Q, N) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q_unit.device:
+        raise TypeError("out is a dense float32 tensor [Q, N] on the features' device")
+    if span_out is None:
+        span_out = torch.empty((Q, N, 2), dtype=torch.int32, device=q_unit.device)
+    elif (tuple(span_out.shape) != (Q, N, 2) or span_out.dtype != torch.int32 or not span_out.is_contiguous()
+          or span_out.device != q_unit.device):
+        raise TypeError("span_out is a dense int32 tensor [Q, N, 2] on the features' device")
+    with torch.cuda.device(q_unit.device):
+        pad = torch.empty(4, dtype=torch.float32, device=q_unit.device)
+        p = [_ws_ptr(t, pad) for t in (q_unit, q_len, len_lo, len_hi, c_unit, c_len, out, span_out)]
+        nat.check(nat.lib().msocr_dtw_subsequence(p[0], p[1], p[2], p[3], Q, p[4], p[5], N, T, H, p[6], p[7], _stream()), "dtw_subsequence")
+    return out, span_out
+
+
 def topk_smallest(dist, k):
     """msocr_topk_smallest: per row of dist (f32 [Q, N] on the device) the k smallest finite values ascending, ties by ascending index
     -> (idx int32 [Q, k], val f32 [Q, k]) on the device; unused slots hold -1 / +inf."""
@@ -1536,6 +1565,23 @@ def dtw_distances_host(q_unit, q_len, len_lo, len_hi, c_unit, c_len):
     p = [_ws_hptr(x) for x in (q_unit, q_len, len_lo, len_hi, c_unit, c_len, out)]
     nat.check(nat.lib().msocr_dtw_distances_host(p[0], p[1], p[2], p[3], Q, p[4], p[5], N, T, H, p[6]), "dtw_distances_host")
     return out
+
+
+def dtw_subsequence_host(q_unit, q_len, len_lo, len_hi, c_unit, c_len):
+    """The CPU twin of `dtw_subsequence` (msocr_dtw_subsequence_host): every product, sum and table entry in f64, one rounding to
+    f32 -> (d f32 [Q, N], span int32 [Q, N, 2]).  It refuses lengths outside [1, T] and len_lo > len_hi."""
+    q_unit, c_unit = _ws_feat_host(q_unit, "q_unit"), _ws_feat_host(c_unit, "c_unit")
+    Q, T, H = q_unit.shape
+    N = c_unit.shape[0]
+    if tuple(c_unit.shape[1:]) != (T, H):
+        raise ValueError("queries and corpus share T and H")
+    q_len, len_lo, len_hi = (_ws_i32_host(x, Q, w) for x, w in ((q_len, "q_len"), (len_lo, "len_lo"), (len_hi, "len_hi")))
+    c_len = _ws_i32_host(c_len, N, "c_len")
+    out = np.empty((Q, N), dtype=np.float32)
+    span = np.empty((Q, N, 2), dtype=np.int32)
+    p = [_ws_hptr(x) for x in (q_unit, q_len, len_lo, len_hi, c_unit, c_len, out, span)]
+    nat.check(nat.lib().msocr_dtw_subsequence_host(p[0], p[1], p[2], p[3], Q, p[4], p[5], N, T, H, p[6], p[7]), "dtw_subsequence_host")
+    return out, span
 
 
 def topk_smallest_host(dist, k):

@@ -149,7 +149,8 @@ class EastNet:
 
         bb = "backbone.extractor."
         w, b = conv_bn(bb + "conv1", bb + "bn1")
-        P["stem"] = (pack_stem_weight(w, 32).to(dtype).to(self.device), b.to(self.device))
+        # split=False marks the packed stem too (K = 7 * 32, 64 channels: conv2d would otherwise split it on first use)
+        P["stem"] = (ops.attach_split(pack_stem_weight(w, 32).to(dtype).to(self.device), split), b.to(self.device))
         for lname, planes, blocks, stride in LAYERS:
             for i in range(blocks):
                 p = f"{bb}{lname}.{i}."
